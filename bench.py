@@ -28,6 +28,11 @@ process -- before anything touches a GPU -- and forwards the child's JSON line.
               measured period of a pass (solves stopped after 1 and 2 iterations).
 * cpu_baseline = the CPU oracle ("port": restatement of the reference algorithm, NOT BLASFEO
               HIGH_PERFORMANCE) on the same workload, min over repetitions, rank 0 at N=1 only.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, dtype and the
+counts of the timed solves).  Everything else -- roofline (event-timed solves), max_kkt_residual, critical_path, the
+batched sweep, cpu_baseline and, for N > 1 in batch mode, the sharded leg -- runs only with `--full`.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float64; see dump_outputs).
 """
 from __future__ import annotations
 
@@ -167,6 +172,31 @@ def dumps(obj) -> str:
     return json.dumps(clean(obj), allow_nan=False)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(outdir: str, mirrors, results) -> None:
+    """What a caller of the timed path receives after its last step, as <outdir>/<name>.npy (float64): the solution arrays of every
+    tree of the step (x, u, lam, mu_x, mu_u, dlam; concatenated over the trees in order) and `verdict`, one row per tree
+    (status, iter, ls_total, ls_last).  Above 64 MB in all, an array is cut to a fixed, seeded sample of its entries
+    (<name>_index.npy holds the indices kept), the same for every run with the same arguments."""
+    sols = [m.solution() for m in mirrors]
+    arrays = {k: np.concatenate([s[k] for s in sols]).astype(np.float64) for k in sols[0]}
+    arrays["verdict"] = np.array([[r[k] for k in ("status", "iter", "ls_total", "ls_last")] for r in results], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        keep = 0.45 * DUMP_CAP_BYTES / total          # each sampled entry also stores its index; room for the file headers
+        for k in [k for k in arrays if arrays[k].ndim == 1]:
+            a = arrays[k]
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, int(a.size * keep)), replace=False))
+            arrays[k] = a[idx]
+            arrays[k + "_index"] = idx.astype(np.float64)
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without the launcher: start it as a child BEFORE any HIP / torch.cuda call and forward its line."""
     port = 29500 + (os.getpid() % 2000)
@@ -255,6 +285,9 @@ def main():
     ap.add_argument("--strict-sharded", action="store_true", help="N > 1: exit with code 3 (after the JSON line has been printed) when the sharded leg failed; by default the exit code is 0 "
                                                                     "because the replicas' line is complete and valid -- `sharded_ok` at the top level of the line is the field to read")
     ap.add_argument("--trees", type=int, default=1, help="independent trees per GPU solved by one batched call per step (throughput mode; default 1 = the latency metric)")
+    ap.add_argument("--full", action="store_true", help="also the legs beside the headline: roofline (event-timed solves), KKT residual, critical path, batched sweep, "
+                                                        "CPU baseline, and for N > 1 in batch mode the sharded leg (--no-cpu-baseline / --no-batched drop two of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -340,26 +373,34 @@ def main():
         # the K steps as the reference's drivers run their NREP solves: a loop in C (tqgpu_solve_n), every solve waiting for its
         # verdict (status, iteration count) before the next starts -- the solver is timed, not this interpreter
         r, iters, ls, launches = g.solve_n(args.steps, **opts)
+        last = [r]
     else:
         # a batch per step: the same loop in C (tqgpu_solve_batch_n): every call returns when the verdict of every tree is on the host
         rs_, iters, ls, launches = capi.solve_batch_n(mirrors, args.steps, **opts)
         r = rs_[0]
+        last = rs_
     for m in mirrors:
         m.device_times(1)                 # synchronises: all K solves are complete (state written back)
     barrier()
     elapsed = time.perf_counter() - t0
     if r["status"] != 0:
         raise SystemExit(f"solver status {r['status']}")
-    # roofline leg: the same solves with one HIP event pair per launch on the solver's stream
-    for m in mirrors:
-        m.event_timing(True)
-    ev_steps = max(1, min(args.steps, 256))
-    for _ in range(3):
-        solve_step()
-    ev_iters = 0
-    for _ in range(ev_steps):
-        ev_iters += solve_step()[0]
-    dev_time = float(g.device_times(ev_steps).sum())
+    if args.dump_outputs:
+        if shard:
+            g.shard_gather_solution()     # (collective: every rank)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, mirrors, last)
+    if args.full:
+        # roofline leg: the same solves with one HIP event pair per launch on the solver's stream
+        for m in mirrors:
+            m.event_timing(True)
+        ev_steps = max(1, min(args.steps, 256))
+        for _ in range(3):
+            solve_step()
+        ev_iters = 0
+        for _ in range(ev_steps):
+            ev_iters += solve_step()[0]
+        dev_time = float(g.device_times(ev_steps).sum())
 
     tot_iters, tmax = float(iters), elapsed
     if dist is not None:
@@ -371,19 +412,40 @@ def main():
         tmax = float(t.item())
         # batch: every rank solved its own tree; shard: all ranks worked on the same iterations
         tot_iters = float(n.item()) if not shard else float(iters)
-    if shard:
+    if shard and args.full:
         g.shard_gather_solution()
 
     out = None
     if rank == 0:
         n_trees = len(mirrors)
+        it_per_solve = iters / args.steps / n_trees
+        ls_per_iter = ls / max(iters, 1)
+        out = {
+            "metric": "dual_newton_iterations_per_second",
+            "value": tot_iters / tmax,
+            "unit": "newton_iter/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * tmax / args.steps,
+            "higher_is_better": True,
+            "scaling": "strong" if shard else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": f"{args.workload}: {desc}", "nodes": int(sum(w["nodes"] for w in items)), "newton_iter_per_solve": it_per_solve,
+                       "ls_trials_per_iter": ls_per_iter, "ms_per_newton_iter": 1e3 * tmax / max(iters, 1),
+                       "kernel_launches_per_solve": launches / args.steps / n_trees, "trees_per_gpu": n_trees,
+                       "device_path": int(g.path),
+                       "parallelism": ("one tree sharded by subtrees, 2 RCCL all-gathers per Newton iteration" if shard else
+                                       "1 tree per GPU (independent scenario trees), no collective") if world > 1 else "single GPU"},
+        }
+    if rank == 0 and args.full:
         kkt = None
         if items[0]["qp"] is not None and n_trees == 1:
             qp = items[0]["qp"]
             qp.set_solution(g.solution())
             kkt = qp.max_kkt_res()
-        it_per_solve = iters / args.steps / n_trees
-        ls_per_iter = ls / max(iters, 1)
         # algorithmic bytes: bytes per Newton iteration (closed form, per tree) x the iterations of the launch
         n_ls = max(1, round(ls_per_iter))
         if len(mirrors) > 1:
@@ -413,26 +475,8 @@ def main():
             # every tree of the step in ONE launch: the batch kernels (a member's own path, taken when it is solved alone, does not matter here)
             kernel = ("f_persist_batch: one launch per step, every tree its own set of tier-subtree workgroups" if g.path == 2 else
                       "g_persist_batch: one launch per step, one workgroup per tree (all phases of all Newton iterations of the tree)")
-        out = {
-            "metric": "dual_newton_iterations_per_second",
-            "value": tot_iters / tmax,
-            "unit": "newton_iter/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * tmax / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if shard else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {desc}", "nodes": int(sum(w["nodes"] for w in items)), "newton_iter_per_solve": it_per_solve,
-                       "ls_trials_per_iter": ls_per_iter, "ms_per_newton_iter": 1e3 * tmax / max(iters, 1),
-                       "device_ms_per_newton_iter": 1e3 * dev_time / max(ev_iters, 1),
-                       "kernel_launches_per_solve": launches / args.steps / n_trees, "max_kkt_residual": kkt, "trees_per_gpu": n_trees,
-                       "device_path": int(g.path),
-                       "parallelism": ("one tree sharded by subtrees, 2 RCCL all-gathers per Newton iteration" if shard else
-                                       "1 tree per GPU (independent scenario trees), no collective") if world > 1 else "single GPU"},
+        out["config"].update({"device_ms_per_newton_iter": 1e3 * dev_time / max(ev_iters, 1), "max_kkt_residual": kkt})
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kernel,
                          "traffic_note": "memory-side bytes per launch (FETCH_SIZE raw + WRITE_SIZE) from profiles/traffic_<workload>.json; one launch = one solve",
@@ -440,7 +484,7 @@ def main():
                          "algorithmic_bytes_per_launch": bytes_step,
                          "algorithmic_bytes_per_iteration": bytes_it, "algorithmic_flops_per_iteration": flops_it,
                          "note": "latency-bound: a chain of dependent block factorisations per tree level; on the persistent paths state and constants are LDS-resident, so memory traffic is far below the algorithmic bytes"},
-        }
+        })
         if world == 1 and n_trees == 1 and g.path == 2 and not args.no_batched:
             # the dependent chain that bounds a solve, against its measured floors
             geo = g.geometry()
@@ -484,11 +528,11 @@ def main():
                 m.close()
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(items, opts)
-    # N > 1, batch mode: ALSO the configuration north_star names -- one C3 tree sharded by subtrees over the ranks (RCCL)
+    # N > 1, batch mode, --full: ALSO the configuration north_star names -- one C3 tree sharded by subtrees over the ranks (RCCL)
     # This leg comes LAST and under a deadline: the line of the replicas above is complete before it starts, and a communicator
     # that never comes up (the RCCL transport has not run on more than one device yet) costs the extra object, not the line.
     sharded = None
-    if world > 1 and not shard and (args.backend == "nccl" or os.environ.get("TREEQP_BENCH_SHARD_ANYWAY")):      # (a gloo rehearsal puts several ranks on one device, which RCCL refuses)
+    if world > 1 and not shard and args.full and (args.backend == "nccl" or os.environ.get("TREEQP_BENCH_SHARD_ANYWAY")):      # (a gloo rehearsal puts several ranks on one device, which RCCL refuses)
         import threading
         leg_done = threading.Event()
         deadline = float(os.environ.get("TREEQP_BENCH_SHARD_DEADLINE", "180"))

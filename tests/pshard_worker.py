@@ -25,10 +25,18 @@ def main():
     nx = np.full(p.Nn, p.nx, dtype=np.int32)
     nu = np.where(nk > 0, p.nu, 0).astype(np.int32)
     flat = capi.TreeQp(nx, nu, nk).fill_lti(p).flat()
-    ref_m = capi.TqGpu(nk, nx, nu).upload(flat, p.lambda0)
-    ref_r = ref_m.solve()
-    ref = ref_m.solution()
-    ref_m.close()
+    # the unsharded reference solves one rank after the other: the n processes share ONE device, n persistent launches of the
+    # whole tree (C3: 293 workgroups each) do not fit on it together, and a launch that cannot get all its workgroups resident
+    # is redone on the launch-per-tier path (tqgpu_timeouts), which is not bit-identical to the single launch compared against
+    for r in range(n):
+        if r == rank:
+            ref_m = capi.TqGpu(nk, nx, nu).upload(flat, p.lambda0)
+            ref_r = ref_m.solve()
+            ref = ref_m.solution()
+            ref_timeouts = capi.lib().tqgpu_timeouts(ref_m.h)
+            ref_m.close()
+        dist.barrier()
+    assert ref_timeouts == 0, ("the reference solve was redone on the launch-per-tier path", ref_timeouts, ref_r)
     g = capi.TqGpu(nk, nx, nu).upload(flat, p.lambda0)
     g.pshard_init(rank, n)
     handles = [None] * n

@@ -67,10 +67,9 @@ def test_product_does_not_link_oracle():
 def test_reference_examples_link_unchanged():
     """Drop-in boundary: the reference's own drivers compile and link UNCHANGED against our headers
     and library (build container only: the sources do not travel)."""
-    ref = Path("/root/reference")
-    if not ref.exists():
-        pytest.skip("/root/reference is not present on this box")
     from treeqp_amd import build
+    if not build.reference_available():
+        pytest.skip("the reference sources are not present, or not readable by this user")
     exes = build.build_reference_dropins()
     names = {e.name for e in exes}
     assert {"spring_mass_tdunes", "thesis_example"} <= names

@@ -29,7 +29,7 @@ for rnd in range(2):
         else:
             env.pop("TREEQP_AMD_LIB", None)
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", steps, "--warmup", "30", "--workload", workload,
-                            "--no-cpu-baseline", "--no-batched", "--trees", trees], env=env, capture_output=True, text=True, timeout=300)
+                            "--full", "--no-cpu-baseline", "--no-batched", "--trees", trees], env=env, capture_output=True, text=True, timeout=300)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if not line:
             print(f"{label:16s} FAILED rc={r.returncode} {r.stderr[-400:]}", flush=True)

@@ -1,14 +1,15 @@
 """profiles/traffic_<workload>.json (what bench.py's roofline.traffic reads) from the PMC summary of tools/evidence.sh:
-python tools/make_traffic.py r04_v1 C2 [C1 ...]  (reads gpurun_out/<tag>/<W>_pmc.txt and <W>_bench.json).
+python tools/make_traffic.py r04_v1 C2 [C1 ...]  (reads <W>_pmc.txt and <W>_bench.json in evidence/<tag>/, or $EVIDENCE_DIR/<tag>/).
 FETCH_SIZE / WRITE_SIZE are in KB per dispatch, from two separate --pmc passes (--kernel-trace only); FETCH_SIZE is left uncorrected
 (MI355X_MICROARCH.md: the gfx950 correction depends on the width of the loads, which is mixed here)."""
-import json, re, sys
+import json, os, re, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 tag = sys.argv[1]
+src = Path(os.environ.get("EVIDENCE_DIR", ROOT / "evidence")) / tag
 for w in sys.argv[2:]:
-    txt = (ROOT / "gpurun_out" / tag / f"{w}_pmc.txt").read_text()
-    bench = json.loads((ROOT / "gpurun_out" / tag / f"{w}_bench.json").read_text().strip().splitlines()[-1])
+    txt = (src / f"{w}_pmc.txt").read_text()
+    bench = json.loads((src / f"{w}_bench.json").read_text().strip().splitlines()[-1])
     rows = {}
     for line in txt.splitlines():
         m = re.match(r"(\S.*?)\s+(FETCH_SIZE|WRITE_SIZE)\s+dispatches\s+(\d+)\s+total\s+([\d.]+)\s+per dispatch\s+([\d.]+)", line)

@@ -7,8 +7,8 @@ wl=${2:-C2}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-BENCH="python3 bench.py --workload $wl --steps 200 --warmup 20 --no-cpu-baseline --no-batched"
-SHORT="python3 bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-batched"
+BENCH="python3 bench.py --full --workload $wl --steps 200 --warmup 20 --no-cpu-baseline --no-batched"
+SHORT="python3 bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-batched"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $BENCH > $out/stats.log 2>&1
 cp $(find $out/stats -name "*kernel_stats.csv" | head -1) $out/${wl}_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

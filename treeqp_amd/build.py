@@ -181,9 +181,17 @@ REF_EXAMPLES = {
 }
 
 
+def reference_available() -> bool:
+    """The reference checkout is there AND readable by this user (a build as another user may see it but not enter it)."""
+    try:
+        return REFERENCE.is_dir() and os.access(REFERENCE, os.R_OK | os.X_OK)
+    except OSError:
+        return False
+
+
 def build_reference_dropins(force: bool = False):
     """Compile the reference's UNCHANGED example drivers against our headers + library."""
-    if not REFERENCE.exists():
+    if not reference_available():
         return []
     outdir = ROOT / "oracle" / "_ref"
     outdir.mkdir(parents=True, exist_ok=True)
