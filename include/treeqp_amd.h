@@ -62,7 +62,7 @@ typedef struct tqgpu_opts {
 } tqgpu_opts;
 
 typedef struct tqgpu_result {
-    int status;                  /* return_t value: 0 optimal, 1 max iterations, 2 not a descent direction */
+    int status;                  /* return_t value: 0 optimal, 1 max iterations, 2 not a descent direction, 4 stage QP solve failed (box nodes) */
     int iter;                    /* Newton iterations */
     int ls_total;                /* total line-search trials */
     int ls_last;                 /* trials of the last iteration */
@@ -88,7 +88,14 @@ int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const double *Rd
  * S (nu x nx) column major, then q, r.  Bounds are ignored while it is selected. */
 int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const double *R, const double *S, const double *q, const double *r);
 /* the same with a per-node choice (opts->qp_solver[] of the reference, dual_Newton_tree.c:124-162): kind[k] = 0 clipping (the
- * diagonals of Q_k and R_k are the weights; off-diagonals and S_k must be zero), 1 dense unconstrained; NULL = all dense */
+ * diagonals of Q_k and R_k are the weights; off-diagonals and S_k must be zero), 1 dense unconstrained (bounds ignored),
+ * 2 dense with box bounds: the bounds of tqgpu_set_bounds apply (qpOASES QProblemB of the reference,
+ * dual_Newton_tree_qpoases.c:153-210, 312-358, 524-560: a hot-started active-set method on the bounds per node, one wave each,
+ * P_k = Z (Z'H_k Z)^-1 Z' of the final working set, multipliers of the bounds in mu_x / mu_u).  NULL = all kind 1.
+ * Kind 2 needs nx[k] + nu[k] <= 64 (TQGPU_EUNSUPPORTED otherwise) and lb <= ub on its entries (TQGPU_EINVAL from this call or
+ * from tqgpu_set_bounds, whichever makes it inconsistent).  A stage solve that does not finish ends tqgpu_solve with
+ * tqgpu_result.status = 4 (TREEQP_DN_STAGE_QP_SOLVE_FAILED).  Re-uploads between solves need no reset: the working sets
+ * kept for the hot start are only a starting guess. */
 int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const double *Q, const double *R, const double *S, const double *q, const double *r);
 int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const double *xmax, const double *umin, const double *umax);
 /* Everything above in one call (NULL = leave alone) plus the starting duals: compared with a pinned host mirror of

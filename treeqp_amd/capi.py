@@ -541,7 +541,8 @@ class TqGpu:
 
     def upload_mixed(self, p, kind, lambda0=None):
         """Per-node choice of the stage solver: kind[k] = 0 clipping (diagonal Q_k, R_k, S_k = 0, box bounds), 1 dense unconstrained
-        (full Q_k, R_k, S_k, bounds at infinity).  p holds A, B, b, Q, R, S (dense layout, column major), q, r and the bounds."""
+        (full Q_k, R_k, S_k, bounds ignored), 2 dense with box bounds (full Q_k, R_k, S_k, nx + nu <= 64, the bounds apply).
+        p holds A, B, b, Q, R, S (dense layout, column major), q, r and the bounds."""
         g = (lambda k: getattr(p, k)) if not isinstance(p, dict) else (lambda k: p[k])
         L = lib()
         keep = {k: _f64(g(k)) for k in ("A", "B", "b", "Q", "R", "S", "q", "r", "xmin", "xmax", "umin", "umax")}

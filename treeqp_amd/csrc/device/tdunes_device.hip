@@ -115,10 +115,14 @@ struct Data {            /* device pointers, passed by value */
      * per node the stage Hessian H = [Q S'; S R] ((nx+nu)^2, column major) and its inverse P = H^-1 */
     int strict;               /* TREEQP_AMD_STRICT_SUM=1: sums that feed decisions are taken in the reference's order (node by node, block by block), see strict_* below */
     int dense;                /* some nodes use the dense unconstrained stage solver */
-    const int *kind;          /* [Nn] per node: 0 clipping, 1 dense unconstrained (read only when dense != 0) */
+    const int *kind;          /* [Nn] per node: 0 clipping, 1 dense unconstrained, 2 dense with box bounds (read only when dense != 0) */
     const double *Hd;
     double *Pd;
     const int *poff;          /* [Nn+1] offsets of the (nx+nu)^2 blocks */
+    /* dense nodes with box bounds (kind 2, stage_box): [0, Nn) the working set of node k (bit i: entry i of [x | u] sits on a
+     * bound), kept across sweeps and solves as the hot start; [Nn, 2 Nn) the working set that P_k was last built for */
+    unsigned long long *bmask;
+    int xpad;                 /* phantom root states of an x0-eliminated tree embedded in a uniform one: unbounded in stage_box */
 };
 
 struct Opts {
@@ -246,6 +250,7 @@ __global__ void __launch_bounds__(WAVE) k_dense_init(Tree T, Data D) {
     const int k = blockIdx.x, lane = threadIdx.x;
     const int nz = T.nx[k] + T.nu[k];
     if (nz == 0 || !D.kind[k]) return;
+    if (D.kind[k] == 2 && lane == 0) D.bmask[T.Nn + k] = 0ull;      /* box nodes: P below is the one of the empty working set */
     const double *H = D.Hd + D.poff[k];
     double *P = D.Pd + D.poff[k];
     double *Lm = lds;                      /* nz x nz, ld = nz */
@@ -317,6 +322,165 @@ __device__ __forceinline__ double dot_batched(const double *a, int sa, const dou
 /* xu != nullptr (k_sg): x, u of a PARENT node are also posted as tagged words -- entry j of x at xu[2 (xoff + j)], of u at
  * xu[2 (sum_nx + uoff + j)] -- for the children's gradient in the same launch */
 /* Cl != nullptr (k_sgp): the children's [A | B], rows stacked child after child, column major with leading dimension ldcl, are in LDS */
+/* value of lane l (l uniform across the wave) to every lane */
+__device__ __forceinline__ double rdlane(double v, int lane) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+/* ------------------------------------------------------------------------------------------ */
+/* stage_box: the stage QP of a dense node with box bounds (kind 2) -- the qpOASES QProblemB   */
+/* solve of the reference (dual_Newton_tree_qpoases.c:312-358) and its elimination matrix      */
+/* (:153-210), as a primal active-set method on the bounds in one wave:                        */
+/*   z = argmin 1/2 z'Hz - hmod'z  s.t.  lb <= z <= ub,   P = Z (Z'HZ)^-1 Z'                     */
+/* Lane i owns entry i of z = [x | u] (nz <= 64).  H and the Cholesky factor of the working-set */
+/* matrix M (H with the rows and columns of fixed entries replaced by those of the identity:    */
+/* its factor is chol(H_FF) in place) live in LDS.  Hot start: the previous z projected onto   */
+/* the box, with the stored working set restricted to the bounds that point meets.  Each step  */
+/* solves M zn = [hmod_F - H_FA z_A ; z_A]; if zn leaves the box (or lands on a bound) the     */
+/* step stops at the first blocking bound (lowest index on ties), which joins the working set; */
+/* entries with equal bounds are always in it; otherwise the fixed                             */
+/* entry of lowest index whose multiplier has the wrong sign is released, or the solve is done. */
+/* Every decision is a wave-uniform ballot.  The returned z is the last zn, i.e. a function of  */
+/* the final working set alone (not of the path).  Multipliers: xUnc / uUnc keep hmod, from    */
+/* which k_export_box forms mu = hmod - Hz.  P is rebuilt only when the working set differs     */
+/* from the one P was built for.                                                                */
+/* ------------------------------------------------------------------------------------------ */
+#define BOX_MAX_STEPS(nz) (4 * (nz) + 8)
+__device__ void stage_box(const Tree &T, const Data &D, int k, int lane, double *lds, const double *hm, const double *lk, int ko, bool save_s) {
+    const int nxk = T.nx[k], nuk = T.nu[k], xo = T.xoff[k], uo = T.uoff[k], d = T.bdim[k];
+    const int nz = nxk + nuk;
+    double *dv = lds;                      /* nz: 1 / L_ii */
+    double *Hs = dv + nz;                  /* nz x nz, column major: H_k, later the columns of P */
+    double *Ls = Hs + (size_t)nz * nz;     /* nz x nz, column major: Cholesky factor of M */
+    const double *Hg = D.Hd + D.poff[k];
+    for (int e = lane; e < nz * nz; e += WAVE) Hs[e] = Hg[e];
+
+    const bool own = lane < nz, isx = lane < nxk;
+    const int j0 = isx ? lane : lane - nxk;
+    const double inf = __builtin_inf();
+    double lo = -inf, hi = inf, h = 0.0, z = 0.0;
+    if (own) {
+        const bool phantom = isx && k == 0 && lane < D.xpad;
+        if (!phantom) { lo = isx ? D.xmin[xo + j0] : D.umin[uo + j0]; hi = isx ? D.xmax[xo + j0] : D.umax[uo + j0]; }
+        h = hm[lane];
+        z = isx ? D.x[xo + j0] : D.u[uo + j0];
+        if (z != z) z = 0.0;
+        z = fmin(fmax(z, lo), hi);
+    }
+    const u64 bit = 1ull << lane;
+    bool fixed = own && (lo == hi || ((D.bmask[k] & bit) && (z == lo || z == hi)));      /* equal bounds: always in the working set */
+    u64 m = __builtin_amdgcn_ballot_w64(fixed);
+    WSYNC();
+
+    bool ok = false;
+    double hz = 0.0, habs = 0.0;           /* (H z)_i and sum_j |H_ij z_j| at the final z */
+    for (int step = 0; step < BOX_MAX_STEPS(nz); step++) {
+        WSYNC();
+        /* M and the right-hand side of the working set m */
+        double r = h;
+        for (int j = 0; j < nz; j++) {
+            const bool fj = (m >> j) & 1ull;
+            if (own) Ls[lane + (size_t)j * nz] = (fixed || fj) ? (lane == j ? 1.0 : 0.0) : Hs[lane + (size_t)j * nz];
+            if (fj) { const double zj = rdlane(z, j); r = fma(-Hs[lane < nz ? lane + (size_t)j * nz : 0], zj, r); }
+        }
+        if (fixed) r = z;
+        WSYNC();
+        /* Cholesky factor of M, left looking, lane i = row i */
+        bool pd = true;
+        for (int j = 0; j < nz; j++) {
+            if (own && lane >= j) {
+                double sacc = Ls[lane + (size_t)j * nz];
+                for (int c = 0; c < j; c++) sacc = fma(-Ls[lane + (size_t)c * nz], Ls[j + (size_t)c * nz], sacc);
+                Ls[lane + (size_t)j * nz] = sacc;
+            }
+            WSYNC();
+            const double cjj = Ls[j + (size_t)j * nz];
+            pd = pd && cjj > 0.0;
+            const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
+            if (own && lane >= j) Ls[lane + (size_t)j * nz] *= finv;
+            if (lane == 0) dv[j] = finv;
+            WSYNC();
+        }
+        if (!pd) break;                                        /* H_FF not positive definite: the stage QP has no solution here */
+        /* L L' zn = r */
+        for (int c = 0; c < nz; c++) {
+            const double yc = rdlane(r, c) * dv[c];
+            if (lane == c) r = yc;
+            else if (own && lane > c) r = fma(-Ls[lane + (size_t)c * nz], yc, r);
+        }
+        for (int c = nz - 1; c >= 0; c--) {
+            const double xc = rdlane(r, c) * dv[c];
+            if (lane == c) r = xc;
+            else if (lane < c) r = fma(-Ls[c + (size_t)lane * nz], xc, r);
+        }
+        const double zn = fixed ? z : (own ? r : 0.0);
+        /* the first bound the segment z -> zn meets; a free solution ON a bound fixes it too (inclusive, as clipping's
+         * `unc >= ub` / `unc <= lb`: on a diagonal node the working set is the clipping's active set, and so is P) */
+        const bool blk = own && !fixed && (zn <= lo || zn >= hi);
+        double a = 1.0;
+        if (blk) a = zn == z ? 0.0 : fmin(fmax((zn <= lo ? lo - z : hi - z) / (zn - z), 0.0), 1.0);
+        const u64 bm = __builtin_amdgcn_ballot_w64(blk);
+        if (bm) {
+            const double amin = -wmax(-a);
+            const u64 at = __builtin_amdgcn_ballot_w64(blk && a == amin);
+            const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(at));
+            if (own && !fixed) z = fmin(fmax(fma(amin, zn - z, z), lo), hi);
+            if (lane == i) { z = zn <= lo ? lo : hi; fixed = true; }
+            m |= 1ull << i;
+            continue;
+        }
+        z = zn;
+        /* multipliers of the fixed entries: g = H z - hmod >= 0 on a lower bound, <= 0 on an upper one */
+        hz = 0.0; habs = 0.0;
+        for (int j = 0; j < nz; j++) {
+            const double zj = rdlane(z, j), hij = Hs[lane < nz ? lane + (size_t)j * nz : 0];
+            hz = fma(hij, zj, hz);
+            habs = fma(fabs(hij), fabs(zj), habs);
+        }
+        const double g = hz - h, tol = 64.0 * __DBL_EPSILON__ * (habs + fabs(h));
+        const bool wrong = fixed && lo < hi && ((z == lo && g < -tol) || (z == hi && g > tol));
+        const u64 wm = __builtin_amdgcn_ballot_w64(wrong);
+        if (!wm) { ok = true; break; }
+        const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(wm));
+        if (lane == i) fixed = false;
+        m &= ~(1ull << i);
+    }
+    if (!ok && lane == 0) { D.ctrl->status = 4; D.ctrl->done = 1; }      /* TREEQP_DN_STAGE_QP_SOLVE_FAILED */
+    if (lane == 0) D.bmask[k] = m;
+    if (own) {
+        if (isx) { if (save_s) D.xUncS[xo + j0] = D.xUnc[xo + j0]; D.x[xo + j0] = z; D.xUnc[xo + j0] = h; }
+        else { if (save_s) D.uUncS[uo + j0] = D.uUnc[uo + j0]; D.u[uo + j0] = z; D.uUnc[uo + j0] = h; }
+    }
+    /* dual term -1/2 z'Hz + hmod'z - cmod, as the unconstrained dense branch takes it */
+    double p_quad = own ? z * hz : 0.0, p_lin = own ? h * z : 0.0, p_cd = 0.0;
+    for (int t = lane; t < d; t += WAVE) p_cd = fma(D.b[ko + t], lk[t], p_cd);
+    p_quad = wave_sum(p_quad); p_lin = wave_sum(p_lin); p_cd = wave_sum(p_cd);
+    if (lane == 0) D.fval[k] = -0.5 * p_quad - p_cd + p_lin;
+    if (!ok || m == D.bmask[T.Nn + k]) return;
+    /* P = M^-1 with the rows and columns of the working set zeroed: lane j solves L L' p_j = e_j into column j of Hs */
+    WSYNC();
+    if (own) {
+        double *col = Hs + (size_t)lane * nz;
+        for (int i = 0; i < nz; i++) {
+            double v = (i == lane && !fixed) ? 1.0 : 0.0;
+            for (int c = 0; c < i; c++) v = fma(-Ls[i + (size_t)c * nz], col[c], v);
+            col[i] = v * dv[i];
+        }
+        for (int i = nz - 1; i >= 0; i--) {
+            double v = col[i];
+            for (int c = i + 1; c < nz; c++) v = fma(-Ls[c + (size_t)i * nz], col[c], v);
+            col[i] = v * dv[i];
+        }
+    }
+    WSYNC();
+    double *P = D.Pd + D.poff[k];
+    for (int e = lane; e < nz * nz; e += WAVE) P[e] = Hs[e];
+    if (lane == 0) D.bmask[T.Nn + k] = m;
+}
+
+template <bool BOX = false>
 __device__ void stage_body(const Tree &T, const Data &D, int mode, int k, int lane, double *lds, bool batch = true, u64 *xu = nullptr, int sum_nx = 0, unsigned xtag = 0u,
                            const double *Cl = nullptr, int ldcl = 0) {
     const Ctrl *c = D.ctrl;
@@ -367,6 +531,9 @@ __device__ void stage_body(const Tree &T, const Data &D, int mode, int k, int la
             if (isx) D.qmod[xo + j] = v; else D.rmod[uo + j] = v;
         }
         WSYNC();
+        if constexpr (BOX) {
+            if (D.kind[k] == 2) { stage_box(T, D, k, lane, hm + nz, hm, lk, ko, save_s); return; }
+        }
         const double *P = D.Pd + D.poff[k], *H = D.Hd + D.poff[k];
         for (int t = lane; t < nz; t += WAVE) {
             double acc = 0.0;
@@ -469,6 +636,12 @@ __global__ void __launch_bounds__(WAVE) k_stage(Tree T, Data D, int mode, int h,
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
     stage_body(T, D, mode, blockIdx.x, threadIdx.x, lds);
+}
+/* k_stage for trees with dense box nodes (kind 2): the same sweep with stage_box compiled in (its LDS, s->lds_box, only here) */
+__global__ void __launch_bounds__(WAVE) k_stage_box(Tree T, Data D, int mode, int h, int t) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
+    stage_body<true>(T, D, mode, blockIdx.x, threadIdx.x, lds);
 }
 #endif
 
@@ -1314,6 +1487,10 @@ struct tqgpu_solver {
     bool w3_seen = false;               /* the last read of the control block came through the result block */
     std::vector<int> ls_pred;           /* trials per iteration of the previous solve: that many trial launches are enqueued behind an iteration's forward sweep (a trial beyond the accepted one is a no-op; a read-back per extra trial is 20 us) */
     bool dense = false, need_dense_init = false;   /* dense unconstrained stage solver selected (generic path only) */
+    bool box = false;            /* some dense nodes have box bounds (kind 2): the stage sweep is k_stage_box with lds_box bytes */
+    size_t lds_box = 0;
+    std::vector<int> h_kind;     /* the kinds last set (tqgpu_set_objective_mixed) */
+    std::vector<double> h_bounds; /* the bounds last set by tqgpu_set_bounds (device layout: xmin | xmax | umin | umax); empty: unknown */
     double *d_Hd = nullptr;      /* writable alias of Data.Hd */
     int *d_kind = nullptr;       /* writable alias of Data.kind */
     std::vector<int> poff;
@@ -1855,6 +2032,7 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, bool fast, int it, int t
         if (!done && s->w3_now) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
         if (!done) {
             if (s->fuse_now && !sharded) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
+            else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, it, t);
             else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, it, t);
         }
         launches++;
@@ -2171,7 +2349,9 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
     if (!ls_begun) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
     if (s->fuse_now) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
     else {
-        hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, h, 1); launches++;
+        if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, h, 1);
+        else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, h, 1);
+        launches++;
         hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, h, 1, 0); launches++;
     }
     mark(3);
@@ -2194,6 +2374,27 @@ __global__ void k_export_all(int n_x, int n_u, int n_lam, int x_pad, int nx0, Da
         const double *lc = lamc ? lamc : (D.ctrl->cur ? D.lam1 : D.lam0);      /* (enqueued behind a solve that is still running: the device knows) */
         ol[i] = lc[nx0 + i]; od[i] = D.dlam[nx0 + i];
     }
+}
+
+/* multipliers of the box nodes' bounds (export of the qpOASES stage solver, dual_Newton_tree_qpoases.c:524-560), over what
+ * k_export_all wrote for them: mu = hmod - H z with the reference's sign, on the working set; 0 on free entries.  On a
+ * MAXIMUM_ITERATIONS exit hmod is phase S's and z the last trial's, on every entry: the pairing of export_mu on clipping nodes
+ * (see Data::xUncS), and on a diagonal node the same numbers.  One wave per node, lane = entry. */
+__global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (!D.dense || D.kind[k] != 2) return;
+    const int nxk = T.nx[k], nz = nxk + T.nu[k], xo = T.xoff[k], uo = T.uoff[k];
+    if (lane >= nz || (k == 0 && lane < x_pad)) return;           /* (phantom root states are not exported) */
+    const bool maxit = D.ctrl->status == 1 && D.ctrl->iter > 0;
+    const bool isx = lane < nxk;
+    const int j0 = isx ? lane : lane - nxk;
+    const double *H = D.Hd + D.poff[k];
+    double hz = 0.0;
+    for (int j = 0; j < nz; j++) hz = fma(H[lane + (size_t)j * nz], j < nxk ? D.x[xo + j] : D.u[uo + j - nxk], hz);
+    const double h = isx ? (maxit ? D.xUncS : D.xUnc)[xo + j0] : (maxit ? D.uUncS : D.uUnc)[uo + j0];
+    const double mu = (maxit || ((D.bmask[k] >> lane) & 1ull)) ? h - hz : 0.0;
+    double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
+    if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
 }
 
 }  // namespace
@@ -2266,7 +2467,7 @@ extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *n
     const size_t o_lami = cv.take(SX * Dbl);
     s->poff.assign(Nn + 1, 0);
     for (int k = 0; k < Nn; k++) s->poff[k + 1] = s->poff[k] + (s->nx[k] + s->nu[k]) * (s->nx[k] + s->nu[k]);
-    const size_t o_kind = cv.take(Nn * I);
+    const size_t o_kind = cv.take(Nn * I), o_bmask = cv.take(2 * (size_t)Nn * sizeof(unsigned long long));
     const size_t o_poff = cv.take((Nn + 1) * I), o_Hd = cv.take((size_t)std::max(s->poff[Nn], 1) * Dbl), o_Pd = cv.take((size_t)std::max(s->poff[Nn], 1) * Dbl);
     const size_t o_ctrl = cv.take(sizeof(Ctrl));
     const size_t o_stamps = cv.take((8 * 32 * 2 + 1024) * sizeof(unsigned long long));   /* + 1024: placement census of the persistent launch (diagnostic builds) */
@@ -2332,6 +2533,7 @@ extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *n
     D.ctrl = at<Ctrl>(base, o_ctrl); D.ls_log = at<int>(base, o_log); D.ls_log_cap = s->ls_log_cap;
     D.strict = s->strict_sum ? 1 : 0;
     D.dense = 0; s->d_kind = at<int>(base, o_kind); D.kind = s->d_kind; s->d_Hd = at<double>(base, o_Hd); D.Hd = s->d_Hd; D.Pd = at<double>(base, o_Pd); D.poff = at<int>(base, o_poff);
+    D.bmask = at<unsigned long long>(base, o_bmask); D.xpad = s->x_pad;
     s->use_fast_orig = s->use_fast;
     s->d_mu_x = at<double>(base, o_mux); s->d_mu_u = at<double>(base, o_muu);
     s->d_lam_init = at<double>(base, o_lami);
@@ -2642,7 +2844,7 @@ extern "C" int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->need_init = true;
     s->need_pack = true;
-    if (s->dense) { s->dense = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; }
+    if (s->dense) { s->dense = false; s->box = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; }
     return TQGPU_OK;
 }
 
@@ -2657,7 +2859,24 @@ extern "C" int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const
 
 /* The same with a per-node choice of the stage solver (opts->qp_solver[] of the reference, dual_Newton_tree.c:124-162):
  * kind[k] = 0: clipping (the diagonals of Q_k, R_k are its weights; their off-diagonals and S_k must be zero), 1: dense
- * unconstrained.  kind == NULL: every node dense. */
+ * unconstrained, 2: dense with the box bounds of tqgpu_set_bounds (stage_box; nx + nu <= 64).  kind == NULL: every node
+ * dense unconstrained. */
+namespace {
+/* lb <= ub on every entry of every box node (the phantom root states are not the caller's) */
+int check_box_bounds(const tqgpu_solver *s) {
+    if (!s->box || s->h_bounds.empty()) return TQGPU_OK;
+    const double *xl = s->h_bounds.data(), *xu = xl + s->sum_nx, *ul = xu + s->sum_nx, *uu = ul + s->sum_nu;
+    for (int k = 0; k < s->Nn; k++) {
+        if (s->h_kind[(size_t)k] != 2) continue;
+        for (int i = (k == 0 ? s->x_pad : 0); i < s->nx[k]; i++)
+            if (!(xl[s->xoff[k] + i] <= xu[s->xoff[k] + i])) return fail(TQGPU_EINVAL, "box node " + std::to_string(k) + ": xmin > xmax");
+        for (int i = 0; i < s->nu[k]; i++)
+            if (!(ul[s->uoff[k] + i] <= uu[s->uoff[k] + i])) return fail(TQGPU_EINVAL, "box node " + std::to_string(k) + ": umin > umax");
+    }
+    return TQGPU_OK;
+}
+}  // namespace
+
 extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const double *Q, const double *R, const double *S, const double *q, const double *r) {
     SETTLE(s);
     if (!s || !Q || !q) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: bad arguments");
@@ -2666,7 +2885,26 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     std::vector<double> H((size_t)std::max(s->poff[s->Nn], 1), 0.0);
     std::vector<double> Qd((size_t)std::max(s->sum_nx, 1), 0.0), Rd((size_t)std::max(s->sum_nu, 1), 0.0);
     std::vector<int> kd((size_t)s->Nn, 1);
-    if (kind) for (int k = 0; k < s->Nn; k++) kd[(size_t)k] = kind[k] ? 1 : 0;
+    if (kind) for (int k = 0; k < s->Nn; k++) {
+        if (kind[k] < 0 || kind[k] > 2) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: kind must be 0, 1 or 2");
+        kd[(size_t)k] = kind[k];
+    }
+    size_t lds_box = 0;
+    for (int k = 0; k < s->Nn; k++) {
+        if (kd[(size_t)k] != 2) continue;
+        const size_t nz = (size_t)s->nx[k] + s->nu[k];
+        if (nz > WAVE) return fail(TQGPU_EUNSUPPORTED, "box node " + std::to_string(k) + ": nx + nu = " + std::to_string(nz) + " > 64 (one wave, one entry per lane)");
+        lds_box = std::max(lds_box, ((size_t)s->bdim[k] + s->nx[k] + 2 * nz + 2 * nz * nz + 2) * sizeof(double));
+    }
+    const bool box_was = s->box;
+    const std::vector<int> kind_was = s->h_kind;
+    s->box = lds_box > 0; s->h_kind = kd;
+    int rc = check_box_bounds(s);
+    if (rc == TQGPU_OK && s->box) {
+        s->lds_box = std::max(s->lds_stage, lds_box);
+        rc = allow_lds(k_stage_box, s->lds_box);
+    }
+    if (rc != TQGPU_OK) { s->box = box_was; s->h_kind = kind_was; return rc; }
     size_t oq = 0, orr = 0, os = 0;
     for (int k = 0; k < s->Nn; k++) {
         const int nu = s->nu[k], nz = s->nx[k] + nu;
@@ -2701,7 +2939,8 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     H2D(s->d_Hd, H.data(), s->poff[s->Nn]);
     HIP_TRY(hipMemcpyAsync(s->d_kind, kd.data(), sizeof(int) * (size_t)s->Nn, hipMemcpyHostToDevice, s->stream));      /* ints: not H2D (doubles) */
     H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
-    /* weights: zero on dense nodes (their multipliers of bounds are zero by construction), the diagonals on clipping nodes */
+    /* weights: zero on dense nodes (k_export_all writes zero multipliers for them; k_export_box those of the box nodes), the diagonals
+     * on clipping nodes */
     H2D(s->Qd, Qd.data(), s->sum_nx); H2D(s->Rd, Rd.data(), s->sum_nu);
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->dense = true; s->need_dense_init = true; s->D.dense = 1; s->need_init = true;
@@ -2714,6 +2953,16 @@ extern "C" int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const doubl
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
     s->in_valid = false;
+    if (xmin && xmax && umin && umax) {
+        /* keep what the box nodes' checks need (lb <= ub); refuse before anything is uploaded */
+        std::vector<double> hb((size_t)2 * s->sum_nx + 2 * (size_t)s->sum_nu, 0.0);
+        const size_t nxe = (size_t)(s->sum_nx - s->x_pad);
+        std::copy(xmin, xmin + nxe, hb.begin() + s->x_pad); std::copy(xmax, xmax + nxe, hb.begin() + s->sum_nx + s->x_pad);
+        std::copy(umin, umin + s->sum_nu, hb.begin() + 2 * (size_t)s->sum_nx); std::copy(umax, umax + s->sum_nu, hb.begin() + 2 * (size_t)s->sum_nx + s->sum_nu);
+        hb.swap(s->h_bounds);
+        const int rc = check_box_bounds(s);
+        if (rc != TQGPU_OK) { hb.swap(s->h_bounds); return rc; }
+    } else s->h_bounds.clear();
     H2D(s->xmin + s->x_pad, xmin, s->sum_nx - s->x_pad); H2D(s->xmax + s->x_pad, xmax, s->sum_nx - s->x_pad); H2D(s->umin, umin, s->sum_nu); H2D(s->umax, umax, s->sum_nu);
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->need_pack = true;
@@ -2742,7 +2991,8 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
-    if (s->dense) { s->dense = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; s->in_valid = false; s->need_init = true; s->need_pack = true; }
+    if (s->dense) { s->dense = false; s->box = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; s->in_valid = false; s->need_init = true; s->need_pack = true; }
+    if (xmin || xmax || umin || umax) s->h_bounds.clear();           /* (the checks of the box nodes' bounds see them through tqgpu_set_bounds only) */
     char *slab = static_cast<char *>(s->slab);
     bool any_pack = false, any_init = false;
     auto put = [&](double *dev, const double *src, int count, bool pack, bool init) -> int {
@@ -2945,11 +3195,14 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         /* first sweep at lambda0 (phase S of iteration 0 + fval0); the persistent launch does it as its prologue */
         if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev0, st));
         s->w3_now = s->w3_ok && !s->dense && !cx.phases && !cx.fast && !s->sharded;
-        s->fuse_now = s->fuse_ok && !cx.phases && !cx.fast && !s->sharded && !s->w3_now;
+        s->fuse_now = s->fuse_ok && !cx.phases && !cx.fast && !s->sharded && !s->w3_now && !s->box;     /* box nodes: a failed stage solve ends
+                                                                                                       the solve in the control block, which the NEXT launch reads */
         if (s->w3_now) { launch_sg(s, cx.O, 0, 0, 0, w3_fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
         else if (s->fuse_now) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
         else {
-            hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 0, 0, 0); cx.launches++;
+            if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 0, 0, 0);
+            else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 0, 0, 0);
+            cx.launches++;
             hipLaunchKernelGGL(k_fval_init, dim3(1), dim3(256), 0, st, T, D); cx.launches++;
         }
         if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev1, st));
@@ -3161,6 +3414,7 @@ static int enqueue_export(tqgpu_solver *s, const double *lamc) {
     const int nxe = s->sum_nx - s->x_pad, nue = s->sum_nu, nl = s->sum_lam;
     const int n = std::max(std::max(nxe, nue), std::max(nl, 1));
     hipLaunchKernelGGL(k_export_all, dim3((n + 255) / 256), dim3(256), 0, s->stream, nxe, nue, nl, s->x_pad, s->nx0, D, lamc, s->d_out);
+    if (s->box) hipLaunchKernelGGL(k_export_box, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
     HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, s->stream));
     return TQGPU_OK;
 }

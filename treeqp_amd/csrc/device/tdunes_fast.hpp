@@ -74,11 +74,7 @@ struct Uni {
     }
 };
 
-__device__ __forceinline__ double rdlane(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
+/* rdlane (value of one lane to every lane): defined in tdunes_device.hip, next to stage_box */
 
 /* 1/sqrt(p) for p > 0, 0 otherwise (non-positive pivot -> zero column, as dpotrf_l) */
 __device__ __forceinline__ double pivot_rsqrt(double p) {

@@ -153,17 +153,21 @@ static void require_clipping_applicable(const tree_qp_in *qp_in, int k)
         fatal("Specified stage QP solver (clipping) not applicable.", NULL);
 }
 
-/* The dense stage solver of this build covers unconstrained nodes only (bounds at +-inf as written by
- * tree_qp_in_set_inf_bounds, no general constraints); constrained dense stage QPs need an active-set QP
- * solver (qpOASES in the reference), which is out of scope. */
-static int is_inf_bound(double lo, double hi) { return lo <= -1e12 && hi >= 1e12; }
-static void require_dense_unconstrained(const tree_qp_in *qp_in, int k)
+/* The dense stage solvers of this build (the reference's TREEQP_QPOASES_SOLVER selector) cover stage QPs with box
+ * bounds (qpOASES QProblemB in the reference, dual_Newton_tree_qpoases.c:312-358); general constraints (nc > 0,
+ * qpOASES QProblem) are out of scope.  A node whose bounds are all infinite (|bound| >= TREEQP_INF, as written by
+ * tree_qp_in_set_inf_bounds) takes the unconstrained dense solver (device kind 1), any other the box solver (kind 2). */
+static int is_inf_bound(double lo, double hi) { return lo <= -TREEQP_INF && hi >= TREEQP_INF; }
+static void require_dense_applicable(const tree_qp_in *qp_in, int k)
 {
-    int ok = qp_in->nc[k] == 0;
-    for (int j = 0; ok && j < qp_in->nx[k]; j++) ok = is_inf_bound(BLASFEO_DVECEL(&qp_in->xmin[k], j), BLASFEO_DVECEL(&qp_in->xmax[k], j));
-    for (int j = 0; ok && j < qp_in->nu[k]; j++) ok = is_inf_bound(BLASFEO_DVECEL(&qp_in->umin[k], j), BLASFEO_DVECEL(&qp_in->umax[k], j));
-    if (!ok)
-        fatal("TREEQP_QPOASES_SOLVER is available for unconstrained nodes only in the MI355X build (dense stage solver; qpOASES itself is out of scope).", NULL);
+    if (qp_in->nc[k] > 0)
+        fatal("TREEQP_QPOASES_SOLVER with general constraints (nc > 0) is not available in the MI355X build (box bounds only).", NULL);
+}
+static int dense_kind(const tree_qp_in *qp_in, int k)
+{
+    for (int j = 0; j < qp_in->nx[k]; j++) if (!is_inf_bound(BLASFEO_DVECEL(&qp_in->xmin[k], j), BLASFEO_DVECEL(&qp_in->xmax[k], j))) return 2;
+    for (int j = 0; j < qp_in->nu[k]; j++) if (!is_inf_bound(BLASFEO_DVECEL(&qp_in->umin[k], j), BLASFEO_DVECEL(&qp_in->umax[k], j))) return 2;
+    return 1;
 }
 
 void treeqp_tdunes_create(const tree_qp_in *qp_in, const treeqp_tdunes_opts_t *opts,
@@ -181,14 +185,14 @@ void treeqp_tdunes_create(const tree_qp_in *qp_in, const treeqp_tdunes_opts_t *o
     work->maxIterAtCreate = opts->maxIter;
 
     /* Stage solvers (dual_Newton_tree.c:1399-1425 dispatches per node): clipping, or -- under the reference's
-     * TREEQP_QPOASES_SOLVER selector -- the dense stage solver for UNCONSTRAINED nodes (the part of that backend
-     * that needs no active-set QP solver: z = H^-1 h, P = H^-1).  One kind for the whole tree. */
+     * TREEQP_QPOASES_SOLVER selector -- the dense stage solvers: unconstrained (z = H^-1 h, P = H^-1) or with box
+     * bounds (an active-set method on the bounds, P = Z (Z'HZ)^-1 Z'), chosen per node and solve from the bounds. */
     int n_dense = 0;
     for (int k = 0; k < Nn; k++) {
         /* the solver (like the reference, dual_Newton_tree.c:675,1377) needs parents == nodes 0..Np-1 */
         if ((tree[k].nkids > 0) != (k < Np)) fatal("tdunes needs all leaves at the same depth.", NULL);
         if (opts->qp_solver[k] == TREEQP_CLIPPING_SOLVER) require_clipping_applicable(qp_in, k);
-        else if (opts->qp_solver[k] == TREEQP_QPOASES_SOLVER) { require_dense_unconstrained(qp_in, k); n_dense++; }
+        else if (opts->qp_solver[k] == TREEQP_QPOASES_SOLVER) { require_dense_applicable(qp_in, k); n_dense++; }
         else fatal("Unknown stage QP solver.", NULL);
     }
     /* any mix of the two kinds across nodes is fine (the reference binds the vtable per node, dual_Newton_tree.c:124-162) */
@@ -377,20 +381,22 @@ return_t treeqp_tdunes_solve(const tree_qp_in *qp_in, tree_qp_out *qp_out,
 
     if (work->denseStageSolver) {
         DEV_CALL(tqgpu_set_dynamics(work->device, A, B, b));
-        /* flat Q, R, S in the order of tree_qp_in_set_ltv_objective_colmajor; bounds are re-checked, not uploaded */
+        /* flat Q, R, S in the order of tree_qp_in_set_ltv_objective_colmajor; the bounds go out first (the device checks lb <= ub
+         * of the box nodes against them) */
         double *Qf = stage; for (int k = 0; k < Nn; k++) for (int j = 0; j < qp_in->nx[k]; j++) for (int i = 0; i < qp_in->nx[k]; i++) *stage++ = BLASFEO_DMATEL(&qp_in->Q[k], i, j);
         double *Rf = stage; for (int k = 0; k < Nn; k++) for (int j = 0; j < qp_in->nu[k]; j++) for (int i = 0; i < qp_in->nu[k]; i++) *stage++ = BLASFEO_DMATEL(&qp_in->R[k], i, j);
         double *Sf = stage; for (int k = 0; k < Nn; k++) for (int j = 0; j < qp_in->nx[k]; j++) for (int i = 0; i < qp_in->nu[k]; i++) *stage++ = BLASFEO_DMATEL(&qp_in->S[k], i, j);
         assert(stage <= work->stage + work->stage_doubles);
         int *kind = malloc(sizeof(int) * (size_t)Nn);
         for (int k = 0; k < Nn; k++) {
-            kind[k] = opts->qp_solver[k] == TREEQP_QPOASES_SOLVER;
-            if (kind[k]) require_dense_unconstrained(qp_in, k); else require_clipping_applicable(qp_in, k);
+            kind[k] = 0;
+            if (opts->qp_solver[k] == TREEQP_QPOASES_SOLVER) { require_dense_applicable(qp_in, k); kind[k] = dense_kind(qp_in, k); }
+            else require_clipping_applicable(qp_in, k);
         }
+        DEV_CALL(tqgpu_set_bounds(work->device, xmin, xmax, umin, umax));
         int rc_obj = tqgpu_set_objective_mixed(work->device, kind, Qf, Rf, Sf, q, r);
         free(kind);
         if (rc_obj != TQGPU_OK) fatal("device call failed in treeqp_tdunes_solve", tqgpu_last_error());
-        DEV_CALL(tqgpu_set_bounds(work->device, xmin, xmax, umin, umax));
         /* warm start from whatever slambda holds (set_dual_initialization or the previous solve) */
         DEV_CALL(tqgpu_set_lambda(work->device, flat_of_vecs(work->slambda, Np, &stage)));
     } else {
@@ -431,7 +437,7 @@ return_t treeqp_tdunes_solve(const tree_qp_in *qp_in, tree_qp_out *qp_out,
     work->lsTotal = res.ls_total;
     status = (return_t)res.status;
     /* like the reference, an early error return leaves qp_out untouched (:1177,1215) */
-    if (status == TREEQP_DN_NOT_DESCENT_DIRECTION) return status;
+    if (status == TREEQP_DN_NOT_DESCENT_DIRECTION || status == TREEQP_DN_STAGE_QP_SOLVE_FAILED) return status;
 
     /* --- export (:1235-1247) */
     treeqp_tic(&interface_tmr);
