@@ -507,7 +507,8 @@ class TqGpu:
 
     @property
     def path(self) -> int:
-        """0 generic per-level kernels, 1 tiered fused kernels, 2 persistent single launch."""
+        """Route under default options: 0 generic kernels (three launches per iteration, or per phase), 1 tiered fused kernels,
+        2 persistent single launch, 3 single-workgroup persistent launch."""
         return int(lib().tqgpu_uses_fused_path(self.h))
 
     def _chk(self, rc):

@@ -1450,6 +1450,10 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 /* host side of the C-ABI                                                                       */
 /* ============================================================================================ */
 
+/* which kernels a solve launches, decided once per solve by route_of: the paths of DESIGN.md §4 (FUSED_TAILS: k_stage_f, k_grad_f) */
+enum class Route { PERSIST, SINGLE_WG, TIERED, THREE_LAUNCH, FUSED_TAILS, PER_PHASE };
+static bool single_launch(Route r) { return r == Route::PERSIST || r == Route::SINGLE_WG; }      /* verdict through the result block */
+
 struct tqgpu_solver {
     int device = 0;
     int Nn = 0, Np = 0, Nh = 0;
@@ -1468,9 +1472,10 @@ struct tqgpu_solver {
     unsigned long long *fuse_red = nullptr;   /* small trees: partials of the reductions that run as the tail of a sweep (Fuse), [Nn][2] tagged words */
     int *fuse_cnt = nullptr;            /* ... and the counter of the workgroups that have posted theirs */
     unsigned fuse_epoch = 0;
-    bool fuse_ok = false, fuse_now = false;       /* fuse_now: this solve uses them (not while phases are timed one by one) */
+    bool fuse_ok = false;
     /* three launches per Newton iteration for the wide-block class (tdunes_wide3.hpp): k_sg, k_hf_w, k_fwd3 */
-    bool w3_ok = false, w3_now = false;
+    bool w3_ok = false;
+    Route route = Route::PER_PHASE;     /* of the last solve begun */
     unsigned long long *w3_xu = nullptr, *w3_red = nullptr;
     int *w3_cnt = nullptr;
     unsigned w3_epoch = 0;
@@ -2015,12 +2020,12 @@ static void launch_sg(tqgpu_solver *s, const Opts &O, int mode, int h, int t, bo
     hipLaunchKernelGGL(k_sg, dim3(grid), dim3(SG_WAVES * WAVE), SG_WAVES * ((s->lds_stage + 7) / 8) * 8, s->stream, s->T, s->D, O, w, mode, h, t);
 }
 
-void launch_trial_phase(tqgpu_solver *s, const Opts &O, bool fast, int it, int t, int phase, int &launches) {
+void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int phase, int &launches) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     const bool sharded = s->sharded;
     if (phase == 0) {
         bool done = false;
-        if (fast) {
+        if (r == Route::TIERED) {
             const int n_stage = sharded ? s->n_nodes : T.Nn;
             switch (s->fast) {
 #define X(idx, nx, nu, md) case idx: hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->lds_fstage, st, T, D, O, sharded ? s->d_node_list : nullptr, n_stage, 7, it, t); done = true; break;
@@ -2029,9 +2034,9 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, bool fast, int it, int t
                 default: break;
             }
         }
-        if (!done && s->w3_now) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
+        if (!done && r == Route::THREE_LAUNCH) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
         if (!done) {
-            if (s->fuse_now && !sharded) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
+            if (r == Route::FUSED_TAILS) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
             else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, it, t);
             else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, it, t);
         }
@@ -2039,14 +2044,14 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, bool fast, int it, int t
         if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->d_node_cnt_list, s->n_nodes_counted, s->d_blk_list, s->n_blk_counted, s->d_xs, s->rank, s->bnd_b0, s->bnd_bn, s->bnd_own0, s->bnd_ownn, it, t); launches++; }
     } else {
         if (sharded) { hipLaunchKernelGGL(k_ls_decide_parts, dim3(1), dim3(WAVE), 0, st, D, O, s->d_xs, s->nranks, it, t, 0); launches++; }
-        else if (!((s->fuse_now || s->w3_now) && !fast)) { hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, it, t, 0); launches++; }
+        else if (r != Route::FUSED_TAILS && r != Route::THREE_LAUNCH) { hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, it, t, 0); launches++; }
     }
 }
 
-int launch_trial(tqgpu_solver *s, const Opts &O, bool fast, int it, int t, int &launches) {
-    launch_trial_phase(s, O, fast, it, t, 0, launches);
+int launch_trial(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int &launches) {
+    launch_trial_phase(s, O, r, it, t, 0, launches);
     if (s->sharded) { int rc = shard_exchange_rccl(s, 2); if (rc) return rc; }
-    launch_trial_phase(s, O, fast, it, t, 1, launches);
+    launch_trial_phase(s, O, r, it, t, 1, launches);
     return TQGPU_OK;
 }
 
@@ -2270,7 +2275,7 @@ int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, 
 void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts = 3, bool phases = false, bool last = false) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     auto mark = [&](int i) { if (phases && (size_t)(4 * h + i) < s->phase_ev.size()) (void)hipEventRecord(s->phase_ev[(size_t)(4 * h + i)], st); };
-    if (s->w3_now) {
+    if (s->route == Route::THREE_LAUNCH) {
         /* three launches: the termination test of this iteration was the tail of the previous launch of k_sg */
         if (!(parts & 2)) return;
         s->bw_epoch++;
@@ -2298,9 +2303,10 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
         for (int tt = 2; tt <= kpred; tt++) { s->w3_post_next = last && tt == kpred; launch_sg(s, O, 1, h, tt); launches++; }
         return;
     }
+    const bool fuse = s->route == Route::FUSED_TAILS;
     mark(0);
     if (parts & 1) {
-        if (s->fuse_now) { hipLaunchKernelGGL(k_grad_f, dim3(T.Nn - 1), dim3(WAVE), 0, st, T, D, O, next_fuse(s), h); launches++; }      /* with k_check as its tail */
+        if (fuse) { hipLaunchKernelGGL(k_grad_f, dim3(T.Nn - 1), dim3(WAVE), 0, st, T, D, O, next_fuse(s), h); launches++; }      /* with k_check as its tail */
         else {
             hipLaunchKernelGGL(k_grad, dim3(T.Nn - 1), dim3(WAVE), 0, st, T, D, O.termCondition, h); launches++;
             hipLaunchKernelGGL(k_check, dim3(1), dim3(256), 0, st, T, D, O, h); launches++;
@@ -2332,8 +2338,8 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
         if (T.Np > 1) {
             s->fw_epoch++;
             if (s->fw_epoch == 0) s->fw_epoch = 1;
-            const Fuse F = s->fuse_now ? next_fuse(s) : no_fuse();          /* with k_ls_begin as its tail */
-            ls_begun = s->fuse_now;
+            const Fuse F = fuse ? next_fuse(s) : no_fuse();          /* with k_ls_begin as its tail */
+            ls_begun = fuse;
             if (wide) hipLaunchKernelGGL(k_forward_all_w, dim3(T.Np - 1), dim3(WT), s->lds_forward_w, st, T, D, s->fw_words, s->fw_epoch, h, F);
             else hipLaunchKernelGGL(k_forward_all, dim3(T.Np - 1), dim3(WAVE), s->lds_forward, st, T, D, s->fw_words, s->fw_epoch, h, F);
             launches++;
@@ -2347,7 +2353,7 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
     }
     mark(2);
     if (!ls_begun) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
-    if (s->fuse_now) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
+    if (fuse) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
     else {
         if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, h, 1);
         else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, h, 1);
@@ -2768,20 +2774,39 @@ extern "C" void tqgpu_destroy(tqgpu_solver *s) {
     delete s;
 }
 
-/* which path a mirror takes: persistent single launch (uniform or multistage trees), tiered launches (uniform
- * trees only), single-workgroup persistent (small trees of any shape), launch per level */
+/* what a mirror admits: the persistent single launch (uniform or multistage trees), launches per tier (uniform trees only) */
 static bool persist_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && s->persist_ok && s->use_persist && !s->sharded; }
 static bool tiered_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && !s->mstage; }
 /* `batch`: as a member of a batched launch (one workgroup per tree) the single-workgroup kernel also takes trees whose
  * state does not fit the LDS mirror; alone, such a tree is faster with one launch per level */
-static bool uses_gpersist(const tqgpu_solver *s, bool batch = false) {
+static bool uses_gpersist(const tqgpu_solver *s, bool batch) {
     return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->dense && !s->sharded && !persist_capable(s) && !tiered_capable(s);
+}
+/* the first route that the mirror and the options admit (batch_member: see uses_gpersist) */
+static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_member) {
+    const int p = o->profile, m = o->maxIter;
+    if (persist_capable(s) && p == 0 && m > 0) return Route::PERSIST;
+    if (uses_gpersist(s, batch_member) && p == 0 && m > 0) return Route::SINGLE_WG;
+    if (tiered_capable(s) && p < 3) return Route::TIERED;
+    if (s->w3_ok && !s->dense && p < 3 && !s->sharded) return Route::THREE_LAUNCH;
+    if (s->fuse_ok && p < 3 && !s->sharded && !s->box) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
+    return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
 extern "C" int tqgpu_uses_fused_path(const tqgpu_solver *s) {
     if (!s) return 0;
-    if (persist_capable(s)) return 2;
-    if (tiered_capable(s)) return 1;
-    return uses_gpersist(s) ? 3 : 0;
+    tqgpu_opts o{}; o.maxIter = 1;          /* the route under default options */
+    const Route r = route_of(s, &o, false);
+    return r == Route::PERSIST ? 2 : r == Route::TIERED ? 1 : r == Route::SINGLE_WG ? 3 : 0;
+}
+
+/* the options as the kernels take them; TREEQP_AMD_STAMPS is for the caller to set */
+static int opts_from(const tqgpu_opts *o, Opts &O) {
+    O.maxIter = o->maxIter; O.termCondition = o->termCondition; O.regType = o->regType;
+    O.lsMaxIter = o->lineSearchMaxIter; O.lsRestartTrigger = o->lineSearchRestartTrigger; O.reuse = o->checkLastActiveSet == 2 ? 1 : 0;
+    O.tol = o->stationarityTolerance; O.regTol = o->regTol; O.regValue = o->regValue;
+    O.gamma = o->lineSearchGamma; O.beta = o->lineSearchBeta; O.stamps = 0;
+    if (O.termCondition < 0 || O.termCondition > 2 || O.regType < 0 || O.regType > 2 || O.regValue < 0) return fail(TQGPU_EINVAL, "invalid option value");
+    return TQGPU_OK;
 }
 
 /* diagnostic: copy the in-kernel time stamps of the last fused iteration (8 kernels x 32 slots x
@@ -3034,13 +3059,13 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
 namespace {
 
 int read_ctrl(tqgpu_solver *s) {
-    if (s->w3_now && s->w3_mirror && !s->w3_tail_sg) {
+    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && !s->w3_tail_sg) {
         /* the last launch enqueued does not post (the first sweep of a solve whose chunk launches nothing else): a one-thread launch does */
         W3 w = next_w3(s);
         w.hm = s->h_res; s->w3_wait = w.tag; s->w3_tail_sg = true;
         hipLaunchKernelGGL(k_w3_post, dim3(1), dim3(WAVE), 0, s->stream, s->D, w);
     }
-    if (s->w3_now && s->w3_mirror && s->w3_tail_sg) {
+    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_tail_sg) {
         /* three-launch family: the last launch enqueued posts the control block to pinned memory itself (w3_mirror) */
         volatile unsigned *seq = &s->h_res->seq;
         const unsigned want = s->w3_wait;
@@ -3111,7 +3136,8 @@ struct SolveCtx {
     Opts O;
     int launches = 0, ring = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool fast = false, persist = false, first_launch = true, prelaunched = false, gpersist = false, phases = false, events = true;
+    Route route = Route::PER_PHASE;
+    bool first_launch = true, prelaunched = false, phases = false, events = true;
     unsigned batch_seq = 0;          /* != 0: this solve's persistent launch is part of a batch launch the caller makes with this launch number */
     int env_stamps = -1, env_nomirror = -1;          /* >= 0: TREEQP_AMD_STAMPS / TREEQP_AMD_NO_W3_MIRROR as the caller read them (tqgpu_solve_batch: once per call, not once per member) */
 #ifdef TQ_HOSTPROF
@@ -3126,14 +3152,9 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
     HIP_TRY(hipSetDevice(s->device));
     s->export_valid = false;
     Opts &O = cx.O;
-    O.maxIter = o->maxIter; O.termCondition = o->termCondition; O.regType = o->regType;
-    O.lsMaxIter = o->lineSearchMaxIter; O.lsRestartTrigger = o->lineSearchRestartTrigger; O.reuse = o->checkLastActiveSet == 2 ? 1 : 0;
-    O.tol = o->stationarityTolerance; O.regTol = o->regTol; O.regValue = o->regValue;
-    O.gamma = o->lineSearchGamma; O.beta = o->lineSearchBeta;
+    if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
     if (cx.env_stamps >= 0) O.stamps = cx.env_stamps;          /* (a batch call reads the environment once for all its members) */
     else { const char *e = getenv("TREEQP_AMD_STAMPS"); O.stamps = e ? std::max(1, atoi(e)) : 0; }
-    if (O.termCondition < 0 || O.termCondition > 2 || O.regType < 0 || O.regType > 2 || O.regValue < 0)
-        return fail(TQGPU_EINVAL, "invalid option value");
 
     if (s->sharded && !s->comm) return fail(TQGPU_ECOMM, "sharded mirror without a communicator: use tqgpu_solve_virtual_ranks");
     const Tree &T = s->T; const Data &D = s->D;
@@ -3149,8 +3170,8 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
     const size_t n_it = (size_t)std::max(o->maxIter, 1);
     if (s->times_dirty || s->iter_times.size() != n_it) s->iter_times.assign(n_it, NAN);
 
-    s->w3_now = false;
-    cx.fast = tiered_capable(s) && o->profile < 3;          /* level 3: the launch-per-level kernels, whose launches ARE the reference's phases */
+    cx.route = s->route = route_of(s, o, defer != nullptr);
+    const bool single = single_launch(cx.route), w3 = cx.route == Route::THREE_LAUNCH;
     cx.phases = o->profile >= 3;
     if (cx.phases) {
         while ((int)s->phase_ev.size() < 4 * (o->maxIter + 1)) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); s->phase_ev.push_back(ev); }
@@ -3159,9 +3180,6 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
     if (s->times_dirty || s->phase_times.size() != 3 * n_it) s->phase_times.assign(3 * n_it, NAN);
     s->first_sweep_time = NAN;
     s->times_dirty = o->profile != 0;
-    cx.persist = persist_capable(s) && !o->profile && o->maxIter > 0;
-    cx.gpersist = !cx.persist && uses_gpersist(s, defer != nullptr) && !o->profile && o->maxIter > 0;
-    if (cx.gpersist) cx.persist = true;                  /* same host flow: one launch, verdict through the result block */
     cx.ring = (int)(s->solve_no % EV_RING);
     cx.ev0 = s->ring_ev0[cx.ring]; cx.ev1 = s->ring_ev1[cx.ring];
     s->solve_no++;
@@ -3169,18 +3187,17 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
      * start to verdict) anyway, so there the pair is optional */
     /* the three-launch family reports through the pinned result block as well (launches of k_sg / k_sgp post the control block and
      * their own clock: w3_mirror) */
-    const bool w3_will = !cx.persist && s->w3_ok && !s->dense && !cx.phases && !cx.fast && !s->sharded;
     const bool no_mirror = cx.env_nomirror >= 0 ? cx.env_nomirror != 0 : getenv("TREEQP_AMD_NO_W3_MIRROR") != nullptr;        /* (A/B and tests: copy + synchronisation per read, HIP events per solve, as before) */
-    s->w3_mirror = w3_will && !o->profile && !no_mirror;
+    s->w3_mirror = w3 && !o->profile && !no_mirror;
     s->w3_seen = false;
     if (s->w3_mirror) s->h_res->seq = 0;          /* (no launch of this mirror is in flight) */
-    cx.events = (s->ev_timing || (!cx.persist && !s->w3_mirror)) && !cx.batch_seq && !defer;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
+    cx.events = (s->ev_timing || (!single && !s->w3_mirror)) && !cx.batch_seq && !defer;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
     s->ring_ok[(size_t)cx.ring] = cx.events ? 1 : 0;
     if (cx.events) HIP_TRY(hipEventRecord(cx.ev0, st));
     /* the three-launch family with k_sgp: the first launch of the solve takes the starting duals and resets the control block itself */
-    const bool w3_fresh = !cx.persist && s->w3_ok && s->w3_sgp && !s->dense && o->profile < 3 && !tiered_capable(s) && !s->sharded;
-    if (!cx.persist && !w3_fresh) HIP_TRY(hipMemsetAsync(D.ctrl, 0, sizeof(Ctrl), st));     /* persistent path: reset by the launch's prologue */
-    if (s->need_init && !cx.gpersist) {     /* g_persist recomputes the reciprocal weights itself; dense nodes never read theirs */
+    const bool fresh = w3 && s->w3_sgp;
+    if (!single && !fresh) HIP_TRY(hipMemsetAsync(D.ctrl, 0, sizeof(Ctrl), st));     /* persistent path: reset by the launch's prologue */
+    if (s->need_init && cx.route != Route::SINGLE_WG) {     /* g_persist recomputes the reciprocal weights itself; dense nodes never read theirs */
         hipLaunchKernelGGL(k_init, dim3((nxu + 255) / 256), dim3(256), 0, st, s->sum_nx, s->sum_nu, D); cx.launches++;
         s->need_init = false;
         s->stream_pending = true;
@@ -3189,16 +3206,13 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         hipLaunchKernelGGL(k_dense_init, dim3(T.Nn), dim3(WAVE), s->lds_dense, st, T, D); cx.launches++;
         s->need_dense_init = false;
     }
-    if (!cx.persist) {
+    if (!single) {
         /* the current buffer is lam0 at the start of every solve */
-        if (!w3_fresh) HIP_TRY(hipMemcpyAsync(D.lam0, s->d_lam_init, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, st));
+        if (!fresh) HIP_TRY(hipMemcpyAsync(D.lam0, s->d_lam_init, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, st));
         /* first sweep at lambda0 (phase S of iteration 0 + fval0); the persistent launch does it as its prologue */
         if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev0, st));
-        s->w3_now = s->w3_ok && !s->dense && !cx.phases && !cx.fast && !s->sharded;
-        s->fuse_now = s->fuse_ok && !cx.phases && !cx.fast && !s->sharded && !s->w3_now && !s->box;     /* box nodes: a failed stage solve ends
-                                                                                                       the solve in the control block, which the NEXT launch reads */
-        if (s->w3_now) { launch_sg(s, cx.O, 0, 0, 0, w3_fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
-        else if (s->fuse_now) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
+        if (w3) { launch_sg(s, cx.O, 0, 0, 0, fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
+        else if (cx.route == Route::FUSED_TAILS) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
         else {
             if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 0, 0, 0);
             else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 0, 0, 0);
@@ -3211,7 +3225,7 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         cx.hp1 = HP_NOW();
 #endif
         int rcx = TQGPU_OK;
-        if (cx.gpersist) {
+        if (cx.route == Route::SINGLE_WG) {
             s->launch_no = (s->launch_no + 1) & 0xFFFFu;
             if (s->launch_no == 0) s->launch_no = 1;
             s->psync.seq = s->launch_no << 16;
@@ -3238,7 +3252,10 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     HIP_TRY(hipSetDevice(s->device));
     const Opts &O = cx.O;
     hipStream_t st = s->stream;
-    const bool fast = cx.fast, persist = cx.persist;
+    const Route route = cx.route;
+    const bool single = single_launch(route), generic = !single && route != Route::TIERED;      /* generic: launch_generic_iteration */
+    /* (a persistent launch that ends inside a line search leaves its further trials to the tiered kernels, where the tree has them) */
+    const Route trials = route == Route::PERSIST && tiered_capable(s) ? Route::TIERED : route;
     int &launches = cx.launches;
     /* Newton loop (dual_Newton_tree.c:1166-1228).  The device decides (termination, Armijo);
      * the host enqueues `chunk` tagged iterations ahead and reads the control block once per chunk.
@@ -3250,19 +3267,19 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     if (finished) { HIP_TRY(hipStreamSynchronize(st)); memset(s->h_ctrl, 0, sizeof(Ctrl)); s->h_ctrl->status = 1; }
     if (o->profile) HIP_TRY(hipEventRecord(s->iter_ev[0], st));
     int chunk = s->last_iter > 0 ? std::min(s->last_iter + 1, 16) : s->chunk;
-    bool predicted = s->last_iter > 0 && !fast && !persist;     /* the chunk is a prediction: its last iteration should only find convergence */
+    bool predicted = s->last_iter > 0 && generic;     /* the chunk is a prediction: its last iteration should only find convergence */
     /* a line search that wants a second trial turns everything enqueued behind it into no-ops (~3 us a launch): a problem that
      * backtracked last time is fed two iterations at a time (TREEQP_AMD_LS_CHUNK; one C5-class tree: 1.15 ms with chunks of 8, 1.04 / 1.01 / 1.06 ms with 4 / 2 / 1),
      * a read-back per chunk instead */
     static const int ls_chunk = getenv("TREEQP_AMD_LS_CHUNK") ? std::max(1, atoi(getenv("TREEQP_AMD_LS_CHUNK"))) : 2;
-    if (s->last_ls_extra && !fast && !persist && chunk > ls_chunk && !(s->w3_now && !s->ls_pred.empty())) { chunk = ls_chunk; predicted = false; }      /* (three-launch family: the further trials are predicted too) */
+    if (s->last_ls_extra && generic && chunk > ls_chunk && !(route == Route::THREE_LAUNCH && !s->ls_pred.empty())) { chunk = ls_chunk; predicted = false; }      /* (three-launch family: the further trials are predicted too) */
     if (cx.phases) { chunk = 1; predicted = false; }            /* phase timing: one iteration per read-back, so that every recorded event belongs to work that ran */
     int rest_due = -1;                                          /* iteration whose termination test ran, whose step did not */
     while (!finished) {
-        const int n = persist ? 0 : std::min(chunk, o->maxIter - h);
-        if (persist) {
+        const int n = single ? 0 : std::min(chunk, o->maxIter - h);
+        if (single) {
             if (!cx.prelaunched) {
-                if (cx.gpersist) return fail(TQGPU_ENODEVICE, "single-workgroup persistent kernel ended without a verdict");
+                if (route == Route::SINGLE_WG) return fail(TQGPU_ENODEVICE, "single-workgroup persistent kernel ended without a verdict");
                 int rcx = launch_persist(s, O, launches, cx.first_launch ? 1 : 0);
                 if (rcx != TQGPU_OK) return rcx;
                 cx.first_launch = false;
@@ -3272,7 +3289,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
         }
         int deferred = -1;
         for (int i = 0; i < n; i++) {
-            if (fast) { int rcx = launch_fast_iteration(s, O, h + i, launches); if (rcx != TQGPU_OK) return rcx; }
+            if (route == Route::TIERED) { int rcx = launch_fast_iteration(s, O, h + i, launches); if (rcx != TQGPU_OK) return rcx; }
             else {
                 int parts = 3;
                 if (rest_due == h + i) parts &= ~1;                                   /* its test already ran */
@@ -3284,13 +3301,13 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
             if (o->profile && ev_idx + 1 < (int)s->iter_ev.size()) HIP_TRY(hipEventRecord(s->iter_ev[++ev_idx], st));
         }
         /* persistent path: the verdict comes through the result block in pinned host memory */
-        int rc = persist ? wait_result_block(s) : read_ctrl(s);
+        int rc = single ? wait_result_block(s) : read_ctrl(s);
         if (rc != TQGPU_OK) return rc;
 #ifdef TQ_HOSTPROF
-        if (persist) { auto hp3 = HP_NOW(); hp_acc[0] += HP_US(cx.hp0, cx.hp1); hp_acc[1] += HP_US(cx.hp1, cx.hp2); hp_acc[2] += HP_US(cx.hp2, hp3); hp_n++;
+        if (single) { auto hp3 = HP_NOW(); hp_acc[0] += HP_US(cx.hp0, cx.hp1); hp_acc[1] += HP_US(cx.hp1, cx.hp2); hp_acc[2] += HP_US(cx.hp2, hp3); hp_n++;
           if (hp_n % 200 == 0) { fprintf(stderr, "[hostprof] pre %.2f us, launch %.2f us, readback+sync %.2f us (avg of %ld)\n", hp_acc[0] / hp_n, hp_acc[1] / hp_n, hp_acc[2] / hp_n, hp_n); } }
 #endif
-        tail_done = persist;
+        tail_done = single;
         bool extra_trials = false;
         /* trials beyond the first go out in batches: 3, then 6, 12, 16, .. per read-back of the control block.  A trial that is
          * accepted turns the rest of its batch into no-ops (~6 us each), so short searches -- the usual case: one or two more
@@ -3305,7 +3322,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
             if (it != ls_of) { ls_of = it; trial_batch = trial_batch0; }
             for (int t = t0; t < t0 + trial_batch && t <= O.lsMaxIter; t++) {
                 s->w3_post_next = t + 1 >= t0 + trial_batch || t + 1 > O.lsMaxIter;      /* the last of the batch */
-                int rcx = launch_trial(s, O, fast, it, t, launches);
+                int rcx = launch_trial(s, O, trials, it, t, launches);
                 if (rcx != TQGPU_OK) return rcx;
             }
             trial_batch = std::min(2 * trial_batch, 16);
@@ -3319,7 +3336,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
          * line search needed further trials (enqueued above, after the read-back), the test found the search pending and did nothing --
          * it is then due again with the rest of its iteration */
         rest_due = (!finished && deferred == h && !extra_trials) ? h : -1;
-        if (persist && !finished && !cx.gpersist) {
+        if (route == Route::PERSIST && !finished) {
             tail_done = false;
             unsigned tmo = 0;
             HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -3328,7 +3345,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     }
     const int host_iter = ev_idx;
     float ms = 0.f;
-    if (!tail_done && !persist && s->w3_now && s->w3_mirror && s->w3_seen && !cx.events && !o->profile && !cx.phases) {
+    if (!tail_done && route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_seen && !cx.events && !o->profile && !cx.phases) {
         /* three-launch family: every launch of the solve is accounted for (the last one's tail has posted the verdict; what its other
          * workgroups still write is stream-ordered before anything the host does next): no synchronisation, the device's own clock */
         unsigned long long t_first;
@@ -3365,7 +3382,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     res->n_launches = launches; res->device_time = 1e-3 * ms; res->last_error_norm = c.err; res->last_fval = c.fval;
     s->last_iter = c.iter;
     s->last_ls_extra = c.ls_total > c.iter ? 1 : 0;
-    if (s->w3_now && s->w3_merge && c.status == 2 && s->T.Np > 1) {
+    if (route == Route::THREE_LAUNCH && s->w3_merge && c.status == 2 && s->T.Np > 1) {
         /* NOT_DESCENT_DIRECTION out of the merged launch (k_sgp mode 2: forward sweep + first trial): the trial sweep ran before the
          * direction test and has put x, u, xUnc, QinvCal of the point lambda + dlambda in place.  The reference returns from
          * line_search with the phase-S iterate at lambda (dual_Newton_tree.c:944-954): one stage sweep at the current duals (which the
@@ -3374,7 +3391,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
         launches++; res->n_launches = launches;
         s->stream_pending = true;
     }
-    if (s->w3_now) {
+    if (route == Route::THREE_LAUNCH) {
         s->ls_pred.clear();
         if (c.status == 0 && c.ls_total > c.iter) {
             /* some iteration needed further trials: fetch the trial counts (only then: a copy is a packet on the queue and a synchronisation) */
@@ -3434,7 +3451,7 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
      * persistent launch now, while it runs, instead of after its verdict has travelled to the host and back (a launch latency, the
      * launch's write-back tail and a synchronisation off the caller's critical path); which dual buffer is current is the device's
      * knowledge.  Valid if that one launch was the whole solve. */
-    const bool ahead = s->export_ahead && cx.persist && cx.prelaunched && !s->pshard && !s->sharded;
+    const bool ahead = s->export_ahead && single_launch(cx.route) && cx.prelaunched && !s->pshard && !s->sharded;
     if (ahead && enqueue_export(s, nullptr) != TQGPU_OK) return TQGPU_ENODEVICE;
     rc = solve_end(s, o, cx, res);
     if (rc == TQGPU_ETIMEOUT) rc = solve_after_timeout(s, o, res);
@@ -3578,16 +3595,14 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
         int used = 0, j = i;
         for (; j < n; j++) {
             tqgpu_solver *s = solvers[j];
-            const bool persist_like = persist_capable(s) && !o->profile && o->maxIter > 0;
-            const bool gp_like = !persist_like && uses_gpersist(s, true) && !o->profile && o->maxIter > 0;
+            const Route r = route_of(s, o, true);
             /* single-workgroup mirrors do not wait for each other: any number per launch; launch-per-level mirrors go alone */
-            const int need = persist_like ? s->geom.G : (gp_like ? 0 : s->co_capacity + 1);
-            /* two workgroups on one CU run at half speed each: a batch fills the CUs once, not twice, unless a member needs more */
+            const int need = r == Route::PERSIST ? s->geom.G : (r == Route::SINGLE_WG ? 0 : s->co_capacity + 1);
             /* separate launches: two workgroups on one CU run at half speed each, so a batch fills the CUs once, not twice, unless a
              * member needs more.  Members that go out together as ONE launch (batch kernel) fill the device up to what is co-resident:
              * a tree's waves are parked at barriers and waits two thirds of the time, and trees that share CUs fill those gaps
              * (C2: 3 trees 72 k it/s, 5 trees 98 k; C1: 22 trees 656 k, 38 trees 922 k). */
-            const bool one_launch = persist_like && batch_kernel_index(s) >= 0 && o->checkLastActiveSet != 2 && !env_batch_launches;
+            const bool one_launch = r == Route::PERSIST && batch_kernel_index(s) >= 0 && o->checkLastActiveSet != 2 && !env_batch_launches;
             const int cap = (!one_launch && s->n_cu > 0 && need <= s->n_cu) ? std::min(s->co_capacity, s->n_cu) : s->co_capacity;
             if (j > i && (s->device != dev || used + need > cap)) break;
             used += need;
@@ -3596,10 +3611,8 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
         int ok_to = begun_from;
         /* single-workgroup mirrors of this wave go out as ONE launch (one workgroup per tree) on the first one's stream */
         std::vector<int> gp_members;
-        for (int k = begun_from; k < begun_to; k++) {
-            tqgpu_solver *s = solvers[k];
-            if (!persist_capable(s) && uses_gpersist(s, true) && !o->profile && o->maxIter > 0) gp_members.push_back(k);
-        }
+        for (int k = begun_from; k < begun_to; k++)
+            if (route_of(solvers[k], o, true) == Route::SINGLE_WG) gp_members.push_back(k);
         tqgpu_solver *lead = gp_members.size() >= 2 ? solvers[gp_members[0]] : nullptr;
         if (lead && lead->gitems_cap < (int)gp_members.size()) {
             if (lead->d_gitems) (void)hipFree(lead->d_gitems);
@@ -3616,7 +3629,7 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
             const tqgpu_solver *f = nullptr;
             for (int k = begun_from; k < begun_to; k++) {
                 const tqgpu_solver *s = solvers[k];
-                if (!(persist_capable(s) && !o->profile && o->maxIter > 0 && o->checkLastActiveSet != 2 && batch_kernel_index(s) >= 0)) continue;
+                if (!(route_of(s, o, true) == Route::PERSIST && o->checkLastActiveSet != 2 && batch_kernel_index(s) >= 0)) continue;
                 if (!f) f = s;
                 if (batch_kernel_index(s) == batch_kernel_index(f) && s->geom.G == f->geom.G && s->lds_persist == f->lds_persist && s->Nn == f->Nn) pm.push_back(k);
             }
@@ -4045,11 +4058,7 @@ extern "C" int tqgpu_pshard_begin(tqgpu_solver *s, const tqgpu_opts *o) {
     HIP_TRY(hipSetDevice(s->device));
     if (o->profile || o->maxIter <= 0 || o->checkLastActiveSet == 2) return fail(TQGPU_EUNSUPPORTED, "sharded persistent solve: default solve options only (no profiling, no factor keeping)");
     Opts O;
-    O.maxIter = o->maxIter; O.termCondition = o->termCondition; O.regType = o->regType;
-    O.lsMaxIter = o->lineSearchMaxIter; O.lsRestartTrigger = o->lineSearchRestartTrigger; O.reuse = 0;
-    O.tol = o->stationarityTolerance; O.regTol = o->regTol; O.regValue = o->regValue;
-    O.gamma = o->lineSearchGamma; O.beta = o->lineSearchBeta; O.stamps = 0;
-    if (O.termCondition < 0 || O.termCondition > 2 || O.regType < 0 || O.regType > 2 || O.regValue < 0) return fail(TQGPU_EINVAL, "invalid option value");
+    if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
     if (((s->launch_no + 1) & 0xFFFFu) == 0)
         return fail(TQGPU_EUNSUPPORTED, "65535 sharded solves since the launch numbers were last reset: call tqgpu_pshard_rewind on every rank, between two barriers of the caller's "
                                         "(the 16-bit launch number tags the hand-over words; a single device wipes its slab when it wraps, ranks that write into each other's slabs cannot do that on their own)");
@@ -4222,10 +4231,7 @@ extern "C" int tqgpu_solve_virtual_ranks(tqgpu_solver **R, int n, const tqgpu_op
     for (int r = 0; r < n; r++) if (!R[r] || R[r]->nranks != n || R[r]->rank != r || R[r]->comm) return fail(TQGPU_EINVAL, "mirror is not virtual rank r of n");
     HIP_TRY(hipSetDevice(R[0]->device));
     Opts O;
-    O.maxIter = o->maxIter; O.termCondition = o->termCondition; O.regType = o->regType;
-    O.lsMaxIter = o->lineSearchMaxIter; O.lsRestartTrigger = o->lineSearchRestartTrigger; O.reuse = o->checkLastActiveSet == 2 ? 1 : 0;
-    O.tol = o->stationarityTolerance; O.regTol = o->regTol; O.regValue = o->regValue;
-    O.gamma = o->lineSearchGamma; O.beta = o->lineSearchBeta; O.stamps = 0;
+    if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
     int launches = 0;
     for (int r = 0; r < n; r++) {
         tqgpu_solver *s = R[r];
@@ -4252,9 +4258,9 @@ extern "C" int tqgpu_solve_virtual_ranks(tqgpu_solver **R, int n, const tqgpu_op
         for (int r = 0; r < n; r++) if ((rc = read_ctrl(R[r]))) return rc;
         while (!R[0]->h_ctrl->done && R[0]->h_ctrl->ls_pending) {
             const int it = R[0]->h_ctrl->iter, t = R[0]->h_ctrl->ls_iter;
-            for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, true, it, t, 0, launches);
+            for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, Route::TIERED, it, t, 0, launches);
             if ((rc = shard_exchange_virtual(R, n, 2))) return rc;
-            for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, true, it, t, 1, launches);
+            for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, Route::TIERED, it, t, 1, launches);
             for (int r = 0; r < n; r++) if ((rc = read_ctrl(R[r]))) return rc;
         }
         for (int r = 1; r < n; r++)
