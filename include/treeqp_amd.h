@@ -92,6 +92,7 @@ int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const double *R,
  * 2 dense with box bounds: the bounds of tqgpu_set_bounds apply (qpOASES QProblemB of the reference,
  * dual_Newton_tree_qpoases.c:153-210, 312-358, 524-560: a hot-started active-set method on the bounds per node, one wave each,
  * P_k = Z (Z'H_k Z)^-1 Z' of the final working set, multipliers of the bounds in mu_x / mu_u).  NULL = all kind 1.
+ * Kinds 1 and 2 need nx[k] + nu[k] <= 142 (H_k is factored in 160 KiB of LDS; TQGPU_EUNSUPPORTED otherwise).
  * Kind 2 needs nx[k] + nu[k] <= 64 (TQGPU_EUNSUPPORTED otherwise) and lb <= ub on its entries (TQGPU_EINVAL from this call or
  * from tqgpu_set_bounds, whichever makes it inconsistent).  A stage solve that does not finish ends tqgpu_solve with
  * tqgpu_result.status = 4 (TREEQP_DN_STAGE_QP_SOLVE_FAILED).  Re-uploads between solves need no reset: the working sets
@@ -121,6 +122,27 @@ int tqgpu_get_solution(tqgpu_solver *s, double *x, double *u, double *lam, doubl
  * 0: generic per-level kernels.  TREEQP_AMD_PATH=generic|tiered in the environment at create time
  * forces the lower paths. */
 int tqgpu_uses_fused_path(const tqgpu_solver *s);
+/* diagnostic: the kernel variants chosen by tqgpu_create and the last tqgpu_set_objective_mixed, and the last solve's route, one bit each (any pointer may be
+ * NULL; reads the mirror, changes nothing).  *sgp_accs: children's [x | u] entries that k_sgp keeps in LDS per parent. */
+#define TQGPU_PLAN_WIDE            (1u << 0)    /* workgroup-per-block kernels of the wide-block class */
+#define TQGPU_PLAN_WIDE_SMALL      (1u << 1)    /* ... taken by the rule for wide trees of small blocks (d <= 16) */
+#define TQGPU_PLAN_W3              (1u << 2)    /* three launches per Newton iteration */
+#define TQGPU_PLAN_W3_SGP          (1u << 3)    /* ... with k_sgp, a workgroup per parent */
+#define TQGPU_PLAN_W3_MERGE        (1u << 4)    /* ... forward sweep and first trial in one launch */
+#define TQGPU_PLAN_FWD_CHAIN       (1u << 5)    /* ... forward sweep along each block's path to the root (k_fwd3c) */
+#define TQGPU_PLAN_FUSE            (1u << 6)    /* reductions as the tails of the sweeps (<= 512 nodes) */
+#define TQGPU_PLAN_PERSIST         (1u << 7)    /* persistent single launch */
+#define TQGPU_PLAN_PERSIST_ONE     (1u << 8)    /* ... in the one-workgroup-per-CU build */
+#define TQGPU_PLAN_GPERSIST        (1u << 9)    /* single-workgroup persistent kernel */
+#define TQGPU_PLAN_GP_STATE_LDS    (1u << 10)   /* ... its mutable state in LDS */
+#define TQGPU_PLAN_GP_CONST_LDS    (1u << 11)   /* ... and its constants */
+#define TQGPU_PLAN_GP_TABLES_LDS   (1u << 12)   /* ... only its index tables (the state does not fit) */
+#define TQGPU_PLAN_GP_SMALL16      (1u << 13)   /* ... four nodes per wave in the stage sweep */
+#define TQGPU_PLAN_GP_SMALL8       (1u << 14)   /* ... eight nodes per wave in the gradient sweep */
+#define TQGPU_PLAN_DENSE           (1u << 15)   /* dense stage solver selected */
+#define TQGPU_PLAN_BOX             (1u << 16)   /* ... with box-constrained nodes */
+#define TQGPU_PLAN_LAST_SINGLE_WG  (1u << 17)   /* the last solve begun (alone or in a batch) ran the single-workgroup kernel */
+int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs);
 /* geometry of the persistent launch: block levels, tiers, workgroups per launch, co-resident workgroup capacity of the device, CUs */
 int tqgpu_geometry(const tqgpu_solver *s, int *levels, int *tiers, int *workgroups, int *capacity, int *compute_units);
 /* diagnostic: persistent launches of this mirror that timed out (device shared with other work) and were redone on another path */

@@ -158,3 +158,135 @@ def ulp_solution_spread(orc, f, opts, copies=4):
                     v = float(np.nanmax(np.abs(p[k] - base[k]))) / max(1.0, float(np.nanmax(np.abs(base[k]))))
                 spread = max(spread, v)
     return spread
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# dense trees: an independent KKT certificate in numpy
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def offsets(d):
+    return np.concatenate([[0], np.cumsum(d["nx"])]), np.concatenate([[0], np.cumsum(d["nu"])])
+
+
+def global_kkt(d, fixed=None):
+    """Solve the equality-constrained QP of the whole tree in numpy: min 1/2 z'Hz + g'z s.t. the dynamics and z_i = bound_i on the
+    entries `fixed` (dict index -> value).  z = [x | u].  Returns z and the multipliers of the fixed entries (>= 0 on a lower bound)."""
+    nk, nx, nu = [np.asarray(d[k], dtype=int) for k in ("nk", "nx", "nu")]
+    Nn = len(nk)
+    xo, uo = offsets(d)
+    SX, SU = int(xo[-1]), int(uo[-1])
+    n = SX + SU
+    H = np.zeros((n, n))
+    qo = ro = so = 0
+    for k in range(Nn):
+        a, m = int(nx[k]), int(nu[k])
+        Q = d["Q"][qo:qo + a * a].reshape((a, a), order="F"); qo += a * a
+        R = d["R"][ro:ro + m * m].reshape((m, m), order="F"); ro += m * m
+        S = d["S"][so:so + m * a].reshape((m, a), order="F"); so += m * a
+        ix, iu = np.arange(xo[k], xo[k + 1]), SX + np.arange(uo[k], uo[k + 1])
+        H[np.ix_(ix, ix)] = Q; H[np.ix_(iu, iu)] = R; H[np.ix_(iu, ix)] = S; H[np.ix_(ix, iu)] = S.T
+    g = np.concatenate([d["q"], d["r"]])
+    dad = P.parents_of(nk)
+    rows, rhs = [], []
+    ao = bo = lo = 0
+    for k in range(1, Nn):
+        p = dad[k]
+        A = d["A"][ao:ao + nx[k] * nx[p]].reshape((nx[k], nx[p]), order="F"); ao += nx[k] * nx[p]
+        B = d["B"][bo:bo + nx[k] * nu[p]].reshape((nx[k], nu[p]), order="F"); bo += nx[k] * nu[p]
+        b = d["b"][lo:lo + nx[k]]; lo += nx[k]
+        C = np.zeros((nx[k], n))
+        C[:, xo[k]:xo[k + 1]] = -np.eye(nx[k])
+        C[:, xo[p]:xo[p + 1]] = A
+        C[:, SX + uo[p]:SX + uo[p + 1]] = B
+        rows.append(C); rhs.append(-b)
+    fixed = fixed or {}
+    fi = sorted(fixed)
+    for i in fi:
+        e = np.zeros((1, n)); e[0, i] = 1.0
+        rows.append(e); rhs.append([fixed[i]])
+    C = np.vstack(rows) if rows else np.zeros((0, n))
+    c = np.concatenate([np.atleast_1d(v) for v in rhs]) if rhs else np.zeros(0)
+    m = C.shape[0]
+    K = np.block([[H, C.T], [C, np.zeros((m, m))]])
+    sol = np.linalg.solve(K, np.concatenate([-g, c]))
+    z, nu_ = sol[:n], sol[n:]
+    mu = -nu_[m - len(fi):] if fi else np.zeros(0)
+    return z, dict(zip(fi, mu))
+
+
+def bounds_vec(d):
+    return np.concatenate([d["xmin"], d["umin"]]), np.concatenate([d["xmax"], d["umax"]])
+
+
+def certify(d, sol, tol=1e-9):
+    """From the returned active set, solve the tree's KKT system in numpy: same x, u; multipliers of the right sign; x, u feasible.
+    Returns the number of active bounds."""
+    z = np.concatenate([sol["x"], sol["u"]])
+    lo, hi = bounds_vec(d)
+    assert np.all(z >= lo - 1e-12) and np.all(z <= hi + 1e-12), "x, u leave the box"
+    fixed = {int(i): float(lo[i]) for i in np.flatnonzero(z == lo)}
+    fixed.update({int(i): float(hi[i]) for i in np.flatnonzero(z == hi)})
+    zc, mu = global_kkt(d, fixed)
+    scale = max(1.0, float(np.max(np.abs(zc))))
+    assert np.max(np.abs(zc - z)) / scale < tol, f"|z - z_kkt| = {np.max(np.abs(zc - z)):.3e}"
+    for i, m in mu.items():
+        mscale = max(1.0, abs(m))
+        if lo[i] == hi[i]:
+            continue
+        if z[i] == lo[i]:
+            assert m >= -tol * mscale, f"entry {i} on its lower bound with multiplier {m:.3e}"
+        else:
+            assert m <= tol * mscale, f"entry {i} on its upper bound with multiplier {m:.3e}"
+    return len(fixed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# exact shapes: a given tree with given node sizes (the kernel-selection limits of tqgpu_create are hit on purpose)
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def _per_node(v, nk, leaf_zero=False):
+    nk = np.asarray(nk, dtype=np.int32)
+    a = np.broadcast_to(np.asarray(v, dtype=np.int32), nk.shape).copy()
+    if leaf_zero:
+        a[nk == 0] = 0
+    return a
+
+
+def shaped_qp(nk, nx, nu, seed, ubound=0.3) -> P.FlatProblem:
+    """Clipping QP on the tree `nk` (children counts in breadth-first order) with per-node nx / nu (ints or arrays; nu is 0 on
+    the leaves), its data drawn as random_shape_qp draws them."""
+    nk = np.asarray(nk, dtype=np.int32)
+    nx, nu = _per_node(nx, nk), _per_node(nu, nk, leaf_zero=True)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    Nn = len(nk)
+    dad = P.parents_of(nk)
+    A = np.concatenate([(1.2 / max(1, nx[dad[k]])) * rng.random(nx[k] * nx[dad[k]]) for k in range(1, Nn)])
+    B = np.concatenate([rng.random(nx[k] * nu[dad[k]]) for k in range(1, Nn)])
+    b = 0.1 * rng.random(int(nx[1:].sum()))
+    sx, su = int(nx.sum()), int(nu.sum())
+    xmin = -P.INF * np.ones(sx)
+    xmax = P.INF * np.ones(sx)
+    x0 = rng.random(nx[0])
+    xmin[:nx[0]] = x0
+    xmax[:nx[0]] = x0
+    return P.FlatProblem(
+        name=f"shaped_qp(Nn={Nn},seed={seed})", nk=nk, nx=nx, nu=nu, A=A, B=B, b=b,
+        Qd=1.0 + 9.0 * rng.random(sx), Rd=0.5 + rng.random(su), q=rng.random(sx) - 0.5, r=rng.random(su) - 0.5,
+        xmin=xmin, xmax=xmax, umin=-ubound * np.ones(su), umax=ubound * np.ones(su))
+
+
+def dense_shaped_qp(nk, nx, nu, seed) -> dict:
+    """The same tree with full Q, R, S on every node (H_k = diag(Qd, Rd) + M M', M of scale 0.3), column major as
+    tqgpu_set_objective_mixed and the oracle's solve_dense take them; the clipping problem's fields are kept."""
+    f = shaped_qp(nk, nx, nu, seed, ubound=1.0)
+    d = {k: np.array(v, copy=True) for k, v in f.as_dict().items()}
+    rng = np.random.Generator(np.random.PCG64(seed + 7919))
+    xo, uo = offsets(d)
+    Q, R, S = [], [], []
+    for k in range(len(d["nk"])):
+        a, m = int(d["nx"][k]), int(d["nu"][k])
+        M = 0.3 * rng.standard_normal((a + m, a + m))
+        H = np.diag(np.concatenate([d["Qd"][xo[k]:xo[k + 1]], d["Rd"][uo[k]:uo[k + 1]]])) + M @ M.T
+        Q.append(H[:a, :a].ravel(order="F")); R.append(H[a:, a:].ravel(order="F")); S.append(H[a:, :a].ravel(order="F"))
+    d["Q"], d["R"], d["S"] = np.concatenate(Q), np.concatenate(R), np.concatenate(S)
+    return d

@@ -9,7 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from helpers import assert_solution_close, product_qp_from_lti
+from helpers import assert_solution_close, bounds_vec, certify, global_kkt, offsets, product_qp_from_lti
 from treeqp_amd import problems as P
 
 pytestmark = pytest.mark.gpu
@@ -34,10 +34,6 @@ def gpu(capi):
 # problem construction and an independent certificate
 # ---------------------------------------------------------------------------------------------------------------------------
 
-def offsets(d):
-    return np.concatenate([[0], np.cumsum(d["nx"])]), np.concatenate([[0], np.cumsum(d["nu"])])
-
-
 def with_dense_blocks(d):
     """flat clipping QP -> the same QP with Q, R, S as dense (diagonal) blocks, as tqgpu_set_objective_mixed takes them"""
     d = {k: np.array(v, copy=True) for k, v in d.items()}
@@ -55,78 +51,6 @@ def stage_of(nk):
     for k in range(1, len(nk)):
         st[k] = st[dad[k]] + 1
     return st
-
-
-def global_kkt(d, fixed=None):
-    """Solve the equality-constrained QP of the whole tree in numpy: min 1/2 z'Hz + g'z s.t. the dynamics and z_i = bound_i on the
-    entries `fixed` (dict index -> value).  z = [x | u].  Returns z and the multipliers of the fixed entries (>= 0 on a lower bound)."""
-    nk, nx, nu = [np.asarray(d[k], dtype=int) for k in ("nk", "nx", "nu")]
-    Nn = len(nk)
-    xo, uo = offsets(d)
-    SX, SU = int(xo[-1]), int(uo[-1])
-    n = SX + SU
-    H = np.zeros((n, n))
-    qo = ro = so = 0
-    for k in range(Nn):
-        a, m = int(nx[k]), int(nu[k])
-        Q = d["Q"][qo:qo + a * a].reshape((a, a), order="F"); qo += a * a
-        R = d["R"][ro:ro + m * m].reshape((m, m), order="F"); ro += m * m
-        S = d["S"][so:so + m * a].reshape((m, a), order="F"); so += m * a
-        ix, iu = np.arange(xo[k], xo[k + 1]), SX + np.arange(uo[k], uo[k + 1])
-        H[np.ix_(ix, ix)] = Q; H[np.ix_(iu, iu)] = R; H[np.ix_(iu, ix)] = S; H[np.ix_(ix, iu)] = S.T
-    g = np.concatenate([d["q"], d["r"]])
-    dad = P.parents_of(nk)
-    rows, rhs = [], []
-    ao = bo = lo = 0
-    for k in range(1, Nn):
-        p = dad[k]
-        A = d["A"][ao:ao + nx[k] * nx[p]].reshape((nx[k], nx[p]), order="F"); ao += nx[k] * nx[p]
-        B = d["B"][bo:bo + nx[k] * nu[p]].reshape((nx[k], nu[p]), order="F"); bo += nx[k] * nu[p]
-        b = d["b"][lo:lo + nx[k]]; lo += nx[k]
-        C = np.zeros((nx[k], n))
-        C[:, xo[k]:xo[k + 1]] = -np.eye(nx[k])
-        C[:, xo[p]:xo[p + 1]] = A
-        C[:, SX + uo[p]:SX + uo[p + 1]] = B
-        rows.append(C); rhs.append(-b)
-    fixed = fixed or {}
-    fi = sorted(fixed)
-    for i in fi:
-        e = np.zeros((1, n)); e[0, i] = 1.0
-        rows.append(e); rhs.append([fixed[i]])
-    C = np.vstack(rows) if rows else np.zeros((0, n))
-    c = np.concatenate([np.atleast_1d(v) for v in rhs]) if rhs else np.zeros(0)
-    m = C.shape[0]
-    K = np.block([[H, C.T], [C, np.zeros((m, m))]])
-    sol = np.linalg.solve(K, np.concatenate([-g, c]))
-    z, nu_ = sol[:n], sol[n:]
-    mu = -nu_[m - len(fi):] if fi else np.zeros(0)
-    return z, dict(zip(fi, mu))
-
-
-def bounds_vec(d):
-    return np.concatenate([d["xmin"], d["umin"]]), np.concatenate([d["xmax"], d["umax"]])
-
-
-def certify(d, sol, tol=1e-9):
-    """From the returned active set, solve the tree's KKT system in numpy: same x, u; multipliers of the right sign; x, u feasible.
-    Returns the number of active bounds."""
-    z = np.concatenate([sol["x"], sol["u"]])
-    lo, hi = bounds_vec(d)
-    assert np.all(z >= lo - 1e-12) and np.all(z <= hi + 1e-12), "x, u leave the box"
-    fixed = {int(i): float(lo[i]) for i in np.flatnonzero(z == lo)}
-    fixed.update({int(i): float(hi[i]) for i in np.flatnonzero(z == hi)})
-    zc, mu = global_kkt(d, fixed)
-    scale = max(1.0, float(np.max(np.abs(zc))))
-    assert np.max(np.abs(zc - z)) / scale < tol, f"|z - z_kkt| = {np.max(np.abs(zc - z)):.3e}"
-    for i, m in mu.items():
-        mscale = max(1.0, abs(m))
-        if lo[i] == hi[i]:
-            continue
-        if z[i] == lo[i]:
-            assert m >= -tol * mscale, f"entry {i} on its lower bound with multiplier {m:.3e}"
-        else:
-            assert m <= tol * mscale, f"entry {i} on its upper bound with multiplier {m:.3e}"
-    return len(fixed)
 
 
 def boxes_around(d, z_f, z_unc, margin=0.05):

@@ -511,6 +511,21 @@ class TqGpu:
         2 persistent single launch, 3 single-workgroup persistent launch."""
         return int(lib().tqgpu_uses_fused_path(self.h))
 
+    PLAN_FLAGS = ("wide", "wide_small", "w3", "w3_sgp", "w3_merge", "fwd_chain", "fuse", "persist", "persist_one", "gpersist",
+                  "gp_state_lds", "gp_const_lds", "gp_tables_lds", "gp_small16", "gp_small8", "dense", "box",
+                  "last_single_wg")
+
+    @property
+    def plan(self) -> dict:
+        """The kernel variants tqgpu_create and the last tqgpu_set_objective_mixed chose, and whether the last solve ran the
+        single-workgroup kernel (tqgpu_debug_plan): name -> bool for each
+        of PLAN_FLAGS (bit i of the mask is PLAN_FLAGS[i]), and sgp_accs, the children's entries k_sgp keeps in LDS per parent."""
+        f, a = C.c_uint(), C.c_int()
+        self._chk(lib().tqgpu_debug_plan(self.h, C.byref(f), C.byref(a)))
+        out = {n: bool(f.value >> i & 1) for i, n in enumerate(self.PLAN_FLAGS)}
+        out["sgp_accs"] = a.value
+        return out
+
     def _chk(self, rc):
         if rc != 0:
             raise RuntimeError(f"tqgpu call failed ({rc}): {lib().tqgpu_last_error().decode()}")

@@ -1461,6 +1461,7 @@ struct tqgpu_solver {
     int sum_nx = 0, sum_nu = 0, sum_lam = 0, sum_A = 0, sum_B = 0, sum_W = 0, sum_Ut = 0, nx0 = 0;
     size_t lds_stage = 0, lds_hess = 0, lds_factor = 0, lds_forward = 0, lds_dense = 0;
     bool wide = false;              /* larger blocks (16 < d <= 64): workgroup-per-block MFMA kernels (tdunes_wide.hpp) */
+    bool wide_small = false;        /* ... taken by a tree of small blocks (d <= 16) too wide for the single-workgroup kernel */
     size_t lds_hess_w = 0, lds_factor_w = 0, lds_forward_w = 0;
     unsigned long long *fw_words = nullptr;   /* launch-per-phase path: the steps of a forward sweep as tagged words (k_forward_all_w), [sum_nx][2] */
     unsigned fw_epoch = 0;              /* tag of the last fused forward launch */
@@ -1694,7 +1695,6 @@ int build_tables(tqgpu_solver *s) {
     for (int k = 0; k < Nn; k++) {
         const size_t d = s->bdim[k], nz = s->nx[k] + s->nu[k];
         s->lds_stage = std::max(s->lds_stage, (d + s->nx[k] + 2 * (s->nx[k] + s->nu[k]) + 2) * sizeof(double));
-        s->lds_dense = std::max(s->lds_dense, ((size_t)(s->nx[k] + s->nu[k]) * (s->nx[k] + s->nu[k] + 1) + 2) * sizeof(double));
         if (k < s->Np) {
             s->lds_hess = std::max(s->lds_hess, (2 * d * nz + 2) * sizeof(double));
             const size_t R = d + 1 + (k > 0 ? s->nx[k] : 0), ld = R | 1;
@@ -1711,6 +1711,7 @@ int build_tables(tqgpu_solver *s) {
             s->lds_factor_w = std::max(s->lds_factor_w, wide_lds_factor(d, nxi));
             s->lds_forward_w = std::max(s->lds_forward_w, wide_lds_forward(d));
         }
+        s->wide_small = false;
         s->wide = dmax > 16 && dmax <= 64 && rmax <= 128 && nzmax <= 32;      /* k_hess_w keeps a parent's entries of P for 8 k-steps of 4 in registers */
         /* Trees of SMALL blocks (d <= 16) that are too wide for the single-workgroup kernel (a level of more than 6 x 16 blocks) take the
          * workgroup-per-block kernels as well: three launches per Newton iteration instead of the five to eight of the launch-per-phase
@@ -1719,11 +1720,11 @@ int build_tables(tqgpu_solver *s) {
             int widest = 0;
             for (int l = 0; l + 1 < (int)s->lvl_first.size(); l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
             const char *e = getenv("TREEQP_AMD_SMALL_WIDE");
-            if (!s->wide && dmax >= 3 && dmax <= 16 && widest > 6 * 16 && rmax <= 128 && nzmax <= 32 && !(e && atoi(e) == 0)) s->wide = true;
+            if (!s->wide && dmax >= 3 && dmax <= 16 && widest > 6 * 16 && rmax <= 128 && nzmax <= 32 && !(e && atoi(e) == 0)) s->wide = s->wide_small = true;
         }
     }
     const size_t lim = 160 * 1024;
-    if (s->lds_factor > lim || s->lds_hess > lim)
+    if (s->lds_factor > lim || s->lds_hess > lim || s->lds_forward > lim)
         return fail(TQGPU_EUNSUPPORTED, "dual Hessian block too large for the LDS-resident kernels (160 KiB per workgroup)");
     return TQGPU_OK;
 }
@@ -2443,7 +2444,7 @@ extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *n
          * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
          * construction) stand aside */
         s->strict_sum = getenv("TREEQP_AMD_STRICT_SUM") && atoi(getenv("TREEQP_AMD_STRICT_SUM")) != 0;
-        if (s->strict_sum) { s->use_fast = 0; s->wide = false; }          /* (the MFMA kernels of the wide-block class sum in tile order) */
+        if (s->strict_sum) { s->use_fast = 0; s->wide = s->wide_small = false; }          /* (the MFMA kernels of the wide-block class sum in tile order) */
         s->use_persist_orig = s->use_persist;
         const char *ch = getenv("TREEQP_AMD_CHUNK");
         if (ch && atoi(ch) > 0) s->chunk = atoi(ch);
@@ -2792,6 +2793,19 @@ static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_mem
     if (s->fuse_ok && p < 3 && !s->sharded && !s->box) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
     return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
+/* the kernel variants tqgpu_create and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
+ * reads fields, changes nothing */
+extern "C" int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs) {
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    const bool bits[] = {s->wide, s->wide_small, s->w3_ok, s->w3_sgp, s->w3_merge, s->d_anc != nullptr, s->fuse_ok, s->persist_ok,
+                         s->persist_one, s->gpersist_ok, s->gp_in_lds, s->gp_const_in_lds, s->gp_tab_in_lds, s->gp_small16, s->gp_small8,
+                         s->dense, s->box, s->solve_no > 0 && s->route == Route::SINGLE_WG};
+    unsigned f = 0;
+    for (unsigned i = 0; i < sizeof(bits) / sizeof(bits[0]); i++) f |= bits[i] ? 1u << i : 0u;
+    if (flags) *flags = f;
+    if (sgp_accs) *sgp_accs = s->sgp_accs;
+    return TQGPU_OK;
+}
 extern "C" int tqgpu_uses_fused_path(const tqgpu_solver *s) {
     if (!s) return 0;
     tqgpu_opts o{}; o.maxIter = 1;          /* the route under default options */
@@ -2910,11 +2924,19 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     std::vector<double> H((size_t)std::max(s->poff[s->Nn], 1), 0.0);
     std::vector<double> Qd((size_t)std::max(s->sum_nx, 1), 0.0), Rd((size_t)std::max(s->sum_nu, 1), 0.0);
     std::vector<int> kd((size_t)s->Nn, 1);
+    int rc0 = TQGPU_OK;
     if (kind) for (int k = 0; k < s->Nn; k++) {
         if (kind[k] < 0 || kind[k] > 2) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: kind must be 0, 1 or 2");
         kd[(size_t)k] = kind[k];
     }
-    size_t lds_box = 0;
+    size_t lds_box = 0, lds_dense = 0;
+    for (int k = 0; k < s->Nn; k++) {
+        /* k_dense_init holds a dense node's H (nz x nz) and its pivots in LDS */
+        const size_t nzd = (size_t)s->nx[k] + s->nu[k];
+        if (kd[(size_t)k]) lds_dense = std::max(lds_dense, (nzd * (nzd + 1) + 2) * sizeof(double));
+    }
+    if (lds_dense > 160 * 1024) return fail(TQGPU_EUNSUPPORTED, "dense node too large for the LDS-resident factorization of H (160 KiB per workgroup)");
+    if ((rc0 = allow_lds(k_dense_init, lds_dense))) return rc0;
     for (int k = 0; k < s->Nn; k++) {
         if (kd[(size_t)k] != 2) continue;
         const size_t nz = (size_t)s->nx[k] + s->nu[k];
@@ -2968,6 +2990,7 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
      * on clipping nodes */
     H2D(s->Qd, Qd.data(), s->sum_nx); H2D(s->Rd, Rd.data(), s->sum_nu);
     HIP_TRY(hipStreamSynchronize(s->stream));
+    s->lds_dense = lds_dense;
     s->dense = true; s->need_dense_init = true; s->D.dense = 1; s->need_init = true;
     s->use_fast = 0;                                       /* per-node dense blocks: generic kernels */
     return TQGPU_OK;
