@@ -1,4 +1,5 @@
-"""The tree shapes on both sides of every kernel-selection limit of tqgpu_create (tdunes_device.hip), shared by the CPU reference
+"""The tree shapes on both sides of every kernel-selection limit of tqgpu_create's steps (detect_shape, setup_per_phase, setup_wide3,
+setup_persist, setup_single_wg in tdunes_device.hip), shared by the CPU reference
 checks (test_limits_reference.py) and the device tests (test_gpu_limits.py).
 
 A shape is written as a nested node (nx, nu, [children]); `flatten` lays it out breadth first.  Each row of ROWS is

@@ -1,4 +1,5 @@
-"""The device path on both sides of every kernel-selection limit of tqgpu_create (tdunes_device.hip): dual block size, node
+"""The device path on both sides of every kernel-selection limit of tqgpu_create's steps (detect_shape, setup_per_phase, setup_wide3,
+setup_persist, setup_single_wg in tdunes_device.hip): dual block size, node
 sizes, children per parent, path length, level width, node count and LDS bytes.  Each shape of limit_shapes.ROWS is solved on the
 default route and with TREEQP_AMD_PATH=generic; tqgpu_debug_plan shows that it took the variant on its side of the limit, and
 verdict, iterations, line-search trials and solution equal the CPU oracle's."""

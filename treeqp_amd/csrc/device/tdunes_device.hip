@@ -1454,11 +1454,60 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 enum class Route { PERSIST, SINGLE_WG, TIERED, THREE_LAUNCH, FUSED_TAILS, PER_PHASE };
 static bool single_launch(Route r) { return r == Route::PERSIST || r == Route::SINGLE_WG; }      /* verdict through the result block */
 
+/* The device and pinned host memory of a mirror.  What is allocated through it is freed by tqgpu_destroy (free_all) unless it was given
+ * back before (release); the named pointers of tqgpu_solver are views.  A failed call has set the error text, with `name` in it. */
+struct Owned {
+    std::vector<void *> dev, pinned;
+    enum Fill { RAW, ZEROED, FINE_GRAINED };      /* FINE_GRAINED: hipExtMallocWithFlags (tqgpu_pshard_init) */
+    static int failed(int code, const char *name, hipError_t e) { return fail(code, std::string("allocation of ") + name + " failed: " + hipGetErrorString(e)); }
+    template <typename T>
+    int device(T *&p, size_t bytes, int code, const char *name, Fill fill = RAW, const void *src = nullptr) {
+        void *q = nullptr;
+        hipError_t e = fill == FINE_GRAINED ? hipExtMallocWithFlags(&q, bytes, hipDeviceMallocFinegrained) : hipMalloc(&q, bytes);
+        if (e != hipSuccess) return failed(code, name, e);
+        dev.push_back(q); p = static_cast<T *>(q);
+        if (fill == ZEROED) e = hipMemset(q, 0, bytes);
+        if (src) e = hipMemcpy(q, src, bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess ? TQGPU_OK : failed(code, name, e);
+    }
+    template <typename T> int zeroed(T *&p, size_t bytes, int code, const char *name) { return device(p, bytes, code, name, ZEROED); }
+    template <typename T> int upload(T *&p, const void *src, size_t bytes, int code, const char *name) { return device(p, bytes, code, name, RAW, src); }
+    template <typename T>
+    int host(T *&p, size_t bytes, const char *name) {
+        void *q = nullptr;
+        hipError_t e = hipHostMalloc(&q, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return failed(TQGPU_ENOMEM, name, e);
+        pinned.push_back(q); p = static_cast<T *>(q);
+        return TQGPU_OK;
+    }
+    /* a buffer that is replaced during the mirror's life (nullptr: nothing to do) */
+    template <typename T>
+    void release(T *&p) {
+        auto d = std::find(dev.begin(), dev.end(), (void *)p), h = std::find(pinned.begin(), pinned.end(), (void *)p);
+        if (d != dev.end()) { (void)hipFree(*d); dev.erase(d); }
+        else if (h != pinned.end()) { (void)hipHostFree(*h); pinned.erase(h); }
+        p = nullptr;
+    }
+    void free_all() {
+        for (void *q : dev) (void)hipFree(q);
+        for (void *q : pinned) (void)hipHostFree(q);
+    }
+};
+
+/* the creation-time switches: read from the environment once per tqgpu_create (read_switches), tested as fields by its steps */
+struct Switches {
+    bool generic, tiered, strict_sum, fwd_levels, bwd_levels, small_wide;
+    bool no_fuse, no_wide3, no_sgp, no_fwd_chain, no_fwd_merge, no_stage16, gp_no_groups, no_persist_one, verbose, has_lds_pad, has_nap;
+    int chunk, lds_pad, capacity_margin, nap;
+};
+
 struct tqgpu_solver {
+    Owned mem;
+    Switches sw{};
     int device = 0;
     int Nn = 0, Np = 0, Nh = 0;
     std::vector<int> nk, nx, nu, dad, stage, kid0, xoff, uoff, aoff, boff, pos, bdim, woff, utoff, lvl_first;
-    int sum_nx = 0, sum_nu = 0, sum_lam = 0, sum_A = 0, sum_B = 0, sum_W = 0, sum_Ut = 0, nx0 = 0;
+    int sum_nx = 0, sum_nu = 0, sum_lam = 0, sum_A = 0, sum_B = 0, sum_W = 0, sum_Ut = 0, nx0 = 0, nxmax = 0;
     size_t lds_stage = 0, lds_hess = 0, lds_factor = 0, lds_forward = 0, lds_dense = 0;
     bool wide = false;              /* larger blocks (16 < d <= 64): workgroup-per-block MFMA kernels (tdunes_wide.hpp) */
     bool wide_small = false;        /* ... taken by a tree of small blocks (d <= 16) too wide for the single-workgroup kernel */
@@ -1719,8 +1768,7 @@ int build_tables(tqgpu_solver *s) {
         {
             int widest = 0;
             for (int l = 0; l + 1 < (int)s->lvl_first.size(); l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
-            const char *e = getenv("TREEQP_AMD_SMALL_WIDE");
-            if (!s->wide && dmax >= 3 && dmax <= 16 && widest > 6 * 16 && rmax <= 128 && nzmax <= 32 && !(e && atoi(e) == 0)) s->wide = s->wide_small = true;
+            if (!s->wide && dmax >= 3 && dmax <= 16 && widest > 6 * 16 && rmax <= 128 && nzmax <= 32 && s->sw.small_wide) s->wide = s->wide_small = true;
         }
     }
     const size_t lim = 160 * 1024;
@@ -2063,7 +2111,7 @@ static int nap_for_grid(int workgroups) {
     static const int t1 = getenv("TREEQP_AMD_NAP_T1") ? atoi(getenv("TREEQP_AMD_NAP_T1")) : 128;
     return workgroups > t1 ? 1 : 0;
 }
-int setup_persist(tqgpu_solver *s, int device) {
+int setup_persist(tqgpu_solver *s) {
     s->persist_ok = false;
     if (s->fast < 0 || s->n_tiers > 8) return TQGPU_OK;
     PGeom &G = s->geom;
@@ -2073,7 +2121,7 @@ int setup_persist(tqgpu_solver *s, int device) {
     G.G = wg;
     int per_cu = 0, per_cu_r = 1 << 20, per_cu_one = 0;      /* _r: the variant that can keep factors (checkLastActiveSet == 2); _one: the build for one workgroup per CU */
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, s->device));
     if (!s->mstage) {
         switch (s->fast) {
 #define X(idx, nx, nu, md)                                                                                                   \
@@ -2101,8 +2149,8 @@ int setup_persist(tqgpu_solver *s, int device) {
             default: break;
         }
     }
-    if (const char *e = getenv("TREEQP_AMD_LDS_PAD")) {      /* experiment: force fewer workgroups per CU */
-        s->lds_persist += (size_t)atoi(e) * 1024;
+    if (s->sw.has_lds_pad) {      /* experiment: force fewer workgroups per CU */
+        s->lds_persist += (size_t)s->sw.lds_pad * 1024;
         switch (s->fast) {
 #define X(idx, nx, nu, md) case idx: if (!s->mstage) { allow_lds(f_persist<nx, nu, md, false>, s->lds_persist); HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->lds_persist)); } break;
             FAST_TABLE(X)
@@ -2118,14 +2166,13 @@ int setup_persist(tqgpu_solver *s, int device) {
     /* (rounds 1 - 2 kept half a CU-load in hand; the admission rule of the MI355X guide -- min(API answer, 8, 800 / (sgpr rounded up to
      * 16 + 16)) per CU -- is what per_cu_r holds, the grid is admitted CU by CU, and a launch that is not resident after all ends in the
      * bounded waits' timeout and the launch-per-tier redo, not in a hang: no margin.  C2 batched: 5 trees 99 k it/s -> 7 trees 133 k.) */
-    int margin = 0;
-    if (const char *e = getenv("TREEQP_AMD_CAPACITY_MARGIN")) margin = atoi(e);      /* experiment */
+    const int margin = s->sw.capacity_margin;      /* experiment */
     const int capacity = per_cu <= 1 ? prop.multiProcessorCount * per_cu : prop.multiProcessorCount * per_cu - margin;
-    if (getenv("TREEQP_AMD_VERBOSE")) fprintf(stderr, "[treeqp_amd] persistent path: %d workgroups, %d per CU possible, capacity %d\n", G.G, per_cu, capacity);
+    if (s->sw.verbose) fprintf(stderr, "[treeqp_amd] persistent path: %d workgroups, %d per CU possible, capacity %d\n", G.G, per_cu, capacity);
     s->co_capacity = std::max(1, capacity);
     s->n_cu = prop.multiProcessorCount;
     /* the build for ONE workgroup per CU (f_persist_one: more registers, 2 % faster) when the launch fits the device that way */
-    s->persist_one = per_cu_one >= 1 && G.G <= prop.multiProcessorCount * std::min(per_cu_one, 1) && !getenv("TREEQP_AMD_NO_PERSIST_ONE");
+    s->persist_one = per_cu_one >= 1 && G.G <= prop.multiProcessorCount * std::min(per_cu_one, 1) && !s->sw.no_persist_one;
     if (per_cu < 1 || G.G > capacity) return TQGPU_OK;
     /* hand-over buffers (tagged 64-bit words, see tdunes_persist.hpp); zeroed once, never reset */
     const int nx0 = s->nx[0];
@@ -2136,8 +2183,7 @@ int setup_persist(tqgpu_solver *s, int device) {
     const size_t n_verdict = 16;
     const size_t n_anc = (size_t)s->Np * (size_t)(nx0 * s->fMD) * (nx0 + 1) * 2;      /* forward records [z0 | M] of the blocks, for the bottom tier's walk down its path (tdunes_persist.hpp, p_forward_tier) */
     const size_t bytes = (n_sch + n_dlt + n_ndt + n_parts + n_errs + 32 + n_bparts + n_sgt + n_rfl + n_verdict + n_anc) * sizeof(unsigned long long);
-    HIP_TRY(hipMalloc(&s->sync_slab, bytes));
-    HIP_TRY(hipMemset(s->sync_slab, 0, bytes));
+    if (int rc = s->mem.zeroed(s->sync_slab, bytes, TQGPU_ENODEVICE, "the hand-over slab")) return rc;
     HIP_TRY(hipDeviceSynchronize());          /* (a device memset may return before it has happened, and the solver's non-blocking stream does not wait for the null stream) */
     s->sync_bytes = bytes;
     unsigned long long *w = static_cast<unsigned long long *>(s->sync_slab);
@@ -2152,15 +2198,11 @@ int setup_persist(tqgpu_solver *s, int device) {
     s->psync.verdict = s->psync.rfl + n_rfl;
     s->psync.anc = s->psync.verdict + n_verdict;
     s->psync.base = w; s->psync.npeer = 1; s->psync.relay_wg = -1; s->psync.anc_local = 1;
-    HIP_TRY(hipMalloc(&s->d_peers, 8 * sizeof(unsigned long long *)));
     for (int r = 0; r < 8; r++) s->h_peers[r] = w;
-    HIP_TRY(hipMemcpy(s->d_peers, s->h_peers, sizeof(s->h_peers), hipMemcpyHostToDevice));
+    if (int rc = s->mem.upload(s->d_peers, s->h_peers, sizeof(s->h_peers), TQGPU_ENODEVICE, "the table of peer slabs")) return rc;
     s->psync.peers = s->d_peers;
     s->psync.seq = 0; s->psync.trip = 0;
-    {
-        const char *e = getenv("TREEQP_AMD_NAP");
-        s->psync.nap = e ? atoi(e) : nap_for_grid(G.G);
-    }
+    s->psync.nap = s->sw.has_nap ? s->sw.nap : nap_for_grid(G.G);
     /* XCD-aware placement: the hardware deals workgroups round-robin over the 8 XCDs (workgroup b -> XCD b % 8)
      * and every XCD has its own L2.  A tier subtree talks to its parent and its children only, so whole
      * families go to one XCD: each subtree of the lowest tier with at most 8 subtrees picks an XCD, everything
@@ -2187,14 +2229,13 @@ int setup_persist(tqgpu_solver *s, int device) {
          * the UPPER tiers -- they work while the bottom tier waits and vice versa -- instead of two bottom-tier subtrees
          * halving each other on the critical path: plain tier order (bottom tier first). */
         if (Gn > prop.multiProcessorCount) for (int b = 0; b < Gn; b++) map[b] = b;
-        HIP_TRY(hipMalloc(&s->wg_map, sizeof(int) * (size_t)Gn));
-        HIP_TRY(hipMemcpy(s->wg_map, map.data(), sizeof(int) * (size_t)Gn, hipMemcpyHostToDevice));
+        if (int rc = s->mem.upload(s->wg_map, map.data(), sizeof(int) * (size_t)Gn, TQGPU_ENODEVICE, "the workgroup placement")) return rc;
         G.wg_of_block = s->wg_map;
     }
     /* packed constants + the start/end view of the mirror */
     const int nz = nx0 + s->nu[0];
     const size_t n_ab = (size_t)(s->Nn - 1) * nx0 * nz, n_cst = (size_t)s->Nn * 16 * 5;
-    HIP_TRY(hipMalloc(&s->pconst_slab, (n_ab + n_cst) * sizeof(double) + sizeof(PDump) + 256));
+    if (int rc = s->mem.device(s->pconst_slab, (n_ab + n_cst) * sizeof(double) + sizeof(PDump) + 256, TQGPU_ENODEVICE, "the packed constants")) return rc;
     double *pc = static_cast<double *>(s->pconst_slab);
     s->pab = pc; s->pcst = pc + n_ab;
     PDump hd;
@@ -2404,58 +2445,72 @@ __global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, in
     if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
 }
 
-}  // namespace
+/* ---- tqgpu_create step by step: each step takes the mirror and returns a TQGPU_* code ---- */
+/* THE list of creation-time switches.  Read per tqgpu_create call, never cached: tests and A/B runs change them between two mirrors. */
+void read_switches(Switches &w) {
+    auto set = [](const char *name) { return getenv(name) != nullptr; };
+    auto is = [](const char *name, const char *value) { const char *e = getenv(name); return e && strcmp(e, value) == 0; };
+    auto num = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+    w.generic = is("TREEQP_AMD_PATH", "generic");                /* launch-per-phase kernels only; no phantom root for x0-eliminated trees */
+    w.tiered = is("TREEQP_AMD_PATH", "tiered");                  /* uniform trees: launches per tier instead of the persistent launch */
+    w.strict_sum = num("TREEQP_AMD_STRICT_SUM", 0) != 0;         /* reference-order sums (Data::strict) */
+    w.chunk = num("TREEQP_AMD_CHUNK", 0);                        /* > 0: Newton iterations enqueued per status read-back */
+    w.fwd_levels = is("TREEQP_AMD_FWD", "levels");               /* forward sweep: one launch per tree level (the round-1 protocol) */
+    w.bwd_levels = is("TREEQP_AMD_BWD", "levels");               /* backward sweep: one launch per tree level */
+    w.no_fuse = set("TREEQP_AMD_NO_FUSE");                       /* small trees: the reductions as launches of their own */
+    w.no_wide3 = set("TREEQP_AMD_NO_WIDE3");                     /* wide-block class: launch-per-phase kernels instead of the three-launch family */
+    w.no_sgp = set("TREEQP_AMD_NO_SGP");                         /* three-launch family: k_sg (a wave per node) instead of k_sgp */
+    w.no_fwd_chain = set("TREEQP_AMD_NO_FWD_CHAIN");             /* ... forward sweep with hand-overs (no k_fwd3c) */
+    w.no_fwd_merge = set("TREEQP_AMD_NO_FWD_MERGE");             /* ... forward sweep as a launch of its own */
+    w.no_stage16 = set("TREEQP_AMD_NO_STAGE16");                 /* single-workgroup kernel: one node per wave in the node sweeps */
+    w.gp_no_groups = set("TREEQP_AMD_GP_NO_GROUPS");             /* single-workgroup kernel: one block per wave on every level */
+    w.small_wide = num("TREEQP_AMD_SMALL_WIDE", 1) != 0;         /* =0: wide trees of small blocks stay on the launch-per-phase kernels */
+    w.has_lds_pad = set("TREEQP_AMD_LDS_PAD"); w.lds_pad = num("TREEQP_AMD_LDS_PAD", 0);      /* experiment: KiB of LDS added to a persistent workgroup, to force fewer per CU */
+    w.capacity_margin = num("TREEQP_AMD_CAPACITY_MARGIN", 0);    /* experiment: workgroups kept free in the co-residency test */
+    w.no_persist_one = set("TREEQP_AMD_NO_PERSIST_ONE");         /* persistent path: never the one-workgroup-per-CU build */
+    w.has_nap = set("TREEQP_AMD_NAP"); w.nap = num("TREEQP_AMD_NAP", 0);      /* persistent path: poll naps of the bottom tier off (0) / on (1) instead of by launch size */
+    w.verbose = set("TREEQP_AMD_VERBOSE");                       /* the persistent path's geometry on stderr */
+}
 
-extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *nk, const int *nx, const int *nu) {
-    if (!out || Nn < 2 || !nk || !nx || !nu) return fail(TQGPU_EINVAL, "tqgpu_create: bad arguments");
-    *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0)
-        return fail(TQGPU_ENODEVICE, std::string("no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") + "); the tdunes hot path has no CPU fallback");
-    if (device < 0) HIP_TRY(hipGetDevice(&device));
-    if (device >= ndev) return fail(TQGPU_EINVAL, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-
-    tqgpu_solver *s = new tqgpu_solver();
-    { static std::atomic<unsigned long> next_uid{1}; s->uid = next_uid.fetch_add(1); }
-    s->device = device; s->Nn = Nn;
-    s->nk.assign(nk, nk + Nn); s->nx.assign(nx, nx + Nn); s->nu.assign(nu, nu + Nn);
+/* tree tables, the uniform / multistage / x0-padded form, and what the switches take away from it */
+int detect_shape(tqgpu_solver *s) {
+    auto detect = [s] { detect_fast(s); if (s->fast < 0) detect_multistage(s); };
     int rc = build_tables(s);
-    if (rc != TQGPU_OK) { delete s; return rc; }
-    detect_fast(s);
-    if (s->fast < 0) detect_multistage(s);
-    if (s->fast < 0 && nx[0] == 0 && Nn > 1 && nx[1] > 0 && !(getenv("TREEQP_AMD_PATH") && strcmp(getenv("TREEQP_AMD_PATH"), "generic") == 0)) {
+    if (rc != TQGPU_OK) return rc;
+    detect();
+    if (s->fast < 0 && s->nx[0] == 0 && s->Nn > 1 && s->nx[1] > 0 && !s->sw.generic) {
         /* x0 eliminated (tree_qp_in_eliminate_x0: nx[0] = 0, the form every MPC caller solves).  If the tree would be
          * uniform / multistage with a full root node, give the root nx phantom states pinned to zero (bounds [0, 0],
          * unit weight, no linear term, zero A columns for the root's children): the same QP, and it takes the
          * persistent path.  The phantom entries sit in front of every x-sized array (A: in front of the first edges)
-         * and never leave the device: the setters / getters below skip them. */
-        s->nx[0] = nx[1];
-        if (build_tables(s) == TQGPU_OK) { detect_fast(s); if (s->fast < 0) detect_multistage(s); }
-        if (s->fast >= 0) { s->x_pad = nx[1]; s->A_pad = nk[0] * nx[1] * nx[1]; }
-        else { s->nx[0] = 0; s->fast = -1; s->mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) { delete s; return rc; } }
+         * and never leave the device: the setters / getters skip them. */
+        const int nx1 = s->nx[1];
+        s->nx[0] = nx1;
+        if (build_tables(s) == TQGPU_OK) detect();
+        if (s->fast >= 0) { s->x_pad = nx1; s->A_pad = s->nk[0] * nx1 * nx1; }
+        else { s->nx[0] = 0; s->fast = -1; s->mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
     }
-    {
-        const char *env = getenv("TREEQP_AMD_PATH");
-        if (env && strcmp(env, "generic") == 0) { s->use_fast = 0; s->use_gpersist = 0; }
-        if (env && strcmp(env, "tiered") == 0) s->use_persist = 0;
-        /* reference-order sums (strict_sum / strict_block_dots): the launch-per-phase kernels and the single-workgroup kernel carry them;
-         * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
-         * construction) stand aside */
-        s->strict_sum = getenv("TREEQP_AMD_STRICT_SUM") && atoi(getenv("TREEQP_AMD_STRICT_SUM")) != 0;
-        if (s->strict_sum) { s->use_fast = 0; s->wide = s->wide_small = false; }          /* (the MFMA kernels of the wide-block class sum in tile order) */
-        s->use_persist_orig = s->use_persist;
-        const char *ch = getenv("TREEQP_AMD_CHUNK");
-        if (ch && atoi(ch) > 0) s->chunk = atoi(ch);
-    }
+    if (s->sw.generic) { s->use_fast = 0; s->use_gpersist = 0; }
+    if (s->sw.tiered) s->use_persist = 0;
+    /* reference-order sums (strict_sum / strict_block_dots): the launch-per-phase kernels and the single-workgroup kernel carry them;
+     * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
+     * construction) stand aside */
+    s->strict_sum = s->sw.strict_sum;
+    if (s->strict_sum) { s->use_fast = 0; s->wide = s->wide_small = false; }          /* (the MFMA kernels of the wide-block class sum in tile order) */
+    s->use_persist_orig = s->use_persist;
+    if (s->sw.chunk > 0) s->chunk = s->sw.chunk;
+    s->nxmax = *std::max_element(s->nx.begin(), s->nx.end());
+    return TQGPU_OK;
+}
 
+/* the slab and what points into it: tables, node records, Tree / Data, host mirrors; the stream and the event ring */
+int layout_slab(tqgpu_solver *s) {
     /* one slab for everything */
     Carver cv;
     const size_t I = sizeof(int), Dbl = sizeof(double);
-    const size_t o_dad = cv.take(Nn * I), o_nk = cv.take(Nn * I), o_kid0 = cv.take(Nn * I), o_nx = cv.take(Nn * I), o_nu = cv.take(Nn * I);
-    const size_t o_xoff = cv.take((Nn + 1) * I), o_uoff = cv.take((Nn + 1) * I), o_aoff = cv.take((Nn + 1) * I), o_boff = cv.take((Nn + 1) * I);
-    const size_t o_pos = cv.take(Nn * I), o_bdim = cv.take(Nn * I), o_woff = cv.take((Nn + 1) * I), o_utoff = cv.take((Nn + 1) * I);
+    const size_t o_dad = cv.take(s->Nn * I), o_nk = cv.take(s->Nn * I), o_kid0 = cv.take(s->Nn * I), o_nx = cv.take(s->Nn * I), o_nu = cv.take(s->Nn * I);
+    const size_t o_xoff = cv.take((s->Nn + 1) * I), o_uoff = cv.take((s->Nn + 1) * I), o_aoff = cv.take((s->Nn + 1) * I), o_boff = cv.take((s->Nn + 1) * I);
+    const size_t o_pos = cv.take(s->Nn * I), o_bdim = cv.take(s->Nn * I), o_woff = cv.take((s->Nn + 1) * I), o_utoff = cv.take((s->Nn + 1) * I);
     const size_t SX = s->sum_nx, SU = s->sum_nu;
     const size_t o_A = cv.take(s->sum_A * Dbl), o_B = cv.take(s->sum_B * Dbl), o_b = cv.take(SX * Dbl);
     const size_t o_Qd = cv.take(SX * Dbl), o_q = cv.take(SX * Dbl), o_xmin = cv.take(SX * Dbl), o_xmax = cv.take(SX * Dbl);
@@ -2467,58 +2522,57 @@ extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *n
     const size_t o_lam0 = cv.take(SX * Dbl), o_lam1 = cv.take(SX * Dbl), o_dlam = cv.take(SX * Dbl), o_res = cv.take(SX * Dbl), o_resMod = cv.take(SX * Dbl);
     const size_t o_invd = cv.take(SX * Dbl);
     const size_t o_W = cv.take(s->sum_W * Dbl), o_CW = cv.take(s->sum_W * Dbl), o_Ut = cv.take(s->sum_Ut * Dbl), o_CUt = cv.take(s->sum_Ut * Dbl);
-    const size_t o_fval = cv.take(Nn * Dbl), o_perr = cv.take((SX + Nn + 1) * Dbl), o_pdot = cv.take(Nn * Dbl);
-    const size_t maxnx = (size_t)*std::max_element(s->nx.begin(), s->nx.end());
-    const size_t o_sbuf = cv.take((s->fast >= 0 ? (size_t)Nn * (maxnx * maxnx + maxnx) : 1) * Dbl), o_ybuf = cv.take((SX + 1) * Dbl);
+    const size_t o_fval = cv.take(s->Nn * Dbl), o_perr = cv.take((SX + s->Nn + 1) * Dbl), o_pdot = cv.take(s->Nn * Dbl);
+    const size_t maxnx = (size_t)s->nxmax;
+    const size_t o_sbuf = cv.take((s->fast >= 0 ? (size_t)s->Nn * (maxnx * maxnx + maxnx) : 1) * Dbl), o_ybuf = cv.take((SX + 1) * Dbl);
     const size_t o_mux = cv.take(SX * Dbl), o_muu = cv.take(SU * Dbl);
     const size_t o_lami = cv.take(SX * Dbl);
-    s->poff.assign(Nn + 1, 0);
-    for (int k = 0; k < Nn; k++) s->poff[k + 1] = s->poff[k] + (s->nx[k] + s->nu[k]) * (s->nx[k] + s->nu[k]);
-    const size_t o_kind = cv.take(Nn * I), o_bmask = cv.take(2 * (size_t)Nn * sizeof(unsigned long long));
-    const size_t o_poff = cv.take((Nn + 1) * I), o_Hd = cv.take((size_t)std::max(s->poff[Nn], 1) * Dbl), o_Pd = cv.take((size_t)std::max(s->poff[Nn], 1) * Dbl);
+    s->poff.assign(s->Nn + 1, 0);
+    for (int k = 0; k < s->Nn; k++) s->poff[k + 1] = s->poff[k] + (s->nx[k] + s->nu[k]) * (s->nx[k] + s->nu[k]);
+    const size_t o_kind = cv.take(s->Nn * I), o_bmask = cv.take(2 * (size_t)s->Nn * sizeof(unsigned long long));
+    const size_t o_poff = cv.take((s->Nn + 1) * I), o_Hd = cv.take((size_t)std::max(s->poff[s->Nn], 1) * Dbl), o_Pd = cv.take((size_t)std::max(s->poff[s->Nn], 1) * Dbl);
     const size_t o_ctrl = cv.take(sizeof(Ctrl));
     const size_t o_stamps = cv.take((8 * 32 * 2 + 1024) * sizeof(unsigned long long));   /* + 1024: placement census of the persistent launch (diagnostic builds) */
     s->ls_log_cap = 4096;
     const size_t o_log = cv.take(s->ls_log_cap * I);
     s->slab_bytes = cv.off + 256;
 
-    auto cleanup_fail = [&](int code) { tqgpu_destroy(s); return code; };
-    if (hipMalloc(&s->slab, s->slab_bytes) != hipSuccess) { delete s; return fail(TQGPU_ENOMEM, "hipMalloc failed for the device mirror"); }
-    if (hipMemset(s->slab, 0, s->slab_bytes) != hipSuccess) return cleanup_fail(fail(TQGPU_ENODEVICE, "hipMemset failed"));
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return cleanup_fail(fail(TQGPU_ENODEVICE, "hipStreamCreate failed"));
+    int rc;
+    if ((rc = s->mem.device(s->slab, s->slab_bytes, TQGPU_ENOMEM, "the device mirror"))) return rc;
+    if (hipMemset(s->slab, 0, s->slab_bytes) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipMemset failed");
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipStreamCreate failed");
     { std::lock_guard<std::mutex> lk(g_streams_mu); g_live_streams.insert(s->stream); }
     s->ring_ev0.assign(EV_RING, nullptr); s->ring_ev1.assign(EV_RING, nullptr); s->ring_ok.assign(EV_RING, 0);
     for (int i = 0; i < EV_RING; i++)
-        if (hipEventCreate(&s->ring_ev0[i]) != hipSuccess || hipEventCreate(&s->ring_ev1[i]) != hipSuccess) return cleanup_fail(fail(TQGPU_ENODEVICE, "hipEventCreate failed"));
-    if (hipHostMalloc((void **)&s->h_res, sizeof(HostRes), hipHostMallocDefault) != hipSuccess) return cleanup_fail(fail(TQGPU_ENOMEM, "hipHostMalloc failed"));
+        if (hipEventCreate(&s->ring_ev0[i]) != hipSuccess || hipEventCreate(&s->ring_ev1[i]) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipEventCreate failed");
+    if ((rc = s->mem.host(s->h_res, sizeof(HostRes), "the result block"))) return rc;
     memset(s->h_res, 0, sizeof(HostRes));
     s->h_ctrl = &s->h_res->c;
-    if (hipHostMalloc((void **)&s->h_ls_log, s->ls_log_cap * I, hipHostMallocDefault) != hipSuccess) return cleanup_fail(fail(TQGPU_ENOMEM, "hipHostMalloc failed"));
+    if ((rc = s->mem.host(s->h_ls_log, s->ls_log_cap * I, "the line-search log"))) return rc;
 
     void *base = s->slab;
-#define UP(off, vec) if (hipMemcpy(at<int>(base, off), (vec).data(), (vec).size() * I, hipMemcpyHostToDevice) != hipSuccess) return cleanup_fail(fail(TQGPU_ENODEVICE, "table upload failed"))
+#define UP(off, vec) if (hipMemcpy(at<int>(base, off), (vec).data(), (vec).size() * I, hipMemcpyHostToDevice) != hipSuccess) return fail(TQGPU_ENODEVICE, "table upload failed")
     UP(o_dad, s->dad); UP(o_nk, s->nk); UP(o_kid0, s->kid0); UP(o_nx, s->nx); UP(o_nu, s->nu);
     UP(o_xoff, s->xoff); UP(o_uoff, s->uoff); UP(o_aoff, s->aoff); UP(o_boff, s->boff);
     UP(o_pos, s->pos); UP(o_bdim, s->bdim); UP(o_woff, s->woff); UP(o_utoff, s->utoff);
     UP(o_poff, s->poff);
 #undef UP
     Tree &T = s->T;
-    T.Nn = Nn; T.Np = s->Np; T.Nh = s->Nh; T.nx0 = s->nx0;
+    T.Nn = s->Nn; T.Np = s->Np; T.Nh = s->Nh; T.nx0 = s->nx0;
     T.dad = at<int>(base, o_dad); T.nk = at<int>(base, o_nk); T.kid0 = at<int>(base, o_kid0);
     T.nx = at<int>(base, o_nx); T.nu = at<int>(base, o_nu); T.xoff = at<int>(base, o_xoff); T.uoff = at<int>(base, o_uoff);
     T.aoff = at<int>(base, o_aoff); T.boff = at<int>(base, o_boff); T.pos = at<int>(base, o_pos);
     T.bdim = at<int>(base, o_bdim); T.woff = at<int>(base, o_woff); T.utoff = at<int>(base, o_utoff);
     {
-        std::vector<int> desc((size_t)DESC_INTS * Nn, 0);
-        for (int k = 0; k < Nn; k++) {
+        std::vector<int> desc((size_t)DESC_INTS * s->Nn, 0);
+        for (int k = 0; k < s->Nn; k++) {
             int *e = &desc[(size_t)DESC_INTS * k];
             const int k0 = s->nk[k] > 0 ? s->kid0[k] : 0, dd = k > 0 ? s->dad[k] : 0;
             e[0] = s->bdim[k]; e[1] = s->nx[k]; e[2] = s->nu[k]; e[3] = s->nk[k]; e[4] = k0; e[5] = s->xoff[k]; e[6] = s->uoff[k];
             e[7] = s->xoff[k0]; e[8] = s->woff[k]; e[9] = s->utoff[k]; e[10] = dd; e[11] = s->pos[k]; e[12] = s->bdim[dd]; e[13] = s->woff[dd];
             for (int u = 0; u < 4 && u < s->nk[k]; u++) { e[16 + 3 * u] = s->nx[k0 + u]; e[17 + 3 * u] = s->aoff[k0 + u]; e[18 + 3 * u] = s->boff[k0 + u]; }
         }
-        if (hipMalloc(&s->d_desc, desc.size() * I) != hipSuccess || hipMemcpy(s->d_desc, desc.data(), desc.size() * I, hipMemcpyHostToDevice) != hipSuccess)
-            return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the node records"));
+        if ((rc = s->mem.upload(s->d_desc, desc.data(), desc.size() * I, TQGPU_ENOMEM, "the node records"))) return rc;
         T.desc = s->d_desc;
     }
     Data &D = s->D;
@@ -2546,185 +2600,196 @@ extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *n
     s->d_lam_init = at<double>(base, o_lami);
     s->in_off0 = o_A; s->in_bytes = o_Qinv - o_A;
     s->out_doubles = 2 * (size_t)(s->sum_nx - s->x_pad) + 2 * (size_t)s->sum_nu + 2 * (size_t)s->sum_lam;
-    if (hipHostMalloc((void **)&s->h_in, std::max<size_t>(s->in_bytes, 8), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&s->h_lam, sizeof(double) * (size_t)std::max(s->sum_nx, 1), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&s->h_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(&s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1)) != hipSuccess)
-        return cleanup_fail(fail(TQGPU_ENOMEM, "allocation of the host mirrors failed"));
+    if ((rc = s->mem.host(s->h_in, std::max<size_t>(s->in_bytes, 8), "the host mirror of the inputs")) ||
+        (rc = s->mem.host(s->h_lam, sizeof(double) * (size_t)std::max(s->sum_nx, 1), "the host mirror of the duals")) ||
+        (rc = s->mem.host(s->h_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), "the host mirror of the solution")) ||
+        (rc = s->mem.device(s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), TQGPU_ENOMEM, "the packed solution")))
+        return rc;
     if (s->x_pad) {
         /* phantom root states: weight 1, everything else zero (the slab is zeroed) */
         std::vector<double> ones((size_t)s->x_pad, 1.0);
-        if (hipMemcpy(s->Qd, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice) != hipSuccess) return cleanup_fail(fail(TQGPU_ENODEVICE, "hipMemcpy failed"));
+        if (hipMemcpy(s->Qd, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipMemcpy failed");
     }
+    return TQGPU_OK;
+}
 
+/* launch-per-phase kernels (any tree): LDS budgets, one launch per sweep or per level, the reductions as tails of the sweeps */
+int setup_per_phase(tqgpu_solver *s) {
+    int rc;
     if ((rc = allow_lds(k_stage, s->lds_stage)) || (rc = allow_lds(k_hess, s->lds_hess)) ||
         (rc = allow_lds(k_factor, s->lds_factor)) || (rc = allow_lds(k_forward, s->lds_forward)) ||
         (rc = allow_lds(k_factor_all, s->lds_factor)) || (rc = allow_lds(k_forward_all, s->lds_forward)) || (rc = allow_lds(k_stage_f, s->lds_stage)))
-        return cleanup_fail(rc);
+        return rc;
     if (s->wide && ((rc = allow_lds(k_hess_w, s->lds_hess_w)) || (rc = allow_lds(k_factor_w, s->lds_factor_w)) || (rc = allow_lds(k_forward_w, s->lds_forward_w)) || (rc = allow_lds(k_forward_all_w, s->lds_forward_w)) || (rc = allow_lds(k_factor_all_w, s->lds_factor_w))))
-        return cleanup_fail(rc);
+        return rc;
     if (s->fast >= 0) {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess || prop.maxThreadsPerBlock < FW * WAVE) s->fast = -1;
+        if (hipGetDeviceProperties(&prop, s->device) != hipSuccess || prop.maxThreadsPerBlock < FW * WAVE) s->fast = -1;
     }
+    s->fw_fused = !s->sw.fwd_levels && !s->strict_sum;      /* (strict: the reference's launch-per-level order of operations) */
+    s->bw_fused = !s->sw.bwd_levels && !s->strict_sum;      /* (a fused sweep subtracts a child's Schur record AFTER an ALWAYS shift of the diagonal, the reference before it) */
+    s->sch_rs = (s->nxmax + 1) * (s->nxmax + 1);
+    s->fuse_ok = s->Nn <= FUSE_MAX && s->Nn >= 2 && !s->sw.no_fuse && !s->strict_sum;
+    /* hand-over words of the fused forward / backward sweeps of the launch-per-phase path (zeroed once; every launch brings its own tag) */
+    const size_t U = sizeof(unsigned long long);
+    if ((rc = s->mem.zeroed(s->fw_words, U * 2 * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the forward hand-over words")) ||
+        (rc = s->mem.zeroed(s->sch_words, U * 2 * (size_t)s->sch_rs * (size_t)s->Nn, TQGPU_ENOMEM, "the Schur hand-over words")))
+        return rc;
+    if (s->fuse_ok && ((rc = s->mem.zeroed(s->fuse_red, U * 2 * (size_t)s->Nn, TQGPU_ENOMEM, "the fused reductions")) ||
+                       (rc = s->mem.zeroed(s->fuse_cnt, 4 * sizeof(int), TQGPU_ENOMEM, "the fused reductions' counter"))))
+        return rc;
+    return TQGPU_OK;
+}
+
+/* the three-launch family of the wide-block class (tdunes_wide3.hpp) */
+int setup_wide3(tqgpu_solver *s) {
+    if (!(s->wide && s->fw_fused && s->bw_fused && !s->sw.no_wide3 && !s->strict_sum)) return TQGPU_OK;      /* (TREEQP_AMD_FWD / BWD = levels ask for the launch-per-level kernels) */
+    for (int k = 0; k < s->Np; k++) s->lds_hf_w = std::max(s->lds_hf_w, wide3_lds(s->bdim[k], k > 0 ? s->nx[k] : 0, s->nx[k] + s->nu[k]));
+    if (!(s->nxmax <= 32 && s->lds_hf_w <= 160 * 1024 && SG_WAVES * s->lds_stage <= 160 * 1024)) return TQGPU_OK;
+    /* k_sgp: one entry of a node's [x | u] per lane, one row of a block per lane */
+    bool fits = true;
+    for (int k = 0; k < s->Nn; k++) fits = fits && s->nx[k] + s->nu[k] <= 64;
+    for (int k = 0; k < s->Np; k++) s->sgp_accs = std::max(s->sgp_accs, std::min(s->nk[k], 8) * (s->nx[k] + s->nu[k]));      /* the children's terms in LDS: up to 8 children (more: taken by wave 0 on its own) */
+    for (int k = 0; k < s->Np; k++) s->lds_sgp = std::max(s->lds_sgp, wide3_lds_sgp(s->bdim[k], s->nx[k] + s->nu[k], s->sgp_accs));
+    s->w3_sgp = fits && s->lds_sgp <= 64 * 1024 && !s->sw.no_sgp;
+    /* forward sweep without hand-overs (k_fwd3c): small nodes, short paths, blocks whose region of CholW has room for the copy of z0
+     * beside the diagnostic stamps */
+    bool okc = s->Np > 1 && !s->sw.no_fwd_chain;
+    for (int k = 0; k < s->Nn && okc; k++) okc = s->nx[k] <= 8;
+    for (int k = 0; k < s->Np && okc; k++) okc = s->bdim[k] >= 3 && s->bdim[k] <= 64;
+    std::vector<int> anc;
+    if (okc) {
+        anc.assign((size_t)FWDC_INTS * s->Np, 0);
+        for (int ii = 1; ii < s->Np && okc; ii++) {
+            std::vector<int> path;                      /* ii, dad(ii), .., the root's child */
+            for (int n = ii; n != 0; n = s->dad[n]) path.push_back(n);
+            const int L = (int)path.size();
+            if (L > 16) { okc = false; break; }
+            int *a = &anc[(size_t)FWDC_INTS * ii];
+            a[0] = L;
+            for (int k = 0; k < L; k++) {
+                const int node = path[(size_t)(L - 1 - k)], prev = s->dad[node], dp_ = s->bdim[prev];
+                a[1 + 4 * k + 0] = s->woff[prev] + dp_ * dp_ - dp_ + s->pos[node];
+                a[1 + 4 * k + 1] = s->utoff[prev] + s->pos[node];
+                a[1 + 4 * k + 2] = dp_;
+                a[1 + 4 * k + 3] = (prev == 0 ? 0 : s->nx[prev]) | (s->nx[node] << 8);
+            }
+        }
+    }
+    s->w3_merge = okc && s->w3_sgp && !s->sw.no_fwd_merge;
+    const size_t U = sizeof(unsigned long long);
+    const size_t groups = std::max((size_t)(s->Nn + SG_WAVES - 1) / SG_WAVES, (size_t)s->Np);      /* workgroups of k_sg / k_sgp / k_fwd3 */
+    int rc;
+    if ((rc = s->mem.zeroed(s->w3_xu, U * 2 * (size_t)std::max(s->sum_nx + s->sum_nu, 1), TQGPU_ENOMEM, "the three-launch hand-over words")) ||
+        (rc = s->mem.zeroed(s->w3_red, U * 4 * groups, TQGPU_ENOMEM, "the three-launch reductions")) ||
+        (rc = s->mem.zeroed(s->w3_cnt, 4 * sizeof(int), TQGPU_ENOMEM, "the three-launch reductions' counter")) ||
+        (rc = allow_lds(k_hf_w, s->lds_hf_w)) || (rc = allow_lds(k_sg, SG_WAVES * ((s->lds_stage + 7) / 8) * 8)))
+        return rc;
+    if (okc && (rc = s->mem.upload(s->d_anc, anc.data(), anc.size() * sizeof(int), TQGPU_ENOMEM, "the path table of the forward sweep"))) return rc;
+    if (s->w3_merge && (rc = s->mem.zeroed(s->d_pdw, U * 2 * (size_t)s->Np, TQGPU_ENOMEM, "the forward sweep's partial sums"))) return rc;
+    s->w3_ok = true;
+    return TQGPU_OK;
+}
+
+int setup_single_wg(tqgpu_solver *s) {
+    /* single-workgroup persistent kernel for small trees of any shape: every level must be a few rounds
+     * of GP_WAVES blocks at most, and the per-wave LDS windows must fit the default 64 KB */
+    int widest = 0;
+    for (int l = 0; l <= s->Nh; l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
+    const size_t per_wave = (std::max(std::max(s->lds_stage, s->lds_hess), std::max(s->lds_factor, s->lds_forward)) + 7) / 8 + 2;
+    s->lds_gp_wave = per_wave;
     {
-        /* hand-over words of the fused forward / backward sweeps of the launch-per-phase path (zeroed once; every launch brings its own tag) */
-        const size_t bytes = sizeof(unsigned long long) * 2 * (size_t)std::max(s->sum_nx, 1);
-        if (hipMalloc(&s->fw_words, bytes) != hipSuccess || hipMemset(s->fw_words, 0, bytes) != hipSuccess)
-            return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the forward hand-over words"));
-        const char *m = getenv("TREEQP_AMD_FWD");              /* =levels: one launch per tree level (the round-1 protocol) */
-        s->fw_fused = !(m && strcmp(m, "levels") == 0) && !s->strict_sum;      /* (strict: the reference's launch-per-level order of operations) */
-        int nxmax = 0;
-        for (int k = 0; k < s->Nn; k++) nxmax = std::max(nxmax, s->nx[k]);
-        s->sch_rs = (nxmax + 1) * (nxmax + 1);
-        const size_t sbytes = sizeof(unsigned long long) * 2 * (size_t)s->sch_rs * (size_t)s->Nn;
-        if (hipMalloc(&s->sch_words, sbytes) != hipSuccess || hipMemset(s->sch_words, 0, sbytes) != hipSuccess)
-            return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the Schur hand-over words"));
-        m = getenv("TREEQP_AMD_BWD");
-        s->bw_fused = !(m && strcmp(m, "levels") == 0) && !s->strict_sum;      /* (a fused sweep subtracts a child's Schur record AFTER an ALWAYS shift of the diagonal, the reference before it) */
-        if (s->Nn <= FUSE_MAX && s->Nn >= 2 && !getenv("TREEQP_AMD_NO_FUSE") && !s->strict_sum) {
-            const size_t rb = sizeof(unsigned long long) * 2 * (size_t)s->Nn;
-            if (hipMalloc(&s->fuse_red, rb) != hipSuccess || hipMemset(s->fuse_red, 0, rb) != hipSuccess ||
-                hipMalloc(&s->fuse_cnt, 4 * sizeof(int)) != hipSuccess || hipMemset(s->fuse_cnt, 0, 4 * sizeof(int)) != hipSuccess)
-                return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the fused reductions"));
-            s->fuse_ok = true;
-        }
+        /* four nodes per wave in the stage sweep: nx + nu <= 16 everywhere, clipping nodes only, and a quarter of the wave's window
+         * holds a node's duals (bdim + nx doubles) */
+        bool ok16 = !s->dense && !s->sw.no_stage16;
+        for (int k = 0; k < s->Nn && ok16; k++) ok16 = s->nx[k] + s->nu[k] <= 16 && (size_t)(s->bdim[k] + s->nx[k]) <= per_wave / 4;
+        s->gp_small16 = ok16;
+        bool ok8 = !s->sw.no_stage16 && !s->strict_sum;          /* eight nodes per wave in the gradient sweep: nx <= 8 everywhere */
+        for (int k = 0; k < s->Nn && ok8; k++) ok8 = s->nx[k] <= 8;
+        s->gp_small8 = ok8;
     }
-    if (s->wide && s->fw_fused && s->bw_fused && !getenv("TREEQP_AMD_NO_WIDE3") && !s->strict_sum) {      /* (TREEQP_AMD_FWD / BWD = levels ask for the launch-per-level kernels) */
-        /* the three-launch family of the wide-block class (tdunes_wide3.hpp) */
-        int nxmax = 0;
-        for (int k = 0; k < Nn; k++) { nxmax = std::max(nxmax, s->nx[k]); if (k < s->Np) s->lds_hf_w = std::max(s->lds_hf_w, wide3_lds(s->bdim[k], k > 0 ? s->nx[k] : 0, s->nx[k] + s->nu[k])); }
-        const size_t groups = std::max((size_t)(Nn + SG_WAVES - 1) / SG_WAVES, (size_t)s->Np);      /* workgroups of k_sg / k_sgp / k_fwd3 */
-        const size_t xb = sizeof(unsigned long long) * 2 * (size_t)std::max(s->sum_nx + s->sum_nu, 1), rb = sizeof(unsigned long long) * 4 * groups;
-        if (nxmax <= 32 && s->lds_hf_w <= 160 * 1024 && SG_WAVES * s->lds_stage <= 160 * 1024) {
-            if (hipMalloc(&s->w3_xu, xb) != hipSuccess || hipMemset(s->w3_xu, 0, xb) != hipSuccess ||
-                hipMalloc(&s->w3_red, rb) != hipSuccess || hipMemset(s->w3_red, 0, rb) != hipSuccess ||
-                hipMalloc(&s->w3_cnt, 4 * sizeof(int)) != hipSuccess || hipMemset(s->w3_cnt, 0, 4 * sizeof(int)) != hipSuccess)
-                return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the three-launch hand-over words"));
-            if ((rc = allow_lds(k_hf_w, s->lds_hf_w)) || (rc = allow_lds(k_sg, SG_WAVES * ((s->lds_stage + 7) / 8) * 8))) return cleanup_fail(rc);
-            /* k_sgp: one entry of a node's [x | u] per lane, one row of a block per lane */
-            bool fits = true;
-            for (int k = 0; k < Nn; k++) fits = fits && s->nx[k] + s->nu[k] <= 64;
-            for (int k = 0; k < s->Np; k++) s->sgp_accs = std::max(s->sgp_accs, std::min(s->nk[k], 8) * (s->nx[k] + s->nu[k]));      /* the children's terms in LDS: up to 8 children (more: taken by wave 0 on its own) */
-            for (int k = 0; k < s->Np; k++) s->lds_sgp = std::max(s->lds_sgp, wide3_lds_sgp(s->bdim[k], s->nx[k] + s->nu[k], s->sgp_accs));
-            s->w3_sgp = fits && s->lds_sgp <= 64 * 1024 && !getenv("TREEQP_AMD_NO_SGP");
-            /* forward sweep without hand-overs (k_fwd3c): small nodes, short paths, blocks whose region of CholW has room for the copy of z0
-             * beside the diagnostic stamps */
-            {
-                bool okc = s->Np > 1 && !getenv("TREEQP_AMD_NO_FWD_CHAIN");
-                for (int k = 0; k < Nn && okc; k++) okc = s->nx[k] <= 8;
-                for (int k = 0; k < s->Np && okc; k++) okc = s->bdim[k] >= 3 && s->bdim[k] <= 64;
-                std::vector<int> anc;
-                if (okc) {
-                    anc.assign((size_t)FWDC_INTS * s->Np, 0);
-                    for (int ii = 1; ii < s->Np && okc; ii++) {
-                        std::vector<int> path;                      /* ii, dad(ii), .., the root's child */
-                        for (int n = ii; n != 0; n = s->dad[n]) path.push_back(n);
-                        const int L = (int)path.size();
-                        if (L > 16) { okc = false; break; }
-                        int *a = &anc[(size_t)FWDC_INTS * ii];
-                        a[0] = L;
-                        for (int k = 0; k < L; k++) {
-                            const int node = path[(size_t)(L - 1 - k)], prev = s->dad[node], dp_ = s->bdim[prev];
-                            a[1 + 4 * k + 0] = s->woff[prev] + dp_ * dp_ - dp_ + s->pos[node];
-                            a[1 + 4 * k + 1] = s->utoff[prev] + s->pos[node];
-                            a[1 + 4 * k + 2] = dp_;
-                            a[1 + 4 * k + 3] = (prev == 0 ? 0 : s->nx[prev]) | (s->nx[node] << 8);
-                        }
-                    }
-                }
-                if (okc && (hipMalloc(&s->d_anc, anc.size() * sizeof(int)) != hipSuccess || hipMemcpy(s->d_anc, anc.data(), anc.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess))
-                    return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the path table of the forward sweep"));
-                if (okc && s->w3_sgp && !getenv("TREEQP_AMD_NO_FWD_MERGE")) {
-                    const size_t pb = sizeof(unsigned long long) * 2 * (size_t)s->Np;
-                    if (hipMalloc(&s->d_pdw, pb) != hipSuccess || hipMemset(s->d_pdw, 0, pb) != hipSuccess)
-                        return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed for the forward sweep's partial sums"));
-                    s->w3_merge = true;
-                }
-            }
-            s->w3_ok = true;
-        }
-    }
-    if ((rc = setup_persist(s, device))) return cleanup_fail(rc);
+    s->gpersist_ok = widest <= 6 * GP_WAVES && per_wave * 8 * GP_WAVES <= 150 * 1024;
+    /* LDS mirror of the mutable state (tdunes_gpersist.hpp): 16 node-sized vectors (rounded up to even), 4 block arrays */
     {
-        /* single-workgroup persistent kernel for small trees of any shape: every level must be a few rounds
-         * of GP_WAVES blocks at most, and the per-wave LDS windows must fit the default 64 KB */
-        int widest = 0;
-        for (int l = 0; l <= s->Nh; l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
-        const size_t per_wave = (std::max(std::max(s->lds_stage, s->lds_hess), std::max(s->lds_factor, s->lds_forward)) + 7) / 8 + 2;
-        s->lds_gp_wave = per_wave;
-        {
-            /* four nodes per wave in the stage sweep: nx + nu <= 16 everywhere, clipping nodes only, and a quarter of the wave's window
-             * holds a node's duals (bdim + nx doubles) */
-            bool ok16 = !s->dense && !getenv("TREEQP_AMD_NO_STAGE16");
-            for (int k = 0; k < Nn && ok16; k++) ok16 = s->nx[k] + s->nu[k] <= 16 && (size_t)(s->bdim[k] + s->nx[k]) <= per_wave / 4;
-            s->gp_small16 = ok16;
-            bool ok8 = !getenv("TREEQP_AMD_NO_STAGE16") && !s->strict_sum;          /* eight nodes per wave in the gradient sweep: nx <= 8 everywhere */
-            for (int k = 0; k < Nn && ok8; k++) ok8 = s->nx[k] <= 8;
-            s->gp_small8 = ok8;
+        auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
+        const size_t sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
+        const size_t mirror = 11 * ev(sx) + 5 * ev(su) + 2 * ev((size_t)s->sum_W) + 2 * ev((size_t)s->sum_Ut) + 2 * ev((size_t)s->Nn) + ev(sx + s->Nn + 1) + ev(su) * 0;
+        const size_t tables = (13 * ((size_t)s->Nn + 3)) / 2 + 16;            /* int tables, in doubles */
+        s->lds_gp_total = (per_wave * GP_WAVES + mirror + tables + 8) * 8;
+        s->gp_in_lds = s->gpersist_ok && s->lds_gp_total <= 150 * 1024;
+        const size_t consts = (ev((size_t)s->sum_A) + ev((size_t)s->sum_B) + 5 * ev(sx) + 4 * ev(su)) * 8;
+        s->gp_const_in_lds = s->gp_in_lds && s->lds_gp_total + consts <= 150 * 1024;
+        if (s->gp_const_in_lds) s->lds_gp_total += consts;
+        if (!s->gp_in_lds) {
+            /* the state does not fit: the index tables alone, next to the per-wave windows, if THEY fit */
+            s->gp_tab_in_lds = s->gpersist_ok && (per_wave * GP_WAVES + tables + 8) * 8 <= 150 * 1024;
+            s->lds_gp_total = (per_wave * GP_WAVES + (s->gp_tab_in_lds ? tables + 8 : 0)) * 8;
         }
-        s->gpersist_ok = widest <= 6 * GP_WAVES && per_wave * 8 * GP_WAVES <= 150 * 1024;
-        /* LDS mirror of the mutable state (tdunes_gpersist.hpp): 16 node-sized vectors (rounded up to even), 4 block arrays */
-        {
-            auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
-            const size_t sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
-            const size_t mirror = 11 * ev(sx) + 5 * ev(su) + 2 * ev((size_t)s->sum_W) + 2 * ev((size_t)s->sum_Ut) + 2 * ev((size_t)Nn) + ev(sx + Nn + 1) + ev(su) * 0;
-            const size_t tables = (13 * ((size_t)Nn + 3)) / 2 + 16;            /* int tables, in doubles */
-            s->lds_gp_total = (per_wave * GP_WAVES + mirror + tables + 8) * 8;
-            s->gp_in_lds = s->gpersist_ok && s->lds_gp_total <= 150 * 1024;
-            const size_t consts = (ev((size_t)s->sum_A) + ev((size_t)s->sum_B) + 5 * ev(sx) + 4 * ev(su)) * 8;
-            s->gp_const_in_lds = s->gp_in_lds && s->lds_gp_total + consts <= 150 * 1024;
-            if (s->gp_const_in_lds) s->lds_gp_total += consts;
-            if (!s->gp_in_lds) {
-                /* the state does not fit: the index tables alone, next to the per-wave windows, if THEY fit */
-                s->gp_tab_in_lds = s->gpersist_ok && (per_wave * GP_WAVES + tables + 8) * 8 <= 150 * 1024;
-                s->lds_gp_total = (per_wave * GP_WAVES + (s->gp_tab_in_lds ? tables + 8 : 0)) * 8;
-            }
-            else if (s->lds_gp_total > 64 * 1024 &&
-                     hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_gp_total) != hipSuccess) {
-                (void)hipGetLastError();
-                s->gp_in_lds = false; s->gp_tab_in_lds = false; s->lds_gp_total = per_wave * GP_WAVES * 8;
-            }
-            if (s->gpersist_ok && !s->gp_in_lds && s->lds_gp_total > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_gp_total) != hipSuccess) {
-                (void)hipGetLastError();
-                s->gpersist_ok = false;
-            }
+        else if (s->lds_gp_total > 64 * 1024 &&
+                 hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_gp_total) != hipSuccess) {
+            (void)hipGetLastError();
+            s->gp_in_lds = false; s->gp_tab_in_lds = false; s->lds_gp_total = per_wave * GP_WAVES * 8;
         }
-        if (s->gpersist_ok) {
-            /* behind the level table: for every level of parents, how many of its blocks one wave takes side by side in the backward /
-             * forward / Hessian sweeps (factor_body_g ...): levels wider than the workgroup's 16 waves whose blocks all have the same
-             * small dimensions (the chains of a pruned scenario tree); 1 = one block per wave */
-            std::vector<int> tab(s->lvl_first);
-            const bool no_grp = getenv("TREEQP_AMD_GP_NO_GROUPS") != nullptr;
-            for (int lvl = 0; lvl <= s->Nh; lvl++) {
-                int grp = 1;
-                const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-                if (!no_grp && lvl >= 1 && lvl < s->Nh && count > GP_WAVES && !s->dense) {
-                    const int d0 = s->bdim[first], n0 = s->nx[first], u0 = s->nu[first], c0 = s->nk[first];
-                    bool same = true;
-                    for (int k = first; k < first + count && same; k++) {
-                        same = s->bdim[k] == d0 && s->nx[k] == n0 && s->nu[k] == u0 && s->nk[k] == c0;
-                        for (int cc = 0; cc < s->nk[k] && same; cc++) same = s->nx[s->kid0[k] + cc] == s->nx[s->kid0[first] + cc];
-                    }
-                    const int R = d0 + 1 + n0;
-                    /* doubles of a group's window: factor_body's tall matrix, forward_body's factor + vectors, hess_body's C and C P */
-                    const size_t need = std::max(std::max((size_t)(R | 1) * d0 + d0 + 2, (size_t)(d0 | 1) * d0 + 2 * d0 + n0 + 2), (size_t)2 * d0 * (n0 + u0) + 2);
-                    if (same && d0 >= 1) {
-                        if (R <= WAVE / 3 && 3 * need <= s->lds_gp_wave) grp = 3;
-                        else if (R <= WAVE / 2 && 2 * need <= s->lds_gp_wave) grp = 2;
-                    }
-                }
-                tab.push_back(grp);
-            }
-            if (hipMalloc(&s->d_lvl_first, sizeof(int) * tab.size()) != hipSuccess ||
-                hipMemcpy(s->d_lvl_first, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice) != hipSuccess)
-                return cleanup_fail(fail(TQGPU_ENOMEM, "hipMalloc failed"));
+        if (s->gpersist_ok && !s->gp_in_lds && s->lds_gp_total > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_gp_total) != hipSuccess) {
+            (void)hipGetLastError();
+            s->gpersist_ok = false;
         }
     }
+    if (s->gpersist_ok) {
+        /* behind the level table: for every level of parents, how many of its blocks one wave takes side by side in the backward /
+         * forward / Hessian sweeps (factor_body_g ...): levels wider than the workgroup's 16 waves whose blocks all have the same
+         * small dimensions (the chains of a pruned scenario tree); 1 = one block per wave */
+        std::vector<int> tab(s->lvl_first);
+        for (int lvl = 0; lvl <= s->Nh; lvl++) {
+            int grp = 1;
+            const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
+            if (!s->sw.gp_no_groups && lvl >= 1 && lvl < s->Nh && count > GP_WAVES && !s->dense) {
+                const int d0 = s->bdim[first], n0 = s->nx[first], u0 = s->nu[first], c0 = s->nk[first];
+                bool same = true;
+                for (int k = first; k < first + count && same; k++) {
+                    same = s->bdim[k] == d0 && s->nx[k] == n0 && s->nu[k] == u0 && s->nk[k] == c0;
+                    for (int cc = 0; cc < s->nk[k] && same; cc++) same = s->nx[s->kid0[k] + cc] == s->nx[s->kid0[first] + cc];
+                }
+                const int R = d0 + 1 + n0;
+                /* doubles of a group's window: factor_body's tall matrix, forward_body's factor + vectors, hess_body's C and C P */
+                const size_t need = std::max(std::max((size_t)(R | 1) * d0 + d0 + 2, (size_t)(d0 | 1) * d0 + 2 * d0 + n0 + 2), (size_t)2 * d0 * (n0 + u0) + 2);
+                if (same && d0 >= 1) {
+                    if (R <= WAVE / 3 && 3 * need <= s->lds_gp_wave) grp = 3;
+                    else if (R <= WAVE / 2 && 2 * need <= s->lds_gp_wave) grp = 2;
+                }
+            }
+            tab.push_back(grp);
+        }
+        return s->mem.upload(s->d_lvl_first, tab.data(), sizeof(int) * tab.size(), TQGPU_ENOMEM, "the level table");
+    }
+    return TQGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *nk, const int *nx, const int *nu) {
+    if (!out || Nn < 2 || !nk || !nx || !nu) return fail(TQGPU_EINVAL, "tqgpu_create: bad arguments");
+    *out = nullptr;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev == 0)
+        return fail(TQGPU_ENODEVICE, std::string("no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "device count is 0") + "); the tdunes hot path has no CPU fallback");
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    if (device >= ndev) return fail(TQGPU_EINVAL, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+
+    tqgpu_solver *s = new tqgpu_solver();
+    { static std::atomic<unsigned long> next_uid{1}; s->uid = next_uid.fetch_add(1); }
+    s->device = device; s->Nn = Nn;
+    s->nk.assign(nk, nk + Nn); s->nx.assign(nx, nx + Nn); s->nu.assign(nu, nu + Nn);
+    read_switches(s->sw);
+    int rc;
+    if ((rc = detect_shape(s)) || (rc = layout_slab(s)) || (rc = setup_per_phase(s)) || (rc = setup_wide3(s)) || (rc = setup_persist(s)) || (rc = setup_single_wg(s))) {}
     /* the zeroing of the slabs above went out as device memsets, which may return before they have happened, on the null stream, which
      * the solver's non-blocking stream does not wait for: everything is in place before the first solve can be enqueued */
-    if (hipDeviceSynchronize() != hipSuccess) return cleanup_fail(fail(TQGPU_ENODEVICE, "hipDeviceSynchronize failed"));
+    else if (hipDeviceSynchronize() != hipSuccess) rc = fail(TQGPU_ENODEVICE, "hipDeviceSynchronize failed");
+    if (rc != TQGPU_OK) { tqgpu_destroy(s); return rc; }
     *out = s;
     return TQGPU_OK;
 }
@@ -2741,37 +2806,10 @@ extern "C" void tqgpu_destroy(tqgpu_solver *s) {
     for (auto &ev : s->ring_ev0) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : s->ring_ev1) if (ev) (void)hipEventDestroy(ev);
     if (s->stream) { { std::lock_guard<std::mutex> lk(g_streams_mu); g_live_streams.erase(s->stream); } (void)hipStreamDestroy(s->stream); }
-    if (s->h_res) (void)hipHostFree(s->h_res);
-    if (s->h_ls_log) (void)hipHostFree(s->h_ls_log);
-    if (s->shard_slab) (void)hipFree(s->shard_slab);
-    if (s->sync_slab) (void)hipFree(s->sync_slab);
-    if (s->pconst_slab) (void)hipFree(s->pconst_slab);
-    if (s->wg_map) (void)hipFree(s->wg_map);
-    if (s->d_desc) (void)hipFree(s->d_desc);
-    if (s->d_pitems) (void)hipFree(s->d_pitems);
-    if (s->h_pitems) (void)hipHostFree(s->h_pitems);
-    if (s->ps_wg_map) (void)hipFree(s->ps_wg_map);
-    if (s->d_peers) (void)hipFree(s->d_peers);
-    for (int r = 0; r < 8; r++) if (s->ps_ipc[r]) (void)hipIpcCloseMemHandle(s->ps_ipc[r]);
-    if (s->w3_xu) (void)hipFree(s->w3_xu);
-    if (s->w3_red) (void)hipFree(s->w3_red);
-    if (s->w3_cnt) (void)hipFree(s->w3_cnt);
-    if (s->fuse_red) (void)hipFree(s->fuse_red);
-    if (s->fuse_cnt) (void)hipFree(s->fuse_cnt);
-    if (s->fw_words) (void)hipFree(s->fw_words);
-    if (s->sch_words) (void)hipFree(s->sch_words);
-    if (s->d_anc) (void)hipFree(s->d_anc);
-    if (s->d_pdw) (void)hipFree(s->d_pdw);
-    if (s->d_gitems) (void)hipFree(s->d_gitems);
-    if (s->h_gitems) (void)hipHostFree(s->h_gitems);
     if (s->batch_ev) (void)hipEventDestroy(s->batch_ev);
-    if (s->h_in) (void)hipHostFree(s->h_in);
-    if (s->h_lam) (void)hipHostFree(s->h_lam);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->d_out) (void)hipFree(s->d_out);
-    if (s->d_lvl_first) (void)hipFree(s->d_lvl_first);
+    for (int r = 0; r < 8; r++) if (s->ps_ipc[r]) (void)hipIpcCloseMemHandle(s->ps_ipc[r]);
     if (s->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(s->comm);
-    if (s->slab) (void)hipFree(s->slab);
+    s->mem.free_all();
     delete s;
 }
 
@@ -2793,7 +2831,7 @@ static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_mem
     if (s->fuse_ok && p < 3 && !s->sharded && !s->box) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
     return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
-/* the kernel variants tqgpu_create and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
+/* the kernel variants the steps of tqgpu_create (setup_per_phase, setup_wide3, setup_persist, setup_single_wg) and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
  * reads fields, changes nothing */
 extern "C" int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs) {
     if (!s) return fail(TQGPU_EINVAL, "null solver");
@@ -3566,6 +3604,17 @@ static int batch_kernel_index(const tqgpu_solver *s) {
 #undef X
     return -1;
 }
+/* the descriptors of a batch launch (device array and its pinned host copy, owned by the batch's first mirror): room for `need` */
+template <typename Item>
+static int grow_items(tqgpu_solver *s, Item *&d, Item *&h, int &cap, size_t need) {
+    if (cap >= (int)need) return TQGPU_OK;
+    s->mem.release(d); s->mem.release(h);
+    cap = 0;
+    int rc;
+    if ((rc = s->mem.device(d, 2 * need * sizeof(Item), TQGPU_ENOMEM, "the batch descriptors")) || (rc = s->mem.host(h, 2 * need * sizeof(Item), "the batch descriptors"))) return rc;
+    cap = (int)(2 * need);
+    return TQGPU_OK;
+}
 static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
     const int G = lead->geom.G;
     static const char *nap_env = getenv("TREEQP_AMD_NAP");
@@ -3637,15 +3686,7 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
         for (int k = begun_from; k < begun_to; k++)
             if (route_of(solvers[k], o, true) == Route::SINGLE_WG) gp_members.push_back(k);
         tqgpu_solver *lead = gp_members.size() >= 2 ? solvers[gp_members[0]] : nullptr;
-        if (lead && lead->gitems_cap < (int)gp_members.size()) {
-            if (lead->d_gitems) (void)hipFree(lead->d_gitems);
-            if (lead->h_gitems) (void)hipHostFree(lead->h_gitems);
-            lead->d_gitems = nullptr; lead->h_gitems = nullptr; lead->gitems_cap = 0;
-            const size_t cap = gp_members.size() * 2;
-            if (hipMalloc(&lead->d_gitems, cap * sizeof(GItem)) != hipSuccess || hipHostMalloc((void **)&lead->h_gitems, cap * sizeof(GItem), hipHostMallocDefault) != hipSuccess)
-                return fail(TQGPU_ENOMEM, "allocation of the batch descriptors failed");
-            lead->gitems_cap = (int)cap;
-        }
+        if (lead) { int rc = grow_items(lead, lead->d_gitems, lead->h_gitems, lead->gitems_cap, gp_members.size()); if (rc) return rc; }
         /* persistent mirrors of this wave that share a shape with a batch kernel go out as ONE launch as well */
         std::vector<int> pm;
         {
@@ -3710,15 +3751,8 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
         if (!pm.empty() && ok_to == begun_to) {
             tqgpu_solver *pl = solvers[pm[0]];
             const size_t np = pm.size();
-            if (pl->pitems_cap < (int)np) {
-                if (pl->d_pitems) (void)hipFree(pl->d_pitems);
-                if (pl->h_pitems) (void)hipHostFree(pl->h_pitems);
-                pl->d_pitems = nullptr; pl->h_pitems = nullptr; pl->pitems_cap = 0; pl->pitems_key.clear();
-                const size_t cap = np * 2;
-                if (hipMalloc(&pl->d_pitems, cap * sizeof(PItem)) != hipSuccess || hipHostMalloc((void **)&pl->h_pitems, cap * sizeof(PItem), hipHostMallocDefault) != hipSuccess)
-                    return fail(TQGPU_ENOMEM, "allocation of the batch descriptors failed");
-                pl->pitems_cap = (int)cap;
-            }
+            if (pl->pitems_cap < (int)np) pl->pitems_key.clear();
+            if (int rc = grow_items(pl, pl->d_pitems, pl->h_pitems, pl->pitems_cap, np)) return rc;
             std::vector<unsigned long> key;
             for (int k : pm) key.push_back(solvers[k]->uid);
             hipStream_t st0 = pl->stream;
@@ -3868,9 +3902,8 @@ int shard_build_lists(tqgpu_solver *s) {
     s->gh_n = (int)gh.size(); s->n_nodes = (int)nodes.size(); s->n_nodes_counted = (int)nodes_cnt.size(); s->n_blk_counted = (int)blks.size();
     const size_t ints = gh.size() + nodes.size() + nodes_cnt.size() + blks.size() + 16;
     const size_t bytes = ints * sizeof(int) + (3 * (size_t)N + 8) * sizeof(double) + 1024;
-    if (s->shard_slab) { (void)hipFree(s->shard_slab); s->shard_slab = nullptr; }
-    HIP_TRY(hipMalloc(&s->shard_slab, bytes));
-    HIP_TRY(hipMemset(s->shard_slab, 0, bytes));
+    s->mem.release(s->shard_slab);
+    if (int rc = s->mem.zeroed(s->shard_slab, bytes, TQGPU_ENODEVICE, "the shard lists")) return rc;
     char *p = static_cast<char *>(s->shard_slab);
     s->d_xerr = reinterpret_cast<double *>(p); p += sizeof(double) * (size_t)(N + 2);
     s->d_xs = reinterpret_cast<double *>(p); p += sizeof(double) * (size_t)(2 * N + 2);
@@ -3995,8 +4028,8 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
     map.resize((size_t)nwg);
     if (nranks == 1) top = s->n_tiers - 1;
     if ((int)map.size() > s->co_capacity) return fail(TQGPU_EUNSUPPORTED, "this rank's workgroups cannot all be resident");
-    if (s->ps_wg_map) { (void)hipFree(s->ps_wg_map); s->ps_wg_map = nullptr; }
-    HIP_TRY(hipMalloc(&s->ps_wg_map, sizeof(int) * std::max<size_t>(map.size(), 1)));
+    s->mem.release(s->ps_wg_map);
+    if (int rc = s->mem.device(s->ps_wg_map, sizeof(int) * std::max<size_t>(map.size(), 1), TQGPU_ENODEVICE, "this rank's workgroup table")) return rc;
     HIP_TRY(hipMemcpy(s->ps_wg_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
     s->ps_G = (int)map.size();
     /* First contact with real xGMI is somebody else's run, so the two things a peer's writes depend on are settled by construction:
@@ -4007,14 +4040,13 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
     s->ps_sys = !getenv("TREEQP_AMD_PSHARD_AGENT");
     if (!s->ps_fine && !getenv("TREEQP_AMD_PSHARD_COARSE")) {
         void *fresh = nullptr;
-        hipError_t ef = hipExtMallocWithFlags(&fresh, s->sync_bytes, hipDeviceMallocFinegrained);
-        if (ef != hipSuccess) return fail(TQGPU_ENODEVICE, std::string("hipExtMallocWithFlags(fine-grained hand-over slab): ") + hipGetErrorString(ef));
+        if (int rc = s->mem.device(fresh, s->sync_bytes, TQGPU_ENODEVICE, "the fine-grained hand-over slab", Owned::FINE_GRAINED)) return rc;
         HIP_TRY(hipStreamSynchronize(s->stream));
         char *ob = static_cast<char *>(s->sync_slab), *nb = static_cast<char *>(fresh);
         auto mv = [&](auto *&q) { if (q) q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(nb + (reinterpret_cast<char *>(q) - ob)); };
         PSync &Y = s->psync;
         mv(Y.sch); mv(Y.dlt); mv(Y.ndt); mv(Y.parts); mv(Y.errs); mv(Y.cmd); mv(Y.vrd); mv(Y.bparts); mv(Y.sgt); mv(Y.rfl); mv(Y.halt); mv(Y.timeout); mv(Y.base); mv(Y.verdict); mv(Y.anc);
-        (void)hipFree(s->sync_slab);
+        s->mem.release(s->sync_slab);
         s->sync_slab = fresh;
         s->ps_fine = true;
         s->pitems_key.clear();                                             /* (a cached batch descriptor would hold the old slab) */
