@@ -182,3 +182,42 @@ def test_batch_of_one_member_per_row_equals_single_solves(gpu):
         assert ms[picked.index(c)].plan["last_single_wg"], c
     for m in ms:
         m.close()
+
+
+def test_single_workgroup_member_alone_in_its_wave_runs_its_own_route(gpu):
+    """The route a batch member runs: a tree that takes g_persist only as a member of a batch launch (its state does not fit LDS) runs
+    it when its wave holds at least two single-workgroup trees, and the route of its own single solve when it is the only one --
+    here among members of other classes (persistent with a batch kernel, three-launch, fused tails), none of which takes
+    g_persist.  Verdict and counts of every member equal its own single solve; the solution of the LDS-too-large trees to 1e-12
+    (the bound of test_batch_of_one_member_per_row_equals_single_solves for members that may run another kernel family)."""
+    def shaped(cid):
+        d = S.problem(S.C, S.case(cid)[1])
+        return gpu.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+
+    def persistent():
+        p = P.spring_mass()
+        nk = p.nk()
+        flat = gpu.TreeQp(np.full(p.Nn, p.nx), np.where(nk > 0, p.nu, 0), nk).fill_lti(p).flat()
+        return gpu.TqGpu(flat["nk"], flat["nx"], flat["nu"]).upload(flat, p.lambda0)
+
+    for n_big in (1, 2):
+        # (widest_level-w97: three-launch and past g_persist's widest level; the small wide trees qualify for g_persist)
+        ms = [persistent(), shaped("widest_level-w97"), shaped("g_persist_LDS-tables_in_lds"), shaped("g_persist_LDS-nothing_in_lds"),
+              shaped("FUSE_MAX-n512"), persistent()]
+        if n_big == 1:
+            ms.pop(3).close()
+        big = range(2, 2 + n_big)
+        singles = []
+        for i, m in enumerate(ms):
+            r = m.solve()
+            plan = m.plan
+            assert not plan["last_single_wg"] and (i not in big or (plan["gpersist"] and not plan["gp_state_lds"])), (i, plan)
+            singles.append((r, m.solution()))
+        res = gpu.solve_batch(ms)
+        for i, (m, r, (r1, s1)) in enumerate(zip(ms, res, singles)):
+            assert (r["status"], r["iter"], r["ls_total"]) == (r1["status"], r1["iter"], r1["ls_total"]), (n_big, i)
+            assert m.plan["last_single_wg"] == (i in big and n_big == 2), (n_big, i)          # (no other member takes g_persist)
+            if i in big:
+                assert_solution_close(m.solution(), s1, 1e-12)
+        for m in ms:
+            m.close()

@@ -1583,7 +1583,6 @@ struct tqgpu_solver {
     int *h_ls_log = nullptr;     /* pinned */
     int ls_log_cap = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> iter_ev;
     std::vector<double> iter_times;
     bool times_dirty = true;              /* iter_times / phase_times may hold times of an earlier (profiled) solve */
@@ -1625,7 +1624,6 @@ struct tqgpu_solver {
     std::vector<unsigned long> pitems_key;                                /* the mirrors (by uid) the device copy of the array describes */
     unsigned long uid = 0;                                                /* unique per mirror of this process (an address can come back) */
     bool stream_pending = false;                                          /* something was enqueued on `stream` without a synchronisation after it (asynchronous uploads, constant packing): a batch launch on ANOTHER stream waits for it first */
-    hipEvent_t batch_ev = nullptr;
     hipStream_t batch_stream = nullptr;                                   /* member of a batch launch in flight: the stream that launch is on (the lead's) */
     bool export_ahead = false;          /* tqgpu_set_export_ahead: the packing kernel and the download of the solution are enqueued right behind a single persistent launch */
     bool export_valid = false;          /* h_out holds (or is about to hold, stream-ordered) the solution of the last solve */
@@ -2105,12 +2103,24 @@ int launch_trial(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int &la
 }
 
 
+/* THE list of process-lifetime switches: read from the environment once, when the first of them is asked for */
+struct ProcessSwitches { int nap_t1, nap, ls_chunk, trial_batch; bool has_nap; };
+static const ProcessSwitches &process_switches() {
+    static const ProcessSwitches w = [] {
+        auto num = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+        ProcessSwitches p;
+        p.nap_t1 = num("TREEQP_AMD_NAP_T1", 128);                             /* workgroups of a launch from which the bottom tier's long poll naps are on (nap_for_grid) */
+        p.has_nap = getenv("TREEQP_AMD_NAP") != nullptr; p.nap = num("TREEQP_AMD_NAP", 0);      /* ... of a batch launch off (0) / on (1) instead (launch_persist_batch) */
+        p.ls_chunk = std::max(1, num("TREEQP_AMD_LS_CHUNK", 2));              /* iterations enqueued per read-back after a solve that backtracked (solve_end) */
+        p.trial_batch = std::max(1, num("TREEQP_AMD_TRIAL_BATCH", 3));        /* line-search trials in the first batch beyond the first trial (solve_end) */
+        return p;
+    }();
+    return w;
+}
+
 /* persistent launch: geometry, sync words, co-residency test */
 /* poll naps by launch size (PollGuard::go_on) */
-static int nap_for_grid(int workgroups) {
-    static const int t1 = getenv("TREEQP_AMD_NAP_T1") ? atoi(getenv("TREEQP_AMD_NAP_T1")) : 128;
-    return workgroups > t1 ? 1 : 0;
-}
+static int nap_for_grid(int workgroups) { return workgroups > process_switches().nap_t1 ? 1 : 0; }
 int setup_persist(tqgpu_solver *s) {
     s->persist_ok = false;
     if (s->fast < 0 || s->n_tiers > 8) return TQGPU_OK;
@@ -2806,7 +2816,6 @@ extern "C" void tqgpu_destroy(tqgpu_solver *s) {
     for (auto &ev : s->ring_ev0) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : s->ring_ev1) if (ev) (void)hipEventDestroy(ev);
     if (s->stream) { { std::lock_guard<std::mutex> lk(g_streams_mu); g_live_streams.erase(s->stream); } (void)hipStreamDestroy(s->stream); }
-    if (s->batch_ev) (void)hipEventDestroy(s->batch_ev);
     for (int r = 0; r < 8; r++) if (s->ps_ipc[r]) (void)hipIpcCloseMemHandle(s->ps_ipc[r]);
     if (s->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(s->comm);
     s->mem.free_all();
@@ -3193,19 +3202,37 @@ namespace {
  * same time (tqgpu_solve_batch): solve_begin enqueues everything up to and including the first launch,
  * solve_end waits for the verdict, runs whatever is left (extra line-search trials, relaunches, the whole
  * Newton loop on the non-persistent paths) and fills the result. */
+/* THE list of solve-time switches: read from the environment once per public call that reaches solve_begin (tqgpu_solve, tqgpu_solve_batch),
+ * not once per member or per redo -- a getenv is a scan of the environment: two dozen of them per batch call of seven members were
+ * microseconds of a 125 us step */
+struct SolveEnv { int stamps = 0; bool no_w3_mirror = false, batch_launches = false, batch_sync = false; };
+SolveEnv read_solve_env(bool batch) {
+    SolveEnv e;
+    const char *st = getenv("TREEQP_AMD_STAMPS");
+    e.stamps = st ? std::max(1, atoi(st)) : 0;                                /* Opts::stamps: diagnostic in-kernel time stamps */
+    e.no_w3_mirror = getenv("TREEQP_AMD_NO_W3_MIRROR") != nullptr;            /* (A/B and tests) three-launch family: copy + synchronisation per read, HIP events per solve, as before */
+    if (!batch) return e;
+    e.batch_launches = getenv("TREEQP_AMD_BATCH_LAUNCHES") != nullptr;        /* one launch per tree, the round-1 protocol */
+    e.batch_sync = getenv("TREEQP_AMD_BATCH_SYNC") != nullptr;                /* every call waits for the end of its batch launches (hand_over) */
+    return e;
+}
+
 struct SolveCtx {
     Opts O;
     int launches = 0, ring = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Route route = Route::PER_PHASE;
+    Route route = Route::PER_PHASE;  /* decided by the caller: route_of(s, o, false) for a solve on its own, batch_route for a member of a batch */
+    SolveEnv env;
     bool first_launch = true, prelaunched = false, phases = false, events = true;
     unsigned batch_seq = 0;          /* != 0: this solve's persistent launch is part of a batch launch the caller makes with this launch number */
-    int env_stamps = -1, env_nomirror = -1;          /* >= 0: TREEQP_AMD_STAMPS / TREEQP_AMD_NO_W3_MIRROR as the caller read them (tqgpu_solve_batch: once per call, not once per member) */
 #ifdef TQ_HOSTPROF
     std::chrono::steady_clock::time_point hp0, hp1, hp2;
 #endif
+    SolveCtx() = default;
+    SolveCtx(const SolveEnv &e, Route r) : route(r), env(e) {}
 };
 
+/* defer: the solve runs Route::SINGLE_WG as a member of a batch launch -- its launch is described there and made by the caller */
 int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer = nullptr) {
 #ifdef TQ_HOSTPROF
     cx.hp0 = HP_NOW();
@@ -3214,8 +3241,7 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
     s->export_valid = false;
     Opts &O = cx.O;
     if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    if (cx.env_stamps >= 0) O.stamps = cx.env_stamps;          /* (a batch call reads the environment once for all its members) */
-    else { const char *e = getenv("TREEQP_AMD_STAMPS"); O.stamps = e ? std::max(1, atoi(e)) : 0; }
+    O.stamps = cx.env.stamps;
 
     if (s->sharded && !s->comm) return fail(TQGPU_ECOMM, "sharded mirror without a communicator: use tqgpu_solve_virtual_ranks");
     const Tree &T = s->T; const Data &D = s->D;
@@ -3231,7 +3257,7 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
     const size_t n_it = (size_t)std::max(o->maxIter, 1);
     if (s->times_dirty || s->iter_times.size() != n_it) s->iter_times.assign(n_it, NAN);
 
-    cx.route = s->route = route_of(s, o, defer != nullptr);
+    s->route = cx.route;
     const bool single = single_launch(cx.route), w3 = cx.route == Route::THREE_LAUNCH;
     cx.phases = o->profile >= 3;
     if (cx.phases) {
@@ -3248,8 +3274,7 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
      * start to verdict) anyway, so there the pair is optional */
     /* the three-launch family reports through the pinned result block as well (launches of k_sg / k_sgp post the control block and
      * their own clock: w3_mirror) */
-    const bool no_mirror = cx.env_nomirror >= 0 ? cx.env_nomirror != 0 : getenv("TREEQP_AMD_NO_W3_MIRROR") != nullptr;        /* (A/B and tests: copy + synchronisation per read, HIP events per solve, as before) */
-    s->w3_mirror = w3 && !o->profile && !no_mirror;
+    s->w3_mirror = w3 && !o->profile && !cx.env.no_w3_mirror;
     s->w3_seen = false;
     if (s->w3_mirror) s->h_res->seq = 0;          /* (no launch of this mirror is in flight) */
     cx.events = (s->ev_timing || (!single && !s->w3_mirror)) && !cx.batch_seq && !defer;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
@@ -3332,7 +3357,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     /* a line search that wants a second trial turns everything enqueued behind it into no-ops (~3 us a launch): a problem that
      * backtracked last time is fed two iterations at a time (TREEQP_AMD_LS_CHUNK; one C5-class tree: 1.15 ms with chunks of 8, 1.04 / 1.01 / 1.06 ms with 4 / 2 / 1),
      * a read-back per chunk instead */
-    static const int ls_chunk = getenv("TREEQP_AMD_LS_CHUNK") ? std::max(1, atoi(getenv("TREEQP_AMD_LS_CHUNK"))) : 2;
+    const int ls_chunk = process_switches().ls_chunk;
     if (s->last_ls_extra && generic && chunk > ls_chunk && !(route == Route::THREE_LAUNCH && !s->ls_pred.empty())) { chunk = ls_chunk; predicted = false; }      /* (three-launch family: the further trials are predicted too) */
     if (cx.phases) { chunk = 1; predicted = false; }            /* phase timing: one iteration per read-back, so that every recorded event belongs to work that ran */
     int rest_due = -1;                                          /* iteration whose termination test ran, whose step did not */
@@ -3373,7 +3398,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
         /* trials beyond the first go out in batches: 3, then 6, 12, 16, .. per read-back of the control block.  A trial that is
          * accepted turns the rest of its batch into no-ops (~6 us each), so short searches -- the usual case: one or two more
          * trials -- want small batches (one C5-class tree: 1.09 ms with batches of 8, 0.99 ms with 3), long ones few read-backs. */
-        static const int trial_batch0 = getenv("TREEQP_AMD_TRIAL_BATCH") ? std::max(1, atoi(getenv("TREEQP_AMD_TRIAL_BATCH"))) : 3;
+        const int trial_batch0 = process_switches().trial_batch;
         int trial_batch = trial_batch0, ls_of = -1;
         while (!s->h_ctrl->done && s->h_ctrl->ls_pending) {
             tail_done = false;
@@ -3474,14 +3499,14 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
  * the persistent path for the next `PERSIST_BACKOFF` solves, then tries it again. */
 constexpr int PERSIST_BACKOFF = 1000;
 
-static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *res) {
+static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const SolveEnv &env, tqgpu_result *res) {
     HIP_TRY(hipMemsetAsync(s->psync.timeout, 0, sizeof(unsigned), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->use_persist = 0;
     s->persist_backoff = PERSIST_BACKOFF;
     s->n_timeouts++;
     if (getenv("TREEQP_AMD_VERBOSE")) fprintf(stderr, "[treeqp_amd] persistent launch timed out (device shared?): solving on the launch-per-tier path\n");
-    SolveCtx cx;
+    SolveCtx cx(env, route_of(s, o, false));          /* a fresh decision: use_persist is off now */
     int rc = solve_begin(s, o, cx);
     if (rc != TQGPU_OK) return rc;
     return solve_end(s, o, cx, res);
@@ -3504,7 +3529,7 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
      * would fall out of step with its peers' */
     if (s->pshard && s->nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve: this mirror is rank " + std::to_string(s->rank) + " of a sharded solve (tqgpu_pshard_init): use tqgpu_pshard_begin / _end");
     if (s->persist_backoff > 0 && --s->persist_backoff == 0) s->use_persist = s->use_persist_orig;
-    SolveCtx cx;
+    SolveCtx cx(read_solve_env(false), route_of(s, o, false));
     int rc = solve_begin(s, o, cx);
     if (rc != TQGPU_OK) return rc;
     const int launches0 = cx.launches;
@@ -3515,7 +3540,7 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
     const bool ahead = s->export_ahead && single_launch(cx.route) && cx.prelaunched && !s->pshard && !s->sharded;
     if (ahead && enqueue_export(s, nullptr) != TQGPU_OK) return TQGPU_ENODEVICE;
     rc = solve_end(s, o, cx, res);
-    if (rc == TQGPU_ETIMEOUT) rc = solve_after_timeout(s, o, res);
+    if (rc == TQGPU_ETIMEOUT) rc = solve_after_timeout(s, o, cx.env, res);
     else if (rc == TQGPU_OK && ahead && res->n_launches == launches0) s->export_valid = true;
     return rc;
 }
@@ -3617,8 +3642,8 @@ static int grow_items(tqgpu_solver *s, Item *&d, Item *&h, int &cap, size_t need
 }
 static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
     const int G = lead->geom.G;
-    static const char *nap_env = getenv("TREEQP_AMD_NAP");
-    const int batch_nap = nap_env ? atoi(nap_env) : nap_for_grid(G * n_trees);     /* the whole launch polls the same memory system */
+    const ProcessSwitches &ps = process_switches();
+    const int batch_nap = ps.has_nap ? ps.nap : nap_for_grid(G * n_trees);     /* the whole launch polls the same memory system */
     static size_t lds_allowed[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     switch (kidx) {
 #define X(idx, nx, nu, md, ms) case idx: { \
@@ -3631,6 +3656,192 @@ static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items
     return TQGPU_OK;
 }
 
+/* ---- tqgpu_solve_batch step by step: member table, wave, groups, begin, group launches, end, hand-over ---- */
+
+/* what a batch call knows of one member; everything but the two group flags is decided once per call (plan_members) */
+struct BatchMember {
+    tqgpu_solver *s;
+    Route plan;                  /* route_of(s, o, true): what the waves and the groups are planned with */
+    Route alone;                 /* route_of(s, o, false): differs from `plan` only for a tree that is SINGLE_WG as a group member alone (uses_gpersist) */
+    int kidx;                    /* the batch kernel (BATCH_TABLE) this member can go out in under these options, or -1 */
+    int need;                    /* workgroups that have to be resident while it runs */
+    bool in_single_wg = false;   /* member of its wave's single-workgroup group ... */
+    bool in_persist = false;     /* ... of its wave's persistent group (form_groups) */
+    SolveCtx cx;
+};
+/* THE rule for the route a member runs: a member planned as SINGLE_WG runs it as a member of its wave's single-workgroup group, and a
+ * wave has that group only with at least two such members; without the group it runs what it would run on its own.  Every other plan
+ * is the same on its own. */
+static Route batch_route(const BatchMember &m) { return m.plan == Route::SINGLE_WG && !m.in_single_wg ? m.alone : m.plan; }
+
+static std::vector<BatchMember> plan_members(tqgpu_solver **solvers, int n, const tqgpu_opts *o) {
+    std::vector<BatchMember> tab((size_t)n);
+    for (int k = 0; k < n; k++) {
+        BatchMember &m = tab[(size_t)k];
+        tqgpu_solver *s = m.s = solvers[k];
+        m.plan = route_of(s, o, true);
+        m.alone = m.plan == Route::SINGLE_WG ? route_of(s, o, false) : m.plan;
+        m.kidx = m.plan == Route::PERSIST && o->checkLastActiveSet != 2 ? batch_kernel_index(s) : -1;
+        /* single-workgroup mirrors do not wait for each other: any number per launch; launch-per-level mirrors go alone */
+        /* (a SINGLE_WG plan counts 0 even where batch_route sends the member to a launch-per-level route in the end) */
+        m.need = m.plan == Route::PERSIST ? s->geom.G : (m.plan == Route::SINGLE_WG ? 0 : s->co_capacity + 1);
+    }
+    return tab;
+}
+
+/* j of the wave [i, j): mirrors on one device whose persistent launches fit together */
+static int wave_end(const std::vector<BatchMember> &tab, int i, const SolveEnv &env) {
+    const int n = (int)tab.size(), dev = tab[(size_t)i].s->device;
+    int used = 0, j = i;
+    for (; j < n; j++) {
+        const BatchMember &m = tab[(size_t)j];
+        const tqgpu_solver *s = m.s;
+        /* separate launches: two workgroups on one CU run at half speed each, so a batch fills the CUs once, not twice, unless a
+         * member needs more.  Members that go out together as ONE launch (batch kernel) fill the device up to what is co-resident:
+         * a tree's waves are parked at barriers and waits two thirds of the time, and trees that share CUs fill those gaps
+         * (C2: 3 trees 72 k it/s, 5 trees 98 k; C1: 22 trees 656 k, 38 trees 922 k). */
+        const bool one_launch = m.kidx >= 0 && !env.batch_launches;
+        const int cap = (!one_launch && s->n_cu > 0 && m.need <= s->n_cu) ? std::min(s->co_capacity, s->n_cu) : s->co_capacity;
+        if (j > i && (s->device != dev || used + m.need > cap)) break;
+        used += m.need;
+    }
+    return j;
+}
+
+/* members of a wave that go out as ONE launch on the lead's stream; the lead's mirror owns the descriptor array */
+struct BatchGroup {
+    std::vector<int> members;          /* indices into the member table, ascending; members[0] is the lead's */
+    tqgpu_solver *lead = nullptr;      /* nullptr: the wave has no such group */
+    size_t launched = 0;               /* members[0 .. launched) went out in the launch */
+};
+
+/* the two groups of the wave [i, j) */
+static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveEnv &env, BatchGroup &wg, BatchGroup &pg) {
+    /* single-workgroup mirrors of this wave go out as ONE launch (one workgroup per tree) on the first one's stream */
+    for (int k = i; k < j; k++) if (tab[(size_t)k].plan == Route::SINGLE_WG) wg.members.push_back(k);
+    if (wg.members.size() < 2) wg.members.clear();
+    /* persistent mirrors of this wave that share a shape with a batch kernel go out as ONE launch as well */
+    const BatchMember *f = nullptr;          /* the first one that has a batch kernel: the others have to match it */
+    for (int k = i; k < j; k++) {
+        const BatchMember &m = tab[(size_t)k];
+        if (m.kidx < 0) continue;
+        if (!f) f = &m;
+        if (m.kidx == f->kidx && m.s->geom.G == f->s->geom.G && m.s->lds_persist == f->s->lds_persist && m.s->Nn == f->s->Nn) pg.members.push_back(k);
+    }
+    if (pg.members.size() < 2 || env.batch_launches) pg.members.clear();      /* (=1: one launch per tree, the round-1 protocol) */
+    for (int k : wg.members) tab[(size_t)k].in_single_wg = true;
+    for (int k : pg.members) tab[(size_t)k].in_persist = true;
+    if (!wg.members.empty()) wg.lead = tab[(size_t)wg.members[0]].s;
+    if (!pg.members.empty()) pg.lead = tab[(size_t)pg.members[0]].s;
+    /* (the single-workgroup members describe their launches into the array as they begin) */
+    return wg.lead ? grow_items(wg.lead, wg.lead->d_gitems, wg.lead->h_gitems, wg.lead->gitems_cap, wg.members.size()) : TQGPU_OK;
+}
+
+/* before a wave begins: whatever batch launch its members were part of last has ended (settle) */
+static int settle_wave(std::vector<BatchMember> &tab, int i, int j, const BatchGroup &wg, const BatchGroup &pg) {
+    for (int k = i; k < j; k++) {
+        const BatchMember &m = tab[(size_t)k];
+        const BatchGroup *g = m.in_persist ? &pg : m.in_single_wg ? &wg : nullptr;
+        /* a member of the previous batch launch that goes out again on the same lead's stream is ordered behind it by that stream */
+        if (g && m.s->settle_stream == g->lead->stream) { if (k == g->members[0]) m.s->settle_stream = nullptr; }
+        else SETTLE(m.s);
+    }
+    return TQGPU_OK;
+}
+
+/* the launch number of the persistent group's launch, << 16 (0: no group): one more than any member's */
+static int persist_group_seq(std::vector<BatchMember> &tab, const BatchGroup &pg, unsigned &pseq) {
+    pseq = 0;
+    if (!pg.lead) return TQGPU_OK;
+    unsigned mx = 0;
+    for (int k : pg.members) mx = std::max(mx, tab[(size_t)k].s->launch_no);
+    unsigned nn = mx + 1;
+    if (nn > 0xFFFFu) {          /* the 16-bit launch number wraps: see launch_persist */
+        HIP_TRY(hipStreamSynchronize(pg.lead->stream));      /* (the previous batch launch's last workgroups are done with the slabs) */
+        for (int k : pg.members) {
+            tqgpu_solver *s = tab[(size_t)k].s;
+            HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
+            s->stream_pending = true;          /* the batch launch (on the lead's stream) waits for the wipe */
+        }
+        nn = 1;
+    }
+    pseq = nn << 16;
+    return TQGPU_OK;
+}
+
+/* the first n members of a group join the launch on the lead's stream: what the others enqueued on their own streams since their
+ * last synchronisation (stream_pending: asynchronous uploads, constant packing -- first solves and changed data only) comes before
+ * the launch, and until the wave is over the members wait for THAT stream where they would wait for their own (batch_stream;
+ * cleared by BatchGuard).  Their later work (solution export) is ordered behind the launch lazily, see hand_over and settle(). */
+/* (round 3: no event traffic in the steady state -- a record and a wait per member before the launch and another wait after it
+ * were 1.5 ms of an 11.5 ms step with 256 single-workgroup trees, a pair of calls per member and step most of a step with 22 small
+ * persistent ones) */
+static int join_lead_stream(std::vector<BatchMember> &tab, const BatchGroup &g, size_t n) {
+    for (size_t m = 1; m < n; m++) {
+        tqgpu_solver *sm = tab[(size_t)g.members[m]].s;
+        if (sm->stream_pending) { HIP_TRY(hipStreamSynchronize(sm->stream)); sm->stream_pending = false; }
+    }
+    for (size_t m = 0; m < n; m++) tab[(size_t)g.members[m]].s->batch_stream = g.lead->stream;
+    return TQGPU_OK;
+}
+
+/* g_persist_batch over the first n members of the group (those that have begun: solve_begin described each one's launch in the lead's array) */
+static int launch_single_wg_group(std::vector<BatchMember> &tab, BatchGroup &wg, size_t n) {
+    tqgpu_solver *lead = wg.lead;
+    size_t lds_batch = 0;
+    for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)wg.members[m]].s->lds_gp_total);
+    int rc = join_lead_stream(tab, wg, n);
+    if (rc != TQGPU_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(lead->d_gitems, lead->h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));
+    if (lds_batch > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_batch));
+    hipLaunchKernelGGL(g_persist_batch, dim3((unsigned)n), dim3(GP_WAVES * WAVE), lds_batch, lead->stream, lead->d_gitems, tab[(size_t)wg.members[0]].cx.O);
+    wg.launched = n;
+    return TQGPU_OK;
+}
+
+/* f_persist_batch over the whole group, with the launch number of persist_group_seq */
+static int launch_persist_group(std::vector<BatchMember> &tab, BatchGroup &pg, unsigned pseq) {
+    tqgpu_solver *pl = pg.lead;
+    const size_t np = pg.members.size();
+    if (pl->pitems_cap < (int)np) pl->pitems_key.clear();
+    if (int rc = grow_items(pl, pl->d_pitems, pl->h_pitems, pl->pitems_cap, np)) return rc;
+    std::vector<unsigned long> key;
+    for (int k : pg.members) key.push_back(tab[(size_t)k].s->uid);
+    if (key != pl->pitems_key) {
+        /* the descriptors are what the single launches pass as kernel arguments; they do not change from solve to solve, so
+         * the device copy is refreshed only when the batch is composed of other mirrors than last time */
+        HIP_TRY(hipStreamSynchronize(pl->stream));                 /* a previous batch launch may still read the array */
+        for (size_t m = 0; m < np; m++) { const tqgpu_solver *sm = tab[(size_t)pg.members[m]].s; pl->h_pitems[m].C = sm->pconst; pl->h_pitems[m].Gm = sm->geom; pl->h_pitems[m].Sy = sm->psync; }
+        HIP_TRY(hipMemcpyAsync(pl->d_pitems, pl->h_pitems, np * sizeof(PItem), hipMemcpyHostToDevice, pl->stream));
+        pl->pitems_key = key;
+    }
+    int rc = join_lead_stream(tab, pg, np);
+    if (rc != TQGPU_OK) return rc;
+    const BatchMember &lead = tab[(size_t)pg.members[0]];
+    if ((rc = launch_persist_batch(pl, lead.kidx, pl->d_pitems, lead.cx.O, (int)np, pseq)) != TQGPU_OK) return rc;
+    pg.launched = np;
+    return TQGPU_OK;
+}
+
+/* after a wave: the members' later work (solution export, the next solve) runs on their own streams: it has to find the batch launch
+ * complete -- every verdict is in, so this waits for the write-back of the last workgroups only, once per batch (sync: after an
+ * error, or TREEQP_AMD_BATCH_SYNC), or leaves the wait to the first such use */
+static int hand_over(std::vector<BatchMember> &tab, const BatchGroup &g, bool sync) {
+    if (!g.launched) return TQGPU_OK;
+    if (sync) HIP_TRY(hipStreamSynchronize(g.lead->stream));
+    else for (size_t m = 1; m < g.launched; m++) tab[(size_t)g.members[m]].s->settle_stream = g.lead->stream;      /* see settle() */
+    return TQGPU_OK;
+}
+
+/* the per-call state a batch leaves on its members, taken back on EVERY exit: in_batch (see tqgpu_solver::in_batch) on all of them,
+ * batch_stream on those of the current wave (wait_result_block and the redo after a timeout read it while the wave is in flight) */
+struct BatchGuard {
+    tqgpu_solver **v; int n, w0 = 0, w1 = 0;
+    BatchGuard(tqgpu_solver **v_, int n_) : v(v_), n(n_) { for (int i = 0; i < n; i++) v[i]->in_batch = true; }
+    void wave(int i, int j) { for (int k = w0; k < w1; k++) v[k]->batch_stream = nullptr; w0 = i; w1 = j; }
+    ~BatchGuard() { wave(0, 0); for (int i = 0; i < n; i++) v[i]->in_batch = false; }
+};
+
 /* Batched multi-tree solve (the usage pattern of examples/fault_tolerance.c:486-530, one QP per
  * configuration): n independent mirrors, same options.  Mirrors on the persistent path have their launches in
  * flight together, as many at a time as fit on the device at once (every workgroup of a persistent launch must
@@ -3640,165 +3851,47 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
     if (!solvers || n < 1 || !o || !results) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: bad arguments");
     for (int i = 0; i < n; i++) if (!solvers[i]) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: null mirror");
     for (int i = 0; i < n; i++) if (solvers[i]->pshard && solvers[i]->nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: a member is one rank of a sharded solve (tqgpu_pshard_init)");
-    std::vector<SolveCtx> cx((size_t)n);
-    struct InBatch {                    /* (see tqgpu_solver::in_batch) */
-        tqgpu_solver **v; int n;
-        InBatch(tqgpu_solver **v_, int n_) : v(v_), n(n_) { for (int i = 0; i < n; i++) v[i]->in_batch = true; }
-        ~InBatch() { for (int i = 0; i < n; i++) v[i]->in_batch = false; }
-    } in_batch_guard(solvers, n);
-    /* the environment switches of a batch call, read ONCE (a getenv is a scan of the environment: two dozen of them per call of seven members
-     * were microseconds of a 125 us step) */
-    const bool env_batch_launches = getenv("TREEQP_AMD_BATCH_LAUNCHES") != nullptr, env_batch_sync = getenv("TREEQP_AMD_BATCH_SYNC") != nullptr;
-    {
-        const char *e = getenv("TREEQP_AMD_STAMPS");
-        const int st = e ? std::max(1, atoi(e)) : 0, nm = getenv("TREEQP_AMD_NO_W3_MIRROR") != nullptr ? 1 : 0;
-        for (int k = 0; k < n; k++) { cx[(size_t)k].env_stamps = st; cx[(size_t)k].env_nomirror = nm; }
-    }
-    int first_err = TQGPU_OK;
-    std::string first_msg;
+    BatchGuard guard(solvers, n);
+    const SolveEnv env = read_solve_env(true);
     for (int k = 0; k < n; k++) {          /* as tqgpu_solve: a mirror that backed off the persistent path returns to it after PERSIST_BACKOFF solves */
         tqgpu_solver *sk = solvers[k];
         if (sk->persist_backoff > 0 && --sk->persist_backoff == 0) sk->use_persist = sk->use_persist_orig;
     }
-    int i = 0;
-    while (i < n) {
-        /* a wave of mirrors on one device whose persistent launches fit together */
-        const int dev = solvers[i]->device;
-        int used = 0, j = i;
-        for (; j < n; j++) {
-            tqgpu_solver *s = solvers[j];
-            const Route r = route_of(s, o, true);
-            /* single-workgroup mirrors do not wait for each other: any number per launch; launch-per-level mirrors go alone */
-            const int need = r == Route::PERSIST ? s->geom.G : (r == Route::SINGLE_WG ? 0 : s->co_capacity + 1);
-            /* separate launches: two workgroups on one CU run at half speed each, so a batch fills the CUs once, not twice, unless a
-             * member needs more.  Members that go out together as ONE launch (batch kernel) fill the device up to what is co-resident:
-             * a tree's waves are parked at barriers and waits two thirds of the time, and trees that share CUs fill those gaps
-             * (C2: 3 trees 72 k it/s, 5 trees 98 k; C1: 22 trees 656 k, 38 trees 922 k). */
-            const bool one_launch = r == Route::PERSIST && batch_kernel_index(s) >= 0 && o->checkLastActiveSet != 2 && !env_batch_launches;
-            const int cap = (!one_launch && s->n_cu > 0 && need <= s->n_cu) ? std::min(s->co_capacity, s->n_cu) : s->co_capacity;
-            if (j > i && (s->device != dev || used + need > cap)) break;
-            used += need;
-        }
-        const int begun_from = i, begun_to = j;
-        int ok_to = begun_from;
-        /* single-workgroup mirrors of this wave go out as ONE launch (one workgroup per tree) on the first one's stream */
-        std::vector<int> gp_members;
-        for (int k = begun_from; k < begun_to; k++)
-            if (route_of(solvers[k], o, true) == Route::SINGLE_WG) gp_members.push_back(k);
-        tqgpu_solver *lead = gp_members.size() >= 2 ? solvers[gp_members[0]] : nullptr;
-        if (lead) { int rc = grow_items(lead, lead->d_gitems, lead->h_gitems, lead->gitems_cap, gp_members.size()); if (rc) return rc; }
-        /* persistent mirrors of this wave that share a shape with a batch kernel go out as ONE launch as well */
-        std::vector<int> pm;
-        {
-            const tqgpu_solver *f = nullptr;
-            for (int k = begun_from; k < begun_to; k++) {
-                const tqgpu_solver *s = solvers[k];
-                if (!(route_of(s, o, true) == Route::PERSIST && o->checkLastActiveSet != 2 && batch_kernel_index(s) >= 0)) continue;
-                if (!f) f = s;
-                if (batch_kernel_index(s) == batch_kernel_index(f) && s->geom.G == f->geom.G && s->lds_persist == f->lds_persist && s->Nn == f->Nn) pm.push_back(k);
-            }
-            if (pm.size() < 2 || env_batch_launches) pm.clear();      /* (=1: one launch per tree, the round-1 protocol) */
-        }
-        for (int k = begun_from; k < begun_to; k++) {
-            /* a member of the previous batch launch that goes out again on the same lead's stream is ordered behind it by that stream */
-            const bool same_lead = (!pm.empty() && solvers[k]->settle_stream == solvers[pm[0]]->stream && std::find(pm.begin(), pm.end(), k) != pm.end()) ||
-                                   (lead && solvers[k]->settle_stream == lead->stream && std::find(gp_members.begin(), gp_members.end(), k) != gp_members.end());
-            if (same_lead) { if ((!pm.empty() && k == pm[0]) || (lead && k == gp_members[0])) solvers[k]->settle_stream = nullptr; }
-            else SETTLE(solvers[k]);
-        }
+    std::vector<BatchMember> tab = plan_members(solvers, n, o);          /* (after the loop above: route_of reads use_persist) */
+    int first_err = TQGPU_OK, rc;
+    std::string first_msg;
+    for (int i = 0, j; i < n && first_err == TQGPU_OK; i = j) {
+        j = wave_end(tab, i, env);
+        guard.wave(i, j);
+        BatchGroup wg, pg;          /* single-workgroup group, persistent group */
         unsigned pseq = 0;
-        if (!pm.empty()) {
-            unsigned mx = 0;
-            for (int k : pm) mx = std::max(mx, solvers[k]->launch_no);
-            unsigned nn = mx + 1;
-            if (nn > 0xFFFFu) {          /* the 16-bit launch number wraps: see launch_persist */
-                HIP_TRY(hipStreamSynchronize(solvers[pm[0]]->stream));      /* (the previous batch launch's last workgroups are done with the slabs) */
-                for (int k : pm) {
-                    HIP_TRY(hipMemsetAsync(solvers[k]->sync_slab, 0, solvers[k]->sync_bytes, solvers[k]->stream));
-                    solvers[k]->stream_pending = true;          /* the batch launch (on the lead's stream) waits for the wipe */
-                }
-                nn = 1;
-            }
-            pseq = nn << 16;
-        }
-        size_t gi = 0, lds_batch = 0, pi = 0;
-        bool gp_launched = false;
-        for (int k = begun_from; k < begun_to; k++) {
-            const bool in_group = lead && gi < gp_members.size() && gp_members[gi] == k;
-            if (pi < pm.size() && pm[pi] == k) { cx[(size_t)k].batch_seq = pseq; pi++; }
-            int rc = solve_begin(solvers[k], o, cx[(size_t)k], in_group ? &lead->h_gitems[gi] : nullptr);
-            if (rc != TQGPU_OK) { if (first_err == TQGPU_OK) { first_err = rc; first_msg = g_err; } break; }
-            if (in_group) { gi++; lds_batch = std::max(lds_batch, solvers[k]->lds_gp_total); }
+        if ((rc = form_groups(tab, i, j, env, wg, pg)) || (rc = settle_wave(tab, i, j, wg, pg)) || (rc = persist_group_seq(tab, pg, pseq))) return rc;
+        int ok_to = i;
+        size_t gi = 0;              /* members of the single-workgroup group that have begun */
+        for (int k = i; k < j; k++) {
+            BatchMember &m = tab[(size_t)k];
+            m.cx = SolveCtx(env, batch_route(m));
+            if (m.in_persist) m.cx.batch_seq = pseq;
+            rc = solve_begin(m.s, o, m.cx, m.in_single_wg ? &wg.lead->h_gitems[gi] : nullptr);
+            if (rc != TQGPU_OK) { first_err = rc; first_msg = g_err; break; }
+            if (m.in_single_wg) gi++;
             ok_to = k + 1;
         }
-        if (lead && gi > 0) {
-            hipStream_t st0 = lead->stream;
-            /* inputs of the other members were uploaded on their own streams: order the launch behind them, and their
-             * later work (solution export) behind the launch */
-            /* (round 3: no event traffic in the steady state -- a record and a wait per member before the launch and another wait after it
-             * were 1.5 ms of an 11.5 ms step with 256 trees.  What a member enqueued on its own stream since its last synchronisation
-             * (asynchronous uploads: stream_pending) is waited for here; the launch's end is waited for lazily, see settle().) */
-            for (size_t m = 1; m < gi; m++) {
-                tqgpu_solver *sm = solvers[gp_members[m]];
-                if (sm->stream_pending) { HIP_TRY(hipStreamSynchronize(sm->stream)); sm->stream_pending = false; }
-            }
-            HIP_TRY(hipMemcpyAsync(lead->d_gitems, lead->h_gitems, gi * sizeof(GItem), hipMemcpyHostToDevice, st0));
-            if (lds_batch > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_batch));
-            hipLaunchKernelGGL(g_persist_batch, dim3((unsigned)gi), dim3(GP_WAVES * WAVE), lds_batch, st0, lead->d_gitems, cx[(size_t)gp_members[0]].O);
-            for (size_t m = 0; m < gi; m++) solvers[gp_members[m]]->batch_stream = st0;
-            gp_launched = true;
-        }
-        if (!pm.empty() && ok_to == begun_to) {
-            tqgpu_solver *pl = solvers[pm[0]];
-            const size_t np = pm.size();
-            if (pl->pitems_cap < (int)np) pl->pitems_key.clear();
-            if (int rc = grow_items(pl, pl->d_pitems, pl->h_pitems, pl->pitems_cap, np)) return rc;
-            std::vector<unsigned long> key;
-            for (int k : pm) key.push_back(solvers[k]->uid);
-            hipStream_t st0 = pl->stream;
-            if (key != pl->pitems_key) {
-                /* the descriptors are what the single launches pass as kernel arguments; they do not change from solve to solve, so
-                 * the device copy is refreshed only when the batch is composed of other mirrors than last time */
-                HIP_TRY(hipStreamSynchronize(st0));                 /* a previous batch launch may still read the array */
-                for (size_t m = 0; m < np; m++) { const tqgpu_solver *sm = solvers[pm[m]]; pl->h_pitems[m].C = sm->pconst; pl->h_pitems[m].Gm = sm->geom; pl->h_pitems[m].Sy = sm->psync; }
-                HIP_TRY(hipMemcpyAsync(pl->d_pitems, pl->h_pitems, np * sizeof(PItem), hipMemcpyHostToDevice, st0));
-                pl->pitems_key = key;
-            }
-            /* what the other members enqueued on their own streams since their last synchronisation (asynchronous uploads, constant
-             * packing: first solves and changed data only) comes before the launch.  No per-member event traffic in the steady state:
-             * a pair of calls per member and step was most of a step with 22 small trees. */
-            for (size_t m = 1; m < np; m++) {
-                tqgpu_solver *sm = solvers[pm[m]];
-                if (sm->stream_pending) { HIP_TRY(hipStreamSynchronize(sm->stream)); sm->stream_pending = false; }
-            }
-            for (int k : pm) solvers[k]->batch_stream = st0;
-            int rcb = launch_persist_batch(pl, batch_kernel_index(pl), pl->d_pitems, cx[(size_t)pm[0]].O, (int)np, pseq);
-            if (rcb != TQGPU_OK) { for (int k : pm) solvers[k]->batch_stream = nullptr; return rcb; }
-        }
-        for (int k = begun_from; k < ok_to; k++) {
+        if (gi > 0 && (rc = launch_single_wg_group(tab, wg, gi))) return rc;
+        if (pg.lead && ok_to == j && (rc = launch_persist_group(tab, pg, pseq))) return rc;
+        for (int k = i; k < ok_to; k++) {
             tqgpu_solver *sk = solvers[k];
-            int rc = solve_end(sk, o, cx[(size_t)k], &results[k]);
+            rc = solve_end(sk, o, tab[(size_t)k].cx, &results[k]);
             if (rc == TQGPU_ETIMEOUT) {
                 /* device shared: redone on its own, see tqgpu_solve.  The redo works on the same device state as the batch launch,
                  * whose later workgroups may not even have started: the launch has to be over before the sticky word is cleared */
                 if (sk->batch_stream) HIP_TRY(hipStreamSynchronize(sk->batch_stream));
-                rc = solve_after_timeout(sk, o, &results[k]);
+                rc = solve_after_timeout(sk, o, env, &results[k]);
             }
             if (rc != TQGPU_OK && first_err == TQGPU_OK) { first_err = rc; first_msg = g_err; }
         }
-        for (int k = begun_from; k < begun_to; k++) solvers[k]->batch_stream = nullptr;
-        /* the members' later work (solution export, the next solve) runs on their own streams: it has to find the batch launch
-         * complete -- every verdict is in, so this waits for the write-back of the last workgroups only, once per batch */
-        if (!pm.empty() && ok_to == begun_to) {
-            if (first_err != TQGPU_OK || env_batch_sync) HIP_TRY(hipStreamSynchronize(solvers[pm[0]]->stream));
-            else for (size_t m = 1; m < pm.size(); m++) solvers[pm[m]]->settle_stream = solvers[pm[0]]->stream;      /* see settle() */
-        }
-        if (gp_launched) {
-            if (first_err != TQGPU_OK || env_batch_sync) HIP_TRY(hipStreamSynchronize(lead->stream));
-            else for (size_t m = 1; m < gi; m++) solvers[gp_members[m]]->settle_stream = lead->stream;
-        }
-        if (first_err != TQGPU_OK) break;
-        i = j;
+        const bool sync = first_err != TQGPU_OK || env.batch_sync;
+        if ((rc = hand_over(tab, pg, sync)) || (rc = hand_over(tab, wg, sync))) return rc;
     }
     if (first_err != TQGPU_OK) return fail(first_err, first_msg);
     return TQGPU_OK;
