@@ -168,6 +168,17 @@ def offsets(d):
     return np.concatenate([[0], np.cumsum(d["nx"])]), np.concatenate([[0], np.cumsum(d["nu"])])
 
 
+def with_dense_blocks(d):
+    """flat clipping QP -> the same QP with Q, R, S as dense (diagonal) blocks, as tqgpu_set_objective_mixed takes them"""
+    d = {k: np.array(v, copy=True) for k, v in d.items()}
+    xo, uo = offsets(d)
+    nx, nu = d["nx"], d["nu"]
+    d["Q"] = np.concatenate([np.diag(d["Qd"][xo[k]:xo[k + 1]]).ravel(order="F") for k in range(len(nx))])
+    d["R"] = np.concatenate([np.diag(d["Rd"][uo[k]:uo[k + 1]]).ravel(order="F") for k in range(len(nx))])
+    d["S"] = np.zeros(int(np.sum(np.asarray(nx) * np.asarray(nu))))
+    return d
+
+
 def global_kkt(d, fixed=None):
     """Solve the equality-constrained QP of the whole tree in numpy: min 1/2 z'Hz + g'z s.t. the dynamics and z_i = bound_i on the
     entries `fixed` (dict index -> value).  z = [x | u].  Returns z and the multipliers of the fixed entries (>= 0 on a lower bound)."""

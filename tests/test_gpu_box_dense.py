@@ -9,7 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from helpers import assert_solution_close, bounds_vec, certify, global_kkt, offsets, product_qp_from_lti
+from helpers import assert_solution_close, bounds_vec, certify, global_kkt, offsets, product_qp_from_lti, with_dense_blocks
 from treeqp_amd import problems as P
 
 pytestmark = pytest.mark.gpu
@@ -33,17 +33,6 @@ def gpu(capi):
 # ---------------------------------------------------------------------------------------------------------------------------
 # problem construction and an independent certificate
 # ---------------------------------------------------------------------------------------------------------------------------
-
-def with_dense_blocks(d):
-    """flat clipping QP -> the same QP with Q, R, S as dense (diagonal) blocks, as tqgpu_set_objective_mixed takes them"""
-    d = {k: np.array(v, copy=True) for k, v in d.items()}
-    xo, uo = offsets(d)
-    nx, nu = d["nx"], d["nu"]
-    d["Q"] = np.concatenate([np.diag(d["Qd"][xo[k]:xo[k + 1]]).ravel(order="F") for k in range(len(nx))])
-    d["R"] = np.concatenate([np.diag(d["Rd"][uo[k]:uo[k + 1]]).ravel(order="F") for k in range(len(nx))])
-    d["S"] = np.zeros(int(np.sum(np.asarray(nx) * np.asarray(nu))))
-    return d
-
 
 def stage_of(nk):
     dad = P.parents_of(nk)
