@@ -62,7 +62,7 @@ typedef struct tqgpu_opts {
 } tqgpu_opts;
 
 typedef struct tqgpu_result {
-    int status;                  /* return_t value: 0 optimal, 1 max iterations, 2 not a descent direction, 4 stage QP solve failed (box nodes) */
+    int status;                  /* return_t value: 0 optimal, 1 max iterations, 2 not a descent direction, 4 stage QP solve failed (box nodes, nodes with general constraints) */
     int iter;                    /* Newton iterations */
     int ls_total;                /* total line-search trials */
     int ls_last;                 /* trials of the last iteration */
@@ -89,6 +89,7 @@ int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const double *Rd
 int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const double *R, const double *S, const double *q, const double *r);
 /* the same with a per-node choice (opts->qp_solver[] of the reference, dual_Newton_tree.c:124-162): kind[k] = 0 clipping (the
  * diagonals of Q_k and R_k are the weights; off-diagonals and S_k must be zero), 1 dense unconstrained (bounds ignored),
+ * 3 dense with box bounds and the general constraints of tqgpu_set_constraints (below; without rows on the node: kind 2),
  * 2 dense with box bounds: the bounds of tqgpu_set_bounds apply (qpOASES QProblemB of the reference,
  * dual_Newton_tree_qpoases.c:153-210, 312-358, 524-560: a hot-started active-set method on the bounds per node, one wave each,
  * P_k = Z (Z'H_k Z)^-1 Z' of the final working set, multipliers of the bounds in mu_x / mu_u).  NULL = all kind 1.
@@ -99,6 +100,16 @@ int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const double *R,
  * kept for the hot start are only a starting guess. */
 int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const double *Q, const double *R, const double *S, const double *q, const double *r);
 int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const double *xmax, const double *umin, const double *umax);
+/* General constraints dmin <= C x + D u <= dmax on the nodes of kind 3 (qpOASES QProblem of the reference,
+ * dual_Newton_tree_qpoases.c:226-300, 312-358, 524-570): nc[k] rows on node k, C (nc x nx) and D (nc x nu) column major, node after
+ * node; NULL = leave alone.  nc != NULL (re)defines the rows: C, D not given with it are zero, dmin, dmax unbounded.  The stage QP
+ * is solved by a dual active-set method (Goldfarb and Idnani), one wave per node, on the launch-per-phase route; it needs
+ * nx[k] + nu[k] <= 64 (TQGPU_EUNSUPPORTED from tqgpu_set_objective_mixed) and nc[k] <= 64 (TQGPU_EUNSUPPORTED from this call);
+ * dmin > dmax is TQGPU_EINVAL.  An infeasible stage QP ends tqgpu_solve with tqgpu_result.status = 4.  The multipliers of the
+ * rows (sign of tree_qp_out.mu_d: + on dmax, - on dmin) come from tqgpu_get_mu_d, sum_nc doubles (tqgpu_dims2). */
+int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const double *C, const double *D, const double *dmin, const double *dmax);
+int tqgpu_get_mu_d(tqgpu_solver *s, double *mu_d);
+int tqgpu_dims2(const tqgpu_solver *s, int *sum_nc);
 /* Everything above in one call (NULL = leave alone) plus the starting duals: compared with a pinned host mirror of
  * what the device holds, only what changed is uploaded, without synchronisation.  This is what the drop-in
  * treeqp_tdunes_solve uses, which -- like the reference, dual_Newton_tree.c:1142-1160 -- re-reads qp_in at every solve. */
@@ -142,6 +153,7 @@ int tqgpu_uses_fused_path(const tqgpu_solver *s);
 #define TQGPU_PLAN_DENSE           (1u << 15)   /* dense stage solver selected */
 #define TQGPU_PLAN_BOX             (1u << 16)   /* ... with box-constrained nodes */
 #define TQGPU_PLAN_LAST_SINGLE_WG  (1u << 17)   /* the last solve begun (alone or in a batch) ran the single-workgroup kernel */
+#define TQGPU_PLAN_GEN             (1u << 18)   /* dense stage solver with nodes that have general constraints (kind 3) */
 int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs);
 /* geometry of the persistent launch: block levels, tiers, workgroups per launch, co-resident workgroup capacity of the device, CUs */
 int tqgpu_geometry(const tqgpu_solver *s, int *levels, int *tiers, int *workgroups, int *capacity, int *compute_units);

@@ -220,6 +220,10 @@ class TreeQp:
     def set_node_bounds(self, k, xmin, xmax, umin, umax):
         lib().tree_qp_in_set_node_bounds(_dp(_f64(xmin)), _dp(_f64(xmax)), _dp(_f64(umin)), _dp(_f64(umax)), C.byref(self.qp_in), int(k))
 
+    def set_node_general_constraints(self, k, C_, D, dmin, dmax):
+        f = lambda M: _dp(_f64(np.asarray(M).reshape(-1, order="F") if np.ndim(M) == 2 else M))
+        lib().tree_qp_in_set_node_general_constraints(f(C_), f(D), _dp(_f64(dmin)), _dp(_f64(dmax)), C.byref(self.qp_in), int(k))
+
     def set_ltv_dynamics(self, A, B, b):
         lib().tree_qp_in_set_ltv_dynamics_colmajor(_dp(_f64(A)), _dp(_f64(B)), _dp(_f64(b)), C.byref(self.qp_in))
 
@@ -274,8 +278,11 @@ class TreeQp:
     def solution(self) -> dict:
         o = self.qp_out
         N = self.N
-        return dict(x=self._cat_vec(o.x, N), u=self._cat_vec(o.u, N), lam=self._cat_vec(o.lam, N - 1),
-                    mu_x=self._cat_vec(o.mu_x, N), mu_u=self._cat_vec(o.mu_u, N))
+        out = dict(x=self._cat_vec(o.x, N), u=self._cat_vec(o.u, N), lam=self._cat_vec(o.lam, N - 1),
+                   mu_x=self._cat_vec(o.mu_x, N), mu_u=self._cat_vec(o.mu_u, N))
+        if any(o.mu_d[k].m for k in range(N)):
+            out["mu_d"] = self._cat_vec(o.mu_d, N)
+        return out
 
     def set_solution(self, sol: dict):
         """Write a flat solution into qp_out (used to exercise the host KKT check without a GPU)."""
@@ -288,6 +295,11 @@ class TreeQp:
                 m = arr[k].m
                 setter(_dp(_f64(sol[name][off[name]:off[name] + m])), C.byref(o), k)
                 off[name] += m
+            if "mu_d" in sol and o.mu_d[k].m:
+                m = o.mu_d[k].m
+                at = off.setdefault("mu_d", 0)
+                L.tree_qp_out_set_node_mu_d(_dp(_f64(sol["mu_d"][at:at + m])), C.byref(o), k)
+                off["mu_d"] = at + m
             if k > 0:
                 m = o.lam[k - 1].m
                 L.tree_qp_out_set_edge_lam(_dp(_f64(sol["lam"][off["lam"]:off["lam"] + m])), C.byref(o), k - 1)
@@ -513,7 +525,7 @@ class TqGpu:
 
     PLAN_FLAGS = ("wide", "wide_small", "w3", "w3_sgp", "w3_merge", "fwd_chain", "fuse", "persist", "persist_one", "gpersist",
                   "gp_state_lds", "gp_const_lds", "gp_tables_lds", "gp_small16", "gp_small8", "dense", "box",
-                  "last_single_wg")
+                  "last_single_wg", "gen")
 
     @property
     def plan(self) -> dict:
@@ -570,6 +582,17 @@ class TqGpu:
         self.set_lambda(lambda0)
         return self
 
+    def set_constraints(self, nc=None, C_=None, D=None, dmin=None, dmax=None):
+        """General constraints dmin <= C x + D u <= dmax of the kind-3 nodes: nc rows per node, C (nc x nx) and D (nc x nu) column
+        major, flat, node after node; None = leave alone (nc given: C, D not given are zero, dmin, dmax unbounded)."""
+        keep = [None if a is None else _f64(a) for a in (C_, D, dmin, dmax)]
+        n = None if nc is None else _i32(nc)
+        self._chk(lib().tqgpu_set_constraints(self.h, None if n is None else _ip(n), *[_dp(a) for a in keep]))
+        v = C.c_int()
+        self._chk(lib().tqgpu_dims2(self.h, C.byref(v)))
+        self.sum_nc = v.value
+        return self
+
     def set_lambda(self, lam):
         a = None if lam is None else _f64(lam)
         if a is not None:
@@ -622,6 +645,9 @@ class TqGpu:
         out = dict(x=np.zeros(self.sum_nx), u=np.zeros(self.sum_nu), lam=np.zeros(self.sum_lam),
                    mu_x=np.zeros(self.sum_nx), mu_u=np.zeros(self.sum_nu), dlam=np.zeros(self.sum_lam))
         self._chk(lib().tqgpu_get_solution(self.h, _dp(out["x"]), _dp(out["u"]), _dp(out["lam"]), _dp(out["mu_x"]), _dp(out["mu_u"]), _dp(out["dlam"])))
+        if getattr(self, "sum_nc", 0):          # general constraints were set: the multipliers of the rows
+            out["mu_d"] = np.zeros(self.sum_nc)
+            self._chk(lib().tqgpu_get_mu_d(self.h, _dp(out["mu_d"])))
         return out
 
     def iteration_log(self, cap=4096):

@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <numeric>
 #include <set>
 #include <string>
 #include <vector>
@@ -123,6 +124,19 @@ struct Data {            /* device pointers, passed by value */
      * bound), kept across sweeps and solves as the hot start; [Nn, 2 Nn) the working set that P_k was last built for */
     unsigned long long *bmask;
     int xpad;                 /* phantom root states of an x0-eliminated tree embedded in a uniform one: unbounded in stage_box */
+    const struct Gen *gen;    /* dense nodes with box bounds and general constraints (kind 3, stage_gen); nullptr until tqgpu_set_constraints */
+};
+
+/* general constraints dmin <= G z <= dmax of the kind-3 nodes, G = [C | D] (tqgpu_set_constraints): a record in device memory, so that
+ * Data grows by one pointer */
+struct Gen {
+    const int *nc;            /* [Nn] rows of node k */
+    const int *roff;          /* [Nn + 1] offsets of the rows (dmin, dmax, mu) */
+    const int *goff;          /* [Nn + 1] offsets of the blocks of Gt */
+    const double *Gt;         /* per node: row r of G at Gt[r nz .. r nz + nz) (phantom root states included, zero) */
+    const double *dmin, *dmax;
+    double *mu;               /* row multipliers of the last stage solve, with the sign of qp_out->mu_d; 0 off the working set */
+    unsigned long long *rmask;   /* [0, Nn) rows in the final working set of node k; [Nn, 2 Nn) the rows P_k was last built for */
 };
 
 struct Opts {
@@ -250,7 +264,8 @@ __global__ void __launch_bounds__(WAVE) k_dense_init(Tree T, Data D) {
     const int k = blockIdx.x, lane = threadIdx.x;
     const int nz = T.nx[k] + T.nu[k];
     if (nz == 0 || !D.kind[k]) return;
-    if (D.kind[k] == 2 && lane == 0) D.bmask[T.Nn + k] = 0ull;      /* box nodes: P below is the one of the empty working set */
+    if (D.kind[k] >= 2 && lane == 0) D.bmask[T.Nn + k] = 0ull;      /* box nodes: P below is the one of the empty working set */
+    if (D.kind[k] == 3 && lane == 0) D.gen->rmask[T.Nn + k] = 0ull;
     const double *H = D.Hd + D.poff[k];
     double *P = D.Pd + D.poff[k];
     double *Lm = lds;                      /* nz x nz, ld = nz */
@@ -480,7 +495,242 @@ __device__ void stage_box(const Tree &T, const Data &D, int k, int lane, double 
     if (lane == 0) D.bmask[T.Nn + k] = m;
 }
 
-template <bool BOX = false>
+
+/* ------------------------------------------------------------------------------------------ */
+/* stage_gen: the stage QP of a dense node with box bounds and general constraints (kind 3) -- */
+/* the qpOASES QProblem solve of the reference (dual_Newton_tree_qpoases.c:226-300, 312-358)   */
+/* as a dual active-set method (Goldfarb and Idnani) in one wave:                              */
+/*   z = argmin 1/2 z'Hz - hmod'z  s.t.  lb <= z <= ub,  dmin <= G z <= dmax,  G = [C | D]      */
+/* Lane i owns entry i of z (nz <= 64) and row i of G (nc <= 64).  The working set is a set of */
+/* bounds (fixed entries, as in stage_box: M is H with the rows and columns of fixed entries   */
+/* replaced by those of the identity, so fixed entries stay exactly on their bound) and a set  */
+/* of rows W; Y = L^-1 G_W' on the free entries (L the factor of M) and S = Y'Y, with the rows */
+/* and columns of the rows outside W replaced by those of the identity, are rebuilt and        */
+/* factorised at every step.  The method starts at the minimiser over the equalities (entries  */
+/* with lb == ub, rows with dmin == dmax) and needs no feasible point.  Per step: the most     */
+/* violated constraint p (lowest index on ties, bounds before rows), the primal direction      */
+/* dz = P n_p and the dual direction r, the step min(t_dual, t_full); a partial step drops the */
+/* blocking member and keeps p, a full step adds p.  n_p'P n_p <= 64 eps n_p'M^-1 n_p means p   */
+/* depends on the working set: only the dual step is taken.  No step at all: the stage QP is   */
+/* infeasible (status 4, as a non-positive pivot and the step cap).  Every decision is a       */
+/* wave-uniform ballot.  The returned z and row multipliers are the solution of the final      */
+/* working set's system alone, not of the path; every stage solve starts cold, so a repeated   */
+/* solve is bit-identical.  P = M^-1 - M^-1 G_W' S^-1 G_W M^-1 (fixed rows and columns zero)   */
+/* is rebuilt only when either mask differs from the one it was built for.                     */
+/* ------------------------------------------------------------------------------------------ */
+#define GEN_MAX_STEPS(nz, nc) (4 * ((nz) + (nc)) + 8)
+__device__ void stage_gen(const Tree &T, const Data &D, int k, int lane, double *lds, const double *hm, const double *lk, int ko, bool save_s) {
+    const Gen &Gn = *D.gen;
+    const int nxk = T.nx[k], nuk = T.nu[k], xo = T.xoff[k], uo = T.uoff[k], d = T.bdim[k];
+    const int nz = nxk + nuk, nc = Gn.nc[k], ro = Gn.roff[k];
+    double *dv = lds;                      /* nz: 1 / L_ii */
+    double *sv = dv + nz;                  /* nc: 1 / (factor of S)_ii */
+    double *Hs = sv + nc;                  /* nz x nz, column major: H_k */
+    double *Ls = Hs + (size_t)nz * nz;     /* nz x nz: Cholesky factor of M */
+    double *Ys = Ls + (size_t)nz * nz;     /* nz x nc: Y, the columns of the rows in W */
+    double *Ss = Ys + (size_t)nz * nc;     /* nc x nc: S and its factor */
+    const double *Hg = D.Hd + D.poff[k];
+    const double *Gt = Gn.Gt + Gn.goff[k];
+    for (int e = lane; e < nz * nz; e += WAVE) Hs[e] = Hg[e];
+
+    const bool own = lane < nz, isx = lane < nxk, row = lane < nc;
+    const int j0 = isx ? lane : lane - nxk;
+    const int zl = own ? lane : 0, rl = row ? lane : 0;      /* clamped indices for masked reads */
+    const double inf = __builtin_inf(), eps64 = 64.0 * __DBL_EPSILON__;
+    double lo = -inf, hi = inf, h = 0.0, z = 0.0, dlo = -inf, dhi = inf;
+    if (own) {
+        const bool phantom = isx && k == 0 && lane < D.xpad;
+        if (!phantom) { lo = isx ? D.xmin[xo + j0] : D.umin[uo + j0]; hi = isx ? D.xmax[xo + j0] : D.umax[uo + j0]; }
+        h = hm[lane];
+    }
+    if (row) { dlo = Gn.dmin[ro + lane]; dhi = Gn.dmax[ro + lane]; }
+    /* the working set: fixed / sg (+1 on the lower bound, -1 on the upper one) per entry, inw / sr per row; nu_r is the multiplier
+     * of row r in  H z - hmod = G_W' nu + (multipliers of the fixed entries) */
+    bool fixed = own && lo == hi, inw = row && dlo == dhi;
+    double sg = 1.0, sr = 1.0, nur = 0.0;
+    if (fixed) z = lo;
+    u64 mb = __builtin_amdgcn_ballot_w64(fixed), mr = __builtin_amdgcn_ballot_w64(inw);
+    WSYNC();
+
+    /* L v = w and L' v = w, entry i of the vectors in lane i; the same with the factor of S (row space) */
+    auto fwdL = [&](double v) { for (int c = 0; c < nz; c++) { const double yc = rdlane(v, c) * dv[c]; if (lane == c) v = yc; else if (own && lane > c) v = fma(-Ls[lane + (size_t)c * nz], yc, v); } return v; };
+    auto bwdL = [&](double v) { for (int c = nz - 1; c >= 0; c--) { const double xc = rdlane(v, c) * dv[c]; if (lane == c) v = xc; else if (lane < c) v = fma(-Ls[c + (size_t)lane * nz], xc, v); } return v; };
+    auto solveS = [&](double v) {
+        for (int c = 0; c < nc; c++) { const double yc = rdlane(v, c) * sv[c]; if (lane == c) v = yc; else if (row && lane > c) v = fma(-Ss[lane + (size_t)c * nc], yc, v); }
+        for (int c = nc - 1; c >= 0; c--) { const double xc = rdlane(v, c) * sv[c]; if (lane == c) v = xc; else if (lane < c) v = fma(-Ss[c + (size_t)lane * nc], xc, v); }
+        return v;
+    };
+    /* (Y' a)_r in lane r for the rows of W, 0 elsewhere; (Y w)_i in lane i; (G_W' w)_i in lane i */
+    auto Yt = [&](double a) { double acc = 0.0; for (int i = 0; i < nz; i++) acc = fma(Ys[i + (size_t)rl * nz], rdlane(a, i), acc); return inw ? acc : 0.0; };
+    auto Yw = [&](double w) { double acc = 0.0; for (int r = 0; r < nc; r++) if ((mr >> r) & 1ull) acc = fma(Ys[zl + (size_t)r * nz], rdlane(w, r), acc); return own ? acc : 0.0; };
+    auto Gtw = [&](double w) { double acc = 0.0; for (int r = 0; r < nc; r++) if ((mr >> r) & 1ull) acc = fma(Gt[zl + (size_t)r * nz], rdlane(w, r), acc); return own ? acc : 0.0; };
+    auto Hv = [&](double v) { double acc = 0.0; for (int j = 0; j < nz; j++) acc = fma(Hs[zl + (size_t)j * nz], rdlane(v, j), acc); return own ? acc : 0.0; };
+    /* the minimiser on the working set (fixed entries of z stay): z and nu */
+    auto eqp = [&]() {
+        double r = h;
+        for (int j = 0; j < nz; j++) if ((mb >> j) & 1ull) r = fma(-Hs[zl + (size_t)j * nz], rdlane(z, j), r);
+        if (fixed || !own) r = fixed ? z : 0.0;
+        const double y0 = fwdL(r);
+        double c = 0.0;                                       /* G_W z0 - d_W */
+        for (int j = 0; j < nz; j++) if ((mb >> j) & 1ull) c = fma(Gt[j + (size_t)rl * nz], rdlane(z, j), c);
+        const double yt = Yt(y0);
+        c = inw ? c + yt - (sr > 0.0 ? dlo : dhi) : 0.0;
+        const double w = solveS(c);
+        const double zn = bwdL(y0 - Yw(w));
+        if (own && !fixed) z = zn;
+        nur = inw ? -w : 0.0;
+    };
+
+    bool ok = false;
+    int ptype = 0, pidx = 0;               /* the constraint being added: 0 none, 1 bound, 2 row; its side in psg, its multiplier in up */
+    double psg = 1.0, up = 0.0;
+    for (int step = 0; step < GEN_MAX_STEPS(nz, nc); step++) {
+        WSYNC();
+        /* M of the fixed set and its Cholesky factor, left looking, lane i = row i (as stage_box) */
+        for (int j = 0; j < nz; j++) {
+            const bool fj = (mb >> j) & 1ull;
+            if (own) Ls[lane + (size_t)j * nz] = (fixed || fj) ? (lane == j ? 1.0 : 0.0) : Hs[lane + (size_t)j * nz];
+        }
+        WSYNC();
+        bool pd = true;
+        for (int j = 0; j < nz; j++) {
+            if (own && lane >= j) {
+                double sacc = Ls[lane + (size_t)j * nz];
+                for (int c = 0; c < j; c++) sacc = fma(-Ls[lane + (size_t)c * nz], Ls[j + (size_t)c * nz], sacc);
+                Ls[lane + (size_t)j * nz] = sacc;
+            }
+            WSYNC();
+            const double cjj = Ls[j + (size_t)j * nz];
+            pd = pd && cjj > 0.0;
+            const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
+            if (own && lane >= j) Ls[lane + (size_t)j * nz] *= finv;
+            if (lane == 0) dv[j] = finv;
+            WSYNC();
+        }
+        if (!pd) break;                                        /* H_FF not positive definite */
+        /* Y and S of the rows in W, and the factor of S */
+        for (int r = 0; r < nc; r++) {
+            if (!((mr >> r) & 1ull)) continue;
+            const double y = fwdL(own && !fixed ? Gt[lane + (size_t)r * nz] : 0.0);
+            if (own) Ys[lane + (size_t)r * nz] = y;
+        }
+        WSYNC();
+        for (int j = 0; j < nc; j++) {
+            const bool wj = (mr >> j) & 1ull;
+            double acc = lane == j ? 1.0 : 0.0;
+            if (wj && inw) { acc = 0.0; for (int i = 0; i < nz; i++) acc = fma(Ys[i + (size_t)rl * nz], Ys[i + (size_t)j * nz], acc); }
+            else if (wj) acc = 0.0;
+            if (row) Ss[lane + (size_t)j * nc] = acc;
+        }
+        WSYNC();
+        for (int j = 0; j < nc; j++) {
+            const double sjj = Ss[j + (size_t)j * nc];
+            if (row && lane >= j) {
+                double sacc = Ss[lane + (size_t)j * nc];
+                for (int c = 0; c < j; c++) sacc = fma(-Ss[lane + (size_t)c * nc], Ss[j + (size_t)c * nc], sacc);
+                Ss[lane + (size_t)j * nc] = sacc;
+            }
+            WSYNC();
+            const double cjj = Ss[j + (size_t)j * nc];
+            pd = pd && cjj > eps64 * sjj;                      /* the rows of the working set depend on each other */
+            const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
+            if (row && lane >= j) Ss[lane + (size_t)j * nc] *= finv;
+            if (lane == 0) sv[j] = finv;
+            WSYNC();
+        }
+        if (!pd) break;
+        if (step == 0) eqp();
+        if (ptype == 0) {
+            /* the most violated constraint outside the working set */
+            double vb = 0.0, vr = 0.0, act = 0.0, aabs = 0.0;
+            if (own && !fixed) {
+                if (lo - z > eps64 * (fabs(z) + fabs(lo))) vb = lo - z;
+                if (z - hi > eps64 * (fabs(z) + fabs(hi))) vb = z - hi;
+            }
+            for (int j = 0; j < nz; j++) { const double t = Gt[j + (size_t)rl * nz] * rdlane(z, j); act += t; aabs += fabs(t); }
+            if (row && !inw) {
+                if (dlo - act > eps64 * (aabs + fabs(dlo))) vr = dlo - act;
+                if (act - dhi > eps64 * (aabs + fabs(dhi))) vr = act - dhi;
+            }
+            const double vmax = fmax(wmax(vb), wmax(vr));
+            if (!(vmax > 0.0)) { eqp(); ok = true; break; }
+            const u64 bb = __builtin_amdgcn_ballot_w64(vb == vmax), br = __builtin_amdgcn_ballot_w64(vr == vmax);
+            ptype = bb ? 1 : 2;
+            pidx = __builtin_amdgcn_readfirstlane(__builtin_ctzll(bb ? bb : br));
+            const double side = ptype == 1 ? (z < lo ? 1.0 : -1.0) : (act < dlo ? 1.0 : -1.0);
+            psg = rdlane(side, pidx);
+            up = 0.0;
+        }
+        /* n_p, its violation b_p - n_p'z > 0, the directions */
+        const double np = ptype == 1 ? (lane == pidx ? psg : 0.0) : (own ? psg * Gt[lane + (size_t)pidx * nz] : 0.0);
+        double viol;
+        if (ptype == 1) viol = rdlane(psg > 0.0 ? lo - z : z - hi, pidx);
+        else { const double act = wsum(own ? Gt[lane + (size_t)pidx * nz] * z : 0.0); viol = psg > 0.0 ? rdlane(dlo, pidx) - act : act - rdlane(dhi, pidx); }
+        const double a = fwdL(own && !fixed ? np : 0.0);
+        const double rr = solveS(Yt(a));
+        const double e = a - Yw(rr);
+        const double q = wsum(e * e), qd = wsum(a * a);
+        const bool dep = !(q > eps64 * qd);                    /* p depends on the working set: no primal step */
+        double dz = bwdL(e);
+        if (!own || fixed) dz = 0.0;
+        /* multipliers of the fixed entries and of the rows (u >= 0 with their sides) and the rates at which a step lowers them */
+        const double gtr = Gtw(rr), gtn = Gtw(nur);
+        const double om = Hv(z) - h - gtn - np * up;           /* fixed entries: sg * om is their multiplier */
+        const double rb = np - Hv(dz) - gtr;
+        const bool cb = fixed && lo < hi && sg * rb > 0.0, cr = inw && dlo < dhi && sr * rr > 0.0;
+        const double tb = cb ? fmax(sg * om, 0.0) / (sg * rb) : inf, tr = cr ? fmax(sr * nur, 0.0) / (sr * rr) : inf;
+        const double tbm = -wmax(-tb), trm = -wmax(-tr);
+        const double t1 = fmin(tbm, trm), t2 = dep ? inf : fmax(viol, 0.0) / q;
+        if (t1 == inf && t2 == inf) break;                     /* no step possible: the stage QP is infeasible */
+        const double t = fmin(t1, t2);
+        if (!dep && own && !fixed) z = fma(t, dz, z);
+        if (inw) nur = fma(-t, rr, nur);
+        up += t;
+        if (t2 <= t1) {
+            /* full step: p joins the working set */
+            if (ptype == 1) { if (lane == pidx) { z = psg > 0.0 ? lo : hi; fixed = true; sg = psg; } mb |= 1ull << pidx; }
+            else { if (lane == pidx) { inw = true; sr = psg; nur = psg * up; } mr |= 1ull << pidx; }
+            ptype = 0;
+        } else if (tbm <= trm) {
+            const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__builtin_amdgcn_ballot_w64(cb && tb == tbm)));
+            if (lane == i) fixed = false;
+            mb &= ~(1ull << i);
+        } else {
+            const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__builtin_amdgcn_ballot_w64(cr && tr == trm)));
+            if (lane == i) { inw = false; nur = 0.0; }
+            mr &= ~(1ull << i);
+        }
+    }
+    if (!ok && lane == 0) { D.ctrl->status = 4; D.ctrl->done = 1; }      /* TREEQP_DN_STAGE_QP_SOLVE_FAILED */
+    if (lane == 0) { D.bmask[k] = mb; Gn.rmask[k] = mr; }
+    if (row) Gn.mu[ro + lane] = inw ? -nur : 0.0;
+    if (own) {
+        if (isx) { if (save_s) D.xUncS[xo + j0] = D.xUnc[xo + j0]; D.x[xo + j0] = z; D.xUnc[xo + j0] = h; }
+        else { if (save_s) D.uUncS[uo + j0] = D.uUnc[uo + j0]; D.u[uo + j0] = z; D.uUnc[uo + j0] = h; }
+    }
+    /* dual term -1/2 z'Hz + hmod'z - cmod, as stage_box takes it */
+    const double hz = Hv(z);
+    double p_quad = own ? z * hz : 0.0, p_lin = own ? h * z : 0.0, p_cd = 0.0;
+    for (int t = lane; t < d; t += WAVE) p_cd = fma(D.b[ko + t], lk[t], p_cd);
+    p_quad = wave_sum(p_quad); p_lin = wave_sum(p_lin); p_cd = wave_sum(p_cd);
+    if (lane == 0) D.fval[k] = -0.5 * p_quad - p_cd + p_lin;
+    if (!ok || (mb == D.bmask[T.Nn + k] && mr == Gn.rmask[T.Nn + k])) return;
+    /* column j of P is the primal direction of n = e_j (the factors of the final working set are in LDS) */
+    double *P = D.Pd + D.poff[k];
+    for (int j = 0; j < nz; j++) {
+        double col = 0.0;
+        if (!((mb >> j) & 1ull)) {
+            const double a = fwdL(lane == j ? 1.0 : 0.0);
+            col = bwdL(a - Yw(solveS(Yt(a))));
+            if (!own || fixed) col = 0.0;
+        }
+        if (own) P[lane + (size_t)j * nz] = col;
+    }
+    if (lane == 0) { D.bmask[T.Nn + k] = mb; Gn.rmask[T.Nn + k] = mr; }
+}
+
+/* BOX: 0 no box nodes, 1 stage_box compiled in, 2 stage_box and stage_gen */
+template <int BOX = 0>
 __device__ void stage_body(const Tree &T, const Data &D, int mode, int k, int lane, double *lds, bool batch = true, u64 *xu = nullptr, int sum_nx = 0, unsigned xtag = 0u,
                            const double *Cl = nullptr, int ldcl = 0) {
     const Ctrl *c = D.ctrl;
@@ -533,6 +783,9 @@ __device__ void stage_body(const Tree &T, const Data &D, int mode, int k, int la
         WSYNC();
         if constexpr (BOX) {
             if (D.kind[k] == 2) { stage_box(T, D, k, lane, hm + nz, hm, lk, ko, save_s); return; }
+        }
+        if constexpr (BOX == 2) {
+            if (D.kind[k] == 3) { stage_gen(T, D, k, lane, hm + nz, hm, lk, ko, save_s); return; }
         }
         const double *P = D.Pd + D.poff[k], *H = D.Hd + D.poff[k];
         for (int t = lane; t < nz; t += WAVE) {
@@ -641,7 +894,13 @@ __global__ void __launch_bounds__(WAVE) k_stage(Tree T, Data D, int mode, int h,
 __global__ void __launch_bounds__(WAVE) k_stage_box(Tree T, Data D, int mode, int h, int t) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
-    stage_body<true>(T, D, mode, blockIdx.x, threadIdx.x, lds);
+    stage_body<1>(T, D, mode, blockIdx.x, threadIdx.x, lds);
+}
+/* k_stage for trees with kind-3 nodes: the same sweep with stage_gen compiled in as well (its LDS, s->lds_gen, only here) */
+__global__ void __launch_bounds__(WAVE) k_stage_gen(Tree T, Data D, int mode, int h, int t) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
+    stage_body<2>(T, D, mode, blockIdx.x, threadIdx.x, lds);
 }
 #endif
 
@@ -1544,7 +1803,18 @@ struct tqgpu_solver {
     bool dense = false, need_dense_init = false;   /* dense unconstrained stage solver selected (generic path only) */
     bool box = false;            /* some dense nodes have box bounds (kind 2): the stage sweep is k_stage_box with lds_box bytes */
     size_t lds_box = 0;
-    std::vector<int> h_kind;     /* the kinds last set (tqgpu_set_objective_mixed) */
+    bool gen = false;            /* some dense nodes have general constraints as well (kind 3): the stage sweep is k_stage_gen with lds_gen bytes */
+    size_t lds_gen = 0;
+    std::vector<int> h_kind;     /* the kinds last set (tqgpu_set_objective_mixed), as the device has them: a kind-3 node without rows is a kind-2 node */
+    std::vector<int> h_kind_req; /* ... as the caller gave them */
+    /* general constraints (tqgpu_set_constraints): rows per node, offsets, host copies of dmin | dmax, the device arrays and the record Data.gen points to */
+    std::vector<int> gnc, groff, ggoff;
+    std::vector<double> h_drange;
+    int sum_nc = 0;
+    int *d_gtab = nullptr;
+    double *d_Gt = nullptr, *d_drange = nullptr, *d_gmu = nullptr;
+    unsigned long long *d_rmask = nullptr;
+    Gen *d_gen = nullptr;
     std::vector<double> h_bounds; /* the bounds last set by tqgpu_set_bounds (device layout: xmin | xmax | umin | umax); empty: unknown */
     double *d_Hd = nullptr;      /* writable alias of Data.Hd */
     int *d_kind = nullptr;       /* writable alias of Data.kind */
@@ -2084,6 +2354,7 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
         if (!done && r == Route::THREE_LAUNCH) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
         if (!done) {
             if (r == Route::FUSED_TAILS) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
+            else if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, 1, it, t);
             else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, it, t);
             else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, it, t);
         }
@@ -2407,7 +2678,8 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
     if (!ls_begun) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
     if (fuse) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
     else {
-        if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, h, 1);
+        if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, 1, h, 1);
+        else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, h, 1);
         else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, h, 1);
         launches++;
         hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, h, 1, 0); launches++;
@@ -2449,6 +2721,27 @@ __global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, in
     const double *H = D.Hd + D.poff[k];
     double hz = 0.0;
     for (int j = 0; j < nz; j++) hz = fma(H[lane + (size_t)j * nz], j < nxk ? D.x[xo + j] : D.u[uo + j - nxk], hz);
+    const double h = isx ? (maxit ? D.xUncS : D.xUnc)[xo + j0] : (maxit ? D.uUncS : D.uUnc)[uo + j0];
+    const double mu = (maxit || ((D.bmask[k] >> lane) & 1ull)) ? h - hz : 0.0;
+    double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
+    if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
+}
+
+/* the same for the nodes with general constraints (kind 3): mu = hmod - H z - G' mu_d on the fixed entries, with the row multipliers
+ * stage_gen left in Gen::mu (the sign of tree_qp_out_calculate_KKT_res: Qx + q + ... + mu_x + C' mu_d = 0) */
+__global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    if (!D.dense || D.kind[k] != 3) return;
+    const Gen &Gn = *D.gen;
+    const int nxk = T.nx[k], nz = nxk + T.nu[k], xo = T.xoff[k], uo = T.uoff[k], nc = Gn.nc[k];
+    if (lane >= nz || (k == 0 && lane < x_pad)) return;
+    const bool maxit = D.ctrl->status == 1 && D.ctrl->iter > 0;
+    const bool isx = lane < nxk;
+    const int j0 = isx ? lane : lane - nxk;
+    const double *H = D.Hd + D.poff[k], *Gt = Gn.Gt + Gn.goff[k], *mud = Gn.mu + Gn.roff[k];
+    double hz = 0.0;
+    for (int j = 0; j < nz; j++) hz = fma(H[lane + (size_t)j * nz], j < nxk ? D.x[xo + j] : D.u[uo + j - nxk], hz);
+    for (int r = 0; r < nc; r++) hz = fma(Gt[lane + (size_t)r * nz], mud[r], hz);
     const double h = isx ? (maxit ? D.xUncS : D.xUnc)[xo + j0] : (maxit ? D.uUncS : D.uUnc)[uo + j0];
     const double mu = (maxit || ((D.bmask[k] >> lane) & 1ull)) ? h - hz : 0.0;
     double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
@@ -2837,7 +3130,7 @@ static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_mem
     if (uses_gpersist(s, batch_member) && p == 0 && m > 0) return Route::SINGLE_WG;
     if (tiered_capable(s) && p < 3) return Route::TIERED;
     if (s->w3_ok && !s->dense && p < 3 && !s->sharded) return Route::THREE_LAUNCH;
-    if (s->fuse_ok && p < 3 && !s->sharded && !s->box) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
+    if (s->fuse_ok && p < 3 && !s->sharded && !s->box && !s->gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
     return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
 /* the kernel variants the steps of tqgpu_create (setup_per_phase, setup_wide3, setup_persist, setup_single_wg) and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
@@ -2846,7 +3139,7 @@ extern "C" int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     const bool bits[] = {s->wide, s->wide_small, s->w3_ok, s->w3_sgp, s->w3_merge, s->d_anc != nullptr, s->fuse_ok, s->persist_ok,
                          s->persist_one, s->gpersist_ok, s->gp_in_lds, s->gp_const_in_lds, s->gp_tab_in_lds, s->gp_small16, s->gp_small8,
-                         s->dense, s->box, s->solve_no > 0 && s->route == Route::SINGLE_WG};
+                         s->dense, s->box, s->solve_no > 0 && s->route == Route::SINGLE_WG, s->gen};
     unsigned f = 0;
     for (unsigned i = 0; i < sizeof(bits) / sizeof(bits[0]); i++) f |= bits[i] ? 1u << i : 0u;
     if (flags) *flags = f;
@@ -2930,7 +3223,7 @@ extern "C" int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->need_init = true;
     s->need_pack = true;
-    if (s->dense) { s->dense = false; s->box = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; }
+    if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; }
     return TQGPU_OK;
 }
 
@@ -2950,15 +3243,41 @@ extern "C" int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const
 namespace {
 /* lb <= ub on every entry of every box node (the phantom root states are not the caller's) */
 int check_box_bounds(const tqgpu_solver *s) {
-    if (!s->box || s->h_bounds.empty()) return TQGPU_OK;
+    if (!(s->box || s->gen) || s->h_bounds.empty()) return TQGPU_OK;
     const double *xl = s->h_bounds.data(), *xu = xl + s->sum_nx, *ul = xu + s->sum_nx, *uu = ul + s->sum_nu;
     for (int k = 0; k < s->Nn; k++) {
-        if (s->h_kind[(size_t)k] != 2) continue;
+        if (s->h_kind[(size_t)k] < 2) continue;
         for (int i = (k == 0 ? s->x_pad : 0); i < s->nx[k]; i++)
             if (!(xl[s->xoff[k] + i] <= xu[s->xoff[k] + i])) return fail(TQGPU_EINVAL, "box node " + std::to_string(k) + ": xmin > xmax");
         for (int i = 0; i < s->nu[k]; i++)
             if (!(ul[s->uoff[k] + i] <= uu[s->uoff[k] + i])) return fail(TQGPU_EINVAL, "box node " + std::to_string(k) + ": umin > umax");
     }
+    return TQGPU_OK;
+}
+/* The kinds the caller asked for become the kinds of the device (a kind-3 node that has no rows is a kind-2 node), with the LDS of
+ * the sweeps that serve them.  On failure nothing has changed. */
+int apply_kinds(tqgpu_solver *s, const std::vector<int> &req) {
+    std::vector<int> kd = req;
+    size_t lds_box = 0, lds_gen = 0;
+    for (int k = 0; k < s->Nn; k++) {
+        if (kd[(size_t)k] < 2) continue;
+        const size_t nz = (size_t)s->nx[k] + s->nu[k], nc = s->gnc.empty() ? 0 : (size_t)s->gnc[(size_t)k];
+        if (nz > WAVE) return fail(TQGPU_EUNSUPPORTED, "box node " + std::to_string(k) + ": nx + nu = " + std::to_string(nz) + " > 64 (one wave, one entry per lane)");
+        if (kd[(size_t)k] == 3 && (nc == 0 || nz == 0)) kd[(size_t)k] = 2;
+        const size_t head = (size_t)s->bdim[k] + s->nx[k] + 2 * nz + 2;
+        if (kd[(size_t)k] == 2) lds_box = std::max(lds_box, (head + 2 * nz * nz) * sizeof(double));
+        else lds_gen = std::max(lds_gen, (head + nc + 2 * nz * nz + nz * nc + nc * nc) * sizeof(double));
+    }
+    const bool box_was = s->box, gen_was = s->gen;
+    const std::vector<int> kind_was = s->h_kind;
+    s->box = lds_box > 0; s->gen = lds_gen > 0; s->h_kind = kd;
+    int rc = check_box_bounds(s);
+    if (rc == TQGPU_OK && s->gen) rc = allow_lds(k_stage_gen, std::max(std::max(s->lds_stage, lds_box), lds_gen));
+    else if (rc == TQGPU_OK && s->box) rc = allow_lds(k_stage_box, std::max(s->lds_stage, lds_box));
+    if (rc != TQGPU_OK) { s->box = box_was; s->gen = gen_was; s->h_kind = kind_was; return rc; }
+    s->lds_box = std::max(s->lds_stage, lds_box);
+    s->lds_gen = std::max(s->lds_box, lds_gen);
+    s->h_kind_req = req;
     return TQGPU_OK;
 }
 }  // namespace
@@ -2973,10 +3292,10 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     std::vector<int> kd((size_t)s->Nn, 1);
     int rc0 = TQGPU_OK;
     if (kind) for (int k = 0; k < s->Nn; k++) {
-        if (kind[k] < 0 || kind[k] > 2) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: kind must be 0, 1 or 2");
+        if (kind[k] < 0 || kind[k] > 3) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: kind must be 0, 1, 2 or 3");
         kd[(size_t)k] = kind[k];
     }
-    size_t lds_box = 0, lds_dense = 0;
+    size_t lds_dense = 0;
     for (int k = 0; k < s->Nn; k++) {
         /* k_dense_init holds a dense node's H (nz x nz) and its pivots in LDS */
         const size_t nzd = (size_t)s->nx[k] + s->nu[k];
@@ -2984,21 +3303,8 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     }
     if (lds_dense > 160 * 1024) return fail(TQGPU_EUNSUPPORTED, "dense node too large for the LDS-resident factorization of H (160 KiB per workgroup)");
     if ((rc0 = allow_lds(k_dense_init, lds_dense))) return rc0;
-    for (int k = 0; k < s->Nn; k++) {
-        if (kd[(size_t)k] != 2) continue;
-        const size_t nz = (size_t)s->nx[k] + s->nu[k];
-        if (nz > WAVE) return fail(TQGPU_EUNSUPPORTED, "box node " + std::to_string(k) + ": nx + nu = " + std::to_string(nz) + " > 64 (one wave, one entry per lane)");
-        lds_box = std::max(lds_box, ((size_t)s->bdim[k] + s->nx[k] + 2 * nz + 2 * nz * nz + 2) * sizeof(double));
-    }
-    const bool box_was = s->box;
-    const std::vector<int> kind_was = s->h_kind;
-    s->box = lds_box > 0; s->h_kind = kd;
-    int rc = check_box_bounds(s);
-    if (rc == TQGPU_OK && s->box) {
-        s->lds_box = std::max(s->lds_stage, lds_box);
-        rc = allow_lds(k_stage_box, s->lds_box);
-    }
-    if (rc != TQGPU_OK) { s->box = box_was; s->h_kind = kind_was; return rc; }
+    const int rc = apply_kinds(s, kd);
+    if (rc != TQGPU_OK) return rc;
     size_t oq = 0, orr = 0, os = 0;
     for (int k = 0; k < s->Nn; k++) {
         const int nu = s->nu[k], nz = s->nx[k] + nu;
@@ -3031,7 +3337,7 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     }
     s->in_valid = false;
     H2D(s->d_Hd, H.data(), s->poff[s->Nn]);
-    HIP_TRY(hipMemcpyAsync(s->d_kind, kd.data(), sizeof(int) * (size_t)s->Nn, hipMemcpyHostToDevice, s->stream));      /* ints: not H2D (doubles) */
+    HIP_TRY(hipMemcpyAsync(s->d_kind, s->h_kind.data(), sizeof(int) * (size_t)s->Nn, hipMemcpyHostToDevice, s->stream));      /* ints: not H2D (doubles) */
     H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
     /* weights: zero on dense nodes (k_export_all writes zero multipliers for them; k_export_box those of the box nodes), the diagonals
      * on clipping nodes */
@@ -3064,6 +3370,95 @@ extern "C" int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const doubl
     return TQGPU_OK;
 }
 
+/* General constraints dmin <= C x + D u <= dmax of the nodes (the qpOASES QProblem of the reference, dual_Newton_tree_qpoases.c:226-300):
+ * nc rows per node, C (nc x nx) and D (nc x nu) column major, node after node.  nc != NULL (re)defines the rows: what is not given with it
+ * is zero (C, D) and unbounded (dmin, dmax).  They apply on the nodes of kind 3 (tqgpu_set_objective_mixed, before or after this call). */
+extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const double *C, const double *Dm, const double *dmin, const double *dmax) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    if (s->sharded || s->pshard) return fail(TQGPU_EINVAL, "general constraints are not available in sharded mode");
+    if (!nc && s->gnc.empty()) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: the rows per node (nc) have not been given yet");
+    HIP_TRY(hipSetDevice(s->device));
+    const int Nn = s->Nn;
+    if (nc) for (int k = 0; k < Nn; k++) {
+        if (nc[k] < 0) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: negative number of rows");
+        if (nc[k] > WAVE) return fail(TQGPU_EUNSUPPORTED, "node " + std::to_string(k) + ": nc = " + std::to_string(nc[k]) + " > 64 (one wave, one row per lane)");
+    }
+    /* dmin <= dmax, before anything changes */
+    const int total = nc ? std::accumulate(nc, nc + Nn, 0) : s->sum_nc;
+    std::vector<double> dr((size_t)2 * total);
+    for (int i = 0; i < total; i++) {
+        dr[(size_t)i] = dmin ? dmin[i] : (nc ? -__builtin_inf() : s->h_drange[(size_t)i]);
+        dr[(size_t)total + i] = dmax ? dmax[i] : (nc ? __builtin_inf() : s->h_drange[(size_t)s->sum_nc + i]);
+        if (!(dr[(size_t)i] <= dr[(size_t)total + i])) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: dmin > dmax in row " + std::to_string(i));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (nc) {
+        const std::vector<int> nc_was = s->gnc;
+        s->gnc.assign(nc, nc + Nn);
+        if (s->dense) { const int rck = apply_kinds(s, s->h_kind_req); if (rck != TQGPU_OK) { s->gnc = nc_was; return rck; } }
+        s->groff.assign((size_t)Nn + 1, 0); s->ggoff.assign((size_t)Nn + 1, 0);
+        for (int k = 0; k < Nn; k++) {
+            s->groff[(size_t)k + 1] = s->groff[(size_t)k] + nc[k];
+            s->ggoff[(size_t)k + 1] = s->ggoff[(size_t)k] + nc[k] * (s->nx[k] + s->nu[k]);
+        }
+        s->sum_nc = total;
+        s->mem.release(s->d_gtab); s->mem.release(s->d_Gt); s->mem.release(s->d_drange); s->mem.release(s->d_gmu); s->mem.release(s->d_rmask); s->mem.release(s->d_gen);
+        std::vector<int> tab(s->gnc);
+        tab.insert(tab.end(), s->groff.begin(), s->groff.end()); tab.insert(tab.end(), s->ggoff.begin(), s->ggoff.end());
+        int rc;
+        if ((rc = s->mem.upload(s->d_gtab, tab.data(), tab.size() * sizeof(int), TQGPU_ENOMEM, "the tables of the general constraints")) ||
+            (rc = s->mem.zeroed(s->d_Gt, sizeof(double) * (size_t)std::max(s->ggoff[(size_t)Nn], 1), TQGPU_ENOMEM, "the rows of the general constraints")) ||
+            (rc = s->mem.zeroed(s->d_drange, sizeof(double) * (size_t)std::max(2 * total, 1), TQGPU_ENOMEM, "the ranges of the general constraints")) ||
+            (rc = s->mem.zeroed(s->d_gmu, sizeof(double) * (size_t)std::max(total, 1), TQGPU_ENOMEM, "the multipliers of the general constraints")) ||
+            (rc = s->mem.zeroed(s->d_rmask, sizeof(unsigned long long) * 2 * (size_t)Nn, TQGPU_ENOMEM, "the working sets of the general constraints")))
+            return rc;
+        Gen g;
+        g.nc = s->d_gtab; g.roff = s->d_gtab + Nn; g.goff = s->d_gtab + 2 * Nn + 1;
+        g.Gt = s->d_Gt; g.dmin = s->d_drange; g.dmax = s->d_drange + total; g.mu = s->d_gmu; g.rmask = s->d_rmask;
+        if ((rc = s->mem.upload(s->d_gen, &g, sizeof(Gen), TQGPU_ENOMEM, "the record of the general constraints"))) return rc;
+        s->D.gen = s->d_gen;
+        if (s->dense) HIP_TRY(hipMemcpy(s->d_kind, s->h_kind.data(), sizeof(int) * (size_t)Nn, hipMemcpyHostToDevice));
+        s->need_dense_init = true;
+    }
+    if (C || Dm) {
+        /* rows of G = [C | D] (the phantom root states keep their zero columns); what is not given stays */
+        std::vector<double> Gt((size_t)std::max(s->ggoff[(size_t)Nn], 1), 0.0);
+        if (!(C && Dm)) HIP_TRY(hipMemcpy(Gt.data(), s->d_Gt, sizeof(double) * (size_t)s->ggoff[(size_t)Nn], hipMemcpyDeviceToHost));
+        size_t oc = 0, od = 0;
+        for (int k = 0; k < Nn; k++) {
+            const int pad = k == 0 ? s->x_pad : 0, nxc = s->nx[k] - pad, nu = s->nu[k], nz = s->nx[k] + nu, m = s->gnc[(size_t)k];
+            double *g = Gt.data() + s->ggoff[(size_t)k];
+            if (C) for (int j = 0; j < nxc; j++) for (int r = 0; r < m; r++) g[(size_t)r * nz + pad + j] = C[oc + r + (size_t)j * m];
+            if (Dm) for (int j = 0; j < nu; j++) for (int r = 0; r < m; r++) g[(size_t)r * nz + s->nx[k] + j] = Dm[od + r + (size_t)j * m];
+            oc += (size_t)m * nxc; od += (size_t)m * nu;
+        }
+        HIP_TRY(hipMemcpy(s->d_Gt, Gt.data(), sizeof(double) * (size_t)s->ggoff[(size_t)Nn], hipMemcpyHostToDevice));
+        s->need_dense_init = true;          /* the kept P_k were built with other rows */
+    }
+    if (total > 0 && (nc || dmin || dmax)) HIP_TRY(hipMemcpy(s->d_drange, dr.data(), sizeof(double) * 2 * (size_t)total, hipMemcpyHostToDevice));
+    s->h_drange.swap(dr);
+    s->export_valid = false;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_dims2(const tqgpu_solver *s, int *sum_nc) {
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    if (sum_nc) *sum_nc = s->sum_nc;
+    return TQGPU_OK;
+}
+
+/* the row multipliers of the last solve (sum_nc doubles, node after node): those of the final working sets of the kind-3 nodes, 0 elsewhere */
+extern "C" int tqgpu_get_mu_d(tqgpu_solver *s, double *mu_d) {
+    SETTLE(s);
+    if (!s || !mu_d) return fail(TQGPU_EINVAL, "tqgpu_get_mu_d: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->sum_nc > 0) HIP_TRY(hipMemcpy(mu_d, s->d_gmu, sizeof(double) * (size_t)s->sum_nc, hipMemcpyDeviceToHost));
+    if (!s->gen) std::fill(mu_d, mu_d + s->sum_nc, 0.0);
+    return TQGPU_OK;
+}
+
 extern "C" int tqgpu_set_lambda(tqgpu_solver *s, const double *lambda) {
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
@@ -3086,7 +3481,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
-    if (s->dense) { s->dense = false; s->box = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; s->in_valid = false; s->need_init = true; s->need_pack = true; }
+    if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; s->in_valid = false; s->need_init = true; s->need_pack = true; }
     if (xmin || xmax || umin || umax) s->h_bounds.clear();           /* (the checks of the box nodes' bounds see them through tqgpu_set_bounds only) */
     char *slab = static_cast<char *>(s->slab);
     bool any_pack = false, any_init = false;
@@ -3300,7 +3695,8 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         if (w3) { launch_sg(s, cx.O, 0, 0, 0, fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
         else if (cx.route == Route::FUSED_TAILS) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
         else {
-            if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 0, 0, 0);
+            if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, 0, 0, 0);
+            else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 0, 0, 0);
             else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 0, 0, 0);
             cx.launches++;
             hipLaunchKernelGGL(k_fval_init, dim3(1), dim3(256), 0, st, T, D); cx.launches++;
@@ -3518,6 +3914,7 @@ static int enqueue_export(tqgpu_solver *s, const double *lamc) {
     const int n = std::max(std::max(nxe, nue), std::max(nl, 1));
     hipLaunchKernelGGL(k_export_all, dim3((n + 255) / 256), dim3(256), 0, s->stream, nxe, nue, nl, s->x_pad, s->nx0, D, lamc, s->d_out);
     if (s->box) hipLaunchKernelGGL(k_export_box, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
+    if (s->gen) hipLaunchKernelGGL(k_export_gen, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
     HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, s->stream));
     return TQGPU_OK;
 }

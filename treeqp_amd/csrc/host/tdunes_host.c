@@ -112,6 +112,8 @@ static int staging_doubles(const tree_qp_in *qp_in)
         d += 4 * (size_t)qp_in->nx[k] + 4 * (size_t)qp_in->nu[k];
         /* dense stage solver: Q, R, S flattened */
         d += (size_t)(qp_in->nx[k] + qp_in->nu[k]) * (qp_in->nx[k] + qp_in->nu[k]);
+        /* general constraints: C, D, dmin, dmax gathered, mu_d on the way back */
+        d += (size_t)qp_in->nc[k] * (qp_in->nx[k] + qp_in->nu[k] + 3);
         if (k > 0) {
             const int p = qp_in->tree[k].dad;
             d += (size_t)qp_in->nx[k] * (qp_in->nx[p] + qp_in->nu[p] + 1);
@@ -154,17 +156,19 @@ static void require_clipping_applicable(const tree_qp_in *qp_in, int k)
 }
 
 /* The dense stage solvers of this build (the reference's TREEQP_QPOASES_SOLVER selector) cover stage QPs with box
- * bounds (qpOASES QProblemB in the reference, dual_Newton_tree_qpoases.c:312-358); general constraints (nc > 0,
- * qpOASES QProblem) are out of scope.  A node whose bounds are all infinite (|bound| >= TREEQP_INF, as written by
- * tree_qp_in_set_inf_bounds) takes the unconstrained dense solver (device kind 1), any other the box solver (kind 2). */
+ * bounds (qpOASES QProblemB in the reference, dual_Newton_tree_qpoases.c:312-358) and with general constraints (nc > 0,
+ * qpOASES QProblem, :226-300) up to 64 variables and 64 rows per node.  A node with rows takes the solver for general
+ * constraints (device kind 3); without rows, a node whose bounds are all infinite (|bound| >= TREEQP_INF, as written by
+ * tree_qp_in_set_inf_bounds) takes the unconstrained dense solver (kind 1), any other the box solver (kind 2). */
 static int is_inf_bound(double lo, double hi) { return lo <= -TREEQP_INF && hi >= TREEQP_INF; }
 static void require_dense_applicable(const tree_qp_in *qp_in, int k)
 {
-    if (qp_in->nc[k] > 0)
-        fatal("TREEQP_QPOASES_SOLVER with general constraints (nc > 0) is not available in the MI355X build (box bounds only).", NULL);
+    if (qp_in->nc[k] > 0 && (qp_in->nc[k] > 64 || qp_in->nx[k] + qp_in->nu[k] > 64))
+        fatal("TREEQP_QPOASES_SOLVER with general constraints (nc > 0) needs nx + nu <= 64 and nc <= 64 per node in the MI355X build.", NULL);
 }
 static int dense_kind(const tree_qp_in *qp_in, int k)
 {
+    if (qp_in->nc[k] > 0) return 3;
     for (int j = 0; j < qp_in->nx[k]; j++) if (!is_inf_bound(BLASFEO_DVECEL(&qp_in->xmin[k], j), BLASFEO_DVECEL(&qp_in->xmax[k], j))) return 2;
     for (int j = 0; j < qp_in->nu[k]; j++) if (!is_inf_bound(BLASFEO_DVECEL(&qp_in->umin[k], j), BLASFEO_DVECEL(&qp_in->umax[k], j))) return 2;
     return 1;
@@ -388,12 +392,23 @@ return_t treeqp_tdunes_solve(const tree_qp_in *qp_in, tree_qp_out *qp_out,
         double *Sf = stage; for (int k = 0; k < Nn; k++) for (int j = 0; j < qp_in->nx[k]; j++) for (int i = 0; i < qp_in->nu[k]; i++) *stage++ = BLASFEO_DMATEL(&qp_in->S[k], i, j);
         assert(stage <= work->stage + work->stage_doubles);
         int *kind = malloc(sizeof(int) * (size_t)Nn);
+        int n_rows = 0;
         for (int k = 0; k < Nn; k++) {
             kind[k] = 0;
             if (opts->qp_solver[k] == TREEQP_QPOASES_SOLVER) { require_dense_applicable(qp_in, k); kind[k] = dense_kind(qp_in, k); }
             else require_clipping_applicable(qp_in, k);
+            n_rows += qp_in->nc[k];
         }
         DEV_CALL(tqgpu_set_bounds(work->device, xmin, xmax, umin, umax));
+        if (n_rows > 0) {
+            /* general constraints: C, D flat per node (column major), dmin, dmax; they go out before the kinds that use them */
+            const double *Cf = flat_of_mats(qp_in->C, Nn, &stage);
+            const double *Df = flat_of_mats(qp_in->D, Nn, &stage);
+            const double *dlo = flat_of_vecs(qp_in->dmin, Nn, &stage);
+            const double *dhi = flat_of_vecs(qp_in->dmax, Nn, &stage);
+            assert(stage <= work->stage + work->stage_doubles);
+            DEV_CALL(tqgpu_set_constraints(work->device, qp_in->nc, Cf, Df, dlo, dhi));
+        }
         int rc_obj = tqgpu_set_objective_mixed(work->device, kind, Qf, Rf, Sf, q, r);
         free(kind);
         if (rc_obj != TQGPU_OK) fatal("device call failed in treeqp_tdunes_solve", tqgpu_last_error());
@@ -455,6 +470,11 @@ return_t treeqp_tdunes_solve(const tree_qp_in *qp_in, tree_qp_out *qp_out,
     if (ol) { if (sum_lam) memcpy(ol, wl, sizeof(double) * (size_t)sum_lam); } else scatter(wl, qp_out->lam, Nn - 1, NULL);
     if (!omx) scatter(tmp_mx, qp_out->mu_x, Nn, qp_in->nx);
     if (!omu) scatter(tmp_mu, qp_out->mu_u, Nn, qp_in->nu);
+    if (work->denseStageSolver && total_number_of_general_constraints(qp_in) > 0) {
+        double *tmp_md = work->stage + sum_nx + sum_nu;
+        DEV_CALL(tqgpu_get_mu_d(work->device, tmp_md));
+        scatter(tmp_md, qp_out->mu_d, Nn, qp_in->nc);
+    }
 
     qp_out->info.iter = res.iter;
     qp_out->info.solver_time = solver_time;
