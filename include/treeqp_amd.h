@@ -110,6 +110,21 @@ int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const double *xmax, co
 int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const double *C, const double *D, const double *dmin, const double *dmax);
 int tqgpu_get_mu_d(tqgpu_solver *s, double *mu_d);
 int tqgpu_dims2(const tqgpu_solver *s, int *sum_nc);
+/* The hot start of the kind-3 stage solver (default on, per mirror).  On: a stage solve starts from the working set (bounds, rows and
+ * their sides) its node ended the last stage solve with, across sweeps and solves: the set is checked against the current data,
+ * members with a multiplier of the wrong sign leave, and the dual active-set method goes on from there; a start that does not lead
+ * to a solution is followed by one cold solve, so that only a cold solve's failure gives status 4.  Where the solution is strictly
+ * complementary the result is that of the cold start bit for bit (it is a function of the final working set alone).  Off: every
+ * stage solve starts at the minimiser over the equalities.  The call empties the stored sets of every kind-3 node; so does any
+ * tqgpu_set_objective* (H, and with it q, r: there is no call for the linear terms alone) and a tqgpu_set_constraints that passes nc
+ * (the rows are redefined), C or D, while bounds, dmin / dmax alone, duals and x0 keep them.  treeqp_tdunes_solve sends all of these
+ * at every solve, so through the drop-in layer the hot start acts from sweep to sweep within a solve only.
+ * TQGPU_EINVAL on a null solver; without kind-3 nodes the setting is kept for later and nothing else happens. */
+int tqgpu_set_gen_hot_start(tqgpu_solver *s, int on);
+/* Active-set steps of the kind-3 stage solver per node, last[Nn] and total[Nn] (either may be NULL): one step is one pass of its loop,
+ * with one factorisation of S (the dual-feasibility rounds of a hot start and a cold redo count).  last: in the last stage sweep;
+ * total: summed over the sweeps of the last tqgpu_solve (zeroed when a solve starts).  0 on nodes of other kinds. */
+int tqgpu_get_stage_steps(tqgpu_solver *s, int *last, long *total);
 /* Everything above in one call (NULL = leave alone) plus the starting duals: compared with a pinned host mirror of
  * what the device holds, only what changed is uploaded, without synchronisation.  This is what the drop-in
  * treeqp_tdunes_solve uses, which -- like the reference, dual_Newton_tree.c:1142-1160 -- re-reads qp_in at every solve. */

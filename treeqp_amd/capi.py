@@ -593,6 +593,17 @@ class TqGpu:
         self.sum_nc = v.value
         return self
 
+    def set_gen_hot_start(self, on: bool):
+        """the kind-3 stage solver starts from the working set of its node's last stage solve (default) or cold; empties the stored sets"""
+        self._chk(lib().tqgpu_set_gen_hot_start(self.h, int(bool(on))))
+        return self
+
+    def stage_steps(self) -> dict:
+        """active-set steps of the kind-3 stage solver per node: last (the last stage sweep), total (summed over the last solve)"""
+        last, total = np.zeros(len(self.nk), dtype=np.int32), np.zeros(len(self.nk), dtype=np.int64)
+        self._chk(lib().tqgpu_get_stage_steps(self.h, _ip(last), total.ctypes.data_as(C.POINTER(C.c_long))))
+        return dict(last=last, total=total)
+
     def set_lambda(self, lam):
         a = None if lam is None else _f64(lam)
         if a is not None:

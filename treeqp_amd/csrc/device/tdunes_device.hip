@@ -137,6 +137,12 @@ struct Gen {
     const double *dmin, *dmax;
     double *mu;               /* row multipliers of the last stage solve, with the sign of qp_out->mu_d; 0 off the working set */
     unsigned long long *rmask;   /* [0, Nn) rows in the final working set of node k; [Nn, 2 Nn) the rows P_k was last built for */
+    /* the hot start of stage_gen: with bmask[k] and rmask[k] the sides of the final working set (bit set = upper side), [0, Nn) of the
+     * bounds, [Nn, 2 Nn) of the rows; hot = 0: every stage solve starts cold (tqgpu_set_gen_hot_start) */
+    unsigned long long *sides;
+    int hot;
+    int *steps_last;             /* [Nn] active-set steps of node k in the last stage sweep, [Nn] their sum over the last solve (tqgpu_get_stage_steps) */
+    long *steps_total;
 };
 
 struct Opts {
@@ -265,7 +271,10 @@ __global__ void __launch_bounds__(WAVE) k_dense_init(Tree T, Data D) {
     const int nz = T.nx[k] + T.nu[k];
     if (nz == 0 || !D.kind[k]) return;
     if (D.kind[k] >= 2 && lane == 0) D.bmask[T.Nn + k] = 0ull;      /* box nodes: P below is the one of the empty working set */
-    if (D.kind[k] == 3 && lane == 0) D.gen->rmask[T.Nn + k] = 0ull;
+    if (D.kind[k] == 3 && lane == 0) {                              /* and stage_gen starts cold after an upload of H or of C, D */
+        D.gen->rmask[T.Nn + k] = 0ull;
+        D.bmask[k] = 0ull; D.gen->rmask[k] = 0ull; D.gen->sides[k] = 0ull; D.gen->sides[T.Nn + k] = 0ull;
+    }
     const double *H = D.Hd + D.poff[k];
     double *P = D.Pd + D.poff[k];
     double *Lm = lds;                      /* nz x nz, ld = nz */
@@ -506,17 +515,31 @@ __device__ void stage_box(const Tree &T, const Data &D, int k, int lane, double 
 /* replaced by those of the identity, so fixed entries stay exactly on their bound) and a set  */
 /* of rows W; Y = L^-1 G_W' on the free entries (L the factor of M) and S = Y'Y, with the rows */
 /* and columns of the rows outside W replaced by those of the identity, are rebuilt and        */
-/* factorised at every step.  The method starts at the minimiser over the equalities (entries  */
-/* with lb == ub, rows with dmin == dmax) and needs no feasible point.  Per step: the most     */
-/* violated constraint p (lowest index on ties, bounds before rows), the primal direction      */
-/* dz = P n_p and the dual direction r, the step min(t_dual, t_full); a partial step drops the */
-/* blocking member and keeps p, a full step adds p.  n_p'P n_p <= 64 eps n_p'M^-1 n_p means p   */
-/* depends on the working set: only the dual step is taken.  No step at all: the stage QP is   */
-/* infeasible (status 4, as a non-positive pivot and the step cap).  Every decision is a       */
-/* wave-uniform ballot.  The returned z and row multipliers are the solution of the final      */
-/* working set's system alone, not of the path; every stage solve starts cold, so a repeated   */
-/* solve is bit-identical.  P = M^-1 - M^-1 G_W' S^-1 G_W M^-1 (fixed rows and columns zero)   */
-/* is rebuilt only when either mask differs from the one it was built for.                     */
+/* factorised at every step; M and L only when the set of fixed entries differs from the one L */
+/* was built for.  The method needs no feasible point.  Per step: the most violated constraint */
+/* p (lowest index on ties, bounds before rows), the primal direction dz = P n_p and the dual   */
+/* direction r, the step min(t_dual, t_full); a partial step drops the blocking member and     */
+/* keeps p, a full step adds p.  n_p'P n_p <= 64 eps n_p'M^-1 n_p means p depends on the        */
+/* working set: only the dual step is taken.  Every decision is a wave-uniform ballot.         */
+/* Start.  Cold (Gen::hot == 0): the minimiser over the equalities (entries with lb == ub,     */
+/* rows with dmin == dmax).  Hot (the default): the working set and sides the node's last      */
+/* stage solve ended with (bmask[k], rmask[k], Gen::sides, kept across sweeps and solves),     */
+/* made safe against the current data -- lanes beyond nz / nc and members whose bound on the   */
+/* stored side is infinite leave, equalities come in -- then dual-feasibility rounds: the      */
+/* minimiser on the set, and every member that is no equality and whose multiplier (sg om for  */
+/* a bound, sr nu_r for a row) is negative beyond 64 eps (sum of |terms|) leaves, all of them  */
+/* in one round, until none does (the set only shrinks).  What remains -- z minimises on W,    */
+/* multipliers >= 0, W independent -- is a state of the loop above, which goes on from there.  */
+/* A hot pass that ends in any other way than with a solution (a non-positive pivot of M or S  */
+/* on the stored set, i.e. a dependent one; the step cap of 4 (nz + nc) + 8, which the rounds  */
+/* count against; no step possible) is followed by one cold pass, exactly the cold solve; only */
+/* its failure is status 4 (an infeasible stage QP still ends there).  The returned z and row  */
+/* multipliers are the solution of the final working set's system alone, not of the path: hot  */
+/* and cold solves that end on the same set and sides (they do where the solution is strictly  */
+/* complementary) agree bit for bit, and so do repeated solves.  k_dense_init empties the      */
+/* stored set when H or C, D are uploaded.  P = M^-1 - M^-1 G_W' S^-1 G_W M^-1 (fixed rows and */
+/* columns zero) is rebuilt only when either mask differs from the one it was built for.       */
+/* Gen::steps_last / steps_total count the passes of the loop (one factorisation of S each).   */
 /* ------------------------------------------------------------------------------------------ */
 #define GEN_MAX_STEPS(nz, nc) (4 * ((nz) + (nc)) + 8)
 __device__ void stage_gen(const Tree &T, const Data &D, int k, int lane, double *lds, const double *hm, const double *lk, int ko, bool save_s) {
@@ -546,10 +569,9 @@ __device__ void stage_gen(const Tree &T, const Data &D, int k, int lane, double 
     if (row) { dlo = Gn.dmin[ro + lane]; dhi = Gn.dmax[ro + lane]; }
     /* the working set: fixed / sg (+1 on the lower bound, -1 on the upper one) per entry, inw / sr per row; nu_r is the multiplier
      * of row r in  H z - hmod = G_W' nu + (multipliers of the fixed entries) */
-    bool fixed = own && lo == hi, inw = row && dlo == dhi;
+    bool fixed = false, inw = false;
     double sg = 1.0, sr = 1.0, nur = 0.0;
-    if (fixed) z = lo;
-    u64 mb = __builtin_amdgcn_ballot_w64(fixed), mr = __builtin_amdgcn_ballot_w64(inw);
+    u64 mb = 0ull, mr = 0ull;
     WSYNC();
 
     /* L v = w and L' v = w, entry i of the vectors in lane i; the same with the factor of S (row space) */
@@ -582,127 +604,175 @@ __device__ void stage_gen(const Tree &T, const Data &D, int k, int lane, double 
     };
 
     bool ok = false;
-    int ptype = 0, pidx = 0;               /* the constraint being added: 0 none, 1 bound, 2 row; its side in psg, its multiplier in up */
-    double psg = 1.0, up = 0.0;
-    for (int step = 0; step < GEN_MAX_STEPS(nz, nc); step++) {
-        WSYNC();
-        /* M of the fixed set and its Cholesky factor, left looking, lane i = row i (as stage_box) */
-        for (int j = 0; j < nz; j++) {
-            const bool fj = (mb >> j) & 1ull;
-            if (own) Ls[lane + (size_t)j * nz] = (fixed || fj) ? (lane == j ? 1.0 : 0.0) : Hs[lane + (size_t)j * nz];
+    int steps = 0;                         /* active-set steps of this stage solve, every pass (tqgpu_get_stage_steps) */
+    u64 lmb = 0ull;                        /* the fixed set the factor in Ls was built for (lhave: there is one) */
+    bool lhave = false;
+    /* pass 0: from the stored working set (hot start on); pass 1: cold, from the equalities -- the only pass with the hot start off, and the
+     * redo of a pass 0 that did not end with ok */
+    for (int pass = Gn.hot ? 0 : 1; pass < 2 && !ok; pass++) {
+        bool dfr = pass == 0;                  /* dual-feasibility rounds of the stored set still to do */
+        {
+            /* the stored set against the current data: lanes beyond nz / nc and members whose bound on the stored side is infinite drop out */
+            bool kb = false, kr = false, ub = false, ur = false;
+            if (dfr) {
+                ub = (Gn.sides[k] >> lane) & 1ull; ur = (Gn.sides[T.Nn + k] >> lane) & 1ull;
+                kb = own && ((D.bmask[k] >> lane) & 1ull) && (ub ? hi < inf : lo > -inf);
+                kr = row && ((Gn.rmask[k] >> lane) & 1ull) && (ur ? dhi < inf : dlo > -inf);
+            }
+            fixed = own && (lo == hi || kb); inw = row && (dlo == dhi || kr);
+            sg = (fixed && lo < hi && ub) ? -1.0 : 1.0; sr = (inw && dlo < dhi && ur) ? -1.0 : 1.0;
+            nur = 0.0;
+            z = fixed ? (sg > 0.0 ? lo : hi) : 0.0;
+            mb = __builtin_amdgcn_ballot_w64(fixed); mr = __builtin_amdgcn_ballot_w64(inw);
         }
-        WSYNC();
-        bool pd = true;
-        for (int j = 0; j < nz; j++) {
-            if (own && lane >= j) {
-                double sacc = Ls[lane + (size_t)j * nz];
-                for (int c = 0; c < j; c++) sacc = fma(-Ls[lane + (size_t)c * nz], Ls[j + (size_t)c * nz], sacc);
-                Ls[lane + (size_t)j * nz] = sacc;
+        int ptype = 0, pidx = 0;               /* the constraint being added: 0 none, 1 bound, 2 row; its side in psg, its multiplier in up */
+        double psg = 1.0, up = 0.0;
+        for (int step = 0; step < GEN_MAX_STEPS(nz, nc); step++) {
+            steps++;
+            WSYNC();
+            bool pd = true;
+            if (!lhave || mb != lmb) {
+                /* M of the fixed set and its Cholesky factor, left looking, lane i = row i (as stage_box); kept while the fixed set stays */
+                lhave = false;
+                for (int j = 0; j < nz; j++) {
+                    const bool fj = (mb >> j) & 1ull;
+                    if (own) Ls[lane + (size_t)j * nz] = (fixed || fj) ? (lane == j ? 1.0 : 0.0) : Hs[lane + (size_t)j * nz];
+                }
+                WSYNC();
+                for (int j = 0; j < nz; j++) {
+                    if (own && lane >= j) {
+                        double sacc = Ls[lane + (size_t)j * nz];
+                        for (int c = 0; c < j; c++) sacc = fma(-Ls[lane + (size_t)c * nz], Ls[j + (size_t)c * nz], sacc);
+                        Ls[lane + (size_t)j * nz] = sacc;
+                    }
+                    WSYNC();
+                    const double cjj = Ls[j + (size_t)j * nz];
+                    pd = pd && cjj > 0.0;
+                    const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
+                    if (own && lane >= j) Ls[lane + (size_t)j * nz] *= finv;
+                    if (lane == 0) dv[j] = finv;
+                    WSYNC();
+                }
+                lhave = pd; lmb = mb;
+            }
+            if (!pd) break;                                        /* H_FF not positive definite */
+            /* Y and S of the rows in W, and the factor of S */
+            for (int r = 0; r < nc; r++) {
+                if (!((mr >> r) & 1ull)) continue;
+                const double y = fwdL(own && !fixed ? Gt[lane + (size_t)r * nz] : 0.0);
+                if (own) Ys[lane + (size_t)r * nz] = y;
             }
             WSYNC();
-            const double cjj = Ls[j + (size_t)j * nz];
-            pd = pd && cjj > 0.0;
-            const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
-            if (own && lane >= j) Ls[lane + (size_t)j * nz] *= finv;
-            if (lane == 0) dv[j] = finv;
-            WSYNC();
-        }
-        if (!pd) break;                                        /* H_FF not positive definite */
-        /* Y and S of the rows in W, and the factor of S */
-        for (int r = 0; r < nc; r++) {
-            if (!((mr >> r) & 1ull)) continue;
-            const double y = fwdL(own && !fixed ? Gt[lane + (size_t)r * nz] : 0.0);
-            if (own) Ys[lane + (size_t)r * nz] = y;
-        }
-        WSYNC();
-        for (int j = 0; j < nc; j++) {
-            const bool wj = (mr >> j) & 1ull;
-            double acc = lane == j ? 1.0 : 0.0;
-            if (wj && inw) { acc = 0.0; for (int i = 0; i < nz; i++) acc = fma(Ys[i + (size_t)rl * nz], Ys[i + (size_t)j * nz], acc); }
-            else if (wj) acc = 0.0;
-            if (row) Ss[lane + (size_t)j * nc] = acc;
-        }
-        WSYNC();
-        for (int j = 0; j < nc; j++) {
-            const double sjj = Ss[j + (size_t)j * nc];
-            if (row && lane >= j) {
-                double sacc = Ss[lane + (size_t)j * nc];
-                for (int c = 0; c < j; c++) sacc = fma(-Ss[lane + (size_t)c * nc], Ss[j + (size_t)c * nc], sacc);
-                Ss[lane + (size_t)j * nc] = sacc;
+            for (int j = 0; j < nc; j++) {
+                const bool wj = (mr >> j) & 1ull;
+                double acc = lane == j ? 1.0 : 0.0;
+                if (wj && inw) { acc = 0.0; for (int i = 0; i < nz; i++) acc = fma(Ys[i + (size_t)rl * nz], Ys[i + (size_t)j * nz], acc); }
+                else if (wj) acc = 0.0;
+                if (row) Ss[lane + (size_t)j * nc] = acc;
             }
             WSYNC();
-            const double cjj = Ss[j + (size_t)j * nc];
-            pd = pd && cjj > eps64 * sjj;                      /* the rows of the working set depend on each other */
-            const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
-            if (row && lane >= j) Ss[lane + (size_t)j * nc] *= finv;
-            if (lane == 0) sv[j] = finv;
-            WSYNC();
-        }
-        if (!pd) break;
-        if (step == 0) eqp();
-        if (ptype == 0) {
-            /* the most violated constraint outside the working set */
-            double vb = 0.0, vr = 0.0, act = 0.0, aabs = 0.0;
-            if (own && !fixed) {
-                if (lo - z > eps64 * (fabs(z) + fabs(lo))) vb = lo - z;
-                if (z - hi > eps64 * (fabs(z) + fabs(hi))) vb = z - hi;
+            for (int j = 0; j < nc; j++) {
+                const double sjj = Ss[j + (size_t)j * nc];
+                if (row && lane >= j) {
+                    double sacc = Ss[lane + (size_t)j * nc];
+                    for (int c = 0; c < j; c++) sacc = fma(-Ss[lane + (size_t)c * nc], Ss[j + (size_t)c * nc], sacc);
+                    Ss[lane + (size_t)j * nc] = sacc;
+                }
+                WSYNC();
+                const double cjj = Ss[j + (size_t)j * nc];
+                pd = pd && cjj > eps64 * sjj;                      /* the rows of the working set depend on each other */
+                const double finv = cjj > 0.0 ? 1.0 / sqrt(cjj) : 0.0;
+                if (row && lane >= j) Ss[lane + (size_t)j * nc] *= finv;
+                if (lane == 0) sv[j] = finv;
+                WSYNC();
             }
-            for (int j = 0; j < nz; j++) { const double t = Gt[j + (size_t)rl * nz] * rdlane(z, j); act += t; aabs += fabs(t); }
-            if (row && !inw) {
-                if (dlo - act > eps64 * (aabs + fabs(dlo))) vr = dlo - act;
-                if (act - dhi > eps64 * (aabs + fabs(dhi))) vr = act - dhi;
+            if (!pd) break;
+            if (dfr) {
+                /* the minimiser on the stored set and the multipliers of its members that are no equalities, sg om and sr nu_r: every member whose
+                 * multiplier is negative beyond 64 eps (sum of |terms|) leaves, all of them in one round; the set only shrinks */
+                eqp();
+                double om = -h, oa = fabs(h);
+                for (int j = 0; j < nz; j++) { const double t = Hs[zl + (size_t)j * nz] * rdlane(z, j); om += t; oa += fabs(t); }
+                for (int r = 0; r < nc; r++) if ((mr >> r) & 1ull) { const double t = Gt[zl + (size_t)r * nz] * rdlane(nur, r); om -= t; oa += fabs(t); }
+                const double na = wsum(fabs(nur));
+                const bool wrongb = fixed && lo < hi && sg * om < -eps64 * oa, wrongr = inw && dlo < dhi && sr * nur < -eps64 * na;
+                const u64 wb = __builtin_amdgcn_ballot_w64(wrongb), wr = __builtin_amdgcn_ballot_w64(wrongr);
+                if (wb | wr) {
+                    if (wrongb) fixed = false;
+                    if (wrongr) { inw = false; nur = 0.0; }
+                    mb &= ~wb; mr &= ~wr;
+                    continue;
+                }
+                dfr = false;                                       /* z minimises on W, the multipliers are >= 0: the loop below goes on from here */
+            } else if (step == 0) eqp();
+            if (ptype == 0) {
+                /* the most violated constraint outside the working set */
+                double vb = 0.0, vr = 0.0, act = 0.0, aabs = 0.0;
+                if (own && !fixed) {
+                    if (lo - z > eps64 * (fabs(z) + fabs(lo))) vb = lo - z;
+                    if (z - hi > eps64 * (fabs(z) + fabs(hi))) vb = z - hi;
+                }
+                for (int j = 0; j < nz; j++) { const double t = Gt[j + (size_t)rl * nz] * rdlane(z, j); act += t; aabs += fabs(t); }
+                if (row && !inw) {
+                    if (dlo - act > eps64 * (aabs + fabs(dlo))) vr = dlo - act;
+                    if (act - dhi > eps64 * (aabs + fabs(dhi))) vr = act - dhi;
+                }
+                const double vmax = fmax(wmax(vb), wmax(vr));
+                if (!(vmax > 0.0)) { eqp(); ok = true; break; }
+                const u64 bb = __builtin_amdgcn_ballot_w64(vb == vmax), br = __builtin_amdgcn_ballot_w64(vr == vmax);
+                ptype = bb ? 1 : 2;
+                pidx = __builtin_amdgcn_readfirstlane(__builtin_ctzll(bb ? bb : br));
+                const double side = ptype == 1 ? (z < lo ? 1.0 : -1.0) : (act < dlo ? 1.0 : -1.0);
+                psg = rdlane(side, pidx);
+                up = 0.0;
             }
-            const double vmax = fmax(wmax(vb), wmax(vr));
-            if (!(vmax > 0.0)) { eqp(); ok = true; break; }
-            const u64 bb = __builtin_amdgcn_ballot_w64(vb == vmax), br = __builtin_amdgcn_ballot_w64(vr == vmax);
-            ptype = bb ? 1 : 2;
-            pidx = __builtin_amdgcn_readfirstlane(__builtin_ctzll(bb ? bb : br));
-            const double side = ptype == 1 ? (z < lo ? 1.0 : -1.0) : (act < dlo ? 1.0 : -1.0);
-            psg = rdlane(side, pidx);
-            up = 0.0;
-        }
-        /* n_p, its violation b_p - n_p'z > 0, the directions */
-        const double np = ptype == 1 ? (lane == pidx ? psg : 0.0) : (own ? psg * Gt[lane + (size_t)pidx * nz] : 0.0);
-        double viol;
-        if (ptype == 1) viol = rdlane(psg > 0.0 ? lo - z : z - hi, pidx);
-        else { const double act = wsum(own ? Gt[lane + (size_t)pidx * nz] * z : 0.0); viol = psg > 0.0 ? rdlane(dlo, pidx) - act : act - rdlane(dhi, pidx); }
-        const double a = fwdL(own && !fixed ? np : 0.0);
-        const double rr = solveS(Yt(a));
-        const double e = a - Yw(rr);
-        const double q = wsum(e * e), qd = wsum(a * a);
-        const bool dep = !(q > eps64 * qd);                    /* p depends on the working set: no primal step */
-        double dz = bwdL(e);
-        if (!own || fixed) dz = 0.0;
-        /* multipliers of the fixed entries and of the rows (u >= 0 with their sides) and the rates at which a step lowers them */
-        const double gtr = Gtw(rr), gtn = Gtw(nur);
-        const double om = Hv(z) - h - gtn - np * up;           /* fixed entries: sg * om is their multiplier */
-        const double rb = np - Hv(dz) - gtr;
-        const bool cb = fixed && lo < hi && sg * rb > 0.0, cr = inw && dlo < dhi && sr * rr > 0.0;
-        const double tb = cb ? fmax(sg * om, 0.0) / (sg * rb) : inf, tr = cr ? fmax(sr * nur, 0.0) / (sr * rr) : inf;
-        const double tbm = -wmax(-tb), trm = -wmax(-tr);
-        const double t1 = fmin(tbm, trm), t2 = dep ? inf : fmax(viol, 0.0) / q;
-        if (t1 == inf && t2 == inf) break;                     /* no step possible: the stage QP is infeasible */
-        const double t = fmin(t1, t2);
-        if (!dep && own && !fixed) z = fma(t, dz, z);
-        if (inw) nur = fma(-t, rr, nur);
-        up += t;
-        if (t2 <= t1) {
-            /* full step: p joins the working set */
-            if (ptype == 1) { if (lane == pidx) { z = psg > 0.0 ? lo : hi; fixed = true; sg = psg; } mb |= 1ull << pidx; }
-            else { if (lane == pidx) { inw = true; sr = psg; nur = psg * up; } mr |= 1ull << pidx; }
-            ptype = 0;
-        } else if (tbm <= trm) {
-            const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__builtin_amdgcn_ballot_w64(cb && tb == tbm)));
-            if (lane == i) fixed = false;
-            mb &= ~(1ull << i);
-        } else {
-            const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__builtin_amdgcn_ballot_w64(cr && tr == trm)));
-            if (lane == i) { inw = false; nur = 0.0; }
-            mr &= ~(1ull << i);
+            /* n_p, its violation b_p - n_p'z > 0, the directions */
+            const double np = ptype == 1 ? (lane == pidx ? psg : 0.0) : (own ? psg * Gt[lane + (size_t)pidx * nz] : 0.0);
+            double viol;
+            if (ptype == 1) viol = rdlane(psg > 0.0 ? lo - z : z - hi, pidx);
+            else { const double act = wsum(own ? Gt[lane + (size_t)pidx * nz] * z : 0.0); viol = psg > 0.0 ? rdlane(dlo, pidx) - act : act - rdlane(dhi, pidx); }
+            const double a = fwdL(own && !fixed ? np : 0.0);
+            const double rr = solveS(Yt(a));
+            const double e = a - Yw(rr);
+            const double q = wsum(e * e), qd = wsum(a * a);
+            const bool dep = !(q > eps64 * qd);                    /* p depends on the working set: no primal step */
+            double dz = bwdL(e);
+            if (!own || fixed) dz = 0.0;
+            /* multipliers of the fixed entries and of the rows (u >= 0 with their sides) and the rates at which a step lowers them */
+            const double gtr = Gtw(rr), gtn = Gtw(nur);
+            const double om = Hv(z) - h - gtn - np * up;           /* fixed entries: sg * om is their multiplier */
+            const double rb = np - Hv(dz) - gtr;
+            const bool cb = fixed && lo < hi && sg * rb > 0.0, cr = inw && dlo < dhi && sr * rr > 0.0;
+            const double tb = cb ? fmax(sg * om, 0.0) / (sg * rb) : inf, tr = cr ? fmax(sr * nur, 0.0) / (sr * rr) : inf;
+            const double tbm = -wmax(-tb), trm = -wmax(-tr);
+            const double t1 = fmin(tbm, trm), t2 = dep ? inf : fmax(viol, 0.0) / q;
+            if (t1 == inf && t2 == inf) break;                     /* no step possible: the stage QP is infeasible */
+            const double t = fmin(t1, t2);
+            if (!dep && own && !fixed) z = fma(t, dz, z);
+            if (inw) nur = fma(-t, rr, nur);
+            up += t;
+            if (t2 <= t1) {
+                /* full step: p joins the working set */
+                if (ptype == 1) { if (lane == pidx) { z = psg > 0.0 ? lo : hi; fixed = true; sg = psg; } mb |= 1ull << pidx; }
+                else { if (lane == pidx) { inw = true; sr = psg; nur = psg * up; } mr |= 1ull << pidx; }
+                ptype = 0;
+            } else if (tbm <= trm) {
+                const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__builtin_amdgcn_ballot_w64(cb && tb == tbm)));
+                if (lane == i) fixed = false;
+                mb &= ~(1ull << i);
+            } else {
+                const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__builtin_amdgcn_ballot_w64(cr && tr == trm)));
+                if (lane == i) { inw = false; nur = 0.0; }
+                mr &= ~(1ull << i);
+            }
         }
     }
     if (!ok && lane == 0) { D.ctrl->status = 4; D.ctrl->done = 1; }      /* TREEQP_DN_STAGE_QP_SOLVE_FAILED */
-    if (lane == 0) { D.bmask[k] = mb; Gn.rmask[k] = mr; }
+    const u64 ub = __builtin_amdgcn_ballot_w64(fixed && sg < 0.0), ur = __builtin_amdgcn_ballot_w64(inw && sr < 0.0);
+    if (lane == 0) {
+        D.bmask[k] = mb; Gn.rmask[k] = mr; Gn.sides[k] = ub; Gn.sides[T.Nn + k] = ur;
+        Gn.steps_last[k] = steps; Gn.steps_total[k] += steps;
+    }
     if (row) Gn.mu[ro + lane] = inw ? -nur : 0.0;
     if (own) {
         if (isx) { if (save_s) D.xUncS[xo + j0] = D.xUnc[xo + j0]; D.x[xo + j0] = z; D.xUnc[xo + j0] = h; }
@@ -1813,7 +1883,10 @@ struct tqgpu_solver {
     int sum_nc = 0;
     int *d_gtab = nullptr;
     double *d_Gt = nullptr, *d_drange = nullptr, *d_gmu = nullptr;
-    unsigned long long *d_rmask = nullptr;
+    unsigned long long *d_rmask = nullptr;     /* 4 Nn words: Gen::rmask (2 Nn), Gen::sides (2 Nn) */
+    long *d_gsteps = nullptr;    /* Gen::steps_total (Nn longs), then Gen::steps_last (Nn ints) */
+    bool gen_hot = true;         /* stage_gen starts from the stored working sets (tqgpu_set_gen_hot_start) */
+    Gen h_gen{};                 /* what d_gen holds */
     Gen *d_gen = nullptr;
     std::vector<double> h_bounds; /* the bounds last set by tqgpu_set_bounds (device layout: xmin | xmax | umin | umax); empty: unknown */
     double *d_Hd = nullptr;      /* writable alias of Data.Hd */
@@ -3403,7 +3476,7 @@ extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const doubl
             s->ggoff[(size_t)k + 1] = s->ggoff[(size_t)k] + nc[k] * (s->nx[k] + s->nu[k]);
         }
         s->sum_nc = total;
-        s->mem.release(s->d_gtab); s->mem.release(s->d_Gt); s->mem.release(s->d_drange); s->mem.release(s->d_gmu); s->mem.release(s->d_rmask); s->mem.release(s->d_gen);
+        s->mem.release(s->d_gtab); s->mem.release(s->d_Gt); s->mem.release(s->d_drange); s->mem.release(s->d_gmu); s->mem.release(s->d_rmask); s->mem.release(s->d_gsteps); s->mem.release(s->d_gen);
         std::vector<int> tab(s->gnc);
         tab.insert(tab.end(), s->groff.begin(), s->groff.end()); tab.insert(tab.end(), s->ggoff.begin(), s->ggoff.end());
         int rc;
@@ -3411,12 +3484,16 @@ extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const doubl
             (rc = s->mem.zeroed(s->d_Gt, sizeof(double) * (size_t)std::max(s->ggoff[(size_t)Nn], 1), TQGPU_ENOMEM, "the rows of the general constraints")) ||
             (rc = s->mem.zeroed(s->d_drange, sizeof(double) * (size_t)std::max(2 * total, 1), TQGPU_ENOMEM, "the ranges of the general constraints")) ||
             (rc = s->mem.zeroed(s->d_gmu, sizeof(double) * (size_t)std::max(total, 1), TQGPU_ENOMEM, "the multipliers of the general constraints")) ||
-            (rc = s->mem.zeroed(s->d_rmask, sizeof(unsigned long long) * 2 * (size_t)Nn, TQGPU_ENOMEM, "the working sets of the general constraints")))
+            (rc = s->mem.zeroed(s->d_rmask, sizeof(unsigned long long) * 4 * (size_t)Nn, TQGPU_ENOMEM, "the working sets of the general constraints")) ||
+            (rc = s->mem.zeroed(s->d_gsteps, (sizeof(long) + sizeof(int)) * (size_t)Nn, TQGPU_ENOMEM, "the step counters of the general constraints")))
             return rc;
         Gen g;
         g.nc = s->d_gtab; g.roff = s->d_gtab + Nn; g.goff = s->d_gtab + 2 * Nn + 1;
         g.Gt = s->d_Gt; g.dmin = s->d_drange; g.dmax = s->d_drange + total; g.mu = s->d_gmu; g.rmask = s->d_rmask;
+        g.sides = s->d_rmask + 2 * (size_t)Nn; g.hot = s->gen_hot ? 1 : 0;
+        g.steps_total = s->d_gsteps; g.steps_last = reinterpret_cast<int *>(s->d_gsteps + Nn);
         if ((rc = s->mem.upload(s->d_gen, &g, sizeof(Gen), TQGPU_ENOMEM, "the record of the general constraints"))) return rc;
+        s->h_gen = g;
         s->D.gen = s->d_gen;
         if (s->dense) HIP_TRY(hipMemcpy(s->d_kind, s->h_kind.data(), sizeof(int) * (size_t)Nn, hipMemcpyHostToDevice));
         s->need_dense_init = true;
@@ -3456,6 +3533,48 @@ extern "C" int tqgpu_get_mu_d(tqgpu_solver *s, double *mu_d) {
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (s->sum_nc > 0) HIP_TRY(hipMemcpy(mu_d, s->d_gmu, sizeof(double) * (size_t)s->sum_nc, hipMemcpyDeviceToHost));
     if (!s->gen) std::fill(mu_d, mu_d + s->sum_nc, 0.0);
+    return TQGPU_OK;
+}
+
+/* stage_gen's hot start on / off (default on).  Off: every stage solve of a kind-3 node starts at the minimiser over the equalities.  Either
+ * way the call empties the stored working sets of the kind-3 nodes (the box nodes keep theirs). */
+extern "C" int tqgpu_set_gen_hot_start(tqgpu_solver *s, int on) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    s->gen_hot = on != 0;
+    if (!s->d_gen) return TQGPU_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t Nn = (size_t)s->Nn;
+    s->h_gen.hot = s->gen_hot ? 1 : 0;
+    /* everything on the mirror's own stream, so that it is ordered before the next solve's launches by construction */
+    std::vector<unsigned long long> bm(Nn);
+    HIP_TRY(hipMemcpyAsync(bm.data(), s->D.bmask, sizeof(unsigned long long) * Nn, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (size_t k = 0; k < Nn && k < s->h_kind.size(); k++) if (s->h_kind[k] == 3) bm[k] = 0ull;
+    HIP_TRY(hipMemcpyAsync(s->D.bmask, bm.data(), sizeof(unsigned long long) * Nn, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_gen, &s->h_gen, sizeof(Gen), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_rmask, 0, sizeof(unsigned long long) * Nn, s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_rmask + 2 * Nn, 0, sizeof(unsigned long long) * 2 * Nn, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TQGPU_OK;
+}
+
+/* active-set steps of stage_gen per node (Nn entries each, either may be NULL): in the last stage sweep, and summed over the last tqgpu_solve.
+ * One step is one factorisation of S: the dual-feasibility rounds of a hot start and a cold redo count.  0 on nodes of other kinds. */
+extern "C" int tqgpu_get_stage_steps(tqgpu_solver *s, int *last, long *total) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    const size_t Nn = (size_t)s->Nn;
+    if (!s->gen || !s->d_gsteps) {
+        if (last) std::fill(last, last + Nn, 0);
+        if (total) std::fill(total, total + Nn, 0L);
+        return TQGPU_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (total) HIP_TRY(hipMemcpy(total, s->d_gsteps, sizeof(long) * Nn, hipMemcpyDeviceToHost));
+    if (last) HIP_TRY(hipMemcpy(last, s->d_gsteps + Nn, sizeof(int) * Nn, hipMemcpyDeviceToHost));
     return TQGPU_OK;
 }
 
@@ -3683,6 +3802,7 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         s->need_init = false;
         s->stream_pending = true;
     }
+    if (s->gen && s->d_gsteps) HIP_TRY(hipMemsetAsync(s->d_gsteps, 0, (sizeof(long) + sizeof(int)) * (size_t)T.Nn, st));      /* tqgpu_get_stage_steps: per solve */
     if (s->dense && s->need_dense_init) {
         hipLaunchKernelGGL(k_dense_init, dim3(T.Nn), dim3(WAVE), s->lds_dense, st, T, D); cx.launches++;
         s->need_dense_init = false;
