@@ -86,6 +86,9 @@ int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const double *Rd
  * bounds: z_k = H_k^-1 h_k, P_k = H_k^-1 with H_k = [Q S'; S R].  Flat layout as
  * tree_qp_in_set_ltv_objective_colmajor (tree_qp_common.c:2010-2050): per node Q (nx x nx), R (nu x nu),
  * S (nu x nx) column major, then q, r.  Bounds are ignored while it is selected. */
+/* Routes of the dense kinds (1, 2, 3 below).  By default a tree with dense nodes runs one launch per phase and tree level.  With
+ * tqgpu_set_dense_single_launch (further down; opt-in) a small tree runs its whole solve as ONE launch of one workgroup, the dense
+ * stage solvers compiled in: same bodies, same results up to the order of the workgroup's sums. */
 int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const double *R, const double *S, const double *q, const double *r);
 /* the same with a per-node choice (opts->qp_solver[] of the reference, dual_Newton_tree.c:124-162): kind[k] = 0 clipping (the
  * diagonals of Q_k and R_k are the weights; off-diagonals and S_k must be zero), 1 dense unconstrained (bounds ignored),
@@ -103,7 +106,8 @@ int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const double *xmax, co
 /* General constraints dmin <= C x + D u <= dmax on the nodes of kind 3 (qpOASES QProblem of the reference,
  * dual_Newton_tree_qpoases.c:226-300, 312-358, 524-570): nc[k] rows on node k, C (nc x nx) and D (nc x nu) column major, node after
  * node; NULL = leave alone.  nc != NULL (re)defines the rows: C, D not given with it are zero, dmin, dmax unbounded.  The stage QP
- * is solved by a dual active-set method (Goldfarb and Idnani), one wave per node, on the launch-per-phase route; it needs
+ * is solved by a dual active-set method (Goldfarb and Idnani), one wave per node, on the launch-per-phase route or, on request,
+ * inside the single-workgroup launch (tqgpu_set_dense_single_launch); it needs
  * nx[k] + nu[k] <= 64 (TQGPU_EUNSUPPORTED from tqgpu_set_objective_mixed) and nc[k] <= 64 (TQGPU_EUNSUPPORTED from this call);
  * dmin > dmax is TQGPU_EINVAL.  An infeasible stage QP ends tqgpu_solve with tqgpu_result.status = 4.  The multipliers of the
  * rows (sign of tree_qp_out.mu_d: + on dmax, - on dmin) come from tqgpu_get_mu_d, sum_nc doubles (tqgpu_dims2). */
@@ -169,7 +173,22 @@ int tqgpu_uses_fused_path(const tqgpu_solver *s);
 #define TQGPU_PLAN_BOX             (1u << 16)   /* ... with box-constrained nodes */
 #define TQGPU_PLAN_LAST_SINGLE_WG  (1u << 17)   /* the last solve begun (alone or in a batch) ran the single-workgroup kernel */
 #define TQGPU_PLAN_GEN             (1u << 18)   /* dense stage solver with nodes that have general constraints (kind 3) */
+#define TQGPU_PLAN_DENSE_SINGLE_WG (1u << 19)   /* dense tree opted in to the single-workgroup launch AND eligible for it (tqgpu_set_dense_single_launch) */
 int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs);
+/* Single-launch solves of dense trees (kinds 1 / 2 / 3), per mirror, default off; TREEQP_AMD_DENSE_SINGLE_LAUNCH=1 in the environment
+ * at create time is the same as calling the setter with 1.  On: a dense tree that fits runs its whole solve as one launch of one
+ * workgroup (tqgpu_uses_fused_path gives 3) instead of one launch per phase and level.  It fits when no tree level has more than 96
+ * nodes and the stage windows find room: a node's stage solve needs head + 2 nz^2 doubles of LDS (kind 2) or
+ * head + nc + 2 nz^2 + nz nc + nc^2 (kind 3), nz = nx + nu, head = children's nx + nx + 2 nz + 2; the stage sweep runs on
+ * stage_waves <= 16 waves, each with a window of the tree's largest need, stage_waves being the largest count whose windows, with the
+ * index tables, stay within 150 KiB.  Eligibility follows the kinds and rows last set (tqgpu_set_objective_mixed / _dense,
+ * tqgpu_set_constraints with nc).  A tree that does not fit, a profiled solve (opts->profile != 0), maxIter <= 0 and the members of a
+ * tqgpu_solve_batch keep the launch-per-phase route.  The stored working sets (the hot start of kinds 2 and 3) are shared by both
+ * routes: switching between two solves needs no reset.  Results agree with the default route's up to the order of the sums (1e-10
+ * on well-conditioned problems); status 4 (a stage QP without solution) ends the solve inside the launch with the same verdict. */
+int tqgpu_set_dense_single_launch(tqgpu_solver *s, int on);
+/* any pointer may be NULL: the setting, whether the current kinds / rows fit, waves of the stage sweep (0 if not eligible) */
+int tqgpu_get_dense_single_launch(const tqgpu_solver *s, int *on, int *eligible, int *stage_waves);
 /* geometry of the persistent launch: block levels, tiers, workgroups per launch, co-resident workgroup capacity of the device, CUs */
 int tqgpu_geometry(const tqgpu_solver *s, int *levels, int *tiers, int *workgroups, int *capacity, int *compute_units);
 /* diagnostic: persistent launches of this mirror that timed out (device shared with other work) and were redone on another path */

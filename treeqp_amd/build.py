@@ -62,6 +62,7 @@ PERSIST_SLICES = 9
 DEVICE_PARTS = {
     "host": ("TQP_HOST", []),
     "gpersist": ("TQP_GP", []),
+    "gpdense": ("TQP_GPD", []),
     "wide": ("TQP_WIDE", []),
     "wide3": ("TQP_W3", []),
     "tiered": ("TQP_TIER", []),

@@ -525,7 +525,7 @@ class TqGpu:
 
     PLAN_FLAGS = ("wide", "wide_small", "w3", "w3_sgp", "w3_merge", "fwd_chain", "fuse", "persist", "persist_one", "gpersist",
                   "gp_state_lds", "gp_const_lds", "gp_tables_lds", "gp_small16", "gp_small8", "dense", "box",
-                  "last_single_wg", "gen")
+                  "last_single_wg", "gen", "dense_single_wg")
 
     @property
     def plan(self) -> dict:
@@ -597,6 +597,18 @@ class TqGpu:
         """the kind-3 stage solver starts from the working set of its node's last stage solve (default) or cold; empties the stored sets"""
         self._chk(lib().tqgpu_set_gen_hot_start(self.h, int(bool(on))))
         return self
+
+    def set_dense_single_launch(self, on: bool):
+        """opt-in: a dense tree (kinds 1 / 2 / 3) that fits runs its whole solve as one launch of one workgroup"""
+        self._chk(lib().tqgpu_set_dense_single_launch(self.h, int(bool(on))))
+        return self
+
+    @property
+    def dense_single_launch(self) -> tuple:
+        """(on, eligible, stage_waves): the setting, whether the current kinds / rows fit, waves of the stage sweep (0: not eligible)"""
+        v = [C.c_int() for _ in range(3)]
+        self._chk(lib().tqgpu_get_dense_single_launch(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def stage_steps(self) -> dict:
         """active-set steps of the kind-3 stage solver per node: last (the last stage sweep), total (summed over the last solve)"""

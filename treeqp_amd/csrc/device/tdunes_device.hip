@@ -1827,6 +1827,7 @@ struct Owned {
 struct Switches {
     bool generic, tiered, strict_sum, fwd_levels, bwd_levels, small_wide;
     bool no_fuse, no_wide3, no_sgp, no_fwd_chain, no_fwd_merge, no_stage16, gp_no_groups, no_persist_one, verbose, has_lds_pad, has_nap;
+    bool dense_single;
     int chunk, lds_pad, capacity_margin, nap;
 };
 
@@ -1912,6 +1913,14 @@ struct tqgpu_solver {
     bool persist_one = false;          /* the persistent launch of this tree takes the one-workgroup-per-CU build */
     bool in_batch = false;             /* inside tqgpu_solve_batch: members launched one by one run side by side, two workgroups to a CU -- not with that build */
     bool gp_in_lds = false, gp_const_in_lds = false, gp_tab_in_lds = false, gp_small16 = false, gp_small8 = false;
+    /* the single-workgroup solve of a dense tree (g_persist_dense, opt-in): the plan of plan_dense_single for the kinds and rows last set */
+    bool dense_single = false;      /* the caller's choice (tqgpu_set_dense_single_launch, TREEQP_AMD_DENSE_SINGLE_LAUNCH=1) */
+    bool dense_gp_ok = false;       /* the tree with its current kinds and rows fits */
+    int dense_stage_waves = 0;      /* waves of the stage sweep (0: does not fit) */
+    int dense_phase_waves = 0;      /* waves of the sweeps over blocks (GPD_WAVES unless that many windows of lds_gp_wave doubles do not fit) */
+    size_t dense_win_stage = 0, dense_win_region = 0;      /* doubles: a stage window, the window region */
+    size_t lds_gpd_total = 0;       /* bytes of dynamic LDS of g_persist_dense */
+    bool gpd_in_lds = false, gpd_const_in_lds = false, gpd_tab_in_lds = false;
     double *pab = nullptr, *pcst = nullptr;
     bool need_pack = true;          /* QP data changed since the constants were packed */
     /* writable aliases of the const inputs */
@@ -2845,6 +2854,7 @@ void read_switches(Switches &w) {
     w.capacity_margin = num("TREEQP_AMD_CAPACITY_MARGIN", 0);    /* experiment: workgroups kept free in the co-residency test */
     w.no_persist_one = set("TREEQP_AMD_NO_PERSIST_ONE");         /* persistent path: never the one-workgroup-per-CU build */
     w.has_nap = set("TREEQP_AMD_NAP"); w.nap = num("TREEQP_AMD_NAP", 0);      /* persistent path: poll naps of the bottom tier off (0) / on (1) instead of by launch size */
+    w.dense_single = num("TREEQP_AMD_DENSE_SINGLE_LAUNCH", 0) != 0;      /* dense trees that fit: the whole solve as one launch of one workgroup (tqgpu_set_dense_single_launch) */
     w.verbose = set("TREEQP_AMD_VERBOSE");                       /* the persistent path's geometry on stderr */
 }
 
@@ -2867,6 +2877,7 @@ int detect_shape(tqgpu_solver *s) {
         else { s->nx[0] = 0; s->fast = -1; s->mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
     }
     if (s->sw.generic) { s->use_fast = 0; s->use_gpersist = 0; }
+    s->dense_single = s->sw.dense_single;
     if (s->sw.tiered) s->use_persist = 0;
     /* reference-order sums (strict_sum / strict_block_dots): the launch-per-phase kernels and the single-workgroup kernel carry them;
      * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
@@ -3194,7 +3205,9 @@ static bool tiered_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->us
 /* `batch`: as a member of a batched launch (one workgroup per tree) the single-workgroup kernel also takes trees whose
  * state does not fit the LDS mirror; alone, such a tree is faster with one launch per level */
 static bool uses_gpersist(const tqgpu_solver *s, bool batch) {
-    return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->dense && !s->sharded && !persist_capable(s) && !tiered_capable(s);
+    /* a dense tree: only on request, only where plan_dense_single found room, and never as a member of a batch (g_persist_batch has no dense variant) */
+    if (s->dense) return s->dense_single && s->dense_gp_ok && !batch && s->use_gpersist && !s->sharded;
+    return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->sharded && !persist_capable(s) && !tiered_capable(s);
 }
 /* the first route that the mirror and the options admit (batch_member: see uses_gpersist) */
 static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_member) {
@@ -3212,7 +3225,8 @@ extern "C" int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     const bool bits[] = {s->wide, s->wide_small, s->w3_ok, s->w3_sgp, s->w3_merge, s->d_anc != nullptr, s->fuse_ok, s->persist_ok,
                          s->persist_one, s->gpersist_ok, s->gp_in_lds, s->gp_const_in_lds, s->gp_tab_in_lds, s->gp_small16, s->gp_small8,
-                         s->dense, s->box, s->solve_no > 0 && s->route == Route::SINGLE_WG, s->gen};
+                         s->dense, s->box, s->solve_no > 0 && s->route == Route::SINGLE_WG, s->gen,
+                         s->dense && s->dense_single && s->dense_gp_ok};
     unsigned f = 0;
     for (unsigned i = 0; i < sizeof(bits) / sizeof(bits[0]); i++) f |= bits[i] ? 1u << i : 0u;
     if (flags) *flags = f;
@@ -3224,6 +3238,23 @@ extern "C" int tqgpu_uses_fused_path(const tqgpu_solver *s) {
     tqgpu_opts o{}; o.maxIter = 1;          /* the route under default options */
     const Route r = route_of(s, &o, false);
     return r == Route::PERSIST ? 2 : r == Route::TIERED ? 1 : r == Route::SINGLE_WG ? 3 : 0;
+}
+
+/* opt-in: a dense tree (kinds 1 / 2 / 3) that fits runs its whole solve as one launch of one workgroup (g_persist_dense).  The stored working
+ * sets are shared between the routes: switching between two solves needs no reset. */
+extern "C" int tqgpu_set_dense_single_launch(tqgpu_solver *s, int on) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    s->dense_single = on != 0;
+    return TQGPU_OK;
+}
+extern "C" int tqgpu_get_dense_single_launch(const tqgpu_solver *s, int *on, int *eligible, int *stage_waves) {
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    const bool ok = s->dense && s->dense_gp_ok;
+    if (on) *on = s->dense_single ? 1 : 0;
+    if (eligible) *eligible = ok ? 1 : 0;
+    if (stage_waves) *stage_waves = ok ? s->dense_stage_waves : 0;
+    return TQGPU_OK;
 }
 
 /* the options as the kernels take them; TREEQP_AMD_STAMPS is for the caller to set */
@@ -3353,6 +3384,45 @@ int apply_kinds(tqgpu_solver *s, const std::vector<int> &req) {
     s->h_kind_req = req;
     return TQGPU_OK;
 }
+/* The LDS plan of g_persist_dense for the kinds and rows the mirror has now (they decide the stage windows, so this runs where they are
+ * set, not at creation).  The window region holds GPD_WAVES windows of the other phases (lds_gp_wave doubles each; fewer waves take
+ * blocks where that many do not fit: the Hessian window of a node with nz = 64 and 40 child states is 40 KiB) or, overlaid,
+ * stage_waves windows of the tree's largest stage need (lds_stage / lds_box / lds_gen); behind it the index tables and, while they
+ * fit, the state mirror and the constants, as in setup_single_wg.  stage_waves is the largest count <= GPD_WAVES for which the total
+ * stays within setup_single_wg's 150 KiB; 0 (or a size the runtime refuses): not eligible. */
+void plan_dense_single(tqgpu_solver *s) {
+    s->dense_gp_ok = false; s->dense_stage_waves = 0; s->dense_phase_waves = 0; s->lds_gpd_total = 0; s->gpd_in_lds = s->gpd_const_in_lds = s->gpd_tab_in_lds = false;
+    if (!s->dense) return;
+    constexpr size_t budget = 150 * 1024;
+    int widest = 0;
+    for (int l = 0; l <= s->Nh; l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
+    const size_t per_wave = s->lds_gp_wave;
+    if (widest > 6 * GP_WAVES) return;      /* the width test of setup_single_wg */
+    /* the level table (setup_single_wg uploads it only for trees g_persist takes; the dense kernel reads the first nodes of the levels, never the groups) */
+    if (!s->d_lvl_first && s->mem.upload(s->d_lvl_first, s->lvl_first.data(), sizeof(int) * s->lvl_first.size(), TQGPU_ENOMEM, "the level table") != TQGPU_OK) return;
+    const size_t win = ((s->gen ? s->lds_gen : s->box ? s->lds_box : s->lds_stage) + 15) / 16 * 2;      /* doubles, even: the windows stay 16-byte aligned */
+    auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
+    const size_t sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
+    const size_t mirror = 11 * ev(sx) + 5 * ev(su) + 2 * ev((size_t)s->sum_W) + 2 * ev((size_t)s->sum_Ut) + 2 * ev((size_t)s->Nn) + ev(sx + s->Nn + 1);
+    const size_t tables = (13 * ((size_t)s->Nn + 3)) / 2 + 16;
+    const size_t consts = ev((size_t)s->sum_A) + ev((size_t)s->sum_B) + 5 * ev(sx) + 4 * ev(su);
+    int sw = 0, pw = 0;
+    for (int w = GPD_WAVES; w >= 1 && !pw; w--) if ((per_wave * w + tables + 8) * 8 <= budget) pw = w;
+    for (int w = GPD_WAVES; w >= 1 && !sw; w--) if ((win * w + tables + 8) * 8 <= budget) sw = w;
+    if (!sw || !pw) return;
+    const size_t region = std::max(per_wave * (size_t)pw, win * (size_t)sw);
+    size_t total = (region + tables + 8) * 8;
+    s->gpd_tab_in_lds = true;
+    if (total + mirror * 8 <= budget) { s->gpd_in_lds = true; total += mirror * 8; }
+    if (s->gpd_in_lds && total + consts * 8 <= budget) { s->gpd_const_in_lds = true; total += consts * 8; }
+    if (total > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist_dense), hipFuncAttributeMaxDynamicSharedMemorySize, (int)total) != hipSuccess) {
+        (void)hipGetLastError();
+        s->gpd_in_lds = s->gpd_const_in_lds = s->gpd_tab_in_lds = false;
+        return;
+    }
+    s->dense_stage_waves = sw; s->dense_phase_waves = pw; s->dense_win_stage = win; s->dense_win_region = region; s->lds_gpd_total = total;
+    s->dense_gp_ok = true;
+}
 }  // namespace
 
 extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const double *Q, const double *R, const double *S, const double *q, const double *r) {
@@ -3419,6 +3489,7 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     s->lds_dense = lds_dense;
     s->dense = true; s->need_dense_init = true; s->D.dense = 1; s->need_init = true;
     s->use_fast = 0;                                       /* per-node dense blocks: generic kernels */
+    plan_dense_single(s);
     return TQGPU_OK;
 }
 
@@ -3469,7 +3540,7 @@ extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const doubl
     if (nc) {
         const std::vector<int> nc_was = s->gnc;
         s->gnc.assign(nc, nc + Nn);
-        if (s->dense) { const int rck = apply_kinds(s, s->h_kind_req); if (rck != TQGPU_OK) { s->gnc = nc_was; return rck; } }
+        if (s->dense) { const int rck = apply_kinds(s, s->h_kind_req); if (rck != TQGPU_OK) { s->gnc = nc_was; return rck; } plan_dense_single(s); }
         s->groff.assign((size_t)Nn + 1, 0); s->ggoff.assign((size_t)Nn + 1, 0);
         for (int k = 0; k < Nn; k++) {
             s->groff[(size_t)k + 1] = s->groff[(size_t)k] + nc[k];
@@ -3835,7 +3906,16 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
             gp.lvl_first = s->d_lvl_first; gp.lam_init = s->d_lam_init; gp.hres = s->h_res; gp.seq = s->psync.seq; gp.lds_wave = (int)s->lds_gp_wave;
             gp.in_lds = s->gp_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gp_in_lds && s->gp_tab_in_lds) ? 1 : 0; gp.small16 = s->gp_small16 ? 1 : 0; gp.small8 = s->gp_small8 ? 1 : 0; gp.sum_nx = s->sum_nx; gp.sum_nu = s->sum_nu; gp.sum_W = s->sum_W; gp.sum_Ut = s->sum_Ut;
             gp.const_in_lds = s->gp_const_in_lds ? 1 : 0; gp.sum_A = s->sum_A; gp.sum_B = s->sum_B;
-            if (defer) { defer->T = T; defer->D = D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
+            gp.stage_waves = 0; gp.win_stage = 0; gp.win_region = 0; gp.phase_waves = 0;
+            if (s->dense) {
+                /* g_persist_dense with the plan of plan_dense_single (never deferred: route_of keeps dense members of a batch off this route) */
+                if (defer) return fail(TQGPU_EINVAL, "a dense tree cannot be a member of a single-workgroup batch launch");
+                gp.in_lds = s->gpd_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd_in_lds && s->gpd_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd_const_in_lds ? 1 : 0;
+                gp.small16 = 0; gp.small8 = s->gp_small8 ? 1 : 0;
+                gp.stage_waves = s->dense_stage_waves; gp.phase_waves = s->dense_phase_waves; gp.win_stage = (int)s->dense_win_stage; gp.win_region = (int)s->dense_win_region;
+                hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->lds_gpd_total, st, T, D, O, gp);
+            }
+            else if (defer) { defer->T = T; defer->D = D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
             else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->lds_gp_total, st, T, D, O, gp);
             cx.launches++;
         } else rcx = launch_persist(s, O, cx.launches, 1, cx.batch_seq);

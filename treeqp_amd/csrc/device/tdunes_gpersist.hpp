@@ -32,6 +32,11 @@ struct GParams {
     int tab_in_lds;              /* 1 (in_lds == 0): at least the index tables are -- every node or block step starts with a chain of dependent look-ups */
     int const_in_lds;            /* 1: ... and so are the constants (A, B, b, weights, linear terms, bounds) */
     int sum_nx, sum_nu, sum_W, sum_Ut, sum_A, sum_B;
+    /* g_persist_dense only (behind what g_persist reads) */
+    int stage_waves;             /* waves that take nodes in the stage sweep: each has a window of win_stage doubles */
+    int win_stage;               /* doubles of the largest stage window of the tree (kind 2: head + 2 nz^2, kind 3: head + nc + 2 nz^2 + nz nc + nc^2) */
+    int phase_waves;             /* waves that take blocks in the Hessian, factorisation and substitution sweeps (a window of lds_wave doubles each): GPD_WAVES unless that many windows do not fit */
+    int win_region;              /* doubles of the window region: max(phase_waves * lds_wave, stage_waves * win_stage) -- the stage windows overlay the other phases' */
 };
 
 /* The state the phases read and write (block matrices, factors, residuals, steps, duals, node variables) is
@@ -176,20 +181,30 @@ __device__ __forceinline__ double *gp_take(double *&cursor, int n) { double *p =
 /* The two descriptor structs hold ~60 pointers.  As kernel arguments (or locals) they would have to live in
  * scalar registers for the whole kernel -- 120 SGPRs, more than a wave has -- and every use would be a spill
  * reload.  They live in LDS instead: the bodies fetch the pointer they need when they need it. */
+/* DENSE (g_persist_dense): the stage sweep is stage_body<2> -- dense unconstrained nodes, stage_box, stage_gen -- one node per wave on
+ * G.stage_waves of the NW waves, each with a window of G.win_stage doubles.  These windows overlay the region that holds the
+ * G.phase_waves windows of the other phases (a workgroup barrier separates a stage sweep from what comes before and after it, so the two are
+ * never live at once); the state mirror and the tables lie behind the larger of the two.  What the dense stage solvers keep besides
+ * the node variables (Pd, bmask, Gen::*, xUncS / uUncS, the step counters) stays in global memory like Hd: the workgroup runs on one
+ * CU, and a barrier makes its writes visible to its other waves.  A stage solve without a solution writes status 4 into the control
+ * block (stage_box / stage_gen); the launch-per-phase route finds it there with its next launch, here the loop looks after each sweep. */
+template <int DENSE, int NW>
 __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GParams G) {
     __shared__ Data sD;
     __shared__ Tree sT;
     Data D = D_in;
     Tree T = T_in;
     extern __shared__ __attribute__((aligned(16))) double lds_all[];
-    __shared__ double sh[GP_WAVES];
+    __shared__ double sh[NW];
     __shared__ int flag;
     Ctrl *c = D.ctrl;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double *lds = lds_all + (size_t)wave * G.lds_wave;
-    double *cur_tab = lds_all + (size_t)GP_WAVES * G.lds_wave;      /* where the LDS copy of the index tables goes (behind the state mirror, if there is one) */
+    const size_t region = DENSE ? (size_t)G.win_region : (size_t)NW * G.lds_wave;
+    const int PW = DENSE ? G.phase_waves : NW;      /* waves that take blocks in the sweeps with an LDS window (H, F): all of them, unless a dense tree's windows are too large for that */
+    double *cur_tab = lds_all + region;      /* where the LDS copy of the index tables goes (behind the state mirror, if there is one) */
     if (G.in_lds) {
-        double *cur_p = lds_all + (size_t)GP_WAVES * G.lds_wave;
+        double *cur_p = lds_all + region;
         const int sx = G.sum_nx, su = G.sum_nu, Nn_ = T.Nn;
         D.Qinv = gp_take(cur_p, sx); D.Rinv = gp_take(cur_p, su);
         D.qmod = gp_take(cur_p, sx); D.rmod = gp_take(cur_p, su); D.x = gp_take(cur_p, sx); D.u = gp_take(cur_p, su);
@@ -204,13 +219,18 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
             double *cA = gp_take(cur_p, G.sum_A), *cB = gp_take(cur_p, G.sum_B), *cb = gp_take(cur_p, sx);
             double *cQd = gp_take(cur_p, sx), *cq = gp_take(cur_p, sx), *cxl = gp_take(cur_p, sx), *cxu = gp_take(cur_p, sx);
             double *cRd = gp_take(cur_p, su), *cr = gp_take(cur_p, su), *cul = gp_take(cur_p, su), *cuu = gp_take(cur_p, su);
-            for (int i = threadIdx.x; i < G.sum_A; i += GP_WAVES * WAVE) cA[i] = D_in.A[i];
-            for (int i = threadIdx.x; i < G.sum_B; i += GP_WAVES * WAVE) cB[i] = D_in.B[i];
-            for (int i = threadIdx.x; i < sx; i += GP_WAVES * WAVE) { cb[i] = D_in.b[i]; cQd[i] = D_in.Qd[i]; cq[i] = D_in.q[i]; cxl[i] = D_in.xmin[i]; cxu[i] = D_in.xmax[i]; }
-            for (int i = threadIdx.x; i < su; i += GP_WAVES * WAVE) { cRd[i] = D_in.Rd[i]; cr[i] = D_in.r[i]; cul[i] = D_in.umin[i]; cuu[i] = D_in.umax[i]; }
+            for (int i = threadIdx.x; i < G.sum_A; i += NW * WAVE) cA[i] = D_in.A[i];
+            for (int i = threadIdx.x; i < G.sum_B; i += NW * WAVE) cB[i] = D_in.B[i];
+            for (int i = threadIdx.x; i < sx; i += NW * WAVE) { cb[i] = D_in.b[i]; cQd[i] = D_in.Qd[i]; cq[i] = D_in.q[i]; cxl[i] = D_in.xmin[i]; cxu[i] = D_in.xmax[i]; }
+            for (int i = threadIdx.x; i < su; i += NW * WAVE) { cRd[i] = D_in.Rd[i]; cr[i] = D_in.r[i]; cul[i] = D_in.umin[i]; cuu[i] = D_in.umax[i]; }
             D.A = cA; D.B = cB; D.b = cb; D.Qd = cQd; D.q = cq; D.xmin = cxl; D.xmax = cxu; D.Rd = cRd; D.r = cr; D.umin = cul; D.umax = cuu;
         }
         cur_tab = cur_p;
+        if constexpr (DENSE) {
+            /* stage_box starts from the x, u of the previous solve (projected onto the box): the mirror begins with them, as the global arrays do on the other routes */
+            for (int i = threadIdx.x; i < sx; i += NW * WAVE) D.x[i] = D_in.x[i];
+            for (int i = threadIdx.x; i < su; i += NW * WAVE) D.u[i] = D_in.u[i];
+        }
     }
     if (G.in_lds || G.tab_in_lds) {
         /* the index tables: every node or block step starts with a chain of dependent table look-ups -- from global memory that is
@@ -222,7 +242,7 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
         const int len[13] = {Nn_, Nn_, Nn_, Nn_, Nn_, n1, n1, n1, n1, Nn_, Nn_, n1, n1};
         int *dst[13];
         for (int a = 0; a < 13; a++) { dst[a] = ip; ip += (len[a] + 1) & ~1; }
-        for (int a = 0; a < 13; a++) for (int i = threadIdx.x; i < len[a]; i += GP_WAVES * WAVE) dst[a][i] = src[a][i];
+        for (int a = 0; a < 13; a++) for (int i = threadIdx.x; i < len[a]; i += NW * WAVE) dst[a][i] = src[a][i];
         T.dad = dst[0]; T.nk = dst[1]; T.kid0 = dst[2]; T.nx = dst[3]; T.nu = dst[4]; T.xoff = dst[5]; T.uoff = dst[6];
         T.aoff = dst[7]; T.boff = dst[8]; T.pos = dst[9]; T.bdim = dst[10]; T.woff = dst[11]; T.utoff = dst[12];
         __syncthreads();
@@ -241,32 +261,34 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
         c->done = 0; c->status = 0; c->iter = 0; c->cur = 0; c->ls_pending = 0; c->ls_iter = 0; c->ls_total = 0; c->ls_last = 0;
         c->restart_counter = 0; c->n_reg = 0; c->tau = 0.0; c->tauPrev = 0.0; c->fval0 = 0.0; c->fval = 0.0; c->dot = 0.0; c->err = 0.0;
     }
-    for (int i = threadIdx.x; i < sT.xoff[Nn]; i += GP_WAVES * WAVE) sD.lam0[i] = G.lam_init[i];
+    for (int i = threadIdx.x; i < sT.xoff[Nn]; i += NW * WAVE) sD.lam0[i] = G.lam_init[i];
     if (sD.Qinv) {
-        for (int i = threadIdx.x; i < sT.xoff[Nn]; i += GP_WAVES * WAVE) sD.Qinv[i] = 1.0 / sD.Qd[i];     /* k_init */
-        for (int i = threadIdx.x; i < sT.uoff[Nn]; i += GP_WAVES * WAVE) sD.Rinv[i] = 1.0 / sD.Rd[i];
+        for (int i = threadIdx.x; i < sT.xoff[Nn]; i += NW * WAVE) sD.Qinv[i] = 1.0 / sD.Qd[i];     /* k_init */
+        for (int i = threadIdx.x; i < sT.uoff[Nn]; i += NW * WAVE) sD.Rinv[i] = 1.0 / sD.Rd[i];
     }
     __syncthreads();
 
     /* first sweep at lambda0 (phase S of iteration 0) and fval0 */
     const int win16 = G.lds_wave / 4;           /* LDS per row of 16 lanes in stage_body16 */
     auto stage_sweep = [&](int mode) {
-        if (G.small16 && !sD.strict) { const SweepCtl sc = sweep_ctl(c, mode); for (int k0 = 4 * wave; k0 < Nn; k0 += 4 * GP_WAVES) stage_body16(sT, sD, mode, k0, min(4, Nn - k0), lane, lds, win16, !G.const_in_lds, sc); }
-        else for (int k = wave; k < Nn; k += GP_WAVES) stage_body(sT, sD, mode, k, lane, lds, !G.const_in_lds);
+        if constexpr (DENSE) { if (wave < G.stage_waves) for (int k = wave; k < Nn; k += G.stage_waves) stage_body<2>(sT, sD, mode, k, lane, lds_all + (size_t)wave * G.win_stage, !G.const_in_lds); }
+        else if (G.small16 && !sD.strict) { const SweepCtl sc = sweep_ctl(c, mode); for (int k0 = 4 * wave; k0 < Nn; k0 += 4 * NW) stage_body16(sT, sD, mode, k0, min(4, Nn - k0), lane, lds, win16, !G.const_in_lds, sc); }
+        else for (int k = wave; k < Nn; k += NW) stage_body(sT, sD, mode, k, lane, lds, !G.const_in_lds);
     };
     stage_sweep(0);
     __syncthreads();
     {
         const double f = sD.strict ? bcast0(threadIdx.x == 0 ? strict_sum(sD.fval, Nn) : 0.0, sh) : block_reduce<false>(sD.fval, Nn, sh);
-        if (threadIdx.x == 0) { c->fval0 = f; c->fval = f; }
+        if (threadIdx.x == 0) { c->fval0 = f; c->fval = f; if constexpr (DENSE) flag = c->done; }
     }
     __syncthreads();
     GP_MARK(0);
 
     for (;;) {
+        if constexpr (DENSE) { if (flag) break; }      /* a stage QP of the first sweep has no solution: status 4, fval0 taken as k_fval_init takes it */
         /* ---- G: dual gradient + termination test (dual_Newton_tree.c:519-543) ---- */
-        if (G.small8) { for (int k0 = 1 + 8 * wave; k0 < Nn; k0 += 8 * GP_WAVES) grad_body8(sT, sD, O.termCondition, k0, min(8, Nn - k0), lane, !G.const_in_lds); }
-        else for (int k = 1 + wave; k < Nn; k += GP_WAVES) grad_body(sT, sD, O.termCondition, k, lane, !G.const_in_lds);
+        if (G.small8) { for (int k0 = 1 + 8 * wave; k0 < Nn; k0 += 8 * NW) grad_body8(sT, sD, O.termCondition, k0, min(8, Nn - k0), lane, !G.const_in_lds); }
+        else for (int k = 1 + wave; k < Nn; k += NW) grad_body(sT, sD, O.termCondition, k, lane, !G.const_in_lds);
         __syncthreads();
         {
             double err = (O.termCondition == 2) ? block_reduce<true>(sD.part_err + 1, Nn - 1, sh)
@@ -283,7 +305,7 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
         if (flag) break;
 
         /* ---- H: block dual Hessian (:551-615) ---- */
-        for (int p = wave; p < Np; p += GP_WAVES) hess_body(sT, sD, p, lane, lds);      /* (side by side in lane groups, as the sweeps below: measured slower, 67 against 56 us per iteration of a 308-node tree) */
+        if (!DENSE || wave < PW) for (int p = wave; p < Np; p += PW) hess_body(sT, sD, p, lane, lds);      /* (side by side in lane groups, as the sweeps below: measured slower, 67 against 56 us per iteration of a 308-node tree) */
         __syncthreads();
         GP_MARK(2);
 
@@ -291,20 +313,20 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
          * parent's block), then forward substitution (:641-805) ---- */
         for (int lvl = Nh - 1; lvl >= 0; lvl--) {
             const int first = G.lvl_first[lvl], count = G.lvl_first[lvl + 1] - first;
-            const int grp = G.lvl_first[Nh + 2 + lvl];          /* blocks of this level one wave takes side by side (1: one block per wave) */
-            if (grp == 3 && sT.bdim[first] == 8 && sT.nx[first] == 8) { for (int b = 3 * wave; b < count; b += 3 * GP_WAVES) factor_body_g<3, 8, 8>(sT, sD, O, first + b, min(3, count - b), lane, lds, G.lds_wave / 3); }
-            else if (grp == 3) { for (int b = 3 * wave; b < count; b += 3 * GP_WAVES) factor_body_g<3>(sT, sD, O, first + b, min(3, count - b), lane, lds, G.lds_wave / 3); }
-            else if (grp == 2) { for (int b = 2 * wave; b < count; b += 2 * GP_WAVES) factor_body_g<2>(sT, sD, O, first + b, min(2, count - b), lane, lds, G.lds_wave / 2); }
-            else for (int b = wave; b < count; b += GP_WAVES) factor_body(sT, sD, O, first + b, lane, lds);
+            const int grp = DENSE ? 1 : G.lvl_first[Nh + 2 + lvl];          /* blocks of this level one wave takes side by side (1: one block per wave; dense trees: never grouped) */
+            if (grp == 3 && sT.bdim[first] == 8 && sT.nx[first] == 8) { for (int b = 3 * wave; b < count; b += 3 * NW) factor_body_g<3, 8, 8>(sT, sD, O, first + b, min(3, count - b), lane, lds, G.lds_wave / 3); }
+            else if (grp == 3) { for (int b = 3 * wave; b < count; b += 3 * NW) factor_body_g<3>(sT, sD, O, first + b, min(3, count - b), lane, lds, G.lds_wave / 3); }
+            else if (grp == 2) { for (int b = 2 * wave; b < count; b += 2 * NW) factor_body_g<2>(sT, sD, O, first + b, min(2, count - b), lane, lds, G.lds_wave / 2); }
+            else if (!DENSE || wave < PW) for (int b = wave; b < count; b += PW) factor_body(sT, sD, O, first + b, lane, lds);
             __syncthreads();
         }
         GP_MARK(3);
         for (int lvl = 1; lvl < Nh; lvl++) {
             const int first = G.lvl_first[lvl], count = G.lvl_first[lvl + 1] - first;
-            const int grp = G.lvl_first[Nh + 2 + lvl];
-            if (grp == 3) { for (int b = 3 * wave; b < count; b += 3 * GP_WAVES) forward_body_g<3>(sT, sD, first + b, min(3, count - b), lane, lds, G.lds_wave / 3); }
-            else if (grp == 2) { for (int b = 2 * wave; b < count; b += 2 * GP_WAVES) forward_body_g<2>(sT, sD, first + b, min(2, count - b), lane, lds, G.lds_wave / 2); }
-            else for (int b = wave; b < count; b += GP_WAVES) forward_body(sT, sD, first + b, lane, lds);
+            const int grp = DENSE ? 1 : G.lvl_first[Nh + 2 + lvl];
+            if (grp == 3) { for (int b = 3 * wave; b < count; b += 3 * NW) forward_body_g<3>(sT, sD, first + b, min(3, count - b), lane, lds, G.lds_wave / 3); }
+            else if (grp == 2) { for (int b = 2 * wave; b < count; b += 2 * NW) forward_body_g<2>(sT, sD, first + b, min(2, count - b), lane, lds, G.lds_wave / 2); }
+            else if (!DENSE || wave < PW) for (int b = wave; b < count; b += PW) forward_body(sT, sD, first + b, lane, lds);
             __syncthreads();
         }
         GP_MARK(4);
@@ -326,7 +348,10 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
             stage_sweep(1);
             __syncthreads();
             const double f = sD.strict ? bcast0(threadIdx.x == 0 ? strict_sum(sD.fval, Nn) : 0.0, sh) : block_reduce<false>(sD.fval, Nn, sh);
-            if (threadIdx.x == 0) { ls_decide_tail(c, sD, O, f); flag = c->ls_pending; }
+            if (threadIdx.x == 0) {
+                if (DENSE && c->done) flag = 0;      /* status 4 out of this trial: the control block stays as the trial found it (k_ls_decide is a no-op then) */
+                else { ls_decide_tail(c, sD, O, f); flag = c->ls_pending; }
+            }
             __syncthreads();
             if (!flag) break;
         }
@@ -343,11 +368,11 @@ __device__ __forceinline__ void g_persist_body(Tree T_in, Data D_in, Opts O, GPa
     __syncthreads();
     if (G.in_lds) {
         const int sx = G.sum_nx, su = G.sum_nu;
-        for (int i = threadIdx.x; i < sx; i += GP_WAVES * WAVE) {
+        for (int i = threadIdx.x; i < sx; i += NW * WAVE) {
             D_in.x[i] = sD.x[i]; D_in.xUnc[i] = sD.xUnc[i]; D_in.qmod[i] = sD.qmod[i]; D_in.QinvCal[i] = sD.QinvCal[i];
             D_in.lam0[i] = sD.lam0[i]; D_in.lam1[i] = sD.lam1[i]; D_in.dlam[i] = sD.dlam[i]; D_in.res[i] = sD.res[i];
         }
-        for (int i = threadIdx.x; i < su; i += GP_WAVES * WAVE) { D_in.u[i] = sD.u[i]; D_in.uUnc[i] = sD.uUnc[i]; D_in.rmod[i] = sD.rmod[i]; D_in.RinvCal[i] = sD.RinvCal[i]; }
+        for (int i = threadIdx.x; i < su; i += NW * WAVE) { D_in.u[i] = sD.u[i]; D_in.uUnc[i] = sD.uUnc[i]; D_in.rmod[i] = sD.rmod[i]; D_in.RinvCal[i] = sD.RinvCal[i]; }
     }
     /* verdict to the host */
     __syncthreads();
@@ -367,7 +392,7 @@ __global__ void __launch_bounds__(GP_WAVES * WAVE) g_persist(Tree T_in, Data D_i
 #if !TQ_HAS(TQP_GP)
 ;
 #else
-{ g_persist_body(T_in, D_in, O, G); }
+{ g_persist_body<0, GP_WAVES>(T_in, D_in, O, G); }
 #endif
 
 /* a batch of independent small trees (fault_tolerance.c keeps one QP per spring configuration, :486-530): ONE launch, one
@@ -380,6 +405,18 @@ __global__ void __launch_bounds__(GP_WAVES * WAVE) g_persist_batch(const GItem *
 #else
 {
     const GItem *it = items + blockIdx.x;
-    g_persist_body(it->T, it->D, O, it->G);
+    g_persist_body<0, GP_WAVES>(it->T, it->D, O, it->G);
 }
+#endif
+
+/* the same solve for trees with dense nodes (kinds 1, 2, 3; opt-in: tqgpu_set_dense_single_launch).  GPD_WAVES waves: stage_gen alone
+ * wants 125 registers per lane, which a workgroup of 16 waves (128 per lane) leaves no room around */
+#ifndef GPD_WAVES
+#define GPD_WAVES 16
+#endif
+__global__ void __launch_bounds__(GPD_WAVES * WAVE) g_persist_dense(Tree T_in, Data D_in, Opts O, GParams G)
+#if !TQ_HAS(TQP_GPD)
+;
+#else
+{ g_persist_body<1, GPD_WAVES>(T_in, D_in, O, G); }
 #endif

@@ -19,7 +19,8 @@
 #define TQP_SHARD   0x040   /* f_persist_sh<.., 1>: compiled with -DTQ_LD_SCOPE=__HIP_MEMORY_SCOPE_SYSTEM (polls of a slab that peers write over xGMI) */
 #define TQP_BATCH   0x080   /* f_persist_batch */
 #define TQP_SHARD_AG 0x100  /* f_persist_sh<.., 0>: the same kernel with agent-scope polls (A/B on a node) */
-#define TQP_ALL     0x1FF
+#define TQP_GPD     0x200   /* g_persist_dense: the single-workgroup solve with the dense stage solvers compiled in (tdunes_gpersist.hpp) */
+#define TQP_ALL     0x3FF
 
 #ifndef TQ_PARTS
 #define TQ_PARTS TQP_ALL
