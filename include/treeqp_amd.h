@@ -183,12 +183,23 @@ int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs);
  * stage_waves <= 16 waves, each with a window of the tree's largest need, stage_waves being the largest count whose windows, with the
  * index tables, stay within 150 KiB.  Eligibility follows the kinds and rows last set (tqgpu_set_objective_mixed / _dense,
  * tqgpu_set_constraints with nc).  A tree that does not fit, a profiled solve (opts->profile != 0), maxIter <= 0 and the members of a
- * tqgpu_solve_batch keep the launch-per-phase route.  The stored working sets (the hot start of kinds 2 and 3) are shared by both
+ * tqgpu_solve_batch keep the launch-per-phase route, unless tqgpu_set_dense_batch_launch.  The stored working sets (the hot start of kinds 2 and 3) are shared by both
  * routes: switching between two solves needs no reset.  Results agree with the default route's up to the order of the sums (1e-10
  * on well-conditioned problems); status 4 (a stage QP without solution) ends the solve inside the launch with the same verdict. */
 int tqgpu_set_dense_single_launch(tqgpu_solver *s, int on);
 /* any pointer may be NULL: the setting, whether the current kinds / rows fit, waves of the stage sweep (0 if not eligible) */
 int tqgpu_get_dense_single_launch(const tqgpu_solver *s, int *on, int *eligible, int *stage_waves);
+/* Batches of dense trees in one launch, per mirror, default off; TREEQP_AMD_DENSE_BATCH_LAUNCH=1 in the environment at create time is
+ * the same as calling the setter with 1.  On: where tqgpu_solve_batch finds at least two such members that fit (the rule above, the same
+ * `eligible`) next to each other on one device, they go out as ONE launch with one workgroup per tree, each workgroup computing exactly what the
+ * member's tqgpu_set_dense_single_launch solve computes (bit for bit) -- instead of one member after the other on the launch-per-phase
+ * route.  A member alone in its batch, a profiled solve and maxIter <= 0 run what the mirror runs on its own.  Independent of
+ * tqgpu_set_dense_single_launch: this option says nothing about tqgpu_solve, that one nothing about batches.  Status 4 in one member ends
+ * that member's workgroup only; working sets and step counters are shared with the other routes, switching needs no reset.  After the
+ * batch, TQGPU_PLAN_LAST_SINGLE_WG is set on the members that went out in the launch. */
+int tqgpu_set_dense_batch_launch(tqgpu_solver *s, int on);
+/* any pointer may be NULL: the setting, whether the current kinds / rows fit (as tqgpu_get_dense_single_launch reports it) */
+int tqgpu_get_dense_batch_launch(const tqgpu_solver *s, int *on, int *eligible);
 /* geometry of the persistent launch: block levels, tiers, workgroups per launch, co-resident workgroup capacity of the device, CUs */
 int tqgpu_geometry(const tqgpu_solver *s, int *levels, int *tiers, int *workgroups, int *capacity, int *compute_units);
 /* diagnostic: persistent launches of this mirror that timed out (device shared with other work) and were redone on another path */

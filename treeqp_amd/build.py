@@ -63,6 +63,7 @@ DEVICE_PARTS = {
     "host": ("TQP_HOST", []),
     "gpersist": ("TQP_GP", []),
     "gpdense": ("TQP_GPD", []),
+    "gpdbatch": ("TQP_GPDB", []),
     "wide": ("TQP_WIDE", []),
     "wide3": ("TQP_W3", []),
     "tiered": ("TQP_TIER", []),

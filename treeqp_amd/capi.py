@@ -610,6 +610,17 @@ class TqGpu:
         self._chk(lib().tqgpu_get_dense_single_launch(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def set_dense_batch_launch(self, on: bool):
+        """opt-in: dense trees that fit go out of solve_batch together, as one launch with a workgroup per tree (says nothing about solve())"""
+        self._chk(lib().tqgpu_set_dense_batch_launch(self.h, int(bool(on))))
+        return self
+
+    def dense_batch_launch(self) -> tuple:
+        """(on, eligible): the setting, whether the current kinds / rows fit (the `eligible` of dense_single_launch)"""
+        v = [C.c_int() for _ in range(2)]
+        self._chk(lib().tqgpu_get_dense_batch_launch(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     def stage_steps(self) -> dict:
         """active-set steps of the kind-3 stage solver per node: last (the last stage sweep), total (summed over the last solve)"""
         last, total = np.zeros(len(self.nk), dtype=np.int32), np.zeros(len(self.nk), dtype=np.int64)

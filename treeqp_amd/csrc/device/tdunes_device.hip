@@ -1827,7 +1827,7 @@ struct Owned {
 struct Switches {
     bool generic, tiered, strict_sum, fwd_levels, bwd_levels, small_wide;
     bool no_fuse, no_wide3, no_sgp, no_fwd_chain, no_fwd_merge, no_stage16, gp_no_groups, no_persist_one, verbose, has_lds_pad, has_nap;
-    bool dense_single;
+    bool dense_single, dense_batch;
     int chunk, lds_pad, capacity_margin, nap;
 };
 
@@ -1915,6 +1915,7 @@ struct tqgpu_solver {
     bool gp_in_lds = false, gp_const_in_lds = false, gp_tab_in_lds = false, gp_small16 = false, gp_small8 = false;
     /* the single-workgroup solve of a dense tree (g_persist_dense, opt-in): the plan of plan_dense_single for the kinds and rows last set */
     bool dense_single = false;      /* the caller's choice (tqgpu_set_dense_single_launch, TREEQP_AMD_DENSE_SINGLE_LAUNCH=1) */
+    bool dense_batch = false;       /* ... for the members of a batch: one launch of g_persist_dense_batch, a workgroup per tree (tqgpu_set_dense_batch_launch, TREEQP_AMD_DENSE_BATCH_LAUNCH=1); independent of dense_single */
     bool dense_gp_ok = false;       /* the tree with its current kinds and rows fits */
     int dense_stage_waves = 0;      /* waves of the stage sweep (0: does not fit) */
     int dense_phase_waves = 0;      /* waves of the sweeps over blocks (GPD_WAVES unless that many windows of lds_gp_wave doubles do not fit) */
@@ -2855,6 +2856,7 @@ void read_switches(Switches &w) {
     w.no_persist_one = set("TREEQP_AMD_NO_PERSIST_ONE");         /* persistent path: never the one-workgroup-per-CU build */
     w.has_nap = set("TREEQP_AMD_NAP"); w.nap = num("TREEQP_AMD_NAP", 0);      /* persistent path: poll naps of the bottom tier off (0) / on (1) instead of by launch size */
     w.dense_single = num("TREEQP_AMD_DENSE_SINGLE_LAUNCH", 0) != 0;      /* dense trees that fit: the whole solve as one launch of one workgroup (tqgpu_set_dense_single_launch) */
+    w.dense_batch = num("TREEQP_AMD_DENSE_BATCH_LAUNCH", 0) != 0;        /* ... as members of a batch: one launch, a workgroup per tree (tqgpu_set_dense_batch_launch) */
     w.verbose = set("TREEQP_AMD_VERBOSE");                       /* the persistent path's geometry on stderr */
 }
 
@@ -2878,6 +2880,7 @@ int detect_shape(tqgpu_solver *s) {
     }
     if (s->sw.generic) { s->use_fast = 0; s->use_gpersist = 0; }
     s->dense_single = s->sw.dense_single;
+    s->dense_batch = s->sw.dense_batch;
     if (s->sw.tiered) s->use_persist = 0;
     /* reference-order sums (strict_sum / strict_block_dots): the launch-per-phase kernels and the single-workgroup kernel carry them;
      * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
@@ -3205,8 +3208,9 @@ static bool tiered_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->us
 /* `batch`: as a member of a batched launch (one workgroup per tree) the single-workgroup kernel also takes trees whose
  * state does not fit the LDS mirror; alone, such a tree is faster with one launch per level */
 static bool uses_gpersist(const tqgpu_solver *s, bool batch) {
-    /* a dense tree: only on request, only where plan_dense_single found room, and never as a member of a batch (g_persist_batch has no dense variant) */
-    if (s->dense) return s->dense_single && s->dense_gp_ok && !batch && s->use_gpersist && !s->sharded;
+    /* a dense tree: only on request, only where plan_dense_single found room; alone and as a member of a batch are two requests
+     * (g_persist_dense, g_persist_dense_batch) */
+    if (s->dense) return (batch ? s->dense_batch : s->dense_single) && s->dense_gp_ok && s->use_gpersist && !s->sharded;
     return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->sharded && !persist_capable(s) && !tiered_capable(s);
 }
 /* the first route that the mirror and the options admit (batch_member: see uses_gpersist) */
@@ -3254,6 +3258,22 @@ extern "C" int tqgpu_get_dense_single_launch(const tqgpu_solver *s, int *on, int
     if (on) *on = s->dense_single ? 1 : 0;
     if (eligible) *eligible = ok ? 1 : 0;
     if (stage_waves) *stage_waves = ok ? s->dense_stage_waves : 0;
+    return TQGPU_OK;
+}
+
+/* opt-in: dense trees that fit go out of tqgpu_solve_batch together, as ONE launch with a workgroup per tree (g_persist_dense_batch), where
+ * each would otherwise run the launch-per-phase route on its own, one after the other.  Says nothing about the mirror solved alone, and
+ * tqgpu_set_dense_single_launch says nothing about batches.  The stored working sets are shared between the routes, as there. */
+extern "C" int tqgpu_set_dense_batch_launch(tqgpu_solver *s, int on) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    s->dense_batch = on != 0;
+    return TQGPU_OK;
+}
+extern "C" int tqgpu_get_dense_batch_launch(const tqgpu_solver *s, int *on, int *eligible) {
+    if (!s) return fail(TQGPU_EINVAL, "null solver");
+    if (on) *on = s->dense_batch ? 1 : 0;
+    if (eligible) *eligible = s->dense && s->dense_gp_ok ? 1 : 0;
     return TQGPU_OK;
 }
 
@@ -3873,10 +3893,13 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         s->need_init = false;
         s->stream_pending = true;
     }
-    if (s->gen && s->d_gsteps) HIP_TRY(hipMemsetAsync(s->d_gsteps, 0, (sizeof(long) + sizeof(int)) * (size_t)T.Nn, st));      /* tqgpu_get_stage_steps: per solve */
+    /* tqgpu_get_stage_steps: per solve.  (A dense member of a batch launch: that launch is on the lead's stream and resets the counters in its own
+     * prologue, g_persist_dense_batch -- a memset on this stream would have to be waited for, once per member and call) */
+    if (s->gen && s->d_gsteps && !(defer && s->dense)) HIP_TRY(hipMemsetAsync(s->d_gsteps, 0, (sizeof(long) + sizeof(int)) * (size_t)T.Nn, st));
     if (s->dense && s->need_dense_init) {
         hipLaunchKernelGGL(k_dense_init, dim3(T.Nn), dim3(WAVE), s->lds_dense, st, T, D); cx.launches++;
         s->need_dense_init = false;
+        if (defer) s->stream_pending = true;      /* the batch launch on the lead's stream waits for it (join_lead_stream): first solves and changed data only */
     }
     if (!single) {
         /* the current buffer is lam0 at the start of every solve */
@@ -3908,12 +3931,12 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
             gp.const_in_lds = s->gp_const_in_lds ? 1 : 0; gp.sum_A = s->sum_A; gp.sum_B = s->sum_B;
             gp.stage_waves = 0; gp.win_stage = 0; gp.win_region = 0; gp.phase_waves = 0;
             if (s->dense) {
-                /* g_persist_dense with the plan of plan_dense_single (never deferred: route_of keeps dense members of a batch off this route) */
-                if (defer) return fail(TQGPU_EINVAL, "a dense tree cannot be a member of a single-workgroup batch launch");
+                /* g_persist_dense with the plan of plan_dense_single; deferred: the same parameters for this member's workgroup of g_persist_dense_batch */
                 gp.in_lds = s->gpd_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd_in_lds && s->gpd_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd_const_in_lds ? 1 : 0;
                 gp.small16 = 0; gp.small8 = s->gp_small8 ? 1 : 0;
                 gp.stage_waves = s->dense_stage_waves; gp.phase_waves = s->dense_phase_waves; gp.win_stage = (int)s->dense_win_stage; gp.win_region = (int)s->dense_win_region;
-                hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->lds_gpd_total, st, T, D, O, gp);
+                if (defer) { defer->T = T; defer->D = D; defer->G = gp; }
+                else hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->lds_gpd_total, st, T, D, O, gp);
             }
             else if (defer) { defer->T = T; defer->D = D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
             else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->lds_gp_total, st, T, D, O, gp);
@@ -4255,21 +4278,25 @@ static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items
 
 /* ---- tqgpu_solve_batch step by step: member table, wave, groups, begin, group launches, end, hand-over ---- */
 
-/* what a batch call knows of one member; everything but the two group flags is decided once per call (plan_members) */
+/* what a batch call knows of one member; everything but the three group flags is decided once per call (plan_members) */
 struct BatchMember {
     tqgpu_solver *s;
     Route plan;                  /* route_of(s, o, true): what the waves and the groups are planned with */
     Route alone;                 /* route_of(s, o, false): differs from `plan` only for a tree that is SINGLE_WG as a group member alone (uses_gpersist) */
     int kidx;                    /* the batch kernel (BATCH_TABLE) this member can go out in under these options, or -1 */
     int need;                    /* workgroups that have to be resident while it runs */
-    bool in_single_wg = false;   /* member of its wave's single-workgroup group ... */
+    bool in_single_wg = false;   /* member of its wave's single-workgroup group (clipping trees: g_persist_batch) ... */
+    bool in_dense_wg = false;    /* ... of its wave's dense single-workgroup group (g_persist_dense_batch) ... */
     bool in_persist = false;     /* ... of its wave's persistent group (form_groups) */
     SolveCtx cx;
 };
-/* THE rule for the route a member runs: a member planned as SINGLE_WG runs it as a member of its wave's single-workgroup group, and a
- * wave has that group only with at least two such members; without the group it runs what it would run on its own.  Every other plan
- * is the same on its own. */
-static Route batch_route(const BatchMember &m) { return m.plan == Route::SINGLE_WG && !m.in_single_wg ? m.alone : m.plan; }
+/* THE rule for the route a member runs: a member planned as SINGLE_WG runs it as a member of its wave's single-workgroup group -- the
+ * clipping trees' or the dense trees', two kernels -- and a wave has such a group only with at least two members of that kind; without
+ * the group it runs what it would run on its own.  Every other plan is the same on its own. */
+static Route batch_route(const BatchMember &m) { return m.plan == Route::SINGLE_WG && !m.in_single_wg && !m.in_dense_wg ? m.alone : m.plan; }
+/* the group a member goes out in, or nullptr */
+template <typename Group>
+static Group *group_of(const BatchMember &m, Group &wg, Group &dg, Group &pg) { return m.in_persist ? &pg : m.in_single_wg ? &wg : m.in_dense_wg ? &dg : nullptr; }
 
 static std::vector<BatchMember> plan_members(tqgpu_solver **solvers, int n, const tqgpu_opts *o) {
     std::vector<BatchMember> tab((size_t)n);
@@ -4312,11 +4339,13 @@ struct BatchGroup {
     size_t launched = 0;               /* members[0 .. launched) went out in the launch */
 };
 
-/* the two groups of the wave [i, j) */
-static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveEnv &env, BatchGroup &wg, BatchGroup &pg) {
-    /* single-workgroup mirrors of this wave go out as ONE launch (one workgroup per tree) on the first one's stream */
-    for (int k = i; k < j; k++) if (tab[(size_t)k].plan == Route::SINGLE_WG) wg.members.push_back(k);
+/* the three groups of the wave [i, j) */
+static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveEnv &env, BatchGroup &wg, BatchGroup &dg, BatchGroup &pg) {
+    /* single-workgroup mirrors of this wave go out as ONE launch (one workgroup per tree) on the first one's stream; the dense ones among
+     * them (uses_gpersist: opted in with tqgpu_set_dense_batch_launch) run another kernel and are a group of their own */
+    for (int k = i; k < j; k++) if (tab[(size_t)k].plan == Route::SINGLE_WG) (tab[(size_t)k].s->dense ? dg : wg).members.push_back(k);
     if (wg.members.size() < 2) wg.members.clear();
+    if (dg.members.size() < 2) dg.members.clear();
     /* persistent mirrors of this wave that share a shape with a batch kernel go out as ONE launch as well */
     const BatchMember *f = nullptr;          /* the first one that has a batch kernel: the others have to match it */
     for (int k = i; k < j; k++) {
@@ -4327,18 +4356,22 @@ static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveE
     }
     if (pg.members.size() < 2 || env.batch_launches) pg.members.clear();      /* (=1: one launch per tree, the round-1 protocol) */
     for (int k : wg.members) tab[(size_t)k].in_single_wg = true;
+    for (int k : dg.members) tab[(size_t)k].in_dense_wg = true;
     for (int k : pg.members) tab[(size_t)k].in_persist = true;
     if (!wg.members.empty()) wg.lead = tab[(size_t)wg.members[0]].s;
+    if (!dg.members.empty()) dg.lead = tab[(size_t)dg.members[0]].s;
     if (!pg.members.empty()) pg.lead = tab[(size_t)pg.members[0]].s;
     /* (the single-workgroup members describe their launches into the array as they begin) */
-    return wg.lead ? grow_items(wg.lead, wg.lead->d_gitems, wg.lead->h_gitems, wg.lead->gitems_cap, wg.members.size()) : TQGPU_OK;
+    for (BatchGroup *g : {&wg, &dg})
+        if (g->lead) if (int rc = grow_items(g->lead, g->lead->d_gitems, g->lead->h_gitems, g->lead->gitems_cap, g->members.size())) return rc;
+    return TQGPU_OK;
 }
 
 /* before a wave begins: whatever batch launch its members were part of last has ended (settle) */
-static int settle_wave(std::vector<BatchMember> &tab, int i, int j, const BatchGroup &wg, const BatchGroup &pg) {
+static int settle_wave(std::vector<BatchMember> &tab, int i, int j, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg) {
     for (int k = i; k < j; k++) {
         const BatchMember &m = tab[(size_t)k];
-        const BatchGroup *g = m.in_persist ? &pg : m.in_single_wg ? &wg : nullptr;
+        const BatchGroup *g = group_of(m, wg, dg, pg);
         /* a member of the previous batch launch that goes out again on the same lead's stream is ordered behind it by that stream */
         if (g && m.s->settle_stream == g->lead->stream) { if (k == g->members[0]) m.s->settle_stream = nullptr; }
         else SETTLE(m.s);
@@ -4393,6 +4426,22 @@ static int launch_single_wg_group(std::vector<BatchMember> &tab, BatchGroup &wg,
     if (lds_batch > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_batch));
     hipLaunchKernelGGL(g_persist_batch, dim3((unsigned)n), dim3(GP_WAVES * WAVE), lds_batch, lead->stream, lead->d_gitems, tab[(size_t)wg.members[0]].cx.O);
     wg.launched = n;
+    return TQGPU_OK;
+}
+
+/* g_persist_dense_batch over the first n members of the dense group: n workgroups of GPD_WAVES waves, the LDS of the largest plan among them
+ * (every member's offsets come from its own GParams).  What a member enqueued on its own stream for this solve (k_dense_init after an upload)
+ * is waited for by join_lead_stream; in the steady state nothing is, and the call costs no synchronisation per member. */
+static int launch_dense_wg_group(std::vector<BatchMember> &tab, BatchGroup &dg, size_t n) {
+    tqgpu_solver *lead = dg.lead;
+    size_t lds_batch = 0;
+    for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)dg.members[m]].s->lds_gpd_total);
+    int rc = join_lead_stream(tab, dg, n);
+    if (rc != TQGPU_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(lead->d_gitems, lead->h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));
+    if ((rc = allow_lds(g_persist_dense_batch, lds_batch)) != TQGPU_OK) return rc;      /* (plan_dense_single asked the same of g_persist_dense for every member) */
+    hipLaunchKernelGGL(g_persist_dense_batch, dim3((unsigned)n), dim3(GPD_WAVES * WAVE), lds_batch, lead->stream, lead->d_gitems, tab[(size_t)dg.members[0]].cx.O);
+    dg.launched = n;
     return TQGPU_OK;
 }
 
@@ -4460,21 +4509,23 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
     for (int i = 0, j; i < n && first_err == TQGPU_OK; i = j) {
         j = wave_end(tab, i, env);
         guard.wave(i, j);
-        BatchGroup wg, pg;          /* single-workgroup group, persistent group */
+        BatchGroup wg, dg, pg;      /* single-workgroup group, dense single-workgroup group, persistent group */
         unsigned pseq = 0;
-        if ((rc = form_groups(tab, i, j, env, wg, pg)) || (rc = settle_wave(tab, i, j, wg, pg)) || (rc = persist_group_seq(tab, pg, pseq))) return rc;
+        if ((rc = form_groups(tab, i, j, env, wg, dg, pg)) || (rc = settle_wave(tab, i, j, wg, dg, pg)) || (rc = persist_group_seq(tab, pg, pseq))) return rc;
         int ok_to = i;
-        size_t gi = 0;              /* members of the single-workgroup group that have begun */
+        size_t gi = 0, di = 0;      /* members of the single-workgroup group / of the dense one that have begun */
         for (int k = i; k < j; k++) {
             BatchMember &m = tab[(size_t)k];
             m.cx = SolveCtx(env, batch_route(m));
             if (m.in_persist) m.cx.batch_seq = pseq;
-            rc = solve_begin(m.s, o, m.cx, m.in_single_wg ? &wg.lead->h_gitems[gi] : nullptr);
+            rc = solve_begin(m.s, o, m.cx, m.in_single_wg ? &wg.lead->h_gitems[gi] : m.in_dense_wg ? &dg.lead->h_gitems[di] : nullptr);
             if (rc != TQGPU_OK) { first_err = rc; first_msg = g_err; break; }
             if (m.in_single_wg) gi++;
+            if (m.in_dense_wg) di++;
             ok_to = k + 1;
         }
         if (gi > 0 && (rc = launch_single_wg_group(tab, wg, gi))) return rc;
+        if (di > 0 && (rc = launch_dense_wg_group(tab, dg, di))) return rc;
         if (pg.lead && ok_to == j && (rc = launch_persist_group(tab, pg, pseq))) return rc;
         for (int k = i; k < ok_to; k++) {
             tqgpu_solver *sk = solvers[k];
@@ -4488,7 +4539,7 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
             if (rc != TQGPU_OK && first_err == TQGPU_OK) { first_err = rc; first_msg = g_err; }
         }
         const bool sync = first_err != TQGPU_OK || env.batch_sync;
-        if ((rc = hand_over(tab, pg, sync)) || (rc = hand_over(tab, wg, sync))) return rc;
+        if ((rc = hand_over(tab, pg, sync)) || (rc = hand_over(tab, wg, sync)) || (rc = hand_over(tab, dg, sync))) return rc;
     }
     if (first_err != TQGPU_OK) return fail(first_err, first_msg);
     return TQGPU_OK;

@@ -420,3 +420,23 @@ __global__ void __launch_bounds__(GPD_WAVES * WAVE) g_persist_dense(Tree T_in, D
 #else
 { g_persist_body<1, GPD_WAVES>(T_in, D_in, O, G); }
 #endif
+
+/* a batch of small dense trees (opt-in: tqgpu_set_dense_batch_launch): to g_persist_dense what g_persist_batch is to g_persist -- one
+ * workgroup per tree, each with the Tree / Data / GParams of its solo launch.  The body takes every size and offset from its own G
+ * (lds_wave, win_stage, win_region, stage_waves, phase_waves, the *_in_lds bits), never from the launch's LDS size, which is the
+ * largest member's: a member computes what its solo launch computes.  The step counters of stage_gen (tqgpu_get_stage_steps: per
+ * solve) are reset here, by the workgroup that owns them -- on the solo route the host does it with a memset on the mirror's own
+ * stream, which this launch (on the lead's stream) is not ordered behind; the body's first barrier comes before its first stage sweep. */
+__global__ void __launch_bounds__(GPD_WAVES * WAVE) g_persist_dense_batch(const GItem *items, Opts O)
+#if !TQ_HAS(TQP_GPDB)
+;
+#else
+{
+    const GItem *it = items + blockIdx.x;
+    if (const Gen *gn = it->D.gen) {
+        long *tot = gn->steps_total; int *last = gn->steps_last;
+        for (int k = threadIdx.x, n = it->T.Nn; k < n; k += GPD_WAVES * WAVE) { tot[k] = 0; last[k] = 0; }
+    }
+    g_persist_body<1, GPD_WAVES>(it->T, it->D, O, it->G);
+}
+#endif

@@ -20,7 +20,9 @@
 #define TQP_BATCH   0x080   /* f_persist_batch */
 #define TQP_SHARD_AG 0x100  /* f_persist_sh<.., 0>: the same kernel with agent-scope polls (A/B on a node) */
 #define TQP_GPD     0x200   /* g_persist_dense: the single-workgroup solve with the dense stage solvers compiled in (tdunes_gpersist.hpp) */
-#define TQP_ALL     0x3FF
+#define TQP_GPDB    0x400   /* g_persist_dense_batch: a part of its own -- in one translation unit with g_persist_dense the bodies have two callers, the inliner
+                             * decides otherwise, and g_persist_dense comes out as another kernel than the one that was measured */
+#define TQP_ALL     0x7FF
 
 #ifndef TQ_PARTS
 #define TQ_PARTS TQP_ALL
