@@ -2388,11 +2388,11 @@ int launch_fast_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches) 
 }
 
 /* one more line-search trial of iteration `it`; phase 0: sweep (+ pack), phase 1: decide */
+/* the next tag of a family of tagged words: counts up and skips 0, the value of a word never written */
+static unsigned next_tag(unsigned &epoch) { if (++epoch == 0) epoch = 1; return epoch; }
 static Fuse next_fuse(tqgpu_solver *s) {
     Fuse F; F.red = s->fuse_red; F.cnt = s->fuse_cnt; F.on = 1;
-    s->fuse_epoch++;
-    if (s->fuse_epoch == 0) s->fuse_epoch = 1;
-    F.tag = s->fuse_epoch;
+    F.tag = next_tag(s->fuse_epoch);
     return F;
 }
 static Fuse no_fuse() { Fuse F; F.red = nullptr; F.cnt = nullptr; F.tag = 0; F.on = 0; return F; }
@@ -2400,10 +2400,16 @@ static W3 next_w3(tqgpu_solver *s) {
     W3 w; w.xu = s->w3_xu; w.red = s->w3_red; w.cnt = s->w3_cnt; w.sum_nx = s->sum_nx; w.lds_wave = (int)((s->lds_stage + 7) / 8);
     w.hm = nullptr;
     s->w3_tail_sg = false;
-    s->w3_epoch++;
-    if (s->w3_epoch == 0) s->w3_epoch = 1;
-    w.tag = s->w3_epoch;
+    w.tag = next_tag(s->w3_epoch);
     return w;
+}
+/* one stage sweep of the launch-per-phase route, by the stage solver the tree's nodes need (general constraints / box bounds / clipping
+ * and dense unconstrained): the one place that picks among the three */
+static void launch_stage_sweep(tqgpu_solver *s, int mode, int h, int t) {
+    const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
+    if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, mode, h, t);
+    else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, mode, h, t);
+    else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, mode, h, t);
 }
 static void launch_sg(tqgpu_solver *s, const Opts &O, int mode, int h, int t, bool fresh = false) {
     W3 w = next_w3(s);
@@ -2437,9 +2443,7 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
         if (!done && r == Route::THREE_LAUNCH) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
         if (!done) {
             if (r == Route::FUSED_TAILS) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
-            else if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, 1, it, t);
-            else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, it, t);
-            else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, it, t);
+            else launch_stage_sweep(s, 1, it, t);
         }
         launches++;
         if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->d_node_cnt_list, s->n_nodes_counted, s->d_blk_list, s->n_blk_counted, s->d_xs, s->rank, s->bnd_b0, s->bnd_bn, s->bnd_own0, s->bnd_ownn, it, t); launches++; }
@@ -2618,17 +2622,23 @@ int setup_persist(tqgpu_solver *s) {
 
 /* one persistent launch (prologue = first sweep of the solve + control block reset): no memset, the
  * hand-over words are told apart by the launch number in their tags */
+/* the 16-bit launch number of a mirror's single launches (f_persist*, g_persist*): the tag of the hand-over words and of the result block,
+ * never 0.  launch_no_after: 0 when the number wraps; step_launch_no: takes the next number and says whether it wrapped */
+static unsigned launch_no_after(unsigned n) { return (n + 1) & 0xFFFFu; }
+static bool step_launch_no(tqgpu_solver *s) {
+    s->launch_no = launch_no_after(s->launch_no);
+    if (s->launch_no != 0) return false;
+    s->launch_no = 1;
+    return true;
+}
+
 int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, unsigned batch_seq = 0) {
     const Data &D = s->D; hipStream_t st = s->stream;
     if (batch_seq) s->launch_no = batch_seq >> 16;          /* part of a batch launch: the caller chose the number (and wiped the buffers if it wrapped) */
-    else {
-        s->launch_no = (s->launch_no + 1) & 0xFFFFu;
-        if (s->launch_no == 0) {
-            /* the 16-bit launch number wraps: words that are not rewritten by every launch (the line-search command / verdict /
-             * batch partials) could still carry a tag of 65535 launches ago -- wipe the hand-over buffers (stream-ordered) */
-            s->launch_no = 1;
-            HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, st));
-        }
+    else if (step_launch_no(s)) {
+        /* the 16-bit launch number wraps: words that are not rewritten by every launch (the line-search command / verdict /
+         * batch partials) could still carry a tag of 65535 launches ago -- wipe the hand-over buffers (stream-ordered) */
+        HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, st));
     }
     s->psync.seq = s->launch_no << 16;
     if (s->need_pack) {
@@ -2677,38 +2687,34 @@ int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, 
 
 /* one Newton iteration on the generic path = its termination test (gradient + check) and the rest (Newton system, step,
  * first trial); `parts` bit 0 / bit 1 select them.  The host enqueues the iteration it expects to be the last one
- * (warm: as many as the previous solve needed) without the rest: ~17 launches that would only find `done` set. */
-void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts = 3, bool phases = false, bool last = false) {
+ * (warm: as many as the previous solve needed) without the rest: ~17 launches that would only find `done` set.
+ * Two families: launch_w3_iteration (THREE_LAUNCH), launch_phase_iteration (FUSED_TAILS, PER_PHASE); launch_generic_iteration picks. */
+/* the three-launch family: k_hf_w, the forward sweep, the first trial and the trials the previous solve's counts predict */
+void launch_w3_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts, bool last) {
+    const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
+    /* three launches: the termination test of this iteration was the tail of the previous launch of k_sg */
+    if (!(parts & 2)) return;
+    const unsigned bw_tag = next_tag(s->bw_epoch);
+    s->w3_tail_sg = false;
+    hipLaunchKernelGGL(k_hf_w, dim3(T.Np), dim3(WT), s->lds_hf_w, st, T, D, O, s->sch_words, s->sch_rs, bw_tag, h); launches++;
+    const bool merged = T.Np > 1 && s->w3_merge;      /* forward sweep + first trial: one launch (k_sgp mode 2) */
+    if (!merged && T.Np > 1) {
+        const unsigned fw_tag = next_tag(s->fw_epoch);
+        if (s->d_anc) hipLaunchKernelGGL(k_fwd3c, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->d_anc, h);
+        else hipLaunchKernelGGL(k_fwd3, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->fw_words, fw_tag, h);
+        launches++;
+    } else if (!merged) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
+    /* the first trial and the predicted trials 2 .. kpred; where this is the last iteration of the chunk that launches anything, the last of them posts */
+    const int kpred = h < (int)s->ls_pred.size() ? std::min(s->ls_pred[(size_t)h], O.lsMaxIter) : 1;
+    s->w3_post_next = last && kpred < 2;
+    launch_sg(s, O, merged ? 2 : 1, h, 1); launches++;
+    for (int tt = 2; tt <= kpred; tt++) { s->w3_post_next = last && tt == kpred; launch_sg(s, O, 1, h, tt); launches++; }
+}
+
+/* the launch-per-phase kernels, with the reductions as launches of their own (PER_PHASE) or as the tails of their producers (FUSED_TAILS) */
+void launch_phase_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts, bool phases) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     auto mark = [&](int i) { if (phases && (size_t)(4 * h + i) < s->phase_ev.size()) (void)hipEventRecord(s->phase_ev[(size_t)(4 * h + i)], st); };
-    if (s->route == Route::THREE_LAUNCH) {
-        /* three launches: the termination test of this iteration was the tail of the previous launch of k_sg */
-        if (!(parts & 2)) return;
-        s->bw_epoch++;
-        if (s->bw_epoch == 0) s->bw_epoch = 1;
-        s->w3_tail_sg = false;
-        hipLaunchKernelGGL(k_hf_w, dim3(T.Np), dim3(WT), s->lds_hf_w, st, T, D, O, s->sch_words, s->sch_rs, s->bw_epoch, h); launches++;
-        const int kpred0 = h < (int)s->ls_pred.size() ? std::min(s->ls_pred[(size_t)h], O.lsMaxIter) : 1;
-        if (T.Np > 1 && s->w3_merge) {
-            /* forward sweep + first trial: one launch */
-            s->w3_post_next = last && kpred0 < 2;
-            launch_sg(s, O, 2, h, 1); launches++;
-            for (int tt = 2; tt <= kpred0; tt++) { s->w3_post_next = last && tt == kpred0; launch_sg(s, O, 1, h, tt); launches++; }
-            return;
-        }
-        if (T.Np > 1) {
-            s->fw_epoch++;
-            if (s->fw_epoch == 0) s->fw_epoch = 1;
-            if (s->d_anc) hipLaunchKernelGGL(k_fwd3c, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->d_anc, h);
-            else hipLaunchKernelGGL(k_fwd3, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->fw_words, s->fw_epoch, h);
-            launches++;
-        } else { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
-        const int kpred = h < (int)s->ls_pred.size() ? std::min(s->ls_pred[(size_t)h], O.lsMaxIter) : 1;
-        s->w3_post_next = last && kpred < 2;
-        launch_sg(s, O, 1, h, 1); launches++;
-        for (int tt = 2; tt <= kpred; tt++) { s->w3_post_next = last && tt == kpred; launch_sg(s, O, 1, h, tt); launches++; }
-        return;
-    }
     const bool fuse = s->route == Route::FUSED_TAILS;
     mark(0);
     if (parts & 1) {
@@ -2727,10 +2733,9 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
     mark(1);
     if (s->sch_words && s->bw_fused && !phases) {
         /* all levels in one launch, last block first: a block waits for its children's Schur records inside the kernel */
-        s->bw_epoch++;
-        if (s->bw_epoch == 0) s->bw_epoch = 1;
-        if (wide) hipLaunchKernelGGL(k_factor_all_w, dim3(T.Np), dim3(WT), s->lds_factor_w, st, T, D, O, s->sch_words, s->sch_rs, s->bw_epoch, h);
-        else hipLaunchKernelGGL(k_factor_all, dim3(T.Np), dim3(WAVE), s->lds_factor, st, T, D, O, s->sch_words, s->sch_rs, s->bw_epoch, h);
+        const unsigned bw_tag = next_tag(s->bw_epoch);
+        if (wide) hipLaunchKernelGGL(k_factor_all_w, dim3(T.Np), dim3(WT), s->lds_factor_w, st, T, D, O, s->sch_words, s->sch_rs, bw_tag, h);
+        else hipLaunchKernelGGL(k_factor_all, dim3(T.Np), dim3(WAVE), s->lds_factor, st, T, D, O, s->sch_words, s->sch_rs, bw_tag, h);
         launches++;
     } else
     for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
@@ -2742,12 +2747,11 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
     if (s->fw_words && s->fw_fused && !phases) {
         /* all levels below the root in one launch: a block waits for its parent's step inside the kernel */
         if (T.Np > 1) {
-            s->fw_epoch++;
-            if (s->fw_epoch == 0) s->fw_epoch = 1;
+            const unsigned fw_tag = next_tag(s->fw_epoch);
             const Fuse F = fuse ? next_fuse(s) : no_fuse();          /* with k_ls_begin as its tail */
             ls_begun = fuse;
-            if (wide) hipLaunchKernelGGL(k_forward_all_w, dim3(T.Np - 1), dim3(WT), s->lds_forward_w, st, T, D, s->fw_words, s->fw_epoch, h, F);
-            else hipLaunchKernelGGL(k_forward_all, dim3(T.Np - 1), dim3(WAVE), s->lds_forward, st, T, D, s->fw_words, s->fw_epoch, h, F);
+            if (wide) hipLaunchKernelGGL(k_forward_all_w, dim3(T.Np - 1), dim3(WT), s->lds_forward_w, st, T, D, s->fw_words, fw_tag, h, F);
+            else hipLaunchKernelGGL(k_forward_all, dim3(T.Np - 1), dim3(WAVE), s->lds_forward, st, T, D, s->fw_words, fw_tag, h, F);
             launches++;
         }
     } else
@@ -2761,13 +2765,15 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
     if (!ls_begun) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
     if (fuse) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
     else {
-        if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, 1, h, 1);
-        else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 1, h, 1);
-        else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 1, h, 1);
-        launches++;
+        launch_stage_sweep(s, 1, h, 1); launches++;
         hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, h, 1, 0); launches++;
     }
     mark(3);
+}
+
+void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts, bool phases, bool last) {
+    if (s->route == Route::THREE_LAUNCH) launch_w3_iteration(s, O, h, launches, parts, last);
+    else launch_phase_iteration(s, O, h, launches, parts, phases);
 }
 
 /* solution export in one piece: out = [x | u | lam | dlam | mu_x | mu_u] (x and mu_x without the phantom root
@@ -3828,7 +3834,7 @@ struct SolveCtx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     Route route = Route::PER_PHASE;  /* decided by the caller: route_of(s, o, false) for a solve on its own, batch_route for a member of a batch */
     SolveEnv env;
-    bool first_launch = true, prelaunched = false, phases = false, events = true;
+    bool phases = false, events = true;
     unsigned batch_seq = 0;          /* != 0: this solve's persistent launch is part of a batch launch the caller makes with this launch number */
 #ifdef TQ_HOSTPROF
     std::chrono::steady_clock::time_point hp0, hp1, hp2;
@@ -3837,36 +3843,33 @@ struct SolveCtx {
     SolveCtx(const SolveEnv &e, Route r) : route(r), env(e) {}
 };
 
-/* defer: the solve runs Route::SINGLE_WG as a member of a batch launch -- its launch is described there and made by the caller */
-int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer = nullptr) {
-#ifdef TQ_HOSTPROF
-    cx.hp0 = HP_NOW();
-#endif
+int grow_events(std::vector<hipEvent_t> &v, int n) {
+    while ((int)v.size() < n) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); v.push_back(ev); }
+    return TQGPU_OK;
+}
+
+/* solve_begin, every route: the options, the time records, the ring slot of the event pair, how the verdict will travel (w3_mirror),
+ * and the first event.  in_batch_launch: the solve's launch is made by the caller, on the lead's stream */
+int prepare_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, bool in_batch_launch) {
     HIP_TRY(hipSetDevice(s->device));
     s->export_valid = false;
-    Opts &O = cx.O;
-    if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    O.stamps = cx.env.stamps;
+    if (opts_from(o, cx.O) != TQGPU_OK) return TQGPU_EINVAL;
+    cx.O.stamps = cx.env.stamps;
 
     if (s->sharded && !s->comm) return fail(TQGPU_ECOMM, "sharded mirror without a communicator: use tqgpu_solve_virtual_ranks");
-    const Tree &T = s->T; const Data &D = s->D;
-    hipStream_t st = s->stream;
-    const int nxu = std::max(s->sum_nx, s->sum_nu);
 
     /* ls_log needs no reset: entry i is written by iteration i */
 
-    if (o->profile) {
-        while ((int)s->iter_ev.size() < o->maxIter + 1) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); s->iter_ev.push_back(ev); }
-    }
+    int rc;
+    if (o->profile && (rc = grow_events(s->iter_ev, o->maxIter + 1)) != TQGPU_OK) return rc;
     /* (the per-iteration / per-phase time records are all-NaN unless a profiled solve has written into them: not refilled per solve) */
     const size_t n_it = (size_t)std::max(o->maxIter, 1);
     if (s->times_dirty || s->iter_times.size() != n_it) s->iter_times.assign(n_it, NAN);
 
     s->route = cx.route;
-    const bool single = single_launch(cx.route), w3 = cx.route == Route::THREE_LAUNCH;
     cx.phases = o->profile >= 3;
     if (cx.phases) {
-        while ((int)s->phase_ev.size() < 4 * (o->maxIter + 1)) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); s->phase_ev.push_back(ev); }
+        if ((rc = grow_events(s->phase_ev, 4 * (o->maxIter + 1))) != TQGPU_OK) return rc;
         if (!s->sweep_ev0) { HIP_TRY(hipEventCreate(&s->sweep_ev0)); HIP_TRY(hipEventCreate(&s->sweep_ev1)); }
     }
     if (s->times_dirty || s->phase_times.size() != 3 * n_it) s->phase_times.assign(3 * n_it, NAN);
@@ -3879,16 +3882,20 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
      * start to verdict) anyway, so there the pair is optional */
     /* the three-launch family reports through the pinned result block as well (launches of k_sg / k_sgp post the control block and
      * their own clock: w3_mirror) */
-    s->w3_mirror = w3 && !o->profile && !cx.env.no_w3_mirror;
+    s->w3_mirror = cx.route == Route::THREE_LAUNCH && !o->profile && !cx.env.no_w3_mirror;
     s->w3_seen = false;
     if (s->w3_mirror) s->h_res->seq = 0;          /* (no launch of this mirror is in flight) */
-    cx.events = (s->ev_timing || (!single && !s->w3_mirror)) && !cx.batch_seq && !defer;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
+    cx.events = (s->ev_timing || (!single_launch(cx.route) && !s->w3_mirror)) && !cx.batch_seq && !in_batch_launch;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
     s->ring_ok[(size_t)cx.ring] = cx.events ? 1 : 0;
-    if (cx.events) HIP_TRY(hipEventRecord(cx.ev0, st));
-    /* the three-launch family with k_sgp: the first launch of the solve takes the starting duals and resets the control block itself */
-    const bool fresh = w3 && s->w3_sgp;
-    if (!single && !fresh) HIP_TRY(hipMemsetAsync(D.ctrl, 0, sizeof(Ctrl), st));     /* persistent path: reset by the launch's prologue */
+    if (cx.events) HIP_TRY(hipEventRecord(cx.ev0, s->stream));
+    return TQGPU_OK;
+}
+
+/* solve_begin, every route: what a first solve or changed data ask for, and the stage solver's step counters */
+int enqueue_setup(tqgpu_solver *s, SolveCtx &cx, const GItem *defer) {
+    const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     if (s->need_init && cx.route != Route::SINGLE_WG) {     /* g_persist recomputes the reciprocal weights itself; dense nodes never read theirs */
+        const int nxu = std::max(s->sum_nx, s->sum_nu);
         hipLaunchKernelGGL(k_init, dim3((nxu + 255) / 256), dim3(256), 0, st, s->sum_nx, s->sum_nu, D); cx.launches++;
         s->need_init = false;
         s->stream_pending = true;
@@ -3901,72 +3908,160 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
         s->need_dense_init = false;
         if (defer) s->stream_pending = true;      /* the batch launch on the lead's stream waits for it (join_lead_stream): first solves and changed data only */
     }
-    if (!single) {
-        /* the current buffer is lam0 at the start of every solve */
-        if (!fresh) HIP_TRY(hipMemcpyAsync(D.lam0, s->d_lam_init, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, st));
-        /* first sweep at lambda0 (phase S of iteration 0 + fval0); the persistent launch does it as its prologue */
-        if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev0, st));
-        if (w3) { launch_sg(s, cx.O, 0, 0, 0, fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
-        else if (cx.route == Route::FUSED_TAILS) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
-        else {
-            if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, 0, 0, 0);
-            else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, 0, 0, 0);
-            else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, 0, 0, 0);
-            cx.launches++;
-            hipLaunchKernelGGL(k_fval_init, dim3(1), dim3(256), 0, st, T, D); cx.launches++;
-        }
-        if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev1, st));
+    return TQGPU_OK;
+}
+
+/* TIERED, THREE_LAUNCH, FUSED_TAILS, PER_PHASE: control block, starting duals and the first sweep; solve_end enqueues the iterations */
+int begin_enqueued(tqgpu_solver *s, SolveCtx &cx) {
+    const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
+    const bool w3 = cx.route == Route::THREE_LAUNCH;
+    /* the three-launch family with k_sgp: the first launch of the solve takes the starting duals and resets the control block itself */
+    const bool fresh = w3 && s->w3_sgp;
+    if (!fresh) HIP_TRY(hipMemsetAsync(D.ctrl, 0, sizeof(Ctrl), st));     /* persistent path: reset by the launch's prologue */
+    int rc = enqueue_setup(s, cx, nullptr);
+    if (rc != TQGPU_OK) return rc;
+    /* the current buffer is lam0 at the start of every solve */
+    if (!fresh) HIP_TRY(hipMemcpyAsync(D.lam0, s->d_lam_init, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, st));
+    /* first sweep at lambda0 (phase S of iteration 0 + fval0); the persistent launch does it as its prologue */
+    if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev0, st));
+    if (w3) { launch_sg(s, cx.O, 0, 0, 0, fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
+    else if (cx.route == Route::FUSED_TAILS) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
+    else {
+        launch_stage_sweep(s, 0, 0, 0); cx.launches++;
+        hipLaunchKernelGGL(k_fval_init, dim3(1), dim3(256), 0, st, T, D); cx.launches++;
+    }
+    if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev1, st));
+    return TQGPU_OK;
+}
+
+/* the parameters of this mirror's single-workgroup launch: g_persist with the plan of setup_single_wg, or, on a dense tree,
+ * g_persist_dense with the plan of plan_dense_single (deferred: the same parameters for this member's workgroup of the batch launch) */
+GParams gparams_of(const tqgpu_solver *s) {
+    GParams gp;
+    gp.lvl_first = s->d_lvl_first; gp.lam_init = s->d_lam_init; gp.hres = s->h_res; gp.seq = s->psync.seq; gp.lds_wave = (int)s->lds_gp_wave;
+    gp.sum_nx = s->sum_nx; gp.sum_nu = s->sum_nu; gp.sum_W = s->sum_W; gp.sum_Ut = s->sum_Ut; gp.sum_A = s->sum_A; gp.sum_B = s->sum_B;
+    gp.small8 = s->gp_small8 ? 1 : 0;
+    if (!s->dense) {
+        gp.in_lds = s->gp_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gp_in_lds && s->gp_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gp_const_in_lds ? 1 : 0;
+        gp.small16 = s->gp_small16 ? 1 : 0;
+        gp.stage_waves = 0; gp.win_stage = 0; gp.win_region = 0; gp.phase_waves = 0;
     } else {
+        gp.in_lds = s->gpd_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd_in_lds && s->gpd_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd_const_in_lds ? 1 : 0;
+        gp.small16 = 0;
+        gp.stage_waves = s->dense_stage_waves; gp.phase_waves = s->dense_phase_waves; gp.win_stage = (int)s->dense_win_stage; gp.win_region = (int)s->dense_win_region;
+    }
+    return gp;
+}
+
+/* SINGLE_WG: the whole solve as one launch of one workgroup, g_persist or g_persist_dense; defer: described there for the caller's batch
+ * launch instead.  No wipe when the launch number wraps, unlike launch_persist: one workgroup hands nothing over through sync_slab, and
+ * every word of the result block, the only thing the number tags here, is rewritten by every launch */
+int begin_single_wg(tqgpu_solver *s, SolveCtx &cx, GItem *defer) {
+    (void)step_launch_no(s);
+    s->psync.seq = s->launch_no << 16;
+    const GParams gp = gparams_of(s);
+    if (defer) { defer->T = s->T; defer->D = s->D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
+    else if (s->dense) hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->lds_gpd_total, s->stream, s->T, s->D, cx.O, gp);
+    else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->lds_gp_total, s->stream, s->T, s->D, cx.O, gp);
+    cx.launches++;          /* (also the caller's) */
+    return TQGPU_OK;
+}
+
+/* PERSIST: the launch with its prologue, or its share of the caller's batch launch (batch_seq) */
+int begin_persist(tqgpu_solver *s, SolveCtx &cx) { return launch_persist(s, cx.O, cx.launches, 1, cx.batch_seq); }
+
+/* defer: the solve runs Route::SINGLE_WG as a member of a batch launch -- its launch is described there and made by the caller */
+int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer = nullptr) {
 #ifdef TQ_HOSTPROF
-        cx.hp1 = HP_NOW();
+    cx.hp0 = HP_NOW();
 #endif
-        int rcx = TQGPU_OK;
-        if (cx.route == Route::SINGLE_WG) {
-            s->launch_no = (s->launch_no + 1) & 0xFFFFu;
-            if (s->launch_no == 0) s->launch_no = 1;
-            s->psync.seq = s->launch_no << 16;
-            GParams gp;
-            gp.lvl_first = s->d_lvl_first; gp.lam_init = s->d_lam_init; gp.hres = s->h_res; gp.seq = s->psync.seq; gp.lds_wave = (int)s->lds_gp_wave;
-            gp.in_lds = s->gp_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gp_in_lds && s->gp_tab_in_lds) ? 1 : 0; gp.small16 = s->gp_small16 ? 1 : 0; gp.small8 = s->gp_small8 ? 1 : 0; gp.sum_nx = s->sum_nx; gp.sum_nu = s->sum_nu; gp.sum_W = s->sum_W; gp.sum_Ut = s->sum_Ut;
-            gp.const_in_lds = s->gp_const_in_lds ? 1 : 0; gp.sum_A = s->sum_A; gp.sum_B = s->sum_B;
-            gp.stage_waves = 0; gp.win_stage = 0; gp.win_region = 0; gp.phase_waves = 0;
-            if (s->dense) {
-                /* g_persist_dense with the plan of plan_dense_single; deferred: the same parameters for this member's workgroup of g_persist_dense_batch */
-                gp.in_lds = s->gpd_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd_in_lds && s->gpd_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd_const_in_lds ? 1 : 0;
-                gp.small16 = 0; gp.small8 = s->gp_small8 ? 1 : 0;
-                gp.stage_waves = s->dense_stage_waves; gp.phase_waves = s->dense_phase_waves; gp.win_stage = (int)s->dense_win_stage; gp.win_region = (int)s->dense_win_region;
-                if (defer) { defer->T = T; defer->D = D; defer->G = gp; }
-                else hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->lds_gpd_total, st, T, D, O, gp);
-            }
-            else if (defer) { defer->T = T; defer->D = D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
-            else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->lds_gp_total, st, T, D, O, gp);
-            cx.launches++;
-        } else rcx = launch_persist(s, O, cx.launches, 1, cx.batch_seq);
-        if (rcx != TQGPU_OK) return rcx;
-        cx.first_launch = false; cx.prelaunched = true;
-        /* the launch normally ends the solve: close the timing here */
-        if (cx.events) HIP_TRY(hipEventRecord(cx.ev1, st));
+    int rc = prepare_solve(s, o, cx, defer != nullptr);
+    if (rc != TQGPU_OK) return rc;
+    if (!single_launch(cx.route)) return begin_enqueued(s, cx);
+    if ((rc = enqueue_setup(s, cx, defer)) != TQGPU_OK) return rc;
 #ifdef TQ_HOSTPROF
-        cx.hp2 = HP_NOW();
+    cx.hp1 = HP_NOW();
 #endif
+    rc = cx.route == Route::SINGLE_WG ? begin_single_wg(s, cx, defer) : begin_persist(s, cx);
+    if (rc != TQGPU_OK) return rc;
+    /* the launch normally ends the solve: close the timing here */
+    if (cx.events) HIP_TRY(hipEventRecord(cx.ev1, s->stream));
+#ifdef TQ_HOSTPROF
+    cx.hp2 = HP_NOW();
+#endif
+    return TQGPU_OK;
+}
+
+/* the line search of iteration h_ctrl->iter wants more trials than were enqueued: batches of them, a read-back after each, until it
+ * is decided.  `any`: at least one trial went out */
+int run_extra_trials(tqgpu_solver *s, const Opts &O, Route trials, int &launches, bool &any) {
+    /* trials beyond the first go out in batches: 3, then 6, 12, 16, .. per read-back of the control block.  A trial that is
+     * accepted turns the rest of its batch into no-ops (~6 us each), so short searches -- the usual case: one or two more
+     * trials -- want small batches (one C5-class tree: 1.09 ms with batches of 8, 0.99 ms with 3), long ones few read-backs. */
+    const int trial_batch0 = process_switches().trial_batch;
+    int trial_batch = trial_batch0, ls_of = -1;
+    any = false;
+    while (!s->h_ctrl->done && s->h_ctrl->ls_pending) {
+        any = true;
+        /* the line search of iteration `iter` wants more trials: a batch of them */
+        const int it = s->h_ctrl->iter, t0 = s->h_ctrl->ls_iter;
+        if (it != ls_of) { ls_of = it; trial_batch = trial_batch0; }
+        for (int t = t0; t < t0 + trial_batch && t <= O.lsMaxIter; t++) {
+            s->w3_post_next = t + 1 >= t0 + trial_batch || t + 1 > O.lsMaxIter;      /* the last of the batch */
+            int rcx = launch_trial(s, O, trials, it, t, launches);
+            if (rcx != TQGPU_OK) return rcx;
+        }
+        trial_batch = std::min(2 * trial_batch, 16);
+        int rc = read_ctrl(s);
+        if (rc != TQGPU_OK) return rc;
     }
     return TQGPU_OK;
 }
 
-int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *res) {
-    HIP_TRY(hipSetDevice(s->device));
+/* solve_end of PERSIST and SINGLE_WG: solve_begin made the launch; the verdict comes through the result block in pinned host memory.
+ * (route_of gives these routes only with profile == 0 and maxIter > 0: no iteration events, no empty solve.)
+ * tail_done: that one launch was the whole solve */
+int end_single_launch(tqgpu_solver *s, SolveCtx &cx, bool &tail_done) {
+    const Route route = cx.route;
+    /* (a persistent launch that ends inside a line search leaves its further trials to the tiered kernels, where the tree has them) */
+    const Route trials = route == Route::PERSIST && tiered_capable(s) ? Route::TIERED : route;
+    for (bool relaunch = false;; relaunch = true) {
+        if (relaunch) {
+            if (route == Route::SINGLE_WG) return fail(TQGPU_ENODEVICE, "single-workgroup persistent kernel ended without a verdict");
+            int rcx = launch_persist(s, cx.O, cx.launches, 0);          /* no prologue: the state is in global memory */
+            if (rcx != TQGPU_OK) return rcx;
+            if (cx.events) HIP_TRY(hipEventRecord(cx.ev1, s->stream));
+        }
+        int rc = wait_result_block(s);
+        if (rc != TQGPU_OK) return rc;
+#ifdef TQ_HOSTPROF
+        { auto hp3 = HP_NOW(); hp_acc[0] += HP_US(cx.hp0, cx.hp1); hp_acc[1] += HP_US(cx.hp1, cx.hp2); hp_acc[2] += HP_US(cx.hp2, hp3); hp_n++;
+          if (hp_n % 200 == 0) { fprintf(stderr, "[hostprof] pre %.2f us, launch %.2f us, readback+sync %.2f us (avg of %ld)\n", hp_acc[0] / hp_n, hp_acc[1] / hp_n, hp_acc[2] / hp_n, hp_n); } }
+#endif
+        bool extra_trials = false;
+        if ((rc = run_extra_trials(s, cx.O, trials, cx.launches, extra_trials)) != TQGPU_OK) return rc;
+        tail_done = !extra_trials;
+        if (s->h_ctrl->done) return TQGPU_OK;
+        tail_done = false;
+        if (route == Route::PERSIST) {
+            unsigned tmo = 0;
+            HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
+            if (tmo) return fail(TQGPU_ETIMEOUT, "persistent solve kernel: a bounded inter-workgroup wait timed out");
+        }
+    }
+}
+
+/* solve_end of TIERED, THREE_LAUNCH, FUSED_TAILS and PER_PHASE.  host_iter: iterations whose event was recorded */
+int end_enqueued(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, int &host_iter) {
     const Opts &O = cx.O;
     hipStream_t st = s->stream;
     const Route route = cx.route;
-    const bool single = single_launch(route), generic = !single && route != Route::TIERED;      /* generic: launch_generic_iteration */
-    /* (a persistent launch that ends inside a line search leaves its further trials to the tiered kernels, where the tree has them) */
-    const Route trials = route == Route::PERSIST && tiered_capable(s) ? Route::TIERED : route;
+    const bool generic = route != Route::TIERED;      /* generic: launch_generic_iteration */
     int &launches = cx.launches;
     /* Newton loop (dual_Newton_tree.c:1166-1228).  The device decides (termination, Armijo);
      * the host enqueues `chunk` tagged iterations ahead and reads the control block once per chunk.
      * Iterations enqueued beyond convergence, or while a line search still needs trials, are
      * no-ops by their phase guards. */
-    bool tail_done = false;
     int h = 0, ev_idx = 0;
     bool finished = o->maxIter <= 0;       /* nothing to iterate: reported as "maximum iterations" */
     if (finished) { HIP_TRY(hipStreamSynchronize(st)); memset(s->h_ctrl, 0, sizeof(Ctrl)); s->h_ctrl->status = 1; }
@@ -3981,17 +4076,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     if (cx.phases) { chunk = 1; predicted = false; }            /* phase timing: one iteration per read-back, so that every recorded event belongs to work that ran */
     int rest_due = -1;                                          /* iteration whose termination test ran, whose step did not */
     while (!finished) {
-        const int n = single ? 0 : std::min(chunk, o->maxIter - h);
-        if (single) {
-            if (!cx.prelaunched) {
-                if (route == Route::SINGLE_WG) return fail(TQGPU_ENODEVICE, "single-workgroup persistent kernel ended without a verdict");
-                int rcx = launch_persist(s, O, launches, cx.first_launch ? 1 : 0);
-                if (rcx != TQGPU_OK) return rcx;
-                cx.first_launch = false;
-                if (cx.events) HIP_TRY(hipEventRecord(cx.ev1, st));
-            }
-            cx.prelaunched = false;
-        }
+        const int n = std::min(chunk, o->maxIter - h);
         int deferred = -1;
         for (int i = 0; i < n; i++) {
             if (route == Route::TIERED) { int rcx = launch_fast_iteration(s, O, h + i, launches); if (rcx != TQGPU_OK) return rcx; }
@@ -4005,34 +4090,10 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
             }
             if (o->profile && ev_idx + 1 < (int)s->iter_ev.size()) HIP_TRY(hipEventRecord(s->iter_ev[++ev_idx], st));
         }
-        /* persistent path: the verdict comes through the result block in pinned host memory */
-        int rc = single ? wait_result_block(s) : read_ctrl(s);
+        int rc = read_ctrl(s);
         if (rc != TQGPU_OK) return rc;
-#ifdef TQ_HOSTPROF
-        if (single) { auto hp3 = HP_NOW(); hp_acc[0] += HP_US(cx.hp0, cx.hp1); hp_acc[1] += HP_US(cx.hp1, cx.hp2); hp_acc[2] += HP_US(cx.hp2, hp3); hp_n++;
-          if (hp_n % 200 == 0) { fprintf(stderr, "[hostprof] pre %.2f us, launch %.2f us, readback+sync %.2f us (avg of %ld)\n", hp_acc[0] / hp_n, hp_acc[1] / hp_n, hp_acc[2] / hp_n, hp_n); } }
-#endif
-        tail_done = single;
         bool extra_trials = false;
-        /* trials beyond the first go out in batches: 3, then 6, 12, 16, .. per read-back of the control block.  A trial that is
-         * accepted turns the rest of its batch into no-ops (~6 us each), so short searches -- the usual case: one or two more
-         * trials -- want small batches (one C5-class tree: 1.09 ms with batches of 8, 0.99 ms with 3), long ones few read-backs. */
-        const int trial_batch0 = process_switches().trial_batch;
-        int trial_batch = trial_batch0, ls_of = -1;
-        while (!s->h_ctrl->done && s->h_ctrl->ls_pending) {
-            tail_done = false;
-            extra_trials = true;
-            /* the line search of iteration `iter` wants more trials: a batch of them */
-            const int it = s->h_ctrl->iter, t0 = s->h_ctrl->ls_iter;
-            if (it != ls_of) { ls_of = it; trial_batch = trial_batch0; }
-            for (int t = t0; t < t0 + trial_batch && t <= O.lsMaxIter; t++) {
-                s->w3_post_next = t + 1 >= t0 + trial_batch || t + 1 > O.lsMaxIter;      /* the last of the batch */
-                int rcx = launch_trial(s, O, trials, it, t, launches);
-                if (rcx != TQGPU_OK) return rcx;
-            }
-            trial_batch = std::min(2 * trial_batch, 16);
-            if ((rc = read_ctrl(s)) != TQGPU_OK) return rc;
-        }
+        if ((rc = run_extra_trials(s, O, route, launches, extra_trials)) != TQGPU_OK) return rc;
         h = s->h_ctrl->iter;
         finished = s->h_ctrl->done != 0;
         chunk = cx.phases ? 1 : s->chunk;
@@ -4041,16 +4102,16 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
          * line search needed further trials (enqueued above, after the read-back), the test found the search pending and did nothing --
          * it is then due again with the rest of its iteration */
         rest_due = (!finished && deferred == h && !extra_trials) ? h : -1;
-        if (route == Route::PERSIST && !finished) {
-            tail_done = false;
-            unsigned tmo = 0;
-            HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
-            if (tmo) return fail(TQGPU_ETIMEOUT, "persistent solve kernel: a bounded inter-workgroup wait timed out");
-        }
     }
-    const int host_iter = ev_idx;
-    float ms = 0.f;
-    if (!tail_done && route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_seen && !cx.events && !o->profile && !cx.phases) {
+    host_iter = ev_idx;
+    return TQGPU_OK;
+}
+
+/* the device time of the solve [ms], by what is known without waiting: the three-launch mirror's clock, the event pair or the last
+ * launch's clock (these two wait for the stream), the single launch's clock */
+int solve_device_ms(tqgpu_solver *s, const tqgpu_opts *o, const SolveCtx &cx, bool tail_done, float &ms) {
+    hipStream_t st = s->stream;
+    if (!tail_done && cx.route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_seen && !cx.events && !o->profile && !cx.phases) {
         /* three-launch family: every launch of the solve is accounted for (the last one's tail has posted the verdict; what its other
          * workgroups still write is stream-ordered before anything the host does next): no synchronisation, the device's own clock */
         unsigned long long t_first;
@@ -4066,6 +4127,15 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
          * solve can be read later through tqgpu_get_device_times, which synchronises) */
         ms = 1e-5f * (float)(s->h_res->t_end - s->h_res->t_start);
     }
+    return TQGPU_OK;
+}
+
+/* solve_end, every route: device time, the time records of a profiled solve, the result, and what the next solve of this mirror predicts from */
+int finish_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *res, bool tail_done, int host_iter) {
+    hipStream_t st = s->stream;
+    float ms = 0.f;
+    int rc = solve_device_ms(s, o, cx, tail_done, ms);
+    if (rc != TQGPU_OK) return rc;
     hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(TQGPU_ENODEVICE, std::string("kernel launch failed: ") + hipGetErrorString(le));
 
@@ -4084,19 +4154,19 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
     }
     const Ctrl &c = *s->h_ctrl;
     res->status = c.status; res->iter = c.iter; res->ls_total = c.ls_total; res->ls_last = c.ls_last;
-    res->n_launches = launches; res->device_time = 1e-3 * ms; res->last_error_norm = c.err; res->last_fval = c.fval;
+    res->n_launches = cx.launches; res->device_time = 1e-3 * ms; res->last_error_norm = c.err; res->last_fval = c.fval;
     s->last_iter = c.iter;
     s->last_ls_extra = c.ls_total > c.iter ? 1 : 0;
-    if (route == Route::THREE_LAUNCH && s->w3_merge && c.status == 2 && s->T.Np > 1) {
+    if (cx.route == Route::THREE_LAUNCH && s->w3_merge && c.status == 2 && s->T.Np > 1) {
         /* NOT_DESCENT_DIRECTION out of the merged launch (k_sgp mode 2: forward sweep + first trial): the trial sweep ran before the
          * direction test and has put x, u, xUnc, QinvCal of the point lambda + dlambda in place.  The reference returns from
          * line_search with the phase-S iterate at lambda (dual_Newton_tree.c:944-954): one stage sweep at the current duals (which the
          * trial did not touch: it wrote the other buffer) restores exactly that -- same arithmetic, operation for operation. */
         hipLaunchKernelGGL(k_stage, dim3(s->T.Nn), dim3(WAVE), s->lds_stage, st, s->T, s->D, 0, 0, 0);
-        launches++; res->n_launches = launches;
+        res->n_launches = ++cx.launches;
         s->stream_pending = true;
     }
-    if (route == Route::THREE_LAUNCH) {
+    if (cx.route == Route::THREE_LAUNCH) {
         s->ls_pred.clear();
         if (c.status == 0 && c.ls_total > c.iter) {
             /* some iteration needed further trials: fetch the trial counts (only then: a copy is a packet on the queue and a synchronisation) */
@@ -4107,6 +4177,15 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
         }
     }
     return TQGPU_OK;
+}
+
+int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *res) {
+    HIP_TRY(hipSetDevice(s->device));
+    bool tail_done = false;
+    int host_iter = 0;
+    const int rc = single_launch(cx.route) ? end_single_launch(s, cx, tail_done) : end_enqueued(s, o, cx, host_iter);
+    if (rc != TQGPU_OK) return rc;
+    return finish_solve(s, o, cx, res, tail_done, host_iter);
 }
 
 }  // namespace
@@ -4157,7 +4236,7 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
      * persistent launch now, while it runs, instead of after its verdict has travelled to the host and back (a launch latency, the
      * launch's write-back tail and a synchronisation off the caller's critical path); which dual buffer is current is the device's
      * knowledge.  Valid if that one launch was the whole solve. */
-    const bool ahead = s->export_ahead && single_launch(cx.route) && cx.prelaunched && !s->pshard && !s->sharded;
+    const bool ahead = s->export_ahead && single_launch(cx.route) && !s->pshard && !s->sharded;          /* (solve_begin has made the launch) */
     if (ahead && enqueue_export(s, nullptr) != TQGPU_OK) return TQGPU_ENODEVICE;
     rc = solve_end(s, o, cx, res);
     if (rc == TQGPU_ETIMEOUT) rc = solve_after_timeout(s, o, cx.env, res);
@@ -4855,7 +4934,7 @@ extern "C" int tqgpu_pshard_begin(tqgpu_solver *s, const tqgpu_opts *o) {
     if (o->profile || o->maxIter <= 0 || o->checkLastActiveSet == 2) return fail(TQGPU_EUNSUPPORTED, "sharded persistent solve: default solve options only (no profiling, no factor keeping)");
     Opts O;
     if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    if (((s->launch_no + 1) & 0xFFFFu) == 0)
+    if (launch_no_after(s->launch_no) == 0)
         return fail(TQGPU_EUNSUPPORTED, "65535 sharded solves since the launch numbers were last reset: call tqgpu_pshard_rewind on every rank, between two barriers of the caller's "
                                         "(the 16-bit launch number tags the hand-over words; a single device wipes its slab when it wraps, ranks that write into each other's slabs cannot do that on their own)");
     memset(s->h_res, 0, sizeof(HostRes));
