@@ -235,14 +235,9 @@ def flat_xu(st):
     return x, u, sx, su
 
 
-def newton_step(d, lam0, dense=False, kinds=None, reg=0.0):
-    """The step of the dual Newton method at lam0 (concatenation of lambda_1 .. lambda_{Nn-1}).  kinds: per-node stage solver (0
-    clipping on the diagonals of Q, R; 1 dense unconstrained; 2 dense with box bounds), H_k then from the blocks Q, R, S; None:
-    all clipping on Qd, Rd (dense=False) or all dense unconstrained (dense=True).  Returns dict(dlam, res, cond, margin, cert,
-    stages): margin is the smallest, over the entries whose bounds differ, of the distance of an unclipped stage value to a
-    clipping threshold (clipping nodes), of the distance of a free entry to either bound and of |g_i| of a fixed entry (box
-    nodes); inf on dense unconstrained trees.  stages is what stage_solutions returns.  reg > 0 adds reg I to M (the solver's
-    regType = 1); the device pins use reg = 0."""
+def assemble(d, lam0, dense=False, kinds=None):
+    """The Newton system at lam0, in longdouble: (M, res, stages) with M = G P G' the negated dual Hessian, res the dynamics
+    residual and stages what stage_solutions returns (its "tree" holds the offsets of the duals)."""
     st = stage_solutions(d, lam0, dense, kinds)
     nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, _ = st["tree"]
     z, Pm = st["z"], st["P"]
@@ -264,6 +259,19 @@ def newton_step(d, lam0, dense=False, kinds=None, reg=0.0):
             blk = -CP[:, :nx[p]]
             M[ik, ip] += blk
             M[ip, ik] += blk.T
+    return M, res, st
+
+
+def newton_step(d, lam0, dense=False, kinds=None, reg=0.0):
+    """The step of the dual Newton method at lam0 (concatenation of lambda_1 .. lambda_{Nn-1}).  kinds: per-node stage solver (0
+    clipping on the diagonals of Q, R; 1 dense unconstrained; 2 dense with box bounds), H_k then from the blocks Q, R, S; None:
+    all clipping on Qd, Rd (dense=False) or all dense unconstrained (dense=True).  Returns dict(dlam, res, cond, margin, cert,
+    stages): margin is the smallest, over the entries whose bounds differ, of the distance of an unclipped stage value to a
+    clipping threshold (clipping nodes), of the distance of a free entry to either bound and of |g_i| of a fixed entry (box
+    nodes); inf on dense unconstrained trees.  stages is what stage_solutions returns.  reg > 0 adds reg I to M (the solver's
+    regType = 1); the device pins of the unregularised step use reg = 0 (reg_ref.py has the block-wise regularisation)."""
+    M, res, st = assemble(d, lam0, dense, kinds)
+    n = len(res)
     if reg:
         M = M + LD(reg) * np.eye(n, dtype=LD)
     M64 = M.astype(np.float64)

@@ -274,8 +274,10 @@ def test_wide_block_kernels_regularisation(gpu, orc, reg):
 def test_three_launch_family_matches_oracle_and_launch_per_phase(gpu, orc, reg):
     """k_sgp / k_hf_w / k_fwd3 (stage + gradient + tails; H + backward sweep + forward preparation; forward sweep + tail) against the
     oracle and against the launch-per-phase kernels they stand in for (TREEQP_AMD_NO_WIDE3=1), on bounded problems with d = 24
-    blocks, variable numbers of children, several Newton iterations and line-search trials, under every regularisation mode
-    (on-the-fly with a tolerance that makes blocks refactorise).  Same verdict, iteration and trial counts; 3 launches per
+    blocks, variable numbers of children, several Newton iterations and line-search trials, under every regularisation mode.
+    (On these two problems on-the-fly regularisation shifts no block, at regTol = 1e-3 as little as at 1e-6: the oracle reports
+    n_regularized = 0.  The shift-and-refactorise branch of k_hf_w and of the launch-per-phase kernels is pinned by the wide3-* and
+    wide-* rows of test_gpu_reg_step.py.)  Same verdict, iteration and trial counts; 3 launches per
     iteration + 1 instead of 11."""
     extra_trials = 0
     for f in (P.pruned_chain_qp(), P.pruned_chain_qp(Nh=6, seed=5)):
