@@ -7,12 +7,17 @@ ls_last), the launches it made (n_launches), the tqgpu_debug_plan flags, the rou
 order of route_of in tdunes_device.hip), and the stage solver's step counts where the tree has general constraints.  Solutions are not part
 of the record: the default reductions are not order-fixed, and the parity tests bound them.
 
+The sharded cases (one tree over several ranks: virtual ranks, a one-rank RCCL communicator, the sharded persistent launch) record the
+verdict, the counts and n_launches per mirror, and sha256 digests of the raw bytes of x, u and lam after the gather: these paths are
+launches on ordered streams, and the sharded persistent solution is bit-identical to the single-device one.
+
 Every problem comes from code the suite already has (limit_shapes, box_cases, gen_cases, treeqp_amd.problems)."""
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
 import functools
+import hashlib
 import os
 
 import numpy as np
@@ -107,9 +112,9 @@ LEVELS = {"TREEQP_AMD_FWD": "levels", "TREEQP_AMD_BWD": "levels"}
 PER_PHASE_ONLY = {**GENERIC, "TREEQP_AMD_NO_WIDE3": "1", "TREEQP_AMD_NO_FUSE": "1"}
 
 
-def _case(cid, route, *makes, env=None, opts=None, batch=False, profile=0, logs=False, export_ahead=False, backtracks=False):
+def _case(cid, route, *makes, env=None, opts=None, batch=False, profile=0, logs=False, export_ahead=False, backtracks=False, shard=None):
     return dict(id=cid, route=route, makes=makes, env=env or {}, opts=opts or {}, batch=batch, profile=profile, logs=logs,
-                export_ahead=export_ahead, backtracks=backtracks)
+                export_ahead=export_ahead, backtracks=backtracks, shard=shard)
 
 
 def _cases():
@@ -157,6 +162,17 @@ def _cases():
             _case(f"{name}-profile3", None, make, env=env, profile=3, logs=logs),
         ]
     out.append(_case("single_wg-export_ahead", "SINGLE_WG", CLIP_WG, export_ahead=True))
+    # one tree over several ranks (shard = (transport, ranks)): the smallest trees test_gpu_parity.py and test_gpu_pshard.py shard
+    chain127 = _lti(lambda: P.linear_chain(2, 6, 6))
+    out += [
+        _case("shard-virtual-n2", None, chain127, shard=("virtual", 2)),
+        _case("shard-virtual-n8", None, chain127, shard=("virtual", 8)),
+        # the random start of test_sharded_virtual_ranks_backtracking: further trials, so launch_trial_phase and exchange 2 in the trial loop
+        _case("shard-virtual-n4-backtracking", None, _lti(lambda: P.linear_chain(2, 6, 6, ubound=0.1), far=(2, 10.0)), shard=("virtual", 4), backtracks=True),
+        # solve and gather after a shard_init with a fresh id, the same after a second shard_init with another id, then once more warm
+        _case("shard-rccl-one_rank", None, chain127, shard=("rccl", 1)),
+        _case("pshard-local-n2", None, _lti(lambda: P.linear_chain(2, 6, 6, ubound=0.05)), shard=("pshard", 2)),
+    ]
     return out
 
 
@@ -215,8 +231,46 @@ def _record(capi, c, g, r):
     return rec
 
 
+def _shard_record(g, r):
+    sol = g.solution()
+    rec = {k: int(r[k]) for k in ("status", "iter", "ls_total", "ls_last", "n_launches")}
+    rec.update({f"sha256_{k}": hashlib.sha256(np.ascontiguousarray(sol[k]).tobytes()).hexdigest() for k in ("x", "u", "lam")})
+    return rec
+
+
+def _run_sharded(capi, c):
+    kind, n = c["shard"]
+    ms = [c["makes"][0](capi) for _ in range(n)]
+    try:
+        for r, g in enumerate(ms):
+            if kind == "virtual":
+                g.shard_init(r, n)
+            elif kind == "pshard":
+                g.pshard_init(r, n)
+        out = []
+        for i in range(SOLVES):
+            if kind == "virtual":
+                res = [capi.solve_virtual_ranks(ms, **c["opts"])] * n          # one verdict for all ranks; every rank ends with the solution
+            elif kind == "pshard":
+                res = capi.pshard_solve_local(ms, **c["opts"])
+            else:
+                if i < 2:
+                    ms[0].shard_init(0, 1, capi.shard_unique_id())             # (the second communicator replaces the first)
+                    assert ms[0].path == 1, (c["id"], "a sharded mirror runs the launch-per-tier kernels")
+                res = [ms[0].solve(**c["opts"])]
+                ms[0].shard_gather_solution()
+            out.append([_shard_record(g, r) for g, r in zip(ms, res)])
+    finally:
+        for g in ms:
+            g.close()
+    return out
+
+
 def run_case(capi, c):
     """-> [solve 0, solve 1, solve 2], each a list of one record per mirror"""
+    if c["shard"]:
+        with switches(c["env"]):
+            return _run_sharded(capi, c)
     with switches(c["env"]):
         ms = [make(capi) for make in c["makes"]]
         try:

@@ -1,7 +1,9 @@
 """What every route of a solve enqueues, against tests/golden/solve_sequence_pins.json (recorded by tools/make_solve_pins.py on the
 device, before the host side of the solve was split by route): three consecutive solves -- cold, warm, warm -- on fresh mirrors per
 case of solve_sequence_cases.py, equal to the record field for field: verdict, iterations, trials, launches, plan flags, route, the
-stage solver's step counts, and the number of finite entries of the iteration and phase logs where the case profiles.
+stage solver's step counts, and the number of finite entries of the iteration and phase logs where the case profiles.  The sharded
+cases (virtual ranks, one-rank RCCL, sharded persistent launch; recorded before the multi-rank host code was folded onto shared
+helpers) compare verdict, counts, launches and sha256 digests of the gathered x, u and lam per mirror.
 
 A case listed under "unstable" in the fixture gave differing records on the build it was recorded on; it is skipped here."""
 from __future__ import annotations

@@ -3,7 +3,7 @@
 The host side of a solve (solve_begin / solve_end and the launch functions of tdunes_device.hip) decides which launches go out, how many
 iterations are enqueued ahead of a read-back, how line-search trials are batched and predicted.  None of that shows in a solution; it
 shows in n_launches, in the counts, and in the plan flags.  This script records them for the cases of tests/solve_sequence_cases.py --
-three consecutive solves, cold / warm / warm, on fresh mirrors -- on the build it is run on.  test_gpu_solve_sequence.py replays the
+three consecutive solves, cold / warm / warm, on fresh mirrors, the sharded modes among them -- on the build it is run on.  test_gpu_solve_sequence.py replays the
 cases and asserts equality field for field, so the fixture is recorded BEFORE a change of the host side that is to preserve behaviour,
 and re-recorded only by a change that means to alter what is enqueued.
 

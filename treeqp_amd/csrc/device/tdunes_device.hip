@@ -2157,6 +2157,26 @@ void fast_geometry(int idx, int &TH, size_t &tier_lds, size_t &stage_lds) {
 }
 
 
+/* level `level` of a uniform tree with MD children per parent: the index of its first node, and its width */
+int uni_first(int MD, int level) { int n = 0, w = 1; for (int l = 0; l < level; l++) { n += w; w *= MD; } return n; }
+int uni_width(int MD, int level) { int w = 1; for (int l = 0; l < level; l++) w *= MD; return w; }
+
+/* the branching part of a uniform tree: block levels 0 .. top-1 grouped bottom-up into tiers of TH levels, the top tier takes the rest;
+ * the grid of a tier is the width of its first level */
+struct UniTier { int l0, l1, grid; };
+std::vector<UniTier> uni_tiers(int top, int TH, int MD) {
+    std::vector<UniTier> out;
+    for (int l1 = top; l1 > 0;) {
+        const int l0 = std::max(0, l1 - TH);
+        out.push_back({l0, l1, uni_width(MD, l0)});
+        l1 = l0;
+    }
+    return out;
+}
+void add_tier(tqgpu_solver *s, int l0, int l1, int grid, int chain) {
+    s->tier_l0.push_back(l0); s->tier_l1.push_back(l1); s->tier_grid.push_back(grid); s->tier_chain.push_back(chain);
+}
+
 /* multistage tree?  (setup_multistage_tree(md, Nr, Nh) with 1 <= Nr < Nh: every node above stage Nr has md
  * children, every parent from stage Nr on has one; uniform nx, nu) */
 void detect_multistage(tqgpu_solver *s) {
@@ -2181,8 +2201,7 @@ void detect_multistage(tqgpu_solver *s) {
     MSTAGE_TABLE(X)
 #undef X
     if (idx < 0) return;
-    int S = 1;
-    for (int l = 0; l < Nr; l++) S *= MD;
+    const int S = uni_width(MD, Nr);
     s->fast = idx; s->fNX = NX; s->fNU = NU; s->fMD = MD;
     s->mstage = true; s->ms_Nr = Nr; s->ms_S = S; s->ms_nB = s->lvl_first[Nr];
     int TH = 1;
@@ -2191,16 +2210,10 @@ void detect_multistage(tqgpu_solver *s) {
     /* chain part bottom-up in tiers of at most 8 levels (Uni<..., 1>::TH), then the branching part in tiers of TH levels */
     for (int l1 = Nh; l1 > Nr;) {
         const int l0 = std::max(Nr, l1 - 8);
-        s->tier_l0.push_back(l0); s->tier_l1.push_back(l1); s->tier_grid.push_back(S); s->tier_chain.push_back(1);
+        add_tier(s, l0, l1, S, 1);
         l1 = l0;
     }
-    for (int l1 = Nr; l1 > 0;) {
-        const int l0 = std::max(0, l1 - TH);
-        int grid = 1;
-        for (int l = 0; l < l0; l++) grid *= MD;
-        s->tier_l0.push_back(l0); s->tier_l1.push_back(l1); s->tier_grid.push_back(grid); s->tier_chain.push_back(0);
-        l1 = l0;
-    }
+    for (const UniTier &t : uni_tiers(Nr, TH, MD)) add_tier(s, t.l0, t.l1, t.grid, 0);
     s->n_tiers = (int)s->tier_l0.size();
 }
 
@@ -2219,16 +2232,9 @@ void detect_fast(tqgpu_solver *s) {
     s->fast = idx; s->fNX = NX; s->fNU = NU; s->fMD = MD;
     int TH = 1;
     fast_geometry(idx, TH, s->lds_fast, s->lds_fstage);
-    /* block levels 0 .. Nh-1 grouped bottom-up into tiers of TH levels; the top tier takes the rest */
-    const int Nh = s->Nh;
-    s->n_tiers = (Nh + TH - 1) / TH;
     s->tier_l0.clear(); s->tier_l1.clear(); s->tier_grid.clear(); s->tier_chain.clear();
-    for (int i = 0; i < s->n_tiers; i++) {
-        const int l1 = Nh - i * TH, l0 = std::max(0, l1 - TH);
-        int grid = 1;
-        for (int l = 0; l < l0; l++) grid *= MD;
-        s->tier_l0.push_back(l0); s->tier_l1.push_back(l1); s->tier_grid.push_back(grid); s->tier_chain.push_back(0);
-    }
+    for (const UniTier &t : uni_tiers(s->Nh, TH, MD)) add_tier(s, t.l0, t.l1, t.grid, 0);
+    s->n_tiers = (int)s->tier_l0.size();
 }
 
 /* ---- RCCL, loaded lazily so that single-device users do not depend on it ---- */
@@ -2262,8 +2268,6 @@ constexpr int NCCL_DOUBLE = 8;     /* ncclFloat64 */
 
 #define NCCL_TRY(expr) do { int r_ = (expr); if (r_ != 0) return fail(TQGPU_ECOMM, std::string(#expr) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error")); } while (0)
 
-int uni_first(int MD, int level) { int n = 0, w = 1; for (int l = 0; l < level; l++) { n += w; w *= MD; } return n; }
-
 Shard shard_desc(const tqgpu_solver *s, int tier) {
     Shard sh{};
     if (s->sharded) {
@@ -2274,54 +2278,55 @@ Shard shard_desc(const tqgpu_solver *s, int tier) {
     return sh;
 }
 
-/* exchange #1 (after the last partitioned backward tier): Schur records of the boundary subtree
- * roots and the termination partials; exchange #2 (after the trial sweep): {fval, dot} partials and
- * x / QinvCal of the boundary root nodes.  In-place all-gathers on the solver's stream. */
-int shard_exchange_rccl(tqgpu_solver *s, int which) {
-    const int N = s->nranks, r = s->rank, MD = s->fMD, NX = s->fNX;
-    const int lb = s->tier_l0[s->part_top], gb = s->tier_grid[s->part_top], w = gb / N;
-    const int f0 = uni_first(MD, lb);
-    const size_t SCH = (size_t)NX * NX + NX;
-    NCCL_TRY(g_rccl.GroupStart());
-    if (which == 1) {
-        double *base = s->D.Sbuf + (size_t)f0 * SCH;
-        NCCL_TRY(g_rccl.AllGather(base + (size_t)r * w * SCH, base, (size_t)w * SCH, NCCL_DOUBLE, s->comm, s->stream));
-        NCCL_TRY(g_rccl.AllGather(s->d_xerr + r, s->d_xerr, 1, NCCL_DOUBLE, s->comm, s->stream));
-    } else {
-        NCCL_TRY(g_rccl.AllGather(s->d_xs + 2 * r, s->d_xs, 2, NCCL_DOUBLE, s->comm, s->stream));
-        double *xb = s->D.x + (size_t)NX * f0, *qb = s->D.QinvCal + (size_t)NX * f0;
-        NCCL_TRY(g_rccl.AllGather(xb + (size_t)r * w * NX, xb, (size_t)w * NX, NCCL_DOUBLE, s->comm, s->stream));
-        NCCL_TRY(g_rccl.AllGather(qb + (size_t)r * w * NX, qb, (size_t)w * NX, NCCL_DOUBLE, s->comm, s->stream));
+/* a rank-partitioned range: rank r's share is base[r * per_rank, (r + 1) * per_rank) */
+struct RangeSpec { double *base; size_t per_rank; };
+
+/* what the ranks exchange per Newton iteration.  which = 1 (after the last partitioned backward tier): Schur records of the boundary
+ * subtree roots and the termination partials; which = 2 (after a trial sweep): {fval, dot} partials and x / QinvCal of the boundary
+ * root nodes */
+std::vector<RangeSpec> exchange_ranges(tqgpu_solver *s, int which) {
+    const size_t NX = (size_t)s->fNX, SCH = NX * NX + NX;
+    const size_t f0 = (size_t)uni_first(s->fMD, s->tier_l0[s->part_top]), w = (size_t)(s->tier_grid[s->part_top] / s->nranks);
+    if (which == 1) return {{s->D.Sbuf + f0 * SCH, w * SCH}, {s->d_xerr, 1}};
+    return {{s->d_xs, 2}, {s->D.x + NX * f0, w * NX}, {s->D.QinvCal + NX * f0, w * NX}};
+}
+
+/* the partitioned part of the solution, one set of ranges per node level >= the boundary level: for the gather after a solve */
+std::vector<RangeSpec> solution_ranges(tqgpu_solver *s) {
+    std::vector<RangeSpec> out;
+    const int MD = s->fMD, NX = s->fNX, NU = s->fNU, N = s->nranks;
+    const int lb = s->tier_l0[s->part_top];
+    const Data &D = s->D;
+    double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
+    for (int l = lb; l <= s->Nh; l++) {
+        const size_t f0 = (size_t)uni_first(MD, l), w = (size_t)uni_width(MD, l) / N;
+        double *xs[] = {D.x, D.xUnc, D.xUncS, lamc, D.dlam};
+        for (double *a : xs) out.push_back({a + NX * f0, w * NX});
+        if (l < s->Nh) { double *us[] = {D.u, D.uUnc, D.uUncS}; for (double *a : us) out.push_back({a + NU * f0, w * NU}); }
     }
+    return out;
+}
+
+/* the RCCL transport: one group of in-place all-gathers on the solver's stream, in the order of the list */
+int allgather_rccl(tqgpu_solver *s, const std::vector<RangeSpec> &ranges) {
+    NCCL_TRY(g_rccl.GroupStart());
+    for (const RangeSpec &rg : ranges) NCCL_TRY(g_rccl.AllGather(rg.base + (size_t)s->rank * rg.per_rank, rg.base, rg.per_rank, NCCL_DOUBLE, s->comm, s->stream));
     NCCL_TRY(g_rccl.GroupEnd());
     return TQGPU_OK;
 }
 
-/* the same exchanges between `n` mirrors living in one process on one device ("virtual ranks"):
- * used to validate the partition / hand-off logic on a single GPU */
-int shard_exchange_virtual(tqgpu_solver **R, int n, int which) {
-    tqgpu_solver *s0 = R[0];
-    const int MD = s0->fMD, NX = s0->fNX;
-    const int lb = s0->tier_l0[s0->part_top], gb = s0->tier_grid[s0->part_top], w = gb / n;
-    const int f0 = uni_first(MD, lb);
-    const size_t SCH = (size_t)NX * NX + NX;
+/* the same between `n` mirrors living in one process on one device ("virtual ranks", to validate the partition / hand-off logic on a
+ * single GPU).  ranges_of is asked per mirror: a mirror's h_ctrl->cur selects its own dual buffer */
+template <typename F>
+int allgather_virtual(tqgpu_solver **R, int n, F ranges_of) {
     for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
     /* every source stream is idle now; the copies are ordered on the DESTINATION mirror's stream, in
      * front of its next phase (the solver streams are non-blocking: the null stream would not order) */
     for (int src = 0; src < n; src++) for (int dst = 0; dst < n; dst++) {
         if (src == dst) continue;
-        tqgpu_solver *a = R[src], *b = R[dst];
-        hipStream_t st = b->stream;
-        if (which == 1) {
-            const size_t off = ((size_t)f0 + (size_t)src * w) * SCH;
-            HIP_TRY(hipMemcpyAsync(b->D.Sbuf + off, a->D.Sbuf + off, sizeof(double) * w * SCH, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(b->d_xerr + src, a->d_xerr + src, sizeof(double), hipMemcpyDeviceToDevice, st));
-        } else {
-            HIP_TRY(hipMemcpyAsync(b->d_xs + 2 * src, a->d_xs + 2 * src, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-            const size_t off = (size_t)NX * (f0 + (size_t)src * w);
-            HIP_TRY(hipMemcpyAsync(b->D.x + off, a->D.x + off, sizeof(double) * w * NX, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(b->D.QinvCal + off, a->D.QinvCal + off, sizeof(double) * w * NX, hipMemcpyDeviceToDevice, st));
-        }
+        const std::vector<RangeSpec> from = ranges_of(R[src]), to = ranges_of(R[dst]);
+        for (size_t i = 0; i < from.size(); i++)
+            HIP_TRY(hipMemcpyAsync(to[i].base + (size_t)src * to[i].per_rank, from[i].base + (size_t)src * from[i].per_rank, sizeof(double) * from[i].per_rank, hipMemcpyDeviceToDevice, R[dst]->stream));
     }
     for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
     return TQGPU_OK;
@@ -2380,9 +2385,9 @@ void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &la
 
 int launch_fast_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches) {
     launch_fast_phase(s, O, h, 0, launches);
-    if (s->sharded) { int rc = shard_exchange_rccl(s, 1); if (rc) return rc; }
+    if (s->sharded) { int rc = allgather_rccl(s, exchange_ranges(s, 1)); if (rc) return rc; }
     launch_fast_phase(s, O, h, 1, launches);
-    if (s->sharded) { int rc = shard_exchange_rccl(s, 2); if (rc) return rc; }
+    if (s->sharded) { int rc = allgather_rccl(s, exchange_ranges(s, 2)); if (rc) return rc; }
     launch_fast_phase(s, O, h, 2, launches);
     return TQGPU_OK;
 }
@@ -2455,7 +2460,7 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
 
 int launch_trial(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int &launches) {
     launch_trial_phase(s, O, r, it, t, 0, launches);
-    if (s->sharded) { int rc = shard_exchange_rccl(s, 2); if (rc) return rc; }
+    if (s->sharded) { int rc = allgather_rccl(s, exchange_ranges(s, 2)); if (rc) return rc; }
     launch_trial_phase(s, O, r, it, t, 1, launches);
     return TQGPU_OK;
 }
@@ -3739,33 +3744,6 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
 
 namespace {
 
-int read_ctrl(tqgpu_solver *s) {
-    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && !s->w3_tail_sg) {
-        /* the last launch enqueued does not post (the first sweep of a solve whose chunk launches nothing else): a one-thread launch does */
-        W3 w = next_w3(s);
-        w.hm = s->h_res; s->w3_wait = w.tag; s->w3_tail_sg = true;
-        hipLaunchKernelGGL(k_w3_post, dim3(1), dim3(WAVE), 0, s->stream, s->D, w);
-    }
-    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_tail_sg) {
-        /* three-launch family: the last launch enqueued posts the control block to pinned memory itself (w3_mirror) */
-        volatile unsigned *seq = &s->h_res->seq;
-        const unsigned want = s->w3_wait;
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = true;
-        for (long spins = 0; *seq != want; spins++) {
-            __builtin_ia32_pause();
-            if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { seen = false; break; }
-        }
-        if (seen) { std::atomic_thread_fence(std::memory_order_acquire); s->w3_seen = true; return TQGPU_OK; }      /* h_ctrl IS the block's control block */
-    }
-    s->w3_seen = false;
-    HIP_TRY(hipMemcpyAsync(s->h_ctrl, s->D.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-
-/* persistent launch: wait for the result block the top workgroup writes into pinned host memory (the
- * kernel may still be writing the state back -- everything else the host does is stream-ordered behind it) */
 /* the block as tagged words (HostRes::tg, posted by the persistent launches): complete when every word carries `want`; unpacked into the fields */
 bool take_tagged_block(HostRes *hr, unsigned want) {
     volatile unsigned long long *tg = hr->tg;
@@ -3779,23 +3757,64 @@ bool take_tagged_block(HostRes *hr, unsigned want) {
     return true;
 }
 
-int wait_result_block(tqgpu_solver *s) {
-    volatile unsigned *seq = &s->h_res->seq;
-    const unsigned want = s->psync.seq;
+/* spin until the pinned result block carries `want`, for 2 s at the most (the clock is read every 65 536 spins); tagged: the block may
+ * arrive as tagged words.  -> whether it arrived; what to do when it did not is the caller's */
+bool await_result_block(HostRes *hr, unsigned want, bool tagged) {
+    volatile unsigned *seq = &hr->seq;
     const auto t0 = std::chrono::steady_clock::now();
+    bool seen = true;
     for (long spins = 0; *seq != want; spins++) {
-        if (take_tagged_block(s->h_res, want)) break;
+        if (tagged && take_tagged_block(hr, want)) break;
         __builtin_ia32_pause();
-        if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            /* no verdict (a wait inside the kernel timed out, or the launch failed): fall back to the stream.  A member of a
-             * batch launch first waits for THAT launch (it runs on the lead's stream; the member's own stream is not ordered
-             * behind it, and its control block is only final when the launch has ended) */
-            if (s->batch_stream) HIP_TRY(hipStreamSynchronize(s->batch_stream));
-            return read_ctrl(s);
-        }
+        if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { seen = false; break; }
     }
     std::atomic_thread_fence(std::memory_order_acquire);
+    return seen;
+}
+
+/* the sticky word a bounded wait inside a persistent launch sets when it gives up: read (the stream has been waited for, or the verdict
+ * is in), and cleared on the mirror's stream */
+int read_timeout_word(tqgpu_solver *s, unsigned &tmo) {
+    HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
     return TQGPU_OK;
+}
+int clear_timeout_word(tqgpu_solver *s) {
+    HIP_TRY(hipMemsetAsync(s->psync.timeout, 0, sizeof(unsigned), s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TQGPU_OK;
+}
+
+void fill_result(tqgpu_result *res, const Ctrl &c, int launches, double device_seconds) {
+    res->status = c.status; res->iter = c.iter; res->ls_total = c.ls_total; res->ls_last = c.ls_last;
+    res->n_launches = launches; res->device_time = device_seconds; res->last_error_norm = c.err; res->last_fval = c.fval;
+}
+
+int read_ctrl(tqgpu_solver *s) {
+    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && !s->w3_tail_sg) {
+        /* the last launch enqueued does not post (the first sweep of a solve whose chunk launches nothing else): a one-thread launch does */
+        W3 w = next_w3(s);
+        w.hm = s->h_res; s->w3_wait = w.tag; s->w3_tail_sg = true;
+        hipLaunchKernelGGL(k_w3_post, dim3(1), dim3(WAVE), 0, s->stream, s->D, w);
+    }
+    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_tail_sg) {
+        /* three-launch family: the last launch enqueued posts the control block to pinned memory itself (w3_mirror) */
+        if (await_result_block(s->h_res, s->w3_wait, false)) { s->w3_seen = true; return TQGPU_OK; }      /* h_ctrl IS the block's control block */
+    }
+    s->w3_seen = false;
+    HIP_TRY(hipMemcpyAsync(s->h_ctrl, s->D.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return TQGPU_OK;
+}
+
+/* persistent launch: wait for the result block the top workgroup writes into pinned host memory (the
+ * kernel may still be writing the state back -- everything else the host does is stream-ordered behind it) */
+int wait_result_block(tqgpu_solver *s) {
+    if (await_result_block(s->h_res, s->psync.seq, true)) return TQGPU_OK;
+    /* no verdict (a wait inside the kernel timed out, or the launch failed): fall back to the stream.  A member of a
+     * batch launch first waits for THAT launch (it runs on the lead's stream; the member's own stream is not ordered
+     * behind it, and its control block is only final when the launch has ended) */
+    if (s->batch_stream) HIP_TRY(hipStreamSynchronize(s->batch_stream));
+    return read_ctrl(s);
 }
 
 }  // namespace
@@ -4045,7 +4064,7 @@ int end_single_launch(tqgpu_solver *s, SolveCtx &cx, bool &tail_done) {
         tail_done = false;
         if (route == Route::PERSIST) {
             unsigned tmo = 0;
-            HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
+            if ((rc = read_timeout_word(s, tmo)) != TQGPU_OK) return rc;
             if (tmo) return fail(TQGPU_ETIMEOUT, "persistent solve kernel: a bounded inter-workgroup wait timed out");
         }
     }
@@ -4153,8 +4172,7 @@ int finish_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_resul
         }
     }
     const Ctrl &c = *s->h_ctrl;
-    res->status = c.status; res->iter = c.iter; res->ls_total = c.ls_total; res->ls_last = c.ls_last;
-    res->n_launches = cx.launches; res->device_time = 1e-3 * ms; res->last_error_norm = c.err; res->last_fval = c.fval;
+    fill_result(res, c, cx.launches, 1e-3 * ms);
     s->last_iter = c.iter;
     s->last_ls_extra = c.ls_total > c.iter ? 1 : 0;
     if (cx.route == Route::THREE_LAUNCH && s->w3_merge && c.status == 2 && s->T.Np > 1) {
@@ -4198,8 +4216,7 @@ int solve_end(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_result *
 constexpr int PERSIST_BACKOFF = 1000;
 
 static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const SolveEnv &env, tqgpu_result *res) {
-    HIP_TRY(hipMemsetAsync(s->psync.timeout, 0, sizeof(unsigned), s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (int rc = clear_timeout_word(s)) return rc;
     s->use_persist = 0;
     s->persist_backoff = PERSIST_BACKOFF;
     s->n_timeouts++;
@@ -4644,26 +4661,6 @@ extern "C" int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_op
 
 namespace {
 
-/* enumerate the (array, first element, count per rank) ranges that are rank-partitioned, one per
- * node level >= lb; used for the final solution gather */
-struct RangeSpec { double *base; size_t per_rank; };
-
-std::vector<RangeSpec> solution_ranges(tqgpu_solver *s) {
-    std::vector<RangeSpec> out;
-    const int MD = s->fMD, NX = s->fNX, NU = s->fNU, N = s->nranks;
-    const int lb = s->tier_l0[s->part_top];
-    const Data &D = s->D;
-    double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
-    for (int l = lb; l <= s->Nh; l++) {
-        int wl = 1; for (int i = 0; i < l; i++) wl *= MD;
-        const size_t f0 = (size_t)uni_first(MD, l), w = (size_t)wl / N;
-        double *xs[] = {D.x, D.xUnc, D.xUncS, lamc, D.dlam};
-        for (double *a : xs) out.push_back({a + NX * f0, w * NX});
-        if (l < s->Nh) { double *us[] = {D.u, D.uUnc, D.uUncS}; for (double *a : us) out.push_back({a + NU * f0, w * NU}); }
-    }
-    return out;
-}
-
 /* The partition of a uniform tree over `N` ranks, host arithmetic only: tiers whose subtree count is a multiple of N
  * are partitioned by contiguous subtree ranges, the tiers above are replicated.  Used by shard_build_lists and exported as
  * tqgpu_shard_plan (the CPU tests compare it with the Python planner the gloo protocol tests use). */
@@ -4681,16 +4678,15 @@ int shard_plan_host(int MD, int NX, int Nh, const std::vector<int> &tier_l0, con
     if (P.part_top < 0) return fail(TQGPU_EUNSUPPORTED, "tree too small to shard over this many ranks");
     const int lb = tier_l0[P.part_top], l00 = tier_l0[0];
     P.lb = lb;
-    auto width = [&](int l) { int w = 1; for (int i = 0; i < l; i++) w *= MD; return w; };
     {
-        const int gb = width(lb), w = gb / N;
+        const int gb = uni_width(MD, lb), w = gb / N;
         P.bnd_b0 = NX * uni_first(MD, lb); P.bnd_bn = NX * gb; P.bnd_own0 = NX * r * w; P.bnd_ownn = NX * w;
     }
     std::vector<int> &gh = P.gh, &nodes = P.nodes, &nodes_cnt = P.nodes_cnt, &blks = P.blks;
     gh.clear(); nodes.clear(); nodes_cnt.clear(); blks.clear();
     /* owned */
     for (int l = lb; l <= Nh; l++) {
-        const int w = width(l) / N, f0 = uni_first(MD, l) + r * w;
+        const int w = uni_width(MD, l) / N, f0 = uni_first(MD, l) + r * w;
         for (int i = 0; i < w; i++) {
             nodes.push_back(f0 + i); nodes_cnt.push_back(f0 + i);
             if (l < Nh) blks.push_back(f0 + i);
@@ -4700,7 +4696,7 @@ int shard_plan_host(int MD, int NX, int Nh, const std::vector<int> &tier_l0, con
     P.gh_counted = (int)gh.size();
     /* replicated (levels above the boundary): computed by every rank, counted by rank 0 only */
     for (int l = 0; l < lb; l++) {
-        const int w = width(l), f0 = uni_first(MD, l);
+        const int w = uni_width(MD, l), f0 = uni_first(MD, l);
         for (int i = 0; i < w; i++) {
             nodes.push_back(f0 + i); gh.push_back(f0 + i);
             if (r == 0) { nodes_cnt.push_back(f0 + i); blks.push_back(f0 + i); }
@@ -4737,6 +4733,14 @@ int shard_build_lists(tqgpu_solver *s) {
     return TQGPU_OK;
 }
 
+void set_shard(tqgpu_solver *s, int rank, int nranks, bool on) { s->rank = rank; s->nranks = nranks; s->sharded = on; }
+
+/* the table of the ranks' slabs (sharded persistent launch), host to device */
+int upload_peers(tqgpu_solver *s) {
+    HIP_TRY(hipMemcpy(s->d_peers, s->h_peers, sizeof(s->h_peers), hipMemcpyHostToDevice));
+    return TQGPU_OK;
+}
+
 }  // namespace
 
 extern "C" int tqgpu_shard_unique_id(void *id128) {
@@ -4756,13 +4760,7 @@ extern "C" int tqgpu_shard_plan(int md, int nx, int Nh, int nranks, int rank, in
     if (md < 2 || Nh < 2 || nranks < 1 || rank < 0 || rank >= nranks) return fail(TQGPU_EINVAL, "tqgpu_shard_plan: bad arguments");
     const int TH = md == 2 ? 3 : (md <= 4 ? 2 : 1);
     std::vector<int> l0v, gridv;
-    const int nt = (Nh + TH - 1) / TH;
-    for (int i = 0; i < nt; i++) {
-        const int l1 = Nh - i * TH, l0 = std::max(0, l1 - TH);
-        int grid = 1;
-        for (int l = 0; l < l0; l++) grid *= md;
-        l0v.push_back(l0); gridv.push_back(grid);
-    }
+    for (const UniTier &t : uni_tiers(Nh, TH, md)) { l0v.push_back(t.l0); gridv.push_back(t.grid); }
     ShardPlanHost P;
     int rc = shard_plan_host(md, nx, Nh, l0v, gridv, nranks, rank, P);
     if (rc) return rc;
@@ -4786,14 +4784,14 @@ extern "C" int tqgpu_shard_init(tqgpu_solver *s, int rank, int nranks, const voi
     if (s->comm) { (void)g_rccl.CommDestroy(s->comm); s->comm = nullptr; }      /* a second call replaces the communicator, it does not leak it */
     /* one rank WITHOUT a communicator = back to the unsharded mirror; one rank WITH one = the sharded code path on a single device
      * (every exchange is a one-rank in-place all-gather): exercises rccl_load / ncclCommInitRank / ncclAllGather where only one GPU exists */
-    if (nranks == 1 && !id128) { s->nranks = 1; s->rank = 0; s->sharded = false; return TQGPU_OK; }
+    if (nranks == 1 && !id128) { set_shard(s, 0, 1, false); return TQGPU_OK; }
     if (s->fast < 0 || !s->use_fast || s->mstage) return fail(TQGPU_EUNSUPPORTED, "sharding needs the fused uniform-tree path");
-    s->nranks = nranks; s->rank = rank; s->sharded = true;
+    set_shard(s, rank, nranks, true);
     s->export_valid = false;
     int rc = shard_build_lists(s);
-    if (rc) { s->nranks = 1; s->rank = 0; s->sharded = false; return rc; }
+    if (rc) { set_shard(s, 0, 1, false); return rc; }
     if (id128) {
-        if ((rc = rccl_load())) { s->nranks = 1; s->rank = 0; s->sharded = false; return rc; }
+        if ((rc = rccl_load())) { set_shard(s, 0, 1, false); return rc; }
         RcclApi::UniqueId id;
         memcpy(&id, id128, sizeof(id));
         NCCL_TRY(g_rccl.CommInitRank(&s->comm, nranks, id, rank));
@@ -4809,10 +4807,7 @@ extern "C" int tqgpu_shard_gather_solution(tqgpu_solver *s) {
     if (!s->sharded) return TQGPU_OK;
     if (!s->comm) return fail(TQGPU_ECOMM, "no communicator (virtual ranks gather through tqgpu_solve_virtual_ranks)");
     HIP_TRY(hipSetDevice(s->device));
-    auto ranges = solution_ranges(s);
-    NCCL_TRY(g_rccl.GroupStart());
-    for (auto &rg : ranges) NCCL_TRY(g_rccl.AllGather(rg.base + (size_t)s->rank * rg.per_rank, rg.base, rg.per_rank, NCCL_DOUBLE, s->comm, s->stream));
-    NCCL_TRY(g_rccl.GroupEnd());
+    if (int rc = allgather_rccl(s, solution_ranges(s))) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
     return TQGPU_OK;
 }
@@ -4877,7 +4872,7 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
     s->psync.anc_local = (nranks == 1 || top >= 1) ? 1 : 0;          /* tiers 0 .. top are dealt over the ranks by contiguous subtree ranges: with top >= 1 a tier-1 workgroup sits with the bottom-tier workgroups below it */
     s->psync.relay_wg = (rank > 0 && !map.empty()) ? map[0] : -1;          /* ranks without the top workgroup: their first workgroup passes the verdict on to the host */
     for (int r = 0; r < 8; r++) s->h_peers[r] = s->psync.base;             /* until connected: own slab */
-    HIP_TRY(hipMemcpy(s->d_peers, s->h_peers, sizeof(s->h_peers), hipMemcpyHostToDevice));
+    if (int rc = upload_peers(s)) return rc;
     s->psync.nap = nap_for_grid(s->ps_G);
     s->launch_no = 0;
     HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
@@ -4896,8 +4891,7 @@ extern "C" int tqgpu_pshard_connect_local(tqgpu_solver *s, int r, tqgpu_solver *
         (void)hipGetLastError();
     }
     s->h_peers[r] = static_cast<unsigned long long *>(peer->sync_slab);
-    HIP_TRY(hipMemcpy(s->d_peers, s->h_peers, sizeof(s->h_peers), hipMemcpyHostToDevice));
-    return TQGPU_OK;
+    return upload_peers(s);
 }
 /* peers in other processes: an IPC handle of this rank's slab (64 bytes) out, the peers' handles in */
 extern "C" int tqgpu_pshard_ipc_export(tqgpu_solver *s, void *handle64) {
@@ -4921,8 +4915,7 @@ extern "C" int tqgpu_pshard_ipc_connect(tqgpu_solver *s, int r, const void *hand
     if (s->ps_ipc[r]) (void)hipIpcCloseMemHandle(s->ps_ipc[r]);
     s->ps_ipc[r] = ptr;
     s->h_peers[r] = static_cast<unsigned long long *>(ptr);
-    HIP_TRY(hipMemcpy(s->d_peers, s->h_peers, sizeof(s->h_peers), hipMemcpyHostToDevice));
-    return TQGPU_OK;
+    return upload_peers(s);
 }
 
 /* one solve in two halves (so that one process can drive several ranks): _begin enqueues this rank's launch, _end waits for the
@@ -4958,48 +4951,29 @@ extern "C" int tqgpu_pshard_rewind(tqgpu_solver *s) {
     s->launch_no = 0;
     return TQGPU_OK;
 }
+/* tqgpu_pshard_end without a verdict: a time-out of a bounded wait (the sticky word, cleared here), or the error the caller names */
+static int pshard_no_verdict(tqgpu_solver *s, const char *timeout_hint, int code, const char *text) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    unsigned tmo = 0;
+    if (int rc = read_timeout_word(s, tmo)) return rc;
+    if (!tmo) return fail(code, text);
+    if (int rc = clear_timeout_word(s)) return rc;
+    return fail(TQGPU_ETIMEOUT, std::string("sharded persistent solve: a bounded wait for another rank's workgroups timed out") + timeout_hint);
+}
 extern "C" int tqgpu_pshard_end(tqgpu_solver *s, tqgpu_result *res) {
     SETTLE(s);
     if (!s || !res || !s->pshard) return fail(TQGPU_EINVAL, "tqgpu_pshard_end: not a sharded mirror");
     HIP_TRY(hipSetDevice(s->device));
     /* the verdict reaches every rank's host through its pinned result block: written by the top workgroup (rank 0) or passed on from the
      * rank's slab by its relay workgroup -- no stream synchronisation on the way (the state write-back of the other workgroups is still
-     * running; everything the host does next on this mirror is stream-ordered behind the launch) */
-    {
-        volatile unsigned *seq = &s->h_res->seq;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (long spins = 0; *seq != s->psync.seq; spins++) {
-            if (take_tagged_block(s->h_res, s->psync.seq)) break;          /* (rank 0: the top workgroup's tagged words; the other ranks' relay workgroups post the plain block) */
-            __builtin_ia32_pause();
-            if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (s->h_res->seq != s->psync.seq) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        unsigned tmo = 0;
-        HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
-        if (tmo) {
-            HIP_TRY(hipMemsetAsync(s->psync.timeout, 0, sizeof(unsigned), s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            return fail(TQGPU_ETIMEOUT, "sharded persistent solve: a bounded wait for another rank's workgroups timed out (are all ranks' launches in flight together?)");
-        }
-        return fail(TQGPU_ECOMM, "sharded persistent solve: no verdict from the top workgroup");
-    }
+     * running; everything the host does next on this mirror is stream-ordered behind the launch).  (rank 0: the top workgroup's tagged
+     * words; the other ranks' relay workgroups post the plain block) */
+    if (!await_result_block(s->h_res, s->psync.seq, true))
+        return pshard_no_verdict(s, " (are all ranks' launches in flight together?)", TQGPU_ECOMM, "sharded persistent solve: no verdict from the top workgroup");
     const Ctrl &c = *s->h_ctrl;
-    if (!c.done) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        unsigned tmo = 0;
-        HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
-        if (tmo) {
-            HIP_TRY(hipMemsetAsync(s->psync.timeout, 0, sizeof(unsigned), s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            return fail(TQGPU_ETIMEOUT, "sharded persistent solve: a bounded wait for another rank's workgroups timed out");
-        }
-        return fail(TQGPU_EUNSUPPORTED, "sharded persistent solve: the launch ended without a verdict (tag space exhausted: more than 60000 passes)");
-    }
-    res->status = c.status; res->iter = c.iter; res->ls_total = c.ls_total; res->ls_last = c.ls_last;
-    res->n_launches = 1; res->device_time = s->rank == 0 ? 1e-8 * (double)(s->h_res->t_end - s->h_res->t_start) : 0.0; res->last_error_norm = c.err; res->last_fval = c.fval;
+    if (!c.done)
+        return pshard_no_verdict(s, "", TQGPU_EUNSUPPORTED, "sharded persistent solve: the launch ended without a verdict (tag space exhausted: more than 60000 passes)");
+    fill_result(res, c, 1, s->rank == 0 ? 1e-8 * (double)(s->h_res->t_end - s->h_res->t_start) : 0.0);
     s->last_iter = c.iter;
     return TQGPU_OK;
 }
@@ -5016,7 +4990,7 @@ std::vector<PsRange> pshard_owned_ranges(tqgpu_solver *s, int rank) {
     double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
     const int lb = N > 1 ? s->tier_l0[s->part_top] : s->Nh + 1;
     for (int l = 0; l <= s->Nh; l++) {
-        int wl = 1; for (int i = 0; i < l; i++) wl *= MD;
+        const int wl = uni_width(MD, l);
         const size_t f0 = (size_t)uni_first(MD, l);
         /* node data (x, u, ...) of level l belongs to the workgroup that owns the node; the duals of a node's own edge belong to the
          * BLOCK of its parent, one level up: the duals of the boundary level are the top tiers' (rank 0) */
@@ -5037,6 +5011,17 @@ std::vector<PsRange> pshard_owned_ranges(tqgpu_solver *s, int rank) {
     }
     return out;
 }
+/* rank `rank`'s ranges to the host buffer (to_host: tqgpu_pshard_pack) or from it (tqgpu_pshard_unpack) */
+int copy_owned_ranges(tqgpu_solver *s, int rank, double *buf, long cap, bool to_host) {
+    size_t o = 0;
+    for (auto &rg : pshard_owned_ranges(s, rank)) {
+        if ((long)(o + rg.n) > cap) return fail(TQGPU_EINVAL, to_host ? "tqgpu_pshard_pack: buffer too small" : "tqgpu_pshard_unpack: buffer too small");
+        if (to_host) HIP_TRY(hipMemcpy(buf + o, rg.base, sizeof(double) * rg.n, hipMemcpyDeviceToHost));
+        else HIP_TRY(hipMemcpy(rg.base, buf + o, sizeof(double) * rg.n, hipMemcpyHostToDevice));
+        o += rg.n;
+    }
+    return TQGPU_OK;
+}
 }  // namespace
 extern "C" long tqgpu_pshard_pack_size(tqgpu_solver *s) {
     if (!s || !s->pshard) return -1;
@@ -5051,26 +5036,14 @@ extern "C" int tqgpu_pshard_pack(tqgpu_solver *s, double *out, long cap) {
     /* tqgpu_pshard_end returns on the verdict word while the workgroups still write their state back, and the copies below run on the
      * null stream, which the solver's non-blocking stream does not order: wait for the launch first */
     HIP_TRY(hipStreamSynchronize(s->stream));
-    size_t o = 0;
-    for (auto &rg : pshard_owned_ranges(s, s->rank)) {
-        if ((long)(o + rg.n) > cap) return fail(TQGPU_EINVAL, "tqgpu_pshard_pack: buffer too small");
-        HIP_TRY(hipMemcpy(out + o, rg.base, sizeof(double) * rg.n, hipMemcpyDeviceToHost));
-        o += rg.n;
-    }
-    return TQGPU_OK;
+    return copy_owned_ranges(s, s->rank, out, cap, true);
 }
 extern "C" int tqgpu_pshard_unpack(tqgpu_solver *s, int src_rank, const double *in, long n_in) {
     SETTLE(s);
     if (!s || !in || !s->pshard || src_rank < 0 || src_rank >= s->nranks) return fail(TQGPU_EINVAL, "tqgpu_pshard_unpack: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));          /* (as tqgpu_pshard_pack: this rank's own write-back must not land on top of the peers' shares) */
-    size_t o = 0;
-    for (auto &rg : pshard_owned_ranges(s, src_rank)) {
-        if ((long)(o + rg.n) > n_in) return fail(TQGPU_EINVAL, "tqgpu_pshard_unpack: buffer too small");
-        HIP_TRY(hipMemcpy(rg.base, in + o, sizeof(double) * rg.n, hipMemcpyHostToDevice));
-        o += rg.n;
-    }
-    return TQGPU_OK;
+    return copy_owned_ranges(s, src_rank, const_cast<double *>(in), n_in, false);
 }
 
 /* n mirrors of the SAME problem in this process (one device: a rehearsal with real concurrency -- n launches on n streams that wait
@@ -5107,34 +5080,25 @@ extern "C" int tqgpu_solve_virtual_ranks(tqgpu_solver **R, int n, const tqgpu_op
     HIP_TRY(hipSetDevice(R[0]->device));
     Opts O;
     if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    int launches = 0;
+    int launches = 0, rc;
     for (int r = 0; r < n; r++) {
-        tqgpu_solver *s = R[r];
-        hipStream_t st = s->stream;
-        Ctrl init; memset(&init, 0, sizeof(init));
-        HIP_TRY(hipMemcpyAsync(s->D.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(s->D.ls_log, 0, sizeof(int) * (size_t)s->ls_log_cap, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpyAsync(s->D.lam0, s->d_lam_init, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, st));
-        const int nxu = std::max(s->sum_nx, s->sum_nu);
-        if (s->need_init) { hipLaunchKernelGGL(k_init, dim3((nxu + 255) / 256), dim3(256), 0, st, s->sum_nx, s->sum_nu, s->D); s->need_init = false; }
-        hipLaunchKernelGGL(k_stage, dim3(s->T.Nn), dim3(WAVE), s->lds_stage, st, s->T, s->D, 0, 0, 0);
-        hipLaunchKernelGGL(k_fval_init, dim3(1), dim3(256), 0, st, s->T, s->D);
+        SolveCtx prologue(SolveEnv(), Route::TIERED);          /* its launch count is dropped: n_launches reports the iterations' and trials' launches */
+        if ((rc = begin_enqueued(R[r], prologue))) return rc;
     }
-    int rc;
+    auto exchange = [&](int which) { return allgather_virtual(R, n, [which](tqgpu_solver *m) { return exchange_ranges(m, which); }); };
     bool finished = o->maxIter <= 0;
     int h = 0;
     while (!finished) {
         for (int r = 0; r < n; r++) launch_fast_phase(R[r], O, h, 0, launches);
-        if ((rc = shard_exchange_virtual(R, n, 1))) return rc;
+        if ((rc = exchange(1))) return rc;
         for (int r = 0; r < n; r++) launch_fast_phase(R[r], O, h, 1, launches);
-        if ((rc = shard_exchange_virtual(R, n, 2))) return rc;
+        if ((rc = exchange(2))) return rc;
         for (int r = 0; r < n; r++) launch_fast_phase(R[r], O, h, 2, launches);
         for (int r = 0; r < n; r++) if ((rc = read_ctrl(R[r]))) return rc;
         while (!R[0]->h_ctrl->done && R[0]->h_ctrl->ls_pending) {
             const int it = R[0]->h_ctrl->iter, t = R[0]->h_ctrl->ls_iter;
             for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, Route::TIERED, it, t, 0, launches);
-            if ((rc = shard_exchange_virtual(R, n, 2))) return rc;
+            if ((rc = exchange(2))) return rc;
             for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, Route::TIERED, it, t, 1, launches);
             for (int r = 0; r < n; r++) if ((rc = read_ctrl(R[r]))) return rc;
         }
@@ -5144,23 +5108,11 @@ extern "C" int tqgpu_solve_virtual_ranks(tqgpu_solver **R, int n, const tqgpu_op
         h = R[0]->h_ctrl->iter;
         finished = R[0]->h_ctrl->done != 0;
     }
-    /* gather the partitioned solution ranges into every mirror */
-    for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
-    if (o->maxIter > 0) {
-        for (int src = 0; src < n; src++) {
-            auto rs = solution_ranges(R[src]);
-            for (int dst = 0; dst < n; dst++) {
-                if (dst == src) continue;
-                auto rd = solution_ranges(R[dst]);
-                for (size_t i = 0; i < rs.size(); i++)
-                    HIP_TRY(hipMemcpyAsync(rd[i].base + (size_t)src * rd[i].per_rank, rs[i].base + (size_t)src * rs[i].per_rank, sizeof(double) * rs[i].per_rank, hipMemcpyDeviceToDevice, R[dst]->stream));
-            }
-        }
-        for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
-    }
+    /* gather the partitioned solution ranges into every mirror (nothing iterated: only the wait for the streams) */
+    if (o->maxIter > 0) { if ((rc = allgather_virtual(R, n, solution_ranges))) return rc; }
+    else for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
     const Ctrl &c = *R[0]->h_ctrl;
-    res->status = c.status; res->iter = c.iter; res->ls_total = c.ls_total; res->ls_last = c.ls_last;
-    res->n_launches = launches; res->device_time = 0.0; res->last_error_norm = c.err; res->last_fval = c.fval;
+    fill_result(res, c, launches, 0.0);
     for (int r = 0; r < n; r++) R[r]->last_iter = c.iter;
     return TQGPU_OK;
 }
