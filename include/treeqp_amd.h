@@ -148,6 +148,40 @@ int tqgpu_set_export_ahead(tqgpu_solver *s, int on);
 /* any output pointer may be NULL */
 int tqgpu_get_solution(tqgpu_solver *s, double *x, double *u, double *lam, double *mu_x, double *mu_u, double *dlam);
 
+/* KKT residuals of a point, evaluated on the device: what tree_qp_out_calculate_KKT_res (tree_qp_common.c:540-788) and
+ * tree_qp_out_max_KKT_res compute on the host after a download, from the device copies of the data (one wave per node, then one
+ * workgroup for the maxima; no atomics, so the result does not depend on scheduling).  Six classes, in the reference's order: */
+#define TQGPU_KKT_STAT   0   /* Qx + q + S'u + mu_x + C'mu_d - lam_k + sum_kids A'lam_kid ; Ru + r + Sx + mu_u + D'mu_d + sum_kids B'lam_kid */
+#define TQGPU_KKT_DYN    1   /* A x_dad + B u_dad + b - x_k */
+#define TQGPU_KKT_BFEAS  2   /* violation of xmin/xmax, umin/umax */
+#define TQGPU_KKT_BCOMPL 3   /* mu > 0 ? mu (v - max) : mu (min - v) */
+#define TQGPU_KKT_GFEAS  4   /* violation of dmin <= Cx + Du <= dmax */
+#define TQGPU_KKT_GCOMPL 5   /* the same product with mu_d and Cx + Du */
+/* res[c]: the largest absolute entry of class c over the tree; node[c]: the lowest node that attains it, -1 (and res[c] = 0) where the
+ * class has no entry (no edges, no rows); per_node (Nn x 6, node-major, or NULL): the six maxima of every node, 0 where the node has no
+ * entry of the class.  The figure the reference's drivers assert on (`kkt_err < 1e-8`) is the largest of res[0..6), NaN if any is.
+ *   - A multiplier that is exactly 0 contributes 0 to its complementarity entry whatever the bound (the reference computes 0 * inf = NaN);
+ *     a non-zero multiplier against an infinite bound gives inf.
+ *   - A NaN anywhere in a class makes res[c] NaN and node[c] the lowest such node (tree_qp_out_max_KKT_res treats NaN as worst too);
+ *     a NaN value counts as violating its bounds.  Ties between nodes go to the lowest index.
+ *   - Nodes of kind 1 ignore their bounds, which may never have been uploaded: they contribute 0 to BFEAS and BCOMPL, while their
+ *     mu_x, mu_u enter stationarity as given.  Rows count on the nodes of kind 3, the only ones where they apply.
+ *   - The phantom root states of an x0-eliminated tree on the persistent path belong to no class.
+ * tqgpu_kkt_residual: the point of the last solve, whatever its route and status -- exactly what tqgpu_get_solution and tqgpu_get_mu_d
+ *   return, read where it lies (the packing kernel is enqueued unless it went out ahead, tqgpu_set_export_ahead); 12 (+ Nn x 6) values
+ *   come back through pinned memory, one synchronisation.  TQGPU_EINVAL on a null solver and on a mirror that has not solved yet.
+ * tqgpu_kkt_residual_at: any point (a warm start, another solver's answer) in the flat layout of tqgpu_get_solution, mu_d as
+ *   tqgpu_get_mu_d gives it; x, u, lam are required, a NULL multiplier array is all zeros.  Needs an uploaded problem, no solve, and
+ *   changes nothing a later solve or tqgpu_get_solution reads.
+ * tqgpu_kkt_residual_batch: every member's evaluation is enqueued on its own stream, then each is waited for once; res n x 6, node
+ *   n x 6 or NULL; member i gets bit for bit what tqgpu_kkt_residual(solvers[i]) gives.
+ * A rank of a sharded solve (tqgpu_pshard_init / tqgpu_shard_init with nranks > 1) is refused with TQGPU_EUNSUPPORTED by all three. */
+int tqgpu_kkt_residual(tqgpu_solver *s, double res[6], int node[6], double *per_node);
+int tqgpu_kkt_residual_at(tqgpu_solver *s, const double *x, const double *u, const double *lam,
+                          const double *mu_x, const double *mu_u, const double *mu_d,
+                          double res[6], int node[6], double *per_node);
+int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *res, int *node);
+
 /* 2: persistent single-launch solve (tdunes_persist.hpp); 1: tiered fused kernels (tdunes_fast.hpp);
  * 0: generic per-level kernels.  TREEQP_AMD_PATH=generic|tiered in the environment at create time
  * forces the lower paths. */

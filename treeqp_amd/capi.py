@@ -475,6 +475,28 @@ def solve_batch(mirrors, profile=0, **kw) -> list:
     return [{f: getattr(res[i], f) for f, _ in GpuResult._fields_} for i in range(n)]
 
 
+KKT_CLASSES = ("stat", "dyn", "bfeas", "bcompl", "gfeas", "gcompl")      # TQGPU_KKT_* of include/treeqp_amd.h, in order
+
+
+def _kkt_dict(res, node, per_node=None) -> dict:
+    out = dict(res=res, node=node, max=float("nan") if np.isnan(res).any() else float(res.max()))
+    if per_node is not None:
+        out["per_node"] = per_node
+    return out
+
+
+def kkt_residual_batch(mirrors) -> list:
+    """KKT residuals of the last solve of every mirror, evaluated on the device: all enqueued, then one wait per member
+    (tqgpu_kkt_residual_batch) -> one dict of TqGpu.kkt_residual per member."""
+    n = len(mirrors)
+    arr = (C.c_void_p * n)(*[m.h for m in mirrors])
+    res, node = np.zeros((n, 6)), np.zeros((n, 6), dtype=np.int32)
+    rc = lib().tqgpu_kkt_residual_batch(arr, n, _dp(res), _ip(node))
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_kkt_residual_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    return [_kkt_dict(res[i].copy(), node[i].copy()) for i in range(n)]
+
+
 def solve_batch_n(mirrors, steps: int, profile=0, **kw):
     """`steps` batched solves back to back in C (tqgpu_solve_batch_n) -> (results of the last call, sum of iterations, of trials, of launches)."""
     o = GpuOpts(maxIter=100, termCondition=2, stationarityTolerance=1e-8, regType=2, regTol=1e-6, regValue=1e-6,
@@ -683,6 +705,42 @@ class TqGpu:
             out["mu_d"] = np.zeros(self.sum_nc)
             self._chk(lib().tqgpu_get_mu_d(self.h, _dp(out["mu_d"])))
         return out
+
+    def kkt_residual(self, per_node=False) -> dict:
+        """KKT residuals of the last solve's point, evaluated on the device (tqgpu_kkt_residual): res[6] the largest absolute entry of
+        each class of KKT_CLASSES, node[6] the lowest node that attains it (-1: class without entries), max the largest of res (NaN if
+        any is) -- the figure tree_qp_out_max_KKT_res gives; per_node=True adds the (Nn, 6) maxima of every node."""
+        res, node = np.zeros(6), np.zeros(6, dtype=np.int32)
+        pn = np.zeros((len(self.nk), 6)) if per_node else None
+        self._chk(lib().tqgpu_kkt_residual(self.h, _dp(res), _ip(node), _dp(pn)))
+        return _kkt_dict(res, node, pn)
+
+    def kkt_residual_at(self, sol: dict, mu_d=None, per_node=False) -> dict:
+        """The same for any point: sol as solution() returns it (x, u, lam required; mu_x, mu_u and mu_d -- the argument, else
+        sol["mu_d"] -- may be missing or None: zeros).  Needs an uploaded problem, no solve; changes nothing a solve reads."""
+        if mu_d is None:
+            mu_d = sol.get("mu_d")
+        want = dict(x=self.sum_nx, u=self.sum_nu, lam=self.sum_lam, mu_x=self.sum_nx, mu_u=self.sum_nu)
+        keep = {}
+        for k, n in want.items():
+            a = sol.get(k)
+            if a is None:
+                if k in ("x", "u", "lam"):
+                    raise ValueError(f"kkt_residual_at: {k} is required")
+                keep[k] = None
+                continue
+            keep[k] = _f64(a)
+            if len(keep[k]) != n:
+                raise ValueError(f"kkt_residual_at: {k} has {len(keep[k])} entries, the tree {n}")
+        if mu_d is not None:
+            mu_d = _f64(mu_d)
+            if len(mu_d) != getattr(self, "sum_nc", 0):
+                raise ValueError(f"kkt_residual_at: mu_d has {len(mu_d)} entries, the tree {getattr(self, 'sum_nc', 0)} rows")
+        res, node = np.zeros(6), np.zeros(6, dtype=np.int32)
+        pn = np.zeros((len(self.nk), 6)) if per_node else None
+        self._chk(lib().tqgpu_kkt_residual_at(self.h, _dp(keep["x"]), _dp(keep["u"]), _dp(keep["lam"]), _dp(keep["mu_x"]), _dp(keep["mu_u"]),
+                                              _dp(mu_d), _dp(res), _ip(node), _dp(pn)))
+        return _kkt_dict(res, node, pn)
 
     def iteration_log(self, cap=4096):
         ls = np.zeros(cap, dtype=np.int32)

@@ -1957,6 +1957,9 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     double *d_out = nullptr, *h_out = nullptr; size_t out_doubles = 0;
+    /* tqgpu_kkt_residual*: [six maxima | six nodes | pad | Nn x 6 table] on the device and pinned (setup_kkt, on first use); the point of
+     * tqgpu_kkt_residual_at, [x | u | lam | mu_x | mu_u | mu_d], on the device and pinned (grows with sum_nc) */
+    double *d_kkt = nullptr, *h_kkt = nullptr, *d_kkt_pt = nullptr, *h_kkt_pt = nullptr; size_t kkt_pt_cap = 0;
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -2842,8 +2845,128 @@ __global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, in
     if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
 }
 
+/* ---- KKT residuals of a point, evaluated where the data is (tqgpu_kkt_residual*; tree_qp_out_calculate_KKT_res, tree_qp_common.c:540-788) ----
+ * The point comes as pointers in the flat user layout of tqgpu_get_solution (no phantom root states; a null multiplier array is all
+ * zeros), so the same kernels serve d_out + Gen::mu and the scratch buffer of tqgpu_kkt_residual_at. */
+struct KktPoint { const double *x, *u, *lam, *mu_x, *mu_u, *mu_d; };
+constexpr int KKT_CLASSES = 6;
+constexpr int KKT_HEAD = 10;      /* doubles in front of the per-node table: six maxima, six ints (the nodes), one pad */
+
+__device__ __forceinline__ double kkt_viol(double v, double lo, double hi) { return v > hi ? v - hi : v < lo ? lo - v : (v != v ? v : 0.0); }
+/* a multiplier that is exactly zero contributes zero whatever the bound (the reference's 0 * inf is NaN) */
+__device__ __forceinline__ double kkt_compl(double mu, double v, double lo, double hi) { return mu == 0.0 ? 0.0 : mu > 0.0 ? mu * (v - hi) : mu * (lo - v); }
+/* entry j of [x | u] of a node; phantom root states are zero and belong to no class */
+__device__ __forceinline__ double kkt_z(const KktPoint &P, int j, int nxn, int xo, int uo, int pad, int x_pad) {
+    return j < nxn ? (j < pad ? 0.0 : P.x[xo + j - x_pad]) : P.u[uo + j - nxn];
+}
+
+/* One wave per node: lane j owns entry j of [x | u], then of the rows, striding by 64 on larger nodes.  Per class the largest absolute
+ * entry of the node, NaN kept (nanmax / wmax), goes to table[6 k + class]; -1 where the node has no entry of the class.  Nodes of kind 1
+ * ignore their bounds (entries 0); rows count on nodes of kind 3 only. */
+__global__ void __launch_bounds__(WAVE) k_kkt(Tree T, Data D, int x_pad, KktPoint P, double *table) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const int nxk = T.nx[k], nuk = T.nu[k], nz = nxk + nuk, xo = T.xoff[k], uo = T.uoff[k], nx0 = T.nx0;
+    const int pad = k == 0 ? x_pad : 0;
+    const int kind = D.dense ? D.kind[k] : 0;
+    const int nc = kind == 3 ? D.gen->nc[k] : 0, ro = kind == 3 ? D.gen->roff[k] : 0;
+    const double *Gt = kind == 3 ? D.gen->Gt + D.gen->goff[k] : nullptr;
+    const double *H = kind ? D.Hd + D.poff[k] : nullptr;
+    double m[KKT_CLASSES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+
+    for (int j = lane; j < nz; j += WAVE) {
+        if (j < pad) continue;
+        const bool isx = j < nxk;
+        const int jj = isx ? j : j - nxk;
+        const double zj = kkt_z(P, j, nxk, xo, uo, pad, x_pad);
+        const double mu = isx ? (P.mu_x ? P.mu_x[xo + j - x_pad] : 0.0) : (P.mu_u ? P.mu_u[uo + jj] : 0.0);
+        /* stationarity: H z + h + mu + G' mu_d - lam_k + sum over the children of [A B]' lam_kid (column j of A / B is contiguous) */
+        double acc = 0.0;
+        if (kind) for (int i = 0; i < nz; i++) acc = fma(H[j + (size_t)i * nz], kkt_z(P, i, nxk, xo, uo, pad, x_pad), acc);
+        else acc = (isx ? D.Qd[xo + j] : D.Rd[uo + jj]) * zj;
+        acc += isx ? D.q[xo + j] : D.r[uo + jj];
+        acc += mu;
+        for (int r = 0; r < nc; r++) acc = fma(Gt[(size_t)r * nz + j], P.mu_d ? P.mu_d[ro + r] : 0.0, acc);
+        if (k > 0 && isx) acc -= P.lam[xo - nx0 + j];
+        for (int c = 0; c < T.nk[k]; c++) {
+            const int kid = T.kid0[k] + c, nxc = T.nx[kid];
+            const double *col = isx ? D.A + T.aoff[kid] + (size_t)j * nxc : D.B + T.boff[kid] + (size_t)jj * nxc;
+            const double *lk = P.lam + T.xoff[kid] - nx0;
+            for (int i = 0; i < nxc; i++) acc = fma(col[i], lk[i], acc);
+        }
+        m[TQGPU_KKT_STAT] = nanmax(m[TQGPU_KKT_STAT], fabs(acc));
+        /* bounds: violation and complementarity */
+        if (kind != 1) {
+            const double lo = isx ? D.xmin[xo + j] : D.umin[uo + jj], hi = isx ? D.xmax[xo + j] : D.umax[uo + jj];
+            m[TQGPU_KKT_BFEAS] = nanmax(m[TQGPU_KKT_BFEAS], fabs(kkt_viol(zj, lo, hi)));
+            m[TQGPU_KKT_BCOMPL] = nanmax(m[TQGPU_KKT_BCOMPL], fabs(kkt_compl(mu, zj, lo, hi)));
+        }
+    }
+    /* dynamics: A x_dad + B u_dad + b - x_k */
+    if (k > 0) {
+        const int dad = T.dad[k], nxd = T.nx[dad], nud = T.nu[dad], xod = T.xoff[dad], uod = T.uoff[dad], padd = dad == 0 ? x_pad : 0;
+        const double *A = D.A + T.aoff[k], *B = D.B + T.boff[k];
+        for (int i = lane; i < nxk; i += WAVE) {
+            double acc = 0.0;
+            for (int j = padd; j < nxd; j++) acc = fma(A[i + (size_t)j * nxk], P.x[xod + j - x_pad], acc);
+            for (int j = 0; j < nud; j++) acc = fma(B[i + (size_t)j * nxk], P.u[uod + j], acc);
+            acc += D.b[xo + i];
+            acc -= P.x[xo + i - x_pad];
+            m[TQGPU_KKT_DYN] = nanmax(m[TQGPU_KKT_DYN], fabs(acc));
+        }
+    }
+    /* rows: G z against [dmin, dmax], row r of G at Gt[r nz ..) */
+    for (int r = lane; r < nc; r += WAVE) {
+        double g = 0.0;
+        for (int j = pad; j < nz; j++) g = fma(Gt[(size_t)r * nz + j], kkt_z(P, j, nxk, xo, uo, pad, x_pad), g);
+        const double lo = D.gen->dmin[ro + r], hi = D.gen->dmax[ro + r], mu = P.mu_d ? P.mu_d[ro + r] : 0.0;
+        m[TQGPU_KKT_GFEAS] = nanmax(m[TQGPU_KKT_GFEAS], fabs(kkt_viol(g, lo, hi)));
+        m[TQGPU_KKT_GCOMPL] = nanmax(m[TQGPU_KKT_GCOMPL], fabs(kkt_compl(mu, g, lo, hi)));
+    }
+    const bool have_z = nz - pad > 0;
+    const bool have[KKT_CLASSES] = {have_z, k > 0 && nxk > 0, have_z, have_z, nc > 0, nc > 0};
+#pragma unroll
+    for (int c = 0; c < KKT_CLASSES; c++) {
+        const double v = wmax(m[c]);
+        if (lane == 0) table[(size_t)KKT_CLASSES * k + c] = have[c] ? v : -1.0;
+    }
+}
+
+/* (v, n) before (bv, bn): a NaN first, then the larger value, the lower node among equals; n < 0: nothing yet */
+__device__ __forceinline__ bool kkt_before(double v, int n, double bv, int bn) {
+    if (n < 0) return false;
+    if (bn < 0) return true;
+    const bool vn = v != v, bvn = bv != bv;
+    if (vn || bvn) return vn && (!bvn || n < bn);
+    return v > bv || (v == bv && n < bn);
+}
+
+/* One workgroup: the table's six columns to six maxima and the lowest nodes that attain them (head[0..6), ints at head + 6; node -1
+ * and value 0 for a class without entries); the table's -1 marks become 0.  A fixed tree of comparisons, no atomics. */
+__global__ void __launch_bounds__(256) k_kkt_max(int Nn, double *table, double *head) {
+    __shared__ double sv[256];
+    __shared__ int sn[256];
+    const int t = threadIdx.x;
+    int *node = reinterpret_cast<int *>(head + KKT_CLASSES);
+    for (int c = 0; c < KKT_CLASSES; c++) {
+        double bv = 0.0; int bn = -1;
+        for (int k = t; k < Nn; k += 256) {
+            const double v = table[(size_t)KKT_CLASSES * k + c];
+            if (v < 0.0) { table[(size_t)KKT_CLASSES * k + c] = 0.0; continue; }
+            if (kkt_before(v, k, bv, bn)) { bv = v; bn = k; }
+        }
+        sv[t] = bv; sn[t] = bn;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if (t < w && kkt_before(sv[t + w], sn[t + w], sv[t], sn[t])) { sv[t] = sv[t + w]; sn[t] = sn[t + w]; }
+            __syncthreads();
+        }
+        if (t == 0) { head[c] = sn[0] < 0 ? 0.0 : sv[0]; node[c] = sn[0]; }
+        __syncthreads();
+    }
+}
+
 /* ---- tqgpu_create step by step: each step takes the mirror and returns a TQGPU_* code ---- */
-/* THE list of creation-time switches.  Read per tqgpu_create call, never cached: tests and A/B runs change them between two mirrors. */
+/* THE list of creation-time switches. Read per tqgpu_create call, never cached: tests and A/B runs change them between two mirrors. */
 void read_switches(Switches &w) {
     auto set = [](const char *name) { return getenv(name) != nullptr; };
     auto is = [](const char *name, const char *value) { const char *e = getenv(name); return e && strcmp(e, value) == 0; };
@@ -3163,6 +3286,25 @@ int setup_single_wg(tqgpu_solver *s) {
             tab.push_back(grp);
         }
         return s->mem.upload(s->d_lvl_first, tab.data(), sizeof(int) * tab.size(), TQGPU_ENOMEM, "the level table");
+    }
+    return TQGPU_OK;
+}
+
+/* the buffers of tqgpu_kkt_residual*, on first use (most mirrors never ask): the result block, and with_point the scratch point of
+ * tqgpu_kkt_residual_at, which grows when tqgpu_set_constraints has added rows since */
+int setup_kkt(tqgpu_solver *s, bool with_point) {
+    int rc;
+    const size_t res_bytes = sizeof(double) * (KKT_HEAD + (size_t)KKT_CLASSES * s->Nn);
+    if (!s->d_kkt && ((rc = s->mem.device(s->d_kkt, res_bytes, TQGPU_ENOMEM, "the KKT residuals")) || (rc = s->mem.host(s->h_kkt, res_bytes, "the host mirror of the KKT residuals"))))
+        return rc;
+    const size_t need = 2 * (size_t)(s->sum_nx - s->x_pad) + 2 * (size_t)s->sum_nu + (size_t)s->sum_lam + (size_t)s->sum_nc;
+    if (with_point && (!s->d_kkt_pt || need > s->kkt_pt_cap)) {
+        s->mem.release(s->d_kkt_pt); s->mem.release(s->h_kkt_pt);
+        s->kkt_pt_cap = 0;
+        if ((rc = s->mem.device(s->d_kkt_pt, sizeof(double) * std::max<size_t>(need, 1), TQGPU_ENOMEM, "the point of tqgpu_kkt_residual_at")) ||
+            (rc = s->mem.host(s->h_kkt_pt, sizeof(double) * std::max<size_t>(need, 1), "the host mirror of that point")))
+            return rc;
+        s->kkt_pt_cap = need;
     }
     return TQGPU_OK;
 }
@@ -4227,14 +4369,14 @@ static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const Solve
     return solve_end(s, o, cx, res);
 }
 
-static int enqueue_export(tqgpu_solver *s, const double *lamc) {
+static int enqueue_export(tqgpu_solver *s, const double *lamc, bool download = true) {      /* download = false: d_out only (tqgpu_kkt_residual reads it there) */
     const Data &D = s->D;
     const int nxe = s->sum_nx - s->x_pad, nue = s->sum_nu, nl = s->sum_lam;
     const int n = std::max(std::max(nxe, nue), std::max(nl, 1));
     hipLaunchKernelGGL(k_export_all, dim3((n + 255) / 256), dim3(256), 0, s->stream, nxe, nue, nl, s->x_pad, s->nx0, D, lamc, s->d_out);
     if (s->box) hipLaunchKernelGGL(k_export_box, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
     if (s->gen) hipLaunchKernelGGL(k_export_gen, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
-    HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, s->stream));
+    if (download) HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, s->stream));
     return TQGPU_OK;
 }
 
@@ -5135,6 +5277,100 @@ extern "C" int tqgpu_get_solution(tqgpu_solver *s, double *x, double *u, double 
     if (dlam && nl > 0) memcpy(dlam, od, sizeof(double) * (size_t)nl);
     if (mu_x && nxe > 0) memcpy(mu_x, omx, sizeof(double) * (size_t)nxe);
     if (mu_u && nue > 0) memcpy(mu_u, omu, sizeof(double) * (size_t)nue);
+    return TQGPU_OK;
+}
+
+/* ---- KKT residuals on the device ---- */
+namespace {
+/* the two kernels and the download of the result block, on the mirror's stream; nothing is waited for */
+int kkt_enqueue(tqgpu_solver *s, const KktPoint &P, bool per_node) {
+    hipLaunchKernelGGL(k_kkt, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, s->D, s->x_pad, P, s->d_kkt + KKT_HEAD);
+    hipLaunchKernelGGL(k_kkt_max, dim3(1), dim3(256), 0, s->stream, s->T.Nn, s->d_kkt + KKT_HEAD, s->d_kkt);
+    HIP_TRY(hipGetLastError());
+    const size_t n = KKT_HEAD + (per_node ? (size_t)KKT_CLASSES * s->Nn : 0);
+    HIP_TRY(hipMemcpyAsync(s->h_kkt, s->d_kkt, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
+    return TQGPU_OK;
+}
+void kkt_collect(const tqgpu_solver *s, double *res, int *node, double *per_node) {
+    if (res) memcpy(res, s->h_kkt, sizeof(double) * KKT_CLASSES);
+    if (node) memcpy(node, s->h_kkt + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
+    if (per_node) memcpy(per_node, s->h_kkt + KKT_HEAD, sizeof(double) * (size_t)KKT_CLASSES * s->Nn);
+}
+/* what every entry point refuses: a rank of a sharded solve holds a part of the solution and runs a part of the launches */
+int kkt_refuse(const tqgpu_solver *s, const char *who) {
+    if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
+    if ((s->pshard || s->sharded) && s->nranks > 1)
+        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": this mirror is rank " + std::to_string(s->rank) + " of a sharded solve; KKT residuals are evaluated on single-device mirrors");
+    return TQGPU_OK;
+}
+/* the point of the last solve, where tqgpu_get_solution and tqgpu_get_mu_d read it: the export (enqueued here unless it went out ahead) and Gen::mu */
+int kkt_enqueue_last(tqgpu_solver *s, bool per_node) {
+    int rc;
+    if (s->solve_no == 0) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual: this mirror has not solved yet (tqgpu_kkt_residual_at takes any point)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = setup_kkt(s, false))) return rc;
+    if (!s->export_valid && (rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
+    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), nue = (size_t)s->sum_nu, nl = (size_t)s->sum_lam;
+    KktPoint P;
+    P.x = s->d_out; P.u = P.x + nxe; P.lam = P.u + nue; P.mu_x = P.lam + 2 * nl; P.mu_u = P.mu_x + nxe;
+    P.mu_d = s->gen ? s->d_gmu : nullptr;
+    return kkt_enqueue(s, P, per_node);
+}
+}  // namespace
+
+extern "C" int tqgpu_kkt_residual(tqgpu_solver *s, double res[6], int node[6], double *per_node) {
+    SETTLE(s);
+    int rc;
+    if ((rc = kkt_refuse(s, "tqgpu_kkt_residual")) || (rc = kkt_enqueue_last(s, per_node != nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    kkt_collect(s, res, node, per_node);
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_kkt_residual_at(tqgpu_solver *s, const double *x, const double *u, const double *lam, const double *mu_x, const double *mu_u,
+                                     const double *mu_d, double res[6], int node[6], double *per_node) {
+    SETTLE(s);
+    int rc;
+    if ((rc = kkt_refuse(s, "tqgpu_kkt_residual_at"))) return rc;
+    if (!x || !u || !lam) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_at: x, u and lam are required");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = setup_kkt(s, true))) return rc;
+    /* the point through pinned memory in one copy; an array that was not given stays a null pointer for the kernel */
+    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), nue = (size_t)s->sum_nu, nl = (size_t)s->sum_lam, nr = (size_t)s->sum_nc;
+    size_t off = 0;
+    auto put = [&](const double *src, size_t n) -> const double * {
+        if (!src) return nullptr;
+        if (n) memcpy(s->h_kkt_pt + off, src, sizeof(double) * n);
+        const double *d = s->d_kkt_pt + off;
+        off += n;
+        return d;
+    };
+    KktPoint P;
+    P.x = put(x, nxe); P.u = put(u, nue); P.lam = put(lam, nl); P.mu_x = put(mu_x, nxe); P.mu_u = put(mu_u, nue); P.mu_d = put(mu_d, nr);
+    if (off) HIP_TRY(hipMemcpyAsync(s->d_kkt_pt, s->h_kkt_pt, sizeof(double) * off, hipMemcpyHostToDevice, s->stream));
+    if ((rc = kkt_enqueue(s, P, per_node != nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    kkt_collect(s, res, node, per_node);
+    return TQGPU_OK;
+}
+
+/* every member's evaluation goes out on its own stream before the first wait */
+extern "C" int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *res, int *node) {
+    if (!solvers || n < 0 || (n > 0 && !res)) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_batch: bad arguments");
+    int rc;
+    for (int i = 0; i < n; i++) {
+        if ((rc = kkt_refuse(solvers[i], "tqgpu_kkt_residual_batch"))) return rc;
+        if (solvers[i]->solve_no == 0) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_batch: member " + std::to_string(i) + " has not solved yet");
+    }
+    for (int i = 0; i < n; i++) {
+        SETTLE(solvers[i]);
+        if ((rc = kkt_enqueue_last(solvers[i], false))) return rc;
+    }
+    for (int i = 0; i < n; i++) {
+        HIP_TRY(hipSetDevice(solvers[i]->device));
+        HIP_TRY(hipStreamSynchronize(solvers[i]->stream));
+        kkt_collect(solvers[i], res + (size_t)KKT_CLASSES * i, node ? node + (size_t)KKT_CLASSES * i : nullptr, nullptr);
+    }
     return TQGPU_OK;
 }
 
