@@ -68,9 +68,25 @@ typedef struct tqgpu_result {
     int ls_last;                 /* trials of the last iteration */
     int n_launches;              /* kernels launched during the solve */
     double device_time;          /* seconds between the first and last kernel (HIP events) */
-    double last_error_norm;      /* termination norm at exit */
-    double last_fval;            /* dual function value at the last accepted point */
+    double last_error_norm;      /* termination norm (opts->termCondition: sum of squares, two-norm or largest entry of the dynamics residual), see below */
+    double last_fval;            /* dual function value as the solver minimises it, see below */
 } tqgpu_result;
+/* Which point last_error_norm and last_fval belong to, per exit (the pairing of the reference's loop, dual_Newton_tree.c:1166-1228: the norm
+ * is taken when an iteration starts, the value when its line search ends):
+ *   status 0 (optimal)         last_error_norm: at the returned point -- the norm of A x_dad + B u_dad + b - x of the returned x, u; below the
+ *                              tolerance.  last_fval: at the returned lam, the point the last line search accepted (iter >= 1).  With iter == 0
+ *                              (the starting duals were optimal) no line search ran and last_fval belongs to no accepted point.
+ *   status 1 (max iterations)  the two belong to DIFFERENT points.  last_error_norm: at the point the last iteration started from,
+ *                              lam - beta^(t - 1) dlam of the returned lam and dlam, t = min(ls_last, lineSearchMaxIter) the trials made (ls_last is
+ *                              lineSearchMaxIter + 1 when none was accepted); the starting duals for maxIter = 1.  last_fval:
+ *                              at the returned lam, the last trial's point (accepted, or the last one tried when the line search ran out).
+ *                              maxIter <= 0: nothing is iterated; status 1, iter, ls_total, ls_last, last_error_norm and last_fval are 0 on
+ *                              every route, whatever an earlier solve reported (tqgpu_pshard_begin refuses maxIter <= 0).
+ *   status 2 (not a descent direction)  last_error_norm: at the point the failed iteration started from, NaN if the data or the duals hold a
+ *                              NaN (the largest-entry norm keeps a NaN); last_fval is not that of the returned point.
+ *   status 4 (stage QP solve failed)    neither belongs to the returned point.
+ * ls_last is the last entry of tqgpu_get_iteration_log and ls_total the sum of its first `iter` entries.  A member of tqgpu_solve_batch and
+ * every rank of a sharded solve report their own solve's values. */
 
 int tqgpu_device_count(void);
 const char *tqgpu_last_error(void);

@@ -290,14 +290,7 @@ def newton_step(d, lam0, kinds, reg=0.0):
 
 
 def dual_terms(d, lam, kinds):
-    st = stage_solutions(d, lam, kinds)
-    nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, kd = st["tree"]
-    lam = np.asarray(lam, dtype=LD)
-    out = np.zeros(len(nk), dtype=LD)
-    for p, (zk, h) in enumerate(zip(st["z"], st["h"])):
-        Hz = st["H"][p].astype(LD) * zk if st["H"][p].ndim == 1 else st["H"][p].astype(LD) @ zk
-        out[p] = -LD(0.5) * (zk @ Hz) + h @ zk - sum((b[k] @ lam[lo_[k]:lo_[k] + nx[k]] for k in kids[p]), LD(0))
-    return out
+    return N.terms_of_stages(stage_solutions(d, lam, kinds), lam)[0]
 
 
 def armijo_trials(d, lam0, dlam, res, opts, kinds):

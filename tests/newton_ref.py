@@ -235,10 +235,8 @@ def flat_xu(st):
     return x, u, sx, su
 
 
-def assemble(d, lam0, dense=False, kinds=None):
-    """The Newton system at lam0, in longdouble: (M, res, stages) with M = G P G' the negated dual Hessian, res the dynamics
-    residual and stages what stage_solutions returns (its "tree" holds the offsets of the duals)."""
-    st = stage_solutions(d, lam0, dense, kinds)
+def assemble_from(st):
+    """(M, res) of assemble from stage solutions st (stage_solutions' here, or gen_ref's)"""
     nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, _ = st["tree"]
     z, Pm = st["z"], st["P"]
     Nn = len(nk)
@@ -259,7 +257,14 @@ def assemble(d, lam0, dense=False, kinds=None):
             blk = -CP[:, :nx[p]]
             M[ik, ip] += blk
             M[ip, ik] += blk.T
-    return M, res, st
+    return M, res
+
+
+def assemble(d, lam0, dense=False, kinds=None):
+    """The Newton system at lam0, in longdouble: (M, res, stages) with M = G P G' the negated dual Hessian, res the dynamics
+    residual and stages what stage_solutions returns (its "tree" holds the offsets of the duals)."""
+    st = stage_solutions(d, lam0, dense, kinds)
+    return assemble_from(st) + (st,)
 
 
 def newton_step(d, lam0, dense=False, kinds=None, reg=0.0):
@@ -298,17 +303,46 @@ def starting_duals(d, dense=False, tries=20, gap=1e-6, kinds=None):
     raise AssertionError(f"no lambda0 of {tries} seeds keeps the stage values {gap} away from the clipping thresholds")
 
 
+def abs_h(st, lam, p):
+    """T_h of node p: the sum of the absolute values of the terms of h = [lam_p - q - sum A'lam | -r - sum B'lam]"""
+    nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, kd = st["tree"]
+    lam = np.asarray(lam, dtype=LD)
+    h = st["h"][p]
+    Th, own = np.zeros(len(h), dtype=LD), h.copy()
+    if p > 0:
+        lp = lam[lo_[p]:lo_[p] + nx[p]]
+        Th[:nx[p]] += np.abs(lp)
+        own[:nx[p]] -= lp
+    for k in kids[p]:
+        l = lam[lo_[k]:lo_[k] + nx[k]]
+        Th += np.concatenate([np.abs(A[k]).T @ np.abs(l), np.abs(B[k]).T @ np.abs(l)])
+        own = own + np.concatenate([A[k].T @ l, B[k].T @ l])
+    return Th + np.abs(own)                                # (own: -q, -r, what h holds beside the duals)
+
+
+def terms_of_stages(st, lam):
+    """The nodes' terms of the dual function from stage solutions st at lam (what stage_solutions, here or in gen_ref, returns):
+    (terms, scales), both per node in longdouble.  terms[p] = -1/2 z'H z + h'z - sum_children b_k'lambda_k; scales[p] is the sum of
+    the absolute values of every product inside it, with the sums that make up h taken apart as well:
+    1/2 |z|'|H||z| + T_h'|z| + sum_children |b_k|'|lambda_k|, T_h = |lambda_p| + |q| + sum_children |A_k|'|lambda_k| (and |r|,
+    |B_k|'|lambda_k| on the inputs)."""
+    nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, kd = st["tree"]
+    lam = np.asarray(lam, dtype=LD)
+    out, scale = np.zeros(len(nk), dtype=LD), np.zeros(len(nk), dtype=LD)
+    for p, (zk, h) in enumerate(zip(st["z"], st["h"])):
+        Hp = st["H"][p].astype(LD)
+        Hz, aHz = (Hp * zk, np.abs(Hp) * np.abs(zk)) if Hp.ndim == 1 else (Hp @ zk, np.abs(Hp) @ np.abs(zk))
+        lk = [lam[lo_[k]:lo_[k] + nx[k]] for k in kids[p]]
+        out[p] = -LD(0.5) * (zk @ Hz) + h @ zk - sum((b[k] @ l for k, l in zip(kids[p], lk)), LD(0))
+        Th = abs_h(st, lam, p)
+        scale[p] = LD(0.5) * (np.abs(zk) @ aHz) + Th @ np.abs(zk) + sum((np.abs(b[k]) @ np.abs(l) for k, l in zip(kids[p], lk)), LD(0))
+    return out, scale
+
+
 def dual_terms(d, lam, kinds=None, dense=False):
     """The nodes' terms of the dual function at lam, as the kernels take them: -1/2 z'H z + h'z - sum_children b_k'lambda_k, in
     longdouble."""
-    st = stage_solutions(d, lam, dense, kinds)
-    nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, kd = st["tree"]
-    lam = np.asarray(lam, dtype=LD)
-    out = np.zeros(len(nk), dtype=LD)
-    for p, (zk, h) in enumerate(zip(st["z"], st["h"])):
-        Hz = st["H"][p].astype(LD) * zk if st["H"][p].ndim == 1 else st["H"][p].astype(LD) @ zk
-        out[p] = -LD(0.5) * (zk @ Hz) + h @ zk - sum((b[k] @ lam[lo_[k]:lo_[k] + nx[k]] for k in kids[p]), LD(0))
-    return out
+    return terms_of_stages(stage_solutions(d, lam, dense, kinds), lam)[0]
 
 
 def dual_value(d, lam, kinds=None, dense=False):

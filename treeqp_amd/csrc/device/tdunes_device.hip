@@ -5252,7 +5252,11 @@ extern "C" int tqgpu_solve_virtual_ranks(tqgpu_solver **R, int n, const tqgpu_op
     }
     /* gather the partitioned solution ranges into every mirror (nothing iterated: only the wait for the streams) */
     if (o->maxIter > 0) { if ((rc = allgather_virtual(R, n, solution_ranges))) return rc; }
-    else for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
+    else for (int r = 0; r < n; r++) {
+        /* as end_enqueued: reported as "maximum iterations" with every count and both values 0, whatever the last solve left in the host copy */
+        HIP_TRY(hipStreamSynchronize(R[r]->stream));
+        memset(R[r]->h_ctrl, 0, sizeof(Ctrl)); R[r]->h_ctrl->status = 1;
+    }
     const Ctrl &c = *R[0]->h_ctrl;
     fill_result(res, c, launches, 0.0);
     for (int r = 0; r < n; r++) R[r]->last_iter = c.iter;
