@@ -189,14 +189,27 @@ int tqgpu_get_solution(tqgpu_solver *s, double *x, double *u, double *lam, doubl
  * tqgpu_kkt_residual_at: any point (a warm start, another solver's answer) in the flat layout of tqgpu_get_solution, mu_d as
  *   tqgpu_get_mu_d gives it; x, u, lam are required, a NULL multiplier array is all zeros.  Needs an uploaded problem, no solve, and
  *   changes nothing a later solve or tqgpu_get_solution reads.
- * tqgpu_kkt_residual_batch: every member's evaluation is enqueued on its own stream, then each is waited for once; res n x 6, node
- *   n x 6 or NULL; member i gets bit for bit what tqgpu_kkt_residual(solvers[i]) gives.
+ * tqgpu_kkt_residual_batch: res n x 6, node n x 6 or NULL; member i gets bit for bit what tqgpu_kkt_residual(solvers[i]) gives.  The
+ *   members of one device are checked together on the stream of the first of them: one upload of a descriptor per member, at most five
+ *   launches (the packing of the members that have not exported ahead -- up to three -- , one wave per (member, node), one workgroup per
+ *   member for the maxima), one download of all heads and one wait, whatever n.  A member's own stream is waited for only where it may
+ *   hold work that stream has not seen: uploads since its last synchronisation, an export that went out ahead, a solve of its own
+ *   (tqgpu_solve) since its last check; behind a tqgpu_solve_batch whose launch the members shared nothing is.  A member alone on its
+ *   device, a batch that names a mirror twice and one in which a single tree is most of the nodes go member by member: everything is
+ *   enqueued on the members' own streams (3 to 5 launches and a copy each), then each is waited for once.
+ *   TREEQP_AMD_KKT_BATCH=members in the environment, read at each call, forces that route (A/B runs, escape hatch).
+ *   Afterwards the members' solution is packed on the device but not downloaded: tqgpu_get_solution does what it does behind
+ *   tqgpu_kkt_residual.
+ * tqgpu_kkt_batch_stats: what the calling thread's last tqgpu_kkt_residual_batch cost, summed over devices: kernel launches, copies (either
+ *   direction), stream waits, and the members that went through the batched kernels (0 on the per-member route).  Any pointer may be
+ *   NULL; reads host state only.
  * A rank of a sharded solve (tqgpu_pshard_init / tqgpu_shard_init with nranks > 1) is refused with TQGPU_EUNSUPPORTED by all three. */
 int tqgpu_kkt_residual(tqgpu_solver *s, double res[6], int node[6], double *per_node);
 int tqgpu_kkt_residual_at(tqgpu_solver *s, const double *x, const double *u, const double *lam,
                           const double *mu_x, const double *mu_u, const double *mu_d,
                           double res[6], int node[6], double *per_node);
 int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *res, int *node);
+int tqgpu_kkt_batch_stats(int *launches, int *copies, int *waits, int *batched_members);
 
 /* 2: persistent single-launch solve (tdunes_persist.hpp); 1: tiered fused kernels (tdunes_fast.hpp);
  * 0: generic per-level kernels.  TREEQP_AMD_PATH=generic|tiered in the environment at create time

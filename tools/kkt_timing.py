@@ -2,10 +2,10 @@
 behind the packing kernel, 12 values back) against the host path of the reference's drivers (tqgpu_get_solution, then
 tree_qp_out_max_KKT_res over the container, as solve_qp_json.c does it).
 
-    python tools/kkt_timing.py [--rounds 300] [--warmup 30] [--batch 64] [c2] [c3] [batch]
+    python tools/kkt_timing.py [--rounds 300] [--warmup 30] [--batch 2,16,64,256] [c2] [c3] [batch]
 
 Workloads: c2 = problems.linear_chain(2, 9, 9), 1 023 nodes; c3 = linear_chain(2, 11, 11), 4 095 nodes (both one persistent
-launch per solve); batch = 64 mirrors of C1, problems.spring_mass(), through tqgpu_solve_batch.
+launch per solve); batch = 2, 16, 64 and 256 mirrors of C1, problems.spring_mass(), through tqgpu_solve_batch.
 
 Per workload, in one process and alternating round by round so that all share the machine's state:
 
@@ -17,10 +17,14 @@ Per workload, in one process and alternating round by round so that all share th
 Every timed call ends in a device synchronisation or is host code; the clock is the host's perf_counter around the calls, made
 straight through ctypes with prepared arguments.  Reported: median, min and p90 in microseconds, and the two costs of a check:
 device = (solve+kkt) - solve; host = (solve+get) - solve + host_kkt.  The host figure leaves out the caller's copy of the arrays
-into tree_qp_out, which the drivers also pay.  For the batch: tqgpu_solve_batch alone, with tqgpu_kkt_residual_batch, with one
-tqgpu_get_solution per member, and tree_qp_out_max_KKT_res over every member's container.  The device figure and the host figure
-of the last round are printed side by side as a check that both certify the same point."""
+into tree_qp_out, which the drivers also pay.  For the batch: tqgpu_solve_batch alone, with tqgpu_kkt_residual_batch on both
+of its routes (solve+kkt: the members in one set of launches; solve+kkt/m: member by member, TREEQP_AMD_KKT_BATCH=members), with one
+tqgpu_get_solution per member, and tree_qp_out_max_KKT_res over every member's container; per route the device cost of every round
+(that round minus the median solve) as median, min and p90, and what tqgpu_kkt_batch_stats counted.  A library without that symbol
+(TREEQP_AMD_LIB pointing at an earlier build, for the comparison with a parent commit) runs its one route under both names.  The
+device figure and the host figure of the last round are printed side by side as a check that both certify the same point."""
 import ctypes as C
+import os
 import sys
 import time
 from pathlib import Path
@@ -114,6 +118,19 @@ def batch(capi, n, rounds, warmup):
         solve()
         assert L.tqgpu_kkt_residual_batch(arr, n, rp, npn) == 0
 
+    cost = {}
+
+    def solve_kkt_members():
+        os.environ["TREEQP_AMD_KKT_BATCH"] = "members"          # read by the library at each call
+        try:
+            solve_kkt()
+        finally:
+            del os.environ["TREEQP_AMD_KKT_BATCH"]
+        cost["members"] = batch_stats()
+
+    def batch_stats():
+        return capi.kkt_batch_stats() if hasattr(L, "tqgpu_kkt_batch_stats") else None
+
     def solve_get():
         solve()
         for g in ms:
@@ -128,7 +145,7 @@ def batch(capi, n, rounds, warmup):
     def host_kkt():
         host[0] = max(L.tree_qp_out_max_KKT_res(a, b) for a, b in refs)
 
-    modes = dict(solve=solve, **{"solve+kkt": solve_kkt, "solve+get": solve_get, "host_kkt": host_kkt})
+    modes = dict(solve=solve, **{"solve+kkt": solve_kkt, "solve+kkt/m": solve_kkt_members, "solve+get": solve_get, "host_kkt": host_kkt})
     ts = {k: [] for k in modes}
     for i in range(warmup + rounds):
         for k, f in modes.items():
@@ -136,11 +153,21 @@ def batch(capi, n, rounds, warmup):
             f()
             if i >= warmup:
                 ts[k].append(time.perf_counter() - t0)
+            if k == "solve+kkt":
+                cost["batched"] = batch_stats()
     print(f"batch of {n} x C1 ({p.Nn} nodes each, path {g0.path}), status {sorted({rs[i].status for i in range(n)})}; {rounds} rounds after {warmup}", flush=True)
     med = {k: line(k, v) for k, v in ts.items()}
-    dev, hst = med["solve+kkt"] - med["solve"], med["solve+get"] - med["solve"] + med["host_kkt"]
-    print(f"    a check of the batch costs: device {dev:8.1f} us, host {hst:8.1f} us (downloads {med['solve+get'] - med['solve']:.1f} + loops {med['host_kkt']:.1f}); "
-          f"device / host = {dev / hst:.2f}; the batch solve alone {med['solve']:.1f} us", flush=True)
+    hst = med["solve+get"] - med["solve"] + med["host_kkt"]
+    # the device cost round by round (the check's round minus the median solve), so that a route's median can be held against the
+    # other's minimum
+    for k, what in (("solve+kkt", "one set of launches"), ("solve+kkt/m", "member by member (TREEQP_AMD_KKT_BATCH=members)")):
+        d = np.asarray(ts[k]) - 1e-6 * med["solve"]
+        dm, dlo, dp90 = stats(d)
+        c = cost.get("batched" if k == "solve+kkt" else "members")
+        print(f"    a check of the batch costs, {what}: device {dm:8.1f} us median, {dlo:8.1f} min, {dp90:8.1f} p90"
+              + (f"; {c['launches']} launches, {c['copies']} copies, {c['waits']} waits, {c['batched_members']} members batched" if c else ""), flush=True)
+    print(f"    host {hst:8.1f} us (downloads {med['solve+get'] - med['solve']:.1f} + loops {med['host_kkt']:.1f}); "
+          f"the batch solve alone {med['solve']:.1f} us", flush=True)
     print(f"    max KKT residual over the batch: device {res.max():.3e}, host {host[0]:.3e}", flush=True)
     for g in ms:
         g.close()
@@ -148,11 +175,11 @@ def batch(capi, n, rounds, warmup):
 
 def main():
     args = sys.argv[1:]
-    rounds, warmup, nb = 300, 30, 64
+    rounds, warmup, nb = 300, 30, "2,16,64,256"
     while args and args[0].startswith("--"):
         if args[0] == "--rounds": rounds = int(args[1])
         if args[0] == "--warmup": warmup = int(args[1])
-        if args[0] == "--batch": nb = int(args[1])
+        if args[0] == "--batch": nb = args[1]
         args = args[2:]
     from treeqp_amd import capi, problems as P
     if capi.device_count() < 1:
@@ -163,7 +190,8 @@ def main():
     if "c3" in todo:
         single(capi, "C3", P.linear_chain(2, 11, 11), rounds, warmup)
     if "batch" in todo:
-        batch(capi, nb, max(rounds // 3, 20), max(warmup // 3, 5))
+        for n in (int(v) for v in nb.split(",")):
+            batch(capi, n, max(rounds // 3, 20), max(warmup // 3, 5))
     return 0
 
 

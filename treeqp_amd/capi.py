@@ -486,8 +486,8 @@ def _kkt_dict(res, node, per_node=None) -> dict:
 
 
 def kkt_residual_batch(mirrors) -> list:
-    """KKT residuals of the last solve of every mirror, evaluated on the device: all enqueued, then one wait per member
-    (tqgpu_kkt_residual_batch) -> one dict of TqGpu.kkt_residual per member."""
+    """KKT residuals of the last solve of every mirror, evaluated on the device: the members of one device in one set of launches
+    and one wait (tqgpu_kkt_residual_batch; what it cost: kkt_batch_stats) -> one dict of TqGpu.kkt_residual per member."""
     n = len(mirrors)
     arr = (C.c_void_p * n)(*[m.h for m in mirrors])
     res, node = np.zeros((n, 6)), np.zeros((n, 6), dtype=np.int32)
@@ -495,6 +495,16 @@ def kkt_residual_batch(mirrors) -> list:
     if rc != 0:
         raise RuntimeError(f"tqgpu_kkt_residual_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
     return [_kkt_dict(res[i].copy(), node[i].copy()) for i in range(n)]
+
+
+def kkt_batch_stats() -> dict:
+    """What this thread's last kkt_residual_batch cost, summed over devices (tqgpu_kkt_batch_stats): kernel launches, copies, stream
+    waits, and batched_members, the members that went through the batched kernels (0 with TREEQP_AMD_KKT_BATCH=members)."""
+    v = [C.c_int(0) for _ in range(4)]
+    rc = lib().tqgpu_kkt_batch_stats(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_kkt_batch_stats failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    return dict(zip(("launches", "copies", "waits", "batched_members"), (x.value for x in v)))
 
 
 def solve_batch_n(mirrors, steps: int, profile=0, **kw):

@@ -1831,6 +1831,8 @@ struct Switches {
     int chunk, lds_pad, capacity_margin, nap;
 };
 
+namespace { struct KItem; struct KHead; }      /* the batched KKT check's descriptor and head (defined with its kernels) */
+
 struct tqgpu_solver {
     Owned mem;
     Switches sw{};
@@ -1960,6 +1962,11 @@ struct tqgpu_solver {
     /* tqgpu_kkt_residual*: [six maxima | six nodes | pad | Nn x 6 table] on the device and pinned (setup_kkt, on first use); the point of
      * tqgpu_kkt_residual_at, [x | u | lam | mu_x | mu_u | mu_d], on the device and pinned (grows with sum_nc) */
     double *d_kkt = nullptr, *h_kkt = nullptr, *d_kkt_pt = nullptr, *h_kkt_pt = nullptr; size_t kkt_pt_cap = 0;
+    /* tqgpu_kkt_residual_batch, batched route (the first member of a device's group owns both): one descriptor per member, uploaded
+     * with every call, and the members' heads in one block, downloaded in one copy */
+    KItem *d_kitems = nullptr, *h_kitems = nullptr; int kitems_cap = 0;
+    KHead *d_kheads = nullptr, *h_kheads = nullptr; int kheads_cap = 0;
+    long kkt_drained_at = 0;            /* solve_no at which the batched route last knew this mirror's own stream to hold nothing of its solves */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -2786,8 +2793,7 @@ void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launch
 
 /* solution export in one piece: out = [x | u | lam | dlam | mu_x | mu_u] (x and mu_x without the phantom root
  * states), mu = Q .* (xUnc - x) (export_mu, clipping.c:386-399) */
-__global__ void k_export_all(int n_x, int n_u, int n_lam, int x_pad, int nx0, Data D, const double *lamc, double *out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void export_all_entry(int i, int n_x, int n_u, int n_lam, int x_pad, int nx0, const Data &D, const double *lamc, double *out) {
     double *ox = out, *ou = ox + n_x, *ol = ou + n_u, *od = ol + n_lam, *omx = od + n_lam, *omu = omx + n_x;
     /* MAXIMUM_ITERATIONS_REACHED with at least one iteration done: x, u are the last trial's, the unclipped values phase S's (see Data) */
     const bool maxit = D.ctrl->status == 1 && D.ctrl->iter > 0;
@@ -2802,13 +2808,15 @@ __global__ void k_export_all(int n_x, int n_u, int n_lam, int x_pad, int nx0, Da
         ol[i] = lc[nx0 + i]; od[i] = D.dlam[nx0 + i];
     }
 }
+__global__ void k_export_all(int n_x, int n_u, int n_lam, int x_pad, int nx0, Data D, const double *lamc, double *out) {
+    export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, n_x, n_u, n_lam, x_pad, nx0, D, lamc, out);
+}
 
 /* multipliers of the box nodes' bounds (export of the qpOASES stage solver, dual_Newton_tree_qpoases.c:524-560), over what
  * k_export_all wrote for them: mu = hmod - H z with the reference's sign, on the working set; 0 on free entries.  On a
  * MAXIMUM_ITERATIONS exit hmod is phase S's and z the last trial's, on every entry: the pairing of export_mu on clipping nodes
  * (see Data::xUncS), and on a diagonal node the same numbers.  One wave per node, lane = entry. */
-__global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
+__device__ __forceinline__ void export_box_node(const Tree &T, const Data &D, int n_x, int n_u, int n_lam, int x_pad, double *out, int k, int lane) {
     if (!D.dense || D.kind[k] != 2) return;
     const int nxk = T.nx[k], nz = nxk + T.nu[k], xo = T.xoff[k], uo = T.uoff[k];
     if (lane >= nz || (k == 0 && lane < x_pad)) return;           /* (phantom root states are not exported) */
@@ -2823,11 +2831,13 @@ __global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, in
     double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
     if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
 }
+__global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
+    export_box_node(T, D, n_x, n_u, n_lam, x_pad, out, blockIdx.x, threadIdx.x);
+}
 
 /* the same for the nodes with general constraints (kind 3): mu = hmod - H z - G' mu_d on the fixed entries, with the row multipliers
  * stage_gen left in Gen::mu (the sign of tree_qp_out_calculate_KKT_res: Qx + q + ... + mu_x + C' mu_d = 0) */
-__global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
+__device__ __forceinline__ void export_gen_node(const Tree &T, const Data &D, int n_x, int n_u, int n_lam, int x_pad, double *out, int k, int lane) {
     if (!D.dense || D.kind[k] != 3) return;
     const Gen &Gn = *D.gen;
     const int nxk = T.nx[k], nz = nxk + T.nu[k], xo = T.xoff[k], uo = T.uoff[k], nc = Gn.nc[k];
@@ -2843,6 +2853,9 @@ __global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, in
     const double mu = (maxit || ((D.bmask[k] >> lane) & 1ull)) ? h - hz : 0.0;
     double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
     if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
+}
+__global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
+    export_gen_node(T, D, n_x, n_u, n_lam, x_pad, out, blockIdx.x, threadIdx.x);
 }
 
 /* ---- KKT residuals of a point, evaluated where the data is (tqgpu_kkt_residual*; tree_qp_out_calculate_KKT_res, tree_qp_common.c:540-788) ----
@@ -2863,8 +2876,7 @@ __device__ __forceinline__ double kkt_z(const KktPoint &P, int j, int nxn, int x
 /* One wave per node: lane j owns entry j of [x | u], then of the rows, striding by 64 on larger nodes.  Per class the largest absolute
  * entry of the node, NaN kept (nanmax / wmax), goes to table[6 k + class]; -1 where the node has no entry of the class.  Nodes of kind 1
  * ignore their bounds (entries 0); rows count on nodes of kind 3 only. */
-__global__ void __launch_bounds__(WAVE) k_kkt(Tree T, Data D, int x_pad, KktPoint P, double *table) {
-    const int k = blockIdx.x, lane = threadIdx.x;
+__device__ __forceinline__ void kkt_node(const Tree &T, const Data &D, int x_pad, const KktPoint &P, double *table, int k, int lane) {
     const int nxk = T.nx[k], nuk = T.nu[k], nz = nxk + nuk, xo = T.xoff[k], uo = T.uoff[k], nx0 = T.nx0;
     const int pad = k == 0 ? x_pad : 0;
     const int kind = D.dense ? D.kind[k] : 0;
@@ -2930,6 +2942,9 @@ __global__ void __launch_bounds__(WAVE) k_kkt(Tree T, Data D, int x_pad, KktPoin
         if (lane == 0) table[(size_t)KKT_CLASSES * k + c] = have[c] ? v : -1.0;
     }
 }
+__global__ void __launch_bounds__(WAVE) k_kkt(Tree T, Data D, int x_pad, KktPoint P, double *table) {
+    kkt_node(T, D, x_pad, P, table, blockIdx.x, threadIdx.x);
+}
 
 /* (v, n) before (bv, bn): a NaN first, then the larger value, the lower node among equals; n < 0: nothing yet */
 __device__ __forceinline__ bool kkt_before(double v, int n, double bv, int bn) {
@@ -2942,10 +2957,7 @@ __device__ __forceinline__ bool kkt_before(double v, int n, double bv, int bn) {
 
 /* One workgroup: the table's six columns to six maxima and the lowest nodes that attain them (head[0..6), ints at head + 6; node -1
  * and value 0 for a class without entries); the table's -1 marks become 0.  A fixed tree of comparisons, no atomics. */
-__global__ void __launch_bounds__(256) k_kkt_max(int Nn, double *table, double *head) {
-    __shared__ double sv[256];
-    __shared__ int sn[256];
-    const int t = threadIdx.x;
+__device__ __forceinline__ void kkt_max_columns(int Nn, double *table, double *head, double *sv, int *sn, int t) {
     int *node = reinterpret_cast<int *>(head + KKT_CLASSES);
     for (int c = 0; c < KKT_CLASSES; c++) {
         double bv = 0.0; int bn = -1;
@@ -2963,6 +2975,54 @@ __global__ void __launch_bounds__(256) k_kkt_max(int Nn, double *table, double *
         if (t == 0) { head[c] = sn[0] < 0 ? 0.0 : sv[0]; node[c] = sn[0]; }
         __syncthreads();
     }
+}
+__global__ void __launch_bounds__(256) k_kkt_max(int Nn, double *table, double *head) {
+    __shared__ double sv[256];
+    __shared__ int sn[256];
+    kkt_max_columns(Nn, table, head, sv, sn, threadIdx.x);
+}
+
+/* ---- the same for a batch of mirrors in one launch each (tqgpu_kkt_residual_batch) ----
+ * One descriptor per member, uploaded with every call: what the single launches pass as kernel arguments.  Every kernel below is the
+ * single kernel's body (the __device__ functions above, so the arithmetic of a node is the same instruction for instruction) behind
+ * a look-up of the member: blockIdx.y = member, blockIdx.x = what blockIdx.x is in the single launch.  The grid is as wide as the
+ * largest member needs; a workgroup beyond its member's own extent, or of a member the kernel does not apply to, returns at once
+ * and writes nothing. */
+struct KItem {
+    Tree T; Data D; KktPoint P;
+    const double *lamc;            /* the current duals (lam0 or lam1, as the host knows after the solve) */
+    double *d_out, *table, *head;  /* the member's export block and per-node table; its KKT_HEAD doubles in the batch's contiguous block of heads */
+    int x_pad, nxe, nue, nl, nx0;  /* phantom root states; the export sizes (x without them, u, lam) */
+    int needs_export, box, gen;    /* d_out is not packed yet (no export went out ahead); the tree has nodes of kind 2 / of kind 3 */
+};
+struct KHead { double v[KKT_HEAD]; };      /* six maxima, six ints, one pad: what k_kkt_max writes in front of a mirror's own table */
+__global__ void __launch_bounds__(256) k_export_all_batch(const KItem *__restrict__ items) {
+    const KItem &it = items[blockIdx.y];
+    if (!it.needs_export) return;
+    export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, it.nxe, it.nue, it.nl, it.x_pad, it.nx0, it.D, it.lamc, it.d_out);
+}
+__global__ void __launch_bounds__(WAVE) k_export_box_batch(const KItem *__restrict__ items) {
+    const KItem &it = items[blockIdx.y];
+    if (!it.needs_export || !it.box || (int)blockIdx.x >= it.T.Nn) return;
+    export_box_node(it.T, it.D, it.nxe, it.nue, it.nl, it.x_pad, it.d_out, blockIdx.x, threadIdx.x);
+}
+__global__ void __launch_bounds__(WAVE) k_export_gen_batch(const KItem *__restrict__ items) {
+    const KItem &it = items[blockIdx.y];
+    if (!it.needs_export || !it.gen || (int)blockIdx.x >= it.T.Nn) return;
+    export_gen_node(it.T, it.D, it.nxe, it.nue, it.nl, it.x_pad, it.d_out, blockIdx.x, threadIdx.x);
+}
+/* one wave per (member, node) */
+__global__ void __launch_bounds__(WAVE) k_kkt_batch(const KItem *__restrict__ items) {
+    const KItem &it = items[blockIdx.y];
+    if ((int)blockIdx.x >= it.T.Nn) return;
+    kkt_node(it.T, it.D, it.x_pad, it.P, it.table, blockIdx.x, threadIdx.x);
+}
+/* one workgroup per member */
+__global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__ items) {
+    __shared__ double sv[256];
+    __shared__ int sn[256];
+    const KItem &it = items[blockIdx.x];
+    kkt_max_columns(it.T.Nn, it.table, it.head, sv, sn, threadIdx.x);
 }
 
 /* ---- tqgpu_create step by step: each step takes the mirror and returns a TQGPU_* code ---- */
@@ -5358,7 +5418,99 @@ extern "C" int tqgpu_kkt_residual_at(tqgpu_solver *s, const double *x, const dou
     return TQGPU_OK;
 }
 
-/* every member's evaluation goes out on its own stream before the first wait */
+/* ---- tqgpu_kkt_residual_batch: per device one group; a group of KKT_BATCH_MIN members or more goes out as ONE set of launches on
+ * its first member's stream (the lead's), anything else member by member on the members' own streams ---- */
+namespace {
+struct KktBatchStats { int launches = 0, copies = 0, waits = 0, batched = 0; };
+thread_local KktBatchStats g_kkt_stats;          /* of this thread's last tqgpu_kkt_residual_batch (tqgpu_kkt_batch_stats) */
+constexpr int KKT_BATCH_MIN = 2;                 /* members of one device from which the batched route is taken: at 2 C1 trees it measured 37 us against 64 us member by member (profiles/r12_kkt_batch_timing.txt) */
+constexpr size_t KKT_GRID_Y = 65535;             /* blockIdx.y is the member */
+
+struct KktGroup { int device; std::vector<int> idx; bool batched = false; };
+
+/* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
+ * waves that return at once, and is checked member by member instead. */
+bool kkt_group_batched(tqgpu_solver **v, const KktGroup &g) {
+    if (g.idx.size() < (size_t)KKT_BATCH_MIN || g.idx.size() > KKT_GRID_Y) return false;
+    size_t sum = 0, mx = 0;
+    std::set<const tqgpu_solver *> seen;
+    for (int i : g.idx) {
+        if (!seen.insert(v[i]).second) return false;          /* a mirror named twice: two workgroups would reduce (and rewrite) one table */
+        sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn);
+    }
+    return mx * g.idx.size() <= 8 * sum + 4096;
+}
+
+/* one member on its own stream: the route of tqgpu_kkt_residual without the wait */
+int kkt_member_enqueue(tqgpu_solver *s, KktBatchStats &st) {
+    if (s->settle_stream && s->settle_stream != s->stream) st.waits++;
+    SETTLE(s);
+    st.launches += (s->export_valid ? 0 : 1 + (s->box ? 1 : 0) + (s->gen ? 1 : 0)) + 2;
+    st.copies++;
+    return kkt_enqueue_last(s, false);
+}
+
+/* A group on its lead's stream: the descriptors in one copy, the packing of the members that have not exported ahead (k_export_all_batch,
+ * and the box and row overlays where some member has such nodes), k_kkt_batch, k_kkt_max_batch, the heads in one copy.  Nothing is
+ * waited for here in the steady state -- a loop of tqgpu_solve_batch and this call on the same members -- where every member's solve
+ * was part of a launch on this very stream (settle_stream), as in join_lead_stream.  A member's own stream is waited for only where it
+ * may hold work this stream has not seen: uploads (stream_pending), an export that went out ahead, or a solve of its own that returned
+ * on its verdict (a single launch may still write its state back then). */
+int kkt_group_enqueue(tqgpu_solver **v, const KktGroup &g, KktBatchStats &st) {
+    tqgpu_solver *lead = v[g.idx[0]];
+    const size_t n = g.idx.size();
+    int rc;
+    HIP_TRY(hipSetDevice(lead->device));
+    for (int i : g.idx) if ((rc = setup_kkt(v[i], false))) return rc;
+    if ((rc = grow_items(lead, lead->d_kitems, lead->h_kitems, lead->kitems_cap, n)) || (rc = grow_items(lead, lead->d_kheads, lead->h_kheads, lead->kheads_cap, n))) return rc;
+    int nn_all = 0, nn_box = 0, nn_gen = 0, cells = 0;          /* widths of the four grids (0: no launch) */
+    std::vector<hipStream_t> waited;                             /* streams this call has synchronised (a handful: one per wave of the batch solve at the most) */
+    auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
+    for (size_t m = 0; m < n; m++) {
+        tqgpu_solver *s = v[g.idx[m]];
+        const bool in_launch = s->settle_stream != nullptr;          /* its last solve was part of a batch launch that has not been waited for */
+        if (s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;          /* ... on this stream: ordered by it, and waited for with the heads; or on one this call has waited for already (the members of a later wave of the batch solve, behind their lead) */
+        else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); st.waits++; } SETTLE(s); }
+        const bool own_solve = !in_launch && s->solve_no != s->kkt_drained_at;
+        if (s->stream != lead->stream && (s->stream_pending || s->export_valid || own_solve)) {
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            s->stream_pending = false;
+            waited.push_back(s->stream);
+            st.waits++;
+        }
+        s->kkt_drained_at = s->solve_no;
+        KItem &it = lead->h_kitems[m];
+        it.T = s->T; it.D = s->D;
+        it.x_pad = s->x_pad; it.nxe = s->sum_nx - s->x_pad; it.nue = s->sum_nu; it.nl = s->sum_lam; it.nx0 = s->nx0;
+        it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
+        it.d_out = s->d_out; it.table = s->d_kkt + KKT_HEAD; it.head = lead->d_kheads[m].v;
+        it.P.x = s->d_out; it.P.u = it.P.x + it.nxe; it.P.lam = it.P.u + it.nue; it.P.mu_x = it.P.lam + 2 * (size_t)it.nl; it.P.mu_u = it.P.mu_x + it.nxe;
+        it.P.mu_d = s->gen ? s->d_gmu : nullptr;
+        it.needs_export = s->export_valid ? 0 : 1; it.box = s->box ? 1 : 0; it.gen = s->gen ? 1 : 0;
+        nn_all = std::max(nn_all, s->T.Nn);
+        if (it.needs_export) {
+            cells = std::max(cells, std::max(std::max(it.nxe, it.nue), std::max(it.nl, 1)));
+            if (it.box) nn_box = std::max(nn_box, s->T.Nn);
+            if (it.gen) nn_gen = std::max(nn_gen, s->T.Nn);
+        }
+    }
+    hipStream_t ls = lead->stream;
+    const unsigned ny = (unsigned)n;
+    HIP_TRY(hipMemcpyAsync(lead->d_kitems, lead->h_kitems, n * sizeof(KItem), hipMemcpyHostToDevice, ls)); st.copies++;
+    if (cells) { hipLaunchKernelGGL(k_export_all_batch, dim3((unsigned)((cells + 255) / 256), ny), dim3(256), 0, ls, lead->d_kitems); st.launches++; }
+    if (nn_box) { hipLaunchKernelGGL(k_export_box_batch, dim3((unsigned)nn_box, ny), dim3(WAVE), 0, ls, lead->d_kitems); st.launches++; }
+    if (nn_gen) { hipLaunchKernelGGL(k_export_gen_batch, dim3((unsigned)nn_gen, ny), dim3(WAVE), 0, ls, lead->d_kitems); st.launches++; }
+    hipLaunchKernelGGL(k_kkt_batch, dim3((unsigned)nn_all, ny), dim3(WAVE), 0, ls, lead->d_kitems); st.launches++;
+    hipLaunchKernelGGL(k_kkt_max_batch, dim3(ny), dim3(256), 0, ls, lead->d_kitems); st.launches++;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lead->h_kheads, lead->d_kheads, n * sizeof(KHead), hipMemcpyDeviceToHost, ls)); st.copies++;
+    st.batched += (int)n;
+    return TQGPU_OK;
+}
+}  // namespace
+
+/* Everything goes out before the first wait.  The members' d_out is packed afterwards, their h_out is not: export_valid stays as it
+ * was, so tqgpu_get_solution packs and downloads as it does behind tqgpu_kkt_residual. */
 extern "C" int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *res, int *node) {
     if (!solvers || n < 0 || (n > 0 && !res)) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_batch: bad arguments");
     int rc;
@@ -5366,15 +5518,43 @@ extern "C" int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *r
         if ((rc = kkt_refuse(solvers[i], "tqgpu_kkt_residual_batch"))) return rc;
         if (solvers[i]->solve_no == 0) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_batch: member " + std::to_string(i) + " has not solved yet");
     }
+    KktBatchStats &st = g_kkt_stats;
+    st = KktBatchStats();
+    const char *sw = getenv("TREEQP_AMD_KKT_BATCH");          /* =members: every member on its own stream, as a group of one goes */
+    const bool by_member = sw && strcmp(sw, "members") == 0;
+    std::vector<KktGroup> groups;
     for (int i = 0; i < n; i++) {
-        SETTLE(solvers[i]);
-        if ((rc = kkt_enqueue_last(solvers[i], false))) return rc;
+        auto g = std::find_if(groups.begin(), groups.end(), [&](const KktGroup &q) { return q.device == solvers[i]->device; });
+        if (g == groups.end()) { groups.push_back(KktGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
+        g->idx.push_back(i);
     }
-    for (int i = 0; i < n; i++) {
-        HIP_TRY(hipSetDevice(solvers[i]->device));
-        HIP_TRY(hipStreamSynchronize(solvers[i]->stream));
-        kkt_collect(solvers[i], res + (size_t)KKT_CLASSES * i, node ? node + (size_t)KKT_CLASSES * i : nullptr, nullptr);
+    for (KktGroup &g : groups) {
+        g.batched = !by_member && kkt_group_batched(solvers, g);
+        if (g.batched) {
+            if ((rc = kkt_group_enqueue(solvers, g, st))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
+        } else for (int i : g.idx) if ((rc = kkt_member_enqueue(solvers[i], st))) return rc;
     }
+    for (const KktGroup &g : groups) {
+        tqgpu_solver *lead = solvers[g.idx[0]];
+        HIP_TRY(hipSetDevice(lead->device));
+        if (g.batched) { HIP_TRY(hipStreamSynchronize(lead->stream)); st.waits++; }
+        for (size_t m = 0; m < g.idx.size(); m++) {
+            const int i = g.idx[m];
+            if (!g.batched) { HIP_TRY(hipStreamSynchronize(solvers[i]->stream)); st.waits++; kkt_collect(solvers[i], res + (size_t)KKT_CLASSES * i, node ? node + (size_t)KKT_CLASSES * i : nullptr, nullptr); continue; }
+            const double *h = lead->h_kheads[m].v;
+            memcpy(res + (size_t)KKT_CLASSES * i, h, sizeof(double) * KKT_CLASSES);
+            if (node) memcpy(node + (size_t)KKT_CLASSES * i, h + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
+        }
+    }
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_kkt_batch_stats(int *launches, int *copies, int *waits, int *batched_members) {
+    const KktBatchStats &st = g_kkt_stats;
+    if (launches) *launches = st.launches;
+    if (copies) *copies = st.copies;
+    if (waits) *waits = st.waits;
+    if (batched_members) *batched_members = st.batched;
     return TQGPU_OK;
 }
 
