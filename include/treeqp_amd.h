@@ -347,6 +347,71 @@ int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, i
  * solve is a single persistent launch run concurrently, as many as fit on the device at once. */
 int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, tqgpu_result *results);
 
+/* ---- MPC steps without the host in the data path: the x0 fold, the warm start and u[0] on the device ----------------------------
+ * An MPC loop on an x0-eliminated tree (nx[0] == 0, tree_qp_in_eliminate_x0 / tree_qp_in_set_x0_*: qp_container.c) moves x0, starts
+ * from the last duals, solves and applies u[0].  These calls keep all of it on the device: the originals of what multiplies x0 stay
+ * there, a kernel folds a new x0 into b, r[0], dmin[0], dmax[0] in place, another copies the last duals into the start buffer, and a
+ * small kernel behind the solve posts u[0] into pinned memory.  Every call below refuses a rank of a sharded solve
+ * (tqgpu_shard_init / tqgpu_pshard_init with nranks > 1) with TQGPU_EUNSUPPORTED.
+ *   tqgpu_mpc_set_root   the originals, copied into device memory (the caller's arrays are free afterwards).  nk0 = nk[0] children:
+ *                        A0: for each child of the root in order nx[kid] x nx0, column major, concatenated; b0: nx[kid] each;
+ *                        S0 (nu[0] x nx0, column major) with r0 (nu[0]); C0 (nc[0] x nx0, column major) with dmin0, dmax0 (nc[0] each).
+ *                        S0 == NULL and C0 == NULL mean zero: r[0] resp. dmin[0], dmax[0] are then left alone by the fold.
+ *                        TQGPU_EINVAL: the root still has states (eliminate x0 first), nx0 <= 0, A0 or b0 missing, S0 without r0 or C0
+ *                        without dmin0 and dmax0, a non-zero S0 on a root of kind 0 (clipping: S must be zero), C0 without rows on the
+ *                        root (tqgpu_set_constraints; a root that is not of kind 3 has none).  A call replaces an earlier one.
+ *   tqgpu_mpc_set_x0     one kernel on the mirror's stream, no synchronisation (the next solve is ordered behind it):
+ *                          b_kid   = b0_kid + A0_kid x0   for the children of the root, one wave per child, rows over lanes;
+ *                          r[0]    = r0 + S0 x0           where S0 was given;
+ *                          dmin[0] = dmin0 - C0 x0, dmax[0] = dmax0 - C0 x0   where C0 was given.
+ *                        Summation order: every entry starts from the original (b0, r0, dmin0, dmax0) and takes one fused
+ *                        multiply-add per column j = 0, 1, .., nx0 - 1, ascending: v = fma(A0[i, j], x0[j], v), for the rows
+ *                        v = fma(-C0[i, j], x0[j], v).  x0 is copied into a pinned buffer of the mirror, which the kernel reads.
+ *                        The stored working sets of kinds 2 and 3 are kept; the pinned host mirror of tqgpu_set_problem is
+ *                        invalidated (the next tqgpu_set_problem uploads everything it is given).  No route packs b; the persistent
+ *                        route packs r and the bounds (they are repacked when r[0] moved), the rows of kind 3 are read in place.
+ *                        A tqgpu_set_constraints that changes nc[0] after tqgpu_mpc_set_root leaves C0 without its rows: TQGPU_EINVAL
+ *                        here until tqgpu_mpc_set_root is called again.
+ *                        TQGPU_EINVAL before tqgpu_mpc_set_root.
+ *   tqgpu_set_warm_start mode 0 (default): every solve starts from the buffer of tqgpu_set_lambda.  Mode 1: every solve starts from
+ *                        the duals tqgpu_get_solution would return at that moment, whatever the last route and status: a kernel
+ *                        ahead of the solve copies them (sum_nx doubles, node-indexed, phantom root states included) into the start
+ *                        buffer, and reads on the device which of the two dual buffers is current.  Before the mirror's first solve,
+ *                        and after a tqgpu_set_lambda (or a tqgpu_set_problem that passes lambda), the start is what that call filled,
+ *                        for one solve.  The mode applies to tqgpu_solve, tqgpu_solve_n, the members of tqgpu_solve_batch(_n) and the
+ *                        step calls.  The redo after a timed-out persistent launch starts where the timed-out attempt started.
+ *   tqgpu_get_root_terms what the device holds now (any pointer may be NULL): b of the root's children (sum of their nx), r[0] (nu[0]),
+ *                        dmin[0], dmax[0] (nc[0] each; untouched where the root has no rows).  Waits for the mirror's stream.
+ *   tqgpu_mpc_step       tqgpu_mpc_set_x0 (x0 == NULL: keep the current one), the warm start of the current mode and tqgpu_solve, then
+ *                        u[0] (nu[0] doubles) into u0: a one-workgroup kernel behind the solve writes the values into pinned memory,
+ *                        then a tag the host polls.  On the single-launch routes (persistent, single-workgroup) that kernel is
+ *                        enqueued behind the launch at once and the host waits for its tag only: the verdict is in by then.  If
+ *                        the launch was not the whole solve (further line-search trials, a relaunch, a timeout) u[0] is posted again
+ *                        behind the rest.  tqgpu_get_solution, tqgpu_get_mu_d, tqgpu_kkt_residual work afterwards as behind tqgpu_solve.
+ *   tqgpu_mpc_step_batch the same for n mirrors, x0s member after member (NULL: all keep theirs), u0s member after member, nu[0] of
+ *                        each.  Per device the folds and warm-start copies of all members are ONE launch on the stream of the
+ *                        device's first member (a descriptor per member, one upload per device and call), ahead of what
+ *                        tqgpu_solve_batch launches, and their u[0] are collected by ONE launch behind it.  A member gets bit for bit
+ *                        what tqgpu_mpc_step gives it alone wherever tqgpu_solve_batch gives what tqgpu_solve gives.
+ *   tqgpu_mpc_stats      what the calling thread's last tqgpu_mpc_step / _step_batch cost (any pointer may be NULL; host state only):
+ *                        launches: kernels enqueued (fold + warm start, the solves' own -- a launch shared by a group of a batch counts
+ *                          once --, u0 posts);
+ *                        copies: hipMemcpy calls in either direction (descriptor uploads, read-backs of the control block on the
+ *                          launch-per-phase routes);
+ *                        waits: times the host had to wait for the device: a stream synchronisation, or a poll of a pinned block
+ *                          that was not complete at the first look.
+ *                        A step on the persistent route that ends inside its launch: 3 launches, 0 copies, 1 wait.  A batch step of
+ *                        persistent members that share one launch: 3 launches, 1 copy, 1 wait, whatever n. */
+int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, const double *b0, const double *S0, const double *r0,
+                       const double *C0, const double *dmin0, const double *dmax0);
+int tqgpu_mpc_set_x0(tqgpu_solver *s, const double *x0);
+int tqgpu_set_warm_start(tqgpu_solver *s, int mode);
+int tqgpu_get_warm_start(const tqgpu_solver *s, int *mode);
+int tqgpu_get_root_terms(tqgpu_solver *s, double *b_kids, double *r0, double *dmin0, double *dmax0);
+int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opts *opts, tqgpu_result *res, double *u0);
+int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double *x0s, const tqgpu_opts *opts, tqgpu_result *results, double *u0s);
+int tqgpu_mpc_stats(int *launches, int *copies, int *waits);
+
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written
  * (at most 512 solves back) or -1.  tqgpu_result.device_time of a single-launch (persistent) solve is

@@ -1,0 +1,193 @@
+"""What one step of an MPC loop costs, on the GPU box: the device loop (tqgpu_mpc_step, warm start mode 1: x0 fold, warm start and
+u[0] on the device) against the host loop, the only way before these calls existed (numpy fold of x0 into b, tqgpu_set_problem with
+the last duals, tqgpu_solve, tqgpu_get_solution).
+
+    python tools/mpc_loop.py [--steps 200] [--skip 10] [--batch 64] [c1] [c2] [batch]
+
+Workloads, all x0-eliminated (nx[0] == 0): c1 = problems.spring_mass(), 85 nodes; c2 = problems.linear_chain(2, 9, 9), 1 023 nodes;
+batch = 64 mirrors of c1 from different x0 (tqgpu_mpc_step_batch against fold + tqgpu_set_problem per member, tqgpu_solve_batch,
+tqgpu_get_solution per member).  x0 moves on a prescribed path around the problem's own x0, entry i at step k
+x0_i (1 + 0.05 sin(0.3 k + i + member)): the plant driven through one realisation leaves the feasible set of these benchmark
+problems within a few steps, where no solver converges, so x0 is prescribed instead.  The host loop runs first; the device loop
+runs the same sequence in the same process, on a mirror of the same problem, so that
+step k of both loops is the same QP from the same duals: iterations and trials per step are compared and the steps that differ are
+counted.  Per loop: wall time per step (host perf_counter around the step's calls; median, min, p90 over the steps after --skip),
+the solve's device time (tqgpu_result.device_time), kernel launches and copies per step (device loop: tqgpu_mpc_stats; host loop:
+the solve's launches plus the packing kernel of tqgpu_get_solution, and its three copies: b up, the duals up, the solution down)."""
+import ctypes as C
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+
+import numpy as np  # noqa: E402
+
+
+def stats(ts):
+    a = 1e6 * np.asarray(ts)
+    return float(np.median(a)), float(a.min()), float(np.percentile(a, 90))
+
+
+def eliminated(capi, p):
+    """(x0-eliminated flat problem, A0 per root child, b0, B of the first edge, x0 of the problem)"""
+    import mpc_cases as M
+    nk = p.nk()
+    flat = capi.TreeQp(np.full(p.Nn, p.nx), np.where(nk > 0, p.nu, 0), nk).fill_lti(p).flat()
+    nk0, nx = int(nk[0]), p.nx
+    A0 = [flat["A"][k * nx * nx:(k + 1) * nx * nx].reshape((nx, nx), order="F").copy() for k in range(nk0)]
+    b0 = flat["b"][:nk0 * nx].copy()
+    B0 = flat["B"][:nx * p.nu].reshape((nx, p.nu), order="F").copy()
+    d, _ = M.eliminate(flat)
+    return d, A0, b0, B0, np.asarray(p.x0, dtype=np.float64).copy()
+
+
+def moved(x0, k, member):
+    return x0 * (1.0 + 0.05 * np.sin(0.3 * k + np.arange(len(x0)) + member))
+
+
+def fold_b(A0, b0, x0):
+    return np.concatenate([b0[i * len(x0):(i + 1) * len(x0)] + A @ x0 for i, A in enumerate(A0)])
+
+
+def report(name, wall, dev, launches, copies, skip):
+    med, lo, p90 = stats(wall[skip:])
+    print(f"    {name:12s} wall median {med:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f} | device {1e6 * np.median(dev[skip:]):7.1f} us | "
+          f"launches {np.median(launches[skip:]):.0f}  copies {np.median(copies[skip:]):.0f}", flush=True)
+    return med
+
+
+def single(capi, name, p, steps, skip):
+    L = capi.lib()
+    d, A0, b0, B0, x0 = eliminated(capi, p)
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    nu0, nb = int(d["nu"][0]), len(b0)
+    # host loop
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    keep = {k: np.ascontiguousarray(d[k], dtype=np.float64) for k in ("A", "B", "b", "Qd", "Rd", "q", "r", "xmin", "xmax", "umin", "umax")}
+    lam = np.zeros(g.sum_lam)
+    sol = [np.zeros(n) for n in (g.sum_nx, g.sum_nu, g.sum_lam, g.sum_nx, g.sum_nu, g.sum_lam)]
+    sp = [dp(b) for b in sol]
+    order = ("A", "B", "b", "Qd", "Rd", "q", "r", "xmin", "xmax", "umin", "umax")
+    xs, hw, hd, hl, hc, hcnt, hu = [], [], [], [], [], [], []
+    x = moved(x0, 0, 0)
+    for _ in range(steps):
+        xs.append(x.copy())
+        t0 = time.perf_counter()
+        keep["b"][:nb] = fold_b(A0, b0, x)
+        assert L.tqgpu_set_problem(g.h, *[dp(keep[k]) for k in order], dp(lam)) == 0
+        assert L.tqgpu_solve(g.h, C.byref(o), C.byref(r)) == 0
+        assert L.tqgpu_get_solution(g.h, *sp) == 0
+        hw.append(time.perf_counter() - t0)
+        lam[:] = sol[2]
+        hu.append(sol[1][:nu0].copy())
+        hd.append(r.device_time); hl.append(r.n_launches + 1); hc.append(3); hcnt.append((r.status, r.iter, r.ls_total))
+        x = moved(x0, len(xs), 0)
+    g.close()
+    # device loop, the same x0 sequence
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    g.mpc_set_root(A0, b0)
+    g.set_warm_start(1)
+    u0 = np.zeros(max(nu0, 1))
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    dw, dd, dl, dc, dcnt, du = [], [], [], [], [], 0.0
+    for k in range(steps):
+        xk = xs[k]
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_step(g.h, dp(xk), C.byref(o), C.byref(r), dp(u0)) == 0
+        dw.append(time.perf_counter() - t0)
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        dd.append(r.device_time); dl.append(la.value); dc.append(co.value); dcnt.append((r.status, r.iter, r.ls_total))
+        du = max(du, float(np.max(np.abs(u0[:nu0] - hu[k]))))
+    kkt = g.kkt_residual()["max"]
+    g.close()
+    differ = sum(a != b for a, b in zip(hcnt, dcnt))
+    print(f"{name}: {len(d['nk'])} nodes, {steps} steps, iterations per step median {np.median([c[1] for c in hcnt]):.0f} "
+          f"(first step {hcnt[0][1]}), all status 0: {all(c[0] == 0 for c in hcnt + dcnt)}")
+    h = report("host loop", hw, hd, hl, hc, skip)
+    v = report("device loop", dw, dd, dl, dc, skip)
+    print(f"    steps with other iterations or trials than the host loop: {differ} of {steps}; largest |u0 (device) - u0 (host)| {du:.2e}; "
+          f"KKT of the last device step {kkt:.2e}; host / device wall {h / v:.2f}", flush=True)
+
+
+def batch(capi, p, n, steps, skip):
+    L = capi.lib()
+    d, A0, b0, B0, x0 = eliminated(capi, p)
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o = capi._gpu_opts()
+    nu0, nb, nx = int(d["nu"][0]), len(b0), len(x0)
+    order = ("A", "B", "b", "Qd", "Rd", "q", "r", "xmin", "xmax", "umin", "umax")
+    mk = lambda: [capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d) for _ in range(n)]
+    # host loop
+    ms = mk()
+    arr = (C.c_void_p * n)(*[m.h for m in ms])
+    res = (capi.GpuResult * n)()
+    keeps = [{k: np.ascontiguousarray(d[k], dtype=np.float64).copy() for k in order} for _ in range(n)]
+    lams = [np.zeros(ms[0].sum_lam) for _ in range(n)]
+    sols = [[np.zeros(s) for s in (ms[0].sum_nx, ms[0].sum_nu, ms[0].sum_lam, ms[0].sum_nx, ms[0].sum_nu, ms[0].sum_lam)] for _ in range(n)]
+    X = [moved(x0, 0, i) for i in range(n)]
+    xs, hw, hcnt = [], [], []
+    for _ in range(steps):
+        xs.append([x.copy() for x in X])
+        t0 = time.perf_counter()
+        for i in range(n):
+            keeps[i]["b"][:nb] = fold_b(A0, b0, X[i])
+            assert L.tqgpu_set_problem(ms[i].h, *[dp(keeps[i][k]) for k in order], dp(lams[i])) == 0
+        assert L.tqgpu_solve_batch(arr, n, C.byref(o), res) == 0
+        for i in range(n):
+            assert L.tqgpu_get_solution(ms[i].h, *[dp(b) for b in sols[i]]) == 0
+        hw.append(time.perf_counter() - t0)
+        hcnt.append([(res[i].status, res[i].iter, res[i].ls_total) for i in range(n)])
+        for i in range(n):
+            lams[i][:] = sols[i][2]
+            X[i] = moved(x0, len(xs), i)
+    for m in ms:
+        m.close()
+    # device loop
+    ms = mk()
+    arr = (C.c_void_p * n)(*[m.h for m in ms])
+    for m in ms:
+        m.mpc_set_root(A0, b0)
+        m.set_warm_start(1)
+    u0s = np.zeros(n * max(nu0, 1))
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    dw, dl, dc, dwt, dcnt = [], [], [], [], []
+    for k in range(steps):
+        xk = np.ascontiguousarray(np.concatenate(xs[k]))
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_step_batch(arr, n, dp(xk), C.byref(o), res, dp(u0s)) == 0
+        dw.append(time.perf_counter() - t0)
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        dl.append(la.value); dc.append(co.value); dwt.append(wa.value)
+        dcnt.append([(res[i].status, res[i].iter, res[i].ls_total) for i in range(n)])
+    for m in ms:
+        m.close()
+    differ = sum(a != b for ha, da in zip(hcnt, dcnt) for a, b in zip(ha, da))
+    h, hlo, hp = stats(hw[skip:])
+    v, vlo, vp = stats(dw[skip:])
+    print(f"batch: {n} mirrors of c1, {steps} steps, all status 0: {all(c[0] == 0 for row in hcnt + dcnt for c in row)}")
+    print(f"    host loop    wall median {h:8.1f} us  min {hlo:8.1f}  p90 {hp:8.1f} | copies {3 * n} (three per member)")
+    print(f"    device loop  wall median {v:8.1f} us  min {vlo:8.1f}  p90 {vp:8.1f} | launches {np.median(dl[skip:]):.0f}  copies {np.median(dc[skip:]):.0f}  waits {np.median(dwt[skip:]):.0f}")
+    print(f"    member steps with other iterations or trials than the host loop: {differ} of {n * steps}; host / device wall {h / v:.2f}", flush=True)
+
+
+def main():
+    from treeqp_amd import capi, problems as P
+    args = sys.argv[1:]
+    take = lambda flag, default: int(args[args.index(flag) + 1]) if flag in args else default
+    steps, skip, n = take("--steps", 200), take("--skip", 10), take("--batch", 64)
+    names = [a for a in args if a in ("c1", "c2", "batch")] or ["c1", "c2", "batch"]
+    if capi.device_count() < 1:
+        raise SystemExit("no HIP device")
+    if "c1" in names:
+        single(capi, "c1", P.spring_mass(), steps, skip)
+    if "c2" in names:
+        single(capi, "c2", P.linear_chain(2, 9, 9), steps, skip)
+    if "batch" in names:
+        batch(capi, P.spring_mass(), n, steps, skip)
+
+
+if __name__ == "__main__":
+    main()

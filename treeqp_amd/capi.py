@@ -525,6 +525,45 @@ def solve_batch_n(mirrors, steps: int, profile=0, **kw):
     return [{f: getattr(res[i], f) for f, _ in GpuResult._fields_} for i in range(n)], it.value, ls.value, la.value
 
 
+def _gpu_opts(profile=0, **kw) -> GpuOpts:
+    o = GpuOpts(maxIter=100, termCondition=2, stationarityTolerance=1e-8, regType=2, regTol=1e-6, regValue=1e-6,
+                lineSearchMaxIter=50, lineSearchGamma=0.1, lineSearchBeta=0.6, lineSearchRestartTrigger=-1, profile=profile, checkLastActiveSet=1)
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
+
+
+def mpc_step_batch(mirrors, x0s=None, profile=0, **kw):
+    """One MPC step of every mirror (tqgpu_mpc_step_batch): x0s, one vector per member (None: all keep theirs), is folded in on the
+    device, the warm start of each member's mode is taken, the batch is solved and u[0] of every member comes back
+    -> (list of result dicts, list of u0 arrays)."""
+    o = _gpu_opts(profile, **kw)
+    n = len(mirrors)
+    arr = (C.c_void_p * n)(*[m.h for m in mirrors])
+    res = (GpuResult * n)()
+    x = None if x0s is None else _f64(np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in x0s]))
+    nu0 = [int(m.nu[0]) for m in mirrors]
+    u = np.zeros(max(sum(nu0), 1))
+    rc = lib().tqgpu_mpc_step_batch(arr, n, _dp(x), C.byref(o), res, _dp(u))
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_mpc_step_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    at = np.concatenate([[0], np.cumsum(nu0)]).astype(int)
+    return ([{f: getattr(res[i], f) for f, _ in GpuResult._fields_} for i in range(n)],
+            [u[at[i]:at[i + 1]].copy() for i in range(n)])
+
+
+def mpc_stats() -> dict:
+    """What this thread's last mpc_step / mpc_step_batch cost (tqgpu_mpc_stats): kernel launches, copies in either direction, waits
+    of the host for the device."""
+    v = [C.c_int(0) for _ in range(3)]
+    rc = lib().tqgpu_mpc_stats(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_mpc_stats failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    return dict(zip(("launches", "copies", "waits"), (x.value for x in v)))
+
+
 class TqGpu:
     def __init__(self, nk, nx, nu, device: int = -1):
         L = lib()
@@ -623,6 +662,8 @@ class TqGpu:
         v = C.c_int()
         self._chk(lib().tqgpu_dims2(self.h, C.byref(v)))
         self.sum_nc = v.value
+        if n is not None:
+            self._nc = n
         return self
 
     def set_gen_hot_start(self, on: bool):
@@ -664,6 +705,77 @@ class TqGpu:
         if a is not None:
             assert len(a) == self.sum_lam
         self._chk(lib().tqgpu_set_lambda(self.h, _dp(a)))
+
+    # ---- MPC steps: x0 fold, warm start and u[0] on the device (tqgpu_mpc_*) ----
+    def _root_sizes(self):
+        """(rows of b0 = the nx of the root's children, nu[0], nc[0])"""
+        nk0 = int(self.nk[0])
+        nc0 = 0
+        if getattr(self, "_nc", None) is not None:
+            nc0 = int(self._nc[0])
+        return int(self.nx[1:1 + nk0].sum()), int(self.nu[0]), nc0
+
+    def mpc_set_root(self, A0, b0, S0=None, r0=None, C0=None, dmin0=None, dmax0=None):
+        """The originals of everything that multiplies x0 on an x0-eliminated tree, kept on the device (tqgpu_mpc_set_root): A0 a list
+        of (nx[kid], nx0) matrices, one per child of the root (or their column-major concatenation), b0 the children's b
+        concatenated; S0 (nu[0], nx0) with r0; C0 (nc[0], nx0) with dmin0, dmax0.  None for S0 / C0 means zero."""
+        if isinstance(A0, (list, tuple)):
+            nx0 = int(np.asarray(A0[0]).shape[1])
+            a = _f64(np.concatenate([np.asarray(M, dtype=np.float64).ravel(order="F") for M in A0]))
+        else:
+            a = _f64(A0)
+            nx0 = len(a) // max(self._root_sizes()[0], 1)
+        mat = lambda M: None if M is None else _f64(np.asarray(M, dtype=np.float64).ravel(order="F"))
+        vec = lambda v: None if v is None else _f64(v)
+        keep = [a, vec(b0), mat(S0), vec(r0), mat(C0), vec(dmin0), vec(dmax0)]
+        self._chk(lib().tqgpu_mpc_set_root(self.h, int(nx0), *[_dp(k) for k in keep]))
+        self.nx0 = int(nx0)
+        return self
+
+    def mpc_set_x0(self, x0):
+        """Fold x0 into b of the root's children, r[0], dmin[0], dmax[0] on the device, in place, without synchronisation."""
+        a = _f64(x0)
+        assert len(a) == self.nx0
+        self._chk(lib().tqgpu_mpc_set_x0(self.h, _dp(a)))
+        return self
+
+    def set_warm_start(self, mode: int):
+        """0: every solve starts from the buffer of set_lambda (default); 1: from the duals of the last solve, copied on the device"""
+        self._chk(lib().tqgpu_set_warm_start(self.h, int(mode)))
+        return self
+
+    @property
+    def warm_start(self) -> int:
+        v = C.c_int()
+        self._chk(lib().tqgpu_get_warm_start(self.h, C.byref(v)))
+        return v.value
+
+    def root_terms(self, nc0=None) -> dict:
+        """What the device holds now (tqgpu_get_root_terms): b of the root's children, r[0], and dmin[0], dmax[0] where the root has
+        rows (nc0: their number, by default what set_constraints was given)."""
+        nb, nu0, nc = self._root_sizes()
+        nc = nc if nc0 is None else int(nc0)
+        out = dict(b=np.zeros(nb), r=np.zeros(nu0))
+        if nc:
+            out["dmin"], out["dmax"] = np.zeros(nc), np.zeros(nc)
+        self._chk(lib().tqgpu_get_root_terms(self.h, _dp(out["b"]), _dp(out["r"]), _dp(out.get("dmin")), _dp(out.get("dmax"))))
+        return out
+
+    def mpc_step(self, x0=None, profile=0, **kw):
+        """One MPC step (tqgpu_mpc_step): fold x0 (None: keep the current one), warm start of the current mode, solve
+        -> (result dict, u[0])."""
+        key = (profile, tuple(sorted(kw.items())))
+        cache = self.__dict__.setdefault("_opts_cache", {})
+        o = cache.get(key)
+        if o is None:
+            o = cache[key] = _gpu_opts(profile, **kw)
+        a = None if x0 is None else _f64(x0)
+        if a is not None:
+            assert len(a) == self.nx0
+        r = GpuResult()
+        u0 = np.zeros(max(int(self.nu[0]), 1))
+        self._chk(lib().tqgpu_mpc_step(self.h, _dp(a), C.byref(o), C.byref(r), _dp(u0)))
+        return {f: getattr(r, f) for f, _ in GpuResult._fields_}, u0[:int(self.nu[0])]
 
     def export_ahead(self, on: bool) -> None:
         """the solution's packing kernel and download go out behind the solve's launch (callers that fetch the solution after every solve)"""

@@ -1831,7 +1831,7 @@ struct Switches {
     int chunk, lds_pad, capacity_margin, nap;
 };
 
-namespace { struct KItem; struct KHead; }      /* the batched KKT check's descriptor and head (defined with its kernels) */
+namespace { struct KItem; struct KHead; struct MItem; }      /* the descriptors of the batched KKT check and of the MPC steps, the check's head (defined with their kernels) */
 
 struct tqgpu_solver {
     Owned mem;
@@ -1967,6 +1967,17 @@ struct tqgpu_solver {
     KItem *d_kitems = nullptr, *h_kitems = nullptr; int kitems_cap = 0;
     KHead *d_kheads = nullptr, *h_kheads = nullptr; int kheads_cap = 0;
     long kkt_drained_at = 0;            /* solve_no at which the batched route last knew this mirror's own stream to hold nothing of its solves */
+    /* MPC steps (tqgpu_mpc_*): the originals of what multiplies x0, [A0 | b0 | S0 | r0 | C0 | dmin0 | dmax0] in one device block (tqgpu_mpc_set_root);
+     * pinned: x0 (nx0 doubles), u[0] (nu[0] doubles) and the tag of k_mpc_post */
+    double *d_mpc = nullptr, *h_mpc = nullptr;
+    int mpc_nx0 = 0, mpc_nb = 0, mpc_nc0 = 0;      /* nx0, rows of b0 (the children's nx), rows of C0; mpc_nx0 == 0: no root terms yet */
+    bool mpc_S0 = false, mpc_C0 = false;
+    unsigned long long mpc_tag = 0;                /* the tag of the last u0 post this mirror waited for (its own block, or as the lead of a batch) */
+    int warm_mode = 0;                  /* tqgpu_set_warm_start */
+    bool warm_fresh = true;             /* the start buffer holds what the caller (or a batch step's launch) put there for the next solve: no copy ahead of it */
+    long mpc_drained_at = 0;            /* as kkt_drained_at, for the batch step's launch ahead of the solves */
+    MItem *d_mitems = nullptr, *h_mitems = nullptr; int mitems_cap = 0;      /* batch steps: one descriptor per member of this device (the device's first member owns the array) */
+    double *h_mpc_u0s = nullptr; int mpc_u0s_cap = 0;                        /* ... and their u[0] with the tag behind them, pinned */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -3025,6 +3036,87 @@ __global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__
     kkt_max_columns(it.T.Nn, it.table, it.head, sv, sn, threadIdx.x);
 }
 
+/* ---- MPC steps (tqgpu_mpc_*): the x0 fold and the warm-start copy ahead of a solve, the post of u[0] behind it ----
+ * One descriptor per mirror: a kernel argument for a mirror on its own, an array (blockIdx.y = member) for a batch, as KItem.
+ * k_mpc_pre, waves of 64 lanes, blockIdx.x:
+ *   [0, nk0)     the fold of root child blockIdx.x: rows over lanes, b = b0, then fma over the columns j of A0 ascending;
+ *   nk0          r[0] = r0 + S0 x0 and the rows dmin[0] = dmin0 - C0 x0, dmax[0] = dmax0 - C0 x0, entries over lanes, same order;
+ *   nk0 + 1 ..   the warm start: MPC_WARM_SPAN doubles of the current duals each (Ctrl::cur says which buffer: read here, so nothing waits for the host)
+ *                into the start buffer, node-indexed as they lie (phantom root states included).
+ * The fold writes b, r, dmin, dmax; the copy reads lam0 / lam1 and writes lam_init: the roles touch disjoint data.  No atomics. */
+struct MItem {
+    Tree T; Data D;
+    const double *A0, *b0, *S0, *r0, *C0, *dmin0, *dmax0;      /* the originals in device memory (S0, C0: nullptr = zero, the target is left alone) */
+    const double *x0;                  /* pinned, read over the bus */
+    double *b, *r, *dmin, *dmax;       /* the targets: Data::b, Data::r, Gen::dmin, Gen::dmax */
+    double *lam_init;                  /* the start buffer */
+    double *u0;                        /* pinned: where k_mpc_post puts u[0] */
+    int nx0, nc0, nu0, sum_nx;
+    int fold, warm;                    /* what k_mpc_pre does for this mirror */
+};
+constexpr int MPC_WARM_SPAN = 512;
+__device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane) {
+    const Tree &T = it.T;
+    const int nk0 = T.nk[0], nx0 = it.nx0;
+    if (blk < nk0) {
+        if (!it.fold) return;
+        const int first = T.kid0[0], kid = first + blk, nxk = T.nx[kid];
+        int ao = 0, bo = 0;
+        for (int c = 0; c < blk; c++) { const int n = T.nx[first + c]; ao += n * nx0; bo += n; }
+        const double *A = it.A0 + ao, *b0 = it.b0 + bo;
+        double *b = it.b + T.xoff[kid];
+        for (int i = lane; i < nxk; i += WAVE) {
+            double v = b0[i];
+            for (int j = 0; j < nx0; j++) v = fma(A[i + (size_t)j * nxk], it.x0[j], v);
+            b[i] = v;
+        }
+        return;
+    }
+    if (blk == nk0) {
+        if (!it.fold) return;
+        const int nu0 = it.nu0, nc0 = it.nc0;
+        if (it.S0) for (int i = lane; i < nu0; i += WAVE) {
+            double v = it.r0[i];
+            for (int j = 0; j < nx0; j++) v = fma(it.S0[i + (size_t)j * nu0], it.x0[j], v);
+            it.r[i] = v;
+        }
+        if (it.C0) for (int i = lane; i < nc0; i += WAVE) {
+            double lo = it.dmin0[i], hi = it.dmax0[i];
+            for (int j = 0; j < nx0; j++) { const double c = -it.C0[i + (size_t)j * nc0]; lo = fma(c, it.x0[j], lo); hi = fma(c, it.x0[j], hi); }
+            it.dmin[i] = lo; it.dmax[i] = hi;
+        }
+        return;
+    }
+    if (!it.warm) return;
+    const double *src = it.D.ctrl->cur ? it.D.lam1 : it.D.lam0;
+    const int base = (blk - nk0 - 1) * MPC_WARM_SPAN;
+    for (int t = 0; t < MPC_WARM_SPAN / WAVE; t++) {
+        const int i = base + t * WAVE + lane;
+        if (i < it.sum_nx) it.lam_init[i] = src[i];
+    }
+}
+__global__ void __launch_bounds__(WAVE) k_mpc_pre(MItem it) { mpc_pre_block(it, blockIdx.x, threadIdx.x); }
+__global__ void __launch_bounds__(WAVE) k_mpc_pre_batch(const MItem *__restrict__ items) { mpc_pre_block(items[blockIdx.y], blockIdx.x, threadIdx.x); }
+/* k_mpc_post, one workgroup, enqueued behind the solve: u[0] of every member into pinned memory (sixteen lanes per member), every store
+ * acknowledged, then the tag the host polls -- the way the single launches post their verdict (g_persist_body) */
+__device__ __forceinline__ void mpc_post_values(const MItem &it, int l, int stride) {
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(it.u0);
+    for (int i = l; i < it.nu0; i += stride) __hip_atomic_store(dst + i, (unsigned long long)__double_as_longlong(it.D.u[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__device__ __forceinline__ void mpc_post_tag(unsigned long long *tag, unsigned long long want) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(tag, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+__global__ void __launch_bounds__(256) k_mpc_post(MItem it, unsigned long long *tag, unsigned long long want) {
+    mpc_post_values(it, threadIdx.x, 256);
+    mpc_post_tag(tag, want);
+}
+__global__ void __launch_bounds__(256) k_mpc_post_batch(const MItem *__restrict__ items, int n, unsigned long long *tag, unsigned long long want) {
+    for (int m = threadIdx.x >> 4; m < n; m += 16) mpc_post_values(items[m], threadIdx.x & 15, 16);
+    mpc_post_tag(tag, want);
+}
+
 /* ---- tqgpu_create step by step: each step takes the mirror and returns a TQGPU_* code ---- */
 /* THE list of creation-time switches. Read per tqgpu_create call, never cached: tests and A/B runs change them between two mirrors. */
 void read_switches(Switches &w) {
@@ -3888,6 +3980,7 @@ extern "C" int tqgpu_set_lambda(tqgpu_solver *s, const double *lambda) {
     HIP_TRY(hipSetDevice(s->device));
     /* kept in a resident buffer: every tqgpu_solve starts from it (device-to-device copy) */
     s->lam_valid = false;
+    s->warm_fresh = true;            /* warm start mode 1: the next solve starts from this buffer */
     if (lambda) { H2D(s->d_lam_init + s->nx0, lambda, s->sum_lam); }
     else HIP_TRY(hipMemsetAsync(s->d_lam_init, 0, sizeof(double) * (size_t)s->sum_nx, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -3933,6 +4026,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
     if (any_pack) s->need_pack = true;
     if (lambda && s->sum_lam > 0) {
         const size_t bytes = sizeof(double) * (size_t)s->sum_lam;
+        s->warm_fresh = true;        /* as tqgpu_set_lambda (a warm-start copy since the last upload has cleared lam_valid) */
         if (!s->lam_valid || memcmp(s->h_lam, lambda, bytes) != 0) {
             memcpy(s->h_lam, lambda, bytes);
             HIP_TRY(hipMemcpyAsync(s->d_lam_init + s->nx0, s->h_lam, bytes, hipMemcpyHostToDevice, s->stream));
@@ -3945,6 +4039,13 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
 #undef H2D
 
 namespace {
+
+/* tqgpu_mpc_stats: what this thread's last MPC step cost.  `live` points at the record while a step runs, so that the solve's own read-backs
+ * and waits are counted where they happen; outside a step nothing is counted. */
+struct MpcStats { int launches = 0, copies = 0, waits = 0; };
+thread_local MpcStats g_mpc_stats;
+thread_local MpcStats *g_mpc_live = nullptr;
+#define MPC_COUNT(field, n) do { if (g_mpc_live) g_mpc_live->field += (n); } while (0)
 
 /* the block as tagged words (HostRes::tg, posted by the persistent launches): complete when every word carries `want`; unpacked into the fields */
 bool take_tagged_block(HostRes *hr, unsigned want) {
@@ -3967,6 +4068,7 @@ bool await_result_block(HostRes *hr, unsigned want, bool tagged) {
     bool seen = true;
     for (long spins = 0; *seq != want; spins++) {
         if (tagged && take_tagged_block(hr, want)) break;
+        if (spins == 0) MPC_COUNT(waits, 1);          /* not complete at the first look */
         __builtin_ia32_pause();
         if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) { seen = false; break; }
     }
@@ -4005,6 +4107,7 @@ int read_ctrl(tqgpu_solver *s) {
     s->w3_seen = false;
     HIP_TRY(hipMemcpyAsync(s->h_ctrl, s->D.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    MPC_COUNT(copies, 1); MPC_COUNT(waits, 1);
     return TQGPU_OK;
 }
 
@@ -4191,13 +4294,31 @@ int begin_single_wg(tqgpu_solver *s, SolveCtx &cx, GItem *defer) {
 /* PERSIST: the launch with its prologue, or its share of the caller's batch launch (batch_seq) */
 int begin_persist(tqgpu_solver *s, SolveCtx &cx) { return launch_persist(s, cx.O, cx.launches, 1, cx.batch_seq); }
 
+/* warm start mode 1 (tqgpu_set_warm_start): the duals of the last solve into the start buffer, on the mirror's own stream ahead of everything the
+ * solve enqueues there.  The last solve may have been part of a batch launch on another stream (settle); a launch the caller makes on
+ * another stream waits for this one (stream_pending, join_lead_stream).  A batch step does all its members' copies in one launch
+ * instead and leaves warm_fresh set. */
+MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm);
+int enqueue_warm_start(tqgpu_solver *s, SolveCtx &cx) {
+    int rc = settle(s);
+    if (rc != TQGPU_OK) return rc;
+    const int blocks = s->nk[0] + 1 + (s->sum_nx + MPC_WARM_SPAN - 1) / MPC_WARM_SPAN;
+    hipLaunchKernelGGL(k_mpc_pre, dim3((unsigned)blocks), dim3(WAVE), 0, s->stream, mpc_item(s, false, true)); cx.launches++;
+    s->lam_valid = false;          /* the pinned mirror of tqgpu_set_problem's duals no longer describes the start buffer */
+    s->stream_pending = true;
+    return TQGPU_OK;
+}
+
 /* defer: the solve runs Route::SINGLE_WG as a member of a batch launch -- its launch is described there and made by the caller */
 int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer = nullptr) {
 #ifdef TQ_HOSTPROF
     cx.hp0 = HP_NOW();
 #endif
+    const bool warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0;          /* (solve_no: before prepare_solve counts this one) */
+    s->warm_fresh = false;
     int rc = prepare_solve(s, o, cx, defer != nullptr);
     if (rc != TQGPU_OK) return rc;
+    if (warm && (rc = enqueue_warm_start(s, cx)) != TQGPU_OK) return rc;
     if (!single_launch(cx.route)) return begin_enqueued(s, cx);
     if ((rc = enqueue_setup(s, cx, defer)) != TQGPU_OK) return rc;
 #ifdef TQ_HOSTPROF
@@ -4341,6 +4462,7 @@ int solve_device_ms(tqgpu_solver *s, const tqgpu_opts *o, const SolveCtx &cx, bo
     } else if (!tail_done) {
         if (cx.events) HIP_TRY(hipEventRecord(cx.ev1, st));
         HIP_TRY(hipStreamSynchronize(st));
+        MPC_COUNT(waits, 1);
         if (cx.events) HIP_TRY(hipEventElapsedTime(&ms, cx.ev0, cx.ev1));
         else ms = 1e-5f * (float)(s->h_res->t_end - s->h_res->t_start);      /* several persistent launches (relaunch): the last one's own clock */
     } else {
@@ -4393,6 +4515,7 @@ int finish_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_resul
             const int nlog = std::min(c.iter, std::min(s->ls_log_cap, 256));
             HIP_TRY(hipMemcpyAsync(s->h_ls_log, s->D.ls_log, sizeof(int) * (size_t)nlog, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
+            MPC_COUNT(copies, 1); MPC_COUNT(waits, 1);
             s->ls_pred.assign(s->h_ls_log, s->h_ls_log + nlog);
         }
     }
@@ -4423,6 +4546,7 @@ static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const Solve
     s->persist_backoff = PERSIST_BACKOFF;
     s->n_timeouts++;
     if (getenv("TREEQP_AMD_VERBOSE")) fprintf(stderr, "[treeqp_amd] persistent launch timed out (device shared?): solving on the launch-per-tier path\n");
+    s->warm_fresh = true;                              /* from the same starting duals: the start buffer holds them, whatever the warm-start mode */
     SolveCtx cx(env, route_of(s, o, false));          /* a fresh decision: use_persist is off now */
     int rc = solve_begin(s, o, cx);
     if (rc != TQGPU_OK) return rc;
@@ -4791,7 +4915,13 @@ struct BatchGuard {
  * flight together, as many at a time as fit on the device at once (every workgroup of a persistent launch must
  * be resident); the others are solved one after the other.  results[i] belongs to solvers[i]; the first error
  * is returned after every started solve has been waited for. */
-extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *o, tqgpu_result *results) {
+/* mb: the batch is a batch step (tqgpu_mpc_step_batch), which orders its launch ahead of each wave, posts u[0] behind the wave's launches where
+ * it can, and counts what went out; nullptr for tqgpu_solve_batch itself */
+struct MpcBatch;
+static int mpc_before_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int j, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg);
+static int mpc_behind_launches(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int j, int ok_to, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg);
+static void mpc_after_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int ok_to, const tqgpu_result *results, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg);
+static int solve_batch_impl(tqgpu_solver **solvers, int n, const tqgpu_opts *o, tqgpu_result *results, MpcBatch *mb) {
     if (!solvers || n < 1 || !o || !results) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: bad arguments");
     for (int i = 0; i < n; i++) if (!solvers[i]) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: null mirror");
     for (int i = 0; i < n; i++) if (solvers[i]->pshard && solvers[i]->nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: a member is one rank of a sharded solve (tqgpu_pshard_init)");
@@ -4810,6 +4940,7 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
         BatchGroup wg, dg, pg;      /* single-workgroup group, dense single-workgroup group, persistent group */
         unsigned pseq = 0;
         if ((rc = form_groups(tab, i, j, env, wg, dg, pg)) || (rc = settle_wave(tab, i, j, wg, dg, pg)) || (rc = persist_group_seq(tab, pg, pseq))) return rc;
+        if (mb && (rc = mpc_before_wave(*mb, tab, i, j, wg, dg, pg))) return rc;
         int ok_to = i;
         size_t gi = 0, di = 0;      /* members of the single-workgroup group / of the dense one that have begun */
         for (int k = i; k < j; k++) {
@@ -4825,6 +4956,7 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
         if (gi > 0 && (rc = launch_single_wg_group(tab, wg, gi))) return rc;
         if (di > 0 && (rc = launch_dense_wg_group(tab, dg, di))) return rc;
         if (pg.lead && ok_to == j && (rc = launch_persist_group(tab, pg, pseq))) return rc;
+        if (mb && (rc = mpc_behind_launches(*mb, tab, i, j, ok_to, wg, dg, pg))) return rc;
         for (int k = i; k < ok_to; k++) {
             tqgpu_solver *sk = solvers[k];
             rc = solve_end(sk, o, tab[(size_t)k].cx, &results[k]);
@@ -4836,12 +4968,15 @@ extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts
             }
             if (rc != TQGPU_OK && first_err == TQGPU_OK) { first_err = rc; first_msg = g_err; }
         }
+        if (mb) mpc_after_wave(*mb, tab, i, ok_to, results, wg, dg, pg);
         const bool sync = first_err != TQGPU_OK || env.batch_sync;
         if ((rc = hand_over(tab, pg, sync)) || (rc = hand_over(tab, wg, sync)) || (rc = hand_over(tab, dg, sync))) return rc;
     }
     if (first_err != TQGPU_OK) return fail(first_err, first_msg);
     return TQGPU_OK;
 }
+
+extern "C" int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *o, tqgpu_result *results) { return solve_batch_impl(solvers, n, o, results, nullptr); }
 
 extern "C" int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_opts *o, int steps, tqgpu_result *results, long *iter_sum, long *ls_sum, long *launch_sum) {
     if (steps < 1) return fail(TQGPU_EINVAL, "tqgpu_solve_batch_n: bad arguments");
@@ -4854,6 +4989,377 @@ extern "C" int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_op
     if (iter_sum) *iter_sum = it;
     if (ls_sum) *ls_sum = ls;
     if (launch_sum) *launch_sum = la;
+    return TQGPU_OK;
+}
+
+/* ============================================================================================ */
+/* MPC steps: x0 fold, warm start and u[0] without the host in the data path (tqgpu_mpc_*)      */
+/* ============================================================================================ */
+
+namespace {
+
+int mpc_refuse(const tqgpu_solver *s, const char *who) {
+    if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
+    if ((s->pshard || s->sharded) && s->nranks > 1)
+        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": this mirror is rank " + std::to_string(s->rank) + " of a sharded solve; MPC steps run on single-device mirrors");
+    return TQGPU_OK;
+}
+
+/* the descriptor of a mirror for k_mpc_pre / k_mpc_post: views into d_mpc and h_mpc (null before tqgpu_mpc_set_root: fold must be false then) */
+MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm) {
+    MItem it{};
+    it.T = s->T; it.D = s->D;
+    const size_t nx0 = (size_t)s->mpc_nx0, nb = (size_t)s->mpc_nb, nu0 = (size_t)s->nu[0], nc0 = (size_t)s->mpc_nc0;
+    if (s->d_mpc) {
+        const double *p = s->d_mpc;
+        it.A0 = p; p += nb * nx0; it.b0 = p; p += nb;
+        it.S0 = s->mpc_S0 ? p : nullptr; p += nu0 * nx0; it.r0 = p; p += nu0;
+        it.C0 = s->mpc_C0 ? p : nullptr; p += nc0 * nx0; it.dmin0 = p; p += nc0; it.dmax0 = p;
+        it.x0 = s->h_mpc; it.u0 = s->h_mpc + nx0;
+    }
+    it.b = s->b; it.r = s->r;
+    it.dmin = s->mpc_C0 ? s->d_drange : nullptr; it.dmax = s->mpc_C0 ? s->d_drange + s->sum_nc : nullptr;
+    it.lam_init = s->d_lam_init;
+    it.nx0 = s->mpc_nx0; it.nc0 = s->mpc_nc0; it.nu0 = s->nu[0]; it.sum_nx = s->sum_nx;
+    it.fold = fold ? 1 : 0; it.warm = warm ? 1 : 0;
+    return it;
+}
+unsigned mpc_pre_blocks(const tqgpu_solver *s) { return (unsigned)(s->nk[0] + 1 + (s->sum_nx + MPC_WARM_SPAN - 1) / MPC_WARM_SPAN); }
+
+/* a new x0 into the mirror's pinned buffer, and what the fold makes stale on the host side; nothing is enqueued */
+int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
+    if (!s->d_mpc) return fail(TQGPU_EINVAL, std::string(who) + ": the root terms have not been given yet (tqgpu_mpc_set_root)");
+    if (s->mpc_C0 && (s->gnc.empty() || s->gnc[0] != s->mpc_nc0 || !s->d_drange))
+        return fail(TQGPU_EINVAL, std::string(who) + ": the rows of the root were redefined after tqgpu_mpc_set_root (call it again)");
+    if (!x0) return TQGPU_OK;
+    memcpy(s->h_mpc, x0, sizeof(double) * (size_t)s->mpc_nx0);
+    s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes b (and r) */
+    if (s->mpc_S0) s->need_pack = true;     /* the persistent route packs r with the bounds (k_pack_persist); b and the rows of kind 3 are read in place */
+    return TQGPU_OK;
+}
+
+/* the tag of a u0 post: complete at the first look, or waited for -- 2 s of polling, then the stream */
+int mpc_wait_tag(const double *block_end, unsigned long long want, hipStream_t st) {
+    const volatile unsigned long long *tag = reinterpret_cast<const volatile unsigned long long *>(block_end);
+    if (*tag != want) {
+        MPC_COUNT(waits, 1);
+        const auto t0 = std::chrono::steady_clock::now();
+        for (long spins = 0; *tag != want; spins++) {
+            __builtin_ia32_pause();
+            if ((spins & 0xFFFF) == 0xFFFF && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) break;
+        }
+        if (*tag != want) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (*tag != want) return fail(TQGPU_ENODEVICE, "the post of u[0] did not arrive");
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return TQGPU_OK;
+}
+
+struct MpcLive {          /* counts into g_mpc_stats while a step runs */
+    MpcLive() { g_mpc_stats = MpcStats(); g_mpc_live = &g_mpc_stats; }
+    ~MpcLive() { g_mpc_live = nullptr; }
+};
+
+int mpc_post_one(tqgpu_solver *s) {
+    unsigned long long *tag = reinterpret_cast<unsigned long long *>(s->h_mpc + s->mpc_nx0 + s->nu[0]);
+    hipLaunchKernelGGL(k_mpc_post, dim3(1), dim3(256), 0, s->stream, mpc_item(s, false, false), tag, ++s->mpc_tag);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1);
+    return TQGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, const double *b0, const double *S0, const double *r0,
+                                  const double *C0, const double *dmin0, const double *dmax0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_root"))) return rc;
+    SETTLE(s);
+    if (s->nx[0] - s->x_pad > 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: the root still has " + std::to_string(s->nx[0] - s->x_pad) + " states: eliminate x0 first");
+    if (nx0 <= 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: nx0 must be positive");
+    if (s->nk[0] > 0 && (!A0 || !b0)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: A0 and b0 are required");
+    if (S0 && !r0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: S0 comes with r0");
+    if (C0 && !(dmin0 && dmax0)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: C0 comes with dmin0 and dmax0");
+    const size_t n0 = (size_t)nx0, nu0 = (size_t)s->nu[0];
+    const bool kind0 = !s->dense || s->h_kind.empty() || s->h_kind[0] == 0;
+    if (S0 && kind0) {
+        for (size_t i = 0; i < nu0 * n0; i++) if (S0[i] != 0.0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: S0 is not zero on a root of kind 0 (clipping: S must be zero)");
+        S0 = nullptr;
+    }
+    const int nc0 = (!s->gnc.empty() && s->dense && !s->h_kind.empty() && s->h_kind[0] == 3) ? s->gnc[0] : 0;
+    if (C0 && nc0 <= 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: C0 without rows on the root (tqgpu_set_constraints, root of kind 3)");
+    size_t nb = 0;
+    for (int c = 0; c < s->nk[0]; c++) nb += (size_t)s->nx[(size_t)s->kid0[0] + c];
+    const size_t nc = C0 ? (size_t)nc0 : 0;
+    std::vector<double> blk(nb * n0 + nb + nu0 * n0 + nu0 + nc * n0 + 2 * nc + 1, 0.0);
+    double *p = blk.data();
+    if (nb) { memcpy(p, A0, sizeof(double) * nb * n0); p += nb * n0; memcpy(p, b0, sizeof(double) * nb); p += nb; }
+    if (S0) { memcpy(p, S0, sizeof(double) * nu0 * n0); memcpy(p + nu0 * n0, r0, sizeof(double) * nu0); }
+    p += nu0 * n0 + nu0;
+    if (C0) { memcpy(p, C0, sizeof(double) * nc * n0); p += nc * n0; memcpy(p, dmin0, sizeof(double) * nc); p += nc; memcpy(p, dmax0, sizeof(double) * nc); }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the block that is replaced */
+    s->mem.release(s->d_mpc); s->mem.release(s->h_mpc);
+    s->mpc_nx0 = 0;
+    if ((rc = s->mem.upload(s->d_mpc, blk.data(), sizeof(double) * blk.size(), TQGPU_ENOMEM, "the root terms")) ||
+        (rc = s->mem.host(s->h_mpc, sizeof(double) * (n0 + nu0 + 2), "the pinned x0 and u0")))
+        return rc;
+    memset(s->h_mpc, 0, sizeof(double) * (n0 + nu0 + 2));
+    s->mpc_nx0 = nx0; s->mpc_nb = (int)nb; s->mpc_nc0 = (int)nc; s->mpc_S0 = S0 != nullptr; s->mpc_C0 = C0 != nullptr;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_set_x0(tqgpu_solver *s, const double *x0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_x0"))) return rc;
+    if (!x0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_x0: x0 is required");
+    if (!s->d_mpc) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_x0: the root terms have not been given yet (tqgpu_mpc_set_root)");
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = mpc_take_x0(s, x0, "tqgpu_mpc_set_x0"))) return rc;
+    hipLaunchKernelGGL(k_mpc_pre, dim3((unsigned)(s->nk[0] + 1)), dim3(WAVE), 0, s->stream, mpc_item(s, true, false));
+    HIP_TRY(hipGetLastError());
+    s->stream_pending = true;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_set_warm_start(tqgpu_solver *s, int mode) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_set_warm_start"))) return rc;
+    if (mode != 0 && mode != 1) return fail(TQGPU_EINVAL, "tqgpu_set_warm_start: mode must be 0 or 1");
+    s->warm_mode = mode;
+    return TQGPU_OK;
+}
+extern "C" int tqgpu_get_warm_start(const tqgpu_solver *s, int *mode) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_get_warm_start"))) return rc;
+    if (mode) *mode = s->warm_mode;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_get_root_terms(tqgpu_solver *s, double *b_kids, double *r0, double *dmin0, double *dmax0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_get_root_terms"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    size_t nb = 0;
+    for (int c = 0; c < s->nk[0]; c++) nb += (size_t)s->nx[(size_t)s->kid0[0] + c];
+    if (b_kids && nb) HIP_TRY(hipMemcpy(b_kids, s->b + s->xoff[(size_t)s->kid0[0]], sizeof(double) * nb, hipMemcpyDeviceToHost));          /* the children are nodes 1 .. nk[0]: one piece */
+    if (r0 && s->nu[0] > 0) HIP_TRY(hipMemcpy(r0, s->r, sizeof(double) * (size_t)s->nu[0], hipMemcpyDeviceToHost));
+    const int nc0 = s->gnc.empty() || !s->d_drange ? 0 : s->gnc[0];
+    if (dmin0 && nc0) HIP_TRY(hipMemcpy(dmin0, s->d_drange, sizeof(double) * (size_t)nc0, hipMemcpyDeviceToHost));
+    if (dmax0 && nc0) HIP_TRY(hipMemcpy(dmax0, s->d_drange + s->sum_nc, sizeof(double) * (size_t)nc0, hipMemcpyDeviceToHost));
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opts *o, tqgpu_result *res, double *u0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_step"))) return rc;
+    if (!o || !res || !u0) return fail(TQGPU_EINVAL, "tqgpu_mpc_step: bad arguments");
+    if ((rc = mpc_take_x0(s, nullptr, "tqgpu_mpc_step"))) return rc;          /* (the refusals, before anything is touched) */
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    if ((rc = mpc_take_x0(s, x0, "tqgpu_mpc_step"))) return rc;
+    const bool fold = x0 != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0;
+    if (fold || warm) {
+        hipLaunchKernelGGL(k_mpc_pre, dim3(warm ? mpc_pre_blocks(s) : (unsigned)(s->nk[0] + 1)), dim3(WAVE), 0, s->stream, mpc_item(s, fold, warm));
+        HIP_TRY(hipGetLastError());
+        MPC_COUNT(launches, 1);
+        if (warm) s->lam_valid = false;
+        s->stream_pending = true;
+    }
+    s->warm_fresh = true;          /* the start buffer is ready: solve_begin copies nothing */
+    if (s->persist_backoff > 0 && --s->persist_backoff == 0) s->use_persist = s->use_persist_orig;
+    SolveCtx cx(read_solve_env(false), route_of(s, o, false));
+    if ((rc = solve_begin(s, o, cx)) != TQGPU_OK) return rc;
+    const int launches0 = cx.launches;
+    const double *tag = s->h_mpc + s->mpc_nx0 + s->nu[0];
+    /* a single launch: the post goes out behind it now, and the host waits for the tag alone -- the verdict is in the result block by then */
+    bool ahead = single_launch(cx.route);
+    if (ahead && ((rc = mpc_post_one(s)) || (rc = mpc_wait_tag(tag, s->mpc_tag, s->stream)))) ahead = false;          /* (solve_end says what became of the launch) */
+    rc = solve_end(s, o, cx, res);
+    if (rc == TQGPU_ETIMEOUT) { rc = solve_after_timeout(s, o, cx.env, res); ahead = false; }
+    if (rc != TQGPU_OK) return rc;
+    MPC_COUNT(launches, res->n_launches);
+    if (ahead && res->n_launches != launches0) ahead = false;          /* further trials or a relaunch moved u behind the post */
+    if (!ahead && ((rc = mpc_post_one(s)) || (rc = mpc_wait_tag(tag, s->mpc_tag, s->stream)))) return rc;
+    memcpy(u0, s->h_mpc + s->mpc_nx0, sizeof(double) * (size_t)s->nu[0]);
+    return TQGPU_OK;
+}
+
+/* ---- the batch step: per device one launch ahead of the waves of tqgpu_solve_batch, one behind them ---- */
+struct MpcDevice {
+    int device = 0;
+    tqgpu_solver *lead = nullptr;      /* the device's first member: its stream carries both launches, its mirror owns the descriptors and the u0 block */
+    std::vector<int> idx;              /* the device's members, indices into the batch */
+    bool ordered = false;              /* every launch of a later wave finds the launch ahead complete */
+    bool posted = false;               /* u[0] of all members is in the block, behind their last launch */
+    std::vector<int> launches0;        /* per member of idx: launches when its solve had begun (an ahead post is valid if none followed) */
+    size_t n_u0 = 0;                   /* doubles of u0 in the block; the tag lies behind them */
+};
+struct MpcBatch { std::vector<MpcDevice> dev; };
+
+static MpcDevice *mpc_device_of(MpcBatch &mb, int device) {
+    for (MpcDevice &d : mb.dev) if (d.device == device) return &d;
+    return nullptr;
+}
+/* the stream a member's solve launches on in this wave: its group's lead's, or its own */
+static hipStream_t mpc_launch_stream(const BatchMember &m, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg) {
+    const BatchGroup *g = group_of(m, wg, dg, pg);
+    return g ? g->lead->stream : m.s->stream;
+}
+static int mpc_post_batch(MpcDevice &d) {
+    tqgpu_solver *lead = d.lead;
+    unsigned long long *tag = reinterpret_cast<unsigned long long *>(lead->h_mpc_u0s + d.n_u0);
+    hipLaunchKernelGGL(k_mpc_post_batch, dim3(1), dim3(256), 0, lead->stream, lead->d_mitems, (int)d.idx.size(), tag, ++lead->mpc_tag);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1);
+    return mpc_wait_tag(lead->h_mpc_u0s + d.n_u0, lead->mpc_tag, lead->stream);
+}
+/* A wave's launches go out on its group leads' streams and its other members' own; the launch ahead is on the device lead's.  The first wave of
+ * a device that launches anywhere else waits for that stream once; a later wave comes after a verdict of the first, which came after the launch. */
+static int mpc_before_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int j, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg) {
+    MpcDevice *d = mpc_device_of(mb, tab[(size_t)i].s->device);
+    if (!d || d->ordered) return TQGPU_OK;
+    bool elsewhere = false;
+    for (int k = i; k < j; k++) elsewhere |= mpc_launch_stream(tab[(size_t)k], wg, dg, pg) != d->lead->stream;
+    if (elsewhere) { HIP_TRY(hipStreamSynchronize(d->lead->stream)); MPC_COUNT(waits, 1); }
+    d->ordered = true;
+    return TQGPU_OK;
+}
+/* behind the launches of a wave that holds all members of its device, every one of them a single launch on the device lead's stream: the post goes
+ * out now and the host waits for its tag alone; the verdicts are in by then */
+static int mpc_behind_launches(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int j, int ok_to, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg) {
+    MpcDevice *d = mpc_device_of(mb, tab[(size_t)i].s->device);
+    if (!d || ok_to != j || (size_t)(j - i) != d->idx.size() || d->idx[0] != i) return TQGPU_OK;
+    for (int k = i; k < j; k++) {
+        const BatchMember &m = tab[(size_t)k];
+        if (!single_launch(m.cx.route) || mpc_launch_stream(m, wg, dg, pg) != d->lead->stream) return TQGPU_OK;
+    }
+    d->launches0.clear();
+    for (int k = i; k < j; k++) d->launches0.push_back(tab[(size_t)k].cx.launches);
+    if (mpc_post_batch(*d) == TQGPU_OK) d->posted = true;          /* (else: the solves' ends say what became of the launches, and the post is made again) */
+    return TQGPU_OK;
+}
+/* the wave's launches, a shared one once; and whether a post that went out ahead still holds */
+static void mpc_after_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int ok_to, const tqgpu_result *results, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg) {
+    for (const BatchGroup *g : {&wg, &dg, &pg}) if (g->launched) MPC_COUNT(launches, 1);
+    MpcDevice *d = mpc_device_of(mb, tab[(size_t)i].s->device);
+    for (int k = i; k < ok_to; k++) {
+        const BatchGroup *g = group_of(tab[(size_t)k], wg, dg, pg);
+        MPC_COUNT(launches, results[k].n_launches - (g && g->launched ? 1 : 0));
+        if (d && d->posted && (size_t)(k - i) < d->launches0.size() && results[k].n_launches != d->launches0[(size_t)(k - i)]) d->posted = false;
+    }
+}
+
+extern "C" int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double *x0s, const tqgpu_opts *o, tqgpu_result *results, double *u0s) {
+    if (!solvers || n < 1 || !o || !results || !u0s) return fail(TQGPU_EINVAL, "tqgpu_mpc_step_batch: bad arguments");
+    int rc;
+    for (int i = 0; i < n; i++) {
+        if ((rc = mpc_refuse(solvers[i], "tqgpu_mpc_step_batch")) || (rc = mpc_take_x0(solvers[i], nullptr, "tqgpu_mpc_step_batch"))) return rc;
+        for (int k = 0; k < i; k++) if (solvers[k] == solvers[i]) return fail(TQGPU_EINVAL, "tqgpu_mpc_step_batch: a mirror is named twice");
+    }
+    MpcLive live;
+    MpcBatch mb;
+    for (int i = 0; i < n; i++) {
+        MpcDevice *d = mpc_device_of(mb, solvers[i]->device);
+        if (!d) { mb.dev.push_back(MpcDevice()); d = &mb.dev.back(); d->device = solvers[i]->device; d->lead = solvers[i]; }
+        d->idx.push_back(i);
+    }
+    /* the launch ahead, per device: a member's data is touched on the lead's stream, so whatever its own stream (uploads, a solve of its own) or
+     * another batch's lead's stream may still hold for it comes first -- as kkt_group_enqueue; in a loop of batch steps nothing is waited for */
+    size_t x_at = 0;
+    std::vector<size_t> x_off((size_t)n);
+    for (int i = 0; i < n; i++) { x_off[(size_t)i] = x_at; x_at += (size_t)solvers[i]->mpc_nx0; }
+    for (MpcDevice &d : mb.dev) {
+        tqgpu_solver *lead = d.lead;
+        const size_t nm = d.idx.size();
+        HIP_TRY(hipSetDevice(lead->device));
+        if ((rc = grow_items(lead, lead->d_mitems, lead->h_mitems, lead->mitems_cap, nm))) return rc;
+        d.n_u0 = 0;
+        for (int i : d.idx) d.n_u0 += (size_t)solvers[i]->nu[0];
+        if (lead->mpc_u0s_cap < (int)d.n_u0 + 1) {
+            HIP_TRY(hipStreamSynchronize(lead->stream));
+            lead->mem.release(lead->h_mpc_u0s); lead->mpc_u0s_cap = 0;
+            if ((rc = lead->mem.host(lead->h_mpc_u0s, sizeof(double) * (2 * d.n_u0 + 2), "the pinned u0 block of a batch step"))) return rc;
+            memset(lead->h_mpc_u0s, 0, sizeof(double) * (2 * d.n_u0 + 2));
+            lead->mpc_u0s_cap = (int)(2 * d.n_u0 + 2);
+        }
+        std::vector<hipStream_t> waited;
+        auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
+        unsigned blocks = 1;
+        bool any = false;
+        size_t u_at = 0;
+        for (size_t m = 0; m < nm; m++) {
+            tqgpu_solver *s = solvers[d.idx[m]];
+            const bool in_launch = s->settle_stream != nullptr;
+            if (in_launch && s->settle_stream != lead->stream && !was_waited_for(s->settle_stream)) {
+                if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); MPC_COUNT(waits, 1); }
+                SETTLE(s);
+            }
+            const bool own_solve = !in_launch && s->solve_no != s->mpc_drained_at;
+            if (s->stream != lead->stream && (s->stream_pending || own_solve)) {
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                s->stream_pending = false;
+                waited.push_back(s->stream);
+                MPC_COUNT(waits, 1);
+            }
+            if ((rc = mpc_take_x0(s, x0s ? x0s + x_off[(size_t)d.idx[m]] : nullptr, "tqgpu_mpc_step_batch"))) return rc;
+            const bool fold = x0s != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0;
+            MItem &it = lead->h_mitems[m];
+            it = mpc_item(s, fold, warm);
+            it.u0 = lead->h_mpc_u0s + u_at;          /* the batch's block, not the member's own */
+            u_at += (size_t)s->nu[0];
+            if (fold || warm) { any = true; blocks = std::max(blocks, warm ? mpc_pre_blocks(s) : (unsigned)(s->nk[0] + 1)); }
+            if (warm) s->lam_valid = false;
+            s->warm_fresh = true;          /* the start buffer is ready (or stays the caller's): solve_begin copies nothing */
+        }
+        HIP_TRY(hipMemcpyAsync(lead->d_mitems, lead->h_mitems, nm * sizeof(MItem), hipMemcpyHostToDevice, lead->stream)); MPC_COUNT(copies, 1);
+        if (any) {
+            hipLaunchKernelGGL(k_mpc_pre_batch, dim3(blocks, (unsigned)nm), dim3(WAVE), 0, lead->stream, lead->d_mitems);
+            HIP_TRY(hipGetLastError());
+            MPC_COUNT(launches, 1);
+        }
+        lead->stream_pending = true;
+    }
+    rc = solve_batch_impl(solvers, n, o, results, &mb);
+    for (int i = 0; i < n; i++) solvers[i]->mpc_drained_at = solvers[i]->solve_no;          /* (a member that launched on its own stream is waited for below, where the post is made) */
+    if (rc != TQGPU_OK) return rc;
+    for (MpcDevice &d : mb.dev) {
+        HIP_TRY(hipSetDevice(d.lead->device));
+        if (!d.posted) {
+            /* the post behind everything: a member whose last launch ran on another stream than the lead's is waited for first */
+            std::vector<hipStream_t> waited;
+            for (int i : d.idx) {
+                tqgpu_solver *s = solvers[i];
+                const hipStream_t t = s->settle_stream ? s->settle_stream : s->stream;
+                if (t == d.lead->stream || std::find(waited.begin(), waited.end(), t) != waited.end()) continue;
+                HIP_TRY(hipStreamSynchronize(t));
+                waited.push_back(t);
+                MPC_COUNT(waits, 1);
+            }
+            if ((rc = mpc_post_batch(d))) return rc;
+        }
+        size_t u_at = 0;
+        for (int i : d.idx) {
+            size_t out = 0;
+            for (int k = 0; k < i; k++) out += (size_t)solvers[k]->nu[0];
+            memcpy(u0s + out, d.lead->h_mpc_u0s + u_at, sizeof(double) * (size_t)solvers[i]->nu[0]);
+            u_at += (size_t)solvers[i]->nu[0];
+        }
+    }
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_stats(int *launches, int *copies, int *waits) {
+    const MpcStats &st = g_mpc_stats;
+    if (launches) *launches = st.launches;
+    if (copies) *copies = st.copies;
+    if (waits) *waits = st.waits;
     return TQGPU_OK;
 }
 
