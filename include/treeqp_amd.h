@@ -348,11 +348,12 @@ int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, i
 int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, tqgpu_result *results);
 
 /* ---- MPC steps without the host in the data path: the x0 fold, the warm start and u[0] on the device ----------------------------
- * An MPC loop on an x0-eliminated tree (nx[0] == 0, tree_qp_in_eliminate_x0 / tree_qp_in_set_x0_*: qp_container.c) moves x0, starts
- * from the last duals, solves and applies u[0].  These calls keep all of it on the device: the originals of what multiplies x0 stay
- * there, a kernel folds a new x0 into b, r[0], dmin[0], dmax[0] in place, another copies the last duals into the start buffer, and a
- * small kernel behind the solve posts u[0] into pinned memory.  Every call below refuses a rank of a sharded solve
- * (tqgpu_shard_init / tqgpu_pshard_init with nranks > 1) with TQGPU_EUNSUPPORTED.
+ * An MPC loop on an x0-eliminated tree (nx[0] == 0, tree_qp_in_eliminate_x0 / tree_qp_in_set_x0_*: qp_container.c), or on a tree whose
+ * root keeps its states (tqgpu_mpc_set_root_states), moves x0, starts from the last duals, solves and applies u[0].  These calls
+ * keep all of it on the device: the originals of what multiplies x0 stay there, a kernel folds a new x0 into b, r[0], dmin[0],
+ * dmax[0] in place, another copies the last duals into the start buffer, and a small kernel behind the solve posts u[0] into
+ * pinned memory.  Every call below, the getters included, refuses a rank of a sharded solve (tqgpu_shard_init / tqgpu_pshard_init
+ * with nranks > 1) with TQGPU_EUNSUPPORTED, before it touches the device.
  *   tqgpu_mpc_set_root   the originals, copied into device memory (the caller's arrays are free afterwards).  nk0 = nk[0] children:
  *                        A0: for each child of the root in order nx[kid] x nx0, column major, concatenated; b0: nx[kid] each;
  *                        S0 (nu[0] x nx0, column major) with r0 (nu[0]); C0 (nc[0] x nx0, column major) with dmin0, dmax0 (nc[0] each).
@@ -372,7 +373,23 @@ int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, tqg
  *                        route packs r and the bounds (they are repacked when r[0] moved), the rows of kind 3 are read in place.
  *                        A tqgpu_set_constraints that changes nc[0] after tqgpu_mpc_set_root leaves C0 without its rows: TQGPU_EINVAL
  *                        here until tqgpu_mpc_set_root is called again.
- *                        TQGPU_EINVAL before tqgpu_mpc_set_root.
+ *                        TQGPU_EINVAL before tqgpu_mpc_set_root (or tqgpu_mpc_set_root_states).
+ *   tqgpu_mpc_set_root_states   the other form of root: a tree whose root keeps its nx[0] states takes x0 as xmin[0] = xmax[0] = x0 (the
+ *                        nx0 > 0 branch of tree_qp_in_set_x0_strvec).  The call declares that, keeps nothing on the device but a pinned
+ *                        buffer for x0 and u[0], and afterwards tqgpu_mpc_set_x0, tqgpu_mpc_step, tqgpu_mpc_step_batch,
+ *                        tqgpu_set_warm_start and tqgpu_mpc_stats work on the mirror as on an eliminated one, with nx0 = nx[0].
+ *                        The fold is one more role of the same kernel and launch: lanes copy x0[i] bit for bit into xmin[0][i] and
+ *                        xmax[0][i]; no arithmetic.  The persistent route keeps a copy of the bounds in its packed constants: where
+ *                        those are current the fold writes the root's lower and upper entries there as well, so that no re-pack is
+ *                        asked for and a steady-state step stays at 3 launches, 0 copies, 1 wait; where a re-pack is pending for
+ *                        another reason, it reads the folded bounds.  Every other route (single-workgroup, three-launch, wide,
+ *                        tiered, generic, the stage solvers of kinds 2 and 3, the batched launches) reads the bounds in place at
+ *                        every launch.  The stored working sets of kinds 2 and 3 are kept; the pinned host mirror of
+ *                        tqgpu_set_problem is invalidated.
+ *                        TQGPU_EINVAL: the root has no states (tqgpu_mpc_set_root is the call for an eliminated root), or it is of
+ *                        kind 1, whose bounds are ignored -- checked here and again at every fold, in case the kinds changed.
+ *   tqgpu_get_root_bounds       what the device holds now for the root: xmin[0], xmax[0], nx[0] doubles each (either may be NULL).
+ *                        Waits for the mirror's stream.  TQGPU_EUNSUPPORTED on a rank of a sharded solve, as every call here.
  *   tqgpu_set_warm_start mode 0 (default): every solve starts from the buffer of tqgpu_set_lambda.  Mode 1: every solve starts from
  *                        the duals tqgpu_get_solution would return at that moment, whatever the last route and status: a kernel
  *                        ahead of the solve copies them (sum_nx doubles, node-indexed, phantom root states included) into the start
@@ -388,11 +405,28 @@ int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, tqg
  *                        enqueued behind the launch at once and the host waits for its tag only: the verdict is in by then.  If
  *                        the launch was not the whole solve (further line-search trials, a relaunch, a timeout) u[0] is posted again
  *                        behind the rest.  tqgpu_get_solution, tqgpu_get_mu_d, tqgpu_kkt_residual work afterwards as behind tqgpu_solve.
+ *   tqgpu_mpc_set_certify       per mirror, default off.  On: tqgpu_mpc_step also evaluates the KKT residuals of the point it returns, in
+ *                        the same wait: behind the solve and ahead of the post of u[0] it enqueues the packing of the solution (one
+ *                        kernel, one more each where the tree has nodes of kind 2 and of kind 3; the device says which dual buffer
+ *                        is current), the two kernels of tqgpu_kkt_residual and the download of their 12-value head, so the tag the
+ *                        host waits for covers the certificate.  On the single-launch routes all of it goes out behind the launch
+ *                        at once; if the launch was not the whole solve it is enqueued again behind the rest, and the certificate
+ *                        belongs to the returned point.  A certified step on a single-launch route that ends inside its launch:
+ *                        1 (fold + warm start) + 1 (the solve) + 1 + [kind 2] + [kind 3] (packing) + 2 (KKT) + 1 (post) launches,
+ *                        1 copy, 1 wait.  Afterwards the packed point is valid on the device: tqgpu_kkt_residual does not pack
+ *                        again, tqgpu_get_solution only downloads.  tqgpu_mpc_step_batch ignores the setting (a batch has
+ *                        tqgpu_kkt_residual_batch).
+ *   tqgpu_mpc_get_certificate   res[6], node[6] of the last tqgpu_mpc_step of this mirror (either may be NULL; host state only): bit for
+ *                        bit what tqgpu_kkt_residual(s, res, node, NULL) returns right after that step.  TQGPU_EINVAL if that step
+ *                        was not certified, or none has run.
  *   tqgpu_mpc_step_batch the same for n mirrors, x0s member after member (NULL: all keep theirs), u0s member after member, nu[0] of
- *                        each.  Per device the folds and warm-start copies of all members are ONE launch on the stream of the
- *                        device's first member (a descriptor per member, one upload per device and call), ahead of what
- *                        tqgpu_solve_batch launches, and their u[0] are collected by ONE launch behind it.  A member gets bit for bit
- *                        what tqgpu_mpc_step gives it alone wherever tqgpu_solve_batch gives what tqgpu_solve gives.
+ *                        each (x0s: nx0 doubles per member, whichever form its root has; both forms may be mixed).  Per device the
+ *                        folds and warm-start copies of all members are ONE launch on the stream of the device's first member (a
+ *                        descriptor per member, one upload per device and call), ahead of what tqgpu_solve_batch launches, and their
+ *                        u[0] are collected by ONE launch behind it.  A member gets bit for bit what tqgpu_mpc_step gives it alone
+ *                        wherever tqgpu_solve_batch gives what tqgpu_solve gives.  A member of a shared persistent launch whose
+ *                        constants have to be packed again (its first solve, changed data) packs them on its own stream: that
+ *                        stream's work is ordered behind the folds by one wait for the first member's stream in such a step.
  *   tqgpu_mpc_stats      what the calling thread's last tqgpu_mpc_step / _step_batch cost (any pointer may be NULL; host state only):
  *                        launches: kernels enqueued (fold + warm start, the solves' own -- a launch shared by a group of a batch counts
  *                          once --, u0 posts);
@@ -404,12 +438,16 @@ int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, tqg
  *                        persistent members that share one launch: 3 launches, 1 copy, 1 wait, whatever n. */
 int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, const double *b0, const double *S0, const double *r0,
                        const double *C0, const double *dmin0, const double *dmax0);
+int tqgpu_mpc_set_root_states(tqgpu_solver *s);
+int tqgpu_get_root_bounds(tqgpu_solver *s, double *xmin0, double *xmax0);
 int tqgpu_mpc_set_x0(tqgpu_solver *s, const double *x0);
 int tqgpu_set_warm_start(tqgpu_solver *s, int mode);
 int tqgpu_get_warm_start(const tqgpu_solver *s, int *mode);
 int tqgpu_get_root_terms(tqgpu_solver *s, double *b_kids, double *r0, double *dmin0, double *dmax0);
 int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opts *opts, tqgpu_result *res, double *u0);
 int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double *x0s, const tqgpu_opts *opts, tqgpu_result *results, double *u0s);
+int tqgpu_mpc_set_certify(tqgpu_solver *s, int on);
+int tqgpu_mpc_get_certificate(tqgpu_solver *s, double res[6], int node[6]);
 int tqgpu_mpc_stats(int *launches, int *copies, int *waits);
 
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's

@@ -2,7 +2,7 @@
 u[0] on the device) against the host loop, the only way before these calls existed (numpy fold of x0 into b, tqgpu_set_problem with
 the last duals, tqgpu_solve, tqgpu_get_solution).
 
-    python tools/mpc_loop.py [--steps 200] [--skip 10] [--batch 64] [c1] [c2] [batch]
+    python tools/mpc_loop.py [--steps 200] [--skip 10] [--batch 64] [--root-states [--certify]] [c1] [c2] [batch]
 
 Workloads, all x0-eliminated (nx[0] == 0): c1 = problems.spring_mass(), 85 nodes; c2 = problems.linear_chain(2, 9, 9), 1 023 nodes;
 batch = 64 mirrors of c1 from different x0 (tqgpu_mpc_step_batch against fold + tqgpu_set_problem per member, tqgpu_solve_batch,
@@ -13,7 +13,18 @@ runs the same sequence in the same process, on a mirror of the same problem, so 
 step k of both loops is the same QP from the same duals: iterations and trials per step are compared and the steps that differ are
 counted.  Per loop: wall time per step (host perf_counter around the step's calls; median, min, p90 over the steps after --skip),
 the solve's device time (tqgpu_result.device_time), kernel launches and copies per step (device loop: tqgpu_mpc_stats; host loop:
-the solve's launches plus the packing kernel of tqgpu_get_solution, and its three copies: b up, the duals up, the solution down)."""
+the solve's launches plus the packing kernel of tqgpu_get_solution, and its three copies: b up, the duals up, the solution down).
+
+--root-states: the same workloads as they are, not eliminated: the root keeps its states and x0 enters as xmin[0] = xmax[0] = x0
+(tqgpu_mpc_set_root_states).  The host loop is then tqgpu_set_warm_start(1) once and per step tqgpu_set_problem with the root's
+bounds replaced, tqgpu_solve, tqgpu_get_solution (three copies: the two bound arrays up -- the mirror of tqgpu_set_problem finds
+them by comparing every array --, the solution down; launches: the warm-start copy, the solve's own with the re-pack of the
+persistent route, the packing kernel of the solution).  Both loops run on the same x0 sequence, a prescribed path again, here
+x0_i (0.95 + 0.05 sin(0.3 k + i + member)), which stays within the problem's own x0.  --certify adds a third loop and a fourth: the
+certified step (tqgpu_mpc_set_certify) against the plain step followed by tqgpu_kkt_residual, the two ways to know the KKT classes
+of the point whose u[0] is applied.  The certified loop's launches, copies and waits are counted (tqgpu_mpc_stats); those of the
+"step + kkt" loop are the step's counted ones plus what tqgpu_kkt_residual adds by its code, which nothing counts: three launches
+(the packing kernel, k_kkt, k_kkt_max), one copy, one stream synchronisation.  The printed line says so."""
 import ctypes as C
 import sys
 import time
@@ -45,6 +56,12 @@ def eliminated(capi, p):
 
 def moved(x0, k, member):
     return x0 * (1.0 + 0.05 * np.sin(0.3 * k + np.arange(len(x0)) + member))
+
+
+def moved_inward(x0, k, member):
+    """the path of the root-states mode: as `moved`, but never beyond the problem's own x0 (entry i between 0.9 and 1.0 of it): C2's own
+    x0 lies at the edge of what its input bounds can hold, and 5 % beyond it no solve converges"""
+    return x0 * (0.95 + 0.05 * np.sin(0.3 * k + np.arange(len(x0)) + member))
 
 
 def fold_b(A0, b0, x0):
@@ -173,6 +190,145 @@ def batch(capi, p, n, steps, skip):
     print(f"    member steps with other iterations or trials than the host loop: {differ} of {n * steps}; host / device wall {h / v:.2f}", flush=True)
 
 
+ORDER = ("A", "B", "b", "Qd", "Rd", "q", "r", "xmin", "xmax", "umin", "umax")
+
+
+def full_root(capi, p):
+    """(flat problem with the root's states, x0 of the problem)"""
+    nk = p.nk()
+    flat = capi.TreeQp(np.full(p.Nn, p.nx), np.where(nk > 0, p.nu, 0), nk).fill_lti(p).flat()
+    return flat, np.asarray(p.x0, dtype=np.float64).copy()
+
+
+def single_root(capi, name, p, steps, skip, certify):
+    L = capi.lib()
+    d, x0 = full_root(capi, p)
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    nu0, nx0 = int(d["nu"][0]), len(x0)
+    xs = [moved_inward(x0, k, 0) for k in range(steps)]
+    # host loop
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    g.set_warm_start(1)
+    keep = {k: np.ascontiguousarray(d[k], dtype=np.float64).copy() for k in ORDER}
+    sol = [np.zeros(n) for n in (g.sum_nx, g.sum_nu, g.sum_lam, g.sum_nx, g.sum_nu, g.sum_lam)]
+    sp = [dp(b) for b in sol]
+    hw, hd, hl, hc, hcnt, hu = [], [], [], [], [], []
+    for x in xs:
+        t0 = time.perf_counter()
+        keep["xmin"][:nx0] = x
+        keep["xmax"][:nx0] = x
+        assert L.tqgpu_set_problem(g.h, *[dp(keep[k]) for k in ORDER], None) == 0
+        assert L.tqgpu_solve(g.h, C.byref(o), C.byref(r)) == 0
+        assert L.tqgpu_get_solution(g.h, *sp) == 0
+        hw.append(time.perf_counter() - t0)
+        hu.append(sol[1][:nu0].copy())
+        hd.append(r.device_time); hl.append(r.n_launches + 2); hc.append(3); hcnt.append((r.status, r.iter, r.ls_total))      # (+ the warm-start copy, the packing kernel of the export)
+    g.close()
+    u0 = np.zeros(max(nu0, 1))
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    res6, node6 = np.zeros(6), np.zeros(6, dtype=np.int32)
+
+    def device_loop(mode):
+        """mode: 'step', 'certified' (tqgpu_mpc_set_certify), 'step+kkt' (the step, then tqgpu_kkt_residual)"""
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        g.mpc_set_root_states()
+        g.set_warm_start(1)
+        g.mpc_set_certify(mode == "certified")
+        w, dv, ln, cp, wt, cnt, du, same = [], [], [], [], [], [], 0.0, True
+        for k in range(steps):
+            t0 = time.perf_counter()
+            assert L.tqgpu_mpc_step(g.h, dp(xs[k]), C.byref(o), C.byref(r), dp(u0)) == 0
+            if mode == "step+kkt":
+                assert L.tqgpu_kkt_residual(g.h, dp(res6), node6.ctypes.data_as(capi.c_int_p), None) == 0
+            w.append(time.perf_counter() - t0)
+            L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+            extra = (3, 1, 1) if mode == "step+kkt" else (0, 0, 0)          # (tqgpu_kkt_residual: the packing kernel and the two KKT kernels; the head down; the stream)
+            dv.append(r.device_time); ln.append(la.value + extra[0]); cp.append(co.value + extra[1]); wt.append(wa.value + extra[2])
+            cnt.append((r.status, r.iter, r.ls_total))
+            du = max(du, float(np.max(np.abs(u0[:nu0] - hu[k]))))
+            if mode == "certified":
+                assert L.tqgpu_mpc_get_certificate(g.h, dp(res6), node6.ctypes.data_as(capi.c_int_p)) == 0
+        kkt = float(res6.max()) if mode != "step" else g.kkt_residual()["max"]
+        g.close()
+        return w, dv, ln, cp, wt, cnt, du, kkt
+
+    dw, dd, dl, dc, dwt, dcnt, du, kkt = device_loop("step")
+    differ = sum(a != b for a, b in zip(hcnt, dcnt))
+    print(f"{name}, root with states: {len(d['nk'])} nodes, {steps} steps, iterations per step median {np.median([c[1] for c in hcnt]):.0f} "
+          f"(first step {hcnt[0][1]}), all status 0: {all(c[0] == 0 for c in hcnt + dcnt)}")
+    h = report("host loop", hw, hd, hl, hc, skip)
+    v = report("device loop", dw, dd, dl, dc, skip)
+    print(f"    device loop waits per step {np.median(dwt[skip:]):.0f}; steps with other iterations or trials than the host loop: {differ} of {steps}; "
+          f"largest |u0 (device) - u0 (host)| {du:.2e}; KKT of the last device step {kkt:.2e}; host / device wall {h / v:.2f}", flush=True)
+    if certify:
+        cw, cd, cl, cc, cwt, ccnt, cu, ck = device_loop("certified")
+        kw, kd, kl, kc, kwt, kcnt, ku, kk = device_loop("step+kkt")
+        a = report("certified", cw, cd, cl, cc, skip)
+        b = report("step + kkt", kw, kd, kl, kc, skip)
+        print("    (step + kkt: launches, copies and waits are the step's counted ones + 3, 1, 1 for tqgpu_kkt_residual, derived from its code, not counted)")
+        print(f"    waits per step: certified {np.median(cwt[skip:]):.0f} (counted), step + tqgpu_kkt_residual {np.median(kwt[skip:]):.0f} (derived); iterations and trials equal to the plain loop's: "
+              f"{ccnt == dcnt and kcnt == dcnt}; last certificate {ck:.2e} / {kk:.2e}; (step + kkt) / certified wall {b / a:.2f}", flush=True)
+
+
+def batch_root(capi, p, n, steps, skip):
+    L = capi.lib()
+    d, x0 = full_root(capi, p)
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o = capi._gpu_opts()
+    nu0, nx0 = int(d["nu"][0]), len(x0)
+    mk = lambda: [capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d) for _ in range(n)]
+    xs = [[moved_inward(x0, k, i) for i in range(n)] for k in range(steps)]
+    # host loop
+    ms = mk()
+    arr = (C.c_void_p * n)(*[m.h for m in ms])
+    res = (capi.GpuResult * n)()
+    keeps = [{k: np.ascontiguousarray(d[k], dtype=np.float64).copy() for k in ORDER} for _ in range(n)]
+    sols = [[np.zeros(s) for s in (ms[0].sum_nx, ms[0].sum_nu, ms[0].sum_lam, ms[0].sum_nx, ms[0].sum_nu, ms[0].sum_lam)] for _ in range(n)]
+    for m in ms:
+        m.set_warm_start(1)
+    hw, hcnt = [], []
+    for k in range(steps):
+        t0 = time.perf_counter()
+        for i in range(n):
+            keeps[i]["xmin"][:nx0] = xs[k][i]
+            keeps[i]["xmax"][:nx0] = xs[k][i]
+            assert L.tqgpu_set_problem(ms[i].h, *[dp(keeps[i][q]) for q in ORDER], None) == 0
+        assert L.tqgpu_solve_batch(arr, n, C.byref(o), res) == 0
+        for i in range(n):
+            assert L.tqgpu_get_solution(ms[i].h, *[dp(b) for b in sols[i]]) == 0
+        hw.append(time.perf_counter() - t0)
+        hcnt.append([(res[i].status, res[i].iter, res[i].ls_total) for i in range(n)])
+    for m in ms:
+        m.close()
+    # device loop
+    ms = mk()
+    arr = (C.c_void_p * n)(*[m.h for m in ms])
+    for m in ms:
+        m.mpc_set_root_states()
+        m.set_warm_start(1)
+    u0s = np.zeros(n * max(nu0, 1))
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    dw, dl, dc, dwt, dcnt = [], [], [], [], []
+    for k in range(steps):
+        xk = np.ascontiguousarray(np.concatenate(xs[k]))
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_step_batch(arr, n, dp(xk), C.byref(o), res, dp(u0s)) == 0
+        dw.append(time.perf_counter() - t0)
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        dl.append(la.value); dc.append(co.value); dwt.append(wa.value)
+        dcnt.append([(res[i].status, res[i].iter, res[i].ls_total) for i in range(n)])
+    for m in ms:
+        m.close()
+    differ = sum(a != b for ha, da in zip(hcnt, dcnt) for a, b in zip(ha, da))
+    h, hlo, hp = stats(hw[skip:])
+    v, vlo, vp = stats(dw[skip:])
+    print(f"batch, roots with states: {n} mirrors of c1, {steps} steps, all status 0: {all(c[0] == 0 for row in hcnt + dcnt for c in row)}")
+    print(f"    host loop    wall median {h:8.1f} us  min {hlo:8.1f}  p90 {hp:8.1f} | copies {3 * n} (three per member)")
+    print(f"    device loop  wall median {v:8.1f} us  min {vlo:8.1f}  p90 {vp:8.1f} | launches {np.median(dl[skip:]):.0f}  copies {np.median(dc[skip:]):.0f}  waits {np.median(dwt[skip:]):.0f}")
+    print(f"    member steps with other iterations or trials than the host loop: {differ} of {n * steps}; host / device wall {h / v:.2f}", flush=True)
+
+
 def main():
     from treeqp_amd import capi, problems as P
     args = sys.argv[1:]
@@ -181,6 +337,14 @@ def main():
     names = [a for a in args if a in ("c1", "c2", "batch")] or ["c1", "c2", "batch"]
     if capi.device_count() < 1:
         raise SystemExit("no HIP device")
+    if "--root-states" in args:
+        if "c1" in names:
+            single_root(capi, "c1", P.spring_mass(), steps, skip, "--certify" in args)
+        if "c2" in names:
+            single_root(capi, "c2", P.linear_chain(2, 9, 9), steps, skip, "--certify" in args)
+        if "batch" in names:
+            batch_root(capi, P.spring_mass(), n, steps, skip)
+        return
     if "c1" in names:
         single(capi, "c1", P.spring_mass(), steps, skip)
     if "c2" in names:

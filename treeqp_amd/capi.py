@@ -536,13 +536,16 @@ def _gpu_opts(profile=0, **kw) -> GpuOpts:
 
 
 def mpc_step_batch(mirrors, x0s=None, profile=0, **kw):
-    """One MPC step of every mirror (tqgpu_mpc_step_batch): x0s, one vector per member (None: all keep theirs), is folded in on the
+    """One MPC step of every mirror (tqgpu_mpc_step_batch): x0s, one vector per member (None: all keep theirs; nx0 entries each, members
+    with an eliminated root and members whose root keeps its states may be mixed), is folded in on the
     device, the warm start of each member's mode is taken, the batch is solved and u[0] of every member comes back
     -> (list of result dicts, list of u0 arrays)."""
     o = _gpu_opts(profile, **kw)
     n = len(mirrors)
     arr = (C.c_void_p * n)(*[m.h for m in mirrors])
     res = (GpuResult * n)()
+    if x0s is not None:
+        assert len(x0s) == n and all(len(np.ravel(v)) == m.nx0 for v, m in zip(x0s, mirrors)), "x0s: nx0 entries per member"
     x = None if x0s is None else _f64(np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in x0s]))
     nu0 = [int(m.nu[0]) for m in mirrors]
     u = np.zeros(max(sum(nu0), 1))
@@ -731,6 +734,31 @@ class TqGpu:
         self._chk(lib().tqgpu_mpc_set_root(self.h, int(nx0), *[_dp(k) for k in keep]))
         self.nx0 = int(nx0)
         return self
+
+    def mpc_set_root_states(self):
+        """The root keeps its nx[0] states and x0 enters as xmin[0] = xmax[0] = x0 (tqgpu_mpc_set_root_states): afterwards mpc_set_x0,
+        mpc_step and mpc_step_batch work as on an x0-eliminated tree, with nx0 = nx[0]."""
+        self._chk(lib().tqgpu_mpc_set_root_states(self.h))
+        self.nx0 = int(self.nx[0])
+        return self
+
+    def root_bounds(self) -> tuple:
+        """(xmin[0], xmax[0]) as the device holds them now (tqgpu_get_root_bounds); waits for the stream."""
+        lo, hi = np.zeros(int(self.nx[0])), np.zeros(int(self.nx[0]))
+        self._chk(lib().tqgpu_get_root_bounds(self.h, _dp(lo), _dp(hi)))
+        return lo, hi
+
+    def mpc_set_certify(self, on: bool):
+        """on: every mpc_step also evaluates the KKT residuals of its point on the device, in the same wait (tqgpu_mpc_set_certify)"""
+        self._chk(lib().tqgpu_mpc_set_certify(self.h, int(bool(on))))
+        return self
+
+    def mpc_certificate(self) -> dict:
+        """The KKT residuals of the last (certified) mpc_step, as kkt_residual() would return them right after it
+        (tqgpu_mpc_get_certificate; host state only)."""
+        res, node = np.zeros(6), np.zeros(6, dtype=np.int32)
+        self._chk(lib().tqgpu_mpc_get_certificate(self.h, _dp(res), _ip(node)))
+        return _kkt_dict(res, node)
 
     def mpc_set_x0(self, x0):
         """Fold x0 into b of the root's children, r[0], dmin[0], dmax[0] on the device, in place, without synchronisation."""

@@ -1972,6 +1972,9 @@ struct tqgpu_solver {
     double *d_mpc = nullptr, *h_mpc = nullptr;
     int mpc_nx0 = 0, mpc_nb = 0, mpc_nc0 = 0;      /* nx0, rows of b0 (the children's nx), rows of C0; mpc_nx0 == 0: no root terms yet */
     bool mpc_S0 = false, mpc_C0 = false;
+    bool mpc_root_states = false;                  /* tqgpu_mpc_set_root_states: x0 enters as xmin[0] = xmax[0] = x0 over the root's nx[0] states; no originals (d_mpc stays null) */
+    bool mpc_certify = false, mpc_cert_valid = false;      /* tqgpu_mpc_set_certify; mpc_cert holds the certificate of the last tqgpu_mpc_step */
+    double mpc_cert[10] = {};                      /* the head of the KKT result block (KKT_HEAD doubles) as it arrived with the step's tag */
     unsigned long long mpc_tag = 0;                /* the tag of the last u0 post this mirror waited for (its own block, or as the lead of a batch) */
     int warm_mode = 0;                  /* tqgpu_set_warm_start */
     bool warm_fresh = true;             /* the start buffer holds what the caller (or a batch step's launch) put there for the next solve: no copy ahead of it */
@@ -2001,6 +2004,7 @@ struct tqgpu_solver {
     hipStream_t batch_stream = nullptr;                                   /* member of a batch launch in flight: the stream that launch is on (the lead's) */
     bool export_ahead = false;          /* tqgpu_set_export_ahead: the packing kernel and the download of the solution are enqueued right behind a single persistent launch */
     bool export_valid = false;          /* h_out holds (or is about to hold, stream-ordered) the solution of the last solve */
+    bool export_dev_only = false;       /* with export_valid: the pack is in d_out only (a certified tqgpu_mpc_step); tqgpu_get_solution downloads it */
     hipStream_t settle_stream = nullptr;                                  /* member of a batch launch whose verdict is in but whose last workgroups may still write back:
                                                                            * the lead's stream, to be waited for before this mirror is touched through its own stream (settle) */
     size_t sync_words_bytes = 0, lds_persist = 0;
@@ -2875,6 +2879,7 @@ __global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, in
 struct KktPoint { const double *x, *u, *lam, *mu_x, *mu_u, *mu_d; };
 constexpr int KKT_CLASSES = 6;
 constexpr int KKT_HEAD = 10;      /* doubles in front of the per-node table: six maxima, six ints (the nodes), one pad */
+static_assert(sizeof(tqgpu_solver::mpc_cert) == sizeof(double) * KKT_HEAD, "the certificate of a step is the head of the KKT result block");
 
 __device__ __forceinline__ double kkt_viol(double v, double lo, double hi) { return v > hi ? v - hi : v < lo ? lo - v : (v != v ? v : 0.0); }
 /* a multiplier that is exactly zero contributes zero whatever the bound (the reference's 0 * inf is NaN) */
@@ -3041,14 +3046,18 @@ __global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__
  * k_mpc_pre, waves of 64 lanes, blockIdx.x:
  *   [0, nk0)     the fold of root child blockIdx.x: rows over lanes, b = b0, then fma over the columns j of A0 ascending;
  *   nk0          r[0] = r0 + S0 x0 and the rows dmin[0] = dmin0 - C0 x0, dmax[0] = dmax0 - C0 x0, entries over lanes, same order;
+ *                a root that keeps its states (xlo != nullptr) instead: xmin[0] = xmax[0] = x0, copied bit for bit, states over lanes, and
+ *                entries 3, 4 (lower, upper) of the root's packed constants, k_pack_persist's layout cst[(0 * 16 + t) * 5 + ..]; blocks [0, nk0) idle;
  *   nk0 + 1 ..   the warm start: MPC_WARM_SPAN doubles of the current duals each (Ctrl::cur says which buffer: read here, so nothing waits for the host)
  *                into the start buffer, node-indexed as they lie (phantom root states included).
- * The fold writes b, r, dmin, dmax; the copy reads lam0 / lam1 and writes lam_init: the roles touch disjoint data.  No atomics. */
+ * The fold writes b, r, dmin, dmax (or xmin, xmax of the root and their packed copies); the copy reads lam0 / lam1 and writes lam_init: the roles touch disjoint data.  No atomics. */
 struct MItem {
     Tree T; Data D;
     const double *A0, *b0, *S0, *r0, *C0, *dmin0, *dmax0;      /* the originals in device memory (S0, C0: nullptr = zero, the target is left alone) */
     const double *x0;                  /* pinned, read over the bus */
     double *b, *r, *dmin, *dmax;       /* the targets: Data::b, Data::r, Gen::dmin, Gen::dmax */
+    double *xlo, *xhi;                 /* a root that keeps its states (tqgpu_mpc_set_root_states): Data::xmin, Data::xmax of the root, the fold's only targets */
+    double *cst;                       /* ... and the root's packed constants of the persistent route where they are current (else nullptr: the coming re-pack reads Data) */
     double *lam_init;                  /* the start buffer */
     double *u0;                        /* pinned: where k_mpc_post puts u[0] */
     int nx0, nc0, nu0, sum_nx;
@@ -3059,7 +3068,7 @@ __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane
     const Tree &T = it.T;
     const int nk0 = T.nk[0], nx0 = it.nx0;
     if (blk < nk0) {
-        if (!it.fold) return;
+        if (!it.fold || it.xlo) return;
         const int first = T.kid0[0], kid = first + blk, nxk = T.nx[kid];
         int ao = 0, bo = 0;
         for (int c = 0; c < blk; c++) { const int n = T.nx[first + c]; ao += n * nx0; bo += n; }
@@ -3074,6 +3083,14 @@ __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane
     }
     if (blk == nk0) {
         if (!it.fold) return;
+        if (it.xlo) {
+            for (int i = lane; i < nx0; i += WAVE) {
+                const double v = it.x0[i];
+                it.xlo[i] = v; it.xhi[i] = v;
+                if (it.cst && i < 16) { it.cst[(size_t)i * 5 + 3] = v; it.cst[(size_t)i * 5 + 4] = v; }
+            }
+            return;
+        }
         const int nu0 = it.nu0, nc0 = it.nc0;
         if (it.S0) for (int i = lane; i < nu0; i += WAVE) {
             double v = it.r0[i];
@@ -4583,7 +4600,7 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
     if (ahead && enqueue_export(s, nullptr) != TQGPU_OK) return TQGPU_ENODEVICE;
     rc = solve_end(s, o, cx, res);
     if (rc == TQGPU_ETIMEOUT) rc = solve_after_timeout(s, o, cx.env, res);
-    else if (rc == TQGPU_OK && ahead && res->n_launches == launches0) s->export_valid = true;
+    else if (rc == TQGPU_OK && ahead && res->n_launches == launches0) { s->export_valid = true; s->export_dev_only = false; }
     return rc;
 }
 
@@ -4998,6 +5015,8 @@ extern "C" int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_op
 
 namespace {
 
+int root_kind_of(const tqgpu_solver *s) { return s->dense && !s->h_kind.empty() ? s->h_kind[0] : 0; }
+
 int mpc_refuse(const tqgpu_solver *s, const char *who) {
     if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
     if ((s->pshard || s->sharded) && s->nranks > 1)
@@ -5005,7 +5024,7 @@ int mpc_refuse(const tqgpu_solver *s, const char *who) {
     return TQGPU_OK;
 }
 
-/* the descriptor of a mirror for k_mpc_pre / k_mpc_post: views into d_mpc and h_mpc (null before tqgpu_mpc_set_root: fold must be false then) */
+/* the descriptor of a mirror for k_mpc_pre / k_mpc_post: views into d_mpc and h_mpc (null before tqgpu_mpc_set_root / _set_root_states: fold must be false then) */
 MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm) {
     MItem it{};
     it.T = s->T; it.D = s->D;
@@ -5015,7 +5034,12 @@ MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm) {
         it.A0 = p; p += nb * nx0; it.b0 = p; p += nb;
         it.S0 = s->mpc_S0 ? p : nullptr; p += nu0 * nx0; it.r0 = p; p += nu0;
         it.C0 = s->mpc_C0 ? p : nullptr; p += nc0 * nx0; it.dmin0 = p; p += nc0; it.dmax0 = p;
-        it.x0 = s->h_mpc; it.u0 = s->h_mpc + nx0;
+    }
+    if (s->h_mpc) { it.x0 = s->h_mpc; it.u0 = s->h_mpc + nx0; }
+    if (s->mpc_root_states) {
+        /* the packed constants hold a copy of the bounds (k_pack_persist); no other route keeps one: they read Data::xmin / xmax at every launch */
+        it.xlo = s->xmin; it.xhi = s->xmax;
+        it.cst = s->persist_ok && s->pcst && !s->need_pack ? s->pcst : nullptr;
     }
     it.b = s->b; it.r = s->r;
     it.dmin = s->mpc_C0 ? s->d_drange : nullptr; it.dmax = s->mpc_C0 ? s->d_drange + s->sum_nc : nullptr;
@@ -5028,7 +5052,19 @@ unsigned mpc_pre_blocks(const tqgpu_solver *s) { return (unsigned)(s->nk[0] + 1 
 
 /* a new x0 into the mirror's pinned buffer, and what the fold makes stale on the host side; nothing is enqueued */
 int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
-    if (!s->d_mpc) return fail(TQGPU_EINVAL, std::string(who) + ": the root terms have not been given yet (tqgpu_mpc_set_root)");
+    if (!s->d_mpc && !s->mpc_root_states) return fail(TQGPU_EINVAL, std::string(who) + ": the root terms have not been given yet (tqgpu_mpc_set_root, or tqgpu_mpc_set_root_states on a root that keeps its states)");
+    if (s->mpc_root_states) {
+        if (root_kind_of(s) == 1) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 1 after tqgpu_mpc_set_root_states: its bounds are ignored, x0 cannot be imposed");
+        if (!x0) return TQGPU_OK;
+        const size_t n0 = (size_t)s->mpc_nx0;
+        memcpy(s->h_mpc, x0, sizeof(double) * n0);
+        s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes xmin, xmax */
+        if (!s->h_bounds.empty()) {             /* what the box nodes' checks see (tqgpu_set_bounds) */
+            std::copy(x0, x0 + n0, s->h_bounds.begin());
+            std::copy(x0, x0 + n0, s->h_bounds.begin() + s->sum_nx);
+        }
+        return TQGPU_OK;                        /* need_pack stays as it is: the fold writes the packed copy itself */
+    }
     if (s->mpc_C0 && (s->gnc.empty() || s->gnc[0] != s->mpc_nc0 || !s->d_drange))
         return fail(TQGPU_EINVAL, std::string(who) + ": the rows of the root were redefined after tqgpu_mpc_set_root (call it again)");
     if (!x0) return TQGPU_OK;
@@ -5061,6 +5097,8 @@ struct MpcLive {          /* counts into g_mpc_stats while a step runs */
     MpcLive() { g_mpc_stats = MpcStats(); g_mpc_live = &g_mpc_stats; }
     ~MpcLive() { g_mpc_live = nullptr; }
 };
+
+int mpc_enqueue_certificate(tqgpu_solver *s);          /* (with the KKT entry points, below) */
 
 int mpc_post_one(tqgpu_solver *s) {
     unsigned long long *tag = reinterpret_cast<unsigned long long *>(s->h_mpc + s->mpc_nx0 + s->nu[0]);
@@ -5111,11 +5149,58 @@ extern "C" int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, co
     return TQGPU_OK;
 }
 
+extern "C" int tqgpu_mpc_set_root_states(tqgpu_solver *s) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_root_states"))) return rc;
+    SETTLE(s);
+    const int n0 = s->nx[0] - s->x_pad;
+    if (n0 <= 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root_states: the root has no states (x0 is eliminated: tqgpu_mpc_set_root takes the root terms)");
+    if (root_kind_of(s) == 1) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root_states: the root is of kind 1, whose bounds are ignored: x0 cannot be imposed through them");
+    const size_t nu0 = (size_t)s->nu[0];
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the pinned block that is replaced */
+    s->mem.release(s->d_mpc); s->mem.release(s->h_mpc);
+    s->mpc_nx0 = 0; s->mpc_root_states = false;
+    if ((rc = s->mem.host(s->h_mpc, sizeof(double) * ((size_t)n0 + nu0 + 2), "the pinned x0 and u0"))) return rc;
+    memset(s->h_mpc, 0, sizeof(double) * ((size_t)n0 + nu0 + 2));
+    s->mpc_nx0 = n0; s->mpc_nb = 0; s->mpc_nc0 = 0; s->mpc_S0 = false; s->mpc_C0 = false;
+    s->mpc_root_states = true;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_get_root_bounds(tqgpu_solver *s, double *xmin0, double *xmax0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_get_root_bounds"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const int n0 = s->nx[0] - s->x_pad;
+    if (xmin0 && n0 > 0) HIP_TRY(hipMemcpy(xmin0, s->xmin + s->x_pad, sizeof(double) * (size_t)n0, hipMemcpyDeviceToHost));
+    if (xmax0 && n0 > 0) HIP_TRY(hipMemcpy(xmax0, s->xmax + s->x_pad, sizeof(double) * (size_t)n0, hipMemcpyDeviceToHost));
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_set_certify(tqgpu_solver *s, int on) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_certify"))) return rc;
+    s->mpc_certify = on != 0;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_certificate(tqgpu_solver *s, double res[6], int node[6]) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_certificate"))) return rc;
+    if (!s->mpc_cert_valid) return fail(TQGPU_EINVAL, "tqgpu_mpc_get_certificate: the last tqgpu_mpc_step of this mirror was not certified (tqgpu_mpc_set_certify), or none has run");
+    if (res) memcpy(res, s->mpc_cert, sizeof(double) * KKT_CLASSES);
+    if (node) memcpy(node, s->mpc_cert + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
+    return TQGPU_OK;
+}
+
 extern "C" int tqgpu_mpc_set_x0(tqgpu_solver *s, const double *x0) {
     int rc;
     if ((rc = mpc_refuse(s, "tqgpu_mpc_set_x0"))) return rc;
     if (!x0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_x0: x0 is required");
-    if (!s->d_mpc) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_x0: the root terms have not been given yet (tqgpu_mpc_set_root)");
+    if ((rc = mpc_take_x0(s, nullptr, "tqgpu_mpc_set_x0"))) return rc;          /* (the refusals, before anything is touched) */
     SETTLE(s);
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = mpc_take_x0(s, x0, "tqgpu_mpc_set_x0"))) return rc;
@@ -5174,20 +5259,42 @@ extern "C" int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opt
     }
     s->warm_fresh = true;          /* the start buffer is ready: solve_begin copies nothing */
     if (s->persist_backoff > 0 && --s->persist_backoff == 0) s->use_persist = s->use_persist_orig;
+    const bool certify = s->mpc_certify;
+    s->mpc_cert_valid = false;
+    if (certify && (rc = setup_kkt(s, false))) return rc;          /* (allocations, the first time: ahead of the launch) */
     SolveCtx cx(read_solve_env(false), route_of(s, o, false));
     if ((rc = solve_begin(s, o, cx)) != TQGPU_OK) return rc;
     const int launches0 = cx.launches;
     const double *tag = s->h_mpc + s->mpc_nx0 + s->nu[0];
-    /* a single launch: the post goes out behind it now, and the host waits for the tag alone -- the verdict is in the result block by then */
+    /* what goes out behind the solve: of a certified step the packing of the point (which dual buffer is current is the device's knowledge, as
+     * behind tqgpu_set_export_ahead), the two KKT kernels and the download of their head; then the post, whose tag therefore covers them all */
+    auto behind = [&]() -> int {
+        int rcb;
+        if (certify && (rcb = mpc_enqueue_certificate(s))) return rcb;
+        if ((rcb = mpc_post_one(s))) return rcb;
+        return mpc_wait_tag(tag, s->mpc_tag, s->stream);
+    };
+    /* a single launch: all of it goes out behind it now, and the host waits for the tag alone -- the verdict is in the result block by then */
     bool ahead = single_launch(cx.route);
-    if (ahead && ((rc = mpc_post_one(s)) || (rc = mpc_wait_tag(tag, s->mpc_tag, s->stream)))) ahead = false;          /* (solve_end says what became of the launch) */
+    if (ahead) {
+        const MpcStats mark = g_mpc_stats;
+        if (behind() != TQGPU_OK) {          /* (solve_end says what became of the launch; all of it is enqueued again behind it, and counted then) */
+            ahead = false;
+            g_mpc_stats.launches = mark.launches; g_mpc_stats.copies = mark.copies;
+        }
+    }
     rc = solve_end(s, o, cx, res);
     if (rc == TQGPU_ETIMEOUT) { rc = solve_after_timeout(s, o, cx.env, res); ahead = false; }
     if (rc != TQGPU_OK) return rc;
     MPC_COUNT(launches, res->n_launches);
     if (ahead && res->n_launches != launches0) ahead = false;          /* further trials or a relaunch moved u behind the post */
-    if (!ahead && ((rc = mpc_post_one(s)) || (rc = mpc_wait_tag(tag, s->mpc_tag, s->stream)))) return rc;
+    if (!ahead && (rc = behind())) return rc;
     memcpy(u0, s->h_mpc + s->mpc_nx0, sizeof(double) * (size_t)s->nu[0]);
+    if (certify) {
+        memcpy(s->mpc_cert, s->h_kkt, sizeof(s->mpc_cert));
+        s->mpc_cert_valid = true;
+        s->export_valid = true; s->export_dev_only = true;          /* d_out holds the returned point: tqgpu_kkt_residual reads it there, tqgpu_get_solution downloads it */
+    }
     return TQGPU_OK;
 }
 
@@ -5221,12 +5328,19 @@ static int mpc_post_batch(MpcDevice &d) {
     return mpc_wait_tag(lead->h_mpc_u0s + d.n_u0, lead->mpc_tag, lead->stream);
 }
 /* A wave's launches go out on its group leads' streams and its other members' own; the launch ahead is on the device lead's.  The first wave of
- * a device that launches anywhere else waits for that stream once; a later wave comes after a verdict of the first, which came after the launch. */
+ * a device that launches anywhere else waits for that stream once; a later wave comes after a verdict of the first, which came after the launch.
+ * A member of the persistent group launches on the lead's stream, but packs its constants on its OWN stream where a re-pack is pending (launch_persist:
+ * k_pack_persist, first solves and changed data only), and the pack reads what the fold writes -- the root's bounds of a root that keeps its
+ * states, Data::r: such a member counts as launching elsewhere, so its pack finds the fold complete. */
 static int mpc_before_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, int j, const BatchGroup &wg, const BatchGroup &dg, const BatchGroup &pg) {
     MpcDevice *d = mpc_device_of(mb, tab[(size_t)i].s->device);
     if (!d || d->ordered) return TQGPU_OK;
     bool elsewhere = false;
-    for (int k = i; k < j; k++) elsewhere |= mpc_launch_stream(tab[(size_t)k], wg, dg, pg) != d->lead->stream;
+    for (int k = i; k < j; k++) {
+        const BatchMember &m = tab[(size_t)k];
+        elsewhere |= mpc_launch_stream(m, wg, dg, pg) != d->lead->stream;
+        elsewhere |= m.in_persist && m.s->need_pack && m.s->stream != d->lead->stream;
+    }
     if (elsewhere) { HIP_TRY(hipStreamSynchronize(d->lead->stream)); MPC_COUNT(waits, 1); }
     d->ordered = true;
     return TQGPU_OK;
@@ -5839,6 +5953,10 @@ extern "C" int tqgpu_get_solution(tqgpu_solver *s, double *x, double *u, double 
     const double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
     const int nxe = s->sum_nx - s->x_pad, nue = s->sum_nu, nl = s->sum_lam;
     if (!s->export_valid) { int rce = enqueue_export(s, lamc); if (rce != TQGPU_OK) return rce; }      /* (else: went out behind the solve, tqgpu_set_export_ahead) */
+    else if (s->export_dev_only) {          /* packed behind a certified tqgpu_mpc_step, not downloaded yet */
+        HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, st));
+        s->export_dev_only = false;
+    }
     HIP_TRY(hipStreamSynchronize(st));
     const double *ox = s->h_out, *ou = ox + nxe, *ol = ou + nue, *od = ol + nl, *omx = od + nl, *omu = omx + nxe;
     if (x && nxe > 0) memcpy(x, ox, sizeof(double) * (size_t)nxe);
@@ -5866,6 +5984,24 @@ void kkt_collect(const tqgpu_solver *s, double *res, int *node, double *per_node
     if (node) memcpy(node, s->h_kkt + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
     if (per_node) memcpy(per_node, s->h_kkt + KKT_HEAD, sizeof(double) * (size_t)KKT_CLASSES * s->Nn);
 }
+/* the point of a KKT check that reads the export block d_out (and Gen::mu) */
+KktPoint kkt_point_of_export(const tqgpu_solver *s) {
+    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), nue = (size_t)s->sum_nu, nl = (size_t)s->sum_lam;
+    KktPoint P;
+    P.x = s->d_out; P.u = P.x + nxe; P.lam = P.u + nue; P.mu_x = P.lam + 2 * nl; P.mu_u = P.mu_x + nxe;
+    P.mu_d = s->gen ? s->d_gmu : nullptr;
+    return P;
+}
+/* behind the solve of a certified tqgpu_mpc_step (setup_kkt has run): the packing into d_out with the dual buffer the DEVICE calls current -- the
+ * host's h_ctrl->cur is the last solve's while this one runs --, k_kkt, k_kkt_max and the download of the head; nothing is waited for */
+int mpc_enqueue_certificate(tqgpu_solver *s) {
+    int rc;
+    if ((rc = enqueue_export(s, nullptr, false))) return rc;
+    MPC_COUNT(launches, 1 + (s->box ? 1 : 0) + (s->gen ? 1 : 0));
+    if ((rc = kkt_enqueue(s, kkt_point_of_export(s), false))) return rc;
+    MPC_COUNT(launches, 2); MPC_COUNT(copies, 1);
+    return TQGPU_OK;
+}
 /* what every entry point refuses: a rank of a sharded solve holds a part of the solution and runs a part of the launches */
 int kkt_refuse(const tqgpu_solver *s, const char *who) {
     if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
@@ -5880,11 +6016,7 @@ int kkt_enqueue_last(tqgpu_solver *s, bool per_node) {
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = setup_kkt(s, false))) return rc;
     if (!s->export_valid && (rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
-    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), nue = (size_t)s->sum_nu, nl = (size_t)s->sum_lam;
-    KktPoint P;
-    P.x = s->d_out; P.u = P.x + nxe; P.lam = P.u + nue; P.mu_x = P.lam + 2 * nl; P.mu_u = P.mu_x + nxe;
-    P.mu_d = s->gen ? s->d_gmu : nullptr;
-    return kkt_enqueue(s, P, per_node);
+    return kkt_enqueue(s, kkt_point_of_export(s), per_node);
 }
 }  // namespace
 
