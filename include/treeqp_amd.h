@@ -450,6 +450,59 @@ int tqgpu_mpc_set_certify(tqgpu_solver *s, int on);
 int tqgpu_mpc_get_certificate(tqgpu_solver *s, double res[6], int node[6]);
 int tqgpu_mpc_stats(int *launches, int *copies, int *waits);
 
+/* ---- Tracking MPC: the linear terms alone, and a reference window folded into q, r on the device ----------------------------------
+ * A tracking MPC penalises (x - xref)' Q (x - xref) + (u - uref)' R (u - uref) (+ the S terms) along a setpoint or a trajectory that
+ * shifts by one stage per step: only the linear terms q_k = q0_k - Q_k xref - S_k' uref, r_k = r0_k - S_k xref - R_k uref change, on
+ * every node.  In a scenario tree all nodes of a stage share the reference, so the whole trajectory lives on the device once and a step
+ * moves a window index.
+ *   tqgpu_set_linear_terms      q, r in the layout of tqgpu_set_objective_diag; either may be NULL (left alone).  Uploads q and r only, asks
+ *                        the persistent route to pack its constants again and invalidates the pinned host mirror of tqgpu_set_problem.
+ *                        The kinds, H, the factors (k_init / k_dense_init are not run again) and the stored working sets of kinds 2 and
+ *                        3 (the hot start) stay -- tqgpu_set_objective_mixed, the only other way to move r on a dense tree, empties them.
+ *                        Works on every mirror (a rank of a sharded solve included).
+ *   tqgpu_get_linear_terms      what the device holds now, same layout (phantom root states excluded; either may be NULL).  Waits for the
+ *                        mirror's stream.
+ *   tqgpu_mpc_set_tracking      xtraj (T x NXT) and utraj (T x NUT), stage-major (row t, then the entries), T >= 1 (T == 1: a setpoint);
+ *                        q0, r0: the base linear terms in the flat layout (NULL: zeros).  All of it is copied into one device block with
+ *                        the nodes' stages (the caller's arrays are free afterwards); a call replaces an earlier one and forgets the
+ *                        window.  The device's q, r are not touched until a window is set.
+ *                        TQGPU_EINVAL: a node with nx[k] not in {0, NXT} or nu[k] not in {0, NUT}, T < 1, xtraj / utraj NULL while the
+ *                        matching width is positive.
+ *   tqgpu_mpc_set_window        one kernel on the mirror's stream, no synchronisation (as tqgpu_mpc_set_x0): node k reads trajectory row
+ *                        rho = min(t0 + stage[k], T - 1) and every entry of its q, r becomes one chain of fused multiply-adds from its
+ *                        base, columns ascending, one wave per node, rows over lanes:
+ *                          kind 0:          q[i] = fma(-Qd[i], xref[i], q0[i]),  r[i] = fma(-Rd[i], uref[i], r0[i]);
+ *                          kinds 1 / 2 / 3: row i of H_k = [Q S'; S R]: v = base[i]; v = fma(-H[i, j], xref[j], v), j = 0 .. nx - 1;
+ *                                           v = fma(-H[i, nx + j], uref[j], v), j = 0 .. nu - 1.
+ *                        Phantom root states keep their q; a leaf has no u part; the root of an x0-eliminated tree has no x part.
+ *                        An x0-eliminated root with S0 (tqgpu_mpc_set_root; nx0 must equal NXT): r[0] is one chain, base (r0 of
+ *                        tqgpu_mpc_set_tracking; the r0 of tqgpu_mpc_set_root is not read), - R_0 uref, - S0 xref_rho, + S0 x0 with the
+ *                        x0 last given (zeros before the first), computed whenever the window or x0 moves once a window is set: the
+ *                        x0 fold of such a mirror never starts from a stale original.  A tqgpu_mpc_set_root with another nx0 while a
+ *                        window is in force makes every x0 fold and step TQGPU_EINVAL until nx0 and NXT agree again.
+ *                        The persistent route keeps q, r in its packed constants: where those are current the fold writes entry 0 of
+ *                        every node's slots as well and asks for no re-pack; where a re-pack is pending it reads the folded Data.  Every
+ *                        other route (single-workgroup, three-launch, wide, tiered, generic, the stage solvers of kinds 1 / 2 / 3, the
+ *                        batched launches) reads q, r in place at every launch.  Kept: the stored working sets, H, the factor of
+ *                        k_dense_init.  The pinned host mirror of tqgpu_set_problem is invalidated.  tqgpu_set_linear_terms or an
+ *                        upload of the objective afterwards overwrites q, r until the next window fold, which starts from the bases.
+ *                        TQGPU_EINVAL: t0 < 0, or before tqgpu_mpc_set_tracking.
+ *   tqgpu_mpc_get_window        the window in force, -1 before the first fold (host state only).
+ *   tqgpu_mpc_step_at / tqgpu_mpc_step_batch_at   tqgpu_mpc_step / tqgpu_mpc_step_batch with the window fold inside their ONE launch ahead
+ *                        of the solve (further blocks of the same kernel): t0 (t0s[i] per member; t0s == NULL: all -1) >= 0 moves the
+ *                        window, < 0 keeps it -- then the call is the plain step, on mirrors without tracking too, which a batch may
+ *                        mix with tracking ones.  t0 >= 0 before tqgpu_mpc_set_tracking: TQGPU_EINVAL.  Counts are those of the plain
+ *                        steps (persistent route, ending inside its launch: 3 launches, 0 copies, 1 wait; a batch of persistent members
+ *                        3, 1, 1); certification (tqgpu_mpc_set_certify) works unchanged.
+ * The tqgpu_mpc_* calls above refuse a rank of a sharded solve with TQGPU_EUNSUPPORTED, as every tqgpu_mpc_* call. */
+int tqgpu_set_linear_terms(tqgpu_solver *s, const double *q, const double *r);
+int tqgpu_get_linear_terms(tqgpu_solver *s, double *q, double *r);
+int tqgpu_mpc_set_tracking(tqgpu_solver *s, int NXT, int NUT, int T, const double *xtraj, const double *utraj, const double *q0, const double *r0);
+int tqgpu_mpc_set_window(tqgpu_solver *s, int t0);
+int tqgpu_mpc_get_window(const tqgpu_solver *s, int *t0);
+int tqgpu_mpc_step_at(tqgpu_solver *s, const double *x0, int t0, const tqgpu_opts *opts, tqgpu_result *res, double *u0);
+int tqgpu_mpc_step_batch_at(tqgpu_solver **solvers, int n, const double *x0s, const int *t0s, const tqgpu_opts *opts, tqgpu_result *results, double *u0s);
+
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written
  * (at most 512 solves back) or -1.  tqgpu_result.device_time of a single-launch (persistent) solve is

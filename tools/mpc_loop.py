@@ -3,6 +3,7 @@ u[0] on the device) against the host loop, the only way before these calls exist
 the last duals, tqgpu_solve, tqgpu_get_solution).
 
     python tools/mpc_loop.py [--steps 200] [--skip 10] [--batch 64] [--root-states [--certify]] [c1] [c2] [batch]
+    python tools/mpc_loop.py --tracking [--steps 200] [--skip 10] [--batch 64] [c1] [c2] [kind3] [batch]
 
 Workloads, all x0-eliminated (nx[0] == 0): c1 = problems.spring_mass(), 85 nodes; c2 = problems.linear_chain(2, 9, 9), 1 023 nodes;
 batch = 64 mirrors of c1 from different x0 (tqgpu_mpc_step_batch against fold + tqgpu_set_problem per member, tqgpu_solve_batch,
@@ -24,7 +25,15 @@ x0_i (0.95 + 0.05 sin(0.3 k + i + member)), which stays within the problem's own
 certified step (tqgpu_mpc_set_certify) against the plain step followed by tqgpu_kkt_residual, the two ways to know the KKT classes
 of the point whose u[0] is applied.  The certified loop's launches, copies and waits are counted (tqgpu_mpc_stats); those of the
 "step + kkt" loop are the step's counted ones plus what tqgpu_kkt_residual adds by its code, which nothing counts: three launches
-(the packing kernel, k_kkt, k_kkt_max), one copy, one stream synchronisation.  The printed line says so."""
+(the packing kernel, k_kkt, k_kkt_max), one copy, one stream synchronisation.  The printed line says so.
+
+--tracking: the root-states workloads with a reference trajectory that shifts one stage per step (tqgpu_mpc_set_tracking, and the window
+inside tqgpu_mpc_step_at / tqgpu_mpc_step_batch_at; member i of the batch is i stages ahead) against the host loop of the parent
+commit's API: numpy fold of the window into q, r, tqgpu_set_problem with the root's bounds replaced, tqgpu_solve, tqgpu_get_solution
+(five copies: q, r and the two bound arrays up, the solution down).  kind3 is an 85-node dense tree with 21 kind-3 nodes (kind3_tree:
+the shape of tests/gen_cases.scaled_one_row with data that converge): there the host loop has to go through tqgpu_set_objective_mixed,
+which empties the stored working sets; the device loop is tqgpu_mpc_step_at, tqgpu_get_solution; active-set steps per kind-3 node and
+stage sweep are printed for both."""
 import ctypes as C
 import sys
 import time
@@ -329,14 +338,256 @@ def batch_root(capi, p, n, steps, skip):
     print(f"    member steps with other iterations or trials than the host loop: {differ} of {n * steps}; host / device wall {h / v:.2f}", flush=True)
 
 
+def node_stages(nk):
+    st, nxt = np.zeros(len(nk), dtype=int), 1
+    for k, n in enumerate(np.asarray(nk, dtype=int)):
+        st[nxt:nxt + n] = st[k] + 1
+        nxt += n
+    return st
+
+
+def reference(x0, nu, rows):
+    """a reference that shifts one stage per step: row t is 2 % of x0, entry i swinging with sin(0.2 t + i); inputs track zero"""
+    t = np.arange(rows)[:, None]
+    return 0.02 * x0[None, :] * np.sin(0.2 * t + np.arange(len(x0))[None, :]), np.zeros((rows, nu))
+
+
+def tracking_single(capi, name, p, steps, skip):
+    """root with states, clipping: the host loop folds the window in numpy (q = q0 - Qd xref, r = r0 - Rd uref, rows by stage) and
+    hands everything to tqgpu_set_problem; the device loop is tqgpu_mpc_step_at"""
+    L = capi.lib()
+    d, x0 = full_root(capi, p)
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    nu0, nx0, nx, nu = int(d["nu"][0]), len(x0), int(d["nx"][0]), int(d["nu"][0])
+    st = node_stages(d["nk"])
+    X, U = reference(x0, nu, steps + int(st.max()) + 1)
+    stx, stu = np.repeat(st, d["nx"]), np.repeat(st, d["nu"])
+    ix, iu = np.tile(np.arange(nx), len(st)), np.tile(np.arange(nu), int((np.asarray(d["nu"]) > 0).sum()))
+    xs = [moved_inward(x0, k, 0) for k in range(steps)]
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    g.set_warm_start(1)
+    keep = {k: np.ascontiguousarray(d[k], dtype=np.float64).copy() for k in ORDER}
+    q0, r0 = keep["q"].copy(), keep["r"].copy()
+    sol = [np.zeros(n) for n in (g.sum_nx, g.sum_nu, g.sum_lam, g.sum_nx, g.sum_nu, g.sum_lam)]
+    sp = [dp(b) for b in sol]
+    hw, hd, hl, hc, hcnt, hu = [], [], [], [], [], []
+    for k, x in enumerate(xs):
+        t0 = time.perf_counter()
+        keep["xmin"][:nx0] = x
+        keep["xmax"][:nx0] = x
+        keep["q"][:] = q0 - keep["Qd"] * X[k + stx, ix]
+        keep["r"][:] = r0 - keep["Rd"] * U[k + stu, iu]
+        assert L.tqgpu_set_problem(g.h, *[dp(keep[n]) for n in ORDER], None) == 0
+        assert L.tqgpu_solve(g.h, C.byref(o), C.byref(r)) == 0
+        assert L.tqgpu_get_solution(g.h, *sp) == 0
+        hw.append(time.perf_counter() - t0)
+        hu.append(sol[1][:nu0].copy())
+        hd.append(r.device_time); hl.append(r.n_launches + 2); hc.append(5); hcnt.append((r.status, r.iter, r.ls_total))      # (copies: q, r, the two bound arrays up, the solution down)
+    g.close()
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    g.mpc_set_root_states()
+    g.set_warm_start(1)
+    g.mpc_set_tracking(X, U, q0, r0)
+    u0 = np.zeros(max(nu0, 1))
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    dw, dd, dl, dc, dwt, dcnt, du = [], [], [], [], [], [], 0.0
+    for k in range(steps):
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_step_at(g.h, dp(xs[k]), k, C.byref(o), C.byref(r), dp(u0)) == 0
+        dw.append(time.perf_counter() - t0)
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        dd.append(r.device_time); dl.append(la.value); dc.append(co.value); dwt.append(wa.value); dcnt.append((r.status, r.iter, r.ls_total))
+        du = max(du, float(np.max(np.abs(u0[:nu0] - hu[k]))))
+    kkt = g.kkt_residual()["max"]
+    g.close()
+    differ = sum(a != b for a, b in zip(hcnt, dcnt))
+    print(f"{name}, tracking, root with states: {len(d['nk'])} nodes, {steps} steps, iterations per step mean {np.mean([c[1] for c in hcnt]):.2f} / {np.mean([c[1] for c in dcnt]):.2f}, "
+          f"trials per step mean {np.mean([c[2] for c in hcnt]):.2f} / {np.mean([c[2] for c in dcnt]):.2f} (host / device), all status 0: {all(c[0] == 0 for c in hcnt + dcnt)}")
+    h = report("host loop", hw, hd, hl, hc, skip)
+    v = report("device loop", dw, dd, dl, dc, skip)
+    print(f"    device loop waits per step {np.median(dwt[skip:]):.0f}; steps with other iterations or trials than the host loop: {differ} of {steps}; "
+          f"largest |u0 (device) - u0 (host)| {du:.2e}; KKT of the last device step {kkt:.2e}; host / device wall {h / v:.2f}", flush=True)
+
+
+def tracking_batch(capi, p, n, steps, skip):
+    L = capi.lib()
+    d, x0 = full_root(capi, p)
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o = capi._gpu_opts()
+    nu0, nx0, nx, nu = int(d["nu"][0]), len(x0), int(d["nx"][0]), int(d["nu"][0])
+    st = node_stages(d["nk"])
+    X, U = reference(x0, nu, steps + n + int(st.max()) + 1)
+    stx, stu = np.repeat(st, d["nx"]), np.repeat(st, d["nu"])
+    ix, iu = np.tile(np.arange(nx), len(st)), np.tile(np.arange(nu), int((np.asarray(d["nu"]) > 0).sum()))
+    mk = lambda: [capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d) for _ in range(n)]
+    xs = [[moved_inward(x0, k, i) for i in range(n)] for k in range(steps)]
+    ms = mk()
+    arr = (C.c_void_p * n)(*[m.h for m in ms])
+    res = (capi.GpuResult * n)()
+    keeps = [{k: np.ascontiguousarray(d[k], dtype=np.float64).copy() for k in ORDER} for _ in range(n)]
+    q0, r0 = keeps[0]["q"].copy(), keeps[0]["r"].copy()
+    sols = [[np.zeros(s) for s in (ms[0].sum_nx, ms[0].sum_nu, ms[0].sum_lam, ms[0].sum_nx, ms[0].sum_nu, ms[0].sum_lam)] for _ in range(n)]
+    for m in ms:
+        m.set_warm_start(1)
+    hw, hcnt = [], []
+    for k in range(steps):
+        t0 = time.perf_counter()
+        for i in range(n):          # member i is i stages ahead along the same reference
+            keeps[i]["xmin"][:nx0] = xs[k][i]
+            keeps[i]["xmax"][:nx0] = xs[k][i]
+            keeps[i]["q"][:] = q0 - keeps[i]["Qd"] * X[k + i + stx, ix]
+            keeps[i]["r"][:] = r0 - keeps[i]["Rd"] * U[k + i + stu, iu]
+            assert L.tqgpu_set_problem(ms[i].h, *[dp(keeps[i][q]) for q in ORDER], None) == 0
+        assert L.tqgpu_solve_batch(arr, n, C.byref(o), res) == 0
+        for i in range(n):
+            assert L.tqgpu_get_solution(ms[i].h, *[dp(b) for b in sols[i]]) == 0
+        hw.append(time.perf_counter() - t0)
+        hcnt.append([(res[i].status, res[i].iter, res[i].ls_total) for i in range(n)])
+    for m in ms:
+        m.close()
+    ms = mk()
+    arr = (C.c_void_p * n)(*[m.h for m in ms])
+    for m in ms:
+        m.mpc_set_root_states()
+        m.set_warm_start(1)
+        m.mpc_set_tracking(X, U, q0, r0)
+    u0s = np.zeros(n * max(nu0, 1))
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    dw, dl, dc, dwt, dcnt = [], [], [], [], []
+    for k in range(steps):
+        xk = np.ascontiguousarray(np.concatenate(xs[k]))
+        t0s = np.arange(k, k + n, dtype=np.int32)
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_step_batch_at(arr, n, dp(xk), t0s.ctypes.data_as(capi.c_int_p), C.byref(o), res, dp(u0s)) == 0
+        dw.append(time.perf_counter() - t0)
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        dl.append(la.value); dc.append(co.value); dwt.append(wa.value)
+        dcnt.append([(res[i].status, res[i].iter, res[i].ls_total) for i in range(n)])
+    for m in ms:
+        m.close()
+    differ = sum(a != b for ha, da in zip(hcnt, dcnt) for a, b in zip(ha, da))
+    h, hlo, hp = stats(hw[skip:])
+    v, vlo, vp = stats(dw[skip:])
+    mean = lambda cnt, j: np.mean([c[j] for row in cnt for c in row])
+    print(f"batch, tracking, roots with states: {n} mirrors of c1, {steps} steps, iterations per member step mean {mean(hcnt, 1):.2f} / {mean(dcnt, 1):.2f}, trials {mean(hcnt, 2):.2f} / {mean(dcnt, 2):.2f} "
+          f"(host / device), all status 0: {all(c[0] == 0 for row in hcnt + dcnt for c in row)}")
+    print(f"    host loop    wall median {h:8.1f} us  min {hlo:8.1f}  p90 {hp:8.1f} | copies {5 * n} (five per member)")
+    print(f"    device loop  wall median {v:8.1f} us  min {vlo:8.1f}  p90 {vp:8.1f} | launches {np.median(dl[skip:]):.0f}  copies {np.median(dc[skip:]):.0f}  waits {np.median(dwt[skip:]):.0f}")
+    print(f"    member steps with other iterations or trials than the host loop: {differ} of {n * steps}; host / device wall {h / v:.2f}", flush=True)
+
+
+def kind3_tree(seed=7, span=0.0625):
+    """85 nodes (1 + 4 + 16 + 64, nx = 2, nu = 1: the shape of tests/gen_cases.scaled_one_row) with dense data that converge
+    (helpers.dense_shaped_qp): the 21 parents are kind-3 nodes with one row each, C x + D u within +- span (C = 0 on the root, whose
+    states are fixed), the leaves kind 2"""
+    import helpers as H
+    import limit_shapes as S
+    shape = (2, 1, [(2, 1, [(2, 1, [S.leaf(2)] * 4)] * 4)] * 4)
+    nk, nx, nu = S.flatten(shape)
+    d = H.dense_shaped_qp(nk, nx, nu, seed)
+    kinds = np.where(nk > 0, 3, 2).astype(np.int32)
+    rng = np.random.Generator(np.random.PCG64(seed + 5))
+    n3 = int((nk > 0).sum())
+    d["nc"] = (nk > 0).astype(np.int32)
+    d["C"] = 0.25 * rng.standard_normal(2 * n3)
+    d["C"][:2] = 0.0
+    d["D"] = 0.5 + np.abs(rng.standard_normal(n3))
+    d["dmin"], d["dmax"] = -span * np.ones(n3), span * np.ones(n3)
+    return d, kinds
+
+
+def tracking_kind3(capi, steps, skip):
+    """the 85-node tree of kind3_tree (21 kind-3 nodes): the reference moves one stage per step, x0 stays.  Host loop: vectorised numpy
+    fold over the dense blocks, upload_mixed with the last duals (the only way to move r on a dense tree before
+    tqgpu_set_linear_terms; tqgpu_set_objective_mixed empties the stored working sets), solve, download.  Device loop:
+    tqgpu_mpc_step_at with warm start 1, download."""
+    import solve_sequence_cases as SC
+    import tracking_cases as K
+    d, kinds = kind3_tree()
+    nk = np.asarray(d["nk"])
+    n3, Np = int((kinds == 3).sum()), int((nk > 0).sum())
+    assert np.all(nk[:Np] > 0) and np.all(nk[Np:] == 0)          # breadth first: the parents come first
+    st = node_stages(nk)
+    t = np.arange(steps + int(st.max()) + 1)[:, None]
+    X = 0.05 * np.sin(0.2 * t + np.arange(2)[None, :])
+    U = 0.05 * np.sin(0.2 * t + 1.0 + np.arange(1)[None, :])
+    Hp = np.stack([np.block([[Q, S_.T], [S_, R_]]) for Q, R_, S_ in (K.blocks(d, k) for k in range(Np))])
+    Hl = np.stack([K.blocks(d, k)[0] for k in range(Np, len(nk))])
+    q0, r0 = np.array(d["q"], copy=True), np.array(d["r"], copy=True)
+    opts = dict(SC.FULL)
+
+    def host_fold(k):
+        vp = np.einsum("nij,nj->ni", Hp, np.concatenate([X[k + st[:Np]], U[k + st[:Np]]], axis=1))
+        vl = np.einsum("nij,nj->ni", Hl, X[k + st[Np:]])
+        return q0 - np.concatenate([vp[:, :2].ravel(), vl.ravel()]), r0 - vp[:, 2:].ravel()
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"])
+        g.set_constraints(d["nc"], d["C"], d["D"], d["dmin"], d["dmax"])
+        g.upload_mixed(d, kinds, None)
+        g.set_warm_start(1)
+        return g
+
+    qk, rk = host_fold(3)
+    qn, rn = K.fold(dict(d=d, form="states", T=len(X), q0=q0, r0=r0, xtraj=X, utraj=U), 3)
+    assert np.allclose(qk, qn, rtol=0, atol=1e-14) and np.allclose(rk, rn, rtol=0, atol=1e-14)
+    out = {}
+    for how in ("host loop", "device loop"):
+        g = mirror()
+        if how == "device loop":
+            g.mpc_set_root_states()
+            g.mpc_set_tracking(X, U, q0, r0)
+        w, cnt, act, st_, lam, usum = [], [], [], [], None, []
+        for k in range(steps):
+            t0 = time.perf_counter()
+            if how == "host loop":
+                q, r = host_fold(k)
+                g.upload_mixed(dict(d, q=q, r=r), kinds, lam)
+                res = g.solve(**opts)
+            else:
+                res, _ = g.mpc_step(None, t0=k, **opts)
+                st_.append(capi.mpc_stats())
+            sol = g.solution()
+            w.append(time.perf_counter() - t0)
+            lam = sol["lam"]
+            usum.append(sol["u"].copy())
+            cnt.append((res["status"], res["iter"], res["ls_total"], res["n_launches"]))
+            act.append(float(g.stage_steps()["total"].sum()) / (n3 * (res["ls_total"] + 1)))
+        rows = int(np.count_nonzero(sol["mu_d"]))
+        g.close()
+        out[how] = (w, cnt, act, usum, rows, st_)
+    hc, dc = out["host loop"][1], out["device loop"][1]
+    differ = sum(a[:3] != b[:3] for a, b in zip(hc, dc))
+    du = max(float(np.max(np.abs(a - b))) for a, b in zip(out["host loop"][3], out["device loop"][3]))
+    print(f"kind3, tracking: 85 nodes, {n3} of kind 3 with one row each, {steps} steps; steps with other iterations or trials than the host loop: {differ} of {steps}; "
+          f"largest |u (device) - u (host)| {du:.2e}; rows active at the last solution {out['host loop'][4]} / {out['device loop'][4]}")
+    for how, (w, cnt, act, _, _, st_) in out.items():
+        med, lo, p90 = stats(w[skip:])
+        extra = f" | step launches {np.median([s['launches'] for s in st_[skip:]]):.0f} copies {np.median([s['copies'] for s in st_[skip:]]):.0f} waits {np.median([s['waits'] for s in st_[skip:]]):.0f}" if st_ else ""
+        print(f"    {how:12s} wall median {med:9.1f} us  min {lo:9.1f}  p90 {p90:9.1f} | iterations mean {np.mean([c[1] for c in cnt[skip:]]):.2f}  trials mean {np.mean([c[2] for c in cnt[skip:]]):.2f}  "
+              f"solve launches median {np.median([c[3] for c in cnt[skip:]]):.0f} | status 0 in {sum(c[0] == 0 for c in cnt)} of {steps} | "
+              f"active-set steps per kind-3 node and sweep (ls_total + 1 sweeps) {np.mean(act[skip:]):.2f}{extra}", flush=True)
+
+
 def main():
     from treeqp_amd import capi, problems as P
     args = sys.argv[1:]
     take = lambda flag, default: int(args[args.index(flag) + 1]) if flag in args else default
     steps, skip, n = take("--steps", 200), take("--skip", 10), take("--batch", 64)
-    names = [a for a in args if a in ("c1", "c2", "batch")] or ["c1", "c2", "batch"]
+    names = [a for a in args if a in ("c1", "c2", "batch", "kind3")] or ["c1", "c2", "batch"]
     if capi.device_count() < 1:
         raise SystemExit("no HIP device")
+    if "--tracking" in args:
+        if "c1" in names:
+            tracking_single(capi, "c1", P.spring_mass(), steps, skip)
+        if "c2" in names:
+            tracking_single(capi, "c2", P.linear_chain(2, 9, 9), steps, skip)
+        if "kind3" in names:
+            tracking_kind3(capi, steps, skip)
+        if "batch" in names:
+            tracking_batch(capi, P.spring_mass(), n, steps, skip)
+        return
     if "--root-states" in args:
         if "c1" in names:
             single_root(capi, "c1", P.spring_mass(), steps, skip, "--certify" in args)

@@ -539,7 +539,9 @@ def mpc_step_batch(mirrors, x0s=None, profile=0, **kw):
     """One MPC step of every mirror (tqgpu_mpc_step_batch): x0s, one vector per member (None: all keep theirs; nx0 entries each, members
     with an eliminated root and members whose root keeps its states may be mixed), is folded in on the
     device, the warm start of each member's mode is taken, the batch is solved and u[0] of every member comes back
-    -> (list of result dicts, list of u0 arrays)."""
+    -> (list of result dicts, list of u0 arrays).  t0s (tqgpu_mpc_step_batch_at): one reference window per member, folded into q, r in
+    the same launch; an entry < 0 keeps the member's window (members without tracking take -1).  t0s is a keyword like the options."""
+    t0s = kw.pop("t0s", None)
     o = _gpu_opts(profile, **kw)
     n = len(mirrors)
     arr = (C.c_void_p * n)(*[m.h for m in mirrors])
@@ -549,9 +551,14 @@ def mpc_step_batch(mirrors, x0s=None, profile=0, **kw):
     x = None if x0s is None else _f64(np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in x0s]))
     nu0 = [int(m.nu[0]) for m in mirrors]
     u = np.zeros(max(sum(nu0), 1))
-    rc = lib().tqgpu_mpc_step_batch(arr, n, _dp(x), C.byref(o), res, _dp(u))
+    if t0s is None:
+        rc = lib().tqgpu_mpc_step_batch(arr, n, _dp(x), C.byref(o), res, _dp(u))
+    else:
+        t = _i32(t0s)
+        assert len(t) == n, "t0s: one window per member"
+        rc = lib().tqgpu_mpc_step_batch_at(arr, n, _dp(x), _ip(t), C.byref(o), res, _dp(u))
     if rc != 0:
-        raise RuntimeError(f"tqgpu_mpc_step_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+        raise RuntimeError(f"tqgpu_mpc_step_batch{'' if t0s is None else '_at'} failed ({rc}): {lib().tqgpu_last_error().decode()}")
     at = np.concatenate([[0], np.cumsum(nu0)]).astype(int)
     return ([{f: getattr(res[i], f) for f, _ in GpuResult._fields_} for i in range(n)],
             [u[at[i]:at[i + 1]].copy() for i in range(n)])
@@ -789,9 +796,50 @@ class TqGpu:
         self._chk(lib().tqgpu_get_root_terms(self.h, _dp(out["b"]), _dp(out["r"]), _dp(out.get("dmin")), _dp(out.get("dmax"))))
         return out
 
+    # ---- tracking: the linear terms alone, a reference window folded into q, r on the device ----
+    def set_linear_terms(self, q=None, r=None):
+        """q, r alone (tqgpu_set_linear_terms; None: left alone): kinds, H, factors and the stored working sets of kinds 2 and 3 stay."""
+        a, b = (None if q is None else _f64(q)), (None if r is None else _f64(r))
+        assert a is None or len(a) == self.sum_nx
+        assert b is None or len(b) == self.sum_nu
+        self._chk(lib().tqgpu_set_linear_terms(self.h, _dp(a), _dp(b)))
+        return self
+
+    def linear_terms(self) -> tuple:
+        """(q, r) as the device holds them now (tqgpu_get_linear_terms); waits for the stream."""
+        q, r = np.zeros(self.sum_nx), np.zeros(self.sum_nu)
+        self._chk(lib().tqgpu_get_linear_terms(self.h, _dp(q), _dp(r)))
+        return q, r
+
+    def mpc_set_tracking(self, xtraj, utraj, q0=None, r0=None):
+        """The reference trajectory, xtraj (T, NXT) and utraj (T, NUT), one row per stage, and the base linear terms q0, r0 (flat; None:
+        zeros), kept on the device (tqgpu_mpc_set_tracking).  The window is set by mpc_set_window, mpc_step(t0=) or mpc_step_batch(t0s=)."""
+        X, U = np.atleast_2d(_f64(xtraj)), np.atleast_2d(_f64(utraj))
+        assert X.shape[0] == U.shape[0], "xtraj and utraj: one row per stage each"
+        a, b = (None if q0 is None else _f64(q0)), (None if r0 is None else _f64(r0))
+        assert a is None or len(a) == self.sum_nx
+        assert b is None or len(b) == self.sum_nu
+        X, U = np.ascontiguousarray(X), np.ascontiguousarray(U)
+        self._chk(lib().tqgpu_mpc_set_tracking(self.h, int(X.shape[1]), int(U.shape[1]), int(X.shape[0]),
+                                               _dp(X) if X.size else None, _dp(U) if U.size else None, _dp(a), _dp(b)))
+        return self
+
+    def mpc_set_window(self, t0: int):
+        """Fold the reference window that starts at row t0 into q, r on the device, in place, without synchronisation (tqgpu_mpc_set_window)."""
+        self._chk(lib().tqgpu_mpc_set_window(self.h, int(t0)))
+        return self
+
+    @property
+    def mpc_window(self) -> int:
+        v = C.c_int()
+        self._chk(lib().tqgpu_mpc_get_window(self.h, C.byref(v)))
+        return v.value
+
     def mpc_step(self, x0=None, profile=0, **kw):
         """One MPC step (tqgpu_mpc_step): fold x0 (None: keep the current one), warm start of the current mode, solve
-        -> (result dict, u[0])."""
+        -> (result dict, u[0]).  t0=, a keyword like the options (tqgpu_mpc_step_at): the reference window to fold into q, r in the same
+        launch; None or < 0 keeps the window in force."""
+        t0 = kw.pop("t0", None)
         key = (profile, tuple(sorted(kw.items())))
         cache = self.__dict__.setdefault("_opts_cache", {})
         o = cache.get(key)
@@ -802,7 +850,10 @@ class TqGpu:
             assert len(a) == self.nx0
         r = GpuResult()
         u0 = np.zeros(max(int(self.nu[0]), 1))
-        self._chk(lib().tqgpu_mpc_step(self.h, _dp(a), C.byref(o), C.byref(r), _dp(u0)))
+        if t0 is None:
+            self._chk(lib().tqgpu_mpc_step(self.h, _dp(a), C.byref(o), C.byref(r), _dp(u0)))
+        else:
+            self._chk(lib().tqgpu_mpc_step_at(self.h, _dp(a), int(t0), C.byref(o), C.byref(r), _dp(u0)))
         return {f: getattr(r, f) for f, _ in GpuResult._fields_}, u0[:int(self.nu[0])]
 
     def export_ahead(self, on: bool) -> None:

@@ -1981,6 +1981,10 @@ struct tqgpu_solver {
     long mpc_drained_at = 0;            /* as kkt_drained_at, for the batch step's launch ahead of the solves */
     MItem *d_mitems = nullptr, *h_mitems = nullptr; int mitems_cap = 0;      /* batch steps: one descriptor per member of this device (the device's first member owns the array) */
     double *h_mpc_u0s = nullptr; int mpc_u0s_cap = 0;                        /* ... and their u[0] with the tag behind them, pinned */
+    /* tracking (tqgpu_mpc_set_tracking): [xtraj T x NXT | utraj T x NUT | q0 (sum_nx, node-indexed as Data::q, phantom root states included) |
+     * r0 (sum_nu)] in one device block, the nodes' stages behind it as ints; trk_t0: the window the device's q, r were last folded for (-1: none yet) */
+    double *d_trk = nullptr;
+    int trk_T = 0, trk_nxt = 0, trk_nut = 0, trk_t0 = -1;
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -3050,7 +3054,13 @@ __global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__
  *                entries 3, 4 (lower, upper) of the root's packed constants, k_pack_persist's layout cst[(0 * 16 + t) * 5 + ..]; blocks [0, nk0) idle;
  *   nk0 + 1 ..   the warm start: MPC_WARM_SPAN doubles of the current duals each (Ctrl::cur says which buffer: read here, so nothing waits for the host)
  *                into the start buffer, node-indexed as they lie (phantom root states included).
- * The fold writes b, r, dmin, dmax (or xmin, xmax of the root and their packed copies); the copy reads lam0 / lam1 and writes lam_init: the roles touch disjoint data.  No atomics. */
+ *   behind them, one block per node (mirrors with a reference trajectory, tqgpu_mpc_set_tracking, in a launch that moves the window):
+ *                the linear terms of node k for trajectory row min(t0 + stage[k], T - 1), rows of [x | u] over lanes, every entry one chain
+ *                of fused multiply-adds from its base, columns ascending (mpc_track_node); where the packed constants of the persistent
+ *                route are current, entry 0 of the node's slots as well.  r[0] of an x0-eliminated root with S0 belongs to block nk0,
+ *                which then computes base - R_0 uref - S0 xref + S0 x0 as one chain (mpc_track_root_r) instead of r0 + S0 x0.
+ * The fold writes b, r, dmin, dmax (or xmin, xmax of the root and their packed copies); the copy reads lam0 / lam1 and writes lam_init; the
+ * window fold writes q, r (and their packed copies): the roles touch disjoint data.  No atomics. */
 struct MItem {
     Tree T; Data D;
     const double *A0, *b0, *S0, *r0, *C0, *dmin0, *dmax0;      /* the originals in device memory (S0, C0: nullptr = zero, the target is left alone) */
@@ -3062,11 +3072,65 @@ struct MItem {
     double *u0;                        /* pinned: where k_mpc_post puts u[0] */
     int nx0, nc0, nu0, sum_nx;
     int fold, warm;                    /* what k_mpc_pre does for this mirror */
+    /* tracking (xtraj == nullptr: none): the trajectory, the base linear terms and the nodes' stages in device memory; the targets Data::q,
+     * Data::r (r above) and entry 0 of the packed constants where they are current (else nullptr); t0: the window now in force (-1: none yet) */
+    const double *xtraj, *utraj, *q0, *rb0;
+    const int *stage;
+    double *q, *pcq;
+    int trk, t0, Tn, nxt, nut, xpad;   /* trk: this launch folds the window t0 */
 };
 constexpr int MPC_WARM_SPAN = 512;
+/* the trajectory row of node k for the window in force */
+__device__ __forceinline__ int mpc_track_row(const MItem &it, int k) {
+    const int row = it.t0 + it.stage[k];
+    return row < it.Tn - 1 ? row : it.Tn - 1;
+}
+/* does block nk0 own r[0]?  (an x0-eliminated root with S0 on a tracking mirror whose window has been set) */
+__device__ __forceinline__ bool mpc_track_owns_r0(const MItem &it) { return it.xtraj && it.S0 && it.t0 >= 0; }
+/* q, r of node k: kind 0 v = fma(-Qd[i], xref[i], q0[i]) (r: Rd, uref); kinds 1 / 2 / 3, row i of H_k: v = base[i], then
+ * v = fma(-H[i, j], xref[j], v) over the x columns, then v = fma(-H[i, nx + j], uref[j], v) over the u columns.  Phantom root states keep
+ * their q (and are no columns); a leaf has no u part. */
+__device__ __forceinline__ void mpc_track_node(const MItem &it, int k, int lane) {
+    const Tree &T = it.T;
+    if (!it.trk || !it.xtraj || k >= T.Nn) return;
+    const int pad = k == 0 ? it.xpad : 0, nx = T.nx[k], nu = T.nu[k], nxe = nx - pad, nz = nx + nu;
+    const int xo = T.xoff[k], uo = T.uoff[k], row = mpc_track_row(it, k);
+    const double *xr = it.xtraj + (size_t)row * it.nxt, *ur = it.utraj + (size_t)row * it.nut;
+    const int kind = it.D.dense ? it.D.kind[k] : 0;
+    const bool r_elsewhere = k == 0 && mpc_track_owns_r0(it);
+    for (int i = pad + lane; i < nz; i += WAVE) {
+        const bool isx = i < nx;
+        if (!isx && r_elsewhere) continue;
+        double v = isx ? it.q0[xo + i] : it.rb0[uo + i - nx];
+        if (kind == 0) v = isx ? fma(-it.D.Qd[xo + i], xr[i - pad], v) : fma(-it.D.Rd[uo + i - nx], ur[i - nx], v);
+        else {
+            const double *H = it.D.Hd + it.D.poff[k];
+            for (int j = 0; j < nxe; j++) v = fma(-H[i + (size_t)(pad + j) * nz], xr[j], v);
+            for (int j = 0; j < nu; j++) v = fma(-H[i + (size_t)(nx + j) * nz], ur[j], v);
+        }
+        if (isx) it.q[xo + i] = v; else it.r[uo + i - nx] = v;
+        if (it.pcq && i < 16) it.pcq[((size_t)k * 16 + i) * 5] = v;          /* k_pack_persist's layout: slot t = i of node k, entry 0 */
+    }
+}
+/* r[0] of an x0-eliminated root with S0, one chain: base, - R_0 uref, - S0 xref, + S0 x0 */
+__device__ __forceinline__ void mpc_track_root_r(const MItem &it, int lane) {
+    const Tree &T = it.T;
+    const int nx = T.nx[0], nu0 = it.nu0, nz = nx + nu0, nx0 = it.nx0, row = mpc_track_row(it, 0);          /* nx: phantom states only */
+    const double *xr = it.xtraj + (size_t)row * it.nxt, *ur = it.utraj + (size_t)row * it.nut;
+    const double *H = it.D.Hd + it.D.poff[0];          /* (S0 is refused on a root of kind 0) */
+    for (int i = lane; i < nu0; i += WAVE) {
+        double v = it.rb0[i];
+        for (int j = 0; j < nu0; j++) v = fma(-H[nx + i + (size_t)(nx + j) * nz], ur[j], v);
+        for (int j = 0; j < nx0; j++) v = fma(-it.S0[i + (size_t)j * nu0], xr[j], v);
+        for (int j = 0; j < nx0; j++) v = fma(it.S0[i + (size_t)j * nu0], it.x0[j], v);
+        it.r[i] = v;
+    }
+}
 __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane) {
     const Tree &T = it.T;
     const int nk0 = T.nk[0], nx0 = it.nx0;
+    const int track0 = nk0 + 1 + (it.sum_nx + MPC_WARM_SPAN - 1) / MPC_WARM_SPAN;
+    if (blk >= track0) { mpc_track_node(it, blk - track0, lane); return; }
     if (blk < nk0) {
         if (!it.fold || it.xlo) return;
         const int first = T.kid0[0], kid = first + blk, nxk = T.nx[kid];
@@ -3082,6 +3146,8 @@ __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane
         return;
     }
     if (blk == nk0) {
+        const bool owns_r0 = mpc_track_owns_r0(it);
+        if (owns_r0 && (it.fold || it.trk)) mpc_track_root_r(it, lane);
         if (!it.fold) return;
         if (it.xlo) {
             for (int i = lane; i < nx0; i += WAVE) {
@@ -3092,7 +3158,7 @@ __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane
             return;
         }
         const int nu0 = it.nu0, nc0 = it.nc0;
-        if (it.S0) for (int i = lane; i < nu0; i += WAVE) {
+        if (it.S0 && !owns_r0) for (int i = lane; i < nu0; i += WAVE) {
             double v = it.r0[i];
             for (int j = 0; j < nx0; j++) v = fma(it.S0[i + (size_t)j * nu0], it.x0[j], v);
             it.r[i] = v;
@@ -3670,6 +3736,29 @@ extern "C" int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const
     s->need_init = true;
     s->need_pack = true;
     if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; }
+    return TQGPU_OK;
+}
+
+/* The linear terms alone, in the layout of tqgpu_set_objective_diag (either may be NULL: left alone): q and r are uploaded and the persistent
+ * route packs them again; the kinds, H, the factors of k_init / k_dense_init and the stored working sets of kinds 2 and 3 stay. */
+extern "C" int tqgpu_set_linear_terms(tqgpu_solver *s, const double *q, const double *r) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "tqgpu_set_linear_terms: null solver");
+    HIP_TRY(hipSetDevice(s->device));
+    s->in_valid = false;
+    H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->need_pack = true;
+    return TQGPU_OK;
+}
+extern "C" int tqgpu_get_linear_terms(tqgpu_solver *s, double *q, double *r) {
+    SETTLE(s);
+    if (!s) return fail(TQGPU_EINVAL, "tqgpu_get_linear_terms: null solver");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const int nxe = s->sum_nx - s->x_pad;
+    if (q && nxe > 0) HIP_TRY(hipMemcpy(q, s->q + s->x_pad, sizeof(double) * (size_t)nxe, hipMemcpyDeviceToHost));
+    if (r && s->sum_nu > 0) HIP_TRY(hipMemcpy(r, s->r, sizeof(double) * (size_t)s->sum_nu, hipMemcpyDeviceToHost));
     return TQGPU_OK;
 }
 
@@ -4315,7 +4404,7 @@ int begin_persist(tqgpu_solver *s, SolveCtx &cx) { return launch_persist(s, cx.O
  * solve enqueues there.  The last solve may have been part of a batch launch on another stream (settle); a launch the caller makes on
  * another stream waits for this one (stream_pending, join_lead_stream).  A batch step does all its members' copies in one launch
  * instead and leaves warm_fresh set. */
-MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm);
+MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track = false);
 int enqueue_warm_start(tqgpu_solver *s, SolveCtx &cx) {
     int rc = settle(s);
     if (rc != TQGPU_OK) return rc;
@@ -5025,7 +5114,7 @@ int mpc_refuse(const tqgpu_solver *s, const char *who) {
 }
 
 /* the descriptor of a mirror for k_mpc_pre / k_mpc_post: views into d_mpc and h_mpc (null before tqgpu_mpc_set_root / _set_root_states: fold must be false then) */
-MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm) {
+MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track) {
     MItem it{};
     it.T = s->T; it.D = s->D;
     const size_t nx0 = (size_t)s->mpc_nx0, nb = (size_t)s->mpc_nb, nu0 = (size_t)s->nu[0], nc0 = (size_t)s->mpc_nc0;
@@ -5046,9 +5135,37 @@ MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm) {
     it.lam_init = s->d_lam_init;
     it.nx0 = s->mpc_nx0; it.nc0 = s->mpc_nc0; it.nu0 = s->nu[0]; it.sum_nx = s->sum_nx;
     it.fold = fold ? 1 : 0; it.warm = warm ? 1 : 0;
+    if (s->d_trk) {
+        const double *p = s->d_trk;
+        it.xtraj = p; p += (size_t)s->trk_T * s->trk_nxt; it.utraj = p; p += (size_t)s->trk_T * s->trk_nut;
+        it.q0 = p; p += s->sum_nx; it.rb0 = p; p += s->sum_nu;
+        it.stage = reinterpret_cast<const int *>(p);
+        it.q = s->q;
+        /* the packed constants hold a copy of q, r (k_pack_persist); every other route reads Data::q / r in place at every launch */
+        it.pcq = s->persist_ok && s->pcst && !s->need_pack ? s->pcst : nullptr;
+        it.trk = track ? 1 : 0; it.t0 = s->trk_t0; it.Tn = s->trk_T; it.nxt = s->trk_nxt; it.nut = s->trk_nut; it.xpad = s->x_pad;
+    }
     return it;
 }
 unsigned mpc_pre_blocks(const tqgpu_solver *s) { return (unsigned)(s->nk[0] + 1 + (s->sum_nx + MPC_WARM_SPAN - 1) / MPC_WARM_SPAN); }
+/* the blocks of a launch of k_mpc_pre: up to the fold, the warm-start copy, or the nodes of the window fold */
+unsigned mpc_launch_blocks(const tqgpu_solver *s, bool warm, bool track) {
+    return track ? mpc_pre_blocks(s) + (unsigned)s->Nn : warm ? mpc_pre_blocks(s) : (unsigned)(s->nk[0] + 1);
+}
+
+/* a new window for a mirror with a reference trajectory, and what its fold makes stale on the host side; nothing is enqueued.  t0 < 0: the
+ * window in force stays (no refusal: a mirror without tracking takes such a step as before) */
+int mpc_take_window(tqgpu_solver *s, int t0, bool commit, const char *who) {
+    if (t0 < 0) return TQGPU_OK;
+    if (!s->d_trk) return fail(TQGPU_EINVAL, std::string(who) + ": the reference trajectory has not been given yet (tqgpu_mpc_set_tracking)");
+    if (s->mpc_S0 && s->mpc_nx0 != s->trk_nxt)
+        return fail(TQGPU_EINVAL, std::string(who) + ": S0 of tqgpu_mpc_set_root has " + std::to_string(s->mpc_nx0) + " columns, the trajectory " + std::to_string(s->trk_nxt) + " states");
+    if (s->mpc_S0 && root_kind_of(s) == 0) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 0 after tqgpu_mpc_set_root gave it an S0");
+    if (!commit) return TQGPU_OK;
+    s->trk_t0 = t0;
+    s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes q, r */
+    return TQGPU_OK;                        /* need_pack stays as it is: the fold writes the packed copy itself, a pending pack reads Data */
+}
 
 /* a new x0 into the mirror's pinned buffer, and what the fold makes stale on the host side; nothing is enqueued */
 int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
@@ -5067,6 +5184,9 @@ int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
     }
     if (s->mpc_C0 && (s->gnc.empty() || s->gnc[0] != s->mpc_nc0 || !s->d_drange))
         return fail(TQGPU_EINVAL, std::string(who) + ": the rows of the root were redefined after tqgpu_mpc_set_root (call it again)");
+    /* a tracking mirror whose window is set: r[0] of a root with S0 is the chain of mpc_track_root_r, which reads nx0 entries of a trajectory row */
+    if (s->d_trk && s->trk_t0 >= 0 && s->mpc_S0 && s->mpc_nx0 != s->trk_nxt)
+        return fail(TQGPU_EINVAL, std::string(who) + ": S0 of tqgpu_mpc_set_root has " + std::to_string(s->mpc_nx0) + " columns, the trajectory of tqgpu_mpc_set_tracking " + std::to_string(s->trk_nxt) + " states");
     if (!x0) return TQGPU_OK;
     memcpy(s->h_mpc, x0, sizeof(double) * (size_t)s->mpc_nx0);
     s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes b (and r) */
@@ -5210,6 +5330,62 @@ extern "C" int tqgpu_mpc_set_x0(tqgpu_solver *s, const double *x0) {
     return TQGPU_OK;
 }
 
+extern "C" int tqgpu_mpc_set_tracking(tqgpu_solver *s, int NXT, int NUT, int T, const double *xtraj, const double *utraj, const double *q0, const double *r0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_tracking"))) return rc;
+    SETTLE(s);
+    if (T < 1) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_tracking: T must be at least 1");
+    if (NXT < 0 || NUT < 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_tracking: NXT and NUT must not be negative");
+    if ((NXT > 0 && !xtraj) || (NUT > 0 && !utraj)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_tracking: xtraj and utraj are required where NXT, NUT are positive");
+    for (int k = 0; k < s->Nn; k++) {
+        const int nxe = s->nx[k] - (k == 0 ? s->x_pad : 0);
+        if ((nxe != 0 && nxe != NXT) || (s->nu[k] != 0 && s->nu[k] != NUT))
+            return fail(TQGPU_EINVAL, "tqgpu_mpc_set_tracking: node " + std::to_string(k) + " has nx = " + std::to_string(nxe) + ", nu = " + std::to_string(s->nu[k]) +
+                        ": every node must have nx in {0, " + std::to_string(NXT) + "} and nu in {0, " + std::to_string(NUT) + "} (one reference per stage)");
+    }
+    const size_t nxt = (size_t)NXT, nut = (size_t)NUT, nT = (size_t)T, sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
+    const size_t doubles = nT * nxt + nT * nut + sx + su, ints = (size_t)s->Nn;
+    std::vector<double> blk(doubles + (ints + 1) / 2 + 1, 0.0);
+    double *p = blk.data();
+    if (nxt) memcpy(p, xtraj, sizeof(double) * nT * nxt);
+    p += nT * nxt;
+    if (nut) memcpy(p, utraj, sizeof(double) * nT * nut);
+    p += nT * nut;
+    if (q0 && sx > (size_t)s->x_pad) memcpy(p + s->x_pad, q0, sizeof(double) * (sx - (size_t)s->x_pad));          /* (the phantom root states keep their q: their base is never read) */
+    p += sx;
+    if (r0 && su) memcpy(p, r0, sizeof(double) * su);
+    p += su;
+    memcpy(p, s->stage.data(), sizeof(int) * ints);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the block that is replaced */
+    s->mem.release(s->d_trk);
+    s->trk_T = 0; s->trk_t0 = -1;
+    if ((rc = s->mem.upload(s->d_trk, blk.data(), sizeof(double) * blk.size(), TQGPU_ENOMEM, "the reference trajectory"))) return rc;
+    s->trk_T = T; s->trk_nxt = NXT; s->trk_nut = NUT;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_set_window(tqgpu_solver *s, int t0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_window"))) return rc;
+    if (t0 < 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_window: t0 must not be negative");
+    if ((rc = mpc_take_window(s, t0, false, "tqgpu_mpc_set_window"))) return rc;          /* (the refusals, before anything is touched) */
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = mpc_take_window(s, t0, true, "tqgpu_mpc_set_window"))) return rc;
+    hipLaunchKernelGGL(k_mpc_pre, dim3(mpc_launch_blocks(s, false, true)), dim3(WAVE), 0, s->stream, mpc_item(s, false, false, true));
+    HIP_TRY(hipGetLastError());
+    s->stream_pending = true;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_window(const tqgpu_solver *s, int *t0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_window"))) return rc;
+    if (t0) *t0 = s->trk_t0;
+    return TQGPU_OK;
+}
+
 extern "C" int tqgpu_set_warm_start(tqgpu_solver *s, int mode) {
     int rc;
     if ((rc = mpc_refuse(s, "tqgpu_set_warm_start"))) return rc;
@@ -5240,18 +5416,19 @@ extern "C" int tqgpu_get_root_terms(tqgpu_solver *s, double *b_kids, double *r0,
     return TQGPU_OK;
 }
 
-extern "C" int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opts *o, tqgpu_result *res, double *u0) {
+/* tqgpu_mpc_step (t0 = -1) and tqgpu_mpc_step_at: the window fold, where there is one, rides in the step's one launch ahead of the solve */
+static int mpc_step_impl(tqgpu_solver *s, const double *x0, int t0, const tqgpu_opts *o, tqgpu_result *res, double *u0, const char *who) {
     int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_step"))) return rc;
-    if (!o || !res || !u0) return fail(TQGPU_EINVAL, "tqgpu_mpc_step: bad arguments");
-    if ((rc = mpc_take_x0(s, nullptr, "tqgpu_mpc_step"))) return rc;          /* (the refusals, before anything is touched) */
+    if ((rc = mpc_refuse(s, who))) return rc;
+    if (!o || !res || !u0) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments");
+    if ((rc = mpc_take_x0(s, nullptr, who)) || (rc = mpc_take_window(s, t0, false, who))) return rc;          /* (the refusals, before anything is touched) */
     SETTLE(s);
     HIP_TRY(hipSetDevice(s->device));
     MpcLive live;
-    if ((rc = mpc_take_x0(s, x0, "tqgpu_mpc_step"))) return rc;
-    const bool fold = x0 != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0;
-    if (fold || warm) {
-        hipLaunchKernelGGL(k_mpc_pre, dim3(warm ? mpc_pre_blocks(s) : (unsigned)(s->nk[0] + 1)), dim3(WAVE), 0, s->stream, mpc_item(s, fold, warm));
+    if ((rc = mpc_take_x0(s, x0, who)) || (rc = mpc_take_window(s, t0, true, who))) return rc;
+    const bool fold = x0 != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0, track = t0 >= 0;
+    if (fold || warm || track) {
+        hipLaunchKernelGGL(k_mpc_pre, dim3(mpc_launch_blocks(s, warm, track)), dim3(WAVE), 0, s->stream, mpc_item(s, fold, warm, track));
         HIP_TRY(hipGetLastError());
         MPC_COUNT(launches, 1);
         if (warm) s->lam_valid = false;
@@ -5296,6 +5473,12 @@ extern "C" int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opt
         s->export_valid = true; s->export_dev_only = true;          /* d_out holds the returned point: tqgpu_kkt_residual reads it there, tqgpu_get_solution downloads it */
     }
     return TQGPU_OK;
+}
+extern "C" int tqgpu_mpc_step(tqgpu_solver *s, const double *x0, const tqgpu_opts *o, tqgpu_result *res, double *u0) {
+    return mpc_step_impl(s, x0, -1, o, res, u0, "tqgpu_mpc_step");
+}
+extern "C" int tqgpu_mpc_step_at(tqgpu_solver *s, const double *x0, int t0, const tqgpu_opts *o, tqgpu_result *res, double *u0) {
+    return mpc_step_impl(s, x0, t0, o, res, u0, "tqgpu_mpc_step_at");
 }
 
 /* ---- the batch step: per device one launch ahead of the waves of tqgpu_solve_batch, one behind them ---- */
@@ -5370,12 +5553,13 @@ static void mpc_after_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, i
     }
 }
 
-extern "C" int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double *x0s, const tqgpu_opts *o, tqgpu_result *results, double *u0s) {
-    if (!solvers || n < 1 || !o || !results || !u0s) return fail(TQGPU_EINVAL, "tqgpu_mpc_step_batch: bad arguments");
+/* tqgpu_mpc_step_batch (t0s = nullptr) and tqgpu_mpc_step_batch_at: t0s[i] >= 0 moves member i's window in the launch ahead */
+static int mpc_step_batch_impl(tqgpu_solver **solvers, int n, const double *x0s, const int *t0s, const tqgpu_opts *o, tqgpu_result *results, double *u0s, const char *who) {
+    if (!solvers || n < 1 || !o || !results || !u0s) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments");
     int rc;
     for (int i = 0; i < n; i++) {
-        if ((rc = mpc_refuse(solvers[i], "tqgpu_mpc_step_batch")) || (rc = mpc_take_x0(solvers[i], nullptr, "tqgpu_mpc_step_batch"))) return rc;
-        for (int k = 0; k < i; k++) if (solvers[k] == solvers[i]) return fail(TQGPU_EINVAL, "tqgpu_mpc_step_batch: a mirror is named twice");
+        if ((rc = mpc_refuse(solvers[i], who)) || (rc = mpc_take_x0(solvers[i], nullptr, who)) || (rc = mpc_take_window(solvers[i], t0s ? t0s[i] : -1, false, who))) return rc;
+        for (int k = 0; k < i; k++) if (solvers[k] == solvers[i]) return fail(TQGPU_EINVAL, std::string(who) + ": a mirror is named twice");
     }
     MpcLive live;
     MpcBatch mb;
@@ -5422,13 +5606,14 @@ extern "C" int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double 
                 waited.push_back(s->stream);
                 MPC_COUNT(waits, 1);
             }
-            if ((rc = mpc_take_x0(s, x0s ? x0s + x_off[(size_t)d.idx[m]] : nullptr, "tqgpu_mpc_step_batch"))) return rc;
-            const bool fold = x0s != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0;
+            const int t0 = t0s ? t0s[d.idx[m]] : -1;
+            if ((rc = mpc_take_x0(s, x0s ? x0s + x_off[(size_t)d.idx[m]] : nullptr, who)) || (rc = mpc_take_window(s, t0, true, who))) return rc;
+            const bool fold = x0s != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0, track = t0 >= 0;
             MItem &it = lead->h_mitems[m];
-            it = mpc_item(s, fold, warm);
+            it = mpc_item(s, fold, warm, track);
             it.u0 = lead->h_mpc_u0s + u_at;          /* the batch's block, not the member's own */
             u_at += (size_t)s->nu[0];
-            if (fold || warm) { any = true; blocks = std::max(blocks, warm ? mpc_pre_blocks(s) : (unsigned)(s->nk[0] + 1)); }
+            if (fold || warm || track) { any = true; blocks = std::max(blocks, mpc_launch_blocks(s, warm, track)); }
             if (warm) s->lam_valid = false;
             s->warm_fresh = true;          /* the start buffer is ready (or stays the caller's): solve_begin copies nothing */
         }
@@ -5467,6 +5652,13 @@ extern "C" int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double 
         }
     }
     return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_step_batch(tqgpu_solver **solvers, int n, const double *x0s, const tqgpu_opts *o, tqgpu_result *results, double *u0s) {
+    return mpc_step_batch_impl(solvers, n, x0s, nullptr, o, results, u0s, "tqgpu_mpc_step_batch");
+}
+extern "C" int tqgpu_mpc_step_batch_at(tqgpu_solver **solvers, int n, const double *x0s, const int *t0s, const tqgpu_opts *o, tqgpu_result *results, double *u0s) {
+    return mpc_step_batch_impl(solvers, n, x0s, t0s, o, results, u0s, "tqgpu_mpc_step_batch_at");
 }
 
 extern "C" int tqgpu_mpc_stats(int *launches, int *copies, int *waits) {
