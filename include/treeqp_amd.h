@@ -397,6 +397,7 @@ int tqgpu_solve_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, tqg
  *                        and after a tqgpu_set_lambda (or a tqgpu_set_problem that passes lambda), the start is what that call filled,
  *                        for one solve.  The mode applies to tqgpu_solve, tqgpu_solve_n, the members of tqgpu_solve_batch(_n) and the
  *                        step calls.  The redo after a timed-out persistent launch starts where the timed-out attempt started.
+ *                        Mode 2: as mode 1, through the shift map of the realised child (tqgpu_mpc_set_shift, below).
  *   tqgpu_get_root_terms what the device holds now (any pointer may be NULL): b of the root's children (sum of their nx), r[0] (nu[0]),
  *                        dmin[0], dmax[0] (nc[0] each; untouched where the root has no rows).  Waits for the mirror's stream.
  *   tqgpu_mpc_step       tqgpu_mpc_set_x0 (x0 == NULL: keep the current one), the warm start of the current mode and tqgpu_solve, then
@@ -502,6 +503,70 @@ int tqgpu_mpc_set_window(tqgpu_solver *s, int t0);
 int tqgpu_mpc_get_window(const tqgpu_solver *s, int *t0);
 int tqgpu_mpc_step_at(tqgpu_solver *s, const double *x0, int t0, const tqgpu_opts *opts, tqgpu_result *res, double *u0);
 int tqgpu_mpc_step_batch_at(tqgpu_solver **solvers, int n, const double *x0s, const int *t0s, const tqgpu_opts *opts, tqgpu_result *results, double *u0s);
+
+/* ---- The shifted warm start: duals and working sets move a stage with the horizon ------------------------------------------------
+ * After an MPC step one child j of the root has been realised and becomes the new root: what was stage t + 1 is stage t now (with
+ * tracking, tqgpu_mpc_step_at(.., t + 1, ..) moves every node's reference one row).  Warm start mode 1 copies lam_k into lam_k and so
+ * starts every node one stage late; mode 2 starts node k from the duals of its image img(k) in the old problem, on the device.
+ * Nodes are numbered level by level: the children of k are kid0[k] .. kid0[k] + nk[k] - 1.
+ *   the map              img(0) = kid0[0] + j.  For k >= 1 with parent p and sibling index c = k - kid0[p]:
+ *                          img(p) has children:  img(k) = kid0[img(p)] + min(c, nk[img(p)] - 1)   (the clamp: a multistage tree, whose
+ *                                                image has stopped branching);
+ *                          img(p) is a leaf:     img(k) = img(p) under TQGPU_SHIFT_LEAF_REPEAT (a repeated leaf), -1 under TQGPU_SHIFT_LEAF_ZERO;
+ *                          img(p) == -1 by the leaf policy:  img(k) = -1.
+ *                        Last, where nx[img(k)] != nx[k] the image does not fit and img(k) = -1; this does not propagate: the nodes
+ *                        below keep the image their path gives them.  Off the repeated leaves img(k) is one level deeper than k, so
+ *                        img(k) > k, and dad(img(k)) == img(dad(k)): the copied dual belongs to an edge between corresponding nodes.
+ *                        The start dual of node k >= 1 is the last dual of img(k), copied bit for bit, or 0.0 where img(k) = -1.  The
+ *                        entries of node 0 (phantom root states, or the root's own) are copied unshifted, as mode 1 does.
+ *   tqgpu_shift_map      the map, img[Nn], for nk, nx as tqgpu_create takes them: host arithmetic only, no device (as tqgpu_shard_plan).
+ *                        TQGPU_EINVAL: realised outside [0, nk[0]), Nn < 1, an nk that is negative somewhere or does not name Nn nodes
+ *                        level by level, an unknown leaf policy, img == NULL.  A tree of one node gives an empty map (img is not written).
+ *   tqgpu_mpc_set_shift  what = TQGPU_SHIFT_DUALS, optionally | TQGPU_SHIFT_WORKING_SETS: builds the maps of all nk[0] realisations once
+ *                        and keeps them in device memory: per realisation an entry-level source table (for every entry of the start
+ *                        buffer the entry of the last duals it is copied from, -1: 0.0; sum_nx ints), which fits the span-per-block copy
+ *                        of the warm start, and a node table (Nn ints).  Waits for the mirror's stream.  what == 0 forgets the maps and
+ *                        returns mode 2 to mode 1.  A call replaces an earlier one and resets the realisation to 0.
+ *                        TQGPU_EINVAL: an unknown leaf policy, unknown bits, TQGPU_SHIFT_WORKING_SETS without TQGPU_SHIFT_DUALS.
+ *   tqgpu_mpc_set_realised   the child of the root that the last step realised: host state only, default 0, TQGPU_EINVAL outside [0, nk[0]).
+ *   tqgpu_mpc_get_shift  leaf policy, what and the realisation in force (any pointer may be NULL; host state only).
+ *   tqgpu_set_warm_start(s, 2)   every warm start goes through the map of the realisation in force, wherever mode 1 would copy: tqgpu_solve,
+ *                        tqgpu_solve_n, the members of tqgpu_solve_batch(_n) and every tqgpu_mpc_step*; the warm blocks of the step's ONE
+ *                        launch gather instead of copying (an index load per entry), so the counts of tqgpu_mpc_stats stay (3, 0, 1 on
+ *                        a single-launch route, 3, 1, 1 for a batch of persistent members).  TQGPU_EINVAL before tqgpu_mpc_set_shift.
+ *                        The rules of mode 1 stay: the mirror's first solve and the solve after a tqgpu_set_lambda start from what
+ *                        that call filled; the redo of a timed-out launch starts where the attempt started.  A member of a batch gets
+ *                        bit for bit what it gets alone; members in modes 0, 1 and 2 and with different realisations may be mixed.
+ *   tqgpu_mpc_shift      the shift alone, as tqgpu_mpc_set_x0 is the fold alone: one kernel on the mirror's stream, no synchronisation.
+ *                        The next solve starts from the shifted duals, for one solve, in any mode; a mirror in mode 0 starts from the
+ *                        buffer of tqgpu_set_lambda again afterwards (the kernel saves it, the solve after the next puts it back with
+ *                        one device-to-device copy).  It also moves the working sets if they were asked for.  TQGPU_EINVAL before
+ *                        tqgpu_mpc_set_shift and before the mirror's first solve.
+ *   the working sets     (TQGPU_SHIFT_WORKING_SETS, trees with nodes of kind 2 or 3) in the same launch as the duals, wherever those
+ *                        are gathered: node k takes the bound set and its sides from img(k) where both nodes are of kind 2 or 3, nx
+ *                        and nu agree, img(k) != -1 and img(k) is not a repeated leaf; under the same conditions it takes the row set
+ *                        and its sides where both are of kind 3 and nc agrees.  Every other node keeps its own sets.  The kinds, nu and
+ *                        nc are read on the device at every launch: after tqgpu_set_objective_mixed or a tqgpu_set_constraints that
+ *                        changes nc the maps need no rebuild, the rule is applied to what the device holds then.  The stage solvers
+ *                        re-validate a set they are given, so a shifted set needs no reset after tqgpu_set_constraints.  The gather is
+ *                        in place: img(k) > k for every node that takes a set, and one wave walks the nodes in ascending chunks of 64
+ *                        with all loads of a chunk ahead of its stores.  The halves that say what P_k was last built for are not touched.
+ *   tqgpu_get_working_sets / tqgpu_set_working_sets   Nn words each, any pointer may be NULL: the hot-start halves of the stored sets,
+ *                        bounds (bit i: entry i of [x | u] of node k sits on a bound), rows, and their sides (bit set: upper side).
+ *                        Nodes of kinds 0 and 1 read as 0 and ignore what is set; rows and row_sides are those of the kind-3 nodes.
+ *                        The getter waits for the stream; the setter uploads and keeps everything else.
+ * All of the calls above that take a solver refuse a rank of a sharded solve with TQGPU_EUNSUPPORTED, and a null solver with TQGPU_EINVAL. */
+#define TQGPU_SHIFT_LEAF_REPEAT 0
+#define TQGPU_SHIFT_LEAF_ZERO   1
+#define TQGPU_SHIFT_DUALS        1u
+#define TQGPU_SHIFT_WORKING_SETS 2u
+int tqgpu_shift_map(int Nn, const int *nk, const int *nx, int realised, int leaf, int *img);
+int tqgpu_mpc_set_shift(tqgpu_solver *s, int leaf, unsigned what);
+int tqgpu_mpc_set_realised(tqgpu_solver *s, int child);
+int tqgpu_mpc_get_shift(const tqgpu_solver *s, int *leaf, unsigned *what, int *realised);
+int tqgpu_mpc_shift(tqgpu_solver *s);
+int tqgpu_get_working_sets(tqgpu_solver *s, unsigned long long *bounds, unsigned long long *rows, unsigned long long *bound_sides, unsigned long long *row_sides);
+int tqgpu_set_working_sets(tqgpu_solver *s, const unsigned long long *bounds, const unsigned long long *rows, const unsigned long long *bound_sides, const unsigned long long *row_sides);
 
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written

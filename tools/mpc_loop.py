@@ -4,6 +4,7 @@ the last duals, tqgpu_solve, tqgpu_get_solution).
 
     python tools/mpc_loop.py [--steps 200] [--skip 10] [--batch 64] [--root-states [--certify]] [c1] [c2] [batch]
     python tools/mpc_loop.py --tracking [--steps 200] [--skip 10] [--batch 64] [c1] [c2] [kind3] [batch]
+    python tools/mpc_loop.py --shift --tracking --root-states [--steps 200] [--skip 10] [c1] [c2] [kind3]
 
 Workloads, all x0-eliminated (nx[0] == 0): c1 = problems.spring_mass(), 85 nodes; c2 = problems.linear_chain(2, 9, 9), 1 023 nodes;
 batch = 64 mirrors of c1 from different x0 (tqgpu_mpc_step_batch against fold + tqgpu_set_problem per member, tqgpu_solve_batch,
@@ -33,7 +34,11 @@ commit's API: numpy fold of the window into q, r, tqgpu_set_problem with the roo
 (five copies: q, r and the two bound arrays up, the solution down).  kind3 is an 85-node dense tree with 21 kind-3 nodes (kind3_tree:
 the shape of tests/gen_cases.scaled_one_row with data that converge): there the host loop has to go through tqgpu_set_objective_mixed,
 which empties the stored working sets; the device loop is tqgpu_mpc_step_at, tqgpu_get_solution; active-set steps per kind-3 node and
-stage sweep are printed for both."""
+stage sweep are printed for both.
+
+--shift (on top of --tracking and --root-states): the same closed-loop sequences three ways, warm start mode 2 (tqgpu_mpc_set_shift: the
+duals, and on kind3 also the working sets, move a stage on the device), mode 1, and the host loop that the API without the shift allows
+(tqgpu_get_solution, numpy gather, tqgpu_set_lambda, tqgpu_mpc_step_at); see shift_compare."""
 import ctypes as C
 import sys
 import time
@@ -570,6 +575,89 @@ def tracking_kind3(capi, steps, skip):
               f"active-set steps per kind-3 node and sweep (ls_total + 1 sweeps) {np.mean(act[skip:]):.2f}{extra}", flush=True)
 
 
+def shift_compare(capi, name, d, x0, steps, skip, kinds=None, opts=None, X=None, U=None, move_x0=True):
+    """--shift: the same closed-loop sequences (root with states, tracking) three ways: warm start mode 2 (the shift on the device), mode 1
+    (the unshifted copy), and the host loop that the API without the shift allows: tqgpu_get_solution, numpy gather, tqgpu_set_lambda,
+    tqgpu_mpc_step_at.  The realised child cycles through the root's children.  Two sequences: `moving` (the reference shifts one stage
+    per step, x0 on its prescribed path) and `standing` (a setpoint and a fixed x0: the same QP at every step, where the unshifted duals
+    are the solution already and a shift can only displace them)."""
+    L = capi.lib()
+    import shift_cases as SH
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    opts = opts or {}
+    o, r = capi._gpu_opts(**opts), capi.GpuResult()
+    nk, nx = np.asarray(d["nk"]), np.asarray(d["nx"])
+    nk0, nu0 = int(nk[0]), int(d["nu"][0])
+    n3 = 0 if kinds is None else int((kinds == 3).sum())
+    st = node_stages(nk)
+    if X is None:
+        X, U = reference(x0, int(d["nu"][0]), steps + int(st.max()) + 1)
+    # the host gather as one fancy index: entry i of the start duals (nodes 1 ..) from entry src[j][i] of the last, or 0.0
+    off = np.concatenate([[0], np.cumsum(nx[1:])])
+    src = []
+    for j in range(nk0):
+        img = SH.ref_map(nk, nx, j, SH.REPEAT)[0]
+        s = np.full(int(nx[1:].sum()), -1, dtype=np.int64)
+        for k in range(1, len(nk)):
+            if img[k] >= 1:
+                s[off[k - 1]:off[k - 1] + nx[k]] = off[img[k] - 1] + np.arange(nx[k])
+        src.append(s)
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"])
+        if kinds is None:
+            g.upload(d)
+        else:
+            g.set_constraints(d["nc"], d["C"], d["D"], d["dmin"], d["dmax"])
+            g.upload_mixed(d, kinds, None)
+        g.mpc_set_root_states()
+        return g
+
+    ways = [("mode 2", 2, capi.SHIFT_DUALS)] + ([("mode 2 + sets", 2, capi.SHIFT_DUALS | capi.SHIFT_WORKING_SETS)] if n3 else []) + [("mode 1", 1, 0), ("host shift", 0, 0)]
+    for seq in ("moving", "standing"):
+        xs = [moved_inward(x0, k, 0) if seq == "moving" and move_x0 else x0 for k in range(steps)]
+        print(f"{name}, --shift, sequence `{seq}`: {len(nk)} nodes, {steps} steps, realised child k mod {nk0}", flush=True)
+        base = None
+        for how, mode, what in ways:
+            g = mirror()
+            g.mpc_set_tracking(X if seq == "moving" else X[:1], U if seq == "moving" else U[:1], d["q"], d["r"])
+            if what:
+                g.mpc_set_shift(SH.REPEAT, what)
+            g.set_warm_start(mode)
+            sol = [np.zeros(n) for n in (g.sum_nx, g.sum_nu, g.sum_lam, g.sum_nx, g.sum_nu, g.sum_lam)]
+            sp = [dp(b) for b in sol]
+            start = np.zeros(g.sum_lam)
+            u0 = np.zeros(max(nu0, 1))
+            w, cnt, act = [], [], []
+            for k in range(steps):
+                j = k % nk0
+                t0 = time.perf_counter()
+                if k > 0 and how == "host shift":
+                    assert L.tqgpu_get_solution(g.h, *sp) == 0
+                    np.take(sol[2], src[j], out=start, mode="clip")
+                    start[src[j] < 0] = 0.0
+                    assert L.tqgpu_set_lambda(g.h, dp(start)) == 0
+                elif mode == 2:
+                    assert L.tqgpu_mpc_set_realised(g.h, j) == 0
+                assert L.tqgpu_mpc_step_at(g.h, dp(np.ascontiguousarray(xs[k])), k, C.byref(o), C.byref(r), dp(u0)) == 0, L.tqgpu_last_error()
+                w.append(time.perf_counter() - t0)
+                cnt.append((r.status, r.iter, r.ls_total))
+                if n3:
+                    act.append(float(g.stage_steps()["total"].sum()) / (n3 * (r.ls_total + 1)))
+            g.close()
+            med, lo, p90 = stats(w[skip:])
+            if how == "host shift":
+                same = sum(a == b for a, b in zip(cnt, base))
+                tail = f" | steps with the counts of mode 2: {same} of {steps}; mode 2 / host shift wall {base_med / med:.2f}"
+            else:
+                tail = ""
+            if how == "mode 2":
+                base, base_med = cnt, med
+            extra = f" | active-set steps per kind-3 node and sweep {np.mean(act[skip:]):.2f}" if n3 else ""
+            print(f"    {how:14s} wall median {med:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f} | iterations per step mean {np.mean([c[1] for c in cnt[skip:]]):.2f}  "
+                  f"trials per step mean {np.mean([c[2] for c in cnt[skip:]]):.2f} | status 0 in {sum(c[0] == 0 for c in cnt)} of {steps}{extra}{tail}", flush=True)
+
+
 def main():
     from treeqp_amd import capi, problems as P
     args = sys.argv[1:]
@@ -578,6 +666,21 @@ def main():
     names = [a for a in args if a in ("c1", "c2", "batch", "kind3")] or ["c1", "c2", "batch"]
     if capi.device_count() < 1:
         raise SystemExit("no HIP device")
+    if "--shift" in args:
+        import solve_sequence_cases as SC
+        for nm, p in (("c1", P.spring_mass()), ("c2", P.linear_chain(2, 9, 9))):
+            if nm in names:
+                d, x0 = full_root(capi, p)
+                shift_compare(capi, nm, d, x0, steps, skip)
+        if "kind3" in names:
+            d, kinds = kind3_tree()
+            st = node_stages(d["nk"])
+            t = np.arange(steps + int(st.max()) + 1)[:, None]
+            X = 0.05 * np.sin(0.2 * t + np.arange(2)[None, :])
+            U = 0.05 * np.sin(0.2 * t + 1.0 + np.arange(1)[None, :])
+            x0 = np.array(d["xmin"][:2], copy=True)
+            shift_compare(capi, "kind3", d, x0, steps, skip, kinds=kinds, opts=dict(SC.FULL), X=X, U=U, move_x0=False)          # (x0 stays, as in --tracking kind3)
+        return
     if "--tracking" in args:
         if "c1" in names:
             tracking_single(capi, "c1", P.spring_mass(), steps, skip)

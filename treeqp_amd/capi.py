@@ -564,6 +564,23 @@ def mpc_step_batch(mirrors, x0s=None, profile=0, **kw):
             [u[at[i]:at[i + 1]].copy() for i in range(n)])
 
 
+SHIFT_LEAF_REPEAT, SHIFT_LEAF_ZERO = 0, 1          # TQGPU_SHIFT_LEAF_* of include/treeqp_amd.h
+SHIFT_DUALS, SHIFT_WORKING_SETS = 1, 2             # TQGPU_SHIFT_*
+c_u64_p = C.POINTER(C.c_uint64)
+
+
+def shift_map(nk, nx, realised: int, leaf: int = SHIFT_LEAF_REPEAT) -> np.ndarray:
+    """img[Nn] of tqgpu_shift_map: the node of the old problem every node of the new one starts from after child `realised` of the root
+    became the root (-1: none); host arithmetic only.  A tree of one node gives an empty array."""
+    a, b = _i32(nk), _i32(nx)
+    assert len(a) == len(b)
+    img = np.full(len(a), -1, dtype=np.int32)
+    rc = lib().tqgpu_shift_map(len(a), _ip(a), _ip(b), int(realised), int(leaf), _ip(img))
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_shift_map failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    return img if len(a) > 1 else img[:0]
+
+
 def mpc_stats() -> dict:
     """What this thread's last mpc_step / mpc_step_batch cost (tqgpu_mpc_stats): kernel launches, copies in either direction, waits
     of the host for the device."""
@@ -774,8 +791,49 @@ class TqGpu:
         self._chk(lib().tqgpu_mpc_set_x0(self.h, _dp(a)))
         return self
 
+    # ---- the shifted warm start: duals and working sets move a stage (tqgpu_mpc_set_shift, tqgpu_mpc_shift) ----
+    def mpc_set_shift(self, leaf: int = SHIFT_LEAF_REPEAT, what: int = SHIFT_DUALS):
+        """Build the shift maps of all nk[0] realisations on the device (tqgpu_mpc_set_shift): leaf SHIFT_LEAF_REPEAT or SHIFT_LEAF_ZERO,
+        what SHIFT_DUALS, optionally | SHIFT_WORKING_SETS; what == 0 forgets them and returns warm start mode 2 to mode 1."""
+        self._chk(lib().tqgpu_mpc_set_shift(self.h, int(leaf), C.c_uint(int(what))))
+        return self
+
+    def mpc_set_realised(self, child: int):
+        """The child of the root that the last step realised (tqgpu_mpc_set_realised; host state only, default 0)."""
+        self._chk(lib().tqgpu_mpc_set_realised(self.h, int(child)))
+        return self
+
+    @property
+    def mpc_shift_state(self) -> dict:
+        """leaf policy, what and the realisation in force (tqgpu_mpc_get_shift)"""
+        leaf, what, real = C.c_int(), C.c_uint(), C.c_int()
+        self._chk(lib().tqgpu_mpc_get_shift(self.h, C.byref(leaf), C.byref(what), C.byref(real)))
+        return dict(leaf=leaf.value, what=what.value, realised=real.value)
+
+    def mpc_shift(self):
+        """The shift alone (tqgpu_mpc_shift): one kernel, no synchronisation; the next solve starts from the shifted duals, in any mode,
+        and the working sets have moved if they were asked for."""
+        self._chk(lib().tqgpu_mpc_shift(self.h))
+        return self
+
+    def working_sets(self) -> dict:
+        """The hot-start halves of the stored working sets (tqgpu_get_working_sets), one uint64 per node each: bounds, rows, bound_sides,
+        row_sides; 0 on nodes of kinds 0 and 1.  Waits for the stream."""
+        out = {k: np.zeros(len(self.nk), dtype=np.uint64) for k in ("bounds", "rows", "bound_sides", "row_sides")}
+        self._chk(lib().tqgpu_get_working_sets(self.h, *[out[k].ctypes.data_as(c_u64_p) for k in ("bounds", "rows", "bound_sides", "row_sides")]))
+        return out
+
+    def set_working_sets(self, bounds=None, rows=None, bound_sides=None, row_sides=None):
+        """Upload hot-start working sets (tqgpu_set_working_sets; None: left alone); nodes of kinds 0 and 1 ignore theirs."""
+        keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64) for a in (bounds, rows, bound_sides, row_sides)]
+        for a in keep:
+            assert a is None or len(a) == len(self.nk)
+        self._chk(lib().tqgpu_set_working_sets(self.h, *[None if a is None else a.ctypes.data_as(c_u64_p) for a in keep]))
+        return self
+
     def set_warm_start(self, mode: int):
-        """0: every solve starts from the buffer of set_lambda (default); 1: from the duals of the last solve, copied on the device"""
+        """0: every solve starts from the buffer of set_lambda (default); 1: from the duals of the last solve, copied on the device;
+        2: from the duals of every node's image under the shift map of the realised child (mpc_set_shift first)"""
         self._chk(lib().tqgpu_set_warm_start(self.h, int(mode)))
         return self
 

@@ -1978,6 +1978,14 @@ struct tqgpu_solver {
     unsigned long long mpc_tag = 0;                /* the tag of the last u0 post this mirror waited for (its own block, or as the lead of a batch) */
     int warm_mode = 0;                  /* tqgpu_set_warm_start */
     bool warm_fresh = true;             /* the start buffer holds what the caller (or a batch step's launch) put there for the next solve: no copy ahead of it */
+    /* the shift (tqgpu_mpc_set_shift): per realisation j < max(nk[0], 1) the source entry of every entry of the start buffer, [j][sum_nx]
+     * ints, and behind them the node tables [j][Nn] (the image a node may take its working sets from, -1: none), in one device block;
+     * d_lam_keep: sum_nx doubles, the caller's start buffer while a tqgpu_mpc_shift of a mirror in mode 0 holds its place for one solve */
+    int *d_shift = nullptr;
+    double *d_lam_keep = nullptr;
+    int shift_leaf = 0, shift_realised = 0;
+    unsigned shift_what = 0;
+    int shift_restore = 0;              /* 1: tqgpu_mpc_shift saved the start buffer of a mirror in mode 0, the next solve consumes the shifted one; 2: that solve has begun, the one after it puts the saved buffer back first */
     long mpc_drained_at = 0;            /* as kkt_drained_at, for the batch step's launch ahead of the solves */
     MItem *d_mitems = nullptr, *h_mitems = nullptr; int mitems_cap = 0;      /* batch steps: one descriptor per member of this device (the device's first member owns the array) */
     double *h_mpc_u0s = nullptr; int mpc_u0s_cap = 0;                        /* ... and their u[0] with the tag behind them, pinned */
@@ -3053,7 +3061,10 @@ __global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__
  *                a root that keeps its states (xlo != nullptr) instead: xmin[0] = xmax[0] = x0, copied bit for bit, states over lanes, and
  *                entries 3, 4 (lower, upper) of the root's packed constants, k_pack_persist's layout cst[(0 * 16 + t) * 5 + ..]; blocks [0, nk0) idle;
  *   nk0 + 1 ..   the warm start: MPC_WARM_SPAN doubles of the current duals each (Ctrl::cur says which buffer: read here, so nothing waits for the host)
- *                into the start buffer, node-indexed as they lie (phantom root states included).
+ *                into the start buffer, node-indexed as they lie (phantom root states included).  A shifted warm start (warm start mode 2,
+ *                tqgpu_mpc_shift) gathers instead: entry i of the start buffer is entry shift_src[i] of the current duals, or 0.0 where
+ *                shift_src[i] < 0 (the entry-level source table of the current realisation, tqgpu_mpc_set_shift): a copy with an index
+ *                load per entry.  Block nk0 then also moves the stored working sets of kinds 2 and 3 a stage (mpc_shift_sets).
  *   behind them, one block per node (mirrors with a reference trajectory, tqgpu_mpc_set_tracking, in a launch that moves the window):
  *                the linear terms of node k for trajectory row min(t0 + stage[k], T - 1), rows of [x | u] over lanes, every entry one chain
  *                of fused multiply-adds from its base, columns ascending (mpc_track_node); where the packed constants of the persistent
@@ -3072,6 +3083,14 @@ struct MItem {
     double *u0;                        /* pinned: where k_mpc_post puts u[0] */
     int nx0, nc0, nu0, sum_nx;
     int fold, warm;                    /* what k_mpc_pre does for this mirror */
+    /* the shift (tqgpu_mpc_set_shift; shift_src == nullptr: the plain copy): the source entry of every entry of the start buffer for the
+     * realisation in force (-1: 0.0), and the node table of that realisation, [Nn] the image a node may take its working sets from (-1: it
+     * keeps its own), where the sets move too (else nullptr); lam_keep: where tqgpu_mpc_shift saves the start buffer of a mirror in mode 0 */
+    const int *shift_src, *shift_node;
+    double *lam_keep;
+    unsigned long long *ws_rmask, *ws_sides;      /* Gen::rmask, Gen::sides where the tree has rows (else nullptr), with ws_nc = Gen::nc */
+    const int *ws_nc;
+    int realised;
     /* tracking (xtraj == nullptr: none): the trajectory, the base linear terms and the nodes' stages in device memory; the targets Data::q,
      * Data::r (r above) and entry 0 of the packed constants where they are current (else nullptr); t0: the window now in force (-1: none yet) */
     const double *xtraj, *utraj, *q0, *rb0;
@@ -3126,6 +3145,34 @@ __device__ __forceinline__ void mpc_track_root_r(const MItem &it, int lane) {
         it.r[i] = v;
     }
 }
+/* The stored working sets move a stage, in place: node k takes the bound set (and its sides) of m = shift_node[k] where both are of kind
+ * 2 or 3 and nu agrees (nx does, by the map), the row set (and its sides) where both are of kind 3 and nc agrees; every other node keeps
+ * its own; the halves [Nn, 2 Nn) that say what P_k was built for are not touched.  m > k for every node that takes a set (images are one
+ * level deeper and nodes are numbered level by level), so ONE wave that walks the nodes in ascending chunks of 64, with all loads of a
+ * chunk complete ahead of its stores, reads only words no earlier store has replaced: no scratch copy, no atomics, no dependence on the
+ * order of blocks (no other block touches these words). */
+__device__ __forceinline__ void mpc_shift_sets(const MItem &it, int lane) {
+    const int Nn = it.T.Nn;
+    const int *kind = it.D.kind;
+    unsigned long long *bm = it.D.bmask, *rm = it.ws_rmask, *sd = it.ws_sides;
+    for (int base = 0; base < Nn; base += WAVE) {
+        const int k = base + lane;
+        const int m = k < Nn ? it.shift_node[k] : -1;
+        bool tb = false, tr = false;
+        unsigned long long vb = 0ull, vsb = 0ull, vr = 0ull, vsr = 0ull;
+        if (m > k && m < Nn) {
+            const int kk = kind[k], km = kind[m];
+            tb = kk >= 2 && km >= 2 && it.T.nu[k] == it.T.nu[m];
+            tr = tb && rm && kk == 3 && km == 3 && it.ws_nc[k] == it.ws_nc[m];
+            if (tb) { vb = bm[m]; if (sd) vsb = sd[m]; }
+            if (tr) { vr = rm[m]; vsr = sd[Nn + m]; }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          /* every load of the chunk has returned ... */
+        __builtin_amdgcn_wave_barrier();                          /* ... before any of its stores is issued */
+        if (tb) { bm[k] = vb; if (sd) sd[k] = vsb; }
+        if (tr) { rm[k] = vr; sd[Nn + k] = vsr; }
+    }
+}
 __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane) {
     const Tree &T = it.T;
     const int nk0 = T.nk[0], nx0 = it.nx0;
@@ -3146,6 +3193,7 @@ __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane
         return;
     }
     if (blk == nk0) {
+        if (it.warm && it.shift_node) mpc_shift_sets(it, lane);
         const bool owns_r0 = mpc_track_owns_r0(it);
         if (owns_r0 && (it.fold || it.trk)) mpc_track_root_r(it, lane);
         if (!it.fold) return;
@@ -3173,9 +3221,30 @@ __device__ __forceinline__ void mpc_pre_block(const MItem &it, int blk, int lane
     if (!it.warm) return;
     const double *src = it.D.ctrl->cur ? it.D.lam1 : it.D.lam0;
     const int base = (blk - nk0 - 1) * MPC_WARM_SPAN;
+    if (!it.shift_src) {
+        for (int t = 0; t < MPC_WARM_SPAN / WAVE; t++) {
+            const int i = base + t * WAVE + lane;
+            if (i < it.sum_nx) it.lam_init[i] = src[i];
+        }
+        return;
+    }
+    /* the shifted start: the indices of the span first, then the gathered duals (independent loads), then the stores; a thread saves the entry
+     * it is about to replace where the caller's start buffer has to come back (lam_keep) */
+    int from[MPC_WARM_SPAN / WAVE];
+    double v[MPC_WARM_SPAN / WAVE];
+#pragma unroll
     for (int t = 0; t < MPC_WARM_SPAN / WAVE; t++) {
         const int i = base + t * WAVE + lane;
-        if (i < it.sum_nx) it.lam_init[i] = src[i];
+        from[t] = i < it.sum_nx ? it.shift_src[i] : -1;
+    }
+#pragma unroll
+    for (int t = 0; t < MPC_WARM_SPAN / WAVE; t++) v[t] = from[t] >= 0 && from[t] < it.sum_nx ? src[from[t]] : 0.0;
+#pragma unroll
+    for (int t = 0; t < MPC_WARM_SPAN / WAVE; t++) {
+        const int i = base + t * WAVE + lane;
+        if (i >= it.sum_nx) continue;
+        if (it.lam_keep) it.lam_keep[i] = it.lam_init[i];
+        it.lam_init[i] = v[t];
     }
 }
 __global__ void __launch_bounds__(WAVE) k_mpc_pre(MItem it) { mpc_pre_block(it, blockIdx.x, threadIdx.x); }
@@ -4087,6 +4156,7 @@ extern "C" int tqgpu_set_lambda(tqgpu_solver *s, const double *lambda) {
     /* kept in a resident buffer: every tqgpu_solve starts from it (device-to-device copy) */
     s->lam_valid = false;
     s->warm_fresh = true;            /* warm start mode 1: the next solve starts from this buffer */
+    s->shift_restore = 0;            /* (a buffer saved by tqgpu_mpc_shift is superseded) */
     if (lambda) { H2D(s->d_lam_init + s->nx0, lambda, s->sum_lam); }
     else HIP_TRY(hipMemsetAsync(s->d_lam_init, 0, sizeof(double) * (size_t)s->sum_nx, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -4133,6 +4203,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
     if (lambda && s->sum_lam > 0) {
         const size_t bytes = sizeof(double) * (size_t)s->sum_lam;
         s->warm_fresh = true;        /* as tqgpu_set_lambda (a warm-start copy since the last upload has cleared lam_valid) */
+        s->shift_restore = 0;
         if (!s->lam_valid || memcmp(s->h_lam, lambda, bytes) != 0) {
             memcpy(s->h_lam, lambda, bytes);
             HIP_TRY(hipMemcpyAsync(s->d_lam_init + s->nx0, s->h_lam, bytes, hipMemcpyHostToDevice, s->stream));
@@ -4404,7 +4475,7 @@ int begin_persist(tqgpu_solver *s, SolveCtx &cx) { return launch_persist(s, cx.O
  * solve enqueues there.  The last solve may have been part of a batch launch on another stream (settle); a launch the caller makes on
  * another stream waits for this one (stream_pending, join_lead_stream).  A batch step does all its members' copies in one launch
  * instead and leaves warm_fresh set. */
-MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track = false);
+MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track = false, bool shift = false);
 int enqueue_warm_start(tqgpu_solver *s, SolveCtx &cx) {
     int rc = settle(s);
     if (rc != TQGPU_OK) return rc;
@@ -4420,11 +4491,23 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
 #ifdef TQ_HOSTPROF
     cx.hp0 = HP_NOW();
 #endif
-    const bool warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0;          /* (solve_no: before prepare_solve counts this one) */
+    const bool warm = s->warm_mode >= 1 && !s->warm_fresh && s->solve_no > 0;          /* (solve_no: before prepare_solve counts this one) */
     s->warm_fresh = false;
     int rc = prepare_solve(s, o, cx, defer != nullptr);
     if (rc != TQGPU_OK) return rc;
     if (warm && (rc = enqueue_warm_start(s, cx)) != TQGPU_OK) return rc;
+    /* a tqgpu_mpc_shift of a mirror in mode 0 lent the start buffer to the shifted duals for ONE solve: this one (1 -> 2), or the one before
+     * (2: the caller's buffer comes back first, on the mirror's own stream as the warm-start copy; in another mode the buffer is not the caller's) */
+    if (s->shift_restore == 1) s->shift_restore = 2;
+    else if (s->shift_restore == 2) {
+        s->shift_restore = 0;
+        if (s->warm_mode == 0 && s->d_lam_keep) {
+            if ((rc = settle(s)) != TQGPU_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(s->d_lam_init, s->d_lam_keep, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, s->stream)); MPC_COUNT(copies, 1);
+            s->lam_valid = false;
+            s->stream_pending = true;
+        }
+    }
     if (!single_launch(cx.route)) return begin_enqueued(s, cx);
     if ((rc = enqueue_setup(s, cx, defer)) != TQGPU_OK) return rc;
 #ifdef TQ_HOSTPROF
@@ -4653,6 +4736,7 @@ static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const Solve
     s->n_timeouts++;
     if (getenv("TREEQP_AMD_VERBOSE")) fprintf(stderr, "[treeqp_amd] persistent launch timed out (device shared?): solving on the launch-per-tier path\n");
     s->warm_fresh = true;                              /* from the same starting duals: the start buffer holds them, whatever the warm-start mode */
+    if (s->shift_restore == 2) s->shift_restore = 1;   /* (... also where tqgpu_mpc_shift put them there for this solve) */
     SolveCtx cx(env, route_of(s, o, false));          /* a fresh decision: use_persist is off now */
     int rc = solve_begin(s, o, cx);
     if (rc != TQGPU_OK) return rc;
@@ -5114,7 +5198,7 @@ int mpc_refuse(const tqgpu_solver *s, const char *who) {
 }
 
 /* the descriptor of a mirror for k_mpc_pre / k_mpc_post: views into d_mpc and h_mpc (null before tqgpu_mpc_set_root / _set_root_states: fold must be false then) */
-MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track) {
+MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track, bool shift) {
     MItem it{};
     it.T = s->T; it.D = s->D;
     const size_t nx0 = (size_t)s->mpc_nx0, nb = (size_t)s->mpc_nb, nu0 = (size_t)s->nu[0], nc0 = (size_t)s->mpc_nc0;
@@ -5135,6 +5219,16 @@ MItem mpc_item(const tqgpu_solver *s, bool fold, bool warm, bool track) {
     it.lam_init = s->d_lam_init;
     it.nx0 = s->mpc_nx0; it.nc0 = s->mpc_nc0; it.nu0 = s->nu[0]; it.sum_nx = s->sum_nx;
     it.fold = fold ? 1 : 0; it.warm = warm ? 1 : 0;
+    /* the warm start of mode 2, and tqgpu_mpc_shift in any mode (shift), go through the tables of the realisation in force; the node
+     * table only where the sets were asked for and the tree has nodes of kinds 2 / 3 now (Data::kind is read there) */
+    if (warm && s->d_shift && (shift || s->warm_mode == 2)) {
+        const size_t nreal = (size_t)std::max(s->nk[0], 1), j = (size_t)s->shift_realised;
+        it.shift_src = s->d_shift + j * (size_t)s->sum_nx;
+        if ((s->shift_what & TQGPU_SHIFT_WORKING_SETS) && s->dense && (s->box || s->gen) && s->D.kind && s->D.bmask)
+            it.shift_node = s->d_shift + nreal * (size_t)s->sum_nx + j * (size_t)s->Nn;
+        if (s->gen && s->d_rmask && s->h_gen.nc) { it.ws_rmask = s->d_rmask; it.ws_sides = s->d_rmask + 2 * (size_t)s->Nn; it.ws_nc = s->h_gen.nc; }
+        it.realised = s->shift_realised;
+    }
     if (s->d_trk) {
         const double *p = s->d_trk;
         it.xtraj = p; p += (size_t)s->trk_T * s->trk_nxt; it.utraj = p; p += (size_t)s->trk_T * s->trk_nut;
@@ -5389,7 +5483,8 @@ extern "C" int tqgpu_mpc_get_window(const tqgpu_solver *s, int *t0) {
 extern "C" int tqgpu_set_warm_start(tqgpu_solver *s, int mode) {
     int rc;
     if ((rc = mpc_refuse(s, "tqgpu_set_warm_start"))) return rc;
-    if (mode != 0 && mode != 1) return fail(TQGPU_EINVAL, "tqgpu_set_warm_start: mode must be 0 or 1");
+    if (mode != 0 && mode != 1 && mode != 2) return fail(TQGPU_EINVAL, "tqgpu_set_warm_start: mode must be 0, 1 or 2");
+    if (mode == 2 && !s->d_shift) return fail(TQGPU_EINVAL, "tqgpu_set_warm_start: mode 2 needs the maps of tqgpu_mpc_set_shift first");
     s->warm_mode = mode;
     return TQGPU_OK;
 }
@@ -5397,6 +5492,173 @@ extern "C" int tqgpu_get_warm_start(const tqgpu_solver *s, int *mode) {
     int rc;
     if ((rc = mpc_refuse(s, "tqgpu_get_warm_start"))) return rc;
     if (mode) *mode = s->warm_mode;
+    return TQGPU_OK;
+}
+
+/* ---- the shift: after a step the realised child of the root is the new root, and every node starts from its image's duals and sets ---- */
+namespace {
+/* img[k], and rep[k] != 0 where the image is a repeated leaf (img[k] == img[dad(k)]).  Nodes are numbered level by level, so kid0 is the
+ * running sum of nk and a parent's image is known before its children's.  The fit of nx is applied last and does not propagate: a node
+ * below one whose image does not fit still has the image its path gives it. */
+int shift_map_core(int Nn, const int *nk, const int *nx, int realised, int leaf, std::vector<int> &img, std::vector<char> &rep, const char *who) {
+    if (Nn < 1 || !nk || !nx) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments");
+    if (leaf != TQGPU_SHIFT_LEAF_REPEAT && leaf != TQGPU_SHIFT_LEAF_ZERO) return fail(TQGPU_EINVAL, std::string(who) + ": unknown leaf policy " + std::to_string(leaf));
+    std::vector<int> kid0((size_t)Nn);
+    long at = 1;
+    for (int k = 0; k < Nn; k++) {
+        if (nk[k] < 0 || (k > 0 && at <= k)) return fail(TQGPU_EINVAL, std::string(who) + ": nk does not describe a tree numbered level by level");
+        kid0[(size_t)k] = (int)at;
+        at += nk[k];
+        if (at > Nn) return fail(TQGPU_EINVAL, std::string(who) + ": nk names more than Nn nodes");
+    }
+    if (at != Nn) return fail(TQGPU_EINVAL, std::string(who) + ": nk names " + std::to_string(at) + " nodes, Nn is " + std::to_string(Nn));
+    img.assign((size_t)Nn, -1); rep.assign((size_t)Nn, 0);
+    if (Nn == 1) return TQGPU_OK;          /* (a tree of one node: an empty map, whatever `realised`) */
+    if (realised < 0 || realised >= nk[0]) return fail(TQGPU_EINVAL, std::string(who) + ": realised = " + std::to_string(realised) + ", the root has " + std::to_string(nk[0]) + " children");
+    img[0] = kid0[0] + realised;
+    for (int p = 0; p < Nn; p++) {
+        const int ip = img[(size_t)p];
+        for (int c = 0; c < nk[p]; c++) {
+            const int k = kid0[(size_t)p] + c;
+            if (ip < 0) continue;
+            if (nk[ip] > 0) img[(size_t)k] = kid0[(size_t)ip] + std::min(c, nk[ip] - 1);
+            else if (leaf == TQGPU_SHIFT_LEAF_REPEAT) { img[(size_t)k] = ip; rep[(size_t)k] = 1; }
+        }
+    }
+    for (int k = 0; k < Nn; k++) if (img[(size_t)k] >= 0 && nx[img[(size_t)k]] != nx[k]) { img[(size_t)k] = -1; rep[(size_t)k] = 0; }
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_shift_map(int Nn, const int *nk, const int *nx, int realised, int leaf, int *img) {
+    std::vector<int> m; std::vector<char> rep;
+    int rc = shift_map_core(Nn, nk, nx, realised, leaf, m, rep, "tqgpu_shift_map");
+    if (rc != TQGPU_OK) return rc;
+    if (!img) return fail(TQGPU_EINVAL, "tqgpu_shift_map: img is required");
+    if (Nn > 1) std::copy(m.begin(), m.end(), img);
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_set_shift(tqgpu_solver *s, int leaf, unsigned what) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_shift"))) return rc;
+    if (what & ~(unsigned)(TQGPU_SHIFT_DUALS | TQGPU_SHIFT_WORKING_SETS)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_shift: unknown bits in `what`");
+    if (what != 0 && !(what & TQGPU_SHIFT_DUALS)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_shift: the working sets move with the duals (TQGPU_SHIFT_DUALS | TQGPU_SHIFT_WORKING_SETS)");
+    if (what != 0 && leaf != TQGPU_SHIFT_LEAF_REPEAT && leaf != TQGPU_SHIFT_LEAF_ZERO) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_shift: unknown leaf policy " + std::to_string(leaf));
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));          /* (a launch in flight may still read the tables that go) */
+    s->mem.release(s->d_shift); s->mem.release(s->d_lam_keep);
+    s->shift_what = 0; s->shift_realised = 0; s->shift_restore = 0;
+    if (s->warm_mode == 2) s->warm_mode = 1;
+    if (what == 0) return TQGPU_OK;
+    /* the caller's dimensions: the phantom root states are not theirs (and node 0's entries are copied unshifted whatever its image) */
+    const int Nn = s->Nn, nreal = std::max(s->nk[0], 1);
+    std::vector<int> nxu(s->nx.begin(), s->nx.begin() + Nn);
+    nxu[0] -= s->x_pad;
+    std::vector<int> tab((size_t)nreal * ((size_t)s->sum_nx + (size_t)Nn), -1), img;
+    std::vector<char> rep;
+    for (int j = 0; j < nreal; j++) {
+        if ((rc = shift_map_core(Nn, s->nk.data(), nxu.data(), j, leaf, img, rep, "tqgpu_mpc_set_shift"))) return rc;
+        int *src = tab.data() + (size_t)j * s->sum_nx, *node = tab.data() + (size_t)nreal * s->sum_nx + (size_t)j * Nn;
+        for (int i = 0; i < s->nx[0]; i++) src[s->xoff[0] + i] = s->xoff[0] + i;
+        for (int k = 1; k < Nn; k++) {
+            const int m = img[(size_t)k];
+            if (m < 0) continue;
+            for (int i = 0; i < s->nx[k]; i++) src[s->xoff[k] + i] = s->xoff[m] + i;
+        }
+        /* the sets: never from a repeated leaf, never to the root of a tree with phantom states (its bits are laid out otherwise) */
+        for (int k = 0; k < Nn; k++) {
+            const int m = img[(size_t)k];
+            if (m > k && !rep[(size_t)k] && !(k == 0 && s->x_pad > 0)) node[k] = m;
+        }
+    }
+    if ((rc = s->mem.upload(s->d_shift, tab.data(), sizeof(int) * tab.size(), TQGPU_ENOMEM, "the shift maps")) ||
+        (rc = s->mem.zeroed(s->d_lam_keep, sizeof(double) * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the saved start buffer"))) {
+        s->mem.release(s->d_shift); s->mem.release(s->d_lam_keep);
+        return rc;
+    }
+    s->shift_leaf = leaf; s->shift_what = what;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_set_realised(tqgpu_solver *s, int child) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_set_realised"))) return rc;
+    if (child < 0 || child >= std::max(s->nk[0], 1)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_realised: child = " + std::to_string(child) + ", the root has " + std::to_string(s->nk[0]) + " children");
+    s->shift_realised = child;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_shift(const tqgpu_solver *s, int *leaf, unsigned *what, int *realised) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_shift"))) return rc;
+    if (leaf) *leaf = s->shift_leaf;
+    if (what) *what = s->shift_what;
+    if (realised) *realised = s->shift_realised;
+    return TQGPU_OK;
+}
+
+/* the shift alone: one launch of k_mpc_pre (block nk0 for the sets, the warm blocks for the duals) on the mirror's stream, nothing waited for */
+extern "C" int tqgpu_mpc_shift(tqgpu_solver *s) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_shift"))) return rc;
+    if (!s->d_shift) return fail(TQGPU_EINVAL, "tqgpu_mpc_shift: the maps have not been built yet (tqgpu_mpc_set_shift)");
+    if (s->solve_no < 1) return fail(TQGPU_EINVAL, "tqgpu_mpc_shift: this mirror has not solved yet: there are no duals to shift");
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MItem it = mpc_item(s, false, true, false, true);
+    /* mode 0 promises the caller's start buffer to every solve: the kernel saves it (once: a second shift ahead of the same solve finds the
+     * shifted duals there), and the solve after the next puts it back (solve_begin) */
+    const bool lend = s->warm_mode == 0;
+    if (lend && s->shift_restore == 0) it.lam_keep = s->d_lam_keep;
+    hipLaunchKernelGGL(k_mpc_pre, dim3(mpc_launch_blocks(s, true, false)), dim3(WAVE), 0, s->stream, it);
+    HIP_TRY(hipGetLastError());
+    if (lend) s->shift_restore = 1;
+    s->warm_fresh = true;          /* the next solve starts from the start buffer as it is now, in any mode */
+    s->lam_valid = false;
+    s->stream_pending = true;
+    return TQGPU_OK;
+}
+
+/* the hot-start halves of the stored working sets, [0, Nn) of bmask, rmask and of both parts of sides; 0 on nodes of kinds 0 and 1 */
+extern "C" int tqgpu_get_working_sets(tqgpu_solver *s, unsigned long long *bounds, unsigned long long *rows, unsigned long long *bound_sides, unsigned long long *row_sides) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_get_working_sets"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t Nn = (size_t)s->Nn, bytes = sizeof(unsigned long long) * Nn;
+    const bool sets = s->dense && (s->box || s->gen) && s->h_kind.size() == Nn, rows_there = sets && s->gen && s->d_rmask;
+    unsigned long long *out[4] = {bounds, rows, bound_sides, row_sides};
+    const unsigned long long *from[4] = {sets ? s->D.bmask : nullptr, rows_there ? s->d_rmask : nullptr, rows_there ? s->d_rmask + 2 * Nn : nullptr, rows_there ? s->d_rmask + 3 * Nn : nullptr};
+    for (int a = 0; a < 4; a++) {
+        if (!out[a]) continue;
+        if (from[a]) HIP_TRY(hipMemcpy(out[a], from[a], bytes, hipMemcpyDeviceToHost));
+        else std::fill(out[a], out[a] + Nn, 0ull);
+        for (size_t k = 0; k < Nn; k++) if (!sets || s->h_kind[k] < 2 || ((a == 1 || a == 3) && s->h_kind[k] != 3)) out[a][k] = 0ull;
+    }
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_set_working_sets(tqgpu_solver *s, const unsigned long long *bounds, const unsigned long long *rows, const unsigned long long *bound_sides, const unsigned long long *row_sides) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_set_working_sets"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t Nn = (size_t)s->Nn, bytes = sizeof(unsigned long long) * Nn;
+    const bool sets = s->dense && (s->box || s->gen) && s->h_kind.size() == Nn, rows_there = sets && s->gen && s->d_rmask;
+    if (!sets) return TQGPU_OK;          /* no node of kind 2 or 3: nothing reads a set */
+    const unsigned long long *in[4] = {bounds, rows, bound_sides, row_sides};
+    unsigned long long *to[4] = {s->D.bmask, rows_there ? s->d_rmask : nullptr, rows_there ? s->d_rmask + 2 * Nn : nullptr, rows_there ? s->d_rmask + 3 * Nn : nullptr};
+    std::vector<unsigned long long> w(Nn);
+    for (int a = 0; a < 4; a++) {
+        if (!in[a] || !to[a]) continue;
+        HIP_TRY(hipMemcpy(w.data(), to[a], bytes, hipMemcpyDeviceToHost));          /* (the words of the other nodes stay) */
+        for (size_t k = 0; k < Nn; k++) if (s->h_kind[k] >= 2 && !((a == 1 || a == 3) && s->h_kind[k] != 3)) w[k] = in[a][k];
+        HIP_TRY(hipMemcpy(to[a], w.data(), bytes, hipMemcpyHostToDevice));
+    }
     return TQGPU_OK;
 }
 
@@ -5426,7 +5688,7 @@ static int mpc_step_impl(tqgpu_solver *s, const double *x0, int t0, const tqgpu_
     HIP_TRY(hipSetDevice(s->device));
     MpcLive live;
     if ((rc = mpc_take_x0(s, x0, who)) || (rc = mpc_take_window(s, t0, true, who))) return rc;
-    const bool fold = x0 != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0, track = t0 >= 0;
+    const bool fold = x0 != nullptr, warm = s->warm_mode >= 1 && !s->warm_fresh && s->solve_no > 0, track = t0 >= 0;
     if (fold || warm || track) {
         hipLaunchKernelGGL(k_mpc_pre, dim3(mpc_launch_blocks(s, warm, track)), dim3(WAVE), 0, s->stream, mpc_item(s, fold, warm, track));
         HIP_TRY(hipGetLastError());
@@ -5608,7 +5870,7 @@ static int mpc_step_batch_impl(tqgpu_solver **solvers, int n, const double *x0s,
             }
             const int t0 = t0s ? t0s[d.idx[m]] : -1;
             if ((rc = mpc_take_x0(s, x0s ? x0s + x_off[(size_t)d.idx[m]] : nullptr, who)) || (rc = mpc_take_window(s, t0, true, who))) return rc;
-            const bool fold = x0s != nullptr, warm = s->warm_mode == 1 && !s->warm_fresh && s->solve_no > 0, track = t0 >= 0;
+            const bool fold = x0s != nullptr, warm = s->warm_mode >= 1 && !s->warm_fresh && s->solve_no > 0, track = t0 >= 0;
             MItem &it = lead->h_mitems[m];
             it = mpc_item(s, fold, warm, track);
             it.u0 = lead->h_mpc_u0s + u_at;          /* the batch's block, not the member's own */
