@@ -568,6 +568,57 @@ int tqgpu_mpc_shift(tqgpu_solver *s);
 int tqgpu_get_working_sets(tqgpu_solver *s, unsigned long long *bounds, unsigned long long *rows, unsigned long long *bound_sides, unsigned long long *row_sides);
 int tqgpu_set_working_sets(tqgpu_solver *s, const unsigned long long *bounds, const unsigned long long *rows, const unsigned long long *bound_sides, const unsigned long long *row_sides);
 
+/* ---- Parametric sensitivities of an MPC step: du0/dx0 (the feedback gain K), dz/dx0 and dlam/dx0 on the device ----------------------
+ * How the answer of the last solve moves when x0 moves, at the point tqgpu_get_solution would return, with the active set frozen there.
+ *   P_k                  the elimination matrix of node k for z_k = [x_k; u_k].  Kind 0: diagonal, 1/Qd_i (1/Rd_i) where the exported value
+ *                        is strictly inside its bounds, 0.0 where it equals xmin / xmax (umin / umax) bit for bit (clipping assigns the
+ *                        bound itself, so the comparison is exact); the phantom root states of an embedded x0-eliminated tree are free
+ *                        (their A columns are zero).  Kind 1: P_k = H_k^-1, what the device keeps since its last factorisation of H_k.
+ *   M                    the dual Hessian as the solver builds it: with C = [A_c B_c] stacked over the children c of p,
+ *                        W_p = C P_p C' + blockdiag(P_c^{xx}),  Ut_p = -(C P_p)[:, :nx_p]';  with res_c = A_c x_p + B_c u_p + b_c - x_c
+ *                        (class TQGPU_KKT_DYN), d res / d lam = -M.
+ *   G                    G = d res / d x0 at fixed lam (sum_lam x nx0), non-zero only in the rows of the root's children c:
+ *                        eliminated root (tqgpu_mpc_set_root):  G_c = A0_c - B_c P_0 S0  (the second term only where S0 was given);
+ *                        root with states (tqgpu_mpc_set_root_states):  G_c = A_c.
+ *   M dLam = G           solved block by block with the tall Cholesky of the solver and the regularisation rule of opts (regType, regTol,
+ *                        regValue) as the solver's own factorisation applies it; n_reg: the blocks regularised.
+ *   dZ                   dZ_k = P_k ( [dLam_k; 0] - sum_c C_c' dLam_c ) + direct_k  for every node k, with
+ *                        direct_0 = -P_0 [0; S0] for an eliminated root, direct_0 = [I; 0] on the root's states for a root with states,
+ *                        direct_k = 0 elsewhere.  K = the u rows of dZ_0.
+ *   uniqueness           M = E P E', so a null vector v of M gives P E' v = 0: dZ (and K) is unique even where M is singular, as long as
+ *                        G lies in the range of M; dLam is unique only when n_reg == 0.
+ *   tqgpu_mpc_sensitivity   evaluates all of it for the point of the last solve, whatever its route and status.  Like tqgpu_kkt_residual it
+ *                        reads the export block (the packing is enqueued unless it went out ahead or a certified step packed the point)
+ *                        and the problem data in place.  Launches, one wave per unit, ordered by launch boundaries on the mirror's
+ *                        stream (no kernel waits for another workgroup): 1 (W, Ut, P, G) + one per block level, deepest first (tall
+ *                        Cholesky of [W; Ut], Schur complement into the parent's W; the root carries G' as nx0 extra rows) + one per
+ *                        block level below the root (grid: blocks x nx0) + 1 (dZ, K).  The results stay on the device; K (nu[0] x nx0,
+ *                        column major), u0*, x0_ref (the x0 last folded) and n_reg come back through pinned memory in one copy, with
+ *                        one wait.  It works in buffers of its own (allocated on first use, freed by tqgpu_destroy) and changes nothing
+ *                        a later solve, tqgpu_get_solution or tqgpu_kkt_residual reads.  Counted into tqgpu_mpc_stats.
+ *                        TQGPU_EINVAL: before tqgpu_mpc_set_root / _set_root_states, before the first solve, opts == NULL, and where the
+ *                        problem was changed (an upload, an x0 fold, a window move) since the last solve: the point and the data must
+ *                        belong together.
+ *                        TQGPU_EUNSUPPORTED: a tree with nodes of kind 2 or 3 (Pd need not belong to the final working set after a line
+ *                        search's last trial), a rank of a sharded solve, a tall root block [W; G'] that does not fit 160 KiB of LDS.
+ *   tqgpu_mpc_get_gain   K, u0*, x0_ref of the last tqgpu_mpc_sensitivity (any pointer may be NULL; host state only).
+ *   tqgpu_mpc_get_sensitivities   dx, du, dlam: column j of each array is the flat layout of tqgpu_get_solution for parameter x0[j]
+ *                        (sum_nx x nx0, sum_nu x nx0, sum_lam x nx0; phantom root states excluded).  Downloads and waits: a stream
+ *                        synchronisation and up to three blocking copies, which tqgpu_mpc_stats does not count (a diagnostic read-out).
+ *   tqgpu_mpc_predict    one kernel and one wait.  With dx_j = x0_new[j] - x0_ref[j] every entry is one chain, j ascending:
+ *                          v = u0*[i];  v = fma(K[i, j], dx_j, v);
+ *                        on a root of kind 0 the result is clipped into [umin[0], umax[0]] as the device holds them, n_clipped counts the
+ *                        entries moved.  duals != 0: the same launch (a wave per node) writes lam*_e + sum_j dLam[e, j] dx_j into the
+ *                        start buffer, v = lam*[e]; v = fma(dLam[e, j], dx_j, v), j ascending.  That start holds for ONE solve in any
+ *                        warm-start mode, by the mechanism of tqgpu_mpc_shift: the buffer of tqgpu_set_lambda is saved and restored the
+ *                        same way.
+ * A stored sensitivity is invalidated by any upload that changes the problem (tqgpu_set_*, an x0 fold, a window move) and by a new solve:
+ * the getters and tqgpu_mpc_predict then return TQGPU_EINVAL, as they do before the first tqgpu_mpc_sensitivity. */
+int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *opts, int *n_reg);
+int tqgpu_mpc_get_gain(tqgpu_solver *s, double *K, double *u0, double *x0_ref);
+int tqgpu_mpc_get_sensitivities(tqgpu_solver *s, double *dx, double *du, double *dlam);
+int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, int duals, int *n_clipped);
+
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written
  * (at most 512 solves back) or -1.  tqgpu_result.device_time of a single-launch (persistent) solve is

@@ -38,7 +38,15 @@ stage sweep are printed for both.
 
 --shift (on top of --tracking and --root-states): the same closed-loop sequences three ways, warm start mode 2 (tqgpu_mpc_set_shift: the
 duals, and on kind3 also the working sets, move a stage on the device), mode 1, and the host loop that the API without the shift allows
-(tqgpu_get_solution, numpy gather, tqgpu_set_lambda, tqgpu_mpc_step_at); see shift_compare."""
+(tqgpu_get_solution, numpy gather, tqgpu_set_lambda, tqgpu_mpc_step_at); see shift_compare.
+
+    python tools/mpc_loop.py --gain [--steps 200] [--skip 10] [c1] [c2]
+    python tools/mpc_loop.py --predict [--steps 200] [--skip 10] [c1] [c2]
+
+--gain: the time of tqgpu_mpc_sensitivity next to the step, against nx0 finite-difference steps through tqgpu_mpc_step, on c1 and c2
+with root states and on c1 x0-eliminated, with the launches, copies and waits of both (gain_compare).  --predict: iterations per step of
+the dual predictor (tqgpu_mpc_sensitivity + tqgpu_mpc_predict with duals) against warm start mode 1 over the sequences of --root-states
+and --tracking (predict_compare)."""
 import ctypes as C
 import sys
 import time
@@ -658,6 +666,110 @@ def shift_compare(capi, name, d, x0, steps, skip, kinds=None, opts=None, X=None,
                   f"trials per step mean {np.mean([c[2] for c in cnt[skip:]]):.2f} | status 0 in {sum(c[0] == 0 for c in cnt)} of {steps}{extra}{tail}", flush=True)
 
 
+def gain_compare(capi, name, p, root_states, steps, skip, h=2.0 ** -20):
+    """--gain: per step of the device loop (warm start mode 1, the x0 path of the plain modes) the time of tqgpu_mpc_sensitivity behind
+    the step, against the only way the API without it has to the gain: nx0 more steps at x0 + h e_j through tqgpu_mpc_step (each a fold
+    and a solve from the last duals), K[:, j] = (u0_j - u0) / h.  Both are timed around their calls with the host clock, interleaved
+    step by step on one mirror each; launches, copies and waits are those tqgpu_mpc_stats counts (summed over the nx0 steps)."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    if root_states:
+        d, x0 = full_root(capi, p)
+        xs = [moved_inward(x0, k, 0) for k in range(steps)]
+    else:
+        d, A0, b0, _, x0 = eliminated(capi, p)
+        xs = [moved(x0, k, 0) for k in range(steps)]
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        if root_states:
+            g.mpc_set_root_states()
+        else:
+            g.mpc_set_root(A0, b0)
+        g.set_warm_start(1)
+        return g
+
+    nu0, nx0 = int(d["nu"][0]), len(x0)
+    u0, uj, K = np.zeros(max(nu0, 1)), np.zeros(max(nu0, 1)), np.zeros(nu0 * nx0)
+    la, co, wa, nreg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    gs, gf = mirror(), mirror()
+    tw, ts, tf, cs, cf, dk, regs = [], [], [], [], [], 0.0, 0
+    for k in range(steps):
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_step(gs.h, dp(xs[k]), C.byref(o), C.byref(r), dp(u0)) == 0
+        t1 = time.perf_counter()
+        assert L.tqgpu_mpc_sensitivity(gs.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()
+        t2 = time.perf_counter()
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        assert L.tqgpu_mpc_get_gain(gs.h, dp(K), None, None) == 0
+        tw.append(t1 - t0); ts.append(t2 - t1); cs.append((la.value, co.value, wa.value)); regs += nreg.value
+        # finite differences on the twin: its own step first (not timed: both ways pay it), then nx0 steps, each from the duals of the one before
+        assert L.tqgpu_mpc_step(gf.h, dp(xs[k]), C.byref(o), C.byref(r), dp(u0)) == 0
+        Kfd, cnt = np.zeros((nu0, nx0)), np.zeros(3, dtype=int)
+        t0 = time.perf_counter()
+        for j in range(nx0):
+            xj = xs[k].copy()
+            xj[j] += h
+            assert L.tqgpu_mpc_step(gf.h, dp(xj), C.byref(o), C.byref(r), dp(uj)) == 0
+            L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+            cnt += (la.value, co.value, wa.value)
+            Kfd[:, j] = (uj[:nu0] - u0[:nu0]) / h
+        tf.append(time.perf_counter() - t0); cf.append(tuple(cnt))
+        dk = max(dk, float(np.max(np.abs(K.reshape((nu0, nx0), order="F") - Kfd))))
+    gs.close(); gf.close()
+    med = lambda v: tuple(int(np.median([c[i] for c in v[skip:]])) for i in range(3))
+    form = "root with states" if root_states else "x0 eliminated"
+    print(f"{name}, --gain, {form}: {len(d['nk'])} nodes, nx0 {nx0}, nu[0] {nu0}, {steps} steps; blocks regularised over the run {regs}")
+    for what, t, c in (("step", tw, None), ("sensitivity", ts, cs), (f"{nx0} FD steps", tf, cf)):
+        m, lo, p90 = stats(t[skip:])
+        tail = "" if c is None else "  | launches %d  copies %d  waits %d" % med(c)
+        print(f"    {what:14s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}{tail}", flush=True)
+    print(f"    FD / sensitivity wall {np.median(tf[skip:]) / np.median(ts[skip:]):.2f}; largest |K - K_fd| over the run {dk:.2e} (h = 2^-20; the two differ "
+          f"where a step at x0 + h e_j changes the active set or stops at the tolerance)", flush=True)
+
+
+def predict_compare(capi, name, p, tracking, steps, skip):
+    """--predict: iterations and trials per step over the closed-loop sequence of --root-states (tracking: of --tracking), two ways on a
+    root with states: warm start mode 1, and mode 1 with the dual predictor: behind every step tqgpu_mpc_sensitivity, then
+    tqgpu_mpc_predict(x0 of the next step, duals = 1), so that the next solve starts from lam* + dlam/dx0 (x0_next - x0).  With tracking
+    the window also moves between the steps, which the tangent in x0 does not see.  Wall time per step includes the two extra calls."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    d, x0 = full_root(capi, p)
+    nu0 = int(d["nu"][0])
+    xs = [moved_inward(x0, k, 0) for k in range(steps + 1)]
+    if tracking:
+        X, U = reference(x0, nu0, steps + int(node_stages(d["nk"]).max()) + 2)
+    u0, up = np.zeros(max(nu0, 1)), np.zeros(max(nu0, 1))
+    nreg, ncl = C.c_int(), C.c_int()
+    print(f"{name}, --predict, root with states{', tracking' if tracking else ''}: {len(d['nk'])} nodes, {steps} steps", flush=True)
+    for how in ("mode 1", "mode 1 + predictor"):
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        g.mpc_set_root_states()
+        g.set_warm_start(1)
+        if tracking:
+            g.mpc_set_tracking(X, U, d["q"], d["r"])
+        w, cnt, perr, clipped = [], [], [], 0
+        for k in range(steps):
+            t0 = time.perf_counter()
+            assert L.tqgpu_mpc_step_at(g.h, dp(xs[k]), k if tracking else -1, C.byref(o), C.byref(r), dp(u0)) == 0, L.tqgpu_last_error()
+            cnt.append((r.status, r.iter, r.ls_total))
+            if k > 0 and how != "mode 1":
+                perr.append(float(np.max(np.abs(up[:nu0] - u0[:nu0]))))
+            if how != "mode 1":
+                assert L.tqgpu_mpc_sensitivity(g.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()
+                assert L.tqgpu_mpc_predict(g.h, dp(xs[k + 1]), dp(up), 1, C.byref(ncl)) == 0, L.tqgpu_last_error()
+                clipped += ncl.value
+            w.append(time.perf_counter() - t0)
+        g.close()
+        m, lo, p90 = stats(w[skip:])
+        tail = f" | largest |u0_pred - u0 of the next solve| {max(perr):.2e}, median {np.median(perr):.2e}; entries clipped {clipped}" if perr else ""
+        print(f"    {how:20s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f} | iterations per step mean {np.mean([c[1] for c in cnt[skip:]]):.2f}  "
+              f"trials per step mean {np.mean([c[2] for c in cnt[skip:]]):.2f} | status 0 in {sum(c[0] == 0 for c in cnt)} of {steps}{tail}", flush=True)
+
+
 def main():
     from treeqp_amd import capi, problems as P
     args = sys.argv[1:]
@@ -666,6 +778,19 @@ def main():
     names = [a for a in args if a in ("c1", "c2", "batch", "kind3")] or ["c1", "c2", "batch"]
     if capi.device_count() < 1:
         raise SystemExit("no HIP device")
+    if "--gain" in args:
+        if "c1" in names:
+            gain_compare(capi, "c1", P.spring_mass(), True, steps, skip)
+            gain_compare(capi, "c1", P.spring_mass(), False, steps, skip)
+        if "c2" in names:
+            gain_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--predict" in args:
+        for nm, p in (("c1", P.spring_mass()), ("c2", P.linear_chain(2, 9, 9))):
+            if nm in names:
+                predict_compare(capi, nm, p, False, steps, skip)
+                predict_compare(capi, nm, p, True, steps, skip)
+        return
     if "--shift" in args:
         import solve_sequence_cases as SC
         for nm, p in (("c1", P.spring_mass()), ("c2", P.linear_chain(2, 9, 9))):

@@ -71,6 +71,7 @@ DEVICE_PARTS = {
     "shard": ("TQP_SHARD", ["-DTQ_LD_SCOPE=__HIP_MEMORY_SCOPE_SYSTEM"]),
     "shard_ag": ("TQP_SHARD_AG", []),
     "batch": ("TQP_BATCH", []),
+    "sens": ("TQP_SENS", []),
 }
 JOBS = max(1, min(len(DEVICE_PARTS), (os.cpu_count() or 4)))
 

@@ -914,6 +914,42 @@ class TqGpu:
             self._chk(lib().tqgpu_mpc_step_at(self.h, _dp(a), int(t0), C.byref(o), C.byref(r), _dp(u0)))
         return {f: getattr(r, f) for f, _ in GpuResult._fields_}, u0[:int(self.nu[0])]
 
+    # ---- parametric sensitivities of an MPC step: du0/dx0, dz/dx0, dlam/dx0 (tqgpu_mpc_sensitivity, tqgpu_mpc_predict) ----
+    def mpc_sensitivity(self, profile=0, **kw) -> int:
+        """Sensitivities of the last solve's point with respect to x0, active set frozen (tqgpu_mpc_sensitivity); the options give the
+        regularisation rule of the factorisation.  Returns n_reg, the blocks regularised; the results stay on the device
+        (mpc_gain, mpc_sensitivities, mpc_predict)."""
+        n = C.c_int(0)
+        o = _gpu_opts(profile, **kw)
+        self._chk(lib().tqgpu_mpc_sensitivity(self.h, C.byref(o), C.byref(n)))
+        return n.value
+
+    def mpc_gain(self) -> tuple:
+        """(K (nu[0], nx0), u0*, x0_ref) of the last mpc_sensitivity (tqgpu_mpc_get_gain; host state only)."""
+        nu0, nx0 = int(self.nu[0]), int(self.nx0)
+        K, u0, x0 = np.zeros(max(nu0 * nx0, 1)), np.zeros(max(nu0, 1)), np.zeros(max(nx0, 1))
+        self._chk(lib().tqgpu_mpc_get_gain(self.h, _dp(K), _dp(u0), _dp(x0)))
+        return K[:nu0 * nx0].reshape((nu0, nx0), order="F"), u0[:nu0], x0[:nx0]
+
+    def mpc_sensitivities(self) -> dict:
+        """dx (sum_nx, nx0), du (sum_nu, nx0), dlam (sum_lam, nx0): column j is the flat layout of get_solution for parameter x0[j]
+        (tqgpu_mpc_get_sensitivities; downloads and waits)."""
+        nx0 = int(self.nx0)
+        out = {}
+        for key, n in (("dx", self.sum_nx), ("du", self.sum_nu), ("dlam", self.sum_lam)):
+            out[key] = np.zeros(max(int(n) * nx0, 1))
+        self._chk(lib().tqgpu_mpc_get_sensitivities(self.h, _dp(out["dx"]), _dp(out["du"]), _dp(out["dlam"])))
+        return {key: out[key][:int(n) * nx0].reshape((int(n), nx0), order="F") for key, n in (("dx", self.sum_nx), ("du", self.sum_nu), ("dlam", self.sum_lam))}
+
+    def mpc_predict(self, x0_new, duals: bool = False) -> tuple:
+        """(u0_pred, n_clipped): u0* + K (x0_new - x0_ref), one fma chain per entry, clipped into the root's bounds on a root of kind 0
+        (tqgpu_mpc_predict).  duals: the same launch writes lam* + dlam/dx0 (x0_new - x0_ref) into the start buffer, for one solve."""
+        a = _f64(x0_new)
+        assert len(a) == self.nx0
+        u0, n = np.zeros(max(int(self.nu[0]), 1)), C.c_int(0)
+        self._chk(lib().tqgpu_mpc_predict(self.h, _dp(a), _dp(u0), int(bool(duals)), C.byref(n)))
+        return u0[:int(self.nu[0])], n.value
+
     def export_ahead(self, on: bool) -> None:
         """the solution's packing kernel and download go out behind the solve's launch (callers that fetch the solution after every solve)"""
         self._chk(lib().tqgpu_set_export_ahead(self.h, int(bool(on))))

@@ -1765,6 +1765,7 @@ __global__ void __launch_bounds__(WAVE) k_ls_decide_parts(Data D, Opts O, const 
 #include "tdunes_wide.hpp"
 #include "tdunes_wide3.hpp"
 #include "tdunes_gpersist.hpp"
+#include "tdunes_sens.hpp"
 
 }  // namespace tqd
 using namespace tqd;
@@ -1993,6 +1994,15 @@ struct tqgpu_solver {
      * r0 (sum_nu)] in one device block, the nodes' stages behind it as ints; trk_t0: the window the device's q, r were last folded for (-1: none yet) */
     double *d_trk = nullptr;
     int trk_T = 0, trk_nxt = 0, trk_nut = 0, trk_t0 = -1;
+    /* tqgpu_mpc_sensitivity: buffers of its own (setup_sens, on first use; one device block, views in `sens`); pinned h_sens:
+     * [head: K (nu0 x nx0) | u0 (nu0) | x0_ref (nx0) | n_reg] [x0_new (nx0)] [u0_pred (nu0) | n_clipped]; sens_valid: the stored sensitivity
+     * belongs to the point and the data the device holds now (cleared by every upload, fold, window move and solve) */
+    double *d_sens = nullptr, *h_sens = nullptr;
+    Sens sens{};
+    int sens_nx0 = 0;
+    bool sens_valid = false;
+    bool sens_dirty = false;            /* the problem was changed (upload, fold, window move) since the last solve: its point and the data no longer belong together */
+    size_t lds_sens_factor = 0, lds_sens_primal = 0;
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -3787,7 +3797,7 @@ extern "C" int tqgpu_set_dynamics(tqgpu_solver *s, const double *A, const double
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
-    s->in_valid = false;
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;
     H2D(s->A + s->A_pad, A, s->sum_A - s->A_pad); H2D(s->B, B, s->sum_B);
     H2D(s->b + s->nx0, b, s->sum_lam);              /* node-indexed on the device: root slot unused */
     HIP_TRY(hipStreamSynchronize(s->stream));       /* the caller may reuse its buffers */
@@ -3799,7 +3809,7 @@ extern "C" int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
-    s->in_valid = false;
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;
     H2D(s->Qd + s->x_pad, Qd, s->sum_nx - s->x_pad); H2D(s->Rd, Rd, s->sum_nu); H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->need_init = true;
@@ -3814,7 +3824,7 @@ extern "C" int tqgpu_set_linear_terms(tqgpu_solver *s, const double *q, const do
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "tqgpu_set_linear_terms: null solver");
     HIP_TRY(hipSetDevice(s->device));
-    s->in_valid = false;
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;
     H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->need_pack = true;
@@ -3978,7 +3988,7 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
         }
         oq += (size_t)nx * nx; orr += (size_t)nu * nu; os += (size_t)nu * nx;
     }
-    s->in_valid = false;
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;
     H2D(s->d_Hd, H.data(), s->poff[s->Nn]);
     HIP_TRY(hipMemcpyAsync(s->d_kind, s->h_kind.data(), sizeof(int) * (size_t)s->Nn, hipMemcpyHostToDevice, s->stream));      /* ints: not H2D (doubles) */
     H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
@@ -3997,7 +4007,7 @@ extern "C" int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const doubl
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
-    s->in_valid = false;
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;
     if (xmin && xmax && umin && umax) {
         /* keep what the box nodes' checks need (lb <= ub); refuse before anything is uploaded */
         std::vector<double> hb((size_t)2 * s->sum_nx + 2 * (size_t)s->sum_nu, 0.0);
@@ -4086,7 +4096,7 @@ extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const doubl
     }
     if (total > 0 && (nc || dmin || dmax)) HIP_TRY(hipMemcpy(s->d_drange, dr.data(), sizeof(double) * 2 * (size_t)total, hipMemcpyHostToDevice));
     s->h_drange.swap(dr);
-    s->export_valid = false;
+    s->export_valid = false; s->sens_valid = false; s->sens_dirty = true;
     return TQGPU_OK;
 }
 
@@ -4173,7 +4183,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     HIP_TRY(hipSetDevice(s->device));
-    if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; s->in_valid = false; s->need_init = true; s->need_pack = true; }
+    if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; s->in_valid = false; s->sens_valid = false; s->sens_dirty = true; s->need_init = true; s->need_pack = true; }
     if (xmin || xmax || umin || umax) s->h_bounds.clear();           /* (the checks of the box nodes' bounds see them through tqgpu_set_bounds only) */
     char *slab = static_cast<char *>(s->slab);
     bool any_pack = false, any_init = false;
@@ -4185,6 +4195,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
         memcpy(mir, src, bytes);
         HIP_TRY(hipMemcpyAsync(dev, mir, bytes, hipMemcpyHostToDevice, s->stream));
         s->stream_pending = true;
+        s->sens_valid = false; s->sens_dirty = true;
         any_pack |= pack; any_init |= init;
         return TQGPU_OK;
     };
@@ -4354,6 +4365,7 @@ int grow_events(std::vector<hipEvent_t> &v, int n) {
 int prepare_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, bool in_batch_launch) {
     HIP_TRY(hipSetDevice(s->device));
     s->export_valid = false;
+    s->sens_valid = false; s->sens_dirty = false;          /* a stored sensitivity belongs to the point of the solve before this one; point and data belong together again */
     if (opts_from(o, cx.O) != TQGPU_OK) return TQGPU_EINVAL;
     cx.O.stamps = cx.env.stamps;
 
@@ -5257,7 +5269,7 @@ int mpc_take_window(tqgpu_solver *s, int t0, bool commit, const char *who) {
     if (s->mpc_S0 && root_kind_of(s) == 0) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 0 after tqgpu_mpc_set_root gave it an S0");
     if (!commit) return TQGPU_OK;
     s->trk_t0 = t0;
-    s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes q, r */
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;                    /* the pinned mirror of tqgpu_set_problem no longer describes q, r */
     return TQGPU_OK;                        /* need_pack stays as it is: the fold writes the packed copy itself, a pending pack reads Data */
 }
 
@@ -5269,7 +5281,7 @@ int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
         if (!x0) return TQGPU_OK;
         const size_t n0 = (size_t)s->mpc_nx0;
         memcpy(s->h_mpc, x0, sizeof(double) * n0);
-        s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes xmin, xmax */
+        s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;                    /* the pinned mirror of tqgpu_set_problem no longer describes xmin, xmax */
         if (!s->h_bounds.empty()) {             /* what the box nodes' checks see (tqgpu_set_bounds) */
             std::copy(x0, x0 + n0, s->h_bounds.begin());
             std::copy(x0, x0 + n0, s->h_bounds.begin() + s->sum_nx);
@@ -5283,7 +5295,7 @@ int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
         return fail(TQGPU_EINVAL, std::string(who) + ": S0 of tqgpu_mpc_set_root has " + std::to_string(s->mpc_nx0) + " columns, the trajectory of tqgpu_mpc_set_tracking " + std::to_string(s->trk_nxt) + " states");
     if (!x0) return TQGPU_OK;
     memcpy(s->h_mpc, x0, sizeof(double) * (size_t)s->mpc_nx0);
-    s->in_valid = false;                    /* the pinned mirror of tqgpu_set_problem no longer describes b (and r) */
+    s->in_valid = false; s->sens_valid = false; s->sens_dirty = true;                    /* the pinned mirror of tqgpu_set_problem no longer describes b (and r) */
     if (s->mpc_S0) s->need_pack = true;     /* the persistent route packs r with the bounds (k_pack_persist); b and the rows of kind 3 are read in place */
     return TQGPU_OK;
 }
@@ -5353,7 +5365,7 @@ extern "C" int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, co
     if (C0) { memcpy(p, C0, sizeof(double) * nc * n0); p += nc * n0; memcpy(p, dmin0, sizeof(double) * nc); p += nc; memcpy(p, dmax0, sizeof(double) * nc); }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the block that is replaced */
-    s->mem.release(s->d_mpc); s->mem.release(s->h_mpc);
+    s->mem.release(s->d_mpc); s->mem.release(s->h_mpc); s->sens_valid = false;
     s->mpc_nx0 = 0;
     if ((rc = s->mem.upload(s->d_mpc, blk.data(), sizeof(double) * blk.size(), TQGPU_ENOMEM, "the root terms")) ||
         (rc = s->mem.host(s->h_mpc, sizeof(double) * (n0 + nu0 + 2), "the pinned x0 and u0")))
@@ -5373,7 +5385,7 @@ extern "C" int tqgpu_mpc_set_root_states(tqgpu_solver *s) {
     const size_t nu0 = (size_t)s->nu[0];
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the pinned block that is replaced */
-    s->mem.release(s->d_mpc); s->mem.release(s->h_mpc);
+    s->mem.release(s->d_mpc); s->mem.release(s->h_mpc); s->sens_valid = false;
     s->mpc_nx0 = 0; s->mpc_root_states = false;
     if ((rc = s->mem.host(s->h_mpc, sizeof(double) * ((size_t)n0 + nu0 + 2), "the pinned x0 and u0"))) return rc;
     memset(s->h_mpc, 0, sizeof(double) * ((size_t)n0 + nu0 + 2));
@@ -5928,6 +5940,164 @@ extern "C" int tqgpu_mpc_stats(int *launches, int *copies, int *waits) {
     if (launches) *launches = st.launches;
     if (copies) *copies = st.copies;
     if (waits) *waits = st.waits;
+    return TQGPU_OK;
+}
+
+/* ---- parametric sensitivities of an MPC step (tdunes_sens.hpp): du0/dx0, dz/dx0, dlam/dx0 at the point of the last solve ---- */
+namespace {
+size_t sens_head_doubles(const tqgpu_solver *s) { return (size_t)s->nu[0] * s->sens_nx0 + (size_t)s->nu[0] + (size_t)s->sens_nx0 + 1; }
+
+/* the feature's buffers, on first use and again when nx0 changed: one zeroed device block, the pinned block, the LDS windows */
+int setup_sens(tqgpu_solver *s) {
+    int rc;
+    const size_t nx0 = (size_t)s->mpc_nx0, nu0 = (size_t)s->nu[0], snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu;
+    size_t lf = 0, lp = 0;
+    for (int k = 0; k < s->Nn; k++) {
+        lp = std::max(lp, ((size_t)(s->nx[k] + s->nu[k]) * nx0 + 2) * sizeof(double));
+        if (k < s->Np) {
+            const size_t d = (size_t)s->bdim[k], R = d + (k > 0 ? (size_t)s->nx[k] : nx0), ld = R | 1;
+            lf = std::max(lf, (ld * d + d + 2) * sizeof(double));
+        }
+    }
+    if (lf > 160 * 1024 || lp > 160 * 1024)
+        return fail(TQGPU_EUNSUPPORTED, "tqgpu_mpc_sensitivity: the tall root block [W; G'] (or a node's nz x nx0 window) does not fit 160 KiB of LDS");
+    if (s->d_sens && s->sens_nx0 == s->mpc_nx0) return TQGPU_OK;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->mem.release(s->d_sens); s->mem.release(s->h_sens);
+    s->sens_valid = false; s->sens_nx0 = 0;
+    size_t off = 0;
+    auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
+    const size_t oW = take(s->sum_W), oUt = take(s->sum_Ut), oCW = take(s->sum_W), oCUt = take(s->sum_Ut), oiv = take(snx), oPx = take(snx), oPu = take(snu);
+    const size_t oG = take((size_t)s->bdim[0] * nx0), odl = take(snx * nx0), odx = take(snx * nx0), odu = take(snu * nx0);
+    const size_t head = nu0 * nx0 + nu0 + nx0 + 1, oh = take(head), onr = take(2);
+    if ((rc = s->mem.zeroed(s->d_sens, sizeof(double) * std::max<size_t>(off, 2), TQGPU_ENOMEM, "the sensitivities")) ||
+        (rc = s->mem.host(s->h_sens, sizeof(double) * (head + nx0 + nu0 + 2), "the pinned gain")))
+        return rc;
+    memset(s->h_sens, 0, sizeof(double) * (head + nx0 + nu0 + 2));
+    if ((rc = allow_lds(k_sens_hess, s->lds_hess)) || (rc = allow_lds(k_sens_factor, lf)) || (rc = allow_lds(k_sens_forward, s->lds_forward)) || (rc = allow_lds(k_sens_primal, lp)))
+        return rc;
+    Sens &S = s->sens;
+    S = Sens{};
+    double *p = s->d_sens;
+    S.W = p + oW; S.Ut = p + oUt; S.CholW = p + oCW; S.CholUt = p + oCUt; S.invd = p + oiv; S.Px = p + oPx; S.Pu = p + oPu;
+    S.G = p + oG; S.dlam = p + odl; S.dx = p + odx; S.du = p + odu; S.head = p + oh; S.n_reg = reinterpret_cast<int *>(p + onr);
+    S.nx0 = s->mpc_nx0; S.xpad = s->x_pad; S.sum_nx = s->sum_nx; S.sum_nu = s->sum_nu; S.nu0 = s->nu[0];
+    s->sens_nx0 = s->mpc_nx0; s->lds_sens_factor = lf; s->lds_sens_primal = lp;
+    return TQGPU_OK;
+}
+int sens_need(const tqgpu_solver *s, const char *who) {
+    if (!s->sens_valid) return fail(TQGPU_EINVAL, std::string(who) + ": no sensitivity has been computed for the point and the data the device holds now (tqgpu_mpc_sensitivity after the last solve, upload and fold)");
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *n_reg) {
+    const char *who = "tqgpu_mpc_sensitivity";
+    int rc;
+    if ((rc = mpc_refuse(s, who))) return rc;
+    if (!o) return fail(TQGPU_EINVAL, std::string(who) + ": opts is required (the regularisation rule of the factorisation)");
+    if ((rc = mpc_take_x0(s, nullptr, who))) return rc;          /* no root form declared yet, and what a fold would refuse */
+    if (s->solve_no == 0) return fail(TQGPU_EINVAL, std::string(who) + ": this mirror has not solved yet: there is no point to differentiate at");
+    if (s->sens_dirty)
+        return fail(TQGPU_EINVAL, std::string(who) + ": the problem was changed (an upload, an x0 fold or a window move) since the last solve: its point does not belong to the data the device holds now; solve first");
+    if (s->dense) for (int k : s->h_kind) if (k >= 2)
+        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the tree has nodes of kind 2 or 3: Pd need not belong to the final working set after a line search's last trial");
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    if ((rc = setup_sens(s))) return rc;
+    s->sens_valid = false;
+    if (!s->export_valid) {
+        if ((rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
+        MPC_COUNT(launches, 1);
+    }
+    Sens S = s->sens;
+    S.x = s->d_out; S.u = S.x + (s->sum_nx - s->x_pad);
+    S.root_states = s->mpc_root_states ? 1 : 0;
+    if (s->d_mpc) { S.A0 = s->d_mpc; S.S0 = s->mpc_S0 ? s->d_mpc + (size_t)s->mpc_nb * s->mpc_nx0 + s->mpc_nb : nullptr; }
+    S.x0 = s->h_mpc;
+    const Tree &T = s->T;
+    hipStream_t st = s->stream;
+    hipLaunchKernelGGL(k_sens_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, st, T, s->D, S);
+    for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
+        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
+        hipLaunchKernelGGL(k_sens_factor, dim3(count), dim3(WAVE), s->lds_sens_factor, st, T, O, S, first);
+    }
+    for (int lvl = 1; lvl < T.Nh; lvl++) {
+        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
+        hipLaunchKernelGGL(k_sens_forward, dim3(count, (unsigned)s->sens_nx0), dim3(WAVE), s->lds_forward, st, T, S, first);
+    }
+    hipLaunchKernelGGL(k_sens_primal, dim3(T.Nn), dim3(WAVE), s->lds_sens_primal, st, T, s->D, S);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1 + T.Nh + (T.Nh - 1) + 1);
+    const size_t head = sens_head_doubles(s);
+    HIP_TRY(hipMemcpyAsync(s->h_sens, S.head, sizeof(double) * head, hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
+    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
+    s->sens = S;
+    s->sens_valid = true;
+    if (n_reg) *n_reg = (int)s->h_sens[head - 1];
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_gain(tqgpu_solver *s, double *K, double *u0, double *x0_ref) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_gain")) || (rc = sens_need(s, "tqgpu_mpc_get_gain"))) return rc;
+    const size_t nu0 = (size_t)s->nu[0], nx0 = (size_t)s->sens_nx0;
+    if (K && nu0 * nx0) memcpy(K, s->h_sens, sizeof(double) * nu0 * nx0);
+    if (u0 && nu0) memcpy(u0, s->h_sens + nu0 * nx0, sizeof(double) * nu0);
+    if (x0_ref && nx0) memcpy(x0_ref, s->h_sens + nu0 * nx0 + nu0, sizeof(double) * nx0);
+    return TQGPU_OK;
+}
+
+/* a diagnostic download (whole buffers through pageable memory, repacked on the host): not part of a step, not counted into tqgpu_mpc_stats */
+extern "C" int tqgpu_mpc_get_sensitivities(tqgpu_solver *s, double *dx, double *du, double *dlam) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_sensitivities")) || (rc = sens_need(s, "tqgpu_mpc_get_sensitivities"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t nx0 = (size_t)s->sens_nx0, snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, nl = (size_t)s->sum_lam;
+    std::vector<double> tmp(std::max(snx, snu) * nx0 + 1);
+    if (dx || dlam) {
+        for (int which = 0; which < 2; which++) {
+            double *out = which ? dlam : dx;
+            if (!out) continue;
+            HIP_TRY(hipMemcpy(tmp.data(), which ? s->sens.dlam : s->sens.dx, sizeof(double) * snx * nx0, hipMemcpyDeviceToHost));
+            const size_t skip = which ? (size_t)s->nx0 : (size_t)s->x_pad, n = which ? nl : nxe;      /* the root has no dual; phantom root states are left out */
+            for (size_t j = 0; j < nx0; j++) if (n) memcpy(out + j * n, tmp.data() + j * snx + skip, sizeof(double) * n);
+        }
+    }
+    if (du && snu * nx0) HIP_TRY(hipMemcpy(du, s->sens.du, sizeof(double) * snu * nx0, hipMemcpyDeviceToHost));
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, int duals, int *n_clipped) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_predict")) || (rc = sens_need(s, "tqgpu_mpc_predict"))) return rc;
+    if (!x0_new) return fail(TQGPU_EINVAL, "tqgpu_mpc_predict: x0_new is required");
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    const size_t nu0 = (size_t)s->nu[0], nx0 = (size_t)s->sens_nx0, head = sens_head_doubles(s);
+    double *x0n = s->h_sens + head, *out = x0n + nx0;
+    memcpy(x0n, x0_new, sizeof(double) * nx0);
+    /* the predicted duals take the start buffer for ONE solve, as the shifted ones of tqgpu_mpc_shift do: in mode 0 the kernel saves the
+     * caller's buffer (once) and the solve after the next puts it back (solve_begin) */
+    const bool lend = duals && s->warm_mode == 0;
+    if (lend && !s->d_lam_keep && (rc = s->mem.zeroed(s->d_lam_keep, sizeof(double) * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the saved start buffer"))) return rc;
+    double *keep = lend && s->shift_restore == 0 ? s->d_lam_keep : nullptr;
+    hipLaunchKernelGGL(k_mpc_predict, dim3(duals ? 1 + (unsigned)s->Nn : 1u), dim3(WAVE), 0, s->stream, s->T, s->D, s->sens, (const double *)x0n, s->d_lam_init, keep, out);
+    HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
+    if (duals) {
+        if (lend) s->shift_restore = 1;
+        s->warm_fresh = true;          /* the next solve starts from the start buffer as it is now, in any mode */
+        s->lam_valid = false;
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream)); MPC_COUNT(waits, 1);
+    if (u0_pred && nu0) memcpy(u0_pred, out, sizeof(double) * nu0);
+    if (n_clipped) *n_clipped = (int)out[nu0];
     return TQGPU_OK;
 }
 

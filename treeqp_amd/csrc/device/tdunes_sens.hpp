@@ -1,0 +1,371 @@
+/*
+ * tdunes_sens.hpp -- parametric sensitivities of an MPC step: d(x, u, lam) / d x0 at the point of the last solve, active set frozen.
+ *
+ * Included by tdunes_device.hip; the kernels are written after hess_body, factor_body and forward_body (same tall Cholesky, same
+ * substitutions, same WSYNC discipline), with nx0 right-hand sides instead of one.  One wave per unit on a private LDS window, one
+ * launch per phase and block level; no kernel waits for another workgroup: the launch boundaries on the mirror's stream order them.
+ *
+ *   M dLam = G,   M = the dual Hessian hess_body builds (W_p, Ut_p) with the elimination matrices P_k of the exported point,
+ *                 G = d res / d x0 at fixed lam: rows of the root's children only,
+ *                     eliminated root:  G_c = A0_c - B_c P_0 S0 (second term where S0 was given);   root with states:  G_c = A_c
+ *   dZ_k = P_k ( [dLam_k; 0] - sum_c C_c' dLam_c ) + direct_k,   direct_0 = -P_0 [0; S0] (eliminated root), [I; 0] (root with states)
+ *   K = the u rows of dZ_0.
+ *
+ * P_k: kind 0 diagonal, 1 / Qd_i (1 / Rd_i) where the exported value is strictly inside its bounds, 0.0 where it equals a bound bit for
+ * bit (clipping assigns the bound itself), phantom root states free; kind 1: Data::Pd.  Everything is written into the feature's own
+ * buffers (struct Sens); Data is only read.
+ */
+#pragma once
+
+struct Sens {
+    const double *x, *u;               /* the export block: x (phantom root states excluded), u */
+    double *W, *Ut, *CholW, *CholUt;   /* as Data::W .. of the solver, laid out by Tree::woff / utoff */
+    double *invd;                      /* reciprocal pivots, node-indexed as Data::invd */
+    double *Px, *Pu;                   /* the diagonal P of kind-0 nodes, node-indexed as Data::x / Data::u */
+    double *G;                         /* bdim[0] x nx0, column major */
+    double *dlam, *dx, *du;            /* sum_nx x nx0, sum_nx x nx0, sum_nu x nx0, column major, node-indexed (phantom root states included) */
+    double *head;                      /* [K (nu0 x nx0, column major) | u0 (nu0) | x0_ref (nx0) | n_reg] */
+    int *n_reg;
+    const double *A0, *S0;             /* the originals of an eliminated root (S0: nullptr = zero) */
+    const double *x0;                  /* pinned: the x0 last folded (eliminated root) */
+    int nx0, xpad, root_states, sum_nx, sum_nu, nu0;
+};
+
+__device__ __forceinline__ int sens_kind(const Data &D, int k) { return D.dense ? D.kind[k] : 0; }
+/* entry i of the diagonal P of kind-0 node k, i over [x | u] */
+__device__ __forceinline__ double sens_pdiag(const Tree &T, const Data &D, const Sens &S, int k, int i) {
+    const int nx = T.nx[k], pad = k == 0 ? S.xpad : 0;
+    if (i < nx) {
+        const int g = T.xoff[k] + i;
+        if (i < pad) return 1.0 / D.Qd[g];
+        const double v = S.x[g - S.xpad];
+        return (v == D.xmin[g] || v == D.xmax[g]) ? 0.0 : 1.0 / D.Qd[g];
+    }
+    const int g = T.uoff[k] + i - nx;
+    const double v = S.u[g];
+    return (v == D.umin[g] || v == D.umax[g]) ? 0.0 : 1.0 / D.Rd[g];
+}
+
+/* ---- k_sens_hess: one wave per parent block p: W_p, Ut_p as hess_body builds them, the diagonal P of p's kind-0 children (and of the
+ * root), and from the root's block G ---- */
+__device__ void sens_hess_body(const Tree &T, const Data &D, const Sens &S, int p, int lane, double *lds) {
+    const int d = T.bdim[p], nxp = T.nx[p], nup = T.nu[p], nz = nxp + nup;
+    double *Cs = lds;                 /* d x nz, column major, ld = d */
+    double *CP = lds + (size_t)d * nz;
+    const int k0 = T.kid0[p];
+    const bool pdense = sens_kind(D, p) != 0;
+    if (p == 0 && lane == 0) *S.n_reg = 0;
+    /* the diagonal P of the kind-0 nodes this block owns: its children, and the root itself */
+    for (int cc = (p == 0 ? -1 : 0); cc < T.nk[p]; cc++) {
+        const int k = cc < 0 ? 0 : k0 + cc;
+        if (sens_kind(D, k)) continue;
+        const int nxk = T.nx[k], nzk = nxk + T.nu[k];
+        for (int i = lane; i < nzk; i += WAVE) {
+            const double pv = sens_pdiag(T, D, S, k, i);
+            if (i < nxk) S.Px[T.xoff[k] + i] = pv; else S.Pu[T.uoff[k] + i - nxk] = pv;
+        }
+    }
+    /* stage the children's [A B] rows */
+    int rowoff = 0;
+    for (int cc = 0; cc < T.nk[p]; cc++) {
+        const int kid = k0 + cc, nxc = T.nx[kid];
+        const double *A = D.A + T.aoff[kid], *B = D.B + T.boff[kid];
+        for (int e = lane; e < nxc * nz; e += WAVE) {
+            const int i = e % nxc, col = e / nxc;
+            const double a = col < nxp ? A[i + (size_t)col * nxc] : B[i + (size_t)(col - nxp) * nxc];
+            Cs[rowoff + i + (size_t)col * d] = a;
+            if (!pdense) CP[rowoff + i + (size_t)col * d] = a * sens_pdiag(T, D, S, p, col);
+        }
+        rowoff += nxc;
+    }
+    WSYNC();
+    if (pdense) {
+        const double *P = D.Pd + D.poff[p];
+        for (int e = lane; e < d * nz; e += WAVE) {
+            const int i = e % d, col = e / d;
+            double acc = 0.0;
+            for (int cidx = 0; cidx < nz; cidx++) acc = fma(Cs[i + (size_t)cidx * d], P[cidx + (size_t)col * nz], acc);
+            CP[i + (size_t)col * d] = acc;
+        }
+        WSYNC();
+    }
+    double *W = S.W + T.woff[p];
+    for (int e = lane; e < d * d; e += WAVE) {
+        const int i = e % d, j = e / d;
+        if (i < j) continue;
+        double acc = 0.0, acc2 = 0.0;
+        for (int cidx = 0; cidx < nxp; cidx++) acc = fma(Cs[i + (size_t)cidx * d], CP[j + (size_t)cidx * d], acc);
+        for (int cidx = nxp; cidx < nz; cidx++) acc2 = fma(Cs[i + (size_t)cidx * d], CP[j + (size_t)cidx * d], acc2);
+        double w = acc + acc2;
+        /* the state block of the child's own elimination matrix on the diagonal block */
+        int ro = 0;
+        for (int cc = 0; cc < T.nk[p]; cc++) {
+            const int kid = k0 + cc, nxc = T.nx[kid];
+            if (i >= ro && i < ro + nxc && j >= ro && j < ro + nxc) {
+                if (sens_kind(D, kid)) { const int nzk = nxc + T.nu[kid]; w += D.Pd[D.poff[kid] + (i - ro) + (size_t)(j - ro) * nzk]; }
+                else if (i == j) w += sens_pdiag(T, D, S, kid, i - ro);
+            }
+            ro += nxc;
+        }
+        W[i + (size_t)j * d] = w;
+    }
+    if (p > 0) {
+        double *Ut = S.Ut + T.utoff[p];
+        for (int e = lane; e < nxp * d; e += WAVE) {
+            const int i = e % nxp, rr = e / nxp;
+            Ut[i + (size_t)rr * nxp] = -1.0 * CP[rr + (size_t)i * d];
+        }
+    } else {
+        /* G: A0 - (C P_0)[:, u] S0 for an eliminated root, the state columns of C for a root that keeps its states */
+        const int nx0 = S.nx0;
+        for (int e = lane; e < d * nx0; e += WAVE) {
+            const int i = e % d, j = e / d;
+            double g;
+            if (S.root_states) g = Cs[i + (size_t)(S.xpad + j) * d];
+            else {
+                /* A0 lies child after child, each nx[kid] x nx0: find row i's child */
+                int ro = 0, ao = 0, kid = k0;
+                for (; kid < k0 + T.nk[0]; kid++) { const int n = T.nx[kid]; if (i < ro + n) break; ro += n; ao += n * nx0; }
+                const int nxc = T.nx[kid];
+                g = S.A0[ao + (i - ro) + (size_t)j * nxc];
+                if (S.S0) {
+                    double acc = 0.0;
+                    for (int m = 0; m < nup; m++) acc = fma(CP[i + (size_t)(nxp + m) * d], S.S0[m + (size_t)j * nup], acc);
+                    g -= acc;
+                }
+            }
+            S.G[i + (size_t)j * d] = g;
+        }
+    }
+}
+
+/* ---- k_sens_factor: one wave per block of one level, deepest level first: tall Cholesky of [W; Ut] with factor_body's regularisation,
+ * the Schur complement into the parent's W through global memory; the root carries G' as nx0 extra rows: Y = (L^-1 G)', dLam_0 = L^-T Y ---- */
+__device__ void sens_factor_body(const Tree &T, const Opts &O, const Sens &S, int ii, int lane, double *lds) {
+    const int d = T.bdim[ii], nxi = ii > 0 ? T.nx[ii] : S.nx0;
+    const int R = d + nxi, ld = R | 1;
+    double *Tm = lds;                         /* ld x d */
+    double *invd = lds + (size_t)ld * d;      /* d */
+    const double *W = S.W + T.woff[ii];
+    const int bo = T.xoff[T.kid0[ii]];
+    const double *Ut = S.Ut + T.utoff[ii];
+
+    for (int pass = 0; pass < 2; pass++) {
+        for (int e = lane; e < d * d; e += WAVE) {
+            const int i = e % d, j = e / d;
+            double w = W[i + (size_t)j * d];
+            if (i == j && (O.regType == 1 || pass == 1)) w += O.regValue;
+            Tm[i + (size_t)j * ld] = w;
+        }
+        for (int e = lane; e < nxi * d; e += WAVE) {
+            const int i = e % nxi, j = e / nxi;
+            Tm[d + i + (size_t)j * ld] = ii > 0 ? Ut[i + (size_t)j * nxi] : S.G[j + (size_t)i * d];
+        }
+        WSYNC();
+        tall_potrf(Tm, invd, R, d, ld, lane);
+        if (O.regType != 2 || pass == 1) break;
+        int small = 0;
+        for (int j = lane; j < d; j += WAVE) small |= (Tm[j + (size_t)j * ld] <= O.regTol);
+        if (!__any(small)) break;
+        if (lane == 0) atomicAdd(S.n_reg, 1);
+        WSYNC();
+    }
+    double *L = S.CholW + T.woff[ii];
+    for (int e = lane; e < d * d; e += WAVE) {
+        const int i = e % d, j = e / d;
+        if (i >= j) L[i + (size_t)j * d] = Tm[i + (size_t)j * ld];
+    }
+    for (int j = lane; j < d; j += WAVE) S.invd[bo + j] = invd[j];
+    if (ii > 0) {
+        double *CUt = S.CholUt + T.utoff[ii];
+        for (int e = lane; e < nxi * d; e += WAVE) {
+            const int i = e % nxi, j = e / nxi;
+            CUt[i + (size_t)j * nxi] = Tm[d + i + (size_t)j * ld];
+        }
+        const int dd = T.dad[ii], pos = T.pos[ii], ddim = T.bdim[dd];
+        double *Wd = S.W + T.woff[dd];
+        for (int e = lane; e < nxi * nxi; e += WAVE) {
+            const int i = e % nxi, j = e / nxi;
+            if (i < j) continue;
+            double acc = 0.0;
+            for (int cidx = 0; cidx < d; cidx++) acc = fma(Tm[d + i + (size_t)cidx * ld], Tm[d + j + (size_t)cidx * ld], acc);
+            Wd[(pos + i) + (size_t)(pos + j) * ddim] -= acc;
+        }
+    } else {
+        /* all nx0 right-hand sides at once: column-oriented back substitution, k descending, (row, column) pairs over the lanes */
+        for (int k = d - 1; k >= 0; k--) {
+            WSYNC();
+            const double ivk = invd[k];
+            for (int e = lane; e < k * nxi; e += WAVE) {
+                const int i = e % k, j = e / k;
+                const double zk = Tm[d + j + (size_t)k * ld] * ivk;
+                Tm[d + j + (size_t)i * ld] = fma(-Tm[k + (size_t)i * ld], zk, Tm[d + j + (size_t)i * ld]);
+            }
+            WSYNC();
+            for (int j = lane; j < nxi; j += WAVE) Tm[d + j + (size_t)k * ld] *= ivk;
+        }
+        WSYNC();
+        for (int e = lane; e < d * nxi; e += WAVE) {
+            const int i = e % d, j = e / d;
+            S.dlam[bo + i + (size_t)j * S.sum_nx] = Tm[d + j + (size_t)i * ld];
+        }
+    }
+}
+
+/* ---- k_sens_forward: one wave per (block of one level, column j): dLam_ii = -L^-T CholUt' dLam_dad[pos ..], forward_body's substitution ---- */
+__device__ void sens_forward_body(const Tree &T, const Sens &S, int ii, int col, int lane, double *lds) {
+    const int d = T.bdim[ii], nxi = T.nx[ii], ld = d | 1;
+    double *L = lds;                      /* ld x d */
+    double *z = lds + (size_t)ld * d;     /* d */
+    double *dl = z + d;                   /* nxi */
+    double *iv = dl + nxi;                /* d */
+    const int bo = T.xoff[T.kid0[ii]], xo = T.xoff[ii];
+    const double *Lg = S.CholW + T.woff[ii];
+    double *dlam = S.dlam + (size_t)col * S.sum_nx;
+    for (int e = lane; e < d * d; e += WAVE) {
+        const int i = e % d, j = e / d;
+        if (i >= j) L[i + (size_t)j * ld] = Lg[i + (size_t)j * d];
+    }
+    for (int j = lane; j < d; j += WAVE) iv[j] = S.invd[bo + j];
+    for (int i = lane; i < nxi; i += WAVE) dl[i] = dlam[xo + i];
+    WSYNC();
+    const double *CUt = S.CholUt + T.utoff[ii];
+    for (int j = lane; j < d; j += WAVE) {
+        double acc = 0.0;
+        for (int i = 0; i < nxi; i++) acc = fma(CUt[i + (size_t)j * nxi], dl[i], acc);
+        z[j] = -acc;
+    }
+    for (int k = d - 1; k >= 0; k--) {
+        WSYNC();
+        const double zk = z[k] * iv[k];
+        for (int i = lane; i < k; i += WAVE) z[i] = fma(-L[k + (size_t)i * ld], zk, z[i]);
+        WSYNC();
+        if (lane == 0) z[k] = zk;
+    }
+    WSYNC();
+    for (int j = lane; j < d; j += WAVE) dlam[bo + j] = z[j];
+}
+
+/* ---- k_sens_primal: one wave per node: dZ_k = P_k ( [dLam_k; 0] - sum_c C_c' dLam_c ) + direct_k; node 0 also fills the head ---- */
+__device__ void sens_primal_body(const Tree &T, const Data &D, const Sens &S, int k, int lane, double *lds) {
+    const int nxk = T.nx[k], nuk = T.nu[k], nz = nxk + nuk, nx0 = S.nx0, pad = k == 0 ? S.xpad : 0;
+    const int xo = T.xoff[k], uo = T.uoff[k], k0 = T.kid0[k], nkids = k < T.Np ? T.nk[k] : 0;
+    double *v = lds;                      /* nz x nx0 */
+    for (int e = lane; e < nz * nx0; e += WAVE) {
+        const int i = e % nz, j = e / nz;
+        const double *dl = S.dlam + (size_t)j * S.sum_nx;
+        double acc = 0.0;
+        for (int cc = 0; cc < nkids; cc++) {
+            const int kid = k0 + cc, nxc = T.nx[kid];
+            const double *Cc = i < nxk ? D.A + T.aoff[kid] + (size_t)i * nxc : D.B + T.boff[kid] + (size_t)(i - nxk) * nxc;
+            const double *dc = dl + T.xoff[kid];
+            for (int r = 0; r < nxc; r++) acc = fma(Cc[r], dc[r], acc);
+        }
+        double w = (k > 0 && i < nxk ? dl[xo + i] : 0.0) - acc;
+        if (k == 0 && !S.root_states && S.S0 && i >= nxk) w -= S.S0[(i - nxk) + (size_t)j * nuk];
+        v[e] = w;
+    }
+    WSYNC();
+    const int kind = sens_kind(D, k);
+    for (int e = lane; e < nz * nx0; e += WAVE) {
+        const int i = e % nz, j = e / nz;
+        double r;
+        if (kind == 0) r = (i < nxk ? S.Px[xo + i] : S.Pu[uo + i - nxk]) * v[e];
+        else {
+            const double *P = D.Pd + D.poff[k];
+            r = 0.0;
+            for (int m = 0; m < nz; m++) r = fma(P[i + (size_t)m * nz], v[m + (size_t)j * nz], r);
+        }
+        if (k == 0 && S.root_states && i < nxk) r += (i - pad == j) ? 1.0 : 0.0;
+        if (i < nxk) S.dx[xo + i + (size_t)j * S.sum_nx] = r;
+        else {
+            S.du[uo + i - nxk + (size_t)j * S.sum_nu] = r;
+            if (k == 0) S.head[(i - nxk) + (size_t)j * nuk] = r;
+        }
+    }
+    if (k == 0) {
+        double *h = S.head + (size_t)nuk * nx0;
+        for (int i = lane; i < nuk; i += WAVE) h[i] = S.u[i];
+        for (int j = lane; j < nx0; j += WAVE) h[nuk + j] = S.root_states ? D.xmin[pad + j] : S.x0[j];
+        if (lane == 0) h[nuk + nx0] = (double)*S.n_reg;
+    }
+}
+
+/* ---- k_mpc_predict: block 0: u0_pred[i] = u0[i], then fma(K[i, j], dx_j, .) over j ascending, dx_j = x0_new[j] - x0_ref[j], clipped into
+ * [umin[0], umax[0]] on a root of kind 0; blocks 1 + k (duals != 0): entry e of node k of the start buffer = the current dual, then
+ * fma(dLam[e, j], dx_j, .) over j ascending (lam_keep: the entry it replaces is saved first).  out: pinned, [u0_pred (nu0) | n_clipped] ---- */
+__device__ void sens_predict_body(const Tree &T, const Data &D, const Sens &S, const double *x0_new, double *lam_init, double *lam_keep, double *out, int blk, int lane) {
+    const int nx0 = S.nx0, nu0 = S.nu0;
+    const double *h = S.head, *x0r = h + (size_t)nu0 * nx0 + nu0;
+    if (blk == 0) {
+        const bool clip = sens_kind(D, 0) == 0;
+        int moved = 0;
+        for (int i0 = 0; i0 < nu0; i0 += WAVE) {
+            const int i = i0 + lane;
+            bool mv = false;
+            if (i < nu0) {
+                double w = h[(size_t)nu0 * nx0 + i];
+                for (int j = 0; j < nx0; j++) w = fma(h[i + (size_t)j * nu0], x0_new[j] - x0r[j], w);
+                if (clip) {
+                    const double lo = D.umin[i], hi = D.umax[i];
+                    if (w < lo) { w = lo; mv = true; } else if (w > hi) { w = hi; mv = true; }
+                }
+                out[i] = w;
+            }
+            moved += __popcll(__builtin_amdgcn_ballot_w64(mv));
+        }
+        if (lane == 0) out[nu0] = (double)moved;
+        return;
+    }
+    const int k = blk - 1, xo = T.xoff[k];
+    const double *src = D.ctrl->cur ? D.lam1 : D.lam0;
+    for (int e = lane; e < T.nx[k]; e += WAVE) {
+        double w = src[xo + e];
+        for (int j = 0; j < nx0; j++) w = fma(S.dlam[xo + e + (size_t)j * S.sum_nx], x0_new[j] - x0r[j], w);
+        if (lam_keep) lam_keep[xo + e] = lam_init[xo + e];
+        lam_init[xo + e] = w;
+    }
+}
+
+__global__ void __launch_bounds__(WAVE) k_sens_hess(Tree T, Data D, Sens S)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    sens_hess_body(T, D, S, blockIdx.x, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_sens_factor(Tree T, Opts O, Sens S, int first)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    sens_factor_body(T, O, S, first + (int)blockIdx.x, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_sens_forward(Tree T, Sens S, int first)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    sens_forward_body(T, S, first + (int)blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_sens_primal(Tree T, Data D, Sens S)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    sens_primal_body(T, D, S, blockIdx.x, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_mpc_predict(Tree T, Data D, Sens S, const double *x0_new, double *lam_init, double *lam_keep, double *out)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{ sens_predict_body(T, D, S, x0_new, lam_init, lam_keep, out, blockIdx.x, threadIdx.x); }
+#endif
