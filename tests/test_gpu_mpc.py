@@ -322,7 +322,81 @@ def test_single_step_cost_on_the_persistent_route(capi):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# 7. refusals
+# 7. the routes into k_mpc_pre, two by two: a step that does it all in its one launch, and the same state reached through the call
+#    that does one part alone
+# ---------------------------------------------------------------------------------------------------------------------------------
+# what the commit before the shared launcher counted on this tree (one launch of one workgroup per solve): of a step, k_mpc_pre + the
+# solve + the post of u0 and no copy -- whatever k_mpc_pre has to do, and nothing for a tqgpu_mpc_set_x0, _set_window or _shift ahead
+# of it, which are no steps; of a tqgpu_solve in warm start mode 1, the solve and its own warm-start copy
+PRE_STEP = dict(launches=3, copies=0)
+PRE_STEP_N_LAUNCHES = 1
+PRE_SOLVE_N_LAUNCHES = 2
+
+
+def _pre_pair(what, ra, ua, rb, ub, stats_a, stats_b, launches_b):
+    print(f"{what}: step {[ra[k] for k in COUNTS]} launches {ra['n_launches']} stats {stats_a}; other route {[rb[k] for k in COUNTS]} "
+          f"launches {rb['n_launches']} stats {stats_b}")
+    for k in COUNTS:
+        assert ra[k] == rb[k], f"{what}: {k} {ra[k]} != {rb[k]}"
+    assert ra["status"] == 0
+    _same_bits(ua, ub, f"{what}: u0")
+    for st in (stats_a, stats_b):
+        assert {k: st[k] for k in PRE_STEP} == PRE_STEP, f"{what}: {st}"
+    assert ra["n_launches"] == PRE_STEP_N_LAUNCHES and rb["n_launches"] == launches_b
+
+
+def test_routes_into_the_pre_kernel_agree(capi):
+    import tracking_cases as T
+    c = M.case("one_child")
+    xs = M.exact_x0s(c["nx0"], 3)
+    made = []
+
+    def pair(make, mode_a, mode_b):
+        a, b = make(), make()
+        made.extend([a, b])
+        assert a.path == 3
+        a.set_warm_start(mode_a); b.set_warm_start(mode_b)
+        return a, b
+    try:
+        # fold + warm start in a step's launch | tqgpu_mpc_set_x0, then the warm-start copy of tqgpu_solve's solve_begin
+        a, b = pair(lambda: M.make(capi, c), 1, 1)
+        for g in (a, b):
+            g.mpc_step(xs[0], **c["opts"])
+        ra, ua = a.mpc_step(xs[1], **c["opts"])
+        st = capi.mpc_stats()
+        b.mpc_set_x0(xs[1])
+        rb = b.solve(**c["opts"])
+        _pre_pair("warm start", ra, ua, rb, _u0(b.solution(), c), st, capi.mpc_stats(), PRE_SOLVE_N_LAUNCHES)          # (the record stays the step's: b counted nothing)
+
+        # the shifted warm start of mode 2 in a step's launch | tqgpu_mpc_shift of a mirror in mode 0, then a step that only folds
+        a, b = pair(lambda: M.make(capi, c).mpc_set_shift(), 2, 0)
+        for g in (a, b):
+            g.mpc_step(xs[0], **c["opts"])
+        ra, ua = a.mpc_step(xs[1], **c["opts"])
+        st = capi.mpc_stats()
+        b.mpc_shift()
+        rb, ub = b.mpc_step(xs[1], **c["opts"])
+        _pre_pair("shift", ra, ua, rb, ub, st, capi.mpc_stats(), PRE_STEP_N_LAUNCHES)
+
+        # the window fold in a step's launch (tqgpu_mpc_step_at) | tqgpu_mpc_set_window, then a step that keeps the window.  A reference
+        # trajectory needs one nx below the root: the same tree with nx = 3 on every node
+        ct = T._elim("one_child_nx3", H.shaped_qp([1, 2, 0, 0], [0, 3, 3, 3], 2, 21).as_dict(), M.NX0, 5, True)
+        a, b = pair(lambda: T.make(capi, ct), 1, 1)
+        for g in (a, b):
+            g.mpc_step(xs[0], t0=0, **ct["opts"])
+        ra, ua = a.mpc_step(xs[1], t0=2, **ct["opts"])
+        st = capi.mpc_stats()
+        b.mpc_set_window(2)
+        rb, ub = b.mpc_step(xs[1], **ct["opts"])
+        assert a.mpc_window == 2 == b.mpc_window
+        _pre_pair("window", ra, ua, rb, ub, st, capi.mpc_stats(), PRE_STEP_N_LAUNCHES)
+    finally:
+        for g in made:
+            g.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 8. refusals
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _refused(capi, rc, code, text):
     assert rc == code, f"{rc} != {code}: {capi.lib().tqgpu_last_error().decode()}"
