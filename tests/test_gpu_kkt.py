@@ -20,6 +20,7 @@ import pytest
 import gen_cases as GC
 import kkt_ref as K
 import limit_shapes as LS
+import mpc_root_cases as R
 from helpers import product_qp_from_lti, with_dense_blocks
 from limit_shapes import leaf
 from treeqp_amd import problems as P
@@ -260,6 +261,93 @@ def test_the_check_leaves_the_solver_alone(gpu):
         assert np.array_equal(sa2[k], sb2[k]), f"second solve: {k}"
     assert np.array_equal(sta["last"], stb["last"]) and np.array_equal(sta["total"], stb["total"])
     a.close(); b.close()
+
+
+# ---- the export state: every route to tqgpu_get_solution gives the same bits ----
+
+def _thesis(gpu):
+    return _clip_mirror(gpu, P.thesis_example().as_dict()), {}
+
+
+def _kinds_two_and_three(gpu):
+    d, kinds = _mixed_problem()
+    g = _dense_mirror(gpu, d, kinds)
+    assert g.plan["gen"] and g.plan["box"]
+    return g, FULL
+
+
+def _x0_eliminated(gpu):
+    p = P.linear_chain(2, 2, 2, nm=1, nu=1)
+    g = _clip_mirror(gpu, product_qp_from_lti(gpu, p, eliminate_x0=True).flat())
+    assert g.path == 2 and g.sum_nx == 12          # embedded with phantom root states, the single persistent launch
+    return g, {}
+
+
+@pytest.mark.parametrize("make", [_thesis, _kinds_two_and_three, _x0_eliminated], ids=lambda f: f.__name__.strip("_"))
+def test_every_route_of_the_export_state_gives_the_same_solution(gpu, monkeypatch, make):
+    """One solve with the same options on fresh mirrors, then tqgpu_get_solution behind: nothing, tqgpu_set_export_ahead (a no-op off
+    the single persistent launch), tqgpu_kkt_residual, tqgpu_kkt_residual_batch of the mirror and a twin on the batched route and
+    member by member, and a second tqgpu_get_solution.  No arithmetic differs between them: every comparison is exact."""
+    def solved(ahead=False):
+        g, opts = make(gpu)
+        if ahead:
+            g.export_ahead(True)
+        r = g.solve(**opts)
+        return g, (r["status"], r["iter"], r["ls_total"])
+
+    sols, kkts, keys = {}, {}, {}
+    g, keys["plain"] = solved()
+    sols["plain"] = g.solution()
+    sols["a second tqgpu_get_solution"] = g.solution()
+    g.close()
+    g, keys["export ahead"] = solved(ahead=True)
+    sols["export ahead"] = g.solution()
+    g.close()
+    g, keys["kkt_residual first"] = solved()
+    kkts["single"] = g.kkt_residual()
+    sols["kkt_residual first"] = g.solution()
+    g.close()
+    for route, batched in (("batched", 2), ("members", 0)):
+        if route == "members":
+            monkeypatch.setenv("TREEQP_AMD_KKT_BATCH", "members")
+        (g, keys[route]), (twin, keys[route + " twin"]) = solved(), solved()
+        kkts[route], kkts[route + " twin"] = gpu.kkt_residual_batch([g, twin])
+        assert gpu.kkt_batch_stats()["batched_members"] == batched, gpu.kkt_batch_stats()
+        sols["kkt_residual_batch first, " + route] = g.solution()
+        g.close(); twin.close()
+    print(keys["plain"], kkts["single"])
+    assert len(set(keys.values())) == 1, keys
+    for what, s in sols.items():
+        for k in ("x", "u", "lam", "mu_x", "mu_u", "dlam"):
+            assert np.all(np.isfinite(s[k])), f"{what}: {k} is not finite"
+            assert np.array_equal(s[k], sols["plain"][k]), f"{what}: {k} differs from a plain tqgpu_get_solution"
+    for what, k in kkts.items():
+        assert np.array_equal(k["res"], kkts["single"]["res"]) and np.array_equal(k["node"], kkts["single"]["node"]), (what, k, kkts["single"])
+
+
+def test_a_certified_step_exports_the_same_solution(gpu):
+    """the same behind a certified tqgpu_mpc_step, whose pack stays on the device until somebody asks: on the smallest tree of
+    mpc_root_cases, against a twin that does not certify"""
+    c = R.case("one_child")
+    x0 = R.x0_sequence(c, 5, steps=1)[0]
+    sols, kkts = {}, {}
+    for what in ("plain", "certified", "certified, kkt_residual first", "certified, twice"):
+        g = R.make(gpu, c, root_states=True)
+        g.mpc_set_certify(what != "plain")
+        g.mpc_step(x0, **c["opts"])
+        if what != "plain":
+            kkts[what] = g.mpc_certificate()
+        if "kkt_residual" in what:
+            kkts["tqgpu_kkt_residual"] = g.kkt_residual()
+        if "twice" in what:
+            g.solution()
+        sols[what] = g.solution()
+        g.close()
+    for what, s in sols.items():
+        for k in s:
+            assert np.all(np.isfinite(s[k])) and np.array_equal(s[k], sols["plain"][k]), f"{what}: {k}"
+    for what, k in kkts.items():
+        assert np.array_equal(k["res"], kkts["certified"]["res"]) and np.array_equal(k["node"], kkts["certified"]["node"]), what
 
 
 # ---- batch and refusals ----

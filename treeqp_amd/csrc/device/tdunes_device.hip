@@ -1856,7 +1856,7 @@ struct MpcShift {
     int restore = 0;                    /* 1: tqgpu_mpc_shift saved the start buffer of a mirror in mode 0, the next solve consumes the shifted one; 2: that solve has begun, the one after it puts the saved buffer back first */
 };
 struct MpcBatchBuf {
-    long drained_at = 0;                /* as kkt_drained_at, for the batch step's launch ahead of the solves */
+    long drained_at = 0;                /* as Kkt::drained_at, for the batch step's launch ahead of the solves */
     MItem *d_items = nullptr, *h_items = nullptr; int items_cap = 0;      /* batch steps: one descriptor per member of this device (the device's first member owns the array) */
     double *h_u0s = nullptr; int u0s_cap = 0;                             /* ... and their u[0] with the tag behind them, pinned */
 };
@@ -1870,6 +1870,50 @@ struct MpcSens {
     double *d = nullptr, *h = nullptr; Sens v{}; int nx0 = 0;
     bool valid = false, dirty = false;  /* dirty: the problem was changed (upload, fold, window move) since the last solve: its point and the data no longer belong together */
     size_t lds_factor = 0, lds_primal = 0;
+};
+
+/* ---- the solution's way out and its check (tdunes_kkt.hpp): the solution in one piece, [x | u | lam | dlam | mu_x | mu_u], packed on the device (d) and
+ * downloaded into pinned memory (h).  valid: h holds (or is about to hold, stream-ordered) the solution of the last solve; dev_only, with valid: the pack
+ * is in d only (a certified tqgpu_mpc_step), tqgpu_get_solution downloads it.  The three transitions below are the only writers of the two flags. ---- */
+struct Export {
+    double *d = nullptr, *h = nullptr; size_t doubles = 0;
+    bool ahead = false;                 /* tqgpu_set_export_ahead: the packing kernel and the download of the solution are enqueued right behind a single persistent launch */
+    bool valid = false, dev_only = false;
+    void invalidate() { valid = false; }                                   /* the device holds another point, or is about to: a solve begins, rows or the sharing change */
+    void packed_on_device() { valid = true; dev_only = true; }             /* packed behind a certified step; no download yet */
+    void packed_and_downloading() { valid = true; dev_only = false; }      /* the pack and its download are on the stream (an export ahead), or the download of a pack that was on the device only */
+};
+/* tqgpu_kkt_residual*: d, h, [six maxima | six nodes | pad | Nn x 6 table] on the device and pinned (setup_kkt, on first use); d_pt, h_pt, the point of
+ * tqgpu_kkt_residual_at, [x | u | lam | mu_x | mu_u | mu_d], on the device and pinned (grows with sum_nc).
+ * tqgpu_kkt_residual_batch, batched route (the first member of a device's group owns both): one descriptor per member, uploaded
+ * with every call, and the members' heads in one block, downloaded in one copy */
+struct Kkt {
+    double *d = nullptr, *h = nullptr, *d_pt = nullptr, *h_pt = nullptr; size_t pt_cap = 0;
+    KItem *d_items = nullptr, *h_items = nullptr; int items_cap = 0;
+    KHead *d_heads = nullptr, *h_heads = nullptr; int heads_cap = 0;
+    long drained_at = 0;                /* solve_no at which the batched route last knew this mirror's own stream to hold nothing of its solves */
+};
+/* ---- the two multi-device modes (tdunes_shard.hpp): the subtree-sharded mode (tqgpu_shard_*); rank, nranks and part_top are the sharded persistent launch's as well ---- */
+struct SubtreeShard {
+    int nranks = 1, rank = 0, part_top = -1;      /* part_top: highest partitioned tier */
+    bool on = false;          /* subtree-sharded mode (nranks > 1, or ONE rank with a communicator: the same code path, used to exercise the RCCL transport on a one-GPU box) */
+    int *d_gh_list = nullptr, *d_node_list = nullptr, *d_node_cnt_list = nullptr, *d_blk_list = nullptr;
+    int gh_n = 0, gh_counted = 0, n_nodes = 0, n_nodes_counted = 0, n_blk_counted = 0;
+    double *d_xerr = nullptr, *d_xs = nullptr;
+    int bnd_b0 = 0, bnd_bn = 0, bnd_own0 = 0, bnd_ownn = 0;   /* element ranges of the boundary nodes' duals */
+    void *slab = nullptr;
+    void *comm = nullptr;     /* RCCL communicator (nullptr: single device or virtual ranks) */
+};
+/* ONE tree over several devices INSIDE the persistent launch (tqgpu_pshard_*): this rank's share of the workgroups */
+struct PersistShard {
+    bool on = false;
+    bool sys = true;                /* the sharded launch polls its slab with system-scope loads (f_persist_sh<.., 1>); TREEQP_AMD_PSHARD_AGENT=1: agent scope, as on one device */
+    bool fine = false;              /* the hand-over slab was re-allocated as fine-grained memory (tqgpu_pshard_init; TREEQP_AMD_PSHARD_COARSE=1 keeps plain hipMalloc memory) */
+    int *wg_map = nullptr;          /* blockIdx.x -> workgroup id, this rank's workgroups (bottom tier first) */
+    int G = 0;
+    void *ipc[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      /* peer slabs opened through IPC handles (closed by tqgpu_destroy) */
+    unsigned long long *h_peers[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* slabs of all ranks (a mirror that is not sharded: its own, eight times) ... */
+    unsigned long long **d_peers = nullptr;                                                               /* ... and the device copy of the table the kernel reads */
 };
 
 struct tqgpu_solver {
@@ -1997,15 +2041,7 @@ struct tqgpu_solver {
      * the solution in one piece */
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
-    double *d_out = nullptr, *h_out = nullptr; size_t out_doubles = 0;
-    /* tqgpu_kkt_residual*: [six maxima | six nodes | pad | Nn x 6 table] on the device and pinned (setup_kkt, on first use); the point of
-     * tqgpu_kkt_residual_at, [x | u | lam | mu_x | mu_u | mu_d], on the device and pinned (grows with sum_nc) */
-    double *d_kkt = nullptr, *h_kkt = nullptr, *d_kkt_pt = nullptr, *h_kkt_pt = nullptr; size_t kkt_pt_cap = 0;
-    /* tqgpu_kkt_residual_batch, batched route (the first member of a device's group owns both): one descriptor per member, uploaded
-     * with every call, and the members' heads in one block, downloaded in one copy */
-    KItem *d_kitems = nullptr, *h_kitems = nullptr; int kitems_cap = 0;
-    KHead *d_kheads = nullptr, *h_kheads = nullptr; int kheads_cap = 0;
-    long kkt_drained_at = 0;            /* solve_no at which the batched route last knew this mirror's own stream to hold nothing of its solves */
+    Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
     MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens;      /* the MPC family (tdunes_mpc.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
@@ -2028,31 +2064,11 @@ struct tqgpu_solver {
     unsigned long uid = 0;                                                /* unique per mirror of this process (an address can come back) */
     bool stream_pending = false;                                          /* something was enqueued on `stream` without a synchronisation after it (asynchronous uploads, constant packing): a batch launch on ANOTHER stream waits for it first */
     hipStream_t batch_stream = nullptr;                                   /* member of a batch launch in flight: the stream that launch is on (the lead's) */
-    bool export_ahead = false;          /* tqgpu_set_export_ahead: the packing kernel and the download of the solution are enqueued right behind a single persistent launch */
-    bool export_valid = false;          /* h_out holds (or is about to hold, stream-ordered) the solution of the last solve */
-    bool export_dev_only = false;       /* with export_valid: the pack is in d_out only (a certified tqgpu_mpc_step); tqgpu_get_solution downloads it */
     hipStream_t settle_stream = nullptr;                                  /* member of a batch launch whose verdict is in but whose last workgroups may still write back:
                                                                            * the lead's stream, to be waited for before this mirror is touched through its own stream (settle) */
     size_t sync_words_bytes = 0, lds_persist = 0;
-    /* ONE tree over several devices INSIDE the persistent launch (tqgpu_pshard_*): this rank's share of the workgroups */
     bool strict_sum = false;        /* TREEQP_AMD_STRICT_SUM=1 (Data::strict) */
-    bool pshard = false;
-    bool ps_sys = true;             /* the sharded launch polls its slab with system-scope loads (f_persist_sh<.., 1>); TREEQP_AMD_PSHARD_AGENT=1: agent scope, as on one device */
-    bool ps_fine = false;           /* the hand-over slab was re-allocated as fine-grained memory (tqgpu_pshard_init; TREEQP_AMD_PSHARD_COARSE=1 keeps plain hipMalloc memory) */
-    int *ps_wg_map = nullptr;       /* blockIdx.x -> workgroup id, this rank's workgroups (bottom tier first) */
-    int ps_G = 0;
-    void *ps_ipc[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      /* peer slabs opened through IPC handles (closed by tqgpu_destroy) */
-    unsigned long long *h_peers[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* slabs of all ranks ... */
-    unsigned long long **d_peers = nullptr;                                                               /* ... and the device copy of the table the kernel reads */
-    /* sharded mode */
-    int nranks = 1, rank = 0, part_top = -1;      /* part_top: highest partitioned tier */
-    bool sharded = false;     /* subtree-sharded mode (nranks > 1, or ONE rank with a communicator: the same code path, used to exercise the RCCL transport on a one-GPU box) */
-    int *d_gh_list = nullptr, *d_node_list = nullptr, *d_node_cnt_list = nullptr, *d_blk_list = nullptr;
-    int gh_n = 0, gh_counted = 0, n_nodes = 0, n_nodes_counted = 0, n_blk_counted = 0;
-    double *d_xerr = nullptr, *d_xs = nullptr;
-    int bnd_b0 = 0, bnd_bn = 0, bnd_own0 = 0, bnd_ownn = 0;   /* element ranges of the boundary nodes' duals */
-    void *shard_slab = nullptr;
-    void *comm = nullptr;     /* RCCL communicator (nullptr: single device or virtual ranks) */
+    SubtreeShard shard; PersistShard pshard;      /* the two multi-device modes (tdunes_shard.hpp) */
     int chunk = 4;            /* Newton iterations enqueued per status read-back */
 };
 
@@ -2288,114 +2304,22 @@ void detect_fast(tqgpu_solver *s) {
     s->n_tiers = (int)s->tier_l0.size();
 }
 
-/* ---- RCCL, loaded lazily so that single-device users do not depend on it ---- */
-struct RcclApi {
-    void *lib = nullptr;
-    struct UniqueId { char internal[128]; };
-    int (*GetUniqueId)(UniqueId *) = nullptr;
-    int (*CommInitRank)(void **, int, UniqueId, int) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    const char *(*GetErrorString)(int) = nullptr;
-};
-RcclApi g_rccl;
-
-int rccl_load() {
-    if (g_rccl.lib) return TQGPU_OK;
-    const char *names[] = {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"};
-    void *lib = nullptr;
-    for (const char *n : names) if ((lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-    if (!lib) return fail(TQGPU_ECOMM, std::string("cannot load librccl.so: ") + dlerror());
-#define SYM(field, name) g_rccl.field = reinterpret_cast<decltype(g_rccl.field)>(dlsym(lib, name)); if (!g_rccl.field) return fail(TQGPU_ECOMM, std::string("librccl.so lacks ") + name)
-    SYM(GetUniqueId, "ncclGetUniqueId"); SYM(CommInitRank, "ncclCommInitRank"); SYM(CommDestroy, "ncclCommDestroy");
-    SYM(AllGather, "ncclAllGather"); SYM(GroupStart, "ncclGroupStart"); SYM(GroupEnd, "ncclGroupEnd"); SYM(GetErrorString, "ncclGetErrorString");
-#undef SYM
-    g_rccl.lib = lib;
-    return TQGPU_OK;
-}
-constexpr int NCCL_DOUBLE = 8;     /* ncclFloat64 */
-
-#define NCCL_TRY(expr) do { int r_ = (expr); if (r_ != 0) return fail(TQGPU_ECOMM, std::string(#expr) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error")); } while (0)
-
-Shard shard_desc(const tqgpu_solver *s, int tier) {
-    Shard sh{};
-    if (s->sharded) {
-        if (tier >= 0 && tier <= s->part_top) sh.wg_off = s->rank * (s->tier_grid[tier] / s->nranks);
-        sh.gh_list = s->d_gh_list; sh.gh_n = s->gh_n; sh.gh_counted = s->gh_counted;
-        sh.err_src = s->d_xerr;
-    }
-    return sh;
-}
-
-/* a rank-partitioned range: rank r's share is base[r * per_rank, (r + 1) * per_rank) */
-struct RangeSpec { double *base; size_t per_rank; };
-
-/* what the ranks exchange per Newton iteration.  which = 1 (after the last partitioned backward tier): Schur records of the boundary
- * subtree roots and the termination partials; which = 2 (after a trial sweep): {fval, dot} partials and x / QinvCal of the boundary
- * root nodes */
-std::vector<RangeSpec> exchange_ranges(tqgpu_solver *s, int which) {
-    const size_t NX = (size_t)s->fNX, SCH = NX * NX + NX;
-    const size_t f0 = (size_t)uni_first(s->fMD, s->tier_l0[s->part_top]), w = (size_t)(s->tier_grid[s->part_top] / s->nranks);
-    if (which == 1) return {{s->D.Sbuf + f0 * SCH, w * SCH}, {s->d_xerr, 1}};
-    return {{s->d_xs, 2}, {s->D.x + NX * f0, w * NX}, {s->D.QinvCal + NX * f0, w * NX}};
-}
-
-/* the partitioned part of the solution, one set of ranges per node level >= the boundary level: for the gather after a solve */
-std::vector<RangeSpec> solution_ranges(tqgpu_solver *s) {
-    std::vector<RangeSpec> out;
-    const int MD = s->fMD, NX = s->fNX, NU = s->fNU, N = s->nranks;
-    const int lb = s->tier_l0[s->part_top];
-    const Data &D = s->D;
-    double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
-    for (int l = lb; l <= s->Nh; l++) {
-        const size_t f0 = (size_t)uni_first(MD, l), w = (size_t)uni_width(MD, l) / N;
-        double *xs[] = {D.x, D.xUnc, D.xUncS, lamc, D.dlam};
-        for (double *a : xs) out.push_back({a + NX * f0, w * NX});
-        if (l < s->Nh) { double *us[] = {D.u, D.uUnc, D.uUncS}; for (double *a : us) out.push_back({a + NU * f0, w * NU}); }
-    }
-    return out;
-}
-
-/* the RCCL transport: one group of in-place all-gathers on the solver's stream, in the order of the list */
-int allgather_rccl(tqgpu_solver *s, const std::vector<RangeSpec> &ranges) {
-    NCCL_TRY(g_rccl.GroupStart());
-    for (const RangeSpec &rg : ranges) NCCL_TRY(g_rccl.AllGather(rg.base + (size_t)s->rank * rg.per_rank, rg.base, rg.per_rank, NCCL_DOUBLE, s->comm, s->stream));
-    NCCL_TRY(g_rccl.GroupEnd());
-    return TQGPU_OK;
-}
-
-/* the same between `n` mirrors living in one process on one device ("virtual ranks", to validate the partition / hand-off logic on a
- * single GPU).  ranges_of is asked per mirror: a mirror's h_ctrl->cur selects its own dual buffer */
-template <typename F>
-int allgather_virtual(tqgpu_solver **R, int n, F ranges_of) {
-    for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
-    /* every source stream is idle now; the copies are ordered on the DESTINATION mirror's stream, in
-     * front of its next phase (the solver streams are non-blocking: the null stream would not order) */
-    for (int src = 0; src < n; src++) for (int dst = 0; dst < n; dst++) {
-        if (src == dst) continue;
-        const std::vector<RangeSpec> from = ranges_of(R[src]), to = ranges_of(R[dst]);
-        for (size_t i = 0; i < from.size(); i++)
-            HIP_TRY(hipMemcpyAsync(to[i].base + (size_t)src * to[i].per_rank, from[i].base + (size_t)src * from[i].per_rank, sizeof(double) * from[i].per_rank, hipMemcpyDeviceToDevice, R[dst]->stream));
-    }
-    for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));
-    return TQGPU_OK;
-}
+/* the sharded modes' part in the launches per tier and in tqgpu_destroy (tdunes_shard.hpp) */
+Shard shard_desc(const tqgpu_solver *s, int tier); int shard_exchange(tqgpu_solver *s, int which); void shard_release(tqgpu_solver *s);
 
 /* One fused Newton iteration, split in three phases around the two exchange points of the sharded
  * mode.  Single device: phases run back to back, no exchange. */
 void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &launches) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     const dim3 blk(FW * WAVE);
-    const int nt = s->n_tiers, N = s->nranks;
-    const bool sharded = s->sharded;
-    const int P = sharded ? s->part_top : -1;
+    const int nt = s->n_tiers, N = s->shard.nranks;
+    const bool sharded = s->shard.on;
+    const int P = sharded ? s->shard.part_top : -1;
     auto tgrid = [&](int i) { return (sharded && i <= P) ? s->tier_grid[i] / N : s->tier_grid[i]; };
     /* which kernel runs first / performs the termination test */
     const int check_tier = sharded ? P + 1 : 1;          /* index in 0..nt-1 (nt-1 = top) */
     const int nparts = sharded ? N : (nt > 1 ? s->tier_grid[0] : FW);
-    const int n_stage = sharded ? s->n_nodes : T.Nn;
+    const int n_stage = sharded ? s->shard.n_nodes : T.Nn;
     switch (s->fast) {
 #define X(idx, nx, nu, md)                                                                                                   \
     case idx:                                                                                                                \
@@ -2404,7 +2328,7 @@ void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &la
                 hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->lds_fast, st, T, D, O, shard_desc(s, i),    \
                                    s->tier_l0[i], s->tier_l1[i], i == 0, !sharded && i == check_tier, nparts, i, h); launches++; \
             }                                                                                                                \
-            if (sharded) { hipLaunchKernelGGL(k_shard_pack1, dim3(1), dim3(256), 0, st, D, tgrid(0), s->d_xerr, s->rank, O.termCondition, h); launches++; } \
+            if (sharded) { hipLaunchKernelGGL(k_shard_pack1, dim3(1), dim3(256), 0, st, D, tgrid(0), s->shard.d_xerr, s->shard.rank, O.termCondition, h); launches++; } \
         }                                                                                                                    \
         if (phase == 1) {                                                                                                    \
             for (int i = (sharded ? P + 1 : nt - 1); i < nt - 1; i++) {                                                      \
@@ -2418,9 +2342,9 @@ void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &la
                                    s->tier_l0[i], s->tier_l1[i], nt + (nt - 2 - i), h); launches++;                          \
             }                                                                                                                \
             hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), blk, s->lds_fstage, st, T, D, O,        \
-                               sharded ? s->d_node_list : nullptr, n_stage, 2 * nt - 1, h, 1); launches++;                   \
-            if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->d_node_cnt_list, s->n_nodes_counted, \
-                                              s->d_blk_list, s->n_blk_counted, s->d_xs, s->rank, s->bnd_b0, s->bnd_bn, s->bnd_own0, s->bnd_ownn, h, 1); launches++; } \
+                               sharded ? s->shard.d_node_list : nullptr, n_stage, 2 * nt - 1, h, 1); launches++;                   \
+            if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->shard.d_node_cnt_list, s->shard.n_nodes_counted, \
+                                              s->shard.d_blk_list, s->shard.n_blk_counted, s->shard.d_xs, s->shard.rank, s->shard.bnd_b0, s->shard.bnd_bn, s->shard.bnd_own0, s->shard.bnd_ownn, h, 1); launches++; } \
         }                                                                                                                    \
         break;
         FAST_TABLE(X)
@@ -2428,7 +2352,7 @@ void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &la
         default: break;
     }
     if (phase == 2) {
-        if (sharded) hipLaunchKernelGGL(k_ls_decide_parts, dim3(1), dim3(WAVE), 0, st, D, O, s->d_xs, N, h, 1, 1);
+        if (sharded) hipLaunchKernelGGL(k_ls_decide_parts, dim3(1), dim3(WAVE), 0, st, D, O, s->shard.d_xs, N, h, 1, 1);
         else hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, h, 1, 1);
         launches++;
     }
@@ -2436,9 +2360,9 @@ void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &la
 
 int launch_fast_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches) {
     launch_fast_phase(s, O, h, 0, launches);
-    if (s->sharded) { int rc = allgather_rccl(s, exchange_ranges(s, 1)); if (rc) return rc; }
+    if (s->shard.on) { int rc = shard_exchange(s, 1); if (rc) return rc; }
     launch_fast_phase(s, O, h, 1, launches);
-    if (s->sharded) { int rc = allgather_rccl(s, exchange_ranges(s, 2)); if (rc) return rc; }
+    if (s->shard.on) { int rc = shard_exchange(s, 2); if (rc) return rc; }
     launch_fast_phase(s, O, h, 2, launches);
     return TQGPU_OK;
 }
@@ -2484,13 +2408,13 @@ static void launch_sg(tqgpu_solver *s, const Opts &O, int mode, int h, int t, bo
 
 void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int phase, int &launches) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
-    const bool sharded = s->sharded;
+    const bool sharded = s->shard.on;
     if (phase == 0) {
         bool done = false;
         if (r == Route::TIERED) {
-            const int n_stage = sharded ? s->n_nodes : T.Nn;
+            const int n_stage = sharded ? s->shard.n_nodes : T.Nn;
             switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->lds_fstage, st, T, D, O, sharded ? s->d_node_list : nullptr, n_stage, 7, it, t); done = true; break;
+#define X(idx, nx, nu, md) case idx: hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->lds_fstage, st, T, D, O, sharded ? s->shard.d_node_list : nullptr, n_stage, 7, it, t); done = true; break;
                 FAST_TABLE(X)
 #undef X
                 default: break;
@@ -2502,16 +2426,16 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
             else launch_stage_sweep(s, 1, it, t);
         }
         launches++;
-        if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->d_node_cnt_list, s->n_nodes_counted, s->d_blk_list, s->n_blk_counted, s->d_xs, s->rank, s->bnd_b0, s->bnd_bn, s->bnd_own0, s->bnd_ownn, it, t); launches++; }
+        if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->shard.d_node_cnt_list, s->shard.n_nodes_counted, s->shard.d_blk_list, s->shard.n_blk_counted, s->shard.d_xs, s->shard.rank, s->shard.bnd_b0, s->shard.bnd_bn, s->shard.bnd_own0, s->shard.bnd_ownn, it, t); launches++; }
     } else {
-        if (sharded) { hipLaunchKernelGGL(k_ls_decide_parts, dim3(1), dim3(WAVE), 0, st, D, O, s->d_xs, s->nranks, it, t, 0); launches++; }
+        if (sharded) { hipLaunchKernelGGL(k_ls_decide_parts, dim3(1), dim3(WAVE), 0, st, D, O, s->shard.d_xs, s->shard.nranks, it, t, 0); launches++; }
         else if (r != Route::FUSED_TAILS && r != Route::THREE_LAUNCH) { hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, it, t, 0); launches++; }
     }
 }
 
 int launch_trial(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int &launches) {
     launch_trial_phase(s, O, r, it, t, 0, launches);
-    if (s->sharded) { int rc = allgather_rccl(s, exchange_ranges(s, 2)); if (rc) return rc; }
+    if (s->shard.on) { int rc = shard_exchange(s, 2); if (rc) return rc; }
     launch_trial_phase(s, O, r, it, t, 1, launches);
     return TQGPU_OK;
 }
@@ -2622,9 +2546,9 @@ int setup_persist(tqgpu_solver *s) {
     s->psync.verdict = s->psync.rfl + n_rfl;
     s->psync.anc = s->psync.verdict + n_verdict;
     s->psync.base = w; s->psync.npeer = 1; s->psync.relay_wg = -1; s->psync.anc_local = 1;
-    for (int r = 0; r < 8; r++) s->h_peers[r] = w;
-    if (int rc = s->mem.upload(s->d_peers, s->h_peers, sizeof(s->h_peers), TQGPU_ENODEVICE, "the table of peer slabs")) return rc;
-    s->psync.peers = s->d_peers;
+    for (int r = 0; r < 8; r++) s->pshard.h_peers[r] = w;
+    if (int rc = s->mem.upload(s->pshard.d_peers, s->pshard.h_peers, sizeof(s->pshard.h_peers), TQGPU_ENODEVICE, "the table of peer slabs")) return rc;
+    s->psync.peers = s->pshard.d_peers;
     s->psync.seq = 0; s->psync.trip = 0;
     s->psync.nap = s->sw.has_nap ? s->sw.nap : nap_for_grid(G.G);
     /* XCD-aware placement: the hardware deals workgroups round-robin over the 8 XCDs (workgroup b -> XCD b % 8)
@@ -2704,13 +2628,13 @@ int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, 
         s->stream_pending = true;
     }
     if (batch_seq) { launches++; return TQGPU_OK; }          /* the caller launches the batch */
-    if (s->pshard) {
+    if (s->pshard.on) {
         /* this rank's share of the workgroups; the geometry (tiers, global workgroup numbers, G) is the whole tree's */
         PGeom Gm = s->geom;
-        Gm.wg_of_block = s->ps_wg_map;
+        Gm.wg_of_block = s->pshard.wg_map;
         switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: if (s->ps_sys) hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 1>), dim3(s->ps_G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, Gm, s->psync, prologue); \
-                                    else hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 0>), dim3(s->ps_G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, Gm, s->psync, prologue); break;
+#define X(idx, nx, nu, md) case idx: if (s->pshard.sys) hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 1>), dim3(s->pshard.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, Gm, s->psync, prologue); \
+                                    else hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 0>), dim3(s->pshard.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, Gm, s->psync, prologue); break;
             SHARD_TABLE(X)
 #undef X
             default: return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape");
@@ -2830,241 +2754,6 @@ void launch_phase_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches
 void launch_generic_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts, bool phases, bool last) {
     if (s->route == Route::THREE_LAUNCH) launch_w3_iteration(s, O, h, launches, parts, last);
     else launch_phase_iteration(s, O, h, launches, parts, phases);
-}
-
-/* solution export in one piece: out = [x | u | lam | dlam | mu_x | mu_u] (x and mu_x without the phantom root
- * states), mu = Q .* (xUnc - x) (export_mu, clipping.c:386-399) */
-__device__ __forceinline__ void export_all_entry(int i, int n_x, int n_u, int n_lam, int x_pad, int nx0, const Data &D, const double *lamc, double *out) {
-    double *ox = out, *ou = ox + n_x, *ol = ou + n_u, *od = ol + n_lam, *omx = od + n_lam, *omu = omx + n_x;
-    /* MAXIMUM_ITERATIONS_REACHED with at least one iteration done: x, u are the last trial's, the unclipped values phase S's (see Data) */
-    const bool maxit = D.ctrl->status == 1 && D.ctrl->iter > 0;
-    if (i < n_x) {
-        const int j = i + x_pad;
-        ox[i] = D.x[j];
-        omx[i] = D.Qd[j] * fma(-1.0, D.x[j], (maxit ? D.xUncS : D.xUnc)[j]);      /* dense nodes: Qd = 0 (no bounds, no multipliers) */
-    }
-    if (i < n_u) { ou[i] = D.u[i]; omu[i] = D.Rd[i] * fma(-1.0, D.u[i], (maxit ? D.uUncS : D.uUnc)[i]); }
-    if (i < n_lam) {
-        const double *lc = lamc ? lamc : (D.ctrl->cur ? D.lam1 : D.lam0);      /* (enqueued behind a solve that is still running: the device knows) */
-        ol[i] = lc[nx0 + i]; od[i] = D.dlam[nx0 + i];
-    }
-}
-__global__ void k_export_all(int n_x, int n_u, int n_lam, int x_pad, int nx0, Data D, const double *lamc, double *out) {
-    export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, n_x, n_u, n_lam, x_pad, nx0, D, lamc, out);
-}
-
-/* multipliers of the box nodes' bounds (export of the qpOASES stage solver, dual_Newton_tree_qpoases.c:524-560), over what
- * k_export_all wrote for them: mu = hmod - H z with the reference's sign, on the working set; 0 on free entries.  On a
- * MAXIMUM_ITERATIONS exit hmod is phase S's and z the last trial's, on every entry: the pairing of export_mu on clipping nodes
- * (see Data::xUncS), and on a diagonal node the same numbers.  One wave per node, lane = entry. */
-__device__ __forceinline__ void export_box_node(const Tree &T, const Data &D, int n_x, int n_u, int n_lam, int x_pad, double *out, int k, int lane) {
-    if (!D.dense || D.kind[k] != 2) return;
-    const int nxk = T.nx[k], nz = nxk + T.nu[k], xo = T.xoff[k], uo = T.uoff[k];
-    if (lane >= nz || (k == 0 && lane < x_pad)) return;           /* (phantom root states are not exported) */
-    const bool maxit = D.ctrl->status == 1 && D.ctrl->iter > 0;
-    const bool isx = lane < nxk;
-    const int j0 = isx ? lane : lane - nxk;
-    const double *H = D.Hd + D.poff[k];
-    double hz = 0.0;
-    for (int j = 0; j < nz; j++) hz = fma(H[lane + (size_t)j * nz], j < nxk ? D.x[xo + j] : D.u[uo + j - nxk], hz);
-    const double h = isx ? (maxit ? D.xUncS : D.xUnc)[xo + j0] : (maxit ? D.uUncS : D.uUnc)[uo + j0];
-    const double mu = (maxit || ((D.bmask[k] >> lane) & 1ull)) ? h - hz : 0.0;
-    double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
-    if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
-}
-__global__ void __launch_bounds__(WAVE) k_export_box(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
-    export_box_node(T, D, n_x, n_u, n_lam, x_pad, out, blockIdx.x, threadIdx.x);
-}
-
-/* the same for the nodes with general constraints (kind 3): mu = hmod - H z - G' mu_d on the fixed entries, with the row multipliers
- * stage_gen left in Gen::mu (the sign of tree_qp_out_calculate_KKT_res: Qx + q + ... + mu_x + C' mu_d = 0) */
-__device__ __forceinline__ void export_gen_node(const Tree &T, const Data &D, int n_x, int n_u, int n_lam, int x_pad, double *out, int k, int lane) {
-    if (!D.dense || D.kind[k] != 3) return;
-    const Gen &Gn = *D.gen;
-    const int nxk = T.nx[k], nz = nxk + T.nu[k], xo = T.xoff[k], uo = T.uoff[k], nc = Gn.nc[k];
-    if (lane >= nz || (k == 0 && lane < x_pad)) return;
-    const bool maxit = D.ctrl->status == 1 && D.ctrl->iter > 0;
-    const bool isx = lane < nxk;
-    const int j0 = isx ? lane : lane - nxk;
-    const double *H = D.Hd + D.poff[k], *Gt = Gn.Gt + Gn.goff[k], *mud = Gn.mu + Gn.roff[k];
-    double hz = 0.0;
-    for (int j = 0; j < nz; j++) hz = fma(H[lane + (size_t)j * nz], j < nxk ? D.x[xo + j] : D.u[uo + j - nxk], hz);
-    for (int r = 0; r < nc; r++) hz = fma(Gt[lane + (size_t)r * nz], mud[r], hz);
-    const double h = isx ? (maxit ? D.xUncS : D.xUnc)[xo + j0] : (maxit ? D.uUncS : D.uUnc)[uo + j0];
-    const double mu = (maxit || ((D.bmask[k] >> lane) & 1ull)) ? h - hz : 0.0;
-    double *omx = out + n_x + n_u + 2 * (size_t)n_lam, *omu = omx + n_x;
-    if (isx) omx[xo + j0 - x_pad] = mu; else omu[uo + j0] = mu;
-}
-__global__ void __launch_bounds__(WAVE) k_export_gen(Tree T, Data D, int n_x, int n_u, int n_lam, int x_pad, double *out) {
-    export_gen_node(T, D, n_x, n_u, n_lam, x_pad, out, blockIdx.x, threadIdx.x);
-}
-
-/* ---- KKT residuals of a point, evaluated where the data is (tqgpu_kkt_residual*; tree_qp_out_calculate_KKT_res, tree_qp_common.c:540-788) ----
- * The point comes as pointers in the flat user layout of tqgpu_get_solution (no phantom root states; a null multiplier array is all
- * zeros), so the same kernels serve d_out + Gen::mu and the scratch buffer of tqgpu_kkt_residual_at. */
-struct KktPoint { const double *x, *u, *lam, *mu_x, *mu_u, *mu_d; };
-constexpr int KKT_CLASSES = 6;
-constexpr int KKT_HEAD = 10;      /* doubles in front of the per-node table: six maxima, six ints (the nodes), one pad */
-static_assert(sizeof(MpcRoot::cert) == sizeof(double) * KKT_HEAD, "the certificate of a step is the head of the KKT result block");
-
-__device__ __forceinline__ double kkt_viol(double v, double lo, double hi) { return v > hi ? v - hi : v < lo ? lo - v : (v != v ? v : 0.0); }
-/* a multiplier that is exactly zero contributes zero whatever the bound (the reference's 0 * inf is NaN) */
-__device__ __forceinline__ double kkt_compl(double mu, double v, double lo, double hi) { return mu == 0.0 ? 0.0 : mu > 0.0 ? mu * (v - hi) : mu * (lo - v); }
-/* entry j of [x | u] of a node; phantom root states are zero and belong to no class */
-__device__ __forceinline__ double kkt_z(const KktPoint &P, int j, int nxn, int xo, int uo, int pad, int x_pad) {
-    return j < nxn ? (j < pad ? 0.0 : P.x[xo + j - x_pad]) : P.u[uo + j - nxn];
-}
-
-/* One wave per node: lane j owns entry j of [x | u], then of the rows, striding by 64 on larger nodes.  Per class the largest absolute
- * entry of the node, NaN kept (nanmax / wmax), goes to table[6 k + class]; -1 where the node has no entry of the class.  Nodes of kind 1
- * ignore their bounds (entries 0); rows count on nodes of kind 3 only. */
-__device__ __forceinline__ void kkt_node(const Tree &T, const Data &D, int x_pad, const KktPoint &P, double *table, int k, int lane) {
-    const int nxk = T.nx[k], nuk = T.nu[k], nz = nxk + nuk, xo = T.xoff[k], uo = T.uoff[k], nx0 = T.nx0;
-    const int pad = k == 0 ? x_pad : 0;
-    const int kind = D.dense ? D.kind[k] : 0;
-    const int nc = kind == 3 ? D.gen->nc[k] : 0, ro = kind == 3 ? D.gen->roff[k] : 0;
-    const double *Gt = kind == 3 ? D.gen->Gt + D.gen->goff[k] : nullptr;
-    const double *H = kind ? D.Hd + D.poff[k] : nullptr;
-    double m[KKT_CLASSES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-
-    for (int j = lane; j < nz; j += WAVE) {
-        if (j < pad) continue;
-        const bool isx = j < nxk;
-        const int jj = isx ? j : j - nxk;
-        const double zj = kkt_z(P, j, nxk, xo, uo, pad, x_pad);
-        const double mu = isx ? (P.mu_x ? P.mu_x[xo + j - x_pad] : 0.0) : (P.mu_u ? P.mu_u[uo + jj] : 0.0);
-        /* stationarity: H z + h + mu + G' mu_d - lam_k + sum over the children of [A B]' lam_kid (column j of A / B is contiguous) */
-        double acc = 0.0;
-        if (kind) for (int i = 0; i < nz; i++) acc = fma(H[j + (size_t)i * nz], kkt_z(P, i, nxk, xo, uo, pad, x_pad), acc);
-        else acc = (isx ? D.Qd[xo + j] : D.Rd[uo + jj]) * zj;
-        acc += isx ? D.q[xo + j] : D.r[uo + jj];
-        acc += mu;
-        for (int r = 0; r < nc; r++) acc = fma(Gt[(size_t)r * nz + j], P.mu_d ? P.mu_d[ro + r] : 0.0, acc);
-        if (k > 0 && isx) acc -= P.lam[xo - nx0 + j];
-        for (int c = 0; c < T.nk[k]; c++) {
-            const int kid = T.kid0[k] + c, nxc = T.nx[kid];
-            const double *col = isx ? D.A + T.aoff[kid] + (size_t)j * nxc : D.B + T.boff[kid] + (size_t)jj * nxc;
-            const double *lk = P.lam + T.xoff[kid] - nx0;
-            for (int i = 0; i < nxc; i++) acc = fma(col[i], lk[i], acc);
-        }
-        m[TQGPU_KKT_STAT] = nanmax(m[TQGPU_KKT_STAT], fabs(acc));
-        /* bounds: violation and complementarity */
-        if (kind != 1) {
-            const double lo = isx ? D.xmin[xo + j] : D.umin[uo + jj], hi = isx ? D.xmax[xo + j] : D.umax[uo + jj];
-            m[TQGPU_KKT_BFEAS] = nanmax(m[TQGPU_KKT_BFEAS], fabs(kkt_viol(zj, lo, hi)));
-            m[TQGPU_KKT_BCOMPL] = nanmax(m[TQGPU_KKT_BCOMPL], fabs(kkt_compl(mu, zj, lo, hi)));
-        }
-    }
-    /* dynamics: A x_dad + B u_dad + b - x_k */
-    if (k > 0) {
-        const int dad = T.dad[k], nxd = T.nx[dad], nud = T.nu[dad], xod = T.xoff[dad], uod = T.uoff[dad], padd = dad == 0 ? x_pad : 0;
-        const double *A = D.A + T.aoff[k], *B = D.B + T.boff[k];
-        for (int i = lane; i < nxk; i += WAVE) {
-            double acc = 0.0;
-            for (int j = padd; j < nxd; j++) acc = fma(A[i + (size_t)j * nxk], P.x[xod + j - x_pad], acc);
-            for (int j = 0; j < nud; j++) acc = fma(B[i + (size_t)j * nxk], P.u[uod + j], acc);
-            acc += D.b[xo + i];
-            acc -= P.x[xo + i - x_pad];
-            m[TQGPU_KKT_DYN] = nanmax(m[TQGPU_KKT_DYN], fabs(acc));
-        }
-    }
-    /* rows: G z against [dmin, dmax], row r of G at Gt[r nz ..) */
-    for (int r = lane; r < nc; r += WAVE) {
-        double g = 0.0;
-        for (int j = pad; j < nz; j++) g = fma(Gt[(size_t)r * nz + j], kkt_z(P, j, nxk, xo, uo, pad, x_pad), g);
-        const double lo = D.gen->dmin[ro + r], hi = D.gen->dmax[ro + r], mu = P.mu_d ? P.mu_d[ro + r] : 0.0;
-        m[TQGPU_KKT_GFEAS] = nanmax(m[TQGPU_KKT_GFEAS], fabs(kkt_viol(g, lo, hi)));
-        m[TQGPU_KKT_GCOMPL] = nanmax(m[TQGPU_KKT_GCOMPL], fabs(kkt_compl(mu, g, lo, hi)));
-    }
-    const bool have_z = nz - pad > 0;
-    const bool have[KKT_CLASSES] = {have_z, k > 0 && nxk > 0, have_z, have_z, nc > 0, nc > 0};
-#pragma unroll
-    for (int c = 0; c < KKT_CLASSES; c++) {
-        const double v = wmax(m[c]);
-        if (lane == 0) table[(size_t)KKT_CLASSES * k + c] = have[c] ? v : -1.0;
-    }
-}
-__global__ void __launch_bounds__(WAVE) k_kkt(Tree T, Data D, int x_pad, KktPoint P, double *table) {
-    kkt_node(T, D, x_pad, P, table, blockIdx.x, threadIdx.x);
-}
-
-/* (v, n) before (bv, bn): a NaN first, then the larger value, the lower node among equals; n < 0: nothing yet */
-__device__ __forceinline__ bool kkt_before(double v, int n, double bv, int bn) {
-    if (n < 0) return false;
-    if (bn < 0) return true;
-    const bool vn = v != v, bvn = bv != bv;
-    if (vn || bvn) return vn && (!bvn || n < bn);
-    return v > bv || (v == bv && n < bn);
-}
-
-/* One workgroup: the table's six columns to six maxima and the lowest nodes that attain them (head[0..6), ints at head + 6; node -1
- * and value 0 for a class without entries); the table's -1 marks become 0.  A fixed tree of comparisons, no atomics. */
-__device__ __forceinline__ void kkt_max_columns(int Nn, double *table, double *head, double *sv, int *sn, int t) {
-    int *node = reinterpret_cast<int *>(head + KKT_CLASSES);
-    for (int c = 0; c < KKT_CLASSES; c++) {
-        double bv = 0.0; int bn = -1;
-        for (int k = t; k < Nn; k += 256) {
-            const double v = table[(size_t)KKT_CLASSES * k + c];
-            if (v < 0.0) { table[(size_t)KKT_CLASSES * k + c] = 0.0; continue; }
-            if (kkt_before(v, k, bv, bn)) { bv = v; bn = k; }
-        }
-        sv[t] = bv; sn[t] = bn;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (t < w && kkt_before(sv[t + w], sn[t + w], sv[t], sn[t])) { sv[t] = sv[t + w]; sn[t] = sn[t + w]; }
-            __syncthreads();
-        }
-        if (t == 0) { head[c] = sn[0] < 0 ? 0.0 : sv[0]; node[c] = sn[0]; }
-        __syncthreads();
-    }
-}
-__global__ void __launch_bounds__(256) k_kkt_max(int Nn, double *table, double *head) {
-    __shared__ double sv[256];
-    __shared__ int sn[256];
-    kkt_max_columns(Nn, table, head, sv, sn, threadIdx.x);
-}
-
-/* ---- the same for a batch of mirrors in one launch each (tqgpu_kkt_residual_batch) ----
- * One descriptor per member, uploaded with every call: what the single launches pass as kernel arguments.  Every kernel below is the
- * single kernel's body (the __device__ functions above, so the arithmetic of a node is the same instruction for instruction) behind
- * a look-up of the member: blockIdx.y = member, blockIdx.x = what blockIdx.x is in the single launch.  The grid is as wide as the
- * largest member needs; a workgroup beyond its member's own extent, or of a member the kernel does not apply to, returns at once
- * and writes nothing. */
-struct KItem {
-    Tree T; Data D; KktPoint P;
-    const double *lamc;            /* the current duals (lam0 or lam1, as the host knows after the solve) */
-    double *d_out, *table, *head;  /* the member's export block and per-node table; its KKT_HEAD doubles in the batch's contiguous block of heads */
-    int x_pad, nxe, nue, nl, nx0;  /* phantom root states; the export sizes (x without them, u, lam) */
-    int needs_export, box, gen;    /* d_out is not packed yet (no export went out ahead); the tree has nodes of kind 2 / of kind 3 */
-};
-struct KHead { double v[KKT_HEAD]; };      /* six maxima, six ints, one pad: what k_kkt_max writes in front of a mirror's own table */
-__global__ void __launch_bounds__(256) k_export_all_batch(const KItem *__restrict__ items) {
-    const KItem &it = items[blockIdx.y];
-    if (!it.needs_export) return;
-    export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, it.nxe, it.nue, it.nl, it.x_pad, it.nx0, it.D, it.lamc, it.d_out);
-}
-__global__ void __launch_bounds__(WAVE) k_export_box_batch(const KItem *__restrict__ items) {
-    const KItem &it = items[blockIdx.y];
-    if (!it.needs_export || !it.box || (int)blockIdx.x >= it.T.Nn) return;
-    export_box_node(it.T, it.D, it.nxe, it.nue, it.nl, it.x_pad, it.d_out, blockIdx.x, threadIdx.x);
-}
-__global__ void __launch_bounds__(WAVE) k_export_gen_batch(const KItem *__restrict__ items) {
-    const KItem &it = items[blockIdx.y];
-    if (!it.needs_export || !it.gen || (int)blockIdx.x >= it.T.Nn) return;
-    export_gen_node(it.T, it.D, it.nxe, it.nue, it.nl, it.x_pad, it.d_out, blockIdx.x, threadIdx.x);
-}
-/* one wave per (member, node) */
-__global__ void __launch_bounds__(WAVE) k_kkt_batch(const KItem *__restrict__ items) {
-    const KItem &it = items[blockIdx.y];
-    if ((int)blockIdx.x >= it.T.Nn) return;
-    kkt_node(it.T, it.D, it.x_pad, it.P, it.table, blockIdx.x, threadIdx.x);
-}
-/* one workgroup per member */
-__global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__ items) {
-    __shared__ double sv[256];
-    __shared__ int sn[256];
-    const KItem &it = items[blockIdx.x];
-    kkt_max_columns(it.T.Nn, it.table, it.head, sv, sn, threadIdx.x);
 }
 
 /* ---- tqgpu_create step by step: each step takes the mirror and returns a TQGPU_* code ---- */
@@ -3225,11 +2914,11 @@ int layout_slab(tqgpu_solver *s) {
     s->d_mu_x = at<double>(base, o_mux); s->d_mu_u = at<double>(base, o_muu);
     s->d_lam_init = at<double>(base, o_lami);
     s->in_off0 = o_A; s->in_bytes = o_Qinv - o_A;
-    s->out_doubles = 2 * (size_t)(s->sum_nx - s->x_pad) + 2 * (size_t)s->sum_nu + 2 * (size_t)s->sum_lam;
+    s->out.doubles = 2 * (size_t)(s->sum_nx - s->x_pad) + 2 * (size_t)s->sum_nu + 2 * (size_t)s->sum_lam;
     if ((rc = s->mem.host(s->h_in, std::max<size_t>(s->in_bytes, 8), "the host mirror of the inputs")) ||
         (rc = s->mem.host(s->h_lam, sizeof(double) * (size_t)std::max(s->sum_nx, 1), "the host mirror of the duals")) ||
-        (rc = s->mem.host(s->h_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), "the host mirror of the solution")) ||
-        (rc = s->mem.device(s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), TQGPU_ENOMEM, "the packed solution")))
+        (rc = s->mem.host(s->out.h, sizeof(double) * std::max<size_t>(s->out.doubles, 1), "the host mirror of the solution")) ||
+        (rc = s->mem.device(s->out.d, sizeof(double) * std::max<size_t>(s->out.doubles, 1), TQGPU_ENOMEM, "the packed solution")))
         return rc;
     if (s->x_pad) {
         /* phantom root states: weight 1, everything else zero (the slab is zeroed) */
@@ -3392,25 +3081,6 @@ int setup_single_wg(tqgpu_solver *s) {
     return TQGPU_OK;
 }
 
-/* the buffers of tqgpu_kkt_residual*, on first use (most mirrors never ask): the result block, and with_point the scratch point of
- * tqgpu_kkt_residual_at, which grows when tqgpu_set_constraints has added rows since */
-int setup_kkt(tqgpu_solver *s, bool with_point) {
-    int rc;
-    const size_t res_bytes = sizeof(double) * (KKT_HEAD + (size_t)KKT_CLASSES * s->Nn);
-    if (!s->d_kkt && ((rc = s->mem.device(s->d_kkt, res_bytes, TQGPU_ENOMEM, "the KKT residuals")) || (rc = s->mem.host(s->h_kkt, res_bytes, "the host mirror of the KKT residuals"))))
-        return rc;
-    const size_t need = 2 * (size_t)(s->sum_nx - s->x_pad) + 2 * (size_t)s->sum_nu + (size_t)s->sum_lam + (size_t)s->sum_nc;
-    if (with_point && (!s->d_kkt_pt || need > s->kkt_pt_cap)) {
-        s->mem.release(s->d_kkt_pt); s->mem.release(s->h_kkt_pt);
-        s->kkt_pt_cap = 0;
-        if ((rc = s->mem.device(s->d_kkt_pt, sizeof(double) * std::max<size_t>(need, 1), TQGPU_ENOMEM, "the point of tqgpu_kkt_residual_at")) ||
-            (rc = s->mem.host(s->h_kkt_pt, sizeof(double) * std::max<size_t>(need, 1), "the host mirror of that point")))
-            return rc;
-        s->kkt_pt_cap = need;
-    }
-    return TQGPU_OK;
-}
-
 }  // namespace
 
 extern "C" int tqgpu_create(tqgpu_solver **out, int device, int Nn, const int *nk, const int *nx, const int *nu) {
@@ -3451,22 +3121,21 @@ extern "C" void tqgpu_destroy(tqgpu_solver *s) {
     for (auto &ev : s->ring_ev0) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : s->ring_ev1) if (ev) (void)hipEventDestroy(ev);
     if (s->stream) { { std::lock_guard<std::mutex> lk(g_streams_mu); g_live_streams.erase(s->stream); } (void)hipStreamDestroy(s->stream); }
-    for (int r = 0; r < 8; r++) if (s->ps_ipc[r]) (void)hipIpcCloseMemHandle(s->ps_ipc[r]);
-    if (s->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(s->comm);
+    shard_release(s);
     s->mem.free_all();
     delete s;
 }
 
 /* what a mirror admits: the persistent single launch (uniform or multistage trees), launches per tier (uniform trees only) */
-static bool persist_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && s->persist_ok && s->use_persist && !s->sharded; }
+static bool persist_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && s->persist_ok && s->use_persist && !s->shard.on; }
 static bool tiered_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && !s->mstage; }
 /* `batch`: as a member of a batched launch (one workgroup per tree) the single-workgroup kernel also takes trees whose
  * state does not fit the LDS mirror; alone, such a tree is faster with one launch per level */
 static bool uses_gpersist(const tqgpu_solver *s, bool batch) {
     /* a dense tree: only on request, only where plan_dense_single found room; alone and as a member of a batch are two requests
      * (g_persist_dense, g_persist_dense_batch) */
-    if (s->dense) return (batch ? s->dense_batch : s->dense_single) && s->dense_gp_ok && s->use_gpersist && !s->sharded;
-    return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->sharded && !persist_capable(s) && !tiered_capable(s);
+    if (s->dense) return (batch ? s->dense_batch : s->dense_single) && s->dense_gp_ok && s->use_gpersist && !s->shard.on;
+    return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->shard.on && !persist_capable(s) && !tiered_capable(s);
 }
 /* the first route that the mirror and the options admit (batch_member: see uses_gpersist) */
 static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_member) {
@@ -3474,8 +3143,8 @@ static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_mem
     if (persist_capable(s) && p == 0 && m > 0) return Route::PERSIST;
     if (uses_gpersist(s, batch_member) && p == 0 && m > 0) return Route::SINGLE_WG;
     if (tiered_capable(s) && p < 3) return Route::TIERED;
-    if (s->w3_ok && !s->dense && p < 3 && !s->sharded) return Route::THREE_LAUNCH;
-    if (s->fuse_ok && p < 3 && !s->sharded && !s->box && !s->gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
+    if (s->w3_ok && !s->dense && p < 3 && !s->shard.on) return Route::THREE_LAUNCH;
+    if (s->fuse_ok && p < 3 && !s->shard.on && !s->box && !s->gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
     return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
 /* the kernel variants the steps of tqgpu_create (setup_per_phase, setup_wide3, setup_persist, setup_single_wg) and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
@@ -3730,7 +3399,7 @@ void plan_dense_single(tqgpu_solver *s) {
 extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const double *Q, const double *R, const double *S, const double *q, const double *r) {
     SETTLE(s);
     if (!s || !Q || !q) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: bad arguments");
-    if (s->sharded) return fail(TQGPU_EINVAL, "the dense stage solver is not available in sharded mode");
+    if (s->shard.on) return fail(TQGPU_EINVAL, "the dense stage solver is not available in sharded mode");
     HIP_TRY(hipSetDevice(s->device));
     std::vector<double> H((size_t)std::max(s->poff[s->Nn], 1), 0.0);
     std::vector<double> Qd((size_t)std::max(s->sum_nx, 1), 0.0), Rd((size_t)std::max(s->sum_nu, 1), 0.0);
@@ -3821,7 +3490,7 @@ extern "C" int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const doubl
 extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const double *C, const double *Dm, const double *dmin, const double *dmax) {
     SETTLE(s);
     if (!s) return fail(TQGPU_EINVAL, "null solver");
-    if (s->sharded || s->pshard) return fail(TQGPU_EINVAL, "general constraints are not available in sharded mode");
+    if (s->shard.on || s->pshard.on) return fail(TQGPU_EINVAL, "general constraints are not available in sharded mode");
     if (!nc && s->gnc.empty()) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: the rows per node (nc) have not been given yet");
     HIP_TRY(hipSetDevice(s->device));
     const int Nn = s->Nn;
@@ -3887,7 +3556,7 @@ extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const doubl
     }
     if (total > 0 && (nc || dmin || dmax)) HIP_TRY(hipMemcpy(s->d_drange, dr.data(), sizeof(double) * 2 * (size_t)total, hipMemcpyHostToDevice));
     s->h_drange.swap(dr);
-    s->export_valid = false; s->sens.valid = false; s->sens.dirty = true;          /* not problem_changed: the rows are no input of tqgpu_set_problem (in_valid stays), the exported point goes */
+    s->out.invalidate(); s->sens.valid = false; s->sens.dirty = true;          /* not problem_changed: the rows are no input of tqgpu_set_problem (in_valid stays), the exported point goes */
     return TQGPU_OK;
 }
 
@@ -4162,12 +3831,12 @@ int grow_events(std::vector<hipEvent_t> &v, int n) {
  * and the first event.  in_batch_launch: the solve's launch is made by the caller, on the lead's stream */
 int prepare_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, bool in_batch_launch) {
     HIP_TRY(hipSetDevice(s->device));
-    s->export_valid = false;
+    s->out.invalidate();
     s->sens.valid = false; s->sens.dirty = false;          /* (not problem_changed: the data stays) a stored sensitivity belongs to the point of the solve before this one; point and data belong together again */
     if (opts_from(o, cx.O) != TQGPU_OK) return TQGPU_EINVAL;
     cx.O.stamps = cx.env.stamps;
 
-    if (s->sharded && !s->comm) return fail(TQGPU_ECOMM, "sharded mirror without a communicator: use tqgpu_solve_virtual_ranks");
+    if (s->shard.on && !s->shard.comm) return fail(TQGPU_ECOMM, "sharded mirror without a communicator: use tqgpu_solve_virtual_ranks");
 
     /* ls_log needs no reset: entry i is written by iteration i */
 
@@ -4548,23 +4217,14 @@ static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const Solve
     return solve_end(s, o, cx, res);
 }
 
-static int enqueue_export(tqgpu_solver *s, const double *lamc, bool download = true) {      /* download = false: d_out only (tqgpu_kkt_residual reads it there) */
-    const Data &D = s->D;
-    const int nxe = s->sum_nx - s->x_pad, nue = s->sum_nu, nl = s->sum_lam;
-    const int n = std::max(std::max(nxe, nue), std::max(nl, 1));
-    hipLaunchKernelGGL(k_export_all, dim3((n + 255) / 256), dim3(256), 0, s->stream, nxe, nue, nl, s->x_pad, s->nx0, D, lamc, s->d_out);
-    if (s->box) hipLaunchKernelGGL(k_export_box, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
-    if (s->gen) hipLaunchKernelGGL(k_export_gen, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, nxe, nue, nl, s->x_pad, s->d_out);
-    if (download) HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, s->stream));
-    return TQGPU_OK;
-}
+static int enqueue_export(tqgpu_solver *s, const double *lamc, bool download = true);      /* tdunes_kkt.hpp */
 
 extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *res) {
     SETTLE(s);
     if (!s || !o || !res) return fail(TQGPU_EINVAL, "tqgpu_solve: bad arguments");
     /* a mirror that is one rank's share of a sharded solve launches only that share: on its own it would time out, and its launch number
      * would fall out of step with its peers' */
-    if (s->pshard && s->nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve: this mirror is rank " + std::to_string(s->rank) + " of a sharded solve (tqgpu_pshard_init): use tqgpu_pshard_begin / _end");
+    if (s->pshard.on && s->shard.nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve: this mirror is rank " + std::to_string(s->shard.rank) + " of a sharded solve (tqgpu_pshard_init): use tqgpu_pshard_begin / _end");
     if (s->persist_backoff > 0 && --s->persist_backoff == 0) s->use_persist = s->use_persist_orig;
     SolveCtx cx(read_solve_env(false), route_of(s, o, false));
     int rc = solve_begin(s, o, cx);
@@ -4574,19 +4234,12 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
      * persistent launch now, while it runs, instead of after its verdict has travelled to the host and back (a launch latency, the
      * launch's write-back tail and a synchronisation off the caller's critical path); which dual buffer is current is the device's
      * knowledge.  Valid if that one launch was the whole solve. */
-    const bool ahead = s->export_ahead && single_launch(cx.route) && !s->pshard && !s->sharded;          /* (solve_begin has made the launch) */
+    const bool ahead = s->out.ahead && single_launch(cx.route) && !s->pshard.on && !s->shard.on;          /* (solve_begin has made the launch) */
     if (ahead && enqueue_export(s, nullptr) != TQGPU_OK) return TQGPU_ENODEVICE;
     rc = solve_end(s, o, cx, res);
     if (rc == TQGPU_ETIMEOUT) rc = solve_after_timeout(s, o, cx.env, res);
-    else if (rc == TQGPU_OK && ahead && res->n_launches == launches0) { s->export_valid = true; s->export_dev_only = false; }
+    else if (rc == TQGPU_OK && ahead && res->n_launches == launches0) s->out.packed_and_downloading();
     return rc;
-}
-
-extern "C" int tqgpu_set_export_ahead(tqgpu_solver *s, int on) {
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    s->export_ahead = on != 0;
-    s->export_valid = false;
-    return TQGPU_OK;
 }
 
 /* n solves of the same problem from the same starting duals, one after the other (each waits for its verdict), as the reference's
@@ -4919,7 +4572,7 @@ static void mpc_after_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, i
 static int solve_batch_impl(tqgpu_solver **solvers, int n, const tqgpu_opts *o, tqgpu_result *results, MpcBatch *mb) {
     if (!solvers || n < 1 || !o || !results) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: bad arguments");
     for (int i = 0; i < n; i++) if (!solvers[i]) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: null mirror");
-    for (int i = 0; i < n; i++) if (solvers[i]->pshard && solvers[i]->nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: a member is one rank of a sharded solve (tqgpu_pshard_init)");
+    for (int i = 0; i < n; i++) if (solvers[i]->pshard.on && solvers[i]->shard.nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve_batch: a member is one rank of a sharded solve (tqgpu_pshard_init)");
     BatchGuard guard(solvers, n);
     const SolveEnv env = read_solve_env(true);
     for (int k = 0; k < n; k++) {          /* as tqgpu_solve: a mirror that backed off the persistent path returns to it after PERSIST_BACKOFF solves */
@@ -4987,726 +4640,9 @@ extern "C" int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_op
     return TQGPU_OK;
 }
 
+#include "tdunes_kkt.hpp"
 #include "tdunes_mpc.hpp"
-
-/* ============================================================================================ */
-/* sharded mode: one tree over several devices                                  */
-/* ============================================================================================ */
-
-namespace {
-
-/* The partition of a uniform tree over `N` ranks, host arithmetic only: tiers whose subtree count is a multiple of N
- * are partitioned by contiguous subtree ranges, the tiers above are replicated.  Used by shard_build_lists and exported as
- * tqgpu_shard_plan (the CPU tests compare it with the Python planner the gloo protocol tests use). */
-struct ShardPlanHost {
-    int part_top = -1, lb = 0, gh_counted = 0;
-    int bnd_b0 = 0, bnd_bn = 0, bnd_own0 = 0, bnd_ownn = 0;
-    std::vector<int> gh, nodes, nodes_cnt, blks;
-};
-
-int shard_plan_host(int MD, int NX, int Nh, const std::vector<int> &tier_l0, const std::vector<int> &tier_grid, int N, int r, ShardPlanHost &P) {
-    const int nt = (int)tier_l0.size();
-    /* highest partitioned tier: subtree count divisible by the number of ranks */
-    P.part_top = -1;
-    for (int i = 0; i < nt - 1; i++) if (tier_grid[i] % N == 0 && tier_grid[i] >= N) P.part_top = i;
-    if (P.part_top < 0) return fail(TQGPU_EUNSUPPORTED, "tree too small to shard over this many ranks");
-    const int lb = tier_l0[P.part_top], l00 = tier_l0[0];
-    P.lb = lb;
-    {
-        const int gb = uni_width(MD, lb), w = gb / N;
-        P.bnd_b0 = NX * uni_first(MD, lb); P.bnd_bn = NX * gb; P.bnd_own0 = NX * r * w; P.bnd_ownn = NX * w;
-    }
-    std::vector<int> &gh = P.gh, &nodes = P.nodes, &nodes_cnt = P.nodes_cnt, &blks = P.blks;
-    gh.clear(); nodes.clear(); nodes_cnt.clear(); blks.clear();
-    /* owned */
-    for (int l = lb; l <= Nh; l++) {
-        const int w = uni_width(MD, l) / N, f0 = uni_first(MD, l) + r * w;
-        for (int i = 0; i < w; i++) {
-            nodes.push_back(f0 + i); nodes_cnt.push_back(f0 + i);
-            if (l < Nh) blks.push_back(f0 + i);
-            if (l < l00) gh.push_back(f0 + i);
-        }
-    }
-    P.gh_counted = (int)gh.size();
-    /* replicated (levels above the boundary): computed by every rank, counted by rank 0 only */
-    for (int l = 0; l < lb; l++) {
-        const int w = uni_width(MD, l), f0 = uni_first(MD, l);
-        for (int i = 0; i < w; i++) {
-            nodes.push_back(f0 + i); gh.push_back(f0 + i);
-            if (r == 0) { nodes_cnt.push_back(f0 + i); blks.push_back(f0 + i); }
-        }
-    }
-    if (r == 0) P.gh_counted = (int)gh.size();
-    return TQGPU_OK;
-}
-
-int shard_build_lists(tqgpu_solver *s) {
-    const int N = s->nranks;
-    ShardPlanHost P;
-    int rcp = shard_plan_host(s->fMD, s->fNX, s->Nh, s->tier_l0, s->tier_grid, N, s->rank, P);
-    if (rcp) return rcp;
-    s->part_top = P.part_top;
-    s->bnd_b0 = P.bnd_b0; s->bnd_bn = P.bnd_bn; s->bnd_own0 = P.bnd_own0; s->bnd_ownn = P.bnd_ownn;
-    std::vector<int> &gh = P.gh, &nodes = P.nodes, &nodes_cnt = P.nodes_cnt, &blks = P.blks;
-    s->gh_counted = P.gh_counted;
-    s->gh_n = (int)gh.size(); s->n_nodes = (int)nodes.size(); s->n_nodes_counted = (int)nodes_cnt.size(); s->n_blk_counted = (int)blks.size();
-    const size_t ints = gh.size() + nodes.size() + nodes_cnt.size() + blks.size() + 16;
-    const size_t bytes = ints * sizeof(int) + (3 * (size_t)N + 8) * sizeof(double) + 1024;
-    s->mem.release(s->shard_slab);
-    if (int rc = s->mem.zeroed(s->shard_slab, bytes, TQGPU_ENODEVICE, "the shard lists")) return rc;
-    char *p = static_cast<char *>(s->shard_slab);
-    s->d_xerr = reinterpret_cast<double *>(p); p += sizeof(double) * (size_t)(N + 2);
-    s->d_xs = reinterpret_cast<double *>(p); p += sizeof(double) * (size_t)(2 * N + 2);
-    auto put = [&](std::vector<int> &v, int *&dst) -> int {
-        dst = reinterpret_cast<int *>(p); p += sizeof(int) * (v.size() + 2);
-        if (!v.empty() && hipMemcpy(dst, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(TQGPU_ENODEVICE, "shard list upload failed");
-        return TQGPU_OK;
-    };
-    int rc;
-    if ((rc = put(gh, s->d_gh_list)) || (rc = put(nodes, s->d_node_list)) || (rc = put(nodes_cnt, s->d_node_cnt_list)) || (rc = put(blks, s->d_blk_list))) return rc;
-    return TQGPU_OK;
-}
-
-void set_shard(tqgpu_solver *s, int rank, int nranks, bool on) { s->rank = rank; s->nranks = nranks; s->sharded = on; }
-
-/* the table of the ranks' slabs (sharded persistent launch), host to device */
-int upload_peers(tqgpu_solver *s) {
-    HIP_TRY(hipMemcpy(s->d_peers, s->h_peers, sizeof(s->h_peers), hipMemcpyHostToDevice));
-    return TQGPU_OK;
-}
-
-}  // namespace
-
-extern "C" int tqgpu_shard_unique_id(void *id128) {
-    if (!id128) return fail(TQGPU_EINVAL, "null id buffer");
-    int rc = rccl_load();
-    if (rc) return rc;
-    RcclApi::UniqueId id;
-    NCCL_TRY(g_rccl.GetUniqueId(&id));
-    memcpy(id128, &id, sizeof(id));
-    return TQGPU_OK;
-}
-
-/* the partition plan without a device (host arithmetic of shard_build_lists): uniform complete md-ary tree with Nh block levels, tiers
- * of the fused path (3 levels for md = 2, 2 for md <= 4, else 1).  Lists may be NULL / caps 0 to query the sizes only. */
-extern "C" int tqgpu_shard_plan(int md, int nx, int Nh, int nranks, int rank, int *part_top, int *boundary_level, int *gh_counted,
-                                int *gh_list, int gh_cap, int *gh_n, int *owned_nodes, int owned_cap, int *owned_n) {
-    if (md < 2 || Nh < 2 || nranks < 1 || rank < 0 || rank >= nranks) return fail(TQGPU_EINVAL, "tqgpu_shard_plan: bad arguments");
-    const int TH = md == 2 ? 3 : (md <= 4 ? 2 : 1);
-    std::vector<int> l0v, gridv;
-    for (const UniTier &t : uni_tiers(Nh, TH, md)) { l0v.push_back(t.l0); gridv.push_back(t.grid); }
-    ShardPlanHost P;
-    int rc = shard_plan_host(md, nx, Nh, l0v, gridv, nranks, rank, P);
-    if (rc) return rc;
-    if (part_top) *part_top = P.part_top;
-    if (boundary_level) *boundary_level = P.lb;
-    if (gh_counted) *gh_counted = P.gh_counted;
-    if (gh_n) *gh_n = (int)P.gh.size();
-    if (gh_list) for (int i = 0; i < (int)P.gh.size() && i < gh_cap; i++) gh_list[i] = P.gh[(size_t)i];
-    /* owned nodes = the partitioned part of the node list (levels >= boundary), in level order */
-    int no = 0;
-    const int first_repl = uni_first(md, P.lb);
-    for (int v : P.nodes) if (v >= first_repl) { if (owned_nodes && no < owned_cap) owned_nodes[no] = v; no++; }
-    if (owned_n) *owned_n = no;
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_shard_init(tqgpu_solver *s, int rank, int nranks, const void *id128) {
-    SETTLE(s);
-    if (!s || nranks < 1 || rank < 0 || rank >= nranks) return fail(TQGPU_EINVAL, "tqgpu_shard_init: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->comm) { (void)g_rccl.CommDestroy(s->comm); s->comm = nullptr; }      /* a second call replaces the communicator, it does not leak it */
-    /* one rank WITHOUT a communicator = back to the unsharded mirror; one rank WITH one = the sharded code path on a single device
-     * (every exchange is a one-rank in-place all-gather): exercises rccl_load / ncclCommInitRank / ncclAllGather where only one GPU exists */
-    if (nranks == 1 && !id128) { set_shard(s, 0, 1, false); return TQGPU_OK; }
-    if (s->fast < 0 || !s->use_fast || s->mstage) return fail(TQGPU_EUNSUPPORTED, "sharding needs the fused uniform-tree path");
-    set_shard(s, rank, nranks, true);
-    s->export_valid = false;
-    int rc = shard_build_lists(s);
-    if (rc) { set_shard(s, 0, 1, false); return rc; }
-    if (id128) {
-        if ((rc = rccl_load())) { set_shard(s, 0, 1, false); return rc; }
-        RcclApi::UniqueId id;
-        memcpy(&id, id128, sizeof(id));
-        NCCL_TRY(g_rccl.CommInitRank(&s->comm, nranks, id, rank));
-    }
-    return TQGPU_OK;
-}
-
-/* after a sharded solve every rank holds valid x,u,lambda,... only for its own and the replicated
- * nodes: gather the partitioned ranges so that tqgpu_get_solution returns the full solution */
-extern "C" int tqgpu_shard_gather_solution(tqgpu_solver *s) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    if (!s->sharded) return TQGPU_OK;
-    if (!s->comm) return fail(TQGPU_ECOMM, "no communicator (virtual ranks gather through tqgpu_solve_virtual_ranks)");
-    HIP_TRY(hipSetDevice(s->device));
-    if (int rc = allgather_rccl(s, solution_ranges(s))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-
-/* ============================================================================================ */
-/* ONE tree over several devices INSIDE the persistent launch                                   */
-/* ============================================================================================ */
-/* The single-device persistent launch is a set of workgroups that talk through tagged words in one slab (tdunes_persist.hpp).
- * Sharded, the SAME set of workgroups is dealt over one launch per device: tiers whose subtree count is a multiple of the number of
- * ranks go to the ranks by contiguous subtree ranges, the tiers above them to rank 0 -- no workgroup exists twice,
- * so there is nothing to keep consistent but the words themselves.  Every rank has a slab of the same layout; a producer writes
- * each word into every slab (system-scope stores into peer-mapped memory), a consumer polls its own.  What crosses devices per
- * Newton iteration: the Schur records and x / QinvCal of the boundary subtree roots and every workgroup's termination and
- * dual-function partials upwards, the step of the boundary blocks, the line-search commands and the halt word downwards; no
- * collective, no host in the loop.  RCCL (or any transport the caller has: tqgpu_pshard_pack / _unpack) is only used to collect
- * the solution afterwards.  Every rank must call tqgpu_pshard_solve the same number of times (the launch number tags the words). */
-extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
-    SETTLE(s);
-    if (!s || nranks < 1 || nranks > 8 || rank < 0 || rank >= nranks) return fail(TQGPU_EINVAL, "tqgpu_pshard_init: bad arguments (1 .. 8 ranks)");
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->persist_ok || s->mstage || s->fast < 0 || !s->use_fast || !s->use_persist) return fail(TQGPU_EUNSUPPORTED, "sharding inside the persistent launch needs the persistent path of a uniform complete tree");
-    if (!shard_instantiated(s->fast)) return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape (SHARD_TABLE)");
-    switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: { int rca = allow_lds(f_persist_sh<nx, nu, md, 1>, s->lds_persist); if (!rca) rca = allow_lds(f_persist_sh<nx, nu, md, 0>, s->lds_persist); if (rca) return rca; } break;
-        SHARD_TABLE(X)
-#undef X
-        default: break;
-    }
-    int nwg = 0, top = -1;
-    if (tqgpu_pshard_plan(s->fMD, s->Nh, nranks, rank, nullptr, 0, &nwg, &top, nullptr) != 0) return fail(TQGPU_EUNSUPPORTED, "tree too small to shard over this many ranks");
-    std::vector<int> map((size_t)std::max(nwg, 1));
-    (void)tqgpu_pshard_plan(s->fMD, s->Nh, nranks, rank, map.data(), nwg, &nwg, &top, nullptr);
-    map.resize((size_t)nwg);
-    if (nranks == 1) top = s->n_tiers - 1;
-    if ((int)map.size() > s->co_capacity) return fail(TQGPU_EUNSUPPORTED, "this rank's workgroups cannot all be resident");
-    s->mem.release(s->ps_wg_map);
-    if (int rc = s->mem.device(s->ps_wg_map, sizeof(int) * std::max<size_t>(map.size(), 1), TQGPU_ENODEVICE, "this rank's workgroup table")) return rc;
-    HIP_TRY(hipMemcpy(s->ps_wg_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
-    s->ps_G = (int)map.size();
-    /* First contact with real xGMI is somebody else's run, so the two things a peer's writes depend on are settled by construction:
-     * (a) the slab the peers write into is FINE-GRAINED memory (coarse-grained hipMalloc memory is only guaranteed coherent across
-     *     devices at kernel boundaries; this kernel polls it while the peers write), and
-     * (b) the polls are system-scope loads (ps_sys: f_persist_sh<.., 1>, compiled with TQ_LD_SCOPE = system).
-     * TREEQP_AMD_PSHARD_COARSE=1 / TREEQP_AMD_PSHARD_AGENT=1 restore the single-device combination for an A/B on a node. */
-    s->ps_sys = !getenv("TREEQP_AMD_PSHARD_AGENT");
-    if (!s->ps_fine && !getenv("TREEQP_AMD_PSHARD_COARSE")) {
-        void *fresh = nullptr;
-        if (int rc = s->mem.device(fresh, s->sync_bytes, TQGPU_ENODEVICE, "the fine-grained hand-over slab", Owned::FINE_GRAINED)) return rc;
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        char *ob = static_cast<char *>(s->sync_slab), *nb = static_cast<char *>(fresh);
-        auto mv = [&](auto *&q) { if (q) q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(nb + (reinterpret_cast<char *>(q) - ob)); };
-        PSync &Y = s->psync;
-        mv(Y.sch); mv(Y.dlt); mv(Y.ndt); mv(Y.parts); mv(Y.errs); mv(Y.cmd); mv(Y.vrd); mv(Y.bparts); mv(Y.sgt); mv(Y.rfl); mv(Y.halt); mv(Y.timeout); mv(Y.base); mv(Y.verdict); mv(Y.anc);
-        s->mem.release(s->sync_slab);
-        s->sync_slab = fresh;
-        s->ps_fine = true;
-        s->pitems_key.clear();                                             /* (a cached batch descriptor would hold the old slab) */
-    }
-    s->export_valid = false;
-    s->pshard = true; s->rank = rank; s->nranks = nranks; s->part_top = nranks > 1 ? top : -1;
-    s->psync.npeer = nranks;
-    s->psync.anc_local = (nranks == 1 || top >= 1) ? 1 : 0;          /* tiers 0 .. top are dealt over the ranks by contiguous subtree ranges: with top >= 1 a tier-1 workgroup sits with the bottom-tier workgroups below it */
-    s->psync.relay_wg = (rank > 0 && !map.empty()) ? map[0] : -1;          /* ranks without the top workgroup: their first workgroup passes the verdict on to the host */
-    for (int r = 0; r < 8; r++) s->h_peers[r] = s->psync.base;             /* until connected: own slab */
-    if (int rc = upload_peers(s)) return rc;
-    s->psync.nap = nap_for_grid(s->ps_G);
-    s->launch_no = 0;
-    HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-
-/* peer `r` lives in this process (several mirrors on one device, or on several devices with peer access enabled by the caller) */
-extern "C" int tqgpu_pshard_connect_local(tqgpu_solver *s, int r, tqgpu_solver *peer) {
-    SETTLE(s);
-    if (!s || !peer || !s->pshard || r < 0 || r >= s->nranks || !peer->sync_slab || peer->sync_bytes != s->sync_bytes) return fail(TQGPU_EINVAL, "tqgpu_pshard_connect_local: bad arguments");
-    if (peer->device != s->device) {
-        HIP_TRY(hipSetDevice(s->device));
-        hipError_t e = hipDeviceEnablePeerAccess(peer->device, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(TQGPU_ECOMM, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
-        (void)hipGetLastError();
-    }
-    s->h_peers[r] = static_cast<unsigned long long *>(peer->sync_slab);
-    return upload_peers(s);
-}
-/* peers in other processes: an IPC handle of this rank's slab (64 bytes) out, the peers' handles in */
-extern "C" int tqgpu_pshard_ipc_export(tqgpu_solver *s, void *handle64) {
-    if (!s || !handle64 || !s->sync_slab) return fail(TQGPU_EINVAL, "tqgpu_pshard_ipc_export: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
-    hipIpcMemHandle_t h;
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-    hipError_t e = hipIpcGetMemHandle(&h, s->sync_slab);
-    if (e != hipSuccess) return fail(TQGPU_ECOMM, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e));
-    memcpy(handle64, &h, 64);
-    return TQGPU_OK;
-}
-extern "C" int tqgpu_pshard_ipc_connect(tqgpu_solver *s, int r, const void *handle64) {
-    if (!s || !handle64 || !s->pshard || r < 0 || r >= s->nranks || r == s->rank) return fail(TQGPU_EINVAL, "tqgpu_pshard_ipc_connect: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
-    hipIpcMemHandle_t h;
-    memcpy(&h, handle64, 64);
-    void *ptr = nullptr;
-    hipError_t e = hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess);
-    if (e != hipSuccess) return fail(TQGPU_ECOMM, std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(e));
-    if (s->ps_ipc[r]) (void)hipIpcCloseMemHandle(s->ps_ipc[r]);
-    s->ps_ipc[r] = ptr;
-    s->h_peers[r] = static_cast<unsigned long long *>(ptr);
-    return upload_peers(s);
-}
-
-/* one solve in two halves (so that one process can drive several ranks): _begin enqueues this rank's launch, _end waits for the
- * verdict.  All ranks' launches have to be in flight together: they wait for each other (bounded: 0.5 s, then TQGPU_ETIMEOUT). */
-extern "C" int tqgpu_pshard_begin(tqgpu_solver *s, const tqgpu_opts *o) {
-    SETTLE(s);
-    if (!s || !o || !s->pshard) return fail(TQGPU_EINVAL, "tqgpu_pshard_begin: not a sharded mirror");
-    HIP_TRY(hipSetDevice(s->device));
-    if (o->profile || o->maxIter <= 0 || o->checkLastActiveSet == 2) return fail(TQGPU_EUNSUPPORTED, "sharded persistent solve: default solve options only (no profiling, no factor keeping)");
-    Opts O;
-    if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    if (launch_no_after(s->launch_no) == 0)
-        return fail(TQGPU_EUNSUPPORTED, "65535 sharded solves since the launch numbers were last reset: call tqgpu_pshard_rewind on every rank, between two barriers of the caller's "
-                                        "(the 16-bit launch number tags the hand-over words; a single device wipes its slab when it wraps, ranks that write into each other's slabs cannot do that on their own)");
-    memset(s->h_res, 0, sizeof(HostRes));
-    int launches = 0;
-    s->solve_no++;
-    s->export_valid = false;
-    return launch_persist(s, O, launches, 1);
-}
-/* launch numbers back to zero and the slab wiped; peers stay connected.  EVERY rank, with no sharded solve in flight anywhere (a barrier
- * of the caller's before and after): a peer's launch that is still running, or already running again, writes into the slab being wiped */
-extern "C" int tqgpu_pshard_rewind(tqgpu_solver *s) {
-    SETTLE(s);
-    if (!s || !s->pshard) return fail(TQGPU_EINVAL, "tqgpu_pshard_rewind: not a sharded mirror");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    /* (hipMemset of device memory may return before the wipe has happened; it runs on the null stream, which the solver's non-blocking
-     * stream does not wait for: the wipe goes on the solver's stream and is waited for -- found by the 100 000-solve soak, where the
-     * first C3 solve after a rewind lost words to the wipe) */
-    HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->launch_no = 0;
-    return TQGPU_OK;
-}
-/* tqgpu_pshard_end without a verdict: a time-out of a bounded wait (the sticky word, cleared here), or the error the caller names */
-static int pshard_no_verdict(tqgpu_solver *s, const char *timeout_hint, int code, const char *text) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    unsigned tmo = 0;
-    if (int rc = read_timeout_word(s, tmo)) return rc;
-    if (!tmo) return fail(code, text);
-    if (int rc = clear_timeout_word(s)) return rc;
-    return fail(TQGPU_ETIMEOUT, std::string("sharded persistent solve: a bounded wait for another rank's workgroups timed out") + timeout_hint);
-}
-extern "C" int tqgpu_pshard_end(tqgpu_solver *s, tqgpu_result *res) {
-    SETTLE(s);
-    if (!s || !res || !s->pshard) return fail(TQGPU_EINVAL, "tqgpu_pshard_end: not a sharded mirror");
-    HIP_TRY(hipSetDevice(s->device));
-    /* the verdict reaches every rank's host through its pinned result block: written by the top workgroup (rank 0) or passed on from the
-     * rank's slab by its relay workgroup -- no stream synchronisation on the way (the state write-back of the other workgroups is still
-     * running; everything the host does next on this mirror is stream-ordered behind the launch).  (rank 0: the top workgroup's tagged
-     * words; the other ranks' relay workgroups post the plain block) */
-    if (!await_result_block(s->h_res, s->psync.seq, true))
-        return pshard_no_verdict(s, " (are all ranks' launches in flight together?)", TQGPU_ECOMM, "sharded persistent solve: no verdict from the top workgroup");
-    const Ctrl &c = *s->h_ctrl;
-    if (!c.done)
-        return pshard_no_verdict(s, "", TQGPU_EUNSUPPORTED, "sharded persistent solve: the launch ended without a verdict (tag space exhausted: more than 60000 passes)");
-    fill_result(res, c, 1, s->rank == 0 ? 1e-8 * (double)(s->h_res->t_end - s->h_res->t_start) : 0.0);
-    s->last_iter = c.iter;
-    return TQGPU_OK;
-}
-
-/* what this rank holds of the solution (its chunk of every partitioned range; rank 0: also the levels above the partition), packed
- * into a host buffer, and the inverse: the transport hook for callers that collect the solution themselves (any all-gather of
- * equal-sized buffers: tqgpu_pshard_pack_size is the same on every rank) */
-namespace {
-struct PsRange { double *base; size_t n; };
-std::vector<PsRange> pshard_owned_ranges(tqgpu_solver *s, int rank) {
-    std::vector<PsRange> out;
-    const int MD = s->fMD, NX = s->fNX, NU = s->fNU, N = s->nranks;
-    const Data &D = s->D;
-    double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
-    const int lb = N > 1 ? s->tier_l0[s->part_top] : s->Nh + 1;
-    for (int l = 0; l <= s->Nh; l++) {
-        const int wl = uni_width(MD, l);
-        const size_t f0 = (size_t)uni_first(MD, l);
-        /* node data (x, u, ...) of level l belongs to the workgroup that owns the node; the duals of a node's own edge belong to the
-         * BLOCK of its parent, one level up: the duals of the boundary level are the top tiers' (rank 0) */
-        for (int what = 0; what < 2; what++) {
-            const int lbw = what == 0 ? lb : lb + 1;
-            size_t first, cnt;
-            if (l >= lbw) { cnt = (size_t)wl / N; first = f0 + (size_t)rank * cnt; }
-            else { if (rank != 0) continue; cnt = (size_t)wl; first = f0; }
-            if (what == 0) {
-                double *xs[] = {D.x, D.xUnc, D.xUncS};
-                for (double *a : xs) out.push_back({a + NX * first, cnt * NX});
-                if (l < s->Nh) { double *us[] = {D.u, D.uUnc, D.uUncS}; for (double *a : us) out.push_back({a + NU * first, cnt * NU}); }
-            } else {
-                double *ls[] = {lamc, D.dlam};
-                for (double *a : ls) out.push_back({a + NX * first, cnt * NX});
-            }
-        }
-    }
-    return out;
-}
-/* rank `rank`'s ranges to the host buffer (to_host: tqgpu_pshard_pack) or from it (tqgpu_pshard_unpack) */
-int copy_owned_ranges(tqgpu_solver *s, int rank, double *buf, long cap, bool to_host) {
-    size_t o = 0;
-    for (auto &rg : pshard_owned_ranges(s, rank)) {
-        if ((long)(o + rg.n) > cap) return fail(TQGPU_EINVAL, to_host ? "tqgpu_pshard_pack: buffer too small" : "tqgpu_pshard_unpack: buffer too small");
-        if (to_host) HIP_TRY(hipMemcpy(buf + o, rg.base, sizeof(double) * rg.n, hipMemcpyDeviceToHost));
-        else HIP_TRY(hipMemcpy(rg.base, buf + o, sizeof(double) * rg.n, hipMemcpyHostToDevice));
-        o += rg.n;
-    }
-    return TQGPU_OK;
-}
-}  // namespace
-extern "C" long tqgpu_pshard_pack_size(tqgpu_solver *s) {
-    if (!s || !s->pshard) return -1;
-    size_t n = 0;
-    for (auto &rg : pshard_owned_ranges(s, 0)) n += rg.n;          /* rank 0 holds the most */
-    return (long)n;
-}
-extern "C" int tqgpu_pshard_pack(tqgpu_solver *s, double *out, long cap) {
-    SETTLE(s);
-    if (!s || !out || !s->pshard) return fail(TQGPU_EINVAL, "tqgpu_pshard_pack: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
-    /* tqgpu_pshard_end returns on the verdict word while the workgroups still write their state back, and the copies below run on the
-     * null stream, which the solver's non-blocking stream does not order: wait for the launch first */
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return copy_owned_ranges(s, s->rank, out, cap, true);
-}
-extern "C" int tqgpu_pshard_unpack(tqgpu_solver *s, int src_rank, const double *in, long n_in) {
-    SETTLE(s);
-    if (!s || !in || !s->pshard || src_rank < 0 || src_rank >= s->nranks) return fail(TQGPU_EINVAL, "tqgpu_pshard_unpack: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));          /* (as tqgpu_pshard_pack: this rank's own write-back must not land on top of the peers' shares) */
-    return copy_owned_ranges(s, src_rank, const_cast<double *>(in), n_in, false);
-}
-
-/* n mirrors of the SAME problem in this process (one device: a rehearsal with real concurrency -- n launches on n streams that wait
- * for each other inside the kernels -- or n devices with peer access): connect, solve, collect the solution into every mirror */
-extern "C" int tqgpu_pshard_solve_local(tqgpu_solver **R, int n, const tqgpu_opts *o, tqgpu_result *res) {
-    for (int r_ = 0; R && r_ < n; r_++) SETTLE(R[r_]);
-    if (!R || n < 1 || n > 8 || !o || !res) return fail(TQGPU_EINVAL, "tqgpu_pshard_solve_local: bad arguments");
-    for (int r = 0; r < n; r++) if (!R[r] || !R[r]->pshard || R[r]->nranks != n || R[r]->rank != r) return fail(TQGPU_EINVAL, "tqgpu_pshard_solve_local: mirror r must be tqgpu_pshard_init(r, n)");
-    for (int r = 0; r < n; r++) for (int q = 0; q < n; q++) { int rc = tqgpu_pshard_connect_local(R[r], q, R[q]); if (rc) return rc; }
-    for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));          /* uploads done: the launches go out back to back */
-    if (R[0]->launch_no >= 0x8000u) for (int r = 0; r < n; r++) { int rc = tqgpu_pshard_rewind(R[r]); if (rc) return rc; }      /* (all ranks idle here) */
-    for (int r = 0; r < n; r++) { int rc = tqgpu_pshard_begin(R[r], o); if (rc) return rc; }
-    int first = TQGPU_OK;
-    std::string msg;
-    for (int r = 0; r < n; r++) { int rc = tqgpu_pshard_end(R[r], &res[r]); if (rc && !first) { first = rc; msg = g_err; } }
-    if (first) return fail(first, msg);
-    std::vector<double> buf((size_t)std::max<long>(tqgpu_pshard_pack_size(R[0]), 1));
-    for (int src = 0; src < n; src++) {
-        int rc = tqgpu_pshard_pack(R[src], buf.data(), (long)buf.size());
-        if (rc) return rc;
-        for (int dst = 0; dst < n; dst++) if (dst != src && (rc = tqgpu_pshard_unpack(R[dst], src, buf.data(), (long)buf.size()))) return rc;
-    }
-    return TQGPU_OK;
-}
-
-/* Diagnostic / test entry: run `n` mirrors of the SAME problem as ranks 0..n-1 of a sharded solve
- * inside one process on one device, exchanging by device copies.  Validates partition, hand-off and
- * decision logic without a multi-GPU node.  Every mirror must have been shard-initialised with
- * (rank = its index, nranks = n, id128 = NULL).  The full solution is gathered into every mirror. */
-extern "C" int tqgpu_solve_virtual_ranks(tqgpu_solver **R, int n, const tqgpu_opts *o, tqgpu_result *res) {
-    for (int r_ = 0; R && r_ < n; r_++) SETTLE(R[r_]);
-    if (!R || n < 2 || !o || !res) return fail(TQGPU_EINVAL, "tqgpu_solve_virtual_ranks: bad arguments");
-    for (int r = 0; r < n; r++) if (!R[r] || R[r]->nranks != n || R[r]->rank != r || R[r]->comm) return fail(TQGPU_EINVAL, "mirror is not virtual rank r of n");
-    HIP_TRY(hipSetDevice(R[0]->device));
-    Opts O;
-    if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    int launches = 0, rc;
-    for (int r = 0; r < n; r++) {
-        SolveCtx prologue(SolveEnv(), Route::TIERED);          /* its launch count is dropped: n_launches reports the iterations' and trials' launches */
-        if ((rc = begin_enqueued(R[r], prologue))) return rc;
-    }
-    auto exchange = [&](int which) { return allgather_virtual(R, n, [which](tqgpu_solver *m) { return exchange_ranges(m, which); }); };
-    bool finished = o->maxIter <= 0;
-    int h = 0;
-    while (!finished) {
-        for (int r = 0; r < n; r++) launch_fast_phase(R[r], O, h, 0, launches);
-        if ((rc = exchange(1))) return rc;
-        for (int r = 0; r < n; r++) launch_fast_phase(R[r], O, h, 1, launches);
-        if ((rc = exchange(2))) return rc;
-        for (int r = 0; r < n; r++) launch_fast_phase(R[r], O, h, 2, launches);
-        for (int r = 0; r < n; r++) if ((rc = read_ctrl(R[r]))) return rc;
-        while (!R[0]->h_ctrl->done && R[0]->h_ctrl->ls_pending) {
-            const int it = R[0]->h_ctrl->iter, t = R[0]->h_ctrl->ls_iter;
-            for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, Route::TIERED, it, t, 0, launches);
-            if ((rc = exchange(2))) return rc;
-            for (int r = 0; r < n; r++) launch_trial_phase(R[r], O, Route::TIERED, it, t, 1, launches);
-            for (int r = 0; r < n; r++) if ((rc = read_ctrl(R[r]))) return rc;
-        }
-        for (int r = 1; r < n; r++)
-            if (R[r]->h_ctrl->iter != R[0]->h_ctrl->iter || R[r]->h_ctrl->done != R[0]->h_ctrl->done || R[r]->h_ctrl->status != R[0]->h_ctrl->status)
-                return fail(TQGPU_ECOMM, "virtual ranks took different decisions");
-        h = R[0]->h_ctrl->iter;
-        finished = R[0]->h_ctrl->done != 0;
-    }
-    /* gather the partitioned solution ranges into every mirror (nothing iterated: only the wait for the streams) */
-    if (o->maxIter > 0) { if ((rc = allgather_virtual(R, n, solution_ranges))) return rc; }
-    else for (int r = 0; r < n; r++) {
-        /* as end_enqueued: reported as "maximum iterations" with every count and both values 0, whatever the last solve left in the host copy */
-        HIP_TRY(hipStreamSynchronize(R[r]->stream));
-        memset(R[r]->h_ctrl, 0, sizeof(Ctrl)); R[r]->h_ctrl->status = 1;
-    }
-    const Ctrl &c = *R[0]->h_ctrl;
-    fill_result(res, c, launches, 0.0);
-    for (int r = 0; r < n; r++) R[r]->last_iter = c.iter;
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_get_solution(tqgpu_solver *s, double *x, double *u, double *lam, double *mu_x, double *mu_u, double *dlam) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    const Data &D = s->D;
-    /* one packing kernel, one download into pinned memory, one synchronisation (ordered behind the solve on the stream) */
-    const double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
-    const int nxe = s->sum_nx - s->x_pad, nue = s->sum_nu, nl = s->sum_lam;
-    if (!s->export_valid) { int rce = enqueue_export(s, lamc); if (rce != TQGPU_OK) return rce; }      /* (else: went out behind the solve, tqgpu_set_export_ahead) */
-    else if (s->export_dev_only) {          /* packed behind a certified tqgpu_mpc_step, not downloaded yet */
-        HIP_TRY(hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * std::max<size_t>(s->out_doubles, 1), hipMemcpyDeviceToHost, st));
-        s->export_dev_only = false;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    const double *ox = s->h_out, *ou = ox + nxe, *ol = ou + nue, *od = ol + nl, *omx = od + nl, *omu = omx + nxe;
-    if (x && nxe > 0) memcpy(x, ox, sizeof(double) * (size_t)nxe);
-    if (u && nue > 0) memcpy(u, ou, sizeof(double) * (size_t)nue);
-    if (lam && nl > 0) memcpy(lam, ol, sizeof(double) * (size_t)nl);
-    if (dlam && nl > 0) memcpy(dlam, od, sizeof(double) * (size_t)nl);
-    if (mu_x && nxe > 0) memcpy(mu_x, omx, sizeof(double) * (size_t)nxe);
-    if (mu_u && nue > 0) memcpy(mu_u, omu, sizeof(double) * (size_t)nue);
-    return TQGPU_OK;
-}
-
-/* ---- KKT residuals on the device ---- */
-namespace {
-/* the two kernels and the download of the result block, on the mirror's stream; nothing is waited for */
-int kkt_enqueue(tqgpu_solver *s, const KktPoint &P, bool per_node) {
-    hipLaunchKernelGGL(k_kkt, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, s->D, s->x_pad, P, s->d_kkt + KKT_HEAD);
-    hipLaunchKernelGGL(k_kkt_max, dim3(1), dim3(256), 0, s->stream, s->T.Nn, s->d_kkt + KKT_HEAD, s->d_kkt);
-    HIP_TRY(hipGetLastError());
-    const size_t n = KKT_HEAD + (per_node ? (size_t)KKT_CLASSES * s->Nn : 0);
-    HIP_TRY(hipMemcpyAsync(s->h_kkt, s->d_kkt, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
-    return TQGPU_OK;
-}
-void kkt_collect(const tqgpu_solver *s, double *res, int *node, double *per_node) {
-    if (res) memcpy(res, s->h_kkt, sizeof(double) * KKT_CLASSES);
-    if (node) memcpy(node, s->h_kkt + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
-    if (per_node) memcpy(per_node, s->h_kkt + KKT_HEAD, sizeof(double) * (size_t)KKT_CLASSES * s->Nn);
-}
-/* the point of a KKT check that reads the export block d_out (and Gen::mu) */
-KktPoint kkt_point_of_export(const tqgpu_solver *s) {
-    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), nue = (size_t)s->sum_nu, nl = (size_t)s->sum_lam;
-    KktPoint P;
-    P.x = s->d_out; P.u = P.x + nxe; P.lam = P.u + nue; P.mu_x = P.lam + 2 * nl; P.mu_u = P.mu_x + nxe;
-    P.mu_d = s->gen ? s->d_gmu : nullptr;
-    return P;
-}
-/* behind the solve of a certified tqgpu_mpc_step (setup_kkt has run): the packing into d_out with the dual buffer the DEVICE calls current -- the
- * host's h_ctrl->cur is the last solve's while this one runs --, k_kkt, k_kkt_max and the download of the head; nothing is waited for */
-int mpc_enqueue_certificate(tqgpu_solver *s) {
-    int rc;
-    if ((rc = enqueue_export(s, nullptr, false))) return rc;
-    MPC_COUNT(launches, 1 + (s->box ? 1 : 0) + (s->gen ? 1 : 0));
-    if ((rc = kkt_enqueue(s, kkt_point_of_export(s), false))) return rc;
-    MPC_COUNT(launches, 2); MPC_COUNT(copies, 1);
-    return TQGPU_OK;
-}
-/* what every entry point refuses: a rank of a sharded solve holds a part of the solution and runs a part of the launches */
-int kkt_refuse(const tqgpu_solver *s, const char *who) {
-    if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
-    if ((s->pshard || s->sharded) && s->nranks > 1)
-        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": this mirror is rank " + std::to_string(s->rank) + " of a sharded solve; KKT residuals are evaluated on single-device mirrors");
-    return TQGPU_OK;
-}
-/* the point of the last solve, where tqgpu_get_solution and tqgpu_get_mu_d read it: the export (enqueued here unless it went out ahead) and Gen::mu */
-int kkt_enqueue_last(tqgpu_solver *s, bool per_node) {
-    int rc;
-    if (s->solve_no == 0) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual: this mirror has not solved yet (tqgpu_kkt_residual_at takes any point)");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = setup_kkt(s, false))) return rc;
-    if (!s->export_valid && (rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
-    return kkt_enqueue(s, kkt_point_of_export(s), per_node);
-}
-}  // namespace
-
-extern "C" int tqgpu_kkt_residual(tqgpu_solver *s, double res[6], int node[6], double *per_node) {
-    SETTLE(s);
-    int rc;
-    if ((rc = kkt_refuse(s, "tqgpu_kkt_residual")) || (rc = kkt_enqueue_last(s, per_node != nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    kkt_collect(s, res, node, per_node);
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_kkt_residual_at(tqgpu_solver *s, const double *x, const double *u, const double *lam, const double *mu_x, const double *mu_u,
-                                     const double *mu_d, double res[6], int node[6], double *per_node) {
-    SETTLE(s);
-    int rc;
-    if ((rc = kkt_refuse(s, "tqgpu_kkt_residual_at"))) return rc;
-    if (!x || !u || !lam) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_at: x, u and lam are required");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = setup_kkt(s, true))) return rc;
-    /* the point through pinned memory in one copy; an array that was not given stays a null pointer for the kernel */
-    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), nue = (size_t)s->sum_nu, nl = (size_t)s->sum_lam, nr = (size_t)s->sum_nc;
-    size_t off = 0;
-    auto put = [&](const double *src, size_t n) -> const double * {
-        if (!src) return nullptr;
-        if (n) memcpy(s->h_kkt_pt + off, src, sizeof(double) * n);
-        const double *d = s->d_kkt_pt + off;
-        off += n;
-        return d;
-    };
-    KktPoint P;
-    P.x = put(x, nxe); P.u = put(u, nue); P.lam = put(lam, nl); P.mu_x = put(mu_x, nxe); P.mu_u = put(mu_u, nue); P.mu_d = put(mu_d, nr);
-    if (off) HIP_TRY(hipMemcpyAsync(s->d_kkt_pt, s->h_kkt_pt, sizeof(double) * off, hipMemcpyHostToDevice, s->stream));
-    if ((rc = kkt_enqueue(s, P, per_node != nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    kkt_collect(s, res, node, per_node);
-    return TQGPU_OK;
-}
-
-/* ---- tqgpu_kkt_residual_batch: per device one group; a group of KKT_BATCH_MIN members or more goes out as ONE set of launches on
- * its first member's stream (the lead's), anything else member by member on the members' own streams ---- */
-namespace {
-struct KktBatchStats { int launches = 0, copies = 0, waits = 0, batched = 0; };
-thread_local KktBatchStats g_kkt_stats;          /* of this thread's last tqgpu_kkt_residual_batch (tqgpu_kkt_batch_stats) */
-constexpr int KKT_BATCH_MIN = 2;                 /* members of one device from which the batched route is taken: at 2 C1 trees it measured 37 us against 64 us member by member (profiles/r12_kkt_batch_timing.txt) */
-constexpr size_t KKT_GRID_Y = 65535;             /* blockIdx.y is the member */
-
-struct KktGroup { int device; std::vector<int> idx; bool batched = false; };
-
-/* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
- * waves that return at once, and is checked member by member instead. */
-bool kkt_group_batched(tqgpu_solver **v, const KktGroup &g) {
-    if (g.idx.size() < (size_t)KKT_BATCH_MIN || g.idx.size() > KKT_GRID_Y) return false;
-    size_t sum = 0, mx = 0;
-    std::set<const tqgpu_solver *> seen;
-    for (int i : g.idx) {
-        if (!seen.insert(v[i]).second) return false;          /* a mirror named twice: two workgroups would reduce (and rewrite) one table */
-        sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn);
-    }
-    return mx * g.idx.size() <= 8 * sum + 4096;
-}
-
-/* one member on its own stream: the route of tqgpu_kkt_residual without the wait */
-int kkt_member_enqueue(tqgpu_solver *s, KktBatchStats &st) {
-    if (s->settle_stream && s->settle_stream != s->stream) st.waits++;
-    SETTLE(s);
-    st.launches += (s->export_valid ? 0 : 1 + (s->box ? 1 : 0) + (s->gen ? 1 : 0)) + 2;
-    st.copies++;
-    return kkt_enqueue_last(s, false);
-}
-
-/* A group on its lead's stream: the descriptors in one copy, the packing of the members that have not exported ahead (k_export_all_batch,
- * and the box and row overlays where some member has such nodes), k_kkt_batch, k_kkt_max_batch, the heads in one copy.  Nothing is
- * waited for here in the steady state -- a loop of tqgpu_solve_batch and this call on the same members -- where every member's solve
- * was part of a launch on this very stream (settle_stream), as in join_lead_stream.  A member's own stream is waited for only where it
- * may hold work this stream has not seen: uploads (stream_pending), an export that went out ahead, or a solve of its own that returned
- * on its verdict (a single launch may still write its state back then). */
-int kkt_group_enqueue(tqgpu_solver **v, const KktGroup &g, KktBatchStats &st) {
-    tqgpu_solver *lead = v[g.idx[0]];
-    const size_t n = g.idx.size();
-    int rc;
-    HIP_TRY(hipSetDevice(lead->device));
-    for (int i : g.idx) if ((rc = setup_kkt(v[i], false))) return rc;
-    if ((rc = grow_items(lead, lead->d_kitems, lead->h_kitems, lead->kitems_cap, n)) || (rc = grow_items(lead, lead->d_kheads, lead->h_kheads, lead->kheads_cap, n))) return rc;
-    int nn_all = 0, nn_box = 0, nn_gen = 0, cells = 0;          /* widths of the four grids (0: no launch) */
-    std::vector<hipStream_t> waited;                             /* streams this call has synchronised (a handful: one per wave of the batch solve at the most) */
-    auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
-    for (size_t m = 0; m < n; m++) {
-        tqgpu_solver *s = v[g.idx[m]];
-        const bool in_launch = s->settle_stream != nullptr;          /* its last solve was part of a batch launch that has not been waited for */
-        if (s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;          /* ... on this stream: ordered by it, and waited for with the heads; or on one this call has waited for already (the members of a later wave of the batch solve, behind their lead) */
-        else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); st.waits++; } SETTLE(s); }
-        const bool own_solve = !in_launch && s->solve_no != s->kkt_drained_at;
-        if (s->stream != lead->stream && (s->stream_pending || s->export_valid || own_solve)) {
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            s->stream_pending = false;
-            waited.push_back(s->stream);
-            st.waits++;
-        }
-        s->kkt_drained_at = s->solve_no;
-        KItem &it = lead->h_kitems[m];
-        it.T = s->T; it.D = s->D;
-        it.x_pad = s->x_pad; it.nxe = s->sum_nx - s->x_pad; it.nue = s->sum_nu; it.nl = s->sum_lam; it.nx0 = s->nx0;
-        it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
-        it.d_out = s->d_out; it.table = s->d_kkt + KKT_HEAD; it.head = lead->d_kheads[m].v;
-        it.P.x = s->d_out; it.P.u = it.P.x + it.nxe; it.P.lam = it.P.u + it.nue; it.P.mu_x = it.P.lam + 2 * (size_t)it.nl; it.P.mu_u = it.P.mu_x + it.nxe;
-        it.P.mu_d = s->gen ? s->d_gmu : nullptr;
-        it.needs_export = s->export_valid ? 0 : 1; it.box = s->box ? 1 : 0; it.gen = s->gen ? 1 : 0;
-        nn_all = std::max(nn_all, s->T.Nn);
-        if (it.needs_export) {
-            cells = std::max(cells, std::max(std::max(it.nxe, it.nue), std::max(it.nl, 1)));
-            if (it.box) nn_box = std::max(nn_box, s->T.Nn);
-            if (it.gen) nn_gen = std::max(nn_gen, s->T.Nn);
-        }
-    }
-    hipStream_t ls = lead->stream;
-    const unsigned ny = (unsigned)n;
-    HIP_TRY(hipMemcpyAsync(lead->d_kitems, lead->h_kitems, n * sizeof(KItem), hipMemcpyHostToDevice, ls)); st.copies++;
-    if (cells) { hipLaunchKernelGGL(k_export_all_batch, dim3((unsigned)((cells + 255) / 256), ny), dim3(256), 0, ls, lead->d_kitems); st.launches++; }
-    if (nn_box) { hipLaunchKernelGGL(k_export_box_batch, dim3((unsigned)nn_box, ny), dim3(WAVE), 0, ls, lead->d_kitems); st.launches++; }
-    if (nn_gen) { hipLaunchKernelGGL(k_export_gen_batch, dim3((unsigned)nn_gen, ny), dim3(WAVE), 0, ls, lead->d_kitems); st.launches++; }
-    hipLaunchKernelGGL(k_kkt_batch, dim3((unsigned)nn_all, ny), dim3(WAVE), 0, ls, lead->d_kitems); st.launches++;
-    hipLaunchKernelGGL(k_kkt_max_batch, dim3(ny), dim3(256), 0, ls, lead->d_kitems); st.launches++;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(lead->h_kheads, lead->d_kheads, n * sizeof(KHead), hipMemcpyDeviceToHost, ls)); st.copies++;
-    st.batched += (int)n;
-    return TQGPU_OK;
-}
-}  // namespace
-
-/* Everything goes out before the first wait.  The members' d_out is packed afterwards, their h_out is not: export_valid stays as it
- * was, so tqgpu_get_solution packs and downloads as it does behind tqgpu_kkt_residual. */
-extern "C" int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *res, int *node) {
-    if (!solvers || n < 0 || (n > 0 && !res)) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_batch: bad arguments");
-    int rc;
-    for (int i = 0; i < n; i++) {
-        if ((rc = kkt_refuse(solvers[i], "tqgpu_kkt_residual_batch"))) return rc;
-        if (solvers[i]->solve_no == 0) return fail(TQGPU_EINVAL, "tqgpu_kkt_residual_batch: member " + std::to_string(i) + " has not solved yet");
-    }
-    KktBatchStats &st = g_kkt_stats;
-    st = KktBatchStats();
-    const char *sw = getenv("TREEQP_AMD_KKT_BATCH");          /* =members: every member on its own stream, as a group of one goes */
-    const bool by_member = sw && strcmp(sw, "members") == 0;
-    std::vector<KktGroup> groups;
-    for (int i = 0; i < n; i++) {
-        auto g = std::find_if(groups.begin(), groups.end(), [&](const KktGroup &q) { return q.device == solvers[i]->device; });
-        if (g == groups.end()) { groups.push_back(KktGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
-        g->idx.push_back(i);
-    }
-    for (KktGroup &g : groups) {
-        g.batched = !by_member && kkt_group_batched(solvers, g);
-        if (g.batched) {
-            if ((rc = kkt_group_enqueue(solvers, g, st))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
-        } else for (int i : g.idx) if ((rc = kkt_member_enqueue(solvers[i], st))) return rc;
-    }
-    for (const KktGroup &g : groups) {
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        if (g.batched) { HIP_TRY(hipStreamSynchronize(lead->stream)); st.waits++; }
-        for (size_t m = 0; m < g.idx.size(); m++) {
-            const int i = g.idx[m];
-            if (!g.batched) { HIP_TRY(hipStreamSynchronize(solvers[i]->stream)); st.waits++; kkt_collect(solvers[i], res + (size_t)KKT_CLASSES * i, node ? node + (size_t)KKT_CLASSES * i : nullptr, nullptr); continue; }
-            const double *h = lead->h_kheads[m].v;
-            memcpy(res + (size_t)KKT_CLASSES * i, h, sizeof(double) * KKT_CLASSES);
-            if (node) memcpy(node + (size_t)KKT_CLASSES * i, h + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
-        }
-    }
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_kkt_batch_stats(int *launches, int *copies, int *waits, int *batched_members) {
-    const KktBatchStats &st = g_kkt_stats;
-    if (launches) *launches = st.launches;
-    if (copies) *copies = st.copies;
-    if (waits) *waits = st.waits;
-    if (batched_members) *batched_members = st.batched;
-    return TQGPU_OK;
-}
+#include "tdunes_shard.hpp"
 
 extern "C" int tqgpu_get_iteration_log(tqgpu_solver *s, int *ls_iters, double *iter_times, int cap) {
     SETTLE(s);

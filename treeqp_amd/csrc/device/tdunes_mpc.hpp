@@ -230,8 +230,8 @@ int root_kind_of(const tqgpu_solver *s) { return s->dense && !s->h_kind.empty() 
 
 int mpc_refuse(const tqgpu_solver *s, const char *who) {
     if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
-    if ((s->pshard || s->sharded) && s->nranks > 1)
-        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": this mirror is rank " + std::to_string(s->rank) + " of a sharded solve; MPC steps run on single-device mirrors");
+    if ((s->pshard.on || s->shard.on) && s->shard.nranks > 1)
+        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": this mirror is rank " + std::to_string(s->shard.rank) + " of a sharded solve; MPC steps run on single-device mirrors");
     return TQGPU_OK;
 }
 
@@ -362,8 +362,6 @@ struct MpcLive {          /* counts into g_mpc_stats while a step runs */
     MpcLive() { g_mpc_stats = MpcStats(); g_mpc_live = &g_mpc_stats; }
     ~MpcLive() { g_mpc_live = nullptr; }
 };
-
-int mpc_enqueue_certificate(tqgpu_solver *s);          /* (with the KKT entry points, below) */
 
 int mpc_post_one(tqgpu_solver *s) {
     unsigned long long *tag = reinterpret_cast<unsigned long long *>(s->mpc.h + s->mpc.nx0 + s->nu[0]);
@@ -761,9 +759,9 @@ static int mpc_step_impl(tqgpu_solver *s, const double *x0, int t0, const tqgpu_
     if (!ahead && (rc = behind())) return rc;
     memcpy(u0, s->mpc.h + s->mpc.nx0, sizeof(double) * (size_t)s->nu[0]);
     if (certify) {
-        memcpy(s->mpc.cert, s->h_kkt, sizeof(s->mpc.cert));
+        memcpy(s->mpc.cert, s->kkt.h, sizeof(s->mpc.cert));
         s->mpc.cert_valid = true;
-        s->export_valid = true; s->export_dev_only = true;          /* d_out holds the returned point: tqgpu_kkt_residual reads it there, tqgpu_get_solution downloads it */
+        s->out.packed_on_device();          /* d_out holds the returned point: tqgpu_kkt_residual reads it there, tqgpu_get_solution downloads it */
     }
     return TQGPU_OK;
 }
@@ -1018,12 +1016,12 @@ extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *
     MpcLive live;
     if ((rc = setup_sens(s))) return rc;
     s->sens.valid = false;
-    if (!s->export_valid) {
+    if (!s->out.valid) {
         if ((rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
         MPC_COUNT(launches, 1);
     }
     Sens S = s->sens.v;
-    S.x = s->d_out; S.u = S.x + (s->sum_nx - s->x_pad);
+    S.x = s->out.d; S.u = S.x + export_sizes(s).nxe;
     S.root_states = s->mpc.states ? 1 : 0;
     if (s->mpc.d) { S.A0 = s->mpc.d; S.S0 = s->mpc.S0 ? s->mpc.d + (size_t)s->mpc.nb * s->mpc.nx0 + s->mpc.nb : nullptr; }
     S.x0 = s->mpc.h;
