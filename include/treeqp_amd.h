@@ -619,6 +619,47 @@ int tqgpu_mpc_get_gain(tqgpu_solver *s, double *K, double *u0, double *x0_ref);
 int tqgpu_mpc_get_sensitivities(tqgpu_solver *s, double *dx, double *du, double *dlam);
 int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, int duals, int *n_clipped);
 
+/* ---- The adjoint of an MPC step: dL/dq, dL/dr, dL/db and dL/dx0 on the device ----------------------------------------------------------
+ * The reverse of the sensitivities above.  For a scalar loss L of the step's solution z = (x, u) and w = dL/dz, with the active set frozen
+ * at the point tqgpu_get_solution would return, the KKT system is symmetric: the adjoint is one more solve with the same dual Hessian M,
+ * with one right-hand side per column of w instead of nx0, and a right-hand side that is non-zero in every block.  P_k, M, C_c = [A_c B_c],
+ * W_p, Ut_p as above; w_k = [wx_k; wu_k], the phantom root states of an embedded x0-eliminated tree carry w = 0.
+ *   R                    rows of child c of p:  R_c = (P_c w_c)^x - C_c P_p w_p
+ *   M Y = R              the same tall Cholesky, the same regularisation rule of opts, the same n_reg.  Block by block with L, CholUt as the
+ *                        factorisation leaves them: leaf to root, every non-root block ii, deepest level first, t_ii = L_ii^-1 R_ii and
+ *                        R_dad[pos .. pos + nx_ii) -= CholUt_ii t_ii (the rows of different children of one parent are disjoint: no
+ *                        atomics); at the root t_0 = L_0^-1 R_0, Y_0 = L_0^-T t_0; root to leaves Y_ii = L_ii^-T ( t_ii - CholUt_ii' Y_dad[pos ..] ).
+ *   gb                   gb_c = Y_c  (dL/db_c, sum_lam entries)
+ *   gq, gr               [gq_k; gr_k] = -P_k ( w_k - [Y_k; 0] + sum_c C_c' Y_c )  for every node k ([Y_0; 0] = 0 at the root)
+ *   gx0                  eliminated root (tqgpu_mpc_set_root):  gx0 = sum_c A0_c' Y_c + S0' gr_0  (the second term where S0 was given);
+ *                        root with states (tqgpu_mpc_set_root_states):  gx0 = wx_0 + sum_c A_c' Y_c.
+ *   uniqueness           R lies in the range of M = E P E', so gq and gr are unique even where M is singular;
+ *                        gb is unique only when n_reg == 0, and on the same condition gx0 of an eliminated root.
+ *   tqgpu_mpc_adjoint    wx ((sum_nx without phantom root states) x nw) and wu (sum_nu x nw): column j is the flat layout of
+ *                        tqgpu_get_solution; either may be NULL, meaning zero.  One host-to-device copy of w through pinned memory, the
+ *                        launches (one wave per unit and column, the nw columns on grid dimension y, ordered by launch boundaries on the
+ *                        mirror's stream): 1 (R) + one per block level, deepest first (t, the push; the root completes Y_0) + one per
+ *                        block level below the root (Y) + 1 (gq, gr, gb, gx0), that is 2 Nh + 1; then one device-to-host copy of
+ *                        [gx0 | n_reg] and one wait.  The factor: where tqgpu_mpc_sensitivity (or an earlier tqgpu_mpc_adjoint) has left
+ *                        the factor of this point on the device, it is used as it is (built with the opts of that call); otherwise the
+ *                        call builds it first exactly as tqgpu_mpc_sensitivity does, Nh + 1 more launches (3 Nh + 2 in all), plus the
+ *                        packing of the point where that has not gone out.  Results are the same bit for bit either way, and column j of
+ *                        a call with nw columns is bit for bit the call with that column alone.  It works in buffers of its own
+ *                        (allocated on first use, again when nw grows, freed by tqgpu_destroy) and changes nothing a later solve,
+ *                        tqgpu_get_solution or tqgpu_kkt_residual reads, nor a stored sensitivity: tqgpu_mpc_predict and the getters
+ *                        above keep their values.  Counted into tqgpu_mpc_stats (2 copies, 1 wait).
+ *                        TQGPU_EINVAL, TQGPU_EUNSUPPORTED: wherever tqgpu_mpc_sensitivity returns them; TQGPU_EINVAL also for nw < 1;
+ *                        TQGPU_EUNSUPPORTED also, before any launch, for an nw with (nz nw + 2) * 8 > 160 KiB for a node's nz = nx + nu
+ *                        (the rule of the sensitivity's nz x nx0 window).
+ *   tqgpu_mpc_get_adjoint_x0   gx0 (nx0 x nw, column major) of the last tqgpu_mpc_adjoint (host state only).
+ *   tqgpu_mpc_get_adjoint      gq ((sum_nx without phantom root states) x nw), gr (sum_nu x nw), gb (sum_lam x nw), column major; any
+ *                        pointer may be NULL.  Downloads and waits; not counted (a diagnostic read-out).
+ * A stored adjoint is invalidated by the same events as a stored sensitivity; the getters then return TQGPU_EINVAL.  The gradients with
+ * respect to H, A, B are outer products of these vectors with the solution and are left to the caller. */
+int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *opts, const double *wx, const double *wu, int nw, int *n_reg);
+int tqgpu_mpc_get_adjoint_x0(tqgpu_solver *s, double *gx0);
+int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb);
+
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written
  * (at most 512 solves back) or -1.  tqgpu_result.device_time of a single-launch (persistent) solve is

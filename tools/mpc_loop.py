@@ -46,7 +46,13 @@ duals, and on kind3 also the working sets, move a stage on the device), mode 1, 
 --gain: the time of tqgpu_mpc_sensitivity next to the step, against nx0 finite-difference steps through tqgpu_mpc_step, on c1 and c2
 with root states and on c1 x0-eliminated, with the launches, copies and waits of both (gain_compare).  --predict: iterations per step of
 the dual predictor (tqgpu_mpc_sensitivity + tqgpu_mpc_predict with duals) against warm start mode 1 over the sequences of --root-states
-and --tracking (predict_compare)."""
+and --tracking (predict_compare).
+
+    python tools/mpc_loop.py --adjoint [--steps 200] [--skip 10] [c1] [c2]
+
+--adjoint: behind every step, three ways to the gradient of a scalar loss with one random w = dL/dz, on c1 and c2 with root states and on
+c1 x0-eliminated: tqgpu_mpc_adjoint, tqgpu_mpc_sensitivity + tqgpu_mpc_get_sensitivities + the host product dZ' w, and tqgpu_mpc_adjoint
+behind tqgpu_mpc_sensitivity (the factor stored), with the launches, copies and waits of each (adjoint_compare)."""
 import ctypes as C
 import sys
 import time
@@ -729,6 +735,83 @@ def gain_compare(capi, name, p, root_states, steps, skip, h=2.0 ** -20):
           f"where a step at x0 + h e_j changes the active set or stops at the tolerance)", flush=True)
 
 
+def adjoint_compare(capi, name, p, root_states, steps, skip):
+    """--adjoint: per step of the device loop (warm start mode 1, the x0 path of the plain modes), three ways to a gradient of a scalar
+    loss with dL/dz = w, one random w per step, each on a mirror of its own and timed around its calls with the host clock:
+    (a) tqgpu_mpc_adjoint + tqgpu_mpc_get_adjoint_x0: dL/dx0, with dL/dq, dL/dr, dL/db left on the device;
+    (b) tqgpu_mpc_sensitivity + tqgpu_mpc_get_sensitivities + the host product dZ' w: the only way to dL/dx0 without the adjoint;
+    (c) tqgpu_mpc_adjoint after tqgpu_mpc_sensitivity (not timed), which finds the factor stored.
+    Launches, copies and waits of (a) and (c) are those tqgpu_mpc_stats counts; (b): the sensitivity's counted ones plus what
+    tqgpu_mpc_get_sensitivities adds by its code, which nothing counts: two copies (dx, du) and one stream synchronisation."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    if root_states:
+        d, x0 = full_root(capi, p)
+        xs = [moved_inward(x0, k, 0) for k in range(steps)]
+    else:
+        d, A0, b0, _, x0 = eliminated(capi, p)
+        xs = [moved(x0, k, 0) for k in range(steps)]
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        if root_states:
+            g.mpc_set_root_states()
+        else:
+            g.mpc_set_root(A0, b0)
+        g.set_warm_start(1)
+        return g
+
+    nu0, nx0 = int(d["nu"][0]), len(x0)
+    ga, gb_, gc = mirror(), mirror(), mirror()
+    snx, snu = int(ga.sum_nx), int(ga.sum_nu)
+    u0 = np.zeros(max(nu0, 1))
+    gx = [np.zeros(nx0) for _ in range(3)]
+    dx, du = np.zeros(snx * nx0), np.zeros(snu * nx0)
+    la, co, wa, nreg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rng = np.random.Generator(np.random.PCG64(2020))
+    t = {k: [] for k in "abc"}
+    c = {k: [] for k in "abc"}
+    dab, dac, regs = 0.0, 0.0, 0
+
+    def counted(extra=(0, 0, 0)):
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        return la.value + extra[0], co.value + extra[1], wa.value + extra[2]
+
+    for k in range(steps):
+        wx, wu = rng.standard_normal(snx), rng.standard_normal(snu)
+        for g in (ga, gb_, gc):
+            assert L.tqgpu_mpc_step(g.h, dp(xs[k]), C.byref(o), C.byref(r), dp(u0)) == 0
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_adjoint(ga.h, C.byref(o), dp(wx), dp(wu), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+        assert L.tqgpu_mpc_get_adjoint_x0(ga.h, dp(gx[0])) == 0
+        t["a"].append(time.perf_counter() - t0); c["a"].append(counted()); regs += nreg.value
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_sensitivity(gb_.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()
+        cb = counted((0, 2, 1))
+        assert L.tqgpu_mpc_get_sensitivities(gb_.h, dp(dx), dp(du), None) == 0
+        gx[1][:] = dx.reshape((snx, nx0), order="F").T @ wx + du.reshape((snu, nx0), order="F").T @ wu
+        t["b"].append(time.perf_counter() - t0); c["b"].append(cb)
+        assert L.tqgpu_mpc_sensitivity(gc.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_adjoint(gc.h, C.byref(o), dp(wx), dp(wu), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+        assert L.tqgpu_mpc_get_adjoint_x0(gc.h, dp(gx[2])) == 0
+        t["c"].append(time.perf_counter() - t0); c["c"].append(counted())
+        scale = max(1.0, float(np.max(np.abs(gx[1]))))
+        dab, dac = max(dab, float(np.max(np.abs(gx[0] - gx[1]))) / scale), max(dac, float(np.max(np.abs(gx[0] - gx[2]))))
+    for g in (ga, gb_, gc):
+        g.close()
+    med = lambda v: tuple(int(np.median([e[i] for e in v[skip:]])) for i in range(3))
+    form = "root with states" if root_states else "x0 eliminated"
+    print(f"{name}, --adjoint, {form}: {len(d['nk'])} nodes, nx0 {nx0}, nu[0] {nu0}, {steps} steps; blocks regularised over the run of (a) {regs}")
+    for key, what in (("a", "(a) adjoint"), ("b", "(b) sensitivity + dZ' w"), ("c", "(c) adjoint, factor stored")):
+        m, lo, p90 = stats(t[key][skip:])
+        print(f"    {what:28s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d" % med(c[key]), flush=True)
+    print(f"    ((b): the sensitivity's counted launches, copies, waits + 0, 2, 1 for tqgpu_mpc_get_sensitivities, derived from its code, not counted)")
+    print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; (b) / (c) wall {np.median(t['b'][skip:]) / np.median(t['c'][skip:]):.2f}; "
+          f"largest |gx0 (a) - gx0 (b)| / max(1, |gx0|) over the run {dab:.2e}; largest |gx0 (a) - gx0 (c)| {dac:.2e}", flush=True)
+
+
 def predict_compare(capi, name, p, tracking, steps, skip):
     """--predict: iterations and trials per step over the closed-loop sequence of --root-states (tracking: of --tracking), two ways on a
     root with states: warm start mode 1, and mode 1 with the dual predictor: behind every step tqgpu_mpc_sensitivity, then
@@ -784,6 +867,13 @@ def main():
             gain_compare(capi, "c1", P.spring_mass(), False, steps, skip)
         if "c2" in names:
             gain_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--adjoint" in args:
+        if "c1" in names:
+            adjoint_compare(capi, "c1", P.spring_mass(), True, steps, skip)
+            adjoint_compare(capi, "c1", P.spring_mass(), False, steps, skip)
+        if "c2" in names:
+            adjoint_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
         return
     if "--predict" in args:
         for nm, p in (("c1", P.spring_mass()), ("c2", P.linear_chain(2, 9, 9))):

@@ -950,6 +950,40 @@ class TqGpu:
         self._chk(lib().tqgpu_mpc_predict(self.h, _dp(a), _dp(u0), int(bool(duals)), C.byref(n)))
         return u0[:int(self.nu[0])], n.value
 
+    # ---- the adjoint of an MPC step: dL/dq, dL/dr, dL/db, dL/dx0 for w = dL/dz (tqgpu_mpc_adjoint) ----
+    def mpc_adjoint(self, wx=None, wu=None, profile=0, **kw) -> dict:
+        """Adjoint of the last solve's point, active set frozen (tqgpu_mpc_adjoint): wx (sum_nx, nw) and wu (sum_nu, nw) are the loss
+        gradient in the flat layout of get_solution, None meaning zero, a 1-D array one column.  Returns dict(gx0 (nx0, nw), n_reg); gq, gr,
+        gb stay on the device (mpc_adjoint_grads).  The options give the regularisation rule where the call has to factorise."""
+        nw, arrs = None, []
+        for a, rows in ((wx, int(self.sum_nx)), (wu, int(self.sum_nu))):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            a = a.reshape((rows, -1), order="F") if a.ndim == 1 else a
+            assert a.shape[0] == rows and (nw is None or a.shape[1] == nw), a.shape
+            nw = a.shape[1]
+            arrs.append(np.asfortranarray(a))
+        nw = 1 if nw is None else nw
+        n, nx0 = C.c_int(0), int(self.nx0)
+        o = _gpu_opts(profile, **kw)
+        ptr = [None if a is None else a.ctypes.data_as(c_dbl_p) for a in arrs]
+        self._chk(lib().tqgpu_mpc_adjoint(self.h, C.byref(o), ptr[0], ptr[1], int(nw), C.byref(n)))
+        self._adj_nw = int(nw)
+        g = np.zeros(max(nx0 * nw, 1))
+        self._chk(lib().tqgpu_mpc_get_adjoint_x0(self.h, _dp(g)))
+        return dict(gx0=g[:nx0 * nw].reshape((nx0, nw), order="F"), n_reg=n.value)
+
+    def mpc_adjoint_grads(self) -> dict:
+        """gq (sum_nx, nw), gr (sum_nu, nw), gb (sum_lam, nw) of the last mpc_adjoint: column j is the flat layout of get_solution
+        (tqgpu_mpc_get_adjoint; downloads and waits)."""
+        sizes = (("gq", int(self.sum_nx)), ("gr", int(self.sum_nu)), ("gb", int(self.sum_lam)))
+        nw = self.__dict__.get("_adj_nw", 1)          # (a stale count meets a refusal: the stored adjoint went with what made it stale)
+        out = {key: np.zeros(max(n * nw, 1)) for key, n in sizes}
+        self._chk(lib().tqgpu_mpc_get_adjoint(self.h, _dp(out["gq"]), _dp(out["gr"]), _dp(out["gb"])))
+        return {key: out[key][:n * nw].reshape((n, nw), order="F") for key, n in sizes}
+
     def export_ahead(self, on: bool) -> None:
         """the solution's packing kernel and download go out behind the solve's launch (callers that fetch the solution after every solve)"""
         self._chk(lib().tqgpu_set_export_ahead(self.h, int(bool(on))))

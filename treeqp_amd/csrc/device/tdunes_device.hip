@@ -1869,7 +1869,15 @@ struct MpcTrack { double *d = nullptr; int T = 0, nxt = 0, nut = 0, t0 = -1; };
 struct MpcSens {
     double *d = nullptr, *h = nullptr; Sens v{}; int nx0 = 0;
     bool valid = false, dirty = false;  /* dirty: the problem was changed (upload, fold, window move) since the last solve: its point and the data no longer belong together */
+    bool factored = false;              /* P, L, CholUt, invd of the point and the data the device holds now are in v (tqgpu_mpc_sensitivity, tqgpu_mpc_adjoint); valid implies it */
     size_t lds_factor = 0, lds_primal = 0;
+    /* tqgpu_mpc_adjoint: buffers of its own (setup_adj, on first use and again when nw grows; one device block ad, views in a); pinned ah:
+     * [w: wx ((sum_nx - x_pad) x nw) | wu (sum_nu x nw)] [head: gx0 (nx0 x nw) | n_reg]; adj_valid: the stored adjoint (nw columns)
+     * belongs to the point and the data the device holds now */
+    double *ad = nullptr, *ah = nullptr; Adj a{}; int nw_cap = 0, nw = 0, adj_nx0 = 0;
+    bool adj_valid = false;
+    size_t lds_rhs = 0, lds_grad = 0;
+    void invalidate() { valid = factored = adj_valid = false; }      /* every upload, fold, window move and solve */
 };
 
 /* ---- the solution's way out and its check (tdunes_kkt.hpp): the solution in one piece, [x | u | lam | dlam | mu_x | mu_u], packed on the device (d) and
@@ -3248,7 +3256,7 @@ extern "C" int tqgpu_dims(const tqgpu_solver *s, int *sum_nx, int *sum_nu, int *
  * sensitivity and the pairing of the last solve's point with the data; repack: the packed constants of the persistent route as well */
 static void problem_changed(tqgpu_solver *s, bool repack) {
     s->in_valid = false;
-    s->sens.valid = false; s->sens.dirty = true; if (repack) s->need_pack = true;
+    s->sens.invalidate(); s->sens.dirty = true; if (repack) s->need_pack = true;
 }
 
 #define H2D(dst, src, count)                                                                                   \
@@ -3556,7 +3564,7 @@ extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const doubl
     }
     if (total > 0 && (nc || dmin || dmax)) HIP_TRY(hipMemcpy(s->d_drange, dr.data(), sizeof(double) * 2 * (size_t)total, hipMemcpyHostToDevice));
     s->h_drange.swap(dr);
-    s->out.invalidate(); s->sens.valid = false; s->sens.dirty = true;          /* not problem_changed: the rows are no input of tqgpu_set_problem (in_valid stays), the exported point goes */
+    s->out.invalidate(); s->sens.invalidate(); s->sens.dirty = true;          /* not problem_changed: the rows are no input of tqgpu_set_problem (in_valid stays), the exported point goes */
     return TQGPU_OK;
 }
 
@@ -3655,7 +3663,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
         memcpy(mir, src, bytes);
         HIP_TRY(hipMemcpyAsync(dev, mir, bytes, hipMemcpyHostToDevice, s->stream));
         s->stream_pending = true;
-        s->sens.valid = false; s->sens.dirty = true;          /* not problem_changed: the pinned mirror has just been brought up to date, in_valid stays */
+        s->sens.invalidate(); s->sens.dirty = true;          /* not problem_changed: the pinned mirror has just been brought up to date, in_valid stays */
         any_pack |= pack; any_init |= init;
         return TQGPU_OK;
     };
@@ -3832,7 +3840,7 @@ int grow_events(std::vector<hipEvent_t> &v, int n) {
 int prepare_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, bool in_batch_launch) {
     HIP_TRY(hipSetDevice(s->device));
     s->out.invalidate();
-    s->sens.valid = false; s->sens.dirty = false;          /* (not problem_changed: the data stays) a stored sensitivity belongs to the point of the solve before this one; point and data belong together again */
+    s->sens.invalidate(); s->sens.dirty = false;          /* (not problem_changed: the data stays) a stored sensitivity belongs to the point of the solve before this one; point and data belong together again */
     if (opts_from(o, cx.O) != TQGPU_OK) return TQGPU_EINVAL;
     cx.O.stamps = cx.env.stamps;
 

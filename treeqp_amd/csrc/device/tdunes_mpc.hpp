@@ -402,7 +402,7 @@ extern "C" int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, co
     if (C0) { memcpy(p, C0, sizeof(double) * nc * n0); p += nc * n0; memcpy(p, dmin0, sizeof(double) * nc); p += nc; memcpy(p, dmax0, sizeof(double) * nc); }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the block that is replaced */
-    s->mem.release(s->mpc.d); s->mem.release(s->mpc.h); s->sens.valid = false;
+    s->mem.release(s->mpc.d); s->mem.release(s->mpc.h); s->sens.invalidate();
     s->mpc.nx0 = 0;
     if ((rc = s->mem.upload(s->mpc.d, blk.data(), sizeof(double) * blk.size(), TQGPU_ENOMEM, "the root terms")) ||
         (rc = s->mem.host(s->mpc.h, sizeof(double) * (n0 + nu0 + 2), "the pinned x0 and u0")))
@@ -422,7 +422,7 @@ extern "C" int tqgpu_mpc_set_root_states(tqgpu_solver *s) {
     const size_t nu0 = (size_t)s->nu[0];
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the pinned block that is replaced */
-    s->mem.release(s->mpc.d); s->mem.release(s->mpc.h); s->sens.valid = false;
+    s->mem.release(s->mpc.d); s->mem.release(s->mpc.h); s->sens.invalidate();
     s->mpc.nx0 = 0; s->mpc.states = false;
     if ((rc = s->mem.host(s->mpc.h, sizeof(double) * ((size_t)n0 + nu0 + 2), "the pinned x0 and u0"))) return rc;
     memset(s->mpc.h, 0, sizeof(double) * ((size_t)n0 + nu0 + 2));
@@ -971,7 +971,7 @@ int setup_sens(tqgpu_solver *s) {
     if (s->sens.d && s->sens.nx0 == s->mpc.nx0) return TQGPU_OK;
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->mem.release(s->sens.d); s->mem.release(s->sens.h);
-    s->sens.valid = false; s->sens.nx0 = 0;
+    s->sens.invalidate(); s->sens.nx0 = 0;
     size_t off = 0;
     auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
     const size_t oW = take(s->sum_W), oUt = take(s->sum_Ut), oCW = take(s->sum_W), oCUt = take(s->sum_Ut), oiv = take(snx), oPx = take(snx), oPu = take(snu);
@@ -996,10 +996,8 @@ int sens_need(const tqgpu_solver *s, const char *who) {
     if (!s->sens.valid) return fail(TQGPU_EINVAL, std::string(who) + ": no sensitivity has been computed for the point and the data the device holds now (tqgpu_mpc_sensitivity after the last solve, upload and fold)");
     return TQGPU_OK;
 }
-}  // namespace
-
-extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *n_reg) {
-    const char *who = "tqgpu_mpc_sensitivity";
+/* what tqgpu_mpc_sensitivity and tqgpu_mpc_adjoint refuse alike, before anything is touched */
+int sens_refuse(tqgpu_solver *s, const tqgpu_opts *o, const char *who) {
     int rc;
     if ((rc = mpc_refuse(s, who))) return rc;
     if (!o) return fail(TQGPU_EINVAL, std::string(who) + ": opts is required (the regularisation rule of the factorisation)");
@@ -1009,42 +1007,189 @@ extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *
         return fail(TQGPU_EINVAL, std::string(who) + ": the problem was changed (an upload, an x0 fold or a window move) since the last solve: its point does not belong to the data the device holds now; solve first");
     if (s->dense) for (int k : s->h_kind) if (k >= 2)
         return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the tree has nodes of kind 2 or 3: Pd need not belong to the final working set after a line search's last trial");
+    return TQGPU_OK;
+}
+/* P, W, Ut, G and the factor of the point the device holds, into the feature's buffers: the packing of the point where it has not gone
+ * out, k_sens_hess, k_sens_factor per block level, deepest first.  Returns the view the later kernels take (kept in sens.v by the caller) */
+int sens_enqueue_factor(tqgpu_solver *s, const Opts &O, Sens &S) {
+    int rc;
+    if (!s->out.valid) {
+        if ((rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
+        MPC_COUNT(launches, 1);
+    }
+    S = s->sens.v;
+    S.x = s->out.d; S.u = S.x + export_sizes(s).nxe;
+    S.root_states = s->mpc.states ? 1 : 0;
+    if (s->mpc.d) { S.A0 = s->mpc.d; S.S0 = s->mpc.S0 ? s->mpc.d + (size_t)s->mpc.nb * s->mpc.nx0 + s->mpc.nb : nullptr; }
+    S.x0 = s->mpc.h;
+    const Tree &T = s->T;
+    hipLaunchKernelGGL(k_sens_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, s->stream, T, s->D, S);
+    for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
+        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
+        hipLaunchKernelGGL(k_sens_factor, dim3(count), dim3(WAVE), s->sens.lds_factor, s->stream, T, O, S, first);
+    }
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1 + T.Nh);
+    return TQGPU_OK;
+}
+
+/* the adjoint's buffers, on first use and again when nw grows (or nx0 changed): one zeroed device block, the pinned block, the LDS windows.
+ * Refuses, before anything is touched, an nw whose nz x nw window would not fit the 160 KiB setup_sens allows an nz x nx0 window */
+int adj_window_refuse(const tqgpu_solver *s, int nw) {
+    for (int k = 0; k < s->Nn; k++)
+        if (((size_t)(s->nx[k] + s->nu[k]) * (size_t)nw + 2) * sizeof(double) > 160 * 1024)
+            return fail(TQGPU_EUNSUPPORTED, "tqgpu_mpc_adjoint: a node's nz x nw window does not fit 160 KiB of LDS");
+    return TQGPU_OK;
+}
+size_t adj_w_doubles(const tqgpu_solver *s, int nw) { return ((size_t)(s->sum_nx - s->x_pad) + (size_t)s->sum_nu) * (size_t)nw; }
+int setup_adj(tqgpu_solver *s, int nw) {
+    int rc;
+    MpcSens &m = s->sens;
+    const size_t snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, nx0 = (size_t)s->mpc.nx0;
+    if (!m.ad || nw > m.nw_cap || m.adj_nx0 != s->mpc.nx0) {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        s->mem.release(m.ad); s->mem.release(m.ah);
+        m.adj_valid = false; m.nw_cap = 0;
+        const size_t cap = (size_t)nw;
+        size_t off = 0;
+        auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
+        const size_t ow = take((nxe + snu) * cap), oY = take(snx * cap), ot = take(snx * cap), oq = take(snx * cap), or_ = take(snu * cap), ob = take(snx * cap), oh = take(nx0 * cap + 1);
+        if ((rc = s->mem.zeroed(m.ad, sizeof(double) * std::max<size_t>(off, 2), TQGPU_ENOMEM, "the adjoint")) ||
+            (rc = s->mem.host(m.ah, sizeof(double) * ((nxe + snu) * cap + nx0 * cap + 2), "the pinned loss gradient and gx0")))
+            return rc;
+        memset(m.ah, 0, sizeof(double) * ((nxe + snu) * cap + nx0 * cap + 2));
+        size_t lr = 0, lg = 0;
+        for (int k = 0; k < s->Nn; k++) {
+            const size_t nz = (size_t)(s->nx[k] + s->nu[k]);
+            lr = std::max(lr, (nz + 2) * sizeof(double)); lg = std::max(lg, (2 * nz + 2) * sizeof(double));
+        }
+        if ((rc = allow_lds(k_adj_rhs, lr)) || (rc = allow_lds(k_adj_backward, s->lds_forward)) || (rc = allow_lds(k_adj_forward, s->lds_forward)) || (rc = allow_lds(k_adj_grad, lg)))
+            return rc;
+        Adj &A = m.a;
+        A = Adj{};
+        double *p = m.ad;
+        A.wx = p + ow; A.Y = p + oY; A.t = p + ot; A.gq = p + oq; A.gr = p + or_; A.gb = p + ob; A.head = p + oh;
+        A.nxe = (int)nxe;
+        m.nw_cap = nw; m.adj_nx0 = s->mpc.nx0; m.lds_rhs = lr; m.lds_grad = lg;
+    }
+    /* the columns of this call: wu lies behind the nw columns of wx */
+    m.a.nw = nw;
+    m.a.wu = m.a.wx + nxe * (size_t)nw;
+    return TQGPU_OK;
+}
+int adj_need(const tqgpu_solver *s, const char *who) {
+    if (!s->sens.adj_valid) return fail(TQGPU_EINVAL, std::string(who) + ": no adjoint has been computed for the point and the data the device holds now (tqgpu_mpc_adjoint after the last solve, upload and fold)");
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *n_reg) {
+    const char *who = "tqgpu_mpc_sensitivity";
+    int rc;
+    if ((rc = sens_refuse(s, o, who))) return rc;
     Opts O;
     if ((rc = opts_from(o, O))) return rc;
     SETTLE(s);
     HIP_TRY(hipSetDevice(s->device));
     MpcLive live;
     if ((rc = setup_sens(s))) return rc;
-    s->sens.valid = false;
-    if (!s->out.valid) {
-        if ((rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
-        MPC_COUNT(launches, 1);
-    }
-    Sens S = s->sens.v;
-    S.x = s->out.d; S.u = S.x + export_sizes(s).nxe;
-    S.root_states = s->mpc.states ? 1 : 0;
-    if (s->mpc.d) { S.A0 = s->mpc.d; S.S0 = s->mpc.S0 ? s->mpc.d + (size_t)s->mpc.nb * s->mpc.nx0 + s->mpc.nb : nullptr; }
-    S.x0 = s->mpc.h;
+    s->sens.valid = s->sens.factored = false;
+    Sens S;
+    if ((rc = sens_enqueue_factor(s, O, S))) return rc;
     const Tree &T = s->T;
     hipStream_t st = s->stream;
-    hipLaunchKernelGGL(k_sens_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, st, T, s->D, S);
-    for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
-        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        hipLaunchKernelGGL(k_sens_factor, dim3(count), dim3(WAVE), s->sens.lds_factor, st, T, O, S, first);
-    }
     for (int lvl = 1; lvl < T.Nh; lvl++) {
         const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
         hipLaunchKernelGGL(k_sens_forward, dim3(count, (unsigned)s->sens.nx0), dim3(WAVE), s->lds_forward, st, T, S, first);
     }
     hipLaunchKernelGGL(k_sens_primal, dim3(T.Nn), dim3(WAVE), s->sens.lds_primal, st, T, s->D, S);
     HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, 1 + T.Nh + (T.Nh - 1) + 1);
+    MPC_COUNT(launches, (T.Nh - 1) + 1);
     const size_t head = sens_head_doubles(s);
     HIP_TRY(hipMemcpyAsync(s->sens.h, S.head, sizeof(double) * head, hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
     HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
     s->sens.v = S;
-    s->sens.valid = true;
+    s->sens.valid = s->sens.factored = true;
     if (n_reg) *n_reg = (int)s->sens.h[head - 1];
+    return TQGPU_OK;
+}
+
+/* ---- the adjoint of an MPC step (tdunes_sens.hpp): dL/dq, dL/dr, dL/db, dL/dx0 for w = dL/dz at the point of the last solve ---- */
+extern "C" int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *o, const double *wx, const double *wu, int nw, int *n_reg) {
+    const char *who = "tqgpu_mpc_adjoint";
+    int rc;
+    if ((rc = sens_refuse(s, o, who))) return rc;
+    if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    if ((rc = adj_window_refuse(s, nw)) || (rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
+    s->sens.adj_valid = false;
+    MpcSens &m = s->sens;
+    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), snu = (size_t)s->sum_nu, nwd = adj_w_doubles(s, nw), nx0 = (size_t)m.nx0;
+    hipStream_t st = s->stream;
+    /* w through pinned memory in one copy: [wx | wu], a missing part as zeros */
+    if (wx) memcpy(m.ah, wx, sizeof(double) * nxe * nw); else memset(m.ah, 0, sizeof(double) * nxe * nw);
+    if (wu) memcpy(m.ah + nxe * nw, wu, sizeof(double) * snu * nw); else memset(m.ah + nxe * nw, 0, sizeof(double) * snu * nw);
+    if (nwd) { HIP_TRY(hipMemcpyAsync(const_cast<double *>(m.a.wx), m.ah, sizeof(double) * nwd, hipMemcpyHostToDevice, st)); }
+    MPC_COUNT(copies, 1);
+    Sens S = m.v;
+    if (!m.factored) {
+        if ((rc = sens_enqueue_factor(s, O, S))) return rc;
+        m.v = S;
+        m.factored = true;          /* (valid stays false: dlam, dZ and the head of this point have not been computed) */
+    }
+    const Tree &T = s->T;
+    const Adj A = m.a;
+    const unsigned cols = (unsigned)nw;
+    hipLaunchKernelGGL(k_adj_rhs, dim3(T.Np, cols), dim3(WAVE), m.lds_rhs, st, T, s->D, S, A);
+    for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
+        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
+        hipLaunchKernelGGL(k_adj_backward, dim3(count, cols), dim3(WAVE), s->lds_forward, st, T, S, A, first);
+    }
+    for (int lvl = 1; lvl < T.Nh; lvl++) {
+        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
+        hipLaunchKernelGGL(k_adj_forward, dim3(count, cols), dim3(WAVE), s->lds_forward, st, T, S, A, first);
+    }
+    hipLaunchKernelGGL(k_adj_grad, dim3(T.Nn, cols), dim3(WAVE), m.lds_grad, st, T, s->D, S, A);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1 + T.Nh + (T.Nh - 1) + 1);
+    double *hh = m.ah + nwd;
+    HIP_TRY(hipMemcpyAsync(hh, A.head, sizeof(double) * (nx0 * nw + 1), hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
+    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
+    m.nw = nw;
+    m.adj_valid = true;
+    if (n_reg) *n_reg = (int)hh[nx0 * nw];
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_adjoint_x0(tqgpu_solver *s, double *gx0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_adjoint_x0")) || (rc = adj_need(s, "tqgpu_mpc_get_adjoint_x0"))) return rc;
+    const size_t n = (size_t)s->sens.nx0 * (size_t)s->sens.nw;
+    if (gx0 && n) memcpy(gx0, s->sens.ah + adj_w_doubles(s, s->sens.nw), sizeof(double) * n);
+    return TQGPU_OK;
+}
+
+/* a diagnostic download (whole buffers through pageable memory, repacked on the host): not counted into tqgpu_mpc_stats */
+extern "C" int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_adjoint")) || (rc = adj_need(s, "tqgpu_mpc_get_adjoint"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t nw = (size_t)s->sens.nw, snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, nl = (size_t)s->sum_lam;
+    std::vector<double> tmp(snx * nw + 1);
+    for (int which = 0; which < 2; which++) {
+        double *out = which ? gb : gq;
+        if (!out) continue;
+        HIP_TRY(hipMemcpy(tmp.data(), which ? s->sens.a.gb : s->sens.a.gq, sizeof(double) * snx * nw, hipMemcpyDeviceToHost));
+        const size_t skip = which ? (size_t)s->nx0 : (size_t)s->x_pad, n = which ? nl : nxe;      /* the root has no dual; phantom root states are left out */
+        for (size_t j = 0; j < nw; j++) if (n) memcpy(out + j * n, tmp.data() + j * snx + skip, sizeof(double) * n);
+    }
+    if (gr && snu * nw) HIP_TRY(hipMemcpy(gr, s->sens.a.gr, sizeof(double) * snu * nw, hipMemcpyDeviceToHost));
     return TQGPU_OK;
 }
 

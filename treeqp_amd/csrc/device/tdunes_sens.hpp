@@ -14,6 +14,9 @@
  * P_k: kind 0 diagonal, 1 / Qd_i (1 / Rd_i) where the exported value is strictly inside its bounds, 0.0 where it equals a bound bit for
  * bit (clipping assigns the bound itself), phantom root states free; kind 1: Data::Pd.  Everything is written into the feature's own
  * buffers (struct Sens); Data is only read.
+ *
+ * The adjoint of a step (k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad; struct Adj) is the reverse: one more solve with the same
+ * factor, one right-hand side per column of w = dL/dz, non-zero in every block; its formulas stand with its kernels below.
  */
 #pragma once
 
@@ -327,6 +330,196 @@ __device__ void sens_predict_body(const Tree &T, const Data &D, const Sens &S, c
     }
 }
 
+/* ---- the adjoint of a step (tqgpu_mpc_adjoint): w = dL/dz for a scalar loss of the solution z = (x, u), nw columns at once ----
+ *   R_c = (P_c w_c)^x - C_c P_p w_p,   M Y = R with the factor k_sens_factor left (L, CholUt, invd),   gb_c = Y_c,
+ *   [gq_k; gr_k] = -P_k ( w_k - [Y_k; 0] + sum_c C_c' Y_c ),
+ *   gx0 = sum_c A0_c' Y_c + S0' gr_0 (eliminated root),  wx_0 + sum_c A_c' Y_c (root with states).
+ * R is non-zero in every block, so the solve has the leaf-to-root sweep the forward sensitivity skips: t_ii = L_ii^-1 R_ii, the push
+ * R_dad[pos ..] -= CholUt_ii t_ii (the rows of node ii, which no other block of the level touches: no atomics), Y_0 = L_0^-T t_0 at the
+ * root, then Y_ii = L_ii^-T ( t_ii - CholUt_ii' Y_dad[pos ..] ) level by level.  One wave per (unit, column) on blockIdx.y. */
+struct Adj {
+    const double *wx, *wu;             /* the staged w: (sum_nx - xpad) x nw and sum_nu x nw, column major, the flat layout of the solution */
+    double *Y, *t;                     /* sum_nx x nw each, column major, node-indexed as Sens::dlam: R, then Y in its place; t of the non-root blocks */
+    double *gq, *gr, *gb;              /* sum_nx x nw, sum_nu x nw, sum_nx x nw, node-indexed (phantom root states included; gb: the root's rows stay 0) */
+    double *head;                      /* [gx0 (nx0 x nw, column major) | n_reg] */
+    int nw, nxe;
+};
+/* entry i of w_k, i over [x | u], column col; phantom root states carry 0 */
+__device__ __forceinline__ double adj_w(const Tree &T, const Sens &S, const Adj &A, int k, int i, int col) {
+    const int nx = T.nx[k];
+    if (i < nx) {
+        const int g = T.xoff[k] + i;
+        return g < S.xpad ? 0.0 : A.wx[g - S.xpad + (size_t)col * A.nxe];
+    }
+    return A.wu[T.uoff[k] + i - nx + (size_t)col * S.sum_nu];
+}
+/* entry i of P_k w_k */
+__device__ __forceinline__ double adj_pw(const Tree &T, const Data &D, const Sens &S, const Adj &A, int k, int i, int col) {
+    const int nx = T.nx[k], nz = nx + T.nu[k];
+    if (sens_kind(D, k) == 0) return (i < nx ? S.Px[T.xoff[k] + i] : S.Pu[T.uoff[k] + i - nx]) * adj_w(T, S, A, k, i, col);
+    const double *P = D.Pd + D.poff[k];
+    double acc = 0.0;
+    for (int m = 0; m < nz; m++) acc = fma(P[i + (size_t)m * nz], adj_w(T, S, A, k, m, col), acc);
+    return acc;
+}
+
+/* ---- k_adj_rhs: one wave per (parent block p, column): the rows of p's children of R ---- */
+__device__ void adj_rhs_body(const Tree &T, const Data &D, const Sens &S, const Adj &A, int p, int col, int lane, double *lds) {
+    const int nxp = T.nx[p], nup = T.nu[p], nz = nxp + nup, k0 = T.kid0[p];
+    double *pv = lds;                     /* nz: P_p w_p */
+    for (int i = lane; i < nz; i += WAVE) pv[i] = adj_pw(T, D, S, A, p, i, col);
+    WSYNC();
+    double *R = A.Y + (size_t)col * S.sum_nx;
+    for (int cc = 0; cc < T.nk[p]; cc++) {
+        const int kid = k0 + cc, nxc = T.nx[kid];
+        const double *Ac = D.A + T.aoff[kid], *Bc = D.B + T.boff[kid];
+        for (int i = lane; i < nxc; i += WAVE) {
+            double acc = 0.0;
+            for (int m = 0; m < nxp; m++) acc = fma(Ac[i + (size_t)m * nxc], pv[m], acc);
+            for (int m = 0; m < nup; m++) acc = fma(Bc[i + (size_t)m * nxc], pv[nxp + m], acc);
+            R[T.xoff[kid] + i] = adj_pw(T, D, S, A, kid, i, col) - acc;
+        }
+    }
+}
+
+/* ---- k_adj_backward: one wave per (block of one level, column), deepest level first: t = L^-1 R_ii (column-oriented forward substitution),
+ * the push into the parent's rows of R; the root's instance goes on to Y_0 = L^-T t ---- */
+__device__ void adj_backward_body(const Tree &T, const Sens &S, const Adj &A, int ii, int col, int lane, double *lds) {
+    const int d = T.bdim[ii], ld = d | 1;
+    double *L = lds;                      /* ld x d */
+    double *z = lds + (size_t)ld * d;     /* d */
+    double *iv = z + d;                   /* d */
+    const int bo = T.xoff[T.kid0[ii]];
+    const double *Lg = S.CholW + T.woff[ii];
+    double *R = A.Y + (size_t)col * S.sum_nx;
+    for (int e = lane; e < d * d; e += WAVE) {
+        const int i = e % d, j = e / d;
+        if (i >= j) L[i + (size_t)j * ld] = Lg[i + (size_t)j * d];
+    }
+    for (int j = lane; j < d; j += WAVE) { iv[j] = S.invd[bo + j]; z[j] = R[bo + j]; }
+    for (int k = 0; k < d; k++) {
+        WSYNC();
+        const double zk = z[k] * iv[k];
+        for (int i = k + 1 + lane; i < d; i += WAVE) z[i] = fma(-L[i + (size_t)k * ld], zk, z[i]);
+        WSYNC();
+        if (lane == 0) z[k] = zk;
+    }
+    WSYNC();
+    if (ii > 0) {
+        const int nxi = T.nx[ii], xo = T.xoff[ii];
+        const double *CUt = S.CholUt + T.utoff[ii];
+        double *t = A.t + (size_t)col * S.sum_nx;
+        for (int j = lane; j < d; j += WAVE) t[bo + j] = z[j];
+        for (int i = lane; i < nxi; i += WAVE) {
+            double acc = 0.0;
+            for (int j = 0; j < d; j++) acc = fma(CUt[i + (size_t)j * nxi], z[j], acc);
+            R[xo + i] -= acc;
+        }
+        return;
+    }
+    for (int k = d - 1; k >= 0; k--) {
+        WSYNC();
+        const double zk = z[k] * iv[k];
+        for (int i = lane; i < k; i += WAVE) z[i] = fma(-L[k + (size_t)i * ld], zk, z[i]);
+        WSYNC();
+        if (lane == 0) z[k] = zk;
+    }
+    WSYNC();
+    for (int j = lane; j < d; j += WAVE) R[bo + j] = z[j];
+}
+
+/* ---- k_adj_forward: one wave per (block of one level below the root, column): Y_ii = L^-T ( t_ii - CholUt' Y_dad[pos ..] ),
+ * sens_forward_body's substitution plus the t term ---- */
+__device__ void adj_forward_body(const Tree &T, const Sens &S, const Adj &A, int ii, int col, int lane, double *lds) {
+    const int d = T.bdim[ii], nxi = T.nx[ii], ld = d | 1;
+    double *L = lds;                      /* ld x d */
+    double *z = lds + (size_t)ld * d;     /* d */
+    double *dl = z + d;                   /* nxi */
+    double *iv = dl + nxi;                /* d */
+    const int bo = T.xoff[T.kid0[ii]], xo = T.xoff[ii];
+    const double *Lg = S.CholW + T.woff[ii];
+    double *Y = A.Y + (size_t)col * S.sum_nx;
+    const double *t = A.t + (size_t)col * S.sum_nx;
+    for (int e = lane; e < d * d; e += WAVE) {
+        const int i = e % d, j = e / d;
+        if (i >= j) L[i + (size_t)j * ld] = Lg[i + (size_t)j * d];
+    }
+    for (int j = lane; j < d; j += WAVE) iv[j] = S.invd[bo + j];
+    for (int i = lane; i < nxi; i += WAVE) dl[i] = Y[xo + i];
+    WSYNC();
+    const double *CUt = S.CholUt + T.utoff[ii];
+    for (int j = lane; j < d; j += WAVE) {
+        double acc = 0.0;
+        for (int i = 0; i < nxi; i++) acc = fma(CUt[i + (size_t)j * nxi], dl[i], acc);
+        z[j] = t[bo + j] - acc;
+    }
+    for (int k = d - 1; k >= 0; k--) {
+        WSYNC();
+        const double zk = z[k] * iv[k];
+        for (int i = lane; i < k; i += WAVE) z[i] = fma(-L[k + (size_t)i * ld], zk, z[i]);
+        WSYNC();
+        if (lane == 0) z[k] = zk;
+    }
+    WSYNC();
+    for (int j = lane; j < d; j += WAVE) Y[bo + j] = z[j];
+}
+
+/* ---- k_adj_grad: one wave per (node, column): gq, gr, gb; node 0 also gx0 and, in column 0, n_reg into the head ---- */
+__device__ void adj_grad_body(const Tree &T, const Data &D, const Sens &S, const Adj &A, int k, int col, int lane, double *lds) {
+    const int nxk = T.nx[k], nuk = T.nu[k], nz = nxk + nuk, nx0 = S.nx0, pad = k == 0 ? S.xpad : 0;
+    const int xo = T.xoff[k], uo = T.uoff[k], k0 = T.kid0[k], nkids = k < T.Np ? T.nk[k] : 0;
+    double *v = lds;                      /* nz: w_k - [Y_k; 0] + sum_c C_c' Y_c */
+    double *g = lds + nz;                 /* nz: -P_k v */
+    const double *Y = A.Y + (size_t)col * S.sum_nx;
+    for (int i = lane; i < nz; i += WAVE) {
+        double acc = 0.0;
+        for (int cc = 0; cc < nkids; cc++) {
+            const int kid = k0 + cc, nxc = T.nx[kid];
+            const double *Cc = i < nxk ? D.A + T.aoff[kid] + (size_t)i * nxc : D.B + T.boff[kid] + (size_t)(i - nxk) * nxc;
+            const double *yc = Y + T.xoff[kid];
+            for (int r = 0; r < nxc; r++) acc = fma(Cc[r], yc[r], acc);
+        }
+        v[i] = adj_w(T, S, A, k, i, col) - (k > 0 && i < nxk ? Y[xo + i] : 0.0) + acc;
+    }
+    WSYNC();
+    const int kind = sens_kind(D, k);
+    for (int i = lane; i < nz; i += WAVE) {
+        double r;
+        if (kind == 0) r = (i < nxk ? S.Px[xo + i] : S.Pu[uo + i - nxk]) * v[i];
+        else {
+            const double *P = D.Pd + D.poff[k];
+            r = 0.0;
+            for (int m = 0; m < nz; m++) r = fma(P[i + (size_t)m * nz], v[m], r);
+        }
+        r = -r;
+        g[i] = r;
+        if (i < nxk) A.gq[xo + i + (size_t)col * S.sum_nx] = r; else A.gr[uo + i - nxk + (size_t)col * S.sum_nu] = r;
+    }
+    if (k > 0) {
+        for (int i = lane; i < nxk; i += WAVE) A.gb[xo + i + (size_t)col * S.sum_nx] = Y[xo + i];
+        return;
+    }
+    WSYNC();
+    double *gx0 = A.head + (size_t)col * nx0;
+    for (int j = lane; j < nx0; j += WAVE) {
+        double r;
+        if (S.root_states) r = v[pad + j];
+        else {
+            r = 0.0;
+            int ao = 0;
+            for (int cc = 0; cc < nkids; cc++) {
+                const int kid = k0 + cc, nxc = T.nx[kid];
+                const double *A0 = S.A0 + ao + (size_t)j * nxc, *yc = Y + T.xoff[kid];
+                for (int i = 0; i < nxc; i++) r = fma(A0[i], yc[i], r);
+                ao += nxc * nx0;
+            }
+            if (S.S0) for (int m = 0; m < nuk; m++) r = fma(S.S0[m + (size_t)j * nuk], g[nxk + m], r);
+        }
+        gx0[j] = r;
+    }
+    if (col == 0 && lane == 0) A.head[(size_t)nx0 * A.nw] = (double)*S.n_reg;
+}
+
 __global__ void __launch_bounds__(WAVE) k_sens_hess(Tree T, Data D, Sens S)
 #if !TQ_HAS(TQP_SENS)
 ;
@@ -368,4 +561,40 @@ __global__ void __launch_bounds__(WAVE) k_mpc_predict(Tree T, Data D, Sens S, co
 ;
 #else
 { sens_predict_body(T, D, S, x0_new, lam_init, lam_keep, out, blockIdx.x, threadIdx.x); }
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_rhs(Tree T, Data D, Sens S, Adj A)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    adj_rhs_body(T, D, S, A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_backward(Tree T, Sens S, Adj A, int first)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    adj_backward_body(T, S, A, first + (int)blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_forward(Tree T, Sens S, Adj A, int first)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    adj_forward_body(T, S, A, first + (int)blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_grad(Tree T, Data D, Sens S, Adj A)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    adj_grad_body(T, D, S, A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
 #endif
