@@ -659,6 +659,29 @@ int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, in
 int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *opts, const double *wx, const double *wu, int nw, int *n_reg);
 int tqgpu_mpc_get_adjoint_x0(tqgpu_solver *s, double *gx0);
 int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb);
+/* The adjoint of a batch of steps in one set of launches per device: what tqgpu_mpc_adjoint does for one mirror, for n of them.
+ *   wx, wu               the members' blocks one behind the other, member 0 first: member i's block is what tqgpu_mpc_adjoint takes for it,
+ *                        ((sum_nx_i without phantom root states) x nw) and (sum_nu_i x nw), column major; either may be NULL, meaning
+ *                        zero; nw is the same for every member.
+ *   gx0, n_reg           may be NULL; the members' nx0_i x nw blocks one behind the other, and n ints.
+ *   per device           the members of one device form a group led by its first member, whose stream carries everything: three copies
+ *                        (the descriptors with the members' level tables, w of all members, the heads [gx0 | n_reg] of all members) and one
+ *                        wait, whatever n; launches, with Nh_max the deepest member's block levels: [1, the packing of the points, where a
+ *                        member that lacks the factor has not packed its point] + [1 + Nh_max, where a member lacks the factor] +
+ *                        1 + Nh_max + (Nh_max - 1) + 1.  Blocks z of the grid are the members, y the columns, x what it is in the single
+ *                        launches; the backward launch j takes level Nh_i - 1 - j of member i, the forward launch j level j + 1, a
+ *                        shallower member finishes early.  The arithmetic of a member is that of its own tqgpu_mpc_adjoint: every
+ *                        result is the same bit for bit.  Counted into tqgpu_mpc_stats.
+ *   state                afterwards every member is as a successful tqgpu_mpc_adjoint leaves it (tqgpu_mpc_get_adjoint_x0 and
+ *                        tqgpu_mpc_get_adjoint read its own buffers; the factor counts as stored); the flags are set after the wait has
+ *                        succeeded.  A stored sensitivity and everything a solve reads are left alone.
+ *   member by member     groups of fewer than ADJ_BATCH_MIN members (tdunes_mpc.hpp), of more than 65 535, or in which one tree dwarfs
+ *                        the others (the rule of tqgpu_kkt_residual_batch), and every group under TREEQP_AMD_ADJ_BATCH=members, go through
+ *                        tqgpu_mpc_adjoint one member after the other: same results and state, the counts are the sum of the single calls.
+ *   refusals             before any member is touched, with the member's index in the message: whatever tqgpu_mpc_adjoint refuses for a
+ *                        member; TQGPU_EINVAL for n < 1, solvers == NULL, opts == NULL, nw < 1 and a mirror named twice.  Every member's
+ *                        stored adjoint and sensitivity are then as before. */
+int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, const double *wx, const double *wu, int nw, double *gx0, int *n_reg);
 
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written

@@ -52,7 +52,13 @@ and --tracking (predict_compare).
 
 --adjoint: behind every step, three ways to the gradient of a scalar loss with one random w = dL/dz, on c1 and c2 with root states and on
 c1 x0-eliminated: tqgpu_mpc_adjoint, tqgpu_mpc_sensitivity + tqgpu_mpc_get_sensitivities + the host product dZ' w, and tqgpu_mpc_adjoint
-behind tqgpu_mpc_sensitivity (the factor stored), with the launches, copies and waits of each (adjoint_compare)."""
+behind tqgpu_mpc_sensitivity (the factor stored), with the launches, copies and waits of each (adjoint_compare).
+
+    python tools/mpc_loop.py --adjoint-batch N[,N2,..] [--steps 200] [--skip 10] [c1] [c2]
+
+--adjoint-batch: behind every tqgpu_mpc_step_batch of N trees, one random w per member and two ways to the members' gradients, on c1 with
+both root forms and on c2 with root states: (a) one tqgpu_mpc_adjoint_batch, (b) N calls of tqgpu_mpc_adjoint on mirrors of their own; wall
+time, launches, copies and waits of each, and the largest difference of gx0 between them, which must be 0 (adjoint_batch_compare)."""
 import ctypes as C
 import sys
 import time
@@ -812,6 +818,78 @@ def adjoint_compare(capi, name, p, root_states, steps, skip):
           f"largest |gx0 (a) - gx0 (b)| / max(1, |gx0|) over the run {dab:.2e}; largest |gx0 (a) - gx0 (c)| {dac:.2e}", flush=True)
 
 
+def adjoint_batch_compare(capi, name, p, root_states, n, steps, skip):
+    """--adjoint-batch N: behind every tqgpu_mpc_step_batch of N trees (warm start mode 1), one random w per member and two ways to the
+    members' gradients, each on N mirrors of its own, stepped alike, and timed around its calls with the host clock:
+    (a) one tqgpu_mpc_adjoint_batch;
+    (b) N calls of tqgpu_mpc_adjoint + tqgpu_mpc_get_adjoint_x0, member after member.
+    Launches, copies and waits are those tqgpu_mpc_stats counts ((b): summed over the N calls).  The largest difference of gx0 between
+    the two must be 0: a member's arithmetic is the same."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o = capi._gpu_opts()
+    if root_states:
+        d, x0 = full_root(capi, p)
+        xs = [np.concatenate([moved_inward(x0, k, i) for i in range(n)]) for k in range(steps)]
+    else:
+        d, A0, b0, _, x0 = eliminated(capi, p)
+        xs = [np.concatenate([moved(x0, k, i) for i in range(n)]) for k in range(steps)]
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        if root_states:
+            g.mpc_set_root_states()
+        else:
+            g.mpc_set_root(A0, b0)
+        g.set_warm_start(1)
+        return g
+
+    nu0, nx0 = int(d["nu"][0]), len(x0)
+    ga, gb_ = [mirror() for _ in range(n)], [mirror() for _ in range(n)]
+    arr = {k: (C.c_void_p * n)(*[m.h for m in v]) for k, v in (("a", ga), ("b", gb_))}
+    res = (capi.GpuResult * n)()
+    snx, snu = int(ga[0].sum_nx), int(ga[0].sum_nu)
+    u0 = np.zeros(max(nu0 * n, 1))
+    gxa, gxb = np.zeros(nx0 * n), np.zeros(nx0 * n)
+    nregs = np.zeros(n, dtype=np.int32)
+    la, co, wa, nreg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rng = np.random.Generator(np.random.PCG64(2121))
+    t = {k: [] for k in "ab"}
+    c = {k: [] for k in "ab"}
+    dab, regs, bad = 0.0, 0, 0
+
+    def counted():
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        return la.value, co.value, wa.value
+
+    for k in range(steps):
+        wx, wu = rng.standard_normal(snx * n), rng.standard_normal(snu * n)
+        for key in "ab":
+            assert L.tqgpu_mpc_step_batch(arr[key], n, dp(xs[k]), C.byref(o), res, dp(u0)) == 0, L.tqgpu_last_error()
+            bad += sum(res[i].status != 0 for i in range(n))
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_adjoint_batch(arr["a"], n, C.byref(o), dp(wx), dp(wu), 1, dp(gxa), capi._ip(nregs)) == 0, L.tqgpu_last_error()
+        t["a"].append(time.perf_counter() - t0); c["a"].append(counted()); regs += int(nregs.sum())
+        t0 = time.perf_counter()
+        tot = np.zeros(3, dtype=int)
+        for i, g in enumerate(gb_):
+            assert L.tqgpu_mpc_adjoint(g.h, C.byref(o), dp(wx[i * snx:]), dp(wu[i * snu:]), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+            assert L.tqgpu_mpc_get_adjoint_x0(g.h, dp(gxb[i * nx0:])) == 0
+            tot += counted()
+        t["b"].append(time.perf_counter() - t0); c["b"].append(tuple(tot))
+        dab = max(dab, float(np.max(np.abs(gxa - gxb))))
+    for g in ga + gb_:
+        g.close()
+    med = lambda v: tuple(int(np.median([e[i] for e in v[skip:]])) for i in range(3))
+    form = "roots with states" if root_states else "x0 eliminated"
+    print(f"{name}, --adjoint-batch {n}, {form}: {n} mirrors of {len(d['nk'])} nodes, nx0 {nx0}, {steps} steps; member steps with another status than 0: {bad}; "
+          f"blocks regularised over the run of (a) {regs}")
+    for key, what in (("a", "(a) adjoint_batch"), ("b", f"(b) {n} x adjoint")):
+        m, lo, p90 = stats(t[key][skip:])
+        print(f"    {what:28s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d" % med(c[key]), flush=True)
+    print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |gx0 (a) - gx0 (b)| over the run {dab:.2e}", flush=True)
+
+
 def predict_compare(capi, name, p, tracking, steps, skip):
     """--predict: iterations and trials per step over the closed-loop sequence of --root-states (tracking: of --tracking), two ways on a
     root with states: warm start mode 1, and mode 1 with the dual predictor: behind every step tqgpu_mpc_sensitivity, then
@@ -867,6 +945,15 @@ def main():
             gain_compare(capi, "c1", P.spring_mass(), False, steps, skip)
         if "c2" in names:
             gain_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--adjoint-batch" in args:
+        sizes = [int(v) for v in args[args.index("--adjoint-batch") + 1].split(",")]          # N, or N1,N2,.. in one process
+        for nb in sizes:
+            if "c1" in names:
+                adjoint_batch_compare(capi, "c1", P.spring_mass(), True, nb, steps, skip)
+                adjoint_batch_compare(capi, "c1", P.spring_mass(), False, nb, steps, skip)
+            if "c2" in names:
+                adjoint_batch_compare(capi, "c2", P.linear_chain(2, 9, 9), True, nb, steps, skip)
         return
     if "--adjoint" in args:
         if "c1" in names:

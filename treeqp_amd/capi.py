@@ -564,6 +564,40 @@ def mpc_step_batch(mirrors, x0s=None, profile=0, **kw):
             [u[at[i]:at[i + 1]].copy() for i in range(n)])
 
 
+def mpc_adjoint_batch(mirrors, wxs=None, wus=None, profile=0, **kw) -> list:
+    """Adjoint of the last solve's point of every mirror (tqgpu_mpc_adjoint_batch): the members of one device in one set of launches,
+    three copies and one wait.  wxs, wus: one array per member as TqGpu.mpc_adjoint takes them ((sum_nx, nw) and (sum_nu, nw), a 1-D
+    array one column), or None for zeros throughout; nw is the same for every member.  Returns one dict(gx0 (nx0, nw), n_reg) per
+    member; gq, gr, gb stay on the device in the member's own buffers (TqGpu.mpc_adjoint_grads of the member)."""
+    n = len(mirrors)
+    nw, parts = None, []
+    for given, rows_of in ((wxs, lambda m: int(m.sum_nx)), (wus, lambda m: int(m.sum_nu))):
+        if given is None:
+            parts.append(None)
+            continue
+        assert len(given) == n, "one array per member"
+        cols = []
+        for a, m in zip(given, mirrors):
+            a = np.asarray(a, dtype=np.float64)
+            a = a.reshape((rows_of(m), -1), order="F") if a.ndim == 1 else a
+            assert a.shape[0] == rows_of(m) and (nw is None or a.shape[1] == nw), a.shape
+            nw = a.shape[1]
+            cols.append(np.asfortranarray(a).ravel(order="F"))
+        parts.append(_f64(np.concatenate(cols)) if cols else _f64(np.zeros(1)))
+    nw = int(kw.pop("nw", 1)) if nw is None else nw
+    o = _gpu_opts(profile, **kw)
+    arr = (C.c_void_p * max(n, 1))(*[m.h for m in mirrors])
+    nx0 = [int(m.nx0) for m in mirrors]
+    g, nr = np.zeros(max(sum(nx0) * max(nw, 0), 1)), np.zeros(max(n, 1), dtype=np.int32)
+    rc = lib().tqgpu_mpc_adjoint_batch(arr, n, C.byref(o), _dp(parts[0]), _dp(parts[1]), int(nw), _dp(g), _ip(nr))
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_mpc_adjoint_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    at = np.concatenate([[0], np.cumsum(nx0)]).astype(int) * nw
+    for m in mirrors:
+        m._adj_nw = int(nw)
+    return [dict(gx0=g[at[i]:at[i + 1]].copy().reshape((nx0[i], nw), order="F"), n_reg=int(nr[i])) for i in range(n)]
+
+
 SHIFT_LEAF_REPEAT, SHIFT_LEAF_ZERO = 0, 1          # TQGPU_SHIFT_LEAF_* of include/treeqp_amd.h
 SHIFT_DUALS, SHIFT_WORKING_SETS = 1, 2             # TQGPU_SHIFT_*
 c_u64_p = C.POINTER(C.c_uint64)

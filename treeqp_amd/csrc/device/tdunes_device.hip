@@ -1879,6 +1879,16 @@ struct MpcSens {
     size_t lds_rhs = 0, lds_grad = 0;
     void invalidate() { valid = factored = adj_valid = false; }      /* every upload, fold, window move and solve */
 };
+/* tqgpu_mpc_adjoint_batch, batched route (the first member of a device's group owns all three): desc, the descriptors (AItem) with the members'
+ * level tables behind them, uploaded with every call in one copy; w, the loss gradients of all members, [wx | wu] member after member, one
+ * copy (Adj::wx, Adj::wu of a descriptor point into d_w); heads, [gx0 | n_reg] of all members, one copy back (Adj::head points into d_heads).
+ * Each is a device block and its pinned twin; the capacities are bytes of desc, doubles of w and of heads */
+struct MpcAdjBatch {
+    long drained_at = 0;                /* as Kkt::drained_at, for the launches of the batched adjoint */
+    char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
+    double *d_w = nullptr, *h_w = nullptr; size_t w_cap = 0;
+    double *d_heads = nullptr, *h_heads = nullptr; size_t heads_cap = 0;
+};
 
 /* ---- the solution's way out and its check (tdunes_kkt.hpp): the solution in one piece, [x | u | lam | dlam | mu_x | mu_u], packed on the device (d) and
  * downloaded into pinned memory (h).  valid: h holds (or is about to hold, stream-ordered) the solution of the last solve; dev_only, with valid: the pack
@@ -2050,7 +2060,7 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens;      /* the MPC family (tdunes_mpc.hpp), one record per feature */
+    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb;      /* the MPC family (tdunes_mpc.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;

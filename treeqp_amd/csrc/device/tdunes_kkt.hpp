@@ -415,7 +415,9 @@ constexpr size_t KKT_GRID_Y = 65535;             /* blockIdx.y is the member */
 struct KktGroup { int device; std::vector<int> idx; bool batched = false; };
 
 /* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
- * waves that return at once, and is checked member by member instead. */
+ * waves that return at once, and is checked member by member instead.  THE rule (tqgpu_mpc_adjoint_batch shares it): mx, the
+ * largest member's nodes, n members, sum, the nodes of all of them. */
+bool batch_grid_lopsided(size_t mx, size_t n, size_t sum) { return mx * n > 8 * sum + 4096; }
 bool kkt_group_batched(tqgpu_solver **v, const KktGroup &g) {
     if (g.idx.size() < (size_t)KKT_BATCH_MIN || g.idx.size() > KKT_GRID_Y) return false;
     size_t sum = 0, mx = 0;
@@ -424,7 +426,7 @@ bool kkt_group_batched(tqgpu_solver **v, const KktGroup &g) {
         if (!seen.insert(v[i]).second) return false;          /* a mirror named twice: two workgroups would reduce (and rewrite) one table */
         sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn);
     }
-    return mx * g.idx.size() <= 8 * sum + 4096;
+    return !batch_grid_lopsided(mx, g.idx.size(), sum);
 }
 
 /* one member on its own stream: the route of tqgpu_kkt_residual without the wait */

@@ -954,11 +954,10 @@ extern "C" int tqgpu_mpc_stats(int *launches, int *copies, int *waits) {
 namespace {
 size_t sens_head_doubles(const tqgpu_solver *s) { return (size_t)s->nu[0] * s->sens.nx0 + (size_t)s->nu[0] + (size_t)s->sens.nx0 + 1; }
 
-/* the feature's buffers, on first use and again when nx0 changed: one zeroed device block, the pinned block, the LDS windows */
-int setup_sens(tqgpu_solver *s) {
-    int rc;
-    const size_t nx0 = (size_t)s->mpc.nx0, nu0 = (size_t)s->nu[0], snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu;
-    size_t lf = 0, lp = 0;
+/* the LDS windows of k_sens_factor (lf) and k_sens_primal (lp), refused where one does not fit; touches nothing */
+int sens_window_refuse(const tqgpu_solver *s, size_t &lf, size_t &lp) {
+    const size_t nx0 = (size_t)s->mpc.nx0;
+    lf = lp = 0;
     for (int k = 0; k < s->Nn; k++) {
         lp = std::max(lp, ((size_t)(s->nx[k] + s->nu[k]) * nx0 + 2) * sizeof(double));
         if (k < s->Np) {
@@ -968,6 +967,14 @@ int setup_sens(tqgpu_solver *s) {
     }
     if (lf > 160 * 1024 || lp > 160 * 1024)
         return fail(TQGPU_EUNSUPPORTED, "tqgpu_mpc_sensitivity: the tall root block [W; G'] (or a node's nz x nx0 window) does not fit 160 KiB of LDS");
+    return TQGPU_OK;
+}
+/* the feature's buffers, on first use and again when nx0 changed: one zeroed device block, the pinned block, the LDS windows */
+int setup_sens(tqgpu_solver *s) {
+    int rc;
+    const size_t nx0 = (size_t)s->mpc.nx0, nu0 = (size_t)s->nu[0], snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu;
+    size_t lf = 0, lp = 0;
+    if ((rc = sens_window_refuse(s, lf, lp))) return rc;
     if (s->sens.d && s->sens.nx0 == s->mpc.nx0) return TQGPU_OK;
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->mem.release(s->sens.d); s->mem.release(s->sens.h);
@@ -1115,16 +1122,10 @@ extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *
 }
 
 /* ---- the adjoint of an MPC step (tdunes_sens.hpp): dL/dq, dL/dr, dL/db, dL/dx0 for w = dL/dz at the point of the last solve ---- */
-extern "C" int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *o, const double *wx, const double *wu, int nw, int *n_reg) {
-    const char *who = "tqgpu_mpc_adjoint";
+/* one mirror on its own stream, behind the refusals that touch nothing; counted into whatever record is live (tqgpu_mpc_adjoint's own, or that of a
+ * tqgpu_mpc_adjoint_batch that goes member by member) */
+static int mpc_adjoint_one(tqgpu_solver *s, const Opts &O, const double *wx, const double *wu, int nw, int *n_reg) {
     int rc;
-    if ((rc = sens_refuse(s, o, who))) return rc;
-    if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
-    Opts O;
-    if ((rc = opts_from(o, O))) return rc;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    MpcLive live;
     if ((rc = adj_window_refuse(s, nw)) || (rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
     s->sens.adj_valid = false;
     MpcSens &m = s->sens;
@@ -1164,6 +1165,18 @@ extern "C" int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *o, const dou
     if (n_reg) *n_reg = (int)hh[nx0 * nw];
     return TQGPU_OK;
 }
+extern "C" int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *o, const double *wx, const double *wu, int nw, int *n_reg) {
+    const char *who = "tqgpu_mpc_adjoint";
+    int rc;
+    if ((rc = sens_refuse(s, o, who))) return rc;
+    if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    return mpc_adjoint_one(s, O, wx, wu, nw, n_reg);
+}
 
 extern "C" int tqgpu_mpc_get_adjoint_x0(tqgpu_solver *s, double *gx0) {
     int rc;
@@ -1190,6 +1203,237 @@ extern "C" int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, do
         for (size_t j = 0; j < nw; j++) if (n) memcpy(out + j * n, tmp.data() + j * snx + skip, sizeof(double) * n);
     }
     if (gr && snu * nw) HIP_TRY(hipMemcpy(gr, s->sens.a.gr, sizeof(double) * snu * nw, hipMemcpyDeviceToHost));
+    return TQGPU_OK;
+}
+
+/* ---- tqgpu_mpc_adjoint_batch: per device one group; a group of ADJ_BATCH_MIN members or more goes out as ONE set of launches on its first
+ * member's stream (the lead's), anything else member by member through mpc_adjoint_one ---- */
+namespace {
+constexpr int ADJ_BATCH_MIN = 2;                 /* members of one device from which the batched route is taken: at 2 C1 trees it measured 212 us against 417 us member by member, at 4 212 us against 809 us (profiles/r21_mpc_adjoint_batch.txt) */
+constexpr size_t ADJ_GRID_Z = 65535;             /* blockIdx.z is the member */
+
+/* the packing of the members' points: the body of k_export_all_batch over the adjoint's descriptor (kinds 2 and 3 are refused: no overlays) */
+__global__ void __launch_bounds__(256) k_adj_export_batch(const AItem *__restrict__ items) {
+    const AItem &it = items[blockIdx.y];
+    if (!it.needs_export) return;
+    export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, it.nxe, it.nue, it.nl, it.x_pad, it.nx0, it.D, it.lamc, it.d_out);
+}
+
+struct AdjGroup { int device; std::vector<int> idx; bool batched = false; std::vector<Sens> views; };
+struct AdjSpan { size_t wx, wu, gx0; };          /* where a member's blocks begin in the caller's wx, wu and gx0 */
+
+bool adj_group_batched(tqgpu_solver **v, const AdjGroup &g) {
+    if (g.idx.size() < (size_t)ADJ_BATCH_MIN || g.idx.size() > ADJ_GRID_Z) return false;
+    size_t sum = 0, mx = 0;
+    for (int i : g.idx) { sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn); }
+    return !batch_grid_lopsided(mx, g.idx.size(), sum);
+}
+/* a pair of blocks of the lead, device and pinned, with room for `need` units (the lead's stream holds nothing that reads them: every call ends with its wait) */
+template <typename U>
+int adj_grow(tqgpu_solver *lead, U *&d, U *&h, size_t &cap, size_t need, const char *what) {
+    if (cap >= need && d) return TQGPU_OK;
+    lead->mem.release(d); lead->mem.release(h);
+    cap = 0;
+    int rc;
+    const size_t units = 2 * std::max<size_t>(need, 1);
+    if ((rc = lead->mem.device(d, units * sizeof(U), TQGPU_ENOMEM, what)) || (rc = lead->mem.host(h, units * sizeof(U), what))) return rc;
+    cap = units;
+    return TQGPU_OK;
+}
+
+/* A group on its lead's stream: the descriptors and level tables in one copy, w of all members in one copy, the launches, the heads in one
+ * copy; nothing is waited for here in the steady state.  The stream rules are kkt_group_enqueue's: a member whose last solve was part of a
+ * launch on this very stream is ordered by it; a member's own stream is waited for only where it may hold work this stream has not seen
+ * (uploads, an export that went out ahead, a solve of its own).  A member whose last solve was a tqgpu_mpc_step_batch's holds nothing
+ * anywhere: that call returned behind the post of u[0], which went out behind every member's last launch (MpcBatchBuf::drained_at). */
+int adj_group_enqueue(tqgpu_solver **v, AdjGroup &g, const Opts &O, const double *wx, const double *wu, int nw, const std::vector<AdjSpan> &span) {
+    tqgpu_solver *lead = v[g.idx[0]];
+    const size_t n = g.idx.size();
+    int rc;
+    HIP_TRY(hipSetDevice(lead->device));
+    size_t w_all = 0, heads_all = 0, lvl_ints = 0;
+    for (int i : g.idx) {
+        tqgpu_solver *s = v[i];
+        if ((rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
+        w_all += adj_w_doubles(s, nw); heads_all += (size_t)s->sens.nx0 * nw + 1; lvl_ints += 2 * (size_t)s->T.Nh;
+    }
+    MpcAdjBatch &B = lead->adjb;
+    const size_t items_bytes = n * sizeof(AItem);
+    if ((rc = adj_grow(lead, B.d_desc, B.h_desc, B.desc_cap, items_bytes + lvl_ints * sizeof(int), "the descriptors of a batched adjoint")) ||
+        (rc = adj_grow(lead, B.d_w, B.h_w, B.w_cap, w_all, "the loss gradients of a batched adjoint")) ||
+        (rc = adj_grow(lead, B.d_heads, B.h_heads, B.heads_cap, heads_all, "the heads of a batched adjoint")))
+        return rc;
+    AItem *items = reinterpret_cast<AItem *>(B.h_desc);
+    int *h_lvl = reinterpret_cast<int *>(B.h_desc + items_bytes);
+    const int *d_lvl = reinterpret_cast<const int *>(B.d_desc + items_bytes);
+    /* widths of the grids: per launch the largest member's extent (0: no launch) */
+    int np_all = 0, np_fac = 0, nn_all = 0, cells = 0, nh_all = 0, nh_fac = 0;
+    size_t l_hess = 0, l_factor = 0, l_sweep = 0, l_rhs = 0, l_grad = 0;
+    std::vector<int> wide_bwd, wide_fac, wide_fwd;
+    std::vector<hipStream_t> waited;
+    auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
+    size_t w_at = 0, h_at = 0, l_at = 0;
+    g.views.assign(n, Sens{});
+    for (size_t m = 0; m < n; m++) {
+        tqgpu_solver *s = v[g.idx[m]];
+        const bool drained = s->solve_no == s->mpcb.drained_at;
+        const bool in_launch = s->settle_stream != nullptr;
+        if (drained || s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;
+        else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); MPC_COUNT(waits, 1); } SETTLE(s); }
+        const bool own_solve = !in_launch && !drained && s->solve_no != s->adjb.drained_at;
+        if (s->stream != lead->stream && !was_waited_for(s->stream) && (s->stream_pending || s->out.valid || own_solve)) {
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            s->stream_pending = false;
+            waited.push_back(s->stream);
+            MPC_COUNT(waits, 1);
+        }
+        s->adjb.drained_at = s->solve_no;
+        MpcSens &ms = s->sens;
+        ms.adj_valid = false;
+        const ExportSizes z = export_sizes(s);
+        const size_t nxe = (size_t)z.nxe, snu = (size_t)s->sum_nu, nwd = adj_w_doubles(s, nw);
+        AItem &it = items[m];
+        it = AItem{};
+        it.T = s->T; it.D = s->D; it.O = O;
+        it.needs_factor = ms.factored ? 0 : 1;
+        it.needs_export = it.needs_factor && !s->out.valid ? 1 : 0;
+        Sens S = ms.v;
+        if (it.needs_factor) {          /* the view sens_enqueue_factor makes */
+            S.x = s->out.d; S.u = S.x + z.nxe;
+            S.root_states = s->mpc.states ? 1 : 0;
+            if (s->mpc.d) { S.A0 = s->mpc.d; S.S0 = s->mpc.S0 ? s->mpc.d + (size_t)s->mpc.nb * s->mpc.nx0 + s->mpc.nb : nullptr; }
+            S.x0 = s->mpc.h;
+        }
+        it.S = g.views[m] = S;
+        it.A = ms.a;
+        it.A.wx = B.d_w + w_at; it.A.wu = it.A.wx + nxe * (size_t)nw; it.A.head = B.d_heads + h_at;
+        /* w through the lead's pinned block: [wx | wu] of this member, a missing part as zeros */
+        double *hw = B.h_w + w_at;
+        if (wx) memcpy(hw, wx + span[(size_t)g.idx[m]].wx, sizeof(double) * nxe * nw); else memset(hw, 0, sizeof(double) * nxe * nw);
+        if (wu) memcpy(hw + nxe * nw, wu + span[(size_t)g.idx[m]].wu, sizeof(double) * snu * nw); else memset(hw + nxe * nw, 0, sizeof(double) * snu * nw);
+        w_at += nwd; h_at += (size_t)ms.nx0 * nw + 1;
+        const int Nh = s->T.Nh;
+        it.lvl = d_lvl + l_at;
+        for (int l = 0; l < Nh; l++) { h_lvl[l_at + 2 * l] = s->lvl_first[l]; h_lvl[l_at + 2 * l + 1] = s->lvl_first[l + 1] - s->lvl_first[l]; }
+        l_at += 2 * (size_t)Nh;
+        it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
+        it.d_out = s->out.d;
+        it.x_pad = s->x_pad; it.nxe = z.nxe; it.nue = z.nue; it.nl = z.nl; it.nx0 = s->nx0;
+        np_all = std::max(np_all, s->T.Np); nn_all = std::max(nn_all, s->T.Nn); nh_all = std::max(nh_all, Nh);
+        if ((int)wide_bwd.size() < Nh) { wide_bwd.resize(Nh, 0); wide_fwd.resize(Nh, 0); }
+        for (int l = 0; l < Nh; l++) {
+            const int count = s->lvl_first[l + 1] - s->lvl_first[l];
+            wide_bwd[Nh - 1 - l] = std::max(wide_bwd[Nh - 1 - l], count);
+            if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
+        }
+        l_sweep = std::max(l_sweep, s->lds_forward); l_rhs = std::max(l_rhs, ms.lds_rhs); l_grad = std::max(l_grad, ms.lds_grad);
+        if (it.needs_factor) {
+            np_fac = std::max(np_fac, s->T.Np); nh_fac = std::max(nh_fac, Nh);
+            if ((int)wide_fac.size() < Nh) wide_fac.resize(Nh, 0);
+            for (int l = 0; l < Nh; l++) wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], s->lvl_first[l + 1] - s->lvl_first[l]);
+            l_hess = std::max(l_hess, s->lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
+            if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
+        }
+    }
+    if ((rc = allow_lds(k_sens_hess_batch, l_hess)) || (rc = allow_lds(k_sens_factor_batch, l_factor)) || (rc = allow_lds(k_adj_rhs_batch, l_rhs)) ||
+        (rc = allow_lds(k_adj_backward_batch, l_sweep)) || (rc = allow_lds(k_adj_forward_batch, l_sweep)) || (rc = allow_lds(k_adj_grad_batch, l_grad)))
+        return rc;
+    hipStream_t ls = lead->stream;
+    const unsigned nz = (unsigned)n, cols = (unsigned)nw;
+    const AItem *d_items = reinterpret_cast<const AItem *>(B.d_desc);
+    HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, items_bytes + lvl_ints * sizeof(int), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
+    if (w_all) HIP_TRY(hipMemcpyAsync(B.d_w, B.h_w, sizeof(double) * w_all, hipMemcpyHostToDevice, ls));
+    MPC_COUNT(copies, 1);
+    if (cells) { hipLaunchKernelGGL(k_adj_export_batch, dim3((unsigned)((cells + 255) / 256), nz), dim3(256), 0, ls, d_items); MPC_COUNT(launches, 1); }
+    if (np_fac) {
+        hipLaunchKernelGGL(k_sens_hess_batch, dim3((unsigned)np_fac, 1, nz), dim3(WAVE), l_hess, ls, d_items);
+        for (int j = 0; j < nh_fac; j++) hipLaunchKernelGGL(k_sens_factor_batch, dim3((unsigned)wide_fac[j], 1, nz), dim3(WAVE), l_factor, ls, d_items, j);
+        MPC_COUNT(launches, 1 + nh_fac);
+    }
+    hipLaunchKernelGGL(k_adj_rhs_batch, dim3((unsigned)np_all, cols, nz), dim3(WAVE), l_rhs, ls, d_items);
+    for (int j = 0; j < nh_all; j++) hipLaunchKernelGGL(k_adj_backward_batch, dim3((unsigned)wide_bwd[j], cols, nz), dim3(WAVE), l_sweep, ls, d_items, j);
+    for (int j = 0; j + 1 < nh_all; j++) hipLaunchKernelGGL(k_adj_forward_batch, dim3((unsigned)wide_fwd[j], cols, nz), dim3(WAVE), l_sweep, ls, d_items, j);
+    hipLaunchKernelGGL(k_adj_grad_batch, dim3((unsigned)nn_all, cols, nz), dim3(WAVE), l_grad, ls, d_items);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1 + nh_all + (nh_all - 1) + 1);
+    HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
+    lead->stream_pending = true;
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *o, const double *wx, const double *wu, int nw, double *gx0, int *n_reg) {
+    const char *who = "tqgpu_mpc_adjoint_batch";
+    if (!solvers || n < 1 || !o) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and opts are required, n must be at least 1)");
+    if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
+    int rc;
+    /* the refusals, all of them before any member is touched */
+    std::set<const tqgpu_solver *> seen;
+    for (int i = 0; i < n; i++) {
+        size_t lf, lp;
+        if ((rc = sens_refuse(solvers[i], o, who)) || (rc = adj_window_refuse(solvers[i], nw)) || (rc = sens_window_refuse(solvers[i], lf, lp)))
+            return fail(rc, "member " + std::to_string(i) + ": " + g_err);
+        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
+    }
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    const char *sw = getenv("TREEQP_AMD_ADJ_BATCH");          /* =members: every member through tqgpu_mpc_adjoint's own route, as a group of one goes */
+    const bool by_member = sw && strcmp(sw, "members") == 0;
+    std::vector<AdjSpan> span((size_t)n);
+    {
+        AdjSpan at{0, 0, 0};
+        for (int i = 0; i < n; i++) {
+            const tqgpu_solver *s = solvers[i];
+            span[(size_t)i] = at;
+            at.wx += (size_t)(s->sum_nx - s->x_pad) * nw; at.wu += (size_t)s->sum_nu * nw; at.gx0 += (size_t)s->mpc.nx0 * nw;
+        }
+    }
+    std::vector<AdjGroup> groups;
+    for (int i = 0; i < n; i++) {
+        auto g = std::find_if(groups.begin(), groups.end(), [&](const AdjGroup &q) { return q.device == solvers[i]->device; });
+        if (g == groups.end()) { groups.push_back(AdjGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
+        g->idx.push_back(i);
+    }
+    MpcLive live;
+    /* everything goes out before the first wait of a batched group; a group that goes member by member waits member by member */
+    for (AdjGroup &g : groups) {
+        g.batched = !by_member && adj_group_batched(solvers, g);
+        if (g.batched) {
+            if ((rc = adj_group_enqueue(solvers, g, O, wx, wu, nw, span))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
+            continue;
+        }
+        for (int i : g.idx) {
+            tqgpu_solver *s = solvers[i];
+            SETTLE(s);
+            HIP_TRY(hipSetDevice(s->device));
+            const AdjSpan &at = span[(size_t)i];
+            if ((rc = mpc_adjoint_one(s, O, wx ? wx + at.wx : nullptr, wu ? wu + at.wu : nullptr, nw, n_reg ? n_reg + i : nullptr))) return rc;
+            if (gx0) memcpy(gx0 + at.gx0, s->sens.ah + adj_w_doubles(s, nw), sizeof(double) * (size_t)s->sens.nx0 * nw);
+        }
+    }
+    for (AdjGroup &g : groups) {
+        if (!g.batched) continue;
+        tqgpu_solver *lead = solvers[g.idx[0]];
+        HIP_TRY(hipSetDevice(lead->device));
+        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
+        lead->stream_pending = false;
+        size_t h_at = 0;
+        for (size_t m = 0; m < g.idx.size(); m++) {
+            const int i = g.idx[m];
+            tqgpu_solver *s = solvers[i];
+            MpcSens &ms = s->sens;
+            const size_t head = (size_t)ms.nx0 * nw + 1;
+            const double *h = lead->adjb.h_heads + h_at;
+            memcpy(ms.ah + adj_w_doubles(s, nw), h, sizeof(double) * head);          /* where tqgpu_mpc_get_adjoint_x0 reads it */
+            if (gx0) memcpy(gx0 + span[(size_t)i].gx0, h, sizeof(double) * (head - 1));
+            if (n_reg) n_reg[i] = (int)h[head - 1];
+            ms.v = g.views[m];
+            ms.factored = true;          /* (valid stays as it was: a stored sensitivity was not touched, a missing one is still missing) */
+            ms.nw = nw;
+            ms.adj_valid = true;
+            h_at += head;
+        }
+    }
     return TQGPU_OK;
 }
 

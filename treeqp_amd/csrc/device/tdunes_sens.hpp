@@ -16,7 +16,8 @@
  * buffers (struct Sens); Data is only read.
  *
  * The adjoint of a step (k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad; struct Adj) is the reverse: one more solve with the same
- * factor, one right-hand side per column of w = dL/dz, non-zero in every block; its formulas stand with its kernels below.
+ * factor, one right-hand side per column of w = dL/dz, non-zero in every block; its formulas stand with its kernels below.  The batch
+ * forms at the end (struct AItem, k_*_batch) are the same bodies behind a look-up of the member.
  */
 #pragma once
 
@@ -596,5 +597,92 @@ __global__ void __launch_bounds__(WAVE) k_adj_grad(Tree T, Data D, Sens S, Adj A
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     adj_grad_body(T, D, S, A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+
+/* ---- the adjoint for a batch of mirrors in one set of launches (tqgpu_mpc_adjoint_batch) ----
+ * One descriptor per member, uploaded with every call: what the single launches pass as kernel arguments, and the member's level table,
+ * which the single launches read on the host (lvl[2 l], lvl[2 l + 1]: first block and block count of block level l < T.Nh; the tables
+ * travel in the same block behind the items).  Every kernel below is the single kernel's body behind a look-up of the member:
+ * blockIdx.z = member, blockIdx.y = column, blockIdx.x = what it is in the single launch.  The grid is as wide as the largest member
+ * needs at that launch; a wave beyond its member's own extent, on a level the member does not have, or in a hess / factor launch of a
+ * member whose factor is stored, returns at once and writes nothing.  Launch j of the backward sweeps takes level T.Nh - 1 - j of a
+ * member, launch j of the forward sweep level j + 1: members are independent, a shallow one finishes early.  No kernel waits for
+ * another workgroup. */
+struct AItem {
+    Tree T; Data D; Opts O; Sens S; Adj A;
+    const int *lvl;                /* [2 T.Nh] first, count of every block level */
+    const double *lamc;            /* the packing (k_adj_export_batch, tdunes_mpc.hpp): the current duals as the host knows them after the solve, */
+    double *d_out;                 /* the member's export block, */
+    int x_pad, nxe, nue, nl, nx0;  /* phantom root states, the export sizes (x without them, u, lam), the root's states */
+    int needs_export, needs_factor;      /* d_out is not packed yet and the factor has to be built from it; the factor is not stored */
+};
+__global__ void __launch_bounds__(WAVE) k_sens_hess_batch(const AItem *__restrict__ items)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    if (!it.needs_factor || (int)blockIdx.x >= it.T.Np) return;
+    sens_hess_body(it.T, it.D, it.S, blockIdx.x, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_sens_factor_batch(const AItem *__restrict__ items, int j)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    const int lvl = it.T.Nh - 1 - j;
+    if (!it.needs_factor || lvl < 0 || (int)blockIdx.x >= it.lvl[2 * lvl + 1]) return;
+    sens_factor_body(it.T, it.O, it.S, it.lvl[2 * lvl] + (int)blockIdx.x, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_rhs_batch(const AItem *__restrict__ items)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    if ((int)blockIdx.x >= it.T.Np || (int)blockIdx.y >= it.A.nw) return;
+    adj_rhs_body(it.T, it.D, it.S, it.A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_backward_batch(const AItem *__restrict__ items, int j)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    const int lvl = it.T.Nh - 1 - j;
+    if (lvl < 0 || (int)blockIdx.x >= it.lvl[2 * lvl + 1] || (int)blockIdx.y >= it.A.nw) return;
+    adj_backward_body(it.T, it.S, it.A, it.lvl[2 * lvl] + (int)blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_forward_batch(const AItem *__restrict__ items, int j)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    const int lvl = j + 1;
+    if (lvl >= it.T.Nh || (int)blockIdx.x >= it.lvl[2 * lvl + 1] || (int)blockIdx.y >= it.A.nw) return;
+    adj_forward_body(it.T, it.S, it.A, it.lvl[2 * lvl] + (int)blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adj_grad_batch(const AItem *__restrict__ items)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    if ((int)blockIdx.x >= it.T.Nn || (int)blockIdx.y >= it.A.nw) return;
+    adj_grad_body(it.T, it.D, it.S, it.A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
 #endif
