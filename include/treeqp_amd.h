@@ -655,7 +655,7 @@ int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, in
  *   tqgpu_mpc_get_adjoint      gq ((sum_nx without phantom root states) x nw), gr (sum_nu x nw), gb (sum_lam x nw), column major; any
  *                        pointer may be NULL.  Downloads and waits; not counted (a diagnostic read-out).
  * A stored adjoint is invalidated by the same events as a stored sensitivity; the getters then return TQGPU_EINVAL.  The gradients with
- * respect to H, A, B are outer products of these vectors with the solution and are left to the caller. */
+ * respect to H, A, B are outer products of these vectors with the solution: tqgpu_mpc_adjoint_matrices below. */
 int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *opts, const double *wx, const double *wu, int nw, int *n_reg);
 int tqgpu_mpc_get_adjoint_x0(tqgpu_solver *s, double *gx0);
 int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb);
@@ -682,6 +682,72 @@ int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb);
  *                        member; TQGPU_EINVAL for n < 1, solvers == NULL, opts == NULL, nw < 1 and a mirror named twice.  Every member's
  *                        stored adjoint and sensitivity are then as before. */
 int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, const double *wx, const double *wu, int nw, double *gx0, int *n_reg);
+
+/* ---- The adjoint of an MPC step in H, A, B: outer products on the device, summed over parameter groups and over a batch -----------------
+ * Behind tqgpu_mpc_adjoint (or tqgpu_mpc_adjoint_batch), for every column j of w.  z_k = [x_k; u_k] is the point tqgpu_get_solution would
+ * return, gz_k = [gq_k; gr_k] and gb_c = Y_c the stored adjoint, C_c = [A_c B_c], (E v)_c = C_c v_p - v_c^x.  With the active set frozen and
+ * lam taken in the sign for which stationarity off the bounds reads H z + g + E' lam = 0,
+ *     dL = gz' dg + gb' db + gz' dH z + lam' (dE gz) + gb' (dE z).
+ * That lam is tqgpu_get_solution's lam as it stands, not its negative (settled by the dense KKT solve and the finite differences of the tests).
+ *   kind-0 node k        (diagonal Qd, Rd)  gHd_k[i] = gz_k[i] * z_k[i], nx + nu entries; an entry on a bound has gz = 0, its gradient is 0.0 exactly
+ *   kind-1 node k        (dense H_k = [Q S'; S R], (nx + nu)^2, column major)  gH_k = 1/2 (gz_k z_k' + z_k gz_k'); i >= j is computed and mirrored, so
+ *                        the result is symmetric bit for bit
+ *   child c of p         gA_c = lam_c gq_p' + gb_c x_p' (nx_c x nx_p),  gB_c = lam_c gr_p' + gb_c u_p' (nx_c x nu_p), column major
+ *   eliminated root      (tqgpu_mpc_set_root)  gA0_c = gb_c x0' for the root's children, child after child, each nx_c x nx0 (the layout of A0), and
+ *                        gS0 = gr_0 x0' (nu[0] x nx0) where S0 was given, 0.0 where it was not; x0 is the x0 last folded.  A root with states
+ *                        has neither: gA0 and gS0 are not written
+ *   phantom root states  of an x0-eliminated tree embedded in a uniform one (x_pad states in front of node 0, reported by tqgpu_mpc_get_param_groups)
+ *                        count in the sizes of node 0's blocks and of its children's gA; their entries are written 0.0
+ * These are gradients with respect to H, A, B as the device holds them.  Under tqgpu_mpc_set_tracking q and r depend on Q, R, S through the
+ * fold; that chain rule stays with the caller, who has gh = [gq; gr] of the same groups for it.
+ *   groups               a parameter group is a set of nodes whose matrices are one learnable parameter.  hgroup[k] (int[Nn], -1: in no group) is
+ *                        the group of node k's stage Hessian: all members have the same nx, nu, kind and phantom states.  cgroup[c] is the group
+ *                        of node c's dynamics (A_c, B_c, b_c): all members have the same nx_c, nx_p, nu_p; cgroup[0] must be -1.  A NULL map
+ *                        means every node is its own group (h-group k = node k, Nn groups; c-group c - 1 = node c, Nn - 1 groups; the
+ *                        count given with a NULL map is not read).  The result of an h-group is the sum of its members' gH (gHd) and of
+ *                        their linear terms gh = [gq; gr]; of a c-group the sum of gA, gB and gb.
+ *   the order of the sum  is part of the contract.  The members of a group are taken in ascending node index and cut into chunks of
+ *                        ADJMAT_CHUNK = 64 consecutive members.  A chunk's partial is one chain from 0.0 over its members in ascending order, per member
+ *                          gA, gB:  acc = fma(lam_c[i], gz_p[j], acc);  acc = fma(gb_c[i], z_p[j], acc);
+ *                          gHd:     acc = fma(gz_k[i], z_k[i], acc);
+ *                          gH:      acc = fma(gz_k[i], z_k[j], acc);  acc = fma(z_k[i], gz_k[j], acc);   (i >= j; the partial is 0.5 * acc)
+ *                          gh, gb:  acc = acc + gz_k[i],  acc = acc + gb_c[i].
+ *                        The group's value is the plain sum of the partials in ascending chunk order (the first partial, then + the next); in the
+ *                        batch form that sums over members the order is ascending (member, chunk).  No atomics are used anywhere: a value
+ *                        depends neither on the grid nor on which call produced it.
+ *   tqgpu_mpc_set_param_groups   validates the maps (TQGPU_EINVAL with the offending node in tqgpu_last_error: a value outside [-1, n), members of
+ *                        unequal sizes, cgroup[0] != -1, a group without a member, a group that mixes kinds), builds the member lists and chunk
+ *                        tables and uploads them once.  Kinds, the root form and nx0 are compared again at every call: the maps survive
+ *                        tqgpu_set_objective_mixed and tqgpu_mpc_set_root (the tables are then built and uploaded again, once); a group that has
+ *                        come to mix kinds is refused at the call.  TQGPU_EUNSUPPORTED: a group whose result blocks and one member's vectors do
+ *                        not fit 160 KiB of LDS.  The tables are cleared only by another tqgpu_mpc_set_param_groups and tqgpu_destroy.
+ *   tqgpu_mpc_get_param_groups   the counts, per h-group 5 ints (nx, nu, phantom states, members, the kind it has now), per c-group 4 ints (nx_c,
+ *                        nx_p, nu_p, members), sizes as the device counts them, and root[4]: the rows of gA0 (the nx of the root's children; 0: a
+ *                        root with states, no gA0 and gS0), nu[0], nx0, and nw, the columns of the stored adjoint (0: none is stored), by
+ *                        which every output of tqgpu_mpc_adjoint_matrices is sized; any pointer may be NULL (host state only).  This
+ *                        read-out is public so that a caller can size the outputs without repeating the library's bookkeeping.
+ *   tqgpu_mpc_adjoint_matrices   needs a stored adjoint (TQGPU_EINVAL otherwise, as the getters: whatever invalidates it makes this call
+ *                        TQGPU_EINVAL) and the groups; any output may be NULL.  An output holds its groups' blocks one behind the other,
+ *                        ascending group and then column of w: gH (nx + nu entries of a kind-0 group, (nx + nu)^2 of a kind-1 group), gh (nx + nu),
+ *                        gA (nx_c nx_p), gB (nx_c nu_p), gb (nx_c); gA0 and gS0 column after column.  One launch (k_adjmat_part: one wave per
+ *                        chunk and column; a group of one chunk writes its result itself) and, where a group has more than one chunk, a
+ *                        second (k_adjmat_sum); one copy through pinned memory and one wait, counted into tqgpu_mpc_stats.  It writes only
+ *                        buffers of its own: a later solve, tqgpu_kkt_residual, a stored sensitivity and the stored adjoint keep their bits.
+ *                        Refusals are the adjoint's: kinds 2 and 3 and ranks of a sharded solve have no stored adjoint.
+ *   tqgpu_mpc_adjoint_matrices_batch   behind tqgpu_mpc_adjoint_batch.  Per device one copy of the descriptors, one or two launches (grid z: the
+ *                        member), one copy of the results and one wait, whatever n.  reduce = 0: every member's blocks one behind the other in
+ *                        every output, each member bit for bit its own single call.  reduce = 1: one set of blocks, the sum over the members in
+ *                        member order (every chunk writes its partial, k_adjmat_reduce adds them in ascending (member, chunk) order); all
+ *                        members must then have group tables of equal shapes, kinds, root terms and columns, otherwise TQGPU_EINVAL with the
+ *                        member's index.  All refusals come before any member is touched: a member without a stored adjoint or groups, a mirror
+ *                        named twice, n < 1, solvers == NULL, reduce outside {0, 1}.  Groups per device and the fall-back to member by member
+ *                        (TREEQP_AMD_ADJ_BATCH=members, fewer than ADJ_BATCH_MIN members, lopsided groups) are tqgpu_mpc_adjoint_batch's; with
+ *                        reduce = 1 the fall-back, and members on more than one device, add the members' results on the host in the same
+ *                        member order (the same bits for groups of one chunk). */
+int tqgpu_mpc_set_param_groups(tqgpu_solver *s, const int *hgroup, const int *cgroup, int n_hgroups, int n_cgroups);
+int tqgpu_mpc_get_param_groups(tqgpu_solver *s, int *n_hgroups, int *n_cgroups, int *hdims, int *cdims, int *root);
+int tqgpu_mpc_adjoint_matrices(tqgpu_solver *s, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0);
+int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, int reduce, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0);
 
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written

@@ -58,7 +58,14 @@ behind tqgpu_mpc_sensitivity (the factor stored), with the launches, copies and 
 
 --adjoint-batch: behind every tqgpu_mpc_step_batch of N trees, one random w per member and two ways to the members' gradients, on c1 with
 both root forms and on c2 with root states: (a) one tqgpu_mpc_adjoint_batch, (b) N calls of tqgpu_mpc_adjoint on mirrors of their own; wall
-time, launches, copies and waits of each, and the largest difference of gx0 between them, which must be 0 (adjoint_batch_compare)."""
+time, launches, copies and waits of each, and the largest difference of gx0 between them, which must be 0 (adjoint_batch_compare).
+
+    python tools/mpc_loop.py --adjoint-matrices [--adjoint-batch N[,N2,..]] [--steps 200] [--skip 10] [c1] [c2]
+
+--adjoint-matrices: behind every step and adjoint, the gradients of the matrices with one group for all dynamics and one for all stage
+Hessians of equal sizes, two ways: tqgpu_mpc_adjoint_matrices (with --adjoint-batch N: tqgpu_mpc_adjoint_matrices_batch, reduce = 1, behind
+the batch step and the batch adjoint), and the host route, tqgpu_get_solution + tqgpu_mpc_get_adjoint + numpy outer products and sums
+(adjoint_matrices_compare)."""
 import ctypes as C
 import sys
 import time
@@ -890,6 +897,127 @@ def adjoint_batch_compare(capi, name, p, root_states, n, steps, skip):
     print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |gx0 (a) - gx0 (b)| over the run {dab:.2e}", flush=True)
 
 
+def adjoint_matrices_compare(capi, name, p, root_states, n, steps, skip):
+    """--adjoint-matrices [--adjoint-batch N]: behind every step and adjoint of n trees (n == 0: one tree through the single calls), two
+    ways to the gradients of the matrices with one group for all dynamics and one for all stage Hessians of equal sizes (the leaves, and
+    the root of an x0-eliminated tree, are groups of their own), summed over the members, on the same mirrors (the second leg only reads):
+    (a) tqgpu_mpc_adjoint_matrices (n >= 1: tqgpu_mpc_adjoint_matrices_batch with reduce = 1);
+    (b) the host route: per member tqgpu_get_solution + tqgpu_mpc_get_adjoint, then numpy outer products summed over nodes and members.
+    Wall time is the host clock around each leg.  Launches, copies and waits of (a) are those tqgpu_mpc_stats counts; the calls of (b) are
+    not counted there, their numbers are what the two calls do per member: 1 packing launch, 1 + 3 copies, 1 + 1 waits."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o = capi._gpu_opts()
+    m = max(n, 1)
+    if root_states:
+        d, x0 = full_root(capi, p)
+        xs = [np.concatenate([moved_inward(x0, k, i) for i in range(m)]) for k in range(steps)]
+    else:
+        d, A0, b0, _, x0 = eliminated(capi, p)
+        xs = [np.concatenate([moved(x0, k, i) for i in range(m)]) for k in range(steps)]
+    nk, nx, nu = [np.asarray(d[k], dtype=int) for k in ("nk", "nx", "nu")]
+    Nn, nxx, nuu = len(nk), int(nx[1]), int(nu[1])
+    dad = P_parents(nk)
+    inner, leaves = np.flatnonzero((nk > 0) & (np.arange(Nn) > 0)), np.flatnonzero(nk == 0)
+    assert np.all(nx[1:] == nxx) and np.all(nu[inner] == nuu) and int(nu[0]) == nuu, "a uniform tree is expected"
+    hgroup = np.where(nk > 0, 0, 1).astype(np.int32)
+    if not root_states:
+        hgroup[0] = 2          # the root of an x0-eliminated tree has other sizes
+    cgroup = np.zeros(Nn, dtype=np.int32)
+    cgroup[0] = -1
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        if root_states:
+            g.mpc_set_root_states()
+        else:
+            g.mpc_set_root(A0, b0)
+        g.set_warm_start(1)
+        g.mpc_set_param_groups(hgroup, cgroup)
+        return g
+
+    gs = [mirror() for _ in range(m)]
+    arr = (C.c_void_p * m)(*[g.h for g in gs])
+    res = (capi.GpuResult * m)()
+    snx, snu, snl = int(gs[0].sum_nx), int(gs[0].sum_nu), int(gs[0].sum_lam)
+    nx0, nu0 = len(x0), int(nu[0])
+    dims = np.zeros(4, dtype=np.int32)
+    cd = np.zeros(4, dtype=np.int32)
+    assert L.tqgpu_mpc_get_param_groups(gs[0].h, None, None, None, capi._ip(cd), capi._ip(dims)) == 0
+    nxp = int(cd[1])          # the device's count: the phantom root states of an embedded tree are columns of gA
+    gA, gB, gb = np.zeros(nxx * nxp), np.zeros(nxx * nuu), np.zeros(nxx)
+    nzi = nxx + nuu
+    gH, gh = np.zeros(4 * (nzi + nxx + nxp + nuu)), np.zeros(4 * (nzi + nxx + nxp + nuu))
+    gA0, gS0 = np.zeros(max(int(dims[0]) * nx0, 1)), np.zeros(max(nu0 * nx0, 1))
+    u0 = np.zeros(max(nu0 * m, 1))
+    gx, nregs, nreg = np.zeros(nx0 * m), np.zeros(m, dtype=np.int32), C.c_int()
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    x, u, lam = np.zeros(snx), np.zeros(snu), np.zeros(snl)
+    gq, gr, gbn = np.zeros(snx), np.zeros(snu), np.zeros(snl)
+    xoff = np.concatenate([[0], np.cumsum(nx)])
+    rows_x = xoff[1] + np.arange((Nn - 1) * nxx).reshape((Nn - 1, nxx))          # nodes 1 .. Nn - 1 in the flat x
+    par = dad[1:]
+    rng = np.random.Generator(np.random.PCG64(2222))
+    t = {k: [] for k in "ab"}
+    cnt, dA, dB, dH, bad = [], 0.0, 0.0, 0.0, 0
+    for k in range(steps):
+        wx, wu = rng.standard_normal(snx * m), rng.standard_normal(snu * m)
+        if n == 0:
+            assert L.tqgpu_mpc_step(gs[0].h, dp(xs[k]), C.byref(o), res, dp(u0)) == 0, L.tqgpu_last_error()
+            assert L.tqgpu_mpc_adjoint(gs[0].h, C.byref(o), dp(wx), dp(wu), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+        else:
+            assert L.tqgpu_mpc_step_batch(arr, m, dp(xs[k]), C.byref(o), res, dp(u0)) == 0, L.tqgpu_last_error()
+            assert L.tqgpu_mpc_adjoint_batch(arr, m, C.byref(o), dp(wx), dp(wu), 1, dp(gx), capi._ip(nregs)) == 0, L.tqgpu_last_error()
+        bad += sum(res[i].status != 0 for i in range(m))
+        t0 = time.perf_counter()
+        if n == 0:
+            rc = L.tqgpu_mpc_adjoint_matrices(gs[0].h, dp(gH), dp(gh), dp(gA), dp(gB), dp(gb), dp(gA0), dp(gS0))
+        else:
+            rc = L.tqgpu_mpc_adjoint_matrices_batch(arr, m, 1, dp(gH), dp(gh), dp(gA), dp(gB), dp(gb), dp(gA0), dp(gS0))
+        t["a"].append(time.perf_counter() - t0)
+        assert rc == 0, L.tqgpu_last_error()
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        cnt.append((la.value, co.value, wa.value))
+        t0 = time.perf_counter()
+        hA, hB, hHd = np.zeros((nxx, nxx)), np.zeros((nxx, nuu)), np.zeros(nzi)
+        for g in gs:
+            assert L.tqgpu_get_solution(g.h, dp(x), dp(u), dp(lam), None, None, None) == 0
+            assert L.tqgpu_mpc_get_adjoint(g.h, dp(gq), dp(gr), dp(gbn)) == 0
+            lamc, gbc = lam.reshape((Nn - 1, nxx)), gbn.reshape((Nn - 1, nxx))
+            # the parents' x, gq (a root without states: zeros) and u, gr
+            X, GQ = np.zeros((Nn, nxx)), np.zeros((Nn, nxx))
+            X[1:], GQ[1:] = x[rows_x], gq[rows_x]
+            if root_states:
+                X[0], GQ[0] = x[:nxx], gq[:nxx]
+            U, GR = u.reshape((-1, nuu)), gr.reshape((-1, nuu))          # the nodes with inputs are the first ones, level by level
+            hA += lamc.T @ GQ[par] + gbc.T @ X[par]
+            hB += lamc.T @ GR[par] + gbc.T @ U[par]
+            hHd += np.concatenate([np.sum(GQ[inner] * X[inner], axis=0), np.sum(GR[inner] * U[inner], axis=0)])
+            if root_states:
+                hHd += np.concatenate([GQ[0] * X[0], GR[0] * U[0]])
+        t["b"].append(time.perf_counter() - t0)
+        dA = max(dA, float(np.max(np.abs(gA.reshape((nxx, nxp), order="F")[:, nxp - nxx:] - hA))))
+        dB = max(dB, float(np.max(np.abs(gB.reshape((nxx, nuu), order="F") - hB))))
+        dH = max(dH, float(np.max(np.abs(gH[:nzi] - hHd))))
+    for g in gs:
+        g.close()
+    med = tuple(int(np.median([e[i] for e in cnt[skip:]])) for i in range(3))
+    form = "roots with states" if root_states else "x0 eliminated"
+    how = "tqgpu_mpc_adjoint_matrices" if n == 0 else f"tqgpu_mpc_adjoint_matrices_batch, reduce = 1, N = {n}"
+    print(f"{name}, --adjoint-matrices, {form}: {m} mirror(s) of {Nn} nodes, {steps} steps, {how}; one c-group of {Nn - 1} nodes, h-groups of {len(inner) + (1 if root_states else 0)} "
+          f"and {len(leaves)} nodes{'' if root_states else ' and the root'}; member steps with another status than 0: {bad}")
+    ma, lo, p90 = stats(t["a"][skip:])
+    print(f"    {'(a) device':34s} wall median {ma:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d" % med, flush=True)
+    mb, lo, p90 = stats(t["b"][skip:])
+    print(f"    {'(b) downloads + numpy, ' + str(m) + ' member(s)':34s} wall median {mb:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d (not counted by tqgpu_mpc_stats: per member 1, 1 + 3, 1 + 1)" % (m, 4 * m, 2 * m), flush=True)
+    print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |(a) - (b)| over the run: gA {dA:.2e}, gB {dB:.2e}, gHd of the inner nodes {dH:.2e}", flush=True)
+
+
+def P_parents(nk):
+    from treeqp_amd import problems as P
+    return np.asarray(P.parents_of(nk), dtype=int)
+
+
 def predict_compare(capi, name, p, tracking, steps, skip):
     """--predict: iterations and trials per step over the closed-loop sequence of --root-states (tracking: of --tracking), two ways on a
     root with states: warm start mode 1, and mode 1 with the dual predictor: behind every step tqgpu_mpc_sensitivity, then
@@ -945,6 +1073,15 @@ def main():
             gain_compare(capi, "c1", P.spring_mass(), False, steps, skip)
         if "c2" in names:
             gain_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--adjoint-matrices" in args:
+        sizes = [int(v) for v in args[args.index("--adjoint-batch") + 1].split(",")] if "--adjoint-batch" in args else [0]
+        for nb in sizes:
+            if "c1" in names:
+                adjoint_matrices_compare(capi, "c1", P.spring_mass(), True, nb, steps, skip)
+                adjoint_matrices_compare(capi, "c1", P.spring_mass(), False, nb, steps, skip)
+            if "c2" in names:
+                adjoint_matrices_compare(capi, "c2", P.linear_chain(2, 9, 9), True, nb, steps, skip)
         return
     if "--adjoint-batch" in args:
         sizes = [int(v) for v in args[args.index("--adjoint-batch") + 1].split(",")]          # N, or N1,N2,.. in one process

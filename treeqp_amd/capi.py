@@ -598,6 +598,74 @@ def mpc_adjoint_batch(mirrors, wxs=None, wus=None, profile=0, **kw) -> list:
     return [dict(gx0=g[at[i]:at[i + 1]].copy().reshape((nx0[i], nw), order="F"), n_reg=int(nr[i])) for i in range(n)]
 
 
+ADJMAT_KEYS = ("gH", "gh", "gA", "gB", "gb", "gA0", "gS0")
+
+
+def _adjmat_sizes(m):
+    """(per output of tqgpu_mpc_adjoint_matrices the list of its blocks' shapes per column of w, the columns of the stored adjoint), both as
+    the library reports them; gH: (nz,) for a kind-0 group, (nz, nz) for a kind-1 group.  Without a stored adjoint the columns read 1: the
+    buffers are then never written, the call is refused"""
+    nh, nc, root = C.c_int(0), C.c_int(0), np.zeros(4, dtype=np.int32)
+    m._chk(lib().tqgpu_mpc_get_param_groups(m.h, C.byref(nh), C.byref(nc), None, None, None))
+    hd, cd = np.zeros(max(5 * nh.value, 1), dtype=np.int32), np.zeros(max(4 * nc.value, 1), dtype=np.int32)
+    m._chk(lib().tqgpu_mpc_get_param_groups(m.h, None, None, _ip(hd), _ip(cd), _ip(root)))
+    hd, cd = hd[:5 * nh.value].reshape((-1, 5)), cd[:4 * nc.value].reshape((-1, 4))
+    dense = [bool(k) for k in hd[:, 4]]
+    hd = hd[:, :4]
+    nb, nu0, nx0, nw = [int(v) for v in root]
+    root = nb > 0
+    return dict(gH=[(int(a + b), int(a + b)) if dn else (int(a + b),) for (a, b, _, _), dn in zip(hd, dense)], gh=[(int(a + b),) for a, b, _, _ in hd],
+                gA=[(int(a), int(b)) for a, b, _, _ in cd], gB=[(int(a), int(c)) for a, _, c, _ in cd], gb=[(int(a),) for a, _, _, _ in cd],
+                gA0=[(int(m.nx[k]), nx0) for k in range(1, 1 + int(m.nk[0]))] if root else [], gS0=[(nu0, nx0)] if root else []), max(nw, 1)
+
+
+def _adjmat_split(flat, shapes, nw, by_column=False):
+    """one output of nw columns -> a list with one array per group, shape + (nw,); by_column (gA0): the blocks lie column after column,
+    within a column one behind the other"""
+    out, at = [], 0
+    if by_column:
+        total = sum(int(np.prod(shp)) for shp in shapes)
+        cols = flat[:total * nw].reshape((total, nw), order="F")
+        for shp in shapes:
+            n = int(np.prod(shp))
+            out.append(cols[at:at + n].reshape(shp + (nw,), order="F").copy())
+            at += n
+        return out
+    for shp in shapes:
+        n = int(np.prod(shp))
+        out.append(flat[at:at + n * nw].reshape(shp + (nw,), order="F").copy())
+        at += n * nw
+    return out
+
+
+def mpc_adjoint_matrices_batch(mirrors, reduce: bool = False) -> list | dict:
+    """The matrix gradients of every mirror's stored adjoint (tqgpu_mpc_adjoint_matrices_batch, behind mpc_adjoint_batch): per device one copy
+    of descriptors, one or two launches, one copy back and one wait.  reduce False: a list with one dict per member as
+    TqGpu.mpc_adjoint_matrices returns it; reduce True: one dict, the sum over the members in member order (equal group tables required)."""
+    n = len(mirrors)
+    both = [_adjmat_sizes(m) for m in mirrors]
+    sizes, nws = [b[0] for b in both], [b[1] for b in both]
+    if n == 0:          # the library's refusal, not an index error here
+        rc = lib().tqgpu_mpc_adjoint_matrices_batch(None, 0, int(bool(reduce)), *([None] * 7))
+        raise RuntimeError(f"tqgpu_mpc_adjoint_matrices_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    use = range(1) if reduce else range(n)
+    total = {key: sum(sum(int(np.prod(shp)) for shp in sizes[i][key]) * nws[i] for i in use) for key in ADJMAT_KEYS}
+    bufs = {key: np.zeros(max(total[key], 1)) for key in ADJMAT_KEYS}
+    arr = (C.c_void_p * max(n, 1))(*[m.h for m in mirrors])
+    rc = lib().tqgpu_mpc_adjoint_matrices_batch(arr, n, int(bool(reduce)), *[_dp(bufs[key]) for key in ADJMAT_KEYS])
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_mpc_adjoint_matrices_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    out, at = [], {key: 0 for key in ADJMAT_KEYS}
+    for i in use:
+        one = {}
+        for key in ADJMAT_KEYS:
+            cnt = sum(int(np.prod(shp)) for shp in sizes[i][key]) * nws[i]
+            one[key] = _adjmat_split(bufs[key][at[key]:at[key] + cnt], sizes[i][key], nws[i], key == "gA0")
+            at[key] += cnt
+        out.append(one)
+    return out[0] if reduce else out
+
+
 SHIFT_LEAF_REPEAT, SHIFT_LEAF_ZERO = 0, 1          # TQGPU_SHIFT_LEAF_* of include/treeqp_amd.h
 SHIFT_DUALS, SHIFT_WORKING_SETS = 1, 2             # TQGPU_SHIFT_*
 c_u64_p = C.POINTER(C.c_uint64)
@@ -1017,6 +1085,27 @@ class TqGpu:
         out = {key: np.zeros(max(n * nw, 1)) for key, n in sizes}
         self._chk(lib().tqgpu_mpc_get_adjoint(self.h, _dp(out["gq"]), _dp(out["gr"]), _dp(out["gb"])))
         return {key: out[key][:n * nw].reshape((n, nw), order="F") for key, n in sizes}
+
+    # ---- the adjoint in H, A, B: outer products summed over parameter groups (tqgpu_mpc_adjoint_matrices) ----
+    def mpc_set_param_groups(self, hgroup=None, cgroup=None):
+        """The parameter groups of mpc_adjoint_matrices (tqgpu_mpc_set_param_groups): hgroup[k], cgroup[c] in [-1, groups), -1 meaning in
+        no group, None meaning every node its own group; the number of groups is the largest index + 1."""
+        Nn = len(self.nk)
+        hg = None if hgroup is None else _i32(hgroup)
+        cg = None if cgroup is None else _i32(cgroup)
+        assert (hg is None or len(hg) == Nn) and (cg is None or len(cg) == Nn), "one entry per node"
+        self._chk(lib().tqgpu_mpc_set_param_groups(self.h, None if hg is None else _ip(hg), None if cg is None else _ip(cg),
+                                                   0 if hg is None else int(hg.max(initial=-1)) + 1, 0 if cg is None else int(cg.max(initial=-1)) + 1))
+
+    def mpc_adjoint_matrices(self) -> dict:
+        """The gradients of the stored adjoint with respect to the matrices the device holds (tqgpu_mpc_adjoint_matrices): a dict of lists,
+        one array per group with the column of w as its last axis: gH ((nz, nw) for a kind-0 group, (nz, nz, nw) for a kind-1 group), gh
+        (nz, nw), gA (nx_c, nx_p, nw), gB (nx_c, nu_p, nw), gb (nx_c, nw), and for an eliminated root gA0 (one (nx_c, nx0, nw) array per child of
+        the root) and gS0 [(nu[0], nx0, nw)]; sizes count the phantom root states of an embedded tree."""
+        sizes, nw = _adjmat_sizes(self)
+        bufs = {key: np.zeros(max(sum(int(np.prod(shp)) for shp in sizes[key]) * nw, 1)) for key in ADJMAT_KEYS}
+        self._chk(lib().tqgpu_mpc_adjoint_matrices(self.h, *[_dp(bufs[key]) for key in ADJMAT_KEYS]))
+        return {key: _adjmat_split(bufs[key], sizes[key], nw, key == "gA0") for key in ADJMAT_KEYS}
 
     def export_ahead(self, on: bool) -> None:
         """the solution's packing kernel and download go out behind the solve's launch (callers that fetch the solution after every solve)"""

@@ -37,8 +37,10 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1890,6 +1892,21 @@ struct MpcAdjBatch {
     double *d_heads = nullptr, *h_heads = nullptr; size_t heads_cap = 0;
 };
 
+/* tqgpu_mpc_set_param_groups / tqgpu_mpc_adjoint_matrices*: the maps as given (a NULL map filled in), the tables built from them and from the kinds, the
+ * root form and nx0 the device held then (sig; compared at every call, built and uploaded again where they moved), the sizes of the seven result regions
+ * and of the partials in doubles per column of w, the result block on the device and pinned, the partials.  Batched route (the first member of a device's
+ * group owns them): the descriptors (AMItem), uploaded with every call, and the result block of all members with its pinned twin */
+struct MpcAdjMat {
+    bool set = false;
+    std::vector<int> hgroup, cgroup, sig, hdims, cdims;      /* hdims: nx, nu, pad, members per h-group; cdims: nx_c, nx_p, nu_p, members per c-group */
+    int n_h = 0, n_c = 0, n_units = 0;
+    int *d_tab = nullptr;
+    AdjMat v{};
+    size_t reg[8] = {}, part1 = 0, lds = 0;      /* reg[i]: where region i of [gH | gh | gA | gB | gb | gA0 | gS0] begins, reg[7] the total */
+    double *d_res = nullptr, *h_res = nullptr, *d_part = nullptr; size_t res_cap = 0, part_cap = 0;
+    char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
+    double *d_bres = nullptr, *h_bres = nullptr; size_t bres_cap = 0;
+};
 /* ---- the solution's way out and its check (tdunes_kkt.hpp): the solution in one piece, [x | u | lam | dlam | mu_x | mu_u], packed on the device (d) and
  * downloaded into pinned memory (h).  valid: h holds (or is about to hold, stream-ordered) the solution of the last solve; dev_only, with valid: the pack
  * is in d only (a certified tqgpu_mpc_step), tqgpu_get_solution downloads it.  The three transitions below are the only writers of the two flags. ---- */
@@ -2060,7 +2077,7 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb;      /* the MPC family (tdunes_mpc.hpp), one record per feature */
+    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcAdjMat adjm;      /* the MPC family (tdunes_mpc.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;

@@ -1437,6 +1437,335 @@ extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgp
     return TQGPU_OK;
 }
 
+/* ---- the adjoint in H, A, B (tdunes_sens.hpp: k_adjmat_part, k_adjmat_sum): outer products of the stored adjoint with the point, summed over the
+ * caller's parameter groups, back through pinned memory in one copy with one wait ---- */
+namespace {
+constexpr int ADJMAT_REGIONS = 7;          /* gH, gh, gA, gB, gb, gA0, gS0 */
+int adjmat_kind(const tqgpu_solver *s, int k) { return s->dense && !s->h_kind.empty() ? s->h_kind[(size_t)k] : 0; }
+bool adjmat_root(const tqgpu_solver *s) { return s->mpc.d && !s->mpc.states && s->mpc.nx0 > 0; }
+/* what the tables depend on beyond the maps: every node's kind, the root form, nx0 */
+std::vector<int> adjmat_sig(const tqgpu_solver *s) {
+    std::vector<int> sig((size_t)s->Nn + 2);
+    for (int k = 0; k < s->Nn; k++) sig[(size_t)k] = adjmat_kind(s, k);
+    sig[(size_t)s->Nn] = adjmat_root(s) ? 1 : 0; sig[(size_t)s->Nn + 1] = s->mpc.nx0;
+    return sig;
+}
+/* member lists, group and chunk records, the list of groups to sum, the region and partial sizes, the LDS window: built from the maps and the kinds the
+ * device holds now, uploaded in one block.  Refuses a group that mixes kinds and a group whose window does not fit */
+int adjmat_build(tqgpu_solver *s, const char *who) {
+    MpcAdjMat &m = s->adjm;
+    int rc;
+    const int Nn = s->Nn;
+    m.sig.clear();
+    std::vector<std::vector<int>> hm((size_t)m.n_h), cm((size_t)m.n_c);
+    for (int k = 0; k < Nn; k++) {
+        if (m.hgroup[(size_t)k] >= 0) hm[(size_t)m.hgroup[(size_t)k]].push_back(k);
+        if (m.cgroup[(size_t)k] >= 0) cm[(size_t)m.cgroup[(size_t)k]].push_back(k);
+    }
+    for (int g = 0; g < m.n_h; g++) for (int k : hm[(size_t)g]) if (adjmat_kind(s, k) != adjmat_kind(s, hm[(size_t)g][0]))
+        return fail(TQGPU_EINVAL, std::string(who) + ": h-group " + std::to_string(g) + " has come to mix kinds: node " + std::to_string(k) + " is of kind " + std::to_string(adjmat_kind(s, k)) +
+                                  ", node " + std::to_string(hm[(size_t)g][0]) + " of kind " + std::to_string(adjmat_kind(s, hm[(size_t)g][0])));
+    const int root = adjmat_root(s) ? 1 : 0;
+    std::vector<int> hmem, cmem, hgrp((size_t)m.n_h * 8, 0), cgrp((size_t)m.n_c * 8, 0), hchk, cchk, sums;
+    size_t tot[ADJMAT_REGIONS] = {}, part = 0, lds = 0;
+    auto chunks = [](std::vector<int> &chk, int g, int first, int members) {
+        int q = 0;
+        for (int at = 0; at < members; at += ADJMAT_CHUNK, q++) { chk.push_back(g); chk.push_back(first + at); chk.push_back(std::min(ADJMAT_CHUNK, members - at)); chk.push_back(q); }
+        return q;
+    };
+    for (int g = 0; g < m.n_h; g++) {
+        const std::vector<int> &v = hm[(size_t)g];
+        const size_t nz = (size_t)(s->nx[(size_t)v[0]] + s->nu[(size_t)v[0]]), hsz = adjmat_kind(s, v[0]) ? nz * nz : nz;
+        int *rec = &hgrp[(size_t)g * 8];
+        rec[0] = v[0]; rec[1] = (int)tot[0]; rec[2] = (int)tot[1]; rec[4] = (int)(hchk.size() / 4);
+        rec[5] = chunks(hchk, g, (int)hmem.size(), (int)v.size()); rec[6] = (int)part;
+        hmem.insert(hmem.end(), v.begin(), v.end());
+        tot[0] += hsz; tot[1] += nz; part += (size_t)rec[5] * (hsz + nz);
+        lds = std::max(lds, (hsz + nz + 2 * nz + 2) * sizeof(double));
+        if (rec[5] > 1) sums.push_back(g);
+    }
+    for (int g = 0; g < m.n_c; g++) {
+        const std::vector<int> &v = cm[(size_t)g];
+        const int c = v[0], p = s->dad[(size_t)c];
+        const size_t nxc = (size_t)s->nx[(size_t)c], nxp = (size_t)s->nx[(size_t)p], nup = (size_t)s->nu[(size_t)p], gsz = nxc * (nxp + nup + 1);
+        int *rec = &cgrp[(size_t)g * 8];
+        rec[0] = c; rec[1] = (int)tot[2]; rec[2] = (int)tot[3]; rec[3] = (int)tot[4]; rec[4] = (int)(cchk.size() / 4);
+        rec[5] = chunks(cchk, g, (int)cmem.size(), (int)v.size()); rec[6] = (int)part;
+        cmem.insert(cmem.end(), v.begin(), v.end());
+        tot[2] += nxc * nxp; tot[3] += nxc * nup; tot[4] += nxc; part += (size_t)rec[5] * gsz;
+        lds = std::max(lds, (gsz + 2 * nxc + 2 * (nxp + nup) + 2) * sizeof(double));
+        if (rec[5] > 1) sums.push_back(m.n_h + g);
+    }
+    const size_t pR = part;
+    if (root) { tot[5] = (size_t)s->mpc.nb * s->mpc.nx0; tot[6] = (size_t)s->nu[0] * s->mpc.nx0; part += tot[5] + tot[6]; }
+    if (lds > 160 * 1024) return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": a group's window (its result blocks and a member's vectors) does not fit 160 KiB of LDS");
+    /* the region starts: every offset of a record is made absolute */
+    m.reg[0] = 0;
+    for (int i = 0; i < ADJMAT_REGIONS; i++) m.reg[i + 1] = m.reg[i] + tot[i];
+    if (m.reg[ADJMAT_REGIONS] > (size_t)INT_MAX / 2 || part > (size_t)INT_MAX / 2) return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the result does not fit the tables' 32-bit offsets");
+    for (int g = 0; g < m.n_h; g++) { hgrp[(size_t)g * 8 + 1] += (int)m.reg[0]; hgrp[(size_t)g * 8 + 2] += (int)m.reg[1]; }
+    for (int g = 0; g < m.n_c; g++) { cgrp[(size_t)g * 8 + 1] += (int)m.reg[2]; cgrp[(size_t)g * 8 + 2] += (int)m.reg[3]; cgrp[(size_t)g * 8 + 3] += (int)m.reg[4]; }
+    std::vector<int> tab;
+    auto put = [&](const std::vector<int> &v) { const size_t at = tab.size(); tab.insert(tab.end(), v.begin(), v.end()); return at; };
+    const size_t o_hmem = put(hmem), o_cmem = put(cmem), o_hgrp = put(hgrp), o_cgrp = put(cgrp), o_hchk = put(hchk), o_cchk = put(cchk), o_sums = put(sums);
+    tab.push_back(0);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->mem.release(m.d_tab);
+    if ((rc = s->mem.upload(m.d_tab, tab.data(), tab.size() * sizeof(int), TQGPU_ENOMEM, "the tables of the parameter groups"))) return rc;
+    AdjMat &M = m.v;
+    M = AdjMat{};
+    M.hmem = m.d_tab + o_hmem; M.cmem = m.d_tab + o_cmem; M.hgrp = m.d_tab + o_hgrp; M.cgrp = m.d_tab + o_cgrp;
+    M.hchk = m.d_tab + o_hchk; M.cchk = m.d_tab + o_cchk; M.sums = m.d_tab + o_sums;
+    M.n_hgrp = m.n_h; M.n_cgrp = m.n_c; M.n_hchk = (int)(hchk.size() / 4); M.n_cchk = (int)(cchk.size() / 4); M.n_sums = (int)sums.size();
+    M.root = root; M.oA0 = (int)m.reg[5]; M.oS0 = (int)m.reg[6]; M.pR = (int)pR;
+    m.n_units = M.n_hchk + M.n_cchk + root;
+    m.part1 = part; m.lds = lds;
+    m.sig = adjmat_sig(s);
+    return TQGPU_OK;
+}
+/* what the two calls refuse for a mirror before anything of its results is touched; brings the tables up to date with the kinds, the root form and nx0 */
+int adjmat_refuse(tqgpu_solver *s, const char *who) {
+    int rc;
+    if ((rc = mpc_refuse(s, who)) || (rc = adj_need(s, who))) return rc;
+    if (!s->adjm.set) return fail(TQGPU_EINVAL, std::string(who) + ": no parameter groups have been given (tqgpu_mpc_set_param_groups)");
+    if (s->adjm.sig != adjmat_sig(s) && (rc = adjmat_build(s, who))) return rc;
+    return TQGPU_OK;
+}
+/* the result block, its pinned twin and the partials for nw columns */
+int adjmat_room(tqgpu_solver *s, int nw) {
+    MpcAdjMat &m = s->adjm;
+    int rc;
+    const size_t need_res = std::max<size_t>(m.reg[ADJMAT_REGIONS] * (size_t)nw, 1), need_part = std::max<size_t>(m.part1 * (size_t)nw, 1);
+    if (!m.d_res || m.res_cap < need_res) {
+        s->mem.release(m.d_res); s->mem.release(m.h_res); m.res_cap = 0;
+        if ((rc = s->mem.device(m.d_res, need_res * sizeof(double), TQGPU_ENOMEM, "the matrix gradients")) || (rc = s->mem.host(m.h_res, need_res * sizeof(double), "the pinned matrix gradients"))) return rc;
+        m.res_cap = need_res;
+    }
+    if (!m.d_part || m.part_cap < need_part) {
+        s->mem.release(m.d_part); m.part_cap = 0;
+        if ((rc = s->mem.device(m.d_part, need_part * sizeof(double), TQGPU_ENOMEM, "the partial sums of the matrix gradients"))) return rc;
+        m.part_cap = need_part;
+    }
+    return TQGPU_OK;
+}
+/* the view the kernels take: the tables, the duals of the export block, where to write */
+AdjMat adjmat_view(const tqgpu_solver *s, double *res) {
+    AdjMat M = s->adjm.v;
+    const ExportSizes z = export_sizes(s);
+    M.lam = s->out.d + z.nxe + z.nue; M.res = res; M.part = s->adjm.d_part;
+    return M;
+}
+/* the seven regions of a result block of nw columns, each to its pointer at an offset (in doubles) of its own; add: accumulate instead of copying */
+void adjmat_scatter(const MpcAdjMat &m, const double *h, int nw, double *const out[ADJMAT_REGIONS], const size_t at[ADJMAT_REGIONS], bool add = false) {
+    for (int i = 0; i < ADJMAT_REGIONS; i++) {
+        const size_t n = (m.reg[i + 1] - m.reg[i]) * (size_t)nw;
+        if (!out[i] || !n) continue;
+        const double *src = h + m.reg[i] * (size_t)nw;
+        if (!add) memcpy(out[i] + at[i], src, sizeof(double) * n);
+        else for (size_t e = 0; e < n; e++) out[i][at[i] + e] = out[i][at[i] + e] + src[e];
+    }
+}
+/* one mirror on its own stream: one or two launches, one copy, one wait */
+int adjmat_one(tqgpu_solver *s, double *const out[ADJMAT_REGIONS], const size_t at[ADJMAT_REGIONS], bool add = false) {
+    MpcAdjMat &m = s->adjm;
+    int rc;
+    const int nw = s->sens.nw;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = adjmat_room(s, nw)) || (rc = allow_lds(k_adjmat_part, m.lds))) return rc;
+    const AdjMat M = adjmat_view(s, m.d_res);
+    hipStream_t st = s->stream;
+    if (m.n_units) { hipLaunchKernelGGL(k_adjmat_part, dim3((unsigned)m.n_units, (unsigned)nw), dim3(WAVE), m.lds, st, s->T, s->D, s->sens.v, s->sens.a, M); MPC_COUNT(launches, 1); }
+    if (M.n_sums) { hipLaunchKernelGGL(k_adjmat_sum, dim3((unsigned)M.n_sums, (unsigned)nw), dim3(WAVE), 0, st, s->T, s->D, s->sens.v, M, nw); MPC_COUNT(launches, 1); }
+    HIP_TRY(hipGetLastError());
+    const size_t n = m.reg[ADJMAT_REGIONS] * (size_t)nw;
+    if (n) HIP_TRY(hipMemcpyAsync(m.h_res, m.d_res, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    MPC_COUNT(copies, 1);
+    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
+    adjmat_scatter(m, m.h_res, nw, out, at, add);
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_set_param_groups(tqgpu_solver *s, const int *hgroup, const int *cgroup, int n_hgroups, int n_cgroups) {
+    const char *who = "tqgpu_mpc_set_param_groups";
+    int rc;
+    if ((rc = mpc_refuse(s, who))) return rc;
+    const int Nn = s->Nn;
+    std::vector<int> hg((size_t)Nn), cg((size_t)Nn);
+    const int n_h = hgroup ? n_hgroups : Nn, n_c = cgroup ? n_cgroups : Nn - 1;
+    if (n_h < 0 || n_c < 0) return fail(TQGPU_EINVAL, std::string(who) + ": a negative number of groups");
+    for (int k = 0; k < Nn; k++) {
+        hg[(size_t)k] = hgroup ? hgroup[k] : k;
+        cg[(size_t)k] = cgroup ? cgroup[k] : k - 1;
+        if (hg[(size_t)k] < -1 || hg[(size_t)k] >= n_h) return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": hgroup = " + std::to_string(hg[(size_t)k]) + " is outside [-1, " + std::to_string(n_h) + ")");
+        if (cg[(size_t)k] < -1 || cg[(size_t)k] >= n_c) return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": cgroup = " + std::to_string(cg[(size_t)k]) + " is outside [-1, " + std::to_string(n_c) + ")");
+    }
+    if (cg[0] != -1) return fail(TQGPU_EINVAL, std::string(who) + ": node 0: the root has no dynamics, cgroup[0] must be -1");
+    std::vector<int> hfirst((size_t)n_h, -1), cfirst((size_t)n_c, -1), hdims((size_t)n_h * 4, 0), cdims((size_t)n_c * 4, 0);
+    for (int k = 0; k < Nn; k++) {
+        const int g = hg[(size_t)k], pad = k == 0 ? s->x_pad : 0;
+        if (g >= 0) {
+            int *d = &hdims[(size_t)g * 4];
+            if (hfirst[(size_t)g] < 0) { hfirst[(size_t)g] = k; d[0] = s->nx[(size_t)k]; d[1] = s->nu[(size_t)k]; d[2] = pad; }
+            else if (d[0] != s->nx[(size_t)k] || d[1] != s->nu[(size_t)k] || d[2] != pad)
+                return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": nx, nu or the phantom root states differ from those of node " + std::to_string(hfirst[(size_t)g]) + ", the first member of h-group " + std::to_string(g));
+            d[3]++;
+        }
+        const int gc = cg[(size_t)k];
+        if (gc >= 0) {
+            const int p = s->dad[(size_t)k];
+            int *d = &cdims[(size_t)gc * 4];
+            if (cfirst[(size_t)gc] < 0) { cfirst[(size_t)gc] = k; d[0] = s->nx[(size_t)k]; d[1] = s->nx[(size_t)p]; d[2] = s->nu[(size_t)p]; }
+            else if (d[0] != s->nx[(size_t)k] || d[1] != s->nx[(size_t)p] || d[2] != s->nu[(size_t)p])
+                return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": nx of the node, or nx, nu of its parent differ from those of node " + std::to_string(cfirst[(size_t)gc]) + ", the first member of c-group " + std::to_string(gc));
+            d[3]++;
+        }
+    }
+    for (int g = 0; g < n_h; g++) if (hfirst[(size_t)g] < 0) return fail(TQGPU_EINVAL, std::string(who) + ": h-group " + std::to_string(g) + " has no member");
+    for (int g = 0; g < n_c; g++) if (cfirst[(size_t)g] < 0) return fail(TQGPU_EINVAL, std::string(who) + ": c-group " + std::to_string(g) + " has no member");
+    MpcAdjMat &m = s->adjm;
+    m.hgroup = hg; m.cgroup = cg; m.hdims = hdims; m.cdims = cdims; m.n_h = n_h; m.n_c = n_c;
+    m.set = false;
+    if ((rc = adjmat_build(s, who))) return rc;
+    m.set = true;
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_param_groups(tqgpu_solver *s, int *n_hgroups, int *n_cgroups, int *hdims, int *cdims, int *root) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_param_groups"))) return rc;
+    const MpcAdjMat &m = s->adjm;
+    if (!m.set) return fail(TQGPU_EINVAL, "tqgpu_mpc_get_param_groups: no parameter groups have been given (tqgpu_mpc_set_param_groups)");
+    if (n_hgroups) *n_hgroups = m.n_h;
+    if (n_cgroups) *n_cgroups = m.n_c;
+    if (hdims) for (int g = 0; g < m.n_h; g++) {
+        memcpy(hdims + 5 * (size_t)g, &m.hdims[4 * (size_t)g], sizeof(int) * 4);
+        const int first = (int)(std::find(m.hgroup.begin(), m.hgroup.end(), g) - m.hgroup.begin());
+        hdims[5 * (size_t)g + 4] = adjmat_kind(s, first);
+    }
+    if (cdims && !m.cdims.empty()) memcpy(cdims, m.cdims.data(), sizeof(int) * m.cdims.size());
+    if (root) { root[0] = adjmat_root(s) ? s->mpc.nb : 0; root[1] = s->nu[0]; root[2] = s->mpc.nx0; root[3] = s->sens.adj_valid ? s->sens.nw : 0; }
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_adjoint_matrices(tqgpu_solver *s, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0) {
+    int rc;
+    if ((rc = adjmat_refuse(s, "tqgpu_mpc_adjoint_matrices"))) return rc;
+    MpcLive live;
+    double *const out[ADJMAT_REGIONS] = {gH, gh, gA, gB, gb, gA0, gS0};
+    const size_t at[ADJMAT_REGIONS] = {};
+    return adjmat_one(s, out, at);
+}
+
+extern "C" int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, int reduce, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0) {
+    const char *who = "tqgpu_mpc_adjoint_matrices_batch";
+    if (!solvers || n < 1) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers is required, n must be at least 1)");
+    if (reduce != 0 && reduce != 1) return fail(TQGPU_EINVAL, std::string(who) + ": reduce must be 0 or 1");
+    int rc;
+    /* the refusals, all of them before any member's results are touched */
+    std::set<const tqgpu_solver *> seen;
+    for (int i = 0; i < n; i++) {
+        if ((rc = adjmat_refuse(solvers[i], who))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
+        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
+        const MpcAdjMat &a = solvers[0]->adjm, &b = solvers[i]->adjm;
+        if (reduce && (a.hdims != b.hdims || a.cdims != b.cdims || !std::equal(a.reg, a.reg + ADJMAT_REGIONS + 1, b.reg) || a.part1 != b.part1 || a.v.n_hchk != b.v.n_hchk || a.v.n_cchk != b.v.n_cchk ||
+                       a.v.root != b.v.root || solvers[0]->sens.nw != solvers[i]->sens.nw))
+            return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": its group tables (shapes, kinds, root terms) or its columns differ from member 0's; reduce = 1 sums equal shapes");
+    }
+    const char *sw = getenv("TREEQP_AMD_ADJ_BATCH");
+    const bool by_member = sw && strcmp(sw, "members") == 0;
+    double *const out[ADJMAT_REGIONS] = {gH, gh, gA, gB, gb, gA0, gS0};
+    std::vector<std::array<size_t, ADJMAT_REGIONS>> span((size_t)n);
+    {
+        std::array<size_t, ADJMAT_REGIONS> at{};
+        for (int i = 0; i < n; i++) {
+            span[(size_t)i] = at;
+            const MpcAdjMat &m = solvers[i]->adjm;
+            if (!reduce) for (int r = 0; r < ADJMAT_REGIONS; r++) at[(size_t)r] += (m.reg[r + 1] - m.reg[r]) * (size_t)solvers[i]->sens.nw;
+        }
+    }
+    std::vector<AdjGroup> groups;
+    for (int i = 0; i < n; i++) {
+        auto g = std::find_if(groups.begin(), groups.end(), [&](const AdjGroup &q) { return q.device == solvers[i]->device; });
+        if (g == groups.end()) { groups.push_back(AdjGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
+        g->idx.push_back(i);
+    }
+    MpcLive live;
+    bool all_batched = !by_member;
+    for (AdjGroup &g : groups) { g.batched = !by_member && adj_group_batched(solvers, g); all_batched = all_batched && g.batched; }
+    if (reduce && (!all_batched || groups.size() != 1)) {
+        /* the sum over members on the host, in member order: the first member's blocks, then entry by entry the others' */
+        for (int i = 0; i < n; i++) if ((rc = adjmat_one(solvers[i], out, span[0].data(), i > 0))) return rc;
+        return TQGPU_OK;
+    }
+    struct Sent { size_t total; std::vector<size_t> at; };
+    std::vector<Sent> sent(groups.size());
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        AdjGroup &g = groups[gi];
+        if (!g.batched) {
+            for (int i : g.idx) if ((rc = adjmat_one(solvers[i], out, span[(size_t)i].data()))) return rc;
+            continue;
+        }
+        tqgpu_solver *lead = solvers[g.idx[0]];
+        MpcAdjMat &B = lead->adjm;
+        const size_t nm = g.idx.size();
+        HIP_TRY(hipSetDevice(lead->device));
+        size_t total = 0, lds = 0;
+        int units = 0, nsums = 0, cols = 0;
+        sent[gi].at.assign(nm, 0);
+        for (size_t k = 0; k < nm; k++) {
+            tqgpu_solver *s = solvers[g.idx[k]];
+            SETTLE(s);
+            if (s->stream != lead->stream && s->stream_pending) { HIP_TRY(hipStreamSynchronize(s->stream)); s->stream_pending = false; MPC_COUNT(waits, 1); }
+            if ((rc = adjmat_room(s, s->sens.nw))) return rc;
+            sent[gi].at[k] = total;
+            if (!reduce || k == 0) total += s->adjm.reg[ADJMAT_REGIONS] * (size_t)s->sens.nw;
+            units = std::max(units, s->adjm.n_units); nsums = std::max(nsums, s->adjm.v.n_sums); cols = std::max(cols, s->sens.nw); lds = std::max(lds, s->adjm.lds);
+        }
+        sent[gi].total = total;
+        if ((rc = adj_grow(lead, B.d_desc, B.h_desc, B.desc_cap, nm * sizeof(AMItem), "the descriptors of the batched matrix gradients")) ||
+            (rc = adj_grow(lead, B.d_bres, B.h_bres, B.bres_cap, total, "the matrix gradients of a batch")) ||
+            (rc = allow_lds(k_adjmat_part_batch, lds)))
+            return rc;
+        AMItem *items = reinterpret_cast<AMItem *>(B.h_desc);
+        for (size_t k = 0; k < nm; k++) {
+            tqgpu_solver *s = solvers[g.idx[k]];
+            AMItem &it = items[k];
+            it = AMItem{};
+            it.T = s->T; it.D = s->D; it.S = s->sens.v; it.A = s->sens.a;
+            it.M = adjmat_view(s, B.d_bres + (reduce ? 0 : sent[gi].at[k]));
+        }
+        hipStream_t ls = lead->stream;
+        const AMItem *d_items = reinterpret_cast<const AMItem *>(B.d_desc);
+        HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, nm * sizeof(AMItem), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
+        if (units) { hipLaunchKernelGGL(k_adjmat_part_batch, dim3((unsigned)units, (unsigned)cols, (unsigned)nm), dim3(WAVE), lds, ls, d_items, reduce); MPC_COUNT(launches, 1); }
+        if (reduce) {
+            const int gu = lead->adjm.n_h + lead->adjm.n_c + lead->adjm.v.root;
+            if (gu) { hipLaunchKernelGGL(k_adjmat_reduce, dim3((unsigned)gu, (unsigned)cols), dim3(WAVE), 0, ls, d_items, (int)nm); MPC_COUNT(launches, 1); }
+        } else if (nsums) { hipLaunchKernelGGL(k_adjmat_sum_batch, dim3((unsigned)nsums, (unsigned)cols, (unsigned)nm), dim3(WAVE), 0, ls, d_items); MPC_COUNT(launches, 1); }
+        HIP_TRY(hipGetLastError());
+        if (total) HIP_TRY(hipMemcpyAsync(B.h_bres, B.d_bres, sizeof(double) * total, hipMemcpyDeviceToHost, ls));
+        MPC_COUNT(copies, 1);
+        lead->stream_pending = true;
+    }
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        AdjGroup &g = groups[gi];
+        if (!g.batched) continue;
+        tqgpu_solver *lead = solvers[g.idx[0]];
+        HIP_TRY(hipSetDevice(lead->device));
+        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
+        lead->stream_pending = false;
+        for (size_t k = 0; k < g.idx.size(); k++) {
+            if (reduce && k > 0) break;
+            const tqgpu_solver *s = solvers[g.idx[k]];
+            adjmat_scatter(s->adjm, lead->adjm.h_bres + sent[gi].at[k], s->sens.nw, out, span[(size_t)g.idx[k]].data());
+        }
+    }
+    return TQGPU_OK;
+}
+
 extern "C" int tqgpu_mpc_get_gain(tqgpu_solver *s, double *K, double *u0, double *x0_ref) {
     int rc;
     if ((rc = mpc_refuse(s, "tqgpu_mpc_get_gain")) || (rc = sens_need(s, "tqgpu_mpc_get_gain"))) return rc;

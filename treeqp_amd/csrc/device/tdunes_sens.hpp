@@ -686,3 +686,233 @@ __global__ void __launch_bounds__(WAVE) k_adj_grad_batch(const AItem *__restrict
     adj_grad_body(it.T, it.D, it.S, it.A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
 #endif
+
+/* ---- the adjoint in H, A, B (tqgpu_mpc_adjoint_matrices): outer products of a stored adjoint with the point, summed over parameter groups ----
+ *   z_k = [x_k; u_k] the exported point, gz_k = [gq_k; gr_k] and gb_c = Y_c of struct Adj, lam_c the exported dual (its sign is the one
+ *   for which stationarity off the bounds reads H z + g + E' lam = 0 with (E v)_c = C_c v_p - v_c^x); phantom root states carry 0 in z and gz.
+ *   kind-0 node k:   gHd_k[i] = gz_k[i] z_k[i]                      kind-1 node k:   gH_k = 1/2 (gz_k z_k' + z_k gz_k'), i >= j computed, mirrored
+ *   child c of p:    gA_c = lam_c gq_p' + gb_c x_p',  gB_c = lam_c gr_p' + gb_c u_p'      linear terms: gh_k = gz_k, gb_c
+ *   eliminated root: gA0_c = gb_c x0', gS0 = gr_0 x0' (0.0 where S0 was not given)
+ * A group's members are taken in ascending node index in chunks of ADJMAT_CHUNK; a chunk's partial is one chain from 0.0 over its members,
+ * per member  acc = fma(lam_c[i], gz_p[j], acc); acc = fma(gb_c[i], z_p[j], acc)  (gA, gB),  acc = fma(gz_k[i], z_k[i], acc)  (gHd),
+ * acc = fma(gz_k[i], z_k[j], acc); acc = fma(z_k[i], gz_k[j], acc), halved at the end  (gH),  acc = acc + v[i]  (gh, gb); the group's value is
+ * the first partial plus the others in ascending chunk order (k_adjmat_sum), in the reducing batch form in ascending (member, chunk) order.
+ * No atomics.  One wave per (chunk, column) on a private LDS window [accumulators | the member's vectors]; Data, Sens, Adj are only read. */
+#define ADJMAT_CHUNK 64
+#define ADJMAT_PF 2                    /* doubles per lane of the next member's vectors kept in flight ahead of the current member's fmas */
+struct AdjMat {
+    const int *hmem, *cmem;            /* the members (nodes) of the h-groups / c-groups, group after group, ascending within a group */
+    const int *hgrp, *cgrp;            /* 8 ints per group: [0] its first member, [1..3] where its result blocks begin (h: gH, gh, -; c: gA, gB, gb), [4] its
+                                        * first chunk, [5] its chunks, [6] where its partials begin; offsets in doubles per column of w */
+    const int *hchk, *cchk;            /* 4 ints per chunk: group, first member (index into hmem / cmem), members, index of the chunk within its group */
+    const int *sums;                   /* the groups of more than one chunk, as units: h-group g = g, c-group g = n_hgrp + g */
+    const double *lam;                 /* the duals of the export block (sum_lam) */
+    double *res, *part;                /* [gH | gh | gA | gB | gb | gA0 | gS0], every region groups ascending, then columns; the partials */
+    int n_hgrp, n_cgrp, n_hchk, n_cchk, n_sums;
+    int root;                          /* 1: an eliminated root, the last unit is gA0, gS0 */
+    int oA0, oS0, pR;                  /* where gA0, gS0 and the root unit's partial begin, in doubles per column */
+};
+/* what a unit (h-group, c-group, the root terms) writes: up to three result blocks of s1, s2, s3 doubles per column at o1, o2, o3, one partial of gsz */
+struct AdjMatUnit { int s1, s2, s3, o1, o2, o3, gsz, po, nchk, kind, nz, nxc, nzp; };
+__device__ __forceinline__ AdjMatUnit adjmat_unit(const Tree &T, const Data &D, const Sens &S, const AdjMat &M, int unit) {
+    AdjMatUnit U{};
+    if (unit < M.n_hgrp) {
+        const int *rec = M.hgrp + 8 * unit;
+        const int k = rec[0];
+        U.nz = T.nx[k] + T.nu[k]; U.kind = sens_kind(D, k);
+        U.s1 = U.kind ? U.nz * U.nz : U.nz; U.s2 = U.nz; U.s3 = 0;
+        U.o1 = rec[1]; U.o2 = rec[2]; U.o3 = 0; U.nchk = rec[5]; U.po = rec[6];
+    } else if (unit < M.n_hgrp + M.n_cgrp) {
+        const int *rec = M.cgrp + 8 * (unit - M.n_hgrp);
+        const int c = rec[0], p = T.dad[c];
+        U.nxc = T.nx[c]; U.nzp = T.nx[p] + T.nu[p];
+        U.s1 = U.nxc * T.nx[p]; U.s2 = U.nxc * T.nu[p]; U.s3 = U.nxc;
+        U.o1 = rec[1]; U.o2 = rec[2]; U.o3 = rec[3]; U.nchk = rec[5]; U.po = rec[6];
+    } else {
+        U.s1 = T.bdim[0] * S.nx0; U.s2 = T.nu[0] * S.nx0; U.s3 = 0;
+        U.o1 = M.oA0; U.o2 = M.oS0; U.o3 = 0; U.nchk = 1; U.po = M.pR;
+    }
+    U.gsz = U.s1 + U.s2 + U.s3;
+    return U;
+}
+/* entry e of a unit's partial, column col: where it lies in res */
+__device__ __forceinline__ size_t adjmat_res_at(const AdjMatUnit &U, int e, int col, int nw) {
+    if (e < U.s1) return (size_t)U.o1 * nw + (size_t)col * U.s1 + e;
+    e -= U.s1;
+    if (e < U.s2) return (size_t)U.o2 * nw + (size_t)col * U.s2 + e;
+    return (size_t)U.o3 * nw + (size_t)col * U.s3 + (e - U.s2);
+}
+__device__ __forceinline__ size_t adjmat_part_at(const AdjMatUnit &U, int q, int e, int col, int nw) {
+    return ((size_t)U.po + (size_t)q * U.gsz) * nw + (size_t)col * U.gsz + e;
+}
+/* entry idx of [z_k (nz) | gz_k (nz)] of node k */
+__device__ __forceinline__ double adjmat_hvec(const Tree &T, const Sens &S, const Adj &A, int k, int nx, int nz, int idx, int col) {
+    const bool g = idx >= nz;
+    const int i = g ? idx - nz : idx;
+    if (i < nx) {
+        const int e = T.xoff[k] + i;
+        if (e < S.xpad) return 0.0;
+        return g ? A.gq[e + (size_t)col * S.sum_nx] : S.x[e - S.xpad];
+    }
+    const int e = T.uoff[k] + i - nx;
+    return g ? A.gr[e + (size_t)col * S.sum_nu] : S.u[e];
+}
+/* entry idx of [lam_c (nxc) | gb_c (nxc) | z_p (nzp) | gz_p (nzp)] of child c with parent p */
+__device__ __forceinline__ double adjmat_cvec(const Tree &T, const Sens &S, const Adj &A, const AdjMat &M, int c, int p, int nxc, int nxp, int nzp, int idx, int col) {
+    if (idx < nxc) return M.lam[T.xoff[c] - T.nx0 + idx];
+    if (idx < 2 * nxc) return A.gb[T.xoff[c] + idx - nxc + (size_t)col * S.sum_nx];
+    return adjmat_hvec(T, S, A, p, nxp, nzp, idx - 2 * nxc, col);
+}
+
+/* ---- k_adjmat_part: one wave per (chunk of a group, column); the unit behind the chunks is the root terms of an eliminated root.  all_partial: every
+ * chunk writes its partial (the reducing batch form); otherwise the only chunk of a group writes the group's result itself ---- */
+__device__ void adjmat_part_body(const Tree &T, const Data &D, const Sens &S, const Adj &A, const AdjMat &M, int unit, int col, int all_partial, int lane, double *lds) {
+    const int nw = A.nw;
+    if (unit >= M.n_hchk + M.n_cchk) {
+        const AdjMatUnit U = adjmat_unit(T, D, S, M, M.n_hgrp + M.n_cgrp);
+        const int nx0 = S.nx0, nu0 = T.nu[0], k0 = T.kid0[0];
+        for (int e = lane; e < U.gsz; e += WAVE) {
+            double v;
+            if (e < U.s1) {
+                /* A0 lies child after child, each nx[kid] x nx0: find the entry's child */
+                int ao = 0, kid = k0;
+                for (; kid < k0 + T.nk[0]; kid++) { const int n = T.nx[kid] * nx0; if (e < ao + n) break; ao += n; }
+                const int nxc = T.nx[kid], i = (e - ao) % nxc, j = (e - ao) / nxc;
+                v = A.gb[T.xoff[kid] + i + (size_t)col * S.sum_nx] * S.x0[j];
+            } else {
+                const int i = (e - U.s1) % nu0, j = (e - U.s1) / nu0;
+                v = S.S0 ? A.gr[T.uoff[0] + i + (size_t)col * S.sum_nu] * S.x0[j] : 0.0;
+            }
+            if (all_partial) M.part[adjmat_part_at(U, 0, e, col, nw)] = v; else M.res[adjmat_res_at(U, e, col, nw)] = v;
+        }
+        return;
+    }
+    const bool isc = unit >= M.n_hchk;
+    const int *ck = isc ? M.cchk + 4 * (unit - M.n_hchk) : M.hchk + 4 * unit;
+    const AdjMatUnit U = adjmat_unit(T, D, S, M, isc ? M.n_hgrp + ck[0] : ck[0]);
+    const int *mem = (isc ? M.cmem : M.hmem) + ck[1];
+    const int cnt = ck[2], q = ck[3];
+    const int rep = mem[0], nxc = U.nxc, nzp = isc ? U.nzp : U.nz, nxp = isc ? T.nx[T.dad[rep]] : T.nx[rep];
+    const int L = isc ? 2 * nxc + 2 * nzp : 2 * nzp, gsz = U.gsz, hsz = U.s1;
+    double *acc = lds;                    /* gsz */
+    double *vec = lds + gsz;              /* L: the vectors of the member in hand */
+    for (int e = lane; e < gsz; e += WAVE) acc[e] = 0.0;
+    auto fetch = [&](int node, int idx) { return isc ? adjmat_cvec(T, S, A, M, node, T.dad[node], nxc, nxp, nzp, idx, col) : adjmat_hvec(T, S, A, node, nxp, nzp, idx, col); };
+    int n1 = rep, n2 = cnt > 1 ? mem[1] : rep;
+    double pre[ADJMAT_PF];
+#pragma unroll
+    for (int r = 0; r < ADJMAT_PF; r++) { const int idx = lane + r * WAVE; pre[r] = idx < L ? fetch(n1, idx) : 0.0; }
+    for (int m = 0; m < cnt; m++) {
+        const int cur = n1;
+        n1 = n2;
+        if (m + 2 < cnt) n2 = mem[m + 2];
+#pragma unroll
+        for (int r = 0; r < ADJMAT_PF; r++) { const int idx = lane + r * WAVE; if (idx < L) vec[idx] = pre[r]; }
+        for (int idx = lane + ADJMAT_PF * WAVE; idx < L; idx += WAVE) vec[idx] = fetch(cur, idx);
+        WSYNC();
+        if (m + 1 < cnt) {          /* the next member's loads go out ahead of this member's fmas */
+#pragma unroll
+            for (int r = 0; r < ADJMAT_PF; r++) { const int idx = lane + r * WAVE; pre[r] = idx < L ? fetch(n1, idx) : 0.0; }
+        }
+        if (isc) {
+            const double *lam = vec, *gb = vec + nxc, *zp = vec + 2 * nxc, *gzp = zp + nzp;
+            for (int e = lane; e < gsz; e += WAVE) {
+                const int i = e % nxc, j = e / nxc;
+                double a = acc[e];
+                if (j < nzp) { a = fma(lam[i], gzp[j], a); a = fma(gb[i], zp[j], a); }
+                else a = a + gb[i];
+                acc[e] = a;
+            }
+        } else {
+            const double *z = vec, *gz = vec + nzp;
+            for (int e = lane; e < gsz; e += WAVE) {
+                double a = acc[e];
+                if (e >= hsz) a = a + gz[e - hsz];
+                else if (U.kind) {
+                    const int i = e % nzp, j = e / nzp;
+                    if (i < j) continue;
+                    a = fma(gz[i], z[j], a); a = fma(z[i], gz[j], a);
+                } else a = fma(gz[e], z[e], a);
+                acc[e] = a;
+            }
+        }
+        WSYNC();
+    }
+    const bool direct = !all_partial && U.nchk == 1;
+    for (int e = lane; e < gsz; e += WAVE) {
+        double v = acc[e];
+        if (!isc && U.kind && e < hsz) { const int i = e % nzp, j = e / nzp; v = 0.5 * acc[i >= j ? e : j + i * nzp]; }
+        if (direct) M.res[adjmat_res_at(U, e, col, nw)] = v; else M.part[adjmat_part_at(U, q, e, col, nw)] = v;
+    }
+}
+/* ---- k_adjmat_sum: one wave per (group of more than one chunk, column): the first partial plus the others, ascending ---- */
+__device__ void adjmat_sum_body(const Tree &T, const Data &D, const Sens &S, const AdjMat &M, int nw, int unit, int col, int lane) {
+    const AdjMatUnit U = adjmat_unit(T, D, S, M, unit);
+    for (int e = lane; e < U.gsz; e += WAVE) {
+        double v = M.part[adjmat_part_at(U, 0, e, col, nw)];
+        for (int q = 1; q < U.nchk; q++) v = v + M.part[adjmat_part_at(U, q, e, col, nw)];
+        M.res[adjmat_res_at(U, e, col, nw)] = v;
+    }
+}
+__global__ void __launch_bounds__(WAVE) k_adjmat_part(Tree T, Data D, Sens S, Adj A, AdjMat M)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    adjmat_part_body(T, D, S, A, M, blockIdx.x, blockIdx.y, 0, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adjmat_sum(Tree T, Data D, Sens S, AdjMat M, int nw)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{ adjmat_sum_body(T, D, S, M, nw, M.sums[blockIdx.x], blockIdx.y, threadIdx.x); }
+#endif
+
+/* the batch forms (tqgpu_mpc_adjoint_matrices_batch): the same bodies behind a look-up of the member, blockIdx.z = member.  In the reducing form every
+ * member's res is the one block of the call, every chunk writes its partial into its own member's buffer and k_adjmat_reduce, one wave per (unit, column),
+ * adds them in ascending (member, chunk) order; the members' tables have equal shapes then */
+struct AMItem { Tree T; Data D; Sens S; Adj A; AdjMat M; };
+__global__ void __launch_bounds__(WAVE) k_adjmat_part_batch(const AMItem *__restrict__ items, int all_partial)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AMItem &it = items[blockIdx.z];
+    if ((int)blockIdx.x >= it.M.n_hchk + it.M.n_cchk + it.M.root || (int)blockIdx.y >= it.A.nw) return;
+    adjmat_part_body(it.T, it.D, it.S, it.A, it.M, blockIdx.x, blockIdx.y, all_partial, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adjmat_sum_batch(const AMItem *__restrict__ items)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    const AMItem &it = items[blockIdx.z];
+    if ((int)blockIdx.x >= it.M.n_sums || (int)blockIdx.y >= it.A.nw) return;
+    adjmat_sum_body(it.T, it.D, it.S, it.M, it.A.nw, it.M.sums[blockIdx.x], blockIdx.y, threadIdx.x);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_adjmat_reduce(const AMItem *__restrict__ items, int n)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    const int unit = blockIdx.x, col = blockIdx.y, lane = threadIdx.x, nw = items[0].A.nw;
+    const AdjMatUnit U0 = adjmat_unit(items[0].T, items[0].D, items[0].S, items[0].M, unit);
+    for (int e = lane; e < U0.gsz; e += WAVE) {
+        double v = 0.0;
+        for (int m = 0; m < n; m++) {
+            const AMItem &it = items[m];
+            const AdjMatUnit U = adjmat_unit(it.T, it.D, it.S, it.M, unit);
+            for (int q = 0; q < U.nchk; q++) {
+                const double p = it.M.part[adjmat_part_at(U, q, e, col, nw)];
+                v = (m == 0 && q == 0) ? p : v + p;
+            }
+        }
+        items[0].M.res[adjmat_res_at(U0, e, col, nw)] = v;
+    }
+}
+#endif
