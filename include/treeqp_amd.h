@@ -675,7 +675,7 @@ int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb);
  *   state                afterwards every member is as a successful tqgpu_mpc_adjoint leaves it (tqgpu_mpc_get_adjoint_x0 and
  *                        tqgpu_mpc_get_adjoint read its own buffers; the factor counts as stored); the flags are set after the wait has
  *                        succeeded.  A stored sensitivity and everything a solve reads are left alone.
- *   member by member     groups of fewer than ADJ_BATCH_MIN members (tdunes_mpc.hpp), of more than 65 535, or in which one tree dwarfs
+ *   member by member     groups of fewer than ADJ_BATCH_MIN members (tdunes_adjoint.hpp), of more than 65 535, or in which one tree dwarfs
  *                        the others (the rule of tqgpu_kkt_residual_batch), and every group under TREEQP_AMD_ADJ_BATCH=members, go through
  *                        tqgpu_mpc_adjoint one member after the other: same results and state, the counts are the sum of the single calls.
  *   refusals             before any member is touched, with the member's index in the message: whatever tqgpu_mpc_adjoint refuses for a

@@ -1,5 +1,5 @@
 """The shapes on both sides of every size limit of the MPC and sensitivity kernels (tdunes_mpc.hpp: mpc_pre_block, mpc_track_node,
-k_mpc_post, k_mpc_post_batch, setup_sens; tdunes_sens.hpp), shared by the CPU checks (test_mpc_limits_reference.py) and the device
+k_mpc_post, k_mpc_post_batch; tdunes_adjoint.hpp: setup_sens; tdunes_sens.hpp), shared by the CPU checks (test_mpc_limits_reference.py) and the device
 tests (test_gpu_mpc_limits.py).  The limits are the 64 lanes of a wave (the `i = lane; i < n; i += WAVE` loops), the 256 threads and the
 16 lanes / 16 members of the post kernels, the `i < 16` gates on the packed constants, and the 160 KiB of LDS setup_sens checks.
 

@@ -170,6 +170,41 @@ def test_counts_do_not_grow_with_n(capi, n):
         _close(gs)
 
 
+# (launches, copies, waits, batched members) of the KKT batch and the waits of the adjoint batch, in both iterations: the figures of the commit
+# before the stream rule became one function (order_behind_lead), measured with that commit's library on the sequence of the test below
+WAITS_BEHIND_STEP_AND_KKT = {
+    "same4": ((3, 2, 1, 2), 1),          # one batch launch on the lead's stream: both calls wait for their results alone
+    "pair": ((3, 2, 2, 2), 1),
+}
+
+
+@pytest.mark.parametrize("bid", sorted(WAITS_BEHIND_STEP_AND_KKT))
+def test_waits_behind_a_batch_step_and_a_kkt_batch(capi, bid):
+    """Two members of one device (two C1 trees; the smallest pair of adj_batch_cases, whose members solve on streams of their own):
+    tqgpu_mpc_step_batch, then tqgpu_kkt_residual_batch, then tqgpu_mpc_adjoint_batch.  Both batched calls order their members behind the
+    lead's stream by one rule whose switches differ: only the adjoint takes a batch step to have drained every stream."""
+    nw = 1
+    gs = _make(capi, bid, 2)
+    try:
+        wxs, wus = [v[:2] for v in AB.ws(bid, nw)]
+        nh = max(_nh(bid, 2))
+        seen = []
+        for it in range(2):
+            _step(capi, gs, bid)
+            capi.kkt_residual_batch(gs)
+            kkt = capi.kkt_batch_stats()
+            outs = capi.mpc_adjoint_batch(gs, wxs, wus)
+            seen.append(((kkt["launches"], kkt["copies"], kkt["waits"], kkt["batched_members"]), _counts(capi)))
+            print(f"{bid}, iteration {it}: kkt batch (launches, copies, waits, batched members) {seen[-1][0]}, adjoint batch (launches, copies, waits) {seen[-1][1]}")
+        kkt_ref, adj_waits = WAITS_BEHIND_STEP_AND_KKT[bid]
+        for it, (kkt, adj) in enumerate(seen):
+            assert kkt == kkt_ref, (bid, it)
+            assert adj == (1 + (1 + nh) + (2 * nh + 1), 3, adj_waits), (bid, it)          # the KKT batch packs the points, Export::valid stays: packed again
+        _check_members(capi, bid, nw, gs, outs, "behind a batch step and a KKT batch")
+    finally:
+        _close(gs)
+
+
 def test_member_by_member_on_request(capi):
     bid, nw = "same4", 1
     gs = _make(capi, bid)

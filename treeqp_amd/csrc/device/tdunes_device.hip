@@ -31,7 +31,8 @@
  * headers included below: tdunes_fast.hpp / tdunes_persist.hpp (uniform and multistage trees: the whole solve as ONE launch, also
  * dealt over several devices: tqgpu_pshard_*), tdunes_wide.hpp / tdunes_wide3.hpp (dual blocks of 16 < d <= 64 rows: MFMA kernels,
  * three launches per Newton iteration), tdunes_gpersist.hpp (small trees of any shape: one workgroup per tree).  The MPC family (tqgpu_mpc_*),
- * kernels and entry points, is tdunes_mpc.hpp, included into the host part; this file keeps the mirror's records for it and MpcStats, MpcPre.
+ * kernels and entry points, is tdunes_mpc.hpp, and the host side of a step's sensitivities and adjoints tdunes_adjoint.hpp, both included into
+ * the host part; this file keeps the mirror's records for them, MpcStats, MpcPre, and the plan the batched after-solve calls share (DeviceGroup ..).
  */
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -1865,6 +1866,7 @@ struct MpcBatchBuf {
 /* tracking (tqgpu_mpc_set_tracking): d, [xtraj T x NXT | utraj T x NUT | q0 (sum_nx, node-indexed as Data::q, phantom root states included) |
  * r0 (sum_nu)] in one device block, the nodes' stages behind it as ints; t0: the window the device's q, r were last folded for (-1: none yet) */
 struct MpcTrack { double *d = nullptr; int T = 0, nxt = 0, nut = 0, t0 = -1; };
+/* ---- what a mirror keeps for the derivatives of an MPC step (tdunes_adjoint.hpp; kernels in tdunes_sens.hpp): MpcSens, MpcAdjBatch, MpcAdjMat ---- */
 /* tqgpu_mpc_sensitivity: buffers of its own (setup_sens, on first use; one device block d, views in v); pinned h:
  * [head: K (nu0 x nx0) | u0 (nu0) | x0_ref (nx0) | n_reg] [x0_new (nx0)] [u0_pred (nu0) | n_clipped]; valid: the stored sensitivity
  * belongs to the point and the data the device holds now (cleared by every upload, fold, window move and solve) */
@@ -2077,7 +2079,7 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcAdjMat adjm;      /* the MPC family (tdunes_mpc.hpp), one record per feature */
+    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcAdjMat adjm;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, adjm: tdunes_adjoint.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -4354,17 +4356,85 @@ static int batch_kernel_index(const tqgpu_solver *s) {
 #undef X
     return -1;
 }
-/* the descriptors of a batch launch (device array and its pinned host copy, owned by the batch's first mirror): room for `need` */
-template <typename Item>
-static int grow_items(tqgpu_solver *s, Item *&d, Item *&h, int &cap, size_t need) {
-    if (cap >= (int)need) return TQGPU_OK;
+/* a block of a batch launch (device array and its pinned host copy, owned by the batch's first mirror): room for `need` units, twice the
+ * need where it has to grow (the lead's stream holds nothing that reads it: every batched call ends with its wait) */
+template <typename Item, typename Cap>
+static int grow_items(tqgpu_solver *s, Item *&d, Item *&h, Cap &cap, size_t need, const char *what = "the batch descriptors") {
+    if ((size_t)cap >= need && d) return TQGPU_OK;
     s->mem.release(d); s->mem.release(h);
     cap = 0;
     int rc;
-    if ((rc = s->mem.device(d, 2 * need * sizeof(Item), TQGPU_ENOMEM, "the batch descriptors")) || (rc = s->mem.host(h, 2 * need * sizeof(Item), "the batch descriptors"))) return rc;
-    cap = (int)(2 * need);
+    const size_t units = 2 * std::max<size_t>(need, 1);
+    if ((rc = s->mem.device(d, units * sizeof(Item), TQGPU_ENOMEM, what)) || (rc = s->mem.host(h, units * sizeof(Item), what))) return rc;
+    cap = (Cap)units;
     return TQGPU_OK;
 }
+
+/* ---- the plan of the batched after-solve calls (tqgpu_kkt_residual_batch, tqgpu_mpc_adjoint_batch, tqgpu_mpc_adjoint_matrices_batch): per device
+ * one group; a group that fits one grid goes out as ONE set of launches on its first member's stream (the lead's), anything else member by member ---- */
+struct DeviceGroup { int device; std::vector<int> idx; bool batched = false; };
+static std::vector<DeviceGroup> group_by_device(tqgpu_solver **v, int n) {
+    std::vector<DeviceGroup> groups;
+    for (int i = 0; i < n; i++) {
+        auto g = std::find_if(groups.begin(), groups.end(), [&](const DeviceGroup &q) { return q.device == v[i]->device; });
+        if (g == groups.end()) { groups.push_back(DeviceGroup{v[i]->device, {}}); g = groups.end() - 1; }
+        g->idx.push_back(i);
+    }
+    return groups;
+}
+/* TREEQP_AMD_KKT_BATCH, TREEQP_AMD_ADJ_BATCH = members: every member on its own stream, as a group of one goes */
+static bool batch_by_member(const char *var) { const char *sw = getenv(var); return sw && strcmp(sw, "members") == 0; }
+/* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
+ * waves that return at once, and goes member by member instead.  mx, the largest member's nodes, n members, sum, the nodes of all of them. */
+static bool batch_grid_lopsided(size_t mx, size_t n, size_t sum) { return mx * n > 8 * sum + 4096; }
+/* at least min_members, at most as many as the grid dimension that counts the members takes, no mirror twice, not lopsided */
+static bool group_fits_one_grid(tqgpu_solver **v, const DeviceGroup &g, int min_members, size_t grid_limit) {
+    if (g.idx.size() < (size_t)min_members || g.idx.size() > grid_limit) return false;
+    size_t sum = 0, mx = 0;
+    std::set<const tqgpu_solver *> seen;
+    for (int i : g.idx) {
+        if (!seen.insert(v[i]).second) return false;          /* a mirror named twice: two workgroups would reduce (and rewrite) one table */
+        sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn);
+    }
+    return !batch_grid_lopsided(mx, g.idx.size(), sum);
+}
+/* THE stream rule of a batched group: member s is about to be read and written on its lead's stream, so whatever may still run for it elsewhere
+ * comes first.  A member whose last solve was part of a launch on the lead's stream is ordered by it (settle_stream); one whose launch ran on a
+ * stream this call has waited for already (the members of a later wave of the batch solve, behind their lead) needs nothing more; any other
+ * launch is waited for (settle).  The member's own stream is waited for only where it may hold work the lead's stream has not seen: uploads
+ * (stream_pending), an export that went out ahead, or a solve of its own since this family last drained the stream (`drained_at`, the family's
+ * mark: solve_no at which it last knew the stream to hold nothing of the member's solves; set here).  `waited` holds the streams this call has
+ * synchronised (a handful), `waits` counts them.
+ * Three switches, because the callers' wait counts are pinned and differ:
+ *   step_drains   a member whose last solve was a tqgpu_mpc_step_batch's holds nothing anywhere: that call returned behind the post of u[0], which
+ *                 went out behind every member's last launch (MpcBatchBuf::drained_at).  The adjoint takes it; the KKT check does not, and waits
+ *                 for such a member's own stream once.
+ *   skip_waited   a member's own stream that this call has waited for already (as another member's settle_stream) is not waited for again.
+ *                 The adjoint takes it; the KKT check synchronises again where that stream also has uploads pending or an export ahead.
+ *   behind_wait   the call follows one of this member's that returned behind its wait, with no solve between (the adjoint in H, A, B: adj_need
+ *                 guarantees a stored adjoint, which every solve clears): only uploads can be pending.  A launch not yet settled is settled
+ *                 uncounted, an export ahead and the solves are not looked at, and the family's mark stays: a member-by-member adjoint does
+ *                 not set MpcAdjBatch::drained_at, so the full rule would wait once more here. */
+struct LeadOrder { bool step_drains, skip_waited, behind_wait; };
+static int order_behind_lead(tqgpu_solver *s, const tqgpu_solver *lead, long &drained_at, LeadOrder rule, std::vector<hipStream_t> &waited, int &waits) {
+    auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
+    const bool drained = rule.step_drains && s->solve_no == s->mpcb.drained_at;
+    const bool in_launch = s->settle_stream != nullptr;          /* its last solve was part of a batch launch that has not been waited for */
+    if (rule.behind_wait) SETTLE(s);
+    else if (drained || s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;
+    else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); waits++; } SETTLE(s); }
+    const bool own_solve = !in_launch && !drained && s->solve_no != drained_at;
+    const bool own_work = s->stream_pending || (!rule.behind_wait && (s->out.valid || own_solve));
+    if (s->stream != lead->stream && !(rule.skip_waited && was_waited_for(s->stream)) && own_work) {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        s->stream_pending = false;
+        waited.push_back(s->stream);
+        waits++;
+    }
+    if (!rule.behind_wait) drained_at = s->solve_no;
+    return TQGPU_OK;
+}
+constexpr LeadOrder KKT_ORDER{false, false, false}, ADJ_ORDER{true, true, false}, ADJMAT_ORDER{false, false, true};
 static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
     const int G = lead->geom.G;
     const ProcessSwitches &ps = process_switches();
@@ -4677,6 +4747,7 @@ extern "C" int tqgpu_solve_batch_n(tqgpu_solver **solvers, int n, const tqgpu_op
 
 #include "tdunes_kkt.hpp"
 #include "tdunes_mpc.hpp"
+#include "tdunes_adjoint.hpp"
 #include "tdunes_shard.hpp"
 
 extern "C" int tqgpu_get_iteration_log(tqgpu_solver *s, int *ls_iters, double *iter_times, int cap) {

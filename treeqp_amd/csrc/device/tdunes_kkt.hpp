@@ -412,23 +412,6 @@ thread_local KktBatchStats g_kkt_stats;          /* of this thread's last tqgpu_
 constexpr int KKT_BATCH_MIN = 2;                 /* members of one device from which the batched route is taken: at 2 C1 trees it measured 37 us against 64 us member by member (profiles/r12_kkt_batch_timing.txt) */
 constexpr size_t KKT_GRID_Y = 65535;             /* blockIdx.y is the member */
 
-struct KktGroup { int device; std::vector<int> idx; bool batched = false; };
-
-/* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
- * waves that return at once, and is checked member by member instead.  THE rule (tqgpu_mpc_adjoint_batch shares it): mx, the
- * largest member's nodes, n members, sum, the nodes of all of them. */
-bool batch_grid_lopsided(size_t mx, size_t n, size_t sum) { return mx * n > 8 * sum + 4096; }
-bool kkt_group_batched(tqgpu_solver **v, const KktGroup &g) {
-    if (g.idx.size() < (size_t)KKT_BATCH_MIN || g.idx.size() > KKT_GRID_Y) return false;
-    size_t sum = 0, mx = 0;
-    std::set<const tqgpu_solver *> seen;
-    for (int i : g.idx) {
-        if (!seen.insert(v[i]).second) return false;          /* a mirror named twice: two workgroups would reduce (and rewrite) one table */
-        sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn);
-    }
-    return !batch_grid_lopsided(mx, g.idx.size(), sum);
-}
-
 /* one member on its own stream: the route of tqgpu_kkt_residual without the wait */
 int kkt_member_enqueue(tqgpu_solver *s, KktBatchStats &st) {
     if (s->settle_stream && s->settle_stream != s->stream) st.waits++;
@@ -443,8 +426,8 @@ int kkt_member_enqueue(tqgpu_solver *s, KktBatchStats &st) {
  * waited for here in the steady state -- a loop of tqgpu_solve_batch and this call on the same members -- where every member's solve
  * was part of a launch on this very stream (settle_stream), as in join_lead_stream.  A member's own stream is waited for only where it
  * may hold work this stream has not seen: uploads (stream_pending), an export that went out ahead, or a solve of its own that returned
- * on its verdict (a single launch may still write its state back then). */
-int kkt_group_enqueue(tqgpu_solver **v, const KktGroup &g, KktBatchStats &st) {
+ * on its verdict (a single launch may still write its state back then): order_behind_lead, KKT_ORDER. */
+int kkt_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, KktBatchStats &st) {
     tqgpu_solver *lead = v[g.idx[0]];
     const size_t n = g.idx.size();
     int rc;
@@ -452,21 +435,10 @@ int kkt_group_enqueue(tqgpu_solver **v, const KktGroup &g, KktBatchStats &st) {
     for (int i : g.idx) if ((rc = setup_kkt(v[i], false))) return rc;
     if ((rc = grow_items(lead, lead->kkt.d_items, lead->kkt.h_items, lead->kkt.items_cap, n)) || (rc = grow_items(lead, lead->kkt.d_heads, lead->kkt.h_heads, lead->kkt.heads_cap, n))) return rc;
     int nn_all = 0, nn_box = 0, nn_gen = 0, cells = 0;          /* widths of the four grids (0: no launch) */
-    std::vector<hipStream_t> waited;                             /* streams this call has synchronised (a handful: one per wave of the batch solve at the most) */
-    auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
+    std::vector<hipStream_t> waited;
     for (size_t m = 0; m < n; m++) {
         tqgpu_solver *s = v[g.idx[m]];
-        const bool in_launch = s->settle_stream != nullptr;          /* its last solve was part of a batch launch that has not been waited for */
-        if (s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;          /* ... on this stream: ordered by it, and waited for with the heads; or on one this call has waited for already (the members of a later wave of the batch solve, behind their lead) */
-        else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); st.waits++; } SETTLE(s); }
-        const bool own_solve = !in_launch && s->solve_no != s->kkt.drained_at;
-        if (s->stream != lead->stream && (s->stream_pending || s->out.valid || own_solve)) {
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            s->stream_pending = false;
-            waited.push_back(s->stream);
-            st.waits++;
-        }
-        s->kkt.drained_at = s->solve_no;
+        if ((rc = order_behind_lead(s, lead, s->kkt.drained_at, KKT_ORDER, waited, st.waits))) return rc;
         KItem &it = lead->kkt.h_items[m];
         it.T = s->T; it.D = s->D;
         const ExportSizes z = export_sizes(s);
@@ -508,21 +480,15 @@ extern "C" int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *r
     }
     KktBatchStats &st = g_kkt_stats;
     st = KktBatchStats();
-    const char *sw = getenv("TREEQP_AMD_KKT_BATCH");          /* =members: every member on its own stream, as a group of one goes */
-    const bool by_member = sw && strcmp(sw, "members") == 0;
-    std::vector<KktGroup> groups;
-    for (int i = 0; i < n; i++) {
-        auto g = std::find_if(groups.begin(), groups.end(), [&](const KktGroup &q) { return q.device == solvers[i]->device; });
-        if (g == groups.end()) { groups.push_back(KktGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
-        g->idx.push_back(i);
-    }
-    for (KktGroup &g : groups) {
-        g.batched = !by_member && kkt_group_batched(solvers, g);
+    const bool by_member = batch_by_member("TREEQP_AMD_KKT_BATCH");
+    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    for (DeviceGroup &g : groups) {
+        g.batched = !by_member && group_fits_one_grid(solvers, g, KKT_BATCH_MIN, KKT_GRID_Y);
         if (g.batched) {
             if ((rc = kkt_group_enqueue(solvers, g, st))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
         } else for (int i : g.idx) if ((rc = kkt_member_enqueue(solvers[i], st))) return rc;
     }
-    for (const KktGroup &g : groups) {
+    for (const DeviceGroup &g : groups) {
         tqgpu_solver *lead = solvers[g.idx[0]];
         HIP_TRY(hipSetDevice(lead->device));
         if (g.batched) { HIP_TRY(hipStreamSynchronize(lead->stream)); st.waits++; }

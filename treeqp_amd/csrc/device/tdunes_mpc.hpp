@@ -1,8 +1,9 @@
 /*
  * tdunes_mpc.hpp -- the MPC family of the host part: kernels (k_mpc_pre, k_mpc_post, their batch forms), the plan and launcher of k_mpc_pre,
- * the entry points tqgpu_mpc_* and the host side of the sensitivities.  Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST),
- * behind the batch solve.  That file keeps what the solve path uses: the mirror's records MpcRoot .. MpcSens, MpcStats / MPC_COUNT, MpcPre,
- * mpc_warm_due, problem_changed, and the declarations mpc_before_wave / mpc_behind_launches / mpc_after_wave, the seam to the batch step.
+ * the entry points tqgpu_mpc_* of the step, its batch, the root forms, tracking, warm start and shift.  Included once from tdunes_device.hip inside
+ * #if TQ_HAS(TQP_HOST), behind the batch solve.  That file keeps what the solve path uses: the mirror's records MpcRoot .. MpcTrack, MpcStats / MPC_COUNT,
+ * MpcPre, mpc_warm_due, problem_changed, and the declarations mpc_before_wave / mpc_behind_launches / mpc_after_wave, the seam to the batch step.
+ * The derivatives of a step (sensitivities, adjoints) are tdunes_adjoint.hpp's, included behind this file.
  */
 #pragma once
 
@@ -947,881 +948,5 @@ extern "C" int tqgpu_mpc_stats(int *launches, int *copies, int *waits) {
     if (launches) *launches = st.launches;
     if (copies) *copies = st.copies;
     if (waits) *waits = st.waits;
-    return TQGPU_OK;
-}
-
-/* ---- parametric sensitivities of an MPC step (tdunes_sens.hpp): du0/dx0, dz/dx0, dlam/dx0 at the point of the last solve ---- */
-namespace {
-size_t sens_head_doubles(const tqgpu_solver *s) { return (size_t)s->nu[0] * s->sens.nx0 + (size_t)s->nu[0] + (size_t)s->sens.nx0 + 1; }
-
-/* the LDS windows of k_sens_factor (lf) and k_sens_primal (lp), refused where one does not fit; touches nothing */
-int sens_window_refuse(const tqgpu_solver *s, size_t &lf, size_t &lp) {
-    const size_t nx0 = (size_t)s->mpc.nx0;
-    lf = lp = 0;
-    for (int k = 0; k < s->Nn; k++) {
-        lp = std::max(lp, ((size_t)(s->nx[k] + s->nu[k]) * nx0 + 2) * sizeof(double));
-        if (k < s->Np) {
-            const size_t d = (size_t)s->bdim[k], R = d + (k > 0 ? (size_t)s->nx[k] : nx0), ld = R | 1;
-            lf = std::max(lf, (ld * d + d + 2) * sizeof(double));
-        }
-    }
-    if (lf > 160 * 1024 || lp > 160 * 1024)
-        return fail(TQGPU_EUNSUPPORTED, "tqgpu_mpc_sensitivity: the tall root block [W; G'] (or a node's nz x nx0 window) does not fit 160 KiB of LDS");
-    return TQGPU_OK;
-}
-/* the feature's buffers, on first use and again when nx0 changed: one zeroed device block, the pinned block, the LDS windows */
-int setup_sens(tqgpu_solver *s) {
-    int rc;
-    const size_t nx0 = (size_t)s->mpc.nx0, nu0 = (size_t)s->nu[0], snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu;
-    size_t lf = 0, lp = 0;
-    if ((rc = sens_window_refuse(s, lf, lp))) return rc;
-    if (s->sens.d && s->sens.nx0 == s->mpc.nx0) return TQGPU_OK;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->mem.release(s->sens.d); s->mem.release(s->sens.h);
-    s->sens.invalidate(); s->sens.nx0 = 0;
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
-    const size_t oW = take(s->sum_W), oUt = take(s->sum_Ut), oCW = take(s->sum_W), oCUt = take(s->sum_Ut), oiv = take(snx), oPx = take(snx), oPu = take(snu);
-    const size_t oG = take((size_t)s->bdim[0] * nx0), odl = take(snx * nx0), odx = take(snx * nx0), odu = take(snu * nx0);
-    const size_t head = nu0 * nx0 + nu0 + nx0 + 1, oh = take(head), onr = take(2);
-    if ((rc = s->mem.zeroed(s->sens.d, sizeof(double) * std::max<size_t>(off, 2), TQGPU_ENOMEM, "the sensitivities")) ||
-        (rc = s->mem.host(s->sens.h, sizeof(double) * (head + nx0 + nu0 + 2), "the pinned gain")))
-        return rc;
-    memset(s->sens.h, 0, sizeof(double) * (head + nx0 + nu0 + 2));
-    if ((rc = allow_lds(k_sens_hess, s->lds_hess)) || (rc = allow_lds(k_sens_factor, lf)) || (rc = allow_lds(k_sens_forward, s->lds_forward)) || (rc = allow_lds(k_sens_primal, lp)))
-        return rc;
-    Sens &S = s->sens.v;
-    S = Sens{};
-    double *p = s->sens.d;
-    S.W = p + oW; S.Ut = p + oUt; S.CholW = p + oCW; S.CholUt = p + oCUt; S.invd = p + oiv; S.Px = p + oPx; S.Pu = p + oPu;
-    S.G = p + oG; S.dlam = p + odl; S.dx = p + odx; S.du = p + odu; S.head = p + oh; S.n_reg = reinterpret_cast<int *>(p + onr);
-    S.nx0 = s->mpc.nx0; S.xpad = s->x_pad; S.sum_nx = s->sum_nx; S.sum_nu = s->sum_nu; S.nu0 = s->nu[0];
-    s->sens.nx0 = s->mpc.nx0; s->sens.lds_factor = lf; s->sens.lds_primal = lp;
-    return TQGPU_OK;
-}
-int sens_need(const tqgpu_solver *s, const char *who) {
-    if (!s->sens.valid) return fail(TQGPU_EINVAL, std::string(who) + ": no sensitivity has been computed for the point and the data the device holds now (tqgpu_mpc_sensitivity after the last solve, upload and fold)");
-    return TQGPU_OK;
-}
-/* what tqgpu_mpc_sensitivity and tqgpu_mpc_adjoint refuse alike, before anything is touched */
-int sens_refuse(tqgpu_solver *s, const tqgpu_opts *o, const char *who) {
-    int rc;
-    if ((rc = mpc_refuse(s, who))) return rc;
-    if (!o) return fail(TQGPU_EINVAL, std::string(who) + ": opts is required (the regularisation rule of the factorisation)");
-    if ((rc = mpc_take_x0(s, nullptr, who))) return rc;          /* no root form declared yet, and what a fold would refuse */
-    if (s->solve_no == 0) return fail(TQGPU_EINVAL, std::string(who) + ": this mirror has not solved yet: there is no point to differentiate at");
-    if (s->sens.dirty)
-        return fail(TQGPU_EINVAL, std::string(who) + ": the problem was changed (an upload, an x0 fold or a window move) since the last solve: its point does not belong to the data the device holds now; solve first");
-    if (s->dense) for (int k : s->h_kind) if (k >= 2)
-        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the tree has nodes of kind 2 or 3: Pd need not belong to the final working set after a line search's last trial");
-    return TQGPU_OK;
-}
-/* P, W, Ut, G and the factor of the point the device holds, into the feature's buffers: the packing of the point where it has not gone
- * out, k_sens_hess, k_sens_factor per block level, deepest first.  Returns the view the later kernels take (kept in sens.v by the caller) */
-int sens_enqueue_factor(tqgpu_solver *s, const Opts &O, Sens &S) {
-    int rc;
-    if (!s->out.valid) {
-        if ((rc = enqueue_export(s, s->h_ctrl->cur ? s->D.lam1 : s->D.lam0, false))) return rc;
-        MPC_COUNT(launches, 1);
-    }
-    S = s->sens.v;
-    S.x = s->out.d; S.u = S.x + export_sizes(s).nxe;
-    S.root_states = s->mpc.states ? 1 : 0;
-    if (s->mpc.d) { S.A0 = s->mpc.d; S.S0 = s->mpc.S0 ? s->mpc.d + (size_t)s->mpc.nb * s->mpc.nx0 + s->mpc.nb : nullptr; }
-    S.x0 = s->mpc.h;
-    const Tree &T = s->T;
-    hipLaunchKernelGGL(k_sens_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, s->stream, T, s->D, S);
-    for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
-        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        hipLaunchKernelGGL(k_sens_factor, dim3(count), dim3(WAVE), s->sens.lds_factor, s->stream, T, O, S, first);
-    }
-    HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, 1 + T.Nh);
-    return TQGPU_OK;
-}
-
-/* the adjoint's buffers, on first use and again when nw grows (or nx0 changed): one zeroed device block, the pinned block, the LDS windows.
- * Refuses, before anything is touched, an nw whose nz x nw window would not fit the 160 KiB setup_sens allows an nz x nx0 window */
-int adj_window_refuse(const tqgpu_solver *s, int nw) {
-    for (int k = 0; k < s->Nn; k++)
-        if (((size_t)(s->nx[k] + s->nu[k]) * (size_t)nw + 2) * sizeof(double) > 160 * 1024)
-            return fail(TQGPU_EUNSUPPORTED, "tqgpu_mpc_adjoint: a node's nz x nw window does not fit 160 KiB of LDS");
-    return TQGPU_OK;
-}
-size_t adj_w_doubles(const tqgpu_solver *s, int nw) { return ((size_t)(s->sum_nx - s->x_pad) + (size_t)s->sum_nu) * (size_t)nw; }
-int setup_adj(tqgpu_solver *s, int nw) {
-    int rc;
-    MpcSens &m = s->sens;
-    const size_t snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, nx0 = (size_t)s->mpc.nx0;
-    if (!m.ad || nw > m.nw_cap || m.adj_nx0 != s->mpc.nx0) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        s->mem.release(m.ad); s->mem.release(m.ah);
-        m.adj_valid = false; m.nw_cap = 0;
-        const size_t cap = (size_t)nw;
-        size_t off = 0;
-        auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
-        const size_t ow = take((nxe + snu) * cap), oY = take(snx * cap), ot = take(snx * cap), oq = take(snx * cap), or_ = take(snu * cap), ob = take(snx * cap), oh = take(nx0 * cap + 1);
-        if ((rc = s->mem.zeroed(m.ad, sizeof(double) * std::max<size_t>(off, 2), TQGPU_ENOMEM, "the adjoint")) ||
-            (rc = s->mem.host(m.ah, sizeof(double) * ((nxe + snu) * cap + nx0 * cap + 2), "the pinned loss gradient and gx0")))
-            return rc;
-        memset(m.ah, 0, sizeof(double) * ((nxe + snu) * cap + nx0 * cap + 2));
-        size_t lr = 0, lg = 0;
-        for (int k = 0; k < s->Nn; k++) {
-            const size_t nz = (size_t)(s->nx[k] + s->nu[k]);
-            lr = std::max(lr, (nz + 2) * sizeof(double)); lg = std::max(lg, (2 * nz + 2) * sizeof(double));
-        }
-        if ((rc = allow_lds(k_adj_rhs, lr)) || (rc = allow_lds(k_adj_backward, s->lds_forward)) || (rc = allow_lds(k_adj_forward, s->lds_forward)) || (rc = allow_lds(k_adj_grad, lg)))
-            return rc;
-        Adj &A = m.a;
-        A = Adj{};
-        double *p = m.ad;
-        A.wx = p + ow; A.Y = p + oY; A.t = p + ot; A.gq = p + oq; A.gr = p + or_; A.gb = p + ob; A.head = p + oh;
-        A.nxe = (int)nxe;
-        m.nw_cap = nw; m.adj_nx0 = s->mpc.nx0; m.lds_rhs = lr; m.lds_grad = lg;
-    }
-    /* the columns of this call: wu lies behind the nw columns of wx */
-    m.a.nw = nw;
-    m.a.wu = m.a.wx + nxe * (size_t)nw;
-    return TQGPU_OK;
-}
-int adj_need(const tqgpu_solver *s, const char *who) {
-    if (!s->sens.adj_valid) return fail(TQGPU_EINVAL, std::string(who) + ": no adjoint has been computed for the point and the data the device holds now (tqgpu_mpc_adjoint after the last solve, upload and fold)");
-    return TQGPU_OK;
-}
-}  // namespace
-
-extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *n_reg) {
-    const char *who = "tqgpu_mpc_sensitivity";
-    int rc;
-    if ((rc = sens_refuse(s, o, who))) return rc;
-    Opts O;
-    if ((rc = opts_from(o, O))) return rc;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    MpcLive live;
-    if ((rc = setup_sens(s))) return rc;
-    s->sens.valid = s->sens.factored = false;
-    Sens S;
-    if ((rc = sens_enqueue_factor(s, O, S))) return rc;
-    const Tree &T = s->T;
-    hipStream_t st = s->stream;
-    for (int lvl = 1; lvl < T.Nh; lvl++) {
-        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        hipLaunchKernelGGL(k_sens_forward, dim3(count, (unsigned)s->sens.nx0), dim3(WAVE), s->lds_forward, st, T, S, first);
-    }
-    hipLaunchKernelGGL(k_sens_primal, dim3(T.Nn), dim3(WAVE), s->sens.lds_primal, st, T, s->D, S);
-    HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, (T.Nh - 1) + 1);
-    const size_t head = sens_head_doubles(s);
-    HIP_TRY(hipMemcpyAsync(s->sens.h, S.head, sizeof(double) * head, hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
-    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
-    s->sens.v = S;
-    s->sens.valid = s->sens.factored = true;
-    if (n_reg) *n_reg = (int)s->sens.h[head - 1];
-    return TQGPU_OK;
-}
-
-/* ---- the adjoint of an MPC step (tdunes_sens.hpp): dL/dq, dL/dr, dL/db, dL/dx0 for w = dL/dz at the point of the last solve ---- */
-/* one mirror on its own stream, behind the refusals that touch nothing; counted into whatever record is live (tqgpu_mpc_adjoint's own, or that of a
- * tqgpu_mpc_adjoint_batch that goes member by member) */
-static int mpc_adjoint_one(tqgpu_solver *s, const Opts &O, const double *wx, const double *wu, int nw, int *n_reg) {
-    int rc;
-    if ((rc = adj_window_refuse(s, nw)) || (rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
-    s->sens.adj_valid = false;
-    MpcSens &m = s->sens;
-    const size_t nxe = (size_t)(s->sum_nx - s->x_pad), snu = (size_t)s->sum_nu, nwd = adj_w_doubles(s, nw), nx0 = (size_t)m.nx0;
-    hipStream_t st = s->stream;
-    /* w through pinned memory in one copy: [wx | wu], a missing part as zeros */
-    if (wx) memcpy(m.ah, wx, sizeof(double) * nxe * nw); else memset(m.ah, 0, sizeof(double) * nxe * nw);
-    if (wu) memcpy(m.ah + nxe * nw, wu, sizeof(double) * snu * nw); else memset(m.ah + nxe * nw, 0, sizeof(double) * snu * nw);
-    if (nwd) { HIP_TRY(hipMemcpyAsync(const_cast<double *>(m.a.wx), m.ah, sizeof(double) * nwd, hipMemcpyHostToDevice, st)); }
-    MPC_COUNT(copies, 1);
-    Sens S = m.v;
-    if (!m.factored) {
-        if ((rc = sens_enqueue_factor(s, O, S))) return rc;
-        m.v = S;
-        m.factored = true;          /* (valid stays false: dlam, dZ and the head of this point have not been computed) */
-    }
-    const Tree &T = s->T;
-    const Adj A = m.a;
-    const unsigned cols = (unsigned)nw;
-    hipLaunchKernelGGL(k_adj_rhs, dim3(T.Np, cols), dim3(WAVE), m.lds_rhs, st, T, s->D, S, A);
-    for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
-        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        hipLaunchKernelGGL(k_adj_backward, dim3(count, cols), dim3(WAVE), s->lds_forward, st, T, S, A, first);
-    }
-    for (int lvl = 1; lvl < T.Nh; lvl++) {
-        const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        hipLaunchKernelGGL(k_adj_forward, dim3(count, cols), dim3(WAVE), s->lds_forward, st, T, S, A, first);
-    }
-    hipLaunchKernelGGL(k_adj_grad, dim3(T.Nn, cols), dim3(WAVE), m.lds_grad, st, T, s->D, S, A);
-    HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, 1 + T.Nh + (T.Nh - 1) + 1);
-    double *hh = m.ah + nwd;
-    HIP_TRY(hipMemcpyAsync(hh, A.head, sizeof(double) * (nx0 * nw + 1), hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
-    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
-    m.nw = nw;
-    m.adj_valid = true;
-    if (n_reg) *n_reg = (int)hh[nx0 * nw];
-    return TQGPU_OK;
-}
-extern "C" int tqgpu_mpc_adjoint(tqgpu_solver *s, const tqgpu_opts *o, const double *wx, const double *wu, int nw, int *n_reg) {
-    const char *who = "tqgpu_mpc_adjoint";
-    int rc;
-    if ((rc = sens_refuse(s, o, who))) return rc;
-    if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
-    Opts O;
-    if ((rc = opts_from(o, O))) return rc;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    MpcLive live;
-    return mpc_adjoint_one(s, O, wx, wu, nw, n_reg);
-}
-
-extern "C" int tqgpu_mpc_get_adjoint_x0(tqgpu_solver *s, double *gx0) {
-    int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_adjoint_x0")) || (rc = adj_need(s, "tqgpu_mpc_get_adjoint_x0"))) return rc;
-    const size_t n = (size_t)s->sens.nx0 * (size_t)s->sens.nw;
-    if (gx0 && n) memcpy(gx0, s->sens.ah + adj_w_doubles(s, s->sens.nw), sizeof(double) * n);
-    return TQGPU_OK;
-}
-
-/* a diagnostic download (whole buffers through pageable memory, repacked on the host): not counted into tqgpu_mpc_stats */
-extern "C" int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb) {
-    int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_adjoint")) || (rc = adj_need(s, "tqgpu_mpc_get_adjoint"))) return rc;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    const size_t nw = (size_t)s->sens.nw, snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, nl = (size_t)s->sum_lam;
-    std::vector<double> tmp(snx * nw + 1);
-    for (int which = 0; which < 2; which++) {
-        double *out = which ? gb : gq;
-        if (!out) continue;
-        HIP_TRY(hipMemcpy(tmp.data(), which ? s->sens.a.gb : s->sens.a.gq, sizeof(double) * snx * nw, hipMemcpyDeviceToHost));
-        const size_t skip = which ? (size_t)s->nx0 : (size_t)s->x_pad, n = which ? nl : nxe;      /* the root has no dual; phantom root states are left out */
-        for (size_t j = 0; j < nw; j++) if (n) memcpy(out + j * n, tmp.data() + j * snx + skip, sizeof(double) * n);
-    }
-    if (gr && snu * nw) HIP_TRY(hipMemcpy(gr, s->sens.a.gr, sizeof(double) * snu * nw, hipMemcpyDeviceToHost));
-    return TQGPU_OK;
-}
-
-/* ---- tqgpu_mpc_adjoint_batch: per device one group; a group of ADJ_BATCH_MIN members or more goes out as ONE set of launches on its first
- * member's stream (the lead's), anything else member by member through mpc_adjoint_one ---- */
-namespace {
-constexpr int ADJ_BATCH_MIN = 2;                 /* members of one device from which the batched route is taken: at 2 C1 trees it measured 212 us against 417 us member by member, at 4 212 us against 809 us (profiles/r21_mpc_adjoint_batch.txt) */
-constexpr size_t ADJ_GRID_Z = 65535;             /* blockIdx.z is the member */
-
-/* the packing of the members' points: the body of k_export_all_batch over the adjoint's descriptor (kinds 2 and 3 are refused: no overlays) */
-__global__ void __launch_bounds__(256) k_adj_export_batch(const AItem *__restrict__ items) {
-    const AItem &it = items[blockIdx.y];
-    if (!it.needs_export) return;
-    export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, it.nxe, it.nue, it.nl, it.x_pad, it.nx0, it.D, it.lamc, it.d_out);
-}
-
-struct AdjGroup { int device; std::vector<int> idx; bool batched = false; std::vector<Sens> views; };
-struct AdjSpan { size_t wx, wu, gx0; };          /* where a member's blocks begin in the caller's wx, wu and gx0 */
-
-bool adj_group_batched(tqgpu_solver **v, const AdjGroup &g) {
-    if (g.idx.size() < (size_t)ADJ_BATCH_MIN || g.idx.size() > ADJ_GRID_Z) return false;
-    size_t sum = 0, mx = 0;
-    for (int i : g.idx) { sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn); }
-    return !batch_grid_lopsided(mx, g.idx.size(), sum);
-}
-/* a pair of blocks of the lead, device and pinned, with room for `need` units (the lead's stream holds nothing that reads them: every call ends with its wait) */
-template <typename U>
-int adj_grow(tqgpu_solver *lead, U *&d, U *&h, size_t &cap, size_t need, const char *what) {
-    if (cap >= need && d) return TQGPU_OK;
-    lead->mem.release(d); lead->mem.release(h);
-    cap = 0;
-    int rc;
-    const size_t units = 2 * std::max<size_t>(need, 1);
-    if ((rc = lead->mem.device(d, units * sizeof(U), TQGPU_ENOMEM, what)) || (rc = lead->mem.host(h, units * sizeof(U), what))) return rc;
-    cap = units;
-    return TQGPU_OK;
-}
-
-/* A group on its lead's stream: the descriptors and level tables in one copy, w of all members in one copy, the launches, the heads in one
- * copy; nothing is waited for here in the steady state.  The stream rules are kkt_group_enqueue's: a member whose last solve was part of a
- * launch on this very stream is ordered by it; a member's own stream is waited for only where it may hold work this stream has not seen
- * (uploads, an export that went out ahead, a solve of its own).  A member whose last solve was a tqgpu_mpc_step_batch's holds nothing
- * anywhere: that call returned behind the post of u[0], which went out behind every member's last launch (MpcBatchBuf::drained_at). */
-int adj_group_enqueue(tqgpu_solver **v, AdjGroup &g, const Opts &O, const double *wx, const double *wu, int nw, const std::vector<AdjSpan> &span) {
-    tqgpu_solver *lead = v[g.idx[0]];
-    const size_t n = g.idx.size();
-    int rc;
-    HIP_TRY(hipSetDevice(lead->device));
-    size_t w_all = 0, heads_all = 0, lvl_ints = 0;
-    for (int i : g.idx) {
-        tqgpu_solver *s = v[i];
-        if ((rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
-        w_all += adj_w_doubles(s, nw); heads_all += (size_t)s->sens.nx0 * nw + 1; lvl_ints += 2 * (size_t)s->T.Nh;
-    }
-    MpcAdjBatch &B = lead->adjb;
-    const size_t items_bytes = n * sizeof(AItem);
-    if ((rc = adj_grow(lead, B.d_desc, B.h_desc, B.desc_cap, items_bytes + lvl_ints * sizeof(int), "the descriptors of a batched adjoint")) ||
-        (rc = adj_grow(lead, B.d_w, B.h_w, B.w_cap, w_all, "the loss gradients of a batched adjoint")) ||
-        (rc = adj_grow(lead, B.d_heads, B.h_heads, B.heads_cap, heads_all, "the heads of a batched adjoint")))
-        return rc;
-    AItem *items = reinterpret_cast<AItem *>(B.h_desc);
-    int *h_lvl = reinterpret_cast<int *>(B.h_desc + items_bytes);
-    const int *d_lvl = reinterpret_cast<const int *>(B.d_desc + items_bytes);
-    /* widths of the grids: per launch the largest member's extent (0: no launch) */
-    int np_all = 0, np_fac = 0, nn_all = 0, cells = 0, nh_all = 0, nh_fac = 0;
-    size_t l_hess = 0, l_factor = 0, l_sweep = 0, l_rhs = 0, l_grad = 0;
-    std::vector<int> wide_bwd, wide_fac, wide_fwd;
-    std::vector<hipStream_t> waited;
-    auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
-    size_t w_at = 0, h_at = 0, l_at = 0;
-    g.views.assign(n, Sens{});
-    for (size_t m = 0; m < n; m++) {
-        tqgpu_solver *s = v[g.idx[m]];
-        const bool drained = s->solve_no == s->mpcb.drained_at;
-        const bool in_launch = s->settle_stream != nullptr;
-        if (drained || s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;
-        else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); MPC_COUNT(waits, 1); } SETTLE(s); }
-        const bool own_solve = !in_launch && !drained && s->solve_no != s->adjb.drained_at;
-        if (s->stream != lead->stream && !was_waited_for(s->stream) && (s->stream_pending || s->out.valid || own_solve)) {
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            s->stream_pending = false;
-            waited.push_back(s->stream);
-            MPC_COUNT(waits, 1);
-        }
-        s->adjb.drained_at = s->solve_no;
-        MpcSens &ms = s->sens;
-        ms.adj_valid = false;
-        const ExportSizes z = export_sizes(s);
-        const size_t nxe = (size_t)z.nxe, snu = (size_t)s->sum_nu, nwd = adj_w_doubles(s, nw);
-        AItem &it = items[m];
-        it = AItem{};
-        it.T = s->T; it.D = s->D; it.O = O;
-        it.needs_factor = ms.factored ? 0 : 1;
-        it.needs_export = it.needs_factor && !s->out.valid ? 1 : 0;
-        Sens S = ms.v;
-        if (it.needs_factor) {          /* the view sens_enqueue_factor makes */
-            S.x = s->out.d; S.u = S.x + z.nxe;
-            S.root_states = s->mpc.states ? 1 : 0;
-            if (s->mpc.d) { S.A0 = s->mpc.d; S.S0 = s->mpc.S0 ? s->mpc.d + (size_t)s->mpc.nb * s->mpc.nx0 + s->mpc.nb : nullptr; }
-            S.x0 = s->mpc.h;
-        }
-        it.S = g.views[m] = S;
-        it.A = ms.a;
-        it.A.wx = B.d_w + w_at; it.A.wu = it.A.wx + nxe * (size_t)nw; it.A.head = B.d_heads + h_at;
-        /* w through the lead's pinned block: [wx | wu] of this member, a missing part as zeros */
-        double *hw = B.h_w + w_at;
-        if (wx) memcpy(hw, wx + span[(size_t)g.idx[m]].wx, sizeof(double) * nxe * nw); else memset(hw, 0, sizeof(double) * nxe * nw);
-        if (wu) memcpy(hw + nxe * nw, wu + span[(size_t)g.idx[m]].wu, sizeof(double) * snu * nw); else memset(hw + nxe * nw, 0, sizeof(double) * snu * nw);
-        w_at += nwd; h_at += (size_t)ms.nx0 * nw + 1;
-        const int Nh = s->T.Nh;
-        it.lvl = d_lvl + l_at;
-        for (int l = 0; l < Nh; l++) { h_lvl[l_at + 2 * l] = s->lvl_first[l]; h_lvl[l_at + 2 * l + 1] = s->lvl_first[l + 1] - s->lvl_first[l]; }
-        l_at += 2 * (size_t)Nh;
-        it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
-        it.d_out = s->out.d;
-        it.x_pad = s->x_pad; it.nxe = z.nxe; it.nue = z.nue; it.nl = z.nl; it.nx0 = s->nx0;
-        np_all = std::max(np_all, s->T.Np); nn_all = std::max(nn_all, s->T.Nn); nh_all = std::max(nh_all, Nh);
-        if ((int)wide_bwd.size() < Nh) { wide_bwd.resize(Nh, 0); wide_fwd.resize(Nh, 0); }
-        for (int l = 0; l < Nh; l++) {
-            const int count = s->lvl_first[l + 1] - s->lvl_first[l];
-            wide_bwd[Nh - 1 - l] = std::max(wide_bwd[Nh - 1 - l], count);
-            if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
-        }
-        l_sweep = std::max(l_sweep, s->lds_forward); l_rhs = std::max(l_rhs, ms.lds_rhs); l_grad = std::max(l_grad, ms.lds_grad);
-        if (it.needs_factor) {
-            np_fac = std::max(np_fac, s->T.Np); nh_fac = std::max(nh_fac, Nh);
-            if ((int)wide_fac.size() < Nh) wide_fac.resize(Nh, 0);
-            for (int l = 0; l < Nh; l++) wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], s->lvl_first[l + 1] - s->lvl_first[l]);
-            l_hess = std::max(l_hess, s->lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
-            if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
-        }
-    }
-    if ((rc = allow_lds(k_sens_hess_batch, l_hess)) || (rc = allow_lds(k_sens_factor_batch, l_factor)) || (rc = allow_lds(k_adj_rhs_batch, l_rhs)) ||
-        (rc = allow_lds(k_adj_backward_batch, l_sweep)) || (rc = allow_lds(k_adj_forward_batch, l_sweep)) || (rc = allow_lds(k_adj_grad_batch, l_grad)))
-        return rc;
-    hipStream_t ls = lead->stream;
-    const unsigned nz = (unsigned)n, cols = (unsigned)nw;
-    const AItem *d_items = reinterpret_cast<const AItem *>(B.d_desc);
-    HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, items_bytes + lvl_ints * sizeof(int), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
-    if (w_all) HIP_TRY(hipMemcpyAsync(B.d_w, B.h_w, sizeof(double) * w_all, hipMemcpyHostToDevice, ls));
-    MPC_COUNT(copies, 1);
-    if (cells) { hipLaunchKernelGGL(k_adj_export_batch, dim3((unsigned)((cells + 255) / 256), nz), dim3(256), 0, ls, d_items); MPC_COUNT(launches, 1); }
-    if (np_fac) {
-        hipLaunchKernelGGL(k_sens_hess_batch, dim3((unsigned)np_fac, 1, nz), dim3(WAVE), l_hess, ls, d_items);
-        for (int j = 0; j < nh_fac; j++) hipLaunchKernelGGL(k_sens_factor_batch, dim3((unsigned)wide_fac[j], 1, nz), dim3(WAVE), l_factor, ls, d_items, j);
-        MPC_COUNT(launches, 1 + nh_fac);
-    }
-    hipLaunchKernelGGL(k_adj_rhs_batch, dim3((unsigned)np_all, cols, nz), dim3(WAVE), l_rhs, ls, d_items);
-    for (int j = 0; j < nh_all; j++) hipLaunchKernelGGL(k_adj_backward_batch, dim3((unsigned)wide_bwd[j], cols, nz), dim3(WAVE), l_sweep, ls, d_items, j);
-    for (int j = 0; j + 1 < nh_all; j++) hipLaunchKernelGGL(k_adj_forward_batch, dim3((unsigned)wide_fwd[j], cols, nz), dim3(WAVE), l_sweep, ls, d_items, j);
-    hipLaunchKernelGGL(k_adj_grad_batch, dim3((unsigned)nn_all, cols, nz), dim3(WAVE), l_grad, ls, d_items);
-    HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, 1 + nh_all + (nh_all - 1) + 1);
-    HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
-    lead->stream_pending = true;
-    return TQGPU_OK;
-}
-}  // namespace
-
-extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *o, const double *wx, const double *wu, int nw, double *gx0, int *n_reg) {
-    const char *who = "tqgpu_mpc_adjoint_batch";
-    if (!solvers || n < 1 || !o) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and opts are required, n must be at least 1)");
-    if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
-    int rc;
-    /* the refusals, all of them before any member is touched */
-    std::set<const tqgpu_solver *> seen;
-    for (int i = 0; i < n; i++) {
-        size_t lf, lp;
-        if ((rc = sens_refuse(solvers[i], o, who)) || (rc = adj_window_refuse(solvers[i], nw)) || (rc = sens_window_refuse(solvers[i], lf, lp)))
-            return fail(rc, "member " + std::to_string(i) + ": " + g_err);
-        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
-    }
-    Opts O;
-    if ((rc = opts_from(o, O))) return rc;
-    const char *sw = getenv("TREEQP_AMD_ADJ_BATCH");          /* =members: every member through tqgpu_mpc_adjoint's own route, as a group of one goes */
-    const bool by_member = sw && strcmp(sw, "members") == 0;
-    std::vector<AdjSpan> span((size_t)n);
-    {
-        AdjSpan at{0, 0, 0};
-        for (int i = 0; i < n; i++) {
-            const tqgpu_solver *s = solvers[i];
-            span[(size_t)i] = at;
-            at.wx += (size_t)(s->sum_nx - s->x_pad) * nw; at.wu += (size_t)s->sum_nu * nw; at.gx0 += (size_t)s->mpc.nx0 * nw;
-        }
-    }
-    std::vector<AdjGroup> groups;
-    for (int i = 0; i < n; i++) {
-        auto g = std::find_if(groups.begin(), groups.end(), [&](const AdjGroup &q) { return q.device == solvers[i]->device; });
-        if (g == groups.end()) { groups.push_back(AdjGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
-        g->idx.push_back(i);
-    }
-    MpcLive live;
-    /* everything goes out before the first wait of a batched group; a group that goes member by member waits member by member */
-    for (AdjGroup &g : groups) {
-        g.batched = !by_member && adj_group_batched(solvers, g);
-        if (g.batched) {
-            if ((rc = adj_group_enqueue(solvers, g, O, wx, wu, nw, span))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
-            continue;
-        }
-        for (int i : g.idx) {
-            tqgpu_solver *s = solvers[i];
-            SETTLE(s);
-            HIP_TRY(hipSetDevice(s->device));
-            const AdjSpan &at = span[(size_t)i];
-            if ((rc = mpc_adjoint_one(s, O, wx ? wx + at.wx : nullptr, wu ? wu + at.wu : nullptr, nw, n_reg ? n_reg + i : nullptr))) return rc;
-            if (gx0) memcpy(gx0 + at.gx0, s->sens.ah + adj_w_doubles(s, nw), sizeof(double) * (size_t)s->sens.nx0 * nw);
-        }
-    }
-    for (AdjGroup &g : groups) {
-        if (!g.batched) continue;
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->stream_pending = false;
-        size_t h_at = 0;
-        for (size_t m = 0; m < g.idx.size(); m++) {
-            const int i = g.idx[m];
-            tqgpu_solver *s = solvers[i];
-            MpcSens &ms = s->sens;
-            const size_t head = (size_t)ms.nx0 * nw + 1;
-            const double *h = lead->adjb.h_heads + h_at;
-            memcpy(ms.ah + adj_w_doubles(s, nw), h, sizeof(double) * head);          /* where tqgpu_mpc_get_adjoint_x0 reads it */
-            if (gx0) memcpy(gx0 + span[(size_t)i].gx0, h, sizeof(double) * (head - 1));
-            if (n_reg) n_reg[i] = (int)h[head - 1];
-            ms.v = g.views[m];
-            ms.factored = true;          /* (valid stays as it was: a stored sensitivity was not touched, a missing one is still missing) */
-            ms.nw = nw;
-            ms.adj_valid = true;
-            h_at += head;
-        }
-    }
-    return TQGPU_OK;
-}
-
-/* ---- the adjoint in H, A, B (tdunes_sens.hpp: k_adjmat_part, k_adjmat_sum): outer products of the stored adjoint with the point, summed over the
- * caller's parameter groups, back through pinned memory in one copy with one wait ---- */
-namespace {
-constexpr int ADJMAT_REGIONS = 7;          /* gH, gh, gA, gB, gb, gA0, gS0 */
-int adjmat_kind(const tqgpu_solver *s, int k) { return s->dense && !s->h_kind.empty() ? s->h_kind[(size_t)k] : 0; }
-bool adjmat_root(const tqgpu_solver *s) { return s->mpc.d && !s->mpc.states && s->mpc.nx0 > 0; }
-/* what the tables depend on beyond the maps: every node's kind, the root form, nx0 */
-std::vector<int> adjmat_sig(const tqgpu_solver *s) {
-    std::vector<int> sig((size_t)s->Nn + 2);
-    for (int k = 0; k < s->Nn; k++) sig[(size_t)k] = adjmat_kind(s, k);
-    sig[(size_t)s->Nn] = adjmat_root(s) ? 1 : 0; sig[(size_t)s->Nn + 1] = s->mpc.nx0;
-    return sig;
-}
-/* member lists, group and chunk records, the list of groups to sum, the region and partial sizes, the LDS window: built from the maps and the kinds the
- * device holds now, uploaded in one block.  Refuses a group that mixes kinds and a group whose window does not fit */
-int adjmat_build(tqgpu_solver *s, const char *who) {
-    MpcAdjMat &m = s->adjm;
-    int rc;
-    const int Nn = s->Nn;
-    m.sig.clear();
-    std::vector<std::vector<int>> hm((size_t)m.n_h), cm((size_t)m.n_c);
-    for (int k = 0; k < Nn; k++) {
-        if (m.hgroup[(size_t)k] >= 0) hm[(size_t)m.hgroup[(size_t)k]].push_back(k);
-        if (m.cgroup[(size_t)k] >= 0) cm[(size_t)m.cgroup[(size_t)k]].push_back(k);
-    }
-    for (int g = 0; g < m.n_h; g++) for (int k : hm[(size_t)g]) if (adjmat_kind(s, k) != adjmat_kind(s, hm[(size_t)g][0]))
-        return fail(TQGPU_EINVAL, std::string(who) + ": h-group " + std::to_string(g) + " has come to mix kinds: node " + std::to_string(k) + " is of kind " + std::to_string(adjmat_kind(s, k)) +
-                                  ", node " + std::to_string(hm[(size_t)g][0]) + " of kind " + std::to_string(adjmat_kind(s, hm[(size_t)g][0])));
-    const int root = adjmat_root(s) ? 1 : 0;
-    std::vector<int> hmem, cmem, hgrp((size_t)m.n_h * 8, 0), cgrp((size_t)m.n_c * 8, 0), hchk, cchk, sums;
-    size_t tot[ADJMAT_REGIONS] = {}, part = 0, lds = 0;
-    auto chunks = [](std::vector<int> &chk, int g, int first, int members) {
-        int q = 0;
-        for (int at = 0; at < members; at += ADJMAT_CHUNK, q++) { chk.push_back(g); chk.push_back(first + at); chk.push_back(std::min(ADJMAT_CHUNK, members - at)); chk.push_back(q); }
-        return q;
-    };
-    for (int g = 0; g < m.n_h; g++) {
-        const std::vector<int> &v = hm[(size_t)g];
-        const size_t nz = (size_t)(s->nx[(size_t)v[0]] + s->nu[(size_t)v[0]]), hsz = adjmat_kind(s, v[0]) ? nz * nz : nz;
-        int *rec = &hgrp[(size_t)g * 8];
-        rec[0] = v[0]; rec[1] = (int)tot[0]; rec[2] = (int)tot[1]; rec[4] = (int)(hchk.size() / 4);
-        rec[5] = chunks(hchk, g, (int)hmem.size(), (int)v.size()); rec[6] = (int)part;
-        hmem.insert(hmem.end(), v.begin(), v.end());
-        tot[0] += hsz; tot[1] += nz; part += (size_t)rec[5] * (hsz + nz);
-        lds = std::max(lds, (hsz + nz + 2 * nz + 2) * sizeof(double));
-        if (rec[5] > 1) sums.push_back(g);
-    }
-    for (int g = 0; g < m.n_c; g++) {
-        const std::vector<int> &v = cm[(size_t)g];
-        const int c = v[0], p = s->dad[(size_t)c];
-        const size_t nxc = (size_t)s->nx[(size_t)c], nxp = (size_t)s->nx[(size_t)p], nup = (size_t)s->nu[(size_t)p], gsz = nxc * (nxp + nup + 1);
-        int *rec = &cgrp[(size_t)g * 8];
-        rec[0] = c; rec[1] = (int)tot[2]; rec[2] = (int)tot[3]; rec[3] = (int)tot[4]; rec[4] = (int)(cchk.size() / 4);
-        rec[5] = chunks(cchk, g, (int)cmem.size(), (int)v.size()); rec[6] = (int)part;
-        cmem.insert(cmem.end(), v.begin(), v.end());
-        tot[2] += nxc * nxp; tot[3] += nxc * nup; tot[4] += nxc; part += (size_t)rec[5] * gsz;
-        lds = std::max(lds, (gsz + 2 * nxc + 2 * (nxp + nup) + 2) * sizeof(double));
-        if (rec[5] > 1) sums.push_back(m.n_h + g);
-    }
-    const size_t pR = part;
-    if (root) { tot[5] = (size_t)s->mpc.nb * s->mpc.nx0; tot[6] = (size_t)s->nu[0] * s->mpc.nx0; part += tot[5] + tot[6]; }
-    if (lds > 160 * 1024) return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": a group's window (its result blocks and a member's vectors) does not fit 160 KiB of LDS");
-    /* the region starts: every offset of a record is made absolute */
-    m.reg[0] = 0;
-    for (int i = 0; i < ADJMAT_REGIONS; i++) m.reg[i + 1] = m.reg[i] + tot[i];
-    if (m.reg[ADJMAT_REGIONS] > (size_t)INT_MAX / 2 || part > (size_t)INT_MAX / 2) return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the result does not fit the tables' 32-bit offsets");
-    for (int g = 0; g < m.n_h; g++) { hgrp[(size_t)g * 8 + 1] += (int)m.reg[0]; hgrp[(size_t)g * 8 + 2] += (int)m.reg[1]; }
-    for (int g = 0; g < m.n_c; g++) { cgrp[(size_t)g * 8 + 1] += (int)m.reg[2]; cgrp[(size_t)g * 8 + 2] += (int)m.reg[3]; cgrp[(size_t)g * 8 + 3] += (int)m.reg[4]; }
-    std::vector<int> tab;
-    auto put = [&](const std::vector<int> &v) { const size_t at = tab.size(); tab.insert(tab.end(), v.begin(), v.end()); return at; };
-    const size_t o_hmem = put(hmem), o_cmem = put(cmem), o_hgrp = put(hgrp), o_cgrp = put(cgrp), o_hchk = put(hchk), o_cchk = put(cchk), o_sums = put(sums);
-    tab.push_back(0);
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->mem.release(m.d_tab);
-    if ((rc = s->mem.upload(m.d_tab, tab.data(), tab.size() * sizeof(int), TQGPU_ENOMEM, "the tables of the parameter groups"))) return rc;
-    AdjMat &M = m.v;
-    M = AdjMat{};
-    M.hmem = m.d_tab + o_hmem; M.cmem = m.d_tab + o_cmem; M.hgrp = m.d_tab + o_hgrp; M.cgrp = m.d_tab + o_cgrp;
-    M.hchk = m.d_tab + o_hchk; M.cchk = m.d_tab + o_cchk; M.sums = m.d_tab + o_sums;
-    M.n_hgrp = m.n_h; M.n_cgrp = m.n_c; M.n_hchk = (int)(hchk.size() / 4); M.n_cchk = (int)(cchk.size() / 4); M.n_sums = (int)sums.size();
-    M.root = root; M.oA0 = (int)m.reg[5]; M.oS0 = (int)m.reg[6]; M.pR = (int)pR;
-    m.n_units = M.n_hchk + M.n_cchk + root;
-    m.part1 = part; m.lds = lds;
-    m.sig = adjmat_sig(s);
-    return TQGPU_OK;
-}
-/* what the two calls refuse for a mirror before anything of its results is touched; brings the tables up to date with the kinds, the root form and nx0 */
-int adjmat_refuse(tqgpu_solver *s, const char *who) {
-    int rc;
-    if ((rc = mpc_refuse(s, who)) || (rc = adj_need(s, who))) return rc;
-    if (!s->adjm.set) return fail(TQGPU_EINVAL, std::string(who) + ": no parameter groups have been given (tqgpu_mpc_set_param_groups)");
-    if (s->adjm.sig != adjmat_sig(s) && (rc = adjmat_build(s, who))) return rc;
-    return TQGPU_OK;
-}
-/* the result block, its pinned twin and the partials for nw columns */
-int adjmat_room(tqgpu_solver *s, int nw) {
-    MpcAdjMat &m = s->adjm;
-    int rc;
-    const size_t need_res = std::max<size_t>(m.reg[ADJMAT_REGIONS] * (size_t)nw, 1), need_part = std::max<size_t>(m.part1 * (size_t)nw, 1);
-    if (!m.d_res || m.res_cap < need_res) {
-        s->mem.release(m.d_res); s->mem.release(m.h_res); m.res_cap = 0;
-        if ((rc = s->mem.device(m.d_res, need_res * sizeof(double), TQGPU_ENOMEM, "the matrix gradients")) || (rc = s->mem.host(m.h_res, need_res * sizeof(double), "the pinned matrix gradients"))) return rc;
-        m.res_cap = need_res;
-    }
-    if (!m.d_part || m.part_cap < need_part) {
-        s->mem.release(m.d_part); m.part_cap = 0;
-        if ((rc = s->mem.device(m.d_part, need_part * sizeof(double), TQGPU_ENOMEM, "the partial sums of the matrix gradients"))) return rc;
-        m.part_cap = need_part;
-    }
-    return TQGPU_OK;
-}
-/* the view the kernels take: the tables, the duals of the export block, where to write */
-AdjMat adjmat_view(const tqgpu_solver *s, double *res) {
-    AdjMat M = s->adjm.v;
-    const ExportSizes z = export_sizes(s);
-    M.lam = s->out.d + z.nxe + z.nue; M.res = res; M.part = s->adjm.d_part;
-    return M;
-}
-/* the seven regions of a result block of nw columns, each to its pointer at an offset (in doubles) of its own; add: accumulate instead of copying */
-void adjmat_scatter(const MpcAdjMat &m, const double *h, int nw, double *const out[ADJMAT_REGIONS], const size_t at[ADJMAT_REGIONS], bool add = false) {
-    for (int i = 0; i < ADJMAT_REGIONS; i++) {
-        const size_t n = (m.reg[i + 1] - m.reg[i]) * (size_t)nw;
-        if (!out[i] || !n) continue;
-        const double *src = h + m.reg[i] * (size_t)nw;
-        if (!add) memcpy(out[i] + at[i], src, sizeof(double) * n);
-        else for (size_t e = 0; e < n; e++) out[i][at[i] + e] = out[i][at[i] + e] + src[e];
-    }
-}
-/* one mirror on its own stream: one or two launches, one copy, one wait */
-int adjmat_one(tqgpu_solver *s, double *const out[ADJMAT_REGIONS], const size_t at[ADJMAT_REGIONS], bool add = false) {
-    MpcAdjMat &m = s->adjm;
-    int rc;
-    const int nw = s->sens.nw;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = adjmat_room(s, nw)) || (rc = allow_lds(k_adjmat_part, m.lds))) return rc;
-    const AdjMat M = adjmat_view(s, m.d_res);
-    hipStream_t st = s->stream;
-    if (m.n_units) { hipLaunchKernelGGL(k_adjmat_part, dim3((unsigned)m.n_units, (unsigned)nw), dim3(WAVE), m.lds, st, s->T, s->D, s->sens.v, s->sens.a, M); MPC_COUNT(launches, 1); }
-    if (M.n_sums) { hipLaunchKernelGGL(k_adjmat_sum, dim3((unsigned)M.n_sums, (unsigned)nw), dim3(WAVE), 0, st, s->T, s->D, s->sens.v, M, nw); MPC_COUNT(launches, 1); }
-    HIP_TRY(hipGetLastError());
-    const size_t n = m.reg[ADJMAT_REGIONS] * (size_t)nw;
-    if (n) HIP_TRY(hipMemcpyAsync(m.h_res, m.d_res, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    MPC_COUNT(copies, 1);
-    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
-    adjmat_scatter(m, m.h_res, nw, out, at, add);
-    return TQGPU_OK;
-}
-}  // namespace
-
-extern "C" int tqgpu_mpc_set_param_groups(tqgpu_solver *s, const int *hgroup, const int *cgroup, int n_hgroups, int n_cgroups) {
-    const char *who = "tqgpu_mpc_set_param_groups";
-    int rc;
-    if ((rc = mpc_refuse(s, who))) return rc;
-    const int Nn = s->Nn;
-    std::vector<int> hg((size_t)Nn), cg((size_t)Nn);
-    const int n_h = hgroup ? n_hgroups : Nn, n_c = cgroup ? n_cgroups : Nn - 1;
-    if (n_h < 0 || n_c < 0) return fail(TQGPU_EINVAL, std::string(who) + ": a negative number of groups");
-    for (int k = 0; k < Nn; k++) {
-        hg[(size_t)k] = hgroup ? hgroup[k] : k;
-        cg[(size_t)k] = cgroup ? cgroup[k] : k - 1;
-        if (hg[(size_t)k] < -1 || hg[(size_t)k] >= n_h) return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": hgroup = " + std::to_string(hg[(size_t)k]) + " is outside [-1, " + std::to_string(n_h) + ")");
-        if (cg[(size_t)k] < -1 || cg[(size_t)k] >= n_c) return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": cgroup = " + std::to_string(cg[(size_t)k]) + " is outside [-1, " + std::to_string(n_c) + ")");
-    }
-    if (cg[0] != -1) return fail(TQGPU_EINVAL, std::string(who) + ": node 0: the root has no dynamics, cgroup[0] must be -1");
-    std::vector<int> hfirst((size_t)n_h, -1), cfirst((size_t)n_c, -1), hdims((size_t)n_h * 4, 0), cdims((size_t)n_c * 4, 0);
-    for (int k = 0; k < Nn; k++) {
-        const int g = hg[(size_t)k], pad = k == 0 ? s->x_pad : 0;
-        if (g >= 0) {
-            int *d = &hdims[(size_t)g * 4];
-            if (hfirst[(size_t)g] < 0) { hfirst[(size_t)g] = k; d[0] = s->nx[(size_t)k]; d[1] = s->nu[(size_t)k]; d[2] = pad; }
-            else if (d[0] != s->nx[(size_t)k] || d[1] != s->nu[(size_t)k] || d[2] != pad)
-                return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": nx, nu or the phantom root states differ from those of node " + std::to_string(hfirst[(size_t)g]) + ", the first member of h-group " + std::to_string(g));
-            d[3]++;
-        }
-        const int gc = cg[(size_t)k];
-        if (gc >= 0) {
-            const int p = s->dad[(size_t)k];
-            int *d = &cdims[(size_t)gc * 4];
-            if (cfirst[(size_t)gc] < 0) { cfirst[(size_t)gc] = k; d[0] = s->nx[(size_t)k]; d[1] = s->nx[(size_t)p]; d[2] = s->nu[(size_t)p]; }
-            else if (d[0] != s->nx[(size_t)k] || d[1] != s->nx[(size_t)p] || d[2] != s->nu[(size_t)p])
-                return fail(TQGPU_EINVAL, std::string(who) + ": node " + std::to_string(k) + ": nx of the node, or nx, nu of its parent differ from those of node " + std::to_string(cfirst[(size_t)gc]) + ", the first member of c-group " + std::to_string(gc));
-            d[3]++;
-        }
-    }
-    for (int g = 0; g < n_h; g++) if (hfirst[(size_t)g] < 0) return fail(TQGPU_EINVAL, std::string(who) + ": h-group " + std::to_string(g) + " has no member");
-    for (int g = 0; g < n_c; g++) if (cfirst[(size_t)g] < 0) return fail(TQGPU_EINVAL, std::string(who) + ": c-group " + std::to_string(g) + " has no member");
-    MpcAdjMat &m = s->adjm;
-    m.hgroup = hg; m.cgroup = cg; m.hdims = hdims; m.cdims = cdims; m.n_h = n_h; m.n_c = n_c;
-    m.set = false;
-    if ((rc = adjmat_build(s, who))) return rc;
-    m.set = true;
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_mpc_get_param_groups(tqgpu_solver *s, int *n_hgroups, int *n_cgroups, int *hdims, int *cdims, int *root) {
-    int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_param_groups"))) return rc;
-    const MpcAdjMat &m = s->adjm;
-    if (!m.set) return fail(TQGPU_EINVAL, "tqgpu_mpc_get_param_groups: no parameter groups have been given (tqgpu_mpc_set_param_groups)");
-    if (n_hgroups) *n_hgroups = m.n_h;
-    if (n_cgroups) *n_cgroups = m.n_c;
-    if (hdims) for (int g = 0; g < m.n_h; g++) {
-        memcpy(hdims + 5 * (size_t)g, &m.hdims[4 * (size_t)g], sizeof(int) * 4);
-        const int first = (int)(std::find(m.hgroup.begin(), m.hgroup.end(), g) - m.hgroup.begin());
-        hdims[5 * (size_t)g + 4] = adjmat_kind(s, first);
-    }
-    if (cdims && !m.cdims.empty()) memcpy(cdims, m.cdims.data(), sizeof(int) * m.cdims.size());
-    if (root) { root[0] = adjmat_root(s) ? s->mpc.nb : 0; root[1] = s->nu[0]; root[2] = s->mpc.nx0; root[3] = s->sens.adj_valid ? s->sens.nw : 0; }
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_mpc_adjoint_matrices(tqgpu_solver *s, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0) {
-    int rc;
-    if ((rc = adjmat_refuse(s, "tqgpu_mpc_adjoint_matrices"))) return rc;
-    MpcLive live;
-    double *const out[ADJMAT_REGIONS] = {gH, gh, gA, gB, gb, gA0, gS0};
-    const size_t at[ADJMAT_REGIONS] = {};
-    return adjmat_one(s, out, at);
-}
-
-extern "C" int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, int reduce, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0) {
-    const char *who = "tqgpu_mpc_adjoint_matrices_batch";
-    if (!solvers || n < 1) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers is required, n must be at least 1)");
-    if (reduce != 0 && reduce != 1) return fail(TQGPU_EINVAL, std::string(who) + ": reduce must be 0 or 1");
-    int rc;
-    /* the refusals, all of them before any member's results are touched */
-    std::set<const tqgpu_solver *> seen;
-    for (int i = 0; i < n; i++) {
-        if ((rc = adjmat_refuse(solvers[i], who))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
-        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
-        const MpcAdjMat &a = solvers[0]->adjm, &b = solvers[i]->adjm;
-        if (reduce && (a.hdims != b.hdims || a.cdims != b.cdims || !std::equal(a.reg, a.reg + ADJMAT_REGIONS + 1, b.reg) || a.part1 != b.part1 || a.v.n_hchk != b.v.n_hchk || a.v.n_cchk != b.v.n_cchk ||
-                       a.v.root != b.v.root || solvers[0]->sens.nw != solvers[i]->sens.nw))
-            return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": its group tables (shapes, kinds, root terms) or its columns differ from member 0's; reduce = 1 sums equal shapes");
-    }
-    const char *sw = getenv("TREEQP_AMD_ADJ_BATCH");
-    const bool by_member = sw && strcmp(sw, "members") == 0;
-    double *const out[ADJMAT_REGIONS] = {gH, gh, gA, gB, gb, gA0, gS0};
-    std::vector<std::array<size_t, ADJMAT_REGIONS>> span((size_t)n);
-    {
-        std::array<size_t, ADJMAT_REGIONS> at{};
-        for (int i = 0; i < n; i++) {
-            span[(size_t)i] = at;
-            const MpcAdjMat &m = solvers[i]->adjm;
-            if (!reduce) for (int r = 0; r < ADJMAT_REGIONS; r++) at[(size_t)r] += (m.reg[r + 1] - m.reg[r]) * (size_t)solvers[i]->sens.nw;
-        }
-    }
-    std::vector<AdjGroup> groups;
-    for (int i = 0; i < n; i++) {
-        auto g = std::find_if(groups.begin(), groups.end(), [&](const AdjGroup &q) { return q.device == solvers[i]->device; });
-        if (g == groups.end()) { groups.push_back(AdjGroup{solvers[i]->device, {}}); g = groups.end() - 1; }
-        g->idx.push_back(i);
-    }
-    MpcLive live;
-    bool all_batched = !by_member;
-    for (AdjGroup &g : groups) { g.batched = !by_member && adj_group_batched(solvers, g); all_batched = all_batched && g.batched; }
-    if (reduce && (!all_batched || groups.size() != 1)) {
-        /* the sum over members on the host, in member order: the first member's blocks, then entry by entry the others' */
-        for (int i = 0; i < n; i++) if ((rc = adjmat_one(solvers[i], out, span[0].data(), i > 0))) return rc;
-        return TQGPU_OK;
-    }
-    struct Sent { size_t total; std::vector<size_t> at; };
-    std::vector<Sent> sent(groups.size());
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        AdjGroup &g = groups[gi];
-        if (!g.batched) {
-            for (int i : g.idx) if ((rc = adjmat_one(solvers[i], out, span[(size_t)i].data()))) return rc;
-            continue;
-        }
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        MpcAdjMat &B = lead->adjm;
-        const size_t nm = g.idx.size();
-        HIP_TRY(hipSetDevice(lead->device));
-        size_t total = 0, lds = 0;
-        int units = 0, nsums = 0, cols = 0;
-        sent[gi].at.assign(nm, 0);
-        for (size_t k = 0; k < nm; k++) {
-            tqgpu_solver *s = solvers[g.idx[k]];
-            SETTLE(s);
-            if (s->stream != lead->stream && s->stream_pending) { HIP_TRY(hipStreamSynchronize(s->stream)); s->stream_pending = false; MPC_COUNT(waits, 1); }
-            if ((rc = adjmat_room(s, s->sens.nw))) return rc;
-            sent[gi].at[k] = total;
-            if (!reduce || k == 0) total += s->adjm.reg[ADJMAT_REGIONS] * (size_t)s->sens.nw;
-            units = std::max(units, s->adjm.n_units); nsums = std::max(nsums, s->adjm.v.n_sums); cols = std::max(cols, s->sens.nw); lds = std::max(lds, s->adjm.lds);
-        }
-        sent[gi].total = total;
-        if ((rc = adj_grow(lead, B.d_desc, B.h_desc, B.desc_cap, nm * sizeof(AMItem), "the descriptors of the batched matrix gradients")) ||
-            (rc = adj_grow(lead, B.d_bres, B.h_bres, B.bres_cap, total, "the matrix gradients of a batch")) ||
-            (rc = allow_lds(k_adjmat_part_batch, lds)))
-            return rc;
-        AMItem *items = reinterpret_cast<AMItem *>(B.h_desc);
-        for (size_t k = 0; k < nm; k++) {
-            tqgpu_solver *s = solvers[g.idx[k]];
-            AMItem &it = items[k];
-            it = AMItem{};
-            it.T = s->T; it.D = s->D; it.S = s->sens.v; it.A = s->sens.a;
-            it.M = adjmat_view(s, B.d_bres + (reduce ? 0 : sent[gi].at[k]));
-        }
-        hipStream_t ls = lead->stream;
-        const AMItem *d_items = reinterpret_cast<const AMItem *>(B.d_desc);
-        HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, nm * sizeof(AMItem), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
-        if (units) { hipLaunchKernelGGL(k_adjmat_part_batch, dim3((unsigned)units, (unsigned)cols, (unsigned)nm), dim3(WAVE), lds, ls, d_items, reduce); MPC_COUNT(launches, 1); }
-        if (reduce) {
-            const int gu = lead->adjm.n_h + lead->adjm.n_c + lead->adjm.v.root;
-            if (gu) { hipLaunchKernelGGL(k_adjmat_reduce, dim3((unsigned)gu, (unsigned)cols), dim3(WAVE), 0, ls, d_items, (int)nm); MPC_COUNT(launches, 1); }
-        } else if (nsums) { hipLaunchKernelGGL(k_adjmat_sum_batch, dim3((unsigned)nsums, (unsigned)cols, (unsigned)nm), dim3(WAVE), 0, ls, d_items); MPC_COUNT(launches, 1); }
-        HIP_TRY(hipGetLastError());
-        if (total) HIP_TRY(hipMemcpyAsync(B.h_bres, B.d_bres, sizeof(double) * total, hipMemcpyDeviceToHost, ls));
-        MPC_COUNT(copies, 1);
-        lead->stream_pending = true;
-    }
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        AdjGroup &g = groups[gi];
-        if (!g.batched) continue;
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->stream_pending = false;
-        for (size_t k = 0; k < g.idx.size(); k++) {
-            if (reduce && k > 0) break;
-            const tqgpu_solver *s = solvers[g.idx[k]];
-            adjmat_scatter(s->adjm, lead->adjm.h_bres + sent[gi].at[k], s->sens.nw, out, span[(size_t)g.idx[k]].data());
-        }
-    }
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_mpc_get_gain(tqgpu_solver *s, double *K, double *u0, double *x0_ref) {
-    int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_gain")) || (rc = sens_need(s, "tqgpu_mpc_get_gain"))) return rc;
-    const size_t nu0 = (size_t)s->nu[0], nx0 = (size_t)s->sens.nx0;
-    if (K && nu0 * nx0) memcpy(K, s->sens.h, sizeof(double) * nu0 * nx0);
-    if (u0 && nu0) memcpy(u0, s->sens.h + nu0 * nx0, sizeof(double) * nu0);
-    if (x0_ref && nx0) memcpy(x0_ref, s->sens.h + nu0 * nx0 + nu0, sizeof(double) * nx0);
-    return TQGPU_OK;
-}
-
-/* a diagnostic download (whole buffers through pageable memory, repacked on the host): not part of a step, not counted into tqgpu_mpc_stats */
-extern "C" int tqgpu_mpc_get_sensitivities(tqgpu_solver *s, double *dx, double *du, double *dlam) {
-    int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_sensitivities")) || (rc = sens_need(s, "tqgpu_mpc_get_sensitivities"))) return rc;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    const size_t nx0 = (size_t)s->sens.nx0, snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, nl = (size_t)s->sum_lam;
-    std::vector<double> tmp(std::max(snx, snu) * nx0 + 1);
-    if (dx || dlam) {
-        for (int which = 0; which < 2; which++) {
-            double *out = which ? dlam : dx;
-            if (!out) continue;
-            HIP_TRY(hipMemcpy(tmp.data(), which ? s->sens.v.dlam : s->sens.v.dx, sizeof(double) * snx * nx0, hipMemcpyDeviceToHost));
-            const size_t skip = which ? (size_t)s->nx0 : (size_t)s->x_pad, n = which ? nl : nxe;      /* the root has no dual; phantom root states are left out */
-            for (size_t j = 0; j < nx0; j++) if (n) memcpy(out + j * n, tmp.data() + j * snx + skip, sizeof(double) * n);
-        }
-    }
-    if (du && snu * nx0) HIP_TRY(hipMemcpy(du, s->sens.v.du, sizeof(double) * snu * nx0, hipMemcpyDeviceToHost));
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, int duals, int *n_clipped) {
-    int rc;
-    if ((rc = mpc_refuse(s, "tqgpu_mpc_predict")) || (rc = sens_need(s, "tqgpu_mpc_predict"))) return rc;
-    if (!x0_new) return fail(TQGPU_EINVAL, "tqgpu_mpc_predict: x0_new is required");
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    MpcLive live;
-    const size_t nu0 = (size_t)s->nu[0], nx0 = (size_t)s->sens.nx0, head = sens_head_doubles(s);
-    double *x0n = s->sens.h + head, *out = x0n + nx0;
-    memcpy(x0n, x0_new, sizeof(double) * nx0);
-    /* the predicted duals take the start buffer for ONE solve, as the shifted ones of tqgpu_mpc_shift do: in mode 0 the kernel saves the
-     * caller's buffer (once) and the solve after the next puts it back (solve_begin) */
-    const bool lend = duals && s->warm.mode == 0;
-    if (lend && !s->shift.d_keep && (rc = s->mem.zeroed(s->shift.d_keep, sizeof(double) * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the saved start buffer"))) return rc;
-    double *keep = lend && s->shift.restore == 0 ? s->shift.d_keep : nullptr;
-    hipLaunchKernelGGL(k_mpc_predict, dim3(duals ? 1 + (unsigned)s->Nn : 1u), dim3(WAVE), 0, s->stream, s->T, s->D, s->sens.v, (const double *)x0n, s->d_lam_init, keep, out);
-    HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
-    if (duals) {
-        if (lend) s->shift.restore = 1;
-        s->warm.fresh = true;          /* the next solve starts from the start buffer as it is now, in any mode */
-        s->lam_valid = false;
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream)); MPC_COUNT(waits, 1);
-    if (u0_pred && nu0) memcpy(u0_pred, out, sizeof(double) * nu0);
-    if (n_clipped) *n_clipped = (int)out[nu0];
     return TQGPU_OK;
 }

@@ -10,7 +10,7 @@
  */
 #pragma once
 
-#define TQP_HOST    0x001   /* C-ABI host side + launch-per-phase kernels (k_*), k_pack_persist; the MPC family, k_mpc_pre / k_mpc_post (tdunes_mpc.hpp); solution export and KKT check, k_export_* / k_kkt* (tdunes_kkt.hpp); the host side of both multi-device modes (tdunes_shard.hpp) */
+#define TQP_HOST    0x001   /* C-ABI host side + launch-per-phase kernels (k_*), k_pack_persist; the MPC family, k_mpc_pre / k_mpc_post (tdunes_mpc.hpp); the host side of its sensitivities and adjoints, k_adj_export_batch (tdunes_adjoint.hpp); solution export and KKT check, k_export_* / k_kkt* (tdunes_kkt.hpp); the host side of both multi-device modes (tdunes_shard.hpp) */
 #define TQP_GP      0x002   /* g_persist, g_persist_batch (tdunes_gpersist.hpp) */
 #define TQP_WIDE    0x004   /* k_hess_w, k_factor(_all)_w, k_forward(_all)_w (tdunes_wide.hpp) */
 #define TQP_W3      0x008   /* k_sg, k_sgp_t, k_hf_w, k_fwd3(c) (tdunes_wide3.hpp) */
@@ -22,7 +22,7 @@
 #define TQP_GPD     0x200   /* g_persist_dense: the single-workgroup solve with the dense stage solvers compiled in (tdunes_gpersist.hpp) */
 #define TQP_GPDB    0x400   /* g_persist_dense_batch: a part of its own -- in one translation unit with g_persist_dense the bodies have two callers, the inliner
                              * decides otherwise, and g_persist_dense comes out as another kernel than the one that was measured */
-#define TQP_SENS    0x800   /* k_sens_hess, k_sens_factor, k_sens_forward, k_sens_primal, k_mpc_predict, k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad and the batch forms of the adjoint's six, k_*_batch over AItem, k_adjmat_part, k_adjmat_sum and their batch forms over AMItem (tdunes_sens.hpp) */
+#define TQP_SENS    0x800   /* k_sens_hess, k_sens_factor, k_sens_forward, k_sens_primal, k_mpc_predict, k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad and the batch forms of the adjoint's six, k_*_batch over AItem, k_adjmat_part, k_adjmat_sum and their batch forms over AMItem (tdunes_sens.hpp; launched from tdunes_adjoint.hpp in the host part) */
 #define TQP_ALL     0xFFF
 
 #ifndef TQ_PARTS

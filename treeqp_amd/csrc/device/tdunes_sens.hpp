@@ -1,7 +1,7 @@
 /*
  * tdunes_sens.hpp -- parametric sensitivities of an MPC step: d(x, u, lam) / d x0 at the point of the last solve, active set frozen.
  *
- * Included by tdunes_device.hip; the kernels are written after hess_body, factor_body and forward_body (same tall Cholesky, same
+ * Included by tdunes_device.hip (host side: tdunes_adjoint.hpp); the kernels are written after hess_body, factor_body and forward_body (same tall Cholesky, same
  * substitutions, same WSYNC discipline), with nx0 right-hand sides instead of one.  One wave per unit on a private LDS window, one
  * launch per phase and block level; no kernel waits for another workgroup: the launch boundaries on the mirror's stream order them.
  *
@@ -612,7 +612,7 @@ __global__ void __launch_bounds__(WAVE) k_adj_grad(Tree T, Data D, Sens S, Adj A
 struct AItem {
     Tree T; Data D; Opts O; Sens S; Adj A;
     const int *lvl;                /* [2 T.Nh] first, count of every block level */
-    const double *lamc;            /* the packing (k_adj_export_batch, tdunes_mpc.hpp): the current duals as the host knows them after the solve, */
+    const double *lamc;            /* the packing (k_adj_export_batch, tdunes_adjoint.hpp): the current duals as the host knows them after the solve, */
     double *d_out;                 /* the member's export block, */
     int x_pad, nxe, nue, nl, nx0;  /* phantom root states, the export sizes (x without them, u, lam), the root's states */
     int needs_export, needs_factor;      /* d_out is not packed yet and the factor has to be built from it; the factor is not stored */
