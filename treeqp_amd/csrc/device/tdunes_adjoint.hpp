@@ -80,7 +80,7 @@ int sens_refuse(tqgpu_solver *s, const tqgpu_opts *o, const char *who) {
     if (s->solve_no == 0) return fail(TQGPU_EINVAL, std::string(who) + ": this mirror has not solved yet: there is no point to differentiate at");
     if (s->sens.dirty)
         return fail(TQGPU_EINVAL, std::string(who) + ": the problem was changed (an upload, an x0 fold or a window move) since the last solve: its point does not belong to the data the device holds now; solve first");
-    if (s->dense) for (int k : s->h_kind) if (k >= 2)
+    for (int k = 0; k < s->Nn; k++) if (s->sk.kind(k) >= 2)
         return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the tree has nodes of kind 2 or 3: Pd need not belong to the final working set after a line search's last trial");
     return TQGPU_OK;
 }
@@ -460,12 +460,11 @@ extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgp
  * caller's parameter groups, back through pinned memory in one copy with one wait ---- */
 namespace {
 constexpr int ADJMAT_REGIONS = 7;          /* gH, gh, gA, gB, gb, gA0, gS0 */
-int adjmat_kind(const tqgpu_solver *s, int k) { return s->dense && !s->h_kind.empty() ? s->h_kind[(size_t)k] : 0; }
 bool adjmat_root(const tqgpu_solver *s) { return s->mpc.d && !s->mpc.states && s->mpc.nx0 > 0; }
 /* what the tables depend on beyond the maps: every node's kind, the root form, nx0 */
 std::vector<int> adjmat_sig(const tqgpu_solver *s) {
     std::vector<int> sig((size_t)s->Nn + 2);
-    for (int k = 0; k < s->Nn; k++) sig[(size_t)k] = adjmat_kind(s, k);
+    for (int k = 0; k < s->Nn; k++) sig[(size_t)k] = s->sk.kind(k);
     sig[(size_t)s->Nn] = adjmat_root(s) ? 1 : 0; sig[(size_t)s->Nn + 1] = s->mpc.nx0;
     return sig;
 }
@@ -481,9 +480,9 @@ int adjmat_build(tqgpu_solver *s, const char *who) {
         if (m.hgroup[(size_t)k] >= 0) hm[(size_t)m.hgroup[(size_t)k]].push_back(k);
         if (m.cgroup[(size_t)k] >= 0) cm[(size_t)m.cgroup[(size_t)k]].push_back(k);
     }
-    for (int g = 0; g < m.n_h; g++) for (int k : hm[(size_t)g]) if (adjmat_kind(s, k) != adjmat_kind(s, hm[(size_t)g][0]))
-        return fail(TQGPU_EINVAL, std::string(who) + ": h-group " + std::to_string(g) + " has come to mix kinds: node " + std::to_string(k) + " is of kind " + std::to_string(adjmat_kind(s, k)) +
-                                  ", node " + std::to_string(hm[(size_t)g][0]) + " of kind " + std::to_string(adjmat_kind(s, hm[(size_t)g][0])));
+    for (int g = 0; g < m.n_h; g++) for (int k : hm[(size_t)g]) if (s->sk.kind(k) != s->sk.kind(hm[(size_t)g][0]))
+        return fail(TQGPU_EINVAL, std::string(who) + ": h-group " + std::to_string(g) + " has come to mix kinds: node " + std::to_string(k) + " is of kind " + std::to_string(s->sk.kind(k)) +
+                                  ", node " + std::to_string(hm[(size_t)g][0]) + " of kind " + std::to_string(s->sk.kind(hm[(size_t)g][0])));
     const int root = adjmat_root(s) ? 1 : 0;
     std::vector<int> hmem, cmem, hgrp((size_t)m.n_h * 8, 0), cgrp((size_t)m.n_c * 8, 0), hchk, cchk, sums;
     size_t tot[ADJMAT_REGIONS] = {}, part = 0, lds = 0;
@@ -494,7 +493,7 @@ int adjmat_build(tqgpu_solver *s, const char *who) {
     };
     for (int g = 0; g < m.n_h; g++) {
         const std::vector<int> &v = hm[(size_t)g];
-        const size_t nz = (size_t)(s->nx[(size_t)v[0]] + s->nu[(size_t)v[0]]), hsz = adjmat_kind(s, v[0]) ? nz * nz : nz;
+        const size_t nz = (size_t)(s->nx[(size_t)v[0]] + s->nu[(size_t)v[0]]), hsz = s->sk.kind(v[0]) ? nz * nz : nz;
         int *rec = &hgrp[(size_t)g * 8];
         rec[0] = v[0]; rec[1] = (int)tot[0]; rec[2] = (int)tot[1]; rec[4] = (int)(hchk.size() / 4);
         rec[5] = chunks(hchk, g, (int)hmem.size(), (int)v.size()); rec[6] = (int)part;
@@ -709,7 +708,7 @@ extern "C" int tqgpu_mpc_get_param_groups(tqgpu_solver *s, int *n_hgroups, int *
     if (hdims) for (int g = 0; g < m.n_h; g++) {
         memcpy(hdims + 5 * (size_t)g, &m.hdims[4 * (size_t)g], sizeof(int) * 4);
         const int first = (int)(std::find(m.hgroup.begin(), m.hgroup.end(), g) - m.hgroup.begin());
-        hdims[5 * (size_t)g + 4] = adjmat_kind(s, first);
+        hdims[5 * (size_t)g + 4] = s->sk.kind(first);
     }
     if (cdims && !m.cdims.empty()) memcpy(cdims, m.cdims.data(), sizeof(int) * m.cdims.size());
     if (root) { root[0] = adjmat_root(s) ? s->mpc.nb : 0; root[1] = s->nu[0]; root[2] = s->mpc.nx0; root[3] = s->sens.adj_valid ? s->sens.nw : 0; }

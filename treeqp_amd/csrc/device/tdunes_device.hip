@@ -33,6 +33,8 @@
  * three launches per Newton iteration), tdunes_gpersist.hpp (small trees of any shape: one workgroup per tree).  The MPC family (tqgpu_mpc_*),
  * kernels and entry points, is tdunes_mpc.hpp, and the host side of a step's sensitivities and adjoints tdunes_adjoint.hpp, both included into
  * the host part; this file keeps the mirror's records for them, MpcStats, MpcPre, and the plan the batched after-solve calls share (DeviceGroup ..).
+ * What problem a mirror holds and which stage solver each node runs (the setters and getters of the problem's data, tqgpu_set_problem) is
+ * tdunes_problem.hpp, included into the host part ahead of the solve; this file keeps its records StageKinds, GenRows, DenseSingle.
  */
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -964,13 +966,13 @@ __global__ void __launch_bounds__(WAVE) k_stage(Tree T, Data D, int mode, int h,
     if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
     stage_body(T, D, mode, blockIdx.x, threadIdx.x, lds);
 }
-/* k_stage for trees with dense box nodes (kind 2): the same sweep with stage_box compiled in (its LDS, s->lds_box, only here) */
+/* k_stage for trees with dense box nodes (kind 2): the same sweep with stage_box compiled in (its LDS, s->sk.lds_box, only here) */
 __global__ void __launch_bounds__(WAVE) k_stage_box(Tree T, Data D, int mode, int h, int t) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
     stage_body<1>(T, D, mode, blockIdx.x, threadIdx.x, lds);
 }
-/* k_stage for trees with kind-3 nodes: the same sweep with stage_gen compiled in as well (its LDS, s->lds_gen, only here) */
+/* k_stage for trees with kind-3 nodes: the same sweep with stage_gen compiled in as well (its LDS, s->sk.lds_gen, only here) */
 __global__ void __launch_bounds__(WAVE) k_stage_gen(Tree T, Data D, int mode, int h, int t) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (mode == 1 && !phase_trial(D.ctrl, h, t)) return;
@@ -1952,6 +1954,44 @@ struct PersistShard {
     unsigned long long *h_peers[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* slabs of all ranks (a mirror that is not sharded: its own, eight times) ... */
     unsigned long long **d_peers = nullptr;                                                               /* ... and the device copy of the table the kernel reads */
 };
+/* ---- what problem the mirror holds and which stage solver each node runs (tdunes_problem.hpp): StageKinds, GenRows, DenseSingle ---- */
+/* the stage solvers selected (tqgpu_set_objective_mixed; tqgpu_set_objective_diag and tqgpu_set_problem return to clipping): dense, some nodes
+ * use a dense stage solver (generic path only); box, some of them have box bounds (kind 2): the stage sweep is k_stage_box with lds_box bytes;
+ * gen, some have general constraints as well (kind 3): k_stage_gen with lds_gen bytes; lds_dense: k_dense_init's */
+struct StageKinds {
+    bool dense = false, need_dense_init = false, box = false, gen = false;
+    size_t lds_dense = 0, lds_box = 0, lds_gen = 0;
+    std::vector<int> h_kind;     /* the kinds last set, as the device has them: a kind-3 node without rows is a kind-2 node */
+    std::vector<int> h_kind_req; /* ... as the caller gave them */
+    std::vector<double> h_bounds; /* the bounds last set by tqgpu_set_bounds (device layout: xmin | xmax | umin | umax); empty: unknown */
+    double *d_Hd = nullptr; int *d_kind = nullptr;      /* writable aliases of Data.Hd, Data.kind */
+    int kind(int k) const { return dense && !h_kind.empty() ? h_kind[(size_t)k] : 0; }      /* of node k; 0 (clipping) unless the mirror is dense */
+    bool working_sets(size_t Nn) const { return dense && (box || gen) && h_kind.size() == Nn; }      /* the mirror has stored working sets (kinds 2, 3) */
+};
+/* general constraints (tqgpu_set_constraints): rows per node, their offsets and those of the blocks of Gt, host copies of dmin | dmax, the
+ * device blocks and the record Data.gen points to */
+struct GenRows {
+    std::vector<int> nc, roff, goff;
+    std::vector<double> h_drange; int sum_nc = 0;
+    int *d_tab = nullptr;        /* Gen::nc, roff, goff */
+    double *d_Gt = nullptr, *d_drange = nullptr, *d_mu = nullptr;
+    unsigned long long *d_rmask = nullptr;     /* 4 Nn words: Gen::rmask (2 Nn), Gen::sides (2 Nn) */
+    long *d_steps = nullptr;     /* Gen::steps_total (Nn longs), then Gen::steps_last (Nn ints) */
+    bool hot = true;             /* stage_gen starts from the stored working sets (tqgpu_set_gen_hot_start) */
+    Gen h_gen{};                 /* what d_gen holds: the views of the blocks above are taken from it */
+    Gen *d_gen = nullptr;
+    unsigned long long *row_sides(size_t Nn) const { return d_rmask + 3 * Nn; }      /* the second half of h_gen.sides: the sides of the rows */
+};
+/* the single-workgroup solve of a dense tree (g_persist_dense, opt-in): the caller's two choices, then the plan of plan_dense_single for the
+ * kinds and rows last set */
+struct DenseSingle {
+    bool single = false;         /* tqgpu_set_dense_single_launch, TREEQP_AMD_DENSE_SINGLE_LAUNCH=1 */
+    bool batch = false;          /* ... for the members of a batch: one launch of g_persist_dense_batch, a workgroup per tree (tqgpu_set_dense_batch_launch, TREEQP_AMD_DENSE_BATCH_LAUNCH=1); independent of single */
+    bool ok = false;             /* the tree with its current kinds and rows fits */
+    int stage_waves = 0, phase_waves = 0;      /* waves of the stage sweep (0: does not fit), of the sweeps over blocks (GPD_WAVES unless that many windows of lds_gp_wave doubles do not fit) */
+    size_t win_stage = 0, win_region = 0, lds_total = 0;      /* doubles: a stage window, the window region; bytes of dynamic LDS of g_persist_dense */
+    bool in_lds = false, const_in_lds = false, tab_in_lds = false;
+};
 
 struct tqgpu_solver {
     Owned mem;
@@ -1960,7 +2000,7 @@ struct tqgpu_solver {
     int Nn = 0, Np = 0, Nh = 0;
     std::vector<int> nk, nx, nu, dad, stage, kid0, xoff, uoff, aoff, boff, pos, bdim, woff, utoff, lvl_first;
     int sum_nx = 0, sum_nu = 0, sum_lam = 0, sum_A = 0, sum_B = 0, sum_W = 0, sum_Ut = 0, nx0 = 0, nxmax = 0;
-    size_t lds_stage = 0, lds_hess = 0, lds_factor = 0, lds_forward = 0, lds_dense = 0;
+    size_t lds_stage = 0, lds_hess = 0, lds_factor = 0, lds_forward = 0;
     bool wide = false;              /* larger blocks (16 < d <= 64): workgroup-per-block MFMA kernels (tdunes_wide.hpp) */
     bool wide_small = false;        /* ... taken by a tree of small blocks (d <= 16) too wide for the single-workgroup kernel */
     size_t lds_hess_w = 0, lds_factor_w = 0, lds_forward_w = 0;
@@ -1993,27 +2033,7 @@ struct tqgpu_solver {
     bool w3_post_next = false;          /* the next launch of k_sg / k_sgp is the last of what the host enqueues before it reads the verdict: it posts */
     bool w3_seen = false;               /* the last read of the control block came through the result block */
     std::vector<int> ls_pred;           /* trials per iteration of the previous solve: that many trial launches are enqueued behind an iteration's forward sweep (a trial beyond the accepted one is a no-op; a read-back per extra trial is 20 us) */
-    bool dense = false, need_dense_init = false;   /* dense unconstrained stage solver selected (generic path only) */
-    bool box = false;            /* some dense nodes have box bounds (kind 2): the stage sweep is k_stage_box with lds_box bytes */
-    size_t lds_box = 0;
-    bool gen = false;            /* some dense nodes have general constraints as well (kind 3): the stage sweep is k_stage_gen with lds_gen bytes */
-    size_t lds_gen = 0;
-    std::vector<int> h_kind;     /* the kinds last set (tqgpu_set_objective_mixed), as the device has them: a kind-3 node without rows is a kind-2 node */
-    std::vector<int> h_kind_req; /* ... as the caller gave them */
-    /* general constraints (tqgpu_set_constraints): rows per node, offsets, host copies of dmin | dmax, the device arrays and the record Data.gen points to */
-    std::vector<int> gnc, groff, ggoff;
-    std::vector<double> h_drange;
-    int sum_nc = 0;
-    int *d_gtab = nullptr;
-    double *d_Gt = nullptr, *d_drange = nullptr, *d_gmu = nullptr;
-    unsigned long long *d_rmask = nullptr;     /* 4 Nn words: Gen::rmask (2 Nn), Gen::sides (2 Nn) */
-    long *d_gsteps = nullptr;    /* Gen::steps_total (Nn longs), then Gen::steps_last (Nn ints) */
-    bool gen_hot = true;         /* stage_gen starts from the stored working sets (tqgpu_set_gen_hot_start) */
-    Gen h_gen{};                 /* what d_gen holds */
-    Gen *d_gen = nullptr;
-    std::vector<double> h_bounds; /* the bounds last set by tqgpu_set_bounds (device layout: xmin | xmax | umin | umax); empty: unknown */
-    double *d_Hd = nullptr;      /* writable alias of Data.Hd */
-    int *d_kind = nullptr;       /* writable alias of Data.kind */
+    StageKinds sk; GenRows rows; DenseSingle gpd;      /* what problem the mirror holds and which stage solver each node runs (tdunes_problem.hpp) */
     std::vector<int> poff;
     int use_fast_orig = 1;
     void *slab = nullptr;
@@ -2035,15 +2055,6 @@ struct tqgpu_solver {
     bool persist_one = false;          /* the persistent launch of this tree takes the one-workgroup-per-CU build */
     bool in_batch = false;             /* inside tqgpu_solve_batch: members launched one by one run side by side, two workgroups to a CU -- not with that build */
     bool gp_in_lds = false, gp_const_in_lds = false, gp_tab_in_lds = false, gp_small16 = false, gp_small8 = false;
-    /* the single-workgroup solve of a dense tree (g_persist_dense, opt-in): the plan of plan_dense_single for the kinds and rows last set */
-    bool dense_single = false;      /* the caller's choice (tqgpu_set_dense_single_launch, TREEQP_AMD_DENSE_SINGLE_LAUNCH=1) */
-    bool dense_batch = false;       /* ... for the members of a batch: one launch of g_persist_dense_batch, a workgroup per tree (tqgpu_set_dense_batch_launch, TREEQP_AMD_DENSE_BATCH_LAUNCH=1); independent of dense_single */
-    bool dense_gp_ok = false;       /* the tree with its current kinds and rows fits */
-    int dense_stage_waves = 0;      /* waves of the stage sweep (0: does not fit) */
-    int dense_phase_waves = 0;      /* waves of the sweeps over blocks (GPD_WAVES unless that many windows of lds_gp_wave doubles do not fit) */
-    size_t dense_win_stage = 0, dense_win_region = 0;      /* doubles: a stage window, the window region */
-    size_t lds_gpd_total = 0;       /* bytes of dynamic LDS of g_persist_dense */
-    bool gpd_in_lds = false, gpd_const_in_lds = false, gpd_tab_in_lds = false;
     double *pab = nullptr, *pcst = nullptr;
     bool need_pack = true;          /* QP data changed since the constants were packed */
     /* writable aliases of the const inputs */
@@ -2424,8 +2435,8 @@ static W3 next_w3(tqgpu_solver *s) {
  * and dense unconstrained): the one place that picks among the three */
 static void launch_stage_sweep(tqgpu_solver *s, int mode, int h, int t) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
-    if (s->gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->lds_gen, st, T, D, mode, h, t);
-    else if (s->box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->lds_box, st, T, D, mode, h, t);
+    if (s->sk.gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->sk.lds_gen, st, T, D, mode, h, t);
+    else if (s->sk.box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->sk.lds_box, st, T, D, mode, h, t);
     else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, mode, h, t);
 }
 static void launch_sg(tqgpu_solver *s, const Opts &O, int mode, int h, int t, bool fresh = false) {
@@ -2742,7 +2753,7 @@ void launch_phase_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches
         }
     }
     if (!(parts & 2)) return;
-    const bool wide = s->wide && !s->dense;
+    const bool wide = s->wide && !s->sk.dense;
     bool ls_begun = false;           /* the forward sweep's last workgroup has done k_ls_begin's work */
     if (wide) hipLaunchKernelGGL(k_hess_w, dim3(T.Np), dim3(WT), s->lds_hess_w, st, T, D, h);
     else hipLaunchKernelGGL(k_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, st, T, D, h);
@@ -2841,8 +2852,8 @@ int detect_shape(tqgpu_solver *s) {
         else { s->nx[0] = 0; s->fast = -1; s->mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
     }
     if (s->sw.generic) { s->use_fast = 0; s->use_gpersist = 0; }
-    s->dense_single = s->sw.dense_single;
-    s->dense_batch = s->sw.dense_batch;
+    s->gpd.single = s->sw.dense_single;
+    s->gpd.batch = s->sw.dense_batch;
     if (s->sw.tiered) s->use_persist = 0;
     /* reference-order sums (strict_sum / strict_block_dots): the launch-per-phase kernels and the single-workgroup kernel carry them;
      * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
@@ -2945,7 +2956,7 @@ int layout_slab(tqgpu_solver *s) {
     D.stamps = at<unsigned long long>(base, o_stamps);
     D.ctrl = at<Ctrl>(base, o_ctrl); D.ls_log = at<int>(base, o_log); D.ls_log_cap = s->ls_log_cap;
     D.strict = s->strict_sum ? 1 : 0;
-    D.dense = 0; s->d_kind = at<int>(base, o_kind); D.kind = s->d_kind; s->d_Hd = at<double>(base, o_Hd); D.Hd = s->d_Hd; D.Pd = at<double>(base, o_Pd); D.poff = at<int>(base, o_poff);
+    D.dense = 0; s->sk.d_kind = at<int>(base, o_kind); D.kind = s->sk.d_kind; s->sk.d_Hd = at<double>(base, o_Hd); D.Hd = s->sk.d_Hd; D.Pd = at<double>(base, o_Pd); D.poff = at<int>(base, o_poff);
     D.bmask = at<unsigned long long>(base, o_bmask); D.xpad = s->x_pad;
     s->use_fast_orig = s->use_fast;
     s->d_mu_x = at<double>(base, o_mux); s->d_mu_u = at<double>(base, o_muu);
@@ -3053,7 +3064,7 @@ int setup_single_wg(tqgpu_solver *s) {
     {
         /* four nodes per wave in the stage sweep: nx + nu <= 16 everywhere, clipping nodes only, and a quarter of the wave's window
          * holds a node's duals (bdim + nx doubles) */
-        bool ok16 = !s->dense && !s->sw.no_stage16;
+        bool ok16 = !s->sk.dense && !s->sw.no_stage16;
         for (int k = 0; k < s->Nn && ok16; k++) ok16 = s->nx[k] + s->nu[k] <= 16 && (size_t)(s->bdim[k] + s->nx[k]) <= per_wave / 4;
         s->gp_small16 = ok16;
         bool ok8 = !s->sw.no_stage16 && !s->strict_sum;          /* eight nodes per wave in the gradient sweep: nx <= 8 everywhere */
@@ -3096,7 +3107,7 @@ int setup_single_wg(tqgpu_solver *s) {
         for (int lvl = 0; lvl <= s->Nh; lvl++) {
             int grp = 1;
             const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-            if (!s->sw.gp_no_groups && lvl >= 1 && lvl < s->Nh && count > GP_WAVES && !s->dense) {
+            if (!s->sw.gp_no_groups && lvl >= 1 && lvl < s->Nh && count > GP_WAVES && !s->sk.dense) {
                 const int d0 = s->bdim[first], n0 = s->nx[first], u0 = s->nu[first], c0 = s->nk[first];
                 bool same = true;
                 for (int k = first; k < first + count && same; k++) {
@@ -3171,7 +3182,7 @@ static bool tiered_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->us
 static bool uses_gpersist(const tqgpu_solver *s, bool batch) {
     /* a dense tree: only on request, only where plan_dense_single found room; alone and as a member of a batch are two requests
      * (g_persist_dense, g_persist_dense_batch) */
-    if (s->dense) return (batch ? s->dense_batch : s->dense_single) && s->dense_gp_ok && s->use_gpersist && !s->shard.on;
+    if (s->sk.dense) return (batch ? s->gpd.batch : s->gpd.single) && s->gpd.ok && s->use_gpersist && !s->shard.on;
     return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->shard.on && !persist_capable(s) && !tiered_capable(s);
 }
 /* the first route that the mirror and the options admit (batch_member: see uses_gpersist) */
@@ -3180,8 +3191,8 @@ static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_mem
     if (persist_capable(s) && p == 0 && m > 0) return Route::PERSIST;
     if (uses_gpersist(s, batch_member) && p == 0 && m > 0) return Route::SINGLE_WG;
     if (tiered_capable(s) && p < 3) return Route::TIERED;
-    if (s->w3_ok && !s->dense && p < 3 && !s->shard.on) return Route::THREE_LAUNCH;
-    if (s->fuse_ok && p < 3 && !s->shard.on && !s->box && !s->gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
+    if (s->w3_ok && !s->sk.dense && p < 3 && !s->shard.on) return Route::THREE_LAUNCH;
+    if (s->fuse_ok && p < 3 && !s->shard.on && !s->sk.box && !s->sk.gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
     return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
 /* the kernel variants the steps of tqgpu_create (setup_per_phase, setup_wide3, setup_persist, setup_single_wg) and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
@@ -3190,8 +3201,8 @@ extern "C" int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     const bool bits[] = {s->wide, s->wide_small, s->w3_ok, s->w3_sgp, s->w3_merge, s->d_anc != nullptr, s->fuse_ok, s->persist_ok,
                          s->persist_one, s->gpersist_ok, s->gp_in_lds, s->gp_const_in_lds, s->gp_tab_in_lds, s->gp_small16, s->gp_small8,
-                         s->dense, s->box, s->solve_no > 0 && s->route == Route::SINGLE_WG, s->gen,
-                         s->dense && s->dense_single && s->dense_gp_ok};
+                         s->sk.dense, s->sk.box, s->solve_no > 0 && s->route == Route::SINGLE_WG, s->sk.gen,
+                         s->sk.dense && s->gpd.single && s->gpd.ok};
     unsigned f = 0;
     for (unsigned i = 0; i < sizeof(bits) / sizeof(bits[0]); i++) f |= bits[i] ? 1u << i : 0u;
     if (flags) *flags = f;
@@ -3203,39 +3214,6 @@ extern "C" int tqgpu_uses_fused_path(const tqgpu_solver *s) {
     tqgpu_opts o{}; o.maxIter = 1;          /* the route under default options */
     const Route r = route_of(s, &o, false);
     return r == Route::PERSIST ? 2 : r == Route::TIERED ? 1 : r == Route::SINGLE_WG ? 3 : 0;
-}
-
-/* opt-in: a dense tree (kinds 1 / 2 / 3) that fits runs its whole solve as one launch of one workgroup (g_persist_dense).  The stored working
- * sets are shared between the routes: switching between two solves needs no reset. */
-extern "C" int tqgpu_set_dense_single_launch(tqgpu_solver *s, int on) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    s->dense_single = on != 0;
-    return TQGPU_OK;
-}
-extern "C" int tqgpu_get_dense_single_launch(const tqgpu_solver *s, int *on, int *eligible, int *stage_waves) {
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    const bool ok = s->dense && s->dense_gp_ok;
-    if (on) *on = s->dense_single ? 1 : 0;
-    if (eligible) *eligible = ok ? 1 : 0;
-    if (stage_waves) *stage_waves = ok ? s->dense_stage_waves : 0;
-    return TQGPU_OK;
-}
-
-/* opt-in: dense trees that fit go out of tqgpu_solve_batch together, as ONE launch with a workgroup per tree (g_persist_dense_batch), where
- * each would otherwise run the launch-per-phase route on its own, one after the other.  Says nothing about the mirror solved alone, and
- * tqgpu_set_dense_single_launch says nothing about batches.  The stored working sets are shared between the routes, as there. */
-extern "C" int tqgpu_set_dense_batch_launch(tqgpu_solver *s, int on) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    s->dense_batch = on != 0;
-    return TQGPU_OK;
-}
-extern "C" int tqgpu_get_dense_batch_launch(const tqgpu_solver *s, int *on, int *eligible) {
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    if (on) *on = s->dense_batch ? 1 : 0;
-    if (eligible) *eligible = s->dense && s->dense_gp_ok ? 1 : 0;
-    return TQGPU_OK;
 }
 
 /* the options as the kernels take them; TREEQP_AMD_STAMPS is for the caller to set */
@@ -3271,457 +3249,7 @@ extern "C" int tqgpu_get_stamps(tqgpu_solver *s, unsigned long long *out, int ca
     return TQGPU_OK;
 }
 
-extern "C" int tqgpu_dims(const tqgpu_solver *s, int *sum_nx, int *sum_nu, int *sum_lam, int *sum_A, int *sum_B) {
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    if (sum_nx) *sum_nx = s->sum_nx - s->x_pad;
-    if (sum_nu) *sum_nu = s->sum_nu;
-    if (sum_lam) *sum_lam = s->sum_lam;
-    if (sum_A) *sum_A = s->sum_A - s->A_pad;
-    if (sum_B) *sum_B = s->sum_B;
-    return TQGPU_OK;
-}
-
-/* THE statement of what a change of the problem's data on the device makes stale: the pinned mirror of tqgpu_set_problem's inputs, a stored
- * sensitivity and the pairing of the last solve's point with the data; repack: the packed constants of the persistent route as well */
-static void problem_changed(tqgpu_solver *s, bool repack) {
-    s->in_valid = false;
-    s->sens.invalidate(); s->sens.dirty = true; if (repack) s->need_pack = true;
-}
-
-#define H2D(dst, src, count)                                                                                   \
-    do {                                                                                                       \
-        if ((src) && (count) > 0)                                                                              \
-            HIP_TRY(hipMemcpyAsync((dst), (src), sizeof(double) * (size_t)(count), hipMemcpyHostToDevice, s->stream)); \
-    } while (0)
-
-extern "C" int tqgpu_set_dynamics(tqgpu_solver *s, const double *A, const double *B, const double *b) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    problem_changed(s, true);
-    H2D(s->A + s->A_pad, A, s->sum_A - s->A_pad); H2D(s->B, B, s->sum_B);
-    H2D(s->b + s->nx0, b, s->sum_lam);              /* node-indexed on the device: root slot unused */
-    HIP_TRY(hipStreamSynchronize(s->stream));       /* the caller may reuse its buffers */
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_set_objective_diag(tqgpu_solver *s, const double *Qd, const double *Rd, const double *q, const double *r) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    problem_changed(s, true);
-    H2D(s->Qd + s->x_pad, Qd, s->sum_nx - s->x_pad); H2D(s->Rd, Rd, s->sum_nu); H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->need_init = true;
-    if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; }
-    return TQGPU_OK;
-}
-
-/* The linear terms alone, in the layout of tqgpu_set_objective_diag (either may be NULL: left alone): q and r are uploaded and the persistent
- * route packs them again; the kinds, H, the factors of k_init / k_dense_init and the stored working sets of kinds 2 and 3 stay. */
-extern "C" int tqgpu_set_linear_terms(tqgpu_solver *s, const double *q, const double *r) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "tqgpu_set_linear_terms: null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    problem_changed(s, true);
-    H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-extern "C" int tqgpu_get_linear_terms(tqgpu_solver *s, double *q, double *r) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "tqgpu_get_linear_terms: null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    const int nxe = s->sum_nx - s->x_pad;
-    if (q && nxe > 0) HIP_TRY(hipMemcpy(q, s->q + s->x_pad, sizeof(double) * (size_t)nxe, hipMemcpyDeviceToHost));
-    if (r && s->sum_nu > 0) HIP_TRY(hipMemcpy(r, s->r, sizeof(double) * (size_t)s->sum_nu, hipMemcpyDeviceToHost));
-    return TQGPU_OK;
-}
-
-/* Dense objective for the dense UNCONSTRAINED stage solver (the reference's qpOASES stage backend restricted
- * to nodes without bounds, dual_Newton_tree_qpoases.c:153-217,401-476).  Flat layout of
- * tree_qp_in_set_ltv_objective_colmajor (tree_qp_common.c): per node Q (nx x nx), R (nu x nu), S (nu x nx),
- * all column major, then q, r.  Selects the generic device path; tqgpu_set_objective_diag selects clipping again. */
-extern "C" int tqgpu_set_objective_dense(tqgpu_solver *s, const double *Q, const double *R, const double *S, const double *q, const double *r) {
-    SETTLE(s);
-    return tqgpu_set_objective_mixed(s, nullptr, Q, R, S, q, r);
-}
-
-/* The same with a per-node choice of the stage solver (opts->qp_solver[] of the reference, dual_Newton_tree.c:124-162):
- * kind[k] = 0: clipping (the diagonals of Q_k, R_k are its weights; their off-diagonals and S_k must be zero), 1: dense
- * unconstrained, 2: dense with the box bounds of tqgpu_set_bounds (stage_box; nx + nu <= 64).  kind == NULL: every node
- * dense unconstrained. */
-namespace {
-/* lb <= ub on every entry of every box node (the phantom root states are not the caller's) */
-int check_box_bounds(const tqgpu_solver *s) {
-    if (!(s->box || s->gen) || s->h_bounds.empty()) return TQGPU_OK;
-    const double *xl = s->h_bounds.data(), *xu = xl + s->sum_nx, *ul = xu + s->sum_nx, *uu = ul + s->sum_nu;
-    for (int k = 0; k < s->Nn; k++) {
-        if (s->h_kind[(size_t)k] < 2) continue;
-        for (int i = (k == 0 ? s->x_pad : 0); i < s->nx[k]; i++)
-            if (!(xl[s->xoff[k] + i] <= xu[s->xoff[k] + i])) return fail(TQGPU_EINVAL, "box node " + std::to_string(k) + ": xmin > xmax");
-        for (int i = 0; i < s->nu[k]; i++)
-            if (!(ul[s->uoff[k] + i] <= uu[s->uoff[k] + i])) return fail(TQGPU_EINVAL, "box node " + std::to_string(k) + ": umin > umax");
-    }
-    return TQGPU_OK;
-}
-/* The kinds the caller asked for become the kinds of the device (a kind-3 node that has no rows is a kind-2 node), with the LDS of
- * the sweeps that serve them.  On failure nothing has changed. */
-int apply_kinds(tqgpu_solver *s, const std::vector<int> &req) {
-    std::vector<int> kd = req;
-    size_t lds_box = 0, lds_gen = 0;
-    for (int k = 0; k < s->Nn; k++) {
-        if (kd[(size_t)k] < 2) continue;
-        const size_t nz = (size_t)s->nx[k] + s->nu[k], nc = s->gnc.empty() ? 0 : (size_t)s->gnc[(size_t)k];
-        if (nz > WAVE) return fail(TQGPU_EUNSUPPORTED, "box node " + std::to_string(k) + ": nx + nu = " + std::to_string(nz) + " > 64 (one wave, one entry per lane)");
-        if (kd[(size_t)k] == 3 && (nc == 0 || nz == 0)) kd[(size_t)k] = 2;
-        const size_t head = (size_t)s->bdim[k] + s->nx[k] + 2 * nz + 2;
-        if (kd[(size_t)k] == 2) lds_box = std::max(lds_box, (head + 2 * nz * nz) * sizeof(double));
-        else lds_gen = std::max(lds_gen, (head + nc + 2 * nz * nz + nz * nc + nc * nc) * sizeof(double));
-    }
-    const bool box_was = s->box, gen_was = s->gen;
-    const std::vector<int> kind_was = s->h_kind;
-    s->box = lds_box > 0; s->gen = lds_gen > 0; s->h_kind = kd;
-    int rc = check_box_bounds(s);
-    if (rc == TQGPU_OK && s->gen) rc = allow_lds(k_stage_gen, std::max(std::max(s->lds_stage, lds_box), lds_gen));
-    else if (rc == TQGPU_OK && s->box) rc = allow_lds(k_stage_box, std::max(s->lds_stage, lds_box));
-    if (rc != TQGPU_OK) { s->box = box_was; s->gen = gen_was; s->h_kind = kind_was; return rc; }
-    s->lds_box = std::max(s->lds_stage, lds_box);
-    s->lds_gen = std::max(s->lds_box, lds_gen);
-    s->h_kind_req = req;
-    return TQGPU_OK;
-}
-/* The LDS plan of g_persist_dense for the kinds and rows the mirror has now (they decide the stage windows, so this runs where they are
- * set, not at creation).  The window region holds GPD_WAVES windows of the other phases (lds_gp_wave doubles each; fewer waves take
- * blocks where that many do not fit: the Hessian window of a node with nz = 64 and 40 child states is 40 KiB) or, overlaid,
- * stage_waves windows of the tree's largest stage need (lds_stage / lds_box / lds_gen); behind it the index tables and, while they
- * fit, the state mirror and the constants, as in setup_single_wg.  stage_waves is the largest count <= GPD_WAVES for which the total
- * stays within setup_single_wg's 150 KiB; 0 (or a size the runtime refuses): not eligible. */
-void plan_dense_single(tqgpu_solver *s) {
-    s->dense_gp_ok = false; s->dense_stage_waves = 0; s->dense_phase_waves = 0; s->lds_gpd_total = 0; s->gpd_in_lds = s->gpd_const_in_lds = s->gpd_tab_in_lds = false;
-    if (!s->dense) return;
-    constexpr size_t budget = 150 * 1024;
-    int widest = 0;
-    for (int l = 0; l <= s->Nh; l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
-    const size_t per_wave = s->lds_gp_wave;
-    if (widest > 6 * GP_WAVES) return;      /* the width test of setup_single_wg */
-    /* the level table (setup_single_wg uploads it only for trees g_persist takes; the dense kernel reads the first nodes of the levels, never the groups) */
-    if (!s->d_lvl_first && s->mem.upload(s->d_lvl_first, s->lvl_first.data(), sizeof(int) * s->lvl_first.size(), TQGPU_ENOMEM, "the level table") != TQGPU_OK) return;
-    const size_t win = ((s->gen ? s->lds_gen : s->box ? s->lds_box : s->lds_stage) + 15) / 16 * 2;      /* doubles, even: the windows stay 16-byte aligned */
-    auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
-    const size_t sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
-    const size_t mirror = 11 * ev(sx) + 5 * ev(su) + 2 * ev((size_t)s->sum_W) + 2 * ev((size_t)s->sum_Ut) + 2 * ev((size_t)s->Nn) + ev(sx + s->Nn + 1);
-    const size_t tables = (13 * ((size_t)s->Nn + 3)) / 2 + 16;
-    const size_t consts = ev((size_t)s->sum_A) + ev((size_t)s->sum_B) + 5 * ev(sx) + 4 * ev(su);
-    int sw = 0, pw = 0;
-    for (int w = GPD_WAVES; w >= 1 && !pw; w--) if ((per_wave * w + tables + 8) * 8 <= budget) pw = w;
-    for (int w = GPD_WAVES; w >= 1 && !sw; w--) if ((win * w + tables + 8) * 8 <= budget) sw = w;
-    if (!sw || !pw) return;
-    const size_t region = std::max(per_wave * (size_t)pw, win * (size_t)sw);
-    size_t total = (region + tables + 8) * 8;
-    s->gpd_tab_in_lds = true;
-    if (total + mirror * 8 <= budget) { s->gpd_in_lds = true; total += mirror * 8; }
-    if (s->gpd_in_lds && total + consts * 8 <= budget) { s->gpd_const_in_lds = true; total += consts * 8; }
-    if (total > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist_dense), hipFuncAttributeMaxDynamicSharedMemorySize, (int)total) != hipSuccess) {
-        (void)hipGetLastError();
-        s->gpd_in_lds = s->gpd_const_in_lds = s->gpd_tab_in_lds = false;
-        return;
-    }
-    s->dense_stage_waves = sw; s->dense_phase_waves = pw; s->dense_win_stage = win; s->dense_win_region = region; s->lds_gpd_total = total;
-    s->dense_gp_ok = true;
-}
-}  // namespace
-
-extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const double *Q, const double *R, const double *S, const double *q, const double *r) {
-    SETTLE(s);
-    if (!s || !Q || !q) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: bad arguments");
-    if (s->shard.on) return fail(TQGPU_EINVAL, "the dense stage solver is not available in sharded mode");
-    HIP_TRY(hipSetDevice(s->device));
-    std::vector<double> H((size_t)std::max(s->poff[s->Nn], 1), 0.0);
-    std::vector<double> Qd((size_t)std::max(s->sum_nx, 1), 0.0), Rd((size_t)std::max(s->sum_nu, 1), 0.0);
-    std::vector<int> kd((size_t)s->Nn, 1);
-    int rc0 = TQGPU_OK;
-    if (kind) for (int k = 0; k < s->Nn; k++) {
-        if (kind[k] < 0 || kind[k] > 3) return fail(TQGPU_EINVAL, "tqgpu_set_objective_mixed: kind must be 0, 1, 2 or 3");
-        kd[(size_t)k] = kind[k];
-    }
-    size_t lds_dense = 0;
-    for (int k = 0; k < s->Nn; k++) {
-        /* k_dense_init holds a dense node's H (nz x nz) and its pivots in LDS */
-        const size_t nzd = (size_t)s->nx[k] + s->nu[k];
-        if (kd[(size_t)k]) lds_dense = std::max(lds_dense, (nzd * (nzd + 1) + 2) * sizeof(double));
-    }
-    if (lds_dense > 160 * 1024) return fail(TQGPU_EUNSUPPORTED, "dense node too large for the LDS-resident factorization of H (160 KiB per workgroup)");
-    if ((rc0 = allow_lds(k_dense_init, lds_dense))) return rc0;
-    const int rc = apply_kinds(s, kd);
-    if (rc != TQGPU_OK) return rc;
-    size_t oq = 0, orr = 0, os = 0;
-    for (int k = 0; k < s->Nn; k++) {
-        const int nu = s->nu[k], nz = s->nx[k] + nu;
-        double *Hk = H.data() + s->poff[k];
-        if (!kd[(size_t)k]) {
-            /* clipping node: diagonal weights (phantom root states of an embedded x0-eliminated tree keep their unit weight) */
-            const int nxc = s->nx[k] - ((k == 0) ? s->x_pad : 0);
-            for (int i = 0; i < ((k == 0) ? s->x_pad : 0); i++) Qd[(size_t)i] = 1.0;
-            for (int i = 0; i < nxc; i++) Qd[(size_t)s->xoff[k] + ((k == 0) ? s->x_pad : 0) + i] = Q[oq + i + (size_t)i * nxc];
-            for (int i = 0; i < nu; i++) Rd[(size_t)s->uoff[k] + i] = R ? R[orr + i + (size_t)i * nu] : 0.0;
-            oq += (size_t)nxc * nxc; orr += (size_t)nu * nu; os += (size_t)nu * nxc;
-            continue;
-        }
-        if (k == 0 && s->x_pad) {
-            /* phantom root states: identity weight, no coupling; the caller's node 0 has no Q and no S */
-            for (int i = 0; i < s->x_pad; i++) Hk[i + (size_t)i * nz] = 1.0;
-            for (int j = 0; j < nu; j++) for (int i = 0; i < nu; i++) Hk[s->x_pad + i + (size_t)(s->x_pad + j) * nz] = R ? R[orr + i + (size_t)j * nu] : 0.0;
-            orr += (size_t)nu * nu;
-            continue;
-        }
-        const int nx = s->nx[k];
-        for (int j = 0; j < nx; j++) for (int i = 0; i < nx; i++) Hk[i + (size_t)j * nz] = Q[oq + i + (size_t)j * nx];
-        for (int j = 0; j < nu; j++) for (int i = 0; i < nu; i++) Hk[nx + i + (size_t)(nx + j) * nz] = R ? R[orr + i + (size_t)j * nu] : 0.0;
-        for (int j = 0; j < nx; j++) for (int i = 0; i < nu; i++) {          /* S is nu x nx */
-            const double v = S ? S[os + i + (size_t)j * nu] : 0.0;
-            Hk[nx + i + (size_t)j * nz] = v;
-            Hk[j + (size_t)(nx + i) * nz] = v;
-        }
-        oq += (size_t)nx * nx; orr += (size_t)nu * nu; os += (size_t)nu * nx;
-    }
-    problem_changed(s, false);          /* (dense nodes: no packed constants, use_fast goes to 0 below) */
-    H2D(s->d_Hd, H.data(), s->poff[s->Nn]);
-    HIP_TRY(hipMemcpyAsync(s->d_kind, s->h_kind.data(), sizeof(int) * (size_t)s->Nn, hipMemcpyHostToDevice, s->stream));      /* ints: not H2D (doubles) */
-    H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
-    /* weights: zero on dense nodes (k_export_all writes zero multipliers for them; k_export_box those of the box nodes), the diagonals
-     * on clipping nodes */
-    H2D(s->Qd, Qd.data(), s->sum_nx); H2D(s->Rd, Rd.data(), s->sum_nu);
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->lds_dense = lds_dense;
-    s->dense = true; s->need_dense_init = true; s->D.dense = 1; s->need_init = true;
-    s->use_fast = 0;                                       /* per-node dense blocks: generic kernels */
-    plan_dense_single(s);
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_set_bounds(tqgpu_solver *s, const double *xmin, const double *xmax, const double *umin, const double *umax) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    problem_changed(s, true);
-    if (xmin && xmax && umin && umax) {
-        /* keep what the box nodes' checks need (lb <= ub); refuse before anything is uploaded */
-        std::vector<double> hb((size_t)2 * s->sum_nx + 2 * (size_t)s->sum_nu, 0.0);
-        const size_t nxe = (size_t)(s->sum_nx - s->x_pad);
-        std::copy(xmin, xmin + nxe, hb.begin() + s->x_pad); std::copy(xmax, xmax + nxe, hb.begin() + s->sum_nx + s->x_pad);
-        std::copy(umin, umin + s->sum_nu, hb.begin() + 2 * (size_t)s->sum_nx); std::copy(umax, umax + s->sum_nu, hb.begin() + 2 * (size_t)s->sum_nx + s->sum_nu);
-        hb.swap(s->h_bounds);
-        const int rc = check_box_bounds(s);
-        if (rc != TQGPU_OK) { hb.swap(s->h_bounds); return rc; }
-    } else s->h_bounds.clear();
-    H2D(s->xmin + s->x_pad, xmin, s->sum_nx - s->x_pad); H2D(s->xmax + s->x_pad, xmax, s->sum_nx - s->x_pad); H2D(s->umin, umin, s->sum_nu); H2D(s->umax, umax, s->sum_nu);
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-
-/* General constraints dmin <= C x + D u <= dmax of the nodes (the qpOASES QProblem of the reference, dual_Newton_tree_qpoases.c:226-300):
- * nc rows per node, C (nc x nx) and D (nc x nu) column major, node after node.  nc != NULL (re)defines the rows: what is not given with it
- * is zero (C, D) and unbounded (dmin, dmax).  They apply on the nodes of kind 3 (tqgpu_set_objective_mixed, before or after this call). */
-extern "C" int tqgpu_set_constraints(tqgpu_solver *s, const int *nc, const double *C, const double *Dm, const double *dmin, const double *dmax) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    if (s->shard.on || s->pshard.on) return fail(TQGPU_EINVAL, "general constraints are not available in sharded mode");
-    if (!nc && s->gnc.empty()) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: the rows per node (nc) have not been given yet");
-    HIP_TRY(hipSetDevice(s->device));
-    const int Nn = s->Nn;
-    if (nc) for (int k = 0; k < Nn; k++) {
-        if (nc[k] < 0) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: negative number of rows");
-        if (nc[k] > WAVE) return fail(TQGPU_EUNSUPPORTED, "node " + std::to_string(k) + ": nc = " + std::to_string(nc[k]) + " > 64 (one wave, one row per lane)");
-    }
-    /* dmin <= dmax, before anything changes */
-    const int total = nc ? std::accumulate(nc, nc + Nn, 0) : s->sum_nc;
-    std::vector<double> dr((size_t)2 * total);
-    for (int i = 0; i < total; i++) {
-        dr[(size_t)i] = dmin ? dmin[i] : (nc ? -__builtin_inf() : s->h_drange[(size_t)i]);
-        dr[(size_t)total + i] = dmax ? dmax[i] : (nc ? __builtin_inf() : s->h_drange[(size_t)s->sum_nc + i]);
-        if (!(dr[(size_t)i] <= dr[(size_t)total + i])) return fail(TQGPU_EINVAL, "tqgpu_set_constraints: dmin > dmax in row " + std::to_string(i));
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (nc) {
-        const std::vector<int> nc_was = s->gnc;
-        s->gnc.assign(nc, nc + Nn);
-        if (s->dense) { const int rck = apply_kinds(s, s->h_kind_req); if (rck != TQGPU_OK) { s->gnc = nc_was; return rck; } plan_dense_single(s); }
-        s->groff.assign((size_t)Nn + 1, 0); s->ggoff.assign((size_t)Nn + 1, 0);
-        for (int k = 0; k < Nn; k++) {
-            s->groff[(size_t)k + 1] = s->groff[(size_t)k] + nc[k];
-            s->ggoff[(size_t)k + 1] = s->ggoff[(size_t)k] + nc[k] * (s->nx[k] + s->nu[k]);
-        }
-        s->sum_nc = total;
-        s->mem.release(s->d_gtab); s->mem.release(s->d_Gt); s->mem.release(s->d_drange); s->mem.release(s->d_gmu); s->mem.release(s->d_rmask); s->mem.release(s->d_gsteps); s->mem.release(s->d_gen);
-        std::vector<int> tab(s->gnc);
-        tab.insert(tab.end(), s->groff.begin(), s->groff.end()); tab.insert(tab.end(), s->ggoff.begin(), s->ggoff.end());
-        int rc;
-        if ((rc = s->mem.upload(s->d_gtab, tab.data(), tab.size() * sizeof(int), TQGPU_ENOMEM, "the tables of the general constraints")) ||
-            (rc = s->mem.zeroed(s->d_Gt, sizeof(double) * (size_t)std::max(s->ggoff[(size_t)Nn], 1), TQGPU_ENOMEM, "the rows of the general constraints")) ||
-            (rc = s->mem.zeroed(s->d_drange, sizeof(double) * (size_t)std::max(2 * total, 1), TQGPU_ENOMEM, "the ranges of the general constraints")) ||
-            (rc = s->mem.zeroed(s->d_gmu, sizeof(double) * (size_t)std::max(total, 1), TQGPU_ENOMEM, "the multipliers of the general constraints")) ||
-            (rc = s->mem.zeroed(s->d_rmask, sizeof(unsigned long long) * 4 * (size_t)Nn, TQGPU_ENOMEM, "the working sets of the general constraints")) ||
-            (rc = s->mem.zeroed(s->d_gsteps, (sizeof(long) + sizeof(int)) * (size_t)Nn, TQGPU_ENOMEM, "the step counters of the general constraints")))
-            return rc;
-        Gen g;
-        g.nc = s->d_gtab; g.roff = s->d_gtab + Nn; g.goff = s->d_gtab + 2 * Nn + 1;
-        g.Gt = s->d_Gt; g.dmin = s->d_drange; g.dmax = s->d_drange + total; g.mu = s->d_gmu; g.rmask = s->d_rmask;
-        g.sides = s->d_rmask + 2 * (size_t)Nn; g.hot = s->gen_hot ? 1 : 0;
-        g.steps_total = s->d_gsteps; g.steps_last = reinterpret_cast<int *>(s->d_gsteps + Nn);
-        if ((rc = s->mem.upload(s->d_gen, &g, sizeof(Gen), TQGPU_ENOMEM, "the record of the general constraints"))) return rc;
-        s->h_gen = g;
-        s->D.gen = s->d_gen;
-        if (s->dense) HIP_TRY(hipMemcpy(s->d_kind, s->h_kind.data(), sizeof(int) * (size_t)Nn, hipMemcpyHostToDevice));
-        s->need_dense_init = true;
-    }
-    if (C || Dm) {
-        /* rows of G = [C | D] (the phantom root states keep their zero columns); what is not given stays */
-        std::vector<double> Gt((size_t)std::max(s->ggoff[(size_t)Nn], 1), 0.0);
-        if (!(C && Dm)) HIP_TRY(hipMemcpy(Gt.data(), s->d_Gt, sizeof(double) * (size_t)s->ggoff[(size_t)Nn], hipMemcpyDeviceToHost));
-        size_t oc = 0, od = 0;
-        for (int k = 0; k < Nn; k++) {
-            const int pad = k == 0 ? s->x_pad : 0, nxc = s->nx[k] - pad, nu = s->nu[k], nz = s->nx[k] + nu, m = s->gnc[(size_t)k];
-            double *g = Gt.data() + s->ggoff[(size_t)k];
-            if (C) for (int j = 0; j < nxc; j++) for (int r = 0; r < m; r++) g[(size_t)r * nz + pad + j] = C[oc + r + (size_t)j * m];
-            if (Dm) for (int j = 0; j < nu; j++) for (int r = 0; r < m; r++) g[(size_t)r * nz + s->nx[k] + j] = Dm[od + r + (size_t)j * m];
-            oc += (size_t)m * nxc; od += (size_t)m * nu;
-        }
-        HIP_TRY(hipMemcpy(s->d_Gt, Gt.data(), sizeof(double) * (size_t)s->ggoff[(size_t)Nn], hipMemcpyHostToDevice));
-        s->need_dense_init = true;          /* the kept P_k were built with other rows */
-    }
-    if (total > 0 && (nc || dmin || dmax)) HIP_TRY(hipMemcpy(s->d_drange, dr.data(), sizeof(double) * 2 * (size_t)total, hipMemcpyHostToDevice));
-    s->h_drange.swap(dr);
-    s->out.invalidate(); s->sens.invalidate(); s->sens.dirty = true;          /* not problem_changed: the rows are no input of tqgpu_set_problem (in_valid stays), the exported point goes */
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_dims2(const tqgpu_solver *s, int *sum_nc) {
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    if (sum_nc) *sum_nc = s->sum_nc;
-    return TQGPU_OK;
-}
-
-/* the row multipliers of the last solve (sum_nc doubles, node after node): those of the final working sets of the kind-3 nodes, 0 elsewhere */
-extern "C" int tqgpu_get_mu_d(tqgpu_solver *s, double *mu_d) {
-    SETTLE(s);
-    if (!s || !mu_d) return fail(TQGPU_EINVAL, "tqgpu_get_mu_d: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->sum_nc > 0) HIP_TRY(hipMemcpy(mu_d, s->d_gmu, sizeof(double) * (size_t)s->sum_nc, hipMemcpyDeviceToHost));
-    if (!s->gen) std::fill(mu_d, mu_d + s->sum_nc, 0.0);
-    return TQGPU_OK;
-}
-
-/* stage_gen's hot start on / off (default on).  Off: every stage solve of a kind-3 node starts at the minimiser over the equalities.  Either
- * way the call empties the stored working sets of the kind-3 nodes (the box nodes keep theirs). */
-extern "C" int tqgpu_set_gen_hot_start(tqgpu_solver *s, int on) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    s->gen_hot = on != 0;
-    if (!s->d_gen) return TQGPU_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    const size_t Nn = (size_t)s->Nn;
-    s->h_gen.hot = s->gen_hot ? 1 : 0;
-    /* everything on the mirror's own stream, so that it is ordered before the next solve's launches by construction */
-    std::vector<unsigned long long> bm(Nn);
-    HIP_TRY(hipMemcpyAsync(bm.data(), s->D.bmask, sizeof(unsigned long long) * Nn, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    for (size_t k = 0; k < Nn && k < s->h_kind.size(); k++) if (s->h_kind[k] == 3) bm[k] = 0ull;
-    HIP_TRY(hipMemcpyAsync(s->D.bmask, bm.data(), sizeof(unsigned long long) * Nn, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->d_gen, &s->h_gen, sizeof(Gen), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_rmask, 0, sizeof(unsigned long long) * Nn, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_rmask + 2 * Nn, 0, sizeof(unsigned long long) * 2 * Nn, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-
-/* active-set steps of stage_gen per node (Nn entries each, either may be NULL): in the last stage sweep, and summed over the last tqgpu_solve.
- * One step is one factorisation of S: the dual-feasibility rounds of a hot start and a cold redo count.  0 on nodes of other kinds. */
-extern "C" int tqgpu_get_stage_steps(tqgpu_solver *s, int *last, long *total) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    const size_t Nn = (size_t)s->Nn;
-    if (!s->gen || !s->d_gsteps) {
-        if (last) std::fill(last, last + Nn, 0);
-        if (total) std::fill(total, total + Nn, 0L);
-        return TQGPU_OK;
-    }
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (total) HIP_TRY(hipMemcpy(total, s->d_gsteps, sizeof(long) * Nn, hipMemcpyDeviceToHost));
-    if (last) HIP_TRY(hipMemcpy(last, s->d_gsteps + Nn, sizeof(int) * Nn, hipMemcpyDeviceToHost));
-    return TQGPU_OK;
-}
-
-extern "C" int tqgpu_set_lambda(tqgpu_solver *s, const double *lambda) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    /* kept in a resident buffer: every tqgpu_solve starts from it (device-to-device copy) */
-    s->lam_valid = false;
-    s->warm.fresh = true;            /* warm start mode 1: the next solve starts from this buffer */
-    s->shift.restore = 0;            /* (a buffer saved by tqgpu_mpc_shift is superseded) */
-    if (lambda) { H2D(s->d_lam_init + s->nx0, lambda, s->sum_lam); }
-    else HIP_TRY(hipMemsetAsync(s->d_lam_init, 0, sizeof(double) * (size_t)s->sum_nx, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return TQGPU_OK;
-}
-/* The whole clipping QP (and the starting duals) in one call, for callers that hand over all their data before every
- * solve (treeqp_tdunes_solve re-reads qp_in each time, dual_Newton_tree.c:1142-1160): every array is compared with
- * the pinned host mirror of what the device holds and only what changed is copied and uploaded -- asynchronously,
- * from pinned memory, with no synchronisation (the solve is stream-ordered behind it).  An MPC loop that only
- * moves x0 re-uploads b (and r) and nothing else.  NULL arrays are left alone. */
-extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double *B, const double *b,
-                                 const double *Qd, const double *Rd, const double *q, const double *r,
-                                 const double *xmin, const double *xmax, const double *umin, const double *umax, const double *lambda) {
-    SETTLE(s);
-    if (!s) return fail(TQGPU_EINVAL, "null solver");
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->dense) { s->dense = false; s->box = false; s->gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig; problem_changed(s, true); s->need_init = true; }
-    if (xmin || xmax || umin || umax) s->h_bounds.clear();           /* (the checks of the box nodes' bounds see them through tqgpu_set_bounds only) */
-    char *slab = static_cast<char *>(s->slab);
-    bool any_pack = false, any_init = false;
-    auto put = [&](double *dev, const double *src, int count, bool pack, bool init) -> int {
-        if (!src || count <= 0) return TQGPU_OK;
-        char *mir = s->h_in + ((reinterpret_cast<char *>(dev) - slab) - (ptrdiff_t)s->in_off0);
-        const size_t bytes = sizeof(double) * (size_t)count;
-        if (s->in_valid && memcmp(mir, src, bytes) == 0) return TQGPU_OK;
-        memcpy(mir, src, bytes);
-        HIP_TRY(hipMemcpyAsync(dev, mir, bytes, hipMemcpyHostToDevice, s->stream));
-        s->stream_pending = true;
-        s->sens.invalidate(); s->sens.dirty = true;          /* not problem_changed: the pinned mirror has just been brought up to date, in_valid stays */
-        any_pack |= pack; any_init |= init;
-        return TQGPU_OK;
-    };
-    int rc;
-    const int nxe = s->sum_nx - s->x_pad;
-    if ((rc = put(s->A + s->A_pad, A, s->sum_A - s->A_pad, true, false)) || (rc = put(s->B, B, s->sum_B, true, false)) ||
-        (rc = put(s->b + s->nx0, b, s->sum_lam, false, false)) ||
-        (rc = put(s->Qd + s->x_pad, Qd, nxe, true, true)) || (rc = put(s->Rd, Rd, s->sum_nu, true, true)) ||
-        (rc = put(s->q + s->x_pad, q, nxe, true, false)) || (rc = put(s->r, r, s->sum_nu, true, false)) ||
-        (rc = put(s->xmin + s->x_pad, xmin, nxe, true, false)) || (rc = put(s->xmax + s->x_pad, xmax, nxe, true, false)) ||
-        (rc = put(s->umin, umin, s->sum_nu, true, false)) || (rc = put(s->umax, umax, s->sum_nu, true, false)))
-        return rc;
-    s->in_valid = A && B && b && Qd && Rd && q && r && xmin && xmax && umin && umax ? true : s->in_valid;
-    if (any_init) s->need_init = true;
-    if (any_pack) s->need_pack = true;
-    if (lambda && s->sum_lam > 0) {
-        const size_t bytes = sizeof(double) * (size_t)s->sum_lam;
-        s->warm.fresh = true;        /* as tqgpu_set_lambda (a warm-start copy since the last upload has cleared lam_valid) */
-        s->shift.restore = 0;
-        if (!s->lam_valid || memcmp(s->h_lam, lambda, bytes) != 0) {
-            memcpy(s->h_lam, lambda, bytes);
-            HIP_TRY(hipMemcpyAsync(s->d_lam_init + s->nx0, s->h_lam, bytes, hipMemcpyHostToDevice, s->stream));
-            s->stream_pending = true;
-            s->lam_valid = true;
-        }
-    }
-    return TQGPU_OK;
-}
-#undef H2D
+#include "tdunes_problem.hpp"
 
 namespace {
 
@@ -3919,10 +3447,10 @@ int enqueue_setup(tqgpu_solver *s, SolveCtx &cx, const GItem *defer) {
     }
     /* tqgpu_get_stage_steps: per solve.  (A dense member of a batch launch: that launch is on the lead's stream and resets the counters in its own
      * prologue, g_persist_dense_batch -- a memset on this stream would have to be waited for, once per member and call) */
-    if (s->gen && s->d_gsteps && !(defer && s->dense)) HIP_TRY(hipMemsetAsync(s->d_gsteps, 0, (sizeof(long) + sizeof(int)) * (size_t)T.Nn, st));
-    if (s->dense && s->need_dense_init) {
-        hipLaunchKernelGGL(k_dense_init, dim3(T.Nn), dim3(WAVE), s->lds_dense, st, T, D); cx.launches++;
-        s->need_dense_init = false;
+    if (s->sk.gen && s->rows.d_steps && !(defer && s->sk.dense)) HIP_TRY(hipMemsetAsync(s->rows.d_steps, 0, (sizeof(long) + sizeof(int)) * (size_t)T.Nn, st));
+    if (s->sk.dense && s->sk.need_dense_init) {
+        hipLaunchKernelGGL(k_dense_init, dim3(T.Nn), dim3(WAVE), s->sk.lds_dense, st, T, D); cx.launches++;
+        s->sk.need_dense_init = false;
         if (defer) s->stream_pending = true;      /* the batch launch on the lead's stream waits for it (join_lead_stream): first solves and changed data only */
     }
     return TQGPU_OK;
@@ -3958,14 +3486,14 @@ GParams gparams_of(const tqgpu_solver *s) {
     gp.lvl_first = s->d_lvl_first; gp.lam_init = s->d_lam_init; gp.hres = s->h_res; gp.seq = s->psync.seq; gp.lds_wave = (int)s->lds_gp_wave;
     gp.sum_nx = s->sum_nx; gp.sum_nu = s->sum_nu; gp.sum_W = s->sum_W; gp.sum_Ut = s->sum_Ut; gp.sum_A = s->sum_A; gp.sum_B = s->sum_B;
     gp.small8 = s->gp_small8 ? 1 : 0;
-    if (!s->dense) {
+    if (!s->sk.dense) {
         gp.in_lds = s->gp_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gp_in_lds && s->gp_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gp_const_in_lds ? 1 : 0;
         gp.small16 = s->gp_small16 ? 1 : 0;
         gp.stage_waves = 0; gp.win_stage = 0; gp.win_region = 0; gp.phase_waves = 0;
     } else {
-        gp.in_lds = s->gpd_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd_in_lds && s->gpd_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd_const_in_lds ? 1 : 0;
+        gp.in_lds = s->gpd.in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd.in_lds && s->gpd.tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd.const_in_lds ? 1 : 0;
         gp.small16 = 0;
-        gp.stage_waves = s->dense_stage_waves; gp.phase_waves = s->dense_phase_waves; gp.win_stage = (int)s->dense_win_stage; gp.win_region = (int)s->dense_win_region;
+        gp.stage_waves = s->gpd.stage_waves; gp.phase_waves = s->gpd.phase_waves; gp.win_stage = (int)s->gpd.win_stage; gp.win_region = (int)s->gpd.win_region;
     }
     return gp;
 }
@@ -3978,7 +3506,7 @@ int begin_single_wg(tqgpu_solver *s, SolveCtx &cx, GItem *defer) {
     s->psync.seq = s->launch_no << 16;
     const GParams gp = gparams_of(s);
     if (defer) { defer->T = s->T; defer->D = s->D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
-    else if (s->dense) hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->lds_gpd_total, s->stream, s->T, s->D, cx.O, gp);
+    else if (s->sk.dense) hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->gpd.lds_total, s->stream, s->T, s->D, cx.O, gp);
     else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->lds_gp_total, s->stream, s->T, s->D, cx.O, gp);
     cx.launches++;          /* (also the caller's) */
     return TQGPU_OK;
@@ -4518,7 +4046,7 @@ struct BatchGroup {
 static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveEnv &env, BatchGroup &wg, BatchGroup &dg, BatchGroup &pg) {
     /* single-workgroup mirrors of this wave go out as ONE launch (one workgroup per tree) on the first one's stream; the dense ones among
      * them (uses_gpersist: opted in with tqgpu_set_dense_batch_launch) run another kernel and are a group of their own */
-    for (int k = i; k < j; k++) if (tab[(size_t)k].plan == Route::SINGLE_WG) (tab[(size_t)k].s->dense ? dg : wg).members.push_back(k);
+    for (int k = i; k < j; k++) if (tab[(size_t)k].plan == Route::SINGLE_WG) (tab[(size_t)k].s->sk.dense ? dg : wg).members.push_back(k);
     if (wg.members.size() < 2) wg.members.clear();
     if (dg.members.size() < 2) dg.members.clear();
     /* persistent mirrors of this wave that share a shape with a batch kernel go out as ONE launch as well */
@@ -4610,7 +4138,7 @@ static int launch_single_wg_group(std::vector<BatchMember> &tab, BatchGroup &wg,
 static int launch_dense_wg_group(std::vector<BatchMember> &tab, BatchGroup &dg, size_t n) {
     tqgpu_solver *lead = dg.lead;
     size_t lds_batch = 0;
-    for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)dg.members[m]].s->lds_gpd_total);
+    for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)dg.members[m]].s->gpd.lds_total);
     int rc = join_lead_stream(tab, dg, n);
     if (rc != TQGPU_OK) return rc;
     HIP_TRY(hipMemcpyAsync(lead->d_gitems, lead->h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));

@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(256) k_kkt_max_batch(const KItem *__restrict__
 struct ExportSizes { int nxe, nue, nl; };
 ExportSizes export_sizes(const tqgpu_solver *s) { return {s->sum_nx - s->x_pad, s->sum_nu, s->sum_lam}; }
 /* launches of one export: k_export_all, and the box and row overlays where the tree has such nodes */
-int export_launches(const tqgpu_solver *s) { return 1 + (s->box ? 1 : 0) + (s->gen ? 1 : 0); }
+int export_launches(const tqgpu_solver *s) { return 1 + (s->sk.box ? 1 : 0) + (s->sk.gen ? 1 : 0); }
 
 /* the buffers of tqgpu_kkt_residual*, on first use (most mirrors never ask): the result block, and with_point the scratch point of
  * tqgpu_kkt_residual_at, which grows when tqgpu_set_constraints has added rows since */
@@ -258,7 +258,7 @@ int setup_kkt(tqgpu_solver *s, bool with_point) {
     if (!s->kkt.d && ((rc = s->mem.device(s->kkt.d, res_bytes, TQGPU_ENOMEM, "the KKT residuals")) || (rc = s->mem.host(s->kkt.h, res_bytes, "the host mirror of the KKT residuals"))))
         return rc;
     const ExportSizes z = export_sizes(s);
-    const size_t need = 2 * (size_t)z.nxe + 2 * (size_t)z.nue + (size_t)z.nl + (size_t)s->sum_nc;
+    const size_t need = 2 * (size_t)z.nxe + 2 * (size_t)z.nue + (size_t)z.nl + (size_t)s->rows.sum_nc;
     if (with_point && (!s->kkt.d_pt || need > s->kkt.pt_cap)) {
         s->mem.release(s->kkt.d_pt); s->mem.release(s->kkt.h_pt);
         s->kkt.pt_cap = 0;
@@ -278,8 +278,8 @@ static int enqueue_export(tqgpu_solver *s, const double *lamc, bool download) {
     const ExportSizes z = export_sizes(s);
     const int n = std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1));
     hipLaunchKernelGGL(k_export_all, dim3((n + 255) / 256), dim3(256), 0, s->stream, z.nxe, z.nue, z.nl, s->x_pad, s->nx0, D, lamc, s->out.d);
-    if (s->box) hipLaunchKernelGGL(k_export_box, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, z.nxe, z.nue, z.nl, s->x_pad, s->out.d);
-    if (s->gen) hipLaunchKernelGGL(k_export_gen, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, z.nxe, z.nue, z.nl, s->x_pad, s->out.d);
+    if (s->sk.box) hipLaunchKernelGGL(k_export_box, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, z.nxe, z.nue, z.nl, s->x_pad, s->out.d);
+    if (s->sk.gen) hipLaunchKernelGGL(k_export_gen, dim3(s->T.Nn), dim3(WAVE), 0, s->stream, s->T, D, z.nxe, z.nue, z.nl, s->x_pad, s->out.d);
     if (download) HIP_TRY(hipMemcpyAsync(s->out.h, s->out.d, sizeof(double) * std::max<size_t>(s->out.doubles, 1), hipMemcpyDeviceToHost, s->stream));
     return TQGPU_OK;
 }
@@ -337,7 +337,7 @@ KktPoint kkt_point_of_export(const tqgpu_solver *s) {
     const ExportSizes z = export_sizes(s);
     KktPoint P;
     P.x = s->out.d; P.u = P.x + z.nxe; P.lam = P.u + z.nue; P.mu_x = P.lam + 2 * (size_t)z.nl; P.mu_u = P.mu_x + z.nxe;
-    P.mu_d = s->gen ? s->d_gmu : nullptr;
+    P.mu_d = s->sk.gen ? s->rows.d_mu : nullptr;
     return P;
 }
 /* behind the solve of a certified tqgpu_mpc_step (setup_kkt has run): the packing into Export::d with the dual buffer the DEVICE calls current -- the
@@ -396,7 +396,7 @@ extern "C" int tqgpu_kkt_residual_at(tqgpu_solver *s, const double *x, const dou
         return d;
     };
     KktPoint P;
-    P.x = put(x, z.nxe); P.u = put(u, z.nue); P.lam = put(lam, z.nl); P.mu_x = put(mu_x, z.nxe); P.mu_u = put(mu_u, z.nue); P.mu_d = put(mu_d, s->sum_nc);
+    P.x = put(x, z.nxe); P.u = put(u, z.nue); P.lam = put(lam, z.nl); P.mu_x = put(mu_x, z.nxe); P.mu_u = put(mu_u, z.nue); P.mu_d = put(mu_d, s->rows.sum_nc);
     if (off) HIP_TRY(hipMemcpyAsync(s->kkt.d_pt, s->kkt.h_pt, sizeof(double) * off, hipMemcpyHostToDevice, s->stream));
     if ((rc = kkt_enqueue(s, P, per_node != nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -446,7 +446,7 @@ int kkt_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, KktBatchStats &st)
         it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
         it.d_out = s->out.d; it.table = s->kkt.d + KKT_HEAD; it.head = lead->kkt.d_heads[m].v;
         it.P = kkt_point_of_export(s);
-        it.needs_export = s->out.valid ? 0 : 1; it.box = s->box ? 1 : 0; it.gen = s->gen ? 1 : 0;
+        it.needs_export = s->out.valid ? 0 : 1; it.box = s->sk.box ? 1 : 0; it.gen = s->sk.gen ? 1 : 0;
         nn_all = std::max(nn_all, s->T.Nn);
         if (it.needs_export) {
             cells = std::max(cells, std::max(std::max(it.nxe, it.nue), std::max(it.nl, 1)));

@@ -227,8 +227,6 @@ __global__ void __launch_bounds__(256) k_mpc_post_batch(const MItem *__restrict_
 
 /* ---- the host side: x0 fold, warm start and u[0] without the host in the data path (tqgpu_mpc_*) ---- */
 
-int root_kind_of(const tqgpu_solver *s) { return s->dense && !s->h_kind.empty() ? s->h_kind[0] : 0; }
-
 int mpc_refuse(const tqgpu_solver *s, const char *who) {
     if (!s) return fail(TQGPU_EINVAL, std::string(who) + ": null solver");
     if ((s->pshard.on || s->shard.on) && s->shard.nranks > 1)
@@ -254,7 +252,7 @@ MItem mpc_item(const tqgpu_solver *s, MpcPre pre) {
         it.cst = s->persist_ok && s->pcst && !s->need_pack ? s->pcst : nullptr;
     }
     it.b = s->b; it.r = s->r;
-    it.dmin = s->mpc.C0 ? s->d_drange : nullptr; it.dmax = s->mpc.C0 ? s->d_drange + s->sum_nc : nullptr;
+    it.dmin = s->mpc.C0 ? s->rows.d_drange : nullptr; it.dmax = s->mpc.C0 ? s->rows.d_drange + s->rows.sum_nc : nullptr;
     it.lam_init = s->d_lam_init;
     it.nx0 = s->mpc.nx0; it.nc0 = s->mpc.nc0; it.nu0 = s->nu[0]; it.sum_nx = s->sum_nx;
     it.fold = pre.fold ? 1 : 0; it.warm = pre.warm ? 1 : 0;
@@ -263,9 +261,9 @@ MItem mpc_item(const tqgpu_solver *s, MpcPre pre) {
     if (pre.warm && s->shift.d && (pre.shift || s->warm.mode == 2)) {
         const size_t nreal = (size_t)std::max(s->nk[0], 1), j = (size_t)s->shift.realised;
         it.shift_src = s->shift.d + j * (size_t)s->sum_nx;
-        if ((s->shift.what & TQGPU_SHIFT_WORKING_SETS) && s->dense && (s->box || s->gen) && s->D.kind && s->D.bmask)
+        if ((s->shift.what & TQGPU_SHIFT_WORKING_SETS) && s->sk.working_sets((size_t)s->Nn) && s->D.kind && s->D.bmask)
             it.shift_node = s->shift.d + nreal * (size_t)s->sum_nx + j * (size_t)s->Nn;
-        if (s->gen && s->d_rmask && s->h_gen.nc) { it.ws_rmask = s->d_rmask; it.ws_sides = s->d_rmask + 2 * (size_t)s->Nn; it.ws_nc = s->h_gen.nc; }
+        if (s->sk.gen && s->rows.d_rmask && s->rows.h_gen.nc) { it.ws_rmask = s->rows.h_gen.rmask; it.ws_sides = s->rows.h_gen.sides; it.ws_nc = s->rows.h_gen.nc; }
         it.realised = s->shift.realised;
         /* tqgpu_mpc_shift: mode 0 promises the caller's start buffer to every solve: the kernel saves it (once: a second shift ahead of the same
          * solve finds the shifted duals there), and the solve after the next puts it back (solve_begin) */
@@ -307,7 +305,7 @@ int mpc_take_window(tqgpu_solver *s, int t0, bool commit, const char *who) {
     if (!s->trk.d) return fail(TQGPU_EINVAL, std::string(who) + ": the reference trajectory has not been given yet (tqgpu_mpc_set_tracking)");
     if (s->mpc.S0 && s->mpc.nx0 != s->trk.nxt)
         return fail(TQGPU_EINVAL, std::string(who) + ": S0 of tqgpu_mpc_set_root has " + std::to_string(s->mpc.nx0) + " columns, the trajectory " + std::to_string(s->trk.nxt) + " states");
-    if (s->mpc.S0 && root_kind_of(s) == 0) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 0 after tqgpu_mpc_set_root gave it an S0");
+    if (s->mpc.S0 && s->sk.kind(0) == 0) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 0 after tqgpu_mpc_set_root gave it an S0");
     if (!commit) return TQGPU_OK;
     s->trk.t0 = t0;
     problem_changed(s, false);              /* the pinned mirror of tqgpu_set_problem no longer describes q, r */
@@ -318,18 +316,18 @@ int mpc_take_window(tqgpu_solver *s, int t0, bool commit, const char *who) {
 int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
     if (!s->mpc.d && !s->mpc.states) return fail(TQGPU_EINVAL, std::string(who) + ": the root terms have not been given yet (tqgpu_mpc_set_root, or tqgpu_mpc_set_root_states on a root that keeps its states)");
     if (s->mpc.states) {
-        if (root_kind_of(s) == 1) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 1 after tqgpu_mpc_set_root_states: its bounds are ignored, x0 cannot be imposed");
+        if (s->sk.kind(0) == 1) return fail(TQGPU_EINVAL, std::string(who) + ": the root became a node of kind 1 after tqgpu_mpc_set_root_states: its bounds are ignored, x0 cannot be imposed");
         if (!x0) return TQGPU_OK;
         const size_t n0 = (size_t)s->mpc.nx0;
         memcpy(s->mpc.h, x0, sizeof(double) * n0);
         problem_changed(s, false);              /* the pinned mirror of tqgpu_set_problem no longer describes xmin, xmax */
-        if (!s->h_bounds.empty()) {             /* what the box nodes' checks see (tqgpu_set_bounds) */
-            std::copy(x0, x0 + n0, s->h_bounds.begin());
-            std::copy(x0, x0 + n0, s->h_bounds.begin() + s->sum_nx);
+        if (!s->sk.h_bounds.empty()) {             /* what the box nodes' checks see (tqgpu_set_bounds) */
+            std::copy(x0, x0 + n0, s->sk.h_bounds.begin());
+            std::copy(x0, x0 + n0, s->sk.h_bounds.begin() + s->sum_nx);
         }
         return TQGPU_OK;                        /* need_pack stays as it is: the fold writes the packed copy itself */
     }
-    if (s->mpc.C0 && (s->gnc.empty() || s->gnc[0] != s->mpc.nc0 || !s->d_drange))
+    if (s->mpc.C0 && (s->rows.nc.empty() || s->rows.nc[0] != s->mpc.nc0 || !s->rows.d_drange))
         return fail(TQGPU_EINVAL, std::string(who) + ": the rows of the root were redefined after tqgpu_mpc_set_root (call it again)");
     /* a tracking mirror whose window is set: r[0] of a root with S0 is the chain of mpc_track_root_r, which reads nx0 entries of a trajectory row */
     if (s->trk.d && s->trk.t0 >= 0 && s->mpc.S0 && s->mpc.nx0 != s->trk.nxt)
@@ -385,12 +383,12 @@ extern "C" int tqgpu_mpc_set_root(tqgpu_solver *s, int nx0, const double *A0, co
     if (S0 && !r0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: S0 comes with r0");
     if (C0 && !(dmin0 && dmax0)) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: C0 comes with dmin0 and dmax0");
     const size_t n0 = (size_t)nx0, nu0 = (size_t)s->nu[0];
-    const bool kind0 = !s->dense || s->h_kind.empty() || s->h_kind[0] == 0;
+    const bool kind0 = s->sk.kind(0) == 0;
     if (S0 && kind0) {
         for (size_t i = 0; i < nu0 * n0; i++) if (S0[i] != 0.0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: S0 is not zero on a root of kind 0 (clipping: S must be zero)");
         S0 = nullptr;
     }
-    const int nc0 = (!s->gnc.empty() && s->dense && !s->h_kind.empty() && s->h_kind[0] == 3) ? s->gnc[0] : 0;
+    const int nc0 = (!s->rows.nc.empty() && s->sk.kind(0) == 3) ? s->rows.nc[0] : 0;
     if (C0 && nc0 <= 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root: C0 without rows on the root (tqgpu_set_constraints, root of kind 3)");
     size_t nb = 0;
     for (int c = 0; c < s->nk[0]; c++) nb += (size_t)s->nx[(size_t)s->kid0[0] + c];
@@ -419,7 +417,7 @@ extern "C" int tqgpu_mpc_set_root_states(tqgpu_solver *s) {
     SETTLE(s);
     const int n0 = s->nx[0] - s->x_pad;
     if (n0 <= 0) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root_states: the root has no states (x0 is eliminated: tqgpu_mpc_set_root takes the root terms)");
-    if (root_kind_of(s) == 1) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root_states: the root is of kind 1, whose bounds are ignored: x0 cannot be imposed through them");
+    if (s->sk.kind(0) == 1) return fail(TQGPU_EINVAL, "tqgpu_mpc_set_root_states: the root is of kind 1, whose bounds are ignored: x0 cannot be imposed through them");
     const size_t nu0 = (size_t)s->nu[0];
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));          /* a fold in flight reads the pinned block that is replaced */
@@ -665,14 +663,14 @@ extern "C" int tqgpu_get_working_sets(tqgpu_solver *s, unsigned long long *bound
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     const size_t Nn = (size_t)s->Nn, bytes = sizeof(unsigned long long) * Nn;
-    const bool sets = s->dense && (s->box || s->gen) && s->h_kind.size() == Nn, rows_there = sets && s->gen && s->d_rmask;
+    const bool sets = s->sk.working_sets(Nn), rows_there = sets && s->sk.gen && s->rows.d_rmask;
     unsigned long long *out[4] = {bounds, rows, bound_sides, row_sides};
-    const unsigned long long *from[4] = {sets ? s->D.bmask : nullptr, rows_there ? s->d_rmask : nullptr, rows_there ? s->d_rmask + 2 * Nn : nullptr, rows_there ? s->d_rmask + 3 * Nn : nullptr};
+    const unsigned long long *from[4] = {sets ? s->D.bmask : nullptr, rows_there ? s->rows.h_gen.rmask : nullptr, rows_there ? s->rows.h_gen.sides : nullptr, rows_there ? s->rows.row_sides(Nn) : nullptr};
     for (int a = 0; a < 4; a++) {
         if (!out[a]) continue;
         if (from[a]) HIP_TRY(hipMemcpy(out[a], from[a], bytes, hipMemcpyDeviceToHost));
         else std::fill(out[a], out[a] + Nn, 0ull);
-        for (size_t k = 0; k < Nn; k++) if (!sets || s->h_kind[k] < 2 || ((a == 1 || a == 3) && s->h_kind[k] != 3)) out[a][k] = 0ull;
+        for (size_t k = 0; k < Nn; k++) if (!sets || s->sk.h_kind[k] < 2 || ((a == 1 || a == 3) && s->sk.h_kind[k] != 3)) out[a][k] = 0ull;
     }
     return TQGPU_OK;
 }
@@ -684,15 +682,15 @@ extern "C" int tqgpu_set_working_sets(tqgpu_solver *s, const unsigned long long 
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     const size_t Nn = (size_t)s->Nn, bytes = sizeof(unsigned long long) * Nn;
-    const bool sets = s->dense && (s->box || s->gen) && s->h_kind.size() == Nn, rows_there = sets && s->gen && s->d_rmask;
+    const bool sets = s->sk.working_sets(Nn), rows_there = sets && s->sk.gen && s->rows.d_rmask;
     if (!sets) return TQGPU_OK;          /* no node of kind 2 or 3: nothing reads a set */
     const unsigned long long *in[4] = {bounds, rows, bound_sides, row_sides};
-    unsigned long long *to[4] = {s->D.bmask, rows_there ? s->d_rmask : nullptr, rows_there ? s->d_rmask + 2 * Nn : nullptr, rows_there ? s->d_rmask + 3 * Nn : nullptr};
+    unsigned long long *to[4] = {s->D.bmask, rows_there ? s->rows.h_gen.rmask : nullptr, rows_there ? s->rows.h_gen.sides : nullptr, rows_there ? s->rows.row_sides(Nn) : nullptr};
     std::vector<unsigned long long> w(Nn);
     for (int a = 0; a < 4; a++) {
         if (!in[a] || !to[a]) continue;
         HIP_TRY(hipMemcpy(w.data(), to[a], bytes, hipMemcpyDeviceToHost));          /* (the words of the other nodes stay) */
-        for (size_t k = 0; k < Nn; k++) if (s->h_kind[k] >= 2 && !((a == 1 || a == 3) && s->h_kind[k] != 3)) w[k] = in[a][k];
+        for (size_t k = 0; k < Nn; k++) if (s->sk.h_kind[k] >= 2 && !((a == 1 || a == 3) && s->sk.h_kind[k] != 3)) w[k] = in[a][k];
         HIP_TRY(hipMemcpy(to[a], w.data(), bytes, hipMemcpyHostToDevice));
     }
     return TQGPU_OK;
@@ -708,9 +706,9 @@ extern "C" int tqgpu_get_root_terms(tqgpu_solver *s, double *b_kids, double *r0,
     for (int c = 0; c < s->nk[0]; c++) nb += (size_t)s->nx[(size_t)s->kid0[0] + c];
     if (b_kids && nb) HIP_TRY(hipMemcpy(b_kids, s->b + s->xoff[(size_t)s->kid0[0]], sizeof(double) * nb, hipMemcpyDeviceToHost));          /* the children are nodes 1 .. nk[0]: one piece */
     if (r0 && s->nu[0] > 0) HIP_TRY(hipMemcpy(r0, s->r, sizeof(double) * (size_t)s->nu[0], hipMemcpyDeviceToHost));
-    const int nc0 = s->gnc.empty() || !s->d_drange ? 0 : s->gnc[0];
-    if (dmin0 && nc0) HIP_TRY(hipMemcpy(dmin0, s->d_drange, sizeof(double) * (size_t)nc0, hipMemcpyDeviceToHost));
-    if (dmax0 && nc0) HIP_TRY(hipMemcpy(dmax0, s->d_drange + s->sum_nc, sizeof(double) * (size_t)nc0, hipMemcpyDeviceToHost));
+    const int nc0 = s->rows.nc.empty() || !s->rows.d_drange ? 0 : s->rows.nc[0];
+    if (dmin0 && nc0) HIP_TRY(hipMemcpy(dmin0, s->rows.d_drange, sizeof(double) * (size_t)nc0, hipMemcpyDeviceToHost));
+    if (dmax0 && nc0) HIP_TRY(hipMemcpy(dmax0, s->rows.d_drange + s->rows.sum_nc, sizeof(double) * (size_t)nc0, hipMemcpyDeviceToHost));
     return TQGPU_OK;
 }
 
