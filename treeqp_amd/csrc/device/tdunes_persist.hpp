@@ -410,9 +410,10 @@ struct ShiftDiag<D, D> { static __device__ __forceinline__ void run(double (&)[D
 /* in-register tall Cholesky as potrf_rows (left-looking, row broadcasts by readlane) and nothing else in
  * the loop: no per-lane select or store of the reciprocal pivots (the substitutions recompute 1/diag from
  * the stored factor; an exec-masked LDS store per column cost ~70 cycles each in tools/microbench/level_bench);
- * returns the smallest pivot (on-the-fly regularisation trigger) */
+ * returns the smallest pivot (on-the-fly regularisation trigger) of the first nreal columns: the columns beyond them are identity
+ * padding (tdunes_wide.hpp), whose pivot 1.0 is no pivot of the block and must not meet regTol^2 */
 template <int D>
-__device__ __forceinline__ double p_potrf_rows(double (&T)[D], int lane) {
+__device__ __forceinline__ double p_potrf_rows(double (&T)[D], int lane, int nreal = D) {
     double pmin = __builtin_inf();
 #pragma unroll
     for (int j = 0; j < D; j++) {
@@ -420,7 +421,7 @@ __device__ __forceinline__ double p_potrf_rows(double (&T)[D], int lane) {
 #pragma unroll
         for (int k = 0; k < j; k++) s = fma(-T[k], rdlane(T[k], j), s);
         const double pj = rdlane(s, j);
-        pmin = fmin(pmin, pj);
+        pmin = fmin(pmin, j < nreal ? pj : __builtin_inf());
         T[j] = s * pivot_rsqrt3(pj);
     }
     return pmin;

@@ -294,7 +294,7 @@ __device__ __forceinline__ void factor_w_body(const Tree &T, const Data &D, cons
             __syncthreads();                       /* every wave holds its copy of the diagonal tile before wave 0 overwrites it */
             WSTAMP(2 + 3 * (kb >> 4));
             if (mine) {
-                const double pmin = p_potrf_rows<16>(Tr, lane);
+                const double pmin = p_potrf_rows<16>(Tr, lane, d - kb);          /* (columns kb + j >= d: padding) */
                 if (valid && (wave == 0 || !diag)) {
 #pragma unroll
                     for (int j = 0; j < 16; j++) Tm[row + (kb + j) * ld] = Tr[j];

@@ -639,7 +639,7 @@ static inline size_t wide3_lds_sgp(int d, int nz, int accs) { return ((size_t)(d
 /* left-looking tall Cholesky of the first NC columns of a 16-column panel, one row per lane (p_potrf_rows with a
  * column count below the array size: the last panel of a block whose dimension is not a multiple of 16) */
 template <int NC>
-__device__ __forceinline__ double w3_potrf_cols(double (&Tr)[16], int lane) {
+__device__ __forceinline__ double w3_potrf_cols(double (&Tr)[16], int lane, int nreal) {
     double pmin = __builtin_inf();
 #pragma unroll
     for (int j = 0; j < NC; j++) {
@@ -647,17 +647,17 @@ __device__ __forceinline__ double w3_potrf_cols(double (&Tr)[16], int lane) {
 #pragma unroll
         for (int k = 0; k < j; k++) s = fma(-Tr[k], rdlane(Tr[k], j), s);
         const double pj = rdlane(s, j);
-        pmin = fmin(pmin, pj);
+        pmin = fmin(pmin, j < nreal ? pj : __builtin_inf());          /* (a padding column's pivot 1.0 is no pivot of the block) */
         Tr[j] = s * pivot_rsqrt3(pj);
     }
     return pmin;
 }
-__device__ __forceinline__ double w3_chain(double (&Tr)[16], int lane, int wp) {
+__device__ __forceinline__ double w3_chain(double (&Tr)[16], int lane, int wp, int nreal) {
     switch (wp) {
-        case 4: return w3_potrf_cols<4>(Tr, lane);
-        case 8: return w3_potrf_cols<8>(Tr, lane);
-        case 12: return w3_potrf_cols<12>(Tr, lane);
-        default: return w3_potrf_cols<16>(Tr, lane);
+        case 4: return w3_potrf_cols<4>(Tr, lane, nreal);
+        case 8: return w3_potrf_cols<8>(Tr, lane, nreal);
+        case 12: return w3_potrf_cols<12>(Tr, lane, nreal);
+        default: return w3_potrf_cols<16>(Tr, lane, nreal);
     }
 }
 
@@ -1041,7 +1041,7 @@ __global__ void __launch_bounds__(WT, TQ_W3_WPS) k_hf_w(Tree T, Data D, Opts O, 
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 W3STAMP(16 + 3 * p);
 #endif
-                const double pmin = w3_chain(Tr, lane, wp);
+                const double pmin = w3_chain(Tr, lane, wp, d - kb);
 #ifdef TQ_WIDE_STAMPS
                 asm volatile("" :: "v"(Tr[15]), "v"(Tr[0]), "v"(pmin) : "memory");
                 W3STAMP(17 + 3 * p);
