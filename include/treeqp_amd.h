@@ -682,6 +682,49 @@ int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, double *gb);
  *                        member; TQGPU_EINVAL for n < 1, solvers == NULL, opts == NULL, nw < 1 and a mirror named twice.  Every member's
  *                        stored adjoint and sensitivity are then as before. */
 int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, const double *wx, const double *wu, int nw, double *gx0, int *n_reg);
+/* The sensitivities and the predictor of a batch of steps in one set of launches per device: what tqgpu_mpc_sensitivity and tqgpu_mpc_predict
+ * do for one mirror, for n of them.
+ *   tqgpu_mpc_sensitivity_batch
+ *   n_reg                may be NULL; n ints.
+ *   per device           the members of one device form a group led by its first member, whose stream carries everything: two copies (the
+ *                        descriptors with the members' level tables; the heads [K | u0* | x0_ref | n_reg] of all members) and one wait,
+ *                        whatever n; launches, with Nh_max the deepest member's block levels: [1, the packing of the points, where a member
+ *                        has not packed its point] + (1 + Nh_max) + (Nh_max - 1) + 1.  Blocks z of the grid are the members, x what it is in
+ *                        the single launches, y of the forward sweep the column of x0: the grid is as tall as the largest nx0_i, a wave beyond
+ *                        its member's nx0 returns at once; the factor launch j takes level Nh_i - 1 - j of member i, the forward launch j
+ *                        level j + 1.  Like the single call it always builds the factor anew.  The arithmetic of a member is that of its
+ *                        own tqgpu_mpc_sensitivity: every result is the same bit for bit.  Counted into tqgpu_mpc_stats.  (The one wait
+ *                        is that of a loop's steady state behind tqgpu_mpc_step_batch.  A member whose own stream may still hold work
+ *                        the lead's stream has not seen -- uploads, a solve of its own, the set-up kernels of its first solve -- is
+ *                        waited for first, once per such stream, as in tqgpu_mpc_adjoint_batch.)
+ *   state                afterwards every member is as a successful tqgpu_mpc_sensitivity leaves it: tqgpu_mpc_get_gain,
+ *                        tqgpu_mpc_get_sensitivities and tqgpu_mpc_predict of the member read the member's own buffers (the kernel that
+ *                        fills a member's head on the device writes it a second time into the lead's block; the member's pinned head is
+ *                        filled from the group's copy), the factor counts as stored, so that a later tqgpu_mpc_adjoint / _adjoint_batch
+ *                        does not build it; the flags are set after the wait has succeeded.  A stored adjoint and everything a solve
+ *                        reads are left as the single call leaves them.
+ *   member by member     groups of fewer than SENS_BATCH_MIN members (tdunes_adjoint.hpp), of more than 65 535, or in which one tree dwarfs
+ *                        the others (the rule of tqgpu_kkt_residual_batch), and every group under TREEQP_AMD_SENS_BATCH=members, go through
+ *                        tqgpu_mpc_sensitivity one member after the other: same results and state, the counts are the sum of the single calls.
+ *   refusals             before any member is touched, with the member's index in the message ("member i:"): whatever
+ *                        tqgpu_mpc_sensitivity refuses for a member (kinds 2 / 3 and the LDS window included); TQGPU_EINVAL for n < 1,
+ *                        solvers == NULL, opts == NULL and a mirror named twice.  Every member's stored sensitivity and adjoint are then
+ *                        as before.
+ *   tqgpu_mpc_predict_batch
+ *   x0_new               required: the members' nx0_i vectors one behind the other, member 0 first.
+ *   u0_pred, n_clipped   may be NULL; the members' nu[0]_i blocks one behind the other, and n ints.  duals is one flag for all members.
+ *   per device           one launch on the lead's stream (blocks z: the members; x: 0 the prediction of u0, 1 + k node k of the start
+ *                        buffer, with duals only), one copy (the descriptors) and one wait, whatever n; x0_new and the results travel
+ *                        through a pinned block of the lead, which the kernel reads and writes in place.  The arithmetic of a member is
+ *                        tqgpu_mpc_predict's chain, entry for entry; with duals every member's start buffer is treated as the single call
+ *                        treats it (saved once and restored by the solve after the next in warm-start mode 0; it holds for ONE solve in
+ *                        any mode).  Counted into tqgpu_mpc_stats.
+ *   member by member     the rule and the switch of tqgpu_mpc_sensitivity_batch; the counts are the sum of the single calls.
+ *   refusals             before any member is touched, with the member's index in the message: TQGPU_EINVAL for a member without a valid
+ *                        sensitivity, for n < 1, solvers == NULL, x0_new == NULL and a mirror named twice.  No start buffer is changed then.
+ * Groups on more than one device are built like tqgpu_mpc_adjoint_batch's; only one device could be tested. */
+int tqgpu_mpc_sensitivity_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *opts, int *n_reg);
+int tqgpu_mpc_predict_batch(tqgpu_solver **solvers, int n, const double *x0_new, double *u0_pred, int duals, int *n_clipped);
 
 /* ---- The adjoint of an MPC step in H, A, B: outer products on the device, summed over parameter groups and over a batch -----------------
  * Behind tqgpu_mpc_adjoint (or tqgpu_mpc_adjoint_batch), for every column j of w.  z_k = [x_k; u_k] is the point tqgpu_get_solution would

@@ -48,6 +48,13 @@ with root states and on c1 x0-eliminated, with the launches, copies and waits of
 the dual predictor (tqgpu_mpc_sensitivity + tqgpu_mpc_predict with duals) against warm start mode 1 over the sequences of --root-states
 and --tracking (predict_compare).
 
+    python tools/mpc_loop.py --gain-batch N[,N2,..] [--steps 200] [--skip 10] [c1] [c2]
+
+--gain-batch: behind every tqgpu_mpc_step_batch of N trees, the gains and the dual predictor two ways, on c1 x0-eliminated and on c2 with
+root states: (a) tqgpu_mpc_sensitivity_batch and tqgpu_mpc_predict_batch, (b) N calls each of tqgpu_mpc_sensitivity and tqgpu_mpc_predict on
+mirrors of their own; wall time, launches, copies and waits of each, the largest difference of K and of u0_pred between them, which must be
+0, and the iterations per step with the dual predictor against warm start mode 1 alone (gain_batch_compare).
+
     python tools/mpc_loop.py --adjoint [--steps 200] [--skip 10] [c1] [c2]
 
 --adjoint: behind every step, three ways to the gradient of a scalar loss with one random w = dL/dz, on c1 and c2 with root states and on
@@ -67,6 +74,7 @@ Hessians of equal sizes, two ways: tqgpu_mpc_adjoint_matrices (with --adjoint-ba
 the batch step and the batch adjoint), and the host route, tqgpu_get_solution + tqgpu_mpc_get_adjoint + numpy outer products and sums
 (adjoint_matrices_compare)."""
 import ctypes as C
+import os
 import sys
 import time
 from pathlib import Path
@@ -897,6 +905,106 @@ def adjoint_batch_compare(capi, name, p, root_states, n, steps, skip):
     print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |gx0 (a) - gx0 (b)| over the run {dab:.2e}", flush=True)
 
 
+def gain_batch_compare(capi, name, p, root_states, n, steps, skip):
+    """--gain-batch N: behind every tqgpu_mpc_step_batch of N trees (warm start mode 1), the gains and the dual predictor two ways, each on
+    N mirrors of its own, stepped alike, and timed around its calls with the host clock:
+    (a) one tqgpu_mpc_sensitivity_batch and one tqgpu_mpc_predict_batch (x0 of the next step, duals = 1);
+    (b) N calls of tqgpu_mpc_sensitivity and N of tqgpu_mpc_predict (duals = 1), member after member.
+    Launches, copies and waits are those tqgpu_mpc_stats counts ((b): summed over the N calls).  The largest difference of K and of u0_pred
+    between the two must be 0: a member's arithmetic is the same.  A third set of mirrors steps in mode 1 without the predictor: iterations
+    per step of both.  With a library that lacks the batched calls (TREEQP_AMD_LIB naming an earlier build) only (b) and the third set run."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o = capi._gpu_opts()
+    batched = hasattr(L, "tqgpu_mpc_sensitivity_batch")
+    path = moved_inward if root_states else moved
+    if root_states:
+        d, x0 = full_root(capi, p)
+    else:
+        d, A0, b0, _, x0 = eliminated(capi, p)
+    xs = [np.concatenate([path(x0, k, i) for i in range(n)]) for k in range(steps + 1)]
+
+    def mirror():
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        if root_states:
+            g.mpc_set_root_states()
+        else:
+            g.mpc_set_root(A0, b0)
+        g.set_warm_start(1)
+        return g
+
+    nu0, nx0 = int(d["nu"][0]), len(x0)
+    legs = ("a", "b", "c") if batched else ("b", "c")
+    gs = {key: [mirror() for _ in range(n)] for key in legs}
+    arr = {key: (C.c_void_p * n)(*[m.h for m in v]) for key, v in gs.items()}
+    res = (capi.GpuResult * n)()
+    u0 = np.zeros(max(nu0 * n, 1))
+    K = {key: np.zeros(max(nu0 * nx0 * n, 1)) for key in "ab"}
+    up = {key: np.zeros(max(nu0 * n, 1)) for key in "ab"}
+    nregs, ncl = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    la, co, wa, nreg, nc1 = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    t = {key: [] for key in ("step", "a_sens", "a_pred", "b_sens", "b_pred")}
+    c = {key: [] for key in ("a_sens", "a_pred", "b_sens", "b_pred")}
+    iters = {key: [] for key in legs}
+    dK, dU, regs, bad = 0.0, 0.0, 0, 0
+
+    def counted():
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        return la.value, co.value, wa.value
+
+    for k in range(steps):
+        for key in legs:
+            t0 = time.perf_counter()
+            assert L.tqgpu_mpc_step_batch(arr[key], n, dp(xs[k]), C.byref(o), res, dp(u0)) == 0, L.tqgpu_last_error()
+            if key == legs[0]:
+                t["step"].append(time.perf_counter() - t0)
+            bad += sum(res[i].status != 0 for i in range(n))
+            iters[key].append(np.mean([res[i].iter for i in range(n)]))
+        if batched:
+            t0 = time.perf_counter()
+            assert L.tqgpu_mpc_sensitivity_batch(arr["a"], n, C.byref(o), capi._ip(nregs)) == 0, L.tqgpu_last_error()
+            t["a_sens"].append(time.perf_counter() - t0); c["a_sens"].append(counted()); regs += int(nregs.sum())
+            t0 = time.perf_counter()
+            assert L.tqgpu_mpc_predict_batch(arr["a"], n, dp(xs[k + 1]), dp(up["a"]), 1, capi._ip(ncl)) == 0, L.tqgpu_last_error()
+            t["a_pred"].append(time.perf_counter() - t0); c["a_pred"].append(counted())
+            for i, g in enumerate(gs["a"]):
+                assert L.tqgpu_mpc_get_gain(g.h, dp(K["a"][i * nu0 * nx0:]), None, None) == 0
+        t0 = time.perf_counter()
+        tot = np.zeros(3, dtype=int)
+        for g in gs["b"]:
+            assert L.tqgpu_mpc_sensitivity(g.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()
+            tot += counted()
+        t["b_sens"].append(time.perf_counter() - t0); c["b_sens"].append(tuple(tot))
+        t0 = time.perf_counter()
+        tot = np.zeros(3, dtype=int)
+        for i, g in enumerate(gs["b"]):
+            assert L.tqgpu_mpc_predict(g.h, dp(xs[k + 1][i * nx0:]), dp(up["b"][i * nu0:]), 1, C.byref(nc1)) == 0, L.tqgpu_last_error()
+            tot += counted()
+        t["b_pred"].append(time.perf_counter() - t0); c["b_pred"].append(tuple(tot))
+        for i, g in enumerate(gs["b"]):
+            assert L.tqgpu_mpc_get_gain(g.h, dp(K["b"][i * nu0 * nx0:]), None, None) == 0
+        if batched:
+            dK = max(dK, float(np.max(np.abs(K["a"] - K["b"])))); dU = max(dU, float(np.max(np.abs(up["a"] - up["b"]))))
+    for v in gs.values():
+        for g in v:
+            g.close()
+    med = lambda v: tuple(int(np.median([e[i] for e in v[skip:]])) for i in range(3))
+    form = "roots with states" if root_states else "x0 eliminated"
+    print(f"{name}, --gain-batch {n}, {form}: {n} mirrors of {len(d['nk'])} nodes, nx0 {nx0}, {steps} steps, library {os.environ.get('TREEQP_AMD_LIB', 'of this tree')}; "
+          f"member steps with another status than 0: {bad}; blocks regularised over the run of (a) {regs}")
+    m, lo, p90 = stats(t["step"][skip:])
+    print(f"    {'batch step':36s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}", flush=True)
+    rows = [("a_sens", "(a) sensitivity_batch"), ("a_pred", "(a) predict_batch, duals")] if batched else []
+    for key, what in rows + [("b_sens", f"(b) {n} x sensitivity"), ("b_pred", f"(b) {n} x predict, duals")]:
+        m, lo, p90 = stats(t[key][skip:])
+        print(f"    {what:36s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d" % med(c[key]), flush=True)
+    if batched:
+        print(f"    (b) / (a) wall: sensitivity {np.median(t['b_sens'][skip:]) / np.median(t['a_sens'][skip:]):.2f}, predictor "
+              f"{np.median(t['b_pred'][skip:]) / np.median(t['a_pred'][skip:]):.2f}; largest |K (a) - K (b)| over the run {dK:.2e}, largest |u0_pred (a) - u0_pred (b)| {dU:.2e}", flush=True)
+    print("    iterations per step, mean over members and steps: " + ", ".join(
+        f"{what} {np.mean(iters[key][skip:]):.2f}" for key, what in (("a", "(a) batched dual predictor"), ("b", "(b) single dual predictors"), ("c", "mode 1 alone")) if key in legs), flush=True)
+
+
 def adjoint_matrices_compare(capi, name, p, root_states, n, steps, skip):
     """--adjoint-matrices [--adjoint-batch N]: behind every step and adjoint of n trees (n == 0: one tree through the single calls), two
     ways to the gradients of the matrices with one group for all dynamics and one for all stage Hessians of equal sizes (the leaves, and
@@ -1067,6 +1175,14 @@ def main():
     names = [a for a in args if a in ("c1", "c2", "batch", "kind3")] or ["c1", "c2", "batch"]
     if capi.device_count() < 1:
         raise SystemExit("no HIP device")
+    if "--gain-batch" in args:
+        sizes = [int(v) for v in args[args.index("--gain-batch") + 1].split(",")]          # N, or N1,N2,.. in one process
+        for nb in sizes:
+            if "c1" in names:
+                gain_batch_compare(capi, "c1", P.spring_mass(), False, nb, steps, skip)
+            if "c2" in names:
+                gain_batch_compare(capi, "c2", P.linear_chain(2, 9, 9), True, nb, steps, skip)
+        return
     if "--gain" in args:
         if "c1" in names:
             gain_compare(capi, "c1", P.spring_mass(), True, steps, skip)

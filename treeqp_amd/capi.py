@@ -598,6 +598,37 @@ def mpc_adjoint_batch(mirrors, wxs=None, wus=None, profile=0, **kw) -> list:
     return [dict(gx0=g[at[i]:at[i + 1]].copy().reshape((nx0[i], nw), order="F"), n_reg=int(nr[i])) for i in range(n)]
 
 
+def mpc_sensitivity_batch(mirrors, profile=0, **kw) -> list:
+    """Sensitivities of the last solve's point of every mirror (tqgpu_mpc_sensitivity_batch): the members of one device in one set of
+    launches, two copies and one wait.  Returns n_reg per member; the results stay on the device in every member's own buffers
+    (TqGpu.mpc_gain, mpc_sensitivities, mpc_predict of the member, or mpc_predict_batch)."""
+    n = len(mirrors)
+    o = _gpu_opts(profile, **kw)
+    arr = (C.c_void_p * max(n, 1))(*[m.h for m in mirrors])
+    nr = np.zeros(max(n, 1), dtype=np.int32)
+    rc = lib().tqgpu_mpc_sensitivity_batch(arr, n, C.byref(o), _ip(nr))
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_mpc_sensitivity_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    return [int(v) for v in nr[:n]]
+
+
+def mpc_predict_batch(mirrors, x0s, duals=False) -> tuple:
+    """u0* + K (x0_new - x0_ref) of every mirror in one launch per device (tqgpu_mpc_predict_batch): x0s, one vector of nx0 entries per
+    member -> (list of u0_pred, list of n_clipped).  duals: the same launch writes every member's predicted duals into its start buffer,
+    for one solve, as TqGpu.mpc_predict does."""
+    n = len(mirrors)
+    assert len(x0s) == n and all(len(np.ravel(v)) == m.nx0 for v, m in zip(x0s, mirrors)), "x0s: nx0 entries per member"
+    x = _f64(np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in x0s])) if n else _f64(np.zeros(1))
+    nu0 = [int(m.nu[0]) for m in mirrors]
+    u, nc = np.zeros(max(sum(nu0), 1)), np.zeros(max(n, 1), dtype=np.int32)
+    arr = (C.c_void_p * max(n, 1))(*[m.h for m in mirrors])
+    rc = lib().tqgpu_mpc_predict_batch(arr, n, _dp(x), _dp(u), int(bool(duals)), _ip(nc))
+    if rc != 0:
+        raise RuntimeError(f"tqgpu_mpc_predict_batch failed ({rc}): {lib().tqgpu_last_error().decode()}")
+    at = np.concatenate([[0], np.cumsum(nu0)]).astype(int)
+    return [u[at[i]:at[i + 1]].copy() for i in range(n)], [int(v) for v in nc[:n]]
+
+
 ADJMAT_KEYS = ("gH", "gh", "gA", "gB", "gb", "gA0", "gS0")
 
 

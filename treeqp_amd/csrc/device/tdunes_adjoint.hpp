@@ -1,7 +1,7 @@
 /*
  * tdunes_adjoint.hpp -- the host side of the derivatives of an MPC step, in the host part: the entry points tqgpu_mpc_sensitivity, tqgpu_mpc_adjoint,
- * tqgpu_mpc_adjoint_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, and the readers tqgpu_mpc_get_gain,
- * _get_sensitivities, _predict, _get_adjoint*.  Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
+ * tqgpu_mpc_adjoint_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, and the
+ * readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
  * Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind tdunes_mpc.hpp (mpc_refuse, mpc_take_x0, MpcLive) and tdunes_kkt.hpp
  * (enqueue_export, export_all_entry).  That file keeps the mirror's records MpcSens, MpcAdjBatch, MpcAdjMat and the plan of a batched call
  * (DeviceGroup .. order_behind_lead).
@@ -188,15 +188,10 @@ void adj_store(tqgpu_solver *s, const Sens &S, const double *h, int nw, double *
 }
 }  // namespace
 
-extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *n_reg) {
-    const char *who = "tqgpu_mpc_sensitivity";
+/* one mirror on its own stream, behind the refusals that touch nothing; counted into whatever record is live (tqgpu_mpc_sensitivity's own, or that of a
+ * tqgpu_mpc_sensitivity_batch that goes member by member) */
+static int mpc_sensitivity_one(tqgpu_solver *s, const Opts &O, int *n_reg) {
     int rc;
-    if ((rc = sens_refuse(s, o, who))) return rc;
-    Opts O;
-    if ((rc = opts_from(o, O))) return rc;
-    SETTLE(s);
-    HIP_TRY(hipSetDevice(s->device));
-    MpcLive live;
     if ((rc = setup_sens(s))) return rc;
     s->sens.valid = s->sens.factored = false;
     Sens S;
@@ -214,6 +209,17 @@ extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *
     s->sens.valid = s->sens.factored = true;
     if (n_reg) *n_reg = (int)s->sens.h[head - 1];
     return TQGPU_OK;
+}
+extern "C" int tqgpu_mpc_sensitivity(tqgpu_solver *s, const tqgpu_opts *o, int *n_reg) {
+    const char *who = "tqgpu_mpc_sensitivity";
+    int rc;
+    if ((rc = sens_refuse(s, o, who))) return rc;
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    return mpc_sensitivity_one(s, O, n_reg);
 }
 
 /* ---- the adjoint of an MPC step (tdunes_sens.hpp): dL/dq, dL/dr, dL/db, dL/dx0 for w = dL/dz at the point of the last solve ---- */
@@ -451,6 +457,149 @@ extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgp
             const int i = g.idx[m];
             adj_store(solvers[i], views[gi][m], h, nw, gx0 ? gx0 + span[(size_t)i].gx0 : nullptr, n_reg ? n_reg + i : nullptr);
             h += (size_t)solvers[i]->sens.nx0 * nw + 1;
+        }
+    }
+    return TQGPU_OK;
+}
+
+/* ---- tqgpu_mpc_sensitivity_batch: per device one group; a group of SENS_BATCH_MIN members or more goes out as ONE set of launches on its first
+ * member's stream (the lead's), anything else member by member through mpc_sensitivity_one.  Groups on more than one device are built like the
+ * adjoint's; only one device could be tested ---- */
+namespace {
+constexpr int SENS_BATCH_MIN = 2;                /* members of one device from which the batched route is taken: at 2 C1 trees the sensitivity measured 157 us against 290 us member by member, at 4 160 us against 577 us; the predictor with duals 26 us against 42 us, and 28 us against 82 us (profiles/r23_mpc_gain_batch.txt) */
+constexpr size_t SENS_GRID_Z = 65535;            /* blockIdx.z is the member */
+
+/* A group on its lead's stream: the descriptors and level tables in one copy, the launches, the heads of all members in one copy back; nothing is
+ * waited for here in the steady state (order_behind_lead, ADJ_ORDER).  views: per member the view its launches take, kept for the store behind the wait */
+int sens_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> &views, const Opts &O) {
+    tqgpu_solver *lead = v[g.idx[0]];
+    const size_t n = g.idx.size();
+    int rc;
+    HIP_TRY(hipSetDevice(lead->device));
+    size_t heads_all = 0, lvl_ints = 0;
+    for (int i : g.idx) {
+        tqgpu_solver *s = v[i];
+        if ((rc = setup_sens(s))) return rc;
+        heads_all += sens_head_doubles(s); lvl_ints += 2 * (size_t)s->T.Nh;
+    }
+    MpcSensBatch &B = lead->sensb;
+    const size_t items_bytes = n * sizeof(AItem);
+    if ((rc = grow_items(lead, B.d_desc, B.h_desc, B.desc_cap, items_bytes + lvl_ints * sizeof(int), "the descriptors of a batched sensitivity")) ||
+        (rc = grow_items(lead, B.d_heads, B.h_heads, B.heads_cap, heads_all, "the heads of a batched sensitivity")))
+        return rc;
+    AItem *items = reinterpret_cast<AItem *>(B.h_desc);
+    int *h_lvl = reinterpret_cast<int *>(B.h_desc + items_bytes);
+    const int *d_lvl = reinterpret_cast<const int *>(B.d_desc + items_bytes);
+    /* widths of the grids: per launch the largest member's extent */
+    int np_all = 0, nn_all = 0, cells = 0, nh_all = 0, nx0_all = 0;
+    size_t l_hess = 0, l_factor = 0, l_sweep = 0, l_primal = 0;
+    std::vector<int> wide_fac, wide_fwd;
+    std::vector<hipStream_t> waited;
+    int waits = 0;
+    size_t h_at = 0, l_at = 0;
+    views.assign(n, Sens{});
+    for (size_t m = 0; m < n; m++) {
+        tqgpu_solver *s = v[g.idx[m]];
+        if ((rc = order_behind_lead(s, lead, s->sensb.drained_at, ADJ_ORDER, waited, waits))) return rc;
+        MpcSens &ms = s->sens;
+        ms.valid = ms.factored = false;
+        const ExportSizes z = export_sizes(s);
+        AItem &it = items[m];
+        it = AItem{};
+        it.T = s->T; it.D = s->D; it.O = O;
+        it.needs_factor = 1;          /* like the single call: always built anew */
+        it.needs_export = s->out.valid ? 0 : 1;
+        it.S = views[m] = sens_view_of_point(s);
+        it.head_out = B.d_heads + h_at;
+        h_at += sens_head_doubles(s);
+        const int Nh = s->T.Nh;
+        it.lvl = d_lvl + l_at;
+        for (int l = 0; l < Nh; l++) { h_lvl[l_at + 2 * l] = s->lvl_first[l]; h_lvl[l_at + 2 * l + 1] = s->lvl_first[l + 1] - s->lvl_first[l]; }
+        l_at += 2 * (size_t)Nh;
+        it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
+        it.d_out = s->out.d;
+        it.x_pad = s->x_pad; it.nxe = z.nxe; it.nue = z.nue; it.nl = z.nl; it.nx0 = s->nx0;
+        np_all = std::max(np_all, s->T.Np); nn_all = std::max(nn_all, s->T.Nn); nh_all = std::max(nh_all, Nh); nx0_all = std::max(nx0_all, ms.nx0);
+        if ((int)wide_fac.size() < Nh) { wide_fac.resize(Nh, 0); wide_fwd.resize(Nh, 0); }
+        for (int l = 0; l < Nh; l++) {
+            const int count = s->lvl_first[l + 1] - s->lvl_first[l];
+            wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], count);
+            if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
+        }
+        l_hess = std::max(l_hess, s->lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
+        l_sweep = std::max(l_sweep, s->lds_forward); l_primal = std::max(l_primal, ms.lds_primal);
+        if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
+    }
+    MPC_COUNT(waits, waits);
+    if ((rc = allow_lds(k_sens_hess_batch, l_hess)) || (rc = allow_lds(k_sens_factor_batch, l_factor)) || (rc = allow_lds(k_sens_forward_batch, l_sweep)) ||
+        (rc = allow_lds(k_sens_primal_batch, l_primal)))
+        return rc;
+    hipStream_t ls = lead->stream;
+    const unsigned nz = (unsigned)n;
+    const AItem *d_items = reinterpret_cast<const AItem *>(B.d_desc);
+    HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, items_bytes + lvl_ints * sizeof(int), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
+    if (cells) { hipLaunchKernelGGL(k_adj_export_batch, dim3((unsigned)((cells + 255) / 256), nz), dim3(256), 0, ls, d_items); MPC_COUNT(launches, 1); }
+    hipLaunchKernelGGL(k_sens_hess_batch, dim3((unsigned)np_all, 1, nz), dim3(WAVE), l_hess, ls, d_items);
+    for (int j = 0; j < nh_all; j++) hipLaunchKernelGGL(k_sens_factor_batch, dim3((unsigned)wide_fac[j], 1, nz), dim3(WAVE), l_factor, ls, d_items, j);
+    for (int j = 0; j + 1 < nh_all; j++) hipLaunchKernelGGL(k_sens_forward_batch, dim3((unsigned)wide_fwd[j], (unsigned)nx0_all, nz), dim3(WAVE), l_sweep, ls, d_items, j);
+    hipLaunchKernelGGL(k_sens_primal_batch, dim3((unsigned)nn_all, 1, nz), dim3(WAVE), l_primal, ls, d_items);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, (1 + nh_all) + (nh_all - 1) + 1);
+    HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
+    lead->stream_pending = true;
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_sensitivity_batch(tqgpu_solver **solvers, int n, const tqgpu_opts *o, int *n_reg) {
+    const char *who = "tqgpu_mpc_sensitivity_batch";
+    if (!solvers || n < 1 || !o) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and opts are required, n must be at least 1)");
+    int rc;
+    /* the refusals, all of them before any member is touched */
+    std::set<const tqgpu_solver *> seen;
+    for (int i = 0; i < n; i++) {
+        size_t lf, lp;
+        if ((rc = sens_refuse(solvers[i], o, who)) || (rc = sens_window_refuse(solvers[i], lf, lp))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
+        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
+    }
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    const bool by_member = batch_by_member("TREEQP_AMD_SENS_BATCH");          /* every member through tqgpu_mpc_sensitivity's own route */
+    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    std::vector<std::vector<Sens>> views(groups.size());          /* of a batched group's members, from the enqueue to the store */
+    MpcLive live;
+    /* everything goes out before the first wait of a batched group; a group that goes member by member waits member by member */
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        DeviceGroup &g = groups[gi];
+        g.batched = !by_member && group_fits_one_grid(solvers, g, SENS_BATCH_MIN, SENS_GRID_Z);
+        if (g.batched) {
+            if ((rc = sens_group_enqueue(solvers, g, views[gi], O))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
+            continue;
+        }
+        for (int i : g.idx) {
+            tqgpu_solver *s = solvers[i];
+            SETTLE(s);
+            HIP_TRY(hipSetDevice(s->device));
+            if ((rc = mpc_sensitivity_one(s, O, n_reg ? n_reg + i : nullptr))) return rc;
+        }
+    }
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        const DeviceGroup &g = groups[gi];
+        if (!g.batched) continue;
+        tqgpu_solver *lead = solvers[g.idx[0]];
+        HIP_TRY(hipSetDevice(lead->device));
+        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
+        lead->stream_pending = false;
+        /* every member's pinned head from the group's copy, then its flags: as its own call leaves it */
+        const double *h = lead->sensb.h_heads;
+        for (size_t m = 0; m < g.idx.size(); m++) {
+            tqgpu_solver *s = solvers[g.idx[m]];
+            const size_t head = sens_head_doubles(s);
+            memcpy(s->sens.h, h, sizeof(double) * head);
+            s->sens.v = views[gi][m];
+            s->sens.valid = s->sens.factored = true;
+            if (n_reg) n_reg[g.idx[m]] = (int)h[head - 1];
+            h += head;
         }
     }
     return TQGPU_OK;
@@ -804,6 +953,38 @@ extern "C" int tqgpu_mpc_get_sensitivities(tqgpu_solver *s, double *dx, double *
     return TQGPU_OK;
 }
 
+/* the predicted duals take the start buffer for ONE solve, as the shifted ones of tqgpu_mpc_shift do: in mode 0 the kernel saves the caller's buffer
+ * (once) and the solve after the next puts it back (solve_begin).  predict_keep: where the kernel saves it (allocated on first use; nullptr: nothing
+ * to save), before the launch; predict_lent: the host's flags, behind the launch */
+static int predict_keep(tqgpu_solver *s, int duals, double *&keep) {
+    int rc;
+    const bool lend = duals && s->warm.mode == 0;
+    if (lend && !s->shift.d_keep && (rc = s->mem.zeroed(s->shift.d_keep, sizeof(double) * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the saved start buffer"))) return rc;
+    keep = lend && s->shift.restore == 0 ? s->shift.d_keep : nullptr;
+    return TQGPU_OK;
+}
+static void predict_lent(tqgpu_solver *s, int duals) {
+    if (!duals) return;
+    if (s->warm.mode == 0) s->shift.restore = 1;
+    s->warm.fresh = true;          /* the next solve starts from the start buffer as it is now, in any mode */
+    s->lam_valid = false;
+}
+/* one mirror on its own stream, behind the refusals that touch nothing; counted into whatever record is live */
+static int mpc_predict_one(tqgpu_solver *s, const double *x0_new, double *u0_pred, int duals, int *n_clipped) {
+    int rc;
+    const size_t nu0 = (size_t)s->nu[0], nx0 = (size_t)s->sens.nx0, head = sens_head_doubles(s);
+    double *x0n = s->sens.h + head, *out = x0n + nx0;
+    memcpy(x0n, x0_new, sizeof(double) * nx0);
+    double *keep = nullptr;
+    if ((rc = predict_keep(s, duals, keep))) return rc;
+    hipLaunchKernelGGL(k_mpc_predict, dim3(duals ? 1 + (unsigned)s->Nn : 1u), dim3(WAVE), 0, s->stream, s->T, s->D, s->sens.v, (const double *)x0n, s->d_lam_init, keep, out);
+    HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
+    predict_lent(s, duals);
+    HIP_TRY(hipStreamSynchronize(s->stream)); MPC_COUNT(waits, 1);
+    if (u0_pred && nu0) memcpy(u0_pred, out, sizeof(double) * nu0);
+    if (n_clipped) *n_clipped = (int)out[nu0];
+    return TQGPU_OK;
+}
 extern "C" int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, int duals, int *n_clipped) {
     int rc;
     if ((rc = mpc_refuse(s, "tqgpu_mpc_predict")) || (rc = sens_need(s, "tqgpu_mpc_predict"))) return rc;
@@ -811,23 +992,103 @@ extern "C" int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *
     SETTLE(s);
     HIP_TRY(hipSetDevice(s->device));
     MpcLive live;
-    const size_t nu0 = (size_t)s->nu[0], nx0 = (size_t)s->sens.nx0, head = sens_head_doubles(s);
-    double *x0n = s->sens.h + head, *out = x0n + nx0;
-    memcpy(x0n, x0_new, sizeof(double) * nx0);
-    /* the predicted duals take the start buffer for ONE solve, as the shifted ones of tqgpu_mpc_shift do: in mode 0 the kernel saves the
-     * caller's buffer (once) and the solve after the next puts it back (solve_begin) */
-    const bool lend = duals && s->warm.mode == 0;
-    if (lend && !s->shift.d_keep && (rc = s->mem.zeroed(s->shift.d_keep, sizeof(double) * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the saved start buffer"))) return rc;
-    double *keep = lend && s->shift.restore == 0 ? s->shift.d_keep : nullptr;
-    hipLaunchKernelGGL(k_mpc_predict, dim3(duals ? 1 + (unsigned)s->Nn : 1u), dim3(WAVE), 0, s->stream, s->T, s->D, s->sens.v, (const double *)x0n, s->d_lam_init, keep, out);
-    HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
-    if (duals) {
-        if (lend) s->shift.restore = 1;
-        s->warm.fresh = true;          /* the next solve starts from the start buffer as it is now, in any mode */
-        s->lam_valid = false;
+    return mpc_predict_one(s, x0_new, u0_pred, duals, n_clipped);
+}
+
+/* ---- tqgpu_mpc_predict_batch: per device one group, one launch on the lead's stream over all members; x0_new and the results travel through a pinned
+ * block of the lead, which the kernel reads and writes in place, as the single call does through the mirror's ---- */
+namespace {
+struct PredSpan { size_t x0, u0; };          /* where a member's blocks begin in the caller's x0_new and u0_pred */
+int predict_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, const double *x0_new, int duals, const std::vector<PredSpan> &span) {
+    tqgpu_solver *lead = v[g.idx[0]];
+    MpcSensBatch &B = lead->sensb;
+    const size_t n = g.idx.size();
+    int rc;
+    HIP_TRY(hipSetDevice(lead->device));
+    size_t io_all = 0;
+    for (int i : g.idx) io_all += (size_t)v[i]->sens.nx0 + (size_t)v[i]->nu[0] + 1;
+    if ((rc = grow_items(lead, B.d_pdesc, B.h_pdesc, B.pdesc_cap, n * sizeof(PredItem), "the descriptors of a batched predictor"))) return rc;
+    if (!B.h_io || B.io_cap < io_all) {
+        lead->mem.release(B.h_io); B.io_cap = 0;
+        if ((rc = lead->mem.host(B.h_io, sizeof(double) * 2 * io_all, "the pinned block of a batched predictor"))) return rc;
+        B.io_cap = 2 * io_all;
     }
-    HIP_TRY(hipStreamSynchronize(s->stream)); MPC_COUNT(waits, 1);
-    if (u0_pred && nu0) memcpy(u0_pred, out, sizeof(double) * nu0);
-    if (n_clipped) *n_clipped = (int)out[nu0];
+    PredItem *items = reinterpret_cast<PredItem *>(B.h_pdesc);
+    std::vector<hipStream_t> waited;
+    int waits = 0, nn_all = 0;
+    size_t at = 0;
+    for (size_t m = 0; m < n; m++) {
+        tqgpu_solver *s = v[g.idx[m]];
+        /* behind a sensitivity that returned behind its wait, no solve since: only uploads (a start buffer) can be pending on the member's own stream */
+        if ((rc = order_behind_lead(s, lead, s->sensb.drained_at, ADJMAT_ORDER, waited, waits))) return rc;
+        const size_t nx0 = (size_t)s->sens.nx0;
+        PredItem &it = items[m];
+        it = PredItem{};
+        it.T = s->T; it.D = s->D; it.S = s->sens.v;
+        double *x0n = B.h_io + at;
+        memcpy(x0n, x0_new + span[(size_t)g.idx[m]].x0, sizeof(double) * nx0);
+        it.x0_new = x0n; it.out = x0n + nx0;
+        at += nx0 + (size_t)s->nu[0] + 1;
+        it.lam_init = s->d_lam_init; it.duals = duals ? 1 : 0;
+        if ((rc = predict_keep(s, duals, it.lam_keep))) return rc;
+        nn_all = std::max(nn_all, s->Nn);
+    }
+    MPC_COUNT(waits, waits);
+    hipStream_t ls = lead->stream;
+    HIP_TRY(hipMemcpyAsync(B.d_pdesc, B.h_pdesc, n * sizeof(PredItem), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
+    hipLaunchKernelGGL(k_mpc_predict_batch, dim3(duals ? 1 + (unsigned)nn_all : 1u, 1, (unsigned)n), dim3(WAVE), 0, ls, reinterpret_cast<const PredItem *>(B.d_pdesc));
+    HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
+    for (int i : g.idx) predict_lent(v[i], duals);
+    lead->stream_pending = true;
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_predict_batch(tqgpu_solver **solvers, int n, const double *x0_new, double *u0_pred, int duals, int *n_clipped) {
+    const char *who = "tqgpu_mpc_predict_batch";
+    if (!solvers || n < 1 || !x0_new) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and x0_new are required, n must be at least 1)");
+    int rc;
+    /* the refusals, all of them before any member is touched */
+    std::set<const tqgpu_solver *> seen;
+    for (int i = 0; i < n; i++) {
+        if ((rc = mpc_refuse(solvers[i], who)) || (rc = sens_need(solvers[i], who))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
+        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
+    }
+    const bool by_member = batch_by_member("TREEQP_AMD_SENS_BATCH");          /* every member through tqgpu_mpc_predict's own route */
+    std::vector<PredSpan> span((size_t)n);
+    {
+        PredSpan at{0, 0};
+        for (int i = 0; i < n; i++) { span[(size_t)i] = at; at.x0 += (size_t)solvers[i]->sens.nx0; at.u0 += (size_t)solvers[i]->nu[0]; }
+    }
+    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    MpcLive live;
+    for (DeviceGroup &g : groups) {
+        g.batched = !by_member && group_fits_one_grid(solvers, g, SENS_BATCH_MIN, SENS_GRID_Z);
+        if (g.batched) {
+            if ((rc = predict_group_enqueue(solvers, g, x0_new, duals, span))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
+            continue;
+        }
+        for (int i : g.idx) {
+            tqgpu_solver *s = solvers[i];
+            SETTLE(s);
+            HIP_TRY(hipSetDevice(s->device));
+            if ((rc = mpc_predict_one(s, x0_new + span[(size_t)i].x0, u0_pred ? u0_pred + span[(size_t)i].u0 : nullptr, duals, n_clipped ? n_clipped + i : nullptr))) return rc;
+        }
+    }
+    for (const DeviceGroup &g : groups) {
+        if (!g.batched) continue;
+        tqgpu_solver *lead = solvers[g.idx[0]];
+        HIP_TRY(hipSetDevice(lead->device));
+        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
+        lead->stream_pending = false;
+        const double *io = lead->sensb.h_io;
+        for (int i : g.idx) {
+            const size_t nx0 = (size_t)solvers[i]->sens.nx0, nu0 = (size_t)solvers[i]->nu[0];
+            const double *out = io + nx0;
+            if (u0_pred && nu0) memcpy(u0_pred + span[(size_t)i].u0, out, sizeof(double) * nu0);
+            if (n_clipped) n_clipped[i] = (int)out[nu0];
+            io += nx0 + nu0 + 1;
+        }
+    }
     return TQGPU_OK;
 }

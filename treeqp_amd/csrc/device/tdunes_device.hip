@@ -1868,7 +1868,7 @@ struct MpcBatchBuf {
 /* tracking (tqgpu_mpc_set_tracking): d, [xtraj T x NXT | utraj T x NUT | q0 (sum_nx, node-indexed as Data::q, phantom root states included) |
  * r0 (sum_nu)] in one device block, the nodes' stages behind it as ints; t0: the window the device's q, r were last folded for (-1: none yet) */
 struct MpcTrack { double *d = nullptr; int T = 0, nxt = 0, nut = 0, t0 = -1; };
-/* ---- what a mirror keeps for the derivatives of an MPC step (tdunes_adjoint.hpp; kernels in tdunes_sens.hpp): MpcSens, MpcAdjBatch, MpcAdjMat ---- */
+/* ---- what a mirror keeps for the derivatives of an MPC step (tdunes_adjoint.hpp; kernels in tdunes_sens.hpp): MpcSens, MpcAdjBatch, MpcSensBatch, MpcAdjMat ---- */
 /* tqgpu_mpc_sensitivity: buffers of its own (setup_sens, on first use; one device block d, views in v); pinned h:
  * [head: K (nu0 x nx0) | u0 (nu0) | x0_ref (nx0) | n_reg] [x0_new (nx0)] [u0_pred (nu0) | n_clipped]; valid: the stored sensitivity
  * belongs to the point and the data the device holds now (cleared by every upload, fold, window move and solve) */
@@ -1894,6 +1894,18 @@ struct MpcAdjBatch {
     char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
     double *d_w = nullptr, *h_w = nullptr; size_t w_cap = 0;
     double *d_heads = nullptr, *h_heads = nullptr; size_t heads_cap = 0;
+};
+/* tqgpu_mpc_sensitivity_batch and tqgpu_mpc_predict_batch, batched route (the first member of a device's group owns them): desc, the descriptors
+ * (AItem) with the members' level tables behind them, one copy per call; heads, the heads of all members ([K | u0 | x0_ref | n_reg] each, AItem::head_out
+ * points into d_heads), one copy back; pdesc, the predictor's descriptors (PredItem), one copy per call; h_io, pinned only, per member
+ * [x0_new (nx0) | u0_pred (nu0) | n_clipped], which the predictor's kernel reads and writes in place.  Capacities: bytes of desc and pdesc, doubles of
+ * heads and io */
+struct MpcSensBatch {
+    long drained_at = 0;                /* as Kkt::drained_at, for the launches of the batched sensitivity */
+    char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
+    double *d_heads = nullptr, *h_heads = nullptr; size_t heads_cap = 0;
+    char *d_pdesc = nullptr, *h_pdesc = nullptr; size_t pdesc_cap = 0;
+    double *h_io = nullptr; size_t io_cap = 0;
 };
 
 /* tqgpu_mpc_set_param_groups / tqgpu_mpc_adjoint_matrices*: the maps as given (a NULL map filled in), the tables built from them and from the kinds, the
@@ -2090,7 +2102,7 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcAdjMat adjm;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, adjm: tdunes_adjoint.hpp), one record per feature */
+    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcSensBatch sensb; MpcAdjMat adjm;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, sensb, adjm: tdunes_adjoint.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;
@@ -3898,7 +3910,7 @@ static int grow_items(tqgpu_solver *s, Item *&d, Item *&h, Cap &cap, size_t need
     return TQGPU_OK;
 }
 
-/* ---- the plan of the batched after-solve calls (tqgpu_kkt_residual_batch, tqgpu_mpc_adjoint_batch, tqgpu_mpc_adjoint_matrices_batch): per device
+/* ---- the plan of the batched after-solve calls (tqgpu_kkt_residual_batch, tqgpu_mpc_adjoint_batch, tqgpu_mpc_adjoint_matrices_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_predict_batch): per device
  * one group; a group that fits one grid goes out as ONE set of launches on its first member's stream (the lead's), anything else member by member ---- */
 struct DeviceGroup { int device; std::vector<int> idx; bool batched = false; };
 static std::vector<DeviceGroup> group_by_device(tqgpu_solver **v, int n) {
@@ -3910,7 +3922,7 @@ static std::vector<DeviceGroup> group_by_device(tqgpu_solver **v, int n) {
     }
     return groups;
 }
-/* TREEQP_AMD_KKT_BATCH, TREEQP_AMD_ADJ_BATCH = members: every member on its own stream, as a group of one goes */
+/* TREEQP_AMD_KKT_BATCH, TREEQP_AMD_ADJ_BATCH, TREEQP_AMD_SENS_BATCH = members: every member on its own stream, as a group of one goes */
 static bool batch_by_member(const char *var) { const char *sw = getenv(var); return sw && strcmp(sw, "members") == 0; }
 /* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
  * waves that return at once, and goes member by member instead.  mx, the largest member's nodes, n members, sum, the nodes of all of them. */

@@ -616,6 +616,7 @@ struct AItem {
     double *d_out;                 /* the member's export block, */
     int x_pad, nxe, nue, nl, nx0;  /* phantom root states, the export sizes (x without them, u, lam), the root's states */
     int needs_export, needs_factor;      /* d_out is not packed yet and the factor has to be built from it; the factor is not stored */
+    double *head_out;              /* the batched sensitivity: where the member's head lies a second time, in the block of all heads of its group's lead */
 };
 __global__ void __launch_bounds__(WAVE) k_sens_hess_batch(const AItem *__restrict__ items)
 #if !TQ_HAS(TQP_SENS)
@@ -684,6 +685,53 @@ __global__ void __launch_bounds__(WAVE) k_adj_grad_batch(const AItem *__restrict
     const AItem &it = items[blockIdx.z];
     if ((int)blockIdx.x >= it.T.Nn || (int)blockIdx.y >= it.A.nw) return;
     adj_grad_body(it.T, it.D, it.S, it.A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+
+/* ---- the sensitivities and the predictor for a batch of mirrors (tqgpu_mpc_sensitivity_batch, tqgpu_mpc_predict_batch) ----
+ * The forward half over the same descriptor: k_adj_export_batch, k_sens_hess_batch and k_sens_factor_batch above with needs_factor set for every
+ * member, then the two kernels below.  blockIdx.y of the forward sweep is the column of x0: the members' nx0 differ, the grid is as tall as the
+ * largest, a wave beyond its member's nx0 returns at once.  The node-0 wave of k_sens_primal_batch fills the member's own head (Sens::head, which
+ * k_mpc_predict reads later) as the single kernel does, and then copies it to AItem::head_out, so that the heads of a group come back in one copy. */
+__global__ void __launch_bounds__(WAVE) k_sens_forward_batch(const AItem *__restrict__ items, int j)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    const int lvl = j + 1;
+    if (lvl >= it.T.Nh || (int)blockIdx.x >= it.lvl[2 * lvl + 1] || (int)blockIdx.y >= it.S.nx0) return;
+    sens_forward_body(it.T, it.S, it.lvl[2 * lvl] + (int)blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_sens_primal_batch(const AItem *__restrict__ items)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const AItem &it = items[blockIdx.z];
+    if ((int)blockIdx.x >= it.T.Nn) return;
+    sens_primal_body(it.T, it.D, it.S, blockIdx.x, threadIdx.x, lds);
+    if (blockIdx.x != 0) return;
+    /* the head this wave has just written, read back by other lanes than wrote it: through a device-scope fence */
+    __threadfence();
+    WSYNC();
+    const int n = it.S.nu0 * it.S.nx0 + it.S.nu0 + it.S.nx0 + 1;
+    for (int e = threadIdx.x; e < n; e += WAVE) it.head_out[e] = it.S.head[e];
+}
+#endif
+/* one member of a batched predictor: what k_mpc_predict takes as kernel arguments.  x0_new and out lie in a pinned block of the group's lead */
+struct PredItem { Tree T; Data D; Sens S; const double *x0_new; double *lam_init, *lam_keep, *out; int duals; };
+__global__ void __launch_bounds__(WAVE) k_mpc_predict_batch(const PredItem *__restrict__ items)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    const PredItem &it = items[blockIdx.z];
+    if (blockIdx.x > 0 && (!it.duals || (int)blockIdx.x - 1 >= it.T.Nn)) return;
+    sens_predict_body(it.T, it.D, it.S, it.x0_new, it.lam_init, it.lam_keep, it.out, blockIdx.x, threadIdx.x);
 }
 #endif
 
