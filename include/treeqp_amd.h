@@ -586,7 +586,13 @@ int tqgpu_set_working_sets(tqgpu_solver *s, const unsigned long long *bounds, co
  *                        direct_0 = -P_0 [0; S0] for an eliminated root, direct_0 = [I; 0] on the root's states for a root with states,
  *                        direct_k = 0 elsewhere.  K = the u rows of dZ_0.
  *   uniqueness           M = E P E', so a null vector v of M gives P E' v = 0: dZ (and K) is unique even where M is singular, as long as
- *                        G lies in the range of M; dLam is unique only when n_reg == 0.
+ *                        G lies in the range of M; dLam is unique only when n_reg == 0.  This holds for an exact solve, and for what the
+ *                        call computes under regType 0: a pivot <= 0 gives a zero column, that entry of dLam is 0.0 and the rest is the
+ *                        solve without it.  The on-the-fly rule (regType 2, the default) adds regValue to the diagonal of the WHOLE
+ *                        flagged block: where M is singular (a pinned state, xmin == xmax) dZ and K then differ from the exact
+ *                        derivative by O(regValue), some 1e-6 at the default regValue = 1e-6.  Pinned by tests/test_sens_reg_reference.py
+ *                        (test_the_zero_column_is_the_exact_derivative, test_the_default_shift_moves_dz_by_its_size) and
+ *                        tests/test_gpu_mpc_sens_reg.py.
  *   tqgpu_mpc_sensitivity   evaluates all of it for the point of the last solve, whatever its route and status.  Like tqgpu_kkt_residual it
  *                        reads the export block (the packing is enqueued unless it went out ahead or a certified step packed the point)
  *                        and the problem data in place.  Launches, one wave per unit, ordered by launch boundaries on the mirror's
@@ -634,7 +640,9 @@ int tqgpu_mpc_predict(tqgpu_solver *s, const double *x0_new, double *u0_pred, in
  *   gx0                  eliminated root (tqgpu_mpc_set_root):  gx0 = sum_c A0_c' Y_c + S0' gr_0  (the second term where S0 was given);
  *                        root with states (tqgpu_mpc_set_root_states):  gx0 = wx_0 + sum_c A_c' Y_c.
  *   uniqueness           R lies in the range of M = E P E', so gq and gr are unique even where M is singular;
- *                        gb is unique only when n_reg == 0, and on the same condition gx0 of an eliminated root.
+ *                        gb is unique only when n_reg == 0, and on the same condition gx0 of an eliminated root.  As for the
+ *                        sensitivities: true of an exact solve and of the zero column of regType 0; under the on-the-fly shift gq, gr and
+ *                        gx0 move by O(regValue) with the whole flagged block.
  *   tqgpu_mpc_adjoint    wx ((sum_nx without phantom root states) x nw) and wu (sum_nu x nw): column j is the flat layout of
  *                        tqgpu_get_solution; either may be NULL, meaning zero.  One host-to-device copy of w through pinned memory, the
  *                        launches (one wave per unit and column, the nw columns on grid dimension y, ordered by launch boundaries on the

@@ -3,8 +3,10 @@ loss L of z = [x | u], the gradients gq = dL/dq, gr = dL/dr, gb = dL/db and gx0 
 (a) dense_kkt: the transposed KKT system of sens_ref.dense_kkt (pinned rows included) with the right-hand side [w; 0; 0], by lstsq; the
     gradients are read off its solution, gx0 through the chain rule of the parameter form;
 (b) dual_form: R_c = (P_c w_c)^x - C_c P_p w_p, M Y = R, gb = Y, [gq; gr] = -P (w - [Y; 0] + sum_c C_c' Y_c) as include/treeqp_amd.h
-    states them, block by block (leaf to root, root, root to leaves) with the regularisation rule of reg_ref.py.
-Both take the arguments of sens_ref (the flat problem d, the point, the parameter form, kinds) and w = (wx, wu), each (rows,) or (rows, nw)
+    states them, block by block (leaf to root, root, root to leaves) with the regularisation rule of reg_ref.py; it also returns what that
+    rule did (sens_ref.RegRecord) and in_range, the residual of the matrix actually solved;
+(c) dense_shifted: that same shifted system by one dense solve, given shift and zero.
+(a) and (b) take the arguments of sens_ref (the flat problem d, the point, the parameter form, kinds) and w = (wx, wu), each (rows,) or (rows, nw)
 in the flat layout of tqgpu_get_solution, and return dict(gq, gr, gb, gx0, ...) with nw columns."""
 from __future__ import annotations
 
@@ -77,12 +79,15 @@ def dual_form(d, x, u, param, w, kinds=None, regType=2, regTol=1e-6, regValue=1e
     own = lambda p: np.arange(xo[p], xo[p + 1]) - nx[0]
     Wb = {p: M[np.ix_(rng_of(p), rng_of(p))].copy() for p in range(Np)}
     fac, n_reg = {}, 0
+    rec = SR.RegRecord(SL)
     for p in range(Np - 1, -1, -1):
         Wp = Wb[p] + (regValue * np.eye(len(Wb[p])) if regType == 1 else 0.0)
         L, inv = RR.potrf(Wp)
+        rec.first_pass(p, rng_of(p), np.diag(L), regType, regTol, regValue)
         if regType == 2 and np.any(np.diag(L) <= regTol):
             n_reg += 1
             L, inv = RR.potrf(Wp + regValue * np.eye(len(Wp)))
+        rec.final(rng_of(p), inv)
         CUt = None
         if p > 0:
             CUt = RR._right_solve(M[np.ix_(own(p), rng_of(p))], L, inv)
@@ -104,4 +109,18 @@ def dual_form(d, x, u, param, w, kinds=None, regType=2, regTol=1e-6, regValue=1e
     gz = -Pm @ (W + E.T @ Y)
     direct = W[:nx0] + E[:, :nx0].T @ Y if param["form"] == "states" else None
     return dict(gq=gz[:SX], gr=gz[SX:], gb=Y, gx0=_gx0(t, param, db, dg, nx0, gz, Y, direct), n_reg=n_reg,
-                in_range=float(np.max(np.abs(M @ Y - R))) if SL else 0.0)
+                in_range=rec.in_range(M, Y, R), **rec.fields())
+
+
+def dense_shifted(d, x, u, param, w, shift, zero, kinds=None):
+    """(c): the system dual_form solved, (M + diag(shift)) Y = R without the zero-column entries, by one dense solve (sens_ref.shifted_solve:
+    float64 refined once in longdouble), then the gq / gr / gb / gx0 formulas.  Takes only shift and zero from dual_form; shares no
+    elimination with it."""
+    t, Pm, M = SR.dual_system(d, x, u, kinds)
+    db, dg, nx0 = SR._param_terms(t, param)
+    W = stack(t, w)
+    E, SX = t["E"], t["SX"]
+    Y = SR.shifted_solve(M, shift, zero, -E @ (Pm @ W))
+    gz = -Pm @ (W + E.T @ Y)
+    direct = W[:nx0] + E[:, :nx0].T @ Y if param["form"] == "states" else None
+    return dict(gq=gz[:SX], gr=gz[SX:], gb=Y, gx0=_gx0(t, param, db, dg, nx0, gz, Y, direct))

@@ -1,8 +1,10 @@
 """Sensitivities of a tree QP's solution with respect to x0 at a point (x, u) with the active set frozen there, two ways in numpy:
 (a) dense_kkt: the equality-constrained QP with the entries that sit on a bound pinned, differentiated in x0, solved by lstsq;
 (b) dual_form: M dLam = G, dZ = P (..) + direct as include/treeqp_amd.h states them, block by block with the regularisation rule
-    of reg_ref.py.
-Both take the flat problem d (clipping: Qd, Rd; kinds given: Q, R, S column major), the point and the parameter form:
+    of reg_ref.py; it also returns what that rule did (class RegRecord: flagged, pivots, shift, zero, guard), and in_range, the residual
+    of the matrix actually solved, M + diag(shift) without the zero-column entries;
+(c) dense_shifted: that same shifted system by one dense solve (float64, refined once in longdouble), given shift and zero.
+(a) and (b) take the flat problem d (clipping: Qd, Rd; kinds given: Q, R, S column major), the point and the parameter form:
     dict(form="eliminated", A0=[(nx[kid], nx0) ...], S0=None or (nu[0], nx0))      x0 enters b of the root's children and r[0]
     dict(form="states")                                                            x0 enters as xmin[0] = xmax[0] = x0
 and return dict(K, dx, du, dlam, ...), column j for parameter x0[j], rows in the flat layout of tqgpu_get_solution."""
@@ -138,12 +140,15 @@ def dual_form(d, x, u, param, kinds=None, regType=2, regTol=1e-6, regValue=1e-6)
     own = lambda p: np.arange(xo[p], xo[p + 1]) - nx[0]
     W = {p: M[np.ix_(rng_of(p), rng_of(p))].copy() for p in range(Np)}
     fac, n_reg = {}, 0
+    rec = RegRecord(SL)
     for p in range(Np - 1, -1, -1):
         Wp = W[p] + (regValue * np.eye(len(W[p])) if regType == 1 else 0.0)
         L, inv = RR.potrf(Wp)
+        rec.first_pass(p, rng_of(p), np.diag(L), regType, regTol, regValue)
         if regType == 2 and np.any(np.diag(L) <= regTol):
             n_reg += 1
             L, inv = RR.potrf(Wp + regValue * np.eye(len(Wp)))
+        rec.final(rng_of(p), inv)
         Y = None
         if p > 0:
             Ut = M[np.ix_(own(p), rng_of(p))]
@@ -160,5 +165,88 @@ def dual_form(d, x, u, param, kinds=None, regType=2, regTol=1e-6, regValue=1e-6)
             dlam[rng_of(p), j] = -RR._backward(L, inv, Y.T @ dlam[own(p), j])
     dz = -Pm @ E.T @ dlam + direct
     out = _split(t, dz, dlam)
-    out.update(n_reg=n_reg, in_range=float(np.max(np.abs(M @ dlam - G))) if SL else 0.0)
+    out.update(n_reg=n_reg, in_range=rec.in_range(M, dlam, G), **rec.fields())
     return out
+
+
+class RegRecord:
+    """What the block elimination of dual_form (here and in adj_ref) did to the matrix it solved, kept as reg_ref.block_newton_step keeps it:
+    flagged: the blocks (parent ids, in the order they are factorised) whose diagonal was shifted;
+    pivots: per block the L_jj of the first pass, all of them;
+    shift, zero: per dual entry, what was added to its diagonal and whether its column of the factor in use is a zero column;
+    guard: the smallest, over every non-zero L_jj of a first pass, of max(L_jj / regTol, regTol / L_jj) (regType 0 and 1 do not compare
+    with regTol: L_jj / regTol there); an exact 0 counts as infinity, and so does every L_jj where regTol is 0."""
+
+    def __init__(self, SL):
+        self.flagged, self.pivots, self.guard = [], {}, np.inf
+        self.shift, self.zero = np.zeros(SL), np.zeros(SL, dtype=bool)
+
+    def first_pass(self, p, rows, diag, regType, regTol, regValue):
+        diag = np.array(diag, dtype=np.float64, copy=True)
+        self.pivots[p] = diag
+        for v in diag[diag != 0]:
+            if regTol > 0:
+                self.guard = min(self.guard, float(max(v / regTol, regTol / v) if regType == 2 else v / regTol))
+        if regType == 1 or (regType == 2 and np.any(diag <= regTol)):
+            self.flagged.append(p)
+            self.shift[rows] += regValue
+
+    def final(self, rows, inv):
+        self.zero[rows] = np.asarray(inv) == 0
+
+    def in_range(self, M, sol, rhs):
+        """max |(M + diag(shift)) sol - rhs| over the entries that are not zero columns: the matrix actually solved"""
+        keep = ~self.zero
+        if not np.any(keep):
+            return 0.0
+        Ms = (M + np.diag(self.shift))[np.ix_(keep, keep)]
+        return float(np.max(np.abs(Ms @ sol[keep] - rhs[keep]), initial=0.0))
+
+    def fields(self):
+        return dict(flagged=list(self.flagged), pivots=self.pivots, shift=self.shift.copy(), zero=self.zero.copy(), guard=self.guard)
+
+
+def _refined_solve(Ms, rhs):
+    """one dense float64 solve refined once in longdouble, as reg_ref.block_newton_step does its cross-check"""
+    LD = np.longdouble
+    M64 = Ms.astype(np.float64)
+    x = np.linalg.solve(M64, rhs.astype(np.float64)).astype(LD)
+    x = x + np.linalg.solve(M64, (rhs.astype(LD) - Ms.astype(LD) @ x).astype(np.float64)).astype(LD)
+    return x.astype(np.float64)
+
+
+def dual_system(d, x, u, kinds=None):
+    """(t, P, M = E P E') at the point, for dense_shifted here and in adj_ref: no elimination, no regularisation"""
+    t = _assemble(d, kinds)
+    on = pinned(d, x, u, kinds)
+    Pm = np.zeros((t["n"], t["n"]))
+    for k in range(t["Nn"]):
+        ii = t["idx"][k]
+        if t["kinds"][k] == 0:
+            free = ii[~on[ii]]
+            Pm[free, free] = 1.0 / t["H"][free, free]
+        elif len(ii):
+            Pm[np.ix_(ii, ii)] = np.linalg.inv(t["H"][np.ix_(ii, ii)])
+    return t, Pm, t["E"] @ Pm @ t["E"].T
+
+
+def shifted_solve(M, shift, zero, rhs):
+    """(M + diag(shift)) without the zero-column entries, solved densely for every column of rhs; the zero-column entries get 0.0"""
+    keep = ~np.asarray(zero, dtype=bool)
+    sol = np.zeros_like(rhs, dtype=np.float64)
+    if np.any(keep):
+        sol[keep] = _refined_solve((M + np.diag(shift))[np.ix_(keep, keep)], rhs[keep])
+    return sol
+
+
+def dense_shifted(d, x, u, param, shift, zero, kinds=None):
+    """(c): the system dual_form solved, (M + diag(shift)) dLam = G without the zero-column entries, by one dense solve, then
+    dZ = -P E' dLam + direct.  Takes only shift and zero from dual_form; shares no elimination with it."""
+    t, Pm, M = dual_system(d, x, u, kinds)
+    db, dg, nx0 = _param_terms(t, param)
+    direct = -Pm @ dg
+    if param["form"] == "states":
+        direct[:nx0] = np.eye(nx0)
+    G = t["E"] @ direct + db
+    dlam = shifted_solve(M, shift, zero, G)
+    return _split(t, -Pm @ t["E"].T @ dlam + direct, dlam)
