@@ -541,7 +541,9 @@ int tqgpu_mpc_step_batch_at(tqgpu_solver **solvers, int n, const double *x0s, co
  *                        The next solve starts from the shifted duals, for one solve, in any mode; a mirror in mode 0 starts from the
  *                        buffer of tqgpu_set_lambda again afterwards (the kernel saves it, the solve after the next puts it back with
  *                        one device-to-device copy).  It also moves the working sets if they were asked for.  TQGPU_EINVAL before
- *                        tqgpu_mpc_set_shift and before the mirror's first solve.
+ *                        tqgpu_mpc_set_shift and before the mirror's first solve.  Two calls ahead of one solve: the working sets move
+ *                        twice (the second call gathers what the first stored), the duals once -- every call gathers from the duals
+ *                        of the last solve, which a shift does not touch, so the second call fills the start buffer as the first did.
  *   the working sets     (TQGPU_SHIFT_WORKING_SETS, trees with nodes of kind 2 or 3) in the same launch as the duals, wherever those
  *                        are gathered: node k takes the bound set and its sides from img(k) where both nodes are of kind 2 or 3, nx
  *                        and nu agree, img(k) != -1 and img(k) is not a repeated leaf; under the same conditions it takes the row set

@@ -479,6 +479,10 @@ __device__ void stage_box(const Tree &T, const Data &D, int k, int lane, double 
     }
     if (!ok && lane == 0) { D.ctrl->status = 4; D.ctrl->done = 1; }      /* TREEQP_DN_STAGE_QP_SOLVE_FAILED */
     if (lane == 0) D.bmask[k] = m;
+    /* the sides of the final set, where the tree has rows: a shift may hand this node's set to a node of kind 3, which reads them (bit
+     * set = upper bound; equal bounds count as lower, as stage_gen's).  Without them the word kept whatever was stored there last. */
+    const u64 up = __builtin_amdgcn_ballot_w64(fixed && lo < hi && z == hi);
+    if (lane == 0 && D.gen) D.gen->sides[k] = up & m;
     if (own) {
         if (isx) { if (save_s) D.xUncS[xo + j0] = D.xUnc[xo + j0]; D.x[xo + j0] = z; D.xUnc[xo + j0] = h; }
         else { if (save_s) D.uUncS[uo + j0] = D.uUnc[uo + j0]; D.u[uo + j0] = z; D.uUnc[uo + j0] = h; }

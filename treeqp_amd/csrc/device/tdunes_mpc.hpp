@@ -106,7 +106,12 @@ __device__ __forceinline__ void mpc_track_root_r(const MItem &it, int lane) {
  * its own; the halves [Nn, 2 Nn) that say what P_k was built for are not touched.  m > k for every node that takes a set (images are one
  * level deeper and nodes are numbered level by level), so ONE wave that walks the nodes in ascending chunks of 64, with all loads of a
  * chunk complete ahead of its stores, reads only words no earlier store has replaced: no scratch copy, no atomics, no dependence on the
- * order of blocks (no other block touches these words). */
+ * order of blocks (no other block touches these words).
+ * Tested on trees of more than one chunk: tests/shift_set_cases.py holds them (chains of 64 .. 129 nodes, binary trees of 127 .. 255, a tree
+ * that meets every refusal rule on both sides of lane 63, a tree without rows), the injected words that tell a node from its image, and
+ * numpy walks of this loop, ascending / descending, loads first / lane by lane; tests/test_shift_set_reference.py shows without a device on
+ * which of these trees each clause above can be seen to fail, tests/test_gpu_mpc_shift_sets.py holds the kernel to the out-of-place gather bit
+ * for bit, alone, twice ahead of one solve, with the duals' blocks, in a batch, and after the kinds or nc have changed. */
 __device__ __forceinline__ void mpc_shift_sets(const MItem &it, int lane) {
     const int Nn = it.T.Nn;
     const int *kind = it.D.kind;
