@@ -752,7 +752,8 @@ int tqgpu_mpc_predict_batch(tqgpu_solver **solvers, int n, const double *x0_new,
  *   phantom root states  of an x0-eliminated tree embedded in a uniform one (x_pad states in front of node 0, reported by tqgpu_mpc_get_param_groups)
  *                        count in the sizes of node 0's blocks and of its children's gA; their entries are written 0.0
  * These are gradients with respect to H, A, B as the device holds them.  Under tqgpu_mpc_set_tracking q and r depend on Q, R, S through the
- * fold; that chain rule stays with the caller, who has gh = [gq; gr] of the same groups for it.
+ * fold; for H that chain rule stays with the caller, who has gh = [gq; gr] of the same groups for it (for the reference trajectory itself:
+ * tqgpu_mpc_adjoint_reference below).
  *   groups               a parameter group is a set of nodes whose matrices are one learnable parameter.  hgroup[k] (int[Nn], -1: in no group) is
  *                        the group of node k's stage Hessian: all members have the same nx, nu, kind and phantom states.  cgroup[c] is the group
  *                        of node c's dynamics (A_c, B_c, b_c): all members have the same nx_c, nx_p, nu_p; cgroup[0] must be -1.  A NULL map
@@ -801,6 +802,53 @@ int tqgpu_mpc_set_param_groups(tqgpu_solver *s, const int *hgroup, const int *cg
 int tqgpu_mpc_get_param_groups(tqgpu_solver *s, int *n_hgroups, int *n_cgroups, int *hdims, int *cdims, int *root);
 int tqgpu_mpc_adjoint_matrices(tqgpu_solver *s, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0);
 int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, int reduce, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0);
+
+/* ---- The adjoint of an MPC step in the bounds and in the tracking reference -----------------------------------------------------------------
+ * Behind tqgpu_mpc_adjoint (or tqgpu_mpc_adjoint_batch), for every column j of w.  The frozen-active-set KKT system is H z + g + E' lam + I_A' mu = 0,
+ * E z + b = 0, z_A = l_A; its adjoint K a = [w; 0; 0] gives gq = -a_z, gb = -a_lam = Y and dL/dl_A = a_mu = (w - H a_z - E' a_lam)_A.  On a kind-0
+ * node H is diagonal and a_z vanishes on A, so with v_k = w_k - [Y_k; 0] + sum_c C_c' Y_c, the vector k_adj_grad multiplies by -P_k,
+ *     dL/dbound_k[i] = v_k[i]   where the exported value equals that bound bit for bit (the test that makes P_k[i] = 0.0),
+ *                      0.0      elsewhere, on every entry of a kind-1 node (its bounds are not read) and on phantom root states.
+ *   side                 the value equals xmin (umin): the lower gradient takes v, the upper is 0.0; otherwise it equals xmax (umax): the upper
+ *                        gradient takes v.  Where min == max bit for bit (a pinned entry; every state of a root with states) the lower gradient
+ *                        therefore is the derivative for both bounds moved together: on the states of a root with states it equals gx0 bit for
+ *                        bit.  Wherever a bound gradient is written from v, gq / gr of that entry is 0.0, and the reverse.
+ *   tqgpu_mpc_get_adjoint_bounds   gxmin, gxmax ((sum_nx without phantom root states) x nw), gumin, gumax (sum_nu x nw), column major, the layout
+ *                        of tqgpu_mpc_get_adjoint's gq / gr; any pointer may be NULL.  k_adj_grad (and its batch form: after
+ *                        tqgpu_mpc_adjoint_batch every member holds those of its own call, bit for bit) stores them beside gq, gr in the
+ *                        adjoint's own buffers; this is a diagnostic read-out like tqgpu_mpc_get_adjoint: it downloads, waits and is not
+ *                        counted.  TQGPU_EINVAL where tqgpu_mpc_get_adjoint returns it.
+ * Two sums over node sets are computed on the device (k_nodesum_part, k_nodesum_sum).  The order of each sum is part of the contract.  The members of
+ * a set are taken in ascending node index and cut into chunks of ADJMAT_CHUNK = 64 consecutive members; a chunk's partial is one chain from 0.0 over
+ * its members in that order; a result is the first of its partials plus the others in ascending order.  No atomics: a value depends neither on the
+ * grid nor on which call produced it.  One launch (one wave per chunk and column; a result of one partial is written by its chunk), a second where
+ * a result has more than one partial, one copy through pinned memory and one wait, counted into tqgpu_mpc_stats.  Both calls write only buffers of
+ * their own: a later solve, tqgpu_kkt_residual, a stored sensitivity, the stored adjoint and a result of tqgpu_mpc_adjoint_matrices keep their bits.
+ *   tqgpu_mpc_adjoint_bounds   the bound gradients summed over the h-groups of tqgpu_mpc_set_param_groups (a NULL map: every node its own group).
+ *                        glb, gub: per h-group nx + nu entries [x | u], groups ascending, then columns of w: layout and sizes of gh of
+ *                        tqgpu_mpc_adjoint_matrices (tqgpu_mpc_get_param_groups); either may be NULL.  Per member acc = acc + v[i]; the
+ *                        partials are those of the group's chunks in ascending chunk order.  A kind-1 group's block and phantom entries are
+ *                        written 0.0.  Refusals are those of tqgpu_mpc_adjoint_matrices: no stored adjoint, no groups, a group that has come to
+ *                        mix kinds.
+ *   tqgpu_mpc_adjoint_reference   under tqgpu_mpc_set_tracking the fold of node k reads row rho_k = min(t0 + stage[k], T - 1) and
+ *                        [q_k; r_k] = base_k - H_k [xref; uref]_rho, hence [gxref; guref]_rho = - sum over {k : rho_k = rho} of H_k' [gq_k; gr_k]
+ *                        (dL/dq0, dL/dr0 are gq, gr as they stand).  row0 = min(t0, T - 1) and rows, up to row min(t0 + deepest stage, T - 1),
+ *                        for the window t0 in force; gxref (rows x NXT) and guref (rows x NUT), stage-major like xtraj / utraj, column of w
+ *                        outermost.  Any pointer may be NULL; row0, rows are host state only: with both arrays NULL the call gives the sizes
+ *                        and touches nothing else.  A set is a stage (the member lists and chunks are cut per stage and uploaded once by
+ *                        tqgpu_mpc_set_tracking; they do not depend on t0).  Per member, one chain per entry j:
+ *                          kind 0:  acc[j] = fma(-Qd[j], gq[j], acc[j]),  likewise Rd, gr;
+ *                          kind 1:  for column j of the stored H_k (nz x nz, column major)  acc[j] = fma(-H[i + j nz], gz[i], acc[j]), i ascending
+ *                                   over the rows behind the phantom root states, which contribute nothing and are no columns;
+ *                          an x0-eliminated root with S0, behind its own chain:  acc[j] = fma(-S0[m + j nu0], gr_0[m], acc[j]), m ascending
+ *                                   (the mirror image of + S0' gr_0 in gx0); its own chain gives -R_0 gr_0 to guref.
+ *                        A leaf contributes to gxref only.  A row's partials are those of its stages in ascending (stage, chunk) order: a clamped
+ *                        last row collects several stages, T == 1 all of them.  TQGPU_EINVAL: no stored adjoint, before
+ *                        tqgpu_mpc_set_tracking, no window in force (tqgpu_mpc_get_window gives -1; a window moved after the solve has
+ *                        invalidated the adjoint).  TQGPU_EUNSUPPORTED: what the adjoint refuses (kinds 2 and 3, ranks of a sharded solve). */
+int tqgpu_mpc_get_adjoint_bounds(tqgpu_solver *s, double *gxmin, double *gxmax, double *gumin, double *gumax);
+int tqgpu_mpc_adjoint_bounds(tqgpu_solver *s, double *glb, double *gub);
+int tqgpu_mpc_adjoint_reference(tqgpu_solver *s, double *gxref, double *guref, int *row0, int *rows);
 
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written

@@ -1121,6 +1121,163 @@ def adjoint_matrices_compare(capi, name, p, root_states, n, steps, skip):
     print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |(a) - (b)| over the run: gA {dA:.2e}, gB {dB:.2e}, gHd of the inner nodes {dH:.2e}", flush=True)
 
 
+def adjoint_bounds_compare(capi, name, p, root_states, steps, skip):
+    """--adjoint-bounds: behind every step and adjoint of one tree, two ways to the gradients of the bounds summed over the h-groups of
+    --adjoint-matrices (the inner nodes, the leaves, the root of an x0-eliminated tree), on the same mirror (the second leg only reads):
+    (a) tqgpu_mpc_adjoint_bounds;
+    (b) the host route: tqgpu_mpc_get_adjoint (gb = Y) + tqgpu_get_solution, then v = w - [Y; 0] + sum_c C_c' Y_c rebuilt with numpy from Y, A, B, w,
+        kept where the solution equals a bound, summed per group.
+    Wall time is the host clock around each leg.  Launches, copies and waits of (a) are those tqgpu_mpc_stats counts; the calls of (b) are
+    not counted there, their numbers are what the two calls do: 1 packing launch, 1 + 3 copies, 1 + 1 waits."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, res = capi._gpu_opts(), capi.GpuResult()
+    if root_states:
+        d, x0 = full_root(capi, p)
+        xs = [moved_inward(x0, k, 0) for k in range(steps)]
+    else:
+        d, A0, b0, _, x0 = eliminated(capi, p)
+        xs = [moved(x0, k, 0) for k in range(steps)]
+    nk, nx, nu = [np.asarray(d[k], dtype=int) for k in ("nk", "nx", "nu")]
+    Nn, nxx, nuu, nk0 = len(nk), int(nx[1]), int(nu[0]), int(nk[0])
+    dad = P_parents(nk)
+    inner = np.flatnonzero((nk > 0) & (np.arange(Nn) > 0))
+    assert np.all(nx[1:] == nxx) and np.all(nu[inner] == nuu), "a uniform tree is expected"
+    hgroup = np.where(nk > 0, 0, 1).astype(np.int32)
+    if not root_states:
+        hgroup[0] = 2
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    if root_states:
+        g.mpc_set_root_states()
+    else:
+        g.mpc_set_root(A0, b0)
+    g.set_warm_start(1)
+    cg = np.full(Nn, -1, dtype=np.int32)
+    g.mpc_set_param_groups(hgroup, cg)
+    snx, snu, snl = int(g.sum_nx), int(g.sum_nu), int(g.sum_lam)
+    nzi = nxx + nuu
+    glb, gub = np.zeros(4 * (2 * nzi + nxx)), np.zeros(4 * (2 * nzi + nxx))
+    # the children's [A B], child after child: the children of an eliminated root have no A
+    first = 1 if root_states else 1 + nk0
+    A3 = np.asarray(d["A"], dtype=np.float64).reshape((Nn - first, nxx, nxx)).transpose((0, 2, 1))
+    B3 = np.asarray(d["B"], dtype=np.float64).reshape((Nn - 1, nuu, nxx)).transpose((0, 2, 1))
+    par = dad[1:]
+    xoff = int(nx[0])
+    lo_b, hi_b = np.concatenate([d["xmin"], d["umin"]]), np.concatenate([d["xmax"], d["umax"]])
+    x, u = np.zeros(snx), np.zeros(snu)
+    gq, gr, Y = np.zeros(snx), np.zeros(snu), np.zeros(snl)
+    u0, nreg = np.zeros(max(nuu, 1)), C.c_int()
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    rng = np.random.Generator(np.random.PCG64(2323))
+    t = {k: [] for k in "ab"}
+    cnt, dlo, dhi, bad, hits = [], 0.0, 0.0, 0, 0
+    for k in range(steps):
+        wx, wu = rng.standard_normal(snx), rng.standard_normal(snu)
+        assert L.tqgpu_mpc_step(g.h, dp(xs[k]), C.byref(o), C.byref(res), dp(u0)) == 0, L.tqgpu_last_error()
+        assert L.tqgpu_mpc_adjoint(g.h, C.byref(o), dp(wx), dp(wu), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+        bad += res.status != 0
+        t0 = time.perf_counter()
+        rc = L.tqgpu_mpc_adjoint_bounds(g.h, dp(glb), dp(gub))
+        t["a"].append(time.perf_counter() - t0)
+        assert rc == 0, L.tqgpu_last_error()
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        cnt.append((la.value, co.value, wa.value))
+        t0 = time.perf_counter()
+        assert L.tqgpu_get_solution(g.h, dp(x), dp(u), None, None, None, None) == 0
+        assert L.tqgpu_mpc_get_adjoint(g.h, dp(gq), dp(gr), dp(Y)) == 0
+        Yc = Y.reshape((Nn - 1, nxx))
+        vx, vu = wx.copy(), wu.copy()
+        vx[xoff:] -= Y
+        VX, VU = np.zeros((Nn, nxx)), vu.reshape((-1, nuu))
+        np.add.at(VX, par[first - 1:], np.einsum("eij,ei->ej", A3, Yc[first - 1:]))
+        np.add.at(VU, par, np.einsum("eij,ei->ej", B3, Yc))
+        vx[xoff:] += VX[1:].ravel()
+        if root_states:
+            vx[:xoff] += VX[0]
+        v, z = np.concatenate([vx, vu]), np.concatenate([x, u])
+        if root_states:          # the fold has put x0 into both bounds of the root's states
+            lo_b[:nxx] = hi_b[:nxx] = xs[k]
+        on_lo = z == lo_b
+        hlo, hhi = np.where(on_lo, v, 0.0), np.where((z == hi_b) & ~on_lo, v, 0.0)
+        sums = []
+        for h in (hlo, hhi):
+            HX, HU = h[xoff:snx].reshape((Nn - 1, nxx)), h[snx:].reshape((-1, nuu))
+            # the nodes with inputs are the first ones, level by level; a root with states belongs to the group of the inner nodes
+            sx, su = HX[inner - 1].sum(axis=0), HU[inner].sum(axis=0)
+            sums.append(np.concatenate([sx + h[:nxx], su + HU[0]]) if root_states else np.concatenate([sx, su]))
+        t["b"].append(time.perf_counter() - t0)
+        hits += int(np.count_nonzero(hlo) + np.count_nonzero(hhi))
+        dlo, dhi = max(dlo, float(np.max(np.abs(glb[:nzi] - sums[0])))), max(dhi, float(np.max(np.abs(gub[:nzi] - sums[1]))))
+    g.close()
+    med = tuple(int(np.median([e[i] for e in cnt[skip:]])) for i in range(3))
+    form = "root with states" if root_states else "x0 eliminated"
+    print(f"{name}, --adjoint-bounds, {form}: {Nn} nodes, {steps} steps; h-groups of the inner nodes, the leaves{'' if root_states else ' and the root'}; "
+          f"entries on a bound per step {hits / steps:.1f}; steps with another status than 0: {bad}")
+    ma, lo, p90 = stats(t["a"][skip:])
+    print(f"    {'(a) tqgpu_mpc_adjoint_bounds':34s} wall median {ma:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d" % med, flush=True)
+    mb, lo, p90 = stats(t["b"][skip:])
+    print(f"    {'(b) downloads + numpy':34s} wall median {mb:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches 1  copies 4  waits 2 (not counted by tqgpu_mpc_stats: 1, 1 + 3, 1 + 1)", flush=True)
+    print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |(a) - (b)| over the run, the group of the inner nodes: glb {dlo:.2e}, gub {dhi:.2e}", flush=True)
+
+
+def adjoint_reference_compare(capi, name, p, steps, skip):
+    """--adjoint-reference --tracking: the closed loop of --tracking on a root with states (tqgpu_mpc_step_at moves the window a row per step), behind
+    every step an adjoint, then two ways to dL/dxref, dL/duref of the rows the window reads, on the same mirror:
+    (a) tqgpu_mpc_adjoint_reference;
+    (b) the host route: tqgpu_mpc_get_adjoint, then numpy -H' gz (H diagonal: -Qd gq, -Rd gr) summed per row.
+    Counts of (b) are what its one call does: 3 copies, 1 wait, not counted by tqgpu_mpc_stats."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, res = capi._gpu_opts(), capi.GpuResult()
+    d, x0 = full_root(capi, p)
+    nk, nx, nu = [np.asarray(d[k], dtype=int) for k in ("nk", "nx", "nu")]
+    Nn, nxx, nuu = len(nk), int(nx[0]), int(nu[0])
+    st = node_stages(nk)
+    deep = int(st.max())
+    X, U = reference(x0, nuu, steps + deep + 1)
+    xs = [moved_inward(x0, k, 0) for k in range(steps)]
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    g.mpc_set_root_states()
+    g.set_warm_start(1)
+    g.mpc_set_tracking(X, U, d["q"], d["r"])
+    snx, snu, snl = int(g.sum_nx), int(g.sum_nu), int(g.sum_lam)
+    Qd, Rd = np.asarray(d["Qd"], dtype=np.float64), np.asarray(d["Rd"], dtype=np.float64)
+    stu = st[nu > 0]
+    gxr, gur = np.zeros((deep + 1) * nxx), np.zeros((deep + 1) * nuu)
+    gq, gr, gb = np.zeros(snx), np.zeros(snu), np.zeros(snl)
+    u0, nreg, row0, rows = np.zeros(max(nuu, 1)), C.c_int(), C.c_int(), C.c_int()
+    la, co, wa = C.c_int(), C.c_int(), C.c_int()
+    rng = np.random.Generator(np.random.PCG64(2424))
+    t = {k: [] for k in "ab"}
+    cnt, dx, du, bad = [], 0.0, 0.0, 0
+    for k in range(steps):
+        wx, wu = rng.standard_normal(snx), rng.standard_normal(snu)
+        assert L.tqgpu_mpc_step_at(g.h, dp(xs[k]), k, C.byref(o), C.byref(res), dp(u0)) == 0, L.tqgpu_last_error()
+        assert L.tqgpu_mpc_adjoint(g.h, C.byref(o), dp(wx), dp(wu), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+        bad += res.status != 0
+        t0 = time.perf_counter()
+        rc = L.tqgpu_mpc_adjoint_reference(g.h, dp(gxr), dp(gur), C.byref(row0), C.byref(rows))
+        t["a"].append(time.perf_counter() - t0)
+        assert rc == 0 and (row0.value, rows.value) == (k, deep + 1), L.tqgpu_last_error()
+        L.tqgpu_mpc_stats(C.byref(la), C.byref(co), C.byref(wa))
+        cnt.append((la.value, co.value, wa.value))
+        t0 = time.perf_counter()
+        assert L.tqgpu_mpc_get_adjoint(g.h, dp(gq), dp(gr), dp(gb)) == 0
+        HX, HU = np.zeros((deep + 1, nxx)), np.zeros((deep + 1, nuu))
+        np.add.at(HX, st, (-Qd * gq).reshape((Nn, nxx)))
+        np.add.at(HU, stu, (-Rd * gr).reshape((-1, nuu)))
+        t["b"].append(time.perf_counter() - t0)
+        dx, du = max(dx, float(np.max(np.abs(gxr.reshape((deep + 1, nxx)) - HX)))), max(du, float(np.max(np.abs(gur.reshape((deep + 1, nuu)) - HU))))
+    g.close()
+    med = tuple(int(np.median([e[i] for e in cnt[skip:]])) for i in range(3))
+    print(f"{name}, --adjoint-reference --tracking, root with states: {Nn} nodes, {deep + 1} rows per step, {steps} steps; steps with another status than 0: {bad}")
+    ma, lo, p90 = stats(t["a"][skip:])
+    print(f"    {'(a) tqgpu_mpc_adjoint_reference':34s} wall median {ma:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches %d  copies %d  waits %d" % med, flush=True)
+    mb, lo, p90 = stats(t["b"][skip:])
+    print(f"    {'(b) tqgpu_mpc_get_adjoint + numpy':34s} wall median {mb:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f}  | launches 0  copies 3  waits 1 (not counted by tqgpu_mpc_stats)", flush=True)
+    print(f"    (b) / (a) wall {np.median(t['b'][skip:]) / np.median(t['a'][skip:]):.2f}; largest |(a) - (b)| over the run: gxref {dx:.2e}, guref {du:.2e}", flush=True)
+
+
 def P_parents(nk):
     from treeqp_amd import problems as P
     return np.asarray(P.parents_of(nk), dtype=int)
@@ -1189,6 +1346,21 @@ def main():
             gain_compare(capi, "c1", P.spring_mass(), False, steps, skip)
         if "c2" in names:
             gain_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--adjoint-bounds" in args:
+        if "c1" in names:
+            adjoint_bounds_compare(capi, "c1", P.spring_mass(), True, steps, skip)
+            adjoint_bounds_compare(capi, "c1", P.spring_mass(), False, steps, skip)
+        if "c2" in names:
+            adjoint_bounds_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--adjoint-reference" in args:
+        if "--tracking" not in args:
+            raise SystemExit("--adjoint-reference goes with --tracking")
+        if "c1" in names:
+            adjoint_reference_compare(capi, "c1", P.spring_mass(), steps, skip)
+        if "c2" in names:
+            adjoint_reference_compare(capi, "c2", P.linear_chain(2, 9, 9), steps, skip)
         return
     if "--adjoint-matrices" in args:
         sizes = [int(v) for v in args[args.index("--adjoint-batch") + 1].split(",")] if "--adjoint-batch" in args else [0]

@@ -1138,6 +1138,37 @@ class TqGpu:
         self._chk(lib().tqgpu_mpc_adjoint_matrices(self.h, *[_dp(bufs[key]) for key in ADJMAT_KEYS]))
         return {key: _adjmat_split(bufs[key], sizes[key], nw, key == "gA0") for key in ADJMAT_KEYS}
 
+    # ---- the adjoint in the bounds and in the tracking reference (tqgpu_mpc_get_adjoint_bounds, tqgpu_mpc_adjoint_bounds, tqgpu_mpc_adjoint_reference) ----
+    def mpc_get_adjoint_bounds(self) -> dict:
+        """gxmin, gxmax (sum_nx, nw), gumin, gumax (sum_nu, nw) of the last mpc_adjoint: v on the side the exported value sits on, 0.0
+        elsewhere; column j is the flat layout of get_solution (tqgpu_mpc_get_adjoint_bounds; downloads and waits)."""
+        sizes = (("gxmin", int(self.sum_nx)), ("gxmax", int(self.sum_nx)), ("gumin", int(self.sum_nu)), ("gumax", int(self.sum_nu)))
+        nw = self.__dict__.get("_adj_nw", 1)
+        out = {key: np.zeros(max(n * nw, 1)) for key, n in sizes}
+        self._chk(lib().tqgpu_mpc_get_adjoint_bounds(self.h, *[_dp(out[key]) for key, _ in sizes]))
+        return {key: out[key][:n * nw].reshape((n, nw), order="F") for key, n in sizes}
+
+    def mpc_adjoint_bounds(self) -> dict:
+        """The bound gradients of the stored adjoint summed over the h-groups of mpc_set_param_groups (tqgpu_mpc_adjoint_bounds): glb, gub, lists
+        with one (nx + nu, nw) array per group, shaped like gh of mpc_adjoint_matrices."""
+        sizes, nw = _adjmat_sizes(self)
+        bufs = {key: np.zeros(max(sum(int(np.prod(shp)) for shp in sizes["gh"]) * nw, 1)) for key in ("glb", "gub")}
+        self._chk(lib().tqgpu_mpc_adjoint_bounds(self.h, _dp(bufs["glb"]), _dp(bufs["gub"])))
+        return {key: _adjmat_split(bufs[key], sizes["gh"], nw) for key in ("glb", "gub")}
+
+    def mpc_adjoint_reference(self) -> dict:
+        """The gradient of the stored adjoint in the reference trajectory of mpc_set_tracking (tqgpu_mpc_adjoint_reference): dict(row0, rows, gxref
+        (rows, NXT, nw), guref (rows, NUT, nw)) for the rows the window in force reads."""
+        row0, rows = C.c_int(0), C.c_int(0)
+        self._chk(lib().tqgpu_mpc_adjoint_reference(self.h, None, None, C.byref(row0), C.byref(rows)))
+        nxt, nut = int(np.max(self.nx, initial=0)), int(np.max(self.nu, initial=0))          # tracking takes trees of one nx and one nu (0 apart)
+        nw = self.__dict__.get("_adj_nw", 1)
+        gx, gu = np.zeros(max(rows.value * nxt * nw, 1)), np.zeros(max(rows.value * nut * nw, 1))
+        self._chk(lib().tqgpu_mpc_adjoint_reference(self.h, _dp(gx), _dp(gu), None, None))
+        return dict(row0=row0.value, rows=rows.value,
+                    gxref=np.moveaxis(gx[:rows.value * nxt * nw].reshape((nw, rows.value, nxt)), 0, 2).copy(),
+                    guref=np.moveaxis(gu[:rows.value * nut * nw].reshape((nw, rows.value, nut)), 0, 2).copy())
+
     def export_ahead(self, on: bool) -> None:
         """the solution's packing kernel and download go out behind the solve's launch (callers that fetch the solution after every solve)"""
         self._chk(lib().tqgpu_set_export_ahead(self.h, int(bool(on))))

@@ -1,7 +1,7 @@
 /*
  * tdunes_adjoint.hpp -- the host side of the derivatives of an MPC step, in the host part: the entry points tqgpu_mpc_sensitivity, tqgpu_mpc_adjoint,
- * tqgpu_mpc_adjoint_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, and the
- * readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
+ * tqgpu_mpc_adjoint_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, tqgpu_mpc_adjoint_bounds,
+ * tqgpu_mpc_adjoint_reference, and the readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
  * Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind tdunes_mpc.hpp (mpc_refuse, mpc_take_x0, MpcLive) and tdunes_kkt.hpp
  * (enqueue_export, export_all_entry).  That file keeps the mirror's records MpcSens, MpcAdjBatch, MpcAdjMat and the plan of a batched call
  * (DeviceGroup .. order_behind_lead).
@@ -130,7 +130,8 @@ int setup_adj(tqgpu_solver *s, int nw) {
         const size_t cap = (size_t)nw;
         size_t off = 0;
         auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
-        const size_t ow = take((nxe + snu) * cap), oY = take(snx * cap), ot = take(snx * cap), oq = take(snx * cap), or_ = take(snu * cap), ob = take(snx * cap), oh = take(nx0 * cap + 1);
+        const size_t ow = take((nxe + snu) * cap), oY = take(snx * cap), ot = take(snx * cap), oq = take(snx * cap), or_ = take(snu * cap), ob = take(snx * cap), oh = take(nx0 * cap + 1),
+                     olx = take(snx * cap), oux = take(snx * cap), olu = take(snu * cap), ouu = take(snu * cap);
         if ((rc = s->mem.zeroed(m.ad, sizeof(double) * std::max<size_t>(off, 2), TQGPU_ENOMEM, "the adjoint")) ||
             (rc = s->mem.host(m.ah, sizeof(double) * ((nxe + snu) * cap + nx0 * cap + 2), "the pinned loss gradient and gx0")))
             return rc;
@@ -146,6 +147,7 @@ int setup_adj(tqgpu_solver *s, int nw) {
         A = Adj{};
         double *p = m.ad;
         A.wx = p + ow; A.Y = p + oY; A.t = p + ot; A.gq = p + oq; A.gr = p + or_; A.gb = p + ob; A.head = p + oh;
+        A.glx = p + olx; A.gux = p + oux; A.glu = p + olu; A.guu = p + ouu;
         A.nxe = (int)nxe;
         m.nw_cap = nw; m.adj_nx0 = s->mpc.nx0; m.lds_rhs = lr; m.lds_grad = lg;
     }
@@ -284,6 +286,22 @@ extern "C" int tqgpu_mpc_get_adjoint(tqgpu_solver *s, double *gq, double *gr, do
     if (gq && (rc = download_columns(s, s->sens.a.gq, nw, (size_t)s->x_pad, (size_t)(s->sum_nx - s->x_pad), gq))) return rc;      /* phantom root states are left out */
     if (gb && (rc = download_columns(s, s->sens.a.gb, nw, (size_t)s->nx0, (size_t)s->sum_lam, gb))) return rc;                      /* the root has no dual */
     if (gr && snu * nw) HIP_TRY(hipMemcpy(gr, s->sens.a.gr, sizeof(double) * snu * nw, hipMemcpyDeviceToHost));
+    return TQGPU_OK;
+}
+
+/* the bound gradients k_adj_grad left beside gq, gr: a diagnostic download like tqgpu_mpc_get_adjoint, not counted into tqgpu_mpc_stats */
+extern "C" int tqgpu_mpc_get_adjoint_bounds(tqgpu_solver *s, double *gxmin, double *gxmax, double *gumin, double *gumax) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_adjoint_bounds")) || (rc = adj_need(s, "tqgpu_mpc_get_adjoint_bounds"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t nw = (size_t)s->sens.nw, snu = (size_t)s->sum_nu, pad = (size_t)s->x_pad, nxe = (size_t)s->sum_nx - pad;
+    const Adj &A = s->sens.a;
+    if (gxmin && (rc = download_columns(s, A.glx, nw, pad, nxe, gxmin))) return rc;      /* phantom root states are left out */
+    if (gxmax && (rc = download_columns(s, A.gux, nw, pad, nxe, gxmax))) return rc;
+    if (gumin && snu * nw) HIP_TRY(hipMemcpy(gumin, A.glu, sizeof(double) * snu * nw, hipMemcpyDeviceToHost));
+    if (gumax && snu * nw) HIP_TRY(hipMemcpy(gumax, A.guu, sizeof(double) * snu * nw, hipMemcpyDeviceToHost));
     return TQGPU_OK;
 }
 
@@ -688,6 +706,10 @@ int adjmat_build(tqgpu_solver *s, const char *who) {
     M.root = root; M.oA0 = (int)m.reg[5]; M.oS0 = (int)m.reg[6]; M.pR = (int)pR;
     m.n_units = M.n_hchk + M.n_cchk + root;
     m.part1 = part; m.lds = lds;
+    /* the same h-groups for tqgpu_mpc_adjoint_bounds: per chunk [glb | gub] of nx + nu entries each */
+    std::vector<int> width((size_t)m.n_h);
+    for (int g = 0; g < m.n_h; g++) width[(size_t)g] = 2 * (s->nx[(size_t)hm[(size_t)g][0]] + s->nu[(size_t)hm[(size_t)g][0]]);
+    if ((rc = nodesum_build(s, s->bsum, hm, width, 0, who))) return rc;
     m.sig = adjmat_sig(s);
     return TQGPU_OK;
 }
@@ -871,6 +893,85 @@ extern "C" int tqgpu_mpc_adjoint_matrices(tqgpu_solver *s, double *gH, double *g
     double *const out[ADJMAT_REGIONS] = {gH, gh, gA, gB, gb, gA0, gS0};
     const size_t at[ADJMAT_REGIONS] = {};
     return adjmat_one(s, out, at);
+}
+
+/* ---- sums of the stored adjoint over node sets (tdunes_sens.hpp: k_nodesum_part, k_nodesum_sum): the bound gradients over the h-groups, the gradient
+ * of the tracking reference over the nodes of a trajectory row ---- */
+namespace {
+/* one mirror on its own stream: N with the call's own fields set, `targets` results of res_doubles doubles in all: one launch, a second where a
+ * result has more than one partial, one copy through pinned memory, one wait; the results are then in m.h_res */
+int nodesum_run(tqgpu_solver *s, MpcNodeSum &m, NodeSum N, int targets, size_t res_doubles) {
+    int rc;
+    const int nw = s->sens.nw;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t need_res = std::max<size_t>(res_doubles, 1), need_part = std::max<size_t>(m.part1 * (size_t)nw, 1);
+    if (!m.d_res || m.res_cap < need_res) {
+        s->mem.release(m.d_res); s->mem.release(m.h_res); m.res_cap = 0;
+        if ((rc = s->mem.device(m.d_res, need_res * sizeof(double), TQGPU_ENOMEM, "the summed gradients")) || (rc = s->mem.host(m.h_res, need_res * sizeof(double), "the pinned summed gradients"))) return rc;
+        m.res_cap = need_res;
+    }
+    if (!m.d_part || m.part_cap < need_part) {
+        s->mem.release(m.d_part); m.part_cap = 0;
+        if ((rc = s->mem.device(m.d_part, need_part * sizeof(double), TQGPU_ENOMEM, "the partial sums of the summed gradients"))) return rc;
+        m.part_cap = need_part;
+    }
+    if ((rc = allow_lds(k_nodesum_part, m.lds))) return rc;
+    bool many = false;
+    for (int t = 0; t < targets && !many; t++) {
+        int c_lo, c_hi;
+        nodesum_span(m.set.data(), N.n_set, N.mode, N.t0, N.Tn, N.row0, t, c_lo, c_hi);
+        many = c_hi - c_lo > 1;
+    }
+    N.res = m.d_res; N.part = m.d_part;
+    hipStream_t st = s->stream;
+    if (N.n_chk) { hipLaunchKernelGGL(k_nodesum_part, dim3((unsigned)N.n_chk, (unsigned)nw), dim3(WAVE), m.lds, st, s->T, s->D, s->sens.v, s->sens.a, N); MPC_COUNT(launches, 1); }
+    if (many) { hipLaunchKernelGGL(k_nodesum_sum, dim3((unsigned)targets, (unsigned)nw), dim3(WAVE), 0, st, N, nw); MPC_COUNT(launches, 1); }
+    HIP_TRY(hipGetLastError());
+    if (res_doubles) HIP_TRY(hipMemcpyAsync(m.h_res, m.d_res, sizeof(double) * res_doubles, hipMemcpyDeviceToHost, st));
+    MPC_COUNT(copies, 1);
+    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
+    return TQGPU_OK;
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_adjoint_bounds(tqgpu_solver *s, double *glb, double *gub) {
+    int rc;
+    if ((rc = adjmat_refuse(s, "tqgpu_mpc_adjoint_bounds"))) return rc;
+    MpcLive live;
+    MpcNodeSum &m = s->bsum;
+    const size_t n = (size_t)m.v.tot * (size_t)s->sens.nw;
+    if ((rc = nodesum_run(s, m, m.v, m.v.n_set, 2 * n))) return rc;
+    if (glb && n) memcpy(glb, m.h_res, sizeof(double) * n);
+    if (gub && n) memcpy(gub, m.h_res + n, sizeof(double) * n);
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_adjoint_reference(tqgpu_solver *s, double *gxref, double *guref, int *row0, int *rows) {
+    const char *who = "tqgpu_mpc_adjoint_reference";
+    int rc;
+    if ((rc = mpc_refuse(s, who))) return rc;
+    for (int k = 0; k < s->Nn; k++) if (s->sk.kind(k) >= 2)
+        return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the tree has nodes of kind 2 or 3, which the adjoint refuses");
+    if (!s->trk.d) return fail(TQGPU_EINVAL, std::string(who) + ": the reference trajectory has not been given yet (tqgpu_mpc_set_tracking)");
+    if (s->trk.t0 < 0) return fail(TQGPU_EINVAL, std::string(who) + ": no window is in force (tqgpu_mpc_set_window, tqgpu_mpc_step_at): q, r do not depend on the reference yet");
+    if ((rc = adj_need(s, who))) return rc;
+    MpcNodeSum &m = s->rsum;
+    NodeSum N = m.v;
+    N.t0 = s->trk.t0; N.Tn = s->trk.T; N.nxt = s->trk.nxt; N.nut = s->trk.nut;
+    N.row0 = std::min(N.t0, N.Tn - 1);
+    N.rows = std::min(N.t0 + N.n_set - 1, N.Tn - 1) - N.row0 + 1;          /* n_set - 1: the deepest stage */
+    if (row0) *row0 = N.row0;
+    if (rows) *rows = N.rows;
+    if (!gxref && !guref) return TQGPU_OK;          /* the sizes alone: host state only */
+    MpcLive live;
+    const size_t nw = (size_t)s->sens.nw, W = (size_t)(N.nxt + N.nut), cells = nw * (size_t)N.rows;
+    if ((rc = nodesum_run(s, m, N, N.rows, cells * W))) return rc;
+    for (size_t c = 0; c < cells; c++) {
+        if (gxref && N.nxt) memcpy(gxref + c * N.nxt, m.h_res + c * W, sizeof(double) * (size_t)N.nxt);
+        if (guref && N.nut) memcpy(guref + c * N.nut, m.h_res + c * W + N.nxt, sizeof(double) * (size_t)N.nut);
+    }
+    return TQGPU_OK;
 }
 
 extern "C" int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, int reduce, double *gH, double *gh, double *gA, double *gB, double *gb, double *gA0, double *gS0) {

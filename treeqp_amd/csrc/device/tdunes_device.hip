@@ -1927,6 +1927,14 @@ struct MpcAdjMat {
     char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
     double *d_bres = nullptr, *h_bres = nullptr; size_t bres_cap = 0;
 };
+/* tqgpu_mpc_adjoint_bounds (bsum; built with the parameter groups) and tqgpu_mpc_adjoint_reference (rsum; built by tqgpu_mpc_set_tracking): the tables of
+ * k_nodesum_part / k_nodesum_sum in one device block (members, set and chunk records), the set records once more on the host (which results have
+ * more than one partial), the partials per column of w, the LDS window, and the call's own result block, its pinned twin and partials */
+struct MpcNodeSum {
+    int *d_tab = nullptr; NodeSum v{}; std::vector<int> set;
+    size_t part1 = 0, lds = 0;
+    double *d_res = nullptr, *h_res = nullptr, *d_part = nullptr; size_t res_cap = 0, part_cap = 0;
+};
 /* ---- the solution's way out and its check (tdunes_kkt.hpp): the solution in one piece, [x | u | lam | dlam | mu_x | mu_u], packed on the device (d) and
  * downloaded into pinned memory (h).  valid: h holds (or is about to hold, stream-ordered) the solution of the last solve; dev_only, with valid: the pack
  * is in d only (a certified tqgpu_mpc_step), tqgpu_get_solution downloads it.  The three transitions below are the only writers of the two flags. ---- */
@@ -2106,7 +2114,7 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcSensBatch sensb; MpcAdjMat adjm;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, sensb, adjm: tdunes_adjoint.hpp), one record per feature */
+    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcSensBatch sensb; MpcAdjMat adjm; MpcNodeSum bsum, rsum;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, sensb, adjm: tdunes_adjoint.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
     int ms_Nr = 0, ms_S = 0, ms_nB = 0;

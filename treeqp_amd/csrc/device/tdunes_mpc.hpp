@@ -239,6 +239,41 @@ int mpc_refuse(const tqgpu_solver *s, const char *who) {
     return TQGPU_OK;
 }
 
+/* the tables of k_nodesum_part / k_nodesum_sum (tdunes_sens.hpp) for the node sets `sets` (members ascending), width[g] accumulators per chunk of set g:
+ * member lists, set records, the chunks of ADJMAT_CHUNK members cut per set, uploaded in one block; mode 0 also lays the sets' blocks of width / 2
+ * doubles one behind the other (NodeSum::tot) */
+int nodesum_build(tqgpu_solver *s, MpcNodeSum &m, const std::vector<std::vector<int>> &sets, const std::vector<int> &width, int mode, const char *who) {
+    int rc;
+    std::vector<int> mem, chk;
+    m.set.assign(sets.size() * 4, 0);
+    size_t part = 0, tot = 0, wmax = 0;
+    for (size_t g = 0; g < sets.size(); g++) {
+        const int members = (int)sets[g].size(), W = width[g];
+        int *rec = &m.set[4 * g];
+        rec[0] = (int)(chk.size() / 4); rec[2] = (int)tot; rec[3] = W;
+        for (int at = 0; at < members; at += ADJMAT_CHUNK, rec[1]++) {
+            chk.push_back((int)g); chk.push_back((int)mem.size() + at); chk.push_back(std::min(ADJMAT_CHUNK, members - at)); chk.push_back((int)part);
+            part += (size_t)W;
+        }
+        mem.insert(mem.end(), sets[g].begin(), sets[g].end());
+        tot += (size_t)W / 2; wmax = std::max(wmax, (size_t)W);
+    }
+    if (part > (size_t)INT_MAX / 2) return fail(TQGPU_EUNSUPPORTED, std::string(who) + ": the partial sums do not fit the tables' 32-bit offsets");
+    std::vector<int> tab;
+    auto put = [&](const std::vector<int> &v) { const size_t at = tab.size(); tab.insert(tab.end(), v.begin(), v.end()); return at; };
+    const size_t o_mem = put(mem), o_set = put(m.set), o_chk = put(chk);
+    tab.push_back(0);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));          /* a sum in flight reads the block that is replaced */
+    s->mem.release(m.d_tab);
+    m.v = NodeSum{};
+    if ((rc = s->mem.upload(m.d_tab, tab.data(), tab.size() * sizeof(int), TQGPU_ENOMEM, "the tables of the node sets"))) return rc;
+    m.v.mem = m.d_tab + o_mem; m.v.set = m.d_tab + o_set; m.v.chk = m.d_tab + o_chk;
+    m.v.n_set = (int)sets.size(); m.v.n_chk = (int)(chk.size() / 4); m.v.mode = mode; m.v.tot = mode ? 0 : (int)tot;
+    m.part1 = part; m.lds = (2 * wmax + 2) * sizeof(double);
+    return TQGPU_OK;
+}
+
 /* the descriptor of a mirror for k_mpc_pre / k_mpc_post: views into mpc.d and mpc.h (null before tqgpu_mpc_set_root / _set_root_states: fold must be false then) */
 MItem mpc_item(const tqgpu_solver *s, MpcPre pre) {
     MItem it{};
@@ -506,7 +541,13 @@ extern "C" int tqgpu_mpc_set_tracking(tqgpu_solver *s, int NXT, int NUT, int T, 
     s->trk.T = 0; s->trk.t0 = -1;
     if ((rc = s->mem.upload(s->trk.d, blk.data(), sizeof(double) * blk.size(), TQGPU_ENOMEM, "the reference trajectory"))) return rc;
     s->trk.T = T; s->trk.nxt = NXT; s->trk.nut = NUT;
-    return TQGPU_OK;
+    /* the nodes of every stage and their chunks, for tqgpu_mpc_adjoint_reference: they depend on the tree alone, not on the window */
+    std::vector<std::vector<int>> by_stage;
+    for (int k = 0; k < s->Nn; k++) {
+        if ((size_t)s->stage[k] >= by_stage.size()) by_stage.resize((size_t)s->stage[k] + 1);
+        by_stage[(size_t)s->stage[k]].push_back(k);
+    }
+    return nodesum_build(s, s->rsum, by_stage, std::vector<int>(by_stage.size(), NXT + NUT), 1, "tqgpu_mpc_set_tracking");
 }
 
 extern "C" int tqgpu_mpc_set_window(tqgpu_solver *s, int t0) {

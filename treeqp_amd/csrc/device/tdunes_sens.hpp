@@ -343,6 +343,7 @@ struct Adj {
     double *Y, *t;                     /* sum_nx x nw each, column major, node-indexed as Sens::dlam: R, then Y in its place; t of the non-root blocks */
     double *gq, *gr, *gb;              /* sum_nx x nw, sum_nu x nw, sum_nx x nw, node-indexed (phantom root states included; gb: the root's rows stay 0) */
     double *head;                      /* [gx0 (nx0 x nw, column major) | n_reg] */
+    double *glx, *gux, *glu, *guu;     /* dL/dxmin, dL/dxmax (sum_nx x nw), dL/dumin, dL/dumax (sum_nu x nw), node-indexed as gq, gr: v on the side the exported value sits on, 0.0 elsewhere */
     int nw, nxe;
 };
 /* entry i of w_k, i over [x | u], column col; phantom root states carry 0 */
@@ -495,6 +496,17 @@ __device__ void adj_grad_body(const Tree &T, const Data &D, const Sens &S, const
         r = -r;
         g[i] = r;
         if (i < nxk) A.gq[xo + i + (size_t)col * S.sum_nx] = r; else A.gr[uo + i - nxk + (size_t)col * S.sum_nu] = r;
+        /* the bound gradients: v where P is 0.0 because the exported value equals a bound bit for bit (sens_pdiag's test, read again only behind
+         * that 0.0), on the lower side where it equals the lower bound; 0.0 on free entries, kind-1 nodes and phantom root states */
+        double lo = 0.0, hi = 0.0;
+        if (kind == 0 && i >= pad && (i < nxk ? S.Px[xo + i] : S.Pu[uo + i - nxk]) == 0.0) {
+            const int e = i < nxk ? xo + i : uo + i - nxk;
+            const double val = i < nxk ? S.x[e - S.xpad] : S.u[e];
+            if (val == (i < nxk ? D.xmin[e] : D.umin[e])) lo = v[i];
+            else if (val == (i < nxk ? D.xmax[e] : D.umax[e])) hi = v[i];
+        }
+        if (i < nxk) { A.glx[xo + i + (size_t)col * S.sum_nx] = lo; A.gux[xo + i + (size_t)col * S.sum_nx] = hi; }
+        else { A.glu[uo + i - nxk + (size_t)col * S.sum_nu] = lo; A.guu[uo + i - nxk + (size_t)col * S.sum_nu] = hi; }
     }
     if (k > 0) {
         for (int i = lane; i < nxk; i += WAVE) A.gb[xo + i + (size_t)col * S.sum_nx] = Y[xo + i];
@@ -963,4 +975,138 @@ __global__ void __launch_bounds__(WAVE) k_adjmat_reduce(const AMItem *__restrict
         items[0].M.res[adjmat_res_at(U0, e, col, nw)] = v;
     }
 }
+#endif
+
+/* ---- sums of a per-node vector over sets of nodes in a fixed order (tqgpu_mpc_adjoint_bounds, tqgpu_mpc_adjoint_reference) ----
+ *   mode 0, the bound gradients over the h-groups: a set is a group, the vector of member k is [glb_k (nz) | gub_k (nz)] of struct Adj, per member
+ *           acc = acc + v[i];  the result of a set is its group's block of glb and of gub.
+ *   mode 1, the tracking reference: a set is a stage, its members the nodes of that stage, the result the trajectory row the window in force sends
+ *           the stage to, rho = min(t0 + stage, T - 1); [q_k; r_k] = base_k - H_k [xref; uref]_rho, so [gxref; guref]_rho = - sum_k H_k' gz_k:
+ *           kind 0, per member  acc[j] = fma(-Qd[j], gq[j], acc[j]),  acc[NXT + j] = fma(-Rd[j], gr[j], acc[NXT + j]);
+ *           kind 1, per member, for column j of the stored H_k (nz x nz, column major)  acc[j] = fma(-H[i + j nz], gz[i], acc[j]), i ascending
+ *           over the rows behind the phantom root states (the fold leaves their q alone; they are no columns either);
+ *           an eliminated root with S0, behind its own chain  acc[j] = fma(-S0[m + j nu0], gr_0[m], acc[j]), m ascending.
+ *           A member without states (an eliminated root) or inputs (a leaf) leaves those entries alone.
+ * The members of a set are taken in ascending node index in chunks of ADJMAT_CHUNK; a chunk's partial is one chain from 0.0 over its members; a
+ * result is the first of its partials plus the others in ascending order: the chunks of the group (mode 0), of the row's stages in ascending
+ * (stage, chunk) order (mode 1: a clamped last row collects several stages).  Chunks are cut per set, so the tables do not depend on t0.
+ * One wave per (chunk, column) on a private LDS window [accumulators | the member's vector], the next member's vector in flight as in
+ * k_adjmat_part; a result of one partial is written by its chunk, the others by k_nodesum_sum, one wave per (result, column).  No atomics; Data,
+ * Sens, Adj are only read. */
+struct NodeSum {
+    const int *mem;                    /* the members (nodes), set after set, ascending within a set */
+    const int *set;                    /* 4 ints per set: [0] its first chunk, [1] its chunks, [2] mode 0: where its block begins in glb, doubles per column, [3] the accumulators of a chunk */
+    const int *chk;                    /* 4 ints per chunk: set, first member (index into mem), members, where its partial begins in doubles per column */
+    double *res, *part;                /* mode 0: [glb | gub], each groups ascending, then columns; mode 1: per column, per row [gxref (NXT) | guref (NUT)] */
+    int n_set, n_chk, mode;
+    int tot;                           /* mode 0: the doubles per column of glb */
+    int t0, Tn, nxt, nut, row0, rows;  /* mode 1: the window in force, the rows of the trajectory, its widths, the first row of the result and their number */
+};
+/* the chunks [c_lo, c_hi) whose partials make up result `target` (mode 0: the set; mode 1: row row0 + target) */
+__host__ __device__ inline void nodesum_span(const int *set, int n_set, int mode, int t0, int Tn, int row0, int target, int &c_lo, int &c_hi) {
+    int s_lo = target, s_hi = target;
+    if (mode) {
+        const int rho = row0 + target;
+        if (rho >= Tn - 1) { s_lo = Tn - 1 - t0 > 0 ? Tn - 1 - t0 : 0; s_hi = n_set - 1; }
+        else s_lo = s_hi = rho - t0;
+    }
+    c_lo = set[4 * s_lo]; c_hi = set[4 * s_hi] + set[4 * s_hi + 1];
+}
+__device__ __forceinline__ size_t nodesum_res_at(const NodeSum &N, int target, int W, int e, int col, int nw) {
+    if (N.mode) return ((size_t)col * N.rows + target) * W + e;
+    const int nz = W / 2, side = e >= nz;
+    return (size_t)side * N.tot * nw + (size_t)N.set[4 * target + 2] * nw + (size_t)col * nz + (e - side * nz);
+}
+__device__ void nodesum_part_body(const Tree &T, const Data &D, const Sens &S, const Adj &A, const NodeSum &N, int unit, int col, int lane, double *lds) {
+    const int nw = A.nw;
+    const int *ck = N.chk + 4 * unit;
+    const int set = ck[0], cnt = ck[2], W = N.set[4 * set + 3], nxt = N.nxt;
+    const int *mem = N.mem + ck[1];
+    double *acc = lds;                    /* W */
+    double *vec = lds + W;                /* W: the vector of the member in hand */
+    for (int e = lane; e < W; e += WAVE) acc[e] = 0.0;
+    auto fetch = [&](int k, int idx) {
+        const int nx = T.nx[k], nu = T.nu[k];
+        if (N.mode) {          /* [gq_k behind the phantom states (NXT) | gr_k (NUT)], 0.0 for a part the member does not have */
+            const int pad = k == 0 ? S.xpad : 0;
+            if (idx < nxt) return nx - pad > 0 ? A.gq[T.xoff[k] + pad + idx + (size_t)col * S.sum_nx] : 0.0;
+            return nu > 0 ? A.gr[T.uoff[k] + idx - nxt + (size_t)col * S.sum_nu] : 0.0;
+        }
+        const int nz = nx + nu, up = idx >= nz, i = up ? idx - nz : idx;
+        if (i < nx) return (up ? A.gux : A.glx)[T.xoff[k] + i + (size_t)col * S.sum_nx];
+        return (up ? A.guu : A.glu)[T.uoff[k] + i - nx + (size_t)col * S.sum_nu];
+    };
+    int n1 = mem[0], n2 = cnt > 1 ? mem[1] : n1;
+    double pre[ADJMAT_PF];
+#pragma unroll
+    for (int r = 0; r < ADJMAT_PF; r++) { const int idx = lane + r * WAVE; pre[r] = idx < W ? fetch(n1, idx) : 0.0; }
+    for (int m = 0; m < cnt; m++) {
+        const int cur = n1;
+        n1 = n2;
+        if (m + 2 < cnt) n2 = mem[m + 2];
+#pragma unroll
+        for (int r = 0; r < ADJMAT_PF; r++) { const int idx = lane + r * WAVE; if (idx < W) vec[idx] = pre[r]; }
+        for (int idx = lane + ADJMAT_PF * WAVE; idx < W; idx += WAVE) vec[idx] = fetch(cur, idx);
+        WSYNC();
+        if (m + 1 < cnt) {          /* the next member's loads go out ahead of this member's chain */
+#pragma unroll
+            for (int r = 0; r < ADJMAT_PF; r++) { const int idx = lane + r * WAVE; pre[r] = idx < W ? fetch(n1, idx) : 0.0; }
+        }
+        if (!N.mode) for (int e = lane; e < W; e += WAVE) acc[e] = acc[e] + vec[e];
+        else {
+            const int nx = T.nx[cur], nu = T.nu[cur], pad = cur == 0 ? S.xpad : 0, nz = nx + nu, xo = T.xoff[cur], uo = T.uoff[cur];
+            const int kind = sens_kind(D, cur);
+            const bool s0 = cur == 0 && !S.root_states && S.S0;
+            for (int e = lane; e < W; e += WAVE) {
+                const bool isx = e < nxt;
+                const int j = isx ? e : e - nxt;
+                double a = acc[e];
+                if (isx ? nx - pad > 0 : nu > 0) {
+                    if (kind == 0) a = fma(-(isx ? D.Qd[xo + pad + j] : D.Rd[uo + j]), vec[e], a);
+                    else {
+                        const double *H = D.Hd + D.poff[cur] + (size_t)(isx ? pad + j : nx + j) * nz;
+                        for (int i = pad; i < nz; i++) a = fma(-H[i], vec[i < nx ? i - pad : nxt + i - nx], a);
+                    }
+                }
+                if (s0 && isx) for (int mm = 0; mm < nu; mm++) a = fma(-S.S0[mm + (size_t)j * nu], vec[nxt + mm], a);
+                acc[e] = a;
+            }
+        }
+        WSYNC();
+    }
+    int c_lo, c_hi;
+    const int target = N.mode ? ((N.t0 + set < N.Tn - 1 ? N.t0 + set : N.Tn - 1) - N.row0) : set;
+    nodesum_span(N.set, N.n_set, N.mode, N.t0, N.Tn, N.row0, target, c_lo, c_hi);
+    const bool direct = c_hi - c_lo == 1;
+    for (int e = lane; e < W; e += WAVE) {
+        if (direct) N.res[nodesum_res_at(N, target, W, e, col, nw)] = acc[e];
+        else N.part[(size_t)ck[3] * nw + (size_t)col * W + e] = acc[e];
+    }
+}
+/* ---- k_nodesum_sum: one wave per (result, column): the first partial plus the others, ascending; a result of one partial has been written already ---- */
+__device__ void nodesum_sum_body(const NodeSum &N, int nw, int target, int col, int lane) {
+    int c_lo, c_hi;
+    nodesum_span(N.set, N.n_set, N.mode, N.t0, N.Tn, N.row0, target, c_lo, c_hi);
+    if (c_hi - c_lo < 2) return;
+    const int W = N.set[4 * N.chk[4 * c_lo] + 3];
+    for (int e = lane; e < W; e += WAVE) {
+        double v = N.part[(size_t)N.chk[4 * c_lo + 3] * nw + (size_t)col * W + e];
+        for (int c = c_lo + 1; c < c_hi; c++) v = v + N.part[(size_t)N.chk[4 * c + 3] * nw + (size_t)col * W + e];
+        N.res[nodesum_res_at(N, target, W, e, col, nw)] = v;
+    }
+}
+__global__ void __launch_bounds__(WAVE) k_nodesum_part(Tree T, Data D, Sens S, Adj A, NodeSum N)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    nodesum_part_body(T, D, S, A, N, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_nodesum_sum(NodeSum N, int nw)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{ nodesum_sum_body(N, nw, blockIdx.x, blockIdx.y, threadIdx.x); }
 #endif
