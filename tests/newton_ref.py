@@ -184,10 +184,13 @@ def stage_data(d, lam, dense=False, kinds=None):
     return (nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, kinds), H, hs, los, his
 
 
-def stage_solutions(d, lam, dense=False, kinds=None):
+def stage_solutions(d, lam, dense=False, kinds=None, inclusive=True):
     """The stage QPs at lam.  Returns dict(z, side, P, margin, cert, tree, H, h): per node the solution (longdouble), the bound each
     entry sits on (-1, 0, +1; all 0 on a dense unconstrained node), the elimination matrix; margin as newton_step documents it;
-    cert the largest violation certify_box found on a box node."""
+    cert the largest violation certify_box found on a box node.  inclusive: the rule of the clipping nodes.  True is the solver's
+    (a value exactly on a bound is fixed there, P_ii = 0); False is the WRONG rule `>` / `<` (such an entry stays free, same
+    z), kept for the tests that show a tie moves the step; a list with one boolean array per node over its [x | u] applies the
+    wrong rule to the entries that are False there and the solver's to the others."""
     tree, H, hs, los, his = stage_data(d, lam, dense, kinds)
     kinds = tree[-1]
     z, side, Pm = [], [], []
@@ -204,6 +207,9 @@ def stage_solutions(d, lam, dense=False, kinds=None):
             w = H[p].astype(LD)
             zu = h / w
             free = (zu > lo) & (zu < hi)
+            if inclusive is not True:
+                wrong = np.ones(n, dtype=bool) if inclusive is False else ~np.asarray(inclusive[p], dtype=bool)
+                free = free | (wrong & ((zu == lo) | (zu == hi)))
             zk = np.minimum(np.maximum(zu, lo), hi)
             sk = np.where(free, 0, np.where(zu <= lo, -1, 1))
             open_ = lo < hi
@@ -260,22 +266,23 @@ def assemble_from(st):
     return M, res
 
 
-def assemble(d, lam0, dense=False, kinds=None):
+def assemble(d, lam0, dense=False, kinds=None, inclusive=True):
     """The Newton system at lam0, in longdouble: (M, res, stages) with M = G P G' the negated dual Hessian, res the dynamics
     residual and stages what stage_solutions returns (its "tree" holds the offsets of the duals)."""
-    st = stage_solutions(d, lam0, dense, kinds)
+    st = stage_solutions(d, lam0, dense, kinds, inclusive)
     return assemble_from(st) + (st,)
 
 
-def newton_step(d, lam0, dense=False, kinds=None, reg=0.0):
+def newton_step(d, lam0, dense=False, kinds=None, reg=0.0, inclusive=True):
     """The step of the dual Newton method at lam0 (concatenation of lambda_1 .. lambda_{Nn-1}).  kinds: per-node stage solver (0
     clipping on the diagonals of Q, R; 1 dense unconstrained; 2 dense with box bounds), H_k then from the blocks Q, R, S; None:
     all clipping on Qd, Rd (dense=False) or all dense unconstrained (dense=True).  Returns dict(dlam, res, cond, margin, cert,
     stages): margin is the smallest, over the entries whose bounds differ, of the distance of an unclipped stage value to a
     clipping threshold (clipping nodes), of the distance of a free entry to either bound and of |g_i| of a fixed entry (box
     nodes); inf on dense unconstrained trees.  stages is what stage_solutions returns.  reg > 0 adds reg I to M (the solver's
-    regType = 1); the device pins of the unregularised step use reg = 0 (reg_ref.py has the block-wise regularisation)."""
-    M, res, st = assemble(d, lam0, dense, kinds)
+    regType = 1); the device pins of the unregularised step use reg = 0 (reg_ref.py has the block-wise regularisation).
+    inclusive: see stage_solutions (True everywhere but in the tests of the clipping rule itself)."""
+    M, res, st = assemble(d, lam0, dense, kinds, inclusive)
     n = len(res)
     if reg:
         M = M + LD(reg) * np.eye(n, dtype=LD)

@@ -60,7 +60,7 @@ def _backward(L, inv, y):
     return x
 
 
-def block_newton_step(d, lam0, regType, regTol, regValue, dense=False, kinds=None, dtype=LD, check=True):
+def block_newton_step(d, lam0, regType, regTol, regValue, dense=False, kinds=None, dtype=LD, check=True, inclusive=True):
     """The regularised step at lam0.  Returns dict(dlam, res, flagged, pivots, guard, cond, margin, stages, xcheck, shift, zero):
     - flagged: the blocks (parent ids, in the order they are factorised) whose diagonal was shifted;
     - pivots: per block, dict(first=the L_jj of the first pass up to and including the first one <= regTol (all of them when none
@@ -73,8 +73,8 @@ def block_newton_step(d, lam0, regType, regTol, regValue, dense=False, kinds=Non
       that searches for a usable lambda0 looks at it itself);
     - shift, zero: per dual entry, what was added to its diagonal and whether its column is a zero column.
     dtype = np.float64 runs elimination and substitution in float64 (what a float64 implementation computes, for measuring the
-    sensitivity of a row; the cross-check is then not asserted)."""
-    M, res, st = N.assemble(d, lam0, dense, kinds)
+    sensitivity of a row; the cross-check is then not asserted).  inclusive: the clipping rule, see newton_ref.stage_solutions."""
+    M, res, st = N.assemble(d, lam0, dense, kinds, inclusive)
     M, res = M.astype(dtype), res.astype(dtype)
     nk, nx, nu, xo, uo, dad, A, B, b, kids, lo_, _ = st["tree"]
     n = len(res)
