@@ -3,7 +3,7 @@
  * tqgpu_mpc_adjoint_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, tqgpu_mpc_adjoint_bounds,
  * tqgpu_mpc_adjoint_reference, and the readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
  * Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind tdunes_mpc.hpp (mpc_refuse, mpc_take_x0, MpcLive) and tdunes_kkt.hpp
- * (enqueue_export, export_all_entry).  That file keeps the mirror's records MpcSens, MpcAdjBatch, MpcAdjMat and the plan of a batched call
+ * (enqueue_export, export_all_entry).  tdunes_mirror.hpp keeps the mirror's records MpcSens, MpcAdjBatch, MpcAdjMat, tdunes_device.hip the plan of a batched call
  * (DeviceGroup .. order_behind_lead).
  */
 #pragma once
@@ -56,7 +56,7 @@ int setup_sens(tqgpu_solver *s) {
         (rc = s->mem.host(s->sens.h, sizeof(double) * (head + nx0 + nu0 + 2), "the pinned gain")))
         return rc;
     memset(s->sens.h, 0, sizeof(double) * (head + nx0 + nu0 + 2));
-    if ((rc = allow_lds(k_sens_hess, s->lds_hess)) || (rc = allow_lds(k_sens_factor, lf)) || (rc = allow_lds(k_sens_forward, s->lds_forward)) || (rc = allow_lds(k_sens_primal, lp)))
+    if ((rc = allow_lds(k_sens_hess, s->pp.lds_hess)) || (rc = allow_lds(k_sens_factor, lf)) || (rc = allow_lds(k_sens_forward, s->pp.lds_forward)) || (rc = allow_lds(k_sens_primal, lp)))
         return rc;
     Sens &S = s->sens.v;
     S = Sens{};
@@ -103,7 +103,7 @@ int sens_enqueue_factor(tqgpu_solver *s, const Opts &O, Sens &S) {
     }
     S = sens_view_of_point(s);
     const Tree &T = s->T;
-    hipLaunchKernelGGL(k_sens_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, s->stream, T, s->D, S);
+    hipLaunchKernelGGL(k_sens_hess, dim3(T.Np), dim3(WAVE), s->pp.lds_hess, s->stream, T, s->D, S);
     for_levels(s, Walk::to_root, [&](int first, int count) { hipLaunchKernelGGL(k_sens_factor, dim3(count), dim3(WAVE), s->sens.lds_factor, s->stream, T, O, S, first); });
     HIP_TRY(hipGetLastError());
     MPC_COUNT(launches, 1 + T.Nh);
@@ -141,7 +141,7 @@ int setup_adj(tqgpu_solver *s, int nw) {
             const size_t nz = (size_t)(s->nx[k] + s->nu[k]);
             lr = std::max(lr, (nz + 2) * sizeof(double)); lg = std::max(lg, (2 * nz + 2) * sizeof(double));
         }
-        if ((rc = allow_lds(k_adj_rhs, lr)) || (rc = allow_lds(k_adj_backward, s->lds_forward)) || (rc = allow_lds(k_adj_forward, s->lds_forward)) || (rc = allow_lds(k_adj_grad, lg)))
+        if ((rc = allow_lds(k_adj_rhs, lr)) || (rc = allow_lds(k_adj_backward, s->pp.lds_forward)) || (rc = allow_lds(k_adj_forward, s->pp.lds_forward)) || (rc = allow_lds(k_adj_grad, lg)))
             return rc;
         Adj &A = m.a;
         A = Adj{};
@@ -200,7 +200,7 @@ static int mpc_sensitivity_one(tqgpu_solver *s, const Opts &O, int *n_reg) {
     if ((rc = sens_enqueue_factor(s, O, S))) return rc;
     const Tree &T = s->T;
     hipStream_t st = s->stream;
-    for_levels(s, Walk::to_leaves, [&](int first, int count) { hipLaunchKernelGGL(k_sens_forward, dim3(count, (unsigned)s->sens.nx0), dim3(WAVE), s->lds_forward, st, T, S, first); });
+    for_levels(s, Walk::to_leaves, [&](int first, int count) { hipLaunchKernelGGL(k_sens_forward, dim3(count, (unsigned)s->sens.nx0), dim3(WAVE), s->pp.lds_forward, st, T, S, first); });
     hipLaunchKernelGGL(k_sens_primal, dim3(T.Nn), dim3(WAVE), s->sens.lds_primal, st, T, s->D, S);
     HIP_TRY(hipGetLastError());
     MPC_COUNT(launches, (T.Nh - 1) + 1);
@@ -243,8 +243,8 @@ static int mpc_adjoint_one(tqgpu_solver *s, const Opts &O, const double *wx, con
     const Adj A = m.a;
     const unsigned cols = (unsigned)nw;
     hipLaunchKernelGGL(k_adj_rhs, dim3(T.Np, cols), dim3(WAVE), m.lds_rhs, st, T, s->D, S, A);
-    for_levels(s, Walk::to_root, [&](int first, int count) { hipLaunchKernelGGL(k_adj_backward, dim3(count, cols), dim3(WAVE), s->lds_forward, st, T, S, A, first); });
-    for_levels(s, Walk::to_leaves, [&](int first, int count) { hipLaunchKernelGGL(k_adj_forward, dim3(count, cols), dim3(WAVE), s->lds_forward, st, T, S, A, first); });
+    for_levels(s, Walk::to_root, [&](int first, int count) { hipLaunchKernelGGL(k_adj_backward, dim3(count, cols), dim3(WAVE), s->pp.lds_forward, st, T, S, A, first); });
+    for_levels(s, Walk::to_leaves, [&](int first, int count) { hipLaunchKernelGGL(k_adj_forward, dim3(count, cols), dim3(WAVE), s->pp.lds_forward, st, T, S, A, first); });
     hipLaunchKernelGGL(k_adj_grad, dim3(T.Nn, cols), dim3(WAVE), m.lds_grad, st, T, s->D, S, A);
     HIP_TRY(hipGetLastError());
     MPC_COUNT(launches, 1 + T.Nh + (T.Nh - 1) + 1);
@@ -382,12 +382,12 @@ int adj_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> 
             wide_bwd[Nh - 1 - l] = std::max(wide_bwd[Nh - 1 - l], count);
             if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
         }
-        l_sweep = std::max(l_sweep, s->lds_forward); l_rhs = std::max(l_rhs, ms.lds_rhs); l_grad = std::max(l_grad, ms.lds_grad);
+        l_sweep = std::max(l_sweep, s->pp.lds_forward); l_rhs = std::max(l_rhs, ms.lds_rhs); l_grad = std::max(l_grad, ms.lds_grad);
         if (it.needs_factor) {
             np_fac = std::max(np_fac, s->T.Np); nh_fac = std::max(nh_fac, Nh);
             if ((int)wide_fac.size() < Nh) wide_fac.resize(Nh, 0);
             for (int l = 0; l < Nh; l++) wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], s->lvl_first[l + 1] - s->lvl_first[l]);
-            l_hess = std::max(l_hess, s->lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
+            l_hess = std::max(l_hess, s->pp.lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
             if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
         }
     }
@@ -414,7 +414,7 @@ int adj_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> 
     HIP_TRY(hipGetLastError());
     MPC_COUNT(launches, 1 + nh_all + (nh_all - 1) + 1);
     HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
-    lead->stream_pending = true;
+    lead->links.stream_pending = true;
     return TQGPU_OK;
 }
 }  // namespace
@@ -469,7 +469,7 @@ extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgp
         tqgpu_solver *lead = solvers[g.idx[0]];
         HIP_TRY(hipSetDevice(lead->device));
         HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->stream_pending = false;
+        lead->links.stream_pending = false;
         const double *h = lead->adjb.h_heads;
         for (size_t m = 0; m < g.idx.size(); m++) {
             const int i = g.idx[m];
@@ -544,8 +544,8 @@ int sens_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens>
             wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], count);
             if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
         }
-        l_hess = std::max(l_hess, s->lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
-        l_sweep = std::max(l_sweep, s->lds_forward); l_primal = std::max(l_primal, ms.lds_primal);
+        l_hess = std::max(l_hess, s->pp.lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
+        l_sweep = std::max(l_sweep, s->pp.lds_forward); l_primal = std::max(l_primal, ms.lds_primal);
         if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
     }
     MPC_COUNT(waits, waits);
@@ -564,7 +564,7 @@ int sens_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens>
     HIP_TRY(hipGetLastError());
     MPC_COUNT(launches, (1 + nh_all) + (nh_all - 1) + 1);
     HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
-    lead->stream_pending = true;
+    lead->links.stream_pending = true;
     return TQGPU_OK;
 }
 }  // namespace
@@ -607,7 +607,7 @@ extern "C" int tqgpu_mpc_sensitivity_batch(tqgpu_solver **solvers, int n, const 
         tqgpu_solver *lead = solvers[g.idx[0]];
         HIP_TRY(hipSetDevice(lead->device));
         HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->stream_pending = false;
+        lead->links.stream_pending = false;
         /* every member's pinned head from the group's copy, then its flags: as its own call leaves it */
         const double *h = lead->sensb.h_heads;
         for (size_t m = 0; m < g.idx.size(); m++) {
@@ -819,7 +819,7 @@ int adjmat_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, int reduce, std
     HIP_TRY(hipGetLastError());
     if (total) HIP_TRY(hipMemcpyAsync(B.h_bres, B.d_bres, sizeof(double) * total, hipMemcpyDeviceToHost, ls));
     MPC_COUNT(copies, 1);
-    lead->stream_pending = true;
+    lead->links.stream_pending = true;
     return TQGPU_OK;
 }
 }  // namespace
@@ -1021,7 +1021,7 @@ extern "C" int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, i
         tqgpu_solver *lead = solvers[g.idx[0]];
         HIP_TRY(hipSetDevice(lead->device));
         HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->stream_pending = false;
+        lead->links.stream_pending = false;
         for (size_t k = 0; k < (reduce ? 1 : g.idx.size()); k++) {
             const tqgpu_solver *s = solvers[g.idx[k]];
             adjmat_scatter(s->adjm, lead->adjm.h_bres + sent[gi][k], s->sens.nw, out, span[(size_t)g.idx[k]].data());
@@ -1140,7 +1140,7 @@ int predict_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, const double *
     hipLaunchKernelGGL(k_mpc_predict_batch, dim3(duals ? 1 + (unsigned)nn_all : 1u, 1, (unsigned)n), dim3(WAVE), 0, ls, reinterpret_cast<const PredItem *>(B.d_pdesc));
     HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
     for (int i : g.idx) predict_lent(v[i], duals);
-    lead->stream_pending = true;
+    lead->links.stream_pending = true;
     return TQGPU_OK;
 }
 }  // namespace
@@ -1181,7 +1181,7 @@ extern "C" int tqgpu_mpc_predict_batch(tqgpu_solver **solvers, int n, const doub
         tqgpu_solver *lead = solvers[g.idx[0]];
         HIP_TRY(hipSetDevice(lead->device));
         HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->stream_pending = false;
+        lead->links.stream_pending = false;
         const double *io = lead->sensb.h_io;
         for (int i : g.idx) {
             const size_t nx0 = (size_t)solvers[i]->sens.nx0, nu0 = (size_t)solvers[i]->nu[0];

@@ -27,14 +27,20 @@
  * Control flow lives in a device control block (struct Ctrl): every kernel first looks at it and
  * returns if its phase is not due, so the host may enqueue ahead without reading back.
  *
- * The kernels above are the launch-per-phase protocol (any tree).  Faster protocols for the trees that admit them are in the
- * headers included below: tdunes_fast.hpp / tdunes_persist.hpp (uniform and multistage trees: the whole solve as ONE launch, also
- * dealt over several devices: tqgpu_pshard_*), tdunes_wide.hpp / tdunes_wide3.hpp (dual blocks of 16 < d <= 64 rows: MFMA kernels,
- * three launches per Newton iteration), tdunes_gpersist.hpp (small trees of any shape: one workgroup per tree).  The MPC family (tqgpu_mpc_*),
- * kernels and entry points, is tdunes_mpc.hpp, and the host side of a step's sensitivities and adjoints tdunes_adjoint.hpp, both included into
- * the host part; this file keeps the mirror's records for them, MpcStats, MpcPre, and the plan the batched after-solve calls share (DeviceGroup ..).
- * What problem a mirror holds and which stage solver each node runs (the setters and getters of the problem's data, tqgpu_set_problem) is
- * tdunes_problem.hpp, included into the host part ahead of the solve; this file keeps its records StageKinds, GenRows, DenseSingle.
+ * The kernels above are the launch-per-phase protocol (any tree); they and the host side of a solve (setup, launch helpers, solve, batch, logs)
+ * are in this file, with what more than one kernel family uses (Tree .. rdlane).  What is in a header of its own:
+ *   tdunes_fast.hpp / tdunes_persist.hpp   uniform and multistage trees: launches per tier; the whole solve as ONE launch, also dealt over several
+ *                        devices (tqgpu_pshard_*)
+ *   tdunes_wide.hpp / tdunes_wide3.hpp     dual blocks of 16 < d <= 64 rows: MFMA kernels, three launches per Newton iteration
+ *   tdunes_gpersist.hpp  small trees of any shape: one workgroup per tree
+ *   tdunes_sens.hpp      kernels of the sensitivities and adjoints of an MPC step
+ *   tdunes_mirror.hpp    (host part, as all below) tqgpu_solver and its records: one per route (PerPhase, Wide3, SingleWg, Uniform, Persist), one per
+ *                        feature family (Mpc*, Export, Kkt, SubtreeShard, PersistShard, StageKinds, GenRows, DenseSingle), Timing, BatchLinks; Owned, fail, settle
+ *   tdunes_problem.hpp   what problem a mirror holds and which stage solver each node runs: the setters and getters of the problem's data
+ *   tdunes_kkt.hpp       solution export and the KKT check, kernels and entry points
+ *   tdunes_mpc.hpp       the MPC family (tqgpu_mpc_*), kernels and entry points; MpcStats, MpcPre stay here with the solve
+ *   tdunes_adjoint.hpp   the host side of a step's sensitivities and adjoints; the plan the batched after-solve calls share (DeviceGroup ..) stays here
+ *   tdunes_shard.hpp     the two multi-device modes (tqgpu_shard_*, tqgpu_pshard_*)
  */
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -1781,395 +1787,7 @@ __global__ void __launch_bounds__(WAVE) k_ls_decide_parts(Data D, Opts O, const 
 using namespace tqd;
 
 #if TQ_HAS(TQP_HOST)
-namespace tqd {
-thread_local std::string g_err;
-int fail(int code, const std::string &msg) { g_err = msg; return code; }
-}  // namespace tqd
-
-/* ============================================================================================ */
-/* host side of the C-ABI                                                                       */
-/* ============================================================================================ */
-
-/* which kernels a solve launches, decided once per solve by route_of: the paths of DESIGN.md §4 (FUSED_TAILS: k_stage_f, k_grad_f) */
-enum class Route { PERSIST, SINGLE_WG, TIERED, THREE_LAUNCH, FUSED_TAILS, PER_PHASE };
-static bool single_launch(Route r) { return r == Route::PERSIST || r == Route::SINGLE_WG; }      /* verdict through the result block */
-
-/* The device and pinned host memory of a mirror.  What is allocated through it is freed by tqgpu_destroy (free_all) unless it was given
- * back before (release); the named pointers of tqgpu_solver are views.  A failed call has set the error text, with `name` in it. */
-struct Owned {
-    std::vector<void *> dev, pinned;
-    enum Fill { RAW, ZEROED, FINE_GRAINED };      /* FINE_GRAINED: hipExtMallocWithFlags (tqgpu_pshard_init) */
-    static int failed(int code, const char *name, hipError_t e) { return fail(code, std::string("allocation of ") + name + " failed: " + hipGetErrorString(e)); }
-    template <typename T>
-    int device(T *&p, size_t bytes, int code, const char *name, Fill fill = RAW, const void *src = nullptr) {
-        void *q = nullptr;
-        hipError_t e = fill == FINE_GRAINED ? hipExtMallocWithFlags(&q, bytes, hipDeviceMallocFinegrained) : hipMalloc(&q, bytes);
-        if (e != hipSuccess) return failed(code, name, e);
-        dev.push_back(q); p = static_cast<T *>(q);
-        if (fill == ZEROED) e = hipMemset(q, 0, bytes);
-        if (src) e = hipMemcpy(q, src, bytes, hipMemcpyHostToDevice);
-        return e == hipSuccess ? TQGPU_OK : failed(code, name, e);
-    }
-    template <typename T> int zeroed(T *&p, size_t bytes, int code, const char *name) { return device(p, bytes, code, name, ZEROED); }
-    template <typename T> int upload(T *&p, const void *src, size_t bytes, int code, const char *name) { return device(p, bytes, code, name, RAW, src); }
-    template <typename T>
-    int host(T *&p, size_t bytes, const char *name) {
-        void *q = nullptr;
-        hipError_t e = hipHostMalloc(&q, bytes, hipHostMallocDefault);
-        if (e != hipSuccess) return failed(TQGPU_ENOMEM, name, e);
-        pinned.push_back(q); p = static_cast<T *>(q);
-        return TQGPU_OK;
-    }
-    /* a buffer that is replaced during the mirror's life (nullptr: nothing to do) */
-    template <typename T>
-    void release(T *&p) {
-        auto d = std::find(dev.begin(), dev.end(), (void *)p), h = std::find(pinned.begin(), pinned.end(), (void *)p);
-        if (d != dev.end()) { (void)hipFree(*d); dev.erase(d); }
-        else if (h != pinned.end()) { (void)hipHostFree(*h); pinned.erase(h); }
-        p = nullptr;
-    }
-    void free_all() {
-        for (void *q : dev) (void)hipFree(q);
-        for (void *q : pinned) (void)hipHostFree(q);
-    }
-};
-
-/* the creation-time switches: read from the environment once per tqgpu_create (read_switches), tested as fields by its steps */
-struct Switches {
-    bool generic, tiered, strict_sum, fwd_levels, bwd_levels, small_wide;
-    bool no_fuse, no_wide3, no_sgp, no_fwd_chain, no_fwd_merge, no_stage16, gp_no_groups, no_persist_one, verbose, has_lds_pad, has_nap;
-    bool dense_single, dense_batch;
-    int chunk, lds_pad, capacity_margin, nap;
-};
-
-namespace { struct KItem; struct KHead; struct MItem; }      /* the descriptors of the batched KKT check and of the MPC steps, the check's head (defined with their kernels) */
-
-/* ---- what a mirror keeps for the MPC family (tqgpu_mpc_*, tdunes_mpc.hpp), one record per feature ---- */
-/* the root terms (tqgpu_mpc_set_root): d, the originals of what multiplies x0, [A0 | b0 | S0 | r0 | C0 | dmin0 | dmax0] in one device block;
- * h, pinned: x0 (nx0 doubles), u[0] (nu[0] doubles) and the tag of k_mpc_post */
-struct MpcRoot {
-    double *d = nullptr, *h = nullptr;
-    int nx0 = 0, nb = 0, nc0 = 0;       /* nx0, rows of b0 (the children's nx), rows of C0; nx0 == 0: no root terms yet */
-    bool S0 = false, C0 = false, states = false;      /* states, tqgpu_mpc_set_root_states: x0 enters as xmin[0] = xmax[0] = x0 over the root's nx[0] states; no originals (d stays null) */
-    bool certify = false, cert_valid = false;      /* tqgpu_mpc_set_certify; cert holds the certificate of the last tqgpu_mpc_step */
-    double cert[10] = {};               /* the head of the KKT result block (KKT_HEAD doubles) as it arrived with the step's tag */
-    unsigned long long tag = 0;         /* the tag of the last u0 post this mirror waited for (its own block, or as the lead of a batch) */
-};
-/* tqgpu_set_warm_start; fresh: the start buffer holds what the caller (or a batch step's launch) put there for the next solve: no copy ahead of it */
-struct MpcWarm { int mode = 0; bool fresh = true; };
-/* the shift (tqgpu_mpc_set_shift): d, per realisation j < max(nk[0], 1) the source entry of every entry of the start buffer, [j][sum_nx]
- * ints, and behind them the node tables [j][Nn] (the image a node may take its working sets from, -1: none), in one device block;
- * d_keep: sum_nx doubles, the caller's start buffer while a tqgpu_mpc_shift of a mirror in mode 0 holds its place for one solve */
-struct MpcShift {
-    int *d = nullptr; double *d_keep = nullptr; int leaf = 0, realised = 0; unsigned what = 0;
-    int restore = 0;                    /* 1: tqgpu_mpc_shift saved the start buffer of a mirror in mode 0, the next solve consumes the shifted one; 2: that solve has begun, the one after it puts the saved buffer back first */
-};
-struct MpcBatchBuf {
-    long drained_at = 0;                /* as Kkt::drained_at, for the batch step's launch ahead of the solves */
-    MItem *d_items = nullptr, *h_items = nullptr; int items_cap = 0;      /* batch steps: one descriptor per member of this device (the device's first member owns the array) */
-    double *h_u0s = nullptr; int u0s_cap = 0;                             /* ... and their u[0] with the tag behind them, pinned */
-};
-/* tracking (tqgpu_mpc_set_tracking): d, [xtraj T x NXT | utraj T x NUT | q0 (sum_nx, node-indexed as Data::q, phantom root states included) |
- * r0 (sum_nu)] in one device block, the nodes' stages behind it as ints; t0: the window the device's q, r were last folded for (-1: none yet) */
-struct MpcTrack { double *d = nullptr; int T = 0, nxt = 0, nut = 0, t0 = -1; };
-/* ---- what a mirror keeps for the derivatives of an MPC step (tdunes_adjoint.hpp; kernels in tdunes_sens.hpp): MpcSens, MpcAdjBatch, MpcSensBatch, MpcAdjMat ---- */
-/* tqgpu_mpc_sensitivity: buffers of its own (setup_sens, on first use; one device block d, views in v); pinned h:
- * [head: K (nu0 x nx0) | u0 (nu0) | x0_ref (nx0) | n_reg] [x0_new (nx0)] [u0_pred (nu0) | n_clipped]; valid: the stored sensitivity
- * belongs to the point and the data the device holds now (cleared by every upload, fold, window move and solve) */
-struct MpcSens {
-    double *d = nullptr, *h = nullptr; Sens v{}; int nx0 = 0;
-    bool valid = false, dirty = false;  /* dirty: the problem was changed (upload, fold, window move) since the last solve: its point and the data no longer belong together */
-    bool factored = false;              /* P, L, CholUt, invd of the point and the data the device holds now are in v (tqgpu_mpc_sensitivity, tqgpu_mpc_adjoint); valid implies it */
-    size_t lds_factor = 0, lds_primal = 0;
-    /* tqgpu_mpc_adjoint: buffers of its own (setup_adj, on first use and again when nw grows; one device block ad, views in a); pinned ah:
-     * [w: wx ((sum_nx - x_pad) x nw) | wu (sum_nu x nw)] [head: gx0 (nx0 x nw) | n_reg]; adj_valid: the stored adjoint (nw columns)
-     * belongs to the point and the data the device holds now */
-    double *ad = nullptr, *ah = nullptr; Adj a{}; int nw_cap = 0, nw = 0, adj_nx0 = 0;
-    bool adj_valid = false;
-    size_t lds_rhs = 0, lds_grad = 0;
-    void invalidate() { valid = factored = adj_valid = false; }      /* every upload, fold, window move and solve */
-};
-/* tqgpu_mpc_adjoint_batch, batched route (the first member of a device's group owns all three): desc, the descriptors (AItem) with the members'
- * level tables behind them, uploaded with every call in one copy; w, the loss gradients of all members, [wx | wu] member after member, one
- * copy (Adj::wx, Adj::wu of a descriptor point into d_w); heads, [gx0 | n_reg] of all members, one copy back (Adj::head points into d_heads).
- * Each is a device block and its pinned twin; the capacities are bytes of desc, doubles of w and of heads */
-struct MpcAdjBatch {
-    long drained_at = 0;                /* as Kkt::drained_at, for the launches of the batched adjoint */
-    char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
-    double *d_w = nullptr, *h_w = nullptr; size_t w_cap = 0;
-    double *d_heads = nullptr, *h_heads = nullptr; size_t heads_cap = 0;
-};
-/* tqgpu_mpc_sensitivity_batch and tqgpu_mpc_predict_batch, batched route (the first member of a device's group owns them): desc, the descriptors
- * (AItem) with the members' level tables behind them, one copy per call; heads, the heads of all members ([K | u0 | x0_ref | n_reg] each, AItem::head_out
- * points into d_heads), one copy back; pdesc, the predictor's descriptors (PredItem), one copy per call; h_io, pinned only, per member
- * [x0_new (nx0) | u0_pred (nu0) | n_clipped], which the predictor's kernel reads and writes in place.  Capacities: bytes of desc and pdesc, doubles of
- * heads and io */
-struct MpcSensBatch {
-    long drained_at = 0;                /* as Kkt::drained_at, for the launches of the batched sensitivity */
-    char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
-    double *d_heads = nullptr, *h_heads = nullptr; size_t heads_cap = 0;
-    char *d_pdesc = nullptr, *h_pdesc = nullptr; size_t pdesc_cap = 0;
-    double *h_io = nullptr; size_t io_cap = 0;
-};
-
-/* tqgpu_mpc_set_param_groups / tqgpu_mpc_adjoint_matrices*: the maps as given (a NULL map filled in), the tables built from them and from the kinds, the
- * root form and nx0 the device held then (sig; compared at every call, built and uploaded again where they moved), the sizes of the seven result regions
- * and of the partials in doubles per column of w, the result block on the device and pinned, the partials.  Batched route (the first member of a device's
- * group owns them): the descriptors (AMItem), uploaded with every call, and the result block of all members with its pinned twin */
-struct MpcAdjMat {
-    bool set = false;
-    std::vector<int> hgroup, cgroup, sig, hdims, cdims;      /* hdims: nx, nu, pad, members per h-group; cdims: nx_c, nx_p, nu_p, members per c-group */
-    int n_h = 0, n_c = 0, n_units = 0;
-    int *d_tab = nullptr;
-    AdjMat v{};
-    size_t reg[8] = {}, part1 = 0, lds = 0;      /* reg[i]: where region i of [gH | gh | gA | gB | gb | gA0 | gS0] begins, reg[7] the total */
-    double *d_res = nullptr, *h_res = nullptr, *d_part = nullptr; size_t res_cap = 0, part_cap = 0;
-    char *d_desc = nullptr, *h_desc = nullptr; size_t desc_cap = 0;
-    double *d_bres = nullptr, *h_bres = nullptr; size_t bres_cap = 0;
-};
-/* tqgpu_mpc_adjoint_bounds (bsum; built with the parameter groups) and tqgpu_mpc_adjoint_reference (rsum; built by tqgpu_mpc_set_tracking): the tables of
- * k_nodesum_part / k_nodesum_sum in one device block (members, set and chunk records), the set records once more on the host (which results have
- * more than one partial), the partials per column of w, the LDS window, and the call's own result block, its pinned twin and partials */
-struct MpcNodeSum {
-    int *d_tab = nullptr; NodeSum v{}; std::vector<int> set;
-    size_t part1 = 0, lds = 0;
-    double *d_res = nullptr, *h_res = nullptr, *d_part = nullptr; size_t res_cap = 0, part_cap = 0;
-};
-/* ---- the solution's way out and its check (tdunes_kkt.hpp): the solution in one piece, [x | u | lam | dlam | mu_x | mu_u], packed on the device (d) and
- * downloaded into pinned memory (h).  valid: h holds (or is about to hold, stream-ordered) the solution of the last solve; dev_only, with valid: the pack
- * is in d only (a certified tqgpu_mpc_step), tqgpu_get_solution downloads it.  The three transitions below are the only writers of the two flags. ---- */
-struct Export {
-    double *d = nullptr, *h = nullptr; size_t doubles = 0;
-    bool ahead = false;                 /* tqgpu_set_export_ahead: the packing kernel and the download of the solution are enqueued right behind a single persistent launch */
-    bool valid = false, dev_only = false;
-    void invalidate() { valid = false; }                                   /* the device holds another point, or is about to: a solve begins, rows or the sharing change */
-    void packed_on_device() { valid = true; dev_only = true; }             /* packed behind a certified step; no download yet */
-    void packed_and_downloading() { valid = true; dev_only = false; }      /* the pack and its download are on the stream (an export ahead), or the download of a pack that was on the device only */
-};
-/* tqgpu_kkt_residual*: d, h, [six maxima | six nodes | pad | Nn x 6 table] on the device and pinned (setup_kkt, on first use); d_pt, h_pt, the point of
- * tqgpu_kkt_residual_at, [x | u | lam | mu_x | mu_u | mu_d], on the device and pinned (grows with sum_nc).
- * tqgpu_kkt_residual_batch, batched route (the first member of a device's group owns both): one descriptor per member, uploaded
- * with every call, and the members' heads in one block, downloaded in one copy */
-struct Kkt {
-    double *d = nullptr, *h = nullptr, *d_pt = nullptr, *h_pt = nullptr; size_t pt_cap = 0;
-    KItem *d_items = nullptr, *h_items = nullptr; int items_cap = 0;
-    KHead *d_heads = nullptr, *h_heads = nullptr; int heads_cap = 0;
-    long drained_at = 0;                /* solve_no at which the batched route last knew this mirror's own stream to hold nothing of its solves */
-};
-/* ---- the two multi-device modes (tdunes_shard.hpp): the subtree-sharded mode (tqgpu_shard_*); rank, nranks and part_top are the sharded persistent launch's as well ---- */
-struct SubtreeShard {
-    int nranks = 1, rank = 0, part_top = -1;      /* part_top: highest partitioned tier */
-    bool on = false;          /* subtree-sharded mode (nranks > 1, or ONE rank with a communicator: the same code path, used to exercise the RCCL transport on a one-GPU box) */
-    int *d_gh_list = nullptr, *d_node_list = nullptr, *d_node_cnt_list = nullptr, *d_blk_list = nullptr;
-    int gh_n = 0, gh_counted = 0, n_nodes = 0, n_nodes_counted = 0, n_blk_counted = 0;
-    double *d_xerr = nullptr, *d_xs = nullptr;
-    int bnd_b0 = 0, bnd_bn = 0, bnd_own0 = 0, bnd_ownn = 0;   /* element ranges of the boundary nodes' duals */
-    void *slab = nullptr;
-    void *comm = nullptr;     /* RCCL communicator (nullptr: single device or virtual ranks) */
-};
-/* ONE tree over several devices INSIDE the persistent launch (tqgpu_pshard_*): this rank's share of the workgroups */
-struct PersistShard {
-    bool on = false;
-    bool sys = true;                /* the sharded launch polls its slab with system-scope loads (f_persist_sh<.., 1>); TREEQP_AMD_PSHARD_AGENT=1: agent scope, as on one device */
-    bool fine = false;              /* the hand-over slab was re-allocated as fine-grained memory (tqgpu_pshard_init; TREEQP_AMD_PSHARD_COARSE=1 keeps plain hipMalloc memory) */
-    int *wg_map = nullptr;          /* blockIdx.x -> workgroup id, this rank's workgroups (bottom tier first) */
-    int G = 0;
-    void *ipc[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      /* peer slabs opened through IPC handles (closed by tqgpu_destroy) */
-    unsigned long long *h_peers[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* slabs of all ranks (a mirror that is not sharded: its own, eight times) ... */
-    unsigned long long **d_peers = nullptr;                                                               /* ... and the device copy of the table the kernel reads */
-};
-/* ---- what problem the mirror holds and which stage solver each node runs (tdunes_problem.hpp): StageKinds, GenRows, DenseSingle ---- */
-/* the stage solvers selected (tqgpu_set_objective_mixed; tqgpu_set_objective_diag and tqgpu_set_problem return to clipping): dense, some nodes
- * use a dense stage solver (generic path only); box, some of them have box bounds (kind 2): the stage sweep is k_stage_box with lds_box bytes;
- * gen, some have general constraints as well (kind 3): k_stage_gen with lds_gen bytes; lds_dense: k_dense_init's */
-struct StageKinds {
-    bool dense = false, need_dense_init = false, box = false, gen = false;
-    size_t lds_dense = 0, lds_box = 0, lds_gen = 0;
-    std::vector<int> h_kind;     /* the kinds last set, as the device has them: a kind-3 node without rows is a kind-2 node */
-    std::vector<int> h_kind_req; /* ... as the caller gave them */
-    std::vector<double> h_bounds; /* the bounds last set by tqgpu_set_bounds (device layout: xmin | xmax | umin | umax); empty: unknown */
-    double *d_Hd = nullptr; int *d_kind = nullptr;      /* writable aliases of Data.Hd, Data.kind */
-    int kind(int k) const { return dense && !h_kind.empty() ? h_kind[(size_t)k] : 0; }      /* of node k; 0 (clipping) unless the mirror is dense */
-    bool working_sets(size_t Nn) const { return dense && (box || gen) && h_kind.size() == Nn; }      /* the mirror has stored working sets (kinds 2, 3) */
-};
-/* general constraints (tqgpu_set_constraints): rows per node, their offsets and those of the blocks of Gt, host copies of dmin | dmax, the
- * device blocks and the record Data.gen points to */
-struct GenRows {
-    std::vector<int> nc, roff, goff;
-    std::vector<double> h_drange; int sum_nc = 0;
-    int *d_tab = nullptr;        /* Gen::nc, roff, goff */
-    double *d_Gt = nullptr, *d_drange = nullptr, *d_mu = nullptr;
-    unsigned long long *d_rmask = nullptr;     /* 4 Nn words: Gen::rmask (2 Nn), Gen::sides (2 Nn) */
-    long *d_steps = nullptr;     /* Gen::steps_total (Nn longs), then Gen::steps_last (Nn ints) */
-    bool hot = true;             /* stage_gen starts from the stored working sets (tqgpu_set_gen_hot_start) */
-    Gen h_gen{};                 /* what d_gen holds: the views of the blocks above are taken from it */
-    Gen *d_gen = nullptr;
-    unsigned long long *row_sides(size_t Nn) const { return d_rmask + 3 * Nn; }      /* the second half of h_gen.sides: the sides of the rows */
-};
-/* the single-workgroup solve of a dense tree (g_persist_dense, opt-in): the caller's two choices, then the plan of plan_dense_single for the
- * kinds and rows last set */
-struct DenseSingle {
-    bool single = false;         /* tqgpu_set_dense_single_launch, TREEQP_AMD_DENSE_SINGLE_LAUNCH=1 */
-    bool batch = false;          /* ... for the members of a batch: one launch of g_persist_dense_batch, a workgroup per tree (tqgpu_set_dense_batch_launch, TREEQP_AMD_DENSE_BATCH_LAUNCH=1); independent of single */
-    bool ok = false;             /* the tree with its current kinds and rows fits */
-    int stage_waves = 0, phase_waves = 0;      /* waves of the stage sweep (0: does not fit), of the sweeps over blocks (GPD_WAVES unless that many windows of lds_gp_wave doubles do not fit) */
-    size_t win_stage = 0, win_region = 0, lds_total = 0;      /* doubles: a stage window, the window region; bytes of dynamic LDS of g_persist_dense */
-    bool in_lds = false, const_in_lds = false, tab_in_lds = false;
-};
-
-struct tqgpu_solver {
-    Owned mem;
-    Switches sw{};
-    int device = 0;
-    int Nn = 0, Np = 0, Nh = 0;
-    std::vector<int> nk, nx, nu, dad, stage, kid0, xoff, uoff, aoff, boff, pos, bdim, woff, utoff, lvl_first;
-    int sum_nx = 0, sum_nu = 0, sum_lam = 0, sum_A = 0, sum_B = 0, sum_W = 0, sum_Ut = 0, nx0 = 0, nxmax = 0;
-    size_t lds_stage = 0, lds_hess = 0, lds_factor = 0, lds_forward = 0;
-    bool wide = false;              /* larger blocks (16 < d <= 64): workgroup-per-block MFMA kernels (tdunes_wide.hpp) */
-    bool wide_small = false;        /* ... taken by a tree of small blocks (d <= 16) too wide for the single-workgroup kernel */
-    size_t lds_hess_w = 0, lds_factor_w = 0, lds_forward_w = 0;
-    unsigned long long *fw_words = nullptr;   /* launch-per-phase path: the steps of a forward sweep as tagged words (k_forward_all_w), [sum_nx][2] */
-    unsigned fw_epoch = 0;              /* tag of the last fused forward launch */
-    bool fw_fused = true;               /* TREEQP_AMD_FWD=levels: one launch per level instead */
-    unsigned long long *sch_words = nullptr;  /* launch-per-phase path: Schur records of a fused backward sweep as tagged words (k_factor_all_w), [Nn][sch_rs][2] */
-    int sch_rs = 0;                     /* doubles per record: (max nx + 1)^2 */
-    unsigned bw_epoch = 0;
-    bool bw_fused = true;               /* TREEQP_AMD_BWD=levels: one launch per level instead */
-    unsigned long long *fuse_red = nullptr;   /* small trees: partials of the reductions that run as the tail of a sweep (Fuse), [Nn][2] tagged words */
-    int *fuse_cnt = nullptr;            /* ... and the counter of the workgroups that have posted theirs */
-    unsigned fuse_epoch = 0;
-    bool fuse_ok = false;
-    /* three launches per Newton iteration for the wide-block class (tdunes_wide3.hpp): k_sg, k_hf_w, k_fwd3 */
-    bool w3_ok = false;
-    Route route = Route::PER_PHASE;     /* of the last solve begun */
-    unsigned long long *w3_xu = nullptr, *w3_red = nullptr;
-    int *w3_cnt = nullptr;
-    unsigned w3_epoch = 0;
-    size_t lds_hf_w = 0, lds_sgp = 0;
-    int sgp_accs = 0;
-    bool w3_sgp = false;                /* k_sgp (a workgroup per parent) instead of k_sg (a wave per node) */
-    unsigned long long *d_pdw = nullptr; /* k_sgp mode 2: the blocks' parts of res' dlam as tagged words */
-    bool w3_merge = false;              /* forward sweep and first trial in one launch (k_sgp mode 2) */
-    int *d_anc = nullptr;               /* k_fwd3c: the path to the root of every block (tdunes_wide3.hpp); nullptr: the tree does not qualify */
-    bool w3_mirror = false;             /* this solve: the launches of k_sg / k_sgp post the control block to h_res (w3_mirror in tdunes_wide3.hpp) */
-    bool w3_tail_sg = false;            /* the last launch enqueued is one of them: its tag (w3_wait) is what the host polls for */
-    unsigned w3_wait = 0;
-    bool w3_post_next = false;          /* the next launch of k_sg / k_sgp is the last of what the host enqueues before it reads the verdict: it posts */
-    bool w3_seen = false;               /* the last read of the control block came through the result block */
-    std::vector<int> ls_pred;           /* trials per iteration of the previous solve: that many trial launches are enqueued behind an iteration's forward sweep (a trial beyond the accepted one is a no-op; a read-back per extra trial is 20 us) */
-    StageKinds sk; GenRows rows; DenseSingle gpd;      /* what problem the mirror holds and which stage solver each node runs (tdunes_problem.hpp) */
-    std::vector<int> poff;
-    int use_fast_orig = 1;
-    void *slab = nullptr;
-    size_t slab_bytes = 0;
-    Tree T{};
-    Data D{};
-    double *d_mu_x = nullptr, *d_mu_u = nullptr;
-    double *d_lam_init = nullptr;   /* starting point of every solve (tqgpu_set_lambda) */
-    unsigned launch_no = 0;         /* persistent launches so far (16 bits, never 0): tags of the hand-over words */
-    void *pconst_slab = nullptr;    /* packed constants of the persistent path + its PDump */
-    int *wg_map = nullptr;          /* blockIdx.x -> workgroup id (XCD-aware placement) */
-    int co_capacity = 1;            /* workgroups of persistent launches that can be resident on the device together */
-    int n_cu = 0;
-    bool gpersist_ok = false;       /* small tree of any shape: whole solve in one launch of one workgroup (tdunes_gpersist.hpp) */
-    int use_gpersist = 1;
-    int *d_lvl_first = nullptr;
-    size_t lds_gp_wave = 0;         /* doubles of LDS per wave of g_persist */
-    size_t lds_gp_total = 0;        /* bytes of dynamic LDS of g_persist (windows + state mirror) */
-    bool persist_one = false;          /* the persistent launch of this tree takes the one-workgroup-per-CU build */
-    bool in_batch = false;             /* inside tqgpu_solve_batch: members launched one by one run side by side, two workgroups to a CU -- not with that build */
-    bool gp_in_lds = false, gp_const_in_lds = false, gp_tab_in_lds = false, gp_small16 = false, gp_small8 = false;
-    double *pab = nullptr, *pcst = nullptr;
-    bool need_pack = true;          /* QP data changed since the constants were packed */
-    /* writable aliases of the const inputs */
-    double *A = nullptr, *B = nullptr, *b = nullptr, *Qd = nullptr, *Rd = nullptr, *q = nullptr, *r = nullptr;
-    double *xmin = nullptr, *xmax = nullptr, *umin = nullptr, *umax = nullptr;
-    HostRes *h_res = nullptr;    /* pinned; the persistent kernel writes it directly */
-    Ctrl *h_ctrl = nullptr;      /* = &h_res->c */
-    std::vector<hipEvent_t> ring_ev0, ring_ev1;   /* events of the last solves (device times on request) */
-    long solve_no = 0;
-    std::vector<char> ring_ok;                    /* the event pair of that ring slot was recorded by the solve that owns it */
-    bool ev_timing = true;                        /* record a HIP event pair around every solve (tqgpu_set_event_timing) */
-    int *h_ls_log = nullptr;     /* pinned */
-    int ls_log_cap = 0;
-    hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> iter_ev;
-    std::vector<double> iter_times;
-    bool times_dirty = true;              /* iter_times / phase_times may hold times of an earlier (profiled) solve */
-    /* profile level 3 (profiling.h:38-68): events around the phase groups of every iteration on the launch-per-level path:
-     * [iteration][0..4] = start, gradient + termination test + dual Hessian done, factorisation + substitution done, line search done */
-    std::vector<hipEvent_t> phase_ev;
-    std::vector<double> phase_times;      /* [iteration][3]: build_dual, newton_direction, line_search (seconds) */
-    double first_sweep_time = NAN;        /* phase S of iteration 0 (the later ones are the accepted trial sweeps of the line searches) */
-    hipEvent_t sweep_ev0 = nullptr, sweep_ev1 = nullptr;
-    int last_iter = 0;
-    int last_ls_extra = 0;          /* the previous solve needed line-search trials beyond the first of an iteration */
-    bool need_init = true;
-    /* fused path for uniform complete trees */
-    int fast = -1;            /* index into the instantiation table, -1: generic path only */
-    int fNX = 0, fNU = 0, fMD = 0;
-    int n_tiers = 0;          /* tiers of block levels, index 0 = bottom */
-    /* pinned host mirrors: the inputs in slab layout (compare-and-copy uploads of what changed, no synchronisation),
-     * the solution in one piece */
-    char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
-    double *h_lam = nullptr; bool lam_valid = false;
-    Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcSensBatch sensb; MpcAdjMat adjm; MpcNodeSum bsum, rsum;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, sensb, adjm: tdunes_adjoint.hpp), one record per feature */
-    int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
-    bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */
-    int ms_Nr = 0, ms_S = 0, ms_nB = 0;
-    std::vector<int> tier_chain;
-    std::vector<int> tier_l0, tier_l1, tier_grid;
-    size_t lds_fast = 0, lds_fstage = 0;
-    int use_fast = 1;         /* can be switched off (TREEQP_AMD_PATH=generic) */
-    int use_persist = 1;      /* whole Newton loop in one launch when every tier workgroup can be co-resident */
-    int use_persist_orig = 1, persist_backoff = 0, n_timeouts = 0;   /* see solve_after_timeout */
-    bool persist_ok = false;
-    PGeom geom{};
-    PSync psync{};
-    PConst pconst{};
-    void *sync_slab = nullptr; size_t sync_bytes = 0;
-    int *d_desc = nullptr;
-    GItem *d_gitems = nullptr, *h_gitems = nullptr; int gitems_cap = 0;   /* batched single-workgroup launches (first mirror of a batch owns the array) */
-    PItem *d_pitems = nullptr, *h_pitems = nullptr; int pitems_cap = 0;   /* batched persistent launches: one descriptor per tree (first mirror of a batch owns the array) */
-    std::vector<unsigned long> pitems_key;                                /* the mirrors (by uid) the device copy of the array describes */
-    unsigned long uid = 0;                                                /* unique per mirror of this process (an address can come back) */
-    bool stream_pending = false;                                          /* something was enqueued on `stream` without a synchronisation after it (asynchronous uploads, constant packing): a batch launch on ANOTHER stream waits for it first */
-    hipStream_t batch_stream = nullptr;                                   /* member of a batch launch in flight: the stream that launch is on (the lead's) */
-    hipStream_t settle_stream = nullptr;                                  /* member of a batch launch whose verdict is in but whose last workgroups may still write back:
-                                                                           * the lead's stream, to be waited for before this mirror is touched through its own stream (settle) */
-    size_t sync_words_bytes = 0, lds_persist = 0;
-    bool strict_sum = false;        /* TREEQP_AMD_STRICT_SUM=1 (Data::strict) */
-    SubtreeShard shard; PersistShard pshard;      /* the two multi-device modes (tdunes_shard.hpp) */
-    int chunk = 4;            /* Newton iterations enqueued per status read-back */
-};
-
-extern "C" const char *tqgpu_last_error(void) { return g_err.c_str(); }
-/* A batch launch runs on its lead's stream; the other members' own streams are not ordered behind it.  Its end is waited for lazily:
- * a loop of batch solves on the same lead stays stream-ordered by itself and pays no synchronisation per step (10 - 15 us of a
- * 150 us step), anything else that touches a member comes through here first. */
-/* (the lead may have been destroyed in the meantime -- tqgpu_destroy synchronises its stream first, so there is nothing left to wait
- * for, but the handle must not be used: the streams of live mirrors are kept in a set) */
-static std::mutex g_streams_mu;
-static std::set<hipStream_t> g_live_streams;
-static int settle(tqgpu_solver *s) {
-    if (s && s->settle_stream) {
-        hipStream_t t = s->settle_stream;
-        s->settle_stream = nullptr;
-        bool live;
-        { std::lock_guard<std::mutex> lk(g_streams_mu); live = g_live_streams.count(t) != 0; }
-        if (t != s->stream && live) HIP_TRY(hipStreamSynchronize(t));
-    }
-    return TQGPU_OK;
-}
-#define SETTLE(s) do { int rc_ = settle(const_cast<tqgpu_solver *>(s)); if (rc_ != TQGPU_OK) return rc_; } while (0)
-extern "C" const char *tqgpu_version(void) { return "treeqp_amd tdunes device path r3 (gfx950: persistent single launch, three-launch MFMA family for 16 < d <= 64, single-workgroup and launch-per-phase kernels; sharded persistent mode)"; }
-
-extern "C" int tqgpu_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
+#include "tdunes_mirror.hpp"
 
 namespace {
 
@@ -2230,15 +1848,15 @@ int build_tables(tqgpu_solver *s) {
     s->sum_A = s->aoff[Nn]; s->sum_B = s->boff[Nn]; s->sum_W = s->woff[Nn]; s->sum_Ut = s->utoff[Nn];
 
     /* LDS budgets of the wave-per-block kernels */
-    s->lds_stage = s->lds_hess = s->lds_factor = s->lds_forward = 0;
+    s->pp.lds_stage = s->pp.lds_hess = s->pp.lds_factor = s->pp.lds_forward = 0;
     for (int k = 0; k < Nn; k++) {
         const size_t d = s->bdim[k], nz = s->nx[k] + s->nu[k];
-        s->lds_stage = std::max(s->lds_stage, (d + s->nx[k] + 2 * (s->nx[k] + s->nu[k]) + 2) * sizeof(double));
+        s->pp.lds_stage = std::max(s->pp.lds_stage, (d + s->nx[k] + 2 * (s->nx[k] + s->nu[k]) + 2) * sizeof(double));
         if (k < s->Np) {
-            s->lds_hess = std::max(s->lds_hess, (2 * d * nz + 2) * sizeof(double));
+            s->pp.lds_hess = std::max(s->pp.lds_hess, (2 * d * nz + 2) * sizeof(double));
             const size_t R = d + 1 + (k > 0 ? s->nx[k] : 0), ld = R | 1;
-            s->lds_factor = std::max(s->lds_factor, (ld * d + d + 2) * sizeof(double));
-            s->lds_forward = std::max(s->lds_forward, ((d | 1) * d + 2 * d + s->nx[k] + 2) * sizeof(double));
+            s->pp.lds_factor = std::max(s->pp.lds_factor, (ld * d + d + 2) * sizeof(double));
+            s->pp.lds_forward = std::max(s->pp.lds_forward, ((d | 1) * d + 2 * d + s->nx[k] + 2) * sizeof(double));
         }
     }
     {
@@ -2246,23 +1864,23 @@ int build_tables(tqgpu_solver *s) {
         for (int k = 0; k < s->Np; k++) {
             const int d = s->bdim[k], nxi = k > 0 ? s->nx[k] : 0, nz = s->nx[k] + s->nu[k];
             dmax = std::max(dmax, d); rmax = std::max(rmax, wide_rows(d, nxi)); nzmax = std::max(nzmax, nz);
-            s->lds_hess_w = std::max(s->lds_hess_w, wide_lds_hess(d, nz));
-            s->lds_factor_w = std::max(s->lds_factor_w, wide_lds_factor(d, nxi));
-            s->lds_forward_w = std::max(s->lds_forward_w, wide_lds_forward(d));
+            s->pp.lds_hess_w = std::max(s->pp.lds_hess_w, wide_lds_hess(d, nz));
+            s->pp.lds_factor_w = std::max(s->pp.lds_factor_w, wide_lds_factor(d, nxi));
+            s->pp.lds_forward_w = std::max(s->pp.lds_forward_w, wide_lds_forward(d));
         }
-        s->wide_small = false;
-        s->wide = dmax > 16 && dmax <= 64 && rmax <= 128 && nzmax <= 32;      /* k_hess_w keeps a parent's entries of P for 8 k-steps of 4 in registers */
+        s->pp.wide_small = false;
+        s->pp.wide = dmax > 16 && dmax <= 64 && rmax <= 128 && nzmax <= 32;      /* k_hess_w keeps a parent's entries of P for 8 k-steps of 4 in registers */
         /* Trees of SMALL blocks (d <= 16) that are too wide for the single-workgroup kernel (a level of more than 6 x 16 blocks) take the
          * workgroup-per-block kernels as well: three launches per Newton iteration instead of the five to eight of the launch-per-phase
          * kernels (TREEQP_AMD_SMALL_WIDE=0: as before) */
         {
             int widest = 0;
             for (int l = 0; l + 1 < (int)s->lvl_first.size(); l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
-            if (!s->wide && dmax >= 3 && dmax <= 16 && widest > 6 * 16 && rmax <= 128 && nzmax <= 32 && s->sw.small_wide) s->wide = s->wide_small = true;
+            if (!s->pp.wide && dmax >= 3 && dmax <= 16 && widest > 6 * 16 && rmax <= 128 && nzmax <= 32 && s->sw.small_wide) s->pp.wide = s->pp.wide_small = true;
         }
     }
     const size_t lim = 160 * 1024;
-    if (s->lds_factor > lim || s->lds_hess > lim || s->lds_forward > lim)
+    if (s->pp.lds_factor > lim || s->pp.lds_hess > lim || s->pp.lds_forward > lim)
         return fail(TQGPU_EUNSUPPORTED, "dual Hessian block too large for the LDS-resident kernels (160 KiB per workgroup)");
     return TQGPU_OK;
 }
@@ -2313,13 +1931,13 @@ std::vector<UniTier> uni_tiers(int top, int TH, int MD) {
     return out;
 }
 void add_tier(tqgpu_solver *s, int l0, int l1, int grid, int chain) {
-    s->tier_l0.push_back(l0); s->tier_l1.push_back(l1); s->tier_grid.push_back(grid); s->tier_chain.push_back(chain);
+    s->uni.tier_l0.push_back(l0); s->uni.tier_l1.push_back(l1); s->uni.tier_grid.push_back(grid); s->uni.tier_chain.push_back(chain);
 }
 
 /* multistage tree?  (setup_multistage_tree(md, Nr, Nh) with 1 <= Nr < Nh: every node above stage Nr has md
  * children, every parent from stage Nr on has one; uniform nx, nu) */
 void detect_multistage(tqgpu_solver *s) {
-    s->mstage = false;
+    s->uni.mstage = false;
     const int Nn = s->Nn, NX = s->nx[0], NU = s->nu[0], MD = s->nk[0], Nh = s->Nh;
     if (Nh < 2 || MD < 2 || NX % 4 != 0) return;
     int Nr = 0;
@@ -2341,11 +1959,11 @@ void detect_multistage(tqgpu_solver *s) {
 #undef X
     if (idx < 0) return;
     const int S = uni_width(MD, Nr);
-    s->fast = idx; s->fNX = NX; s->fNU = NU; s->fMD = MD;
-    s->mstage = true; s->ms_Nr = Nr; s->ms_S = S; s->ms_nB = s->lvl_first[Nr];
+    s->uni.fast = idx; s->uni.fNX = NX; s->uni.fNU = NU; s->uni.fMD = MD;
+    s->uni.mstage = true; s->uni.ms_Nr = Nr; s->uni.ms_S = S; s->uni.ms_nB = s->lvl_first[Nr];
     int TH = 1;
-    fast_geometry(idx, TH, s->lds_fast, s->lds_fstage);
-    s->tier_l0.clear(); s->tier_l1.clear(); s->tier_grid.clear(); s->tier_chain.clear();
+    fast_geometry(idx, TH, s->uni.lds_fast, s->uni.lds_fstage);
+    s->uni.tier_l0.clear(); s->uni.tier_l1.clear(); s->uni.tier_grid.clear(); s->uni.tier_chain.clear();
     /* chain part bottom-up in tiers of at most 8 levels (Uni<..., 1>::TH), then the branching part in tiers of TH levels */
     for (int l1 = Nh; l1 > Nr;) {
         const int l0 = std::max(Nr, l1 - 8);
@@ -2353,12 +1971,12 @@ void detect_multistage(tqgpu_solver *s) {
         l1 = l0;
     }
     for (const UniTier &t : uni_tiers(Nr, TH, MD)) add_tier(s, t.l0, t.l1, t.grid, 0);
-    s->n_tiers = (int)s->tier_l0.size();
+    s->uni.n_tiers = (int)s->uni.tier_l0.size();
 }
 
 /* uniform complete tree? (every node nx, every parent nu + md children, one leaf depth) */
 void detect_fast(tqgpu_solver *s) {
-    s->fast = -1;
+    s->uni.fast = -1;
     const int Nn = s->Nn, NX = s->nx[0], NU = s->nu[0], MD = s->nk[0];
     if (s->Nh < 2 || MD < 2) return;
     for (int k = 0; k < Nn; k++) {
@@ -2368,12 +1986,12 @@ void detect_fast(tqgpu_solver *s) {
     }
     const int idx = fast_index(NX, NU, MD);
     if (idx < 0) return;
-    s->fast = idx; s->fNX = NX; s->fNU = NU; s->fMD = MD;
+    s->uni.fast = idx; s->uni.fNX = NX; s->uni.fNU = NU; s->uni.fMD = MD;
     int TH = 1;
-    fast_geometry(idx, TH, s->lds_fast, s->lds_fstage);
-    s->tier_l0.clear(); s->tier_l1.clear(); s->tier_grid.clear(); s->tier_chain.clear();
+    fast_geometry(idx, TH, s->uni.lds_fast, s->uni.lds_fstage);
+    s->uni.tier_l0.clear(); s->uni.tier_l1.clear(); s->uni.tier_grid.clear(); s->uni.tier_chain.clear();
     for (const UniTier &t : uni_tiers(s->Nh, TH, MD)) add_tier(s, t.l0, t.l1, t.grid, 0);
-    s->n_tiers = (int)s->tier_l0.size();
+    s->uni.n_tiers = (int)s->uni.tier_l0.size();
 }
 
 /* the sharded modes' part in the launches per tier and in tqgpu_destroy (tdunes_shard.hpp) */
@@ -2384,36 +2002,36 @@ Shard shard_desc(const tqgpu_solver *s, int tier); int shard_exchange(tqgpu_solv
 void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &launches) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     const dim3 blk(FW * WAVE);
-    const int nt = s->n_tiers, N = s->shard.nranks;
+    const int nt = s->uni.n_tiers, N = s->shard.nranks;
     const bool sharded = s->shard.on;
     const int P = sharded ? s->shard.part_top : -1;
-    auto tgrid = [&](int i) { return (sharded && i <= P) ? s->tier_grid[i] / N : s->tier_grid[i]; };
+    auto tgrid = [&](int i) { return (sharded && i <= P) ? s->uni.tier_grid[i] / N : s->uni.tier_grid[i]; };
     /* which kernel runs first / performs the termination test */
     const int check_tier = sharded ? P + 1 : 1;          /* index in 0..nt-1 (nt-1 = top) */
-    const int nparts = sharded ? N : (nt > 1 ? s->tier_grid[0] : FW);
+    const int nparts = sharded ? N : (nt > 1 ? s->uni.tier_grid[0] : FW);
     const int n_stage = sharded ? s->shard.n_nodes : T.Nn;
-    switch (s->fast) {
+    switch (s->uni.fast) {
 #define X(idx, nx, nu, md)                                                                                                   \
     case idx:                                                                                                                \
         if (phase == 0) {                                                                                                    \
             for (int i = 0; i < nt - 1 && (!sharded || i <= P); i++) {                                                       \
-                hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->lds_fast, st, T, D, O, shard_desc(s, i),    \
-                                   s->tier_l0[i], s->tier_l1[i], i == 0, !sharded && i == check_tier, nparts, i, h); launches++; \
+                hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),    \
+                                   s->uni.tier_l0[i], s->uni.tier_l1[i], i == 0, !sharded && i == check_tier, nparts, i, h); launches++; \
             }                                                                                                                \
             if (sharded) { hipLaunchKernelGGL(k_shard_pack1, dim3(1), dim3(256), 0, st, D, tgrid(0), s->shard.d_xerr, s->shard.rank, O.termCondition, h); launches++; } \
         }                                                                                                                    \
         if (phase == 1) {                                                                                                    \
             for (int i = (sharded ? P + 1 : nt - 1); i < nt - 1; i++) {                                                      \
-                hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->lds_fast, st, T, D, O, shard_desc(s, i),    \
-                                   s->tier_l0[i], s->tier_l1[i], 0, i == check_tier, nparts, i, h); launches++;              \
+                hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),    \
+                                   s->uni.tier_l0[i], s->uni.tier_l1[i], 0, i == check_tier, nparts, i, h); launches++;              \
             }                                                                                                                \
-            hipLaunchKernelGGL((f_top<nx, nu, md>), dim3(1), blk, s->lds_fast, st, T, D, O, shard_desc(s, nt - 1),           \
-                               s->tier_l1[nt - 1], nt == 1, (nt - 1) == check_tier, nparts, nt - 1, h); launches++;          \
+            hipLaunchKernelGGL((f_top<nx, nu, md>), dim3(1), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, nt - 1),           \
+                               s->uni.tier_l1[nt - 1], nt == 1, (nt - 1) == check_tier, nparts, nt - 1, h); launches++;          \
             for (int i = nt - 2; i >= 0; i--) {                                                                              \
-                hipLaunchKernelGGL((f_fwd<nx, nu, md>), dim3(tgrid(i)), blk, s->lds_fast, st, T, D, O, shard_desc(s, i),     \
-                                   s->tier_l0[i], s->tier_l1[i], nt + (nt - 2 - i), h); launches++;                          \
+                hipLaunchKernelGGL((f_fwd<nx, nu, md>), dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),     \
+                                   s->uni.tier_l0[i], s->uni.tier_l1[i], nt + (nt - 2 - i), h); launches++;                          \
             }                                                                                                                \
-            hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), blk, s->lds_fstage, st, T, D, O,        \
+            hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), blk, s->uni.lds_fstage, st, T, D, O,        \
                                sharded ? s->shard.d_node_list : nullptr, n_stage, 2 * nt - 1, h, 1); launches++;                   \
             if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->shard.d_node_cnt_list, s->shard.n_nodes_counted, \
                                               s->shard.d_blk_list, s->shard.n_blk_counted, s->shard.d_xs, s->shard.rank, s->shard.bnd_b0, s->shard.bnd_bn, s->shard.bnd_own0, s->shard.bnd_ownn, h, 1); launches++; } \
@@ -2443,16 +2061,16 @@ int launch_fast_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches) 
 /* the next tag of a family of tagged words: counts up and skips 0, the value of a word never written */
 static unsigned next_tag(unsigned &epoch) { if (++epoch == 0) epoch = 1; return epoch; }
 static Fuse next_fuse(tqgpu_solver *s) {
-    Fuse F; F.red = s->fuse_red; F.cnt = s->fuse_cnt; F.on = 1;
-    F.tag = next_tag(s->fuse_epoch);
+    Fuse F; F.red = s->pp.fuse_red; F.cnt = s->pp.fuse_cnt; F.on = 1;
+    F.tag = next_tag(s->pp.fuse_epoch);
     return F;
 }
 static Fuse no_fuse() { Fuse F; F.red = nullptr; F.cnt = nullptr; F.tag = 0; F.on = 0; return F; }
 static W3 next_w3(tqgpu_solver *s) {
-    W3 w; w.xu = s->w3_xu; w.red = s->w3_red; w.cnt = s->w3_cnt; w.sum_nx = s->sum_nx; w.lds_wave = (int)((s->lds_stage + 7) / 8);
+    W3 w; w.xu = s->w3.xu; w.red = s->w3.red; w.cnt = s->w3.cnt; w.sum_nx = s->sum_nx; w.lds_wave = (int)((s->pp.lds_stage + 7) / 8);
     w.hm = nullptr;
-    s->w3_tail_sg = false;
-    w.tag = next_tag(s->w3_epoch);
+    s->w3.tail_sg = false;
+    w.tag = next_tag(s->w3.epoch);
     return w;
 }
 /* one stage sweep of the launch-per-phase route, by the stage solver the tree's nodes need (general constraints / box bounds / clipping
@@ -2461,21 +2079,21 @@ static void launch_stage_sweep(tqgpu_solver *s, int mode, int h, int t) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     if (s->sk.gen) hipLaunchKernelGGL(k_stage_gen, dim3(T.Nn), dim3(WAVE), s->sk.lds_gen, st, T, D, mode, h, t);
     else if (s->sk.box) hipLaunchKernelGGL(k_stage_box, dim3(T.Nn), dim3(WAVE), s->sk.lds_box, st, T, D, mode, h, t);
-    else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, mode, h, t);
+    else hipLaunchKernelGGL(k_stage, dim3(T.Nn), dim3(WAVE), s->pp.lds_stage, st, T, D, mode, h, t);
 }
 static void launch_sg(tqgpu_solver *s, const Opts &O, int mode, int h, int t, bool fresh = false) {
     W3 w = next_w3(s);
     /* (a post is ~14 system-scope stores to host memory and the wait for their acknowledgements, on the launch's critical path: only
      * where the host is going to look) */
-    if (s->w3_mirror && s->w3_post_next) { w.hm = s->h_res; s->w3_wait = w.tag; s->w3_tail_sg = true; }
-    s->w3_post_next = false;
-    if (s->w3_sgp) {
-        if (mode == 2) { SgpFwdYes fa; fa.anc = s->d_anc; fa.pdw = s->d_pdw; hipLaunchKernelGGL(k_sgp_t<true>, dim3(s->T.Np), dim3(WT), s->lds_sgp, s->stream, s->T, s->D, O, w, mode, h, t, s->sgp_accs, (const double *)nullptr, fa); }
-        else hipLaunchKernelGGL(k_sgp_t<false>, dim3(s->T.Np), dim3(WT), s->lds_sgp, s->stream, s->T, s->D, O, w, mode, h, t, s->sgp_accs, fresh ? (const double *)s->d_lam_init : (const double *)nullptr, SgpFwdNo());
+    if (s->w3.mirror && s->w3.post_next) { w.hm = s->h_res; s->w3.wait = w.tag; s->w3.tail_sg = true; }
+    s->w3.post_next = false;
+    if (s->w3.sgp) {
+        if (mode == 2) { SgpFwdYes fa; fa.anc = s->w3.d_anc; fa.pdw = s->w3.d_pdw; hipLaunchKernelGGL(k_sgp_t<true>, dim3(s->T.Np), dim3(WT), s->w3.lds_sgp, s->stream, s->T, s->D, O, w, mode, h, t, s->w3.sgp_accs, (const double *)nullptr, fa); }
+        else hipLaunchKernelGGL(k_sgp_t<false>, dim3(s->T.Np), dim3(WT), s->w3.lds_sgp, s->stream, s->T, s->D, O, w, mode, h, t, s->w3.sgp_accs, fresh ? (const double *)s->d_lam_init : (const double *)nullptr, SgpFwdNo());
         return;
     }
     const int grid = (s->T.Nn + SG_WAVES - 1) / SG_WAVES;
-    hipLaunchKernelGGL(k_sg, dim3(grid), dim3(SG_WAVES * WAVE), SG_WAVES * ((s->lds_stage + 7) / 8) * 8, s->stream, s->T, s->D, O, w, mode, h, t);
+    hipLaunchKernelGGL(k_sg, dim3(grid), dim3(SG_WAVES * WAVE), SG_WAVES * ((s->pp.lds_stage + 7) / 8) * 8, s->stream, s->T, s->D, O, w, mode, h, t);
 }
 
 void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, int phase, int &launches) {
@@ -2485,8 +2103,8 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
         bool done = false;
         if (r == Route::TIERED) {
             const int n_stage = sharded ? s->shard.n_nodes : T.Nn;
-            switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->lds_fstage, st, T, D, O, sharded ? s->shard.d_node_list : nullptr, n_stage, 7, it, t); done = true; break;
+            switch (s->uni.fast) {
+#define X(idx, nx, nu, md) case idx: hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->uni.lds_fstage, st, T, D, O, sharded ? s->shard.d_node_list : nullptr, n_stage, 7, it, t); done = true; break;
                 FAST_TABLE(X)
 #undef X
                 default: break;
@@ -2494,7 +2112,7 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
         }
         if (!done && r == Route::THREE_LAUNCH) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
         if (!done) {
-            if (r == Route::FUSED_TAILS) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
+            if (r == Route::FUSED_TAILS) hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->pp.lds_stage, st, T, D, O, next_fuse(s), 1, it, t);      /* with k_ls_decide as its tail */
             else launch_stage_sweep(s, 1, it, t);
         }
         launches++;
@@ -2532,37 +2150,37 @@ static const ProcessSwitches &process_switches() {
 /* poll naps by launch size (PollGuard::go_on) */
 static int nap_for_grid(int workgroups) { return workgroups > process_switches().nap_t1 ? 1 : 0; }
 int setup_persist(tqgpu_solver *s) {
-    s->persist_ok = false;
-    if (s->fast < 0 || s->n_tiers > 8) return TQGPU_OK;
-    PGeom &G = s->geom;
-    G.n_tiers = s->n_tiers;
+    s->persist.ok = false;
+    if (s->uni.fast < 0 || s->uni.n_tiers > 8) return TQGPU_OK;
+    PGeom &G = s->persist.geom;
+    G.n_tiers = s->uni.n_tiers;
     int wg = 0;
-    for (int i = 0; i < s->n_tiers; i++) { G.l0[i] = s->tier_l0[i]; G.l1[i] = s->tier_l1[i]; G.grid[i] = s->tier_grid[i]; G.chain[i] = s->tier_chain[i]; G.wg0[i] = wg; wg += s->tier_grid[i]; }
+    for (int i = 0; i < s->uni.n_tiers; i++) { G.l0[i] = s->uni.tier_l0[i]; G.l1[i] = s->uni.tier_l1[i]; G.grid[i] = s->uni.tier_grid[i]; G.chain[i] = s->uni.tier_chain[i]; G.wg0[i] = wg; wg += s->uni.tier_grid[i]; }
     G.G = wg;
     int per_cu = 0, per_cu_r = 1 << 20, per_cu_one = 0;      /* _r: the variant that can keep factors (checkLastActiveSet == 2); _one: the build for one workgroup per CU */
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-    if (!s->mstage) {
-        switch (s->fast) {
+    if (!s->uni.mstage) {
+        switch (s->uni.fast) {
 #define X(idx, nx, nu, md)                                                                                                   \
     case idx:                                                                                                                \
-        s->lds_persist = PLds<nx, nu, md>::DOUBLES * sizeof(double);                                                         \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->lds_persist)); \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, f_persist<nx, nu, md, true>, FW * WAVE, s->lds_persist)); \
-        if (allow_lds(f_persist_one<nx, nu, md>, s->lds_persist) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, f_persist_one<nx, nu, md>, FW * WAVE, s->lds_persist) != hipSuccess) per_cu_one = 0; \
+        s->persist.lds = PLds<nx, nu, md>::DOUBLES * sizeof(double);                                                         \
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->persist.lds)); \
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, f_persist<nx, nu, md, true>, FW * WAVE, s->persist.lds)); \
+        if (allow_lds(f_persist_one<nx, nu, md>, s->persist.lds) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, f_persist_one<nx, nu, md>, FW * WAVE, s->persist.lds) != hipSuccess) per_cu_one = 0; \
         break;
             FAST_TABLE(X)
 #undef X
             default: break;
         }
     } else {
-        switch (s->fast) {
+        switch (s->uni.fast) {
 #define X(idx, nx, nu, md)                                                                                                   \
     case idx:                                                                                                                \
-        s->lds_persist = std::max(PLds<nx, nu, md>::DOUBLES, PLds<nx, nu, 1>::DOUBLES) * sizeof(double);                     \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_mpersist<nx, nu, md, false>, FW * WAVE, s->lds_persist)); \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, f_mpersist<nx, nu, md, true>, FW * WAVE, s->lds_persist)); \
-        if (allow_lds(f_mpersist_one<nx, nu, md>, s->lds_persist) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, f_mpersist_one<nx, nu, md>, FW * WAVE, s->lds_persist) != hipSuccess) per_cu_one = 0; \
+        s->persist.lds = std::max(PLds<nx, nu, md>::DOUBLES, PLds<nx, nu, 1>::DOUBLES) * sizeof(double);                     \
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_mpersist<nx, nu, md, false>, FW * WAVE, s->persist.lds)); \
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, f_mpersist<nx, nu, md, true>, FW * WAVE, s->persist.lds)); \
+        if (allow_lds(f_mpersist_one<nx, nu, md>, s->persist.lds) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, f_mpersist_one<nx, nu, md>, FW * WAVE, s->persist.lds) != hipSuccess) per_cu_one = 0; \
         break;
             MSTAGE_TABLE(X)
 #undef X
@@ -2570,9 +2188,9 @@ int setup_persist(tqgpu_solver *s) {
         }
     }
     if (s->sw.has_lds_pad) {      /* experiment: force fewer workgroups per CU */
-        s->lds_persist += (size_t)s->sw.lds_pad * 1024;
-        switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: if (!s->mstage) { allow_lds(f_persist<nx, nu, md, false>, s->lds_persist); HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->lds_persist)); } break;
+        s->persist.lds += (size_t)s->sw.lds_pad * 1024;
+        switch (s->uni.fast) {
+#define X(idx, nx, nu, md) case idx: if (!s->uni.mstage) { allow_lds(f_persist<nx, nu, md, false>, s->persist.lds); HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->persist.lds)); } break;
             FAST_TABLE(X)
 #undef X
             default: break;
@@ -2589,10 +2207,10 @@ int setup_persist(tqgpu_solver *s) {
     const int margin = s->sw.capacity_margin;      /* experiment */
     const int capacity = per_cu <= 1 ? prop.multiProcessorCount * per_cu : prop.multiProcessorCount * per_cu - margin;
     if (s->sw.verbose) fprintf(stderr, "[treeqp_amd] persistent path: %d workgroups, %d per CU possible, capacity %d\n", G.G, per_cu, capacity);
-    s->co_capacity = std::max(1, capacity);
+    s->persist.co_capacity = std::max(1, capacity);
     s->n_cu = prop.multiProcessorCount;
     /* the build for ONE workgroup per CU (f_persist_one: more registers, 2 % faster) when the launch fits the device that way */
-    s->persist_one = per_cu_one >= 1 && G.G <= prop.multiProcessorCount * std::min(per_cu_one, 1) && !s->sw.no_persist_one;
+    s->persist.one = per_cu_one >= 1 && G.G <= prop.multiProcessorCount * std::min(per_cu_one, 1) && !s->sw.no_persist_one;
     if (per_cu < 1 || G.G > capacity) return TQGPU_OK;
     /* hand-over buffers (tagged 64-bit words, see tdunes_persist.hpp); zeroed once, never reset */
     const int nx0 = s->nx[0];
@@ -2601,39 +2219,39 @@ int setup_persist(tqgpu_solver *s) {
     const size_t n_bparts = (size_t)G.G * 16;
     const size_t n_sgt = (size_t)s->Nn * 2, n_rfl = (size_t)s->Nn * 2;      /* active-set signature / reuse flag of a tier subtree root (one tagged double each) */
     const size_t n_verdict = 16;
-    const size_t n_anc = (size_t)s->Np * (size_t)(nx0 * s->fMD) * (nx0 + 1) * 2;      /* forward records [z0 | M] of the blocks, for the bottom tier's walk down its path (tdunes_persist.hpp, p_forward_tier) */
+    const size_t n_anc = (size_t)s->Np * (size_t)(nx0 * s->uni.fMD) * (nx0 + 1) * 2;      /* forward records [z0 | M] of the blocks, for the bottom tier's walk down its path (tdunes_persist.hpp, p_forward_tier) */
     const size_t bytes = (n_sch + n_dlt + n_ndt + n_parts + n_errs + 32 + n_bparts + n_sgt + n_rfl + n_verdict + n_anc) * sizeof(unsigned long long);
-    if (int rc = s->mem.zeroed(s->sync_slab, bytes, TQGPU_ENODEVICE, "the hand-over slab")) return rc;
+    if (int rc = s->mem.zeroed(s->persist.sync_slab, bytes, TQGPU_ENODEVICE, "the hand-over slab")) return rc;
     HIP_TRY(hipDeviceSynchronize());          /* (a device memset may return before it has happened, and the solver's non-blocking stream does not wait for the null stream) */
-    s->sync_bytes = bytes;
-    unsigned long long *w = static_cast<unsigned long long *>(s->sync_slab);
-    s->psync.sch = w; s->psync.dlt = w + n_sch; s->psync.ndt = s->psync.dlt + n_dlt; s->psync.parts = s->psync.ndt + n_ndt;
-    s->psync.errs = s->psync.parts + n_parts;
-    s->psync.halt = reinterpret_cast<unsigned *>(s->psync.errs + n_errs);
-    s->psync.timeout = s->psync.halt + 32;
-    s->psync.cmd = s->psync.errs + n_errs + 24;          /* same 256-byte block: halt | timeout | cmd | vrd */
-    s->psync.vrd = s->psync.errs + n_errs + 28;
-    s->psync.bparts = s->psync.errs + n_errs + 32;
-    s->psync.sgt = s->psync.bparts + n_bparts; s->psync.rfl = s->psync.sgt + n_sgt;
-    s->psync.verdict = s->psync.rfl + n_rfl;
-    s->psync.anc = s->psync.verdict + n_verdict;
-    s->psync.base = w; s->psync.npeer = 1; s->psync.relay_wg = -1; s->psync.anc_local = 1;
+    s->persist.sync_bytes = bytes;
+    unsigned long long *w = static_cast<unsigned long long *>(s->persist.sync_slab);
+    s->persist.psync.sch = w; s->persist.psync.dlt = w + n_sch; s->persist.psync.ndt = s->persist.psync.dlt + n_dlt; s->persist.psync.parts = s->persist.psync.ndt + n_ndt;
+    s->persist.psync.errs = s->persist.psync.parts + n_parts;
+    s->persist.psync.halt = reinterpret_cast<unsigned *>(s->persist.psync.errs + n_errs);
+    s->persist.psync.timeout = s->persist.psync.halt + 32;
+    s->persist.psync.cmd = s->persist.psync.errs + n_errs + 24;          /* same 256-byte block: halt | timeout | cmd | vrd */
+    s->persist.psync.vrd = s->persist.psync.errs + n_errs + 28;
+    s->persist.psync.bparts = s->persist.psync.errs + n_errs + 32;
+    s->persist.psync.sgt = s->persist.psync.bparts + n_bparts; s->persist.psync.rfl = s->persist.psync.sgt + n_sgt;
+    s->persist.psync.verdict = s->persist.psync.rfl + n_rfl;
+    s->persist.psync.anc = s->persist.psync.verdict + n_verdict;
+    s->persist.psync.base = w; s->persist.psync.npeer = 1; s->persist.psync.relay_wg = -1; s->persist.psync.anc_local = 1;
     for (int r = 0; r < 8; r++) s->pshard.h_peers[r] = w;
     if (int rc = s->mem.upload(s->pshard.d_peers, s->pshard.h_peers, sizeof(s->pshard.h_peers), TQGPU_ENODEVICE, "the table of peer slabs")) return rc;
-    s->psync.peers = s->pshard.d_peers;
-    s->psync.seq = 0; s->psync.trip = 0;
-    s->psync.nap = s->sw.has_nap ? s->sw.nap : nap_for_grid(G.G);
+    s->persist.psync.peers = s->pshard.d_peers;
+    s->persist.psync.seq = 0; s->persist.psync.trip = 0;
+    s->persist.psync.nap = s->sw.has_nap ? s->sw.nap : nap_for_grid(G.G);
     /* XCD-aware placement: the hardware deals workgroups round-robin over the 8 XCDs (workgroup b -> XCD b % 8)
      * and every XCD has its own L2.  A tier subtree talks to its parent and its children only, so whole
      * families go to one XCD: each subtree of the lowest tier with at most 8 subtrees picks an XCD, everything
      * below follows its ancestor there; the tiers above (one workgroup each, typically) take what is left. */
     {
         const int NXCD = 8, Gn = G.G;
-        int anchor = s->n_tiers - 1;
-        for (int i = 0; i < s->n_tiers; i++) if (G.grid[i] <= NXCD) { anchor = i; break; }
+        int anchor = s->uni.n_tiers - 1;
+        for (int i = 0; i < s->uni.n_tiers; i++) if (G.grid[i] <= NXCD) { anchor = i; break; }
         std::vector<std::vector<int>> want(NXCD);
         std::vector<int> rest;
-        for (int i = 0; i < s->n_tiers; i++)
+        for (int i = 0; i < s->uni.n_tiers; i++)
             for (int q = 0; q < G.grid[i]; q++) {
                 const int id = G.wg0[i] + q;
                 if (i <= anchor) want[(int)((long long)q * G.grid[anchor] / G.grid[i]) % NXCD].push_back(id);   /* subtree q of tier i sits under subtree q*grid[anchor]/grid[i] */
@@ -2649,15 +2267,15 @@ int setup_persist(tqgpu_solver *s) {
          * the UPPER tiers -- they work while the bottom tier waits and vice versa -- instead of two bottom-tier subtrees
          * halving each other on the critical path: plain tier order (bottom tier first). */
         if (Gn > prop.multiProcessorCount) for (int b = 0; b < Gn; b++) map[b] = b;
-        if (int rc = s->mem.upload(s->wg_map, map.data(), sizeof(int) * (size_t)Gn, TQGPU_ENODEVICE, "the workgroup placement")) return rc;
-        G.wg_of_block = s->wg_map;
+        if (int rc = s->mem.upload(s->persist.wg_map, map.data(), sizeof(int) * (size_t)Gn, TQGPU_ENODEVICE, "the workgroup placement")) return rc;
+        G.wg_of_block = s->persist.wg_map;
     }
     /* packed constants + the start/end view of the mirror */
     const int nz = nx0 + s->nu[0];
     const size_t n_ab = (size_t)(s->Nn - 1) * nx0 * nz, n_cst = (size_t)s->Nn * 16 * 5;
-    if (int rc = s->mem.device(s->pconst_slab, (n_ab + n_cst) * sizeof(double) + sizeof(PDump) + 256, TQGPU_ENODEVICE, "the packed constants")) return rc;
-    double *pc = static_cast<double *>(s->pconst_slab);
-    s->pab = pc; s->pcst = pc + n_ab;
+    if (int rc = s->mem.device(s->persist.pconst_slab, (n_ab + n_cst) * sizeof(double) + sizeof(PDump) + 256, TQGPU_ENODEVICE, "the packed constants")) return rc;
+    double *pc = static_cast<double *>(s->persist.pconst_slab);
+    s->persist.pab = pc; s->persist.pcst = pc + n_ab;
     PDump hd;
     const Data &D = s->D;
     hd.x = D.x; hd.u = D.u; hd.xUnc = D.xUnc; hd.uUnc = D.uUnc; hd.xUncS = D.xUncS; hd.uUncS = D.uUncS; hd.qmod = D.qmod; hd.rmod = D.rmod; hd.QinvCal = D.QinvCal; hd.RinvCal = D.RinvCal;
@@ -2665,10 +2283,10 @@ int setup_persist(tqgpu_solver *s) {
     hd.hres = s->h_res;
     PDump *dd = reinterpret_cast<PDump *>(pc + n_ab + n_cst);
     HIP_TRY(hipMemcpy(dd, &hd, sizeof(PDump), hipMemcpyHostToDevice));
-    s->pconst.AB = s->pab; s->pconst.b = D.b; s->pconst.cst = s->pcst; s->pconst.ctrl = D.ctrl; s->pconst.dump = dd; s->pconst.lam0_src = s->d_lam_init; s->pconst.Np = s->Np;
-    s->pconst.S = s->mstage ? s->ms_S : 0; s->pconst.nB = s->mstage ? s->ms_nB : s->Np; s->pconst.Nr = s->mstage ? s->ms_Nr : s->Nh;
-    s->need_pack = true;
-    s->persist_ok = true;
+    s->persist.pconst.AB = s->persist.pab; s->persist.pconst.b = D.b; s->persist.pconst.cst = s->persist.pcst; s->persist.pconst.ctrl = D.ctrl; s->persist.pconst.dump = dd; s->persist.pconst.lam0_src = s->d_lam_init; s->persist.pconst.Np = s->Np;
+    s->persist.pconst.S = s->uni.mstage ? s->uni.ms_S : 0; s->persist.pconst.nB = s->uni.mstage ? s->uni.ms_nB : s->Np; s->persist.pconst.Nr = s->uni.mstage ? s->uni.ms_Nr : s->Nh;
+    s->persist.need_pack = true;
+    s->persist.ok = true;
     return TQGPU_OK;
 }
 
@@ -2678,35 +2296,35 @@ int setup_persist(tqgpu_solver *s) {
  * never 0.  launch_no_after: 0 when the number wraps; step_launch_no: takes the next number and says whether it wrapped */
 static unsigned launch_no_after(unsigned n) { return (n + 1) & 0xFFFFu; }
 static bool step_launch_no(tqgpu_solver *s) {
-    s->launch_no = launch_no_after(s->launch_no);
-    if (s->launch_no != 0) return false;
-    s->launch_no = 1;
+    s->persist.launch_no = launch_no_after(s->persist.launch_no);
+    if (s->persist.launch_no != 0) return false;
+    s->persist.launch_no = 1;
     return true;
 }
 
 int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, unsigned batch_seq = 0) {
     const Data &D = s->D; hipStream_t st = s->stream;
-    if (batch_seq) s->launch_no = batch_seq >> 16;          /* part of a batch launch: the caller chose the number (and wiped the buffers if it wrapped) */
+    if (batch_seq) s->persist.launch_no = batch_seq >> 16;          /* part of a batch launch: the caller chose the number (and wiped the buffers if it wrapped) */
     else if (step_launch_no(s)) {
         /* the 16-bit launch number wraps: words that are not rewritten by every launch (the line-search command / verdict /
          * batch partials) could still carry a tag of 65535 launches ago -- wipe the hand-over buffers (stream-ordered) */
-        HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, st));
+        HIP_TRY(hipMemsetAsync(s->persist.sync_slab, 0, s->persist.sync_bytes, st));
     }
-    s->psync.seq = s->launch_no << 16;
-    if (s->need_pack) {
+    s->persist.psync.seq = s->persist.launch_no << 16;
+    if (s->persist.need_pack) {
         const int n = std::max(s->Nn * 16, (s->Nn - 1) * s->nx[0] * (s->nx[0] + s->nu[0]));
-        hipLaunchKernelGGL(k_pack_persist, dim3((n + 255) / 256), dim3(256), 0, st, s->Nn, s->Np, s->nx[0], s->nu[0], D, s->pab, s->pcst); launches++;
-        s->need_pack = false;
-        s->stream_pending = true;
+        hipLaunchKernelGGL(k_pack_persist, dim3((n + 255) / 256), dim3(256), 0, st, s->Nn, s->Np, s->nx[0], s->nu[0], D, s->persist.pab, s->persist.pcst); launches++;
+        s->persist.need_pack = false;
+        s->links.stream_pending = true;
     }
     if (batch_seq) { launches++; return TQGPU_OK; }          /* the caller launches the batch */
     if (s->pshard.on) {
         /* this rank's share of the workgroups; the geometry (tiers, global workgroup numbers, G) is the whole tree's */
-        PGeom Gm = s->geom;
+        PGeom Gm = s->persist.geom;
         Gm.wg_of_block = s->pshard.wg_map;
-        switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: if (s->pshard.sys) hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 1>), dim3(s->pshard.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, Gm, s->psync, prologue); \
-                                    else hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 0>), dim3(s->pshard.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, Gm, s->psync, prologue); break;
+        switch (s->uni.fast) {
+#define X(idx, nx, nu, md) case idx: if (s->pshard.sys) hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 1>), dim3(s->pshard.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, Gm, s->persist.psync, prologue); \
+                                    else hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 0>), dim3(s->pshard.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, Gm, s->persist.psync, prologue); break;
             SHARD_TABLE(X)
 #undef X
             default: return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape");
@@ -2714,20 +2332,20 @@ int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, 
         launches++;
         return TQGPU_OK;
     }
-    if (!s->mstage) {
-        switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: if (O.reuse) hipLaunchKernelGGL((f_persist<nx, nu, md, true>), dim3(s->geom.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, s->geom, s->psync, prologue); \
-                                    else if (s->persist_one && !s->in_batch) hipLaunchKernelGGL((f_persist_one<nx, nu, md>), dim3(s->geom.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, s->geom, s->psync, prologue); \
-                                    else hipLaunchKernelGGL((f_persist<nx, nu, md, false>), dim3(s->geom.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, s->geom, s->psync, prologue); break;
+    if (!s->uni.mstage) {
+        switch (s->uni.fast) {
+#define X(idx, nx, nu, md) case idx: if (O.reuse) hipLaunchKernelGGL((f_persist<nx, nu, md, true>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
+                                    else if (s->persist.one && !s->links.in_batch) hipLaunchKernelGGL((f_persist_one<nx, nu, md>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
+                                    else hipLaunchKernelGGL((f_persist<nx, nu, md, false>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); break;
             FAST_TABLE(X)
 #undef X
             default: break;
         }
     } else {
-        switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: if (O.reuse) hipLaunchKernelGGL((f_mpersist<nx, nu, md, true>), dim3(s->geom.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, s->geom, s->psync, prologue); \
-                                    else if (s->persist_one && !s->in_batch) hipLaunchKernelGGL((f_mpersist_one<nx, nu, md>), dim3(s->geom.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, s->geom, s->psync, prologue); \
-                                    else hipLaunchKernelGGL((f_mpersist<nx, nu, md, false>), dim3(s->geom.G), dim3(FW * WAVE), s->lds_persist, st, s->pconst, O, s->geom, s->psync, prologue); break;
+        switch (s->uni.fast) {
+#define X(idx, nx, nu, md) case idx: if (O.reuse) hipLaunchKernelGGL((f_mpersist<nx, nu, md, true>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
+                                    else if (s->persist.one && !s->links.in_batch) hipLaunchKernelGGL((f_mpersist_one<nx, nu, md>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
+                                    else hipLaunchKernelGGL((f_mpersist<nx, nu, md, false>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); break;
             MSTAGE_TABLE(X)
 #undef X
             default: break;
@@ -2746,27 +2364,27 @@ void launch_w3_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, i
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     /* three launches: the termination test of this iteration was the tail of the previous launch of k_sg */
     if (!(parts & 2)) return;
-    const unsigned bw_tag = next_tag(s->bw_epoch);
-    s->w3_tail_sg = false;
-    hipLaunchKernelGGL(k_hf_w, dim3(T.Np), dim3(WT), s->lds_hf_w, st, T, D, O, s->sch_words, s->sch_rs, bw_tag, h); launches++;
-    const bool merged = T.Np > 1 && s->w3_merge;      /* forward sweep + first trial: one launch (k_sgp mode 2) */
+    const unsigned bw_tag = next_tag(s->pp.bw_epoch);
+    s->w3.tail_sg = false;
+    hipLaunchKernelGGL(k_hf_w, dim3(T.Np), dim3(WT), s->w3.lds_hf_w, st, T, D, O, s->pp.sch_words, s->pp.sch_rs, bw_tag, h); launches++;
+    const bool merged = T.Np > 1 && s->w3.merge;      /* forward sweep + first trial: one launch (k_sgp mode 2) */
     if (!merged && T.Np > 1) {
-        const unsigned fw_tag = next_tag(s->fw_epoch);
-        if (s->d_anc) hipLaunchKernelGGL(k_fwd3c, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->d_anc, h);
-        else hipLaunchKernelGGL(k_fwd3, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->fw_words, fw_tag, h);
+        const unsigned fw_tag = next_tag(s->pp.fw_epoch);
+        if (s->w3.d_anc) hipLaunchKernelGGL(k_fwd3c, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->w3.d_anc, h);
+        else hipLaunchKernelGGL(k_fwd3, dim3((T.Np - 1 + SG_WAVES - 1) / SG_WAVES), dim3(SG_WAVES * WAVE), 0, st, T, D, next_w3(s), s->pp.fw_words, fw_tag, h);
         launches++;
     } else if (!merged) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
     /* the first trial and the predicted trials 2 .. kpred; where this is the last iteration of the chunk that launches anything, the last of them posts */
-    const int kpred = h < (int)s->ls_pred.size() ? std::min(s->ls_pred[(size_t)h], O.lsMaxIter) : 1;
-    s->w3_post_next = last && kpred < 2;
+    const int kpred = h < (int)s->pp.ls_pred.size() ? std::min(s->pp.ls_pred[(size_t)h], O.lsMaxIter) : 1;
+    s->w3.post_next = last && kpred < 2;
     launch_sg(s, O, merged ? 2 : 1, h, 1); launches++;
-    for (int tt = 2; tt <= kpred; tt++) { s->w3_post_next = last && tt == kpred; launch_sg(s, O, 1, h, tt); launches++; }
+    for (int tt = 2; tt <= kpred; tt++) { s->w3.post_next = last && tt == kpred; launch_sg(s, O, 1, h, tt); launches++; }
 }
 
 /* the launch-per-phase kernels, with the reductions as launches of their own (PER_PHASE) or as the tails of their producers (FUSED_TAILS) */
 void launch_phase_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches, int parts, bool phases) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
-    auto mark = [&](int i) { if (phases && (size_t)(4 * h + i) < s->phase_ev.size()) (void)hipEventRecord(s->phase_ev[(size_t)(4 * h + i)], st); };
+    auto mark = [&](int i) { if (phases && (size_t)(4 * h + i) < s->tm.phase_ev.size()) (void)hipEventRecord(s->tm.phase_ev[(size_t)(4 * h + i)], st); };
     const bool fuse = s->route == Route::FUSED_TAILS;
     mark(0);
     if (parts & 1) {
@@ -2777,45 +2395,45 @@ void launch_phase_iteration(tqgpu_solver *s, const Opts &O, int h, int &launches
         }
     }
     if (!(parts & 2)) return;
-    const bool wide = s->wide && !s->sk.dense;
+    const bool wide = s->pp.wide && !s->sk.dense;
     bool ls_begun = false;           /* the forward sweep's last workgroup has done k_ls_begin's work */
-    if (wide) hipLaunchKernelGGL(k_hess_w, dim3(T.Np), dim3(WT), s->lds_hess_w, st, T, D, h);
-    else hipLaunchKernelGGL(k_hess, dim3(T.Np), dim3(WAVE), s->lds_hess, st, T, D, h);
+    if (wide) hipLaunchKernelGGL(k_hess_w, dim3(T.Np), dim3(WT), s->pp.lds_hess_w, st, T, D, h);
+    else hipLaunchKernelGGL(k_hess, dim3(T.Np), dim3(WAVE), s->pp.lds_hess, st, T, D, h);
     launches++;
     mark(1);
-    if (s->sch_words && s->bw_fused && !phases) {
+    if (s->pp.sch_words && s->pp.bw_fused && !phases) {
         /* all levels in one launch, last block first: a block waits for its children's Schur records inside the kernel */
-        const unsigned bw_tag = next_tag(s->bw_epoch);
-        if (wide) hipLaunchKernelGGL(k_factor_all_w, dim3(T.Np), dim3(WT), s->lds_factor_w, st, T, D, O, s->sch_words, s->sch_rs, bw_tag, h);
-        else hipLaunchKernelGGL(k_factor_all, dim3(T.Np), dim3(WAVE), s->lds_factor, st, T, D, O, s->sch_words, s->sch_rs, bw_tag, h);
+        const unsigned bw_tag = next_tag(s->pp.bw_epoch);
+        if (wide) hipLaunchKernelGGL(k_factor_all_w, dim3(T.Np), dim3(WT), s->pp.lds_factor_w, st, T, D, O, s->pp.sch_words, s->pp.sch_rs, bw_tag, h);
+        else hipLaunchKernelGGL(k_factor_all, dim3(T.Np), dim3(WAVE), s->pp.lds_factor, st, T, D, O, s->pp.sch_words, s->pp.sch_rs, bw_tag, h);
         launches++;
     } else
     for (int lvl = T.Nh - 1; lvl >= 0; lvl--) {
         const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        if (wide) hipLaunchKernelGGL(k_factor_w, dim3(count), dim3(WT), s->lds_factor_w, st, T, D, O, first, h);
-        else hipLaunchKernelGGL(k_factor, dim3(count), dim3(WAVE), s->lds_factor, st, T, D, O, first, h);
+        if (wide) hipLaunchKernelGGL(k_factor_w, dim3(count), dim3(WT), s->pp.lds_factor_w, st, T, D, O, first, h);
+        else hipLaunchKernelGGL(k_factor, dim3(count), dim3(WAVE), s->pp.lds_factor, st, T, D, O, first, h);
         launches++;
     }
-    if (s->fw_words && s->fw_fused && !phases) {
+    if (s->pp.fw_words && s->pp.fw_fused && !phases) {
         /* all levels below the root in one launch: a block waits for its parent's step inside the kernel */
         if (T.Np > 1) {
-            const unsigned fw_tag = next_tag(s->fw_epoch);
+            const unsigned fw_tag = next_tag(s->pp.fw_epoch);
             const Fuse F = fuse ? next_fuse(s) : no_fuse();          /* with k_ls_begin as its tail */
             ls_begun = fuse;
-            if (wide) hipLaunchKernelGGL(k_forward_all_w, dim3(T.Np - 1), dim3(WT), s->lds_forward_w, st, T, D, s->fw_words, fw_tag, h, F);
-            else hipLaunchKernelGGL(k_forward_all, dim3(T.Np - 1), dim3(WAVE), s->lds_forward, st, T, D, s->fw_words, fw_tag, h, F);
+            if (wide) hipLaunchKernelGGL(k_forward_all_w, dim3(T.Np - 1), dim3(WT), s->pp.lds_forward_w, st, T, D, s->pp.fw_words, fw_tag, h, F);
+            else hipLaunchKernelGGL(k_forward_all, dim3(T.Np - 1), dim3(WAVE), s->pp.lds_forward, st, T, D, s->pp.fw_words, fw_tag, h, F);
             launches++;
         }
     } else
     for (int lvl = 1; lvl < T.Nh; lvl++) {
         const int first = s->lvl_first[lvl], count = s->lvl_first[lvl + 1] - first;
-        if (wide) hipLaunchKernelGGL(k_forward_w, dim3(count), dim3(WT), s->lds_forward_w, st, T, D, first, h);
-        else hipLaunchKernelGGL(k_forward, dim3(count), dim3(WAVE), s->lds_forward, st, T, D, first, h);
+        if (wide) hipLaunchKernelGGL(k_forward_w, dim3(count), dim3(WT), s->pp.lds_forward_w, st, T, D, first, h);
+        else hipLaunchKernelGGL(k_forward, dim3(count), dim3(WAVE), s->pp.lds_forward, st, T, D, first, h);
         launches++;
     }
     mark(2);
     if (!ls_begun) { hipLaunchKernelGGL(k_ls_begin, dim3(1), dim3(256), 0, st, T, D, h); launches++; }
-    if (fuse) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
+    if (fuse) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->pp.lds_stage, st, T, D, O, next_fuse(s), 1, h, 1); launches++; }      /* with k_ls_decide as its tail */
     else {
         launch_stage_sweep(s, 1, h, 1); launches++;
         hipLaunchKernelGGL(k_ls_decide, dim3(1), dim3(256), 0, st, T, D, O, h, 1, 0); launches++;
@@ -2859,11 +2477,11 @@ void read_switches(Switches &w) {
 
 /* tree tables, the uniform / multistage / x0-padded form, and what the switches take away from it */
 int detect_shape(tqgpu_solver *s) {
-    auto detect = [s] { detect_fast(s); if (s->fast < 0) detect_multistage(s); };
+    auto detect = [s] { detect_fast(s); if (s->uni.fast < 0) detect_multistage(s); };
     int rc = build_tables(s);
     if (rc != TQGPU_OK) return rc;
     detect();
-    if (s->fast < 0 && s->nx[0] == 0 && s->Nn > 1 && s->nx[1] > 0 && !s->sw.generic) {
+    if (s->uni.fast < 0 && s->nx[0] == 0 && s->Nn > 1 && s->nx[1] > 0 && !s->sw.generic) {
         /* x0 eliminated (tree_qp_in_eliminate_x0: nx[0] = 0, the form every MPC caller solves).  If the tree would be
          * uniform / multistage with a full root node, give the root nx phantom states pinned to zero (bounds [0, 0],
          * unit weight, no linear term, zero A columns for the root's children): the same QP, and it takes the
@@ -2872,20 +2490,20 @@ int detect_shape(tqgpu_solver *s) {
         const int nx1 = s->nx[1];
         s->nx[0] = nx1;
         if (build_tables(s) == TQGPU_OK) detect();
-        if (s->fast >= 0) { s->x_pad = nx1; s->A_pad = s->nk[0] * nx1 * nx1; }
-        else { s->nx[0] = 0; s->fast = -1; s->mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
+        if (s->uni.fast >= 0) { s->x_pad = nx1; s->A_pad = s->nk[0] * nx1 * nx1; }
+        else { s->nx[0] = 0; s->uni.fast = -1; s->uni.mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
     }
-    if (s->sw.generic) { s->use_fast = 0; s->use_gpersist = 0; }
+    if (s->sw.generic) { s->uni.use_fast = 0; s->gp.use = 0; }
     s->gpd.single = s->sw.dense_single;
     s->gpd.batch = s->sw.dense_batch;
-    if (s->sw.tiered) s->use_persist = 0;
+    if (s->sw.tiered) s->persist.use = 0;
     /* reference-order sums (strict_sum / strict_block_dots): the launch-per-phase kernels and the single-workgroup kernel carry them;
      * the fused tails, the three-launch family and the persistent / tiered kernels (their partial sums are per workgroup by
      * construction) stand aside */
     s->strict_sum = s->sw.strict_sum;
-    if (s->strict_sum) { s->use_fast = 0; s->wide = s->wide_small = false; }          /* (the MFMA kernels of the wide-block class sum in tile order) */
-    s->use_persist_orig = s->use_persist;
-    if (s->sw.chunk > 0) s->chunk = s->sw.chunk;
+    if (s->strict_sum) { s->uni.use_fast = 0; s->pp.wide = s->pp.wide_small = false; }          /* (the MFMA kernels of the wide-block class sum in tile order) */
+    s->persist.use_orig = s->persist.use;
+    if (s->sw.chunk > 0) s->pp.chunk = s->sw.chunk;
     s->nxmax = *std::max_element(s->nx.begin(), s->nx.end());
     return TQGPU_OK;
 }
@@ -2911,7 +2529,7 @@ int layout_slab(tqgpu_solver *s) {
     const size_t o_W = cv.take(s->sum_W * Dbl), o_CW = cv.take(s->sum_W * Dbl), o_Ut = cv.take(s->sum_Ut * Dbl), o_CUt = cv.take(s->sum_Ut * Dbl);
     const size_t o_fval = cv.take(s->Nn * Dbl), o_perr = cv.take((SX + s->Nn + 1) * Dbl), o_pdot = cv.take(s->Nn * Dbl);
     const size_t maxnx = (size_t)s->nxmax;
-    const size_t o_sbuf = cv.take((s->fast >= 0 ? (size_t)s->Nn * (maxnx * maxnx + maxnx) : 1) * Dbl), o_ybuf = cv.take((SX + 1) * Dbl);
+    const size_t o_sbuf = cv.take((s->uni.fast >= 0 ? (size_t)s->Nn * (maxnx * maxnx + maxnx) : 1) * Dbl), o_ybuf = cv.take((SX + 1) * Dbl);
     const size_t o_mux = cv.take(SX * Dbl), o_muu = cv.take(SU * Dbl);
     const size_t o_lami = cv.take(SX * Dbl);
     s->poff.assign(s->Nn + 1, 0);
@@ -2929,9 +2547,9 @@ int layout_slab(tqgpu_solver *s) {
     if (hipMemset(s->slab, 0, s->slab_bytes) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipMemset failed");
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipStreamCreate failed");
     { std::lock_guard<std::mutex> lk(g_streams_mu); g_live_streams.insert(s->stream); }
-    s->ring_ev0.assign(EV_RING, nullptr); s->ring_ev1.assign(EV_RING, nullptr); s->ring_ok.assign(EV_RING, 0);
+    s->tm.ring_ev0.assign(EV_RING, nullptr); s->tm.ring_ev1.assign(EV_RING, nullptr); s->tm.ring_ok.assign(EV_RING, 0);
     for (int i = 0; i < EV_RING; i++)
-        if (hipEventCreate(&s->ring_ev0[i]) != hipSuccess || hipEventCreate(&s->ring_ev1[i]) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipEventCreate failed");
+        if (hipEventCreate(&s->tm.ring_ev0[i]) != hipSuccess || hipEventCreate(&s->tm.ring_ev1[i]) != hipSuccess) return fail(TQGPU_ENODEVICE, "hipEventCreate failed");
     if ((rc = s->mem.host(s->h_res, sizeof(HostRes), "the result block"))) return rc;
     memset(s->h_res, 0, sizeof(HostRes));
     s->h_ctrl = &s->h_res->c;
@@ -2959,8 +2577,8 @@ int layout_slab(tqgpu_solver *s) {
             e[7] = s->xoff[k0]; e[8] = s->woff[k]; e[9] = s->utoff[k]; e[10] = dd; e[11] = s->pos[k]; e[12] = s->bdim[dd]; e[13] = s->woff[dd];
             for (int u = 0; u < 4 && u < s->nk[k]; u++) { e[16 + 3 * u] = s->nx[k0 + u]; e[17 + 3 * u] = s->aoff[k0 + u]; e[18 + 3 * u] = s->boff[k0 + u]; }
         }
-        if ((rc = s->mem.upload(s->d_desc, desc.data(), desc.size() * I, TQGPU_ENOMEM, "the node records"))) return rc;
-        T.desc = s->d_desc;
+        if ((rc = s->mem.upload(s->uni.d_desc, desc.data(), desc.size() * I, TQGPU_ENOMEM, "the node records"))) return rc;
+        T.desc = s->uni.d_desc;
     }
     Data &D = s->D;
     s->A = at<double>(base, o_A); s->B = at<double>(base, o_B); s->b = at<double>(base, o_b);
@@ -2982,7 +2600,7 @@ int layout_slab(tqgpu_solver *s) {
     D.strict = s->strict_sum ? 1 : 0;
     D.dense = 0; s->sk.d_kind = at<int>(base, o_kind); D.kind = s->sk.d_kind; s->sk.d_Hd = at<double>(base, o_Hd); D.Hd = s->sk.d_Hd; D.Pd = at<double>(base, o_Pd); D.poff = at<int>(base, o_poff);
     D.bmask = at<unsigned long long>(base, o_bmask); D.xpad = s->x_pad;
-    s->use_fast_orig = s->use_fast;
+    s->uni.use_fast_orig = s->uni.use_fast;
     s->d_mu_x = at<double>(base, o_mux); s->d_mu_u = at<double>(base, o_muu);
     s->d_lam_init = at<double>(base, o_lami);
     s->in_off0 = o_A; s->in_bytes = o_Qinv - o_A;
@@ -3003,42 +2621,42 @@ int layout_slab(tqgpu_solver *s) {
 /* launch-per-phase kernels (any tree): LDS budgets, one launch per sweep or per level, the reductions as tails of the sweeps */
 int setup_per_phase(tqgpu_solver *s) {
     int rc;
-    if ((rc = allow_lds(k_stage, s->lds_stage)) || (rc = allow_lds(k_hess, s->lds_hess)) ||
-        (rc = allow_lds(k_factor, s->lds_factor)) || (rc = allow_lds(k_forward, s->lds_forward)) ||
-        (rc = allow_lds(k_factor_all, s->lds_factor)) || (rc = allow_lds(k_forward_all, s->lds_forward)) || (rc = allow_lds(k_stage_f, s->lds_stage)))
+    if ((rc = allow_lds(k_stage, s->pp.lds_stage)) || (rc = allow_lds(k_hess, s->pp.lds_hess)) ||
+        (rc = allow_lds(k_factor, s->pp.lds_factor)) || (rc = allow_lds(k_forward, s->pp.lds_forward)) ||
+        (rc = allow_lds(k_factor_all, s->pp.lds_factor)) || (rc = allow_lds(k_forward_all, s->pp.lds_forward)) || (rc = allow_lds(k_stage_f, s->pp.lds_stage)))
         return rc;
-    if (s->wide && ((rc = allow_lds(k_hess_w, s->lds_hess_w)) || (rc = allow_lds(k_factor_w, s->lds_factor_w)) || (rc = allow_lds(k_forward_w, s->lds_forward_w)) || (rc = allow_lds(k_forward_all_w, s->lds_forward_w)) || (rc = allow_lds(k_factor_all_w, s->lds_factor_w))))
+    if (s->pp.wide && ((rc = allow_lds(k_hess_w, s->pp.lds_hess_w)) || (rc = allow_lds(k_factor_w, s->pp.lds_factor_w)) || (rc = allow_lds(k_forward_w, s->pp.lds_forward_w)) || (rc = allow_lds(k_forward_all_w, s->pp.lds_forward_w)) || (rc = allow_lds(k_factor_all_w, s->pp.lds_factor_w))))
         return rc;
-    if (s->fast >= 0) {
+    if (s->uni.fast >= 0) {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, s->device) != hipSuccess || prop.maxThreadsPerBlock < FW * WAVE) s->fast = -1;
+        if (hipGetDeviceProperties(&prop, s->device) != hipSuccess || prop.maxThreadsPerBlock < FW * WAVE) s->uni.fast = -1;
     }
-    s->fw_fused = !s->sw.fwd_levels && !s->strict_sum;      /* (strict: the reference's launch-per-level order of operations) */
-    s->bw_fused = !s->sw.bwd_levels && !s->strict_sum;      /* (a fused sweep subtracts a child's Schur record AFTER an ALWAYS shift of the diagonal, the reference before it) */
-    s->sch_rs = (s->nxmax + 1) * (s->nxmax + 1);
-    s->fuse_ok = s->Nn <= FUSE_MAX && s->Nn >= 2 && !s->sw.no_fuse && !s->strict_sum;
+    s->pp.fw_fused = !s->sw.fwd_levels && !s->strict_sum;      /* (strict: the reference's launch-per-level order of operations) */
+    s->pp.bw_fused = !s->sw.bwd_levels && !s->strict_sum;      /* (a fused sweep subtracts a child's Schur record AFTER an ALWAYS shift of the diagonal, the reference before it) */
+    s->pp.sch_rs = (s->nxmax + 1) * (s->nxmax + 1);
+    s->pp.fuse_ok = s->Nn <= FUSE_MAX && s->Nn >= 2 && !s->sw.no_fuse && !s->strict_sum;
     /* hand-over words of the fused forward / backward sweeps of the launch-per-phase path (zeroed once; every launch brings its own tag) */
     const size_t U = sizeof(unsigned long long);
-    if ((rc = s->mem.zeroed(s->fw_words, U * 2 * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the forward hand-over words")) ||
-        (rc = s->mem.zeroed(s->sch_words, U * 2 * (size_t)s->sch_rs * (size_t)s->Nn, TQGPU_ENOMEM, "the Schur hand-over words")))
+    if ((rc = s->mem.zeroed(s->pp.fw_words, U * 2 * (size_t)std::max(s->sum_nx, 1), TQGPU_ENOMEM, "the forward hand-over words")) ||
+        (rc = s->mem.zeroed(s->pp.sch_words, U * 2 * (size_t)s->pp.sch_rs * (size_t)s->Nn, TQGPU_ENOMEM, "the Schur hand-over words")))
         return rc;
-    if (s->fuse_ok && ((rc = s->mem.zeroed(s->fuse_red, U * 2 * (size_t)s->Nn, TQGPU_ENOMEM, "the fused reductions")) ||
-                       (rc = s->mem.zeroed(s->fuse_cnt, 4 * sizeof(int), TQGPU_ENOMEM, "the fused reductions' counter"))))
+    if (s->pp.fuse_ok && ((rc = s->mem.zeroed(s->pp.fuse_red, U * 2 * (size_t)s->Nn, TQGPU_ENOMEM, "the fused reductions")) ||
+                       (rc = s->mem.zeroed(s->pp.fuse_cnt, 4 * sizeof(int), TQGPU_ENOMEM, "the fused reductions' counter"))))
         return rc;
     return TQGPU_OK;
 }
 
 /* the three-launch family of the wide-block class (tdunes_wide3.hpp) */
 int setup_wide3(tqgpu_solver *s) {
-    if (!(s->wide && s->fw_fused && s->bw_fused && !s->sw.no_wide3 && !s->strict_sum)) return TQGPU_OK;      /* (TREEQP_AMD_FWD / BWD = levels ask for the launch-per-level kernels) */
-    for (int k = 0; k < s->Np; k++) s->lds_hf_w = std::max(s->lds_hf_w, wide3_lds(s->bdim[k], k > 0 ? s->nx[k] : 0, s->nx[k] + s->nu[k]));
-    if (!(s->nxmax <= 32 && s->lds_hf_w <= 160 * 1024 && SG_WAVES * s->lds_stage <= 160 * 1024)) return TQGPU_OK;
+    if (!(s->pp.wide && s->pp.fw_fused && s->pp.bw_fused && !s->sw.no_wide3 && !s->strict_sum)) return TQGPU_OK;      /* (TREEQP_AMD_FWD / BWD = levels ask for the launch-per-level kernels) */
+    for (int k = 0; k < s->Np; k++) s->w3.lds_hf_w = std::max(s->w3.lds_hf_w, wide3_lds(s->bdim[k], k > 0 ? s->nx[k] : 0, s->nx[k] + s->nu[k]));
+    if (!(s->nxmax <= 32 && s->w3.lds_hf_w <= 160 * 1024 && SG_WAVES * s->pp.lds_stage <= 160 * 1024)) return TQGPU_OK;
     /* k_sgp: one entry of a node's [x | u] per lane, one row of a block per lane */
     bool fits = true;
     for (int k = 0; k < s->Nn; k++) fits = fits && s->nx[k] + s->nu[k] <= 64;
-    for (int k = 0; k < s->Np; k++) s->sgp_accs = std::max(s->sgp_accs, std::min(s->nk[k], 8) * (s->nx[k] + s->nu[k]));      /* the children's terms in LDS: up to 8 children (more: taken by wave 0 on its own) */
-    for (int k = 0; k < s->Np; k++) s->lds_sgp = std::max(s->lds_sgp, wide3_lds_sgp(s->bdim[k], s->nx[k] + s->nu[k], s->sgp_accs));
-    s->w3_sgp = fits && s->lds_sgp <= 64 * 1024 && !s->sw.no_sgp;
+    for (int k = 0; k < s->Np; k++) s->w3.sgp_accs = std::max(s->w3.sgp_accs, std::min(s->nk[k], 8) * (s->nx[k] + s->nu[k]));      /* the children's terms in LDS: up to 8 children (more: taken by wave 0 on its own) */
+    for (int k = 0; k < s->Np; k++) s->w3.lds_sgp = std::max(s->w3.lds_sgp, wide3_lds_sgp(s->bdim[k], s->nx[k] + s->nu[k], s->w3.sgp_accs));
+    s->w3.sgp = fits && s->w3.lds_sgp <= 64 * 1024 && !s->sw.no_sgp;
     /* forward sweep without hand-overs (k_fwd3c): small nodes, short paths, blocks whose region of CholW has room for the copy of z0
      * beside the diagnostic stamps */
     bool okc = s->Np > 1 && !s->sw.no_fwd_chain;
@@ -3063,18 +2681,18 @@ int setup_wide3(tqgpu_solver *s) {
             }
         }
     }
-    s->w3_merge = okc && s->w3_sgp && !s->sw.no_fwd_merge;
+    s->w3.merge = okc && s->w3.sgp && !s->sw.no_fwd_merge;
     const size_t U = sizeof(unsigned long long);
     const size_t groups = std::max((size_t)(s->Nn + SG_WAVES - 1) / SG_WAVES, (size_t)s->Np);      /* workgroups of k_sg / k_sgp / k_fwd3 */
     int rc;
-    if ((rc = s->mem.zeroed(s->w3_xu, U * 2 * (size_t)std::max(s->sum_nx + s->sum_nu, 1), TQGPU_ENOMEM, "the three-launch hand-over words")) ||
-        (rc = s->mem.zeroed(s->w3_red, U * 4 * groups, TQGPU_ENOMEM, "the three-launch reductions")) ||
-        (rc = s->mem.zeroed(s->w3_cnt, 4 * sizeof(int), TQGPU_ENOMEM, "the three-launch reductions' counter")) ||
-        (rc = allow_lds(k_hf_w, s->lds_hf_w)) || (rc = allow_lds(k_sg, SG_WAVES * ((s->lds_stage + 7) / 8) * 8)))
+    if ((rc = s->mem.zeroed(s->w3.xu, U * 2 * (size_t)std::max(s->sum_nx + s->sum_nu, 1), TQGPU_ENOMEM, "the three-launch hand-over words")) ||
+        (rc = s->mem.zeroed(s->w3.red, U * 4 * groups, TQGPU_ENOMEM, "the three-launch reductions")) ||
+        (rc = s->mem.zeroed(s->w3.cnt, 4 * sizeof(int), TQGPU_ENOMEM, "the three-launch reductions' counter")) ||
+        (rc = allow_lds(k_hf_w, s->w3.lds_hf_w)) || (rc = allow_lds(k_sg, SG_WAVES * ((s->pp.lds_stage + 7) / 8) * 8)))
         return rc;
-    if (okc && (rc = s->mem.upload(s->d_anc, anc.data(), anc.size() * sizeof(int), TQGPU_ENOMEM, "the path table of the forward sweep"))) return rc;
-    if (s->w3_merge && (rc = s->mem.zeroed(s->d_pdw, U * 2 * (size_t)s->Np, TQGPU_ENOMEM, "the forward sweep's partial sums"))) return rc;
-    s->w3_ok = true;
+    if (okc && (rc = s->mem.upload(s->w3.d_anc, anc.data(), anc.size() * sizeof(int), TQGPU_ENOMEM, "the path table of the forward sweep"))) return rc;
+    if (s->w3.merge && (rc = s->mem.zeroed(s->w3.d_pdw, U * 2 * (size_t)s->Np, TQGPU_ENOMEM, "the forward sweep's partial sums"))) return rc;
+    s->w3.ok = true;
     return TQGPU_OK;
 }
 
@@ -3083,47 +2701,47 @@ int setup_single_wg(tqgpu_solver *s) {
      * of GP_WAVES blocks at most, and the per-wave LDS windows must fit the default 64 KB */
     int widest = 0;
     for (int l = 0; l <= s->Nh; l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
-    const size_t per_wave = (std::max(std::max(s->lds_stage, s->lds_hess), std::max(s->lds_factor, s->lds_forward)) + 7) / 8 + 2;
-    s->lds_gp_wave = per_wave;
+    const size_t per_wave = (std::max(std::max(s->pp.lds_stage, s->pp.lds_hess), std::max(s->pp.lds_factor, s->pp.lds_forward)) + 7) / 8 + 2;
+    s->gp.lds_wave = per_wave;
     {
         /* four nodes per wave in the stage sweep: nx + nu <= 16 everywhere, clipping nodes only, and a quarter of the wave's window
          * holds a node's duals (bdim + nx doubles) */
         bool ok16 = !s->sk.dense && !s->sw.no_stage16;
         for (int k = 0; k < s->Nn && ok16; k++) ok16 = s->nx[k] + s->nu[k] <= 16 && (size_t)(s->bdim[k] + s->nx[k]) <= per_wave / 4;
-        s->gp_small16 = ok16;
+        s->gp.small16 = ok16;
         bool ok8 = !s->sw.no_stage16 && !s->strict_sum;          /* eight nodes per wave in the gradient sweep: nx <= 8 everywhere */
         for (int k = 0; k < s->Nn && ok8; k++) ok8 = s->nx[k] <= 8;
-        s->gp_small8 = ok8;
+        s->gp.small8 = ok8;
     }
-    s->gpersist_ok = widest <= 6 * GP_WAVES && per_wave * 8 * GP_WAVES <= 150 * 1024;
+    s->gp.ok = widest <= 6 * GP_WAVES && per_wave * 8 * GP_WAVES <= 150 * 1024;
     /* LDS mirror of the mutable state (tdunes_gpersist.hpp): 16 node-sized vectors (rounded up to even), 4 block arrays */
     {
         auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
         const size_t sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
         const size_t mirror = 11 * ev(sx) + 5 * ev(su) + 2 * ev((size_t)s->sum_W) + 2 * ev((size_t)s->sum_Ut) + 2 * ev((size_t)s->Nn) + ev(sx + s->Nn + 1) + ev(su) * 0;
         const size_t tables = (13 * ((size_t)s->Nn + 3)) / 2 + 16;            /* int tables, in doubles */
-        s->lds_gp_total = (per_wave * GP_WAVES + mirror + tables + 8) * 8;
-        s->gp_in_lds = s->gpersist_ok && s->lds_gp_total <= 150 * 1024;
+        s->gp.lds_total = (per_wave * GP_WAVES + mirror + tables + 8) * 8;
+        s->gp.in_lds = s->gp.ok && s->gp.lds_total <= 150 * 1024;
         const size_t consts = (ev((size_t)s->sum_A) + ev((size_t)s->sum_B) + 5 * ev(sx) + 4 * ev(su)) * 8;
-        s->gp_const_in_lds = s->gp_in_lds && s->lds_gp_total + consts <= 150 * 1024;
-        if (s->gp_const_in_lds) s->lds_gp_total += consts;
-        if (!s->gp_in_lds) {
+        s->gp.const_in_lds = s->gp.in_lds && s->gp.lds_total + consts <= 150 * 1024;
+        if (s->gp.const_in_lds) s->gp.lds_total += consts;
+        if (!s->gp.in_lds) {
             /* the state does not fit: the index tables alone, next to the per-wave windows, if THEY fit */
-            s->gp_tab_in_lds = s->gpersist_ok && (per_wave * GP_WAVES + tables + 8) * 8 <= 150 * 1024;
-            s->lds_gp_total = (per_wave * GP_WAVES + (s->gp_tab_in_lds ? tables + 8 : 0)) * 8;
+            s->gp.tab_in_lds = s->gp.ok && (per_wave * GP_WAVES + tables + 8) * 8 <= 150 * 1024;
+            s->gp.lds_total = (per_wave * GP_WAVES + (s->gp.tab_in_lds ? tables + 8 : 0)) * 8;
         }
-        else if (s->lds_gp_total > 64 * 1024 &&
-                 hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_gp_total) != hipSuccess) {
+        else if (s->gp.lds_total > 64 * 1024 &&
+                 hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->gp.lds_total) != hipSuccess) {
             (void)hipGetLastError();
-            s->gp_in_lds = false; s->gp_tab_in_lds = false; s->lds_gp_total = per_wave * GP_WAVES * 8;
+            s->gp.in_lds = false; s->gp.tab_in_lds = false; s->gp.lds_total = per_wave * GP_WAVES * 8;
         }
-        if (s->gpersist_ok && !s->gp_in_lds && s->lds_gp_total > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_gp_total) != hipSuccess) {
+        if (s->gp.ok && !s->gp.in_lds && s->gp.lds_total > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->gp.lds_total) != hipSuccess) {
             (void)hipGetLastError();
-            s->gpersist_ok = false;
+            s->gp.ok = false;
         }
     }
-    if (s->gpersist_ok) {
+    if (s->gp.ok) {
         /* behind the level table: for every level of parents, how many of its blocks one wave takes side by side in the backward /
          * forward / Hessian sweeps (factor_body_g ...): levels wider than the workgroup's 16 waves whose blocks all have the same
          * small dimensions (the chains of a pruned scenario tree); 1 = one block per wave */
@@ -3142,13 +2760,13 @@ int setup_single_wg(tqgpu_solver *s) {
                 /* doubles of a group's window: factor_body's tall matrix, forward_body's factor + vectors, hess_body's C and C P */
                 const size_t need = std::max(std::max((size_t)(R | 1) * d0 + d0 + 2, (size_t)(d0 | 1) * d0 + 2 * d0 + n0 + 2), (size_t)2 * d0 * (n0 + u0) + 2);
                 if (same && d0 >= 1) {
-                    if (R <= WAVE / 3 && 3 * need <= s->lds_gp_wave) grp = 3;
-                    else if (R <= WAVE / 2 && 2 * need <= s->lds_gp_wave) grp = 2;
+                    if (R <= WAVE / 3 && 3 * need <= s->gp.lds_wave) grp = 3;
+                    else if (R <= WAVE / 2 && 2 * need <= s->gp.lds_wave) grp = 2;
                 }
             }
             tab.push_back(grp);
         }
-        return s->mem.upload(s->d_lvl_first, tab.data(), sizeof(int) * tab.size(), TQGPU_ENOMEM, "the level table");
+        return s->mem.upload(s->gp.d_lvl_first, tab.data(), sizeof(int) * tab.size(), TQGPU_ENOMEM, "the level table");
     }
     return TQGPU_OK;
 }
@@ -3186,12 +2804,12 @@ extern "C" void tqgpu_destroy(tqgpu_solver *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (auto &ev : s->iter_ev) (void)hipEventDestroy(ev);
-    for (auto &ev : s->phase_ev) (void)hipEventDestroy(ev);
-    if (s->sweep_ev0) (void)hipEventDestroy(s->sweep_ev0);
-    if (s->sweep_ev1) (void)hipEventDestroy(s->sweep_ev1);
-    for (auto &ev : s->ring_ev0) if (ev) (void)hipEventDestroy(ev);
-    for (auto &ev : s->ring_ev1) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : s->tm.iter_ev) (void)hipEventDestroy(ev);
+    for (auto &ev : s->tm.phase_ev) (void)hipEventDestroy(ev);
+    if (s->tm.sweep_ev0) (void)hipEventDestroy(s->tm.sweep_ev0);
+    if (s->tm.sweep_ev1) (void)hipEventDestroy(s->tm.sweep_ev1);
+    for (auto &ev : s->tm.ring_ev0) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : s->tm.ring_ev1) if (ev) (void)hipEventDestroy(ev);
     if (s->stream) { { std::lock_guard<std::mutex> lk(g_streams_mu); g_live_streams.erase(s->stream); } (void)hipStreamDestroy(s->stream); }
     shard_release(s);
     s->mem.free_all();
@@ -3199,15 +2817,15 @@ extern "C" void tqgpu_destroy(tqgpu_solver *s) {
 }
 
 /* what a mirror admits: the persistent single launch (uniform or multistage trees), launches per tier (uniform trees only) */
-static bool persist_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && s->persist_ok && s->use_persist && !s->shard.on; }
-static bool tiered_capable(const tqgpu_solver *s) { return s->fast >= 0 && s->use_fast && !s->mstage; }
+static bool persist_capable(const tqgpu_solver *s) { return s->uni.fast >= 0 && s->uni.use_fast && s->persist.ok && s->persist.use && !s->shard.on; }
+static bool tiered_capable(const tqgpu_solver *s) { return s->uni.fast >= 0 && s->uni.use_fast && !s->uni.mstage; }
 /* `batch`: as a member of a batched launch (one workgroup per tree) the single-workgroup kernel also takes trees whose
  * state does not fit the LDS mirror; alone, such a tree is faster with one launch per level */
 static bool uses_gpersist(const tqgpu_solver *s, bool batch) {
     /* a dense tree: only on request, only where plan_dense_single found room; alone and as a member of a batch are two requests
      * (g_persist_dense, g_persist_dense_batch) */
-    if (s->sk.dense) return (batch ? s->gpd.batch : s->gpd.single) && s->gpd.ok && s->use_gpersist && !s->shard.on;
-    return s->gpersist_ok && (s->gp_in_lds || batch) && s->use_gpersist && !s->shard.on && !persist_capable(s) && !tiered_capable(s);
+    if (s->sk.dense) return (batch ? s->gpd.batch : s->gpd.single) && s->gpd.ok && s->gp.use && !s->shard.on;
+    return s->gp.ok && (s->gp.in_lds || batch) && s->gp.use && !s->shard.on && !persist_capable(s) && !tiered_capable(s);
 }
 /* the first route that the mirror and the options admit (batch_member: see uses_gpersist) */
 static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_member) {
@@ -3215,22 +2833,22 @@ static Route route_of(const tqgpu_solver *s, const tqgpu_opts *o, bool batch_mem
     if (persist_capable(s) && p == 0 && m > 0) return Route::PERSIST;
     if (uses_gpersist(s, batch_member) && p == 0 && m > 0) return Route::SINGLE_WG;
     if (tiered_capable(s) && p < 3) return Route::TIERED;
-    if (s->w3_ok && !s->sk.dense && p < 3 && !s->shard.on) return Route::THREE_LAUNCH;
-    if (s->fuse_ok && p < 3 && !s->shard.on && !s->sk.box && !s->sk.gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
+    if (s->w3.ok && !s->sk.dense && p < 3 && !s->shard.on) return Route::THREE_LAUNCH;
+    if (s->pp.fuse_ok && p < 3 && !s->shard.on && !s->sk.box && !s->sk.gen) return Route::FUSED_TAILS;     /* (box nodes: a failed stage solve ends the solve in the control block, which the NEXT launch reads) */
     return Route::PER_PHASE;       /* (profile level 3: one launch per level, whose launches ARE the reference's phases) */
 }
 /* the kernel variants the steps of tqgpu_create (setup_per_phase, setup_wide3, setup_persist, setup_single_wg) and tqgpu_set_objective_mixed chose, and whether the last solve ran g_persist (TQGPU_PLAN_* bits);
  * reads fields, changes nothing */
 extern "C" int tqgpu_debug_plan(const tqgpu_solver *s, unsigned *flags, int *sgp_accs) {
     if (!s) return fail(TQGPU_EINVAL, "null solver");
-    const bool bits[] = {s->wide, s->wide_small, s->w3_ok, s->w3_sgp, s->w3_merge, s->d_anc != nullptr, s->fuse_ok, s->persist_ok,
-                         s->persist_one, s->gpersist_ok, s->gp_in_lds, s->gp_const_in_lds, s->gp_tab_in_lds, s->gp_small16, s->gp_small8,
+    const bool bits[] = {s->pp.wide, s->pp.wide_small, s->w3.ok, s->w3.sgp, s->w3.merge, s->w3.d_anc != nullptr, s->pp.fuse_ok, s->persist.ok,
+                         s->persist.one, s->gp.ok, s->gp.in_lds, s->gp.const_in_lds, s->gp.tab_in_lds, s->gp.small16, s->gp.small8,
                          s->sk.dense, s->sk.box, s->solve_no > 0 && s->route == Route::SINGLE_WG, s->sk.gen,
                          s->sk.dense && s->gpd.single && s->gpd.ok};
     unsigned f = 0;
     for (unsigned i = 0; i < sizeof(bits) / sizeof(bits[0]); i++) f |= bits[i] ? 1u << i : 0u;
     if (flags) *flags = f;
-    if (sgp_accs) *sgp_accs = s->sgp_accs;
+    if (sgp_accs) *sgp_accs = s->w3.sgp_accs;
     return TQGPU_OK;
 }
 extern "C" int tqgpu_uses_fused_path(const tqgpu_solver *s) {
@@ -3323,11 +2941,11 @@ bool await_result_block(HostRes *hr, unsigned want, bool tagged) {
 /* the sticky word a bounded wait inside a persistent launch sets when it gives up: read (the stream has been waited for, or the verdict
  * is in), and cleared on the mirror's stream */
 int read_timeout_word(tqgpu_solver *s, unsigned &tmo) {
-    HIP_TRY(hipMemcpy(&tmo, s->psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&tmo, s->persist.psync.timeout, sizeof(unsigned), hipMemcpyDeviceToHost));
     return TQGPU_OK;
 }
 int clear_timeout_word(tqgpu_solver *s) {
-    HIP_TRY(hipMemsetAsync(s->psync.timeout, 0, sizeof(unsigned), s->stream));
+    HIP_TRY(hipMemsetAsync(s->persist.psync.timeout, 0, sizeof(unsigned), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return TQGPU_OK;
 }
@@ -3338,17 +2956,17 @@ void fill_result(tqgpu_result *res, const Ctrl &c, int launches, double device_s
 }
 
 int read_ctrl(tqgpu_solver *s) {
-    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && !s->w3_tail_sg) {
+    if (s->route == Route::THREE_LAUNCH && s->w3.mirror && !s->w3.tail_sg) {
         /* the last launch enqueued does not post (the first sweep of a solve whose chunk launches nothing else): a one-thread launch does */
         W3 w = next_w3(s);
-        w.hm = s->h_res; s->w3_wait = w.tag; s->w3_tail_sg = true;
+        w.hm = s->h_res; s->w3.wait = w.tag; s->w3.tail_sg = true;
         hipLaunchKernelGGL(k_w3_post, dim3(1), dim3(WAVE), 0, s->stream, s->D, w);
     }
-    if (s->route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_tail_sg) {
+    if (s->route == Route::THREE_LAUNCH && s->w3.mirror && s->w3.tail_sg) {
         /* three-launch family: the last launch enqueued posts the control block to pinned memory itself (w3_mirror) */
-        if (await_result_block(s->h_res, s->w3_wait, false)) { s->w3_seen = true; return TQGPU_OK; }      /* h_ctrl IS the block's control block */
+        if (await_result_block(s->h_res, s->w3.wait, false)) { s->w3.seen = true; return TQGPU_OK; }      /* h_ctrl IS the block's control block */
     }
-    s->w3_seen = false;
+    s->w3.seen = false;
     HIP_TRY(hipMemcpyAsync(s->h_ctrl, s->D.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     MPC_COUNT(copies, 1); MPC_COUNT(waits, 1);
@@ -3358,11 +2976,11 @@ int read_ctrl(tqgpu_solver *s) {
 /* persistent launch: wait for the result block the top workgroup writes into pinned host memory (the
  * kernel may still be writing the state back -- everything else the host does is stream-ordered behind it) */
 int wait_result_block(tqgpu_solver *s) {
-    if (await_result_block(s->h_res, s->psync.seq, true)) return TQGPU_OK;
+    if (await_result_block(s->h_res, s->persist.psync.seq, true)) return TQGPU_OK;
     /* no verdict (a wait inside the kernel timed out, or the launch failed): fall back to the stream.  A member of a
      * batch launch first waits for THAT launch (it runs on the lead's stream; the member's own stream is not ordered
      * behind it, and its control block is only final when the launch has ended) */
-    if (s->batch_stream) HIP_TRY(hipStreamSynchronize(s->batch_stream));
+    if (s->links.batch_stream) HIP_TRY(hipStreamSynchronize(s->links.batch_stream));
     return read_ctrl(s);
 }
 
@@ -3430,32 +3048,32 @@ int prepare_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, bool in_ba
     /* ls_log needs no reset: entry i is written by iteration i */
 
     int rc;
-    if (o->profile && (rc = grow_events(s->iter_ev, o->maxIter + 1)) != TQGPU_OK) return rc;
+    if (o->profile && (rc = grow_events(s->tm.iter_ev, o->maxIter + 1)) != TQGPU_OK) return rc;
     /* (the per-iteration / per-phase time records are all-NaN unless a profiled solve has written into them: not refilled per solve) */
     const size_t n_it = (size_t)std::max(o->maxIter, 1);
-    if (s->times_dirty || s->iter_times.size() != n_it) s->iter_times.assign(n_it, NAN);
+    if (s->tm.times_dirty || s->tm.iter_times.size() != n_it) s->tm.iter_times.assign(n_it, NAN);
 
     s->route = cx.route;
     cx.phases = o->profile >= 3;
     if (cx.phases) {
-        if ((rc = grow_events(s->phase_ev, 4 * (o->maxIter + 1))) != TQGPU_OK) return rc;
-        if (!s->sweep_ev0) { HIP_TRY(hipEventCreate(&s->sweep_ev0)); HIP_TRY(hipEventCreate(&s->sweep_ev1)); }
+        if ((rc = grow_events(s->tm.phase_ev, 4 * (o->maxIter + 1))) != TQGPU_OK) return rc;
+        if (!s->tm.sweep_ev0) { HIP_TRY(hipEventCreate(&s->tm.sweep_ev0)); HIP_TRY(hipEventCreate(&s->tm.sweep_ev1)); }
     }
-    if (s->times_dirty || s->phase_times.size() != 3 * n_it) s->phase_times.assign(3 * n_it, NAN);
-    s->first_sweep_time = NAN;
-    s->times_dirty = o->profile != 0;
+    if (s->tm.times_dirty || s->tm.phase_times.size() != 3 * n_it) s->tm.phase_times.assign(3 * n_it, NAN);
+    s->tm.first_sweep_time = NAN;
+    s->tm.times_dirty = o->profile != 0;
     cx.ring = (int)(s->solve_no % EV_RING);
-    cx.ev0 = s->ring_ev0[cx.ring]; cx.ev1 = s->ring_ev1[cx.ring];
+    cx.ev0 = s->tm.ring_ev0[cx.ring]; cx.ev1 = s->tm.ring_ev1[cx.ring];
     s->solve_no++;
     /* the event pair costs two more packets on the queue per solve; a single persistent launch reports its own clock (launch
      * start to verdict) anyway, so there the pair is optional */
     /* the three-launch family reports through the pinned result block as well (launches of k_sg / k_sgp post the control block and
      * their own clock: w3_mirror) */
-    s->w3_mirror = cx.route == Route::THREE_LAUNCH && !o->profile && !cx.env.no_w3_mirror;
-    s->w3_seen = false;
-    if (s->w3_mirror) s->h_res->seq = 0;          /* (no launch of this mirror is in flight) */
-    cx.events = (s->ev_timing || (!single_launch(cx.route) && !s->w3_mirror)) && !cx.batch_seq && !in_batch_launch;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
-    s->ring_ok[(size_t)cx.ring] = cx.events ? 1 : 0;
+    s->w3.mirror = cx.route == Route::THREE_LAUNCH && !o->profile && !cx.env.no_w3_mirror;
+    s->w3.seen = false;
+    if (s->w3.mirror) s->h_res->seq = 0;          /* (no launch of this mirror is in flight) */
+    cx.events = (s->tm.ev_timing || (!single_launch(cx.route) && !s->w3.mirror)) && !cx.batch_seq && !in_batch_launch;      /* (a member of a batch launch: the launch is on the lead's stream, an event pair on the member's own would time nothing) */
+    s->tm.ring_ok[(size_t)cx.ring] = cx.events ? 1 : 0;
     if (cx.events) HIP_TRY(hipEventRecord(cx.ev0, s->stream));
     return TQGPU_OK;
 }
@@ -3467,7 +3085,7 @@ int enqueue_setup(tqgpu_solver *s, SolveCtx &cx, const GItem *defer) {
         const int nxu = std::max(s->sum_nx, s->sum_nu);
         hipLaunchKernelGGL(k_init, dim3((nxu + 255) / 256), dim3(256), 0, st, s->sum_nx, s->sum_nu, D); cx.launches++;
         s->need_init = false;
-        s->stream_pending = true;
+        s->links.stream_pending = true;
     }
     /* tqgpu_get_stage_steps: per solve.  (A dense member of a batch launch: that launch is on the lead's stream and resets the counters in its own
      * prologue, g_persist_dense_batch -- a memset on this stream would have to be waited for, once per member and call) */
@@ -3475,7 +3093,7 @@ int enqueue_setup(tqgpu_solver *s, SolveCtx &cx, const GItem *defer) {
     if (s->sk.dense && s->sk.need_dense_init) {
         hipLaunchKernelGGL(k_dense_init, dim3(T.Nn), dim3(WAVE), s->sk.lds_dense, st, T, D); cx.launches++;
         s->sk.need_dense_init = false;
-        if (defer) s->stream_pending = true;      /* the batch launch on the lead's stream waits for it (join_lead_stream): first solves and changed data only */
+        if (defer) s->links.stream_pending = true;      /* the batch launch on the lead's stream waits for it (join_lead_stream): first solves and changed data only */
     }
     return TQGPU_OK;
 }
@@ -3485,21 +3103,21 @@ int begin_enqueued(tqgpu_solver *s, SolveCtx &cx) {
     const Tree &T = s->T; const Data &D = s->D; hipStream_t st = s->stream;
     const bool w3 = cx.route == Route::THREE_LAUNCH;
     /* the three-launch family with k_sgp: the first launch of the solve takes the starting duals and resets the control block itself */
-    const bool fresh = w3 && s->w3_sgp;
+    const bool fresh = w3 && s->w3.sgp;
     if (!fresh) HIP_TRY(hipMemsetAsync(D.ctrl, 0, sizeof(Ctrl), st));     /* persistent path: reset by the launch's prologue */
     int rc = enqueue_setup(s, cx, nullptr);
     if (rc != TQGPU_OK) return rc;
     /* the current buffer is lam0 at the start of every solve */
     if (!fresh) HIP_TRY(hipMemcpyAsync(D.lam0, s->d_lam_init, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, st));
     /* first sweep at lambda0 (phase S of iteration 0 + fval0); the persistent launch does it as its prologue */
-    if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev0, st));
+    if (cx.phases) HIP_TRY(hipEventRecord(s->tm.sweep_ev0, st));
     if (w3) { launch_sg(s, cx.O, 0, 0, 0, fresh); cx.launches++; }          /* with fval0 and the first termination test as its tail */
-    else if (cx.route == Route::FUSED_TAILS) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
+    else if (cx.route == Route::FUSED_TAILS) { hipLaunchKernelGGL(k_stage_f, dim3(T.Nn), dim3(WAVE), s->pp.lds_stage, st, T, D, cx.O, next_fuse(s), 0, 0, 0); cx.launches++; }      /* with k_fval_init as its tail */
     else {
         launch_stage_sweep(s, 0, 0, 0); cx.launches++;
         hipLaunchKernelGGL(k_fval_init, dim3(1), dim3(256), 0, st, T, D); cx.launches++;
     }
-    if (cx.phases) HIP_TRY(hipEventRecord(s->sweep_ev1, st));
+    if (cx.phases) HIP_TRY(hipEventRecord(s->tm.sweep_ev1, st));
     return TQGPU_OK;
 }
 
@@ -3507,12 +3125,12 @@ int begin_enqueued(tqgpu_solver *s, SolveCtx &cx) {
  * g_persist_dense with the plan of plan_dense_single (deferred: the same parameters for this member's workgroup of the batch launch) */
 GParams gparams_of(const tqgpu_solver *s) {
     GParams gp;
-    gp.lvl_first = s->d_lvl_first; gp.lam_init = s->d_lam_init; gp.hres = s->h_res; gp.seq = s->psync.seq; gp.lds_wave = (int)s->lds_gp_wave;
+    gp.lvl_first = s->gp.d_lvl_first; gp.lam_init = s->d_lam_init; gp.hres = s->h_res; gp.seq = s->persist.psync.seq; gp.lds_wave = (int)s->gp.lds_wave;
     gp.sum_nx = s->sum_nx; gp.sum_nu = s->sum_nu; gp.sum_W = s->sum_W; gp.sum_Ut = s->sum_Ut; gp.sum_A = s->sum_A; gp.sum_B = s->sum_B;
-    gp.small8 = s->gp_small8 ? 1 : 0;
+    gp.small8 = s->gp.small8 ? 1 : 0;
     if (!s->sk.dense) {
-        gp.in_lds = s->gp_in_lds ? 1 : 0; gp.tab_in_lds = (!s->gp_in_lds && s->gp_tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gp_const_in_lds ? 1 : 0;
-        gp.small16 = s->gp_small16 ? 1 : 0;
+        gp.in_lds = s->gp.in_lds ? 1 : 0; gp.tab_in_lds = (!s->gp.in_lds && s->gp.tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gp.const_in_lds ? 1 : 0;
+        gp.small16 = s->gp.small16 ? 1 : 0;
         gp.stage_waves = 0; gp.win_stage = 0; gp.win_region = 0; gp.phase_waves = 0;
     } else {
         gp.in_lds = s->gpd.in_lds ? 1 : 0; gp.tab_in_lds = (!s->gpd.in_lds && s->gpd.tab_in_lds) ? 1 : 0; gp.const_in_lds = s->gpd.const_in_lds ? 1 : 0;
@@ -3527,11 +3145,11 @@ GParams gparams_of(const tqgpu_solver *s) {
  * every word of the result block, the only thing the number tags here, is rewritten by every launch */
 int begin_single_wg(tqgpu_solver *s, SolveCtx &cx, GItem *defer) {
     (void)step_launch_no(s);
-    s->psync.seq = s->launch_no << 16;
+    s->persist.psync.seq = s->persist.launch_no << 16;
     const GParams gp = gparams_of(s);
     if (defer) { defer->T = s->T; defer->D = s->D; defer->G = gp; }           /* launched by the caller, together with the rest of its batch */
     else if (s->sk.dense) hipLaunchKernelGGL(g_persist_dense, dim3(1), dim3(GPD_WAVES * WAVE), s->gpd.lds_total, s->stream, s->T, s->D, cx.O, gp);
-    else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->lds_gp_total, s->stream, s->T, s->D, cx.O, gp);
+    else hipLaunchKernelGGL(g_persist, dim3(1), dim3(GP_WAVES * WAVE), s->gp.lds_total, s->stream, s->T, s->D, cx.O, gp);
     cx.launches++;          /* (also the caller's) */
     return TQGPU_OK;
 }
@@ -3568,7 +3186,7 @@ int solve_begin(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, GItem *defer
             if ((rc = settle(s)) != TQGPU_OK) return rc;
             HIP_TRY(hipMemcpyAsync(s->d_lam_init, s->shift.d_keep, sizeof(double) * (size_t)s->sum_nx, hipMemcpyDeviceToDevice, s->stream)); MPC_COUNT(copies, 1);
             s->lam_valid = false;
-            s->stream_pending = true;
+            s->links.stream_pending = true;
         }
     }
     if (!single_launch(cx.route)) return begin_enqueued(s, cx);
@@ -3601,7 +3219,7 @@ int run_extra_trials(tqgpu_solver *s, const Opts &O, Route trials, int &launches
         const int it = s->h_ctrl->iter, t0 = s->h_ctrl->ls_iter;
         if (it != ls_of) { ls_of = it; trial_batch = trial_batch0; }
         for (int t = t0; t < t0 + trial_batch && t <= O.lsMaxIter; t++) {
-            s->w3_post_next = t + 1 >= t0 + trial_batch || t + 1 > O.lsMaxIter;      /* the last of the batch */
+            s->w3.post_next = t + 1 >= t0 + trial_batch || t + 1 > O.lsMaxIter;      /* the last of the batch */
             int rcx = launch_trial(s, O, trials, it, t, launches);
             if (rcx != TQGPU_OK) return rcx;
         }
@@ -3659,14 +3277,14 @@ int end_enqueued(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, int &host_i
     int h = 0, ev_idx = 0;
     bool finished = o->maxIter <= 0;       /* nothing to iterate: reported as "maximum iterations" */
     if (finished) { HIP_TRY(hipStreamSynchronize(st)); memset(s->h_ctrl, 0, sizeof(Ctrl)); s->h_ctrl->status = 1; }
-    if (o->profile) HIP_TRY(hipEventRecord(s->iter_ev[0], st));
-    int chunk = s->last_iter > 0 ? std::min(s->last_iter + 1, 16) : s->chunk;
+    if (o->profile) HIP_TRY(hipEventRecord(s->tm.iter_ev[0], st));
+    int chunk = s->last_iter > 0 ? std::min(s->last_iter + 1, 16) : s->pp.chunk;
     bool predicted = s->last_iter > 0 && generic;     /* the chunk is a prediction: its last iteration should only find convergence */
     /* a line search that wants a second trial turns everything enqueued behind it into no-ops (~3 us a launch): a problem that
      * backtracked last time is fed two iterations at a time (TREEQP_AMD_LS_CHUNK; one C5-class tree: 1.15 ms with chunks of 8, 1.04 / 1.01 / 1.06 ms with 4 / 2 / 1),
      * a read-back per chunk instead */
     const int ls_chunk = process_switches().ls_chunk;
-    if (s->last_ls_extra && generic && chunk > ls_chunk && !(route == Route::THREE_LAUNCH && !s->ls_pred.empty())) { chunk = ls_chunk; predicted = false; }      /* (three-launch family: the further trials are predicted too) */
+    if (s->last_ls_extra && generic && chunk > ls_chunk && !(route == Route::THREE_LAUNCH && !s->pp.ls_pred.empty())) { chunk = ls_chunk; predicted = false; }      /* (three-launch family: the further trials are predicted too) */
     if (cx.phases) { chunk = 1; predicted = false; }            /* phase timing: one iteration per read-back, so that every recorded event belongs to work that ran */
     int rest_due = -1;                                          /* iteration whose termination test ran, whose step did not */
     while (!finished) {
@@ -3682,7 +3300,7 @@ int end_enqueued(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, int &host_i
                 const bool last = i == n - 1 || (predicted && i == n - 2);
                 if (parts) launch_generic_iteration(s, O, h + i, launches, parts, cx.phases, last);
             }
-            if (o->profile && ev_idx + 1 < (int)s->iter_ev.size()) HIP_TRY(hipEventRecord(s->iter_ev[++ev_idx], st));
+            if (o->profile && ev_idx + 1 < (int)s->tm.iter_ev.size()) HIP_TRY(hipEventRecord(s->tm.iter_ev[++ev_idx], st));
         }
         int rc = read_ctrl(s);
         if (rc != TQGPU_OK) return rc;
@@ -3690,7 +3308,7 @@ int end_enqueued(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, int &host_i
         if ((rc = run_extra_trials(s, O, route, launches, extra_trials)) != TQGPU_OK) return rc;
         h = s->h_ctrl->iter;
         finished = s->h_ctrl->done != 0;
-        chunk = cx.phases ? 1 : s->chunk;
+        chunk = cx.phases ? 1 : s->pp.chunk;
         predicted = false;
         /* the termination test of the deferred iteration was enqueued behind the FIRST trial of the line search before it: when that
          * line search needed further trials (enqueued above, after the read-back), the test found the search pending and did nothing --
@@ -3705,7 +3323,7 @@ int end_enqueued(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, int &host_i
  * launch's clock (these two wait for the stream), the single launch's clock */
 int solve_device_ms(tqgpu_solver *s, const tqgpu_opts *o, const SolveCtx &cx, bool tail_done, float &ms) {
     hipStream_t st = s->stream;
-    if (!tail_done && cx.route == Route::THREE_LAUNCH && s->w3_mirror && s->w3_seen && !cx.events && !o->profile && !cx.phases) {
+    if (!tail_done && cx.route == Route::THREE_LAUNCH && s->w3.mirror && s->w3.seen && !cx.events && !o->profile && !cx.phases) {
         /* three-launch family: every launch of the solve is accounted for (the last one's tail has posted the verdict; what its other
          * workgroups still write is stream-ordered before anything the host does next): no synchronisation, the device's own clock */
         unsigned long long t_first;
@@ -3736,39 +3354,39 @@ int finish_solve(tqgpu_solver *s, const tqgpu_opts *o, SolveCtx &cx, tqgpu_resul
 
     if (cx.phases) {
         float t = 0.f;
-        if (hipEventElapsedTime(&t, s->sweep_ev0, s->sweep_ev1) == hipSuccess) s->first_sweep_time = 1e-3 * t;
-        for (int i = 0; i < host_iter && (size_t)(4 * i + 3) < s->phase_ev.size() && (size_t)(3 * i + 2) < s->phase_times.size(); i++)
+        if (hipEventElapsedTime(&t, s->tm.sweep_ev0, s->tm.sweep_ev1) == hipSuccess) s->tm.first_sweep_time = 1e-3 * t;
+        for (int i = 0; i < host_iter && (size_t)(4 * i + 3) < s->tm.phase_ev.size() && (size_t)(3 * i + 2) < s->tm.phase_times.size(); i++)
             for (int ph = 0; ph < 3; ph++)
-                if (hipEventElapsedTime(&t, s->phase_ev[(size_t)(4 * i + ph)], s->phase_ev[(size_t)(4 * i + ph + 1)]) == hipSuccess) s->phase_times[(size_t)(3 * i + ph)] = 1e-3 * t;
+                if (hipEventElapsedTime(&t, s->tm.phase_ev[(size_t)(4 * i + ph)], s->tm.phase_ev[(size_t)(4 * i + ph + 1)]) == hipSuccess) s->tm.phase_times[(size_t)(3 * i + ph)] = 1e-3 * t;
     }
     if (o->profile) {
-        for (int i = 0; i < host_iter && i + 1 < (int)s->iter_ev.size() && i < (int)s->iter_times.size(); i++) {
+        for (int i = 0; i < host_iter && i + 1 < (int)s->tm.iter_ev.size() && i < (int)s->tm.iter_times.size(); i++) {
             float t = 0.f;
-            if (hipEventElapsedTime(&t, s->iter_ev[i], s->iter_ev[i + 1]) == hipSuccess) s->iter_times[i] = 1e-3 * t;
+            if (hipEventElapsedTime(&t, s->tm.iter_ev[i], s->tm.iter_ev[i + 1]) == hipSuccess) s->tm.iter_times[i] = 1e-3 * t;
         }
     }
     const Ctrl &c = *s->h_ctrl;
     fill_result(res, c, cx.launches, 1e-3 * ms);
     s->last_iter = c.iter;
     s->last_ls_extra = c.ls_total > c.iter ? 1 : 0;
-    if (cx.route == Route::THREE_LAUNCH && s->w3_merge && c.status == 2 && s->T.Np > 1) {
+    if (cx.route == Route::THREE_LAUNCH && s->w3.merge && c.status == 2 && s->T.Np > 1) {
         /* NOT_DESCENT_DIRECTION out of the merged launch (k_sgp mode 2: forward sweep + first trial): the trial sweep ran before the
          * direction test and has put x, u, xUnc, QinvCal of the point lambda + dlambda in place.  The reference returns from
          * line_search with the phase-S iterate at lambda (dual_Newton_tree.c:944-954): one stage sweep at the current duals (which the
          * trial did not touch: it wrote the other buffer) restores exactly that -- same arithmetic, operation for operation. */
-        hipLaunchKernelGGL(k_stage, dim3(s->T.Nn), dim3(WAVE), s->lds_stage, st, s->T, s->D, 0, 0, 0);
+        hipLaunchKernelGGL(k_stage, dim3(s->T.Nn), dim3(WAVE), s->pp.lds_stage, st, s->T, s->D, 0, 0, 0);
         res->n_launches = ++cx.launches;
-        s->stream_pending = true;
+        s->links.stream_pending = true;
     }
     if (cx.route == Route::THREE_LAUNCH) {
-        s->ls_pred.clear();
+        s->pp.ls_pred.clear();
         if (c.status == 0 && c.ls_total > c.iter) {
             /* some iteration needed further trials: fetch the trial counts (only then: a copy is a packet on the queue and a synchronisation) */
             const int nlog = std::min(c.iter, std::min(s->ls_log_cap, 256));
             HIP_TRY(hipMemcpyAsync(s->h_ls_log, s->D.ls_log, sizeof(int) * (size_t)nlog, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             MPC_COUNT(copies, 1); MPC_COUNT(waits, 1);
-            s->ls_pred.assign(s->h_ls_log, s->h_ls_log + nlog);
+            s->pp.ls_pred.assign(s->h_ls_log, s->h_ls_log + nlog);
         }
     }
     return TQGPU_OK;
@@ -3794,13 +3412,13 @@ constexpr int PERSIST_BACKOFF = 1000;
 
 static int solve_after_timeout(tqgpu_solver *s, const tqgpu_opts *o, const SolveEnv &env, tqgpu_result *res) {
     if (int rc = clear_timeout_word(s)) return rc;
-    s->use_persist = 0;
-    s->persist_backoff = PERSIST_BACKOFF;
-    s->n_timeouts++;
+    s->persist.use = 0;
+    s->persist.backoff = PERSIST_BACKOFF;
+    s->persist.n_timeouts++;
     if (getenv("TREEQP_AMD_VERBOSE")) fprintf(stderr, "[treeqp_amd] persistent launch timed out (device shared?): solving on the launch-per-tier path\n");
     s->warm.fresh = true;                              /* from the same starting duals: the start buffer holds them, whatever the warm-start mode */
     if (s->shift.restore == 2) s->shift.restore = 1;   /* (... also where tqgpu_mpc_shift put them there for this solve) */
-    SolveCtx cx(env, route_of(s, o, false));          /* a fresh decision: use_persist is off now */
+    SolveCtx cx(env, route_of(s, o, false));          /* a fresh decision: persist.use is off now */
     int rc = solve_begin(s, o, cx);
     if (rc != TQGPU_OK) return rc;
     return solve_end(s, o, cx, res);
@@ -3814,7 +3432,7 @@ extern "C" int tqgpu_solve(tqgpu_solver *s, const tqgpu_opts *o, tqgpu_result *r
     /* a mirror that is one rank's share of a sharded solve launches only that share: on its own it would time out, and its launch number
      * would fall out of step with its peers' */
     if (s->pshard.on && s->shard.nranks > 1) return fail(TQGPU_EINVAL, "tqgpu_solve: this mirror is rank " + std::to_string(s->shard.rank) + " of a sharded solve (tqgpu_pshard_init): use tqgpu_pshard_begin / _end");
-    if (s->persist_backoff > 0 && --s->persist_backoff == 0) s->use_persist = s->use_persist_orig;
+    if (s->persist.backoff > 0 && --s->persist.backoff == 0) s->persist.use = s->persist.use_orig;
     SolveCtx cx(read_solve_env(false), route_of(s, o, false));
     int rc = solve_begin(s, o, cx);
     if (rc != TQGPU_OK) return rc;
@@ -3892,18 +3510,18 @@ extern "C" int tqgpu_debug_occupy_wait(void) {
 extern "C" int tqgpu_geometry(const tqgpu_solver *s, int *levels, int *tiers, int *workgroups, int *capacity, int *compute_units) {
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     if (levels) *levels = s->Nh;
-    if (tiers) *tiers = s->fast >= 0 ? s->n_tiers : 0;
-    if (workgroups) *workgroups = s->persist_ok ? s->geom.G : 0;
-    if (capacity) *capacity = s->persist_ok ? s->co_capacity : 0;
+    if (tiers) *tiers = s->uni.fast >= 0 ? s->uni.n_tiers : 0;
+    if (workgroups) *workgroups = s->persist.ok ? s->persist.geom.G : 0;
+    if (capacity) *capacity = s->persist.ok ? s->persist.co_capacity : 0;
     if (compute_units) *compute_units = s->n_cu;
     return TQGPU_OK;
 }
 
 /* diagnostic: how often a persistent launch of this mirror timed out and the solve was redone on another path */
-extern "C" int tqgpu_timeouts(const tqgpu_solver *s) { return s ? s->n_timeouts : 0; }
+extern "C" int tqgpu_timeouts(const tqgpu_solver *s) { return s ? s->persist.n_timeouts : 0; }
 
 static int batch_kernel_index(const tqgpu_solver *s) {
-#define X(idx, nx, nu, md, ms) if (s->fNX == nx && s->fNU == nu && s->fMD == md && s->mstage == ms) return idx;
+#define X(idx, nx, nu, md, ms) if (s->uni.fNX == nx && s->uni.fNU == nu && s->uni.fMD == md && s->uni.mstage == ms) return idx;
     BATCH_TABLE(X)
 #undef X
     return -1;
@@ -3971,15 +3589,15 @@ struct LeadOrder { bool step_drains, skip_waited, behind_wait; };
 static int order_behind_lead(tqgpu_solver *s, const tqgpu_solver *lead, long &drained_at, LeadOrder rule, std::vector<hipStream_t> &waited, int &waits) {
     auto was_waited_for = [&](hipStream_t t) { return t && std::find(waited.begin(), waited.end(), t) != waited.end(); };
     const bool drained = rule.step_drains && s->solve_no == s->mpcb.drained_at;
-    const bool in_launch = s->settle_stream != nullptr;          /* its last solve was part of a batch launch that has not been waited for */
+    const bool in_launch = s->links.settle_stream != nullptr;          /* its last solve was part of a batch launch that has not been waited for */
     if (rule.behind_wait) SETTLE(s);
-    else if (drained || s->settle_stream == lead->stream || was_waited_for(s->settle_stream)) s->settle_stream = nullptr;
-    else if (in_launch) { if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); waits++; } SETTLE(s); }
+    else if (drained || s->links.settle_stream == lead->stream || was_waited_for(s->links.settle_stream)) s->links.settle_stream = nullptr;
+    else if (in_launch) { if (s->links.settle_stream != s->stream) { waited.push_back(s->links.settle_stream); waits++; } SETTLE(s); }
     const bool own_solve = !in_launch && !drained && s->solve_no != drained_at;
-    const bool own_work = s->stream_pending || (!rule.behind_wait && (s->out.valid || own_solve));
+    const bool own_work = s->links.stream_pending || (!rule.behind_wait && (s->out.valid || own_solve));
     if (s->stream != lead->stream && !(rule.skip_waited && was_waited_for(s->stream)) && own_work) {
         HIP_TRY(hipStreamSynchronize(s->stream));
-        s->stream_pending = false;
+        s->links.stream_pending = false;
         waited.push_back(s->stream);
         waits++;
     }
@@ -3988,14 +3606,14 @@ static int order_behind_lead(tqgpu_solver *s, const tqgpu_solver *lead, long &dr
 }
 constexpr LeadOrder KKT_ORDER{false, false, false}, ADJ_ORDER{true, true, false}, ADJMAT_ORDER{false, false, true};
 static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
-    const int G = lead->geom.G;
+    const int G = lead->persist.geom.G;
     const ProcessSwitches &ps = process_switches();
     const int batch_nap = ps.has_nap ? ps.nap : nap_for_grid(G * n_trees);     /* the whole launch polls the same memory system */
     static size_t lds_allowed[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     switch (kidx) {
 #define X(idx, nx, nu, md, ms) case idx: { \
-        if (lds_allowed[idx] < lead->lds_persist) { int rc = allow_lds(f_persist_batch<nx, nu, md, ms>, lead->lds_persist); if (rc != TQGPU_OK) return rc; lds_allowed[idx] = lead->lds_persist; } \
-        hipLaunchKernelGGL((f_persist_batch<nx, nu, md, ms>), dim3((unsigned)(G * n_trees)), dim3(FW * WAVE), lead->lds_persist, lead->stream, items, O, G, seq, batch_nap); break; }
+        if (lds_allowed[idx] < lead->persist.lds) { int rc = allow_lds(f_persist_batch<nx, nu, md, ms>, lead->persist.lds); if (rc != TQGPU_OK) return rc; lds_allowed[idx] = lead->persist.lds; } \
+        hipLaunchKernelGGL((f_persist_batch<nx, nu, md, ms>), dim3((unsigned)(G * n_trees)), dim3(FW * WAVE), lead->persist.lds, lead->stream, items, O, G, seq, batch_nap); break; }
         BATCH_TABLE(X)
 #undef X
         default: return fail(TQGPU_EINVAL, "no batch kernel for this shape");
@@ -4035,7 +3653,7 @@ static std::vector<BatchMember> plan_members(tqgpu_solver **solvers, int n, cons
         m.kidx = m.plan == Route::PERSIST && o->checkLastActiveSet != 2 ? batch_kernel_index(s) : -1;
         /* single-workgroup mirrors do not wait for each other: any number per launch; launch-per-level mirrors go alone */
         /* (a SINGLE_WG plan counts 0 even where batch_route sends the member to a launch-per-level route in the end) */
-        m.need = m.plan == Route::PERSIST ? s->geom.G : (m.plan == Route::SINGLE_WG ? 0 : s->co_capacity + 1);
+        m.need = m.plan == Route::PERSIST ? s->persist.geom.G : (m.plan == Route::SINGLE_WG ? 0 : s->persist.co_capacity + 1);
     }
     return tab;
 }
@@ -4052,7 +3670,7 @@ static int wave_end(const std::vector<BatchMember> &tab, int i, const SolveEnv &
          * a tree's waves are parked at barriers and waits two thirds of the time, and trees that share CUs fill those gaps
          * (C2: 3 trees 72 k it/s, 5 trees 98 k; C1: 22 trees 656 k, 38 trees 922 k). */
         const bool one_launch = m.kidx >= 0 && !env.batch_launches;
-        const int cap = (!one_launch && s->n_cu > 0 && m.need <= s->n_cu) ? std::min(s->co_capacity, s->n_cu) : s->co_capacity;
+        const int cap = (!one_launch && s->n_cu > 0 && m.need <= s->n_cu) ? std::min(s->persist.co_capacity, s->n_cu) : s->persist.co_capacity;
         if (j > i && (s->device != dev || used + m.need > cap)) break;
         used += m.need;
     }
@@ -4079,7 +3697,7 @@ static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveE
         const BatchMember &m = tab[(size_t)k];
         if (m.kidx < 0) continue;
         if (!f) f = &m;
-        if (m.kidx == f->kidx && m.s->geom.G == f->s->geom.G && m.s->lds_persist == f->s->lds_persist && m.s->Nn == f->s->Nn) pg.members.push_back(k);
+        if (m.kidx == f->kidx && m.s->persist.geom.G == f->s->persist.geom.G && m.s->persist.lds == f->s->persist.lds && m.s->Nn == f->s->Nn) pg.members.push_back(k);
     }
     if (pg.members.size() < 2 || env.batch_launches) pg.members.clear();      /* (=1: one launch per tree, the round-1 protocol) */
     for (int k : wg.members) tab[(size_t)k].in_single_wg = true;
@@ -4090,7 +3708,7 @@ static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveE
     if (!pg.members.empty()) pg.lead = tab[(size_t)pg.members[0]].s;
     /* (the single-workgroup members describe their launches into the array as they begin) */
     for (BatchGroup *g : {&wg, &dg})
-        if (g->lead) if (int rc = grow_items(g->lead, g->lead->d_gitems, g->lead->h_gitems, g->lead->gitems_cap, g->members.size())) return rc;
+        if (g->lead) if (int rc = grow_items(g->lead, g->lead->gp.d_gitems, g->lead->gp.h_gitems, g->lead->gp.gitems_cap, g->members.size())) return rc;
     return TQGPU_OK;
 }
 
@@ -4100,7 +3718,7 @@ static int settle_wave(std::vector<BatchMember> &tab, int i, int j, const BatchG
         const BatchMember &m = tab[(size_t)k];
         const BatchGroup *g = group_of(m, wg, dg, pg);
         /* a member of the previous batch launch that goes out again on the same lead's stream is ordered behind it by that stream */
-        if (g && m.s->settle_stream == g->lead->stream) { if (k == g->members[0]) m.s->settle_stream = nullptr; }
+        if (g && m.s->links.settle_stream == g->lead->stream) { if (k == g->members[0]) m.s->links.settle_stream = nullptr; }
         else SETTLE(m.s);
     }
     return TQGPU_OK;
@@ -4111,14 +3729,14 @@ static int persist_group_seq(std::vector<BatchMember> &tab, const BatchGroup &pg
     pseq = 0;
     if (!pg.lead) return TQGPU_OK;
     unsigned mx = 0;
-    for (int k : pg.members) mx = std::max(mx, tab[(size_t)k].s->launch_no);
+    for (int k : pg.members) mx = std::max(mx, tab[(size_t)k].s->persist.launch_no);
     unsigned nn = mx + 1;
     if (nn > 0xFFFFu) {          /* the 16-bit launch number wraps: see launch_persist */
         HIP_TRY(hipStreamSynchronize(pg.lead->stream));      /* (the previous batch launch's last workgroups are done with the slabs) */
         for (int k : pg.members) {
             tqgpu_solver *s = tab[(size_t)k].s;
-            HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
-            s->stream_pending = true;          /* the batch launch (on the lead's stream) waits for the wipe */
+            HIP_TRY(hipMemsetAsync(s->persist.sync_slab, 0, s->persist.sync_bytes, s->stream));
+            s->links.stream_pending = true;          /* the batch launch (on the lead's stream) waits for the wipe */
         }
         nn = 1;
     }
@@ -4136,9 +3754,9 @@ static int persist_group_seq(std::vector<BatchMember> &tab, const BatchGroup &pg
 static int join_lead_stream(std::vector<BatchMember> &tab, const BatchGroup &g, size_t n) {
     for (size_t m = 1; m < n; m++) {
         tqgpu_solver *sm = tab[(size_t)g.members[m]].s;
-        if (sm->stream_pending) { HIP_TRY(hipStreamSynchronize(sm->stream)); sm->stream_pending = false; }
+        if (sm->links.stream_pending) { HIP_TRY(hipStreamSynchronize(sm->stream)); sm->links.stream_pending = false; }
     }
-    for (size_t m = 0; m < n; m++) tab[(size_t)g.members[m]].s->batch_stream = g.lead->stream;
+    for (size_t m = 0; m < n; m++) tab[(size_t)g.members[m]].s->links.batch_stream = g.lead->stream;
     return TQGPU_OK;
 }
 
@@ -4146,12 +3764,12 @@ static int join_lead_stream(std::vector<BatchMember> &tab, const BatchGroup &g, 
 static int launch_single_wg_group(std::vector<BatchMember> &tab, BatchGroup &wg, size_t n) {
     tqgpu_solver *lead = wg.lead;
     size_t lds_batch = 0;
-    for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)wg.members[m]].s->lds_gp_total);
+    for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)wg.members[m]].s->gp.lds_total);
     int rc = join_lead_stream(tab, wg, n);
     if (rc != TQGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(lead->d_gitems, lead->h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));
+    HIP_TRY(hipMemcpyAsync(lead->gp.d_gitems, lead->gp.h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));
     if (lds_batch > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(g_persist_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_batch));
-    hipLaunchKernelGGL(g_persist_batch, dim3((unsigned)n), dim3(GP_WAVES * WAVE), lds_batch, lead->stream, lead->d_gitems, tab[(size_t)wg.members[0]].cx.O);
+    hipLaunchKernelGGL(g_persist_batch, dim3((unsigned)n), dim3(GP_WAVES * WAVE), lds_batch, lead->stream, lead->gp.d_gitems, tab[(size_t)wg.members[0]].cx.O);
     wg.launched = n;
     return TQGPU_OK;
 }
@@ -4165,9 +3783,9 @@ static int launch_dense_wg_group(std::vector<BatchMember> &tab, BatchGroup &dg, 
     for (size_t m = 0; m < n; m++) lds_batch = std::max(lds_batch, tab[(size_t)dg.members[m]].s->gpd.lds_total);
     int rc = join_lead_stream(tab, dg, n);
     if (rc != TQGPU_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(lead->d_gitems, lead->h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));
+    HIP_TRY(hipMemcpyAsync(lead->gp.d_gitems, lead->gp.h_gitems, n * sizeof(GItem), hipMemcpyHostToDevice, lead->stream));
     if ((rc = allow_lds(g_persist_dense_batch, lds_batch)) != TQGPU_OK) return rc;      /* (plan_dense_single asked the same of g_persist_dense for every member) */
-    hipLaunchKernelGGL(g_persist_dense_batch, dim3((unsigned)n), dim3(GPD_WAVES * WAVE), lds_batch, lead->stream, lead->d_gitems, tab[(size_t)dg.members[0]].cx.O);
+    hipLaunchKernelGGL(g_persist_dense_batch, dim3((unsigned)n), dim3(GPD_WAVES * WAVE), lds_batch, lead->stream, lead->gp.d_gitems, tab[(size_t)dg.members[0]].cx.O);
     dg.launched = n;
     return TQGPU_OK;
 }
@@ -4176,22 +3794,22 @@ static int launch_dense_wg_group(std::vector<BatchMember> &tab, BatchGroup &dg, 
 static int launch_persist_group(std::vector<BatchMember> &tab, BatchGroup &pg, unsigned pseq) {
     tqgpu_solver *pl = pg.lead;
     const size_t np = pg.members.size();
-    if (pl->pitems_cap < (int)np) pl->pitems_key.clear();
-    if (int rc = grow_items(pl, pl->d_pitems, pl->h_pitems, pl->pitems_cap, np)) return rc;
+    if (pl->persist.pitems_cap < (int)np) pl->persist.pitems_key.clear();
+    if (int rc = grow_items(pl, pl->persist.d_pitems, pl->persist.h_pitems, pl->persist.pitems_cap, np)) return rc;
     std::vector<unsigned long> key;
     for (int k : pg.members) key.push_back(tab[(size_t)k].s->uid);
-    if (key != pl->pitems_key) {
+    if (key != pl->persist.pitems_key) {
         /* the descriptors are what the single launches pass as kernel arguments; they do not change from solve to solve, so
          * the device copy is refreshed only when the batch is composed of other mirrors than last time */
         HIP_TRY(hipStreamSynchronize(pl->stream));                 /* a previous batch launch may still read the array */
-        for (size_t m = 0; m < np; m++) { const tqgpu_solver *sm = tab[(size_t)pg.members[m]].s; pl->h_pitems[m].C = sm->pconst; pl->h_pitems[m].Gm = sm->geom; pl->h_pitems[m].Sy = sm->psync; }
-        HIP_TRY(hipMemcpyAsync(pl->d_pitems, pl->h_pitems, np * sizeof(PItem), hipMemcpyHostToDevice, pl->stream));
-        pl->pitems_key = key;
+        for (size_t m = 0; m < np; m++) { const tqgpu_solver *sm = tab[(size_t)pg.members[m]].s; pl->persist.h_pitems[m].C = sm->persist.pconst; pl->persist.h_pitems[m].Gm = sm->persist.geom; pl->persist.h_pitems[m].Sy = sm->persist.psync; }
+        HIP_TRY(hipMemcpyAsync(pl->persist.d_pitems, pl->persist.h_pitems, np * sizeof(PItem), hipMemcpyHostToDevice, pl->stream));
+        pl->persist.pitems_key = key;
     }
     int rc = join_lead_stream(tab, pg, np);
     if (rc != TQGPU_OK) return rc;
     const BatchMember &lead = tab[(size_t)pg.members[0]];
-    if ((rc = launch_persist_batch(pl, lead.kidx, pl->d_pitems, lead.cx.O, (int)np, pseq)) != TQGPU_OK) return rc;
+    if ((rc = launch_persist_batch(pl, lead.kidx, pl->persist.d_pitems, lead.cx.O, (int)np, pseq)) != TQGPU_OK) return rc;
     pg.launched = np;
     return TQGPU_OK;
 }
@@ -4202,17 +3820,17 @@ static int launch_persist_group(std::vector<BatchMember> &tab, BatchGroup &pg, u
 static int hand_over(std::vector<BatchMember> &tab, const BatchGroup &g, bool sync) {
     if (!g.launched) return TQGPU_OK;
     if (sync) HIP_TRY(hipStreamSynchronize(g.lead->stream));
-    else for (size_t m = 1; m < g.launched; m++) tab[(size_t)g.members[m]].s->settle_stream = g.lead->stream;      /* see settle() */
+    else for (size_t m = 1; m < g.launched; m++) tab[(size_t)g.members[m]].s->links.settle_stream = g.lead->stream;      /* see settle() */
     return TQGPU_OK;
 }
 
-/* the per-call state a batch leaves on its members, taken back on EVERY exit: in_batch (see tqgpu_solver::in_batch) on all of them,
+/* the per-call state a batch leaves on its members, taken back on EVERY exit: in_batch (see BatchLinks::in_batch) on all of them,
  * batch_stream on those of the current wave (wait_result_block and the redo after a timeout read it while the wave is in flight) */
 struct BatchGuard {
     tqgpu_solver **v; int n, w0 = 0, w1 = 0;
-    BatchGuard(tqgpu_solver **v_, int n_) : v(v_), n(n_) { for (int i = 0; i < n; i++) v[i]->in_batch = true; }
-    void wave(int i, int j) { for (int k = w0; k < w1; k++) v[k]->batch_stream = nullptr; w0 = i; w1 = j; }
-    ~BatchGuard() { wave(0, 0); for (int i = 0; i < n; i++) v[i]->in_batch = false; }
+    BatchGuard(tqgpu_solver **v_, int n_) : v(v_), n(n_) { for (int i = 0; i < n; i++) v[i]->links.in_batch = true; }
+    void wave(int i, int j) { for (int k = w0; k < w1; k++) v[k]->links.batch_stream = nullptr; w0 = i; w1 = j; }
+    ~BatchGuard() { wave(0, 0); for (int i = 0; i < n; i++) v[i]->links.in_batch = false; }
 };
 
 /* Batched multi-tree solve (the usage pattern of examples/fault_tolerance.c:486-530, one QP per
@@ -4234,9 +3852,9 @@ static int solve_batch_impl(tqgpu_solver **solvers, int n, const tqgpu_opts *o, 
     const SolveEnv env = read_solve_env(true);
     for (int k = 0; k < n; k++) {          /* as tqgpu_solve: a mirror that backed off the persistent path returns to it after PERSIST_BACKOFF solves */
         tqgpu_solver *sk = solvers[k];
-        if (sk->persist_backoff > 0 && --sk->persist_backoff == 0) sk->use_persist = sk->use_persist_orig;
+        if (sk->persist.backoff > 0 && --sk->persist.backoff == 0) sk->persist.use = sk->persist.use_orig;
     }
-    std::vector<BatchMember> tab = plan_members(solvers, n, o);          /* (after the loop above: route_of reads use_persist) */
+    std::vector<BatchMember> tab = plan_members(solvers, n, o);          /* (after the loop above: route_of reads persist.use) */
     int first_err = TQGPU_OK, rc;
     std::string first_msg;
     for (int i = 0, j; i < n && first_err == TQGPU_OK; i = j) {
@@ -4252,7 +3870,7 @@ static int solve_batch_impl(tqgpu_solver **solvers, int n, const tqgpu_opts *o, 
             BatchMember &m = tab[(size_t)k];
             m.cx = SolveCtx(env, batch_route(m));
             if (m.in_persist) m.cx.batch_seq = pseq;
-            rc = solve_begin(m.s, o, m.cx, m.in_single_wg ? &wg.lead->h_gitems[gi] : m.in_dense_wg ? &dg.lead->h_gitems[di] : nullptr);
+            rc = solve_begin(m.s, o, m.cx, m.in_single_wg ? &wg.lead->gp.h_gitems[gi] : m.in_dense_wg ? &dg.lead->gp.h_gitems[di] : nullptr);
             if (rc != TQGPU_OK) { first_err = rc; first_msg = g_err; break; }
             if (m.in_single_wg) gi++;
             if (m.in_dense_wg) di++;
@@ -4268,7 +3886,7 @@ static int solve_batch_impl(tqgpu_solver **solvers, int n, const tqgpu_opts *o, 
             if (rc == TQGPU_ETIMEOUT) {
                 /* device shared: redone on its own, see tqgpu_solve.  The redo works on the same device state as the batch launch,
                  * whose later workgroups may not even have started: the launch has to be over before the sticky word is cleared */
-                if (sk->batch_stream) HIP_TRY(hipStreamSynchronize(sk->batch_stream));
+                if (sk->links.batch_stream) HIP_TRY(hipStreamSynchronize(sk->links.batch_stream));
                 rc = solve_after_timeout(sk, o, env, &results[k]);
             }
             if (rc != TQGPU_OK && first_err == TQGPU_OK) { first_err = rc; first_msg = g_err; }
@@ -4314,7 +3932,7 @@ extern "C" int tqgpu_get_iteration_log(tqgpu_solver *s, int *ls_iters, double *i
     }
     for (int i = 0; i < n; i++) {
         if (ls_iters) ls_iters[i] = s->h_ls_log[i];
-        if (iter_times) iter_times[i] = i < (int)s->iter_times.size() ? s->iter_times[i] : NAN;
+        if (iter_times) iter_times[i] = i < (int)s->tm.iter_times.size() ? s->tm.iter_times[i] : NAN;
     }
     return TQGPU_OK;
 }
@@ -4329,11 +3947,11 @@ extern "C" int tqgpu_get_phase_log(tqgpu_solver *s, double *stage_qps, double *b
     if (!s) return fail(TQGPU_EINVAL, "null solver");
     const int n = std::min(cap, s->last_iter);
     for (int i = 0; i < n; i++) {
-        const bool have = (size_t)(3 * i + 2) < s->phase_times.size();
-        if (stage_qps) stage_qps[i] = i == 0 ? s->first_sweep_time : (std::isnan(s->first_sweep_time) ? NAN : 0.0);
-        if (build_dual) build_dual[i] = have ? s->phase_times[(size_t)(3 * i)] : NAN;
-        if (newton_direction) newton_direction[i] = have ? s->phase_times[(size_t)(3 * i + 1)] : NAN;
-        if (line_search) line_search[i] = have ? s->phase_times[(size_t)(3 * i + 2)] : NAN;
+        const bool have = (size_t)(3 * i + 2) < s->tm.phase_times.size();
+        if (stage_qps) stage_qps[i] = i == 0 ? s->tm.first_sweep_time : (std::isnan(s->tm.first_sweep_time) ? NAN : 0.0);
+        if (build_dual) build_dual[i] = have ? s->tm.phase_times[(size_t)(3 * i)] : NAN;
+        if (newton_direction) newton_direction[i] = have ? s->tm.phase_times[(size_t)(3 * i + 1)] : NAN;
+        if (line_search) line_search[i] = have ? s->tm.phase_times[(size_t)(3 * i + 2)] : NAN;
     }
     return n;
 }
@@ -4348,7 +3966,7 @@ extern "C" int tqgpu_get_device_times(tqgpu_solver *s, double *out, int n) {
     for (long i = 0; i < have; i++) {
         const int ring = (int)((s->solve_no - have + i) % EV_RING);
         float ms = 0.f;
-        out[i] = (s->ring_ok[(size_t)ring] && hipEventElapsedTime(&ms, s->ring_ev0[ring], s->ring_ev1[ring]) == hipSuccess) ? 1e-3 * ms : NAN;
+        out[i] = (s->tm.ring_ok[(size_t)ring] && hipEventElapsedTime(&ms, s->tm.ring_ev0[ring], s->tm.ring_ev1[ring]) == hipSuccess) ? 1e-3 * ms : NAN;
     }
     return (int)have;
 }
@@ -4358,7 +3976,7 @@ extern "C" int tqgpu_get_device_times(tqgpu_solver *s, double *out, int n) {
  * kernel's own clock (launch start to verdict) either way.  The other paths always record (their device time IS the pair). */
 extern "C" int tqgpu_set_event_timing(tqgpu_solver *s, int on) {
     if (!s) return fail(TQGPU_EINVAL, "null solver");
-    s->ev_timing = on != 0;
+    s->tm.ev_timing = on != 0;
     return TQGPU_OK;
 }
 

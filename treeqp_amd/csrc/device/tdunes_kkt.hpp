@@ -2,8 +2,8 @@
  * tdunes_kkt.hpp -- the solution's way out and its check, in the host part: the export kernels (k_export_all, k_export_box, k_export_gen), the KKT
  * kernels (k_kkt, k_kkt_max), their batch forms behind KItem / KHead, and the entry points tqgpu_set_export_ahead, tqgpu_get_solution,
  * tqgpu_kkt_residual, _at, _batch and tqgpu_kkt_batch_stats.  Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind the batch
- * solve and ahead of tdunes_mpc.hpp, whose certified step calls mpc_enqueue_certificate.  That file keeps the mirror's records Export (s->out:
- * the packed solution and the export state, with its three transitions) and Kkt (s->kkt), and declares enqueue_export for tqgpu_solve.
+ * solve and ahead of tdunes_mpc.hpp, whose certified step calls mpc_enqueue_certificate.  tdunes_mirror.hpp keeps the mirror's records Export (s->out:
+ * the packed solution and the export state, with its three transitions) and Kkt (s->kkt); tdunes_device.hip declares enqueue_export for tqgpu_solve.
  */
 #pragma once
 
@@ -414,7 +414,7 @@ constexpr size_t KKT_GRID_Y = 65535;             /* blockIdx.y is the member */
 
 /* one member on its own stream: the route of tqgpu_kkt_residual without the wait */
 int kkt_member_enqueue(tqgpu_solver *s, KktBatchStats &st) {
-    if (s->settle_stream && s->settle_stream != s->stream) st.waits++;
+    if (s->links.settle_stream && s->links.settle_stream != s->stream) st.waits++;
     SETTLE(s);
     st.launches += (s->out.valid ? 0 : export_launches(s)) + 2;
     st.copies++;

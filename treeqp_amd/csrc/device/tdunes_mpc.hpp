@@ -1,7 +1,7 @@
 /*
  * tdunes_mpc.hpp -- the MPC family of the host part: kernels (k_mpc_pre, k_mpc_post, their batch forms), the plan and launcher of k_mpc_pre,
  * the entry points tqgpu_mpc_* of the step, its batch, the root forms, tracking, warm start and shift.  Included once from tdunes_device.hip inside
- * #if TQ_HAS(TQP_HOST), behind the batch solve.  That file keeps what the solve path uses: the mirror's records MpcRoot .. MpcTrack, MpcStats / MPC_COUNT,
+ * #if TQ_HAS(TQP_HOST), behind the batch solve.  That file keeps what the solve path uses: the mirror's records MpcRoot .. MpcTrack (in tdunes_mirror.hpp), MpcStats / MPC_COUNT,
  * MpcPre, mpc_warm_due, problem_changed, and the declarations mpc_before_wave / mpc_behind_launches / mpc_after_wave, the seam to the batch step.
  * The derivatives of a step (sensitivities, adjoints) are tdunes_adjoint.hpp's, included behind this file.
  */
@@ -289,7 +289,7 @@ MItem mpc_item(const tqgpu_solver *s, MpcPre pre) {
     if (s->mpc.states) {
         /* the packed constants hold a copy of the bounds (k_pack_persist); no other route keeps one: they read Data::xmin / xmax at every launch */
         it.xlo = s->xmin; it.xhi = s->xmax;
-        it.cst = s->persist_ok && s->pcst && !s->need_pack ? s->pcst : nullptr;
+        it.cst = s->persist.ok && s->persist.pcst && !s->persist.need_pack ? s->persist.pcst : nullptr;
     }
     it.b = s->b; it.r = s->r;
     it.dmin = s->mpc.C0 ? s->rows.d_drange : nullptr; it.dmax = s->mpc.C0 ? s->rows.d_drange + s->rows.sum_nc : nullptr;
@@ -316,7 +316,7 @@ MItem mpc_item(const tqgpu_solver *s, MpcPre pre) {
         it.stage = reinterpret_cast<const int *>(p);
         it.q = s->q;
         /* the packed constants hold a copy of q, r (k_pack_persist); every other route reads Data::q / r in place at every launch */
-        it.pcq = s->persist_ok && s->pcst && !s->need_pack ? s->pcst : nullptr;
+        it.pcq = s->persist.ok && s->persist.pcst && !s->persist.need_pack ? s->persist.pcst : nullptr;
         it.trk = pre.track ? 1 : 0; it.t0 = s->trk.t0; it.Tn = s->trk.T; it.nxt = s->trk.nxt; it.nut = s->trk.nut; it.xpad = s->x_pad;
     }
     return it;
@@ -334,7 +334,7 @@ int launch_mpc_pre(tqgpu_solver *s, MpcPre p, int *solve_launches = nullptr) {
     HIP_TRY(hipGetLastError());
     if (solve_launches) ++*solve_launches; else MPC_COUNT(launches, 1);
     if (p.warm) s->lam_valid = false;          /* the pinned mirror of tqgpu_set_problem's duals no longer describes the start buffer */
-    s->stream_pending = true;
+    s->links.stream_pending = true;
     return TQGPU_OK;
 }
 
@@ -349,7 +349,7 @@ int mpc_take_window(tqgpu_solver *s, int t0, bool commit, const char *who) {
     if (!commit) return TQGPU_OK;
     s->trk.t0 = t0;
     problem_changed(s, false);              /* the pinned mirror of tqgpu_set_problem no longer describes q, r */
-    return TQGPU_OK;                        /* need_pack stays as it is: the fold writes the packed copy itself, a pending pack reads Data */
+    return TQGPU_OK;                        /* persist.need_pack stays as it is: the fold writes the packed copy itself, a pending pack reads Data */
 }
 
 /* a new x0 into the mirror's pinned buffer, and what the fold makes stale on the host side; nothing is enqueued */
@@ -365,7 +365,7 @@ int mpc_take_x0(tqgpu_solver *s, const double *x0, const char *who) {
             std::copy(x0, x0 + n0, s->sk.h_bounds.begin());
             std::copy(x0, x0 + n0, s->sk.h_bounds.begin() + s->sum_nx);
         }
-        return TQGPU_OK;                        /* need_pack stays as it is: the fold writes the packed copy itself */
+        return TQGPU_OK;                        /* persist.need_pack stays as it is: the fold writes the packed copy itself */
     }
     if (s->mpc.C0 && (s->rows.nc.empty() || s->rows.nc[0] != s->mpc.nc0 || !s->rows.d_drange))
         return fail(TQGPU_EINVAL, std::string(who) + ": the rows of the root were redefined after tqgpu_mpc_set_root (call it again)");
@@ -771,7 +771,7 @@ static int mpc_step_impl(tqgpu_solver *s, const double *x0, int t0, const tqgpu_
     const MpcPre pre{.fold = x0 != nullptr, .warm = mpc_warm_due(s), .track = t0 >= 0};
     if ((pre.fold || pre.warm || pre.track) && (rc = launch_mpc_pre(s, pre))) return rc;
     s->warm.fresh = true;          /* the start buffer is ready: solve_begin copies nothing */
-    if (s->persist_backoff > 0 && --s->persist_backoff == 0) s->use_persist = s->use_persist_orig;
+    if (s->persist.backoff > 0 && --s->persist.backoff == 0) s->persist.use = s->persist.use_orig;
     const bool certify = s->mpc.certify;
     s->mpc.cert_valid = false;
     if (certify && (rc = setup_kkt(s, false))) return rc;          /* (allocations, the first time: ahead of the launch) */
@@ -854,7 +854,7 @@ static int mpc_before_wave(MpcBatch &mb, std::vector<BatchMember> &tab, int i, i
     for (int k = i; k < j; k++) {
         const BatchMember &m = tab[(size_t)k];
         elsewhere |= mpc_launch_stream(m, wg, dg, pg) != d->lead->stream;
-        elsewhere |= m.in_persist && m.s->need_pack && m.s->stream != d->lead->stream;
+        elsewhere |= m.in_persist && m.s->persist.need_pack && m.s->stream != d->lead->stream;
     }
     if (elsewhere) { HIP_TRY(hipStreamSynchronize(d->lead->stream)); MPC_COUNT(waits, 1); }
     d->ordered = true;
@@ -926,15 +926,15 @@ static int mpc_step_batch_impl(tqgpu_solver **solvers, int n, const double *x0s,
         size_t u_at = 0;
         for (size_t m = 0; m < nm; m++) {
             tqgpu_solver *s = solvers[d.idx[m]];
-            const bool in_launch = s->settle_stream != nullptr;
-            if (in_launch && s->settle_stream != lead->stream && !waited_for(waited, s->settle_stream)) {
-                if (s->settle_stream != s->stream) { waited.push_back(s->settle_stream); MPC_COUNT(waits, 1); }
+            const bool in_launch = s->links.settle_stream != nullptr;
+            if (in_launch && s->links.settle_stream != lead->stream && !waited_for(waited, s->links.settle_stream)) {
+                if (s->links.settle_stream != s->stream) { waited.push_back(s->links.settle_stream); MPC_COUNT(waits, 1); }
                 SETTLE(s);
             }
             const bool own_solve = !in_launch && s->solve_no != s->mpcb.drained_at;
-            if (s->stream != lead->stream && (s->stream_pending || own_solve)) {
+            if (s->stream != lead->stream && (s->links.stream_pending || own_solve)) {
                 HIP_TRY(hipStreamSynchronize(s->stream));
-                s->stream_pending = false;
+                s->links.stream_pending = false;
                 waited.push_back(s->stream);
                 MPC_COUNT(waits, 1);
             }
@@ -955,7 +955,7 @@ static int mpc_step_batch_impl(tqgpu_solver **solvers, int n, const double *x0s,
             HIP_TRY(hipGetLastError());
             MPC_COUNT(launches, 1);
         }
-        lead->stream_pending = true;
+        lead->links.stream_pending = true;
     }
     rc = solve_batch_impl(solvers, n, o, results, &mb);
     for (int i = 0; i < n; i++) solvers[i]->mpcb.drained_at = solvers[i]->solve_no;          /* (a member that launched on its own stream is waited for below, where the post is made) */
@@ -967,7 +967,7 @@ static int mpc_step_batch_impl(tqgpu_solver **solvers, int n, const double *x0s,
             std::vector<hipStream_t> waited;
             for (int i : d.idx) {
                 tqgpu_solver *s = solvers[i];
-                const hipStream_t t = s->settle_stream ? s->settle_stream : s->stream;
+                const hipStream_t t = s->links.settle_stream ? s->links.settle_stream : s->stream;
                 if (t == d.lead->stream || waited_for(waited, t)) continue;
                 HIP_TRY(hipStreamSynchronize(t));
                 waited.push_back(t);

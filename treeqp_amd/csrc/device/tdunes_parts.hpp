@@ -10,7 +10,7 @@
  */
 #pragma once
 
-#define TQP_HOST    0x001   /* C-ABI host side + launch-per-phase kernels (k_*), k_pack_persist; the problem's setters and getters (tdunes_problem.hpp); the MPC family, k_mpc_pre / k_mpc_post (tdunes_mpc.hpp); the host side of its sensitivities and adjoints, k_adj_export_batch (tdunes_adjoint.hpp); solution export and KKT check, k_export_* / k_kkt* (tdunes_kkt.hpp); the host side of both multi-device modes (tdunes_shard.hpp) */
+#define TQP_HOST    0x001   /* C-ABI host side (the mirror and its records: tdunes_mirror.hpp) + launch-per-phase kernels (k_*), k_pack_persist; the problem's setters and getters (tdunes_problem.hpp); the MPC family, k_mpc_pre / k_mpc_post (tdunes_mpc.hpp); the host side of its sensitivities and adjoints, k_adj_export_batch (tdunes_adjoint.hpp); solution export and KKT check, k_export_* / k_kkt* (tdunes_kkt.hpp); the host side of both multi-device modes (tdunes_shard.hpp) */
 #define TQP_GP      0x002   /* g_persist, g_persist_batch (tdunes_gpersist.hpp) */
 #define TQP_WIDE    0x004   /* k_hess_w, k_factor(_all)_w, k_forward(_all)_w (tdunes_wide.hpp) */
 #define TQP_W3      0x008   /* k_sg, k_sgp_t, k_hf_w, k_fwd3(c) (tdunes_wide3.hpp) */

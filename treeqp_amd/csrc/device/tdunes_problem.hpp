@@ -3,7 +3,7 @@
  * objective (diagonal, dense, mixed kinds), the bounds, the general constraints, the starting duals and the whole clipping QP (tqgpu_set_problem),
  * the getters of the sizes and of the rows' results, the hot-start switch of stage_gen and the two opt-ins of the single-workgroup dense solve.
  * No kernel here.  Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), ahead of the solve and of tdunes_mpc.hpp (problem_changed).
- * That file keeps the mirror's records StageKinds, GenRows, DenseSingle, and allow_lds.
+ * tdunes_mirror.hpp keeps the mirror's records StageKinds, GenRows, DenseSingle; tdunes_device.hip keeps allow_lds.
  */
 #pragma once
 
@@ -21,13 +21,13 @@ extern "C" int tqgpu_dims(const tqgpu_solver *s, int *sum_nx, int *sum_nu, int *
  * sensitivity and the pairing of the last solve's point with the data; repack: the packed constants of the persistent route as well */
 static void problem_changed(tqgpu_solver *s, bool repack) {
     s->in_valid = false;
-    s->sens.invalidate(); s->sens.dirty = true; if (repack) s->need_pack = true;
+    s->sens.invalidate(); s->sens.dirty = true; if (repack) s->persist.need_pack = true;
 }
 /* THE return to the clipping solver (tqgpu_set_objective_diag, tqgpu_set_problem): the dense kinds are off, the fast paths the tree had at
  * creation are back; the kinds, H and the plan of plan_dense_single stay as they were set.  true: the mirror was dense */
 static bool back_to_clipping(tqgpu_solver *s) {
     if (!s->sk.dense) return false;
-    s->sk.dense = false; s->sk.box = false; s->sk.gen = false; s->D.dense = 0; s->use_fast = s->use_fast_orig;
+    s->sk.dense = false; s->sk.box = false; s->sk.gen = false; s->D.dense = 0; s->uni.use_fast = s->uni.use_fast_orig;
     return true;
 }
 
@@ -123,16 +123,16 @@ int apply_kinds(tqgpu_solver *s, const std::vector<int> &req) {
     const std::vector<int> kind_was = s->sk.h_kind;
     s->sk.box = lds_box > 0; s->sk.gen = lds_gen > 0; s->sk.h_kind = kd;
     int rc = check_box_bounds(s);
-    if (rc == TQGPU_OK && s->sk.gen) rc = allow_lds(k_stage_gen, std::max(std::max(s->lds_stage, lds_box), lds_gen));
-    else if (rc == TQGPU_OK && s->sk.box) rc = allow_lds(k_stage_box, std::max(s->lds_stage, lds_box));
+    if (rc == TQGPU_OK && s->sk.gen) rc = allow_lds(k_stage_gen, std::max(std::max(s->pp.lds_stage, lds_box), lds_gen));
+    else if (rc == TQGPU_OK && s->sk.box) rc = allow_lds(k_stage_box, std::max(s->pp.lds_stage, lds_box));
     if (rc != TQGPU_OK) { s->sk.box = box_was; s->sk.gen = gen_was; s->sk.h_kind = kind_was; return rc; }
-    s->sk.lds_box = std::max(s->lds_stage, lds_box);
+    s->sk.lds_box = std::max(s->pp.lds_stage, lds_box);
     s->sk.lds_gen = std::max(s->sk.lds_box, lds_gen);
     s->sk.h_kind_req = req;
     return TQGPU_OK;
 }
 /* The LDS plan of g_persist_dense for the kinds and rows the mirror has now (they decide the stage windows, so this runs where they are
- * set, not at creation).  The window region holds GPD_WAVES windows of the other phases (lds_gp_wave doubles each; fewer waves take
+ * set, not at creation).  The window region holds GPD_WAVES windows of the other phases (gp.lds_wave doubles each; fewer waves take
  * blocks where that many do not fit: the Hessian window of a node with nz = 64 and 40 child states is 40 KiB) or, overlaid,
  * stage_waves windows of the tree's largest stage need (lds_stage / lds_box / lds_gen); behind it the index tables and, while they
  * fit, the state mirror and the constants, as in setup_single_wg.  stage_waves is the largest count <= GPD_WAVES for which the total
@@ -143,11 +143,11 @@ void plan_dense_single(tqgpu_solver *s) {
     constexpr size_t budget = 150 * 1024;
     int widest = 0;
     for (int l = 0; l <= s->Nh; l++) widest = std::max(widest, s->lvl_first[l + 1] - s->lvl_first[l]);
-    const size_t per_wave = s->lds_gp_wave;
+    const size_t per_wave = s->gp.lds_wave;
     if (widest > 6 * GP_WAVES) return;      /* the width test of setup_single_wg */
     /* the level table (setup_single_wg uploads it only for trees g_persist takes; the dense kernel reads the first nodes of the levels, never the groups) */
-    if (!s->d_lvl_first && s->mem.upload(s->d_lvl_first, s->lvl_first.data(), sizeof(int) * s->lvl_first.size(), TQGPU_ENOMEM, "the level table") != TQGPU_OK) return;
-    const size_t win = ((s->sk.gen ? s->sk.lds_gen : s->sk.box ? s->sk.lds_box : s->lds_stage) + 15) / 16 * 2;      /* doubles, even: the windows stay 16-byte aligned */
+    if (!s->gp.d_lvl_first && s->mem.upload(s->gp.d_lvl_first, s->lvl_first.data(), sizeof(int) * s->lvl_first.size(), TQGPU_ENOMEM, "the level table") != TQGPU_OK) return;
+    const size_t win = ((s->sk.gen ? s->sk.lds_gen : s->sk.box ? s->sk.lds_box : s->pp.lds_stage) + 15) / 16 * 2;      /* doubles, even: the windows stay 16-byte aligned */
     auto ev = [](size_t n) { return (n + 1) & ~(size_t)1; };
     const size_t sx = (size_t)s->sum_nx, su = (size_t)s->sum_nu;
     const size_t mirror = 11 * ev(sx) + 5 * ev(su) + 2 * ev((size_t)s->sum_W) + 2 * ev((size_t)s->sum_Ut) + 2 * ev((size_t)s->Nn) + ev(sx + s->Nn + 1);
@@ -239,7 +239,7 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     int rc;
     if ((rc = mixed_kinds(s, kind, kd, lds_dense)) || (rc = allow_lds(k_dense_init, lds_dense)) || (rc = apply_kinds(s, kd))) return rc;
     mixed_weights(s, kd, Q, R, S, H, Qd, Rd);
-    problem_changed(s, false);          /* (dense nodes: no packed constants, use_fast goes to 0 below) */
+    problem_changed(s, false);          /* (dense nodes: no packed constants, uni.use_fast goes to 0 below) */
     H2D(s->sk.d_Hd, H.data(), s->poff[s->Nn]);
     HIP_TRY(hipMemcpyAsync(s->sk.d_kind, s->sk.h_kind.data(), sizeof(int) * (size_t)s->Nn, hipMemcpyHostToDevice, s->stream));      /* ints: not H2D (doubles) */
     H2D(s->q + s->x_pad, q, s->sum_nx - s->x_pad); H2D(s->r, r, s->sum_nu);
@@ -249,7 +249,7 @@ extern "C" int tqgpu_set_objective_mixed(tqgpu_solver *s, const int *kind, const
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->sk.lds_dense = lds_dense;
     s->sk.dense = true; s->sk.need_dense_init = true; s->D.dense = 1; s->need_init = true;
-    s->use_fast = 0;                                       /* per-node dense blocks: generic kernels */
+    s->uni.use_fast = 0;                                       /* per-node dense blocks: generic kernels */
     plan_dense_single(s);
     return TQGPU_OK;
 }
@@ -468,7 +468,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
         if (s->in_valid && memcmp(mir, src, bytes) == 0) return TQGPU_OK;
         memcpy(mir, src, bytes);
         HIP_TRY(hipMemcpyAsync(dev, mir, bytes, hipMemcpyHostToDevice, s->stream));
-        s->stream_pending = true;
+        s->links.stream_pending = true;
         s->sens.invalidate(); s->sens.dirty = true;          /* not problem_changed: the pinned mirror has just been brought up to date, in_valid stays */
         any_pack |= pack; any_init |= init;
         return TQGPU_OK;
@@ -484,7 +484,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
         return rc;
     s->in_valid = A && B && b && Qd && Rd && q && r && xmin && xmax && umin && umax ? true : s->in_valid;
     if (any_init) s->need_init = true;
-    if (any_pack) s->need_pack = true;
+    if (any_pack) s->persist.need_pack = true;
     if (lambda && s->sum_lam > 0) {
         const size_t bytes = sizeof(double) * (size_t)s->sum_lam;
         s->warm.fresh = true;        /* as tqgpu_set_lambda (a warm-start copy since the last upload has cleared lam_valid) */
@@ -492,7 +492,7 @@ extern "C" int tqgpu_set_problem(tqgpu_solver *s, const double *A, const double 
         if (!s->lam_valid || memcmp(s->h_lam, lambda, bytes) != 0) {
             memcpy(s->h_lam, lambda, bytes);
             HIP_TRY(hipMemcpyAsync(s->d_lam_init + s->nx0, s->h_lam, bytes, hipMemcpyHostToDevice, s->stream));
-            s->stream_pending = true;
+            s->links.stream_pending = true;
             s->lam_valid = true;
         }
     }

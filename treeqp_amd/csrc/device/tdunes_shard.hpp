@@ -2,7 +2,7 @@
  * tdunes_shard.hpp -- the two multi-device modes of the host part: the subtree-sharded mode with RCCL (tqgpu_shard_*, tqgpu_solve_virtual_ranks;
  * RcclApi, the ranges the ranks exchange, the two all-gathers, the partition plan and its lists) and the sharded persistent launch (tqgpu_pshard_*).
  * Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind tdunes_mpc.hpp: the entry points need solve_begin's pieces.  That file
- * keeps the mirror's records SubtreeShard (s->shard) and PersistShard (s->pshard), the kernels k_shard_pack1, k_shard_pack2, k_ls_decide_parts,
+ * keeps the mirror's records SubtreeShard (s->shard) and PersistShard (s->pshard) (in tdunes_mirror.hpp), the kernels k_shard_pack1, k_shard_pack2, k_ls_decide_parts,
  * and declares what its launches per tier and tqgpu_destroy call here: shard_desc, shard_exchange, shard_release.
  */
 #pragma once
@@ -47,7 +47,7 @@ constexpr int NCCL_DOUBLE = 8;     /* ncclFloat64 */
 Shard shard_desc(const tqgpu_solver *s, int tier) {
     Shard sh{};
     if (s->shard.on) {
-        if (tier >= 0 && tier <= s->shard.part_top) sh.wg_off = s->shard.rank * (s->tier_grid[tier] / s->shard.nranks);
+        if (tier >= 0 && tier <= s->shard.part_top) sh.wg_off = s->shard.rank * (s->uni.tier_grid[tier] / s->shard.nranks);
         sh.gh_list = s->shard.d_gh_list; sh.gh_n = s->shard.gh_n; sh.gh_counted = s->shard.gh_counted;
         sh.err_src = s->shard.d_xerr;
     }
@@ -61,8 +61,8 @@ struct RangeSpec { double *base; size_t per_rank; };
  * subtree roots and the termination partials; which = 2 (after a trial sweep): {fval, dot} partials and x / QinvCal of the boundary
  * root nodes */
 std::vector<RangeSpec> exchange_ranges(tqgpu_solver *s, int which) {
-    const size_t NX = (size_t)s->fNX, SCH = NX * NX + NX;
-    const size_t f0 = (size_t)uni_first(s->fMD, s->tier_l0[s->shard.part_top]), w = (size_t)(s->tier_grid[s->shard.part_top] / s->shard.nranks);
+    const size_t NX = (size_t)s->uni.fNX, SCH = NX * NX + NX;
+    const size_t f0 = (size_t)uni_first(s->uni.fMD, s->uni.tier_l0[s->shard.part_top]), w = (size_t)(s->uni.tier_grid[s->shard.part_top] / s->shard.nranks);
     if (which == 1) return {{s->D.Sbuf + f0 * SCH, w * SCH}, {s->shard.d_xerr, 1}};
     return {{s->shard.d_xs, 2}, {s->D.x + NX * f0, w * NX}, {s->D.QinvCal + NX * f0, w * NX}};
 }
@@ -70,8 +70,8 @@ std::vector<RangeSpec> exchange_ranges(tqgpu_solver *s, int which) {
 /* the partitioned part of the solution, one set of ranges per node level >= the boundary level: for the gather after a solve */
 std::vector<RangeSpec> solution_ranges(tqgpu_solver *s) {
     std::vector<RangeSpec> out;
-    const int MD = s->fMD, NX = s->fNX, NU = s->fNU, N = s->shard.nranks;
-    const int lb = s->tier_l0[s->shard.part_top];
+    const int MD = s->uni.fMD, NX = s->uni.fNX, NU = s->uni.fNU, N = s->shard.nranks;
+    const int lb = s->uni.tier_l0[s->shard.part_top];
     const Data &D = s->D;
     double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
     for (int l = lb; l <= s->Nh; l++) {
@@ -159,7 +159,7 @@ int shard_plan_host(int MD, int NX, int Nh, const std::vector<int> &tier_l0, con
 int shard_build_lists(tqgpu_solver *s) {
     const int N = s->shard.nranks;
     ShardPlanHost P;
-    int rcp = shard_plan_host(s->fMD, s->fNX, s->Nh, s->tier_l0, s->tier_grid, N, s->shard.rank, P);
+    int rcp = shard_plan_host(s->uni.fMD, s->uni.fNX, s->Nh, s->uni.tier_l0, s->uni.tier_grid, N, s->shard.rank, P);
     if (rcp) return rcp;
     s->shard.part_top = P.part_top;
     s->shard.bnd_b0 = P.bnd_b0; s->shard.bnd_bn = P.bnd_bn; s->shard.bnd_own0 = P.bnd_own0; s->shard.bnd_ownn = P.bnd_ownn;
@@ -240,7 +240,7 @@ extern "C" int tqgpu_shard_init(tqgpu_solver *s, int rank, int nranks, const voi
     /* one rank WITHOUT a communicator = back to the unsharded mirror; one rank WITH one = the sharded code path on a single device
      * (every exchange is a one-rank in-place all-gather): exercises rccl_load / ncclCommInitRank / ncclAllGather where only one GPU exists */
     if (nranks == 1 && !id128) { set_shard(s, 0, 1, false); return TQGPU_OK; }
-    if (s->fast < 0 || !s->use_fast || s->mstage) return fail(TQGPU_EUNSUPPORTED, "sharding needs the fused uniform-tree path");
+    if (s->uni.fast < 0 || !s->uni.use_fast || s->uni.mstage) return fail(TQGPU_EUNSUPPORTED, "sharding needs the fused uniform-tree path");
     set_shard(s, rank, nranks, true);
     s->out.invalidate();
     int rc = shard_build_lists(s);
@@ -283,21 +283,21 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
     SETTLE(s);
     if (!s || nranks < 1 || nranks > 8 || rank < 0 || rank >= nranks) return fail(TQGPU_EINVAL, "tqgpu_pshard_init: bad arguments (1 .. 8 ranks)");
     HIP_TRY(hipSetDevice(s->device));
-    if (!s->persist_ok || s->mstage || s->fast < 0 || !s->use_fast || !s->use_persist) return fail(TQGPU_EUNSUPPORTED, "sharding inside the persistent launch needs the persistent path of a uniform complete tree");
-    if (!shard_instantiated(s->fast)) return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape (SHARD_TABLE)");
-    switch (s->fast) {
-#define X(idx, nx, nu, md) case idx: { int rca = allow_lds(f_persist_sh<nx, nu, md, 1>, s->lds_persist); if (!rca) rca = allow_lds(f_persist_sh<nx, nu, md, 0>, s->lds_persist); if (rca) return rca; } break;
+    if (!s->persist.ok || s->uni.mstage || s->uni.fast < 0 || !s->uni.use_fast || !s->persist.use) return fail(TQGPU_EUNSUPPORTED, "sharding inside the persistent launch needs the persistent path of a uniform complete tree");
+    if (!shard_instantiated(s->uni.fast)) return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape (SHARD_TABLE)");
+    switch (s->uni.fast) {
+#define X(idx, nx, nu, md) case idx: { int rca = allow_lds(f_persist_sh<nx, nu, md, 1>, s->persist.lds); if (!rca) rca = allow_lds(f_persist_sh<nx, nu, md, 0>, s->persist.lds); if (rca) return rca; } break;
         SHARD_TABLE(X)
 #undef X
         default: break;
     }
     int nwg = 0, top = -1;
-    if (tqgpu_pshard_plan(s->fMD, s->Nh, nranks, rank, nullptr, 0, &nwg, &top, nullptr) != 0) return fail(TQGPU_EUNSUPPORTED, "tree too small to shard over this many ranks");
+    if (tqgpu_pshard_plan(s->uni.fMD, s->Nh, nranks, rank, nullptr, 0, &nwg, &top, nullptr) != 0) return fail(TQGPU_EUNSUPPORTED, "tree too small to shard over this many ranks");
     std::vector<int> map((size_t)std::max(nwg, 1));
-    (void)tqgpu_pshard_plan(s->fMD, s->Nh, nranks, rank, map.data(), nwg, &nwg, &top, nullptr);
+    (void)tqgpu_pshard_plan(s->uni.fMD, s->Nh, nranks, rank, map.data(), nwg, &nwg, &top, nullptr);
     map.resize((size_t)nwg);
-    if (nranks == 1) top = s->n_tiers - 1;
-    if ((int)map.size() > s->co_capacity) return fail(TQGPU_EUNSUPPORTED, "this rank's workgroups cannot all be resident");
+    if (nranks == 1) top = s->uni.n_tiers - 1;
+    if ((int)map.size() > s->persist.co_capacity) return fail(TQGPU_EUNSUPPORTED, "this rank's workgroups cannot all be resident");
     s->mem.release(s->pshard.wg_map);
     if (int rc = s->mem.device(s->pshard.wg_map, sizeof(int) * std::max<size_t>(map.size(), 1), TQGPU_ENODEVICE, "this rank's workgroup table")) return rc;
     HIP_TRY(hipMemcpy(s->pshard.wg_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
@@ -310,27 +310,27 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
     s->pshard.sys = !getenv("TREEQP_AMD_PSHARD_AGENT");
     if (!s->pshard.fine && !getenv("TREEQP_AMD_PSHARD_COARSE")) {
         void *fresh = nullptr;
-        if (int rc = s->mem.device(fresh, s->sync_bytes, TQGPU_ENODEVICE, "the fine-grained hand-over slab", Owned::FINE_GRAINED)) return rc;
+        if (int rc = s->mem.device(fresh, s->persist.sync_bytes, TQGPU_ENODEVICE, "the fine-grained hand-over slab", Owned::FINE_GRAINED)) return rc;
         HIP_TRY(hipStreamSynchronize(s->stream));
-        char *ob = static_cast<char *>(s->sync_slab), *nb = static_cast<char *>(fresh);
+        char *ob = static_cast<char *>(s->persist.sync_slab), *nb = static_cast<char *>(fresh);
         auto mv = [&](auto *&q) { if (q) q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(nb + (reinterpret_cast<char *>(q) - ob)); };
-        PSync &Y = s->psync;
+        PSync &Y = s->persist.psync;
         mv(Y.sch); mv(Y.dlt); mv(Y.ndt); mv(Y.parts); mv(Y.errs); mv(Y.cmd); mv(Y.vrd); mv(Y.bparts); mv(Y.sgt); mv(Y.rfl); mv(Y.halt); mv(Y.timeout); mv(Y.base); mv(Y.verdict); mv(Y.anc);
-        s->mem.release(s->sync_slab);
-        s->sync_slab = fresh;
+        s->mem.release(s->persist.sync_slab);
+        s->persist.sync_slab = fresh;
         s->pshard.fine = true;
-        s->pitems_key.clear();                                             /* (a cached batch descriptor would hold the old slab) */
+        s->persist.pitems_key.clear();                                             /* (a cached batch descriptor would hold the old slab) */
     }
     s->out.invalidate();
     s->pshard.on = true; s->shard.rank = rank; s->shard.nranks = nranks; s->shard.part_top = nranks > 1 ? top : -1;
-    s->psync.npeer = nranks;
-    s->psync.anc_local = (nranks == 1 || top >= 1) ? 1 : 0;          /* tiers 0 .. top are dealt over the ranks by contiguous subtree ranges: with top >= 1 a tier-1 workgroup sits with the bottom-tier workgroups below it */
-    s->psync.relay_wg = (rank > 0 && !map.empty()) ? map[0] : -1;          /* ranks without the top workgroup: their first workgroup passes the verdict on to the host */
-    for (int r = 0; r < 8; r++) s->pshard.h_peers[r] = s->psync.base;             /* until connected: own slab */
+    s->persist.psync.npeer = nranks;
+    s->persist.psync.anc_local = (nranks == 1 || top >= 1) ? 1 : 0;          /* tiers 0 .. top are dealt over the ranks by contiguous subtree ranges: with top >= 1 a tier-1 workgroup sits with the bottom-tier workgroups below it */
+    s->persist.psync.relay_wg = (rank > 0 && !map.empty()) ? map[0] : -1;          /* ranks without the top workgroup: their first workgroup passes the verdict on to the host */
+    for (int r = 0; r < 8; r++) s->pshard.h_peers[r] = s->persist.psync.base;             /* until connected: own slab */
     if (int rc = upload_peers(s)) return rc;
-    s->psync.nap = nap_for_grid(s->pshard.G);
-    s->launch_no = 0;
-    HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
+    s->persist.psync.nap = nap_for_grid(s->pshard.G);
+    s->persist.launch_no = 0;
+    HIP_TRY(hipMemsetAsync(s->persist.sync_slab, 0, s->persist.sync_bytes, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return TQGPU_OK;
 }
@@ -338,23 +338,23 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
 /* peer `r` lives in this process (several mirrors on one device, or on several devices with peer access enabled by the caller) */
 extern "C" int tqgpu_pshard_connect_local(tqgpu_solver *s, int r, tqgpu_solver *peer) {
     SETTLE(s);
-    if (!s || !peer || !s->pshard.on || r < 0 || r >= s->shard.nranks || !peer->sync_slab || peer->sync_bytes != s->sync_bytes) return fail(TQGPU_EINVAL, "tqgpu_pshard_connect_local: bad arguments");
+    if (!s || !peer || !s->pshard.on || r < 0 || r >= s->shard.nranks || !peer->persist.sync_slab || peer->persist.sync_bytes != s->persist.sync_bytes) return fail(TQGPU_EINVAL, "tqgpu_pshard_connect_local: bad arguments");
     if (peer->device != s->device) {
         HIP_TRY(hipSetDevice(s->device));
         hipError_t e = hipDeviceEnablePeerAccess(peer->device, 0);
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return fail(TQGPU_ECOMM, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
         (void)hipGetLastError();
     }
-    s->pshard.h_peers[r] = static_cast<unsigned long long *>(peer->sync_slab);
+    s->pshard.h_peers[r] = static_cast<unsigned long long *>(peer->persist.sync_slab);
     return upload_peers(s);
 }
 /* peers in other processes: an IPC handle of this rank's slab (64 bytes) out, the peers' handles in */
 extern "C" int tqgpu_pshard_ipc_export(tqgpu_solver *s, void *handle64) {
-    if (!s || !handle64 || !s->sync_slab) return fail(TQGPU_EINVAL, "tqgpu_pshard_ipc_export: bad arguments");
+    if (!s || !handle64 || !s->persist.sync_slab) return fail(TQGPU_EINVAL, "tqgpu_pshard_ipc_export: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
     hipIpcMemHandle_t h;
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-    hipError_t e = hipIpcGetMemHandle(&h, s->sync_slab);
+    hipError_t e = hipIpcGetMemHandle(&h, s->persist.sync_slab);
     if (e != hipSuccess) return fail(TQGPU_ECOMM, std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e));
     memcpy(handle64, &h, 64);
     return TQGPU_OK;
@@ -382,7 +382,7 @@ extern "C" int tqgpu_pshard_begin(tqgpu_solver *s, const tqgpu_opts *o) {
     if (o->profile || o->maxIter <= 0 || o->checkLastActiveSet == 2) return fail(TQGPU_EUNSUPPORTED, "sharded persistent solve: default solve options only (no profiling, no factor keeping)");
     Opts O;
     if (opts_from(o, O) != TQGPU_OK) return TQGPU_EINVAL;
-    if (launch_no_after(s->launch_no) == 0)
+    if (launch_no_after(s->persist.launch_no) == 0)
         return fail(TQGPU_EUNSUPPORTED, "65535 sharded solves since the launch numbers were last reset: call tqgpu_pshard_rewind on every rank, between two barriers of the caller's "
                                         "(the 16-bit launch number tags the hand-over words; a single device wipes its slab when it wraps, ranks that write into each other's slabs cannot do that on their own)");
     memset(s->h_res, 0, sizeof(HostRes));
@@ -401,9 +401,9 @@ extern "C" int tqgpu_pshard_rewind(tqgpu_solver *s) {
     /* (hipMemset of device memory may return before the wipe has happened; it runs on the null stream, which the solver's non-blocking
      * stream does not wait for: the wipe goes on the solver's stream and is waited for -- found by the 100 000-solve soak, where the
      * first C3 solve after a rewind lost words to the wipe) */
-    HIP_TRY(hipMemsetAsync(s->sync_slab, 0, s->sync_bytes, s->stream));
+    HIP_TRY(hipMemsetAsync(s->persist.sync_slab, 0, s->persist.sync_bytes, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    s->launch_no = 0;
+    s->persist.launch_no = 0;
     return TQGPU_OK;
 }
 /* tqgpu_pshard_end without a verdict: a time-out of a bounded wait (the sticky word, cleared here), or the error the caller names */
@@ -423,7 +423,7 @@ extern "C" int tqgpu_pshard_end(tqgpu_solver *s, tqgpu_result *res) {
      * rank's slab by its relay workgroup -- no stream synchronisation on the way (the state write-back of the other workgroups is still
      * running; everything the host does next on this mirror is stream-ordered behind the launch).  (rank 0: the top workgroup's tagged
      * words; the other ranks' relay workgroups post the plain block) */
-    if (!await_result_block(s->h_res, s->psync.seq, true))
+    if (!await_result_block(s->h_res, s->persist.psync.seq, true))
         return pshard_no_verdict(s, " (are all ranks' launches in flight together?)", TQGPU_ECOMM, "sharded persistent solve: no verdict from the top workgroup");
     const Ctrl &c = *s->h_ctrl;
     if (!c.done)
@@ -440,10 +440,10 @@ namespace {
 struct PsRange { double *base; size_t n; };
 std::vector<PsRange> pshard_owned_ranges(tqgpu_solver *s, int rank) {
     std::vector<PsRange> out;
-    const int MD = s->fMD, NX = s->fNX, NU = s->fNU, N = s->shard.nranks;
+    const int MD = s->uni.fMD, NX = s->uni.fNX, NU = s->uni.fNU, N = s->shard.nranks;
     const Data &D = s->D;
     double *lamc = s->h_ctrl->cur ? D.lam1 : D.lam0;
-    const int lb = N > 1 ? s->tier_l0[s->shard.part_top] : s->Nh + 1;
+    const int lb = N > 1 ? s->uni.tier_l0[s->shard.part_top] : s->Nh + 1;
     for (int l = 0; l <= s->Nh; l++) {
         const int wl = uni_width(MD, l);
         const size_t f0 = (size_t)uni_first(MD, l);
@@ -509,7 +509,7 @@ extern "C" int tqgpu_pshard_solve_local(tqgpu_solver **R, int n, const tqgpu_opt
     for (int r = 0; r < n; r++) if (!R[r] || !R[r]->pshard.on || R[r]->shard.nranks != n || R[r]->shard.rank != r) return fail(TQGPU_EINVAL, "tqgpu_pshard_solve_local: mirror r must be tqgpu_pshard_init(r, n)");
     for (int r = 0; r < n; r++) for (int q = 0; q < n; q++) { int rc = tqgpu_pshard_connect_local(R[r], q, R[q]); if (rc) return rc; }
     for (int r = 0; r < n; r++) HIP_TRY(hipStreamSynchronize(R[r]->stream));          /* uploads done: the launches go out back to back */
-    if (R[0]->launch_no >= 0x8000u) for (int r = 0; r < n; r++) { int rc = tqgpu_pshard_rewind(R[r]); if (rc) return rc; }      /* (all ranks idle here) */
+    if (R[0]->persist.launch_no >= 0x8000u) for (int r = 0; r < n; r++) { int rc = tqgpu_pshard_rewind(R[r]); if (rc) return rc; }      /* (all ranks idle here) */
     for (int r = 0; r < n; r++) { int rc = tqgpu_pshard_begin(R[r], o); if (rc) return rc; }
     int first = TQGPU_OK;
     std::string msg;
