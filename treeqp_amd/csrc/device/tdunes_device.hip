@@ -36,6 +36,8 @@
  *   tdunes_sens.hpp      kernels of the sensitivities and adjoints of an MPC step
  *   tdunes_mirror.hpp    (host part, as all below) tqgpu_solver and its records: one per route (PerPhase, Wide3, SingleWg, Uniform, Persist), one per
  *                        feature family (Mpc*, Export, Kkt, SubtreeShard, PersistShard, StageKinds, GenRows, DenseSingle), Timing, BatchLinks; Owned, fail, settle
+ *   tdunes_rows.hpp      the kernels of every instantiated (nx, nu, md) as rows of typed pointers, one array per table of tdunes_parts.hpp, and their lookups:
+ *                        how detect_fast .. launch_persist_batch and tqgpu_pshard_init pick a shape's kernels (no switch on a shape in the host code)
  *   tdunes_problem.hpp   what problem a mirror holds and which stage solver each node runs: the setters and getters of the problem's data
  *   tdunes_kkt.hpp       solution export and the KKT check, kernels and entry points
  *   tdunes_mpc.hpp       the MPC family (tqgpu_mpc_*), kernels and entry points; MpcStats, MpcPre stay here with the solve
@@ -1788,6 +1790,7 @@ using namespace tqd;
 
 #if TQ_HAS(TQP_HOST)
 #include "tdunes_mirror.hpp"
+#include "tdunes_rows.hpp"
 
 namespace {
 
@@ -1892,28 +1895,6 @@ int allow_lds(K kernel, size_t bytes) {
 }
 
 
-
-bool shard_instantiated(int idx) {
-#define X(i, nx, nu, md) if (idx == i) return true;
-    SHARD_TABLE(X)
-#undef X
-    return false;
-}
-
-int fast_index(int NX, int NU, int MD) {
-#define X(idx, nx, nu, md) if (NX == nx && NU == nu && MD == md) return idx;
-    FAST_TABLE(X)
-#undef X
-    return -1;
-}
-
-void fast_geometry(int idx, int &TH, size_t &tier_lds, size_t &stage_lds) {
-#define X(i, nx, nu, md) if (idx == i) { TH = Uni<nx, nu, md>::TH; tier_lds = Uni<nx, nu, md>::TIER_LDS * sizeof(double); stage_lds = FW * (Uni<nx, nu, md>::D + nx + 8) * sizeof(double); }
-    FAST_TABLE(X)
-#undef X
-}
-
-
 /* level `level` of a uniform tree with MD children per parent: the index of its first node, and its width */
 int uni_first(int MD, int level) { int n = 0, w = 1; for (int l = 0; l < level; l++) { n += w; w *= MD; } return n; }
 int uni_width(int MD, int level) { int w = 1; for (int l = 0; l < level; l++) w *= MD; return w; }
@@ -1932,6 +1913,11 @@ std::vector<UniTier> uni_tiers(int top, int TH, int MD) {
 }
 void add_tier(tqgpu_solver *s, int l0, int l1, int grid, int chain) {
     s->uni.tier_l0.push_back(l0); s->uni.tier_l1.push_back(l1); s->uni.tier_grid.push_back(grid); s->uni.tier_chain.push_back(chain);
+}
+/* the table line a mirror's fused routes run with (tdunes_rows.hpp): its index, its shape and its LDS sizes; nullptr: none, generic path only */
+void use_row(tqgpu_solver *s, const ShapeRow *row) {
+    s->uni.row = row; s->uni.fast = row ? row->idx : -1;
+    if (row) { s->uni.fNX = row->nx; s->uni.fNU = row->nu; s->uni.fMD = row->md; s->uni.lds_fast = row->tier_lds; s->uni.lds_fstage = row->stage_lds; }
 }
 
 /* multistage tree?  (setup_multistage_tree(md, Nr, Nh) with 1 <= Nr < Nh: every node above stage Nr has md
@@ -1953,16 +1939,12 @@ void detect_multistage(tqgpu_solver *s) {
         if (k < s->Np) { if (s->nu[k] != NU) return; if (k >= s->lvl_first[Nr] && s->nk[k] != 1) return; }
         else if (s->nu[k] != 0) return;
     }
-    int idx = -1;
-#define X(i, nx, nu, md) if (NX == nx && NU == nu && MD == md) idx = i;
-    MSTAGE_TABLE(X)
-#undef X
-    if (idx < 0) return;
+    const ShapeRow *row = find_row(MSTAGE_ROWS, NX, NU, MD);
+    if (!row) return;
     const int S = uni_width(MD, Nr);
-    s->uni.fast = idx; s->uni.fNX = NX; s->uni.fNU = NU; s->uni.fMD = MD;
+    use_row(s, row);
     s->uni.mstage = true; s->uni.ms_Nr = Nr; s->uni.ms_S = S; s->uni.ms_nB = s->lvl_first[Nr];
-    int TH = 1;
-    fast_geometry(idx, TH, s->uni.lds_fast, s->uni.lds_fstage);
+    const int TH = row->TH;
     s->uni.tier_l0.clear(); s->uni.tier_l1.clear(); s->uni.tier_grid.clear(); s->uni.tier_chain.clear();
     /* chain part bottom-up in tiers of at most 8 levels (Uni<..., 1>::TH), then the branching part in tiers of TH levels */
     for (int l1 = Nh; l1 > Nr;) {
@@ -1976,7 +1958,7 @@ void detect_multistage(tqgpu_solver *s) {
 
 /* uniform complete tree? (every node nx, every parent nu + md children, one leaf depth) */
 void detect_fast(tqgpu_solver *s) {
-    s->uni.fast = -1;
+    use_row(s, nullptr);
     const int Nn = s->Nn, NX = s->nx[0], NU = s->nu[0], MD = s->nk[0];
     if (s->Nh < 2 || MD < 2) return;
     for (int k = 0; k < Nn; k++) {
@@ -1984,13 +1966,11 @@ void detect_fast(tqgpu_solver *s) {
         if (k < s->Np) { if (s->nu[k] != NU || s->nk[k] != MD) return; }
         else if (s->nu[k] != 0) return;
     }
-    const int idx = fast_index(NX, NU, MD);
-    if (idx < 0) return;
-    s->uni.fast = idx; s->uni.fNX = NX; s->uni.fNU = NU; s->uni.fMD = MD;
-    int TH = 1;
-    fast_geometry(idx, TH, s->uni.lds_fast, s->uni.lds_fstage);
+    const ShapeRow *row = find_row(FAST_ROWS, NX, NU, MD);
+    if (!row) return;
+    use_row(s, row);
     s->uni.tier_l0.clear(); s->uni.tier_l1.clear(); s->uni.tier_grid.clear(); s->uni.tier_chain.clear();
-    for (const UniTier &t : uni_tiers(s->Nh, TH, MD)) add_tier(s, t.l0, t.l1, t.grid, 0);
+    for (const UniTier &t : uni_tiers(s->Nh, row->TH, MD)) add_tier(s, t.l0, t.l1, t.grid, 0);
     s->uni.n_tiers = (int)s->uni.tier_l0.size();
 }
 
@@ -2010,36 +1990,29 @@ void launch_fast_phase(tqgpu_solver *s, const Opts &O, int h, int phase, int &la
     const int check_tier = sharded ? P + 1 : 1;          /* index in 0..nt-1 (nt-1 = top) */
     const int nparts = sharded ? N : (nt > 1 ? s->uni.tier_grid[0] : FW);
     const int n_stage = sharded ? s->shard.n_nodes : T.Nn;
-    switch (s->uni.fast) {
-#define X(idx, nx, nu, md)                                                                                                   \
-    case idx:                                                                                                                \
-        if (phase == 0) {                                                                                                    \
-            for (int i = 0; i < nt - 1 && (!sharded || i <= P); i++) {                                                       \
-                hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),    \
-                                   s->uni.tier_l0[i], s->uni.tier_l1[i], i == 0, !sharded && i == check_tier, nparts, i, h); launches++; \
-            }                                                                                                                \
-            if (sharded) { hipLaunchKernelGGL(k_shard_pack1, dim3(1), dim3(256), 0, st, D, tgrid(0), s->shard.d_xerr, s->shard.rank, O.termCondition, h); launches++; } \
-        }                                                                                                                    \
-        if (phase == 1) {                                                                                                    \
-            for (int i = (sharded ? P + 1 : nt - 1); i < nt - 1; i++) {                                                      \
-                hipLaunchKernelGGL((f_back<nx, nu, md>), dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),    \
-                                   s->uni.tier_l0[i], s->uni.tier_l1[i], 0, i == check_tier, nparts, i, h); launches++;              \
-            }                                                                                                                \
-            hipLaunchKernelGGL((f_top<nx, nu, md>), dim3(1), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, nt - 1),           \
-                               s->uni.tier_l1[nt - 1], nt == 1, (nt - 1) == check_tier, nparts, nt - 1, h); launches++;          \
-            for (int i = nt - 2; i >= 0; i--) {                                                                              \
-                hipLaunchKernelGGL((f_fwd<nx, nu, md>), dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),     \
-                                   s->uni.tier_l0[i], s->uni.tier_l1[i], nt + (nt - 2 - i), h); launches++;                          \
-            }                                                                                                                \
-            hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), blk, s->uni.lds_fstage, st, T, D, O,        \
-                               sharded ? s->shard.d_node_list : nullptr, n_stage, 2 * nt - 1, h, 1); launches++;                   \
-            if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->shard.d_node_cnt_list, s->shard.n_nodes_counted, \
-                                              s->shard.d_blk_list, s->shard.n_blk_counted, s->shard.d_xs, s->shard.rank, s->shard.bnd_b0, s->shard.bnd_bn, s->shard.bnd_own0, s->shard.bnd_ownn, h, 1); launches++; } \
-        }                                                                                                                    \
-        break;
-        FAST_TABLE(X)
-#undef X
-        default: break;
+    const ShapeRow &K = *s->uni.row;
+    if (phase == 0) {
+        for (int i = 0; i < nt - 1 && (!sharded || i <= P); i++) {
+            hipLaunchKernelGGL(K.back, dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),
+                               s->uni.tier_l0[i], s->uni.tier_l1[i], i == 0, !sharded && i == check_tier, nparts, i, h); launches++;
+        }
+        if (sharded) { hipLaunchKernelGGL(k_shard_pack1, dim3(1), dim3(256), 0, st, D, tgrid(0), s->shard.d_xerr, s->shard.rank, O.termCondition, h); launches++; }
+    }
+    if (phase == 1) {
+        for (int i = (sharded ? P + 1 : nt - 1); i < nt - 1; i++) {
+            hipLaunchKernelGGL(K.back, dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),
+                               s->uni.tier_l0[i], s->uni.tier_l1[i], 0, i == check_tier, nparts, i, h); launches++;
+        }
+        hipLaunchKernelGGL(K.top, dim3(1), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, nt - 1),
+                           s->uni.tier_l1[nt - 1], nt == 1, (nt - 1) == check_tier, nparts, nt - 1, h); launches++;
+        for (int i = nt - 2; i >= 0; i--) {
+            hipLaunchKernelGGL(K.fwd, dim3(tgrid(i)), blk, s->uni.lds_fast, st, T, D, O, shard_desc(s, i),
+                               s->uni.tier_l0[i], s->uni.tier_l1[i], nt + (nt - 2 - i), h); launches++;
+        }
+        hipLaunchKernelGGL(K.stage, dim3((n_stage + FW - 1) / FW), blk, s->uni.lds_fstage, st, T, D, O,
+                           sharded ? s->shard.d_node_list : nullptr, n_stage, 2 * nt - 1, h, 1); launches++;
+        if (sharded) { hipLaunchKernelGGL(k_shard_pack2, dim3(1), dim3(WAVE), 0, st, D, s->shard.d_node_cnt_list, s->shard.n_nodes_counted,
+                                          s->shard.d_blk_list, s->shard.n_blk_counted, s->shard.d_xs, s->shard.rank, s->shard.bnd_b0, s->shard.bnd_bn, s->shard.bnd_own0, s->shard.bnd_ownn, h, 1); launches++; }
     }
     if (phase == 2) {
         if (sharded) hipLaunchKernelGGL(k_ls_decide_parts, dim3(1), dim3(WAVE), 0, st, D, O, s->shard.d_xs, N, h, 1, 1);
@@ -2103,12 +2076,8 @@ void launch_trial_phase(tqgpu_solver *s, const Opts &O, Route r, int it, int t, 
         bool done = false;
         if (r == Route::TIERED) {
             const int n_stage = sharded ? s->shard.n_nodes : T.Nn;
-            switch (s->uni.fast) {
-#define X(idx, nx, nu, md) case idx: hipLaunchKernelGGL((f_stage<nx, nu, md>), dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->uni.lds_fstage, st, T, D, O, sharded ? s->shard.d_node_list : nullptr, n_stage, 7, it, t); done = true; break;
-                FAST_TABLE(X)
-#undef X
-                default: break;
-            }
+            hipLaunchKernelGGL(s->uni.row->stage, dim3((n_stage + FW - 1) / FW), dim3(FW * WAVE), s->uni.lds_fstage, st, T, D, O, sharded ? s->shard.d_node_list : nullptr, n_stage, 7, it, t);
+            done = true;
         }
         if (!done && r == Route::THREE_LAUNCH) { launch_sg(s, O, 1, it, t); done = true; }      /* with the Armijo test and the next termination test as its tail */
         if (!done) {
@@ -2149,6 +2118,14 @@ static const ProcessSwitches &process_switches() {
 /* persistent launch: geometry, sync words, co-residency test */
 /* poll naps by launch size (PollGuard::go_on) */
 static int nap_for_grid(int workgroups) { return workgroups > process_switches().nap_t1 ? 1 : 0; }
+/* workgroups per CU of the three builds of a persistent kernel at `lds` bytes of LDS each; the build for one workgroup per CU is allowed that much
+ * LDS here, and counts 0 where it cannot have it or cannot be asked */
+static int persist_occupancy(const PersistKernels &k, size_t lds, int &per_cu, int &per_cu_r, int &per_cu_one) {
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.plain, FW * WAVE, lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, k.reuse, FW * WAVE, lds));
+    if (allow_lds(k.one, lds) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, k.one, FW * WAVE, lds) != hipSuccess) per_cu_one = 0;
+    return TQGPU_OK;
+}
 int setup_persist(tqgpu_solver *s) {
     s->persist.ok = false;
     if (s->uni.fast < 0 || s->uni.n_tiers > 8) return TQGPU_OK;
@@ -2160,41 +2137,13 @@ int setup_persist(tqgpu_solver *s) {
     int per_cu = 0, per_cu_r = 1 << 20, per_cu_one = 0;      /* _r: the variant that can keep factors (checkLastActiveSet == 2); _one: the build for one workgroup per CU */
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, s->device));
-    if (!s->uni.mstage) {
-        switch (s->uni.fast) {
-#define X(idx, nx, nu, md)                                                                                                   \
-    case idx:                                                                                                                \
-        s->persist.lds = PLds<nx, nu, md>::DOUBLES * sizeof(double);                                                         \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->persist.lds)); \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, f_persist<nx, nu, md, true>, FW * WAVE, s->persist.lds)); \
-        if (allow_lds(f_persist_one<nx, nu, md>, s->persist.lds) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, f_persist_one<nx, nu, md>, FW * WAVE, s->persist.lds) != hipSuccess) per_cu_one = 0; \
-        break;
-            FAST_TABLE(X)
-#undef X
-            default: break;
-        }
-    } else {
-        switch (s->uni.fast) {
-#define X(idx, nx, nu, md)                                                                                                   \
-    case idx:                                                                                                                \
-        s->persist.lds = std::max(PLds<nx, nu, md>::DOUBLES, PLds<nx, nu, 1>::DOUBLES) * sizeof(double);                     \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_mpersist<nx, nu, md, false>, FW * WAVE, s->persist.lds)); \
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_r, f_mpersist<nx, nu, md, true>, FW * WAVE, s->persist.lds)); \
-        if (allow_lds(f_mpersist_one<nx, nu, md>, s->persist.lds) != TQGPU_OK || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_one, f_mpersist_one<nx, nu, md>, FW * WAVE, s->persist.lds) != hipSuccess) per_cu_one = 0; \
-        break;
-            MSTAGE_TABLE(X)
-#undef X
-            default: break;
-        }
-    }
+    const ShapeRow &K = *s->uni.row;
+    const PersistKernels &kernels = s->uni.mstage ? K.mpersist : K.persist;
+    s->persist.lds = s->uni.mstage ? std::max(K.persist_lds, K.chain_lds) : K.persist_lds;
+    if (int rc = persist_occupancy(kernels, s->persist.lds, per_cu, per_cu_r, per_cu_one)) return rc;
     if (s->sw.has_lds_pad) {      /* experiment: force fewer workgroups per CU */
         s->persist.lds += (size_t)s->sw.lds_pad * 1024;
-        switch (s->uni.fast) {
-#define X(idx, nx, nu, md) case idx: if (!s->uni.mstage) { allow_lds(f_persist<nx, nu, md, false>, s->persist.lds); HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f_persist<nx, nu, md, false>, FW * WAVE, s->persist.lds)); } break;
-            FAST_TABLE(X)
-#undef X
-            default: break;
-        }
+        if (!s->uni.mstage) { allow_lds(K.persist.plain, s->persist.lds); HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K.persist.plain, FW * WAVE, s->persist.lds)); }
     }
     /* every workgroup must be resident at once (they wait for each other); keep one block per CU of
      * margin against the occupancy query over-reporting (MI355X guide, "Residency and cooperative launch") */
@@ -2322,35 +2271,14 @@ int launch_persist(tqgpu_solver *s, const Opts &O, int &launches, int prologue, 
         /* this rank's share of the workgroups; the geometry (tiers, global workgroup numbers, G) is the whole tree's */
         PGeom Gm = s->persist.geom;
         Gm.wg_of_block = s->pshard.wg_map;
-        switch (s->uni.fast) {
-#define X(idx, nx, nu, md) case idx: if (s->pshard.sys) hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 1>), dim3(s->pshard.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, Gm, s->persist.psync, prologue); \
-                                    else hipLaunchKernelGGL((f_persist_sh<nx, nu, md, 0>), dim3(s->pshard.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, Gm, s->persist.psync, prologue); break;
-            SHARD_TABLE(X)
-#undef X
-            default: return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape");
-        }
+        if (!s->pshard.row) return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape");
+        hipLaunchKernelGGL(s->pshard.sys ? s->pshard.row->sys : s->pshard.row->agent, dim3(s->pshard.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, Gm, s->persist.psync, prologue);
         launches++;
         return TQGPU_OK;
     }
-    if (!s->uni.mstage) {
-        switch (s->uni.fast) {
-#define X(idx, nx, nu, md) case idx: if (O.reuse) hipLaunchKernelGGL((f_persist<nx, nu, md, true>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
-                                    else if (s->persist.one && !s->links.in_batch) hipLaunchKernelGGL((f_persist_one<nx, nu, md>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
-                                    else hipLaunchKernelGGL((f_persist<nx, nu, md, false>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); break;
-            FAST_TABLE(X)
-#undef X
-            default: break;
-        }
-    } else {
-        switch (s->uni.fast) {
-#define X(idx, nx, nu, md) case idx: if (O.reuse) hipLaunchKernelGGL((f_mpersist<nx, nu, md, true>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
-                                    else if (s->persist.one && !s->links.in_batch) hipLaunchKernelGGL((f_mpersist_one<nx, nu, md>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); \
-                                    else hipLaunchKernelGGL((f_mpersist<nx, nu, md, false>), dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue); break;
-            MSTAGE_TABLE(X)
-#undef X
-            default: break;
-        }
-    }
+    const PersistKernels &kernels = s->uni.mstage ? s->uni.row->mpersist : s->uni.row->persist;
+    const PersistFn kernel = O.reuse ? kernels.reuse : (s->persist.one && !s->links.in_batch) ? kernels.one : kernels.plain;
+    hipLaunchKernelGGL(kernel, dim3(s->persist.geom.G), dim3(FW * WAVE), s->persist.lds, st, s->persist.pconst, O, s->persist.geom, s->persist.psync, prologue);
     launches++;
     return TQGPU_OK;
 }
@@ -2491,7 +2419,7 @@ int detect_shape(tqgpu_solver *s) {
         s->nx[0] = nx1;
         if (build_tables(s) == TQGPU_OK) detect();
         if (s->uni.fast >= 0) { s->x_pad = nx1; s->A_pad = s->nk[0] * nx1 * nx1; }
-        else { s->nx[0] = 0; s->uni.fast = -1; s->uni.mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
+        else { s->nx[0] = 0; use_row(s, nullptr); s->uni.mstage = false; if ((rc = build_tables(s)) != TQGPU_OK) return rc; }
     }
     if (s->sw.generic) { s->uni.use_fast = 0; s->gp.use = 0; }
     s->gpd.single = s->sw.dense_single;
@@ -2629,7 +2557,7 @@ int setup_per_phase(tqgpu_solver *s) {
         return rc;
     if (s->uni.fast >= 0) {
         hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, s->device) != hipSuccess || prop.maxThreadsPerBlock < FW * WAVE) s->uni.fast = -1;
+        if (hipGetDeviceProperties(&prop, s->device) != hipSuccess || prop.maxThreadsPerBlock < FW * WAVE) use_row(s, nullptr);
     }
     s->pp.fw_fused = !s->sw.fwd_levels && !s->strict_sum;      /* (strict: the reference's launch-per-level order of operations) */
     s->pp.bw_fused = !s->sw.bwd_levels && !s->strict_sum;      /* (a fused sweep subtracts a child's Schur record AFTER an ALWAYS shift of the diagonal, the reference before it) */
@@ -3520,12 +3448,6 @@ extern "C" int tqgpu_geometry(const tqgpu_solver *s, int *levels, int *tiers, in
 /* diagnostic: how often a persistent launch of this mirror timed out and the solve was redone on another path */
 extern "C" int tqgpu_timeouts(const tqgpu_solver *s) { return s ? s->persist.n_timeouts : 0; }
 
-static int batch_kernel_index(const tqgpu_solver *s) {
-#define X(idx, nx, nu, md, ms) if (s->uni.fNX == nx && s->uni.fNU == nu && s->uni.fMD == md && s->uni.mstage == ms) return idx;
-    BATCH_TABLE(X)
-#undef X
-    return -1;
-}
 /* a block of a batch launch (device array and its pinned host copy, owned by the batch's first mirror): room for `need` units, twice the
  * need where it has to grow (the lead's stream holds nothing that reads it: every batched call ends with its wait) */
 template <typename Item, typename Cap>
@@ -3605,19 +3527,15 @@ static int order_behind_lead(tqgpu_solver *s, const tqgpu_solver *lead, long &dr
     return TQGPU_OK;
 }
 constexpr LeadOrder KKT_ORDER{false, false, false}, ADJ_ORDER{true, true, false}, ADJMAT_ORDER{false, false, true};
-static int launch_persist_batch(tqgpu_solver *lead, int kidx, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
+static int launch_persist_batch(tqgpu_solver *lead, const BatchRow *row, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
     const int G = lead->persist.geom.G;
     const ProcessSwitches &ps = process_switches();
     const int batch_nap = ps.has_nap ? ps.nap : nap_for_grid(G * n_trees);     /* the whole launch polls the same memory system */
-    static size_t lds_allowed[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    switch (kidx) {
-#define X(idx, nx, nu, md, ms) case idx: { \
-        if (lds_allowed[idx] < lead->persist.lds) { int rc = allow_lds(f_persist_batch<nx, nu, md, ms>, lead->persist.lds); if (rc != TQGPU_OK) return rc; lds_allowed[idx] = lead->persist.lds; } \
-        hipLaunchKernelGGL((f_persist_batch<nx, nu, md, ms>), dim3((unsigned)(G * n_trees)), dim3(FW * WAVE), lead->persist.lds, lead->stream, items, O, G, seq, batch_nap); break; }
-        BATCH_TABLE(X)
-#undef X
-        default: return fail(TQGPU_EINVAL, "no batch kernel for this shape");
-    }
+    static size_t lds_allowed[sizeof(BATCH_ROWS) / sizeof(BATCH_ROWS[0])] = {};      /* per row: the LDS its kernel has been allowed so far */
+    if (!row) return fail(TQGPU_EINVAL, "no batch kernel for this shape");
+    size_t &allowed = lds_allowed[row - BATCH_ROWS];
+    if (allowed < lead->persist.lds) { int rc = allow_lds(row->batch, lead->persist.lds); if (rc != TQGPU_OK) return rc; allowed = lead->persist.lds; }
+    hipLaunchKernelGGL(row->batch, dim3((unsigned)(G * n_trees)), dim3(FW * WAVE), lead->persist.lds, lead->stream, items, O, G, seq, batch_nap);
     return TQGPU_OK;
 }
 
@@ -3628,7 +3546,7 @@ struct BatchMember {
     tqgpu_solver *s;
     Route plan;                  /* route_of(s, o, true): what the waves and the groups are planned with */
     Route alone;                 /* route_of(s, o, false): differs from `plan` only for a tree that is SINGLE_WG as a group member alone (uses_gpersist) */
-    int kidx;                    /* the batch kernel (BATCH_TABLE) this member can go out in under these options, or -1 */
+    const BatchRow *krow;        /* the batch kernel (BATCH_ROWS) this member can go out in under these options, or nullptr */
     int need;                    /* workgroups that have to be resident while it runs */
     bool in_single_wg = false;   /* member of its wave's single-workgroup group (clipping trees: g_persist_batch) ... */
     bool in_dense_wg = false;    /* ... of its wave's dense single-workgroup group (g_persist_dense_batch) ... */
@@ -3650,7 +3568,7 @@ static std::vector<BatchMember> plan_members(tqgpu_solver **solvers, int n, cons
         tqgpu_solver *s = m.s = solvers[k];
         m.plan = route_of(s, o, true);
         m.alone = m.plan == Route::SINGLE_WG ? route_of(s, o, false) : m.plan;
-        m.kidx = m.plan == Route::PERSIST && o->checkLastActiveSet != 2 ? batch_kernel_index(s) : -1;
+        m.krow = m.plan == Route::PERSIST && o->checkLastActiveSet != 2 ? find_batch_row(s->uni.fNX, s->uni.fNU, s->uni.fMD, s->uni.mstage) : nullptr;
         /* single-workgroup mirrors do not wait for each other: any number per launch; launch-per-level mirrors go alone */
         /* (a SINGLE_WG plan counts 0 even where batch_route sends the member to a launch-per-level route in the end) */
         m.need = m.plan == Route::PERSIST ? s->persist.geom.G : (m.plan == Route::SINGLE_WG ? 0 : s->persist.co_capacity + 1);
@@ -3669,7 +3587,7 @@ static int wave_end(const std::vector<BatchMember> &tab, int i, const SolveEnv &
          * member needs more.  Members that go out together as ONE launch (batch kernel) fill the device up to what is co-resident:
          * a tree's waves are parked at barriers and waits two thirds of the time, and trees that share CUs fill those gaps
          * (C2: 3 trees 72 k it/s, 5 trees 98 k; C1: 22 trees 656 k, 38 trees 922 k). */
-        const bool one_launch = m.kidx >= 0 && !env.batch_launches;
+        const bool one_launch = m.krow && !env.batch_launches;
         const int cap = (!one_launch && s->n_cu > 0 && m.need <= s->n_cu) ? std::min(s->persist.co_capacity, s->n_cu) : s->persist.co_capacity;
         if (j > i && (s->device != dev || used + m.need > cap)) break;
         used += m.need;
@@ -3695,9 +3613,9 @@ static int form_groups(std::vector<BatchMember> &tab, int i, int j, const SolveE
     const BatchMember *f = nullptr;          /* the first one that has a batch kernel: the others have to match it */
     for (int k = i; k < j; k++) {
         const BatchMember &m = tab[(size_t)k];
-        if (m.kidx < 0) continue;
+        if (!m.krow) continue;
         if (!f) f = &m;
-        if (m.kidx == f->kidx && m.s->persist.geom.G == f->s->persist.geom.G && m.s->persist.lds == f->s->persist.lds && m.s->Nn == f->s->Nn) pg.members.push_back(k);
+        if (m.krow == f->krow && m.s->persist.geom.G == f->s->persist.geom.G && m.s->persist.lds == f->s->persist.lds && m.s->Nn == f->s->Nn) pg.members.push_back(k);
     }
     if (pg.members.size() < 2 || env.batch_launches) pg.members.clear();      /* (=1: one launch per tree, the round-1 protocol) */
     for (int k : wg.members) tab[(size_t)k].in_single_wg = true;
@@ -3809,7 +3727,7 @@ static int launch_persist_group(std::vector<BatchMember> &tab, BatchGroup &pg, u
     int rc = join_lead_stream(tab, pg, np);
     if (rc != TQGPU_OK) return rc;
     const BatchMember &lead = tab[(size_t)pg.members[0]];
-    if ((rc = launch_persist_batch(pl, lead.kidx, pl->persist.d_pitems, lead.cx.O, (int)np, pseq)) != TQGPU_OK) return rc;
+    if ((rc = launch_persist_batch(pl, lead.krow, pl->persist.d_pitems, lead.cx.O, (int)np, pseq)) != TQGPU_OK) return rc;
     pg.launched = np;
     return TQGPU_OK;
 }

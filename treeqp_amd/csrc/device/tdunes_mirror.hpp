@@ -68,6 +68,7 @@ struct Switches {
 };
 
 namespace { struct KItem; struct KHead; struct MItem; }      /* the descriptors of the batched KKT check and of the MPC steps, the check's head (defined with their kernels) */
+namespace { struct ShapeRow; struct ShardRow; }      /* a shape's sizes and kernels, one record per line of the instantiation tables (tdunes_rows.hpp) */
 
 /* ---- what a mirror keeps for the MPC family (tqgpu_mpc_*, tdunes_mpc.hpp), one record per feature ---- */
 /* the root terms (tqgpu_mpc_set_root): d, the originals of what multiplies x0, [A0 | b0 | S0 | r0 | C0 | dmin0 | dmax0] in one device block;
@@ -199,6 +200,7 @@ struct PersistShard {
     bool fine = false;              /* the hand-over slab was re-allocated as fine-grained memory (tqgpu_pshard_init; TREEQP_AMD_PSHARD_COARSE=1 keeps plain hipMalloc memory) */
     int *wg_map = nullptr;          /* blockIdx.x -> workgroup id, this rank's workgroups (bottom tier first) */
     int G = 0;
+    const ShardRow *row = nullptr;  /* the sharded kernels of this shape (SHARD_ROWS), looked up by tqgpu_pshard_init */
     void *ipc[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      /* peer slabs opened through IPC handles (closed by tqgpu_destroy) */
     unsigned long long *h_peers[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* slabs of all ranks (a mirror that is not sharded: its own, eight times) ... */
     unsigned long long **d_peers = nullptr;                                                               /* ... and the device copy of the table the kernel reads */
@@ -301,6 +303,7 @@ struct SingleWg {
  * detect_multistage and the tiers of the launches per tier */
 struct Uniform {
     int fast = -1;            /* index into the instantiation table, -1: generic path only */
+    const ShapeRow *row = nullptr;   /* that line's sizes and kernels (FAST_ROWS; MSTAGE_ROWS where mstage): set and cleared with `fast` */
     int fNX = 0, fNU = 0, fMD = 0;
     int n_tiers = 0;          /* tiers of block levels, index 0 = bottom */
     bool mstage = false;      /* multistage tree (branching for Nr stages, then chains): persistent kernel f_mpersist only */

@@ -56,7 +56,8 @@
 
 /* shapes with a batch kernel (f_persist_batch: one launch for a batch of trees of one shape); the BASELINE shapes and a few
  * neighbours -- any other (nx, nu, md) of FAST_TABLE / MSTAGE_TABLE is one line away and costs its compile time; without a line
- * the members of a batch are launched one by one */
+ * the members of a batch are launched one by one.  (One line away in all four tables: the owning part instantiates the kernels from
+ * the line, the host builds its row of kernel pointers from it, tdunes_rows.hpp, and has no other list of shapes.) */
 #define BATCH_TABLE(X) X(0, 8, 3, 2, false) X(1, 4, 1, 3, true) X(2, 8, 3, 2, true) X(3, 4, 1, 2, false) X(4, 4, 1, 2, true) X(5, 8, 2, 2, false)
 
 /* Slices of the persistent family: table index idx belongs to slice idx % TQ_PERSIST_NSLICES.  TQ_SL(idx, text) expands to `text`

@@ -284,13 +284,9 @@ extern "C" int tqgpu_pshard_init(tqgpu_solver *s, int rank, int nranks) {
     if (!s || nranks < 1 || nranks > 8 || rank < 0 || rank >= nranks) return fail(TQGPU_EINVAL, "tqgpu_pshard_init: bad arguments (1 .. 8 ranks)");
     HIP_TRY(hipSetDevice(s->device));
     if (!s->persist.ok || s->uni.mstage || s->uni.fast < 0 || !s->uni.use_fast || !s->persist.use) return fail(TQGPU_EUNSUPPORTED, "sharding inside the persistent launch needs the persistent path of a uniform complete tree");
-    if (!shard_instantiated(s->uni.fast)) return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape (SHARD_TABLE)");
-    switch (s->uni.fast) {
-#define X(idx, nx, nu, md) case idx: { int rca = allow_lds(f_persist_sh<nx, nu, md, 1>, s->persist.lds); if (!rca) rca = allow_lds(f_persist_sh<nx, nu, md, 0>, s->persist.lds); if (rca) return rca; } break;
-        SHARD_TABLE(X)
-#undef X
-        default: break;
-    }
+    s->pshard.row = find_row(SHARD_ROWS, s->uni.fNX, s->uni.fNU, s->uni.fMD);
+    if (!s->pshard.row) return fail(TQGPU_EUNSUPPORTED, "the sharded persistent kernel is not instantiated for this shape (SHARD_TABLE)");
+    { int rca = allow_lds(s->pshard.row->sys, s->persist.lds); if (!rca) rca = allow_lds(s->pshard.row->agent, s->persist.lds); if (rca) return rca; }
     int nwg = 0, top = -1;
     if (tqgpu_pshard_plan(s->uni.fMD, s->Nh, nranks, rank, nullptr, 0, &nwg, &top, nullptr) != 0) return fail(TQGPU_EUNSUPPORTED, "tree too small to shard over this many ranks");
     std::vector<int> map((size_t)std::max(nwg, 1));
