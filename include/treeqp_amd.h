@@ -850,6 +850,60 @@ int tqgpu_mpc_get_adjoint_bounds(tqgpu_solver *s, double *gxmin, double *gxmax, 
 int tqgpu_mpc_adjoint_bounds(tqgpu_solver *s, double *glb, double *gub);
 int tqgpu_mpc_adjoint_reference(tqgpu_solver *s, double *gxref, double *guref, int *row0, int *rows);
 
+/* ---- The tangent of an MPC step: dz, dlam along directions in q, r, b, x0, and a predictor that follows the tracking reference -----------------
+ * The forward-mode twin of the adjoint above: how the point of the last solve moves along a direction (dq, dr, db, dx0) of the linear terms,
+ * with the active set frozen.  There the solution is affine in (q, r, b, x0), so the tangent along a FINITE change is exact until the active set
+ * changes.  P_k, M, C_c = [A_c B_c], G, direct_k, the factor and n_reg as in the two sections above; dh_k = [dq_k; dr_k], phantom root states carry 0.
+ *   R                    rows of child c of p:  R_c = (P_c dh_c)^x - C_c P_p dh_p + db_c + G_c dx0  (G_c: the rows of the root's children only)
+ *   M dLam = R           with the stored factor where there is one (tqgpu_mpc_sensitivity, tqgpu_mpc_adjoint or an earlier call left it), otherwise
+ *                        built first exactly as tqgpu_mpc_sensitivity does; the two sweeps are the adjoint's own kernels on the tangent's buffers.
+ *   dZ                   dZ_k = P_k ( [dLam_k; 0] - sum_c C_c' dLam_c ) - P_k dh_k + direct_k dx0;  du0 = the u rows of dZ_0.
+ *   order                R: the adjoint's expression for w := dh, then + db_c where db was given, then v = fma(G[., j], dx0[j], v), j ascending, where
+ *                        dx0 was given.  dZ: the adjoint's chain -P_k ( dh_k - [dLam_k; 0] + sum_c C_c' dLam_c ), then the direct term: a root with
+ *                        states + dx0[i]; an eliminated root with S0  s = S0 dx0 (a chain from 0.0, j ascending), v = fma(-P_0[i, nx + m], s[m], v),
+ *                        m ascending.  A term that was not given is skipped, not added as 0.0.  So with db == dx0 == NULL (dx, du, dlam) equals
+ *                        (gq, gr, gb) of tqgpu_mpc_adjoint(wx = dq, wu = dr) on the same mirror bit for bit, and column j of a call with nd
+ *                        columns is bit for bit the call with that column alone.
+ *   uniqueness           as for the adjoint: dZ is unique where R lies in the range of M (db moves R out of it only where a state is pinned);
+ *                        dLam is unique only when n_reg == 0.
+ *   tqgpu_mpc_tangent    nd directions, column major: dq ((sum_nx without phantom root states) x nd), dr (sum_nu x nd), db (sum_lam x nd, the flat
+ *                        layout of b), dx0 (nx0 x nd); any may be NULL, meaning zero.  One host-to-device copy of the directions through pinned
+ *                        memory; the launches (one wave per unit and column, columns on grid dimension y, ordered by launch boundaries on the
+ *                        mirror's stream): [Nh + 1 for the factor where none is stored, plus the packing of the point where that has not gone
+ *                        out] + 1 (k_tan_rhs) + Nh (k_adj_backward) + Nh - 1 (k_adj_forward) + 1 (k_tan_primal: dZ, dLam, the head), that is
+ *                        2 Nh + 1 behind a stored factor; one device-to-host copy of [du0 | n_reg] and one wait.  Counted into tqgpu_mpc_stats
+ *                        (2 copies, 1 wait).  It works in buffers of its own (allocated on first use, again when nd grows, freed by
+ *                        tqgpu_destroy): a stored sensitivity, a stored adjoint and everything a solve, tqgpu_get_solution or tqgpu_kkt_residual
+ *                        reads keep their bits; the factor counts as stored afterwards.
+ *                        TQGPU_EINVAL, TQGPU_EUNSUPPORTED: wherever tqgpu_mpc_adjoint returns them, with nd for nw (kinds 2 and 3, a rank of a
+ *                        sharded solve, (nz nd + 2) * 8 > 160 KiB, a problem changed since the last solve, before the first solve);
+ *                        TQGPU_EINVAL also for nd < 1 and where all four directions are NULL.  All of them before any launch.
+ *   tqgpu_mpc_get_tangent_u0   du0 (nu[0] x nd, column major) of the last tangent (host state only).
+ *   tqgpu_mpc_get_tangent      dx ((sum_nx without phantom root states) x nd), du (sum_nu x nd), dlam (sum_lam x nd), column major; any pointer
+ *                        may be NULL.  Downloads and waits; not counted (a diagnostic read-out).
+ *   tqgpu_mpc_predict_at   one direction, built on the device: the change the next tqgpu_mpc_step_at(s, x0_new, t0_new) will fold in, measured from
+ *                        the point of the last solve.  dx0 = x0_new - x0_ref (x0_new == NULL: no dx0 term); db = 0; t0_new < 0 keeps the window
+ *                        (dh = 0); t0_new >= 0, under tqgpu_mpc_set_tracking with a window t0 in force: for node k with
+ *                        rho(t) = min(t + stage[k], T - 1), dxref = xtraj[rho(t0_new)] - xtraj[rho(t0)], duref likewise, and dh_k is the chain of
+ *                        the window fold started from 0.0: kind 0  dq[i] = fma(-Qd[i], dxref[i], 0.0), likewise Rd, duref; kind 1  row i of H_k,
+ *                        v = fma(-H[i, j], dxref[j], v) over the x columns, then the u columns with duref; the u rows of an eliminated root
+ *                        with S0 go on with v = fma(-S0[i, j], dxref[j], v) (the + S0 dx0 term is direct_0's and is not added twice).
+ *                        Then the solve above with nd = 1 and ONE more kernel (k_tan_apply): u0_pred[i] = u0*[i] + du0[i], clipped into
+ *                        [umin[0], umax[0]] on a root of kind 0 (n_clipped counts the entries moved); duals != 0: a wave per node writes
+ *                        lam*[e] + dLam[e] into the start buffer, which holds for ONE solve in any warm-start mode, by the mechanism of
+ *                        tqgpu_mpc_predict.  x0_new goes in and [u0_pred | n_clipped | n_reg] come back through pinned memory, which the kernels
+ *                        read and write in place; no q, r, b, trajectory row or direction crosses the bus.  Behind a stored factor: 2 Nh + 2
+ *                        launches, 1 copy (the head [du0 | n_reg], for tqgpu_mpc_get_tangent_u0) and 1 wait, counted into tqgpu_mpc_stats; without
+ *                        one, the factor's launches in front as above.  The call moves neither the window nor x0 (tqgpu_mpc_get_window and
+ *                        x0_ref are unchanged; the step that follows folds both); its tangent stays readable through the two getters.
+ *                        Refusals: those of tqgpu_mpc_tangent; TQGPU_EINVAL also for t0_new >= 0 before tqgpu_mpc_set_tracking, before a window
+ *                        is in force, and where tqgpu_mpc_step_at refuses the window (nx0 != NXT on an eliminated root with S0).
+ * A stored tangent is invalidated by the same events as a stored adjoint; the getters then return TQGPU_EINVAL. */
+int tqgpu_mpc_tangent(tqgpu_solver *s, const tqgpu_opts *opts, const double *dq, const double *dr, const double *db, const double *dx0, int nd, int *n_reg);
+int tqgpu_mpc_get_tangent_u0(tqgpu_solver *s, double *du0);
+int tqgpu_mpc_get_tangent(tqgpu_solver *s, double *dx, double *du, double *dlam);
+int tqgpu_mpc_predict_at(tqgpu_solver *s, const tqgpu_opts *opts, const double *x0_new, int t0_new, double *u0_pred, int duals, int *n_clipped, int *n_reg);
+
 /* Device times [s] of the last n solves (oldest first), measured with HIP events on the solver's
  * stream around everything a solve enqueues; synchronises the stream; returns the number written
  * (at most 512 solves back) or -1.  tqgpu_result.device_time of a single-launch (persistent) solve is

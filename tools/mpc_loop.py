@@ -48,6 +48,14 @@ with root states and on c1 x0-eliminated, with the launches, copies and waits of
 the dual predictor (tqgpu_mpc_sensitivity + tqgpu_mpc_predict with duals) against warm start mode 1 over the sequences of --root-states
 and --tracking (predict_compare).
 
+    python tools/mpc_loop.py --predict-at [--steps 200] [--skip 10] [c1] [c2] [kind3]
+    python tools/mpc_loop.py --tangent [--steps 200] [--skip 10] [c1] [c2] [kind3]
+
+--predict-at: the tracking loop with tqgpu_mpc_predict_at(x0 and window of the next step, duals = 1) ahead of every tqgpu_mpc_step_at, against
+the plain loop and the x0-only predictor (predict_at_compare).  --tangent: tqgpu_mpc_tangent (nd = 1) alone behind every step, against
+tqgpu_mpc_adjoint + tqgpu_mpc_get_adjoint + numpy, the only route to a directional derivative without it (tangent_compare).  kind3: both
+calls refuse trees with nodes of kind 2 or 3; the refusal is printed (refused_kind3).
+
     python tools/mpc_loop.py --gain-batch N[,N2,..] [--steps 200] [--skip 10] [c1] [c2]
 
 --gain-batch: behind every tqgpu_mpc_step_batch of N trees, the gains and the dual predictor two ways, on c1 x0-eliminated and on c2 with
@@ -1324,6 +1332,119 @@ def predict_compare(capi, name, p, tracking, steps, skip):
               f"trials per step mean {np.mean([c[2] for c in cnt[skip:]]):.2f} | status 0 in {sum(c[0] == 0 for c in cnt)} of {steps}{tail}", flush=True)
 
 
+def predict_at_compare(capi, name, p, steps, skip):
+    """--predict-at: the tracking loop of --predict on a root with states, three ways: warm start mode 1; mode 1 with the x0 predictor
+    (tqgpu_mpc_sensitivity + tqgpu_mpc_predict, which does not see the window move); mode 1 with tqgpu_mpc_predict_at(x0 and window of the next
+    step, duals = 1), whose direction follows the reference.  Wall time per step includes the extra calls."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    d, x0 = full_root(capi, p)
+    nu0 = int(d["nu"][0])
+    xs = [moved_inward(x0, k, 0) for k in range(steps + 1)]
+    X, U = reference(x0, nu0, steps + int(node_stages(d["nk"]).max()) + 2)
+    u0, up = np.zeros(max(nu0, 1)), np.zeros(max(nu0, 1))
+    nreg, ncl = C.c_int(), C.c_int()
+    print(f"{name}, --predict-at, root with states, tracking: {len(d['nk'])} nodes, {steps} steps", flush=True)
+    for how in ("mode 1", "mode 1 + x0 predictor", "mode 1 + predict_at"):
+        g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+        g.mpc_set_root_states()
+        g.set_warm_start(1)
+        g.mpc_set_tracking(X, U, d["q"], d["r"])
+        w, cnt, perr, clipped, st = [], [], [], 0, None
+        for k in range(steps):
+            t0 = time.perf_counter()
+            assert L.tqgpu_mpc_step_at(g.h, dp(xs[k]), k, C.byref(o), C.byref(r), dp(u0)) == 0, L.tqgpu_last_error()
+            cnt.append((r.status, r.iter, r.ls_total))
+            if k > 0 and how != "mode 1":
+                perr.append(float(np.max(np.abs(up[:nu0] - u0[:nu0]))))
+            if how == "mode 1 + x0 predictor":
+                assert L.tqgpu_mpc_sensitivity(g.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()
+                assert L.tqgpu_mpc_predict(g.h, dp(xs[k + 1]), dp(up), 1, C.byref(ncl)) == 0, L.tqgpu_last_error()
+                clipped += ncl.value
+            if how == "mode 1 + predict_at":
+                assert L.tqgpu_mpc_predict_at(g.h, C.byref(o), dp(xs[k + 1]), k + 1, dp(up), 1, C.byref(ncl), C.byref(nreg)) == 0, L.tqgpu_last_error()
+                clipped += ncl.value
+                st = capi.mpc_stats()
+            w.append(time.perf_counter() - t0)
+        g.close()
+        m, lo, p90 = stats(w[skip:])
+        tail = f" | largest |u0_pred - u0 of the next solve| {max(perr):.2e}, median {np.median(perr):.2e}; entries clipped {clipped}" if perr else ""
+        tail += f" | the call: {st['launches']} launches, {st['copies']} copies, {st['waits']} waits" if st else ""
+        print(f"    {how:24s} wall median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f} | iterations per step mean {np.mean([c[1] for c in cnt[skip:]]):.2f}  "
+              f"trials per step mean {np.mean([c[2] for c in cnt[skip:]]):.2f} | status 0 in {sum(c[0] == 0 for c in cnt)} of {steps}{tail}", flush=True)
+
+
+def tangent_compare(capi, name, p, steps, skip):
+    """--tangent: behind every step of the tracking loop (root with states) one directional derivative of the step along (dq, dr), two ways:
+    tqgpu_mpc_tangent (nd = 1), and the only route there was without it, tqgpu_mpc_adjoint(w = (dq, dr)) + tqgpu_mpc_get_adjoint + numpy, which by
+    the symmetry of the KKT system gives the same (dx, du) but cannot carry db or dx0.  Time per call, launches, copies, waits of tqgpu_mpc_stats
+    (the downloads of tqgpu_mpc_get_adjoint are not counted there), and the largest difference of the two results."""
+    L = capi.lib()
+    dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+    o, r = capi._gpu_opts(), capi.GpuResult()
+    d, x0 = full_root(capi, p)
+    nu0 = int(d["nu"][0])
+    xs = [moved_inward(x0, k, 0) for k in range(steps + 1)]
+    X, U = reference(x0, nu0, steps + int(node_stages(d["nk"]).max()) + 2)
+    u0 = np.zeros(max(nu0, 1))
+    rng = np.random.default_rng(5)
+    dq, dr = 2.0 ** -10 * rng.standard_normal(len(d["q"])), 2.0 ** -10 * rng.standard_normal(len(d["r"]))
+    nreg = C.c_int()
+    print(f"{name}, --tangent, root with states, tracking: {len(d['nk'])} nodes, {steps} steps", flush=True)
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"]).upload(d)
+    g.mpc_set_root_states()
+    g.set_warm_start(1)
+    g.mpc_set_tracking(X, U, d["q"], d["r"])
+    gq, gr, gb = np.zeros(max(int(g.sum_nx), 1)), np.zeros(max(int(g.sum_nu), 1)), np.zeros(max(int(g.sum_lam), 1))
+    du0 = np.zeros(max(nu0, 1))
+    wt, wa, diff, st_t, st_a = [], [], [], None, None
+    for k in range(steps):
+        assert L.tqgpu_mpc_step_at(g.h, dp(xs[k]), k, C.byref(o), C.byref(r), dp(u0)) == 0, L.tqgpu_last_error()
+        assert L.tqgpu_mpc_sensitivity(g.h, C.byref(o), C.byref(nreg)) == 0, L.tqgpu_last_error()          # both legs find the factor stored
+        order = ("tangent", "adjoint") if k % 2 == 0 else ("adjoint", "tangent")
+        for leg in order:
+            t0 = time.perf_counter()
+            if leg == "tangent":
+                assert L.tqgpu_mpc_tangent(g.h, C.byref(o), dp(dq), dp(dr), None, None, 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+                assert L.tqgpu_mpc_get_tangent_u0(g.h, dp(du0)) == 0
+                wt.append(time.perf_counter() - t0)
+                st_t = capi.mpc_stats()
+            else:
+                assert L.tqgpu_mpc_adjoint(g.h, C.byref(o), dp(dq), dp(dr), 1, C.byref(nreg)) == 0, L.tqgpu_last_error()
+                st_a = capi.mpc_stats()
+                assert L.tqgpu_mpc_get_adjoint(g.h, dp(gq), dp(gr), dp(gb)) == 0
+                via = gr[:nu0].copy()          # du0 = the u rows of the root of gr
+                wa.append(time.perf_counter() - t0)
+        diff.append(float(np.max(np.abs(via - du0[:nu0]))))
+    g.close()
+    for how, w, st, note in (("tqgpu_mpc_tangent", wt, st_t, ""), ("adjoint + download", wa, st_a, " + 3 uncounted blocking downloads and a stream wait; no db, no dx0")):
+        m, lo, p90 = stats(w[skip:])
+        print(f"    {how:24s} per call median {m:8.1f} us  min {lo:8.1f}  p90 {p90:8.1f} | {st['launches']} launches, {st['copies']} copies, {st['waits']} waits{note}", flush=True)
+    print(f"    largest |du0 (tangent) - du0 (adjoint route)| over the loop: {max(diff):.2e}", flush=True)
+
+
+def refused_kind3(capi, what):
+    """kind3 under --predict-at / --tangent: the calls refuse trees with nodes of kind 2 or 3; the record says so"""
+    import solve_sequence_cases as SC
+    L = capi.lib()
+    d, kinds = kind3_tree()
+    g = capi.TqGpu(d["nk"], d["nx"], d["nu"])
+    try:
+        g.set_constraints(d["nc"], d["C"], d["D"], d["dmin"], d["dmax"])
+        g.upload_mixed(d, kinds, None)
+        g.mpc_set_root_states()
+        o, r = capi._gpu_opts(**dict(SC.FULL)), capi.GpuResult()
+        x0 = np.array(d["xmin"][:2], copy=True)
+        u0 = np.zeros(2)
+        dp = lambda a: a.ctypes.data_as(capi.c_dbl_p)
+        rc_step = L.tqgpu_mpc_step(g.h, dp(x0), C.byref(o), C.byref(r), dp(u0))
+        rc = L.tqgpu_mpc_predict_at(g.h, C.byref(o), dp(x0), -1, dp(u0), 1, None, None) if what == "predict-at" else L.tqgpu_mpc_tangent(g.h, C.byref(o), None, None, None, dp(x0), 1, None)
+        print(f"kind3, --{what}: step rc {rc_step}; the call returns {rc}: {L.tqgpu_last_error().decode()}", flush=True)
+    finally:
+        g.close()
+
+
 def main():
     from treeqp_amd import capi, problems as P
     args = sys.argv[1:]
@@ -1386,6 +1507,14 @@ def main():
             adjoint_compare(capi, "c1", P.spring_mass(), False, steps, skip)
         if "c2" in names:
             adjoint_compare(capi, "c2", P.linear_chain(2, 9, 9), True, steps, skip)
+        return
+    if "--predict-at" in args or "--tangent" in args:
+        fn, what = (predict_at_compare, "predict-at") if "--predict-at" in args else (tangent_compare, "tangent")
+        for nm, p in (("c1", P.spring_mass()), ("c2", P.linear_chain(2, 9, 9))):
+            if nm in names:
+                fn(capi, nm, p, steps, skip)
+        if "kind3" in names:
+            refused_kind3(capi, what)
         return
     if "--predict" in args:
         for nm, p in (("c1", P.spring_mass()), ("c2", P.linear_chain(2, 9, 9))):

@@ -1117,6 +1117,57 @@ class TqGpu:
         self._chk(lib().tqgpu_mpc_get_adjoint(self.h, _dp(out["gq"]), _dp(out["gr"]), _dp(out["gb"])))
         return {key: out[key][:n * nw].reshape((n, nw), order="F") for key, n in sizes}
 
+    # ---- the tangent of an MPC step along directions in q, r, b, x0 (tqgpu_mpc_tangent), and the predictor built on it (tqgpu_mpc_predict_at) ----
+    def mpc_tangent(self, dq=None, dr=None, db=None, dx0=None, profile=0, **kw) -> dict:
+        """Tangent of the last solve's point, active set frozen (tqgpu_mpc_tangent): dq (sum_nx, nd), dr (sum_nu, nd), db (sum_lam, nd) and dx0
+        (nx0, nd) are directions in the flat layouts of q, r, b and x0, None meaning zero, a 1-D array one column.  Returns dict(du0 (nu[0], nd),
+        n_reg); dx, du, dlam stay on the device (mpc_tangent_values).  The options give the regularisation rule where the call has to factorise."""
+        nd, arrs = None, []
+        for a, rows in ((dq, int(self.sum_nx)), (dr, int(self.sum_nu)), (db, int(self.sum_lam)), (dx0, int(self.nx0))):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            a = a.reshape((rows, -1), order="F") if a.ndim == 1 else a
+            assert a.shape[0] == rows and (nd is None or a.shape[1] == nd), a.shape
+            nd = a.shape[1]
+            arrs.append(np.asfortranarray(a))
+        nd = 1 if nd is None else nd
+        n, nu0 = C.c_int(0), int(self.nu[0])
+        o = _gpu_opts(profile, **kw)
+        ptr = [None if a is None else a.ctypes.data_as(c_dbl_p) for a in arrs]
+        self._chk(lib().tqgpu_mpc_tangent(self.h, C.byref(o), ptr[0], ptr[1], ptr[2], ptr[3], int(nd), C.byref(n)))
+        self._tan_nd = int(nd)
+        return dict(du0=self.mpc_tangent_u0(), n_reg=n.value)
+
+    def mpc_tangent_u0(self) -> np.ndarray:
+        """du0 (nu[0], nd) of the last mpc_tangent or mpc_predict_at (tqgpu_mpc_get_tangent_u0; host state only)."""
+        nd, nu0 = self.__dict__.get("_tan_nd", 1), int(self.nu[0])
+        g = np.zeros(max(nu0 * nd, 1))
+        self._chk(lib().tqgpu_mpc_get_tangent_u0(self.h, _dp(g)))
+        return g[:nu0 * nd].reshape((nu0, nd), order="F")
+
+    def mpc_tangent_values(self) -> dict:
+        """dx (sum_nx, nd), du (sum_nu, nd), dlam (sum_lam, nd) of the last mpc_tangent or mpc_predict_at: column j is the flat layout of
+        get_solution (tqgpu_mpc_get_tangent; downloads and waits)."""
+        sizes = (("dx", int(self.sum_nx)), ("du", int(self.sum_nu)), ("dlam", int(self.sum_lam)))
+        nd = self.__dict__.get("_tan_nd", 1)          # (a stale count meets a refusal: the stored tangent went with what made it stale)
+        out = {key: np.zeros(max(n * nd, 1)) for key, n in sizes}
+        self._chk(lib().tqgpu_mpc_get_tangent(self.h, _dp(out["dx"]), _dp(out["du"]), _dp(out["dlam"])))
+        return {key: out[key][:n * nd].reshape((n, nd), order="F") for key, n in sizes}
+
+    def mpc_predict_at(self, x0_new=None, t0=-1, duals: bool = False, profile=0, **kw) -> dict:
+        """The change the next mpc_step(x0_new, t0=t0) will fold in, as one direction built on the device, and the tangent along it
+        (tqgpu_mpc_predict_at): dict(u0 = u0* + du0 clipped into the root's bounds on a root of kind 0, n_clipped, n_reg).  duals: the same
+        call writes lam* + dlam into the start buffer, for one solve.  Neither the window nor x0 moves."""
+        a = None if x0_new is None else _f64(x0_new)
+        assert a is None or len(a) == self.nx0
+        u0, nc, nr = np.zeros(max(int(self.nu[0]), 1)), C.c_int(0), C.c_int(0)
+        o = _gpu_opts(profile, **kw)
+        self._chk(lib().tqgpu_mpc_predict_at(self.h, C.byref(o), _dp(a), int(t0), _dp(u0), int(bool(duals)), C.byref(nc), C.byref(nr)))
+        self._tan_nd = 1
+        return dict(u0=u0[:int(self.nu[0])], n_clipped=nc.value, n_reg=nr.value)
+
     # ---- the adjoint in H, A, B: outer products summed over parameter groups (tqgpu_mpc_adjoint_matrices) ----
     def mpc_set_param_groups(self, hgroup=None, cgroup=None):
         """The parameter groups of mpc_adjoint_matrices (tqgpu_mpc_set_param_groups): hgroup[k], cgroup[c] in [-1, groups), -1 meaning in

@@ -1,9 +1,9 @@
 /*
  * tdunes_adjoint.hpp -- the host side of the derivatives of an MPC step, in the host part: the entry points tqgpu_mpc_sensitivity, tqgpu_mpc_adjoint,
  * tqgpu_mpc_adjoint_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, tqgpu_mpc_adjoint_bounds,
- * tqgpu_mpc_adjoint_reference, and the readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
+ * tqgpu_mpc_adjoint_reference, tqgpu_mpc_tangent, tqgpu_mpc_predict_at, and the readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*, _get_tangent*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
  * Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind tdunes_mpc.hpp (mpc_refuse, mpc_take_x0, MpcLive) and tdunes_kkt.hpp
- * (enqueue_export, export_all_entry).  tdunes_mirror.hpp keeps the mirror's records MpcSens, MpcAdjBatch, MpcAdjMat, tdunes_device.hip the plan of a batched call
+ * (enqueue_export, export_all_entry).  tdunes_mirror.hpp keeps the mirror's records MpcSens, MpcTan, MpcAdjBatch, MpcAdjMat, tdunes_device.hip the plan of a batched call
  * (DeviceGroup .. order_behind_lead).
  */
 #pragma once
@@ -1191,5 +1191,187 @@ extern "C" int tqgpu_mpc_predict_batch(tqgpu_solver **solvers, int n, const doub
             io += nx0 + nu0 + 1;
         }
     }
+    return TQGPU_OK;
+}
+
+/* ---- the tangent of an MPC step (tdunes_sens.hpp: k_tan_rhs, k_tan_primal, k_tan_apply around the adjoint's two sweeps): dz, dlam along nd directions
+ * (dq, dr, db, dx0) at the point of the last solve, and the predictor that builds its one direction on the device ---- */
+namespace {
+/* the tangent's buffers, on first use and again when nd grows or nx0 changed: one zeroed device block, the pinned block, the LDS windows */
+int setup_tan(tqgpu_solver *s, int nd) {
+    int rc;
+    MpcTan &m = s->tan;
+    const size_t snx = (size_t)s->sum_nx, snu = (size_t)s->sum_nu, nxe = snx - (size_t)s->x_pad, sl = (size_t)s->sum_lam, nx0 = (size_t)s->mpc.nx0, nu0 = (size_t)s->nu[0];
+    if (!m.d || nd > m.nd_cap || m.nx0 != s->mpc.nx0) {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        s->mem.release(m.d); s->mem.release(m.h);
+        s->sens.tan_valid = false; m.nd_cap = 0;
+        const size_t cap = (size_t)nd, staged = (nxe + snu + sl + nx0) * cap, io = nu0 * cap + 1 + nx0 + nu0 + 2;
+        size_t off = 0;
+        auto take = [&](size_t n) { const size_t o = off; off += (n + 1) / 2 * 2; return o; };
+        const size_t os = take(staged), oY = take(snx * cap), ot = take(snx * cap), ox = take(snx * cap), ou = take(snu * cap), ol = take(snx * cap), oh = take(nu0 * cap + 1);
+        if ((rc = s->mem.zeroed(m.d, sizeof(double) * std::max<size_t>(off, 2), TQGPU_ENOMEM, "the tangent")) ||
+            (rc = s->mem.host(m.h, sizeof(double) * (staged + io + 2), "the pinned directions and du0")))
+            return rc;
+        memset(m.h, 0, sizeof(double) * (staged + io + 2));
+        size_t lds = 0;
+        for (int k = 0; k < s->Nn; k++) lds = std::max(lds, (2 * (size_t)(s->nx[k] + s->nu[k]) + 2) * sizeof(double));
+        if ((rc = allow_lds(k_tan_rhs, lds)) || (rc = allow_lds(k_adj_backward, s->pp.lds_forward)) || (rc = allow_lds(k_adj_forward, s->pp.lds_forward)) || (rc = allow_lds(k_tan_primal, lds)))
+            return rc;
+        Tan &X = m.v;
+        X = Tan{};
+        double *p = m.d;
+        m.stage_d = p + os;
+        X.a.Y = p + oY; X.a.t = p + ot; X.a.gq = p + ox; X.a.gr = p + ou; X.a.gb = p + ol; X.a.head = p + oh;
+        X.a.nxe = (int)nxe; X.sum_lam = s->sum_lam;
+        m.io = m.h + staged;
+        m.nd_cap = nd; m.nx0 = s->mpc.nx0; m.lds = lds;
+    }
+    m.v.a.nw = nd;
+    return TQGPU_OK;
+}
+/* where the head, x0_new and the predictor's results lie in the pinned block */
+double *tan_io_x0(const tqgpu_solver *s) { return s->tan.io + (size_t)s->nu[0] * (size_t)s->tan.nd_cap + 1; }
+double *tan_io_out(const tqgpu_solver *s) { return tan_io_x0(s) + (size_t)s->mpc.nx0; }
+int tan_need(const tqgpu_solver *s, const char *who) {
+    if (!s->sens.tan_valid) return fail(TQGPU_EINVAL, std::string(who) + ": no tangent has been computed for the point and the data the device holds now (tqgpu_mpc_tangent or tqgpu_mpc_predict_at after the last solve, upload and fold)");
+    return TQGPU_OK;
+}
+/* what the tangent refuses beyond sens_refuse, before anything is touched: the windows of the adjoint (nd for nw) and of the factorisation */
+int tan_window_refuse(const tqgpu_solver *s, int nd) {
+    int rc;
+    size_t lf, lp;
+    if ((rc = adj_window_refuse(s, nd)) || (rc = sens_window_refuse(s, lf, lp))) return rc;
+    return TQGPU_OK;
+}
+/* the launches behind the direction: [the factor, where none is stored] k_tan_rhs, the adjoint's two sweeps on the tangent's Y and t, k_tan_primal.
+ * S: the view the launches took, kept for tan_store behind the wait */
+int tan_enqueue(tqgpu_solver *s, const Opts &O, const Tan &X, Sens &S) {
+    int rc;
+    MpcSens &m = s->sens;
+    S = m.v;
+    if (!m.factored && (rc = sens_enqueue_factor(s, O, S))) return rc;
+    const Tree &T = s->T;
+    hipStream_t st = s->stream;
+    const Adj A = X.a;
+    const unsigned cols = (unsigned)A.nw;
+    hipLaunchKernelGGL(k_tan_rhs, dim3(T.Np, cols), dim3(WAVE), s->tan.lds, st, T, s->D, S, X);
+    for_levels(s, Walk::to_root, [&](int first, int count) { hipLaunchKernelGGL(k_adj_backward, dim3(count, cols), dim3(WAVE), s->pp.lds_forward, st, T, S, A, first); });
+    for_levels(s, Walk::to_leaves, [&](int first, int count) { hipLaunchKernelGGL(k_adj_forward, dim3(count, cols), dim3(WAVE), s->pp.lds_forward, st, T, S, A, first); });
+    hipLaunchKernelGGL(k_tan_primal, dim3(T.Nn, cols), dim3(WAVE), s->tan.lds, st, T, s->D, S, X);
+    HIP_TRY(hipGetLastError());
+    MPC_COUNT(launches, 1 + T.Nh + (T.Nh - 1) + 1);
+    return TQGPU_OK;
+}
+/* a finished tangent onto its mirror, behind the wait: the factor counts as stored, a stored sensitivity and a stored adjoint stay as they were */
+void tan_store(tqgpu_solver *s, const Sens &S, const Tan &X, int nd, int *n_reg) {
+    s->sens.v = S; s->sens.factored = true; s->sens.tan_valid = true;
+    s->tan.v = X; s->tan.nd = nd;
+    if (n_reg) *n_reg = (int)s->tan.io[(size_t)s->nu[0] * (size_t)nd];
+}
+}  // namespace
+
+extern "C" int tqgpu_mpc_tangent(tqgpu_solver *s, const tqgpu_opts *o, const double *dq, const double *dr, const double *db, const double *dx0, int nd, int *n_reg) {
+    const char *who = "tqgpu_mpc_tangent";
+    int rc;
+    if ((rc = sens_refuse(s, o, who))) return rc;
+    if (nd < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nd must be at least 1");
+    if (!dq && !dr && !db && !dx0) return fail(TQGPU_EINVAL, std::string(who) + ": no direction (dq, dr, db and dx0 are all NULL)");
+    if ((rc = tan_window_refuse(s, nd))) return rc;
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    if ((rc = setup_sens(s)) || (rc = setup_tan(s, nd))) return rc;
+    s->sens.tan_valid = false;
+    MpcTan &m = s->tan;
+    const size_t nw = adj_w_doubles(s, nd), nb = db ? (size_t)s->sum_lam * nd : 0, n0 = dx0 ? (size_t)s->mpc.nx0 * nd : 0, nu0 = (size_t)s->nu[0];
+    hipStream_t st = s->stream;
+    /* the directions through pinned memory in one copy: [dq | dr] as the adjoint's w (a missing one as zeros), then db and dx0 where given */
+    adj_stage_w(s, m.h, dq, dr, nd);
+    if (nb) memcpy(m.h + nw, db, sizeof(double) * nb);
+    if (n0) memcpy(m.h + nw + nb, dx0, sizeof(double) * n0);
+    if (nw + nb + n0) { HIP_TRY(hipMemcpyAsync(m.stage_d, m.h, sizeof(double) * (nw + nb + n0), hipMemcpyHostToDevice, st)); }
+    MPC_COUNT(copies, 1);
+    Tan X = m.v;
+    X.built = 0; X.x0_new = nullptr; X.xtraj = X.utraj = nullptr; X.stage = nullptr;
+    X.a.wx = m.stage_d; X.a.wu = m.stage_d + (size_t)X.a.nxe * (size_t)nd;
+    X.db = nb ? m.stage_d + nw : nullptr; X.dx0 = n0 ? m.stage_d + nw + nb : nullptr;
+    Sens S;
+    if ((rc = tan_enqueue(s, O, X, S))) return rc;
+    HIP_TRY(hipMemcpyAsync(m.io, X.a.head, sizeof(double) * (nu0 * nd + 1), hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
+    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
+    tan_store(s, S, X, nd, n_reg);
+    return TQGPU_OK;
+}
+
+extern "C" int tqgpu_mpc_get_tangent_u0(tqgpu_solver *s, double *du0) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_tangent_u0")) || (rc = tan_need(s, "tqgpu_mpc_get_tangent_u0"))) return rc;
+    const size_t n = (size_t)s->nu[0] * (size_t)s->tan.nd;
+    if (du0 && n) memcpy(du0, s->tan.io, sizeof(double) * n);
+    return TQGPU_OK;
+}
+
+/* a diagnostic download (whole buffers through pageable memory, repacked on the host): not counted into tqgpu_mpc_stats */
+extern "C" int tqgpu_mpc_get_tangent(tqgpu_solver *s, double *dx, double *du, double *dlam) {
+    int rc;
+    if ((rc = mpc_refuse(s, "tqgpu_mpc_get_tangent")) || (rc = tan_need(s, "tqgpu_mpc_get_tangent"))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t nd = (size_t)s->tan.nd, snu = (size_t)s->sum_nu;
+    const Adj &A = s->tan.v.a;
+    if (dx && (rc = download_columns(s, A.gq, nd, (size_t)s->x_pad, (size_t)(s->sum_nx - s->x_pad), dx))) return rc;      /* phantom root states are left out */
+    if (dlam && (rc = download_columns(s, A.gb, nd, (size_t)s->nx0, (size_t)s->sum_lam, dlam))) return rc;                  /* the root has no dual */
+    if (du && snu * nd) HIP_TRY(hipMemcpy(du, A.gr, sizeof(double) * snu * nd, hipMemcpyDeviceToHost));
+    return TQGPU_OK;
+}
+
+/* one direction built on the device (Tan::built): x0_new in and [u0_pred | n_clipped | n_reg] back through the pinned block, which k_tan_rhs, k_tan_primal
+ * and k_tan_apply read and write in place; the head [du0 | n_reg] in one copy, for tqgpu_mpc_get_tangent_u0 */
+extern "C" int tqgpu_mpc_predict_at(tqgpu_solver *s, const tqgpu_opts *o, const double *x0_new, int t0_new, double *u0_pred, int duals, int *n_clipped, int *n_reg) {
+    const char *who = "tqgpu_mpc_predict_at";
+    int rc;
+    if ((rc = sens_refuse(s, o, who)) || (rc = mpc_take_window(s, t0_new, false, who))) return rc;
+    if (t0_new >= 0 && s->trk.t0 < 0) return fail(TQGPU_EINVAL, std::string(who) + ": no window is in force yet (tqgpu_mpc_set_window, tqgpu_mpc_step_at): there is no reference row to measure the move from");
+    if ((rc = tan_window_refuse(s, 1))) return rc;
+    Opts O;
+    if ((rc = opts_from(o, O))) return rc;
+    SETTLE(s);
+    HIP_TRY(hipSetDevice(s->device));
+    MpcLive live;
+    if ((rc = setup_sens(s)) || (rc = setup_tan(s, 1))) return rc;
+    s->sens.tan_valid = false;
+    MpcTan &m = s->tan;
+    const size_t nx0 = (size_t)s->mpc.nx0, nu0 = (size_t)s->nu[0];
+    hipStream_t st = s->stream;
+    double *x0n = tan_io_x0(s), *out = tan_io_out(s);
+    if (x0_new && nx0) memcpy(x0n, x0_new, sizeof(double) * nx0);
+    Tan X = m.v;
+    X.built = 1; X.db = X.dx0 = nullptr; X.a.wx = X.a.wu = nullptr;
+    X.x0_new = x0_new ? x0n : nullptr;
+    X.xtraj = X.utraj = nullptr; X.stage = nullptr;
+    if (t0_new >= 0) {
+        const double *p = s->trk.d;
+        X.xtraj = p; p += (size_t)s->trk.T * s->trk.nxt; X.utraj = p; p += (size_t)s->trk.T * s->trk.nut;
+        p += (size_t)s->sum_nx + (size_t)s->sum_nu;          /* q0, r0: the bases drop out of the difference */
+        X.stage = reinterpret_cast<const int *>(p);
+        X.t0 = s->trk.t0; X.t1 = t0_new; X.Tn = s->trk.T; X.nxt = s->trk.nxt; X.nut = s->trk.nut;
+    }
+    Sens S;
+    if ((rc = tan_enqueue(s, O, X, S))) return rc;
+    double *keep = nullptr;
+    if ((rc = predict_keep(s, duals, keep))) return rc;
+    hipLaunchKernelGGL(k_tan_apply, dim3(duals ? 1 + (unsigned)s->Nn : 1u), dim3(WAVE), 0, st, s->T, s->D, S, X, s->d_lam_init, keep, out);
+    HIP_TRY(hipGetLastError()); MPC_COUNT(launches, 1);
+    predict_lent(s, duals);
+    HIP_TRY(hipMemcpyAsync(m.io, X.a.head, sizeof(double) * (nu0 + 1), hipMemcpyDeviceToHost, st)); MPC_COUNT(copies, 1);
+    HIP_TRY(hipStreamSynchronize(st)); MPC_COUNT(waits, 1);
+    tan_store(s, S, X, 1, nullptr);
+    if (u0_pred && nu0) memcpy(u0_pred, out, sizeof(double) * nu0);
+    if (n_clipped) *n_clipped = (int)out[nu0];
+    if (n_reg) *n_reg = (int)out[nu0 + 1];
     return TQGPU_OK;
 }

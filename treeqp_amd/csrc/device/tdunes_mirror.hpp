@@ -98,7 +98,7 @@ struct MpcBatchBuf {
 /* tracking (tqgpu_mpc_set_tracking): d, [xtraj T x NXT | utraj T x NUT | q0 (sum_nx, node-indexed as Data::q, phantom root states included) |
  * r0 (sum_nu)] in one device block, the nodes' stages behind it as ints; t0: the window the device's q, r were last folded for (-1: none yet) */
 struct MpcTrack { double *d = nullptr; int T = 0, nxt = 0, nut = 0, t0 = -1; };
-/* ---- what a mirror keeps for the derivatives of an MPC step (tdunes_adjoint.hpp; kernels in tdunes_sens.hpp): MpcSens, MpcAdjBatch, MpcSensBatch, MpcAdjMat ---- */
+/* ---- what a mirror keeps for the derivatives of an MPC step (tdunes_adjoint.hpp; kernels in tdunes_sens.hpp): MpcSens, MpcTan, MpcAdjBatch, MpcSensBatch, MpcAdjMat ---- */
 /* tqgpu_mpc_sensitivity: buffers of its own (setup_sens, on first use; one device block d, views in v); pinned h:
  * [head: K (nu0 x nx0) | u0 (nu0) | x0_ref (nx0) | n_reg] [x0_new (nx0)] [u0_pred (nu0) | n_clipped]; valid: the stored sensitivity
  * belongs to the point and the data the device holds now (cleared by every upload, fold, window move and solve) */
@@ -113,7 +113,16 @@ struct MpcSens {
     double *ad = nullptr, *ah = nullptr; Adj a{}; int nw_cap = 0, nw = 0, adj_nx0 = 0;
     bool adj_valid = false;
     size_t lds_rhs = 0, lds_grad = 0;
-    void invalidate() { valid = factored = adj_valid = false; }      /* every upload, fold, window move and solve */
+    bool tan_valid = false;             /* the stored tangent (MpcTan) belongs to the point and the data the device holds now */
+    void invalidate() { valid = factored = adj_valid = tan_valid = false; }      /* every upload, fold, window move and solve */
+};
+/* tqgpu_mpc_tangent / tqgpu_mpc_predict_at: buffers of its own (setup_tan, on first use and again when nd grows or nx0 changed; one device block d,
+ * views in v); pinned h: [the staged directions dq | dr | db | dx0, those given, nd columns each] and, at io, [head: du0 (nu0 x nd) | n_reg]
+ * [x0_new (nx0)] [u0_pred (nu0) | n_clipped | n_reg]; nd: the columns of the stored tangent (MpcSens::tan_valid says whether it is current) */
+struct MpcTan {
+    double *d = nullptr, *h = nullptr, *io = nullptr; Tan v{}; int nd_cap = 0, nd = 0, nx0 = 0;
+    double *stage_d = nullptr;          /* where the staged directions go on the device: (nxe + sum_nu + sum_lam + nx0) x nd_cap doubles */
+    size_t lds = 0;                     /* the window of k_tan_rhs and k_tan_primal */
 };
 /* tqgpu_mpc_adjoint_batch, batched route (the first member of a device's group owns all three): desc, the descriptors (AItem) with the members'
  * level tables behind them, uploaded with every call in one copy; w, the loss gradients of all members, [wx | wu] member after member, one
@@ -397,7 +406,7 @@ struct tqgpu_solver {
     char *h_in = nullptr; size_t in_off0 = 0, in_bytes = 0; bool in_valid = false;
     double *h_lam = nullptr; bool lam_valid = false;
     Export out; Kkt kkt;                /* the packed solution and its export state; the buffers of the KKT check (tdunes_kkt.hpp) */
-    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcAdjBatch adjb; MpcSensBatch sensb; MpcAdjMat adjm; MpcNodeSum bsum, rsum;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, sensb, adjm: tdunes_adjoint.hpp), one record per feature */
+    MpcRoot mpc; MpcWarm warm; MpcShift shift; MpcBatchBuf mpcb; MpcTrack trk; MpcSens sens; MpcTan tan; MpcAdjBatch adjb; MpcSensBatch sensb; MpcAdjMat adjm; MpcNodeSum bsum, rsum;      /* the MPC family (tdunes_mpc.hpp; sens, adjb, sensb, adjm: tdunes_adjoint.hpp), one record per feature */
     int x_pad = 0, A_pad = 0; /* phantom root states of an x0-eliminated tree embedded in a uniform one (doubles in front of x-sized arrays / of A) */
     unsigned long uid = 0;                                                /* unique per mirror of this process (an address can come back) */
     BatchLinks links;               /* this mirror as a member of a batch launch (tqgpu_solve_batch) */

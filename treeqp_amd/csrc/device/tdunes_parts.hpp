@@ -22,7 +22,7 @@
 #define TQP_GPD     0x200   /* g_persist_dense: the single-workgroup solve with the dense stage solvers compiled in (tdunes_gpersist.hpp) */
 #define TQP_GPDB    0x400   /* g_persist_dense_batch: a part of its own -- in one translation unit with g_persist_dense the bodies have two callers, the inliner
                              * decides otherwise, and g_persist_dense comes out as another kernel than the one that was measured */
-#define TQP_SENS    0x800   /* k_sens_hess, k_sens_factor, k_sens_forward, k_sens_primal, k_mpc_predict, k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad and the batch forms of the adjoint's six and of the sensitivity's forward sweep and primal kernel, k_*_batch over AItem, k_mpc_predict_batch over PredItem, k_adjmat_part, k_adjmat_sum and their batch forms over AMItem, k_nodesum_part, k_nodesum_sum (tdunes_sens.hpp; launched from tdunes_adjoint.hpp in the host part) */
+#define TQP_SENS    0x800   /* k_sens_hess, k_sens_factor, k_sens_forward, k_sens_primal, k_mpc_predict, k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad and the batch forms of the adjoint's six and of the sensitivity's forward sweep and primal kernel, k_*_batch over AItem, k_mpc_predict_batch over PredItem, k_adjmat_part, k_adjmat_sum and their batch forms over AMItem, k_nodesum_part, k_nodesum_sum, k_tan_rhs, k_tan_primal, k_tan_apply (tdunes_sens.hpp; launched from tdunes_adjoint.hpp in the host part) */
 #define TQP_ALL     0xFFF
 
 #ifndef TQ_PARTS

@@ -17,7 +17,9 @@
  *
  * The adjoint of a step (k_adj_rhs, k_adj_backward, k_adj_forward, k_adj_grad; struct Adj) is the reverse: one more solve with the same
  * factor, one right-hand side per column of w = dL/dz, non-zero in every block; its formulas stand with its kernels below.  The batch
- * forms at the end (struct AItem, k_*_batch) are the same bodies behind a look-up of the member.
+ * forms at the end (struct AItem, k_*_batch) are the same bodies behind a look-up of the member.  The tangent of a step (k_tan_rhs,
+ * k_tan_primal, k_tan_apply; struct Tan, last in this file) is the forward-mode twin of the adjoint: its own right-hand side and read-out
+ * around the adjoint's two sweeps.
  */
 #pragma once
 
@@ -1109,4 +1111,206 @@ __global__ void __launch_bounds__(WAVE) k_nodesum_sum(NodeSum N, int nw)
 ;
 #else
 { nodesum_sum_body(N, nw, blockIdx.x, blockIdx.y, threadIdx.x); }
+#endif
+
+/* ---- the tangent of a step (tqgpu_mpc_tangent, tqgpu_mpc_predict_at): the forward-mode twin of the adjoint, nd directions at once ----
+ *   dh_k = [dq_k; dr_k],   R_c = (P_c dh_c)^x - C_c P_p dh_p + db_c + G_c dx0   (G: the rows of the root's children, Sens::G),
+ *   M dLam = R with the factor k_sens_factor left, through k_adj_backward / k_adj_forward on Tan::a (Y, t: the tangent's own),
+ *   dZ_k = -P_k ( dh_k - [dLam_k; 0] + sum_c C_c' dLam_c ) + direct_k dx0,   direct_0 dx0 = -P_0 [0; S0 dx0] (eliminated root), [dx0; 0] (root with states).
+ * The order is fixed: R is adj_rhs_body's expression with w := dh, then + db_c where db was given, then one chain fma(G[., j], dx0[j], .), j
+ * ascending, where dx0 was given; dZ is adj_grad_body's chain for [gq; gr], then the direct term (S0 dx0: a chain from 0.0, j ascending; then
+ * fma(-P_0[i, nx + m], (S0 dx0)[m], .), m ascending).  A term that was not given is skipped.  With db and dx0 absent (dx, du, dlam) are therefore
+ * the (gq, gr, gb) of the adjoint for w = dh bit for bit.
+ * The direction is either staged (built == 0: a.wx, a.wu hold dq, dr as adj_stage_w lays them out; db, dx0 where given) or built on the
+ * device (built == 1, one column, tqgpu_mpc_predict_at): dx0[j] = x0_new[j] - x0_ref[j] (x0_new == nullptr: no dx0), and, where the window
+ * moves (xtraj != nullptr), for node k with row(t) = min(t + stage[k], Tn - 1), dxref = xtraj[row(t1)] - xtraj[row(t0)], duref likewise, dh_k is
+ * mpc_track_node's chain started from 0.0: kind 0 fma(-Qd[i], dxref[i], 0.0); kind 1 over row i of H_k, x columns then u columns; the u rows of
+ * an x0-eliminated root with S0 go on with fma(-S0[i, j], dxref[j], .) (mpc_track_root_r without its + S0 x0, which is direct_0's). */
+struct Tan {
+    Adj a;                             /* wx, wu: the staged dq, dr; Y, t: R / dLam in the making and t; gq, gr, gb: dx, du, dlam (node-indexed as the adjoint's); head: [du0 (nu0 x nd) | n_reg]; nw = nd */
+    const double *db, *dx0;            /* staged: sum_lam x nd, nx0 x nd, column major (nullptr: not given) */
+    const double *x0_new;              /* built: pinned (nullptr: dx0 is zero and skipped) */
+    const double *xtraj, *utraj;       /* built: the trajectory (nullptr: the window stays, dh = 0) */
+    const int *stage;
+    int built, t0, t1, Tn, nxt, nut, sum_lam;
+};
+__device__ __forceinline__ bool tan_has_dx0(const Tan &X) { return X.built ? X.x0_new != nullptr : X.dx0 != nullptr; }
+__device__ __forceinline__ double tan_dx0(const Data &D, const Sens &S, const Tan &X, int j, int col) {
+    if (!X.built) return X.dx0[j + (size_t)col * S.nx0];
+    return X.x0_new[j] - (S.root_states ? D.xmin[S.xpad + j] : S.x0[j]);
+}
+__device__ __forceinline__ int tan_row(const Tan &X, int k, int t) {
+    const int row = t + X.stage[k];
+    return row < X.Tn - 1 ? row : X.Tn - 1;
+}
+/* entry i of dh_k, i over [x | u]; phantom root states carry 0 */
+__device__ __forceinline__ double tan_w(const Tree &T, const Data &D, const Sens &S, const Tan &X, int k, int i, int col) {
+    if (!X.built) return adj_w(T, S, X.a, k, i, col);
+    const int nx = T.nx[k], nu = T.nu[k], nz = nx + nu, pad = k == 0 ? S.xpad : 0;
+    if (!X.xtraj || i < pad) return 0.0;
+    const int r1 = tan_row(X, k, X.t1), r0 = tan_row(X, k, X.t0);
+    const double *x1 = X.xtraj + (size_t)r1 * X.nxt, *x0 = X.xtraj + (size_t)r0 * X.nxt;
+    const double *u1 = X.utraj + (size_t)r1 * X.nut, *u0 = X.utraj + (size_t)r0 * X.nut;
+    if (sens_kind(D, k) == 0)
+        return i < nx ? fma(-D.Qd[T.xoff[k] + i], x1[i - pad] - x0[i - pad], 0.0) : fma(-D.Rd[T.uoff[k] + i - nx], u1[i - nx] - u0[i - nx], 0.0);
+    const double *H = D.Hd + D.poff[k];
+    double v = 0.0;
+    for (int j = 0; j < nx - pad; j++) v = fma(-H[i + (size_t)(pad + j) * nz], x1[j] - x0[j], v);
+    for (int j = 0; j < nu; j++) v = fma(-H[i + (size_t)(nx + j) * nz], u1[j] - u0[j], v);
+    if (k == 0 && i >= nx && !S.root_states && S.S0)
+        for (int j = 0; j < S.nx0; j++) v = fma(-S.S0[(i - nx) + (size_t)j * nu], x1[j] - x0[j], v);
+    return v;
+}
+/* entry i of P_k w, w the nz staged entries of dh_k: adj_pw's arithmetic */
+__device__ __forceinline__ double tan_pw(const Tree &T, const Data &D, const Sens &S, int k, int i, const double *w) {
+    const int nx = T.nx[k], nz = nx + T.nu[k];
+    if (sens_kind(D, k) == 0) return (i < nx ? S.Px[T.xoff[k] + i] : S.Pu[T.uoff[k] + i - nx]) * w[i];
+    const double *P = D.Pd + D.poff[k];
+    double acc = 0.0;
+    for (int m = 0; m < nz; m++) acc = fma(P[i + (size_t)m * nz], w[m], acc);
+    return acc;
+}
+
+/* ---- k_tan_rhs: one wave per (parent block p, column): the rows of p's children of R.  LDS: pv (nz of p), w (the largest nz) ---- */
+__device__ void tan_rhs_body(const Tree &T, const Data &D, const Sens &S, const Tan &X, int p, int col, int lane, double *lds) {
+    const int nxp = T.nx[p], nup = T.nu[p], nz = nxp + nup, k0 = T.kid0[p];
+    double *pv = lds;                     /* nz: P_p dh_p */
+    double *w = lds + nz;                 /* dh of p, then of each child in turn */
+    for (int i = lane; i < nz; i += WAVE) w[i] = tan_w(T, D, S, X, p, i, col);
+    WSYNC();
+    for (int i = lane; i < nz; i += WAVE) pv[i] = tan_pw(T, D, S, p, i, w);
+    WSYNC();
+    double *R = X.a.Y + (size_t)col * S.sum_nx;
+    const bool with_dx0 = p == 0 && tan_has_dx0(X);
+    const int d0 = T.bdim[0], b0 = T.xoff[T.kid0[0]];          /* b0: the root's rows, which the flat layout of b does not have */
+    for (int cc = 0; cc < T.nk[p]; cc++) {
+        const int kid = k0 + cc, nxc = T.nx[kid], nzc = nxc + T.nu[kid];
+        const double *Ac = D.A + T.aoff[kid], *Bc = D.B + T.boff[kid];
+        for (int i = lane; i < nzc; i += WAVE) w[i] = tan_w(T, D, S, X, kid, i, col);
+        WSYNC();
+        for (int i = lane; i < nxc; i += WAVE) {
+            double acc = 0.0;
+            for (int m = 0; m < nxp; m++) acc = fma(Ac[i + (size_t)m * nxc], pv[m], acc);
+            for (int m = 0; m < nup; m++) acc = fma(Bc[i + (size_t)m * nxc], pv[nxp + m], acc);
+            double v = tan_pw(T, D, S, kid, i, w) - acc;
+            if (X.db) v = v + X.db[T.xoff[kid] - b0 + i + (size_t)col * X.sum_lam];
+            if (with_dx0) {
+                const int row = T.xoff[kid] - T.xoff[k0] + i;
+                for (int j = 0; j < S.nx0; j++) v = fma(S.G[row + (size_t)j * d0], tan_dx0(D, S, X, j, col), v);
+            }
+            R[T.xoff[kid] + i] = v;
+        }
+        WSYNC();
+    }
+}
+
+/* ---- k_tan_primal: one wave per (node, column): dx, du, dlam; node 0 also du0 and, in column 0, n_reg into the head.  LDS: v (nz), w (nz) ---- */
+__device__ void tan_primal_body(const Tree &T, const Data &D, const Sens &S, const Tan &X, int k, int col, int lane, double *lds) {
+    const int nxk = T.nx[k], nuk = T.nu[k], nz = nxk + nuk, nx0 = S.nx0, pad = k == 0 ? S.xpad : 0;
+    const int xo = T.xoff[k], uo = T.uoff[k], k0 = T.kid0[k], nkids = k < T.Np ? T.nk[k] : 0;
+    const Adj &A = X.a;
+    double *v = lds;                      /* nz: dh_k - [dLam_k; 0] + sum_c C_c' dLam_c */
+    double *s0 = lds + nz;                /* nu0: S0 dx0 (node 0 of an eliminated root with S0) */
+    const double *Y = A.Y + (size_t)col * S.sum_nx;
+    for (int i = lane; i < nz; i += WAVE) {
+        double acc = 0.0;
+        for (int cc = 0; cc < nkids; cc++) {
+            const int kid = k0 + cc, nxc = T.nx[kid];
+            const double *Cc = i < nxk ? D.A + T.aoff[kid] + (size_t)i * nxc : D.B + T.boff[kid] + (size_t)(i - nxk) * nxc;
+            const double *yc = Y + T.xoff[kid];
+            for (int r = 0; r < nxc; r++) acc = fma(Cc[r], yc[r], acc);
+        }
+        v[i] = tan_w(T, D, S, X, k, i, col) - (k > 0 && i < nxk ? Y[xo + i] : 0.0) + acc;
+    }
+    const bool with_dx0 = k == 0 && tan_has_dx0(X), with_s0 = with_dx0 && !S.root_states && S.S0;
+    if (with_s0) for (int m = lane; m < nuk; m += WAVE) {
+        double acc = 0.0;
+        for (int j = 0; j < nx0; j++) acc = fma(S.S0[m + (size_t)j * nuk], tan_dx0(D, S, X, j, col), acc);
+        s0[m] = acc;
+    }
+    WSYNC();
+    const int kind = sens_kind(D, k);
+    for (int i = lane; i < nz; i += WAVE) {
+        double r;
+        if (kind == 0) r = (i < nxk ? S.Px[xo + i] : S.Pu[uo + i - nxk]) * v[i];
+        else {
+            const double *P = D.Pd + D.poff[k];
+            r = 0.0;
+            for (int m = 0; m < nz; m++) r = fma(P[i + (size_t)m * nz], v[m], r);
+        }
+        r = -r;
+        if (with_s0 && kind != 0) {
+            const double *P = D.Pd + D.poff[k];
+            for (int m = 0; m < nuk; m++) r = fma(-P[i + (size_t)(nxk + m) * nz], s0[m], r);
+        }
+        if (with_dx0 && S.root_states && i >= pad && i < nxk) r = r + tan_dx0(D, S, X, i - pad, col);
+        if (i < nxk) A.gq[xo + i + (size_t)col * S.sum_nx] = r;
+        else {
+            A.gr[uo + i - nxk + (size_t)col * S.sum_nu] = r;
+            if (k == 0) A.head[(i - nxk) + (size_t)col * nuk] = r;
+        }
+    }
+    if (k > 0) {
+        for (int i = lane; i < nxk; i += WAVE) A.gb[xo + i + (size_t)col * S.sum_nx] = Y[xo + i];
+        return;
+    }
+    if (col == 0 && lane == 0) A.head[(size_t)nuk * A.nw] = (double)*S.n_reg;
+}
+
+/* ---- k_tan_apply (tqgpu_mpc_predict_at): block 0: u0_pred[i] = u0*[i] + du0[i], clipped into [umin[0], umax[0]] on a root of kind 0; blocks 1 + k
+ * (duals != 0): entry e of node k of the start buffer = the current dual + dLam[e] (lam_keep: the entry it replaces is saved first).
+ * out: pinned, [u0_pred (nu0) | n_clipped | n_reg] ---- */
+__device__ void tan_apply_body(const Tree &T, const Data &D, const Sens &S, const Tan &X, double *lam_init, double *lam_keep, double *out, int blk, int lane) {
+    const int nu0 = S.nu0;
+    if (blk == 0) {
+        const bool clip = sens_kind(D, 0) == 0;
+        int moved = 0;
+        for (int i0 = 0; i0 < nu0; i0 += WAVE) {
+            const int i = i0 + lane;
+            bool mv = false;
+            if (i < nu0) {
+                double w = S.u[i] + X.a.gr[i];
+                if (clip) {
+                    const double lo = D.umin[i], hi = D.umax[i];
+                    if (w < lo) { w = lo; mv = true; } else if (w > hi) { w = hi; mv = true; }
+                }
+                out[i] = w;
+            }
+            moved += __popcll(__builtin_amdgcn_ballot_w64(mv));
+        }
+        if (lane == 0) { out[nu0] = (double)moved; out[nu0 + 1] = (double)*S.n_reg; }
+        return;
+    }
+    const int k = blk - 1, xo = T.xoff[k];
+    const double *src = D.ctrl->cur ? D.lam1 : D.lam0;
+    for (int e = lane; e < T.nx[k]; e += WAVE) {
+        const double w = src[xo + e] + X.a.gb[xo + e];
+        if (lam_keep) lam_keep[xo + e] = lam_init[xo + e];
+        lam_init[xo + e] = w;
+    }
+}
+
+__global__ void __launch_bounds__(WAVE) k_tan_rhs(Tree T, Data D, Sens S, Tan X)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    tan_rhs_body(T, D, S, X, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_tan_primal(Tree T, Data D, Sens S, Tan X)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    tan_primal_body(T, D, S, X, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+#endif
+__global__ void __launch_bounds__(WAVE) k_tan_apply(Tree T, Data D, Sens S, Tan X, double *lam_init, double *lam_keep, double *out)
+#if !TQ_HAS(TQP_SENS)
+;
+#else
+{ tan_apply_body(T, D, S, X, lam_init, lam_keep, out, blockIdx.x, threadIdx.x); }
 #endif
