@@ -3,8 +3,10 @@
  * tqgpu_mpc_adjoint_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_set_param_groups / _get_param_groups, tqgpu_mpc_adjoint_matrices, _batch, tqgpu_mpc_adjoint_bounds,
  * tqgpu_mpc_adjoint_reference, tqgpu_mpc_tangent, tqgpu_mpc_predict_at, and the readers tqgpu_mpc_get_gain, _get_sensitivities, _predict, _predict_batch, _get_adjoint*, _get_tangent*. Their kernels are tdunes_sens.hpp's (part TQP_SENS); k_adj_export_batch is the one kernel here.
  * Included once from tdunes_device.hip inside #if TQ_HAS(TQP_HOST), behind tdunes_mpc.hpp (mpc_refuse, mpc_take_x0, MpcLive) and tdunes_kkt.hpp
- * (enqueue_export, export_all_entry).  tdunes_mirror.hpp keeps the mirror's records MpcSens, MpcTan, MpcAdjBatch, MpcAdjMat, tdunes_device.hip the plan of a batched call
- * (DeviceGroup .. order_behind_lead).
+ * (enqueue_export, export_all_entry).  tdunes_mirror.hpp keeps the mirror's records MpcSens, MpcTan, MpcAdjBatch, MpcAdjMat, tdunes_device.hip the plan and the driver of a
+ * batched call (refuse_members, member_spans, plan_device_groups, order_behind_lead, run_device_groups): each of the four batched calls here is its refusals, its offsets and
+ * three callbacks (a group out, a member alone, a group back).  What the adjoint's and the sensitivity's groups share is DerivGroup (deriv_group_fill,
+ * deriv_group_launch_factor); a further batched derivative fills its own fields of the items between the two and adds its launches behind them.
  */
 #pragma once
 
@@ -318,56 +320,49 @@ __global__ void __launch_bounds__(256) k_adj_export_batch(const AItem *__restric
     export_all_entry(blockIdx.x * blockDim.x + threadIdx.x, it.nxe, it.nue, it.nl, it.x_pad, it.nx0, it.D, it.lamc, it.d_out);
 }
 
-struct AdjSpan { size_t wx, wu, gx0; };          /* where a member's blocks begin in the caller's wx, wu and gx0 */
-
-/* A group on its lead's stream: the descriptors and level tables in one copy, w of all members in one copy, the launches, the heads in one
- * copy; nothing is waited for here in the steady state (order_behind_lead, ADJ_ORDER).  views: per member the view its launches take,
- * kept for adj_store behind the wait */
-int adj_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> &views, const Opts &O, const double *wx, const double *wu, int nw, const std::vector<AdjSpan> &span) {
+/* ---- a batched group of derivatives on its lead's stream: what the adjoint's and the sensitivity's groups share.  deriv_group_fill: the descriptor block
+ * (AItem per member, the level tables behind them) with everything in it that the packing, k_sens_hess_batch and k_sens_factor_batch read, every member
+ * ordered behind the lead, the widths of the grids; deriv_group_launch_factor: the block up in one copy, then those launches.  A family adds its own fields
+ * to the items between the two, and its own launches and the copy of the heads behind them ---- */
+struct DerivGroup {
+    AItem *items, *d_items;          /* the descriptors in the lead's pinned block and on the device */
+    size_t bytes, n;                 /* of the block with the level tables; members */
+    /* widths of the grids: per launch the largest member's extent (0: no launch); _fac over the members that factorise only */
+    int np_all = 0, nn_all = 0, nh_all = 0, np_fac = 0, nh_fac = 0, cells = 0;
+    std::vector<int> wide_bwd, wide_fwd, wide_fac;          /* per level walking to the root, to the leaves, to the root */
+    size_t l_hess = 0, l_factor = 0, l_sweep = 0;
+};
+/* family: the lead's record that owns the block and the members' mark for order_behind_lead (adjb, sensb); needs_factor_of(s): whether member s builds its
+ * factor anew, and where the family drops the result it is about to replace; views: per member the view its launches take, kept for the store behind the
+ * wait.  The members' buffers are set up by the caller.  Nothing is waited for here in the steady state (order_behind_lead, ADJ_ORDER) */
+template <typename Batch, typename NeedsFactor>
+int deriv_group_fill(tqgpu_solver **v, const DeviceGroup &g, const Opts &O, Batch tqgpu_solver::*family, const char *what, NeedsFactor needs_factor_of, std::vector<Sens> &views, DerivGroup &G) {
     tqgpu_solver *lead = v[g.idx[0]];
-    const size_t n = g.idx.size();
+    Batch &B = lead->*family;
     int rc;
-    HIP_TRY(hipSetDevice(lead->device));
-    size_t w_all = 0, heads_all = 0, lvl_ints = 0;
-    for (int i : g.idx) {
-        tqgpu_solver *s = v[i];
-        if ((rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
-        w_all += adj_w_doubles(s, nw); heads_all += (size_t)s->sens.nx0 * nw + 1; lvl_ints += 2 * (size_t)s->T.Nh;
-    }
-    MpcAdjBatch &B = lead->adjb;
-    const size_t items_bytes = n * sizeof(AItem);
-    if ((rc = grow_items(lead, B.d_desc, B.h_desc, B.desc_cap, items_bytes + lvl_ints * sizeof(int), "the descriptors of a batched adjoint")) ||
-        (rc = grow_items(lead, B.d_w, B.h_w, B.w_cap, w_all, "the loss gradients of a batched adjoint")) ||
-        (rc = grow_items(lead, B.d_heads, B.h_heads, B.heads_cap, heads_all, "the heads of a batched adjoint")))
-        return rc;
-    AItem *items = reinterpret_cast<AItem *>(B.h_desc);
+    G = DerivGroup{};
+    G.n = g.idx.size();
+    const size_t items_bytes = G.n * sizeof(AItem);
+    G.bytes = items_bytes;
+    for (int i : g.idx) G.bytes += 2 * (size_t)v[i]->T.Nh * sizeof(int);
+    if ((rc = grow_items(lead, B.d_desc, B.h_desc, B.desc_cap, G.bytes, what))) return rc;
+    G.items = reinterpret_cast<AItem *>(B.h_desc); G.d_items = reinterpret_cast<AItem *>(B.d_desc);
     int *h_lvl = reinterpret_cast<int *>(B.h_desc + items_bytes);
     const int *d_lvl = reinterpret_cast<const int *>(B.d_desc + items_bytes);
-    /* widths of the grids: per launch the largest member's extent (0: no launch) */
-    int np_all = 0, np_fac = 0, nn_all = 0, cells = 0, nh_all = 0, nh_fac = 0;
-    size_t l_hess = 0, l_factor = 0, l_sweep = 0, l_rhs = 0, l_grad = 0;
-    std::vector<int> wide_bwd, wide_fac, wide_fwd;
     std::vector<hipStream_t> waited;
     int waits = 0;
-    size_t w_at = 0, h_at = 0, l_at = 0;
-    views.assign(n, Sens{});
-    for (size_t m = 0; m < n; m++) {
+    size_t l_at = 0;
+    views.assign(G.n, Sens{});
+    for (size_t m = 0; m < G.n; m++) {
         tqgpu_solver *s = v[g.idx[m]];
-        if ((rc = order_behind_lead(s, lead, s->adjb.drained_at, ADJ_ORDER, waited, waits))) return rc;
-        MpcSens &ms = s->sens;
-        ms.adj_valid = false;
+        if ((rc = order_behind_lead(s, lead, (s->*family).drained_at, ADJ_ORDER, waited, waits))) return rc;
         const ExportSizes z = export_sizes(s);
-        AItem &it = items[m];
+        AItem &it = G.items[m];
         it = AItem{};
         it.T = s->T; it.D = s->D; it.O = O;
-        it.needs_factor = ms.factored ? 0 : 1;
+        it.needs_factor = needs_factor_of(s) ? 1 : 0;
         it.needs_export = it.needs_factor && !s->out.valid ? 1 : 0;
-        it.S = views[m] = it.needs_factor ? sens_view_of_point(s) : ms.v;
-        it.A = ms.a;
-        it.A.wx = B.d_w + w_at; it.A.wu = it.A.wx + (size_t)z.nxe * (size_t)nw; it.A.head = B.d_heads + h_at;
-        const AdjSpan &at = span[(size_t)g.idx[m]];
-        adj_stage_w(s, B.h_w + w_at, wx ? wx + at.wx : nullptr, wu ? wu + at.wu : nullptr, nw);          /* w through the lead's pinned block */
-        w_at += adj_w_doubles(s, nw); h_at += (size_t)ms.nx0 * nw + 1;
+        it.S = views[m] = it.needs_factor ? sens_view_of_point(s) : s->sens.v;
         const int Nh = s->T.Nh;
         it.lvl = d_lvl + l_at;
         for (int l = 0; l < Nh; l++) { h_lvl[l_at + 2 * l] = s->lvl_first[l]; h_lvl[l_at + 2 * l + 1] = s->lvl_first[l + 1] - s->lvl_first[l]; }
@@ -375,44 +370,87 @@ int adj_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> 
         it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
         it.d_out = s->out.d;
         it.x_pad = s->x_pad; it.nxe = z.nxe; it.nue = z.nue; it.nl = z.nl; it.nx0 = s->nx0;
-        np_all = std::max(np_all, s->T.Np); nn_all = std::max(nn_all, s->T.Nn); nh_all = std::max(nh_all, Nh);
-        if ((int)wide_bwd.size() < Nh) { wide_bwd.resize(Nh, 0); wide_fwd.resize(Nh, 0); }
+        G.np_all = std::max(G.np_all, s->T.Np); G.nn_all = std::max(G.nn_all, s->T.Nn); G.nh_all = std::max(G.nh_all, Nh);
+        if ((int)G.wide_bwd.size() < Nh) { G.wide_bwd.resize(Nh, 0); G.wide_fwd.resize(Nh, 0); }
+        if (it.needs_factor && (int)G.wide_fac.size() < Nh) G.wide_fac.resize(Nh, 0);
         for (int l = 0; l < Nh; l++) {
             const int count = s->lvl_first[l + 1] - s->lvl_first[l];
-            wide_bwd[Nh - 1 - l] = std::max(wide_bwd[Nh - 1 - l], count);
-            if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
+            G.wide_bwd[Nh - 1 - l] = std::max(G.wide_bwd[Nh - 1 - l], count);
+            if (l >= 1) G.wide_fwd[l - 1] = std::max(G.wide_fwd[l - 1], count);
+            if (it.needs_factor) G.wide_fac[Nh - 1 - l] = std::max(G.wide_fac[Nh - 1 - l], count);
         }
-        l_sweep = std::max(l_sweep, s->pp.lds_forward); l_rhs = std::max(l_rhs, ms.lds_rhs); l_grad = std::max(l_grad, ms.lds_grad);
+        G.l_sweep = std::max(G.l_sweep, s->pp.lds_forward);
         if (it.needs_factor) {
-            np_fac = std::max(np_fac, s->T.Np); nh_fac = std::max(nh_fac, Nh);
-            if ((int)wide_fac.size() < Nh) wide_fac.resize(Nh, 0);
-            for (int l = 0; l < Nh; l++) wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], s->lvl_first[l + 1] - s->lvl_first[l]);
-            l_hess = std::max(l_hess, s->pp.lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
-            if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
+            G.np_fac = std::max(G.np_fac, s->T.Np); G.nh_fac = std::max(G.nh_fac, Nh);
+            G.l_hess = std::max(G.l_hess, s->pp.lds_hess); G.l_factor = std::max(G.l_factor, s->sens.lds_factor);
+            if (it.needs_export) G.cells = std::max(G.cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
         }
     }
     MPC_COUNT(waits, waits);
-    if ((rc = allow_lds(k_sens_hess_batch, l_hess)) || (rc = allow_lds(k_sens_factor_batch, l_factor)) || (rc = allow_lds(k_adj_rhs_batch, l_rhs)) ||
-        (rc = allow_lds(k_adj_backward_batch, l_sweep)) || (rc = allow_lds(k_adj_forward_batch, l_sweep)) || (rc = allow_lds(k_adj_grad_batch, l_grad)))
+    return TQGPU_OK;
+}
+/* the descriptors in one copy; the packing of the points that have not gone out, k_sens_hess_batch, k_sens_factor_batch per level, deepest first, each over
+ * the members that factorise: nothing where none does.  The caller looks at hipGetLastError behind its own launches */
+int deriv_group_launch_factor(const tqgpu_solver *lead, const DerivGroup &G) {
+    int rc;
+    if ((rc = allow_lds(k_sens_hess_batch, G.l_hess)) || (rc = allow_lds(k_sens_factor_batch, G.l_factor))) return rc;
+    hipStream_t ls = lead->stream;
+    const unsigned nz = (unsigned)G.n;
+    HIP_TRY(hipMemcpyAsync(G.d_items, G.items, G.bytes, hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
+    if (G.cells) { hipLaunchKernelGGL(k_adj_export_batch, dim3((unsigned)((G.cells + 255) / 256), nz), dim3(256), 0, ls, G.d_items); MPC_COUNT(launches, 1); }
+    if (G.np_fac) {
+        hipLaunchKernelGGL(k_sens_hess_batch, dim3((unsigned)G.np_fac, 1, nz), dim3(WAVE), G.l_hess, ls, G.d_items);
+        for (int j = 0; j < G.nh_fac; j++) hipLaunchKernelGGL(k_sens_factor_batch, dim3((unsigned)G.wide_fac[j], 1, nz), dim3(WAVE), G.l_factor, ls, G.d_items, j);
+        MPC_COUNT(launches, 1 + G.nh_fac);
+    }
+    return TQGPU_OK;
+}
+
+struct AdjSpan { size_t wx, wu, gx0; };          /* where a member's blocks begin in the caller's wx, wu and gx0 */
+
+/* The adjoint's group: w of all members in one copy through the lead's pinned block, the factor where a member has none stored, the four adjoint launches, the
+ * heads in one copy */
+int adj_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> &views, const Opts &O, const double *wx, const double *wu, int nw, const std::vector<AdjSpan> &span) {
+    tqgpu_solver *lead = v[g.idx[0]];
+    MpcAdjBatch &B = lead->adjb;
+    int rc;
+    HIP_TRY(hipSetDevice(lead->device));
+    size_t w_all = 0, heads_all = 0;
+    for (int i : g.idx) {
+        tqgpu_solver *s = v[i];
+        if ((rc = setup_sens(s)) || (rc = setup_adj(s, nw))) return rc;
+        w_all += adj_w_doubles(s, nw); heads_all += (size_t)s->sens.nx0 * nw + 1;
+    }
+    DerivGroup G;
+    if ((rc = deriv_group_fill(v, g, O, &tqgpu_solver::adjb, "the descriptors of a batched adjoint", [](tqgpu_solver *s) { s->sens.adj_valid = false; return !s->sens.factored; }, views, G)) ||
+        (rc = grow_items(lead, B.d_w, B.h_w, B.w_cap, w_all, "the loss gradients of a batched adjoint")) ||
+        (rc = grow_items(lead, B.d_heads, B.h_heads, B.heads_cap, heads_all, "the heads of a batched adjoint")))
+        return rc;
+    size_t l_rhs = 0, l_grad = 0, w_at = 0, h_at = 0;
+    for (size_t m = 0; m < G.n; m++) {
+        tqgpu_solver *s = v[g.idx[m]];
+        const MpcSens &ms = s->sens;
+        AItem &it = G.items[m];
+        it.A = ms.a;
+        it.A.wx = B.d_w + w_at; it.A.wu = it.A.wx + (size_t)it.nxe * (size_t)nw; it.A.head = B.d_heads + h_at;
+        const AdjSpan &at = span[(size_t)g.idx[m]];
+        adj_stage_w(s, B.h_w + w_at, wx ? wx + at.wx : nullptr, wu ? wu + at.wu : nullptr, nw);          /* w through the lead's pinned block */
+        w_at += adj_w_doubles(s, nw); h_at += (size_t)ms.nx0 * nw + 1;
+        l_rhs = std::max(l_rhs, ms.lds_rhs); l_grad = std::max(l_grad, ms.lds_grad);
+    }
+    if ((rc = allow_lds(k_adj_rhs_batch, l_rhs)) || (rc = allow_lds(k_adj_backward_batch, G.l_sweep)) || (rc = allow_lds(k_adj_forward_batch, G.l_sweep)) || (rc = allow_lds(k_adj_grad_batch, l_grad)))
         return rc;
     hipStream_t ls = lead->stream;
-    const unsigned nz = (unsigned)n, cols = (unsigned)nw;
-    const AItem *d_items = reinterpret_cast<const AItem *>(B.d_desc);
-    HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, items_bytes + lvl_ints * sizeof(int), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
+    const unsigned nz = (unsigned)G.n, cols = (unsigned)nw;
     if (w_all) HIP_TRY(hipMemcpyAsync(B.d_w, B.h_w, sizeof(double) * w_all, hipMemcpyHostToDevice, ls));
     MPC_COUNT(copies, 1);
-    if (cells) { hipLaunchKernelGGL(k_adj_export_batch, dim3((unsigned)((cells + 255) / 256), nz), dim3(256), 0, ls, d_items); MPC_COUNT(launches, 1); }
-    if (np_fac) {
-        hipLaunchKernelGGL(k_sens_hess_batch, dim3((unsigned)np_fac, 1, nz), dim3(WAVE), l_hess, ls, d_items);
-        for (int j = 0; j < nh_fac; j++) hipLaunchKernelGGL(k_sens_factor_batch, dim3((unsigned)wide_fac[j], 1, nz), dim3(WAVE), l_factor, ls, d_items, j);
-        MPC_COUNT(launches, 1 + nh_fac);
-    }
-    hipLaunchKernelGGL(k_adj_rhs_batch, dim3((unsigned)np_all, cols, nz), dim3(WAVE), l_rhs, ls, d_items);
-    for (int j = 0; j < nh_all; j++) hipLaunchKernelGGL(k_adj_backward_batch, dim3((unsigned)wide_bwd[j], cols, nz), dim3(WAVE), l_sweep, ls, d_items, j);
-    for (int j = 0; j + 1 < nh_all; j++) hipLaunchKernelGGL(k_adj_forward_batch, dim3((unsigned)wide_fwd[j], cols, nz), dim3(WAVE), l_sweep, ls, d_items, j);
-    hipLaunchKernelGGL(k_adj_grad_batch, dim3((unsigned)nn_all, cols, nz), dim3(WAVE), l_grad, ls, d_items);
+    if ((rc = deriv_group_launch_factor(lead, G))) return rc;
+    hipLaunchKernelGGL(k_adj_rhs_batch, dim3((unsigned)G.np_all, cols, nz), dim3(WAVE), l_rhs, ls, G.d_items);
+    for (int j = 0; j < G.nh_all; j++) hipLaunchKernelGGL(k_adj_backward_batch, dim3((unsigned)G.wide_bwd[j], cols, nz), dim3(WAVE), G.l_sweep, ls, G.d_items, j);
+    for (int j = 0; j + 1 < G.nh_all; j++) hipLaunchKernelGGL(k_adj_forward_batch, dim3((unsigned)G.wide_fwd[j], cols, nz), dim3(WAVE), G.l_sweep, ls, G.d_items, j);
+    hipLaunchKernelGGL(k_adj_grad_batch, dim3((unsigned)G.nn_all, cols, nz), dim3(WAVE), l_grad, ls, G.d_items);
     HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, 1 + nh_all + (nh_all - 1) + 1);
+    MPC_COUNT(launches, 1 + G.nh_all + (G.nh_all - 1) + 1);
     HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
     lead->links.stream_pending = true;
     return TQGPU_OK;
@@ -424,60 +462,37 @@ extern "C" int tqgpu_mpc_adjoint_batch(tqgpu_solver **solvers, int n, const tqgp
     if (!solvers || n < 1 || !o) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and opts are required, n must be at least 1)");
     if (nw < 1) return fail(TQGPU_EINVAL, std::string(who) + ": nw must be at least 1");
     int rc;
-    /* the refusals, all of them before any member is touched */
-    std::set<const tqgpu_solver *> seen;
-    for (int i = 0; i < n; i++) {
-        size_t lf, lp;
-        if ((rc = sens_refuse(solvers[i], o, who)) || (rc = adj_window_refuse(solvers[i], nw)) || (rc = sens_window_refuse(solvers[i], lf, lp)))
-            return fail(rc, "member " + std::to_string(i) + ": " + g_err);
-        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
-    }
+    if ((rc = refuse_members(who, solvers, n, [&](tqgpu_solver *s) {
+            size_t lf, lp;
+            int r;
+            if ((r = sens_refuse(s, o, who)) || (r = adj_window_refuse(s, nw))) return r;
+            return sens_window_refuse(s, lf, lp);
+        })))
+        return rc;
     Opts O;
     if ((rc = opts_from(o, O))) return rc;
-    const bool by_member = batch_by_member("TREEQP_AMD_ADJ_BATCH");          /* every member through tqgpu_mpc_adjoint's own route */
-    std::vector<AdjSpan> span((size_t)n);
-    {
-        AdjSpan at{0, 0, 0};
-        for (int i = 0; i < n; i++) {
-            const tqgpu_solver *s = solvers[i];
-            span[(size_t)i] = at;
-            at.wx += (size_t)(s->sum_nx - s->x_pad) * nw; at.wu += (size_t)s->sum_nu * nw; at.gx0 += (size_t)s->mpc.nx0 * nw;
-        }
-    }
-    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    const std::vector<AdjSpan> span = member_spans<AdjSpan>(n, [&](AdjSpan &at, int i) {
+        const tqgpu_solver *s = solvers[i];
+        at.wx += (size_t)(s->sum_nx - s->x_pad) * nw; at.wu += (size_t)s->sum_nu * nw; at.gx0 += (size_t)s->mpc.nx0 * nw;
+    });
+    const std::vector<DeviceGroup> groups = plan_device_groups(solvers, n, "TREEQP_AMD_ADJ_BATCH", ADJ_BATCH_MIN, ADJ_GRID_Z);
     std::vector<std::vector<Sens>> views(groups.size());          /* of a batched group's members, from the enqueue to the collect */
     MpcLive live;
-    /* everything goes out before the first wait of a batched group; a group that goes member by member waits member by member */
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        DeviceGroup &g = groups[gi];
-        g.batched = !by_member && group_fits_one_grid(solvers, g, ADJ_BATCH_MIN, ADJ_GRID_Z);
-        if (g.batched) {
-            if ((rc = adj_group_enqueue(solvers, g, views[gi], O, wx, wu, nw, span))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
-            continue;
-        }
-        for (int i : g.idx) {
-            tqgpu_solver *s = solvers[i];
-            SETTLE(s);
-            HIP_TRY(hipSetDevice(s->device));
+    return run_device_groups(solvers, groups, GroupRun{},
+        [&](const DeviceGroup &g, size_t gi) { return adj_group_enqueue(solvers, g, views[gi], O, wx, wu, nw, span); },
+        [&](int i) {          /* tqgpu_mpc_adjoint's own route */
             const AdjSpan &at = span[(size_t)i];
-            if ((rc = mpc_adjoint_one(s, O, wx ? wx + at.wx : nullptr, wu ? wu + at.wu : nullptr, nw, gx0 ? gx0 + at.gx0 : nullptr, n_reg ? n_reg + i : nullptr))) return rc;
-        }
-    }
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        const DeviceGroup &g = groups[gi];
-        if (!g.batched) continue;
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->links.stream_pending = false;
-        const double *h = lead->adjb.h_heads;
-        for (size_t m = 0; m < g.idx.size(); m++) {
-            const int i = g.idx[m];
-            adj_store(solvers[i], views[gi][m], h, nw, gx0 ? gx0 + span[(size_t)i].gx0 : nullptr, n_reg ? n_reg + i : nullptr);
-            h += (size_t)solvers[i]->sens.nx0 * nw + 1;
-        }
-    }
-    return TQGPU_OK;
+            return mpc_adjoint_one(solvers[i], O, wx ? wx + at.wx : nullptr, wu ? wu + at.wu : nullptr, nw, gx0 ? gx0 + at.gx0 : nullptr, n_reg ? n_reg + i : nullptr);
+        },
+        [&](const DeviceGroup &g, size_t gi) {
+            const double *h = solvers[g.idx[0]]->adjb.h_heads;
+            for (size_t m = 0; m < g.idx.size(); m++) {
+                const int i = g.idx[m];
+                adj_store(solvers[i], views[gi][m], h, nw, gx0 ? gx0 + span[(size_t)i].gx0 : nullptr, n_reg ? n_reg + i : nullptr);
+                h += (size_t)solvers[i]->sens.nx0 * nw + 1;
+            }
+            return TQGPU_OK;
+        });
 }
 
 /* ---- tqgpu_mpc_sensitivity_batch: per device one group; a group of SENS_BATCH_MIN members or more goes out as ONE set of launches on its first
@@ -487,82 +502,37 @@ namespace {
 constexpr int SENS_BATCH_MIN = 2;                /* members of one device from which the batched route is taken: at 2 C1 trees the sensitivity measured 157 us against 290 us member by member, at 4 160 us against 577 us; the predictor with duals 26 us against 42 us, and 28 us against 82 us (profiles/r23_mpc_gain_batch.txt) */
 constexpr size_t SENS_GRID_Z = 65535;            /* blockIdx.z is the member */
 
-/* A group on its lead's stream: the descriptors and level tables in one copy, the launches, the heads of all members in one copy back; nothing is
- * waited for here in the steady state (order_behind_lead, ADJ_ORDER).  views: per member the view its launches take, kept for the store behind the wait */
+/* The sensitivity's group: the factor of every member, like the single call always built anew, the forward sweep and the primal launch, the heads of all
+ * members in one copy back */
 int sens_group_enqueue(tqgpu_solver **v, const DeviceGroup &g, std::vector<Sens> &views, const Opts &O) {
     tqgpu_solver *lead = v[g.idx[0]];
-    const size_t n = g.idx.size();
+    MpcSensBatch &B = lead->sensb;
     int rc;
     HIP_TRY(hipSetDevice(lead->device));
-    size_t heads_all = 0, lvl_ints = 0;
+    size_t heads_all = 0;
     for (int i : g.idx) {
-        tqgpu_solver *s = v[i];
-        if ((rc = setup_sens(s))) return rc;
-        heads_all += sens_head_doubles(s); lvl_ints += 2 * (size_t)s->T.Nh;
+        if ((rc = setup_sens(v[i]))) return rc;
+        heads_all += sens_head_doubles(v[i]);
     }
-    MpcSensBatch &B = lead->sensb;
-    const size_t items_bytes = n * sizeof(AItem);
-    if ((rc = grow_items(lead, B.d_desc, B.h_desc, B.desc_cap, items_bytes + lvl_ints * sizeof(int), "the descriptors of a batched sensitivity")) ||
+    DerivGroup G;
+    if ((rc = deriv_group_fill(v, g, O, &tqgpu_solver::sensb, "the descriptors of a batched sensitivity", [](tqgpu_solver *s) { s->sens.valid = s->sens.factored = false; return true; }, views, G)) ||
         (rc = grow_items(lead, B.d_heads, B.h_heads, B.heads_cap, heads_all, "the heads of a batched sensitivity")))
         return rc;
-    AItem *items = reinterpret_cast<AItem *>(B.h_desc);
-    int *h_lvl = reinterpret_cast<int *>(B.h_desc + items_bytes);
-    const int *d_lvl = reinterpret_cast<const int *>(B.d_desc + items_bytes);
-    /* widths of the grids: per launch the largest member's extent */
-    int np_all = 0, nn_all = 0, cells = 0, nh_all = 0, nx0_all = 0;
-    size_t l_hess = 0, l_factor = 0, l_sweep = 0, l_primal = 0;
-    std::vector<int> wide_fac, wide_fwd;
-    std::vector<hipStream_t> waited;
-    int waits = 0;
-    size_t h_at = 0, l_at = 0;
-    views.assign(n, Sens{});
-    for (size_t m = 0; m < n; m++) {
-        tqgpu_solver *s = v[g.idx[m]];
-        if ((rc = order_behind_lead(s, lead, s->sensb.drained_at, ADJ_ORDER, waited, waits))) return rc;
-        MpcSens &ms = s->sens;
-        ms.valid = ms.factored = false;
-        const ExportSizes z = export_sizes(s);
-        AItem &it = items[m];
-        it = AItem{};
-        it.T = s->T; it.D = s->D; it.O = O;
-        it.needs_factor = 1;          /* like the single call: always built anew */
-        it.needs_export = s->out.valid ? 0 : 1;
-        it.S = views[m] = sens_view_of_point(s);
-        it.head_out = B.d_heads + h_at;
+    int nx0_all = 0;
+    size_t l_primal = 0, h_at = 0;
+    for (size_t m = 0; m < G.n; m++) {
+        const tqgpu_solver *s = v[g.idx[m]];
+        G.items[m].head_out = B.d_heads + h_at;
         h_at += sens_head_doubles(s);
-        const int Nh = s->T.Nh;
-        it.lvl = d_lvl + l_at;
-        for (int l = 0; l < Nh; l++) { h_lvl[l_at + 2 * l] = s->lvl_first[l]; h_lvl[l_at + 2 * l + 1] = s->lvl_first[l + 1] - s->lvl_first[l]; }
-        l_at += 2 * (size_t)Nh;
-        it.lamc = s->h_ctrl->cur ? s->D.lam1 : s->D.lam0;
-        it.d_out = s->out.d;
-        it.x_pad = s->x_pad; it.nxe = z.nxe; it.nue = z.nue; it.nl = z.nl; it.nx0 = s->nx0;
-        np_all = std::max(np_all, s->T.Np); nn_all = std::max(nn_all, s->T.Nn); nh_all = std::max(nh_all, Nh); nx0_all = std::max(nx0_all, ms.nx0);
-        if ((int)wide_fac.size() < Nh) { wide_fac.resize(Nh, 0); wide_fwd.resize(Nh, 0); }
-        for (int l = 0; l < Nh; l++) {
-            const int count = s->lvl_first[l + 1] - s->lvl_first[l];
-            wide_fac[Nh - 1 - l] = std::max(wide_fac[Nh - 1 - l], count);
-            if (l >= 1) wide_fwd[l - 1] = std::max(wide_fwd[l - 1], count);
-        }
-        l_hess = std::max(l_hess, s->pp.lds_hess); l_factor = std::max(l_factor, ms.lds_factor);
-        l_sweep = std::max(l_sweep, s->pp.lds_forward); l_primal = std::max(l_primal, ms.lds_primal);
-        if (it.needs_export) cells = std::max(cells, std::max(std::max(z.nxe, z.nue), std::max(z.nl, 1)));
+        nx0_all = std::max(nx0_all, s->sens.nx0); l_primal = std::max(l_primal, s->sens.lds_primal);
     }
-    MPC_COUNT(waits, waits);
-    if ((rc = allow_lds(k_sens_hess_batch, l_hess)) || (rc = allow_lds(k_sens_factor_batch, l_factor)) || (rc = allow_lds(k_sens_forward_batch, l_sweep)) ||
-        (rc = allow_lds(k_sens_primal_batch, l_primal)))
-        return rc;
+    if ((rc = allow_lds(k_sens_forward_batch, G.l_sweep)) || (rc = allow_lds(k_sens_primal_batch, l_primal)) || (rc = deriv_group_launch_factor(lead, G))) return rc;
     hipStream_t ls = lead->stream;
-    const unsigned nz = (unsigned)n;
-    const AItem *d_items = reinterpret_cast<const AItem *>(B.d_desc);
-    HIP_TRY(hipMemcpyAsync(B.d_desc, B.h_desc, items_bytes + lvl_ints * sizeof(int), hipMemcpyHostToDevice, ls)); MPC_COUNT(copies, 1);
-    if (cells) { hipLaunchKernelGGL(k_adj_export_batch, dim3((unsigned)((cells + 255) / 256), nz), dim3(256), 0, ls, d_items); MPC_COUNT(launches, 1); }
-    hipLaunchKernelGGL(k_sens_hess_batch, dim3((unsigned)np_all, 1, nz), dim3(WAVE), l_hess, ls, d_items);
-    for (int j = 0; j < nh_all; j++) hipLaunchKernelGGL(k_sens_factor_batch, dim3((unsigned)wide_fac[j], 1, nz), dim3(WAVE), l_factor, ls, d_items, j);
-    for (int j = 0; j + 1 < nh_all; j++) hipLaunchKernelGGL(k_sens_forward_batch, dim3((unsigned)wide_fwd[j], (unsigned)nx0_all, nz), dim3(WAVE), l_sweep, ls, d_items, j);
-    hipLaunchKernelGGL(k_sens_primal_batch, dim3((unsigned)nn_all, 1, nz), dim3(WAVE), l_primal, ls, d_items);
+    const unsigned nz = (unsigned)G.n;
+    for (int j = 0; j + 1 < G.nh_all; j++) hipLaunchKernelGGL(k_sens_forward_batch, dim3((unsigned)G.wide_fwd[j], (unsigned)nx0_all, nz), dim3(WAVE), G.l_sweep, ls, G.d_items, j);
+    hipLaunchKernelGGL(k_sens_primal_batch, dim3((unsigned)G.nn_all, 1, nz), dim3(WAVE), l_primal, ls, G.d_items);
     HIP_TRY(hipGetLastError());
-    MPC_COUNT(launches, (1 + nh_all) + (nh_all - 1) + 1);
+    MPC_COUNT(launches, (G.nh_all - 1) + 1);
     HIP_TRY(hipMemcpyAsync(B.h_heads, B.d_heads, sizeof(double) * heads_all, hipMemcpyDeviceToHost, ls)); MPC_COUNT(copies, 1);
     lead->links.stream_pending = true;
     return TQGPU_OK;
@@ -573,54 +543,29 @@ extern "C" int tqgpu_mpc_sensitivity_batch(tqgpu_solver **solvers, int n, const 
     const char *who = "tqgpu_mpc_sensitivity_batch";
     if (!solvers || n < 1 || !o) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and opts are required, n must be at least 1)");
     int rc;
-    /* the refusals, all of them before any member is touched */
-    std::set<const tqgpu_solver *> seen;
-    for (int i = 0; i < n; i++) {
-        size_t lf, lp;
-        if ((rc = sens_refuse(solvers[i], o, who)) || (rc = sens_window_refuse(solvers[i], lf, lp))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
-        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
-    }
+    if ((rc = refuse_members(who, solvers, n, [&](tqgpu_solver *s) { size_t lf, lp; const int r = sens_refuse(s, o, who); return r ? r : sens_window_refuse(s, lf, lp); }))) return rc;
     Opts O;
     if ((rc = opts_from(o, O))) return rc;
-    const bool by_member = batch_by_member("TREEQP_AMD_SENS_BATCH");          /* every member through tqgpu_mpc_sensitivity's own route */
-    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    const std::vector<DeviceGroup> groups = plan_device_groups(solvers, n, "TREEQP_AMD_SENS_BATCH", SENS_BATCH_MIN, SENS_GRID_Z);
     std::vector<std::vector<Sens>> views(groups.size());          /* of a batched group's members, from the enqueue to the store */
     MpcLive live;
-    /* everything goes out before the first wait of a batched group; a group that goes member by member waits member by member */
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        DeviceGroup &g = groups[gi];
-        g.batched = !by_member && group_fits_one_grid(solvers, g, SENS_BATCH_MIN, SENS_GRID_Z);
-        if (g.batched) {
-            if ((rc = sens_group_enqueue(solvers, g, views[gi], O))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
-            continue;
-        }
-        for (int i : g.idx) {
-            tqgpu_solver *s = solvers[i];
-            SETTLE(s);
-            HIP_TRY(hipSetDevice(s->device));
-            if ((rc = mpc_sensitivity_one(s, O, n_reg ? n_reg + i : nullptr))) return rc;
-        }
-    }
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        const DeviceGroup &g = groups[gi];
-        if (!g.batched) continue;
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->links.stream_pending = false;
-        /* every member's pinned head from the group's copy, then its flags: as its own call leaves it */
-        const double *h = lead->sensb.h_heads;
-        for (size_t m = 0; m < g.idx.size(); m++) {
-            tqgpu_solver *s = solvers[g.idx[m]];
-            const size_t head = sens_head_doubles(s);
-            memcpy(s->sens.h, h, sizeof(double) * head);
-            s->sens.v = views[gi][m];
-            s->sens.valid = s->sens.factored = true;
-            if (n_reg) n_reg[g.idx[m]] = (int)h[head - 1];
-            h += head;
-        }
-    }
-    return TQGPU_OK;
+    return run_device_groups(solvers, groups, GroupRun{},
+        [&](const DeviceGroup &g, size_t gi) { return sens_group_enqueue(solvers, g, views[gi], O); },
+        [&](int i) { return mpc_sensitivity_one(solvers[i], O, n_reg ? n_reg + i : nullptr); },          /* tqgpu_mpc_sensitivity's own route */
+        [&](const DeviceGroup &g, size_t gi) {
+            /* every member's pinned head from the group's copy, then its flags: as its own call leaves it */
+            const double *h = solvers[g.idx[0]]->sensb.h_heads;
+            for (size_t m = 0; m < g.idx.size(); m++) {
+                tqgpu_solver *s = solvers[g.idx[m]];
+                const size_t head = sens_head_doubles(s);
+                memcpy(s->sens.h, h, sizeof(double) * head);
+                s->sens.v = views[gi][m];
+                s->sens.valid = s->sens.factored = true;
+                if (n_reg) n_reg[g.idx[m]] = (int)h[head - 1];
+                h += head;
+            }
+            return TQGPU_OK;
+        });
 }
 
 /* ---- the adjoint in H, A, B (tdunes_sens.hpp: k_adjmat_part, k_adjmat_sum): outer products of the stored adjoint with the point, summed over the
@@ -980,54 +925,38 @@ extern "C" int tqgpu_mpc_adjoint_matrices_batch(tqgpu_solver **solvers, int n, i
     if (reduce != 0 && reduce != 1) return fail(TQGPU_EINVAL, std::string(who) + ": reduce must be 0 or 1");
     int rc;
     /* the refusals, all of them before any member's results are touched */
-    std::set<const tqgpu_solver *> seen;
-    for (int i = 0; i < n; i++) {
-        if ((rc = adjmat_refuse(solvers[i], who))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
-        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
-        const MpcAdjMat &a = solvers[0]->adjm, &b = solvers[i]->adjm;
-        if (reduce && (a.hdims != b.hdims || a.cdims != b.cdims || !std::equal(a.reg, a.reg + ADJMAT_REGIONS + 1, b.reg) || a.part1 != b.part1 || a.v.n_hchk != b.v.n_hchk || a.v.n_cchk != b.v.n_cchk ||
-                       a.v.root != b.v.root || solvers[0]->sens.nw != solvers[i]->sens.nw))
-            return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": its group tables (shapes, kinds, root terms) or its columns differ from member 0's; reduce = 1 sums equal shapes");
-    }
-    const bool by_member = batch_by_member("TREEQP_AMD_ADJ_BATCH");
+    if ((rc = refuse_members(who, solvers, n, [&](tqgpu_solver *s) { return adjmat_refuse(s, who); }, [&](int i) {
+            const MpcAdjMat &a = solvers[0]->adjm, &b = solvers[i]->adjm;
+            if (reduce && (a.hdims != b.hdims || a.cdims != b.cdims || !std::equal(a.reg, a.reg + ADJMAT_REGIONS + 1, b.reg) || a.part1 != b.part1 || a.v.n_hchk != b.v.n_hchk || a.v.n_cchk != b.v.n_cchk ||
+                           a.v.root != b.v.root || solvers[0]->sens.nw != solvers[i]->sens.nw))
+                return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": its group tables (shapes, kinds, root terms) or its columns differ from member 0's; reduce = 1 sums equal shapes");
+            return TQGPU_OK;
+        })))
+        return rc;
     double *const out[ADJMAT_REGIONS] = {gH, gh, gA, gB, gb, gA0, gS0};
-    std::vector<std::array<size_t, ADJMAT_REGIONS>> span((size_t)n);
-    {
-        std::array<size_t, ADJMAT_REGIONS> at{};
-        for (int i = 0; i < n; i++) {
-            span[(size_t)i] = at;
-            const MpcAdjMat &m = solvers[i]->adjm;
-            if (!reduce) for (int r = 0; r < ADJMAT_REGIONS; r++) at[(size_t)r] += (m.reg[r + 1] - m.reg[r]) * (size_t)solvers[i]->sens.nw;
-        }
-    }
-    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    typedef std::array<size_t, ADJMAT_REGIONS> Regions;          /* where a member's regions begin in the caller's seven arrays: under reduce = 1 all at the first member's */
+    const std::vector<Regions> span = member_spans<Regions>(n, [&](Regions &at, int i) {
+        const MpcAdjMat &m = solvers[i]->adjm;
+        if (!reduce) for (int r = 0; r < ADJMAT_REGIONS; r++) at[(size_t)r] += (m.reg[r + 1] - m.reg[r]) * (size_t)solvers[i]->sens.nw;
+    });
+    const std::vector<DeviceGroup> groups = plan_device_groups(solvers, n, "TREEQP_AMD_ADJ_BATCH", ADJ_BATCH_MIN, ADJ_GRID_Z);
     MpcLive live;
-    bool all_batched = !by_member;
-    for (DeviceGroup &g : groups) { g.batched = !by_member && group_fits_one_grid(solvers, g, ADJ_BATCH_MIN, ADJ_GRID_Z); all_batched = all_batched && g.batched; }
-    if (reduce && (!all_batched || groups.size() != 1)) {
+    if (reduce && (groups.size() != 1 || !groups[0].batched)) {
         /* the sum over members on the host, in member order: the first member's blocks, then entry by entry the others' */
         for (int i = 0; i < n; i++) if ((rc = adjmat_one(solvers[i], out, span[0].data(), i > 0))) return rc;
         return TQGPU_OK;
     }
     std::vector<std::vector<size_t>> sent(groups.size());          /* where a batched group's members begin in its lead's result block */
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        const DeviceGroup &g = groups[gi];
-        if (g.batched) { if ((rc = adjmat_group_enqueue(solvers, g, reduce, sent[gi]))) return rc; }
-        else for (int i : g.idx) if ((rc = adjmat_one(solvers[i], out, span[(size_t)i].data()))) return rc;
-    }
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        const DeviceGroup &g = groups[gi];
-        if (!g.batched) continue;
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->links.stream_pending = false;
-        for (size_t k = 0; k < (reduce ? 1 : g.idx.size()); k++) {
-            const tqgpu_solver *s = solvers[g.idx[k]];
-            adjmat_scatter(s->adjm, lead->adjm.h_bres + sent[gi][k], s->sens.nw, out, span[(size_t)g.idx[k]].data());
-        }
-    }
-    return TQGPU_OK;
+    return run_device_groups(solvers, groups, GroupRun{false},          /* an enqueue error is returned as it is */
+        [&](const DeviceGroup &g, size_t gi) { return adjmat_group_enqueue(solvers, g, reduce, sent[gi]); },
+        [&](int i) { return adjmat_one(solvers[i], out, span[(size_t)i].data()); },
+        [&](const DeviceGroup &g, size_t gi) {
+            for (size_t k = 0; k < (reduce ? 1 : g.idx.size()); k++) {
+                const tqgpu_solver *s = solvers[g.idx[k]];
+                adjmat_scatter(s->adjm, solvers[g.idx[0]]->adjm.h_bres + sent[gi][k], s->sens.nw, out, span[(size_t)g.idx[k]].data());
+            }
+            return TQGPU_OK;
+        });
 }
 
 extern "C" int tqgpu_mpc_get_gain(tqgpu_solver *s, double *K, double *u0, double *x0_ref) {
@@ -1149,50 +1078,28 @@ extern "C" int tqgpu_mpc_predict_batch(tqgpu_solver **solvers, int n, const doub
     const char *who = "tqgpu_mpc_predict_batch";
     if (!solvers || n < 1 || !x0_new) return fail(TQGPU_EINVAL, std::string(who) + ": bad arguments (solvers and x0_new are required, n must be at least 1)");
     int rc;
-    /* the refusals, all of them before any member is touched */
-    std::set<const tqgpu_solver *> seen;
-    for (int i = 0; i < n; i++) {
-        if ((rc = mpc_refuse(solvers[i], who)) || (rc = sens_need(solvers[i], who))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
-        if (!seen.insert(solvers[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
-    }
-    const bool by_member = batch_by_member("TREEQP_AMD_SENS_BATCH");          /* every member through tqgpu_mpc_predict's own route */
-    std::vector<PredSpan> span((size_t)n);
-    {
-        PredSpan at{0, 0};
-        for (int i = 0; i < n; i++) { span[(size_t)i] = at; at.x0 += (size_t)solvers[i]->sens.nx0; at.u0 += (size_t)solvers[i]->nu[0]; }
-    }
-    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
+    if ((rc = refuse_members(who, solvers, n, [&](tqgpu_solver *s) { const int r = mpc_refuse(s, who); return r ? r : sens_need(s, who); }))) return rc;
+    const std::vector<PredSpan> span = member_spans<PredSpan>(n, [&](PredSpan &at, int i) { at.x0 += (size_t)solvers[i]->sens.nx0; at.u0 += (size_t)solvers[i]->nu[0]; });
+    const std::vector<DeviceGroup> groups = plan_device_groups(solvers, n, "TREEQP_AMD_SENS_BATCH", SENS_BATCH_MIN, SENS_GRID_Z);
     MpcLive live;
-    for (DeviceGroup &g : groups) {
-        g.batched = !by_member && group_fits_one_grid(solvers, g, SENS_BATCH_MIN, SENS_GRID_Z);
-        if (g.batched) {
-            if ((rc = predict_group_enqueue(solvers, g, x0_new, duals, span))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
-            continue;
-        }
-        for (int i : g.idx) {
-            tqgpu_solver *s = solvers[i];
-            SETTLE(s);
-            HIP_TRY(hipSetDevice(s->device));
-            if ((rc = mpc_predict_one(s, x0_new + span[(size_t)i].x0, u0_pred ? u0_pred + span[(size_t)i].u0 : nullptr, duals, n_clipped ? n_clipped + i : nullptr))) return rc;
-        }
-    }
-    for (const DeviceGroup &g : groups) {
-        if (!g.batched) continue;
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        HIP_TRY(hipStreamSynchronize(lead->stream)); MPC_COUNT(waits, 1);
-        lead->links.stream_pending = false;
-        const double *io = lead->sensb.h_io;
-        for (int i : g.idx) {
-            const size_t nx0 = (size_t)solvers[i]->sens.nx0, nu0 = (size_t)solvers[i]->nu[0];
-            const double *out = io + nx0;
-            if (u0_pred && nu0) memcpy(u0_pred + span[(size_t)i].u0, out, sizeof(double) * nu0);
-            if (n_clipped) n_clipped[i] = (int)out[nu0];
-            io += nx0 + nu0 + 1;
-        }
-    }
-    return TQGPU_OK;
+    return run_device_groups(solvers, groups, GroupRun{},
+        [&](const DeviceGroup &g, size_t) { return predict_group_enqueue(solvers, g, x0_new, duals, span); },
+        [&](int i) {          /* tqgpu_mpc_predict's own route */
+            return mpc_predict_one(solvers[i], x0_new + span[(size_t)i].x0, u0_pred ? u0_pred + span[(size_t)i].u0 : nullptr, duals, n_clipped ? n_clipped + i : nullptr);
+        },
+        [&](const DeviceGroup &g, size_t) {
+            const double *io = solvers[g.idx[0]]->sensb.h_io;
+            for (int i : g.idx) {
+                const size_t nx0 = (size_t)solvers[i]->sens.nx0, nu0 = (size_t)solvers[i]->nu[0];
+                const double *out = io + nx0;
+                if (u0_pred && nu0) memcpy(u0_pred + span[(size_t)i].u0, out, sizeof(double) * nu0);
+                if (n_clipped) n_clipped[i] = (int)out[nu0];
+                io += nx0 + nu0 + 1;
+            }
+            return TQGPU_OK;
+        });
 }
+
 
 /* ---- the tangent of an MPC step (tdunes_sens.hpp: k_tan_rhs, k_tan_primal, k_tan_apply around the adjoint's two sweeps): dz, dlam along nd directions
  * (dq, dr, db, dx0) at the point of the last solve, and the predictor that builds its one direction on the device ---- */

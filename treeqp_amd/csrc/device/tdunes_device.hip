@@ -41,7 +41,8 @@
  *   tdunes_problem.hpp   what problem a mirror holds and which stage solver each node runs: the setters and getters of the problem's data
  *   tdunes_kkt.hpp       solution export and the KKT check, kernels and entry points
  *   tdunes_mpc.hpp       the MPC family (tqgpu_mpc_*), kernels and entry points; MpcStats, MpcPre stay here with the solve
- *   tdunes_adjoint.hpp   the host side of a step's sensitivities and adjoints; the plan the batched after-solve calls share (DeviceGroup ..) stays here
+ *   tdunes_adjoint.hpp   the host side of a step's sensitivities and adjoints, the builder of a batched derivative group (DerivGroup); the plan and the driver the batched
+ *                        after-solve calls share (refuse_members, plan_device_groups, order_behind_lead, run_device_groups) stay here
  *   tdunes_shard.hpp     the two multi-device modes (tqgpu_shard_*, tqgpu_pshard_*)
  */
 #include <hip/hip_runtime.h>
@@ -3463,19 +3464,33 @@ static int grow_items(tqgpu_solver *s, Item *&d, Item *&h, Cap &cap, size_t need
 }
 
 /* ---- the plan of the batched after-solve calls (tqgpu_kkt_residual_batch, tqgpu_mpc_adjoint_batch, tqgpu_mpc_adjoint_matrices_batch, tqgpu_mpc_sensitivity_batch, tqgpu_mpc_predict_batch): per device
- * one group; a group that fits one grid goes out as ONE set of launches on its first member's stream (the lead's), anything else member by member ---- */
+ * one group; a group that fits one grid goes out as ONE set of launches on its first member's stream (the lead's), anything else member by member.  A call is its refusals
+ * (refuse_members), its offsets into the caller's flat arrays (member_spans), the groups with their routes decided (plan_device_groups) and three callbacks for
+ * run_device_groups: a batched group out on its lead's stream, one member alone, a batched group's results out of the lead's pinned block behind the one wait ---- */
 struct DeviceGroup { int device; std::vector<int> idx; bool batched = false; };
-static std::vector<DeviceGroup> group_by_device(tqgpu_solver **v, int n) {
-    std::vector<DeviceGroup> groups;
+/* what every member is refused for, before any is touched: refuse(s)'s own message behind "member i: ", then a mirror named twice, then also(i) with a message
+ * of its own, member after member */
+template <typename Refuse, typename Also>
+static int refuse_members(const char *who, tqgpu_solver **v, int n, Refuse refuse, Also also) {
+    std::set<const tqgpu_solver *> seen;
     for (int i = 0; i < n; i++) {
-        auto g = std::find_if(groups.begin(), groups.end(), [&](const DeviceGroup &q) { return q.device == v[i]->device; });
-        if (g == groups.end()) { groups.push_back(DeviceGroup{v[i]->device, {}}); g = groups.end() - 1; }
-        g->idx.push_back(i);
+        int rc;
+        if ((rc = refuse(v[i]))) return fail(rc, "member " + std::to_string(i) + ": " + g_err);
+        if (!seen.insert(v[i]).second) return fail(TQGPU_EINVAL, std::string(who) + ": member " + std::to_string(i) + ": a mirror is named twice");
+        if ((rc = also(i))) return rc;
     }
-    return groups;
+    return TQGPU_OK;
 }
-/* TREEQP_AMD_KKT_BATCH, TREEQP_AMD_ADJ_BATCH, TREEQP_AMD_SENS_BATCH = members: every member on its own stream, as a group of one goes */
-static bool batch_by_member(const char *var) { const char *sw = getenv(var); return sw && strcmp(sw, "members") == 0; }
+template <typename Refuse>
+static int refuse_members(const char *who, tqgpu_solver **v, int n, Refuse refuse) { return refuse_members(who, v, n, refuse, [](int) { return TQGPU_OK; }); }
+/* where every member's blocks begin in the caller's flat arrays: advance(at, i) moves the offsets past member i */
+template <typename Span, typename Advance>
+static std::vector<Span> member_spans(int n, Advance advance) {
+    std::vector<Span> span((size_t)n);
+    Span at{};
+    for (int i = 0; i < n; i++) { span[(size_t)i] = at; advance(at, i); }
+    return span;
+}
 /* The batched kernels' grids are as wide as the largest member: a group in which one tree dwarfs the others would launch mostly
  * waves that return at once, and goes member by member instead.  mx, the largest member's nodes, n members, sum, the nodes of all of them. */
 static bool batch_grid_lopsided(size_t mx, size_t n, size_t sum) { return mx * n > 8 * sum + 4096; }
@@ -3489,6 +3504,20 @@ static bool group_fits_one_grid(tqgpu_solver **v, const DeviceGroup &g, int min_
         sum += (size_t)v[i]->Nn; mx = std::max(mx, (size_t)v[i]->Nn);
     }
     return !batch_grid_lopsided(mx, g.idx.size(), sum);
+}
+/* the members by device, in the caller's order, every group's route decided before anything goes out.  members_var (TREEQP_AMD_KKT_BATCH,
+ * TREEQP_AMD_ADJ_BATCH, TREEQP_AMD_SENS_BATCH) = members, read by every call: every member on its own stream, as a group of one goes */
+static std::vector<DeviceGroup> plan_device_groups(tqgpu_solver **v, int n, const char *members_var, int min_members, size_t grid_limit) {
+    std::vector<DeviceGroup> groups;
+    for (int i = 0; i < n; i++) {
+        auto g = std::find_if(groups.begin(), groups.end(), [&](const DeviceGroup &q) { return q.device == v[i]->device; });
+        if (g == groups.end()) { groups.push_back(DeviceGroup{v[i]->device, {}}); g = groups.end() - 1; }
+        g->idx.push_back(i);
+    }
+    const char *sw = getenv(members_var);
+    const bool by_member = sw && strcmp(sw, "members") == 0;
+    for (DeviceGroup &g : groups) g.batched = !by_member && group_fits_one_grid(v, g, min_members, grid_limit);
+    return groups;
 }
 /* THE stream rule of a batched group: member s is about to be read and written on its lead's stream, so whatever may still run for it elsewhere
  * comes first.  A member whose last solve was part of a launch on the lead's stream is ordered by it (settle_stream); one whose launch ran on a
@@ -3527,6 +3556,38 @@ static int order_behind_lead(tqgpu_solver *s, const tqgpu_solver *lead, long &dr
     return TQGPU_OK;
 }
 constexpr LeadOrder KKT_ORDER{false, false, false}, ADJ_ORDER{true, true, false}, ADJMAT_ORDER{false, false, true};
+/* THE two phases of a batched after-solve call.  Out: enqueue_group(g, gi) for a batched group (an error waits for the lead's stream first, where drain_on_error),
+ * run_member(i) for every member of any other group, to its end behind settle and hipSetDevice.  Back: per batched group the device, ONE wait for the lead's
+ * stream, counted into the live MPC record, stream_pending cleared, collect_group(g, gi).  So everything goes out before the first wait of a batched group; a
+ * group that goes member by member waits member by member.  The KKT check differs in two ways and says so: alone_collects_later, its run_member only enqueues
+ * (and settles, counting, itself) and collect_group is called for the groups that went member by member too, behind no wait of the driver's; waits, where it
+ * counts a batched group's wait instead, stream_pending left as it was */
+struct GroupRun { bool drain_on_error = true, alone_collects_later = false; int *waits = nullptr; };
+template <typename Enqueue, typename Member, typename Collect>
+static int run_device_groups(tqgpu_solver **v, const std::vector<DeviceGroup> &groups, GroupRun how, Enqueue enqueue_group, Member run_member, Collect collect_group) {
+    int rc;
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        const DeviceGroup &g = groups[gi];
+        if (g.batched) {
+            if ((rc = enqueue_group(g, gi))) { if (how.drain_on_error) (void)hipStreamSynchronize(v[g.idx[0]]->stream); return rc; }
+        } else for (int i : g.idx) {
+            if (!how.alone_collects_later) { SETTLE(v[i]); HIP_TRY(hipSetDevice(v[i]->device)); }
+            if ((rc = run_member(i))) return rc;
+        }
+    }
+    for (size_t gi = 0; gi < groups.size(); gi++) {
+        const DeviceGroup &g = groups[gi];
+        if (!g.batched && !how.alone_collects_later) continue;
+        tqgpu_solver *lead = v[g.idx[0]];
+        HIP_TRY(hipSetDevice(lead->device));
+        if (g.batched) {
+            HIP_TRY(hipStreamSynchronize(lead->stream));
+            if (how.waits) ++*how.waits; else { MPC_COUNT(waits, 1); lead->links.stream_pending = false; }
+        }
+        if ((rc = collect_group(g, gi))) return rc;
+    }
+    return TQGPU_OK;
+}
 static int launch_persist_batch(tqgpu_solver *lead, const BatchRow *row, const PItem *items, const Opts &O, int n_trees, unsigned seq) {
     const int G = lead->persist.geom.G;
     const ProcessSwitches &ps = process_switches();

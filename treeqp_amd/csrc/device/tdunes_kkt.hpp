@@ -480,27 +480,22 @@ extern "C" int tqgpu_kkt_residual_batch(tqgpu_solver **solvers, int n, double *r
     }
     KktBatchStats &st = g_kkt_stats;
     st = KktBatchStats();
-    const bool by_member = batch_by_member("TREEQP_AMD_KKT_BATCH");
-    std::vector<DeviceGroup> groups = group_by_device(solvers, n);
-    for (DeviceGroup &g : groups) {
-        g.batched = !by_member && group_fits_one_grid(solvers, g, KKT_BATCH_MIN, KKT_GRID_Y);
-        if (g.batched) {
-            if ((rc = kkt_group_enqueue(solvers, g, st))) { (void)hipStreamSynchronize(solvers[g.idx[0]]->stream); return rc; }
-        } else for (int i : g.idx) if ((rc = kkt_member_enqueue(solvers[i], st))) return rc;
-    }
-    for (const DeviceGroup &g : groups) {
-        tqgpu_solver *lead = solvers[g.idx[0]];
-        HIP_TRY(hipSetDevice(lead->device));
-        if (g.batched) { HIP_TRY(hipStreamSynchronize(lead->stream)); st.waits++; }
-        for (size_t m = 0; m < g.idx.size(); m++) {
-            const int i = g.idx[m];
-            if (!g.batched) { HIP_TRY(hipStreamSynchronize(solvers[i]->stream)); st.waits++; kkt_collect(solvers[i], res + (size_t)KKT_CLASSES * i, node ? node + (size_t)KKT_CLASSES * i : nullptr, nullptr); continue; }
-            const double *h = lead->kkt.h_heads[m].v;
-            memcpy(res + (size_t)KKT_CLASSES * i, h, sizeof(double) * KKT_CLASSES);
-            if (node) memcpy(node + (size_t)KKT_CLASSES * i, h + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
-        }
-    }
-    return TQGPU_OK;
+    /* a mirror named twice is not refused: its group goes member by member (group_fits_one_grid).  The waits are this call's own to count, and a member
+     * that goes alone is only enqueued in the first phase and waited for with the others in the second */
+    const std::vector<DeviceGroup> groups = plan_device_groups(solvers, n, "TREEQP_AMD_KKT_BATCH", KKT_BATCH_MIN, KKT_GRID_Y);
+    return run_device_groups(solvers, groups, GroupRun{true, true, &st.waits},
+        [&](const DeviceGroup &g, size_t) { return kkt_group_enqueue(solvers, g, st); },
+        [&](int i) { return kkt_member_enqueue(solvers[i], st); },
+        [&](const DeviceGroup &g, size_t) {
+            for (size_t m = 0; m < g.idx.size(); m++) {
+                const int i = g.idx[m];
+                if (!g.batched) { HIP_TRY(hipStreamSynchronize(solvers[i]->stream)); st.waits++; kkt_collect(solvers[i], res + (size_t)KKT_CLASSES * i, node ? node + (size_t)KKT_CLASSES * i : nullptr, nullptr); continue; }
+                const double *h = solvers[g.idx[0]]->kkt.h_heads[m].v;
+                memcpy(res + (size_t)KKT_CLASSES * i, h, sizeof(double) * KKT_CLASSES);
+                if (node) memcpy(node + (size_t)KKT_CLASSES * i, h + KKT_CLASSES, sizeof(int) * KKT_CLASSES);
+            }
+            return TQGPU_OK;
+        });
 }
 
 extern "C" int tqgpu_kkt_batch_stats(int *launches, int *copies, int *waits, int *batched_members) {
